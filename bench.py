@@ -9,7 +9,10 @@ are independent), profiles are replicated, and the step ends with the RCCL all-g
 [1000, 192] embeddings that the global clustering stage consumes (torch.distributed, backend
 "nccl" = RCCL).  Inputs are generated on the device before the timed region.
 
-Prints ONE JSON line on rank 0 (see README / DESIGN.md §6 for the field definitions).
+Prints ONE JSON line on rank 0 (see README / DESIGN.md §6 for the field definitions).  A plain run sets up, warms up, times
+--steps steps and prints the headline (`value`, `ms_per_step` = wall ms of one timed step); --full adds every other leg (roofline
+pass, config #3 / #4 / #5, CPU baseline and parity, precision modes, x-vector, ingest, sustained, cold start), all outside the
+timed region.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (same arguments, same inputs).
 """
 from __future__ import annotations
 
@@ -444,6 +447,30 @@ def cold_start_object(timeout_s=120):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: `arrays` (name -> device tensor, what a caller of the timed path receives) as out_dir/<name>.npy, integers as float64,
+    floats as float32.  Past DUMP_MAX_BYTES in all, every array keeps the same fraction of its rows as a fixed, seeded sample (sorted, the
+    row numbers in <name>_rows.npy): two builds run with the same arguments write the same rows, and arrays of equal length keep the same
+    rows, so they still line up row for row."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    host = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    host = {k: v.astype(np.float32 if np.issubdtype(v.dtype, np.floating) else np.float64) for k, v in host.items()}
+    frac = 1.0
+    if sum(v.nbytes for v in host.values()) > DUMP_MAX_BYTES:
+        frac = DUMP_MAX_BYTES * 0.99 / sum(v.nbytes + 8 * len(v) for v in host.values())     # + 8: the row number kept with each row
+    for name, a in host.items():
+        keep = max(1, int(frac * len(a)))
+        if keep < len(a):
+            rows = np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))
+            a = a[rows]
+            np.save(d / f"{name}_rows.npy", rows.astype(np.float64))
+        np.save(d / f"{name}.npy", a)
+
+
 def spawn_ranks(n: int) -> int:
     """`python bench.py --gpus N` without a rank environment: start the N ranks as CHILD processes (torch.distributed.run, one per GPU,
     rendezvous on 127.0.0.1) BEFORE this process makes any GPU call, let rank 0's JSON line through on stdout and return the children's exit
@@ -468,10 +495,17 @@ def main() -> int:
     ap.add_argument("--prewarm", type=int, default=30, help="minimum number of untimed steps BEFORE the W warm-up steps (they also run until the process is 4 s old: start-up stall, see the comment in main); 0 = none")
     ap.add_argument("--segments", type=int, default=1000, help="segments per GPU (config #2: 1000)")
     ap.add_argument("--profiles", type=int, default=100)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-affinity-config3", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the precise-mode, sustained and cold-start legs (they run outside the timed region)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity object measured against it")
+    ap.add_argument("--no-affinity-config3", action="store_true", help="with --full: skip the config #3 / #4-shape affinity and config #5 mat-vec legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the precise-mode, sustained and cold-start legs (they run outside the timed region)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run every leg outside the timed region (roofline pass, config #3 / #4 / #5, "
+                                                        "CPU baseline and parity, precision modes, x-vector, ingest, sustained, cold start; at N > 1 the exchange "
+                                                        "and config #4 / #5 legs); off: set-up, warm-up, the timed steps and the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed on rank 0 as DIR/<name>.npy: embeddings, ids, scores (row for row), at N > 1 also "
+                                                                        f"embeddings_gathered (every rank's, in rank order); float32 / float64, at most {DUMP_MAX_BYTES >> 20} MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus)          # plain `python bench.py --gpus N`: this process becomes the launcher (it has made no GPU call)
@@ -527,7 +561,7 @@ def main() -> int:
         idx, sc = eng.affinity_topk(E, Eb, re, Pn, Pb, rpm, k=1)
         if use_dist and exchange:
             sdist._gather_into(gathered, E)                   # k5: the embedding exchange (RCCL over xGMI): ONE all_gather_into_tensor
-        return idx, sc
+        return E, idx, sc
 
     # A fresh process stalls ONCE, for 60-85 ms, about 1.4 s after it created its GPU context - whatever it is doing then (tools/step_jitter.py,
     # profiles/r03_step_jitter.json: the 2nd or 3rd synchronised step of a process takes 69-87 ms instead of 8.7; a process that sleeps through that
@@ -556,18 +590,23 @@ def main() -> int:
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     fence()
     elapsed = time.perf_counter() - t0
     if use_dist:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step receives from its last timed pass on rank 0: its embeddings, argmax profile IDs and cosine scores (row n of
+        # each = segment n), and at N > 1 the exchanged embeddings of every rank (rank r's segments at rows r * B ... r * B + B - 1)
+        E, idx, sc = last
+        dump_outputs(args.dump_outputs, {"embeddings": E, "ids": idx, "scores": sc, **({"embeddings_gathered": gathered} if use_dist else {})})
 
-    # ---- N > 1: what configs #4 and #5 define, every rank taking part (skipped at N = 1: those configs ARE 8-GPU shapes; their
+    # ---- N > 1, with --full: what configs #4 and #5 define, every rank taking part (skipped at N = 1: those configs ARE 8-GPU shapes; their
     # one-GPU kernels are timed in the `affinity` / `affinity_cluster` objects).  Wall time between fences, max over ranks.
     exchange, cfg4, cfg5 = None, None, None
-    if world > 1:
+    if world > 1 and args.full:
         def timed(fn, reps):
             for _ in range(2):
                 fn()
@@ -657,119 +696,122 @@ def main() -> int:
         ms_step = elapsed / args.steps * 1e3
         value = world * B * args.steps / elapsed
 
-        # ---- roofline pass: per-launch HIP events on the launch stream, one extra step
-        eng.profile_begin()
-        step(exchange=False)                   # rank 0 only: a collective here would never be matched by the other ranks
-        prof = eng.profile_end()
-        # dominant kernel: conv_gemm256_kernel (blk0, the six 1024x1024 TDNN layers, the 3072x3072 MFA layer)
-        big = prof["conv_gemm256"]
-        MAC_BIG = 80 * 5 * 1024 + 6 * 1024 * 1024 + 3072 * 3072        # SURVEY Appendix B rows served by this kernel
-        big_alg_flops = 2.0 * MAC_BIG * T_FRAMES * B
-        achieved = big_alg_flops / (big["ms"] * 1e-3)
-        kernels = {k: {"launches": v["launches"], "ms": round(v["ms"], 4),
-                       "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2) if v["flops"] else None,
-                       "gbps": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["bytes"] else None}
-                   for k, v in prof.items()}
-        step_dev_ms = sum(v["ms"] for v in prof.values())
-        traffic, traffic_src = None, None
-        pmc_files = sorted((ROOT / "profiles").glob("*pmc_bench.json"))
-        if pmc_files and B == 1000:   # HBM-side bytes per launch from a separate rocprofv3 --pmc pass over `bench.py --steps 1` at the
-            try:                       # default 1000 segments (tools/pmc_bench.sh), gfx950-corrected; not this run's counters
-                pm = json.loads(pmc_files[-1].read_text())["conv_gemm256_kernel"]
-                traffic = round((2.0 * pm["FETCH_SIZE_KB"] + pm["WRITE_SIZE_KB"]) * 1024.0 / pm["launches"], 1)
-                traffic_src = f"profiles/{pmc_files[-1].name} (committed PMC pass; refresh with tools/pmc_bench.sh whenever conv_gemm.hip changes)"
-            except Exception:  # noqa: BLE001
-                traffic = None
-        clock_mhz = measure_gemm_clock(eng, step)
-        roofline = {"kernel": "conv_gemm256_kernel", "bound": "mfma", "achieved": round(achieved / 1e12, 2), "peak": PEAK_BF16_MFMA / 1e12,
-                    "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_MFMA, 4), "traffic": traffic,
-                    "traffic_note": "bytes leaving L2 per launch (FETCH_SIZE x2 + WRITE_SIZE, Infinity-Cache hits included), separate --pmc pass" if traffic else None,
-                    "traffic_source": traffic_src, "algorithmic_bytes_per_launch": round(big["bytes"] / big["launches"], 1),
-                    "launches_per_step": big["launches"], "avg_launch_ms": round(big["ms"] / big["launches"], 4),
-                    "algorithmic_flops_per_step": big_alg_flops, "share_of_step_device_time": round(big["ms"] / step_dev_ms, 3),
-                    "executed_tflops": round(big["flops"] / (big["ms"] * 1e-3) / 1e12, 2)}
-        fwd_keys = ("conv_gemm256", "conv_gemm", "se_gate", "asp_stats", "rows_fc", "asp_pool", "asp_fused", "copy")
-        fwd_ms = sum(prof[k]["ms"] for k in fwd_keys if k in prof)
-        fwd_mfma = {"bound": "mfma", "achieved": round(FLOP_PER_SEGMENT * B / (fwd_ms * 1e-3) / 1e12, 2), "peak": PEAK_BF16_MFMA / 1e12,
-                    "unit": "TFLOP/s", "frac": round(FLOP_PER_SEGMENT * B / (fwd_ms * 1e-3) / PEAK_BF16_MFMA, 4),
-                    "model": "SURVEY.md 8(d) 7.539 GFLOP/segment / whole ECAPA forward device time (all kernels)"}
-        # north_star's second view of the forward: layer-boundary HBM model (19.07 MB / segment, bf16)
-        fwd_hbm = {"bound": "hbm", "achieved": round(BYTES_PER_SEGMENT_BF16 * B / (fwd_ms * 1e-3) / 1e9, 1), "peak": PEAK_HBM / 1e9,
-                   "unit": "GB/s", "frac": round(BYTES_PER_SEGMENT_BF16 * B / (fwd_ms * 1e-3) / PEAK_HBM, 4),
-                   "model": "SURVEY.md 8(d) layer-boundary bytes (19.07 MB/segment) / forward device time"}
-
-        # ---- affinity pairs/sec at config #3 (100k segments x 1k profiles) and at config #4's per-GPU shape (125k x 10k), HIP events
-        aff = None
-        if not args.no_affinity_config3:
-            def aff_traffic(tag):
-                """bytes leaving L2 per launch of aff_rowcol_kernel from the committed rocprofv3 --pmc pass at this shape (tools/pmc_any.sh tools/one_aff.py)"""
-                files = sorted((ROOT / "profiles").glob(f"*pmc_aff_{tag}.json"))
-                try:
-                    pmj = json.loads(files[-1].read_text())
-                    pm = pmj.get("aff_rowcol_blocks_kernel") or pmj["aff_rowcol_kernel"]      # the coarse pass's plan at this shape (block plan at config #3 since round 5)
-                    return round((2.0 * pm["FETCH_SIZE"] + pm["WRITE_SIZE"]) * 1024.0, 1), f"profiles/{files[-1].name}"
-                except Exception:  # noqa: BLE001
-                    return None, None
-
-            def affinity_leg(N3, P3, label, tag=None):
-                E3, E3b, r3 = eng.l2norm(torch.randn(N3, 192, device=dev, generator=torch.Generator(device=dev).manual_seed(3)))
-                Q3, Q3b, q3 = eng.l2norm(torch.randn(P3, 192, device=dev, generator=torch.Generator(device=dev).manual_seed(4)))
-                q3m = q3.max().reshape(1)
-                tw = time.perf_counter()
-                while (time.perf_counter() - tw) * 1e3 < WARM_MS / 2:      # short launches after host-side tensor set-up: warm by time, not by count
-                    for _ in range(8):
-                        eng.affinity_topk(E3, E3b, r3, Q3, Q3b, q3m, k=1)
-                    torch.cuda.synchronize()
-                reps = 10
-                eng.profile_begin()
-                for _ in range(reps):
-                    _, _, cnt = eng.affinity_topk(E3, E3b, r3, Q3, Q3b, q3m, k=1, want_count=True)
-                p3 = eng.profile_end()
-                coarse_ms = p3["affinity_coarse"]["ms"] / reps
-                total_ms = sum(v["ms"] for v in p3.values()) / reps
-                fl = 2.0 * N3 * P3 * 192
-                return {"workload": label, "pairs_per_sec": round(N3 * P3 / (total_ms * 1e-3), 1), "ms_total": round(total_ms, 4),
-                        "ms_coarse_mfma": round(coarse_ms, 4), "ms_exact_tail": round(total_ms - coarse_ms, 4),
-                        "total_over_coarse": round(total_ms / coarse_ms, 3), "rows_rescanned": int(cnt.item()),
-                        "roofline": {"kernel": "aff_rowcol_blocks_kernel / aff_rowcol_kernel (coarse pass; the plan is chosen per shape)", "bound": "mfma", "achieved": round(fl / (coarse_ms * 1e-3) / 1e12, 2),
-                                     "peak": PEAK_BF16_MFMA / 1e12, "unit": "TFLOP/s", "frac": round(fl / (coarse_ms * 1e-3) / PEAK_BF16_MFMA, 4),
-                                     "traffic": aff_traffic(tag)[0] if tag else None, "traffic_source": aff_traffic(tag)[1] if tag else None,
-                                     "algorithmic_bytes_per_launch": 2.0 * (N3 + P3) * 192 + 64.0 * N3,
-                                     "traffic_note": "bytes leaving L2 per launch (FETCH_SIZE x2 + WRITE_SIZE), separate --pmc pass"}}
-            aff = affinity_leg(100_000, 1000, "config #3: 100k segments x 1k profiles, row/column-maxima coarse pass + exact fp32 re-score (argmax)", "cfg3")
-            aff["config4_shard_shape"] = affinity_leg(125_000, 10_000, "config #4, one GPU's shard: 125k segments x 10k replicated profiles", "cfg4shape")
-
-        # ---- config #5 kernel: rectified-affinity mat-vec A X (A = max(E E^T, 0) recomputed on MFMA), 100k x 100k
-        clus = None
-        if not args.no_affinity_config3:
-            N5, k5 = 100_000, 16
-            E5, E5b, _ = eng.l2norm(torch.randn(N5, 192, device=dev, generator=torch.Generator(device=dev).manual_seed(5)))
-            X5 = torch.randn(N5, k5, device=dev, generator=torch.Generator(device=dev).manual_seed(6))
-            tw = time.perf_counter()
-            while (time.perf_counter() - tw) * 1e3 < WARM_MS / 2:
-                eng.affinity_matvec(E5b, X5)
-                torch.cuda.synchronize()
+        # ---- everything below runs outside the timed region and only with --full: a plain run reports the headline alone
+        roofline = fwd_mfma = fwd_hbm = kernels = step_dev_ms = clock_mhz = aff = clus = None
+        if args.full:
+            # ---- roofline pass: per-launch HIP events on the launch stream, one extra step
             eng.profile_begin()
-            for _ in range(3):
-                eng.affinity_matvec(E5b, X5)
-            p5 = eng.profile_end()["affinity_matvec"]
-            ms5 = p5["ms"] / 3
-            mv_traffic, mv_src = None, None
-            mv_files = sorted((ROOT / "profiles").glob("*pmc_matvec.json"))
-            if mv_files:      # committed rocprofv3 --pmc pass of this kernel at this shape (tools/pmc_any.sh tools/one_matvec.py): bytes leaving L2 per launch
-                try:
-                    pm = json.loads(mv_files[-1].read_text())["affinity_matvec2_kernel"]
-                    mv_traffic = round((2.0 * pm["FETCH_SIZE"] + pm["WRITE_SIZE"]) * 1024.0, 1)
-                    mv_src = f"profiles/{mv_files[-1].name}"
+            step(exchange=False)                   # rank 0 only: a collective here would never be matched by the other ranks
+            prof = eng.profile_end()
+            # dominant kernel: conv_gemm256_kernel (blk0, the six 1024x1024 TDNN layers, the 3072x3072 MFA layer)
+            big = prof["conv_gemm256"]
+            MAC_BIG = 80 * 5 * 1024 + 6 * 1024 * 1024 + 3072 * 3072        # SURVEY Appendix B rows served by this kernel
+            big_alg_flops = 2.0 * MAC_BIG * T_FRAMES * B
+            achieved = big_alg_flops / (big["ms"] * 1e-3)
+            kernels = {k: {"launches": v["launches"], "ms": round(v["ms"], 4),
+                           "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2) if v["flops"] else None,
+                           "gbps": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["bytes"] else None}
+                       for k, v in prof.items()}
+            step_dev_ms = sum(v["ms"] for v in prof.values())
+            traffic, traffic_src = None, None
+            pmc_files = sorted((ROOT / "profiles").glob("*pmc_bench.json"))
+            if pmc_files and B == 1000:   # HBM-side bytes per launch from a separate rocprofv3 --pmc pass over `bench.py --steps 1` at the
+                try:                       # default 1000 segments (tools/pmc_bench.sh), gfx950-corrected; not this run's counters
+                    pm = json.loads(pmc_files[-1].read_text())["conv_gemm256_kernel"]
+                    traffic = round((2.0 * pm["FETCH_SIZE_KB"] + pm["WRITE_SIZE_KB"]) * 1024.0 / pm["launches"], 1)
+                    traffic_src = f"profiles/{pmc_files[-1].name} (committed PMC pass; refresh with tools/pmc_bench.sh whenever conv_gemm.hip changes)"
                 except Exception:  # noqa: BLE001
-                    pass
-            clus = {"workload": "config #5 tile kernel: 100k x 100k segment-segment affinity recomputed + A.X (k=16), one GPU",
-                    "pairs_per_sec": round(N5 * N5 / (ms5 * 1e-3), 1), "ms": round(ms5, 3),
-                    "roofline": {"kernel": "affinity_matvec2_kernel", "bound": "mfma", "achieved": round(2.0 * N5 * N5 * (192 + k5) / (ms5 * 1e-3) / 1e12, 2),
-                                 "peak": PEAK_BF16_MFMA / 1e12, "unit": "TFLOP/s", "frac": round(2.0 * N5 * N5 * (192 + k5) / (ms5 * 1e-3) / PEAK_BF16_MFMA, 4),
-                                 "traffic": mv_traffic, "traffic_source": mv_src,
-                                 "algorithmic_bytes_per_launch": 2.0 * N5 * 192 + 4.0 * N5 * k5 * 2,
-                                 "note": "executed flops are 1.23x the algorithmic 2 N^2 (192 + k): X is split hi+lo and padded to 32 columns"}}
+                    traffic = None
+            clock_mhz = measure_gemm_clock(eng, step)
+            roofline = {"kernel": "conv_gemm256_kernel", "bound": "mfma", "achieved": round(achieved / 1e12, 2), "peak": PEAK_BF16_MFMA / 1e12,
+                        "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_MFMA, 4), "traffic": traffic,
+                        "traffic_note": "bytes leaving L2 per launch (FETCH_SIZE x2 + WRITE_SIZE, Infinity-Cache hits included), separate --pmc pass" if traffic else None,
+                        "traffic_source": traffic_src, "algorithmic_bytes_per_launch": round(big["bytes"] / big["launches"], 1),
+                        "launches_per_step": big["launches"], "avg_launch_ms": round(big["ms"] / big["launches"], 4),
+                        "algorithmic_flops_per_step": big_alg_flops, "share_of_step_device_time": round(big["ms"] / step_dev_ms, 3),
+                        "executed_tflops": round(big["flops"] / (big["ms"] * 1e-3) / 1e12, 2)}
+            fwd_keys = ("conv_gemm256", "conv_gemm", "se_gate", "asp_stats", "rows_fc", "asp_pool", "asp_fused", "copy")
+            fwd_ms = sum(prof[k]["ms"] for k in fwd_keys if k in prof)
+            fwd_mfma = {"bound": "mfma", "achieved": round(FLOP_PER_SEGMENT * B / (fwd_ms * 1e-3) / 1e12, 2), "peak": PEAK_BF16_MFMA / 1e12,
+                        "unit": "TFLOP/s", "frac": round(FLOP_PER_SEGMENT * B / (fwd_ms * 1e-3) / PEAK_BF16_MFMA, 4),
+                        "model": "SURVEY.md 8(d) 7.539 GFLOP/segment / whole ECAPA forward device time (all kernels)"}
+            # north_star's second view of the forward: layer-boundary HBM model (19.07 MB / segment, bf16)
+            fwd_hbm = {"bound": "hbm", "achieved": round(BYTES_PER_SEGMENT_BF16 * B / (fwd_ms * 1e-3) / 1e9, 1), "peak": PEAK_HBM / 1e9,
+                       "unit": "GB/s", "frac": round(BYTES_PER_SEGMENT_BF16 * B / (fwd_ms * 1e-3) / PEAK_HBM, 4),
+                       "model": "SURVEY.md 8(d) layer-boundary bytes (19.07 MB/segment) / forward device time"}
+
+            # ---- affinity pairs/sec at config #3 (100k segments x 1k profiles) and at config #4's per-GPU shape (125k x 10k), HIP events
+            aff = None
+            if not args.no_affinity_config3:
+                def aff_traffic(tag):
+                    """bytes leaving L2 per launch of aff_rowcol_kernel from the committed rocprofv3 --pmc pass at this shape (tools/pmc_any.sh tools/one_aff.py)"""
+                    files = sorted((ROOT / "profiles").glob(f"*pmc_aff_{tag}.json"))
+                    try:
+                        pmj = json.loads(files[-1].read_text())
+                        pm = pmj.get("aff_rowcol_blocks_kernel") or pmj["aff_rowcol_kernel"]      # the coarse pass's plan at this shape (block plan at config #3 since round 5)
+                        return round((2.0 * pm["FETCH_SIZE"] + pm["WRITE_SIZE"]) * 1024.0, 1), f"profiles/{files[-1].name}"
+                    except Exception:  # noqa: BLE001
+                        return None, None
+
+                def affinity_leg(N3, P3, label, tag=None):
+                    E3, E3b, r3 = eng.l2norm(torch.randn(N3, 192, device=dev, generator=torch.Generator(device=dev).manual_seed(3)))
+                    Q3, Q3b, q3 = eng.l2norm(torch.randn(P3, 192, device=dev, generator=torch.Generator(device=dev).manual_seed(4)))
+                    q3m = q3.max().reshape(1)
+                    tw = time.perf_counter()
+                    while (time.perf_counter() - tw) * 1e3 < WARM_MS / 2:      # short launches after host-side tensor set-up: warm by time, not by count
+                        for _ in range(8):
+                            eng.affinity_topk(E3, E3b, r3, Q3, Q3b, q3m, k=1)
+                        torch.cuda.synchronize()
+                    reps = 10
+                    eng.profile_begin()
+                    for _ in range(reps):
+                        _, _, cnt = eng.affinity_topk(E3, E3b, r3, Q3, Q3b, q3m, k=1, want_count=True)
+                    p3 = eng.profile_end()
+                    coarse_ms = p3["affinity_coarse"]["ms"] / reps
+                    total_ms = sum(v["ms"] for v in p3.values()) / reps
+                    fl = 2.0 * N3 * P3 * 192
+                    return {"workload": label, "pairs_per_sec": round(N3 * P3 / (total_ms * 1e-3), 1), "ms_total": round(total_ms, 4),
+                            "ms_coarse_mfma": round(coarse_ms, 4), "ms_exact_tail": round(total_ms - coarse_ms, 4),
+                            "total_over_coarse": round(total_ms / coarse_ms, 3), "rows_rescanned": int(cnt.item()),
+                            "roofline": {"kernel": "aff_rowcol_blocks_kernel / aff_rowcol_kernel (coarse pass; the plan is chosen per shape)", "bound": "mfma", "achieved": round(fl / (coarse_ms * 1e-3) / 1e12, 2),
+                                         "peak": PEAK_BF16_MFMA / 1e12, "unit": "TFLOP/s", "frac": round(fl / (coarse_ms * 1e-3) / PEAK_BF16_MFMA, 4),
+                                         "traffic": aff_traffic(tag)[0] if tag else None, "traffic_source": aff_traffic(tag)[1] if tag else None,
+                                         "algorithmic_bytes_per_launch": 2.0 * (N3 + P3) * 192 + 64.0 * N3,
+                                         "traffic_note": "bytes leaving L2 per launch (FETCH_SIZE x2 + WRITE_SIZE), separate --pmc pass"}}
+                aff = affinity_leg(100_000, 1000, "config #3: 100k segments x 1k profiles, row/column-maxima coarse pass + exact fp32 re-score (argmax)", "cfg3")
+                aff["config4_shard_shape"] = affinity_leg(125_000, 10_000, "config #4, one GPU's shard: 125k segments x 10k replicated profiles", "cfg4shape")
+
+            # ---- config #5 kernel: rectified-affinity mat-vec A X (A = max(E E^T, 0) recomputed on MFMA), 100k x 100k
+            clus = None
+            if not args.no_affinity_config3:
+                N5, k5 = 100_000, 16
+                E5, E5b, _ = eng.l2norm(torch.randn(N5, 192, device=dev, generator=torch.Generator(device=dev).manual_seed(5)))
+                X5 = torch.randn(N5, k5, device=dev, generator=torch.Generator(device=dev).manual_seed(6))
+                tw = time.perf_counter()
+                while (time.perf_counter() - tw) * 1e3 < WARM_MS / 2:
+                    eng.affinity_matvec(E5b, X5)
+                    torch.cuda.synchronize()
+                eng.profile_begin()
+                for _ in range(3):
+                    eng.affinity_matvec(E5b, X5)
+                p5 = eng.profile_end()["affinity_matvec"]
+                ms5 = p5["ms"] / 3
+                mv_traffic, mv_src = None, None
+                mv_files = sorted((ROOT / "profiles").glob("*pmc_matvec.json"))
+                if mv_files:      # committed rocprofv3 --pmc pass of this kernel at this shape (tools/pmc_any.sh tools/one_matvec.py): bytes leaving L2 per launch
+                    try:
+                        pm = json.loads(mv_files[-1].read_text())["affinity_matvec2_kernel"]
+                        mv_traffic = round((2.0 * pm["FETCH_SIZE"] + pm["WRITE_SIZE"]) * 1024.0, 1)
+                        mv_src = f"profiles/{mv_files[-1].name}"
+                    except Exception:  # noqa: BLE001
+                        pass
+                clus = {"workload": "config #5 tile kernel: 100k x 100k segment-segment affinity recomputed + A.X (k=16), one GPU",
+                        "pairs_per_sec": round(N5 * N5 / (ms5 * 1e-3), 1), "ms": round(ms5, 3),
+                        "roofline": {"kernel": "affinity_matvec2_kernel", "bound": "mfma", "achieved": round(2.0 * N5 * N5 * (192 + k5) / (ms5 * 1e-3) / 1e12, 2),
+                                     "peak": PEAK_BF16_MFMA / 1e12, "unit": "TFLOP/s", "frac": round(2.0 * N5 * N5 * (192 + k5) / (ms5 * 1e-3) / PEAK_BF16_MFMA, 4),
+                                     "traffic": mv_traffic, "traffic_source": mv_src,
+                                     "algorithmic_bytes_per_launch": 2.0 * N5 * 192 + 4.0 * N5 * k5 * 2,
+                                     "note": "executed flops are 1.23x the algorithmic 2 N^2 (192 + k): X is split hi+lo and padded to 32 columns"}}
 
         out = {
             "metric": "segment-embeddings/sec", "value": round(value, 2), "unit": "segment-embeddings/sec",
@@ -779,16 +821,18 @@ def main() -> int:
                        "segments_per_gpu": B, "profiles": args.profiles, "embed_dim": 192, "frames_per_segment": T_FRAMES,
                        "weights": "random-init seed 0 (20.77 M params)", "parallelism": f"segments sharded x{world}, profiles replicated"
                        + (", RCCL all-gather of embeddings per step" if use_dist else "")},
-            "affinity_pairs_per_sec": aff["pairs_per_sec"] if aff else None,
-            "roofline": roofline, "roofline_forward_mfma": fwd_mfma, "roofline_forward_hbm_model": fwd_hbm, "affinity": aff,
-            "affinity_cluster": clus, "embedding_exchange": exchange, "config4_multi_gpu": cfg4, "config5_multi_gpu": cfg5,
-            "kernels": kernels, "step_device_ms": round(step_dev_ms, 3),
             "device": {"name": info["name"], "arch": info["arch"], "cus": info["compute_units"], "clock_mhz": info["clock_khz"] / 1000.0},
-            "peaks_used": {"bf16_mfma_tflops": PEAK_BF16_MFMA / 1e12, "hbm_gbps": PEAK_HBM / 1e9,
-                           "in_kernel_clock_mhz": clock_mhz,
-                           "note": "peak = 2.4 GHz datasheet figure; in_kernel_clock_mhz = shader clock the chip held inside the dominant kernel (s_memtime / s_memrealtime), "
-                                   "clock-adjusted fraction = frac * 2400 / in_kernel_clock_mhz"},
         }
+        if args.full:
+            out.update({
+                "affinity_pairs_per_sec": aff["pairs_per_sec"] if aff else None,
+                "roofline": roofline, "roofline_forward_mfma": fwd_mfma, "roofline_forward_hbm_model": fwd_hbm, "affinity": aff,
+                "affinity_cluster": clus, "embedding_exchange": exchange, "config4_multi_gpu": cfg4, "config5_multi_gpu": cfg5,
+                "kernels": kernels, "step_device_ms": round(step_dev_ms, 3),
+                "peaks_used": {"bf16_mfma_tflops": PEAK_BF16_MFMA / 1e12, "hbm_gbps": PEAK_HBM / 1e9,
+                               "in_kernel_clock_mhz": clock_mhz,
+                               "note": "peak = 2.4 GHz datasheet figure; in_kernel_clock_mhz = shader clock the chip held inside the dominant kernel (s_memtime / s_memrealtime), "
+                                       "clock-adjusted fraction = frac * 2400 / in_kernel_clock_mhz"}})
         try:
             out["rccl_version"] = ".".join(str(x) for x in torch.cuda.nccl.version())
         except Exception:  # noqa: BLE001
@@ -800,7 +844,7 @@ def main() -> int:
                                                                                           "RCCL_ENABLE_INTRANET", "RCCL_MSCCL_ENABLE", "RCCL_MSCCLPP_ENABLE",
                                                                                           "HSA_ENABLE_IPC_MODE_LEGACY", "HSA_FORCE_FINE_GRAIN_PCIE")},
                                      "note": "unset = RCCL's own choice for the topology; compare embedding_exchange.config4_shard.ms with 0.63 ms (direct) / 4.4 ms (ring)"}
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             # sustained: >= 200 steps (~2 s) of the same step, with the in-kernel clock of the dominant kernel before and after, so a reader (and
             # the driver's utilisation sampler) can see whether the 20-step headline holds
             c0 = measure_gemm_clock(eng, step)
@@ -818,17 +862,17 @@ def main() -> int:
             out["sustained"] = {"steps": n_sus, "seconds": round(sus, 3), "value": round(B * n_sus / sus, 1), "ms_per_step": round(sus / n_sus * 1e3, 3),
                                 "ratio_to_headline": round((B * n_sus / sus) / value, 4), "in_kernel_clock_mhz_before": c0, "in_kernel_clock_mhz_after": c1,
                                 "board_power": pw}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"], e_ref = cpu_baseline(pcm_host, P_host)
             # PCM -> score deviation of the GPU path from the fp32 oracle on the baseline's sample (>= 64 segments when the host is
             # fast enough): the honest reading of "identical IDs, scores within 1e-5" for the whole path
             m = min(len(e_ref), 64)
             Eg, _, _ = eng.embed_pcm(pcm)
-            gi, gs = step(exchange=False)
+            _, gi, gs = step(exchange=False)
             out["parity"] = dict(parity_object(Eg[:m].cpu().numpy(), gi[:m, 0].cpu().numpy(), gs[:m, 0].cpu().numpy(), e_ref[:m], P_host),
                                  reference="oracle/ecapa.py mode fp32 (no rounding anywhere) + oracle/scoring.py, same PCM, same profiles",
                                  note="k4 alone (given the embeddings) is exact: max_abs_top1_score_vs_own_embedding; the embedding deviation is the bf16 operand model")
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             try:
                 out["precision_modes"] = precision_modes(eng, pcm, pcm_host, P_host, Pn, Pb, rpm, value, ms_step, out.get("parity"))
             except Exception as exc:  # noqa: BLE001

@@ -184,6 +184,50 @@ def make_schema_golden(ref: Path, here: Path) -> None:
     print("wrote", here / "schema_golden.json")
 
 
+def make_registry_golden(here: Path) -> None:
+    """The toolkit's plug-in contract as data (base.py:22-304): every public member of its EmbeddingBackend ABC (property or method,
+    abstract or not, parameter names and defaults), and what its registry resolves from a config holding both entry forms, plus the
+    error an unknown name raises.  tests/test_host_store_wav_cpu.py checks the backend against this record."""
+    import inspect
+    from speaker_detection_backends import base as rbase
+
+    members = {}
+    for name, obj in vars(rbase.EmbeddingBackend).items():
+        if name.startswith("_"):
+            continue
+        if isinstance(obj, property):
+            members[name] = {"kind": "property", "abstract": bool(getattr(obj, "__isabstractmethod__", False))}
+        elif inspect.isfunction(obj):
+            params = list(inspect.signature(obj).parameters.values())[1:]
+            members[name] = {"kind": "method", "abstract": bool(getattr(obj, "__isabstractmethod__", False)),
+                             "params": [p.name for p in params],
+                             "defaults": {p.name: p.default for p in params if p.default is not inspect.Parameter.empty}}
+    text = "backends:\n  short: pkg_a.backend\n  long:\n    module: pkg_b.backend\n    description: d\n    requires_api_key: false\n"
+    old = os.environ.get("SPEAKER_BACKENDS_CONFIG")
+    with tempfile.TemporaryDirectory() as td:
+        cfg = Path(td) / "b.yaml"
+        cfg.write_text(text)
+        os.environ["SPEAKER_BACKENDS_CONFIG"] = str(cfg)
+        rbase.reload_backends_config()
+        try:
+            resolved = dict(rbase._load_backends_config())
+            try:
+                rbase.get_backend("nope")
+                unknown = None
+            except ValueError as exc:
+                unknown = str(exc)
+        finally:
+            if old is None:
+                os.environ.pop("SPEAKER_BACKENDS_CONFIG", None)
+            else:
+                os.environ["SPEAKER_BACKENDS_CONFIG"] = old
+            rbase.reload_backends_config()
+    out = {"abstract": sorted(rbase.EmbeddingBackend.__abstractmethods__), "members": members,
+           "config": {"text": text, "resolved": resolved, "unknown_error": unknown}}
+    (here / "registry_golden.json").write_text(json.dumps(out, indent=1) + "\n")
+    print("wrote", here / "registry_golden.json")
+
+
 def main() -> int:
     if not REF.exists():
         print("reference not mounted; golden vectors can only be regenerated in the build container",
@@ -401,6 +445,7 @@ def main() -> int:
         out["cli"] = {"wav_seed": 7, "wav_sha256_32": hashlib.sha256(wav.read_bytes()).hexdigest()[:32], "runs": cli}
 
     make_schema_golden(REF, HERE)
+    make_registry_golden(HERE)
     (HERE / "plumbing_golden.json").write_text(json.dumps(out, indent=1, sort_keys=False) + "\n")
     print("wrote", HERE / "plumbing_golden.json", (HERE / "plumbing_golden.json").stat().st_size, "bytes")
     return 0

@@ -195,3 +195,32 @@ def test_bench_rccl_path_refuses_more_ranks_than_devices(monkeypatch, capsys):
     assert bench.main() == 2 and not called
     err = capsys.readouterr().err
     assert "needs 2 visible GPUs" in err and "shows 1" in err and "SDK_BENCH_BACKEND=gloo" in err
+
+
+def test_bench_dump_outputs_dtypes_and_budget(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: every array as DIR/<name>.npy, integers as float64 and floats as float32, values unchanged; past the
+    byte budget each array is cut to a seeded sample of its rows (the same rows on every run and for arrays of equal length, their numbers
+    beside them) and the files stay inside the budget."""
+    import sys as _sys
+    import torch
+    _sys.path.insert(0, str(ROOT))
+    import bench
+    E = torch.randn(500, 192, generator=torch.Generator().manual_seed(0))
+    ids = torch.arange(500, dtype=torch.int32).reshape(-1, 1)
+    sc = torch.rand(500, 1, generator=torch.Generator().manual_seed(1))
+    bench.dump_outputs(str(tmp_path / "all"), {"embeddings": E, "ids": ids, "scores": sc})
+    got = {n: np.load(tmp_path / "all" / f"{n}.npy") for n in ("embeddings", "ids", "scores")}
+    assert sorted(p.name for p in (tmp_path / "all").iterdir()) == ["embeddings.npy", "ids.npy", "scores.npy"]
+    assert got["embeddings"].dtype == np.float32 and got["scores"].dtype == np.float32 and got["ids"].dtype == np.float64
+    assert np.array_equal(got["embeddings"], E.numpy()) and np.array_equal(got["ids"], ids.numpy()) and np.array_equal(got["scores"], sc.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 100_000)
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), {"embeddings": E, "ids": ids, "scores": sc})
+        assert sum(p.stat().st_size for p in (tmp_path / run).iterdir()) <= 100_000
+    rows = np.load(tmp_path / "s1" / "embeddings_rows.npy").astype(np.int64)
+    assert 0 < len(rows) < 500 and np.array_equal(rows, np.load(tmp_path / "s2" / "embeddings_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "embeddings.npy"), E.numpy()[rows])
+    # arrays of the same length keep the same rows: the sampled embeddings, IDs and scores still line up
+    for n, full in (("ids", ids), ("scores", sc)):
+        assert np.array_equal(np.load(tmp_path / "s1" / f"{n}_rows.npy"), rows)
+        assert np.array_equal(np.load(tmp_path / "s1" / f"{n}.npy"), full.numpy()[rows])

@@ -231,21 +231,44 @@ def test_registry(monkeypatch, tmp_path):
 
 
 def test_backend_plugs_into_the_reference_registry(monkeypatch):
-    """Drop-in check against the real toolkit when it is mounted (build container only)."""
-    ref = Path("/root/reference")
-    if not ref.exists():
-        pytest.skip("reference not mounted on this machine")
-    import subprocess, sys
-    code = (
-        "import sys; sys.path[:0]=[%r,%r]\n"
-        "from speaker_detection_backends import get_backend\n"
-        "from speaker_detection_backends.base import EmbeddingBackend\n"
-        "b=get_backend('mi355x'); assert isinstance(b, EmbeddingBackend), type(b).__mro__\n"
-        "print(b.name, b.embedding_dim, b.get_audio_profile().sample_rate, b.model_version)\n" % (str(ref), str(ROOT)))
-    env = dict(os.environ, SPEAKER_BACKENDS_CONFIG=str(ROOT / PKG / "backends.yaml"), PYTHONDONTWRITEBYTECODE="1")
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, r.stderr
-    assert r.stdout.startswith("mi355x 192 16000 mi355x-ecapa1024-")
+    """Drop-in check against the toolkit's plug-in contract as recorded from it (tests/golden/registry_golden.json, written by
+    tests/golden/make_golden.py): its registry's reading of a config, our backends.yaml resolved by that rule and the module's
+    `Backend()` built the way its get_backend builds it, and every member of its EmbeddingBackend ABC present on the backend with
+    the same kind, parameters and defaults, none of the abstract ones left abstract."""
+    import importlib
+    import inspect
+    import tempfile
+    g = json.loads((ROOT / "tests" / "golden" / "registry_golden.json").read_text())
+    api = sub("plugin_api")
+    try:
+        with tempfile.TemporaryDirectory() as td:
+            canned = Path(td) / "b.yaml"
+            canned.write_text(g["config"]["text"])
+            monkeypatch.setenv("SPEAKER_BACKENDS_CONFIG", str(canned))
+            api.reload_backends_config()
+            assert api._load_backends_config() == g["config"]["resolved"]
+            with pytest.raises(ValueError) as exc:
+                api.get_backend("nope")
+            assert str(exc.value) == g["config"]["unknown_error"]
+        monkeypatch.setenv("SPEAKER_BACKENDS_CONFIG", str(ROOT / PKG / "backends.yaml"))
+        api.reload_backends_config()
+        b = importlib.import_module(api._load_backends_config()["mi355x"]).Backend()
+    finally:
+        api.reload_backends_config()
+    assert isinstance(b, api.EmbeddingBackend)
+    assert sorted(api.EmbeddingBackend.__abstractmethods__) == g["abstract"] and not type(b).__abstractmethods__
+    for name, m in g["members"].items():
+        got = inspect.getattr_static(type(b), name)
+        if m["kind"] == "property":
+            assert isinstance(got, property), name
+        else:
+            assert inspect.isfunction(got), name
+            params = list(inspect.signature(got).parameters.values())[1:]
+            assert [p.name for p in params] == m["params"], name
+            assert {p.name: p.default for p in params if p.default is not inspect.Parameter.empty} == m["defaults"], name
+        assert not getattr(got, "__isabstractmethod__", False), name
+    assert (b.name, b.embedding_dim, b.get_audio_profile().sample_rate) == ("mi355x", 192, 16000)
+    assert b.model_version.startswith("mi355x-ecapa1024-")
 
 
 def test_identify_rows_early_exits_mirror_cmd_identify(tmp_path, monkeypatch, capsys):

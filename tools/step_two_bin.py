@@ -11,7 +11,7 @@ res = {"A": [], "B": []}
 for r in range(rounds):
     for tag, lib in (("A", libA), ("B", libB)):
         env = dict(os.environ, SDK_HIP_LIB=str(Path(lib).resolve()))
-        o = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "50", "--no-extras", "--no-cpu-baseline", "--no-affinity-config3"], env=env,
+        o = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "50", "--full", "--no-extras", "--no-cpu-baseline", "--no-affinity-config3"], env=env,
                            capture_output=True, text=True, timeout=400)
         line = [l for l in o.stdout.splitlines() if l.startswith("{")]
         if not line:
