@@ -27,12 +27,14 @@
  *     sdk_ingest_create / _destroy / _acquire / _commit / _submit / _release / _copy_ms          host audio -> HBM, pinned + double-buffered
  *     sdk_ecapa_workspace_bytes  sdk_ecapa_forward  sdk_ecapa_calib_floats  sdk_ecapa_forward_calib            k2
  *     sdk_xvector_workspace_bytes  sdk_xvector_forward                                                  k2 (second model family)
+ *     sdk_resnet_workspace_bytes  sdk_resnet_forward                                                    k2 (third model family: ResNet34)
  *     sdk_l2norm                                                                                        k3
  *     sdk_affinity_workspace_bytes  sdk_affinity_topk                                                   k4
  *     sdk_affinity_matvec_workspace_bytes  sdk_affinity_matvec  sdk_rows_gram_workspace_bytes  sdk_rows_gram
  *     sdk_rows_apply  sdk_chol_inverse  sdk_rows_unit  sdk_kmeans_mindist  sdk_kmeans_assign            k6 (driven by cluster.py)
  * BUILDING BLOCKS AND KNOBS - exported for the parity tests and the A/B tools, free to change between rounds, not for binding:
  *     sdk_conv_gemm*  sdk_colstats_finish  sdk_res2net_chain*  sdk_se_*  sdk_asp_*  sdk_rows_fc  (pieces of sdk_ecapa_forward)
+ *     sdk_resnet_conv2d  (piece of sdk_resnet_forward)
  *     sdk_set_option  sdk_set_gemm_variant  sdk_profile_begin / _end  sdk_debug_set_ptr  sdk_affinity_plan*  sdk_affinity_block_plan*  sdk_affinity_matvec_plan  sdk_conv_gemm_hp
  *     sdk_allgather  sdk_laplacian_topk_workspace_bytes  sdk_laplacian_topk        k5 / k6 drivers for a non-Python host (the library holds no
  *                                                                                     communicator: the caller passes its ncclComm_t; the Python
@@ -104,7 +106,8 @@ int sdk_debug_set_ptr(sdk_ctx* ctx, const char* name, void* device_ptr);
 enum {
   SDK_K_CONV_GEMM = 0, SDK_K_SE_GATE, SDK_K_ASP_STATS, SDK_K_ROWS_FC, SDK_K_ASP_POOL, SDK_K_FBANK_TILE,
   SDK_K_FBANK_NORM, SDK_K_L2NORM, SDK_K_AFF_COARSE, SDK_K_AFF_RESCORE, SDK_K_AFF_RESCAN, SDK_K_COPY,
-  SDK_K_AFF_MATVEC, SDK_K_CONV_GEMM256, SDK_K_ASP_FUSED, SDK_K_RES2NET, SDK_K_RESAMPLE, SDK_K_CONV_GEMM_HP, SDK_K_COUNT
+  SDK_K_AFF_MATVEC, SDK_K_CONV_GEMM256, SDK_K_ASP_FUSED, SDK_K_RES2NET, SDK_K_RESAMPLE, SDK_K_CONV_GEMM_HP,
+  SDK_K_RESNET_CONV, SDK_K_RESNET_STEM, SDK_K_RESNET_POOL, SDK_K_COUNT
 };
 typedef struct sdk_profile_report {
   int32_t launches[24];
@@ -342,6 +345,52 @@ typedef struct sdk_xvector_desc {
 size_t sdk_xvector_workspace_bytes(const sdk_xvector_desc* d, int B, int T);
 int sdk_xvector_forward(sdk_ctx* ctx, const void* wblob, const sdk_xvector_desc* d, const uint16_t* feats, int ldf, int B, int T,
                         void* ws, size_t ws_bytes, float* emb, void* stream);
+
+/* ---- ResNet34 forward (WeSpeaker ResNet34, the PyAnnote 3.1 speaker embedding; resnet.py).  The fbank matrix is a one-channel image of
+ *      height F = n_feats (mel) and width T (frames): element (f, t) of segment b is feats[b*T + t, f].  Activations are channel-last
+ *      [B][F][T][C] (2-byte elements), so the final map flattens to feature c*F4 + f with no transpose.
+ *        stem      3x3 conv 1 -> width[0], stride 1, zero padding 1, folded BN, ReLU
+ *        layer l   blocks[l] BasicBlocks of width[l]; the first block of layers 1..3 has stride 2 and a projection shortcut (1x1 conv + BN)
+ *                  block: y = relu(bn2(conv2(relu(bn1(conv1(x))))) + shortcut(x)); output size o = (n - 1) / 2 + 1 per strided axis
+ *        pooling   temporal statistics of the last map: mean | sqrt(unbiased var + 1e-7) over t, fp32 [B, 2 * width[3] * F4]
+ *        seg_1     fp32 linear layer -> emb [B, embed_dim] (sdk_rows_fc)
+ *      Every conv is one sdk_resnet_conv2d launch (implicit GEMM on the MFMA pipe; BN folded at pack time: its scale multiplies W in fp32
+ *      before the rounding, its shift is the conv's bias).  A projection shortcut is extra K columns of its block's conv2, so conv2 +
+ *      shortcut + add is one launch.  Layer-boundary storage in the blob's 2-byte format, fp32 accumulation, fp32 pooling and seg_1.
+ *      Blob slots (256-byte aligned): conv i (i = 0 the stem, then conv1, conv2 of every block in order) has its weights at off[2 i]
+ *      (2-byte bits [Cout][K], K tap-major: k = (3 dy + dx) Cin + c; the stem [width[0]][9]; a downsampling conv2 has K = 9 C + Cin, the
+ *      shortcut's columns last) and its fp32 bias [Cout] at off[2 i + 1]; off[66] = seg_1 weight (fp32 [2 width[3] F4, embed_dim],
+ *      transposed), off[67] = seg_1 bias.  precision: 0 = bf16 operands and storage, 2 = one fp16 plane (features from
+ *      sdk_fbank_fmt(..., 2, ...)); the precise mode (1) is not built for this family and is refused.  The contract comes from the
+ *      descriptor alone.  T >= 9 (the last map needs two frames for an unbiased variance). */
+typedef struct sdk_resnet_desc {
+  int32_t n_feats, embed_dim, precision, n_layers;   /* n_layers = 4 */
+  int32_t blocks[4], width[4];                       /* widths 32 / 64 / 128 / 256 (each one of those), stem width = width[0] = 32 */
+  int64_t off[72];
+} sdk_resnet_desc;
+size_t sdk_resnet_workspace_bytes(const sdk_resnet_desc* d, int B, int T);
+int sdk_resnet_forward(sdk_ctx* ctx, const void* wblob, const sdk_resnet_desc* d, const uint16_t* feats, int ldf, int B, int T,
+                       void* ws, size_t ws_bytes, float* emb, void* stream);
+/* One 3x3 conv (zero padding 1) of the ResNet34 forward: y = act(x (*) W + bias [+ shortcut] [+ res]), fp32 epilogue, rounded once.
+ *   x [B][F][T][Cin] channel-last (Cin = 1: the stem, x is the fbank matrix [B*T, ldx] read as the image (f, t) = x[b*T + t, f]);
+ *   W [Cout][ldw] 2-byte bits, ldw = 9 Cin + Csc; y [B][Fo][To][Cout] with Fo = (F - 1) / stride + 1, To likewise.
+ *   sc (or NULL): projection-shortcut input [B][Fsc][Tsc][Csc], read at (stride_sc fo, stride_sc to) against W's last Csc columns;
+ *   res (or NULL): identity residual [B][Fo][To][Cout].  flags: SDK_GEMM_RELU, SDK_GEMM_F16.
+ *   Cin in {1, 32, 64, 128, 256} (Cin = 1: Cout = 32, stride 1, no shortcut / residual), Cout in {32, 64, 128, 256}, stride 1 or 2. */
+typedef struct sdk_resnet_conv_args {
+  const uint16_t* x;
+  const uint16_t* W;
+  const float* bias;
+  const uint16_t* sc;
+  const uint16_t* res;
+  uint16_t* y;
+  int64_t ldx;
+  int32_t B, F, T, Cin, Cout, stride;
+  int32_t Csc, Fsc, Tsc, stride_sc;
+  uint32_t flags;
+  int32_t reserved;
+} sdk_resnet_conv_args;
+int sdk_resnet_conv2d(sdk_ctx* ctx, const sdk_resnet_conv_args* a, void* stream);
 
 /* ---- audio conversion to the AudioProfile: replaces the ffmpeg subprocess the reference's backends
  *      run before upload (audio_profiles.py:70-100 `format_ffmpeg_args`; speechmatics_backend.py:231-281).

@@ -57,13 +57,21 @@ class ConvGemmHpArgs(C.Structure):
                 ("M", C.c_int), ("N", C.c_int), ("Cin", C.c_int), ("taps", C.c_int), ("dil", C.c_int), ("T", C.c_int), ("flags", C.c_uint32)]
 
 
+class ResNetConvArgs(C.Structure):
+    """sdk_resnet_conv_args (include/sdk_hip.h): one 3x3 conv of the ResNet34 family."""
+    _fields_ = [("x", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p), ("sc", C.c_void_p), ("res", C.c_void_p), ("y", C.c_void_p),
+                ("ldx", C.c_int64), ("B", C.c_int32), ("F", C.c_int32), ("T", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32),
+                ("stride", C.c_int32), ("Csc", C.c_int32), ("Fsc", C.c_int32), ("Tsc", C.c_int32), ("stride_sc", C.c_int32),
+                ("flags", C.c_uint32), ("reserved", C.c_int32)]
+
+
 class ProfileReport(C.Structure):
     _fields_ = [("launches", C.c_int32 * 24), ("ms", C.c_double * 24), ("flops", C.c_double * 24), ("bytes", C.c_double * 24)]
 
 
 KERNEL_FAMILIES = ["conv_gemm", "se_gate", "asp_stats", "rows_fc", "asp_pool", "fbank_tile", "fbank_norm", "l2norm",
                    "affinity_coarse", "affinity_rescore", "affinity_rescan", "copy", "affinity_matvec", "conv_gemm256", "asp_fused", "res2net_chain", "resample",
-                   "conv_gemm_hp"]
+                   "conv_gemm_hp", "resnet_conv", "resnet_stem", "resnet_pool"]
 
 ABI_VERSION = 4
 GEMM_RELU = 1
@@ -125,6 +133,9 @@ SIGNATURES = {
     "sdk_ecapa_forward_calib": (_i, [_vp, _vp, C.POINTER(EcapaDesc), _vp, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
     "sdk_xvector_workspace_bytes": (_sz, [_vp, _i, _i]),
     "sdk_xvector_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "sdk_resnet_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "sdk_resnet_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "sdk_resnet_conv2d": (_i, [_vp, _vp, _vp]),
     "sdk_resample_out_len": (_i64, [_i64, _i, _i]),
     "sdk_resample_s16": (_i, [_vp, _vp, _i64, _i, _vp, _i, _i, _i, _vp, _i64, _vp]),
     "sdk_l2norm": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),

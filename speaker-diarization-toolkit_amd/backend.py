@@ -12,6 +12,9 @@ Environment:
   SDK_MODEL           "ecapa" (default: ECAPA-TDNN C = 1024) / "xvector" (plain TDNN x-vector, xvector.py): the second model family north_star names.
                       Same front end, same 192-d back end (k3 / k4 / store); model_version names the family, so vectors enrolled with one are
                       refused by the other (store.load_profile_batch).  SDK_XVECTOR_WEIGHTS: .npz in the xvector.py naming (default: seeded synthetic)
+                      / "resnet34" (the WeSpeaker ResNet34 that PyAnnote 3.1 embeds with, resnet.py; 192-d).  SDK_RESNET_WEIGHTS: .npz in the public
+                      state-dict naming of resnet.py (default: seeded synthetic).  Serves SDK_PRECISION 0 and 2, no bias correction, torch engine
+                      only (SDK_NO_TORCH=1 is refused)
   SDK_ECAPA_WEIGHTS   .npz checkpoint in the weights.py naming (default: seeded synthetic weights -
                       there is no network here to fetch a pretrained model; a warning is printed)
   SDK_ECAPA_LAYOUT    "public": SDK_ECAPA_WEIGHTS is a checkpoint in the public ECAPA-TDNN state-dict naming (.ckpt / .pt via
@@ -51,15 +54,15 @@ from .weights import DEFAULT_CONFIG, load_weights, synthetic_weights, weights_di
 class Backend(EmbeddingBackend):
     def __init__(self) -> None:
         self.model = os.environ.get("SDK_MODEL", "ecapa").strip().lower()
-        if self.model not in ("ecapa", "xvector"):
-            raise ValueError(f"SDK_MODEL={self.model!r}: expected 'ecapa' or 'xvector'")
-        wenv = "SDK_XVECTOR_WEIGHTS" if self.model == "xvector" else "SDK_ECAPA_WEIGHTS"
+        if self.model not in ("ecapa", "xvector", "resnet34"):
+            raise ValueError(f"SDK_MODEL={self.model!r}: expected 'ecapa', 'xvector' or 'resnet34'")
+        wenv = {"xvector": "SDK_XVECTOR_WEIGHTS", "resnet34": "SDK_RESNET_WEIGHTS"}.get(self.model, "SDK_ECAPA_WEIGHTS")
         if not os.environ.get(wenv):
-            print(f"mi355x backend: {wenv} not set - using seeded synthetic {'x-vector' if self.model == 'xvector' else 'ECAPA-TDNN'} weights "
+            print(f"mi355x backend: {wenv} not set - using seeded synthetic {dict(xvector='x-vector', resnet34='ResNet34').get(self.model, 'ECAPA-TDNN')} weights "
                   "(scores are self-consistent but not trained)", file=sys.stderr)
         self._cache_hit = False
         self._engine = None
-        self._xvector = None
+        self._extractor = None                          # the x-vector / ResNet34 extractor (None: the engine's own ECAPA-TDNN)
         self._weights = None
         self._digest: Optional[str] = None
         self.window_s = float(os.environ.get("SDK_WINDOW_S", "2.0"))
@@ -79,6 +82,9 @@ class Backend(EmbeddingBackend):
         if self.model == "xvector":
             from .xvector import DEFAULT_XVECTOR
             return DEFAULT_XVECTOR.embed_dim
+        if self.model == "resnet34":
+            from .resnet import DEFAULT_RESNET
+            return DEFAULT_RESNET.embed_dim
         return DEFAULT_CONFIG.embed_dim
 
     @property
@@ -86,6 +92,8 @@ class Backend(EmbeddingBackend):
         if self.model == "xvector":
             from .xvector import DEFAULT_XVECTOR
             return f"{self.name}-xvector{DEFAULT_XVECTOR.channels[0]}-{self._weights_digest()}"
+        if self.model == "resnet34":
+            return f"{self.name}-resnet34-{self._weights_digest()}"
         return f"{self.name}-ecapa1024-{self._weights_digest()}"
 
     @property
@@ -103,6 +111,15 @@ class Backend(EmbeddingBackend):
                 xvector.pack_weights(self._weights)                      # shape check (raises ValueError naming the tensor)
             else:
                 self._weights = xvector.synthetic_weights(0)
+        if self._weights is None and self.model == "resnet34":
+            from . import resnet
+            path = os.environ.get("SDK_RESNET_WEIGHTS")
+            if path:
+                with np.load(path, allow_pickle=False) as z:             # numpy's non-executing loader
+                    self._weights = {k: np.ascontiguousarray(z[k], dtype=np.float32) for k in z.files}
+                resnet.pack_weights(self._weights)                       # shape check (raises ValueError naming the tensor)
+            else:
+                self._weights = resnet.synthetic_weights(0)
         if self._weights is None:
             path = os.environ.get("SDK_ECAPA_WEIGHTS")
             if path:
@@ -120,8 +137,8 @@ class Backend(EmbeddingBackend):
     def _cache_key(self) -> str:
         """Identity of the weights for the packed-blob cache, without reading them (weights_cache.py)."""
         from . import weights_cache
-        if self.model == "xvector":
-            return None                                  # 4.4 M parameters: packed in ~0.1 s, not cached
+        if self.model in ("xvector", "resnet34"):
+            return None                                  # 4.4 M / 6.3 M parameters: packed in well under a second, not cached
         path = os.environ.get("SDK_ECAPA_WEIGHTS")
         return weights_cache.key_for_file(path) if path else weights_cache.key_for_seed(0, DEFAULT_CONFIG)
 
@@ -143,7 +160,7 @@ class Backend(EmbeddingBackend):
         """The numerical setting embeddings are made under (stored beside every enrolled vector; identify warns when a candidate was made
         under another one): model_version names the WEIGHTS - both settings embed into the same space, ~4e-3 apart."""
         prec = int(os.environ.get("SDK_PRECISION", "0"))
-        return {"precision": prec, "bias_correction": bool(os.environ.get("SDK_BIAS_CORRECTION", "1") != "0") and prec in (0, 2)}
+        return {"precision": prec, "bias_correction": bool(os.environ.get("SDK_BIAS_CORRECTION", "1") != "0") and prec in (0, 2) and self.model != "resnet34"}
 
     @property
     def lite(self) -> bool:
@@ -152,6 +169,8 @@ class Backend(EmbeddingBackend):
     def _lite_engine(self):
         """lite.LiteEngine on the cached packed weights; a cache miss is filled ONCE by a child process that runs the torch engine (pack, bias-correction
         calibration pass, store) - this process must not import torch itself (one HIP runtime per process)."""
+        if self.model == "resnet34":
+            raise ValueError("SDK_NO_TORCH=1 with SDK_MODEL=resnet34: the torch-free host path does not serve the ResNet34 family; unset SDK_NO_TORCH")
         from .lite import LiteEngine
         dev = int(os.environ.get("SDK_DEVICE", os.environ.get("LOCAL_RANK", "0")))
         prec = int(os.environ.get("SDK_PRECISION", "0"))
@@ -193,7 +212,17 @@ class Backend(EmbeddingBackend):
                 self._engine = Engine(dev)               # front end, k3, k4; its ECAPA weights are never packed (lazy)
                 if prec:
                     self._engine.set_precision(prec)
-                self._xvector = XVector(self._engine, self._host_weights(), precision=prec)      # bias correction: $SDK_BIAS_CORRECTION (default on)
+                self._extractor = XVector(self._engine, self._host_weights(), precision=prec)    # bias correction: $SDK_BIAS_CORRECTION (default on)
+                return self._engine
+            if self.model == "resnet34":
+                from .resnet import ResNet34
+                prec = int(os.environ.get("SDK_PRECISION", "0"))
+                if prec == 1:
+                    raise ValueError("SDK_PRECISION=1 (the precise mode) is not built for SDK_MODEL=resnet34: use SDK_PRECISION=0 or 2")
+                self._engine = Engine(dev)               # front end, k3, k4; its ECAPA weights are never packed (lazy)
+                if prec:
+                    self._engine.set_precision(prec)
+                self._extractor = ResNet34(self._engine, self._host_weights(), precision=prec)
                 return self._engine
             self._engine = Engine(dev, cache_key=self._cache_key(), weights_fn=self._host_weights, digest_fn=self._weights_digest)
             prec = int(os.environ.get("SDK_PRECISION", "0"))
@@ -204,7 +233,7 @@ class Backend(EmbeddingBackend):
     def _embed_pcm(self, pcm_dev):
         """[B, S] int16 device tensor -> (E fp32, Eb bf16, resid): the selected model family's fbank -> forward -> L2 sequence."""
         eng = self.engine()
-        return self._xvector.embed_pcm(pcm_dev) if self._xvector is not None else eng.embed_pcm(pcm_dev)
+        return self._extractor.embed_pcm(pcm_dev) if self._extractor is not None else eng.embed_pcm(pcm_dev)
 
     # ---- the GPU path ----------------------------------------------------------------------
     def embed_windows(self, pcm: np.ndarray):
@@ -259,7 +288,7 @@ class Backend(EmbeddingBackend):
         if self.lite:
             raise RuntimeError("embed_tables returns device tensors: not available with SDK_NO_TORCH=1 (use embed_tables_host)")
         step = max(1, int(os.environ.get("SDK_MAX_BATCH", "2048")))
-        return eng.embed_from_host(samples, tables, step, forward=self._xvector.forward if self._xvector is not None else None)
+        return eng.embed_from_host(samples, tables, step, forward=self._extractor.forward if self._extractor is not None else None)
 
     def embed_tables_host(self, samples: np.ndarray, tables: Dict[int, np.ndarray], batch=None, k: int = 1):
         """The same for the torch-free host path: {S: (E host, idx, score)}; with a ProfileBatch every batch of windows is scored while resident."""

@@ -69,6 +69,9 @@ int res2net_chain_launch(sdk_ctx* ctx, const uint16_t* U, int64_t ldu, uint16_t*
                          const uint16_t* const* Wpk, const float* const* bias, const float* const* scale, const float* const* shift,
                          int nconv, int B, int T, int dil, void* stream, bool f16 = false);
 
+// resnet.hip: temporal statistics pooling of the ResNet34 family's last map (internal; sdk_resnet_forward)
+int resnet_tstp_impl(sdk_ctx* ctx, const uint16_t* x, int B, int F, int T, int C, float* out, void* stream, bool f16);
+
 struct ProfScope {   // brackets one kernel launch with two events when profiling is enabled
   sdk_ctx* c; hipStream_t s; size_t slot; bool on;
   ProfScope(sdk_ctx* ctx, void* stream, int family, double flops, double bytes) : c(ctx), s((hipStream_t)stream), slot(0), on(ctx && ctx->prof_on) {

@@ -631,3 +631,98 @@ extern "C" int sdk_xvector_forward(sdk_ctx* ctx, const void* wblob, const sdk_xv
   return sdk_rows_fc(ctx, stats, 2 * Cl, nullptr, nullptr, (const float*)(wb + d->off[60]), (const float*)(wb + d->off[61]), emb, d->embed_dim, B, 2 * Cl,
                      d->embed_dim, 0, stream);
 }
+
+// ------------------------------------------------------------------------------ ResNet34 forward
+// The WeSpeaker ResNet34 (the PyAnnote 3.1 speaker embedding): one sdk_resnet_conv2d per conv (a downsampling block's projection shortcut
+// rides in its conv2's K), the temporal statistics pooling, and the embedding layer on sdk_rows_fc (fp32).
+namespace {
+int check_rdesc(const sdk_resnet_desc* d) {
+  SDK_REQUIRE(d, "resnet desc is null");
+  SDK_REQUIRE(d->precision != 1, "resnet desc: precision 1 (the precise mode, SDK_PRECISION=1) is not built for the ResNet34 family; use 0 (bf16) or 2 (fp16)");
+  SDK_REQUIRE(d->precision == 0 || d->precision == 2, "resnet desc: precision=%d (0: bf16 operands, 2: one fp16 plane)", d->precision);
+  SDK_REQUIRE(d->n_layers == 4 && d->n_feats > 0 && d->embed_dim > 0, "resnet desc: n_layers=%d n_feats=%d embed_dim=%d", d->n_layers, d->n_feats, d->embed_dim);
+  SDK_REQUIRE(d->width[0] == 32, "resnet desc: width[0]=%d (the stem writes 32 channels)", d->width[0]);
+  int nconv = 1;
+  for (int l = 0; l < 4; ++l) {
+    SDK_REQUIRE(d->blocks[l] >= 1 && d->blocks[l] <= 8, "resnet desc: blocks[%d]=%d", l, d->blocks[l]);
+    SDK_REQUIRE(d->width[l] == 32 || d->width[l] == 64 || d->width[l] == 128 || d->width[l] == 256, "resnet desc: width[%d]=%d", l, d->width[l]);
+    nconv += 2 * d->blocks[l];
+  }
+  SDK_REQUIRE(nconv <= 33, "resnet desc: %d convs (at most 33 slots)", nconv);
+  for (int i = 0; i < 2 * nconv; ++i) SDK_REQUIRE(d->off[i] >= 0 && d->off[i] % 256 == 0, "resnet desc: slot %d missing or misaligned", i);
+  SDK_REQUIRE(d->off[66] >= 0 && d->off[67] >= 0 && d->off[66] % 256 == 0 && d->off[67] % 256 == 0, "resnet desc: seg_1 slots missing");
+  return 0;
+}
+int rn_out(int n, int s) { return (n - 1) / s + 1; }
+// the three activation buffers hold the largest map of the network; then the pooled statistics [B][2 C4 F4]
+size_t rn_layout(const sdk_resnet_desc* d, int B, int T, char* base, uint16_t** bufs, float** stats) {
+  int F = d->n_feats, Tl = T;
+  size_t big = (size_t)F * T * d->width[0];
+  for (int l = 0; l < 4; ++l) {
+    if (l) { F = rn_out(F, 2); Tl = rn_out(Tl, 2); }
+    const size_t e = (size_t)F * Tl * d->width[l];
+    big = e > big ? e : big;
+  }
+  size_t off = 0;
+  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += a256(bytes); return p; };
+  for (int i = 0; i < 3; ++i) {
+    char* p = take((size_t)B * big * 2);
+    if (bufs) bufs[i] = (uint16_t*)p;
+  }
+  char* s = take((size_t)B * 2 * d->width[3] * F * 4);
+  if (stats) *stats = (float*)s;
+  return off;
+}
+}  // namespace
+
+extern "C" size_t sdk_resnet_workspace_bytes(const sdk_resnet_desc* d, int B, int T) {
+  if (!d || B <= 0 || T <= 0 || d->n_feats <= 0) return 0;
+  return rn_layout(d, B, T, nullptr, nullptr, nullptr);
+}
+
+extern "C" int sdk_resnet_forward(sdk_ctx* ctx, const void* wblob, const sdk_resnet_desc* d, const uint16_t* feats, int ldf, int B, int T,
+                                  void* ws, size_t ws_bytes, float* emb, void* stream) {
+  SDK_REQUIRE(ctx && wblob && feats && ws && emb, "sdk_resnet_forward: null argument");
+  if (int rc = check_rdesc(d)) return rc;
+  SDK_REQUIRE(B > 0 && T >= 9 && (int64_t)B * T < (1ll << 31), "sdk_resnet_forward: bad batch (B=%d T=%d; segments need >= 9 frames)", B, T);
+  SDK_REQUIRE(ldf >= d->n_feats, "sdk_resnet_forward: ldf=%d < feature width %d", ldf, d->n_feats);
+  SDK_REQUIRE(ws_bytes >= sdk_resnet_workspace_bytes(d, B, T) && ((uintptr_t)ws % 256) == 0 && ((uintptr_t)wblob % 256) == 0,
+              "sdk_resnet_forward: workspace too small or misaligned");
+  const bool f16 = d->precision == 2;
+  const uint32_t fl = SDK_GEMM_RELU | (f16 ? SDK_GEMM_F16 : 0u);
+  uint16_t* buf[3];
+  float* stats;
+  rn_layout(d, B, T, (char*)ws, buf, &stats);
+  const char* wb = (const char*)wblob;
+  auto Wp = [&](int i) { return (const uint16_t*)(wb + d->off[2 * i]); };
+  auto Bp = [&](int i) { return (const float*)(wb + d->off[2 * i + 1]); };
+  uint16_t *X = buf[0], *H = buf[1], *Y = buf[2];
+  sdk_resnet_conv_args a;
+  memset(&a, 0, sizeof(a));
+  a.x = feats; a.ldx = ldf; a.W = Wp(0); a.bias = Bp(0); a.y = X;
+  a.B = B; a.F = d->n_feats; a.T = T; a.Cin = 1; a.Cout = d->width[0]; a.stride = 1; a.flags = fl;
+  if (int rc = sdk_resnet_conv2d(ctx, &a, stream)) return rc;
+  int F = d->n_feats, Tl = T, C = d->width[0], conv = 1;
+  for (int l = 0; l < 4; ++l) {
+    for (int j = 0; j < d->blocks[l]; ++j) {
+      const int s = (j == 0 && l > 0) ? 2 : 1, Cw = d->width[l];
+      const int Fo = rn_out(F, s), To = rn_out(Tl, s);
+      const bool proj = j == 0 && (s != 1 || C != Cw);
+      memset(&a, 0, sizeof(a));                                  // conv1 -> BN -> ReLU
+      a.x = X; a.W = Wp(conv); a.bias = Bp(conv); a.y = H;
+      a.B = B; a.F = F; a.T = Tl; a.Cin = C; a.Cout = Cw; a.stride = s; a.flags = fl;
+      if (int rc = sdk_resnet_conv2d(ctx, &a, stream)) return rc;
+      memset(&a, 0, sizeof(a));                                  // conv2 -> BN (+ projection shortcut in K | + identity) -> ReLU
+      a.x = H; a.W = Wp(conv + 1); a.bias = Bp(conv + 1); a.y = Y;
+      a.B = B; a.F = Fo; a.T = To; a.Cin = Cw; a.Cout = Cw; a.stride = 1; a.flags = fl;
+      if (proj) { a.sc = X; a.Csc = C; a.Fsc = F; a.Tsc = Tl; a.stride_sc = s; }
+      else a.res = X;
+      if (int rc = sdk_resnet_conv2d(ctx, &a, stream)) return rc;
+      uint16_t* t = X; X = Y; Y = t;
+      F = Fo; Tl = To; C = Cw; conv += 2;
+    }
+  }
+  if (int rc = resnet_tstp_impl(ctx, X, B, F, Tl, C, stats, stream, f16)) return rc;
+  return sdk_rows_fc(ctx, stats, 2 * C * F, nullptr, nullptr, (const float*)(wb + d->off[66]), (const float*)(wb + d->off[67]), emb, d->embed_dim, B,
+                     2 * C * F, d->embed_dim, 0, stream);
+}
