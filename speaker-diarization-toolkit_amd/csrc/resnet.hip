@@ -263,9 +263,11 @@ extern "C" int sdk_resnet_conv2d(sdk_ctx* ctx, const sdk_resnet_conv_args* a, vo
     SDK_REQUIRE(a->Cout == 32 && a->stride == 1 && !a->sc && !a->res && a->Csc == 0 && a->ldx >= a->F && ((uintptr_t)a->y % 16) == 0,
                 "sdk_resnet_conv2d: the stem (Cin = 1) has Cout = 32, stride 1, no shortcut / residual, ldx >= F (Cout=%d stride=%d ldx=%lld F=%d)",
                 a->Cout, a->stride, (long long)a->ldx, a->F);
-    SDK_REQUIRE((int64_t)a->B * a->F * a->T < (1ll << 31) / 32, "sdk_resnet_conv2d: image too large");
-    ProfScope ps(ctx, stream, SDK_K_RESNET_STEM, 2.0 * a->B * a->F * a->T * 32 * 9, 2.0 * a->B * a->F * a->T * (1 + 32));
+    // the kernel indexes in int64; only the grid size is int32: ceil_div((int)n, RN_NT) must not overflow
     const int64_t n = (int64_t)a->B * a->F * a->T;
+    SDK_REQUIRE(n < (1ll << 31) - RN_NT, "sdk_resnet_conv2d: image too large (stem: B*F*T=%lld output positions, at most 2^31 - %d)", (long long)n,
+                RN_NT + 1);
+    ProfScope ps(ctx, stream, SDK_K_RESNET_STEM, 2.0 * a->B * a->F * a->T * 32 * 9, 2.0 * a->B * a->F * a->T * (1 + 32));
     hipLaunchKernelGGL(f16 ? resnet_stem_kernel<true> : resnet_stem_kernel<false>, dim3((unsigned)ceil_div((int)n, RN_NT)), dim3(RN_NT), 0, st,
                        (const bf16_t*)a->x, a->ldx, (const bf16_t*)a->W, a->bias, (bf16_t*)a->y, a->B, a->F, a->T, (int)(a->flags & SDK_GEMM_RELU));
     SDK_LAUNCH_CHECK();
@@ -274,7 +276,8 @@ extern "C" int sdk_resnet_conv2d(sdk_ctx* ctx, const sdk_resnet_conv_args* a, vo
   SDK_REQUIRE(resnet_width_ok(a->Cin) && resnet_width_ok(a->Cout), "sdk_resnet_conv2d: Cin=%d Cout=%d (each 32, 64, 128 or 256; Cin = 1: the stem)",
               a->Cin, a->Cout);
   SDK_REQUIRE(((uintptr_t)a->x % 16) == 0 && ((uintptr_t)a->W % 16) == 0 && ((uintptr_t)a->y % 16) == 0 && ((uintptr_t)a->res % 16) == 0 &&
-              ((uintptr_t)a->sc % 16) == 0, "sdk_resnet_conv2d: x, W, sc, res and y must be 16-byte aligned");
+              ((uintptr_t)a->sc % 16) == 0, "sdk_resnet_conv2d: x, W, sc, res and y must be 16-byte aligned (x=%p W=%p sc=%p res=%p y=%p)",
+              (const void*)a->x, (const void*)a->W, (const void*)a->sc, (const void*)a->res, (const void*)a->y);
   SDK_REQUIRE(!(a->sc && a->res), "sdk_resnet_conv2d: a projection shortcut and an identity residual exclude each other");
   if (a->sc) {
     SDK_REQUIRE(resnet_width_ok(a->Csc) && (a->stride_sc == 1 || a->stride_sc == 2) && (a->Fsc - 1) / a->stride_sc + 1 == Fo &&

@@ -133,3 +133,18 @@ def conv_ref(x: torch.Tensor, wk: torch.Tensor, bias: torch.Tensor, stride: int,
     if res is not None:
         y = y + res.double()
     return torch.relu(y) if relu else y
+
+
+def tstp_stats(x: torch.Tensor) -> torch.Tensor:
+    """The temporal statistics pooling in float64 on the channel-last last map x [B, F, T, C] -> [B, 2 C F]: mean | sqrt(unbiased var + 1e-7)
+    over t, feature c F + f."""
+    x = x.double().permute(0, 3, 1, 2).reshape(x.shape[0], -1, x.shape[2])
+    return torch.cat([x.mean(dim=-1), torch.sqrt(x.var(dim=-1, unbiased=True) + 1e-7)], dim=1)
+
+
+def storage_ulp(v: torch.Tensor, bits: int) -> torch.Tensor:
+    """Spacing of the 2-byte storage format (bits = 8: bf16, 11: fp16) at |v|; fp16 keeps its subnormal spacing 2^-24 below 2^-14."""
+    _, e = torch.frexp(v.double().abs())
+    u = torch.ldexp(torch.ones_like(v, dtype=torch.float64), e - bits)
+    u = torch.where(v == 0, torch.zeros_like(u), u)
+    return u.clamp_min(2.0 ** -24) if bits == 11 else u
