@@ -32,6 +32,7 @@
  *     sdk_affinity_workspace_bytes  sdk_affinity_topk                                                   k4
  *     sdk_affinity_matvec_workspace_bytes  sdk_affinity_matvec  sdk_rows_gram_workspace_bytes  sdk_rows_gram
  *     sdk_rows_apply  sdk_chol_inverse  sdk_rows_unit  sdk_kmeans_mindist  sdk_kmeans_assign            k6 (driven by cluster.py)
+ *     sdk_centroid_linkage_workspace_bytes  sdk_centroid_linkage                                    k6 threshold path (cluster.agglomerative_cluster)
  * BUILDING BLOCKS AND KNOBS - exported for the parity tests and the A/B tools, free to change between rounds, not for binding:
  *     sdk_conv_gemm*  sdk_colstats_finish  sdk_res2net_chain*  sdk_se_*  sdk_asp_*  sdk_rows_fc  (pieces of sdk_ecapa_forward)
  *     sdk_resnet_conv2d  (piece of sdk_resnet_forward)
@@ -496,6 +497,23 @@ int sdk_rows_unit(sdk_ctx* ctx, const float* X, int n, int k, float* Y, void* st
 int sdk_kmeans_mindist(sdk_ctx* ctx, const float* R, int n, int k, const float* centre, float* d2, int first, void* stream);
 int sdk_kmeans_assign(sdk_ctx* ctx, const float* R, int n, int k, const float* centres, int kc, int32_t* label,
                       float* dist2, float* part_sum, int32_t* part_cnt, void* stream);
+/* ---- k6, threshold path: centroid-linkage agglomerative clustering (scipy.cluster.hierarchy.linkage(X, "centroid"): same arithmetic in
+ *      float64, same layout and numbering).  G independent problems; problem g is rows offsets[g] .. offsets[g+1] of E (fp32 [N_total, dim],
+ *      row stride ldE; unit rows as sdk_l2norm writes them), n_g = offsets[g+1] - offsets[g] rows, 1 <= n_g <= 65536, 1 <= dim <= 2048.
+ *      offsets is HOST memory [G + 1], strictly increasing from 0.
+ *   Z        DEVICE float64 [N_total - G][4]: problem g's n_g - 1 rows start at row offsets[g] - g.  Row t = (id_a, id_b, height, count):
+ *            leaves are 0 .. n_g - 1, merge t creates id n_g + t, id_a < id_b, rows in merge order (centroid heights are not monotone).
+ *   status   DEVICE int32 [G]: 0 ok; 1 = a non-finite row (or distance) in the problem: none of its Z rows is written; 2 = the merge loop
+ *            found no finite pair (non-finite update).  The caller reads it at its next synchronisation.
+ *   Distances: d_ij = sqrt(sum_c (e_ic - e_jc)^2) in float64 (difference form).  Merge x into y (x = the lower row of the closest pair; ties:
+ *   lowest row, then lowest neighbour): d(k, y') = sqrt(max(0, ((n_x d_kx^2 + n_y d_ky^2) - n_x n_y d_xy^2 / (n_x + n_y)) / (n_x + n_y))),
+ *   scipy's centroid Lance-Williams form; the max(0, .) is ours (scipy can return NaN there).  One workgroup per problem runs the merges.
+ *   workspace: sdk_centroid_linkage_workspace_bytes (8 n_g^2 bytes of distances per problem + O(n_g)), 256-byte aligned; 0 for arguments
+ *   the call refuses.  Every refusal returns non-zero, names the value in sdk_last_error() and launches nothing.
+ *   sdk_set_option "ahc_distances_only" 1 (bench knob, tools/ahc_bench.py): stop after the distance and nearest-neighbour kernels (Z not written). */
+size_t sdk_centroid_linkage_workspace_bytes(const int32_t* offsets, int G, int dim);
+int sdk_centroid_linkage(sdk_ctx* ctx, const float* E, int ldE, int dim, const int32_t* offsets, int G, double* Z, int32_t* status,
+                         void* workspace, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -341,6 +341,29 @@ class Backend(EmbeddingBackend):
         sc = np.stack([parts[S][2][row] for _, S, row, _, _ in wins])
         return idx, sc, [(ri, a, b) for ri, _, _, a, b in wins]
 
+    def cluster_ranges(self, samples: np.ndarray, ranges: List[Tuple[float, float]], threshold: float = 0.7045654963945799,
+                       min_cluster_size: int = 12):
+        """Speaker labels for a transcript's segments with no enrolled profiles: embed_ranges -> cluster.agglomerative_cluster (centroid
+        linkage on the GPU, flat cut at `threshold`, clusters under min_cluster_size folded into the nearest large one).
+        Returns (labels [W] int32 per window, windows [(range index, start s, end s)], range_labels [len(ranges)] int32): a range takes the
+        majority label of its windows (ties -> the smaller label), -1 when it has no window.
+        The default threshold and size are PyAnnote 3.1's, tuned for ITS trained ResNet34 embedding (SDK_MODEL=resnet34 with the trained
+        weights); with another family or the synthetic weights pass a threshold of your own."""
+        if self.lite:
+            raise ValueError("cluster_ranges needs the torch engine: not available with SDK_NO_TORCH=1")
+        from .cluster import agglomerative_cluster
+        E, _, _, wins, _ = self.embed_ranges(samples, ranges)
+        range_labels = np.full(len(ranges), -1, dtype=np.int32)
+        if not wins:
+            return np.zeros(0, np.int32), [], range_labels
+        labels = agglomerative_cluster(self.engine(), E, threshold, min_cluster_size).labels
+        per = {}
+        for (ri, _, _), lab in zip(wins, labels):
+            per.setdefault(ri, []).append(int(lab))
+        for ri, labs in per.items():
+            range_labels[ri] = int(np.argmax(np.bincount(labs)))        # first maximum = the smaller label
+        return labels, wins, range_labels
+
     # ---- a2: enroll (base.py:107-128) ---------------------------------------------------------
     def enroll_speaker(self, audio_path: Path, segments: Optional[List[Tuple[float, float]]] = None) -> Dict[str, Any]:
         if segments:           # the caller vouches that each range is this speaker: true-length windows, never widened

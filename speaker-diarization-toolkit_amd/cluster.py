@@ -218,3 +218,108 @@ def _kmeans(provider, comm: _Comm, R: torch.Tensor, lo: int, n_total: int, k: in
         C = torch.where(cnts[:, None] > 0, sums / cnts.clamp_min(1.0)[:, None], C.double()).float().contiguous()
     labels, _, _, _ = provider.kmeans_assign(R, C, want_sums=False)
     return labels
+
+
+# ------------------------------------------------------------------ k6, threshold path: centroid-linkage agglomerative clustering
+PYANNOTE_THRESHOLD = 0.7045654963945799        # PyAnnote 3.1's published default for ITS trained ResNet34 embedding
+PYANNOTE_MIN_CLUSTER_SIZE = 12
+
+
+@dataclass
+class AgglomerativeResult:
+    labels: np.ndarray            # [N] int32 canonical (order of first appearance)
+    linkage: np.ndarray           # [N - 1, 4] float64, scipy's layout and numbering (Engine.centroid_linkage)
+    n_large: int                  # clusters at least the effective minimum size after the cut (all clusters when n_clusters is given)
+
+
+def _flat_partition(Z: np.ndarray, n: int, n_merges: int) -> np.ndarray:
+    """Canonical labels of the partition formed by the first n_merges rows of Z (union-find over node ids)."""
+    parent = np.arange(2 * n - 1 if n > 0 else 0, dtype=np.int64)
+
+    def find(a):
+        r = a
+        while parent[r] != r:
+            r = parent[r]
+        while parent[a] != r:
+            parent[a], a = r, parent[a]
+        return r
+    for t in range(n_merges):
+        a, b = int(Z[t, 0]), int(Z[t, 1])
+        parent[find(a)] = n + t
+        parent[find(b)] = n + t
+    if n == 0:
+        return np.zeros(0, np.int32)
+    roots = np.array([find(i) for i in range(n)], dtype=np.int64)
+    return canonical_labels(roots).astype(np.int32)
+
+
+def fcluster_distance(Z: np.ndarray, t: float) -> np.ndarray:
+    """The flat cut of linkage Z at distance t: canonical labels of the partition formed by the merges BEFORE the first row whose height
+    exceeds t (numpy only).
+
+    For a linkage made by repeated global-minimum merges (Engine.centroid_linkage, scipy's centroid linkage) this equals
+    scipy.cluster.hierarchy.fcluster(Z, t, "distance") even with inversions (non-monotone heights).  Let row k be the first with height > t.
+      - Every earlier merge is <= t: each cluster formed by rows 0 .. k-1 has no height above t inside it, so the cut keeps it whole.
+      - At step k every live pair is > t: row k was the global minimum over the clusters alive then.
+      - Every later node contains a merge above t: following it down, the first merge made at step >= k joined clusters alive at step k
+        (or nodes made of them), at a height > t.  So no later node is kept whole, and no two of the step-k clusters are joined.
+    """
+    Z = np.asarray(Z, dtype=np.float64)
+    n = Z.shape[0] + 1
+    above = np.flatnonzero(Z[:, 2] > t)
+    k = int(above[0]) if above.size else n - 1
+    return _flat_partition(Z, n, k)
+
+
+def agglomerative_cluster(provider, E, threshold: float = PYANNOTE_THRESHOLD, min_cluster_size: int = PYANNOTE_MIN_CLUSTER_SIZE,
+                          n_clusters: Optional[int] = None) -> AgglomerativeResult:
+    """Speaker clusters without knowing their number: centroid linkage on the unit rows E ([N, d] fp32 on the provider's device; the linkage
+    runs in libsdk_hip.so, Engine.centroid_linkage), a flat cut at `threshold`, small clusters folded into the nearest large one.
+
+    This restates the threshold path of PyAnnote 3.1's AgglomerativeClustering as stated here (written from its published description, not
+    from its code; the tests pin THIS rule):
+      1. the effective minimum size is min(min_cluster_size, max(1, round(0.1 N)))  (Python's round: half to even);
+      2. clusters of the cut with at least that many rows are large;
+      3. no large cluster: every label is 0;
+      4. otherwise every small cluster joins the large cluster whose centroid (mean of its unit rows) is nearest in 1 - cos, ties to the
+         large cluster that comes first in label order;
+      5. N == 1 gives [0];
+      6. n_clusters given: the partition after the first N - n_clusters merges, min_cluster_size not applied.  PyAnnote's search over
+         dendrogram levels for a forced count is not reproduced.
+    Labels are canonical (order of first appearance)."""
+    N = int(E.shape[0])
+    if N == 0:
+        return AgglomerativeResult(np.zeros(0, np.int32), np.zeros((0, 4)), 0)
+    Z = provider.centroid_linkage(E).cpu().numpy() if N > 1 else np.zeros((0, 4))
+    if N == 1:
+        return AgglomerativeResult(np.zeros(1, np.int32), Z, 1)
+    if n_clusters is not None:
+        k = min(max(int(n_clusters), 1), N)
+        lab = _flat_partition(Z, N, N - k)
+        return AgglomerativeResult(lab, Z, int(lab.max()) + 1)
+    Eh = E.detach().cpu().numpy().astype(np.float64) if isinstance(E, torch.Tensor) else np.asarray(E, dtype=np.float64)
+    lab, n_large = fold_small_clusters(Eh, fcluster_distance(Z, threshold), min_cluster_size)
+    return AgglomerativeResult(lab, Z, n_large)
+
+
+def fold_small_clusters(E: np.ndarray, labels: np.ndarray, min_cluster_size: int):
+    """Rules 1-4 of agglomerative_cluster on a flat partition (canonical labels) of the rows E (float64): -> (canonical labels, large count)."""
+    N = labels.shape[0]
+    eff = min(int(min_cluster_size), max(1, round(0.1 * N)))
+    K = int(labels.max()) + 1
+    sizes = np.bincount(labels, minlength=K)
+    large = np.flatnonzero(sizes >= eff)
+    if large.size == 0:
+        return np.zeros(N, np.int32), 0
+    if large.size == K:
+        return canonical_labels(labels).astype(np.int32), K
+    cent = np.zeros((K, E.shape[1]))
+    np.add.at(cent, labels, E)
+    cent /= sizes[:, None]
+    unit = cent / np.linalg.norm(cent, axis=1, keepdims=True).clip(1e-300)
+    small = np.flatnonzero(sizes < eff)
+    dist = 1.0 - unit[small] @ unit[large].T          # [small, large] cosine distance
+    to = large[np.argmin(dist, axis=1)]                # first minimum: the large cluster first in label order
+    remap = np.arange(K)
+    remap[small] = to
+    return canonical_labels(remap[labels]).astype(np.int32), int(large.size)

@@ -44,6 +44,7 @@ struct sdk_ctx {
   int aff_boundary_pen = 0;       // k = 1 coarse pass: cost of a group boundary inside a workgroup's range, in stages (affinity_rowcol.hip Geom.pen; 0 = equal unit counts)
   int chol_pivot_rtol_ppb = 1000; // sdk_chol_inverse: a pivot <= this fraction (in 1e-9) of its diagonal entry sets the sticky not_spd flag (default 1e-6: cond(Y) > ~1e3)
   int chol_shift_ppb = 0;         // sdk_chol_inverse: shifted CholeskyQR, G + s I with s = this fraction (in 1e-9) of the mean diagonal entry (0 = off)
+  bool ahc_distances_only = false;  // bench knob (tools/ahc_bench.py): sdk_centroid_linkage stops after the distance and nearest-neighbour kernels
   int aff_variant = 0;            // A/B knob: coarse-pass plan of the row/column kernel (0 = cost model, 7 = range plan, 8 / 12 / 13 = block plan; affinity_rowcol.hip)
   std::vector<const void*> lds_optin;   // kernels of THIS context's device already opted in to > 64 KiB dynamic LDS
   std::vector<sdk_prof_rec> prof;
@@ -71,6 +72,10 @@ int res2net_chain_launch(sdk_ctx* ctx, const uint16_t* U, int64_t ldu, uint16_t*
 
 // resnet.hip: temporal statistics pooling of the ResNet34 family's last map (internal; sdk_resnet_forward)
 int resnet_tstp_impl(sdk_ctx* ctx, const uint16_t* x, int B, int F, int T, int C, float* out, void* stream, bool f16);
+
+// ahc.hip: centroid-linkage agglomerative clustering (sdk_centroid_linkage checks the arguments, then calls these)
+size_t ahc_workspace_bytes(const int32_t* offsets, int G);
+int ahc_launch(sdk_ctx* ctx, const float* E, int ldE, int dim, const int32_t* offsets, int G, double* Z, int32_t* status, void* ws, void* stream);
 
 struct ProfScope {   // brackets one kernel launch with two events when profiling is enabled
   sdk_ctx* c; hipStream_t s; size_t slot; bool on;

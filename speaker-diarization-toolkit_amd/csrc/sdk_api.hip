@@ -128,6 +128,7 @@ extern "C" int sdk_set_option(sdk_ctx* ctx, const char* name, int value) {
   if (strcmp(name, "affinity_whole_groups") == 0) return 0;      // (round-3 knob, measured behind and removed in round 5: accepted and ignored)
   if (strcmp(name, "chol_pivot_rtol_ppb") == 0) { ctx->chol_pivot_rtol_ppb = value < 0 ? 0 : value; return 0; }
   if (strcmp(name, "chol_shift_ppb") == 0) { ctx->chol_shift_ppb = value < 0 ? 0 : value; return 0; }
+  if (strcmp(name, "ahc_distances_only") == 0) { ctx->ahc_distances_only = value != 0; return 0; }
   sdk_set_error("sdk_set_option: unknown option '%s'", name);
   return 2;
 }
@@ -725,4 +726,43 @@ extern "C" int sdk_resnet_forward(sdk_ctx* ctx, const void* wblob, const sdk_res
   if (int rc = resnet_tstp_impl(ctx, X, B, F, Tl, C, stats, stream, f16)) return rc;
   return sdk_rows_fc(ctx, stats, 2 * C * F, nullptr, nullptr, (const float*)(wb + d->off[66]), (const float*)(wb + d->off[67]), emb, d->embed_dim, B,
                      2 * C * F, d->embed_dim, 0, stream);
+}
+
+// ------------------------------------------------------------------------------ centroid-linkage agglomerative clustering (ahc.hip)
+namespace {
+constexpr int AHC_MAX_N = 65536;    // the condensed distance count of one problem stays under 2^31
+constexpr int AHC_MAX_DIM = 2048;
+// the host-side refusals shared by both entry points: 0 = the offsets describe G problems the kernels serve
+int check_ahc_offsets(const char* fn, const int32_t* offsets, int G, int dim) {
+  SDK_REQUIRE(offsets, "%s: offsets is null", fn);
+  SDK_REQUIRE(G >= 1, "%s: G=%d (at least one problem)", fn, G);
+  SDK_REQUIRE(dim >= 1 && dim <= AHC_MAX_DIM, "%s: dim=%d (served: 1 .. %d)", fn, dim, AHC_MAX_DIM);
+  SDK_REQUIRE(offsets[0] == 0, "%s: offsets[0]=%d (the first problem starts at row 0)", fn, offsets[0]);
+  for (int g = 0; g < G; ++g) {
+    const int64_t n = (int64_t)offsets[g + 1] - offsets[g];
+    SDK_REQUIRE(n >= 1, "%s: offsets not increasing at problem %d (offsets[%d]=%d, offsets[%d]=%d: every problem needs a row)", fn, g, g, offsets[g],
+                g + 1, offsets[g + 1]);
+    SDK_REQUIRE(n <= AHC_MAX_N, "%s: problem %d has n=%lld rows (at most %d)", fn, g, (long long)n, AHC_MAX_N);
+  }
+  return 0;
+}
+}  // namespace
+
+extern "C" size_t sdk_centroid_linkage_workspace_bytes(const int32_t* offsets, int G, int dim) {
+  if (check_ahc_offsets("sdk_centroid_linkage_workspace_bytes", offsets, G, dim)) return 0;
+  return ahc_workspace_bytes(offsets, G);
+}
+
+extern "C" int sdk_centroid_linkage(sdk_ctx* ctx, const float* E, int ldE, int dim, const int32_t* offsets, int G, double* Z, int32_t* status,
+                                    void* workspace, size_t ws_bytes, void* stream) {
+  SDK_REQUIRE(ctx && E && Z && status && workspace, "sdk_centroid_linkage: null argument (ctx=%p E=%p Z=%p status=%p workspace=%p)", (void*)ctx,
+              (const void*)E, (void*)Z, (void*)status, workspace);
+  if (int rc = check_ahc_offsets("sdk_centroid_linkage", offsets, G, dim)) return rc;
+  SDK_REQUIRE(ldE >= dim, "sdk_centroid_linkage: ldE=%d < dim=%d", ldE, dim);
+  SDK_REQUIRE((uintptr_t)E % 4 == 0 && (uintptr_t)Z % 8 == 0 && (uintptr_t)status % 4 == 0 && (uintptr_t)workspace % 256 == 0,
+              "sdk_centroid_linkage: misaligned pointer (E=%p needs 4, Z=%p needs 8, status=%p needs 4, workspace=%p needs 256 bytes)",
+              (const void*)E, (void*)Z, (void*)status, workspace);
+  const size_t need = ahc_workspace_bytes(offsets, G);
+  SDK_REQUIRE(ws_bytes >= need, "sdk_centroid_linkage: workspace of %zu bytes, %zu needed", ws_bytes, need);
+  return ahc_launch(ctx, E, ldE, dim, offsets, G, Z, status, workspace, stream);
 }

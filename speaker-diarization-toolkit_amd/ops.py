@@ -631,6 +631,41 @@ class Engine:
                                          _ptr(ps), _ptr(pc), _stream()), "sdk_kmeans_assign")
         return lab, d2, ps, pc
 
+    # ------------------------------------------------------------------ k6 (threshold path: centroid-linkage agglomerative clustering)
+    def centroid_linkage(self, E: torch.Tensor, offsets=None) -> torch.Tensor:
+        """E [N, d] fp32 unit rows (device) -> Z float64 [N - G, 4] (device): scipy's centroid linkage of every problem, in its layout and
+        numbering.  offsets (host, G + 1 strictly increasing row bounds; None = one problem of all N rows): problem g's n_g - 1 rows start at
+        row offsets[g] - g.  Raises ValueError naming the problem when one holds a non-finite row (its rows of Z are then not written; the
+        exception carries .linkage, with the other problems' rows valid, and .status [G])."""
+        _need(E, torch.float32, "E")
+        if E.dim() != 2 or E.stride(1) != 1:
+            E = E.contiguous()
+        N, d = E.shape
+        off = np.asarray([0, N] if offsets is None else offsets, dtype=np.int64)
+        if off.ndim != 1 or off.size < 2 or off[0] != 0 or off[-1] != N:
+            raise ValueError(f"centroid_linkage: offsets must run from 0 to N = {N}, got {off.tolist()[:8]}")
+        off32 = np.ascontiguousarray(off.astype(np.int32))
+        G = off32.size - 1
+        op = off32.ctypes.data_as(C.POINTER(C.c_int32))
+        nbytes = self.lib.sdk_centroid_linkage_workspace_bytes(op, G, d)
+        if nbytes == 0:
+            raise SdkError(f"sdk_centroid_linkage_workspace_bytes: {self.lib.sdk_last_error().decode()}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        Zbuf = torch.empty((max(N - G, 1), 4), dtype=torch.float64, device=self.device)   # never a null pointer (G single-row problems: no rows)
+        status = torch.empty((G,), dtype=torch.int32, device=self.device)
+        check(self.lib.sdk_centroid_linkage(self.ctx, E.data_ptr(), E.stride(0), d, op, G, Zbuf.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                                            nbytes, _stream()), "sdk_centroid_linkage")
+        Z = Zbuf[:N - G]
+        st = status.cpu().numpy()
+        bad = np.flatnonzero(st)
+        if bad.size:
+            g = int(bad[0])
+            err = ValueError(f"centroid_linkage: problem {g} (rows {int(off[g])} .. {int(off[g + 1])}) has a non-finite row or distance "
+                             f"(status {int(st[g])}); problems with one: {bad.tolist()[:16]}")
+            err.linkage, err.status = Z, st             # the other problems' rows of Z are valid
+            raise err
+        return Z
+
     def asp_fused(self, ah, w2, b2, h, B, T, kblocked=False):
         """kblocked: h is [Cm / 64, B*T, 64] (to_kblocked) - the per-segment form only (sdk_asp_kblocked_ok)."""
         if kblocked:

@@ -25,12 +25,18 @@ class ShardResult:
     best_score: np.ndarray              # [n_local, k] fp32 cosine
     cluster_labels: Optional[np.ndarray] = None      # [n_total] int32 canonical labels (same on every rank)
     eigenvalues: Optional[np.ndarray] = None
+    linkage: Optional[np.ndarray] = None             # [n_total - 1, 4] float64 centroid linkage (ahc_threshold given)
 
 
 def run_shard(engine, pcm_local: torch.Tensor, profiles: torch.Tensor, n_total: Optional[int] = None, k: int = 1,
-              threshold: Optional[float] = None, n_clusters: int = 0, cluster_iters: int = 30, group=None) -> ShardResult:
+              threshold: Optional[float] = None, n_clusters: int = 0, cluster_iters: int = 30, group=None,
+              ahc_threshold: Optional[float] = None, ahc_min_cluster_size: int = 12) -> ShardResult:
     """pcm_local [n_local, S] int16 on the engine's device (this rank's rows under dist.shard_bounds);
-    profiles [P, 192] fp32 on the device (replicated).  n_clusters > 0 adds the global spectral clustering."""
+    profiles [P, 192] fp32 on the device (replicated).  n_clusters > 0 adds the global spectral clustering; ahc_threshold adds the
+    agglomerative clustering instead (cluster.agglomerative_cluster: no cluster count needed): the rows are all-gathered and every rank
+    clusters all of them, so the labels are identical on every rank."""
+    if n_clusters > 0 and ahc_threshold is not None:
+        raise ValueError(f"run_shard: n_clusters={n_clusters} (spectral) and ahc_threshold={ahc_threshold} (agglomerative) exclude each other")
     E, Eb, re = engine.embed_pcm(pcm_local)
     Pn, Pb, rp = engine.l2norm(profiles)
     idx, sc = engine.affinity_topk(E, Eb, re, Pn, Pb, rp.max().reshape(1), k=min(k, profiles.shape[0]))
@@ -42,4 +48,9 @@ def run_shard(engine, pcm_local: torch.Tensor, profiles: torch.Tensor, n_total: 
         n_total = n_total if n_total is not None else E.shape[0]
         res = scluster.spectral_cluster(engine, E, Eb, n_total, n_clusters, n_iter=cluster_iters, group=group)
         out.cluster_labels, out.eigenvalues = res.labels, res.eigenvalues
+    elif ahc_threshold is not None:
+        n_total = n_total if n_total is not None else E.shape[0]
+        E_all = scluster._Comm(group).gather_rows(E.contiguous(), n_total)
+        res = scluster.agglomerative_cluster(engine, E_all, float(ahc_threshold), ahc_min_cluster_size)
+        out.cluster_labels, out.linkage = res.labels, res.linkage
     return out
