@@ -91,9 +91,10 @@ int sdk_stream_synchronize(sdk_ctx* ctx, void* stream);
  * NOT a knob - a numerical contract: "precision" 0 (default: bf16 operands, bf16 layer-boundary storage; PCM -> score within ~4e-3 of
  * the fp32 model, ~9e-4 with the host's bias correction) / 1 (fp16 hi+lo planes, three MFMAs per product: within 1e-5, ~3x the GEMM time) /
  * 2 (round 5: ONE fp16 plane - the default schedule with fp16 instead of bf16 storage and MFMA operands: ~5e-4, ~1.7e-4 bias-corrected, ~0.96x the
- * default's throughput; ECAPA-TDNN forward only).  The OPTION is only the default of the entry points that have no format argument: the output
- * format of sdk_fbank / sdk_fbank_windows (bf16 / planes / fp16; sdk_fbank_fmt takes it per call) and the element format the stand-alone sweeps
- * (sdk_se_gate_residual, sdk_asp_stats, sdk_asp_pool, sdk_asp_fused*, sdk_res2net_chain) read and write.  The forwards take the contract from the
+ * default's throughput; the ECAPA-TDNN and x-vector forwards).  The OPTION is only the default of the entry points that have no format argument: the
+ * output format of sdk_fbank / sdk_fbank_windows (bf16 / planes / fp16; sdk_fbank_fmt takes it per call) and the element format the stand-alone
+ * sweeps (sdk_se_gate_residual, sdk_asp_stats, sdk_asp_pool, sdk_asp_fused*, sdk_res2net_chain) read and write; each of them has a _fmt sibling
+ * that takes the format (0: bf16, 2: fp16) per call instead.  The forwards take the contract from the
  * weight blob's descriptor (sdk_ecapa_desc.precision), sdk_conv_gemm from its flags (SDK_GEMM_F16): per call, no shared state. */
 int sdk_set_option(sdk_ctx* ctx, const char* name, int value);
 /* Diagnostics: "stamps" = device buffer [workgroups][64] of uint64 that the affinity kernel (tools/aff_timeline.py) and the
@@ -245,12 +246,20 @@ int sdk_res2net_chain_max_frames(void);
 int sdk_res2net_chain(sdk_ctx* ctx, const uint16_t* U, int64_t ldu, uint16_t* R, int64_t ldr, const uint16_t* const* W,
                       const float* const* bias, const float* const* scale, const float* const* shift, int nconv,
                       int B, int T, int dil, void* stream);
+/* the same with the element format of U, R and W as an argument (0: bf16, 2: fp16) instead of the context's default */
+int sdk_res2net_chain_fmt(sdk_ctx* ctx, const uint16_t* U, int64_t ldu, uint16_t* R, int64_t ldr, const uint16_t* const* W,
+                          const float* const* bias, const float* const* scale, const float* const* shift, int nconv,
+                          int B, int T, int dil, int precision, void* stream);
 size_t sdk_se_workspace_bytes(int B, int C, int Cse);   /* fp32 [B,C] means + [B,Cse] hidden + [B,C] gates */
 int sdk_se_gate_residual(sdk_ctx* ctx, const uint16_t* z, int64_t ldz, const uint16_t* x, int64_t ldx,
                          const float* w1t, const float* b1, const float* w2t, const float* b2,
                          uint16_t* out, int64_t ldo, int B, int T, int C, int Cse,
                          const float* mean_in,      /* optional [B, C] squeeze means already computed (fused GEMM epilogue) */
                          void* ws, size_t ws_bytes, void* stream);   /* ws may be NULL: one-kernel-per-segment form */
+int sdk_se_gate_residual_fmt(sdk_ctx* ctx, const uint16_t* z, int64_t ldz, const uint16_t* x, int64_t ldx,
+                             const float* w1t, const float* b1, const float* w2t, const float* b2,
+                             uint16_t* out, int64_t ldo, int B, int T, int C, int Cse, const float* mean_in,
+                             void* ws, size_t ws_bytes, int precision, void* stream);   /* z, x, out: 0 bf16, 2 fp16 */
 
 /* Attentive statistics pooling pieces.
  *   sdk_asp_stats : ctx[b, 0:C] = mean_t h, ctx[b, C:2C] = sqrt(max(var_t h, 1e-12))   fp32
@@ -266,17 +275,23 @@ int sdk_rows_fc(sdk_ctx* ctx, const float* in, int64_t ldin, const float* in_sca
                 int B, int Cin, int Nout, int act, void* stream);
 int sdk_asp_pool(sdk_ctx* ctx, const float* logits, int64_t ldl, const uint16_t* h, int64_t ldh,
                  int B, int T, int C, float* pooled, void* stream);
+int sdk_asp_pool_fmt(sdk_ctx* ctx, const float* logits, int64_t ldl, const uint16_t* h, int64_t ldh,
+                     int B, int T, int C, float* pooled, int precision, void* stream);   /* h: 0 bf16, 2 fp16 */
 /* Fused form of (attention-logit GEMM + sdk_asp_pool) for T <= sdk_asp_fused_max_frames(): the fp32
  * logits stay in accumulator registers.  ah [B*T, A=128] bf16 attention hidden, w2 [C, A] bf16, b2 [C]. */
 int sdk_asp_fused_max_frames(void);
 int sdk_asp_fused(sdk_ctx* ctx, const uint16_t* ah, int64_t ldah, const uint16_t* w2, const float* b2,
                   const uint16_t* h, int64_t ldh, int B, int T, int C, int A, float* pooled, void* stream);
+int sdk_asp_fused_fmt(sdk_ctx* ctx, const uint16_t* ah, int64_t ldah, const uint16_t* w2, const float* b2,
+                      const uint16_t* h, int64_t ldh, int B, int T, int C, int A, float* pooled, int precision, void* stream);   /* ah, w2, h: 0 bf16, 2 fp16 */
 /* The same with h in the K-blocked layout [C / 64][B*T][64] (SDK_GEMM_C_KBLOCKED above).  Only the per-segment form reads it: where
  * sdk_asp_kblocked_ok(ctx, T, C) is 0 (short or long windows, option asp_per_segment off) the call is an error and the caller keeps h row-major.
  * Bit-identical to sdk_asp_fused on the same values. */
 int sdk_asp_kblocked_ok(sdk_ctx* ctx, int T, int C);
 int sdk_asp_fused_kblocked(sdk_ctx* ctx, const uint16_t* ah, int64_t ldah, const uint16_t* w2, const float* b2,
                            const uint16_t* h, int B, int T, int C, int A, float* pooled, void* stream);
+int sdk_asp_fused_kblocked_fmt(sdk_ctx* ctx, const uint16_t* ah, int64_t ldah, const uint16_t* w2, const float* b2,
+                               const uint16_t* h, int B, int T, int C, int A, float* pooled, int precision, void* stream);
 
 /* ---- PRECISE MODE (sdk_set_option "precision" 1; north_star: cosine scores within 1e-5 of the fp32 model, which bf16 operands miss
  *      by 4e-3 - profiles/r03_error_budget.md).  Tensors the default mode rounds to bf16 travel as fp16 hi + lo PLANES: a [rows, C]

@@ -117,16 +117,21 @@ SIGNATURES = {
     "sdk_colstats_finish": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "sdk_res2net_chain_max_frames": (_i, []),
     "sdk_res2net_chain": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "sdk_res2net_chain_fmt": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "sdk_se_workspace_bytes": (_sz, [_i, _i, _i]),
     "sdk_se_gate_residual": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "sdk_se_gate_residual_fmt": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _sz, _i, _vp]),
     "sdk_asp_stats": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp]),
     "sdk_asp_stats_fmt": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _i, _vp]),
     "sdk_rows_fc": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "sdk_asp_pool": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _vp, _vp]),
+    "sdk_asp_pool_fmt": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _vp, _i, _vp]),
     "sdk_asp_fused_max_frames": (_i, []),
     "sdk_asp_fused": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp, _vp]),
+    "sdk_asp_fused_fmt": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp, _i, _vp]),
     "sdk_asp_kblocked_ok": (_i, [_vp, _i, _i]),
     "sdk_asp_fused_kblocked": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "sdk_asp_fused_kblocked_fmt": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "sdk_ecapa_workspace_bytes": (_sz, [C.POINTER(EcapaDesc), _i, _i]),
     "sdk_ecapa_forward": (_i, [_vp, _vp, C.POINTER(EcapaDesc), _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "sdk_ecapa_calib_floats": (_sz, [C.POINTER(EcapaDesc), _i]),

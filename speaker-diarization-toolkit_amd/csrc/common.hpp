@@ -141,15 +141,20 @@ __device__ __forceinline__ uint32_t pack2(float a, float b) {
   return __builtin_bit_cast(uint32_t, t);
 }
 // the same for a 2-byte storage type chosen at compile time: bf16 (default contract) or fp16 (the single-plane fp16 contract, round 5); fp16 values
-// are clamped to the format's finite range first (a saturated activation, never an inf that turns the next layer into NaN)
+// are clamped to the format's finite range first (a saturated activation, never an inf that turns the next layer into NaN).  A NaN stays NaN, as
+// in bf16: fmaxf(NaN, x) is x, so the clamp alone would store it as -65504, a finite value no later non-finite check could see.
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float sat_f16(float a) {
+  const float c = fminf(fmaxf(a, -65504.f), 65504.f);
+  return a != a ? a : c;
+}
 template <bool F16>
 __device__ __forceinline__ uint32_t pack2t(float a, float b) {
   if constexpr (F16) {
     f16x2_t t;
-    t[0] = (_Float16)fminf(fmaxf(a, -65504.f), 65504.f);
-    t[1] = (_Float16)fminf(fmaxf(b, -65504.f), 65504.f);
+    t[0] = (_Float16)sat_f16(a);
+    t[1] = (_Float16)sat_f16(b);
     return __builtin_bit_cast(uint32_t, t);
   } else {
     return pack2(a, b);
@@ -219,6 +224,9 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
 }
+
+// the variance floor of every std output: max(v, 1e-12) that keeps a NaN (fmaxf(NaN, 1e-12) is 1e-12: a NaN frame would leave a finite std)
+__device__ __forceinline__ float var_floor(float v) { return v < 1e-12f ? 1e-12f : v; }
 
 // reflect (no edge repeat) t into [0, T); valid for -T < t < 2T-1
 __device__ __forceinline__ int reflect_idx(int t, int T) {

@@ -966,7 +966,7 @@ __global__ __launch_bounds__(256) void colstats_finish_kernel(const float* __res
     out[(int64_t)b * N + n] = mean;
   } else {
     out[(int64_t)b * 2 * N + n] = mean;
-    out[(int64_t)b * 2 * N + N + n] = sqrtf(fmaxf(q * invT - mean * mean, 1e-12f));
+    out[(int64_t)b * 2 * N + N + n] = sqrtf(var_floor(q * invT - mean * mean));
   }
 }
 

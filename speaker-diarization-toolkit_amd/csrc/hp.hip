@@ -764,7 +764,7 @@ __global__ __launch_bounds__(256) void asp_stats_hp_kernel(const uint16_t* __res
       const float a = (red[0][0][c8 * 8 + e] + red[1][0][c8 * 8 + e]) * invT;
       const float q = (red[0][1][c8 * 8 + e] + red[1][1][c8 * 8 + e]) * invT;
       out[(int64_t)blockIdx.x * 2 * C + cbase + e] = K[e] + a;
-      out[(int64_t)blockIdx.x * 2 * C + C + cbase + e] = sqrtf(fmaxf(q - a * a, 1e-12f));
+      out[(int64_t)blockIdx.x * 2 * C + C + cbase + e] = sqrtf(var_floor(q - a * a));
     }
   }
 }
@@ -794,7 +794,7 @@ __global__ __launch_bounds__(256) void asp_pool_hp_kernel(const float* __restric
   }
   const float a = s1 / se, q = s2 / se;
   pooled[(int64_t)blockIdx.x * 2 * C + c] = K + a;
-  pooled[(int64_t)blockIdx.x * 2 * C + C + c] = sqrtf(fmaxf(q - a * a, 1e-12f));
+  pooled[(int64_t)blockIdx.x * 2 * C + C + c] = sqrtf(var_floor(q - a * a));
 }
 
 }  // namespace

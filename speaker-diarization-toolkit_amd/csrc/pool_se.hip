@@ -158,7 +158,7 @@ __global__ __launch_bounds__(NT) void asp_stats_kernel(const bf16_t* __restrict_
     for (int e = 0; e < 8; ++e) {
       const float a = (red[0][0][c8 * 8 + e] + red[1][0][c8 * 8 + e]) * invT;
       const float q = (red[0][1][c8 * 8 + e] + red[1][1][c8 * 8 + e]) * invT;
-      const float var = fmaxf(q - a * a, 1e-12f);
+      const float var = var_floor(q - a * a);
       out[(int64_t)blockIdx.x * 2 * C + cbase + e] = K[e] + a;
       out[(int64_t)blockIdx.x * 2 * C + C + cbase + e] = sqrtf(var);
     }
@@ -452,7 +452,7 @@ __global__ __launch_bounds__(NT) void asp_pool_kernel(const float* __restrict__ 
   if (g == 0) {
     s2 = (red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]);
     pooled[(int64_t)blockIdx.x * 2 * C + c] = mu;
-    pooled[(int64_t)blockIdx.x * 2 * C + C + c] = sqrtf(fmaxf(s2 / l, 1e-12f));
+    pooled[(int64_t)blockIdx.x * 2 * C + C + c] = sqrtf(var_floor(s2 / l));
   }
 }
 
@@ -532,30 +532,40 @@ __global__ __launch_bounds__(NT, 2) void asp_fused_kernel(const bf16_t* __restri
     }
   mx = fmaxf(mx, __shfl_xor(mx, 32, 64));          // bias is constant over frames: max(v + bias) = max(v) + bias
   __syncthreads();
-  // ---- phase C: weighted moments about K = h[t = 0] (shifted single pass, fp32).  Rows >= T hold
-  // stale but finite bytes of the hidden tile and get weight 0, so every LDS read is unconditional.
+  // ---- phase C: weighted mean, then the weighted variance about it (two passes over the slab, fp32; the softmax weights stay
+  // in the accumulator registers).  A single pass about a shift K, s2 / l - a^2, loses (K - mu)^2 / var of the variance's bits to
+  // cancellation (frame 0 at 50 sigma, attention elsewhere: 3 to 10 x the fp32 bound, profiles/r08_asp_transient_frame0.txt).  Rows >= T
+  // hold stale but finite bytes of the hidden tile and get weight 0, so every LDS read is unconditional.
   const bf16_t* hl = reinterpret_cast<const bf16_t*>(lds) + wid * 32 + col;
-  const float K = load1t<F16>(hl);
-  float l = 0.f, s1 = 0.f, s2 = 0.f;
+  float l = 0.f, s1 = 0.f;
 #pragma unroll
   for (int rt = 0; rt < NTILES; ++rt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int t = rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
       const float e = t < T ? __expf(acc[rt][r] - mx) : 0.f;
-      const float d = load1t<F16>(hl + t * 128) - K;
+      acc[rt][r] = e;
       l += e;
-      s1 = fmaf(e, d, s1);
-      s2 = fmaf(e * d, d, s2);
+      s1 = fmaf(e, load1t<F16>(hl + t * 128), s1);
       if (r == 15) __builtin_amdgcn_sched_barrier(0);   // one row tile at a time: keeps 16, not 112, reads in flight
     }
   l += __shfl_xor(l, 32, 64);
   s1 += __shfl_xor(s1, 32, 64);
+  const float mu = s1 / l;
+  float s2 = 0.f;
+#pragma unroll
+  for (int rt = 0; rt < NTILES; ++rt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int t = rt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+      const float d = load1t<F16>(hl + t * 128) - mu;
+      s2 = fmaf(acc[rt][r] * d, d, s2);
+      if (r == 15) __builtin_amdgcn_sched_barrier(0);
+    }
   s2 += __shfl_xor(s2, 32, 64);
   if (hh == 0) {
-    const float a = s1 / l;
-    pooled[(int64_t)seg * 2 * C + ch] = K + a;
-    pooled[(int64_t)seg * 2 * C + C + ch] = sqrtf(fmaxf(s2 / l - a * a, 1e-12f));
+    pooled[(int64_t)seg * 2 * C + ch] = mu;
+    pooled[(int64_t)seg * 2 * C + C + ch] = sqrtf(var_floor(s2 / l));
   }
 }
 
@@ -579,7 +589,7 @@ __global__ __launch_bounds__(NT, 2) void asp_fused_kernel(const bf16_t* __restri
 //     top and spills them.
 //   LDS: hidden tile 224 x 256 B (16-B chunk index XOR (row & 15)) + 8 x (208 x 64 B) slabs (chunk XOR
 //        ((row >> 2) & 3): the two half-waves read rows 4 apart) = 163 840 B, all of a CU's LDS.
-// Results differ from asp_fused_kernel by fp32 rounding only (rescaling of the running sums).
+// Results differ from asp_fused_kernel by fp32 rounding only (rescaling of the running sums, per-tile moments merged by Chan's formula).
 constexpr int SEG_ROWS = 208;                 // frames a private h slab holds (T <= 208)
 constexpr int SEG_NT = 512;
 constexpr int SEG_HID_ROWS = 224;               // 7 MFMA row tiles of 32; rows >= T are zero
@@ -656,7 +666,6 @@ __global__ __launch_bounds__(SEG_NT, 2) void asp_seg_kernel(const bf16_t* __rest
   // two per-lane bases (compile-time part 0 or 2) + an immediate
   const uint32_t hoff0 = slab_off + hh * 4 * 64 + ((((col >> 3) ^ hh) ^ 0) << 4) + (col & 7) * 2;
   const uint32_t hoff2 = slab_off + hh * 4 * 64 + ((((col >> 3) ^ hh) ^ 2) << 4) + (col & 7) * 2;
-  const uint32_t koff = slab_off + ((col >> 3) << 4) + (col & 7) * 2;               // h[t = 0]
   if (wid < nblk) {
     fetch_w2(wid, bA);                                        // oldest: older than every piece
 #pragma unroll
@@ -669,7 +678,6 @@ __global__ __launch_bounds__(SEG_NT, 2) void asp_seg_kernel(const bf16_t* __rest
   uint32_t hv[16];                                           // low halves stay zero: ds_read_u16_d16_hi writes the high half only
 #pragma unroll
   for (int r = 0; r < 16; ++r) hv[r] = 0u;
-  uint32_t kv = 0u;
   int tlim = T - 4 * hh;                                       // frame (const + 4 hh) exists  <=>  const < tlim
 
   // a slab element as read by ds_read_u16_d16_hi (value in the register's HIGH half, low half zero): bf16 - the register is the fp32 value;
@@ -702,15 +710,27 @@ __global__ __launch_bounds__(SEG_NT, 2) void asp_seg_kernel(const bf16_t* __rest
                    : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]) :: "memory");
       cur = chain(a);
     }
-    float m = -INFINITY, Kf = 0.f;
-    f32x2 l2 = {0.f, 0.f}, s12 = {0.f, 0.f}, s22 = {0.f, 0.f};   // softmax denominator and the two shifted moments, (even, odd) frames
+    // running state of the lane's frames: softmax maximum m, weight sum L, weighted mean MU and centred second moment M2 (L and M2 relative
+    // to exp(m)).  A tile's mean and centred moment come from two passes over its 16 frames (all in registers), and tiles are merged with
+    // Chan's formula: nothing cancels.  One shift for the whole segment - h[t = 0], s2 / l - a^2 - lost (h[0] - mu)^2 / var of the
+    // variance's bits (frame 0 at 50 sigma: 3 to 10 x the fp32 bound, profiles/r08_asp_transient_frame0.txt)
+    // (a tile's weight pl, mean pK and centred moment ps2 wait to be merged at the top of the next tile, beside its MFMAs)
+    float m = -INFINITY, L = 0.f, MU = 0.f, M2 = 0.f, pl = 0.f, pK = 0.f, ps2 = 0.f;
+    // merge (pl, pK, ps2) into (L, MU, M2); L + pl >= 1: one of them holds the running maximum's frame (weight 1).  v_rcp (1 ulp)
+    // instead of divisions: this runs per tile
+    auto merge = [&]() {
+      const float n = L + pl, f = pl * __builtin_amdgcn_rcpf(n);
+      const float dl = pK - MU;
+      MU = fmaf(dl, f, MU);
+      M2 += ps2 + dl * dl * (L * f);
+      L = n;
+    };
 #pragma unroll
     for (int rt = 0; rt < NTILES; ++rt) {
       // piece rt of this block has landed once all but the ops issued after it are done (see the header comment)
       if (more) { if (rt < NTILES - 1) SEG_WAIT_VM(19); else SEG_WAIT_VM(20); }
       else if (rt == 0) SEG_WAIT_VM(11); else if (rt == 1) SEG_WAIT_VM(9); else if (rt == 2) SEG_WAIT_VM(7);
       else if (rt == 3) SEG_WAIT_VM(5); else if (rt == 4) SEG_WAIT_VM(3); else if (rt == 5) SEG_WAIT_VM(1); else SEG_WAIT_VM(0);
-      if (rt == 0) asm volatile("ds_read_u16_d16_hi %0, %1" : "+v"(kv) : "v"(koff));
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         if (rt * 32 + 8 * (r >> 2) + (r & 3) + 4 < SEG_ROWS)                         // compile-time: frames 208..223 do not exist (weight 0, stale h)
@@ -725,33 +745,32 @@ __global__ __launch_bounds__(SEG_NT, 2) void asp_seg_kernel(const bf16_t* __rest
         asm volatile("s_waitcnt lgkmcnt(0)"
                      : "+v"(hv[0]), "+v"(hv[1]), "+v"(hv[2]), "+v"(hv[3]), "+v"(hv[4]), "+v"(hv[5]), "+v"(hv[6]), "+v"(hv[7]),
                        "+v"(hv[8]), "+v"(hv[9]), "+v"(hv[10]), "+v"(hv[11]), "+v"(hv[12]), "+v"(hv[13]), "+v"(hv[14]), "+v"(hv[15]),
-                       "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]), "+v"(kv)
+                       "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7])
                      :: "memory");
       } else {
         asm volatile("s_waitcnt lgkmcnt(0)"
                      : "+v"(hv[0]), "+v"(hv[1]), "+v"(hv[2]), "+v"(hv[3]), "+v"(hv[4]), "+v"(hv[5]), "+v"(hv[6]), "+v"(hv[7]),
-                       "+v"(hv[8]), "+v"(hv[9]), "+v"(hv[10]), "+v"(hv[11]), "+v"(hv[12]), "+v"(hv[13]), "+v"(hv[14]), "+v"(hv[15]), "+v"(kv)
+                       "+v"(hv[8]), "+v"(hv[9]), "+v"(hv[10]), "+v"(hv[11]), "+v"(hv[12]), "+v"(hv[13]), "+v"(hv[14]), "+v"(hv[15])
                      :: "memory");
       }
       // this tile's slab rows have been read: request the same rows of the wave's next block
       if (more) fetch_piece(blk + 8, rt);
-      if (rt == 0) Kf = slab_f32(kv);
       f32x16 nxt = cur;
       auto step = [&](const bool masked) {
         if (rt + 1 < NTILES) nxt = chain(a);
+        if (rt > 0) merge();
         // online softmax: the running maximum may grow with this tile; the sums so far are rescaled to it
         float tm = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 16; ++r) tm = fmaxf(tm, (!masked || rt * 32 + (r & 3) + 8 * (r >> 2) < tlim) ? cur[r] : -INFINITY);
         const float mn = fmaxf(m, tm);
         const float sc = __builtin_amdgcn_exp2f((m - mn) * LOG2E);   // first tile: exp2(-inf) = 0 (tile 0 always has frames)
-        const f32x2 sc2 = {sc, sc};
-        l2 *= sc2; s12 *= sc2; s22 *= sc2;
+        L *= sc; M2 *= sc;
         m = mn;
         const float mc = -m * LOG2E;
-        const f32x2 mc2 = {mc, mc}, K2 = {Kf, Kf}, log2e2 = {LOG2E, LOG2E};
-        // frame PAIRS on packed fp32 instructions: even and odd frames of the lane accumulate side by side (merged at the
-        // end of the block); 5 vector-issue slots per frame instead of 9
+        const f32x2 mc2 = {mc, mc}, log2e2 = {LOG2E, LOG2E};
+        // the tile's weights, weight sum and weighted sum of h ((even, odd) frames side by side on packed fp32 instructions) ...
+        f32x2 e2[8], l2 = {0.f, 0.f}, s12 = {0.f, 0.f};
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
           const f32x2 x = {cur[r], cur[r + 1]};
@@ -762,13 +781,22 @@ __global__ __launch_bounds__(SEG_NT, 2) void asp_seg_kernel(const bf16_t* __rest
             e[0] = t0 < tlim ? e[0] : 0.f;
             e[1] = t0 + 1 < tlim ? e[1] : 0.f;
           }
-          f32x2 d = {slab_f32(hv[r]), slab_f32(hv[r + 1])};
-          d = d - K2;
-          const f32x2 ed = e * d;
+          const f32x2 hx = {slab_f32(hv[r]), slab_f32(hv[r + 1])};
+          e2[r / 2] = e;
           l2 += e;
-          s12 = e * d + s12;
-          s22 = ed * d + s22;
+          s12 = e * hx + s12;
         }
+        // ... then its centred second moment from the same registers: a true two-pass variance per tile
+        pl = l2[0] + l2[1];
+        pK = pl > 0.f ? (s12[0] + s12[1]) * __builtin_amdgcn_rcpf(pl) : 0.f;
+        const f32x2 mu2 = {pK, pK};
+        f32x2 s22 = {0.f, 0.f};
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) {
+          const f32x2 d = f32x2{slab_f32(hv[r]), slab_f32(hv[r + 1])} - mu2;
+          s22 = (e2[r / 2] * d) * d + s22;
+        }
+        ps2 = s22[0] + s22[1];
         if (rt + 1 < NTILES) {
 #pragma unroll
           for (int i = 0; i < 8; ++i) {
@@ -779,20 +807,19 @@ __global__ __launch_bounds__(SEG_NT, 2) void asp_seg_kernel(const bf16_t* __rest
       };
       if ((rt + 1) * 32 <= T) step(false);                     // wave-uniform: no frame of this tile needs masking
       else step(true);
-      asm volatile("" : "+v"(l2), "+v"(s12), "+v"(s22), "+v"(m));   // pins this tile's arithmetic before the next tile's reads
+      asm volatile("" : "+v"(L), "+v"(MU), "+v"(M2), "+v"(m), "+v"(pl), "+v"(ps2), "+v"(pK));   // pins this tile's arithmetic before the next tile's reads
       cur = nxt;
     }
-    // the two lanes of a channel (frame halves hh = 0 / 1) merge their running states
+    merge();
+    // the two lanes of a channel (frame halves hh = 0 / 1) merge their running states the same way
     const float M = fmaxf(m, __shfl_xor(m, 32, 64));
     const float f = __builtin_amdgcn_exp2f((m - M) * LOG2E);
-    float l = (l2[0] + l2[1]) * f, s1 = (s12[0] + s12[1]) * f, s2 = (s22[0] + s22[1]) * f;
-    l += __shfl_xor(l, 32, 64);
-    s1 += __shfl_xor(s1, 32, 64);
-    s2 += __shfl_xor(s2, 32, 64);
+    const float La = L * f, M2a = M2 * f;
+    const float Lb = __shfl_xor(La, 32, 64), MUb = __shfl_xor(MU, 32, 64), M2b = __shfl_xor(M2a, 32, 64);
     if (hh == 0) {
-      const float a = s1 / l;
-      pooled[(int64_t)seg * 2 * C + ch] = Kf + a;
-      pooled[(int64_t)seg * 2 * C + C + ch] = sqrtf(fmaxf(s2 / l - a * a, 1e-12f));
+      const float n = La + Lb, fb = Lb / n, dl = MUb - MU;
+      pooled[(int64_t)seg * 2 * C + ch] = fmaf(dl, fb, MU);
+      pooled[(int64_t)seg * 2 * C + C + ch] = sqrtf(var_floor((M2a + M2b + dl * dl * (La * fb)) / n));
     }
   };
   for (int blk = wid; blk < nblk; blk += 16) {
@@ -884,6 +911,14 @@ extern "C" int sdk_se_gate_residual(sdk_ctx* ctx, const uint16_t* z, int64_t ldz
   return se_gate_residual_impl(ctx, z, ldz, x, ldx, w1t, b1, w2t, b2, out, ldo, B, T, C, Cse, mean_in, ws, ws_bytes, stream, ctx && ctx->precision == 2);
 }
 
+extern "C" int sdk_se_gate_residual_fmt(sdk_ctx* ctx, const uint16_t* z, int64_t ldz, const uint16_t* x, int64_t ldx,
+                                        const float* w1t, const float* b1, const float* w2t, const float* b2,
+                                        uint16_t* out, int64_t ldo, int B, int T, int C, int Cse, const float* mean_in,
+                                        void* ws, size_t ws_bytes, int precision, void* stream) {
+  SDK_REQUIRE(precision == 0 || precision == 2, "sdk_se_gate_residual_fmt: precision=%d (0: bf16 elements, 2: fp16 elements)", precision);
+  return se_gate_residual_impl(ctx, z, ldz, x, ldx, w1t, b1, w2t, b2, out, ldo, B, T, C, Cse, mean_in, ws, ws_bytes, stream, precision == 2);
+}
+
 int asp_stats_impl(sdk_ctx* ctx, const uint16_t* h, int64_t ldh, int B, int T, int C, float* out_ctx, void* stream, bool f16) {
   SDK_REQUIRE(ctx && h && out_ctx, "sdk_asp_stats: null argument");
   SDK_REQUIRE(B > 0 && T > 0 && C % 8 == 0 && ldh % 8 == 0, "sdk_asp_stats: bad shape (C=%d ldh=%lld)", C, (long long)ldh);
@@ -953,6 +988,12 @@ extern "C" int sdk_asp_pool(sdk_ctx* ctx, const float* logits, int64_t ldl, cons
   return asp_pool_impl(ctx, logits, ldl, h, ldh, B, T, C, pooled, stream, ctx && ctx->precision == 2);
 }
 
+extern "C" int sdk_asp_pool_fmt(sdk_ctx* ctx, const float* logits, int64_t ldl, const uint16_t* h, int64_t ldh, int B,
+                                int T, int C, float* pooled, int precision, void* stream) {
+  SDK_REQUIRE(precision == 0 || precision == 2, "sdk_asp_pool_fmt: precision=%d (0: bf16 elements, 2: fp16 elements)", precision);
+  return asp_pool_impl(ctx, logits, ldl, h, ldh, B, T, C, pooled, stream, precision == 2);
+}
+
 extern "C" int sdk_asp_fused_max_frames(void) { return 224; }
 
 // Internal entry (sdk_ecapa_forward): w2p may be null, or the fragment-ordered copy of w2 (ecapa_layout.h EL_ASP_W2PACK).
@@ -994,11 +1035,23 @@ extern "C" int sdk_asp_fused(sdk_ctx* ctx, const uint16_t* ah, int64_t ldah, con
   return asp_fused_launch(ctx, ah, ldah, w2, nullptr, b2, h, ldh, B, T, C, A, pooled, stream, false, ctx && ctx->precision == 2);
 }
 
+extern "C" int sdk_asp_fused_fmt(sdk_ctx* ctx, const uint16_t* ah, int64_t ldah, const uint16_t* w2, const float* b2,
+                                 const uint16_t* h, int64_t ldh, int B, int T, int C, int A, float* pooled, int precision, void* stream) {
+  SDK_REQUIRE(precision == 0 || precision == 2, "sdk_asp_fused_fmt: precision=%d (0: bf16 elements, 2: fp16 elements)", precision);
+  return asp_fused_launch(ctx, ah, ldah, w2, nullptr, b2, h, ldh, B, T, C, A, pooled, stream, false, precision == 2);
+}
+
 extern "C" int sdk_asp_kblocked_ok(sdk_ctx* ctx, int T, int C) { return ctx && asp_seg_ok(ctx, T, C) ? 1 : 0; }
 
 extern "C" int sdk_asp_fused_kblocked(sdk_ctx* ctx, const uint16_t* ah, int64_t ldah, const uint16_t* w2, const float* b2, const uint16_t* h,
                                       int B, int T, int C, int A, float* pooled, void* stream) {
   return asp_fused_launch(ctx, ah, ldah, w2, nullptr, b2, h, 64, B, T, C, A, pooled, stream, true, ctx && ctx->precision == 2);
+}
+
+extern "C" int sdk_asp_fused_kblocked_fmt(sdk_ctx* ctx, const uint16_t* ah, int64_t ldah, const uint16_t* w2, const float* b2, const uint16_t* h,
+                                          int B, int T, int C, int A, float* pooled, int precision, void* stream) {
+  SDK_REQUIRE(precision == 0 || precision == 2, "sdk_asp_fused_kblocked_fmt: precision=%d (0: bf16 elements, 2: fp16 elements)", precision);
+  return asp_fused_launch(ctx, ah, ldah, w2, nullptr, b2, h, 64, B, T, C, A, pooled, stream, true, precision == 2);
 }
 
 extern "C" int sdk_l2norm(sdk_ctx* ctx, const float* X, int N, int d, float* E, uint16_t* Eb, float* resid,

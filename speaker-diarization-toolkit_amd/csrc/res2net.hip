@@ -498,3 +498,10 @@ extern "C" int sdk_res2net_chain(sdk_ctx* ctx, const uint16_t* U, int64_t ldu, u
                                  int B, int T, int dil, void* stream) {
   return res2net_chain_launch(ctx, U, ldu, R, ldr, W, nullptr, bias, scale, shift, nconv, B, T, dil, stream, ctx && ctx->precision == 2);
 }
+
+extern "C" int sdk_res2net_chain_fmt(sdk_ctx* ctx, const uint16_t* U, int64_t ldu, uint16_t* R, int64_t ldr, const uint16_t* const* W,
+                                     const float* const* bias, const float* const* scale, const float* const* shift, int nconv,
+                                     int B, int T, int dil, int precision, void* stream) {
+  SDK_REQUIRE(precision == 0 || precision == 2, "sdk_res2net_chain_fmt: precision=%d (0: bf16 elements, 2: fp16 elements)", precision);
+  return res2net_chain_launch(ctx, U, ldu, R, ldr, W, nullptr, bias, scale, shift, nconv, B, T, dil, stream, precision == 2);
+}

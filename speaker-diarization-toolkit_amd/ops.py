@@ -27,6 +27,15 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def _elem_fmt(t: torch.Tensor, what: str) -> int:
+    """The C ABI's 2-byte element format of a tensor (the _fmt entry points' `precision`): bf16 -> 0, fp16 -> 2; any other dtype is refused."""
+    if t.dtype == torch.bfloat16:
+        return 0
+    if t.dtype == torch.float16:
+        return 2
+    raise ValueError(f"{what}: 2-byte activations must be bfloat16 or float16, got {t.dtype}")
+
+
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
@@ -528,15 +537,20 @@ class Engine:
         C_ = z.shape[1]
         out = torch.empty_like(z)
         ws = self._scratch_bytes("se", self.lib.sdk_se_workspace_bytes(B, C_, w1t.shape[1])) if split else None
-        check(self.lib.sdk_se_gate_residual(self.ctx, z.data_ptr(), z.stride(0), x.data_ptr(), x.stride(0), w1t.data_ptr(),
-                                            b1.data_ptr(), w2t.data_ptr(), b2.data_ptr(), out.data_ptr(), out.stride(0),
-                                            B, T, C_, w1t.shape[1], None, _ptr(ws), ws.numel() if split else 0, _stream()), "sdk_se_gate_residual")
+        fmt = _elem_fmt(z, "se_gate_residual")
+        if x.dtype != z.dtype:
+            raise ValueError(f"se_gate_residual: z is {z.dtype} but x is {x.dtype}")
+        check(self.lib.sdk_se_gate_residual_fmt(self.ctx, z.data_ptr(), z.stride(0), x.data_ptr(), x.stride(0), w1t.data_ptr(),
+                                                b1.data_ptr(), w2t.data_ptr(), b2.data_ptr(), out.data_ptr(), out.stride(0),
+                                                B, T, C_, w1t.shape[1], None, _ptr(ws), ws.numel() if split else 0, fmt, _stream()),
+              "sdk_se_gate_residual_fmt")
         return out
 
     def asp_stats(self, h, B, T):
         Cm = h.shape[1]
         out = torch.empty((B, 2 * Cm), dtype=torch.float32, device=self.device)
-        check(self.lib.sdk_asp_stats(self.ctx, h.data_ptr(), h.stride(0), B, T, Cm, out.data_ptr(), _stream()), "sdk_asp_stats")
+        check(self.lib.sdk_asp_stats_fmt(self.ctx, h.data_ptr(), h.stride(0), B, T, Cm, out.data_ptr(), _elem_fmt(h, "asp_stats"), _stream()),
+              "sdk_asp_stats_fmt")
         return out
 
     def rows_fc(self, x, wt, bias=None, in_scale=None, in_shift=None, act=0):
@@ -550,8 +564,8 @@ class Engine:
     def asp_pool(self, logits, h, B, T):
         Cm = h.shape[1]
         out = torch.empty((B, 2 * Cm), dtype=torch.float32, device=self.device)
-        check(self.lib.sdk_asp_pool(self.ctx, logits.data_ptr(), logits.stride(0), h.data_ptr(), h.stride(0), B, T, Cm,
-                                    out.data_ptr(), _stream()), "sdk_asp_pool")
+        check(self.lib.sdk_asp_pool_fmt(self.ctx, logits.data_ptr(), logits.stride(0), h.data_ptr(), h.stride(0), B, T, Cm,
+                                        out.data_ptr(), _elem_fmt(h, "asp_pool"), _stream()), "sdk_asp_pool_fmt")
         return out
 
 
@@ -667,17 +681,21 @@ class Engine:
         return Z
 
     def asp_fused(self, ah, w2, b2, h, B, T, kblocked=False):
-        """kblocked: h is [Cm / 64, B*T, 64] (to_kblocked) - the per-segment form only (sdk_asp_kblocked_ok)."""
+        """kblocked: h is [Cm / 64, B*T, 64] (to_kblocked) - the per-segment form only (sdk_asp_kblocked_ok).  The element format (bf16 or
+        fp16) is h's dtype; ah and w2 must match it."""
+        fmt = _elem_fmt(h, "asp_fused")
+        if ah.dtype != h.dtype or w2.dtype != h.dtype:
+            raise ValueError(f"asp_fused: ah {ah.dtype}, w2 {w2.dtype} and h {h.dtype} must share one element format")
         if kblocked:
             Cm = h.shape[0] * 64
             out = torch.empty((B, 2 * Cm), dtype=torch.float32, device=self.device)
-            check(self.lib.sdk_asp_fused_kblocked(self.ctx, ah.data_ptr(), ah.stride(0), w2.data_ptr(), b2.data_ptr(), h.data_ptr(),
-                                                  B, T, Cm, ah.shape[1], out.data_ptr(), _stream()), "sdk_asp_fused_kblocked")
+            check(self.lib.sdk_asp_fused_kblocked_fmt(self.ctx, ah.data_ptr(), ah.stride(0), w2.data_ptr(), b2.data_ptr(), h.data_ptr(),
+                                                      B, T, Cm, ah.shape[1], out.data_ptr(), fmt, _stream()), "sdk_asp_fused_kblocked_fmt")
             return out
         Cm = h.shape[1]
         out = torch.empty((B, 2 * Cm), dtype=torch.float32, device=self.device)
-        check(self.lib.sdk_asp_fused(self.ctx, ah.data_ptr(), ah.stride(0), w2.data_ptr(), b2.data_ptr(), h.data_ptr(), h.stride(0),
-                                     B, T, Cm, ah.shape[1], out.data_ptr(), _stream()), "sdk_asp_fused")
+        check(self.lib.sdk_asp_fused_fmt(self.ctx, ah.data_ptr(), ah.stride(0), w2.data_ptr(), b2.data_ptr(), h.data_ptr(), h.stride(0),
+                                         B, T, Cm, ah.shape[1], out.data_ptr(), fmt, _stream()), "sdk_asp_fused_fmt")
         return out
 
 
