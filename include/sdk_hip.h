@@ -33,9 +33,11 @@
  *     sdk_affinity_matvec_workspace_bytes  sdk_affinity_matvec  sdk_rows_gram_workspace_bytes  sdk_rows_gram
  *     sdk_rows_apply  sdk_chol_inverse  sdk_rows_unit  sdk_kmeans_mindist  sdk_kmeans_assign            k6 (driven by cluster.py)
  *     sdk_centroid_linkage_workspace_bytes  sdk_centroid_linkage                                    k6 threshold path (cluster.agglomerative_cluster)
+ *     sdk_segmentation_frames  sdk_segmentation_workspace_bytes  sdk_segmentation_forward               speaker segmentation (PyanNet, segmentation.py)
  * BUILDING BLOCKS AND KNOBS - exported for the parity tests and the A/B tools, free to change between rounds, not for binding:
  *     sdk_conv_gemm*  sdk_colstats_finish  sdk_res2net_chain*  sdk_se_*  sdk_asp_*  sdk_rows_fc  (pieces of sdk_ecapa_forward)
  *     sdk_resnet_conv2d  (piece of sdk_resnet_forward)
+ *     sdk_sincnet_frontend  sdk_bilstm_layer  (pieces of sdk_segmentation_forward)
  *     sdk_set_option  sdk_set_gemm_variant  sdk_profile_begin / _end  sdk_debug_set_ptr  sdk_affinity_plan*  sdk_affinity_block_plan*  sdk_affinity_matvec_plan  sdk_conv_gemm_hp
  *     sdk_allgather  sdk_laplacian_topk_workspace_bytes  sdk_laplacian_topk        k5 / k6 drivers for a non-Python host (the library holds no
  *                                                                                     communicator: the caller passes its ncclComm_t; the Python
@@ -407,6 +409,55 @@ typedef struct sdk_resnet_conv_args {
   int32_t reserved;
 } sdk_resnet_conv_args;
 int sdk_resnet_conv2d(sdk_ctx* ctx, const sdk_resnet_conv_args* a, void* stream);
+
+/* ---- speaker segmentation: PyanNet as in pyannote segmentation-3.0 (segmentation.py; csrc/segmentation.hip).  One chunk of S >= 991
+ *      samples (16 kHz mono int16) -> F(S) = ((((S - 251) / 10 + 1) / 3 - 4) / 3 - 4) / 3 frames (589 at S = 160 000; frame i sees samples
+ *      [270 i, 270 i + 991)) -> log-probabilities of the 7 powerset classes {}, {0}, {1}, {2}, {0,1}, {0,2}, {1,2}.
+ *   chunk source: starts == NULL: B rows of a [B][ld] int16 matrix (ld >= S, (B - 1) ld + S <= n_samples); else starts [B] int32 (device) =
+ *      first sample of every chunk inside the recording samples [n_samples] (device), samples past its end read as zero - the overlapping
+ *      chunks never exist on the host, as in sdk_fbank_windows.
+ *   sdk_segmentation_forward : -> logp [B][F][7] fp32.  B = 0 is a no-op; S < 991, precision 1 and too small a workspace are refused.
+ *   sdk_sincnet_frontend     : building block: the SincNet stages alone -> out [B F][64] fp32 frames (features 0..59, 60..63 zero).
+ *   sdk_bilstm_layer         : building block: one BiLSTM layer (both directions): x [B F][ldx] fp32 (60 features for layer 0, ldx >= 64;
+ *                              256 for layers 1..3; ldx % 8 == 0) -> y [B F][256] fp32 (forward | reverse); workspace >= B F 4096 bytes.
+ *   sdk_segmentation_workspace_bytes(d, B, S): the forward's and the front end's workspace (0 for arguments they refuse).
+ *   Descriptor: precision 0 (bf16) / 2 (fp16): the format of the weights and of the MFMA operands; activations cross the stages in fp32 and
+ *   enter the MFMAs as hi + lo planes of that format.  off[] = 256-aligned byte offsets of the
+ *   weight slots SDK_SEG_* in one device blob (segmentation.pack_weights writes both). */
+enum {
+  SDK_SEG_SINC = 0,      /* 2-byte [80][256]: the sinc filters (cos 0..39, sin 40..79), taps 251..255 zero */
+  SDK_SEG_SINC_SUM,      /* fp32 [80]: sum of each rounded filter's taps */
+  SDK_SEG_WAVNORM,       /* fp32 [2]: waveform InstanceNorm weight, bias */
+  SDK_SEG_NORM0,         /* fp32 [2][80]: InstanceNorm weight | bias of the sinc block */
+  SDK_SEG_CONV1_W,       /* 2-byte [64][416]: Conv1d(80, 60, 5), k = tap 80 + c; rows >= 60 and k >= 400 zero */
+  SDK_SEG_CONV1_B,       /* fp32 [64] */
+  SDK_SEG_NORM1,         /* fp32 [2][60] */
+  SDK_SEG_CONV2_W,       /* 2-byte [64][320]: Conv1d(60, 60, 5) on 64-channel rows, k = tap 64 + c; c >= 60 and rows >= 60 zero */
+  SDK_SEG_CONV2_B,       /* fp32 [64] */
+  SDK_SEG_NORM2,         /* fp32 [2][60] */
+  SDK_SEG_LSTM,          /* + 3 l: W_ih 2-byte [1024][64 | 256] (rows 512 d + gate row, gates i f g o), bias fp32 [1024] (b_ih + b_hh),
+                            W_hh 2-byte [2][512][128] */
+  SDK_SEG_LIN0_W = SDK_SEG_LSTM + 12,   /* 2-byte [128][256] */
+  SDK_SEG_LIN0_B,        /* fp32 [128] */
+  SDK_SEG_LIN1_W,        /* 2-byte [128][128] */
+  SDK_SEG_LIN1_B,        /* fp32 [128] */
+  SDK_SEG_CLS_W,         /* fp32 [7][128] */
+  SDK_SEG_CLS_B,         /* fp32 [7] */
+  SDK_SEG_SLOTS
+};
+typedef struct sdk_segmentation_desc {
+  int32_t precision;
+  int32_t reserved;
+  int64_t off[32];
+} sdk_segmentation_desc;
+int sdk_segmentation_frames(int S);
+size_t sdk_segmentation_workspace_bytes(const sdk_segmentation_desc* d, int B, int S);
+int sdk_segmentation_forward(sdk_ctx* ctx, const void* wblob, const sdk_segmentation_desc* d, const int16_t* samples, int64_t n_samples,
+                             const int32_t* starts, int ld, int B, int S, void* ws, size_t ws_bytes, float* logp, void* stream);
+int sdk_sincnet_frontend(sdk_ctx* ctx, const void* wblob, const sdk_segmentation_desc* d, const int16_t* samples, int64_t n_samples,
+                         const int32_t* starts, int ld, int B, int S, void* ws, size_t ws_bytes, float* out, void* stream);
+int sdk_bilstm_layer(sdk_ctx* ctx, const void* wblob, const sdk_segmentation_desc* d, int layer, const float* x, int ldx, int B, int F,
+                     void* ws, size_t ws_bytes, float* y, void* stream);
 
 /* ---- audio conversion to the AudioProfile: replaces the ffmpeg subprocess the reference's backends
  *      run before upload (audio_profiles.py:70-100 `format_ffmpeg_args`; speechmatics_backend.py:231-281).

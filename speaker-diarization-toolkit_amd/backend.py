@@ -364,6 +364,44 @@ class Backend(EmbeddingBackend):
             range_labels[ri] = int(np.argmax(np.bincount(labs)))        # first maximum = the smaller label
         return labels, wins, range_labels
 
+    def segmentation(self):
+        """The resident PyanNet segmentation model (segmentation.py), whatever SDK_MODEL is: weights from $SDK_SEGMENTATION_WEIGHTS (.npz in
+        pyannote's naming), else seeded synthetic; precision from SDK_PRECISION (0 or 2; the precise mode is not built for it)."""
+        if self.lite:
+            raise ValueError("speech_ranges needs the torch engine: not available with SDK_NO_TORCH=1")
+        if getattr(self, "_segmentation", None) is None:
+            from .segmentation import Segmentation, load_weights, synthetic_weights as seg_synthetic
+            prec = int(os.environ.get("SDK_PRECISION", "0"))
+            if prec == 1:
+                raise ValueError("SDK_PRECISION=1 (the precise mode) is not built for the segmentation model: use SDK_PRECISION=0 or 2")
+            path = os.environ.get("SDK_SEGMENTATION_WEIGHTS")
+            w = load_weights(path) if path else seg_synthetic(0)
+            self._segmentation = Segmentation(self.engine(), w, precision=prec)
+        return self._segmentation
+
+    def speech_ranges(self, samples: np.ndarray, step_s: float = 1.0):
+        """Speech and overlapped speech of a recording with no transcript: (speech [(start_s, end_s)], overlap [(start_s, end_s)]).
+        The recording (16 kHz mono int16) is uploaded once; 10-s chunks starting at 0, step_s, 2 step_s, ... plus one ending at the recording's
+        end (one zero-padded chunk below 10 s) are cut on the device and segmented in batches of $SDK_SEGMENTATION_BATCH (default 256).  Each
+        chunk's per-frame speaker count (its powerset argmax) is aggregated on the global 270-sample frame grid by segmentation.aggregate_counts:
+        a frame is speech when at least half of the chunks that see it count >= 1 speaker, overlap when at least half count >= 2.  The rule
+        needs no alignment of local speakers between chunks (that belongs to the full diarization pipeline).  `speech` can be passed straight
+        to cluster_ranges."""
+        import torch
+        from .segmentation import aggregate_counts, chunk_starts, speaker_count
+        model = self.segmentation()
+        x = np.ascontiguousarray(samples, dtype=np.int16).reshape(-1)
+        if x.size == 0:
+            return [], []
+        st = chunk_starts(x.size, step_s)
+        rec = torch.from_numpy(x).to(model.eng.device)
+        step = max(1, int(os.environ.get("SDK_SEGMENTATION_BATCH", "256")))
+        counts = []
+        for a in range(0, len(st), step):
+            s = torch.from_numpy(st[a:a + step].astype(np.int32)).to(model.eng.device)
+            counts.append(speaker_count(model.forward(rec, s)).cpu().numpy())
+        return aggregate_counts(np.concatenate(counts), st, x.size)
+
     # ---- a2: enroll (base.py:107-128) ---------------------------------------------------------
     def enroll_speaker(self, audio_path: Path, segments: Optional[List[Tuple[float, float]]] = None) -> Dict[str, Any]:
         if segments:           # the caller vouches that each range is this speaker: true-length windows, never widened
