@@ -34,9 +34,11 @@
  *     sdk_rows_apply  sdk_chol_inverse  sdk_rows_unit  sdk_kmeans_mindist  sdk_kmeans_assign            k6 (driven by cluster.py)
  *     sdk_centroid_linkage_workspace_bytes  sdk_centroid_linkage                                    k6 threshold path (cluster.agglomerative_cluster)
  *     sdk_segmentation_frames  sdk_segmentation_workspace_bytes  sdk_segmentation_forward               speaker segmentation (PyanNet, segmentation.py)
+ *     sdk_powerset_decode  sdk_diarize_masks  sdk_resnet_last_map_frames  sdk_resnet_masked_workspace_bytes
+ *     sdk_resnet_forward_masked  sdk_diarize_frames  sdk_diarize_reconstruct                              speaker diarization (diarize.py)
  * BUILDING BLOCKS AND KNOBS - exported for the parity tests and the A/B tools, free to change between rounds, not for binding:
  *     sdk_conv_gemm*  sdk_colstats_finish  sdk_res2net_chain*  sdk_se_*  sdk_asp_*  sdk_rows_fc  (pieces of sdk_ecapa_forward)
- *     sdk_resnet_conv2d  (piece of sdk_resnet_forward)
+ *     sdk_resnet_conv2d  (piece of sdk_resnet_forward)  sdk_resnet_masked_pool  (piece of sdk_resnet_forward_masked)
  *     sdk_sincnet_frontend  sdk_bilstm_layer  (pieces of sdk_segmentation_forward)
  *     sdk_set_option  sdk_set_gemm_variant  sdk_profile_begin / _end  sdk_debug_set_ptr  sdk_affinity_plan*  sdk_affinity_block_plan*  sdk_affinity_matvec_plan  sdk_conv_gemm_hp
  *     sdk_allgather  sdk_laplacian_topk_workspace_bytes  sdk_laplacian_topk        k5 / k6 drivers for a non-Python host (the library holds no
@@ -409,6 +411,21 @@ typedef struct sdk_resnet_conv_args {
   int32_t reserved;
 } sdk_resnet_conv_args;
 int sdk_resnet_conv2d(sdk_ctx* ctx, const sdk_resnet_conv_args* a, void* stream);
+/* The ResNet34 forward with S weighted poolings per segment (diarize.py: one per local speaker of a 10-s chunk).  The conv trunk - the conv
+ *   sequence of sdk_resnet_forward, bit for bit - runs once per segment; ONE pooling launch reads the last map [B][F4][T4][C] and writes the
+ *   statistics rows b S + s; seg_1 runs over the B S rows -> emb [B S, embed_dim].
+ *   w [B][S][T4] fp32 >= 0 (any weights, not only 0 / 1), T4 = sdk_resnet_last_map_frames(d, T); valid [B][S] int32.  With v1 = sum w,
+ *   v2 = sum w^2:  mean = sum w x / v1,  var = sum w (x - mean)^2 / (v1 - v2 / v1),  std = sqrt(var + 1e-7): two passes, fp32, frames in
+ *   order, feature order as in sdk_resnet_forward; with 0 / 1 weights the unbiased statistic over the selected columns.  A row depends on
+ *   its own weights only.  Rows with valid == 0 are written as zeros (a valid row needs v1 - v2 / v1 > 0: two columns).
+ *   Precision 0 and 2 (1 is refused).  Workspace: sdk_resnet_masked_workspace_bytes(d, B, T, S).
+ *   sdk_resnet_masked_pool: building block: the pooling alone on a last map x [B][F][T][C] (fmt 0: bf16, 2: fp16) -> out [B S][2 C F]. */
+int sdk_resnet_last_map_frames(const sdk_resnet_desc* d, int T);
+size_t sdk_resnet_masked_workspace_bytes(const sdk_resnet_desc* d, int B, int T, int S);
+int sdk_resnet_forward_masked(sdk_ctx* ctx, const void* wblob, const sdk_resnet_desc* d, const uint16_t* feats, int ldf, int B, int T,
+                              int S, const float* w, const int32_t* valid, void* ws, size_t ws_bytes, float* emb, void* stream);
+int sdk_resnet_masked_pool(sdk_ctx* ctx, const uint16_t* x, int B, int F, int T, int C, int S, const float* w, const int32_t* valid,
+                           float* out, int fmt, void* stream);
 
 /* ---- speaker segmentation: PyanNet as in pyannote segmentation-3.0 (segmentation.py; csrc/segmentation.hip).  One chunk of S >= 991
  *      samples (16 kHz mono int16) -> F(S) = ((((S - 251) / 10 + 1) / 3 - 4) / 3 - 4) / 3 frames (589 at S = 160 000; frame i sees samples
@@ -458,6 +475,28 @@ int sdk_sincnet_frontend(sdk_ctx* ctx, const void* wblob, const sdk_segmentation
                          const int32_t* starts, int ld, int B, int S, void* ws, size_t ws_bytes, float* out, void* stream);
 int sdk_bilstm_layer(sdk_ctx* ctx, const void* wblob, const sdk_segmentation_desc* d, int layer, const float* x, int ldx, int B, int F,
                      void* ws, size_t ws_bytes, float* y, void* stream);
+
+/* ---- speaker diarization (diarize.py; csrc/diarize.hip): the integer stages between the segmentation model, the masked ResNet34 forward
+ *      and the clustering.  Every kernel is a gather with one owner per output element and integer arithmetic: no atomics, results
+ *      bit-identical run to run.  Powerset classes as above; active(c, i, s): local speaker s is in the class of frame i of chunk c,
+ *      count(c, i): the size of that class.
+ *   sdk_powerset_decode : logp [C][F][7] fp32 -> cls [C][F] uint8, the argmax class (ties to the lower class; a NaN never wins).
+ *   sdk_diarize_masks   : cls [B][F] -> w [B][3][T4] fp32 (the 0 / 1 pooling weights of sdk_resnet_forward_masked) and info [B][3][4] int32 =
+ *        (active frames, clean frames, used_clean, valid).  Last-map column j takes frame i(j) = min(F - 1, (j F) / T4);
+ *        full[j] = active(i(j), s), clean[j] = full[j] and count(i(j)) < 2; w = clean when sum clean >= 4, else full; valid = sum w >= 2.
+ *        The two frame totals are counted on the F frames (clean: active and count < 2), not on columns.
+ *   sdk_diarize_reconstruct : cls [C][F], starts [C] int32 ascending (first samples of the chunks), labels [C][3] int32 (cluster of each local
+ *        speaker, -1: none), K clusters -> on the G = sdk_diarize_frames(n_samples) global frames (centre 270 g + 495):
+ *        chunk c contributes its frame i = g + q_c, q_c = floor((135 - start_c) / 270), when 0 <= i < F (found by binary search, not a scan);
+ *        act[g][k] = number of contributing chunks with an active local speaker labelled k; nc = contributing chunks; cnt = sum count(c, i);
+ *        count[g] = min((2 cnt + nc) / (2 nc), 2, max_speakers) (0 when nc = 0): uint8 [G];
+ *        speakers [G][2] int32: the count[g] clusters with the largest act > 0, ties to the lower cluster, padded with -1;
+ *        act (or NULL) [G][K] int32.  Any K >= 1. */
+int sdk_powerset_decode(sdk_ctx* ctx, const float* logp, int C, int F, uint8_t* cls, void* stream);
+int sdk_diarize_masks(sdk_ctx* ctx, const uint8_t* cls, int B, int F, int T4, float* w, int32_t* info, void* stream);
+int64_t sdk_diarize_frames(int64_t n_samples);
+int sdk_diarize_reconstruct(sdk_ctx* ctx, const uint8_t* cls, const int32_t* starts, const int32_t* labels, int C, int F, int K,
+                            int64_t n_samples, int max_speakers, uint8_t* count, int32_t* speakers, int32_t* act, void* stream);
 
 /* ---- audio conversion to the AudioProfile: replaces the ffmpeg subprocess the reference's backends
  *      run before upload (audio_profiles.py:70-100 `format_ffmpeg_args`; speechmatics_backend.py:231-281).

@@ -141,6 +141,14 @@ SIGNATURES = {
     "sdk_resnet_workspace_bytes": (_sz, [_vp, _i, _i]),
     "sdk_resnet_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "sdk_resnet_conv2d": (_i, [_vp, _vp, _vp]),
+    "sdk_resnet_last_map_frames": (_i, [_vp, _i]),
+    "sdk_resnet_masked_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "sdk_resnet_forward_masked": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "sdk_resnet_masked_pool": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "sdk_powerset_decode": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "sdk_diarize_masks": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "sdk_diarize_frames": (_i64, [_i64]),
+    "sdk_diarize_reconstruct": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i, _vp, _vp, _vp, _vp]),
     "sdk_segmentation_frames": (_i, [_i]),
     "sdk_segmentation_workspace_bytes": (_sz, [_vp, _i, _i]),
     "sdk_segmentation_forward": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),

@@ -402,6 +402,45 @@ class Backend(EmbeddingBackend):
             counts.append(speaker_count(model.forward(rec, s)).cpu().numpy())
         return aggregate_counts(np.concatenate(counts), st, x.size)
 
+    def diarizer(self):
+        """The resident diarization pipeline (diarize.py): Backend.segmentation() and the ResNet34 built from $SDK_RESNET_WEIGHTS (.npz in the
+        public naming, else seeded synthetic) whatever SDK_MODEL is; precision from SDK_PRECISION (0 or 2)."""
+        if self.lite:
+            raise ValueError("diarize needs the torch engine: not available with SDK_NO_TORCH=1")
+        if getattr(self, "_diarizer", None) is None:
+            from . import resnet
+            from .diarize import Diarizer
+            model = self.segmentation()
+            if self.model == "resnet34":
+                net = self._extractor                            # built by engine() from the same weights
+            else:
+                prec = int(os.environ.get("SDK_PRECISION", "0"))
+                path = os.environ.get("SDK_RESNET_WEIGHTS")
+                if path:
+                    with np.load(path, allow_pickle=False) as z:             # numpy's non-executing loader
+                        w = {k: np.ascontiguousarray(z[k], dtype=np.float32) for k in z.files}
+                else:
+                    w = resnet.synthetic_weights(0)
+                net = resnet.ResNet34(self.engine(), w, precision=prec)
+            self._diarizer = Diarizer(self.engine(), model, net)
+        return self._diarizer
+
+    def diarize(self, samples_or_path, **kw):
+        """Who spoke when, with no transcript and no enrolled profiles: a recording (16 kHz mono int16 samples, or the path of an audio file,
+        decoded to the audio profile) -> diarize.DiarizationResult (turns [(start_s, end_s, speaker)], n_speakers, unit centroids in the
+        embedding space of score_windows, labels, count, speakers); diarize.to_rttm(result.turns, uri) writes RTTM.  Keywords: step_s,
+        threshold, min_cluster_size, max_speakers, logp (diarize.Diarizer.run).  The default threshold is PyAnnote 3.1's, tuned for its
+        trained ResNet34 ($SDK_RESNET_WEIGHTS); with the synthetic weights pass a threshold of your own."""
+        dz = self.diarizer()
+        if isinstance(samples_or_path, (str, Path)):
+            samples_or_path = decode_to_profile(Path(samples_or_path), self.engine(), self.get_audio_profile())
+        prec = dz.eng.precision
+        try:
+            return dz.run(samples_or_path, **kw)
+        finally:
+            if dz.eng.precision != prec:
+                dz.eng.set_precision(prec)                       # the front end's format goes back to the selected family's contract
+
     # ---- a2: enroll (base.py:107-128) ---------------------------------------------------------
     def enroll_speaker(self, audio_path: Path, segments: Optional[List[Tuple[float, float]]] = None) -> Dict[str, Any]:
         if segments:           # the caller vouches that each range is this speaker: true-length windows, never widened

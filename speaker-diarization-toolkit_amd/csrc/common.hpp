@@ -72,6 +72,11 @@ int res2net_chain_launch(sdk_ctx* ctx, const uint16_t* U, int64_t ldu, uint16_t*
 
 // resnet.hip: temporal statistics pooling of the ResNet34 family's last map (internal; sdk_resnet_forward)
 int resnet_tstp_impl(sdk_ctx* ctx, const uint16_t* x, int B, int F, int T, int C, float* out, void* stream, bool f16);
+// resnet.hip: the same pooling with per-(speaker, frame) weights, S rows per segment, and the zeroing of invalid embedding rows
+// (internal; sdk_resnet_forward_masked)
+int resnet_masked_tstp_impl(sdk_ctx* ctx, const uint16_t* x, int B, int F, int T, int C, int S, const float* w, const int32_t* valid, float* out,
+                            void* stream, bool f16);
+int resnet_zero_invalid_impl(sdk_ctx* ctx, float* emb, int n, int dim, const int32_t* valid, void* stream);
 
 // ahc.hip: centroid-linkage agglomerative clustering (sdk_centroid_linkage checks the arguments, then calls these)
 size_t ahc_workspace_bytes(const int32_t* offsets, int G);

@@ -217,6 +217,68 @@ __global__ __launch_bounds__(RN_NT) void resnet_tstp_kernel(const bf16_t* __rest
   }
 }
 
+// The same statistics with a weight per (speaker, frame): S rows per segment from ONE sweep of the last map (diarize.py: the conv trunk runs
+// once per chunk, the speakers of a chunk differ only here).  w [B][S][T] fp32 >= 0, valid [B][S]; out row b S + s.  With v1 = sum w,
+// v2 = sum w^2: mean = sum w x / v1, var = sum w (x - mean)^2 / (v1 - v2 / v1), std = sqrt(var + 1e-7) - for 0 / 1 weights the unbiased
+// statistic over the selected frames.  Two passes, fp32, frames in order; a row's result depends on its own weights only.  Rows with
+// valid == 0 are zeros.  Workgroup = (segment, f), lanes over channels as above; the weights sit in LDS, the speakers go in groups of MP_SG so
+// that a group's pass reads each map element once (S = 3: one group).
+constexpr int MP_SG = 4;
+template <bool F16>
+__global__ __launch_bounds__(RN_NT) void resnet_masked_tstp_kernel(const bf16_t* __restrict__ x, int F, int T, int C, int S, const float* __restrict__ w,
+                                                                   const int32_t* __restrict__ valid, float* __restrict__ out) {
+  extern __shared__ float wl[];                        // [S][T]
+  const int b = blockIdx.x / F, f = blockIdx.x % F;
+  for (int i = threadIdx.x; i < S * T; i += RN_NT) wl[i] = w[(int64_t)b * S * T + i];
+  __syncthreads();
+  for (int s0 = 0; s0 < S; s0 += MP_SG) {
+    const int ns = min(MP_SG, S - s0);
+    float v1[MP_SG], v2[MP_SG];
+    bool ok[MP_SG];
+#pragma unroll
+    for (int i = 0; i < MP_SG; ++i) {
+      v1[i] = 0.f; v2[i] = 0.f;
+      ok[i] = i < ns && valid[b * S + s0 + i] != 0;
+      const float* ws = wl + (s0 + min(i, ns - 1)) * T;
+      for (int t = 0; t < T; ++t) { v1[i] += ws[t]; v2[i] = fmaf(ws[t], ws[t], v2[i]); }
+    }
+    for (int c = threadIdx.x; c < C; c += RN_NT) {
+      const bf16_t* p = x + ((int64_t)b * F + f) * T * C + c;
+      float sum[MP_SG], q[MP_SG], mean[MP_SG];
+#pragma unroll
+      for (int i = 0; i < MP_SG; ++i) { sum[i] = 0.f; q[i] = 0.f; }
+      for (int t = 0; t < T; ++t) {
+        const float v = load1t<F16>(p + (int64_t)t * C);
+#pragma unroll
+        for (int i = 0; i < MP_SG; ++i) sum[i] = fmaf(wl[(s0 + min(i, ns - 1)) * T + t], v, sum[i]);
+      }
+#pragma unroll
+      for (int i = 0; i < MP_SG; ++i) mean[i] = sum[i] / v1[i];
+      for (int t = 0; t < T; ++t) {
+        const float v = load1t<F16>(p + (int64_t)t * C);
+#pragma unroll
+        for (int i = 0; i < MP_SG; ++i) {
+          const float d = v - mean[i];
+          q[i] = fmaf(wl[(s0 + min(i, ns - 1)) * T + t] * d, d, q[i]);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < MP_SG; ++i) {
+        if (i >= ns) continue;
+        float* o = out + ((int64_t)b * S + s0 + i) * 2 * C * F;
+        o[c * F + f] = ok[i] ? mean[i] : 0.f;
+        o[C * F + c * F + f] = ok[i] ? sqrtf(q[i] / (v1[i] - v2[i] / v1[i]) + 1e-7f) : 0.f;
+      }
+    }
+  }
+}
+
+// rows with valid == 0 -> zeros (after seg_1, whose bias would otherwise be their value)
+__global__ __launch_bounds__(RN_NT) void resnet_zero_invalid_kernel(float* __restrict__ emb, int n, int dim, const int32_t* __restrict__ valid) {
+  const int64_t i = (int64_t)blockIdx.x * RN_NT + threadIdx.x;
+  if (i < (int64_t)n * dim && valid[i / dim] == 0) emb[i] = 0.f;
+}
+
 // tile shape: fewest computed positions (edges of the map), then the smallest patch
 void pick_tile(int Fo, int To, int s, int* R, int* W) {
   int64_t best = -1, bestp = 0;
@@ -320,4 +382,31 @@ int resnet_tstp_impl(sdk_ctx* ctx, const uint16_t* x, int B, int F, int T, int C
   hipLaunchKernelGGL(f16 ? resnet_tstp_kernel<true> : resnet_tstp_kernel<false>, dim3(B * F), dim3(RN_NT), 0, (hipStream_t)stream, (const bf16_t*)x, F, T, C, out);
   SDK_LAUNCH_CHECK();
   return 0;
+}
+
+int resnet_masked_tstp_impl(sdk_ctx* ctx, const uint16_t* x, int B, int F, int T, int C, int S, const float* w, const int32_t* valid, float* out,
+                            void* stream, bool f16) {
+  SDK_REQUIRE(ctx && x && w && valid && out, "resnet masked pooling: null argument");
+  SDK_REQUIRE(B > 0 && F > 0 && T >= 2 && C > 0, "resnet masked pooling: the last map has %d frames; the unbiased variance needs >= 2 (B=%d F=%d C=%d)", T, B, F, C);
+  SDK_REQUIRE(S >= 1 && (int64_t)S * T * 4 <= 48 * 1024, "resnet masked pooling: S=%d weight rows of %d frames (S >= 1, S T <= 12288: they are staged in LDS)", S, T);
+  SDK_REQUIRE((int64_t)B * F < (1ll << 31) && (int64_t)B * S < (1ll << 31), "resnet masked pooling: batch too large (B=%d F=%d S=%d)", B, F, S);
+  ProfScope ps(ctx, stream, SDK_K_RESNET_POOL, 4.0 * B * F * T * C * S, 2.0 * B * F * T * C + 8.0 * B * S * F * C + 4.0 * B * S * T);
+  hipLaunchKernelGGL(f16 ? resnet_masked_tstp_kernel<true> : resnet_masked_tstp_kernel<false>, dim3(B * F), dim3(RN_NT), (size_t)S * T * 4, (hipStream_t)stream,
+                     (const bf16_t*)x, F, T, C, S, w, valid, out);
+  SDK_LAUNCH_CHECK();
+  return 0;
+}
+
+int resnet_zero_invalid_impl(sdk_ctx* ctx, float* emb, int n, int dim, const int32_t* valid, void* stream) {
+  SDK_REQUIRE(ctx && emb && valid && n > 0 && dim > 0 && (int64_t)n * dim < (1ll << 31) - RN_NT, "resnet masked rows: bad argument (n=%d dim=%d)", n, dim);
+  ProfScope ps(ctx, stream, SDK_K_COPY, 0.0, 4.0 * n * dim);
+  hipLaunchKernelGGL(resnet_zero_invalid_kernel, dim3(ceil_div(n * dim, RN_NT)), dim3(RN_NT), 0, (hipStream_t)stream, emb, n, dim, valid);
+  SDK_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int sdk_resnet_masked_pool(sdk_ctx* ctx, const uint16_t* x, int B, int F, int T, int C, int S, const float* w, const int32_t* valid,
+                                      float* out, int fmt, void* stream) {
+  SDK_REQUIRE(fmt == 0 || fmt == 2, "sdk_resnet_masked_pool: fmt=%d (0: bf16, 2: fp16; the precise mode is not built for the ResNet34 family)", fmt);
+  return resnet_masked_tstp_impl(ctx, x, B, F, T, C, S, w, valid, out, stream, fmt == 2);
 }

@@ -655,8 +655,9 @@ int check_rdesc(const sdk_resnet_desc* d) {
   return 0;
 }
 int rn_out(int n, int s) { return (n - 1) / s + 1; }
-// the three activation buffers hold the largest map of the network; then the pooled statistics [B][2 C4 F4]
-size_t rn_layout(const sdk_resnet_desc* d, int B, int T, char* base, uint16_t** bufs, float** stats) {
+// the three activation buffers hold the largest map of the network; then the pooled statistics [rows B][2 C4 F4] (rows = 1: one per segment;
+// the masked forward has S per segment)
+size_t rn_layout(const sdk_resnet_desc* d, int B, int T, int rows, char* base, uint16_t** bufs, float** stats) {
   int F = d->n_feats, Tl = T;
   size_t big = (size_t)F * T * d->width[0];
   for (int l = 0; l < 4; ++l) {
@@ -670,31 +671,16 @@ size_t rn_layout(const sdk_resnet_desc* d, int B, int T, char* base, uint16_t** 
     char* p = take((size_t)B * big * 2);
     if (bufs) bufs[i] = (uint16_t*)p;
   }
-  char* s = take((size_t)B * 2 * d->width[3] * F * 4);
+  char* s = take((size_t)B * rows * 2 * d->width[3] * F * 4);
   if (stats) *stats = (float*)s;
   return off;
 }
-}  // namespace
 
-extern "C" size_t sdk_resnet_workspace_bytes(const sdk_resnet_desc* d, int B, int T) {
-  if (!d || B <= 0 || T <= 0 || d->n_feats <= 0) return 0;
-  return rn_layout(d, B, T, nullptr, nullptr, nullptr);
-}
-
-extern "C" int sdk_resnet_forward(sdk_ctx* ctx, const void* wblob, const sdk_resnet_desc* d, const uint16_t* feats, int ldf, int B, int T,
-                                  void* ws, size_t ws_bytes, float* emb, void* stream) {
-  SDK_REQUIRE(ctx && wblob && feats && ws && emb, "sdk_resnet_forward: null argument");
-  if (int rc = check_rdesc(d)) return rc;
-  SDK_REQUIRE(B > 0 && T >= 9 && (int64_t)B * T < (1ll << 31), "sdk_resnet_forward: bad batch (B=%d T=%d; segments need >= 9 frames)", B, T);
-  SDK_REQUIRE(ldf >= d->n_feats, "sdk_resnet_forward: ldf=%d < feature width %d", ldf, d->n_feats);
-  SDK_REQUIRE(ws_bytes >= sdk_resnet_workspace_bytes(d, B, T) && ((uintptr_t)ws % 256) == 0 && ((uintptr_t)wblob % 256) == 0,
-              "sdk_resnet_forward: workspace too small or misaligned");
+// the conv trunk shared by both forwards: feats -> the last map [B][F][Tl][C] in one of the three buffers (*last)
+int rn_trunk(sdk_ctx* ctx, const char* wb, const sdk_resnet_desc* d, const uint16_t* feats, int ldf, int B, int T, uint16_t* const* buf,
+             const uint16_t** last, int* Fl, int* Tlast, int* Cl, void* stream) {
   const bool f16 = d->precision == 2;
   const uint32_t fl = SDK_GEMM_RELU | (f16 ? SDK_GEMM_F16 : 0u);
-  uint16_t* buf[3];
-  float* stats;
-  rn_layout(d, B, T, (char*)ws, buf, &stats);
-  const char* wb = (const char*)wblob;
   auto Wp = [&](int i) { return (const uint16_t*)(wb + d->off[2 * i]); };
   auto Bp = [&](int i) { return (const float*)(wb + d->off[2 * i + 1]); };
   uint16_t *X = buf[0], *H = buf[1], *Y = buf[2];
@@ -723,9 +709,68 @@ extern "C" int sdk_resnet_forward(sdk_ctx* ctx, const void* wblob, const sdk_res
       F = Fo; Tl = To; C = Cw; conv += 2;
     }
   }
-  if (int rc = resnet_tstp_impl(ctx, X, B, F, Tl, C, stats, stream, f16)) return rc;
+  *last = X; *Fl = F; *Tlast = Tl; *Cl = C;
+  return 0;
+}
+}  // namespace
+
+extern "C" size_t sdk_resnet_workspace_bytes(const sdk_resnet_desc* d, int B, int T) {
+  if (!d || B <= 0 || T <= 0 || d->n_feats <= 0) return 0;
+  return rn_layout(d, B, T, 1, nullptr, nullptr, nullptr);
+}
+
+extern "C" size_t sdk_resnet_masked_workspace_bytes(const sdk_resnet_desc* d, int B, int T, int S) {
+  if (!d || B <= 0 || T <= 0 || S <= 0 || d->n_feats <= 0) return 0;
+  return rn_layout(d, B, T, S, nullptr, nullptr, nullptr);
+}
+
+extern "C" int sdk_resnet_last_map_frames(const sdk_resnet_desc* d, int T) {
+  if (!d || T <= 0) return 0;
+  for (int l = 1; l < 4; ++l) T = rn_out(T, 2);
+  return T;
+}
+
+extern "C" int sdk_resnet_forward(sdk_ctx* ctx, const void* wblob, const sdk_resnet_desc* d, const uint16_t* feats, int ldf, int B, int T,
+                                  void* ws, size_t ws_bytes, float* emb, void* stream) {
+  SDK_REQUIRE(ctx && wblob && feats && ws && emb, "sdk_resnet_forward: null argument");
+  if (int rc = check_rdesc(d)) return rc;
+  SDK_REQUIRE(B > 0 && T >= 9 && (int64_t)B * T < (1ll << 31), "sdk_resnet_forward: bad batch (B=%d T=%d; segments need >= 9 frames)", B, T);
+  SDK_REQUIRE(ldf >= d->n_feats, "sdk_resnet_forward: ldf=%d < feature width %d", ldf, d->n_feats);
+  SDK_REQUIRE(ws_bytes >= sdk_resnet_workspace_bytes(d, B, T) && ((uintptr_t)ws % 256) == 0 && ((uintptr_t)wblob % 256) == 0,
+              "sdk_resnet_forward: workspace too small or misaligned");
+  uint16_t* buf[3];
+  float* stats;
+  rn_layout(d, B, T, 1, (char*)ws, buf, &stats);
+  const char* wb = (const char*)wblob;
+  const uint16_t* X;
+  int F, Tl, C;
+  if (int rc = rn_trunk(ctx, wb, d, feats, ldf, B, T, buf, &X, &F, &Tl, &C, stream)) return rc;
+  if (int rc = resnet_tstp_impl(ctx, X, B, F, Tl, C, stats, stream, d->precision == 2)) return rc;
   return sdk_rows_fc(ctx, stats, 2 * C * F, nullptr, nullptr, (const float*)(wb + d->off[66]), (const float*)(wb + d->off[67]), emb, d->embed_dim, B,
                      2 * C * F, d->embed_dim, 0, stream);
+}
+
+extern "C" int sdk_resnet_forward_masked(sdk_ctx* ctx, const void* wblob, const sdk_resnet_desc* d, const uint16_t* feats, int ldf, int B, int T,
+                                         int S, const float* w, const int32_t* valid, void* ws, size_t ws_bytes, float* emb, void* stream) {
+  SDK_REQUIRE(ctx && wblob && feats && w && valid && ws && emb, "sdk_resnet_forward_masked: null argument");
+  if (int rc = check_rdesc(d)) return rc;
+  SDK_REQUIRE(B > 0 && T >= 9 && (int64_t)B * T < (1ll << 31), "sdk_resnet_forward_masked: bad batch (B=%d T=%d; segments need >= 9 frames)", B, T);
+  SDK_REQUIRE(S >= 1 && (int64_t)B * S < (1ll << 31), "sdk_resnet_forward_masked: S=%d weight rows per segment (B=%d)", S, B);
+  SDK_REQUIRE(ldf >= d->n_feats, "sdk_resnet_forward_masked: ldf=%d < feature width %d", ldf, d->n_feats);
+  const size_t need = sdk_resnet_masked_workspace_bytes(d, B, T, S);
+  SDK_REQUIRE(ws_bytes >= need, "sdk_resnet_forward_masked: workspace of %zu bytes, %zu needed (sdk_resnet_masked_workspace_bytes)", ws_bytes, need);
+  SDK_REQUIRE(((uintptr_t)ws % 256) == 0 && ((uintptr_t)wblob % 256) == 0, "sdk_resnet_forward_masked: ws / wblob must be 256-byte aligned");
+  uint16_t* buf[3];
+  float* stats;
+  rn_layout(d, B, T, S, (char*)ws, buf, &stats);
+  const char* wb = (const char*)wblob;
+  const uint16_t* X;
+  int F, Tl, C;
+  if (int rc = rn_trunk(ctx, wb, d, feats, ldf, B, T, buf, &X, &F, &Tl, &C, stream)) return rc;
+  if (int rc = resnet_masked_tstp_impl(ctx, X, B, F, Tl, C, S, w, valid, stats, stream, d->precision == 2)) return rc;
+  if (int rc = sdk_rows_fc(ctx, stats, 2 * C * F, nullptr, nullptr, (const float*)(wb + d->off[66]), (const float*)(wb + d->off[67]), emb, d->embed_dim,
+                           B * S, 2 * C * F, d->embed_dim, 0, stream)) return rc;
+  return resnet_zero_invalid_impl(ctx, emb, B * S, d->embed_dim, valid, stream);
 }
 
 // ------------------------------------------------------------------------------ centroid-linkage agglomerative clustering (ahc.hip)

@@ -1,0 +1,300 @@
+"""Speaker diarization - "who spoke when" for a recording with no transcript: the join of the PyanNet segmentation (segmentation.py), the
+ResNet34 embedding (resnet.py) and the centroid-linkage clustering (cluster.agglomerative_cluster), as PyAnnote 3.1's pipeline joins them
+("Pyannote local speaker diarization" in the upstream toolkit's backends.yaml).  The rules below are THIS build's statement, following
+PyAnnote 3.1 as best known here; no checkpoint and no pyannote code is on hand, so PARITY IS UNPINNED, like the three stages joined, and the
+tests pin these rules.
+
+  chunks      10-s chunks at segmentation.chunk_starts (step_s apart, plus one ending at the recording's end), cut on the device
+  decode      cls [C, F] uint8 = argmax powerset class per frame (ties to the lower class); activity and count come from cls alone
+  masks       per (chunk, local speaker s): pooling weights over the T4 columns of the ResNet's last map.  Column j takes segmentation frame
+              i(j) = min(F - 1, (j F) // T4); full[j] = s active at i(j); clean[j] = full[j] and count(i(j)) < 2; the weights are clean when
+              sum clean >= MIN_CLEAN_COLUMNS, else full; valid = sum w >= MIN_VALID_COLUMNS (the unbiased variance needs two columns)
+  embedding   one conv trunk per chunk, three masked statistics poolings on its last map (ResNet34.forward_masked), seg_1, L2 norm.
+              PyAnnote embeds each (chunk, speaker) pair with a full forward on the same waveform; the mask enters at the pooling only, so
+              sharing the trunk computes the same thing in a third of the work.
+  training    rows that are valid and have TRAIN_CLEAN_DEN * clean_frames >= F go to cluster.agglomerative_cluster unchanged
+  assignment  centroids = float64 mean of each cluster's training unit rows, re-normalised; every valid row with an active frame takes the
+              centroid of largest cosine (ties to the lowest); every other pair gets -1.  No training row: one cluster of all valid active
+              rows (centroid = their mean), or no speaker at all.  Constrained (Hungarian) assignment is not done.
+  stitching   on the global frame grid of segmentation.aggregate_counts (frame g, centre 270 g + 495, takes frame g + q_c of chunk c,
+              q_c = (135 - start_c) // 270): act[g, k] = chunks in which a local speaker labelled k is active; count[g] = the mean chunk count
+              rounded half up, at most 2 and max_speakers; speakers[g] = the count[g] clusters of largest act > 0 (ties to the lower cluster)
+  numbering   clusters are renumbered by first appearance in time: frame order, then slot order, of a provisional stitching pass (clusters
+              that never surface keep their relative order behind the others); the stitching is then run with the final numbers
+  turns       per speaker, runs of frames with segmentation.frames_to_ranges's boundaries; no gap filling; overlap gives simultaneous turns
+
+Decode, masks and stitching run in libsdk_hip.so (csrc/diarize.hip), the pooling in csrc/resnet.hip; the *_host functions below restate
+them in numpy for hosts that post-process stored class tables.  The host receives info, the unit embeddings, and count / speakers only.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from dataclasses import dataclass
+from typing import List, Optional, Tuple
+
+import numpy as np
+
+from .cluster import PYANNOTE_MIN_CLUSTER_SIZE, PYANNOTE_THRESHOLD
+from .segmentation import CHUNK, FRAME_HOP, POWERSET, SAMPLE_RATE, chunk_starts, frames_to_ranges
+from .segmentation import num_frames as seg_frames
+
+MIN_CLEAN_COLUMNS = 4            # ours (~0.32 s of the last map): below it the overlapped columns are kept
+MIN_VALID_COLUMNS = 2            # the unbiased variance needs two columns
+TRAIN_CLEAN_DEN = 5              # ours, after PyAnnote's filter: a training row has clean_frames >= F / 5
+MAX_LINKAGE_ROWS = 65536         # Engine.centroid_linkage serves N <= 65 536
+DEFAULT_BATCH = 128              # $SDK_DIARIZE_BATCH: chunks per forward (the ResNet workspace is ~15 MB per chunk at T = 1001)
+N_LOCAL = 3                      # local speakers of the powerset
+
+_MASK = np.array([[k in cls for k in range(N_LOCAL)] for cls in POWERSET], dtype=bool)       # [7, 3]
+_COUNT = _MASK.sum(1).astype(np.int64)
+
+
+@dataclass
+class DiarizationResult:
+    turns: List[Tuple[float, float, int]]     # (start_s, end_s, speaker), by start then speaker
+    n_speakers: int
+    centroids: np.ndarray                     # [K, embed_dim] unit fp32, in the embedding space of score_windows and enrolled profiles
+    labels: np.ndarray                        # [C, 3] int32: cluster of every (chunk, local speaker), -1: none
+    count: np.ndarray                         # [G] uint8 speakers per global frame
+    speakers: np.ndarray                      # [G, 2] int32, padded with -1
+    starts: np.ndarray                        # [C] int64 first samples of the chunks
+    info: np.ndarray                          # [C, 3, 4] int32 (active frames, clean frames, used_clean, valid)
+    cls: object = None                        # [C, F] uint8 class table (device tensor; None for an empty recording)
+
+
+# ------------------------------------------------------------------------------------------------ host restatements (numpy, vectorised)
+def global_frames(n_samples: int) -> int:
+    return max(0, (int(n_samples) - 495 + FRAME_HOP - 1) // FRAME_HOP)
+
+
+def decode_host(logp: np.ndarray) -> np.ndarray:
+    """logp [..., 7] -> uint8 argmax class (numpy's first maximum: ties to the lower class)."""
+    return np.argmax(np.asarray(logp), axis=-1).astype(np.uint8)
+
+
+def masks_host(cls: np.ndarray, T4: int):
+    """cls [B, F] -> (w [B, 3, T4] fp32, info [B, 3, 4] int32): sdk_diarize_masks."""
+    cls = np.asarray(cls)
+    B, F = cls.shape
+    active = _MASK[cls]                                                  # [B, F, 3]
+    alone = (_COUNT[cls] < 2)[:, :, None]
+    col = np.minimum(F - 1, (np.arange(T4, dtype=np.int64) * F) // T4)
+    full = active[:, col, :].transpose(0, 2, 1)                           # [B, 3, T4]
+    clean = (active & alone)[:, col, :].transpose(0, 2, 1)
+    used = clean.sum(2) >= MIN_CLEAN_COLUMNS
+    w = np.where(used[:, :, None], clean, full)
+    info = np.stack([active.sum(1), (active & alone).sum(1), used, w.sum(2) >= MIN_VALID_COLUMNS], axis=2).astype(np.int32)
+    return w.astype(np.float32), info
+
+
+def reconstruct_host(cls: np.ndarray, starts: np.ndarray, labels: np.ndarray, K: int, n_samples: int, max_speakers: Optional[int] = None):
+    """sdk_diarize_reconstruct in numpy -> (count [G] uint8, speakers [G, 2] int32, act [G, K] int32, nc [G] int64)."""
+    cls, labels = np.asarray(cls), np.asarray(labels)
+    Cn, F = cls.shape
+    G = global_frames(n_samples)
+    cap = 2 if max_speakers is None else min(2, int(max_speakers))
+    act = np.zeros((G, K), np.int32)
+    cnt, nc = np.zeros(G, np.int64), np.zeros(G, np.int64)
+    for c in range(Cn):
+        q = (135 - int(starts[c])) // FRAME_HOP
+        g = np.arange(F) - q
+        m = (g >= 0) & (g < G)
+        cnt[g[m]] += _COUNT[cls[c][m]]
+        nc[g[m]] += 1
+        on = _MASK[cls[c][m]]                                             # [frames, 3]
+        for k in {int(v) for v in labels[c] if v >= 0}:
+            act[g[m], k] += on[:, labels[c] == k].any(1)
+    count = np.where(nc > 0, np.minimum((2 * cnt + nc) // np.maximum(2 * nc, 1), cap), 0)
+    order = np.argsort(-act, axis=1, kind="stable")[:, :2] if K else np.zeros((G, 0), np.int64)      # stable: ties to the lower cluster
+    speakers = np.full((G, 2), -1, np.int32)
+    for slot in range(min(2, K)):
+        k = order[:, slot]
+        ok = (count > slot) & (act[np.arange(G), k] > 0)
+        speakers[ok, slot] = k[ok]
+    return count.astype(np.uint8), speakers, act, nc
+
+
+def training_rows(info: np.ndarray, F: int) -> np.ndarray:
+    """Rows (c * 3 + s) of the clustering's training set: valid and TRAIN_CLEAN_DEN * clean_frames >= F."""
+    i = np.asarray(info).reshape(-1, 4)
+    return np.flatnonzero((i[:, 3] != 0) & (TRAIN_CLEAN_DEN * i[:, 1].astype(np.int64) >= F))
+
+
+def assign_rows(E: np.ndarray, info: np.ndarray, train: np.ndarray, train_labels: np.ndarray):
+    """Unit rows E [C * 3, d], info, the training rows and their cluster labels -> (labels [C, 3] int32, centroids [K, d] fp32 unit)."""
+    i = np.asarray(info).reshape(-1, 4)
+    E64 = np.asarray(E, dtype=np.float64)
+    cand = np.flatnonzero((i[:, 3] != 0) & (i[:, 0] > 0))
+    labels = np.full(i.shape[0], -1, np.int32)
+    if len(train):
+        K = int(np.max(train_labels)) + 1
+        cent = np.zeros((K, E64.shape[1]))
+        np.add.at(cent, np.asarray(train_labels, dtype=np.int64), E64[train])
+        cent /= np.bincount(train_labels, minlength=K)[:, None]
+    elif len(cand):
+        cent = E64[cand].mean(0, keepdims=True)
+    else:
+        return labels.reshape(-1, N_LOCAL), np.zeros((0, E64.shape[1]), np.float32)
+    cent /= np.maximum(np.linalg.norm(cent, axis=1, keepdims=True), 1e-300)
+    if len(cand):
+        labels[cand] = np.argmax(E64[cand] @ cent.T, axis=1)              # first maximum: ties to the lowest centroid
+    return labels.reshape(-1, N_LOCAL), cent.astype(np.float32)
+
+
+def appearance_order(speakers: np.ndarray, K: int) -> np.ndarray:
+    """new id of every provisional cluster: by first appearance in speakers [G, 2] (frame order, then slot order); clusters that never
+    appear follow in their old order."""
+    flat = np.asarray(speakers).reshape(-1)
+    flat = flat[flat >= 0]
+    _, first = np.unique(flat, return_index=True)
+    seen = flat[np.sort(first)]
+    rest = np.setdiff1d(np.arange(K), seen)
+    new = np.empty(K, np.int64)
+    new[np.concatenate([seen, rest]).astype(np.int64)] = np.arange(K)
+    return new
+
+
+def turns_from_frames(speakers: np.ndarray, K: int) -> List[Tuple[float, float, int]]:
+    out = []
+    sp = np.asarray(speakers)
+    for k in range(K):
+        out += [(a, b, k) for a, b in frames_to_ranges((sp == k).any(1))]
+    return sorted(out, key=lambda t: (t[0], t[2]))
+
+
+def to_rttm(turns, uri: str) -> str:
+    """Standard RTTM: one `SPEAKER <uri> 1 <start> <dur> <NA> <NA> SPEAKER_%02d <NA> <NA>` line per turn, 3 decimals."""
+    return "".join(f"SPEAKER {uri} 1 {a:.3f} {b - a:.3f} <NA> <NA> SPEAKER_{k:02d} <NA> <NA>\n" for a, b, k in turns)
+
+
+# ------------------------------------------------------------------------------------------------ device stages
+def powerset_decode(eng, logp):
+    """logp [C, F, 7] fp32 (device) -> cls [C, F] uint8 (device): sdk_powerset_decode."""
+    import torch
+    from ._lib import check
+    from .ops import _stream
+    if logp.dim() != 3 or logp.shape[2] != 7 or logp.dtype != torch.float32:
+        raise ValueError(f"powerset_decode: logp must be fp32 [C, F, 7], got {tuple(logp.shape)} {logp.dtype}")
+    logp = logp.contiguous()
+    cls = torch.empty(logp.shape[:2], dtype=torch.uint8, device=logp.device)
+    check(eng.lib.sdk_powerset_decode(eng.ctx, logp.data_ptr(), logp.shape[0], logp.shape[1], cls.data_ptr(), _stream()), "sdk_powerset_decode")
+    return cls
+
+
+def diarize_masks(eng, cls, T4: int):
+    """cls [B, F] uint8 (device) -> (w [B, 3, T4] fp32, info [B, 3, 4] int32) on the device: sdk_diarize_masks."""
+    import torch
+    from ._lib import check
+    from .ops import _stream
+    if cls.dim() != 2 or cls.dtype != torch.uint8 or not cls.is_contiguous():
+        raise ValueError(f"diarize_masks: cls must be a contiguous uint8 [B, F] tensor, got {tuple(cls.shape)} {cls.dtype}")
+    B, F = cls.shape
+    w = torch.empty((B, N_LOCAL, T4), dtype=torch.float32, device=cls.device)
+    info = torch.empty((B, N_LOCAL, 4), dtype=torch.int32, device=cls.device)
+    check(eng.lib.sdk_diarize_masks(eng.ctx, cls.data_ptr(), B, F, int(T4), w.data_ptr(), info.data_ptr(), _stream()), "sdk_diarize_masks")
+    return w, info
+
+
+def diarize_reconstruct(eng, cls, starts, labels, K: int, n_samples: int, max_speakers: Optional[int] = None, want_act: bool = False):
+    """cls [C, F] uint8, starts [C] int32 ascending, labels [C, 3] int32 (all on the device) -> (count [G] uint8, speakers [G, 2] int32,
+    act [G, K] int32 or None) on the device: sdk_diarize_reconstruct."""
+    import torch
+    from ._lib import check
+    from .ops import _stream
+    if cls.dim() != 2 or cls.dtype != torch.uint8 or not cls.is_contiguous():
+        raise ValueError(f"diarize_reconstruct: cls must be a contiguous uint8 [C, F] tensor, got {tuple(cls.shape)} {cls.dtype}")
+    Cn, F = cls.shape
+    if starts.dtype != torch.int32 or tuple(starts.shape) != (Cn,) or labels.dtype != torch.int32 or tuple(labels.shape) != (Cn, N_LOCAL):
+        raise ValueError(f"diarize_reconstruct: starts int32 [{Cn}] and labels int32 [{Cn}, 3] expected, got {tuple(starts.shape)} {starts.dtype}, "
+                         f"{tuple(labels.shape)} {labels.dtype}")
+    starts, labels = starts.contiguous(), labels.contiguous()
+    G = int(eng.lib.sdk_diarize_frames(int(n_samples)))
+    cap = 2 if max_speakers is None else min(2, int(max_speakers))
+    count = torch.zeros((G,), dtype=torch.uint8, device=cls.device)
+    speakers = torch.full((G, 2), -1, dtype=torch.int32, device=cls.device)
+    act = torch.zeros((G, int(K)), dtype=torch.int32, device=cls.device) if want_act else None
+    check(eng.lib.sdk_diarize_reconstruct(eng.ctx, cls.data_ptr(), starts.data_ptr(), labels.data_ptr(), Cn, F, int(K), int(n_samples), cap,
+                                          count.data_ptr(), speakers.data_ptr(), act.data_ptr() if want_act else None, _stream()),
+          "sdk_diarize_reconstruct")
+    return count, speakers, act
+
+
+class Diarizer:
+    """The pipeline on one ops.Engine: a resident segmentation.Segmentation and a resident resnet.ResNet34."""
+
+    def __init__(self, engine, segmentation, resnet):
+        self.eng, self.seg, self.resnet = engine, segmentation, resnet
+
+    def embed_chunks(self, rec, n_samples: int, starts_dev, logp=None):
+        """One batch of chunks: (cls [B, F] uint8, info [B, 3, 4] int32, unit embeddings [B * 3, d] fp32), all on the device."""
+        from .ops import num_frames as fbank_frames
+        B = int(starts_dev.numel())
+        lp = logp if logp is not None else self.seg.forward(rec, starts_dev)
+        cls = powerset_decode(self.eng, lp)
+        T = fbank_frames(CHUNK)
+        w, info = diarize_masks(self.eng, cls, self.resnet.last_map_frames(T))
+        feats = self.eng.fbank_windows(rec.data_ptr(), n_samples, starts_dev.data_ptr(), B, CHUNK)
+        emb = self.resnet.forward_masked(feats, B, T, w, info[:, :, 3].contiguous())
+        return cls, info, self.eng.l2norm(emb)[0]
+
+    def run(self, samples, step_s: float = 1.0, threshold: float = PYANNOTE_THRESHOLD, min_cluster_size: int = PYANNOTE_MIN_CLUSTER_SIZE,
+            max_speakers: Optional[int] = None, logp=None) -> DiarizationResult:
+        """samples: 16 kHz mono int16 (host) -> DiarizationResult.  logp [C, 589, 7] (fp32, host or device) replaces the segmentation
+        model's output (the chunks are chunk_starts(len(samples), step_s)).  The default threshold and size are PyAnnote 3.1's, tuned for
+        ITS trained embedding; with other weights pass a threshold of your own."""
+        import torch
+        from .cluster import agglomerative_cluster
+        eng = self.eng
+        x = np.ascontiguousarray(samples, dtype=np.int16).reshape(-1)
+        d = self.resnet.cfg.embed_dim
+        if x.size == 0:
+            return DiarizationResult([], 0, np.zeros((0, d), np.float32), np.zeros((0, N_LOCAL), np.int32), np.zeros(0, np.uint8),
+                                     np.full((0, 2), -1, np.int32), np.zeros(0, np.int64), np.zeros((0, N_LOCAL, 4), np.int32))
+        if max_speakers is not None and int(max_speakers) < 0:
+            raise ValueError(f"max_speakers={max_speakers}: must be None or >= 0")
+        st = chunk_starts(x.size, step_s)
+        Cn, F = len(st), seg_frames(CHUNK)
+        if N_LOCAL * Cn > MAX_LINKAGE_ROWS:
+            raise ValueError(f"diarize: {Cn} chunks at step_s={step_s} give up to {N_LOCAL * Cn} embeddings to cluster; the centroid linkage serves at "
+                             f"most {MAX_LINKAGE_ROWS} rows ({MAX_LINKAGE_ROWS // N_LOCAL} chunks): raise step_s or split the recording")
+        if logp is not None:
+            logp = torch.as_tensor(logp, dtype=torch.float32).to(eng.device)
+            if tuple(logp.shape) != (Cn, F, 7):
+                raise ValueError(f"diarize: injected logp must be [{Cn}, {F}, 7] for {x.size} samples at step_s={step_s}, got {tuple(logp.shape)}")
+        if eng.precision != self.resnet.precision:
+            eng.set_precision(self.resnet.precision)            # the front end's output format follows the embedding's numerical contract
+        rec = torch.from_numpy(x).to(eng.device)
+        starts_dev = torch.from_numpy(st.astype(np.int32)).to(eng.device)
+        batch = max(1, int(os.environ.get("SDK_DIARIZE_BATCH", str(DEFAULT_BATCH))))
+        cls = torch.empty((Cn, F), dtype=torch.uint8, device=eng.device)
+        infos, embs = [], []
+        for a in range(0, Cn, batch):
+            c, i, e = self.embed_chunks(rec, x.size, starts_dev[a:a + batch], None if logp is None else logp[a:a + batch])
+            cls[a:a + batch] = c
+            infos.append(i)
+            embs.append(e)
+        E_dev = torch.cat(embs)
+        info = torch.cat(infos).cpu().numpy()
+        E = E_dev.cpu().numpy()
+        E[info.reshape(-1, 4)[:, 3] == 0] = 0.0                 # rows that are not valid are never read as embeddings
+        train = training_rows(info, F)
+        if len(train) > 1:
+            tl = agglomerative_cluster(eng, E_dev.index_select(0, torch.from_numpy(train).to(eng.device)).contiguous(), threshold, min_cluster_size).labels
+        else:
+            tl = np.zeros(len(train), np.int32)
+        labels, cent = assign_rows(E, info, train, tl)
+        K = cent.shape[0]
+
+        def stitch(lab):
+            cnt, spk, _ = diarize_reconstruct(eng, cls, starts_dev, torch.from_numpy(np.ascontiguousarray(lab, dtype=np.int32)).to(eng.device),
+                                              max(K, 1), x.size, max_speakers)
+            return cnt.cpu().numpy(), spk.cpu().numpy()
+        count, speakers = stitch(labels)
+        if K > 1:
+            new = appearance_order(speakers, K)
+            if not np.array_equal(new, np.arange(K)):
+                labels = np.where(labels >= 0, new[np.maximum(labels, 0)], -1).astype(np.int32)
+                cent = cent[np.argsort(new)]
+                count, speakers = stitch(labels)
+        return DiarizationResult(turns_from_frames(speakers, K), K, cent, labels, count, speakers, st, info, cls)

@@ -239,6 +239,31 @@ class ResNet34:
                                      ws.data_ptr(), ws.numel(), emb.data_ptr(), _stream()), "sdk_resnet_forward")
         return emb
 
+    def last_map_frames(self, T: int) -> int:
+        """Width T4 of the last map for segments of T fbank frames (sdk_resnet_last_map_frames)."""
+        return int(self.eng.lib.sdk_resnet_last_map_frames(C.byref(self.desc), int(T)))
+
+    def forward_masked(self, feats, B: int, T: int, w, valid):
+        """The forward with S weighted poolings per segment (sdk_resnet_forward_masked): the conv trunk runs once per segment, one pooling
+        launch writes the S statistics rows.  w [B, S, T4] fp32 >= 0 and valid [B, S] int32 (device) -> raw embeddings [B * S, embed_dim]
+        fp32, row b * S + s; rows with valid == 0 are zeros."""
+        import torch
+        from ._lib import check
+        from .ops import _stream
+        lib = self.eng.lib
+        T4 = self.last_map_frames(T)
+        if w.dim() != 3 or w.shape[0] != B or w.shape[2] != T4 or w.dtype != torch.float32 or not w.is_contiguous():
+            raise ValueError(f"forward_masked: w must be a contiguous fp32 [B = {B}, S, T4 = {T4}] tensor, got {tuple(w.shape)} {w.dtype}")
+        S = int(w.shape[1])
+        if tuple(valid.shape) != (B, S) or valid.dtype != torch.int32 or not valid.is_contiguous():
+            raise ValueError(f"forward_masked: valid must be a contiguous int32 [{B}, {S}] tensor, got {tuple(valid.shape)} {valid.dtype}")
+        ws = self.eng._scratch_bytes("resnet", lib.sdk_resnet_masked_workspace_bytes(C.byref(self.desc), B, T, S))
+        emb = torch.empty((B * S, self.cfg.embed_dim), dtype=torch.float32, device=self.eng.device)
+        check(lib.sdk_resnet_forward_masked(self.eng.ctx, self.blob.data_ptr(), C.byref(self.desc), feats.data_ptr(), feats.stride(0), B, T, S,
+                                            w.data_ptr(), valid.data_ptr(), ws.data_ptr(), ws.numel(), emb.data_ptr(), _stream()),
+              "sdk_resnet_forward_masked")
+        return emb
+
     def embed_pcm(self, pcm):
         from .ops import num_frames
         B, S = pcm.shape
