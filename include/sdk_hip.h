@@ -35,7 +35,8 @@
  *     sdk_centroid_linkage_workspace_bytes  sdk_centroid_linkage                                    k6 threshold path (cluster.agglomerative_cluster)
  *     sdk_segmentation_frames  sdk_segmentation_workspace_bytes  sdk_segmentation_forward               speaker segmentation (PyanNet, segmentation.py)
  *     sdk_powerset_decode  sdk_diarize_masks  sdk_resnet_last_map_frames  sdk_resnet_masked_workspace_bytes
- *     sdk_resnet_forward_masked  sdk_diarize_frames  sdk_diarize_reconstruct                              speaker diarization (diarize.py)
+ *     sdk_resnet_forward_masked  sdk_diarize_frames  sdk_diarize_reconstruct  sdk_diarize_centroids  sdk_diarize_assign
+ *                                                                                                       speaker diarization (diarize.py)
  * BUILDING BLOCKS AND KNOBS - exported for the parity tests and the A/B tools, free to change between rounds, not for binding:
  *     sdk_conv_gemm*  sdk_colstats_finish  sdk_res2net_chain*  sdk_se_*  sdk_asp_*  sdk_rows_fc  (pieces of sdk_ecapa_forward)
  *     sdk_resnet_conv2d  (piece of sdk_resnet_forward)  sdk_resnet_masked_pool  (piece of sdk_resnet_forward_masked)
@@ -497,6 +498,24 @@ int sdk_diarize_masks(sdk_ctx* ctx, const uint8_t* cls, int B, int F, int T4, fl
 int64_t sdk_diarize_frames(int64_t n_samples);
 int sdk_diarize_reconstruct(sdk_ctx* ctx, const uint8_t* cls, const int32_t* starts, const int32_t* labels, int C, int F, int K,
                             int64_t n_samples, int max_speakers, uint8_t* count, int32_t* speakers, int32_t* act, void* stream);
+
+/* ---- the assignment stage of the diarization (diarize.py "assignment"; csrc/diarize.hip): float64 arithmetic in a fixed order, one owner per
+ *      output element, no atomics: bit-identical run to run.  E [3 C][d] fp32 unit rows; d a multiple of 64, at most 512.  A candidate
+ *      of chunk c is a local speaker with info valid != 0 and active frames > 0; no other row of E is read (it may hold anything).
+ *   sdk_diarize_centroids : rows [n] int32 ascending (rows of E), labels [n] int32 in [0, K) (both on the device) -> cent [K][d] fp32 unit
+ *        rows and cent64 [K][d] float64 (or NULL), the same before the final rounding: the float64 sum of each cluster's rows in ascending
+ *        row order, divided by the count, divided by its norm (clamped at 1e-300).  A cluster without rows gives a zero row; a label
+ *        outside [0, K) belongs to no cluster.  rows must lie inside E: the library does not read them back to check.
+ *   sdk_diarize_assign : info [C][3][4] int32 (sdk_diarize_masks), cent64 [K][d] float64 (16-byte aligned) -> labels [C][3] int32 and
+ *        score [C][3] fp32 (the cosine of each row to the centroid it got, 0 where the label is -1).  Cosines are float64 dot products
+ *        summed in column order.  constrained = 0: every candidate takes its largest cosine (ties to the lower cluster).  constrained = 1:
+ *        per chunk with m candidates, among all maps that give n = min(m, K) candidates pairwise different clusters and the others -1,
+ *        the one with the largest total cosine (summed in slot order); ties to the lexicographically smallest label tuple in slot order,
+ *        -1 after every cluster.  A NaN cosine never wins.  One launch, one wave per chunk; any K >= 1, any C >= 0. */
+int sdk_diarize_centroids(sdk_ctx* ctx, const float* E, const int32_t* rows, const int32_t* labels, int n, int K, int d, float* cent,
+                          double* cent64, void* stream);
+int sdk_diarize_assign(sdk_ctx* ctx, const float* E, const int32_t* info, const double* cent64, int C, int K, int d, int constrained,
+                       int32_t* labels, float* score, void* stream);
 
 /* ---- audio conversion to the AudioProfile: replaces the ffmpeg subprocess the reference's backends
  *      run before upload (audio_profiles.py:70-100 `format_ffmpeg_args`; speechmatics_backend.py:231-281).

@@ -149,6 +149,8 @@ SIGNATURES = {
     "sdk_diarize_masks": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "sdk_diarize_frames": (_i64, [_i64]),
     "sdk_diarize_reconstruct": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i, _vp, _vp, _vp, _vp]),
+    "sdk_diarize_centroids": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "sdk_diarize_assign": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sdk_segmentation_frames": (_i, [_i]),
     "sdk_segmentation_workspace_bytes": (_sz, [_vp, _i, _i]),
     "sdk_segmentation_forward": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),

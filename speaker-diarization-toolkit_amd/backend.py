@@ -429,8 +429,10 @@ class Backend(EmbeddingBackend):
         """Who spoke when, with no transcript and no enrolled profiles: a recording (16 kHz mono int16 samples, or the path of an audio file,
         decoded to the audio profile) -> diarize.DiarizationResult (turns [(start_s, end_s, speaker)], n_speakers, unit centroids in the
         embedding space of score_windows, labels, count, speakers); diarize.to_rttm(result.turns, uri) writes RTTM.  Keywords: step_s,
-        threshold, min_cluster_size, max_speakers, logp (diarize.Diarizer.run).  The default threshold is PyAnnote 3.1's, tuned for its
-        trained ResNet34 ($SDK_RESNET_WEIGHTS); with the synthetic weights pass a threshold of your own."""
+        threshold, min_cluster_size, max_speakers, logp, constrained (diarize.Diarizer.run).  The default threshold is PyAnnote 3.1's, tuned
+        for its trained ResNet34 ($SDK_RESNET_WEIGHTS); with the synthetic weights pass a threshold of your own.  constrained=True
+        (PyAnnote's constrained_argmax; default False): the local speakers of a chunk get pairwise different clusters, the one-to-one
+        matching of largest total cosine, computed on the device; the result then carries scores [C, 3]."""
         dz = self.diarizer()
         if isinstance(samples_or_path, (str, Path)):
             samples_or_path = decode_to_profile(Path(samples_or_path), self.engine(), self.get_audio_profile())

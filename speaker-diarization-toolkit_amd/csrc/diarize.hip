@@ -1,13 +1,16 @@
-// Speaker diarization (diarize.py): the integer stages that join the segmentation model, the ResNet34 embedding and the clustering.
+// Speaker diarization (diarize.py): the stages that join the segmentation model, the ResNet34 embedding and the clustering.
 //
 //   powerset_decode_kernel     logp [C][F][7] -> cls [C][F]: the argmax class, ties to the lower class.  Everything later reads cls.
 //   diarize_masks_kernel       cls [B][F] -> the pooling weights of sdk_resnet_forward_masked, w [B][3][T4], and info [B][3][4] per
 //                              (chunk, local speaker): (active frames, clean frames, used_clean, valid).
 //   diarize_reconstruct_kernel cls, chunk starts, labels [C][3] -> count [G], speakers [G][2] (and act [G][K]) on the global frame grid of
 //                              segmentation.aggregate_counts.
+//   diarize_centroids_kernel   unit rows E, training rows and their cluster labels -> the clusters' unit centroids (float64 sums in row order).
+//   diarize_assign_kernel      E, info, centroids -> labels [C][3] and score [C][3]: every candidate row to the centroid of largest cosine, or
+//                              (constrained) the one-to-one matching of a chunk's candidates to clusters with the largest total cosine.
 //
-// Every kernel is a gather: one owner per output element, integer arithmetic (the weights are 0 / 1), no atomics, so the results are
-// bit-identical run to run.
+// Every kernel is a gather: one owner per output element, no atomics, every sum in a fixed order (the first three kernels are integer
+// arithmetic: the weights are 0 / 1), so the results are bit-identical run to run.
 #include "common.hpp"
 
 namespace {
@@ -147,6 +150,200 @@ __global__ __launch_bounds__(DZ_NT) void diarize_reconstruct_kernel(const uint8_
   speakers[2 * (int64_t)g + 1] = n >= 2 ? k2 : -1;
 }
 
+// ---- assignment (diarize.py "assignment"): centroids of the training rows, then every candidate row to a centroid ------------------------
+constexpr int DZ_MAX_D = 512;        // embedding width served by the two assignment kernels (a multiple of 64)
+constexpr int DZ_TILE = 256;         // (row, label) pairs staged in LDS per step of the centroid sum
+
+// block = one cluster k, thread = the columns tid, tid + 256.  The n (row, label) pairs pass through LDS in tiles; every thread walks them in
+// ascending order and adds the rows labelled k in float64, so a column's sum has one owner and one order.  Then mean, norm (block sum of
+// squares in a fixed tree), unit row.  A cluster without rows gives a zero row.
+__global__ __launch_bounds__(DZ_NT) void diarize_centroids_kernel(const float* __restrict__ E, const int32_t* __restrict__ rows,
+                                                                  const int32_t* __restrict__ labels, int n, int d, float* __restrict__ cent,
+                                                                  double* __restrict__ cent64) {
+  __shared__ int32_t s_row[DZ_TILE];
+  __shared__ int32_t s_lab[DZ_TILE];
+  __shared__ double s_red[DZ_NT / 64];
+  const int k = blockIdx.x, tid = threadIdx.x;
+  const int j0 = tid, j1 = tid + DZ_NT;
+  double a0 = 0.0, a1 = 0.0;
+  int cnt = 0;
+  for (int i0 = 0; i0 < n; i0 += DZ_TILE) {
+    const int m = min(DZ_TILE, n - i0);
+    __syncthreads();
+    if (tid < m) {
+      s_row[tid] = rows[i0 + tid];
+      s_lab[tid] = labels[i0 + tid];
+    }
+    __syncthreads();
+    for (int i = 0; i < m; ++i) {
+      if (s_lab[i] != k) continue;                     // uniform over the block
+      const float* e = E + (int64_t)s_row[i] * d;
+      ++cnt;
+      if (j0 < d) a0 += (double)e[j0];
+      if (j1 < d) a1 += (double)e[j1];
+    }
+  }
+  if (cnt) { a0 /= (double)cnt; a1 /= (double)cnt; }
+  double q = (j0 < d ? a0 * a0 : 0.0) + (j1 < d ? a1 * a1 : 0.0);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+  if ((tid & 63) == 0) s_red[tid >> 6] = q;
+  __syncthreads();
+  double nrm = 0.0;
+#pragma unroll
+  for (int w = 0; w < DZ_NT / 64; ++w) nrm += s_red[w];
+  nrm = fmax(sqrt(nrm), 1e-300);
+  a0 /= nrm;
+  a1 /= nrm;
+  if (j0 < d) {
+    cent[(int64_t)k * d + j0] = (float)a0;
+    if (cent64) cent64[(int64_t)k * d + j0] = a0;
+  }
+  if (j1 < d) {
+    cent[(int64_t)k * d + j1] = (float)a1;
+    if (cent64) cent64[(int64_t)k * d + j1] = a1;
+  }
+}
+
+// (value, cluster) lists of a row's three largest cosines, best first; ties to the lower cluster; idx < 0: empty
+struct Top3 { double v[3]; int k[3]; };
+
+__device__ __forceinline__ bool better(double v, int k, double bv, int bk) { return bk < 0 || v > bv || (v == bv && k < bk); }
+
+__device__ __forceinline__ void top3_push(Top3& t, double v, int k) {
+  if (!(v == v)) return;                               // a NaN never wins
+  if (better(v, k, t.v[0], t.k[0])) {
+    t.v[2] = t.v[1]; t.k[2] = t.k[1]; t.v[1] = t.v[0]; t.k[1] = t.k[0]; t.v[0] = v; t.k[0] = k;
+  } else if (better(v, k, t.v[1], t.k[1])) {
+    t.v[2] = t.v[1]; t.k[2] = t.k[1]; t.v[1] = v; t.k[1] = k;
+  } else if (better(v, k, t.v[2], t.k[2])) {
+    t.v[2] = v; t.k[2] = k;
+  }
+}
+
+// one wave per chunk.  The chunk's candidate rows go to LDS as float64; lane l takes the clusters l, l + 64, ..: one float64 dot product per
+// (candidate, cluster), summed over the columns in ascending order, and keeps the three best per candidate.  Three rounds of a wave arg-max
+// merge the lanes' lists; lane 0 then walks the tuples.  Every candidate picks among its (at most) three best clusters, or -1 when there
+// are fewer clusters than candidates: at most 4^3 tuples, of which the valid ones (n = min(m, K) pairwise different clusters) are compared by
+// their total, summed in slot order, then by the label tuple with -1 last.
+__global__ __launch_bounds__(64) void diarize_assign_kernel(const float* __restrict__ E, const int32_t* __restrict__ info,
+                                                            const double* __restrict__ cent, int K, int d, int constrained,
+                                                            int32_t* __restrict__ labels, float* __restrict__ score) {
+  __shared__ double s_e[3][DZ_MAX_D];
+  __shared__ double s_v[3][3];
+  __shared__ int s_k[3][3];
+  const int c = blockIdx.x, lane = threadIdx.x;
+  bool cand[3];
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    const int32_t* in = info + ((int64_t)c * 3 + s) * 4;
+    cand[s] = in[3] != 0 && in[0] > 0;
+  }
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    if (cand[s]) {
+      const float* e = E + ((int64_t)c * 3 + s) * d;
+      for (int j = lane; j < d; j += 64) s_e[s][j] = (double)e[j];
+    }
+  }
+  __syncthreads();
+  Top3 t[3];
+#pragma unroll
+  for (int s = 0; s < 3; ++s)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { t[s].v[i] = 0.0; t[s].k[i] = -1; }
+  for (int k = lane; k < K; k += 64) {
+    const double* ck = cent + (int64_t)k * d;
+    double a[3] = {0.0, 0.0, 0.0};
+    for (int j = 0; j < d; j += 2) {
+      const double2 w = *reinterpret_cast<const double2*>(ck + j);
+#pragma unroll
+      for (int s = 0; s < 3; ++s) {
+        if (cand[s]) {
+          a[s] = fma(s_e[s][j], w.x, a[s]);
+          a[s] = fma(s_e[s][j + 1], w.y, a[s]);
+        }
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < 3; ++s) if (cand[s]) top3_push(t[s], a[s], k);
+  }
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {                      // round r: the best head of the wave, popped from the lane that holds it
+      double v = t[s].v[0];
+      int k = t[s].k[0];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const double ov = __shfl_xor(v, o, 64);
+        const int ok = __shfl_xor(k, o, 64);
+        if (ok >= 0 && better(ov, ok, v, k)) { v = ov; k = ok; }
+      }
+      if (k >= 0 && k == t[s].k[0]) {
+        t[s].v[0] = t[s].v[1]; t[s].k[0] = t[s].k[1]; t[s].v[1] = t[s].v[2]; t[s].k[1] = t[s].k[2]; t[s].k[2] = -1;
+      }
+      if (lane == 0) { s_v[s][r] = v; s_k[s][r] = k; }
+    }
+  }
+  if (lane != 0) return;
+  int slot[3], m = 0;
+  int32_t lab[3] = {-1, -1, -1};
+  float sc[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < 3; ++s) if (cand[s]) slot[m++] = s;
+  if (!constrained) {
+    for (int i = 0; i < m; ++i) {
+      const int s = slot[i];
+      if (s_k[s][0] >= 0) { lab[s] = s_k[s][0]; sc[s] = (float)s_v[s][0]; }
+    }
+  } else if (m > 0) {
+    const int n = min(m, K), nopt = K < m ? 4 : 3;     // option 3 of a candidate: no cluster (only when some candidate must go without)
+    bool have = false;
+    double best = 0.0;
+    int bl[3] = {-1, -1, -1}, bo[3] = {0, 0, 0};
+    const int total_tuples = m == 1 ? nopt : m == 2 ? nopt * nopt : nopt * nopt * nopt;
+    for (int u = 0; u < total_tuples; ++u) {
+      int o[3], l[3], used = 0;
+      int rest = u;
+      for (int i = m - 1; i >= 0; --i) { o[i] = rest % nopt; rest /= nopt; }      // slot 0 is the most significant digit
+      bool ok = true;
+      double tot = 0.0;
+      for (int i = 0; i < m && ok; ++i) {
+        l[i] = o[i] < 3 ? s_k[slot[i]][o[i]] : -1;
+        if (o[i] < 3) {
+          ok = l[i] >= 0;
+          for (int p = 0; p < i; ++p) ok = ok && l[p] != l[i];
+          if (ok) { tot += s_v[slot[i]][o[i]]; ++used; }
+        }
+      }
+      if (!ok || used != n) continue;
+      bool take = !have || tot > best;
+      if (have && tot == best) {                       // the smaller label tuple in slot order, -1 after every cluster
+        for (int i = 0; i < m; ++i) {
+          const unsigned x = (unsigned)l[i], y = (unsigned)bl[i];               // -1 -> 0xffffffff
+          if (x != y) { take = x < y; break; }
+        }
+      }
+      if (take) {
+        have = true;
+        best = tot;
+        for (int i = 0; i < m; ++i) { bl[i] = l[i]; bo[i] = o[i]; }
+      }
+    }
+    if (have)
+      for (int i = 0; i < m; ++i) {
+        lab[slot[i]] = bl[i];
+        sc[slot[i]] = bl[i] >= 0 ? (float)s_v[slot[i]][bo[i]] : 0.f;
+      }
+  }
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    labels[(int64_t)c * 3 + s] = lab[s];
+    score[(int64_t)c * 3 + s] = sc[s];
+  }
+}
+
 }  // namespace
 
 extern "C" int sdk_powerset_decode(sdk_ctx* ctx, const float* logp, int C, int F, uint8_t* cls, void* stream) {
@@ -191,6 +388,35 @@ extern "C" int sdk_diarize_reconstruct(sdk_ctx* ctx, const uint8_t* cls, const i
   ProfScope ps(ctx, stream, SDK_K_COPY, 0.0, (double)G * (9.0 + (act ? 4.0 * K : 0.0)) + (double)C * (F + 20.0));
   hipLaunchKernelGGL(diarize_reconstruct_kernel, dim3((unsigned)((G + DZ_NT - 1) / DZ_NT)), dim3(DZ_NT), 0, (hipStream_t)stream, cls, starts, labels, C, F, K,
                      (int)G, max_speakers, count, speakers, act);
+  SDK_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int sdk_diarize_centroids(sdk_ctx* ctx, const float* E, const int32_t* rows, const int32_t* labels, int n, int K, int d, float* cent,
+                                     double* cent64, void* stream) {
+  SDK_REQUIRE(ctx, "sdk_diarize_centroids: null context");
+  SDK_REQUIRE(n >= 0 && K >= 1, "sdk_diarize_centroids: n=%d K=%d (n at least 0, K at least 1)", n, K);
+  SDK_REQUIRE(d >= 64 && d <= DZ_MAX_D && d % 64 == 0, "sdk_diarize_centroids: d=%d not supported (a multiple of 64, at most %d)", d, DZ_MAX_D);
+  SDK_REQUIRE(cent && (n == 0 || (E && rows && labels)), "sdk_diarize_centroids: null argument (E=%p rows=%p labels=%p cent=%p)", (const void*)E,
+              (const void*)rows, (const void*)labels, (void*)cent);
+  ProfScope ps(ctx, stream, SDK_K_COPY, 2.0 * n * d, (double)n * (4.0 * d + 8.0 * K) + 12.0 * K * d);
+  hipLaunchKernelGGL(diarize_centroids_kernel, dim3(K), dim3(DZ_NT), 0, (hipStream_t)stream, E, rows, labels, n, d, cent, cent64);
+  SDK_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int sdk_diarize_assign(sdk_ctx* ctx, const float* E, const int32_t* info, const double* cent64, int C, int K, int d, int constrained,
+                                  int32_t* labels, float* score, void* stream) {
+  SDK_REQUIRE(ctx, "sdk_diarize_assign: null context");
+  SDK_REQUIRE(C >= 0 && K >= 1, "sdk_diarize_assign: C=%d K=%d (C at least 0, K at least 1)", C, K);
+  SDK_REQUIRE(d >= 64 && d <= DZ_MAX_D && d % 64 == 0, "sdk_diarize_assign: d=%d not supported (a multiple of 64, at most %d)", d, DZ_MAX_D);
+  SDK_REQUIRE(constrained == 0 || constrained == 1, "sdk_diarize_assign: constrained=%d (0 or 1)", constrained);
+  if (C == 0) return 0;
+  SDK_REQUIRE(E && info && cent64 && labels && score, "sdk_diarize_assign: null argument (E=%p info=%p cent64=%p labels=%p score=%p)", (const void*)E,
+              (const void*)info, (const void*)cent64, (void*)labels, (void*)score);
+  SDK_REQUIRE(((uintptr_t)cent64 & 15) == 0, "sdk_diarize_assign: cent64=%p must be 16-byte aligned", (const void*)cent64);
+  ProfScope ps(ctx, stream, SDK_K_COPY, 6.0 * C * K * d, (double)C * (12.0 * d + 72.0) + 8.0 * K * d);
+  hipLaunchKernelGGL(diarize_assign_kernel, dim3(C), dim3(64), 0, (hipStream_t)stream, E, info, cent64, K, d, constrained, labels, score);
   SDK_LAUNCH_CHECK();
   return 0;
 }

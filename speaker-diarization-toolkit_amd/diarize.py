@@ -15,7 +15,16 @@ tests pin these rules.
   training    rows that are valid and have TRAIN_CLEAN_DEN * clean_frames >= F go to cluster.agglomerative_cluster unchanged
   assignment  centroids = float64 mean of each cluster's training unit rows, re-normalised; every valid row with an active frame takes the
               centroid of largest cosine (ties to the lowest); every other pair gets -1.  No training row: one cluster of all valid active
-              rows (centroid = their mean), or no speaker at all.  Constrained (Hungarian) assignment is not done.
+              rows (centroid = their mean), or no speaker at all.
+  constrained assignment (constrained=True; PyAnnote's constrained_argmax): same centroids, same candidates (the local speakers of a chunk
+              with valid != 0 and active frames > 0, in slot order; every other pair gets -1 and its row is never read).  For a chunk with m
+              candidates and K centroids: among all maps that give n = min(m, K) of the candidates pairwise different clusters and the
+              other m - n candidates -1, the one with the largest total cosine, summed in slot order; ties to the lexicographically smallest
+              label tuple in slot order, -1 ordered after every cluster.  Two local speakers of a chunk - two different people, says the
+              segmentation - never share a cluster.  A candidate left without a cluster (K < m) is DROPPED, as in PyAnnote: when the
+              clustering finds one speaker, overlapped speech of a second one is lost.  With K >= m the optimum uses, for every row, one
+              of that row's m largest cosines (ties to the lower cluster), so at most 27 tuples are compared per chunk and no general
+              Hungarian solver is needed.  Runs on the device (sdk_diarize_centroids, sdk_diarize_assign): the embeddings stay there.
   stitching   on the global frame grid of segmentation.aggregate_counts (frame g, centre 270 g + 495, takes frame g + q_c of chunk c,
               q_c = (135 - start_c) // 270): act[g, k] = chunks in which a local speaker labelled k is active; count[g] = the mean chunk count
               rounded half up, at most 2 and max_speakers; speakers[g] = the count[g] clusters of largest act > 0 (ties to the lower cluster)
@@ -23,8 +32,9 @@ tests pin these rules.
               that never surface keep their relative order behind the others); the stitching is then run with the final numbers
   turns       per speaker, runs of frames with segmentation.frames_to_ranges's boundaries; no gap filling; overlap gives simultaneous turns
 
-Decode, masks and stitching run in libsdk_hip.so (csrc/diarize.hip), the pooling in csrc/resnet.hip; the *_host functions below restate
-them in numpy for hosts that post-process stored class tables.  The host receives info, the unit embeddings, and count / speakers only.
+Decode, masks, the constrained assignment and stitching run in libsdk_hip.so (csrc/diarize.hip), the pooling in csrc/resnet.hip; the *_host
+functions below restate them in numpy for hosts that post-process stored class tables.  The host receives info, the unit embeddings (not
+with constrained=True: then labels, scores and centroids instead), and count / speakers only.
 """
 from __future__ import annotations
 
@@ -45,6 +55,7 @@ TRAIN_CLEAN_DEN = 5              # ours, after PyAnnote's filter: a training row
 MAX_LINKAGE_ROWS = 65536         # Engine.centroid_linkage serves N <= 65 536
 DEFAULT_BATCH = 128              # $SDK_DIARIZE_BATCH: chunks per forward (the ResNet workspace is ~15 MB per chunk at T = 1001)
 N_LOCAL = 3                      # local speakers of the powerset
+MAX_ASSIGN_DIM = 512             # sdk_diarize_centroids / sdk_diarize_assign serve d = 64, 128, .. 512
 
 _MASK = np.array([[k in cls for k in range(N_LOCAL)] for cls in POWERSET], dtype=bool)       # [7, 3]
 _COUNT = _MASK.sum(1).astype(np.int64)
@@ -61,6 +72,7 @@ class DiarizationResult:
     starts: np.ndarray                        # [C] int64 first samples of the chunks
     info: np.ndarray                          # [C, 3, 4] int32 (active frames, clean frames, used_clean, valid)
     cls: object = None                        # [C, F] uint8 class table (device tensor; None for an empty recording)
+    scores: Optional[np.ndarray] = None       # [C, 3] fp32 cosine of every assigned row to its centroid, 0 where the label is -1 (constrained=True only)
 
 
 # ------------------------------------------------------------------------------------------------ host restatements (numpy, vectorised)
@@ -142,6 +154,67 @@ def assign_rows(E: np.ndarray, info: np.ndarray, train: np.ndarray, train_labels
     return labels.reshape(-1, N_LOCAL), cent.astype(np.float32)
 
 
+def _centroids64(E64: np.ndarray, cand: np.ndarray, train: np.ndarray, train_labels: np.ndarray) -> np.ndarray:
+    """The float64 unit centroids of assign_rows ([0, d] when there is neither a training row nor a candidate)."""
+    if len(train):
+        K = int(np.max(train_labels)) + 1
+        cent = np.zeros((K, E64.shape[1]))
+        np.add.at(cent, np.asarray(train_labels, dtype=np.int64), E64[train])
+        cent /= np.bincount(train_labels, minlength=K)[:, None]
+    elif len(cand):
+        cent = np.zeros((1, E64.shape[1]))
+        np.add.at(cent, np.zeros(len(cand), np.int64), E64[cand])         # added in ascending row order, as the training rows are
+        cent /= len(cand)
+    else:
+        return np.zeros((0, E64.shape[1]))
+    return cent / np.maximum(np.linalg.norm(cent, axis=1, keepdims=True), 1e-300)
+
+
+def constrained_chunk(cos: np.ndarray) -> Tuple[int, ...]:
+    """cos [m, K] float64, the cosines of one chunk's m candidates (slot order) -> their m labels under the constrained rule."""
+    import itertools
+    m, K = cos.shape
+    n = min(m, K)
+    top = np.argsort(-cos, axis=1, kind="stable")[:, :min(3, K)]          # stable: ties to the lower cluster
+    opts = [[int(k) for k in top[i] if cos[i, k] == cos[i, k]] + ([-1] if K < m else []) for i in range(m)]
+    best, best_key, best_lab = None, None, (-1,) * m
+    for lab in itertools.product(*opts):
+        used = [k for k in lab if k >= 0]
+        if len(used) != n or len(set(used)) != n:
+            continue
+        tot = 0.0
+        for i, k in enumerate(lab):                                       # summed in slot order
+            if k >= 0:
+                tot = tot + cos[i, k]
+        key = tuple(k if k >= 0 else K for k in lab)                      # -1 after every cluster
+        if best is None or tot > best or (tot == best and key < best_key):
+            best, best_key, best_lab = tot, key, lab
+    return best_lab
+
+
+def assign_constrained_host(E: np.ndarray, info: np.ndarray, train: np.ndarray, train_labels: np.ndarray):
+    """assign_rows with the constrained rule (the module docstring; sdk_diarize_centroids + sdk_diarize_assign with constrained = 1 in numpy)
+    -> (labels [C, 3] int32, centroids [K, d] fp32 unit).  Every cosine is one float64 sum over the columns of its own row, so equal rows
+    have equal cosines."""
+    i = np.asarray(info).reshape(-1, 4)
+    Cn = i.shape[0] // N_LOCAL
+    ok = ((i[:, 3] != 0) & (i[:, 0] > 0)).reshape(Cn, N_LOCAL)
+    cand = np.flatnonzero(ok.reshape(-1))
+    E32 = np.asarray(E)
+    E64 = np.zeros(E32.shape, np.float64)
+    E64[cand] = E32[cand]                                                # rows that are no candidates are never read
+    train = np.asarray(train, dtype=np.int64)
+    E64[train] = E32[train]
+    cent = _centroids64(E64, cand, train, np.asarray(train_labels))
+    labels = np.full((Cn, N_LOCAL), -1, np.int32)
+    if cent.shape[0]:
+        for c in np.flatnonzero(ok.any(1)):
+            slots = np.flatnonzero(ok[c])
+            cos = (E64[c * N_LOCAL + slots][:, None, :] * cent[None, :, :]).sum(-1)
+            labels[c, slots] = constrained_chunk(cos)
+    return labels, cent.astype(np.float32)
+
+
 def appearance_order(speakers: np.ndarray, K: int) -> np.ndarray:
     """new id of every provisional cluster: by first appearance in speakers [G, 2] (frame order, then slot order); clusters that never
     appear follow in their old order."""
@@ -220,6 +293,58 @@ def diarize_reconstruct(eng, cls, starts, labels, K: int, n_samples: int, max_sp
     return count, speakers, act
 
 
+def _check_rows(name: str, E, d_what: str = "E"):
+    import torch
+    if E.dim() != 2 or E.dtype != torch.float32 or not E.is_contiguous() or not E.is_cuda:
+        raise ValueError(f"{name}: {d_what} must be a contiguous fp32 [rows, d] device tensor, got {tuple(E.shape)} {E.dtype}")
+    if E.shape[1] < 64 or E.shape[1] % 64 or E.shape[1] > MAX_ASSIGN_DIM:
+        raise ValueError(f"{name}: d={E.shape[1]} not supported (a multiple of 64, at most {MAX_ASSIGN_DIM})")
+
+
+def diarize_centroids(eng, E, rows, labels, K: int):
+    """E [R, d] fp32 unit rows, rows [n] int32 ascending, labels [n] int32 in [0, K) (all on the device) -> (cent [K, d] fp32 unit,
+    cent64 [K, d] float64) on the device: sdk_diarize_centroids.  A cluster without rows gives a zero row."""
+    import torch
+    from ._lib import check
+    from .ops import _stream
+    _check_rows("diarize_centroids", E)
+    if int(K) < 1:
+        raise ValueError(f"diarize_centroids: K={K} (at least 1)")
+    if rows.dtype != torch.int32 or labels.dtype != torch.int32 or rows.dim() != 1 or rows.shape != labels.shape:
+        raise ValueError(f"diarize_centroids: rows and labels must be int32 [n] tensors of one length, got {tuple(rows.shape)} {rows.dtype}, "
+                         f"{tuple(labels.shape)} {labels.dtype}")
+    rows, labels = rows.contiguous(), labels.contiguous()
+    n, d = int(rows.numel()), int(E.shape[1])
+    if n and not (0 <= int(rows.min()) and int(rows.max()) < E.shape[0]):   # the kernel reads E at these rows
+        raise ValueError(f"diarize_centroids: rows must lie in [0, {E.shape[0]}), got {int(rows.min())} .. {int(rows.max())}")
+    cent = torch.empty((int(K), d), dtype=torch.float32, device=E.device)
+    cent64 = torch.empty((int(K), d), dtype=torch.float64, device=E.device)
+    check(eng.lib.sdk_diarize_centroids(eng.ctx, E.data_ptr(), rows.data_ptr(), labels.data_ptr(), n, int(K), d, cent.data_ptr(), cent64.data_ptr(),
+                                        _stream()), "sdk_diarize_centroids")
+    return cent, cent64
+
+
+def diarize_assign(eng, E, info, cent, constrained: bool = False):
+    """E [3 C, d] fp32 unit rows, info [C, 3, 4] int32, cent [K, d] float64 (diarize_centroids' second result), all on the device ->
+    (labels [C, 3] int32, score [C, 3] fp32) on the device: sdk_diarize_assign."""
+    import torch
+    from ._lib import check
+    from .ops import _stream
+    _check_rows("diarize_assign", E)
+    Cn, d = E.shape[0] // N_LOCAL, int(E.shape[1])
+    if E.shape[0] % N_LOCAL or info.dtype != torch.int32 or tuple(info.shape) != (Cn, N_LOCAL, 4) or not info.is_contiguous():
+        raise ValueError(f"diarize_assign: E [3 C, d] and a contiguous int32 info [C, 3, 4] expected, got {tuple(E.shape)}, {tuple(info.shape)} {info.dtype}")
+    if cent.dim() != 2 or cent.dtype != torch.float64 or cent.shape[1] != d or not cent.is_contiguous():
+        raise ValueError(f"diarize_assign: the centroids must be a contiguous float64 [K, {d}] tensor, got {tuple(cent.shape)} {cent.dtype}")
+    if cent.shape[0] < 1:
+        raise ValueError("diarize_assign: K=0 (at least one centroid)")
+    labels = torch.empty((Cn, N_LOCAL), dtype=torch.int32, device=E.device)
+    score = torch.empty((Cn, N_LOCAL), dtype=torch.float32, device=E.device)
+    check(eng.lib.sdk_diarize_assign(eng.ctx, E.data_ptr(), info.data_ptr(), cent.data_ptr(), Cn, int(cent.shape[0]), d, int(bool(constrained)),
+                                     labels.data_ptr(), score.data_ptr(), _stream()), "sdk_diarize_assign")
+    return labels, score
+
+
 class Diarizer:
     """The pipeline on one ops.Engine: a resident segmentation.Segmentation and a resident resnet.ResNet34."""
 
@@ -239,10 +364,11 @@ class Diarizer:
         return cls, info, self.eng.l2norm(emb)[0]
 
     def run(self, samples, step_s: float = 1.0, threshold: float = PYANNOTE_THRESHOLD, min_cluster_size: int = PYANNOTE_MIN_CLUSTER_SIZE,
-            max_speakers: Optional[int] = None, logp=None) -> DiarizationResult:
+            max_speakers: Optional[int] = None, logp=None, constrained: bool = False) -> DiarizationResult:
         """samples: 16 kHz mono int16 (host) -> DiarizationResult.  logp [C, 589, 7] (fp32, host or device) replaces the segmentation
         model's output (the chunks are chunk_starts(len(samples), step_s)).  The default threshold and size are PyAnnote 3.1's, tuned for
-        ITS trained embedding; with other weights pass a threshold of your own."""
+        ITS trained embedding; with other weights pass a threshold of your own.  constrained=True: the constrained assignment of the
+        module docstring, on the device (the result carries scores); False: every row takes its nearest centroid on its own."""
         import torch
         from .cluster import agglomerative_cluster
         eng = self.eng
@@ -275,15 +401,29 @@ class Diarizer:
             infos.append(i)
             embs.append(e)
         E_dev = torch.cat(embs)
-        info = torch.cat(infos).cpu().numpy()
-        E = E_dev.cpu().numpy()
-        E[info.reshape(-1, 4)[:, 3] == 0] = 0.0                 # rows that are not valid are never read as embeddings
+        info_dev = torch.cat(infos)
+        info = info_dev.cpu().numpy()
         train = training_rows(info, F)
         if len(train) > 1:
             tl = agglomerative_cluster(eng, E_dev.index_select(0, torch.from_numpy(train).to(eng.device)).contiguous(), threshold, min_cluster_size).labels
         else:
             tl = np.zeros(len(train), np.int32)
-        labels, cent = assign_rows(E, info, train, tl)
+        scores = None
+        if constrained:
+            flat = info.reshape(-1, 4)
+            rows, rl = (train, tl) if len(train) else (np.flatnonzero((flat[:, 3] != 0) & (flat[:, 0] > 0)), None)    # no training row: the candidates, one cluster
+            if len(rows):
+                rl = np.zeros(len(rows), np.int32) if rl is None else np.asarray(rl, dtype=np.int32)
+                c32, c64 = diarize_centroids(eng, E_dev, torch.from_numpy(rows.astype(np.int32)).to(eng.device), torch.from_numpy(rl).to(eng.device),
+                                             int(rl.max()) + 1)
+                lab_dev, score_dev = diarize_assign(eng, E_dev, info_dev.contiguous(), c64, True)
+                labels, scores, cent = lab_dev.cpu().numpy(), score_dev.cpu().numpy(), c32.cpu().numpy()
+            else:
+                labels, scores, cent = np.full((Cn, N_LOCAL), -1, np.int32), np.zeros((Cn, N_LOCAL), np.float32), np.zeros((0, d), np.float32)
+        else:
+            E = E_dev.cpu().numpy()
+            E[info.reshape(-1, 4)[:, 3] == 0] = 0.0             # rows that are not valid are never read as embeddings
+            labels, cent = assign_rows(E, info, train, tl)
         K = cent.shape[0]
 
         def stitch(lab):
@@ -297,4 +437,4 @@ class Diarizer:
                 labels = np.where(labels >= 0, new[np.maximum(labels, 0)], -1).astype(np.int32)
                 cent = cent[np.argsort(new)]
                 count, speakers = stitch(labels)
-        return DiarizationResult(turns_from_frames(speakers, K), K, cent, labels, count, speakers, st, info, cls)
+        return DiarizationResult(turns_from_frames(speakers, K), K, cent, labels, count, speakers, st, info, cls, scores)

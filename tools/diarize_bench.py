@@ -5,7 +5,10 @@ process on the same inputs:
   trunk sharing   three ResNet34.forward calls per chunk at T = 1001 (what embedding each (chunk, speaker) pair separately costs) against
                   the one masked forward; the ratio is reported, not gated
   reconstruction  the numpy statement of the stitching rule (diarize.reconstruct_host) on the same class table
-Record the line in profiles/r10_diarize_bench.json.  Synthetic weights: the class table is the model's own (noise-like) output, which
+  assignment      the constrained stage on the device (training rows and labels up, sdk_diarize_centroids + sdk_diarize_assign, labels, scores
+                  and centroids down; wall clock, best of three after a warm-up) beside the host stage it stands in for (the download of
+                  the embeddings + diarize.assign_rows) on the same embeddings, and how many chunks the constraint changed
+Record the line in profiles/r11_diarize_assign_bench.json (r10_diarize_bench.json: the line before the constrained stage).  Synthetic weights: the class table is the model's own (noise-like) output, which
 exercises every stage at full size."""
 from __future__ import annotations
 
@@ -113,6 +116,29 @@ def main() -> None:
     t0 = time.perf_counter()
     labels, cent = dz.assign_rows(E, info, train, tl)
     t_assign = time.perf_counter() - t0
+    constrained = None
+    if len(train):
+        def device_stage():
+            c32, c64 = dz.diarize_centroids(eng, E_d, torch.from_numpy(train.astype(np.int32)).cuda(), torch.from_numpy(np.asarray(tl, dtype=np.int32)).cuda(),
+                                            int(np.max(tl)) + 1)
+            lab, sc = dz.diarize_assign(eng, E_d, info_d.contiguous(), c64, True)
+            return lab.cpu().numpy(), sc.cpu().numpy(), c32.cpu().numpy()
+        device_stage()
+        t_dev = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            lab_c, _, cent_c = device_stage()
+            t_dev.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        E_again = E_d.cpu().numpy()
+        t_down = time.perf_counter() - t0
+        del E_again
+        constrained = {"device_stage_ms": round(min(t_dev) * 1e3, 3), "host_assign_rows_ms": round(t_assign * 1e3, 3),
+                       "host_embedding_download_ms": round(t_down * 1e3, 3),
+                       "chunks_changed_by_the_constraint": int((lab_c != labels).any(1).sum()),
+                       "candidates_dropped": int(((lab_c < 0) & (labels >= 0)).sum()),
+                       "centroids_max_abs_diff": float(np.abs(cent_c - cent).max())}
     K = max(cent.shape[0], 1)
     lab_d = torch.from_numpy(labels).cuda()
     dz.diarize_reconstruct(eng, cls, sd, lab_d, K, n)
@@ -131,6 +157,8 @@ def main() -> None:
            "masked_pool_seg1_share_of_forward": round(tail / total, 4) if total else None,
            "total_s": round(total_s, 4), "chunks_per_s": round(Cn / total_s, 1), "real_time_factor": round(total_s / a.seconds, 7),
            "training_rows": int(len(train)), "clusters": int(cent.shape[0]), "turns": len(turns)}
+    if constrained is not None:
+        out["constrained_assignment"] = constrained
     if not a.no_yardstick:
         t_three = 0.0
         for b0 in range(0, Cn, a.batch):
