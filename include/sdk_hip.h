@@ -37,6 +37,7 @@
  *     sdk_powerset_decode  sdk_diarize_masks  sdk_resnet_last_map_frames  sdk_resnet_masked_workspace_bytes
  *     sdk_resnet_forward_masked  sdk_diarize_frames  sdk_diarize_reconstruct  sdk_diarize_centroids  sdk_diarize_assign
  *                                                                                                       speaker diarization (diarize.py)
+ *     sdk_plda_transform  sdk_vbx_workspace_bytes  sdk_vbx  sdk_vbx_centroids                           VBx clustering (plda.py, cluster.vbx_cluster)
  * BUILDING BLOCKS AND KNOBS - exported for the parity tests and the A/B tools, free to change between rounds, not for binding:
  *     sdk_conv_gemm*  sdk_colstats_finish  sdk_res2net_chain*  sdk_se_*  sdk_asp_*  sdk_rows_fc  (pieces of sdk_ecapa_forward)
  *     sdk_resnet_conv2d  (piece of sdk_resnet_forward)  sdk_resnet_masked_pool  (piece of sdk_resnet_forward_masked)
@@ -516,6 +517,38 @@ int sdk_diarize_centroids(sdk_ctx* ctx, const float* E, const int32_t* rows, con
                           double* cent64, void* stream);
 int sdk_diarize_assign(sdk_ctx* ctx, const float* E, const int32_t* info, const double* cent64, int C, int K, int d, int constrained,
                        int32_t* labels, float* score, void* stream);
+
+/* ---- VBx clustering of the diarization (cluster.vbx_cluster, plda.py; csrc/vbx.hip): float64 arithmetic, every sum over rows over fixed 64-row
+ *      blocks whose partials are combined in block order, no floating-point atomics, one owner per output element: bit-identical run to
+ *      run.  n <= 65 536 rows, D = 64 or 128, any S >= 1.
+ *   sdk_plda_transform : E [R][d_in] fp32 unit rows (d_in a multiple of 64, at most 512), rows [n] int32 (rows of E; must lie inside E: the
+ *        library does not read them back to check), the prepared model as float64 device arrays - mean1 [d_in], lda [d_in][D0] (D0 <= 512),
+ *        mean2 [D0], mu [D0], Tt [D0][D] (the first D rows of the PLDA basis T, transposed) -> X [n][D] float64:
+ *        x1 = sqrt(d_in) unit(e - mean1), x2 = sqrt(D0) unit(lda^T x1 - mean2), x = (x2 - mu) Tt; unit divides by max(norm, 1e-300).
+ *   sdk_vbx : X [n][D], Phi [D], the initial labels [n] int32 in [0, S) -> gamma [n][S], pi [S], elbo [max_iters] (entries from n_iter on
+ *        are 0), n_iter and status (one int32 each), all on the device.  gamma0 = softmax_s(init_smoothing [label == s]), pi = 1 / S, then
+ *        per iteration ii (rho = x sqrt(Phi), G_t = -(|x_t|^2 + D ln 2 pi) / 2):
+ *          N_s = sum_t gamma[t][s]; invL[s][d] = 1 / (1 + (Fa / Fb) N_s Phi_d); alpha[s][d] = (Fa / Fb) invL[s][d] sum_t gamma[t][s] rho[t][d];
+ *          z[t][s] = Fa (rho_t . alpha_s - sum_d (invL[s][d] + alpha[s][d]^2) Phi_d / 2 + G_t) + ln pi_s   (pi_s == 0: -inf, gamma exactly 0);
+ *          lse_t = logsumexp_s z[t][s] (maximum subtracted); gamma = exp(z - lse);
+ *          elbo[ii] = sum_t lse_t + (Fb / 2) sum_{s,d} (ln invL - invL - alpha^2 + 1); pi = sum_t gamma / sum_{t,s} gamma;
+ *          stop after this iteration when ii > 0 and elbo[ii] - elbo[ii - 1] < epsilon (epsilon may be infinite, not NaN).
+ *        Every iteration is enqueued; the stop test runs on the device and the launches after the stop leave every output untouched.
+ *        status: 0, or bits 1 (a non-finite x or Phi: nothing ran, n_iter = 0), 2 (a label outside [0, S): the same), 4 (a non-finite elbo:
+ *        stopped there).  The host reads n_iter and status once, after the call.  workspace: sdk_vbx_workspace_bytes (0 for arguments
+ *        sdk_vbx would refuse), 256-byte aligned.
+ *   sdk_vbx_centroids : gamma, pi, E, rows as above (d = E's width) -> K (one int32), keep [S] int32 (the speakers with pi > 1e-7 in
+ *        their order, then -1), labels [n] int32 (or NULL: the arg-max of gamma over the kept speakers, ties to the lower), cent [S][d]
+ *        fp32 and cent64 [S][d] float64 of which the first K rows are written: sum_t gamma[t][keep k] e_t in ascending row order, divided by
+ *        sum_t gamma[t][keep k], divided by its norm (clamped at 1e-300) - the layout sdk_diarize_assign takes. */
+int sdk_plda_transform(sdk_ctx* ctx, const float* E, int d_in, const int32_t* rows, int n, const double* mean1, const double* lda,
+                       const double* mean2, const double* mu, const double* Tt, int D0, int D, double* X, void* stream);
+size_t sdk_vbx_workspace_bytes(int n, int D, int S);
+int sdk_vbx(sdk_ctx* ctx, const double* X, const double* Phi, const int32_t* labels, int n, int D, int S, double Fa, double Fb, int max_iters,
+            double epsilon, double init_smoothing, double* gamma, double* pi, double* elbo, int32_t* n_iter, int32_t* status, void* ws,
+            size_t ws_bytes, void* stream);
+int sdk_vbx_centroids(sdk_ctx* ctx, const double* gamma, const double* pi, const float* E, const int32_t* rows, int n, int S, int d, int32_t* K,
+                      int32_t* keep, int32_t* labels, float* cent, double* cent64, void* stream);
 
 /* ---- audio conversion to the AudioProfile: replaces the ffmpeg subprocess the reference's backends
  *      run before upload (audio_profiles.py:70-100 `format_ffmpeg_args`; speechmatics_backend.py:231-281).

@@ -80,7 +80,7 @@ GEMM_A_KBLOCKED = 4      # A read / C written as [cols / 64][M][64] (include/sdk
 GEMM_C_KBLOCKED = 8
 GEMM_F16 = 16             # fp16 operands and outputs (single-plane fp16 contract)
 
-_vp, _i, _i64, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
+_vp, _i, _i64, _sz, _f64 = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_double
 
 # name -> (restype, argtypes); every symbol include/sdk_hip.h declares must be listed here
 SIGNATURES = {
@@ -151,6 +151,10 @@ SIGNATURES = {
     "sdk_diarize_reconstruct": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i, _vp, _vp, _vp, _vp]),
     "sdk_diarize_centroids": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "sdk_diarize_assign": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "sdk_plda_transform": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "sdk_vbx_workspace_bytes": (_sz, [_i, _i, _i]),
+    "sdk_vbx": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f64, _f64, _i, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sdk_vbx_centroids": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sdk_segmentation_frames": (_i, [_i]),
     "sdk_segmentation_workspace_bytes": (_sz, [_vp, _i, _i]),
     "sdk_segmentation_forward": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),

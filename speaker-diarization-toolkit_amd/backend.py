@@ -404,7 +404,9 @@ class Backend(EmbeddingBackend):
 
     def diarizer(self):
         """The resident diarization pipeline (diarize.py): Backend.segmentation() and the ResNet34 built from $SDK_RESNET_WEIGHTS (.npz in the
-        public naming, else seeded synthetic) whatever SDK_MODEL is; precision from SDK_PRECISION (0 or 2)."""
+        public naming, else seeded synthetic) whatever SDK_MODEL is; precision from SDK_PRECISION (0 or 2).  The PLDA model of
+        clustering="vbx" comes from $SDK_PLDA_TRANSFORM (xvec_transform.npz: mean1, mean2, lda) and $SDK_PLDA (plda.npz: mu, tr, psi), both or
+        neither, with $SDK_PLDA_DIM (64 or 128, default 128) dimensions kept; else a seeded synthetic model, made on first use."""
         if self.lite:
             raise ValueError("diarize needs the torch engine: not available with SDK_NO_TORCH=1")
         if getattr(self, "_diarizer", None) is None:
@@ -422,17 +424,30 @@ class Backend(EmbeddingBackend):
                 else:
                     w = resnet.synthetic_weights(0)
                 net = resnet.ResNet34(self.engine(), w, precision=prec)
-            self._diarizer = Diarizer(self.engine(), model, net)
+            tpath, ppath = os.environ.get("SDK_PLDA_TRANSFORM"), os.environ.get("SDK_PLDA")
+            if bool(tpath) != bool(ppath):
+                raise ValueError("SDK_PLDA_TRANSFORM and SDK_PLDA name the two files of one PLDA model: set both or neither")
+            model_plda = None
+            if tpath:
+                from .plda import load_plda
+                dim = os.environ.get("SDK_PLDA_DIM", "128")
+                if dim not in ("64", "128"):
+                    raise ValueError(f"SDK_PLDA_DIM={dim!r}: the PLDA dimensions kept, 64 or 128")
+                model_plda = load_plda(tpath, ppath, int(dim))
+            self._diarizer = Diarizer(self.engine(), model, net, model_plda)
         return self._diarizer
 
     def diarize(self, samples_or_path, **kw):
         """Who spoke when, with no transcript and no enrolled profiles: a recording (16 kHz mono int16 samples, or the path of an audio file,
         decoded to the audio profile) -> diarize.DiarizationResult (turns [(start_s, end_s, speaker)], n_speakers, unit centroids in the
         embedding space of score_windows, labels, count, speakers); diarize.to_rttm(result.turns, uri) writes RTTM.  Keywords: step_s,
-        threshold, min_cluster_size, max_speakers, logp, constrained (diarize.Diarizer.run).  The default threshold is PyAnnote 3.1's, tuned
+        threshold, min_cluster_size, max_speakers, logp, constrained, clustering, vbx (diarize.Diarizer.run).  The default threshold is PyAnnote 3.1's, tuned
         for its trained ResNet34 ($SDK_RESNET_WEIGHTS); with the synthetic weights pass a threshold of your own.  constrained=True
         (PyAnnote's constrained_argmax; default False): the local speakers of a chunk get pairwise different clusters, the one-to-one
-        matching of largest total cosine, computed on the device; the result then carries scores [C, 3]."""
+        matching of largest total cosine, computed on the device; the result then carries scores [C, 3].  clustering="vbx" (default "ahc"):
+        the cut of the linkage at `threshold` (pass cluster.VBX_AHC_THRESHOLD, 0.6) only initialises a VBx clustering in PLDA space
+        (cluster.vbx_cluster; the model of Backend.diarizer), whose speakers' centroids the assignment then reads; vbx: a dict of Fa, Fb,
+        max_iters, epsilon, init_smoothing.  The result then carries scores, pi and elbo.  Parity with PyAnnote is unpinned."""
         dz = self.diarizer()
         if isinstance(samples_or_path, (str, Path)):
             samples_or_path = decode_to_profile(Path(samples_or_path), self.engine(), self.get_audio_profile())

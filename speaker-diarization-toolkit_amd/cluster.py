@@ -323,3 +323,71 @@ def fold_small_clusters(E: np.ndarray, labels: np.ndarray, min_cluster_size: int
     remap = np.arange(K)
     remap[small] = to
     return canonical_labels(remap[labels]).astype(np.int32), int(large.size)
+
+
+# ------------------------------------------------------------------ VBx: the linkage only initialises a variational-Bayes mixture in PLDA space
+VBX_AHC_THRESHOLD = 0.6          # the initial cut of the linkage (an over-split is what the mixture repairs)
+VBX_FA, VBX_FB, VBX_MAX_ITERS, VBX_EPSILON, VBX_INIT_SMOOTHING = 0.07, 0.8, 20, 1e-4, 7.0
+VBX_MIN_PI = 1e-7                # speakers whose weight falls to this or below have died out (the kernel's constant)
+
+
+@dataclass
+class VbxResult:
+    labels: np.ndarray            # [N] int32: the arg-max of gamma over the kept speakers (ties to the lower); reported, not used for assignment
+    n_speakers: int               # K, the speakers with pi > 1e-7
+    pi: np.ndarray                # [S] float64 speaker weights after the last iteration
+    elbo: np.ndarray              # [n_iter] float64
+    n_iter: int
+    keep: np.ndarray              # [K] int32: the kept speakers among the S initial clusters, ascending
+    init_labels: np.ndarray       # [N] int32 canonical labels of the initial cut (S = max + 1 clusters)
+    cent: object                  # [K, d] fp32 unit centroids (device tensor)
+    cent64: object                # [K, d] float64, the same before the final rounding (device tensor; what sdk_diarize_assign reads)
+    gamma: object                 # [N, S] float64 responsibilities (device tensor)
+
+
+def vbx_cluster(provider, E, plda, threshold: float = VBX_AHC_THRESHOLD, Fa: float = VBX_FA, Fb: float = VBX_FB, max_iters: int = VBX_MAX_ITERS,
+                epsilon: float = VBX_EPSILON, init_smoothing: float = VBX_INIT_SMOOTHING, rows=None) -> VbxResult:
+    """VBx clustering (Landini et al., BUT) of the unit rows E ([R, d] fp32 on the provider's device; rows: the ascending row numbers that
+    take part, host integers, None = all), as the clustering half of PyAnnote's speaker-diarization-community-1 pipeline is stated HERE
+    (written from the published description; no trained PLDA and no pyannote code is on hand: PARITY IS UNPINNED, the tests pin this rule):
+
+      transform       x = the PLDA transform of every row (plda.py), float64, on the device (sdk_plda_transform)
+      initialisation  Engine.centroid_linkage on the rows, cut with fcluster_distance(Z, threshold), no small-cluster fold: S canonical
+                      clusters; gamma0[t, s] = softmax_s(init_smoothing [label_t == s]); pi = 1 / S
+      iteration       float64, no HMM (the loop probability is 0: the embeddings of overlapping chunks are not a chain).  With
+                      rho = x sqrt(Phi), G_t = -(|x_t|^2 + D ln 2 pi) / 2, for ii = 0 .. max_iters - 1:
+                        N_s = sum_t gamma[t, s];  invL[s, :] = 1 / (1 + (Fa / Fb) N_s Phi);  alpha[s, :] = (Fa / Fb) invL[s, :] sum_t gamma[t, s] rho[t, :]
+                        logp[t, s] = Fa (rho_t . alpha_s - sum_d (invL[s, d] + alpha[s, d]^2) Phi_d / 2 + G_t)
+                        z = logp + ln pi (pi_s == 0: -inf, and gamma[:, s] is exactly 0 from then on);  lse_t = logsumexp_s z[t, :] with the
+                        maximum subtracted;  gamma = exp(z - lse)
+                        ELBO = sum_t lse_t + (Fb / 2) sum_{s, d} (ln invL - invL - alpha^2 + 1);  pi = sum_t gamma / sum_{t, s} gamma
+                        stop after this iteration when ii > 0 and ELBO - ELBO_prev < epsilon
+                      All iterations are enqueued at once (sdk_vbx); the stop test runs on the device.
+      result          speakers with pi > 1e-7 are kept, in their order; a kept speaker's centroid is sum_t gamma[t, k] e_t / sum_t gamma[t, k]
+                      over the ORIGINAL unit rows, summed in float64 in ascending row order, re-normalised (sdk_vbx_centroids); a row's hard
+                      label is the arg-max of gamma over the kept speakers, ties to the lower.
+
+    Needs at least two rows.  The linkage Z is downloaded for the cut; after that one host read decides (n_iter, status, K, at the end; a
+    non-finite row raises ValueError there), and the results (labels, pi, elbo, keep) are downloaded after it."""
+    R = int(E.shape[0])
+    rows_h = np.arange(R, dtype=np.int64) if rows is None else np.asarray(rows, dtype=np.int64).reshape(-1)
+    N = int(rows_h.size)
+    if N < 2:
+        raise ValueError(f"vbx_cluster: {N} rows (VBx needs at least 2)")
+    if rows_h.min() < 0 or rows_h.max() >= R or (np.diff(rows_h) <= 0).any():
+        raise ValueError(f"vbx_cluster: rows must ascend strictly inside [0, {R}), got {int(rows_h.min())} .. {int(rows_h.max())}")
+    rows_d = torch.from_numpy(rows_h.astype(np.int32)).to(E.device)
+    Et = E if rows is None else E.index_select(0, rows_d.long()).contiguous()
+    Z = provider.centroid_linkage(Et).cpu().numpy()
+    init = fcluster_distance(Z, threshold).astype(np.int32)
+    S = int(init.max()) + 1
+    X = provider.plda_transform(E, rows_d, plda, check_rows=False)
+    gamma, pi, elbo, n_iter, status = provider.vbx(X, plda.device_arrays(E.device)["Phi"], torch.from_numpy(init).to(E.device), S, Fa, Fb, max_iters,
+                                                   epsilon, init_smoothing)
+    K, keep, labels, cent, cent64 = provider.vbx_centroids(gamma, pi, E, rows_d, check_rows=False)
+    n_it, st, Kn = (int(v) for v in torch.cat([n_iter, status, K]).cpu().numpy())       # the one read
+    if st:
+        raise ValueError(f"vbx_cluster: non-finite input (status {st}: 1 = a non-finite embedding or PLDA value, 4 = a non-finite ELBO after "
+                         f"{n_it} iterations)")
+    return VbxResult(labels.cpu().numpy(), Kn, pi.cpu().numpy(), elbo[:n_it].cpu().numpy(), n_it, keep[:Kn].cpu().numpy(), init, cent[:Kn], cent64[:Kn],
+                     gamma)

@@ -25,6 +25,12 @@ tests pin these rules.
               clustering finds one speaker, overlapped speech of a second one is lost.  With K >= m the optimum uses, for every row, one
               of that row's m largest cosines (ties to the lower cluster), so at most 27 tuples are compared per chunk and no general
               Hungarian solver is needed.  Runs on the device (sdk_diarize_centroids, sdk_diarize_assign): the embeddings stay there.
+  VBx         (clustering="vbx"; the clustering half of PyAnnote's speaker-diarization-community-1 pipeline, stated in cluster.vbx_cluster):
+              the centroid linkage of the training rows, cut at `threshold` with no small-cluster fold, only INITIALISES a variational-Bayes
+              mixture on the PLDA transform of those rows (plda.py); speakers that the cut over-split lose their weight and die out.  The
+              kept speakers' centroids are the responsibility-weighted means of the original unit rows; every candidate row is then assigned
+              by sdk_diarize_assign with the caller's `constrained` flag, so the stretch from embeddings to labels stays on the device and the
+              result carries scores either way.  With fewer than two training rows: as "ahc" (one cluster or none).
   stitching   on the global frame grid of segmentation.aggregate_counts (frame g, centre 270 g + 495, takes frame g + q_c of chunk c,
               q_c = (135 - start_c) // 270): act[g, k] = chunks in which a local speaker labelled k is active; count[g] = the mean chunk count
               rounded half up, at most 2 and max_speakers; speakers[g] = the count[g] clusters of largest act > 0 (ties to the lower cluster)
@@ -72,7 +78,11 @@ class DiarizationResult:
     starts: np.ndarray                        # [C] int64 first samples of the chunks
     info: np.ndarray                          # [C, 3, 4] int32 (active frames, clean frames, used_clean, valid)
     cls: object = None                        # [C, F] uint8 class table (device tensor; None for an empty recording)
-    scores: Optional[np.ndarray] = None       # [C, 3] fp32 cosine of every assigned row to its centroid, 0 where the label is -1 (constrained=True only)
+    scores: Optional[np.ndarray] = None       # [C, 3] fp32 cosine of every assigned row to its centroid, 0 where the label is -1 (constrained=True, or clustering="vbx")
+    # clustering="vbx" sets these two on the result (None otherwise).  Plain attributes with a class default, not dataclass fields: the
+    # field list, and with it the positional constructor, ends with scores as before.
+    pi = None                                 # [S] float64 weights of the S initial speakers after the last iteration
+    elbo = None                               # [n_iter] float64
 
 
 # ------------------------------------------------------------------------------------------------ host restatements (numpy, vectorised)
@@ -348,8 +358,15 @@ def diarize_assign(eng, E, info, cent, constrained: bool = False):
 class Diarizer:
     """The pipeline on one ops.Engine: a resident segmentation.Segmentation and a resident resnet.ResNet34."""
 
-    def __init__(self, engine, segmentation, resnet):
-        self.eng, self.seg, self.resnet = engine, segmentation, resnet
+    def __init__(self, engine, segmentation, resnet, plda=None):
+        self.eng, self.seg, self.resnet, self.plda = engine, segmentation, resnet, plda
+
+    def plda_model(self):
+        """The plda.Plda of clustering="vbx": the one given, else a seeded synthetic model for the embedding width."""
+        if self.plda is None:
+            from .plda import synthetic_plda
+            self.plda = synthetic_plda(self.resnet.cfg.embed_dim, 128, 0)
+        return self.plda
 
     def embed_chunks(self, rec, n_samples: int, starts_dev, logp=None):
         """One batch of chunks: (cls [B, F] uint8, info [B, 3, 4] int32, unit embeddings [B * 3, d] fp32), all on the device."""
@@ -364,14 +381,25 @@ class Diarizer:
         return cls, info, self.eng.l2norm(emb)[0]
 
     def run(self, samples, step_s: float = 1.0, threshold: float = PYANNOTE_THRESHOLD, min_cluster_size: int = PYANNOTE_MIN_CLUSTER_SIZE,
-            max_speakers: Optional[int] = None, logp=None, constrained: bool = False) -> DiarizationResult:
+            max_speakers: Optional[int] = None, logp=None, constrained: bool = False, clustering: str = "ahc",
+            vbx: Optional[dict] = None) -> DiarizationResult:
         """samples: 16 kHz mono int16 (host) -> DiarizationResult.  logp [C, 589, 7] (fp32, host or device) replaces the segmentation
         model's output (the chunks are chunk_starts(len(samples), step_s)).  The default threshold and size are PyAnnote 3.1's, tuned for
         ITS trained embedding; with other weights pass a threshold of your own.  constrained=True: the constrained assignment of the
-        module docstring, on the device (the result carries scores); False: every row takes its nearest centroid on its own."""
+        module docstring, on the device (the result carries scores); False: every row takes its nearest centroid on its own.
+        clustering="vbx": the VBx clustering of the module docstring instead of the cut-and-fold ("ahc", the default); `threshold` keeps its
+        meaning, the cut of the linkage, which now only initialises: pass cluster.VBX_AHC_THRESHOLD (0.6) with it; min_cluster_size is not
+        used.  vbx: a dict of Fa, Fb, max_iters, epsilon, init_smoothing (cluster.vbx_cluster's defaults otherwise).  The result carries
+        scores, pi and elbo."""
         import torch
-        from .cluster import agglomerative_cluster
+        from .cluster import agglomerative_cluster, vbx_cluster
         eng = self.eng
+        if clustering not in ("ahc", "vbx"):
+            raise ValueError(f"diarize: clustering={clustering!r} (\"ahc\" or \"vbx\")")
+        vbx = dict(vbx or {})
+        unknown = sorted(set(vbx) - {"Fa", "Fb", "max_iters", "epsilon", "init_smoothing"})
+        if unknown or (vbx and clustering != "vbx"):
+            raise ValueError(f"diarize: vbx={vbx} (keys Fa, Fb, max_iters, epsilon, init_smoothing; only with clustering=\"vbx\")")
         x = np.ascontiguousarray(samples, dtype=np.int16).reshape(-1)
         d = self.resnet.cfg.embed_dim
         if x.size == 0:
@@ -404,19 +432,26 @@ class Diarizer:
         info_dev = torch.cat(infos)
         info = info_dev.cpu().numpy()
         train = training_rows(info, F)
-        if len(train) > 1:
+        vres = None
+        if clustering == "vbx" and len(train) > 1:
+            vres = vbx_cluster(eng, E_dev, self.plda_model(), threshold, rows=train, **vbx)
+            tl = None
+        elif len(train) > 1:
             tl = agglomerative_cluster(eng, E_dev.index_select(0, torch.from_numpy(train).to(eng.device)).contiguous(), threshold, min_cluster_size).labels
         else:
             tl = np.zeros(len(train), np.int32)
         scores = None
-        if constrained:
+        if vres is not None:
+            lab_dev, score_dev = diarize_assign(eng, E_dev, info_dev.contiguous(), vres.cent64.contiguous(), bool(constrained))
+            labels, scores, cent = lab_dev.cpu().numpy(), score_dev.cpu().numpy(), vres.cent.cpu().numpy()
+        elif constrained or clustering == "vbx":
             flat = info.reshape(-1, 4)
             rows, rl = (train, tl) if len(train) else (np.flatnonzero((flat[:, 3] != 0) & (flat[:, 0] > 0)), None)    # no training row: the candidates, one cluster
             if len(rows):
                 rl = np.zeros(len(rows), np.int32) if rl is None else np.asarray(rl, dtype=np.int32)
                 c32, c64 = diarize_centroids(eng, E_dev, torch.from_numpy(rows.astype(np.int32)).to(eng.device), torch.from_numpy(rl).to(eng.device),
                                              int(rl.max()) + 1)
-                lab_dev, score_dev = diarize_assign(eng, E_dev, info_dev.contiguous(), c64, True)
+                lab_dev, score_dev = diarize_assign(eng, E_dev, info_dev.contiguous(), c64, bool(constrained))
                 labels, scores, cent = lab_dev.cpu().numpy(), score_dev.cpu().numpy(), c32.cpu().numpy()
             else:
                 labels, scores, cent = np.full((Cn, N_LOCAL), -1, np.int32), np.zeros((Cn, N_LOCAL), np.float32), np.zeros((0, d), np.float32)
@@ -437,4 +472,7 @@ class Diarizer:
                 labels = np.where(labels >= 0, new[np.maximum(labels, 0)], -1).astype(np.int32)
                 cent = cent[np.argsort(new)]
                 count, speakers = stitch(labels)
-        return DiarizationResult(turns_from_frames(speakers, K), K, cent, labels, count, speakers, st, info, cls, scores)
+        res = DiarizationResult(turns_from_frames(speakers, K), K, cent, labels, count, speakers, st, info, cls, scores)
+        if vres is not None:
+            res.pi, res.elbo = vres.pi, vres.elbo
+        return res

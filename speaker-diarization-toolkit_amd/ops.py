@@ -680,6 +680,95 @@ class Engine:
             raise err
         return Z
 
+    # ---- VBx clustering (cluster.vbx_cluster, plda.py; csrc/vbx.hip): nothing here synchronises with the host except the range check of rows
+    @staticmethod
+    def _vbx_rows(name: str, E: torch.Tensor, rows: torch.Tensor, check_rows: bool) -> int:
+        if E.dim() != 2 or E.dtype != torch.float32 or not E.is_contiguous() or not E.is_cuda:
+            raise ValueError(f"{name}: E must be a contiguous fp32 [rows, d] device tensor, got {tuple(E.shape)} {E.dtype}")
+        if E.shape[1] < 64 or E.shape[1] % 64 or E.shape[1] > 512:
+            raise ValueError(f"{name}: d={E.shape[1]} not supported (a multiple of 64, at most 512)")
+        if rows.dim() != 1 or rows.dtype != torch.int32 or not rows.is_contiguous() or not rows.is_cuda:
+            raise ValueError(f"{name}: rows must be a contiguous int32 [n] device tensor, got {tuple(rows.shape)} {rows.dtype}")
+        n = int(rows.numel())
+        if n < 1 or n > 65536:
+            raise ValueError(f"{name}: n={n} rows (1 .. 65536)")
+        if check_rows and not (0 <= int(rows.min()) and int(rows.max()) < E.shape[0]):      # the kernels read E at these rows
+            raise ValueError(f"{name}: rows must lie in [0, {E.shape[0]}), got {int(rows.min())} .. {int(rows.max())}")
+        return n
+
+    def plda_transform(self, E: torch.Tensor, rows: torch.Tensor, plda, check_rows: bool = True) -> torch.Tensor:
+        """E [R, d_in] fp32 unit rows, rows [n] int32 (device), plda a plda.Plda -> X [n, D] float64 (device): sdk_plda_transform.
+        check_rows=False: the caller has checked that rows lie in [0, R) (the check reads them back)."""
+        n = self._vbx_rows("plda_transform", E, rows, check_rows)
+        if int(E.shape[1]) != plda.d_in:
+            raise ValueError(f"plda_transform: E has d={E.shape[1]}, the PLDA model takes d_in={plda.d_in}")
+        D = int(plda.lda_dim)
+        if D not in (64, 128) or D > plda.D0:
+            raise ValueError(f"plda_transform: D={D} not supported (64 or 128, at most D0={plda.D0})")
+        m = plda.device_arrays(E.device)
+        X = torch.empty((n, D), dtype=torch.float64, device=E.device)
+        check(self.lib.sdk_plda_transform(self.ctx, E.data_ptr(), plda.d_in, rows.data_ptr(), n, m["mean1"].data_ptr(), m["lda"].data_ptr(),
+                                          m["mean2"].data_ptr(), m["mu"].data_ptr(), m["Tt"].data_ptr(), plda.D0, D, X.data_ptr(), _stream()),
+              "sdk_plda_transform")
+        return X
+
+    def vbx(self, X: torch.Tensor, Phi: torch.Tensor, labels: torch.Tensor, S: int, Fa: float = 0.07, Fb: float = 0.8, max_iters: int = 20,
+            epsilon: float = 1e-4, init_smoothing: float = 7.0):
+        """X [n, D] float64, Phi [D] float64, labels [n] int32 in [0, S) (all on the device) -> (gamma [n, S], pi [S], elbo [max_iters],
+        n_iter [1] int32, status [1] int32), all on the device and not read back: sdk_vbx.  The caller reads n_iter and status once."""
+        if X.dim() != 2 or X.dtype != torch.float64 or not X.is_contiguous() or not X.is_cuda:
+            raise ValueError(f"vbx: X must be a contiguous float64 [n, D] device tensor, got {tuple(X.shape)} {X.dtype}")
+        n, D = int(X.shape[0]), int(X.shape[1])
+        if D not in (64, 128):
+            raise ValueError(f"vbx: D={D} not supported (64 or 128)")
+        if n < 1 or n > 65536:
+            raise ValueError(f"vbx: n={n} rows (1 .. 65536)")
+        if Phi.dtype != torch.float64 or tuple(Phi.shape) != (D,) or not Phi.is_contiguous() or not Phi.is_cuda:
+            raise ValueError(f"vbx: Phi must be a contiguous float64 [{D}] device tensor, got {tuple(Phi.shape)} {Phi.dtype}")
+        if labels.dtype != torch.int32 or tuple(labels.shape) != (n,) or not labels.is_contiguous() or not labels.is_cuda:
+            raise ValueError(f"vbx: labels must be a contiguous int32 [{n}] device tensor, got {tuple(labels.shape)} {labels.dtype}")
+        S, max_iters = int(S), int(max_iters)
+        if S < 1 or S > 65536:
+            raise ValueError(f"vbx: S={S} (1 .. 65536)")
+        if max_iters < 1 or max_iters > 1000:
+            raise ValueError(f"vbx: max_iters={max_iters} (1 .. 1000)")
+        Fa, Fb, epsilon, init_smoothing = float(Fa), float(Fb), float(epsilon), float(init_smoothing)
+        if not (0 < Fa < np.inf and 0 < Fb < np.inf) or epsilon != epsilon or not (0 <= init_smoothing < np.inf):
+            raise ValueError(f"vbx: Fa={Fa} Fb={Fb} (positive, finite), epsilon={epsilon} (not NaN), init_smoothing={init_smoothing} (finite, >= 0)")
+        nbytes = self.lib.sdk_vbx_workspace_bytes(n, D, S)
+        if nbytes == 0:
+            raise SdkError(f"sdk_vbx_workspace_bytes: {self.lib.sdk_last_error().decode()}")
+        dev = X.device
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        gamma = torch.empty((n, S), dtype=torch.float64, device=dev)
+        pi = torch.empty((S,), dtype=torch.float64, device=dev)
+        elbo = torch.empty((max_iters,), dtype=torch.float64, device=dev)
+        n_iter = torch.empty((1,), dtype=torch.int32, device=dev)
+        status = torch.empty((1,), dtype=torch.int32, device=dev)
+        check(self.lib.sdk_vbx(self.ctx, X.data_ptr(), Phi.data_ptr(), labels.data_ptr(), n, D, S, Fa, Fb, max_iters, epsilon, init_smoothing,
+                               gamma.data_ptr(), pi.data_ptr(), elbo.data_ptr(), n_iter.data_ptr(), status.data_ptr(), ws.data_ptr(), nbytes,
+                               _stream()), "sdk_vbx")
+        return gamma, pi, elbo, n_iter, status
+
+    def vbx_centroids(self, gamma: torch.Tensor, pi: torch.Tensor, E: torch.Tensor, rows: torch.Tensor, check_rows: bool = True):
+        """gamma [n, S], pi [S] float64, E [R, d] fp32 unit rows, rows [n] int32 (all on the device) -> (K [1] int32, keep [S] int32,
+        labels [n] int32, cent [S, d] fp32, cent64 [S, d] float64) on the device: sdk_vbx_centroids.  Rows K.. of the centroids are zeros."""
+        n = self._vbx_rows("vbx_centroids", E, rows, check_rows)
+        if gamma.dim() != 2 or gamma.dtype != torch.float64 or gamma.shape[0] != n or not gamma.is_contiguous() or not gamma.is_cuda or gamma.shape[1] < 1:
+            raise ValueError(f"vbx_centroids: gamma must be a contiguous float64 [{n}, S] device tensor, got {tuple(gamma.shape)} {gamma.dtype}")
+        S, d = int(gamma.shape[1]), int(E.shape[1])
+        if pi.dtype != torch.float64 or tuple(pi.shape) != (S,) or not pi.is_contiguous() or not pi.is_cuda:
+            raise ValueError(f"vbx_centroids: pi must be a contiguous float64 [{S}] device tensor, got {tuple(pi.shape)} {pi.dtype}")
+        dev = E.device
+        K = torch.empty((1,), dtype=torch.int32, device=dev)
+        keep = torch.empty((S,), dtype=torch.int32, device=dev)
+        labels = torch.empty((n,), dtype=torch.int32, device=dev)
+        cent = torch.zeros((S, d), dtype=torch.float32, device=dev)
+        cent64 = torch.zeros((S, d), dtype=torch.float64, device=dev)
+        check(self.lib.sdk_vbx_centroids(self.ctx, gamma.data_ptr(), pi.data_ptr(), E.data_ptr(), rows.data_ptr(), n, S, d, K.data_ptr(), keep.data_ptr(),
+                                         labels.data_ptr(), cent.data_ptr(), cent64.data_ptr(), _stream()), "sdk_vbx_centroids")
+        return K, keep, labels, cent, cent64
+
     def asp_fused(self, ah, w2, b2, h, B, T, kblocked=False):
         """kblocked: h is [Cm / 64, B*T, 64] (to_kblocked) - the per-segment form only (sdk_asp_kblocked_ok).  The element format (bf16 or
         fp16) is h's dtype; ah and w2 must match it."""

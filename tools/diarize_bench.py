@@ -8,6 +8,11 @@ process on the same inputs:
   assignment      the constrained stage on the device (training rows and labels up, sdk_diarize_centroids + sdk_diarize_assign, labels, scores
                   and centroids down; wall clock, best of three after a warm-up) beside the host stage it stands in for (the download of
                   the embeddings + diarize.assign_rows) on the same embeddings, and how many chunks the constraint changed
+  vbx             the VBx clustering's device stretch (sdk_plda_transform + sdk_vbx, all iterations enqueued + sdk_vbx_centroids; wall clock
+                  around ONE final synchronisation, best of three after a warm-up) on two inputs - the hour's training rows with the initial
+                  labels of the linkage's cut at 0.6, and a generated table of N = 10 000 rows, D = 128, with 5 true speakers split into 50
+                  initial clusters (the synthetic weights yield one cluster, which exercises nothing) - beside a vectorised numpy restatement
+                  of the same rule on the same input, with at most 16 threads.  Record the line in profiles/r12_vbx_bench.json.
 Record the line in profiles/r11_diarize_assign_bench.json (r10_diarize_bench.json: the line before the constrained stage).  Synthetic weights: the class table is the model's own (noise-like) output, which
 exercises every stage at full size."""
 from __future__ import annotations
@@ -15,15 +20,102 @@ from __future__ import annotations
 import argparse
 import importlib
 import json
+import os
 import sys
 import time
 from pathlib import Path
 
+for _v in ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS"):          # the numpy yardsticks: at most 16 threads
+    os.environ[_v] = str(min(16, int(os.environ.get(_v, "16") or 16)))
 import numpy as np
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 PKG = "speaker-diarization-toolkit_amd"
+
+
+def vbx_numpy(plda, E, init, S, Fa=0.07, Fb=0.8, max_iters=20, epsilon=1e-4, init_smoothing=7.0):
+    """cluster.vbx_cluster's transform, iteration and centroids in vectorised numpy (float64) -> (n_iter, kept speakers, unit centroids)."""
+    X = plda.transform_host(E)
+    Phi = plda.Phi
+    n, D = X.shape
+    rho = X * np.sqrt(Phi)
+    G = -0.5 * ((X ** 2).sum(1) + D * np.log(2 * np.pi))
+    a = np.where(np.arange(S)[None, :] == np.asarray(init)[:, None], 0.0, -init_smoothing)
+    gamma = np.exp(a) / np.exp(a).sum(1, keepdims=True)
+    pi = np.full(S, 1.0 / S)
+    prev, n_iter = None, 0
+    for ii in range(max_iters):
+        invL = 1.0 / (1.0 + Fa / Fb * gamma.sum(0)[:, None] * Phi)
+        alpha = Fa / Fb * invL * (gamma.T @ rho)
+        with np.errstate(divide="ignore"):
+            z = Fa * (rho @ alpha.T - 0.5 * ((invL + alpha ** 2) @ Phi)[None, :] + G[:, None]) + np.log(pi)
+        m = z.max(1, keepdims=True)
+        lse = m[:, 0] + np.log(np.exp(z - m).sum(1))
+        gamma = np.exp(z - lse[:, None])
+        elbo = lse.sum() + 0.5 * Fb * (np.log(invL) - invL - alpha ** 2 + 1).sum()
+        pi = gamma.sum(0) / gamma.sum()
+        n_iter = ii + 1
+        if ii > 0 and elbo - prev < epsilon:
+            break
+        prev = elbo
+    keep = np.flatnonzero(pi > 1e-7)
+    g = gamma[:, keep]
+    cent = (g.T @ E.astype(np.float64)) / g.sum(0)[:, None]
+    return n_iter, keep, cent / np.linalg.norm(cent, axis=1, keepdims=True)
+
+
+def vbx_table(plda_mod, N=10000, d_in=256, D0=128, D=128, S=50, n_true=5, seed=0):
+    """A generated table: n_true speaker means at scale sqrt(Phi) in PLDA space, rows N(mean, I), carried back to unit fp32 embeddings through
+    the inverse of the transform's linear parts; every speaker's rows dealt to its S / n_true initial clusters in turn."""
+    m = plda_mod.synthetic_plda(d_in, D0, seed, D)
+    Phi_full, T_full = plda_mod.prepare(m.tr, m.psi, D0)
+    rng = np.random.default_rng(seed)
+    true = rng.integers(0, n_true, N)
+    x = (rng.standard_normal((n_true, D0)) * np.sqrt(Phi_full))[true] + rng.standard_normal((N, D0))
+
+    def on_sphere(centre, dirs, radius):
+        u = dirs / np.linalg.norm(dirs, axis=1, keepdims=True)
+        b = u @ centre
+        return centre[None, :] + (-b + np.sqrt(b * b + radius * radius - centre @ centre))[:, None] * u
+    y = m.mu[None, :] + x @ np.linalg.inv(T_full).T
+    E = on_sphere(m.mean1, on_sphere(m.mean2, y, np.sqrt(d_in)) @ m.lda.T, 1.0).astype(np.float32)
+    init = np.zeros(N, np.int32)
+    for v in range(n_true):
+        idx = np.flatnonzero(true == v)
+        init[idx] = np.arange(v, S, n_true)[np.arange(len(idx)) % len(np.arange(v, S, n_true))]
+    return m, E, init
+
+
+def vbx_leg(eng, torch, plda, E_d, rows, init, S):
+    """Device time of transform + VBx + centroids (ms, best of three, one synchronisation) and the numpy restatement's on the same input."""
+    rows_d = torch.from_numpy(np.asarray(rows, dtype=np.int32)).cuda()
+    init_d = torch.from_numpy(np.asarray(init, dtype=np.int32)).cuda()
+    Phi = plda.device_arrays(E_d.device)["Phi"]
+
+    def stage():
+        X = eng.plda_transform(E_d, rows_d, plda, check_rows=False)
+        gamma, pi, elbo, n_iter, status = eng.vbx(X, Phi, init_d, S)
+        out = eng.vbx_centroids(gamma, pi, E_d, rows_d, check_rows=False)
+        torch.cuda.synchronize()
+        return n_iter, status, out
+    stage()
+    t_dev = []
+    for _ in range(3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        n_iter, status, (K, keep, _, _, c64) = stage()
+        t_dev.append(time.perf_counter() - t0)
+    Eh = E_d.cpu().numpy()[np.asarray(rows)]
+    t0 = time.perf_counter()
+    n_np, keep_np, cent_np = vbx_numpy(plda, Eh, init, S)
+    t_np = time.perf_counter() - t0
+    Kn = int(K.item())
+    same = Kn == len(keep_np) and np.array_equal(keep.cpu().numpy()[:Kn], keep_np)
+    return {"rows": int(len(rows)), "D": int(plda.lda_dim), "d_in": int(plda.d_in), "initial_speakers": int(S), "kept_speakers": Kn,
+            "n_iter": int(n_iter.item()), "status": int(status.item()), "device_ms": round(min(t_dev) * 1e3, 3), "numpy_ms": round(t_np * 1e3, 3),
+            "numpy_n_iter": int(n_np), "numpy_threads": int(os.environ["OMP_NUM_THREADS"]), "same_kept_speakers": bool(same),
+            "centroids_max_abs_diff": float(np.abs(c64.cpu().numpy()[:Kn] - cent_np).max()) if same else None}
 
 
 def main() -> None:
@@ -159,6 +251,15 @@ def main() -> None:
            "training_rows": int(len(train)), "clusters": int(cent.shape[0]), "turns": len(turns)}
     if constrained is not None:
         out["constrained_assignment"] = constrained
+    plda_mod = importlib.import_module(f"{PKG}.plda")
+    vbx = {}
+    if len(train) > 1:
+        Z = eng.centroid_linkage(E_d.index_select(0, torch.from_numpy(train).cuda()).contiguous()).cpu().numpy()
+        init = cluster.fcluster_distance(Z, cluster.VBX_AHC_THRESHOLD)
+        vbx["hour"] = vbx_leg(eng, torch, plda_mod.synthetic_plda(E_d.shape[1], 128, 0), E_d, train, init, int(init.max()) + 1)
+    m_t, E_t, init_t = vbx_table(plda_mod)
+    vbx["table"] = vbx_leg(eng, torch, m_t, torch.from_numpy(E_t).cuda(), np.arange(len(E_t)), init_t, 50)
+    out["vbx"] = vbx
     if not a.no_yardstick:
         t_three = 0.0
         for b0 in range(0, Cn, a.batch):
