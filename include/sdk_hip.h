@@ -36,6 +36,7 @@
  *     sdk_segmentation_frames  sdk_segmentation_workspace_bytes  sdk_segmentation_forward               speaker segmentation (PyanNet, segmentation.py)
  *     sdk_powerset_decode  sdk_diarize_masks  sdk_resnet_last_map_frames  sdk_resnet_masked_workspace_bytes
  *     sdk_resnet_forward_masked  sdk_diarize_frames  sdk_diarize_reconstruct  sdk_diarize_centroids  sdk_diarize_assign
+ *     sdk_diarize_assign_grouped  sdk_diarize_fold_grouped  sdk_diarize_reconstruct_grouped  sdk_diarize_first_seen  sdk_diarize_renumber
  *                                                                                                       speaker diarization (diarize.py)
  *     sdk_plda_transform  sdk_vbx_workspace_bytes  sdk_vbx  sdk_vbx_centroids                           VBx clustering (plda.py, cluster.vbx_cluster)
  * BUILDING BLOCKS AND KNOBS - exported for the parity tests and the A/B tools, free to change between rounds, not for binding:
@@ -517,6 +518,41 @@ int sdk_diarize_centroids(sdk_ctx* ctx, const float* E, const int32_t* rows, con
                           double* cent64, void* stream);
 int sdk_diarize_assign(sdk_ctx* ctx, const float* E, const int32_t* info, const double* cent64, int C, int K, int d, int constrained,
                        int32_t* labels, float* score, void* stream);
+
+/* ---- many recordings in one pass (diarize.Diarizer.run_many; csrc/diarize.hip): R recordings laid end to end.  chunk_off, frame_off, cent_off,
+ *      cl_off [R + 1] int32 are prefix sums (chunks, global frames, final clusters, clusters of the cut) and, like every other array here, live on
+ *      the DEVICE: the kernels find the recording of a chunk / frame / cluster by a binary search on them (no per-element table).  The totals
+ *      (C chunks, G frames, K or Kc clusters) are passed as arguments so that no call reads the device.  Integer or float64, one owner per
+ *      output element, fixed order: bit-identical run to run; the only atomic is the integer atomicMin of sdk_diarize_first_seen.
+ *   sdk_diarize_assign_grouped : sdk_diarize_assign with the centroids cent_off[r] .. cent_off[r + 1] for the chunks of recording r; labels are
+ *        local to the recording (0 .. K_r - 1); K_r = 0 gives -1 and score 0.  One wave per chunk, any K_r.
+ *   sdk_diarize_fold_grouped : cluster.fold_small_clusters steps 2 - 4.  cent64 [Kc][d] unit centroids of the cut (sdk_diarize_centroids), sizes
+ *        [Kc], eff [R] the effective minimum size.  target [Kc] (scratch): a cluster with sizes >= eff stays, every other goes to the large
+ *        cluster of its recording with the largest float64 cosine (fma chain in column order; ties to the lower cluster), or to the
+ *        recording's first cluster when none is large.  remap [Kc] = cent_off[r] + the kept cluster's number by first appearance (the cut's
+ *        labels are canonical); the caller's cent_off must count the large clusters (1 when none).  out [n] = remap[cut[i]] (cut: the cut's
+ *        global cluster of every training row; NULL with n = 0).
+ *   sdk_diarize_reconstruct_grouped : thread = packed frame; sdk_diarize_reconstruct inside the chunk range and with the K_r of the frame's
+ *        recording (K_r = 0 as K = 1); starts_local [C] are first samples inside the chunk's own recording, ascending per recording;
+ *        n_samples [R] int64; act (or NULL) holds recording r's [G_r][max(K_r, 1)] table at act_off[r] (int64 [R + 1]).
+ *   sdk_diarize_first_seen : first [K] = the least 2 g + slot at which the cluster stands in speakers of its recording (g local), INT32_MAX
+ *        when never (integer atomicMin).
+ *   sdk_diarize_renumber : renum [K] = rank of (first[k], k) inside the recording (diarize.appearance_order); labels [C][3] (local) are
+ *        rewritten in place; the centroid rows go to cent_off[r] + renum[k] of cent_out / cent64_out (not in place). */
+int sdk_diarize_assign_grouped(sdk_ctx* ctx, const float* E, const int32_t* info, const double* cent64, const int32_t* chunk_off,
+                               const int32_t* cent_off, int R, int C, int d, int constrained, int32_t* labels, float* score, void* stream);
+int sdk_diarize_fold_grouped(sdk_ctx* ctx, const double* cent64, const int32_t* sizes, const int32_t* cl_off, const int32_t* eff,
+                             const int32_t* cent_off, int R, int Kc, int d, int32_t* target, int32_t* remap, const int32_t* cut, int n,
+                             int32_t* out, void* stream);
+int sdk_diarize_reconstruct_grouped(sdk_ctx* ctx, const uint8_t* cls, const int32_t* starts_local, const int32_t* labels,
+                                    const int32_t* chunk_off, const int32_t* frame_off, const int64_t* n_samples, const int32_t* cent_off,
+                                    int R, int C, int F, int64_t G, int max_speakers, uint8_t* count, int32_t* speakers, int32_t* act,
+                                    const int64_t* act_off, void* stream);
+int sdk_diarize_first_seen(sdk_ctx* ctx, const int32_t* speakers, const int32_t* frame_off, const int32_t* cent_off, int R, int64_t G, int K,
+                           int32_t* first, void* stream);
+int sdk_diarize_renumber(sdk_ctx* ctx, const int32_t* first, const int32_t* cent_off, const int32_t* chunk_off, int R, int K, int C, int d,
+                         int32_t* renum, int32_t* labels, const float* cent, const double* cent64, float* cent_out, double* cent64_out,
+                         void* stream);
 
 /* ---- VBx clustering of the diarization (cluster.vbx_cluster, plda.py; csrc/vbx.hip): float64 arithmetic, every sum over rows over fixed 64-row
  *      blocks whose partials are combined in block order, no floating-point atomics, one owner per output element: bit-identical run to

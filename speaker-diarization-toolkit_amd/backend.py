@@ -458,6 +458,21 @@ class Backend(EmbeddingBackend):
             if dz.eng.precision != prec:
                 dz.eng.set_precision(prec)                       # the front end's format goes back to the selected family's contract
 
+    def diarize_many(self, samples_or_paths, **kw):
+        """diarize for a folder of recordings in one device pass per pack: a list of recordings (16 kHz mono int16 samples or paths of audio
+        files, decoded to the audio profile) -> a list of diarize.DiarizationResult, in order.  Chunks of different recordings share the
+        segmentation and embedding batches, one grouped linkage launch clusters all recordings, and assignment, fold and stitching run in
+        grouped kernels; the host waits for the device a fixed number of times per pack, not per recording (diarize.Diarizer.run_many,
+        which also states how the results relate to diarize's).  Keywords as diarize; logp is a list with one array per recording."""
+        dz = self.diarizer()
+        recs = [decode_to_profile(Path(x), self.engine(), self.get_audio_profile()) if isinstance(x, (str, Path)) else x for x in samples_or_paths]
+        prec = dz.eng.precision
+        try:
+            return dz.run_many(recs, **kw)
+        finally:
+            if dz.eng.precision != prec:
+                dz.eng.set_precision(prec)                       # the front end's format goes back to the selected family's contract
+
     # ---- a2: enroll (base.py:107-128) ---------------------------------------------------------
     def enroll_speaker(self, audio_path: Path, segments: Optional[List[Tuple[float, float]]] = None) -> Dict[str, Any]:
         if segments:           # the caller vouches that each range is this speaker: true-length windows, never widened

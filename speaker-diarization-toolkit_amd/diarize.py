@@ -38,6 +38,14 @@ tests pin these rules.
               that never surface keep their relative order behind the others); the stitching is then run with the final numbers
   turns       per speaker, runs of frames with segmentation.frames_to_ranges's boundaries; no gap filling; overlap gives simultaneous turns
 
+  many        (Diarizer.run_many, Backend.diarize_many) a folder of recordings crosses the pipeline as packs: the recordings laid end to end in
+              one buffer with CHUNK zero samples behind each (pack_recordings), so chunks of different recordings share the segmentation /
+              embedding batches and a chunk that runs past its recording's end reads zeros, as it does alone; ONE grouped centroid_linkage
+              launch for all recordings; the cut per recording on the host (integers and Z); fold, centroids, assignment, stitching and the
+              renumbering by appearance in grouped kernels (sdk_diarize_*_grouped, sdk_diarize_first_seen, sdk_diarize_renumber) that find
+              a chunk's, frame's or cluster's recording by binary search on prefix-sum tables.  The embeddings never leave the device and
+              the host waits for the device a fixed number of times per pack.
+
 Decode, masks, the constrained assignment and stitching run in libsdk_hip.so (csrc/diarize.hip), the pooling in csrc/resnet.hip; the *_host
 functions below restate them in numpy for hosts that post-process stored class tables.  The host receives info, the unit embeddings (not
 with constrained=True: then labels, scores and centroids instead), and count / speakers only.
@@ -251,6 +259,149 @@ def to_rttm(turns, uri: str) -> str:
     return "".join(f"SPEAKER {uri} 1 {a:.3f} {b - a:.3f} <NA> <NA> SPEAKER_{k:02d} <NA> <NA>\n" for a, b, k in turns)
 
 
+# ------------------------------------------------------------------------------------------------ many recordings: packing and the grouped rules
+MAX_PACK_SAMPLES = (1 << 31) - 1 # starts are int32
+DEFAULT_PACK_SAMPLES = 1 << 28   # $SDK_DIARIZE_PACK_SAMPLES: samples per pack of run_many (gaps included)
+DEFAULT_PACK_LINKAGE_BYTES = 1 << 34   # $SDK_DIARIZE_PACK_LINKAGE_BYTES: bound on the grouped linkage's distance matrices, 8 (3 C_r)^2 bytes per recording
+
+
+@dataclass
+class Pack:
+    """Recordings laid end to end (pack_recordings)."""
+    samples: np.ndarray          # int16: recording r at rec_off[r], at least CHUNK zeros behind every recording
+    starts_packed: np.ndarray    # [C] int32 chunk starts inside samples
+    starts_local: np.ndarray     # [C] int32 chunk starts inside their own recording (chunk_starts; ascending per recording)
+    chunk_off: np.ndarray        # [R + 1] int64 prefix sums of the chunks
+    frame_off: np.ndarray        # [R + 1] int64 prefix sums of global_frames(n_r)
+    n_samples: np.ndarray        # [R] int64
+    rec_off: np.ndarray          # [R] int64 first sample of every recording inside samples
+
+
+def pack_recordings(recordings, step_s: float = 1.0) -> Pack:
+    """16 kHz mono int16 arrays -> Pack.  sdk_segmentation_forward and sdk_fbank_windows cut chunks from a start table and read zeros past the
+    end of the buffer; with CHUNK zeros behind every recording a chunk that runs past its recording's end (a recording below 10 s) reads
+    zeros exactly as it does alone and never the next recording.  An empty recording has no chunk and no frame."""
+    xs = [np.ascontiguousarray(x, dtype=np.int16).reshape(-1) for x in recordings]
+    n = np.array([x.size for x in xs], np.int64)
+    rec_off = np.concatenate([[0], np.cumsum(n + CHUNK)]).astype(np.int64)
+    if rec_off[-1] > MAX_PACK_SAMPLES:
+        raise ValueError(f"pack_recordings: {int(rec_off[-1])} samples with the gaps; a pack holds fewer than 2^31 (the chunk starts are int32)")
+    buf = np.zeros(int(rec_off[-1]), np.int16)
+    local = [chunk_starts(int(m), step_s) if m else np.zeros(0, np.int64) for m in n]
+    for x, o in zip(xs, rec_off):
+        buf[o:o + x.size] = x
+    packed = [st + o for st, o in zip(local, rec_off)]
+    cat = (lambda v: np.concatenate(v) if v else np.zeros(0, np.int64))
+    return Pack(buf, cat(packed).astype(np.int32), cat(local).astype(np.int32), np.concatenate([[0], np.cumsum([len(v) for v in local])]).astype(np.int64),
+                np.concatenate([[0], np.cumsum([global_frames(int(m)) for m in n])]).astype(np.int64), n, rec_off[:-1].copy())
+
+
+def _dot_in_order(A: np.ndarray, B: np.ndarray) -> np.ndarray:
+    """A [m, d], B [K, d] float64 -> [m, K]: every entry one sum over the columns in ascending order (the kernels' order; numpy's own
+    reductions add pairwise)."""
+    acc = np.zeros((A.shape[0], B.shape[0]))
+    for j in range(A.shape[1]):
+        acc += A[:, j, None] * B[None, :, j]
+    return acc
+
+
+def assign_grouped_host(E, info, cent64, chunk_off, cent_off, constrained: bool = False):
+    """sdk_diarize_assign_grouped in numpy: E [3 C, d], info [C, 3, 4], cent64 [K, d] float64, chunk_off / cent_off [R + 1] ->
+    (labels [C, 3] int32 local to the recording, score [C, 3] float64).  Rows that are no candidates are never read."""
+    i = np.asarray(info).reshape(-1, 4)
+    Cn = i.shape[0] // N_LOCAL
+    ok = ((i[:, 3] != 0) & (i[:, 0] > 0)).reshape(Cn, N_LOCAL)
+    labels, score = np.full((Cn, N_LOCAL), -1, np.int32), np.zeros((Cn, N_LOCAL))
+    cent64 = np.asarray(cent64, dtype=np.float64)
+    for r in range(len(chunk_off) - 1):
+        cent = cent64[int(cent_off[r]):int(cent_off[r + 1])]
+        if not cent.shape[0]:
+            continue
+        for c in range(int(chunk_off[r]), int(chunk_off[r + 1])):
+            slots = np.flatnonzero(ok[c])
+            if not slots.size:
+                continue
+            cos = _dot_in_order(np.asarray(E)[c * N_LOCAL + slots].astype(np.float64), cent)
+            if constrained:
+                lab = constrained_chunk(cos)
+            else:
+                lab = [int(np.argmax(np.where(row == row, row, -np.inf))) if (row == row).any() else -1 for row in cos]   # a NaN never wins
+            for s, row, k in zip(slots, cos, lab):
+                if k >= 0:
+                    labels[c, s], score[c, s] = k, row[k]
+    return labels, score
+
+
+def fold_grouped_host(cent64, sizes, cl_off, eff, cent_off) -> np.ndarray:
+    """sdk_diarize_fold_grouped in numpy: the cut's unit centroids [Kc, d] float64, sizes [Kc], cl_off [R + 1], eff [R], cent_off [R + 1] ->
+    remap [Kc] int32, the final global cluster (cent_off[r] + number by first appearance) of every cluster of the cut."""
+    cent64, sizes = np.asarray(cent64, dtype=np.float64), np.asarray(sizes)
+    remap = np.full(sizes.shape[0], -1, np.int32)
+    for r in range(len(cl_off) - 1):
+        b, e = int(cl_off[r]), int(cl_off[r + 1])
+        if b == e:
+            continue
+        large = b + np.flatnonzero(sizes[b:e] >= eff[r])
+        target = np.arange(b, e)
+        if large.size == 0:
+            target[:] = b
+        else:
+            small = b + np.flatnonzero(sizes[b:e] < eff[r])
+            if small.size:
+                target[small - b] = large[np.argmax(_dot_in_order(cent64[small], cent64[large]), axis=1)]   # first maximum: the lower cluster
+        _, first = np.unique(target, return_index=True)                   # kept clusters by the lowest cluster sent to them
+        new = {int(t): int(cent_off[r]) + n for n, t in enumerate(target[np.sort(first)])}
+        remap[b:e] = [new[int(t)] for t in target]
+    return remap
+
+
+def reconstruct_grouped_host(cls, starts_local, labels, chunk_off, frame_off, n_samples, cent_off, max_speakers: Optional[int] = None):
+    """sdk_diarize_reconstruct_grouped in numpy -> (count [G] uint8, speakers [G, 2] int32, act: one [G_r, max(K_r, 1)] int32 table per
+    recording) on the packed frame grid."""
+    G = int(frame_off[-1])
+    count, speakers, acts = np.zeros(G, np.uint8), np.full((G, 2), -1, np.int32), []
+    for r in range(len(chunk_off) - 1):
+        a, b = int(chunk_off[r]), int(chunk_off[r + 1])
+        K = max(int(cent_off[r + 1] - cent_off[r]), 1)
+        n_g = int(frame_off[r + 1] - frame_off[r])
+        if a == b or n_g == 0:
+            acts.append(np.zeros((n_g, K), np.int32))
+            continue
+        cnt, spk, act, _ = reconstruct_host(np.asarray(cls)[a:b], np.asarray(starts_local)[a:b], np.asarray(labels)[a:b], K, int(n_samples[r]), max_speakers)
+        g0 = int(frame_off[r])
+        m = min(n_g, len(cnt))
+        count[g0:g0 + m], speakers[g0:g0 + m] = cnt[:m], spk[:m]
+        acts.append(act)
+    return count, speakers, acts
+
+
+def first_seen_host(speakers, frame_off, cent_off) -> np.ndarray:
+    """sdk_diarize_first_seen in numpy -> first [K] int32: the least 2 g + slot (g inside the recording) at which the cluster stands in
+    speakers [G, 2] of its recording, INT32_MAX when never."""
+    sp = np.asarray(speakers).reshape(-1, 2)
+    first = np.full(int(cent_off[-1]), np.iinfo(np.int32).max, np.int32)
+    for r in range(len(frame_off) - 1):
+        flat = sp[int(frame_off[r]):int(frame_off[r + 1])].reshape(-1)
+        pos = np.flatnonzero((flat >= 0) & (flat < cent_off[r + 1] - cent_off[r]))
+        np.minimum.at(first, int(cent_off[r]) + flat[pos], pos.astype(np.int32))
+    return first
+
+
+def renumber_host(first, cent_off, chunk_off, labels, cent):
+    """sdk_diarize_renumber in numpy: renum [K] = rank of (first[k], k) inside the recording (appearance_order); -> (renum, labels
+    rewritten, cent rows permuted)."""
+    first, labels, cent = np.asarray(first), np.array(labels, dtype=np.int32), np.asarray(cent)
+    renum, out = np.zeros(len(first), np.int32), np.empty_like(cent)
+    for r in range(len(cent_off) - 1):
+        b, e = int(cent_off[r]), int(cent_off[r + 1])
+        order = np.lexsort((np.arange(e - b), first[b:e]))                # by first, then by cluster
+        renum[b + order] = np.arange(e - b)
+        out[b + renum[b:e]] = cent[b:e]
+        lab = labels[int(chunk_off[r]):int(chunk_off[r + 1])]
+        lab[lab >= 0] = renum[b + lab[lab >= 0]]
+    return renum, labels, out
+
+
 # ------------------------------------------------------------------------------------------------ device stages
 def powerset_decode(eng, logp):
     """logp [C, F, 7] fp32 (device) -> cls [C, F] uint8 (device): sdk_powerset_decode."""
@@ -311,9 +462,10 @@ def _check_rows(name: str, E, d_what: str = "E"):
         raise ValueError(f"{name}: d={E.shape[1]} not supported (a multiple of 64, at most {MAX_ASSIGN_DIM})")
 
 
-def diarize_centroids(eng, E, rows, labels, K: int):
+def diarize_centroids(eng, E, rows, labels, K: int, check_rows: bool = True):
     """E [R, d] fp32 unit rows, rows [n] int32 ascending, labels [n] int32 in [0, K) (all on the device) -> (cent [K, d] fp32 unit,
-    cent64 [K, d] float64) on the device: sdk_diarize_centroids.  A cluster without rows gives a zero row."""
+    cent64 [K, d] float64) on the device: sdk_diarize_centroids.  A cluster without rows gives a zero row.  check_rows=False: the caller
+    has checked that rows lie in [0, R) (the check reads them back, which waits for the device)."""
     import torch
     from ._lib import check
     from .ops import _stream
@@ -325,7 +477,7 @@ def diarize_centroids(eng, E, rows, labels, K: int):
                          f"{tuple(labels.shape)} {labels.dtype}")
     rows, labels = rows.contiguous(), labels.contiguous()
     n, d = int(rows.numel()), int(E.shape[1])
-    if n and not (0 <= int(rows.min()) and int(rows.max()) < E.shape[0]):   # the kernel reads E at these rows
+    if check_rows and n and not (0 <= int(rows.min()) and int(rows.max()) < E.shape[0]):   # the kernel reads E at these rows
         raise ValueError(f"diarize_centroids: rows must lie in [0, {E.shape[0]}), got {int(rows.min())} .. {int(rows.max())}")
     cent = torch.empty((int(K), d), dtype=torch.float32, device=E.device)
     cent64 = torch.empty((int(K), d), dtype=torch.float64, device=E.device)
@@ -353,6 +505,156 @@ def diarize_assign(eng, E, info, cent, constrained: bool = False):
     check(eng.lib.sdk_diarize_assign(eng.ctx, E.data_ptr(), info.data_ptr(), cent.data_ptr(), Cn, int(cent.shape[0]), d, int(bool(constrained)),
                                      labels.data_ptr(), score.data_ptr(), _stream()), "sdk_diarize_assign")
     return labels, score
+
+
+class GroupTables:
+    """The prefix-sum tables of a pack on the host (checked here, once) and on the device (what the grouped kernels search)."""
+
+    def __init__(self, eng, chunk_off, frame_off, n_samples, starts_local=None):
+        import torch
+        self.eng = eng
+        self.chunk_off, self.frame_off = np.asarray(chunk_off, dtype=np.int64), np.asarray(frame_off, dtype=np.int64)
+        self.n_samples = np.asarray(n_samples, dtype=np.int64)
+        self.R = R = int(self.n_samples.size)
+        for name, off in (("chunk_off", self.chunk_off), ("frame_off", self.frame_off)):
+            if R < 1 or off.shape != (R + 1,) or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] >= (1 << 30):
+                raise ValueError(f"GroupTables: {name} must hold R + 1 = {R + 1} prefix sums from 0 (below 2^30), got {off.tolist()[:8]}")
+        if not np.array_equal(np.diff(self.frame_off), [global_frames(int(n)) for n in self.n_samples]):
+            raise ValueError("GroupTables: frame_off must be the prefix sums of global_frames(n_samples)")
+        self.C, self.G = int(self.chunk_off[-1]), int(self.frame_off[-1])
+        parts = [self.chunk_off, self.frame_off] + ([np.asarray(starts_local, dtype=np.int64)] if starts_local is not None else [])
+        if starts_local is not None and parts[2].shape != (self.C,):
+            raise ValueError(f"GroupTables: starts_local must hold {self.C} chunk starts, got {parts[2].shape}")
+        up = torch.from_numpy(np.concatenate(parts).astype(np.int32)).to(eng.device)                 # one upload
+        self.chunk_off_d, self.frame_off_d = up[:R + 1], up[R + 1:2 * R + 2]
+        self.starts_local_d = up[2 * R + 2:] if starts_local is not None else None
+        self.n_samples_d = torch.from_numpy(self.n_samples).to(eng.device)
+        self.cent_off = self.cent_off_d = self.act_off = self.act_off_d = None
+        self.K = 0
+
+    def set_clusters(self, cent_off, want_act: bool = False):
+        """cent_off [R + 1]: prefix sums of the recordings' cluster counts."""
+        import torch
+        off = np.asarray(cent_off, dtype=np.int64)
+        if off.shape != (self.R + 1,) or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] >= (1 << 30):
+            raise ValueError(f"GroupTables: cent_off must hold R + 1 = {self.R + 1} prefix sums from 0, got {off.tolist()[:8]}")
+        self.cent_off, self.K = off, int(off[-1])
+        self.cent_off_d = torch.from_numpy(off.astype(np.int32)).to(self.eng.device)
+        self.act_off = np.concatenate([[0], np.cumsum(np.diff(self.frame_off) * np.maximum(np.diff(off), 1))]).astype(np.int64)
+        self.act_off_d = torch.from_numpy(self.act_off).to(self.eng.device) if want_act else None
+        return self
+
+
+def diarize_assign_grouped(eng, E, info, cent, tab: GroupTables, constrained: bool = False):
+    """diarize_assign over a pack: cent [K, d] float64 holds recording r's centroids at tab.cent_off[r] .. tab.cent_off[r + 1] ->
+    (labels [C, 3] int32 local to the recording, score [C, 3] fp32) on the device: sdk_diarize_assign_grouped."""
+    import torch
+    from ._lib import check
+    from .ops import _stream
+    _check_rows("diarize_assign_grouped", E)
+    Cn, d = tab.C, int(E.shape[1])
+    if E.shape[0] != N_LOCAL * Cn or info.dtype != torch.int32 or tuple(info.shape) != (Cn, N_LOCAL, 4) or not info.is_contiguous():
+        raise ValueError(f"diarize_assign_grouped: E [{3 * Cn}, d] and a contiguous int32 info [{Cn}, 3, 4] expected, got {tuple(E.shape)}, {tuple(info.shape)} {info.dtype}")
+    if tab.cent_off is None or cent.dim() != 2 or cent.dtype != torch.float64 or cent.shape[1] != d or not cent.is_contiguous() or cent.shape[0] < max(tab.K, 1):
+        raise ValueError(f"diarize_assign_grouped: the centroids must be a contiguous float64 [{max(tab.K, 1)}, {d}] tensor, got {tuple(cent.shape)} {cent.dtype}")
+    labels = torch.empty((Cn, N_LOCAL), dtype=torch.int32, device=E.device)
+    score = torch.empty((Cn, N_LOCAL), dtype=torch.float32, device=E.device)
+    check(eng.lib.sdk_diarize_assign_grouped(eng.ctx, E.data_ptr(), info.data_ptr(), cent.data_ptr(), tab.chunk_off_d.data_ptr(), tab.cent_off_d.data_ptr(),
+                                             tab.R, Cn, d, int(bool(constrained)), labels.data_ptr(), score.data_ptr(), _stream()), "sdk_diarize_assign_grouped")
+    return labels, score
+
+
+def diarize_fold_grouped(eng, cent, sizes, cl_off, eff, cent_off, cut=None):
+    """The fold of cluster.fold_small_clusters over a pack, on the device: cent [Kc, d] float64 unit centroids of the cut (device), sizes
+    [Kc], cl_off [R + 1], eff [R], cent_off [R + 1] (host integers; cent_off must count the large clusters of every recording, 1 when it has
+    clusters and none is large), cut [n] int32 (device, or None): the cut's global cluster of every training row ->
+    (remap [Kc] int32, out [n] int32 = remap[cut], or None) on the device: sdk_diarize_fold_grouped."""
+    import torch
+    from ._lib import check
+    from .ops import _stream
+    sizes, cl_off, eff, cent_off = (np.asarray(v, dtype=np.int64) for v in (sizes, cl_off, eff, cent_off))
+    R, Kc = int(eff.size), int(sizes.size)
+    large = None
+    if R >= 1 and cl_off.shape == (R + 1,) and cl_off[0] == 0 and cl_off[-1] == Kc and (np.diff(cl_off) >= 0).all():
+        rec = np.repeat(np.arange(R), np.diff(cl_off))                    # the recording of every cluster of the cut
+        large = np.bincount(rec[sizes >= eff[rec]], minlength=R)
+    if large is None or cent_off.shape != (R + 1,) or cent_off[0] != 0 or not np.array_equal(np.diff(cent_off), np.where(np.diff(cl_off) > 0, np.maximum(large, 1), 0)):
+        raise ValueError("diarize_fold_grouped: cl_off must be the R + 1 prefix sums of the cut's cluster counts and cent_off those of the large clusters (1 when none)")
+    d = int(cent.shape[1]) if cent.dim() == 2 else 0
+    if cent.dtype != torch.float64 or not cent.is_contiguous() or cent.shape[0] < Kc or d < 64 or d % 64 or d > MAX_ASSIGN_DIM:
+        raise ValueError(f"diarize_fold_grouped: the centroids must be a contiguous float64 [{Kc}, d] tensor (d a multiple of 64, at most {MAX_ASSIGN_DIM}), got {tuple(cent.shape)} {cent.dtype}")
+    n = 0 if cut is None else int(cut.numel())
+    if cut is not None and (cut.dtype != torch.int32 or cut.dim() != 1 or not cut.is_contiguous()):
+        raise ValueError(f"diarize_fold_grouped: cut must be a contiguous int32 [n] tensor, got {tuple(cut.shape)} {cut.dtype}")
+    up = torch.from_numpy(np.concatenate([sizes, cl_off, eff, cent_off]).astype(np.int32)).to(cent.device)
+    sizes_d, cl_d, eff_d, co_d = up[:Kc], up[Kc:Kc + R + 1], up[Kc + R + 1:Kc + 2 * R + 1], up[Kc + 2 * R + 1:]
+    target = torch.empty((max(Kc, 1),), dtype=torch.int32, device=cent.device)
+    remap = torch.empty((max(Kc, 1),), dtype=torch.int32, device=cent.device)
+    out = torch.empty((max(n, 1),), dtype=torch.int32, device=cent.device)
+    check(eng.lib.sdk_diarize_fold_grouped(eng.ctx, cent.data_ptr(), sizes_d.data_ptr(), cl_d.data_ptr(), eff_d.data_ptr(), co_d.data_ptr(), R, Kc, d,
+                                           target.data_ptr(), remap.data_ptr(), cut.data_ptr() if n else None, n, out.data_ptr(), _stream()),
+          "sdk_diarize_fold_grouped")
+    return remap[:Kc], (out[:n] if cut is not None else None)
+
+
+def diarize_reconstruct_grouped(eng, cls, labels, tab: GroupTables, max_speakers: Optional[int] = None, want_act: bool = False):
+    """diarize_reconstruct over a pack: cls [C, F] uint8, labels [C, 3] int32 local to the recording (device), tab with starts_local and
+    clusters set -> (count [G] uint8, speakers [G, 2] int32, act int32 [tab.act_off[-1]] or None) on the packed frame grid:
+    sdk_diarize_reconstruct_grouped."""
+    import torch
+    from ._lib import check
+    from .ops import _stream
+    if cls.dim() != 2 or cls.dtype != torch.uint8 or not cls.is_contiguous() or cls.shape[0] != tab.C:
+        raise ValueError(f"diarize_reconstruct_grouped: cls must be a contiguous uint8 [{tab.C}, F] tensor, got {tuple(cls.shape)} {cls.dtype}")
+    if labels.dtype != torch.int32 or tuple(labels.shape) != (tab.C, N_LOCAL) or not labels.is_contiguous():
+        raise ValueError(f"diarize_reconstruct_grouped: labels must be a contiguous int32 [{tab.C}, 3] tensor, got {tuple(labels.shape)} {labels.dtype}")
+    if tab.starts_local_d is None or tab.cent_off is None or (want_act and tab.act_off_d is None):
+        raise ValueError("diarize_reconstruct_grouped: the tables need starts_local and set_clusters (want_act=True for act)")
+    cap = 2 if max_speakers is None else min(2, int(max_speakers))
+    count = torch.zeros((tab.G,), dtype=torch.uint8, device=cls.device)
+    speakers = torch.full((tab.G, 2), -1, dtype=torch.int32, device=cls.device)
+    act = torch.zeros((max(int(tab.act_off[-1]), 1),), dtype=torch.int32, device=cls.device) if want_act else None
+    if tab.C and tab.G:
+        check(eng.lib.sdk_diarize_reconstruct_grouped(eng.ctx, cls.data_ptr(), tab.starts_local_d.data_ptr(), labels.data_ptr(), tab.chunk_off_d.data_ptr(),
+                                                      tab.frame_off_d.data_ptr(), tab.n_samples_d.data_ptr(), tab.cent_off_d.data_ptr(), tab.R, tab.C,
+                                                      int(cls.shape[1]), tab.G, cap, count.data_ptr(), speakers.data_ptr(),
+                                                      act.data_ptr() if want_act else None, tab.act_off_d.data_ptr() if want_act else None, _stream()),
+              "sdk_diarize_reconstruct_grouped")
+    return count, speakers, act
+
+
+def diarize_first_seen(eng, speakers, tab: GroupTables):
+    """speakers [G, 2] int32 (device) -> first [K] int32 (device): sdk_diarize_first_seen (integer atomicMin)."""
+    import torch
+    from ._lib import check
+    from .ops import _stream
+    if speakers.dtype != torch.int32 or tuple(speakers.shape) != (tab.G, 2) or not speakers.is_contiguous() or tab.cent_off is None:
+        raise ValueError(f"diarize_first_seen: speakers must be a contiguous int32 [{tab.G}, 2] tensor and the tables hold clusters, got {tuple(speakers.shape)} {speakers.dtype}")
+    first = torch.empty((max(tab.K, 1),), dtype=torch.int32, device=speakers.device)
+    check(eng.lib.sdk_diarize_first_seen(eng.ctx, speakers.data_ptr(), tab.frame_off_d.data_ptr(), tab.cent_off_d.data_ptr(), tab.R, tab.G, tab.K,
+                                         first.data_ptr(), _stream()), "sdk_diarize_first_seen")
+    return first[:tab.K]
+
+
+def diarize_renumber(eng, first, labels, cent, cent64, tab: GroupTables):
+    """first [K] (diarize_first_seen), labels [C, 3] int32 local (REWRITTEN in place), cent [K, d] fp32 and cent64 [K, d] float64 ->
+    (renum [K] int32, cent and cent64 with recording r's rows permuted to their new numbers) on the device: sdk_diarize_renumber."""
+    import torch
+    from ._lib import check
+    from .ops import _stream
+    K = tab.K
+    if first.dtype != torch.int32 or first.numel() != K or labels.dtype != torch.int32 or tuple(labels.shape) != (tab.C, N_LOCAL) or not labels.is_contiguous():
+        raise ValueError(f"diarize_renumber: first int32 [{K}] and a contiguous int32 labels [{tab.C}, 3] expected, got {tuple(first.shape)}, {tuple(labels.shape)} {labels.dtype}")
+    if cent.dtype != torch.float32 or cent64.dtype != torch.float64 or cent.dim() != 2 or cent.shape != cent64.shape or cent.shape[0] < K \
+            or not cent.is_contiguous() or not cent64.is_contiguous():
+        raise ValueError(f"diarize_renumber: contiguous fp32 and float64 centroids [{K}, d] expected, got {tuple(cent.shape)} {cent.dtype}, {tuple(cent64.shape)} {cent64.dtype}")
+    renum = torch.empty((max(K, 1),), dtype=torch.int32, device=labels.device)
+    o32, o64 = torch.empty_like(cent), torch.empty_like(cent64)
+    check(eng.lib.sdk_diarize_renumber(eng.ctx, first.data_ptr(), tab.cent_off_d.data_ptr(), tab.chunk_off_d.data_ptr(), tab.R, K, tab.C, int(cent.shape[1]),
+                                       renum.data_ptr(), labels.data_ptr(), cent.data_ptr(), cent64.data_ptr(), o32.data_ptr(), o64.data_ptr(), _stream()),
+          "sdk_diarize_renumber")
+    return renum[:K], o32, o64
+
 
 
 class Diarizer:
@@ -476,3 +778,215 @@ class Diarizer:
         if vres is not None:
             res.pi, res.elbo = vres.pi, vres.elbo
         return res
+
+    # ---------------------------------------------------------------------------------------------- many recordings in one device pass
+    def _empty(self) -> DiarizationResult:
+        d = self.resnet.cfg.embed_dim
+        return DiarizationResult([], 0, np.zeros((0, d), np.float32), np.zeros((0, N_LOCAL), np.int32), np.zeros(0, np.uint8),
+                                 np.full((0, 2), -1, np.int32), np.zeros(0, np.int64), np.zeros((0, N_LOCAL, 4), np.int32))
+
+    def run_many(self, recordings, step_s: float = 1.0, threshold: float = PYANNOTE_THRESHOLD, min_cluster_size: int = PYANNOTE_MIN_CLUSTER_SIZE,
+                 max_speakers: Optional[int] = None, logp=None, constrained: bool = False, clustering: str = "ahc",
+                 vbx: Optional[dict] = None) -> List[DiarizationResult]:
+        """recordings: a list of 16 kHz mono int16 arrays (host) -> one DiarizationResult per recording, in order; the keywords are run's,
+        logp is None or a list with one [C_r, 589, 7] array per recording.  The recordings cross the pipeline in packs (pack_recordings) of
+        at most $SDK_DIARIZE_PACK_SAMPLES samples (default 2^28, gaps included) whose grouped linkage stays within
+        $SDK_DIARIZE_PACK_LINKAGE_BYTES of distance matrices (default 2^34; Engine.centroid_linkage serves any number of problems of at
+        most 65 536 rows each); a recording that exceeds either bound alone is a pack of its own.  Per pack: one upload, the batches of
+        $SDK_DIARIZE_BATCH chunks (they cross recording boundaries), one download of info, one grouped linkage launch over the recordings
+        with at least two training rows and the download of its status and Z, the cut per recording on the host, then centroids of the cut,
+        fold, final centroids, assignment, stitching, renumbering and second stitching on the device, and one download each of labels,
+        scores, centroids, count and speakers.  self.last_sync holds the number of such waits of the last call, per pack.
+
+        For every recording cls, info, labels, count, speakers, turns, n_speakers and starts equal run(..., constrained=True)'s when
+        constrained=True.  With constrained=False they equal run's provided no decision is a tie or near-tie at float64 rounding: run's
+        unconstrained assignment is a BLAS product on the host, this one sdk_diarize_assign_grouped's column-order float64 sum (so every
+        result carries scores).  The same proviso holds for the fold (run folds on the host with a BLAS product).  Centroids agree to fp32
+        rounding of the same float64 rows.  clustering="vbx" runs cluster.vbx_cluster recording by recording (its own linkage, cut and
+        host reads per recording) between the packed embedding and the grouped assignment: a grouped VBx is out of scope."""
+        from .cluster import vbx_cluster  # noqa: F401  (checked early: the package imports)
+        if clustering not in ("ahc", "vbx"):
+            raise ValueError(f"diarize_many: clustering={clustering!r} (\"ahc\" or \"vbx\")")
+        vbx = dict(vbx or {})
+        unknown = sorted(set(vbx) - {"Fa", "Fb", "max_iters", "epsilon", "init_smoothing"})
+        if unknown or (vbx and clustering != "vbx"):
+            raise ValueError(f"diarize_many: vbx={vbx} (keys Fa, Fb, max_iters, epsilon, init_smoothing; only with clustering=\"vbx\")")
+        if max_speakers is not None and int(max_speakers) < 0:
+            raise ValueError(f"max_speakers={max_speakers}: must be None or >= 0")
+        xs = [np.ascontiguousarray(x, dtype=np.int16).reshape(-1) for x in recordings]
+        if logp is not None and (not isinstance(logp, (list, tuple)) or len(logp) != len(xs)):
+            raise ValueError(f"diarize_many: logp must be None or a list with one array per recording ({len(xs)}), got "
+                             f"{len(logp) if isinstance(logp, (list, tuple)) else type(logp).__name__}")
+        F = seg_frames(CHUNK)
+        n_chunks = [len(chunk_starts(x.size, step_s)) if x.size else 0 for x in xs]
+        for i, Cn in enumerate(n_chunks):
+            if N_LOCAL * Cn > MAX_LINKAGE_ROWS:
+                raise ValueError(f"diarize_many: recording {i}: {Cn} chunks at step_s={step_s} give up to {N_LOCAL * Cn} embeddings to cluster; the centroid "
+                                 f"linkage serves at most {MAX_LINKAGE_ROWS} rows ({MAX_LINKAGE_ROWS // N_LOCAL} chunks): raise step_s or split the recording")
+            if logp is not None and xs[i].size:
+                shp = tuple(getattr(logp[i], "shape", np.shape(logp[i])))
+                if shp != (Cn, F, 7):
+                    raise ValueError(f"diarize_many: recording {i}: injected logp must be [{Cn}, {F}, 7] for {xs[i].size} samples at step_s={step_s}, got {shp}")
+        cap_s = min(MAX_PACK_SAMPLES, max(1, int(os.environ.get("SDK_DIARIZE_PACK_SAMPLES", str(DEFAULT_PACK_SAMPLES)))))
+        cap_b = max(1, int(os.environ.get("SDK_DIARIZE_PACK_LINKAGE_BYTES", str(DEFAULT_PACK_LINKAGE_BYTES))))
+        packs, cur, ns, nb = [], [], 0, 0
+        for i, x in enumerate(xs):
+            s_i, b_i = x.size + CHUNK, 8 * (N_LOCAL * n_chunks[i]) ** 2
+            if s_i > MAX_PACK_SAMPLES:
+                raise ValueError(f"diarize_many: recording {i}: {x.size} samples; a pack holds fewer than 2^31 with its gap")
+            if cur and (ns + s_i > cap_s or nb + b_i > cap_b):
+                packs.append(cur)
+                cur, ns, nb = [], 0, 0
+            cur.append(i)
+            ns, nb = ns + s_i, nb + b_i
+        if cur:
+            packs.append(cur)
+        out: List[Optional[DiarizationResult]] = [None] * len(xs)
+        self.last_sync = []
+        for idx in packs:
+            for i, res in zip(idx, self._run_pack([xs[i] for i in idx], None if logp is None else [logp[i] for i in idx], step_s, threshold,
+                                                  min_cluster_size, max_speakers, constrained, clustering, vbx)):
+                out[i] = res
+        return out
+
+    def _run_pack(self, xs, logps, step_s, threshold, min_cluster_size, max_speakers, constrained, clustering, vbx):
+        import torch
+        from .cluster import fcluster_distance, vbx_cluster
+        eng, dev = self.eng, self.eng.device
+        sync = {"downloads": 0, "uploads": 0}
+        self.last_sync.append(sync)
+        import time
+        stage_s, t_last = {}, [time.perf_counter()]
+        if getattr(self, "trace", False):
+            self.last_stage_s = getattr(self, "last_stage_s", [])
+            self.last_stage_s.append(stage_s)
+
+        def mark(name):                                         # self.trace = True: wall clock per stage, each ended by a device synchronisation
+            if getattr(self, "trace", False):
+                torch.cuda.synchronize()
+                now = time.perf_counter()
+                stage_s[name] = stage_s.get(name, 0.0) + now - t_last[0]
+                t_last[0] = now
+        pack = pack_recordings(xs, step_s)
+        R, d, F = len(xs), self.resnet.cfg.embed_dim, seg_frames(CHUNK)
+        co = pack.chunk_off
+        Cn = int(co[-1])
+        if Cn == 0:
+            return [self._empty() for _ in xs]
+
+        def up(a):
+            sync["uploads"] += 1
+            return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        if eng.precision != self.resnet.precision:
+            eng.set_precision(self.resnet.precision)            # the front end's output format follows the embedding's numerical contract
+        rec = up(pack.samples)
+        starts_dev = up(pack.starts_packed)
+        tab = GroupTables(eng, co, pack.frame_off, pack.n_samples, pack.starts_local)
+        sync["uploads"] += 2
+        lp_all = None
+        if logps is not None:
+            lp_all = torch.cat([torch.as_tensor(l, dtype=torch.float32).to(dev) for l, x in zip(logps, xs) if x.size])
+            sync["uploads"] += R
+        mark("pack_upload")
+        batch = max(1, int(os.environ.get("SDK_DIARIZE_BATCH", str(DEFAULT_BATCH))))
+        cls = torch.empty((Cn, F), dtype=torch.uint8, device=dev)
+        infos, embs = [], []
+        for a in range(0, Cn, batch):                           # the batches cross recording boundaries
+            c, i, e = self.embed_chunks(rec, int(rec.numel()), starts_dev[a:a + batch], None if lp_all is None else lp_all[a:a + batch])
+            cls[a:a + batch] = c
+            infos.append(i)
+            embs.append(e)
+        E_dev = torch.cat(embs)
+        info_dev = torch.cat(infos).contiguous()
+        info = info_dev.cpu().numpy()
+        sync["downloads"] += 1
+        mark("segmentation_embedding")
+        flat = info.reshape(-1, 4)
+        cand_ok = (flat[:, 3] != 0) & (flat[:, 0] > 0)
+        train_ok = (flat[:, 3] != 0) & (TRAIN_CLEAN_DEN * flat[:, 1].astype(np.int64) >= F)
+        rows, n_train = [], []                                   # per recording: the rows that make its centroids (global rows of E, ascending)
+        for r in range(R):
+            a, b = N_LOCAL * int(co[r]), N_LOCAL * int(co[r + 1])
+            tr = a + np.flatnonzero(train_ok[a:b])
+            n_train.append(len(tr))
+            rows.append(tr if len(tr) else a + np.flatnonzero(cand_ok[a:b]))      # no training row: one cluster of the candidates
+        vres = {}
+        if clustering == "vbx":
+            c32s, c64s, K_r = [], [], []
+            for r in range(R):
+                a = N_LOCAL * int(co[r])
+                if n_train[r] > 1:                              # recording by recording: its own linkage, cut and host reads
+                    v = vres[r] = vbx_cluster(eng, E_dev[a:N_LOCAL * int(co[r + 1])], self.plda_model(), threshold, rows=rows[r] - a, **vbx)
+                    c32s.append(v.cent)
+                    c64s.append(v.cent64)
+                    K_r.append(int(v.n_speakers))
+                    sync["downloads"] += 7
+                elif len(rows[r]):
+                    c32, c64 = diarize_centroids(eng, E_dev, up(rows[r].astype(np.int32)), torch.zeros(len(rows[r]), dtype=torch.int32, device=dev), 1,
+                                                 check_rows=False)
+                    c32s.append(c32)
+                    c64s.append(c64)
+                    K_r.append(1)
+                else:
+                    K_r.append(0)
+            cent_off = np.concatenate([[0], np.cumsum(K_r)]).astype(np.int64)
+            c32 = torch.cat(c32s).contiguous() if c32s else None
+            c64 = torch.cat(c64s).contiguous() if c64s else None
+        else:
+            link = [r for r in range(R) if n_train[r] > 1]
+            cuts = {}
+            if link:
+                off = np.concatenate([[0], np.cumsum([n_train[r] for r in link])]).astype(np.int64)
+                E_link = E_dev.index_select(0, up(np.concatenate([rows[r] for r in link]))).contiguous()
+                Z = eng.centroid_linkage(E_link, off).cpu().numpy()                # ONE launch for all recordings; reads status, then Z
+                sync["downloads"] += 2
+                mark("linkage")
+                for g, r in enumerate(link):
+                    cuts[r] = fcluster_distance(Z[int(off[g]) - g:int(off[g + 1]) - g - 1], threshold)
+            cut_all, sizes, cl_off, eff, cent_off = [], [], [0], [], [0]
+            for r in range(R):
+                n = len(rows[r])
+                cut = cuts[r] if r in cuts else np.zeros(n, np.int32)              # one training row, or the candidates: one cluster
+                sz = np.bincount(cut) if n else np.zeros(0, np.int64)
+                m = min(int(min_cluster_size), max(1, round(0.1 * n))) if r in cuts else 1     # cluster.fold_small_clusters, rule 1
+                cut_all.append(cut.astype(np.int64) + cl_off[-1])
+                sizes.append(sz)
+                eff.append(m)
+                cl_off.append(cl_off[-1] + len(sz))
+                cent_off.append(cent_off[-1] + (max(1, int((sz >= m).sum())) if len(sz) else 0))
+            cent_off = np.asarray(cent_off, np.int64)
+            c32 = c64 = None
+            if cl_off[-1]:
+                rows_d = up(np.concatenate(rows).astype(np.int32))
+                cut_d = up(np.concatenate(cut_all).astype(np.int32))
+                _, cut64 = diarize_centroids(eng, E_dev, rows_d, cut_d, cl_off[-1], check_rows=False)
+                _, final_d = diarize_fold_grouped(eng, cut64, np.concatenate(sizes), cl_off, eff, cent_off, cut_d)
+                sync["uploads"] += 1
+                c32, c64 = diarize_centroids(eng, E_dev, rows_d, final_d, int(cent_off[-1]), check_rows=False)
+        tab.set_clusters(cent_off)
+        sync["uploads"] += 1
+        mark("cut_fold_centroids")
+        if c64 is None:                                          # no cluster anywhere: the kernels still get a row to point at
+            c32, c64 = torch.zeros((1, d), dtype=torch.float32, device=dev), torch.zeros((1, d), dtype=torch.float64, device=dev)
+        lab_dev, score_dev = diarize_assign_grouped(eng, E_dev, info_dev, c64, tab, bool(constrained))
+        _, spk_dev, _ = diarize_reconstruct_grouped(eng, cls, lab_dev, tab, max_speakers)
+        first = diarize_first_seen(eng, spk_dev, tab)
+        _, c32, c64 = diarize_renumber(eng, first, lab_dev, c32, c64, tab)         # ties in the top-2 go to the lower number: stitch again
+        cnt_dev, spk_dev, _ = diarize_reconstruct_grouped(eng, cls, lab_dev, tab, max_speakers)
+        labels, scores, cent = lab_dev.cpu().numpy(), score_dev.cpu().numpy(), c32.cpu().numpy()
+        count, speakers = cnt_dev.cpu().numpy(), spk_dev.cpu().numpy()
+        sync["downloads"] += 5
+        mark("assign_stitch_download")
+        out = []
+        for r in range(R):
+            if xs[r].size == 0:
+                out.append(self._empty())
+                continue
+            a, b, g0, g1, k0, k1 = (int(v) for v in (co[r], co[r + 1], pack.frame_off[r], pack.frame_off[r + 1], cent_off[r], cent_off[r + 1]))
+            res = DiarizationResult(turns_from_frames(speakers[g0:g1], k1 - k0), k1 - k0, cent[k0:k1].copy(), labels[a:b].copy(), count[g0:g1].copy(),
+                                    speakers[g0:g1].copy(), pack.starts_local[a:b].astype(np.int64), info[a:b].copy(), cls[a:b], scores[a:b].copy())
+            if r in vres:
+                res.pi, res.elbo = vres[r].pi, vres[r].elbo
+            out.append(res)
+        mark("turns")
+        return out
