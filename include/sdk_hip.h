@@ -39,6 +39,7 @@
  *     sdk_diarize_assign_grouped  sdk_diarize_fold_grouped  sdk_diarize_reconstruct_grouped  sdk_diarize_first_seen  sdk_diarize_renumber
  *                                                                                                       speaker diarization (diarize.py)
  *     sdk_plda_transform  sdk_vbx_workspace_bytes  sdk_vbx  sdk_vbx_centroids                           VBx clustering (plda.py, cluster.vbx_cluster)
+ *     sdk_cohort_stats_workspace_bytes  sdk_cohort_stats  sdk_affinity_topk_snorm                       adaptive score normalisation (snorm.py)
  * BUILDING BLOCKS AND KNOBS - exported for the parity tests and the A/B tools, free to change between rounds, not for binding:
  *     sdk_conv_gemm*  sdk_colstats_finish  sdk_res2net_chain*  sdk_se_*  sdk_asp_*  sdk_rows_fc  (pieces of sdk_ecapa_forward)
  *     sdk_resnet_conv2d  (piece of sdk_resnet_forward)  sdk_resnet_masked_pool  (piece of sdk_resnet_forward_masked)
@@ -58,7 +59,7 @@
 extern "C" {
 #endif
 
-#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5) */
+#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5); still 4 with sdk_cohort_stats* and sdk_affinity_topk_snorm: new exports only, no caller of version 4 breaks */
 
 typedef struct sdk_ctx sdk_ctx;
 
@@ -585,6 +586,27 @@ int sdk_vbx(sdk_ctx* ctx, const double* X, const double* Phi, const int32_t* lab
             size_t ws_bytes, void* stream);
 int sdk_vbx_centroids(sdk_ctx* ctx, const double* gamma, const double* pi, const float* E, const int32_t* rows, int n, int S, int d, int32_t* K,
                       int32_t* keep, int32_t* labels, float* cent, double* cent64, void* stream);
+
+/* ---- adaptive score normalisation against a cohort (AS-norm; snorm.py, csrc/snorm.hip).  E [N][d], P [Pn][d] and Cn [M][d] are unit fp32 rows,
+ *      16-byte aligned; d a multiple of 64, at most 512.  Scores are fp32 dot products on the fp32-input MFMA: one fused-multiply-add chain over
+ *      the d columns in one fixed order, so a score depends on its two rows only (not on N, M, Pn or its place in them).  No floating-point
+ *      atomics: bit-identical run to run.
+ *   sdk_cohort_stats : of the M scores <e_n, c_j> of row n take the K largest (a multiset: equal scores need no tie rule), 1 <= K <= M <= 2^20;
+ *        mean [N] = their mean, std [N] = their population standard deviation (divide by K), floored at 1e-6; both accumulated in float64 in
+ *        a fixed order.  A non-finite row gives NaN statistics.  N = 0 is a no-op.  The rows are taken in row blocks whose [rows][M] fp32 score
+ *        block is the workspace: sdk_cohort_stats_workspace_bytes (host-only; bounded in N; 0 with sdk_last_error set for arguments the call
+ *        refuses), 16-byte aligned.
+ *   sdk_affinity_topk_snorm : z(n, p) = ((s - mean_e[n]) / std_e[n] + (s - mean_p[p]) / std_p[p]) / 2 with s = <e_n, p_p> (formed in float64
+ *        from the fp32 s and statistics, rounded once); per window the k <= 4 largest z, ties to the lower profile, a NaN z never taken ->
+ *        idx [N][k] int32, score [N][k] (z), raw [N][k] (s).  Slots left without a finite candidate hold idx -1, score 0, raw 0.  Pn >= 1; when
+ *        k > Pn the columns Pn .. k - 1 are NOT written.
+ *   Shape refusals (d, M, K, k) come before anything else, the null context included.
+ *   sdk_set_option "snorm_scores_only" 1 (bench knob, tools/snorm_bench.py): sdk_cohort_stats runs its scoring kernel only (mean, std not written). */
+size_t sdk_cohort_stats_workspace_bytes(int N, int M, int K);
+int sdk_cohort_stats(sdk_ctx* ctx, const float* E, int N, const float* Cn, int M, int d, int K, float* mean, float* std, void* ws,
+                     size_t ws_bytes, void* stream);
+int sdk_affinity_topk_snorm(sdk_ctx* ctx, const float* E, const float* mean_e, const float* std_e, int N, const float* P, const float* mean_p,
+                            const float* std_p, int Pn, int d, int k, int32_t* idx, float* score, float* raw, void* stream);
 
 /* ---- audio conversion to the AudioProfile: replaces the ffmpeg subprocess the reference's backends
  *      run before upload (audio_profiles.py:70-100 `format_ffmpeg_args`; speechmatics_backend.py:231-281).

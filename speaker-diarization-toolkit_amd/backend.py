@@ -34,6 +34,12 @@ Environment:
                       ~3.6x the step time) / 2 (one fp16 plane: the default mode's kernels with fp16 storage and operands, within ~1e-4 with the
                       bias correction, ~1.04x the step time; both families).  All modes embed into the SAME space (they differ from each other at
                       the 4e-3 level), so model_version does not depend on it
+  SDK_COHORT          a .npy [M, d] fp32 impostor cohort (Backend.make_cohort writes one): identify_speaker, identify_many, verify_speaker and
+                      score_ranges then decide on the adaptively normalised score z (AS-norm, snorm.py) instead of the raw cosine.  Needs the
+                      torch engine (SDK_NO_TORCH=1 is refused) and SDK_COHORT_THRESHOLD
+  SDK_COHORT_TOPK     cohort scores per side that the statistics are taken over (default 300; min(K, M) is used)
+  SDK_COHORT_THRESHOLD  the vote threshold on the z scale (a float).  No default: it depends on the model family and the cohort, and no trained
+                      weights are on hand to tune one - a cohort without a threshold is refused
 """
 from __future__ import annotations
 
@@ -67,6 +73,27 @@ class Backend(EmbeddingBackend):
         self._digest: Optional[str] = None
         self.window_s = float(os.environ.get("SDK_WINDOW_S", "2.0"))
         self.hop_s = float(os.environ.get("SDK_HOP_S", "1.0"))
+        # adaptive score normalisation (snorm.py): off unless a cohort is configured
+        self.cohort_path = os.environ.get("SDK_COHORT") or None
+        self.cohort_topk = int(os.environ.get("SDK_COHORT_TOPK", "300"))
+        thr = os.environ.get("SDK_COHORT_THRESHOLD")
+        self.cohort_threshold: Optional[float] = None
+        self._cohort = None
+        if bool(self.cohort_path) != bool(thr):
+            raise ValueError("SDK_COHORT (the cohort file) and SDK_COHORT_THRESHOLD (the vote threshold on the normalised scale) go together: "
+                             f"{'SDK_COHORT_THRESHOLD' if self.cohort_path else 'SDK_COHORT'} is not set.  There is no default threshold: it depends on "
+                             "the model family and the cohort")
+        if self.cohort_path:
+            try:
+                self.cohort_threshold = float(thr)
+            except ValueError:
+                raise ValueError(f"SDK_COHORT_THRESHOLD={thr!r}: a float on the normalised (z) scale expected") from None
+            if self.cohort_threshold != self.cohort_threshold:
+                raise ValueError("SDK_COHORT_THRESHOLD is NaN: a float on the normalised (z) scale expected")
+            if self.cohort_topk < 1:
+                raise ValueError(f"SDK_COHORT_TOPK={self.cohort_topk}: at least 1")
+            if os.environ.get("SDK_NO_TORCH") == "1":
+                raise ValueError("SDK_COHORT with SDK_NO_TORCH=1: the normalised path needs the torch engine; unset SDK_NO_TORCH (or SDK_COHORT)")
 
     # ---- metadata (base.py:25-105) -------------------------------------------------------
     @property
@@ -326,11 +353,15 @@ class Backend(EmbeddingBackend):
 
     def score_ranges(self, samples: np.ndarray, ranges: List[Tuple[float, float]], batch, k: int = 1):
         """Single-speaker ranges -> per window (best profile rows [W, k], scores [W, k]) on the host + windows [(range index, start s, end s)]:
-        embed_ranges + score_windows in one call, on either host path (torch engine or SDK_NO_TORCH=1)."""
+        embed_ranges + score_windows in one call, on either host path (torch engine or SDK_NO_TORCH=1).  With a cohort configured (SDK_COHORT)
+        the rows are the normalised top-k and the scores are z values (score_windows_snorm), not cosines."""
         if not self.lite:
             E, Eb, re, wins, _ = self.embed_ranges(samples, ranges)
             if not wins:
                 return np.zeros((0, k), np.int32), np.zeros((0, k), np.float32), []
+            if self.cohort_path:
+                idx, z, _ = self.score_windows_snorm(E, batch, k)
+                return idx, z, wins
             idx, sc = self.score_windows(E, Eb, re, batch, k)
             return idx, sc, wins
         starts_by, wins, _ = range_starts(len(samples), ranges, hop_s=self.hop_s)
@@ -474,7 +505,8 @@ class Backend(EmbeddingBackend):
                 dz.eng.set_precision(prec)                       # the front end's format goes back to the selected family's contract
 
     # ---- a2: enroll (base.py:107-128) ---------------------------------------------------------
-    def enroll_speaker(self, audio_path: Path, segments: Optional[List[Tuple[float, float]]] = None) -> Dict[str, Any]:
+    def _enroll_vector(self, audio_path: Path, segments: Optional[List[Tuple[float, float]]] = None):
+        """The unit mean embedding of a recording's windows (what enroll_speaker stores) and the windows' spans."""
         if segments:           # the caller vouches that each range is this speaker: true-length windows, never widened
             samples = decode_to_profile(Path(audio_path), self.engine(), self.get_audio_profile())
             if self.lite:
@@ -495,6 +527,10 @@ class Backend(EmbeddingBackend):
         else:
             mean = E.double().mean(dim=0)
             vec = (mean / mean.norm().clamp_min(1e-12)).float().cpu().numpy()
+        return vec, spans
+
+    def enroll_speaker(self, audio_path: Path, segments: Optional[List[Tuple[float, float]]] = None) -> Dict[str, Any]:
+        vec, spans = self._enroll_vector(audio_path, segments)
         ext = save_vector(vec, meta=self.numerics())
         return {
             "external_id": ext,                      # the only backend field cmd_enroll persists (speaker_detection:890-904)
@@ -529,6 +565,51 @@ class Backend(EmbeddingBackend):
         batch._dev = (eng, out)
         return out
 
+    # ---- adaptive score normalisation (snorm.py) ---------------------------------------------------
+    def make_cohort(self, audio_paths: List[Path], out_path: Path) -> Dict[str, Any]:
+        """One row per recording - the unit mean embedding enroll_speaker would store for it - written as a [M, d] fp32 .npy: the file
+        SDK_COHORT names.  The recordings should be speakers that are NOT among the enrolled ones (impostors)."""
+        rows = [self._enroll_vector(Path(p), None)[0] for p in audio_paths]
+        if not rows:
+            raise ValueError("make_cohort: no recordings")
+        mat = np.ascontiguousarray(np.stack(rows), dtype=np.float32)
+        out_path = Path(out_path)
+        with open(out_path, "wb") as f:                 # an open file: np.save appends no suffix of its own
+            np.save(f, mat, allow_pickle=False)
+        return {"file": str(out_path), "n_recordings": int(mat.shape[0]), "embedding_dim": int(mat.shape[1]), "model_version": self.model_version}
+
+    def cohort(self):
+        """The configured snorm.Cohort (None without SDK_COHORT), loaded on first use."""
+        if self.cohort_path and self._cohort is None:
+            from .snorm import Cohort
+            self._cohort = Cohort.load(self.cohort_path, self.embedding_dim)
+        return self._cohort
+
+    def profile_stats(self, batch):
+        """(mean_p, std_p) device tensors: the cohort statistics of a ProfileBatch's rows, computed once per batch object and cached on it
+        beside its device copies, keyed by the cohort's digest and K."""
+        eng, co = self.engine(), self.cohort()
+        K = min(self.cohort_topk, len(co))
+        got = getattr(batch, "_snorm", None)
+        if got is not None and got[0] is eng and got[1] == (co.digest, K):
+            return got[2]
+        out = eng.cohort_stats(self.profile_tensors(batch)[0], co.device_rows(eng), K)
+        batch._snorm = (eng, (co.digest, K), out)
+        return out
+
+    def _snorm_enqueue(self, E, batch, k: int = 1):
+        """Normalised top-k of embedded windows against a ProfileBatch -> (idx, z, raw) device tensors; nothing waits."""
+        eng, co = self.engine(), self.cohort()
+        mean_p, std_p = self.profile_stats(batch)
+        mean_e, std_e = eng.cohort_stats(E, co.device_rows(eng), min(self.cohort_topk, len(co)))
+        return eng.affinity_topk_snorm(E, mean_e, std_e, self.profile_tensors(batch)[0], mean_p, std_p, k=max(1, min(k, len(batch), 4)))
+
+    def score_windows_snorm(self, E, batch, k: int = 1):
+        """score_windows on the normalised scale -> (idx, z, raw) on the host; needs a configured cohort."""
+        if self.cohort() is None:
+            raise ValueError("score_windows_snorm: no cohort configured (SDK_COHORT)")
+        return tuple(t.cpu().numpy() for t in self._snorm_enqueue(E, batch, k))
+
     def score_windows(self, E, Eb, re, batch, k: int = 1):
         """Device scoring of embedded windows against a ProfileBatch -> (idx, score) on host."""
         eng = self.engine()
@@ -553,10 +634,16 @@ class Backend(EmbeddingBackend):
         return batch
 
     def identify_speaker(self, audio_path: Path, candidates: List[Dict[str, Any]], threshold: float = 0.354) -> List[Dict[str, Any]]:
+        """With a cohort configured (SDK_COHORT) a window's winner is its normalised top-1 and it votes when z >= SDK_COHORT_THRESHOLD: the raw
+        `threshold` is NOT applied.  The rows then carry norm_score and are sorted by it (aggregate_matches_snorm)."""
         batch = self._load_candidates(candidates)
         if len(batch) == 0:
             return []
         samples, starts, W, spans = self._windows(audio_path, None)
+        if self.cohort_path:
+            E, _, _ = self.embed_tables(samples, {W: starts})[W]
+            idx, z, raw = self.score_windows_snorm(E, batch)
+            return aggregate_matches_snorm(idx[:, 0], z[:, 0], raw[:, 0], spans, batch, self.cohort_threshold)
         if self.lite:
             _, idx, sc = self.embed_tables_host(samples, {W: starts}, batch)[W]
         else:
@@ -569,10 +656,19 @@ class Backend(EmbeddingBackend):
         recording per call, base.py:130-151, and gets its concurrency from up to four CLI processes, speaker-process:627-629).  The profiles are
         loaded and uploaded once; every recording is decoded, handed to the staging slots and its kernels enqueued WITHOUT waiting for the previous
         one - the upload of recording i + 1 runs under the forward pass of recording i (csrc/ingest.hip) - and the host synchronises once, at the end.
-        Row lists equal identify_speaker's, recording by recording (tests/test_gpu_ingest.py)."""
+        Row lists equal identify_speaker's, recording by recording (tests/test_gpu_ingest.py).  With a cohort configured (SDK_COHORT) the
+        decision is identify_speaker's normalised one and the raw `threshold` is NOT applied."""
         batch = self._load_candidates(candidates)
         if len(batch) == 0:
             return [[] for _ in audio_paths]
+        if self.cohort_path:
+            pending = []
+            for path in audio_paths:
+                samples, starts, W, spans = self._windows(path, None)
+                E, _, _ = self.embed_tables(samples, {W: starts})[W]
+                pending.append((self._snorm_enqueue(E, batch), spans))               # enqueued; nothing waits here
+            return [aggregate_matches_snorm(i.cpu().numpy()[:, 0], z.cpu().numpy()[:, 0], r.cpu().numpy()[:, 0], spans, batch, self.cohort_threshold)
+                    for (i, z, r), spans in pending]
         if self.lite:                       # the torch-free path downloads per recording (everything on the null stream): sequential
             out = []
             for path in audio_paths:
@@ -592,11 +688,16 @@ class Backend(EmbeddingBackend):
 
     # ---- a3: verify - the CLI reads result['confidence'] (speaker_detection:1173-1174) ---------
     def verify_speaker(self, audio_path: Path, speaker_profile: Dict[str, Any], threshold: float = 0.354) -> Dict[str, Any]:
+        """With a cohort configured (SDK_COHORT) the match is identify_speaker's normalised decision (the raw `threshold` is NOT applied) and
+        the result carries norm_score; similarity and confidence stay the mean raw cosine."""
         hits = self.identify_speaker(audio_path, [speaker_profile], threshold)
         if not hits:
             return {"match": False, "similarity": 0.0, "confidence": 0.0, "embedding_id": None}
         h = hits[0]
-        return {"match": True, "similarity": h["similarity"], "confidence": h["similarity"], "embedding_id": h.get("embedding_id")}
+        out = {"match": True, "similarity": h["similarity"], "confidence": h["similarity"], "embedding_id": h.get("embedding_id")}
+        if "norm_score" in h:
+            out["norm_score"] = h["norm_score"]
+        return out
 
 
 def aggregate_matches(best_idx: np.ndarray, best_score: np.ndarray, spans, batch, threshold: float) -> List[Dict[str, Any]]:
@@ -620,4 +721,28 @@ def aggregate_matches(best_idx: np.ndarray, best_score: np.ndarray, spans, batch
         out.append({"speaker_id": sid, "similarity": sim, "confidence": sim, "embedding_id": batch.embedding_ids[win_row],
                     "segment": (acc["first"], acc["last"]), "n_segments": len(acc["scores"])})
     out.sort(key=lambda r: (-r["similarity"], r["speaker_id"]))
+    return out
+
+
+def aggregate_matches_snorm(best_idx: np.ndarray, best_z: np.ndarray, best_raw: np.ndarray, spans, batch, z_threshold: float) -> List[Dict[str, Any]]:
+    """aggregate_matches for the normalised path (snorm.py): a window votes for the speaker owning its normalised top-1 row when its z clears
+    `z_threshold` (no raw threshold applies).  similarity = confidence = float64 mean of the RAW cosines of the speaker's voting windows (so
+    combine_signals keeps its [-1, 1] input); norm_score = float64 mean of their z.  Rows sorted by norm_score descending, then speaker id."""
+    per: Dict[str, Dict[str, Any]] = {}
+    for w, (row, z, s) in enumerate(zip(best_idx.tolist(), best_z.tolist(), best_raw.tolist())):
+        if row < 0 or not z >= z_threshold:
+            continue
+        sid = batch.speaker_ids[row]
+        acc = per.setdefault(sid, {"z": [], "raw": [], "rows": {}, "first": spans[w][0], "last": spans[w][1]})
+        acc["z"].append(float(z))
+        acc["raw"].append(float(s))
+        acc["rows"][row] = acc["rows"].get(row, 0) + 1
+        acc["last"] = spans[w][1]
+    out = []
+    for sid, acc in per.items():
+        win_row = max(acc["rows"].items(), key=lambda kv: (kv[1], -kv[0]))[0]
+        sim = float(np.mean(np.asarray(acc["raw"], dtype=np.float64)))
+        out.append({"speaker_id": sid, "similarity": sim, "confidence": sim, "norm_score": float(np.mean(np.asarray(acc["z"], dtype=np.float64))),
+                    "embedding_id": batch.embedding_ids[win_row], "segment": (acc["first"], acc["last"]), "n_segments": len(acc["z"])})
+    out.sort(key=lambda r: (-r["norm_score"], r["speaker_id"]))
     return out

@@ -388,6 +388,73 @@ class Engine:
                                          ws.data_ptr(), ws.numel(), _stream()), "sdk_affinity_topk")
         return (idx, sc, cnt) if want_count else (idx, sc)
 
+    # ------------------------------------------------------------------ adaptive score normalisation (snorm.py)
+    @staticmethod
+    def _snorm_rows(name: str, what: str, t, d: Optional[int] = None) -> Tuple[int, int]:
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"{name}: {what} must be a contiguous fp32 [rows, d] device tensor, got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__} {getattr(t, 'dtype', '')}")
+        n, dd = int(t.shape[0]), int(t.shape[1])
+        if dd < 64 or dd > 512 or dd % 64:
+            raise ValueError(f"{name}: d={dd} not supported (a multiple of 64, at most 512)")
+        if d is not None and dd != d:
+            raise ValueError(f"{name}: {what} has d={dd}, expected {d}")
+        return n, dd
+
+    @staticmethod
+    def _snorm_vec(name: str, what: str, t, n: int) -> None:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (n,) or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"{name}: {what} must be a contiguous fp32 [{n}] device tensor, got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__} {getattr(t, 'dtype', '')}")
+
+    def cohort_stats(self, E: torch.Tensor, cohort: torch.Tensor, K: int, ws: Optional[torch.Tensor] = None):
+        """Unit fp32 rows E [N, d] and cohort [M, d] (device) -> (mean [N], std [N]) fp32 of every row's K largest cohort cosines: the mean and
+        the population standard deviation, floored at snorm.STD_FLOOR (sdk_cohort_stats).  ws: a uint8 device tensor to use as the workspace
+        (default: one of sdk_cohort_stats_workspace_bytes(N, M, K) bytes is allocated)."""
+        N, d = self._snorm_rows("cohort_stats", "E", E)
+        M, _ = self._snorm_rows("cohort_stats", "the cohort", cohort, d)
+        K = int(K)
+        if M < 1 or M > (1 << 20):
+            raise ValueError(f"cohort_stats: M={M} cohort rows (1 .. 2^20)")
+        if K < 1 or K > M:
+            raise ValueError(f"cohort_stats: K={K} (1 .. M={M})")
+        nbytes = int(self.lib.sdk_cohort_stats_workspace_bytes(N, M, K))
+        if nbytes == 0:
+            raise SdkError(f"sdk_cohort_stats_workspace_bytes: {self.lib.sdk_last_error().decode()}")
+        if ws is None:
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=E.device)
+        elif ws.dtype != torch.uint8 or ws.dim() != 1 or not ws.is_cuda or not ws.is_contiguous():
+            raise ValueError(f"cohort_stats: ws must be a contiguous uint8 device tensor, got {tuple(ws.shape)} {ws.dtype}")
+        mean = torch.empty((N,), dtype=torch.float32, device=E.device)
+        std = torch.empty((N,), dtype=torch.float32, device=E.device)
+        check(self.lib.sdk_cohort_stats(self.ctx, E.data_ptr(), N, cohort.data_ptr(), M, d, K, mean.data_ptr(), std.data_ptr(), ws.data_ptr(),
+                                        ws.numel(), _stream()), "sdk_cohort_stats")
+        return mean, std
+
+    def affinity_topk_snorm(self, E: torch.Tensor, mean_e: torch.Tensor, std_e: torch.Tensor, P: torch.Tensor, mean_p: torch.Tensor,
+                            std_p: torch.Tensor, k: int = 1):
+        """Unit fp32 rows E [N, d] and P [Pn, d] with their cohort statistics (cohort_stats) -> (idx [N, k] int32, score [N, k] fp32,
+        raw [N, k] fp32): per window the k <= min(4, Pn) largest z = ((s - mean_e) / std_e + (s - mean_p) / std_p) / 2, s the cosine; ties to
+        the lower profile; raw is s.  A slot without a finite z holds (-1, 0, 0) (sdk_affinity_topk_snorm)."""
+        N, d = self._snorm_rows("affinity_topk_snorm", "E", E)
+        Pn, _ = self._snorm_rows("affinity_topk_snorm", "P", P, d)
+        self._snorm_vec("affinity_topk_snorm", "mean_e", mean_e, N)
+        self._snorm_vec("affinity_topk_snorm", "std_e", std_e, N)
+        self._snorm_vec("affinity_topk_snorm", "mean_p", mean_p, Pn)
+        self._snorm_vec("affinity_topk_snorm", "std_p", std_p, Pn)
+        k = int(k)
+        if k < 1 or k > 4:
+            raise ValueError(f"affinity_topk_snorm: k={k} (1 .. 4)")
+        if Pn < 1 or k > Pn:
+            raise ValueError(f"affinity_topk_snorm: k={k} with Pn={Pn} profiles (the caller clamps k to the number of profiles, at least 1)")
+        idx = torch.empty((N, k), dtype=torch.int32, device=E.device)
+        sc = torch.empty((N, k), dtype=torch.float32, device=E.device)
+        raw = torch.empty((N, k), dtype=torch.float32, device=E.device)
+        check(self.lib.sdk_affinity_topk_snorm(self.ctx, E.data_ptr(), mean_e.data_ptr(), std_e.data_ptr(), N, P.data_ptr(), mean_p.data_ptr(),
+                                               std_p.data_ptr(), Pn, d, k, idx.data_ptr(), sc.data_ptr(), raw.data_ptr(), _stream()),
+              "sdk_affinity_topk_snorm")
+        return idx, sc, raw
+
     # ------------------------------------------------------------------ whole path
     def embed_pcm(self, pcm: torch.Tensor):
         """pcm [B, S] int16 on device -> (E, Eb, resid) L2-normalised embeddings."""
