@@ -57,6 +57,11 @@ class _Comm:
 
 def canonical_labels(lab: np.ndarray) -> np.ndarray:
     lab = np.asarray(lab)
+    if lab.size and int(lab.min()) < 0:
+        # Engine.kmeans_assign labels a row -1 when its distance to every centre is NaN; remap[-1] would quietly give it the last cluster
+        row = int(np.flatnonzero(lab < 0)[0])
+        raise ValueError(f"canonical_labels: row {row} has label {int(lab[row])} ({int((lab < 0).sum())} negative in all): k-means labels a row "
+                         "-1 when it holds a NaN")
     _, first = np.unique(lab, return_index=True)
     remap = np.full(int(lab.max()) + 1, -1, dtype=np.int32)
     for new, old in enumerate(lab[np.sort(first)]):
@@ -169,7 +174,8 @@ def _orth(provider, comm: _Comm, Y: torch.Tensor, k: int, spd_flag: Optional[tor
 
 def _kmeans(provider, comm: _Comm, R: torch.Tensor, lo: int, n_total: int, k: int, n_iter: int) -> torch.Tensor:
     """Maximin initialisation + Lloyd, row-sharded.  Device-side selection throughout (no .item(), no host comparison): at 8 GPUs
-    every host round trip would also be a collective everyone waits in."""
+    every host round trip would also be a collective everyone waits in.  A row that holds a NaN comes back with label -1
+    (Engine.kmeans_assign); nothing here reads the labels on the host, so it is canonical_labels, at the caller's download, that refuses it."""
     dev = R.device
     n_loc = R.shape[0]
     kdim = R.shape[1]

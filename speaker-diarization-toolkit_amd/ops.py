@@ -48,6 +48,37 @@ def _need(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
     return t
 
 
+THIN_MAX = 32      # KV of csrc/spectral.hip: the widest [n, k] block (and the most centres) the thin helpers take
+
+
+def _thin(t, name: str, what: str, shape=None, dtype=torch.float32, contiguous: bool = True) -> torch.Tensor:
+    """An argument of a thin [n, k] helper (rows_gram ... kmeans_assign), which the kernels read through a bare pointer as a contiguous
+    array of `dtype`: anything else is refused here, before any launch, with a ValueError that names the argument.  shape: the exact
+    shape it must have (None = not checked); contiguous=False where the caller passes t.contiguous() on."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{what}: {name} must be a torch.Tensor, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise ValueError(f"{what}: {name} must live in device memory (got {t.device}); there is no CPU path")
+    if t.dtype != dtype:
+        raise ValueError(f"{what}: {name} must be {dtype}, got {t.dtype}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: {name} must have shape {list(shape)}, got {list(t.shape)}")
+    if contiguous and not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be contiguous, got shape {list(t.shape)} with strides {list(t.stride())} (pass {name}.contiguous())")
+    return t
+
+
+def _thin_rows(X, name: str, what: str):
+    """The [n, k] row block of a thin helper: 2-D, n >= 1, 1 <= k <= THIN_MAX, fp32, contiguous -> (n, k)."""
+    _thin(X, name, what, contiguous=False)
+    if X.dim() != 2 or X.shape[0] < 1:
+        raise ValueError(f"{what}: {name} must be [n, k] with n >= 1, got {list(X.shape)}")
+    if not 1 <= X.shape[1] <= THIN_MAX:
+        raise ValueError(f"{what}: k = {X.shape[1]} (the width of {name}) must be in 1..{THIN_MAX}")
+    _thin(X, name, what)
+    return int(X.shape[0]), int(X.shape[1])
+
+
 def num_frames(n_samples: int) -> int:
     return 1 + n_samples // HOP
 
@@ -666,14 +697,20 @@ class Engine:
         return V, lam
 
     def rows_gram(self, X, Y):
-        n, k = X.shape
+        """G [k, k] = X^T Y over the n rows of two contiguous fp32 [n, k] blocks (k <= 32)."""
+        n, k = _thin_rows(X, "X", "rows_gram")
+        _thin(Y, "Y", "rows_gram", shape=(n, k))
         G = torch.empty((k, k), dtype=torch.float32, device=self.device)
         ws = self._scratch_bytes("gram", self.lib.sdk_rows_gram_workspace_bytes(n, k))
         check(self.lib.sdk_rows_gram(self.ctx, X.data_ptr(), Y.data_ptr(), n, k, G.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "sdk_rows_gram")
         return G
 
     def rows_apply(self, X, R, scale=None):
-        n, k = X.shape
+        """Y[i, :] = scale[i] * (X[i, :] @ R): X contiguous fp32 [n, k], R fp32 [k, k], scale fp32 [n] or None."""
+        n, k = _thin_rows(X, "X", "rows_apply")
+        _thin(R, "R", "rows_apply", shape=(k, k), contiguous=False)
+        if scale is not None:
+            _thin(scale, "scale", "rows_apply", shape=(n,))
         Y = torch.empty_like(X)
         check(self.lib.sdk_rows_apply(self.ctx, X.data_ptr(), R.contiguous().data_ptr(), _ptr(scale), n, k, Y.data_ptr(), _stream()), "sdk_rows_apply")
         return Y
@@ -690,19 +727,35 @@ class Engine:
         return Rinv
 
     def rows_unit(self, X):
-        n, k = X.shape
+        """The rows of a contiguous fp32 [n, k] block scaled to unit length (a row shorter than 1e-12 is divided by 1e-12: a zero row stays zero)."""
+        n, k = _thin_rows(X, "X", "rows_unit")
         Y = torch.empty_like(X)
         check(self.lib.sdk_rows_unit(self.ctx, X.data_ptr(), n, k, Y.data_ptr(), _stream()), "sdk_rows_unit")
         return Y
 
     def kmeans_mindist(self, R, centre, d2, first: bool):
-        n, k = R.shape
+        """d2[i] = |R[i] - centre|^2 (first) or min(d2[i], that), in place: R contiguous fp32 [n, k], centre fp32 [k], d2 contiguous fp32 [n]."""
+        n, k = _thin_rows(R, "R", "kmeans_mindist")
+        _thin(centre, "centre", "kmeans_mindist", shape=(k,), contiguous=False)
+        _thin(d2, "d2", "kmeans_mindist", shape=(n,))
         check(self.lib.sdk_kmeans_mindist(self.ctx, R.data_ptr(), n, k, centre.contiguous().data_ptr(), d2.data_ptr(), int(first), _stream()), "sdk_kmeans_mindist")
         return d2
 
     def kmeans_assign(self, R, centres, want_sums: bool = True):
-        n, k = R.shape
-        kc = centres.shape[0]
+        """One k-means step on the contiguous fp32 rows R [n, k] against centres fp32 [kc, k] (k, kc <= 32) ->
+        (label int32 [n], dist2 fp32 [n], part_sum fp32 [ceil(n / 256), kc, k], part_cnt int32 [ceil(n / 256), kc]); the last two are None
+        without want_sums.  label is the nearest centre, ties to the lowest index; part_sum / part_cnt are the sums and counts of each
+        block of 256 rows per label, added in ascending row order (reproducible).
+        A row that holds a NaN (or whose distance to every centre is NaN, as with NaN centres) compares below nothing: it gets label -1 and
+        dist2 +inf and enters no sum and no count; the other rows of its block are not affected.  cluster.canonical_labels refuses a
+        negative label."""
+        n, k = _thin_rows(R, "R", "kmeans_assign")
+        _thin(centres, "centres", "kmeans_assign", contiguous=False)
+        if centres.dim() != 2 or centres.shape[1] != k:
+            raise ValueError(f"kmeans_assign: centres must be [kc, k] with k = {k} (the width of R), got {list(centres.shape)}")
+        kc = int(centres.shape[0])
+        if not 1 <= kc <= THIN_MAX:
+            raise ValueError(f"kmeans_assign: kc = {kc} (the rows of centres) must be in 1..{THIN_MAX}")
         lab = torch.empty((n,), dtype=torch.int32, device=self.device)
         d2 = torch.empty((n,), dtype=torch.float32, device=self.device)
         nb = (n + 255) // 256
