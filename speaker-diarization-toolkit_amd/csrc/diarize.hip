@@ -558,10 +558,7 @@ extern "C" int sdk_diarize_masks(sdk_ctx* ctx, const uint8_t* cls, int B, int F,
   return 0;
 }
 
-extern "C" int64_t sdk_diarize_frames(int64_t n_samples) {
-  const int64_t g = (n_samples - 495 + DZ_HOP - 1) / DZ_HOP;
-  return n_samples < 495 || g < 0 ? 0 : g;
-}
+extern "C" int64_t sdk_diarize_frames(int64_t n_samples) { return dz_frames(n_samples); }
 
 extern "C" int sdk_diarize_reconstruct(sdk_ctx* ctx, const uint8_t* cls, const int32_t* starts, const int32_t* labels, int C, int F, int K,
                                        int64_t n_samples, int max_speakers, uint8_t* count, int32_t* speakers, int32_t* act, void* stream) {

@@ -45,6 +45,14 @@ tests pin these rules.
               renumbering by appearance in grouped kernels (sdk_diarize_*_grouped, sdk_diarize_first_seen, sdk_diarize_renumber) that find
               a chunk's, frame's or cluster's recording by binary search on prefix-sum tables.  The embeddings never leave the device and
               the host waits for the device a fixed number of times per pack.
+  shared      run and run_many are one pipeline: Diarizer._check_options, _check_recording, _embed_all (the batches of embed_chunks) and
+              _empty serve both, as do candidate_mask, training_mask and _speaker_cap; after the embedding run clusters one recording and
+              run_many takes the pack through _pack_rows, _pack_vbx or _pack_ahc, _pack_assign and _pack_results.  They differ on purpose in
+              two places, both for "ahc": run(constrained=False) assigns on the host (assign_rows, a BLAS product, no scores) and run folds
+              small clusters on the host (cluster.agglomerative_cluster, a BLAS product), where run_many's grouped kernels sum every cosine
+              in column order in float64 (every result carries scores).  So with constrained=True run_many's cls, info, labels, count,
+              speakers, turns, n_speakers and starts equal run's, and with constrained=False too unless a decision is a tie or near-tie at
+              float64 rounding; centroids agree to fp32 rounding of the same float64 rows.
 
 Decode, masks, the constrained assignment and stitching run in libsdk_hip.so (csrc/diarize.hip), the pooling in csrc/resnet.hip; the *_host
 functions below restate them in numpy for hosts that post-process stored class tables.  The host receives info, the unit embeddings (not
@@ -52,8 +60,8 @@ with constrained=True: then labels, scores and centroids instead), and count / s
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
+import time
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
@@ -123,7 +131,7 @@ def reconstruct_host(cls: np.ndarray, starts: np.ndarray, labels: np.ndarray, K:
     cls, labels = np.asarray(cls), np.asarray(labels)
     Cn, F = cls.shape
     G = global_frames(n_samples)
-    cap = 2 if max_speakers is None else min(2, int(max_speakers))
+    cap = _speaker_cap(max_speakers)
     act = np.zeros((G, K), np.int32)
     cnt, nc = np.zeros(G, np.int64), np.zeros(G, np.int64)
     for c in range(Cn):
@@ -145,18 +153,33 @@ def reconstruct_host(cls: np.ndarray, starts: np.ndarray, labels: np.ndarray, K:
     return count.astype(np.uint8), speakers, act, nc
 
 
-def training_rows(info: np.ndarray, F: int) -> np.ndarray:
-    """Rows (c * 3 + s) of the clustering's training set: valid and TRAIN_CLEAN_DEN * clean_frames >= F."""
+def _speaker_cap(max_speakers: Optional[int]) -> int:     # speakers per frame: the powerset's 2, fewer when max_speakers says so
+    return 2 if max_speakers is None else min(2, int(max_speakers))
+
+
+def candidate_mask(info: np.ndarray) -> np.ndarray:
+    """bool per row (c * 3 + s): a candidate of the assignment, valid and with an active frame."""
     i = np.asarray(info).reshape(-1, 4)
-    return np.flatnonzero((i[:, 3] != 0) & (TRAIN_CLEAN_DEN * i[:, 1].astype(np.int64) >= F))
+    return (i[:, 3] != 0) & (i[:, 0] > 0)
+
+
+def training_mask(info: np.ndarray, F: int) -> np.ndarray:
+    """bool per row (c * 3 + s): in the clustering's training set, valid and TRAIN_CLEAN_DEN * clean_frames >= F."""
+    i = np.asarray(info).reshape(-1, 4)
+    return (i[:, 3] != 0) & (TRAIN_CLEAN_DEN * i[:, 1].astype(np.int64) >= F)
+
+
+def training_rows(info: np.ndarray, F: int) -> np.ndarray:
+    """Rows (c * 3 + s) of the clustering's training set (training_mask)."""
+    return np.flatnonzero(training_mask(info, F))
 
 
 def assign_rows(E: np.ndarray, info: np.ndarray, train: np.ndarray, train_labels: np.ndarray):
     """Unit rows E [C * 3, d], info, the training rows and their cluster labels -> (labels [C, 3] int32, centroids [K, d] fp32 unit)."""
-    i = np.asarray(info).reshape(-1, 4)
     E64 = np.asarray(E, dtype=np.float64)
-    cand = np.flatnonzero((i[:, 3] != 0) & (i[:, 0] > 0))
-    labels = np.full(i.shape[0], -1, np.int32)
+    ok = candidate_mask(info)
+    cand = np.flatnonzero(ok)
+    labels = np.full(ok.size, -1, np.int32)
     if len(train):
         K = int(np.max(train_labels)) + 1
         cent = np.zeros((K, E64.shape[1]))
@@ -214,9 +237,8 @@ def assign_constrained_host(E: np.ndarray, info: np.ndarray, train: np.ndarray, 
     """assign_rows with the constrained rule (the module docstring; sdk_diarize_centroids + sdk_diarize_assign with constrained = 1 in numpy)
     -> (labels [C, 3] int32, centroids [K, d] fp32 unit).  Every cosine is one float64 sum over the columns of its own row, so equal rows
     have equal cosines."""
-    i = np.asarray(info).reshape(-1, 4)
-    Cn = i.shape[0] // N_LOCAL
-    ok = ((i[:, 3] != 0) & (i[:, 0] > 0)).reshape(Cn, N_LOCAL)
+    ok = candidate_mask(info).reshape(-1, N_LOCAL)
+    Cn = ok.shape[0]
     cand = np.flatnonzero(ok.reshape(-1))
     E32 = np.asarray(E)
     E64 = np.zeros(E32.shape, np.float64)
@@ -308,9 +330,8 @@ def _dot_in_order(A: np.ndarray, B: np.ndarray) -> np.ndarray:
 def assign_grouped_host(E, info, cent64, chunk_off, cent_off, constrained: bool = False):
     """sdk_diarize_assign_grouped in numpy: E [3 C, d], info [C, 3, 4], cent64 [K, d] float64, chunk_off / cent_off [R + 1] ->
     (labels [C, 3] int32 local to the recording, score [C, 3] float64).  Rows that are no candidates are never read."""
-    i = np.asarray(info).reshape(-1, 4)
-    Cn = i.shape[0] // N_LOCAL
-    ok = ((i[:, 3] != 0) & (i[:, 0] > 0)).reshape(Cn, N_LOCAL)
+    ok = candidate_mask(info).reshape(-1, N_LOCAL)
+    Cn = ok.shape[0]
     labels, score = np.full((Cn, N_LOCAL), -1, np.int32), np.zeros((Cn, N_LOCAL))
     cent64 = np.asarray(cent64, dtype=np.float64)
     for r in range(len(chunk_off) - 1):
@@ -403,14 +424,41 @@ def renumber_host(first, cent_off, chunk_off, labels, cent):
 
 
 # ------------------------------------------------------------------------------------------------ device stages
-def powerset_decode(eng, logp):
-    """logp [C, F, 7] fp32 (device) -> cls [C, F] uint8 (device): sdk_powerset_decode."""
+VBX_HOST_READS = 7               # cluster.vbx_cluster waits for the device 7 times: the linkage's status and Z, the one read (n_iter, status, K), labels, pi, elbo, keep
+LINKAGE_HOST_READS = 1           # Engine.centroid_linkage reads its status back before it returns Z
+
+
+def _native():
+    """(torch, _lib.check, ops._stream), imported at the first call and not with this module: the host restatements need neither."""
     import torch
     from ._lib import check
     from .ops import _stream
-    if logp.dim() != 3 or logp.shape[2] != 7 or logp.dtype != torch.float32:
-        raise ValueError(f"powerset_decode: logp must be fp32 [C, F, 7], got {tuple(logp.shape)} {logp.dtype}")
+    return torch, check, _stream
+
+
+def _check_dim(name: str, d: int):
+    if d < 64 or d % 64 or d > MAX_ASSIGN_DIM:
+        raise ValueError(f"{name}: d={d} not supported (a multiple of 64, at most {MAX_ASSIGN_DIM})")
+
+
+def _check_rows(name: str, E, rows: Optional[int] = None):
+    if E.dim() != 2 or str(E.dtype) != "torch.float32" or not E.is_contiguous() or not E.is_cuda or (rows is not None and E.shape[0] != rows):
+        raise ValueError(f"{name}: E must be a contiguous fp32 [{'rows' if rows is None else rows}, d] device tensor, got {tuple(E.shape)} {E.dtype}")
+    _check_dim(name, int(E.shape[1]))
+
+
+def _check_tensor(name: str, what: str, t, dtype: str, shape: tuple, min_rows: int = 0):
+    """The wrappers' check of cls (uint8 [C, F]), labels (int32 [C, 3]), info (int32 [C, 3, 4]), the centroids (float64 [K, d]) and the like:
+    contiguous, torch's dtype `dtype`, of `shape` (None: any size), at least min_rows rows."""
+    if str(t.dtype) != "torch." + dtype or t.dim() != len(shape) or any(n not in (None, m) for n, m in zip(shape, t.shape)) or not t.is_contiguous() or t.shape[0] < min_rows:
+        raise ValueError(f"{name}: {what} must be a contiguous {dtype} tensor of shape {shape} (None: any size; {min_rows} rows or more), got {tuple(t.shape)} {t.dtype}")
+
+
+def powerset_decode(eng, logp):
+    """logp [C, F, 7] fp32 (device) -> cls [C, F] uint8 (device): sdk_powerset_decode."""
+    torch, check, _stream = _native()
     logp = logp.contiguous()
+    _check_tensor("powerset_decode", "logp", logp, "float32", (None, None, 7))
     cls = torch.empty(logp.shape[:2], dtype=torch.uint8, device=logp.device)
     check(eng.lib.sdk_powerset_decode(eng.ctx, logp.data_ptr(), logp.shape[0], logp.shape[1], cls.data_ptr(), _stream()), "sdk_powerset_decode")
     return cls
@@ -418,11 +466,8 @@ def powerset_decode(eng, logp):
 
 def diarize_masks(eng, cls, T4: int):
     """cls [B, F] uint8 (device) -> (w [B, 3, T4] fp32, info [B, 3, 4] int32) on the device: sdk_diarize_masks."""
-    import torch
-    from ._lib import check
-    from .ops import _stream
-    if cls.dim() != 2 or cls.dtype != torch.uint8 or not cls.is_contiguous():
-        raise ValueError(f"diarize_masks: cls must be a contiguous uint8 [B, F] tensor, got {tuple(cls.shape)} {cls.dtype}")
+    torch, check, _stream = _native()
+    _check_tensor("diarize_masks", "cls", cls, "uint8", (None, None))
     B, F = cls.shape
     w = torch.empty((B, N_LOCAL, T4), dtype=torch.float32, device=cls.device)
     info = torch.empty((B, N_LOCAL, 4), dtype=torch.int32, device=cls.device)
@@ -433,49 +478,33 @@ def diarize_masks(eng, cls, T4: int):
 def diarize_reconstruct(eng, cls, starts, labels, K: int, n_samples: int, max_speakers: Optional[int] = None, want_act: bool = False):
     """cls [C, F] uint8, starts [C] int32 ascending, labels [C, 3] int32 (all on the device) -> (count [G] uint8, speakers [G, 2] int32,
     act [G, K] int32 or None) on the device: sdk_diarize_reconstruct."""
-    import torch
-    from ._lib import check
-    from .ops import _stream
-    if cls.dim() != 2 or cls.dtype != torch.uint8 or not cls.is_contiguous():
-        raise ValueError(f"diarize_reconstruct: cls must be a contiguous uint8 [C, F] tensor, got {tuple(cls.shape)} {cls.dtype}")
+    torch, check, _stream = _native()
+    _check_tensor("diarize_reconstruct", "cls", cls, "uint8", (None, None))
     Cn, F = cls.shape
-    if starts.dtype != torch.int32 or tuple(starts.shape) != (Cn,) or labels.dtype != torch.int32 or tuple(labels.shape) != (Cn, N_LOCAL):
-        raise ValueError(f"diarize_reconstruct: starts int32 [{Cn}] and labels int32 [{Cn}, 3] expected, got {tuple(starts.shape)} {starts.dtype}, "
-                         f"{tuple(labels.shape)} {labels.dtype}")
     starts, labels = starts.contiguous(), labels.contiguous()
+    _check_tensor("diarize_reconstruct", "starts", starts, "int32", (Cn,))
+    _check_tensor("diarize_reconstruct", "labels", labels, "int32", (Cn, N_LOCAL))
     G = int(eng.lib.sdk_diarize_frames(int(n_samples)))
-    cap = 2 if max_speakers is None else min(2, int(max_speakers))
     count = torch.zeros((G,), dtype=torch.uint8, device=cls.device)
     speakers = torch.full((G, 2), -1, dtype=torch.int32, device=cls.device)
     act = torch.zeros((G, int(K)), dtype=torch.int32, device=cls.device) if want_act else None
-    check(eng.lib.sdk_diarize_reconstruct(eng.ctx, cls.data_ptr(), starts.data_ptr(), labels.data_ptr(), Cn, F, int(K), int(n_samples), cap,
-                                          count.data_ptr(), speakers.data_ptr(), act.data_ptr() if want_act else None, _stream()),
-          "sdk_diarize_reconstruct")
+    check(eng.lib.sdk_diarize_reconstruct(eng.ctx, cls.data_ptr(), starts.data_ptr(), labels.data_ptr(), Cn, F, int(K), int(n_samples),
+                                          _speaker_cap(max_speakers), count.data_ptr(), speakers.data_ptr(), act.data_ptr() if want_act else None,
+                                          _stream()), "sdk_diarize_reconstruct")
     return count, speakers, act
-
-
-def _check_rows(name: str, E, d_what: str = "E"):
-    import torch
-    if E.dim() != 2 or E.dtype != torch.float32 or not E.is_contiguous() or not E.is_cuda:
-        raise ValueError(f"{name}: {d_what} must be a contiguous fp32 [rows, d] device tensor, got {tuple(E.shape)} {E.dtype}")
-    if E.shape[1] < 64 or E.shape[1] % 64 or E.shape[1] > MAX_ASSIGN_DIM:
-        raise ValueError(f"{name}: d={E.shape[1]} not supported (a multiple of 64, at most {MAX_ASSIGN_DIM})")
 
 
 def diarize_centroids(eng, E, rows, labels, K: int, check_rows: bool = True):
     """E [R, d] fp32 unit rows, rows [n] int32 ascending, labels [n] int32 in [0, K) (all on the device) -> (cent [K, d] fp32 unit,
     cent64 [K, d] float64) on the device: sdk_diarize_centroids.  A cluster without rows gives a zero row.  check_rows=False: the caller
     has checked that rows lie in [0, R) (the check reads them back, which waits for the device)."""
-    import torch
-    from ._lib import check
-    from .ops import _stream
+    torch, check, _stream = _native()
     _check_rows("diarize_centroids", E)
     if int(K) < 1:
         raise ValueError(f"diarize_centroids: K={K} (at least 1)")
-    if rows.dtype != torch.int32 or labels.dtype != torch.int32 or rows.dim() != 1 or rows.shape != labels.shape:
-        raise ValueError(f"diarize_centroids: rows and labels must be int32 [n] tensors of one length, got {tuple(rows.shape)} {rows.dtype}, "
-                         f"{tuple(labels.shape)} {labels.dtype}")
     rows, labels = rows.contiguous(), labels.contiguous()
+    _check_tensor("diarize_centroids", "rows", rows, "int32", (None,))
+    _check_tensor("diarize_centroids", "labels", labels, "int32", tuple(rows.shape))
     n, d = int(rows.numel()), int(E.shape[1])
     if check_rows and n and not (0 <= int(rows.min()) and int(rows.max()) < E.shape[0]):   # the kernel reads E at these rows
         raise ValueError(f"diarize_centroids: rows must lie in [0, {E.shape[0]}), got {int(rows.min())} .. {int(rows.max())}")
@@ -489,15 +518,12 @@ def diarize_centroids(eng, E, rows, labels, K: int, check_rows: bool = True):
 def diarize_assign(eng, E, info, cent, constrained: bool = False):
     """E [3 C, d] fp32 unit rows, info [C, 3, 4] int32, cent [K, d] float64 (diarize_centroids' second result), all on the device ->
     (labels [C, 3] int32, score [C, 3] fp32) on the device: sdk_diarize_assign."""
-    import torch
-    from ._lib import check
-    from .ops import _stream
-    _check_rows("diarize_assign", E)
-    Cn, d = E.shape[0] // N_LOCAL, int(E.shape[1])
-    if E.shape[0] % N_LOCAL or info.dtype != torch.int32 or tuple(info.shape) != (Cn, N_LOCAL, 4) or not info.is_contiguous():
-        raise ValueError(f"diarize_assign: E [3 C, d] and a contiguous int32 info [C, 3, 4] expected, got {tuple(E.shape)}, {tuple(info.shape)} {info.dtype}")
-    if cent.dim() != 2 or cent.dtype != torch.float64 or cent.shape[1] != d or not cent.is_contiguous():
-        raise ValueError(f"diarize_assign: the centroids must be a contiguous float64 [K, {d}] tensor, got {tuple(cent.shape)} {cent.dtype}")
+    torch, check, _stream = _native()
+    Cn = E.shape[0] // N_LOCAL
+    _check_rows("diarize_assign", E, N_LOCAL * Cn)
+    d = int(E.shape[1])
+    _check_tensor("diarize_assign", "info", info, "int32", (Cn, N_LOCAL, 4))
+    _check_tensor("diarize_assign", "the centroids", cent, "float64", (None, d))
     if cent.shape[0] < 1:
         raise ValueError("diarize_assign: K=0 (at least one centroid)")
     labels = torch.empty((Cn, N_LOCAL), dtype=torch.int32, device=E.device)
@@ -508,11 +534,11 @@ def diarize_assign(eng, E, info, cent, constrained: bool = False):
 
 
 class GroupTables:
-    """The prefix-sum tables of a pack on the host (checked here, once) and on the device (what the grouped kernels search)."""
+    """The prefix-sum tables of a pack on the host (checked here, once) and on the device (what the grouped kernels search).  uploads counts
+    the host-to-device copies made so far."""
 
     def __init__(self, eng, chunk_off, frame_off, n_samples, starts_local=None):
-        import torch
-        self.eng = eng
+        self.eng, self.uploads = eng, 0
         self.chunk_off, self.frame_off = np.asarray(chunk_off, dtype=np.int64), np.asarray(frame_off, dtype=np.int64)
         self.n_samples = np.asarray(n_samples, dtype=np.int64)
         self.R = R = int(self.n_samples.size)
@@ -525,38 +551,39 @@ class GroupTables:
         parts = [self.chunk_off, self.frame_off] + ([np.asarray(starts_local, dtype=np.int64)] if starts_local is not None else [])
         if starts_local is not None and parts[2].shape != (self.C,):
             raise ValueError(f"GroupTables: starts_local must hold {self.C} chunk starts, got {parts[2].shape}")
-        up = torch.from_numpy(np.concatenate(parts).astype(np.int32)).to(eng.device)                 # one upload
+        up = self._up(np.concatenate(parts).astype(np.int32))                                        # one upload
         self.chunk_off_d, self.frame_off_d = up[:R + 1], up[R + 1:2 * R + 2]
         self.starts_local_d = up[2 * R + 2:] if starts_local is not None else None
-        self.n_samples_d = torch.from_numpy(self.n_samples).to(eng.device)
+        self.n_samples_d = self._up(self.n_samples)
         self.cent_off = self.cent_off_d = self.act_off = self.act_off_d = None
         self.K = 0
 
+    def _up(self, a: np.ndarray):
+        self.uploads += 1
+        return _native()[0].from_numpy(a).to(self.eng.device)
+
     def set_clusters(self, cent_off, want_act: bool = False):
         """cent_off [R + 1]: prefix sums of the recordings' cluster counts."""
-        import torch
         off = np.asarray(cent_off, dtype=np.int64)
         if off.shape != (self.R + 1,) or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] >= (1 << 30):
             raise ValueError(f"GroupTables: cent_off must hold R + 1 = {self.R + 1} prefix sums from 0, got {off.tolist()[:8]}")
         self.cent_off, self.K = off, int(off[-1])
-        self.cent_off_d = torch.from_numpy(off.astype(np.int32)).to(self.eng.device)
+        self.cent_off_d = self._up(off.astype(np.int32))
         self.act_off = np.concatenate([[0], np.cumsum(np.diff(self.frame_off) * np.maximum(np.diff(off), 1))]).astype(np.int64)
-        self.act_off_d = torch.from_numpy(self.act_off).to(self.eng.device) if want_act else None
+        self.act_off_d = self._up(self.act_off) if want_act else None
         return self
 
 
 def diarize_assign_grouped(eng, E, info, cent, tab: GroupTables, constrained: bool = False):
     """diarize_assign over a pack: cent [K, d] float64 holds recording r's centroids at tab.cent_off[r] .. tab.cent_off[r + 1] ->
     (labels [C, 3] int32 local to the recording, score [C, 3] fp32) on the device: sdk_diarize_assign_grouped."""
-    import torch
-    from ._lib import check
-    from .ops import _stream
-    _check_rows("diarize_assign_grouped", E)
+    torch, check, _stream = _native()
+    _check_rows("diarize_assign_grouped", E, N_LOCAL * tab.C)
     Cn, d = tab.C, int(E.shape[1])
-    if E.shape[0] != N_LOCAL * Cn or info.dtype != torch.int32 or tuple(info.shape) != (Cn, N_LOCAL, 4) or not info.is_contiguous():
-        raise ValueError(f"diarize_assign_grouped: E [{3 * Cn}, d] and a contiguous int32 info [{Cn}, 3, 4] expected, got {tuple(E.shape)}, {tuple(info.shape)} {info.dtype}")
-    if tab.cent_off is None or cent.dim() != 2 or cent.dtype != torch.float64 or cent.shape[1] != d or not cent.is_contiguous() or cent.shape[0] < max(tab.K, 1):
-        raise ValueError(f"diarize_assign_grouped: the centroids must be a contiguous float64 [{max(tab.K, 1)}, {d}] tensor, got {tuple(cent.shape)} {cent.dtype}")
+    _check_tensor("diarize_assign_grouped", "info", info, "int32", (Cn, N_LOCAL, 4))
+    if tab.cent_off is None:
+        raise ValueError("diarize_assign_grouped: the tables hold no clusters (set_clusters)")
+    _check_tensor("diarize_assign_grouped", "the centroids", cent, "float64", (None, d), max(tab.K, 1))
     labels = torch.empty((Cn, N_LOCAL), dtype=torch.int32, device=E.device)
     score = torch.empty((Cn, N_LOCAL), dtype=torch.float32, device=E.device)
     check(eng.lib.sdk_diarize_assign_grouped(eng.ctx, E.data_ptr(), info.data_ptr(), cent.data_ptr(), tab.chunk_off_d.data_ptr(), tab.cent_off_d.data_ptr(),
@@ -564,14 +591,13 @@ def diarize_assign_grouped(eng, E, info, cent, tab: GroupTables, constrained: bo
     return labels, score
 
 
-def diarize_fold_grouped(eng, cent, sizes, cl_off, eff, cent_off, cut=None):
+def diarize_fold_grouped(eng, cent, sizes, cl_off, eff, cent_off, cut=None, upload=None):
     """The fold of cluster.fold_small_clusters over a pack, on the device: cent [Kc, d] float64 unit centroids of the cut (device), sizes
     [Kc], cl_off [R + 1], eff [R], cent_off [R + 1] (host integers; cent_off must count the large clusters of every recording, 1 when it has
     clusters and none is large), cut [n] int32 (device, or None): the cut's global cluster of every training row ->
-    (remap [Kc] int32, out [n] int32 = remap[cut], or None) on the device: sdk_diarize_fold_grouped."""
-    import torch
-    from ._lib import check
-    from .ops import _stream
+    (remap [Kc] int32, out [n] int32 = remap[cut], or None) on the device: sdk_diarize_fold_grouped.  upload: what carries the one table of
+    host integers to cent's device (a caller that counts its transfers passes its own)."""
+    torch, check, _stream = _native()
     sizes, cl_off, eff, cent_off = (np.asarray(v, dtype=np.int64) for v in (sizes, cl_off, eff, cent_off))
     R, Kc = int(eff.size), int(sizes.size)
     large = None
@@ -580,13 +606,13 @@ def diarize_fold_grouped(eng, cent, sizes, cl_off, eff, cent_off, cut=None):
         large = np.bincount(rec[sizes >= eff[rec]], minlength=R)
     if large is None or cent_off.shape != (R + 1,) or cent_off[0] != 0 or not np.array_equal(np.diff(cent_off), np.where(np.diff(cl_off) > 0, np.maximum(large, 1), 0)):
         raise ValueError("diarize_fold_grouped: cl_off must be the R + 1 prefix sums of the cut's cluster counts and cent_off those of the large clusters (1 when none)")
-    d = int(cent.shape[1]) if cent.dim() == 2 else 0
-    if cent.dtype != torch.float64 or not cent.is_contiguous() or cent.shape[0] < Kc or d < 64 or d % 64 or d > MAX_ASSIGN_DIM:
-        raise ValueError(f"diarize_fold_grouped: the centroids must be a contiguous float64 [{Kc}, d] tensor (d a multiple of 64, at most {MAX_ASSIGN_DIM}), got {tuple(cent.shape)} {cent.dtype}")
+    _check_tensor("diarize_fold_grouped", "the centroids", cent, "float64", (None, None), Kc)
+    d = int(cent.shape[1])
+    _check_dim("diarize_fold_grouped", d)
     n = 0 if cut is None else int(cut.numel())
-    if cut is not None and (cut.dtype != torch.int32 or cut.dim() != 1 or not cut.is_contiguous()):
-        raise ValueError(f"diarize_fold_grouped: cut must be a contiguous int32 [n] tensor, got {tuple(cut.shape)} {cut.dtype}")
-    up = torch.from_numpy(np.concatenate([sizes, cl_off, eff, cent_off]).astype(np.int32)).to(cent.device)
+    if cut is not None:
+        _check_tensor("diarize_fold_grouped", "cut", cut, "int32", (None,))
+    up = (upload or (lambda a: torch.from_numpy(a).to(cent.device)))(np.concatenate([sizes, cl_off, eff, cent_off]).astype(np.int32))
     sizes_d, cl_d, eff_d, co_d = up[:Kc], up[Kc:Kc + R + 1], up[Kc + R + 1:Kc + 2 * R + 1], up[Kc + 2 * R + 1:]
     target = torch.empty((max(Kc, 1),), dtype=torch.int32, device=cent.device)
     remap = torch.empty((max(Kc, 1),), dtype=torch.int32, device=cent.device)
@@ -601,23 +627,18 @@ def diarize_reconstruct_grouped(eng, cls, labels, tab: GroupTables, max_speakers
     """diarize_reconstruct over a pack: cls [C, F] uint8, labels [C, 3] int32 local to the recording (device), tab with starts_local and
     clusters set -> (count [G] uint8, speakers [G, 2] int32, act int32 [tab.act_off[-1]] or None) on the packed frame grid:
     sdk_diarize_reconstruct_grouped."""
-    import torch
-    from ._lib import check
-    from .ops import _stream
-    if cls.dim() != 2 or cls.dtype != torch.uint8 or not cls.is_contiguous() or cls.shape[0] != tab.C:
-        raise ValueError(f"diarize_reconstruct_grouped: cls must be a contiguous uint8 [{tab.C}, F] tensor, got {tuple(cls.shape)} {cls.dtype}")
-    if labels.dtype != torch.int32 or tuple(labels.shape) != (tab.C, N_LOCAL) or not labels.is_contiguous():
-        raise ValueError(f"diarize_reconstruct_grouped: labels must be a contiguous int32 [{tab.C}, 3] tensor, got {tuple(labels.shape)} {labels.dtype}")
+    torch, check, _stream = _native()
+    _check_tensor("diarize_reconstruct_grouped", "cls", cls, "uint8", (tab.C, None))
+    _check_tensor("diarize_reconstruct_grouped", "labels", labels, "int32", (tab.C, N_LOCAL))
     if tab.starts_local_d is None or tab.cent_off is None or (want_act and tab.act_off_d is None):
         raise ValueError("diarize_reconstruct_grouped: the tables need starts_local and set_clusters (want_act=True for act)")
-    cap = 2 if max_speakers is None else min(2, int(max_speakers))
     count = torch.zeros((tab.G,), dtype=torch.uint8, device=cls.device)
     speakers = torch.full((tab.G, 2), -1, dtype=torch.int32, device=cls.device)
     act = torch.zeros((max(int(tab.act_off[-1]), 1),), dtype=torch.int32, device=cls.device) if want_act else None
     if tab.C and tab.G:
         check(eng.lib.sdk_diarize_reconstruct_grouped(eng.ctx, cls.data_ptr(), tab.starts_local_d.data_ptr(), labels.data_ptr(), tab.chunk_off_d.data_ptr(),
                                                       tab.frame_off_d.data_ptr(), tab.n_samples_d.data_ptr(), tab.cent_off_d.data_ptr(), tab.R, tab.C,
-                                                      int(cls.shape[1]), tab.G, cap, count.data_ptr(), speakers.data_ptr(),
+                                                      int(cls.shape[1]), tab.G, _speaker_cap(max_speakers), count.data_ptr(), speakers.data_ptr(),
                                                       act.data_ptr() if want_act else None, tab.act_off_d.data_ptr() if want_act else None, _stream()),
               "sdk_diarize_reconstruct_grouped")
     return count, speakers, act
@@ -625,9 +646,7 @@ def diarize_reconstruct_grouped(eng, cls, labels, tab: GroupTables, max_speakers
 
 def diarize_first_seen(eng, speakers, tab: GroupTables):
     """speakers [G, 2] int32 (device) -> first [K] int32 (device): sdk_diarize_first_seen (integer atomicMin)."""
-    import torch
-    from ._lib import check
-    from .ops import _stream
+    torch, check, _stream = _native()
     if speakers.dtype != torch.int32 or tuple(speakers.shape) != (tab.G, 2) or not speakers.is_contiguous() or tab.cent_off is None:
         raise ValueError(f"diarize_first_seen: speakers must be a contiguous int32 [{tab.G}, 2] tensor and the tables hold clusters, got {tuple(speakers.shape)} {speakers.dtype}")
     first = torch.empty((max(tab.K, 1),), dtype=torch.int32, device=speakers.device)
@@ -639,15 +658,12 @@ def diarize_first_seen(eng, speakers, tab: GroupTables):
 def diarize_renumber(eng, first, labels, cent, cent64, tab: GroupTables):
     """first [K] (diarize_first_seen), labels [C, 3] int32 local (REWRITTEN in place), cent [K, d] fp32 and cent64 [K, d] float64 ->
     (renum [K] int32, cent and cent64 with recording r's rows permuted to their new numbers) on the device: sdk_diarize_renumber."""
-    import torch
-    from ._lib import check
-    from .ops import _stream
+    torch, check, _stream = _native()
     K = tab.K
-    if first.dtype != torch.int32 or first.numel() != K or labels.dtype != torch.int32 or tuple(labels.shape) != (tab.C, N_LOCAL) or not labels.is_contiguous():
-        raise ValueError(f"diarize_renumber: first int32 [{K}] and a contiguous int32 labels [{tab.C}, 3] expected, got {tuple(first.shape)}, {tuple(labels.shape)} {labels.dtype}")
-    if cent.dtype != torch.float32 or cent64.dtype != torch.float64 or cent.dim() != 2 or cent.shape != cent64.shape or cent.shape[0] < K \
-            or not cent.is_contiguous() or not cent64.is_contiguous():
-        raise ValueError(f"diarize_renumber: contiguous fp32 and float64 centroids [{K}, d] expected, got {tuple(cent.shape)} {cent.dtype}, {tuple(cent64.shape)} {cent64.dtype}")
+    _check_tensor("diarize_renumber", "first", first, "int32", (K,))
+    _check_tensor("diarize_renumber", "labels", labels, "int32", (tab.C, N_LOCAL))
+    _check_tensor("diarize_renumber", "cent64", cent64, "float64", (None, None), K)
+    _check_tensor("diarize_renumber", "cent", cent, "float32", tuple(cent64.shape))
     renum = torch.empty((max(K, 1),), dtype=torch.int32, device=labels.device)
     o32, o64 = torch.empty_like(cent), torch.empty_like(cent64)
     check(eng.lib.sdk_diarize_renumber(eng.ctx, first.data_ptr(), tab.cent_off_d.data_ptr(), tab.chunk_off_d.data_ptr(), tab.R, K, tab.C, int(cent.shape[1]),
@@ -656,12 +672,15 @@ def diarize_renumber(eng, first, labels, cent, cent64, tab: GroupTables):
     return renum[:K], o32, o64
 
 
-
 class Diarizer:
-    """The pipeline on one ops.Engine: a resident segmentation.Segmentation and a resident resnet.ResNet34."""
+    """The pipeline on one ops.Engine: a resident segmentation.Segmentation and a resident resnet.ResNet34.  run and run_many share the option
+    and recording checks, the embedding of all chunks (_embed_all) and the empty result; they part after that (the module docstring)."""
 
     def __init__(self, engine, segmentation, resnet, plda=None):
         self.eng, self.seg, self.resnet, self.plda = engine, segmentation, resnet, plda
+        self.trace = False               # True: run_many appends one {stage: seconds} per pack to last_stage_s, every stage ended by a device synchronisation
+        self.last_stage_s: List[dict] = []
+        self.last_sync: List[dict] = []  # run_many: the downloads and uploads of the last call, one dict per pack
 
     def plda_model(self):
         """The plda.Plda of clustering="vbx": the one given, else a seeded synthetic model for the embedding width."""
@@ -669,6 +688,34 @@ class Diarizer:
             from .plda import synthetic_plda
             self.plda = synthetic_plda(self.resnet.cfg.embed_dim, 128, 0)
         return self.plda
+
+    # ---------------------------------------------------------------------------------------------- what run and run_many share
+    def _check_options(self, who: str, clustering, vbx, max_speakers) -> dict:
+        """-> vbx as a dict of its own."""
+        if clustering not in ("ahc", "vbx"):
+            raise ValueError(f"{who}: clustering={clustering!r} (\"ahc\" or \"vbx\")")
+        vbx = dict(vbx or {})
+        if set(vbx) - {"Fa", "Fb", "max_iters", "epsilon", "init_smoothing"} or (vbx and clustering != "vbx"):
+            raise ValueError(f"{who}: vbx={vbx} (keys Fa, Fb, max_iters, epsilon, init_smoothing; only with clustering=\"vbx\")")
+        if max_speakers is not None and int(max_speakers) < 0:
+            raise ValueError(f"max_speakers={max_speakers}: must be None or >= 0")
+        return vbx
+
+    def _check_recording(self, who: str, Cn: int, n_samples: int, step_s: float, logp=None):
+        """The linkage's row bound and the shape of an injected logp, for a recording of n_samples > 0 samples in Cn chunks."""
+        F = seg_frames(CHUNK)
+        if N_LOCAL * Cn > MAX_LINKAGE_ROWS:
+            raise ValueError(f"{who}: {Cn} chunks at step_s={step_s} give up to {N_LOCAL * Cn} embeddings to cluster; the centroid linkage serves at "
+                             f"most {MAX_LINKAGE_ROWS} rows ({MAX_LINKAGE_ROWS // N_LOCAL} chunks): raise step_s or split the recording")
+        if logp is not None:
+            shp = tuple(logp.shape if hasattr(logp, "shape") else np.shape(logp))
+            if shp != (Cn, F, 7):
+                raise ValueError(f"{who}: injected logp must be [{Cn}, {F}, 7] for {n_samples} samples at step_s={step_s}, got {shp}")
+
+    def _empty(self) -> DiarizationResult:
+        d = self.resnet.cfg.embed_dim
+        return DiarizationResult([], 0, np.zeros((0, d), np.float32), np.zeros((0, N_LOCAL), np.int32), np.zeros(0, np.uint8),
+                                 np.full((0, 2), -1, np.int32), np.zeros(0, np.int64), np.zeros((0, N_LOCAL, 4), np.int32))
 
     def embed_chunks(self, rec, n_samples: int, starts_dev, logp=None):
         """One batch of chunks: (cls [B, F] uint8, info [B, 3, 4] int32, unit embeddings [B * 3, d] fp32), all on the device."""
@@ -682,6 +729,22 @@ class Diarizer:
         emb = self.resnet.forward_masked(feats, B, T, w, info[:, :, 3].contiguous())
         return cls, info, self.eng.l2norm(emb)[0]
 
+    def _embed_all(self, rec, n: int, starts_dev, logp_dev=None):
+        """Every chunk of the buffer rec (n samples, device) in batches of $SDK_DIARIZE_BATCH -> (cls [C, F] uint8, info [C, 3, 4] int32,
+        unit embeddings [3 C, d] fp32) on the device.  In a pack the batches cross recording boundaries."""
+        torch = _native()[0]
+        Cn = int(starts_dev.numel())
+        batch = max(1, int(os.environ.get("SDK_DIARIZE_BATCH", str(DEFAULT_BATCH))))
+        cls = torch.empty((Cn, seg_frames(CHUNK)), dtype=torch.uint8, device=self.eng.device)
+        infos, embs = [], []
+        for a in range(0, Cn, batch):
+            c, i, e = self.embed_chunks(rec, n, starts_dev[a:a + batch], None if logp_dev is None else logp_dev[a:a + batch])
+            cls[a:a + batch] = c
+            infos.append(i)
+            embs.append(e)
+        return cls, torch.cat(infos), torch.cat(embs)
+
+    # ---------------------------------------------------------------------------------------------- one recording
     def run(self, samples, step_s: float = 1.0, threshold: float = PYANNOTE_THRESHOLD, min_cluster_size: int = PYANNOTE_MIN_CLUSTER_SIZE,
             max_speakers: Optional[int] = None, logp=None, constrained: bool = False, clustering: str = "ahc",
             vbx: Optional[dict] = None) -> DiarizationResult:
@@ -693,77 +756,51 @@ class Diarizer:
         meaning, the cut of the linkage, which now only initialises: pass cluster.VBX_AHC_THRESHOLD (0.6) with it; min_cluster_size is not
         used.  vbx: a dict of Fa, Fb, max_iters, epsilon, init_smoothing (cluster.vbx_cluster's defaults otherwise).  The result carries
         scores, pi and elbo."""
-        import torch
+        vbx = self._check_options("diarize", clustering, vbx, max_speakers)
+        torch = _native()[0]
         from .cluster import agglomerative_cluster, vbx_cluster
         eng = self.eng
-        if clustering not in ("ahc", "vbx"):
-            raise ValueError(f"diarize: clustering={clustering!r} (\"ahc\" or \"vbx\")")
-        vbx = dict(vbx or {})
-        unknown = sorted(set(vbx) - {"Fa", "Fb", "max_iters", "epsilon", "init_smoothing"})
-        if unknown or (vbx and clustering != "vbx"):
-            raise ValueError(f"diarize: vbx={vbx} (keys Fa, Fb, max_iters, epsilon, init_smoothing; only with clustering=\"vbx\")")
         x = np.ascontiguousarray(samples, dtype=np.int16).reshape(-1)
-        d = self.resnet.cfg.embed_dim
         if x.size == 0:
-            return DiarizationResult([], 0, np.zeros((0, d), np.float32), np.zeros((0, N_LOCAL), np.int32), np.zeros(0, np.uint8),
-                                     np.full((0, 2), -1, np.int32), np.zeros(0, np.int64), np.zeros((0, N_LOCAL, 4), np.int32))
-        if max_speakers is not None and int(max_speakers) < 0:
-            raise ValueError(f"max_speakers={max_speakers}: must be None or >= 0")
-        st = chunk_starts(x.size, step_s)
+            return self._empty()
+        st = chunk_starts(x.size, step_s)                       # chunks
         Cn, F = len(st), seg_frames(CHUNK)
-        if N_LOCAL * Cn > MAX_LINKAGE_ROWS:
-            raise ValueError(f"diarize: {Cn} chunks at step_s={step_s} give up to {N_LOCAL * Cn} embeddings to cluster; the centroid linkage serves at "
-                             f"most {MAX_LINKAGE_ROWS} rows ({MAX_LINKAGE_ROWS // N_LOCAL} chunks): raise step_s or split the recording")
+        self._check_recording("diarize", Cn, x.size, step_s, logp)
         if logp is not None:
             logp = torch.as_tensor(logp, dtype=torch.float32).to(eng.device)
-            if tuple(logp.shape) != (Cn, F, 7):
-                raise ValueError(f"diarize: injected logp must be [{Cn}, {F}, 7] for {x.size} samples at step_s={step_s}, got {tuple(logp.shape)}")
         if eng.precision != self.resnet.precision:
             eng.set_precision(self.resnet.precision)            # the front end's output format follows the embedding's numerical contract
         rec = torch.from_numpy(x).to(eng.device)
         starts_dev = torch.from_numpy(st.astype(np.int32)).to(eng.device)
-        batch = max(1, int(os.environ.get("SDK_DIARIZE_BATCH", str(DEFAULT_BATCH))))
-        cls = torch.empty((Cn, F), dtype=torch.uint8, device=eng.device)
-        infos, embs = [], []
-        for a in range(0, Cn, batch):
-            c, i, e = self.embed_chunks(rec, x.size, starts_dev[a:a + batch], None if logp is None else logp[a:a + batch])
-            cls[a:a + batch] = c
-            infos.append(i)
-            embs.append(e)
-        E_dev = torch.cat(embs)
-        info_dev = torch.cat(infos)
+        cls, info_dev, E_dev = self._embed_all(rec, x.size, starts_dev, logp)     # decode, masks, embedding
         info = info_dev.cpu().numpy()
-        train = training_rows(info, F)
-        vres = None
-        if clustering == "vbx" and len(train) > 1:
+        train = training_rows(info, F)                          # training rows and their clustering
+        vres, tl = None, np.zeros(len(train), np.int32)
+        if len(train) > 1 and clustering == "vbx":
             vres = vbx_cluster(eng, E_dev, self.plda_model(), threshold, rows=train, **vbx)
-            tl = None
         elif len(train) > 1:
             tl = agglomerative_cluster(eng, E_dev.index_select(0, torch.from_numpy(train).to(eng.device)).contiguous(), threshold, min_cluster_size).labels
-        else:
-            tl = np.zeros(len(train), np.int32)
-        scores = None
-        if vres is not None:
-            lab_dev, score_dev = diarize_assign(eng, E_dev, info_dev.contiguous(), vres.cent64.contiguous(), bool(constrained))
-            labels, scores, cent = lab_dev.cpu().numpy(), score_dev.cpu().numpy(), vres.cent.cpu().numpy()
-        elif constrained or clustering == "vbx":
-            flat = info.reshape(-1, 4)
-            rows, rl = (train, tl) if len(train) else (np.flatnonzero((flat[:, 3] != 0) & (flat[:, 0] > 0)), None)    # no training row: the candidates, one cluster
-            if len(rows):
-                rl = np.zeros(len(rows), np.int32) if rl is None else np.asarray(rl, dtype=np.int32)
-                c32, c64 = diarize_centroids(eng, E_dev, torch.from_numpy(rows.astype(np.int32)).to(eng.device), torch.from_numpy(rl).to(eng.device),
-                                             int(rl.max()) + 1)
-                lab_dev, score_dev = diarize_assign(eng, E_dev, info_dev.contiguous(), c64, bool(constrained))
-                labels, scores, cent = lab_dev.cpu().numpy(), score_dev.cpu().numpy(), c32.cpu().numpy()
+        if constrained or clustering == "vbx":                  # assignment on the device: the embeddings stay there, the result carries scores
+            if vres is not None:
+                c32, c64 = vres.cent, vres.cent64.contiguous()
             else:
-                labels, scores, cent = np.full((Cn, N_LOCAL), -1, np.int32), np.zeros((Cn, N_LOCAL), np.float32), np.zeros((0, d), np.float32)
-        else:
+                rows = train if len(train) else np.flatnonzero(candidate_mask(info))                 # no training row: the candidates, one cluster
+                rl = np.asarray(tl, dtype=np.int32) if len(train) else np.zeros(len(rows), np.int32)
+                c32, c64 = diarize_centroids(eng, E_dev, torch.from_numpy(rows.astype(np.int32)).to(eng.device), torch.from_numpy(rl).to(eng.device),
+                                             int(rl.max()) + 1) if len(rows) else (None, None)
+            if c64 is not None:
+                lab_dev, score_dev = diarize_assign(eng, E_dev, info_dev, c64, bool(constrained))
+                labels, scores, cent = lab_dev.cpu().numpy(), score_dev.cpu().numpy(), c32.cpu().numpy()
+            else:                                               # neither a training row nor a candidate: no speaker
+                labels, scores, cent = np.full((Cn, N_LOCAL), -1, np.int32), np.zeros((Cn, N_LOCAL), np.float32), np.zeros((0, self.resnet.cfg.embed_dim), np.float32)
+        else:                                                   # assignment of "ahc" unconstrained: on the host, a BLAS product (the module docstring)
             E = E_dev.cpu().numpy()
-            E[info.reshape(-1, 4)[:, 3] == 0] = 0.0             # rows that are not valid are never read as embeddings
+            E[info.reshape(-1, 4)[:, 3] == 0] = 0.0            # rows that are not valid are never read as embeddings
             labels, cent = assign_rows(E, info, train, tl)
+            scores = None
         K = cent.shape[0]
 
-        def stitch(lab):
+        def stitch(lab):                                        # stitching; numbering by appearance below, then turns
             cnt, spk, _ = diarize_reconstruct(eng, cls, starts_dev, torch.from_numpy(np.ascontiguousarray(lab, dtype=np.int32)).to(eng.device),
                                               max(K, 1), x.size, max_speakers)
             return cnt.cpu().numpy(), spk.cpu().numpy()
@@ -780,11 +817,6 @@ class Diarizer:
         return res
 
     # ---------------------------------------------------------------------------------------------- many recordings in one device pass
-    def _empty(self) -> DiarizationResult:
-        d = self.resnet.cfg.embed_dim
-        return DiarizationResult([], 0, np.zeros((0, d), np.float32), np.zeros((0, N_LOCAL), np.int32), np.zeros(0, np.uint8),
-                                 np.full((0, 2), -1, np.int32), np.zeros(0, np.int64), np.zeros((0, N_LOCAL, 4), np.int32))
-
     def run_many(self, recordings, step_s: float = 1.0, threshold: float = PYANNOTE_THRESHOLD, min_cluster_size: int = PYANNOTE_MIN_CLUSTER_SIZE,
                  max_speakers: Optional[int] = None, logp=None, constrained: bool = False, clustering: str = "ahc",
                  vbx: Optional[dict] = None) -> List[DiarizationResult]:
@@ -797,36 +829,18 @@ class Diarizer:
         with at least two training rows and the download of its status and Z, the cut per recording on the host, then centroids of the cut,
         fold, final centroids, assignment, stitching, renumbering and second stitching on the device, and one download each of labels,
         scores, centroids, count and speakers.  self.last_sync holds the number of such waits of the last call, per pack.
-
-        For every recording cls, info, labels, count, speakers, turns, n_speakers and starts equal run(..., constrained=True)'s when
-        constrained=True.  With constrained=False they equal run's provided no decision is a tie or near-tie at float64 rounding: run's
-        unconstrained assignment is a BLAS product on the host, this one sdk_diarize_assign_grouped's column-order float64 sum (so every
-        result carries scores).  The same proviso holds for the fold (run folds on the host with a BLAS product).  Centroids agree to fp32
-        rounding of the same float64 rows.  clustering="vbx" runs cluster.vbx_cluster recording by recording (its own linkage, cut and
-        host reads per recording) between the packed embedding and the grouped assignment: a grouped VBx is out of scope."""
+        Where the results differ from run's on purpose: "shared" in the module docstring.  clustering="vbx" runs cluster.vbx_cluster
+        recording by recording (its own linkage, cut and host reads) between the packed embedding and the grouped assignment."""
         from .cluster import vbx_cluster  # noqa: F401  (checked early: the package imports)
-        if clustering not in ("ahc", "vbx"):
-            raise ValueError(f"diarize_many: clustering={clustering!r} (\"ahc\" or \"vbx\")")
-        vbx = dict(vbx or {})
-        unknown = sorted(set(vbx) - {"Fa", "Fb", "max_iters", "epsilon", "init_smoothing"})
-        if unknown or (vbx and clustering != "vbx"):
-            raise ValueError(f"diarize_many: vbx={vbx} (keys Fa, Fb, max_iters, epsilon, init_smoothing; only with clustering=\"vbx\")")
-        if max_speakers is not None and int(max_speakers) < 0:
-            raise ValueError(f"max_speakers={max_speakers}: must be None or >= 0")
+        vbx = self._check_options("diarize_many", clustering, vbx, max_speakers)
         xs = [np.ascontiguousarray(x, dtype=np.int16).reshape(-1) for x in recordings]
         if logp is not None and (not isinstance(logp, (list, tuple)) or len(logp) != len(xs)):
             raise ValueError(f"diarize_many: logp must be None or a list with one array per recording ({len(xs)}), got "
                              f"{len(logp) if isinstance(logp, (list, tuple)) else type(logp).__name__}")
-        F = seg_frames(CHUNK)
         n_chunks = [len(chunk_starts(x.size, step_s)) if x.size else 0 for x in xs]
-        for i, Cn in enumerate(n_chunks):
-            if N_LOCAL * Cn > MAX_LINKAGE_ROWS:
-                raise ValueError(f"diarize_many: recording {i}: {Cn} chunks at step_s={step_s} give up to {N_LOCAL * Cn} embeddings to cluster; the centroid "
-                                 f"linkage serves at most {MAX_LINKAGE_ROWS} rows ({MAX_LINKAGE_ROWS // N_LOCAL} chunks): raise step_s or split the recording")
-            if logp is not None and xs[i].size:
-                shp = tuple(getattr(logp[i], "shape", np.shape(logp[i])))
-                if shp != (Cn, F, 7):
-                    raise ValueError(f"diarize_many: recording {i}: injected logp must be [{Cn}, {F}, 7] for {xs[i].size} samples at step_s={step_s}, got {shp}")
+        for i, x in enumerate(xs):
+            if x.size:
+                self._check_recording(f"diarize_many: recording {i}", n_chunks[i], x.size, step_s, None if logp is None else logp[i])
         cap_s = min(MAX_PACK_SAMPLES, max(1, int(os.environ.get("SDK_DIARIZE_PACK_SAMPLES", str(DEFAULT_PACK_SAMPLES)))))
         cap_b = max(1, int(os.environ.get("SDK_DIARIZE_PACK_LINKAGE_BYTES", str(DEFAULT_PACK_LINKAGE_BYTES))))
         packs, cur, ns, nb = [], [], 0, 0
@@ -849,144 +863,153 @@ class Diarizer:
                 out[i] = res
         return out
 
+    def _up(self, a, dtype=None):                               # host -> device, counted for the current pack (dtype: torch.as_tensor converts on the way)
+        torch = _native()[0]
+        self.last_sync[-1]["uploads"] += 1
+        return (torch.from_numpy(np.ascontiguousarray(a)) if dtype is None else torch.as_tensor(a, dtype=dtype)).to(self.eng.device)
+
+    def _down(self, t) -> np.ndarray:                           # device -> host, a wait for the device, counted for the current pack
+        self.last_sync[-1]["downloads"] += 1
+        return t.cpu().numpy()
+
+    def _mark(self, name: str):
+        """self.trace: the wall clock since the last mark goes to stage `name` of the current pack, after a device synchronisation."""
+        if self.trace:
+            _native()[0].cuda.synchronize()
+            now, stage_s = time.perf_counter(), self.last_stage_s[-1]
+            stage_s[name] = stage_s.get(name, 0.0) + now - self._t_mark
+            self._t_mark = now
+
     def _run_pack(self, xs, logps, step_s, threshold, min_cluster_size, max_speakers, constrained, clustering, vbx):
-        import torch
-        from .cluster import fcluster_distance, vbx_cluster
-        eng, dev = self.eng, self.eng.device
+        """One pack through its stages; every _mark ends a stage of last_stage_s."""
         sync = {"downloads": 0, "uploads": 0}
         self.last_sync.append(sync)
-        import time
-        stage_s, t_last = {}, [time.perf_counter()]
-        if getattr(self, "trace", False):
-            self.last_stage_s = getattr(self, "last_stage_s", [])
-            self.last_stage_s.append(stage_s)
-
-        def mark(name):                                         # self.trace = True: wall clock per stage, each ended by a device synchronisation
-            if getattr(self, "trace", False):
-                torch.cuda.synchronize()
-                now = time.perf_counter()
-                stage_s[name] = stage_s.get(name, 0.0) + now - t_last[0]
-                t_last[0] = now
+        if self.trace:
+            self.last_stage_s.append({})
+        self._t_mark = time.perf_counter()
         pack = pack_recordings(xs, step_s)
-        R, d, F = len(xs), self.resnet.cfg.embed_dim, seg_frames(CHUNK)
-        co = pack.chunk_off
-        Cn = int(co[-1])
-        if Cn == 0:
+        if int(pack.chunk_off[-1]) == 0:
             return [self._empty() for _ in xs]
+        tab, cls, info_dev, E_dev = self._pack_embed(pack, xs, logps)
+        info = self._down(info_dev)
+        self._mark("segmentation_embedding")
+        rows, n_train = self._pack_rows(info, pack.chunk_off)
+        if clustering == "vbx":
+            c32, c64, cent_off, vres = self._pack_vbx(E_dev, pack.chunk_off, rows, n_train, threshold, vbx)
+        else:
+            c32, c64, cent_off, vres = self._pack_ahc(E_dev, rows, n_train, threshold, min_cluster_size)
+        tab.set_clusters(cent_off)
+        sync["uploads"] += tab.uploads
+        self._mark("cut_fold_centroids")
+        host = self._pack_assign(tab, cls, info_dev, E_dev, c32, c64, constrained, max_speakers)
+        self._mark("assign_stitch_download")
+        out = self._pack_results(xs, pack, cent_off, info, cls, vres, *host)
+        self._mark("turns")
+        return out
 
-        def up(a):
-            sync["uploads"] += 1
-            return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        if eng.precision != self.resnet.precision:
-            eng.set_precision(self.resnet.precision)            # the front end's output format follows the embedding's numerical contract
-        rec = up(pack.samples)
-        starts_dev = up(pack.starts_packed)
-        tab = GroupTables(eng, co, pack.frame_off, pack.n_samples, pack.starts_local)
-        sync["uploads"] += 2
+    def _pack_embed(self, pack: Pack, xs, logps):
+        """Upload the pack and its tables, then embed every chunk -> (tab, cls, info_dev, E_dev)."""
+        torch = _native()[0]
+        if self.eng.precision != self.resnet.precision:
+            self.eng.set_precision(self.resnet.precision)       # the front end's output format follows the embedding's numerical contract
+        rec = self._up(pack.samples)
+        starts_dev = self._up(pack.starts_packed)
+        tab = GroupTables(self.eng, pack.chunk_off, pack.frame_off, pack.n_samples, pack.starts_local)
         lp_all = None
         if logps is not None:
-            lp_all = torch.cat([torch.as_tensor(l, dtype=torch.float32).to(dev) for l, x in zip(logps, xs) if x.size])
-            sync["uploads"] += R
-        mark("pack_upload")
-        batch = max(1, int(os.environ.get("SDK_DIARIZE_BATCH", str(DEFAULT_BATCH))))
-        cls = torch.empty((Cn, F), dtype=torch.uint8, device=dev)
-        infos, embs = [], []
-        for a in range(0, Cn, batch):                           # the batches cross recording boundaries
-            c, i, e = self.embed_chunks(rec, int(rec.numel()), starts_dev[a:a + batch], None if lp_all is None else lp_all[a:a + batch])
-            cls[a:a + batch] = c
-            infos.append(i)
-            embs.append(e)
-        E_dev = torch.cat(embs)
-        info_dev = torch.cat(infos).contiguous()
-        info = info_dev.cpu().numpy()
-        sync["downloads"] += 1
-        mark("segmentation_embedding")
-        flat = info.reshape(-1, 4)
-        cand_ok = (flat[:, 3] != 0) & (flat[:, 0] > 0)
-        train_ok = (flat[:, 3] != 0) & (TRAIN_CLEAN_DEN * flat[:, 1].astype(np.int64) >= F)
-        rows, n_train = [], []                                   # per recording: the rows that make its centroids (global rows of E, ascending)
-        for r in range(R):
+            lp_all = torch.cat([self._up(l, torch.float32) for l, x in zip(logps, xs) if x.size])
+        self._mark("pack_upload")
+        return (tab,) + self._embed_all(rec, int(rec.numel()), starts_dev, lp_all)
+
+    def _pack_rows(self, info: np.ndarray, co: np.ndarray):
+        """Per recording: the rows that make its centroids (global rows of E, ascending) and how many of them are training rows."""
+        cand_ok, train_ok = candidate_mask(info), training_mask(info, seg_frames(CHUNK))
+        rows, n_train = [], []
+        for r in range(len(co) - 1):
             a, b = N_LOCAL * int(co[r]), N_LOCAL * int(co[r + 1])
             tr = a + np.flatnonzero(train_ok[a:b])
             n_train.append(len(tr))
             rows.append(tr if len(tr) else a + np.flatnonzero(cand_ok[a:b]))      # no training row: one cluster of the candidates
-        vres = {}
-        if clustering == "vbx":
-            c32s, c64s, K_r = [], [], []
-            for r in range(R):
-                a = N_LOCAL * int(co[r])
-                if n_train[r] > 1:                              # recording by recording: its own linkage, cut and host reads
-                    v = vres[r] = vbx_cluster(eng, E_dev[a:N_LOCAL * int(co[r + 1])], self.plda_model(), threshold, rows=rows[r] - a, **vbx)
-                    c32s.append(v.cent)
-                    c64s.append(v.cent64)
-                    K_r.append(int(v.n_speakers))
-                    sync["downloads"] += 7
-                elif len(rows[r]):
-                    c32, c64 = diarize_centroids(eng, E_dev, up(rows[r].astype(np.int32)), torch.zeros(len(rows[r]), dtype=torch.int32, device=dev), 1,
-                                                 check_rows=False)
-                    c32s.append(c32)
-                    c64s.append(c64)
-                    K_r.append(1)
-                else:
-                    K_r.append(0)
-            cent_off = np.concatenate([[0], np.cumsum(K_r)]).astype(np.int64)
-            c32 = torch.cat(c32s).contiguous() if c32s else None
-            c64 = torch.cat(c64s).contiguous() if c64s else None
-        else:
-            link = [r for r in range(R) if n_train[r] > 1]
-            cuts = {}
-            if link:
-                off = np.concatenate([[0], np.cumsum([n_train[r] for r in link])]).astype(np.int64)
-                E_link = E_dev.index_select(0, up(np.concatenate([rows[r] for r in link]))).contiguous()
-                Z = eng.centroid_linkage(E_link, off).cpu().numpy()                # ONE launch for all recordings; reads status, then Z
-                sync["downloads"] += 2
-                mark("linkage")
-                for g, r in enumerate(link):
-                    cuts[r] = fcluster_distance(Z[int(off[g]) - g:int(off[g + 1]) - g - 1], threshold)
-            cut_all, sizes, cl_off, eff, cent_off = [], [], [0], [], [0]
-            for r in range(R):
-                n = len(rows[r])
-                cut = cuts[r] if r in cuts else np.zeros(n, np.int32)              # one training row, or the candidates: one cluster
-                sz = np.bincount(cut) if n else np.zeros(0, np.int64)
-                m = min(int(min_cluster_size), max(1, round(0.1 * n))) if r in cuts else 1     # cluster.fold_small_clusters, rule 1
-                cut_all.append(cut.astype(np.int64) + cl_off[-1])
-                sizes.append(sz)
-                eff.append(m)
-                cl_off.append(cl_off[-1] + len(sz))
-                cent_off.append(cent_off[-1] + (max(1, int((sz >= m).sum())) if len(sz) else 0))
-            cent_off = np.asarray(cent_off, np.int64)
-            c32 = c64 = None
-            if cl_off[-1]:
-                rows_d = up(np.concatenate(rows).astype(np.int32))
-                cut_d = up(np.concatenate(cut_all).astype(np.int32))
-                _, cut64 = diarize_centroids(eng, E_dev, rows_d, cut_d, cl_off[-1], check_rows=False)
-                _, final_d = diarize_fold_grouped(eng, cut64, np.concatenate(sizes), cl_off, eff, cent_off, cut_d)
-                sync["uploads"] += 1
-                c32, c64 = diarize_centroids(eng, E_dev, rows_d, final_d, int(cent_off[-1]), check_rows=False)
-        tab.set_clusters(cent_off)
-        sync["uploads"] += 1
-        mark("cut_fold_centroids")
+        return rows, n_train
+
+    def _pack_vbx(self, E_dev, co, rows, n_train, threshold, vbx):
+        """cluster.vbx_cluster recording by recording (its own linkage, cut and host reads) -> (c32, c64, cent_off, {recording: VbxResult})."""
+        torch = _native()[0]
+        from .cluster import vbx_cluster
+        vres, cents, K_r = {}, [], []
+        for r in range(len(rows)):
+            a, K = N_LOCAL * int(co[r]), min(len(rows[r]), 1)
+            if n_train[r] > 1:
+                v = vres[r] = vbx_cluster(self.eng, E_dev[a:N_LOCAL * int(co[r + 1])], self.plda_model(), threshold, rows=rows[r] - a, **vbx)
+                self.last_sync[-1]["downloads"] += VBX_HOST_READS
+                cents.append((v.cent, v.cent64))
+                K = int(v.n_speakers)
+            elif K:                                             # one training row, or the candidates: one cluster
+                cents.append(diarize_centroids(self.eng, E_dev, self._up(rows[r].astype(np.int32)),
+                                               torch.zeros(len(rows[r]), dtype=torch.int32, device=self.eng.device), 1, check_rows=False))
+            K_r.append(K)
+        c32, c64 = (torch.cat(c).contiguous() for c in zip(*cents)) if cents else (None, None)    # None: no recording has a cluster
+        return c32, c64, np.concatenate([[0], np.cumsum(K_r)]).astype(np.int64), vres
+
+    def _pack_ahc(self, E_dev, rows, n_train, threshold, min_cluster_size):
+        """ONE grouped linkage over the recordings with at least two training rows, the cut per recording on the host, the cut's centroids,
+        the grouped fold and the final centroids -> (c32, c64, cent_off, {}), as _pack_vbx."""
+        from .cluster import fcluster_distance
+        eng, R = self.eng, len(rows)
+        link = [r for r in range(R) if n_train[r] > 1]
+        cuts = {}
+        if link:
+            off = np.concatenate([[0], np.cumsum([n_train[r] for r in link])]).astype(np.int64)
+            E_link = E_dev.index_select(0, self._up(np.concatenate([rows[r] for r in link]))).contiguous()
+            Z = self._down(eng.centroid_linkage(E_link, off))                      # ONE launch for all recordings; reads status, then Z
+            self.last_sync[-1]["downloads"] += LINKAGE_HOST_READS
+            self._mark("linkage")
+            for g, r in enumerate(link):
+                cuts[r] = fcluster_distance(Z[int(off[g]) - g:int(off[g + 1]) - g - 1], threshold)
+        cut_all, sizes, cl_off, eff, cent_off = [], [], [0], [], [0]
+        for r in range(R):
+            n = len(rows[r])
+            cut = cuts[r] if r in cuts else np.zeros(n, np.int32)                  # one training row, or the candidates: one cluster
+            sz = np.bincount(cut) if n else np.zeros(0, np.int64)
+            m = min(int(min_cluster_size), max(1, round(0.1 * n))) if r in cuts else 1     # cluster.fold_small_clusters, rule 1
+            cut_all.append(cut.astype(np.int64) + cl_off[-1])
+            sizes.append(sz)
+            eff.append(m)
+            cl_off.append(cl_off[-1] + len(sz))
+            cent_off.append(cent_off[-1] + (max(1, int((sz >= m).sum())) if len(sz) else 0))
+        cent_off = np.asarray(cent_off, np.int64)
+        if not cl_off[-1]:
+            return None, None, cent_off, {}
+        rows_d = self._up(np.concatenate(rows).astype(np.int32))
+        cut_d = self._up(np.concatenate(cut_all).astype(np.int32))
+        _, cut64 = diarize_centroids(eng, E_dev, rows_d, cut_d, cl_off[-1], check_rows=False)
+        _, final_d = diarize_fold_grouped(eng, cut64, np.concatenate(sizes), cl_off, eff, cent_off, cut_d, upload=self._up)
+        return diarize_centroids(eng, E_dev, rows_d, final_d, int(cent_off[-1]), check_rows=False) + (cent_off, {})
+
+    def _pack_assign(self, tab, cls, info_dev, E_dev, c32, c64, constrained, max_speakers):
+        """Grouped assignment, stitching, renumbering by appearance and second stitching -> (labels, scores, cent, count, speakers) on the host."""
+        torch, eng = _native()[0], self.eng
         if c64 is None:                                          # no cluster anywhere: the kernels still get a row to point at
-            c32, c64 = torch.zeros((1, d), dtype=torch.float32, device=dev), torch.zeros((1, d), dtype=torch.float64, device=dev)
+            d = self.resnet.cfg.embed_dim
+            c32, c64 = torch.zeros((1, d), dtype=torch.float32, device=eng.device), torch.zeros((1, d), dtype=torch.float64, device=eng.device)
         lab_dev, score_dev = diarize_assign_grouped(eng, E_dev, info_dev, c64, tab, bool(constrained))
         _, spk_dev, _ = diarize_reconstruct_grouped(eng, cls, lab_dev, tab, max_speakers)
         first = diarize_first_seen(eng, spk_dev, tab)
         _, c32, c64 = diarize_renumber(eng, first, lab_dev, c32, c64, tab)         # ties in the top-2 go to the lower number: stitch again
         cnt_dev, spk_dev, _ = diarize_reconstruct_grouped(eng, cls, lab_dev, tab, max_speakers)
-        labels, scores, cent = lab_dev.cpu().numpy(), score_dev.cpu().numpy(), c32.cpu().numpy()
-        count, speakers = cnt_dev.cpu().numpy(), spk_dev.cpu().numpy()
-        sync["downloads"] += 5
-        mark("assign_stitch_download")
+        return tuple(self._down(t) for t in (lab_dev, score_dev, c32, cnt_dev, spk_dev))
+
+    def _pack_results(self, xs, pack: Pack, cent_off, info, cls, vres, labels, scores, cent, count, speakers):
+        """The pack's host arrays cut into one DiarizationResult per recording."""
         out = []
-        for r in range(R):
-            if xs[r].size == 0:
+        for r, x in enumerate(xs):
+            if x.size == 0:
                 out.append(self._empty())
                 continue
-            a, b, g0, g1, k0, k1 = (int(v) for v in (co[r], co[r + 1], pack.frame_off[r], pack.frame_off[r + 1], cent_off[r], cent_off[r + 1]))
+            a, b, g0, g1, k0, k1 = (int(v) for v in (pack.chunk_off[r], pack.chunk_off[r + 1], pack.frame_off[r], pack.frame_off[r + 1], cent_off[r], cent_off[r + 1]))
             res = DiarizationResult(turns_from_frames(speakers[g0:g1], k1 - k0), k1 - k0, cent[k0:k1].copy(), labels[a:b].copy(), count[g0:g1].copy(),
                                     speakers[g0:g1].copy(), pack.starts_local[a:b].astype(np.int64), info[a:b].copy(), cls[a:b], scores[a:b].copy())
             if r in vres:
                 res.pi, res.elbo = vres[r].pi, vres[r].elbo
             out.append(res)
-        mark("turns")
         return out
