@@ -238,14 +238,17 @@ __global__ __launch_bounds__(256) void fbank_norm_kernel(const float* __restrict
   }
   const float flo = red[0] - 80.0f;
   __syncthreads();
-  // mean over frames per mel bin: thread = (mel m, frame group g of 3)
+  // mean over frames per mel bin: thread = (mel m, frame group g of 3).  Summed as differences from the bin's first frame: a bin that is
+  // constant over the segment (digital silence: every element at the 1e-10 guard) then has a mean equal to its value and features of
+  // exactly 0 - the plain sum of T equal values divided by T is one fp32 ulp off at some T (33: 2^-17 dB in every element)
   const int m = tid % NMEL, g = tid / NMEL;
+  const float pv = fmaxf(Ls[m], flo);
   float s = 0.f;
   if (g < 3)
-    for (int t = g; t < T; t += 3) s += fmaxf(Ls[t * NMEL + m], flo);
+    for (int t = g; t < T; t += 3) s += fmaxf(Ls[t * NMEL + m], flo) - pv;
   red[tid] = s;
   __syncthreads();
-  if (tid < NMEL) mean[tid] = (red[tid] + red[tid + NMEL] + red[tid + 2 * NMEL]) / (float)T;
+  if (tid < NMEL) mean[tid] = pv + (red[tid] + red[tid + NMEL] + red[tid + 2 * NMEL]) / (float)T;
   __syncthreads();
   const int c8n = (HP ? ldf >> 1 : ldf) >> 3;
   bf16_t* out = feats + (int64_t)blockIdx.x * T * ldf;
@@ -265,8 +268,8 @@ __global__ __launch_bounds__(256) void fbank_norm_kernel(const float* __restrict
 // The same per-segment normalisation with the segment's [T x 80] log-mel tile held in LDS: ONE sweep over HBM (16-byte loads, eight in
 // flight per thread), the maximum / the means / the output all come from LDS.  The streaming form above walks global memory three
 // times with a load - wait - use loop (63 dependent round trips per sweep at T = 201); it stays for segments whose tile exceeds LDS.
-// Arithmetic (and its order per mel bin: frames g, g + 3, ... per thread, three partial sums) is the streaming form's, so the
-// features are bit-identical.
+// Arithmetic (and its order per mel bin: frames g, g + 3, ... per thread, three partial sums of the differences from frame 0) is the
+// streaming form's, so the features are bit-identical (tests/test_fbank_gpu.py holds both to one fp32 restatement at T = 480 | 481).
 constexpr int NORM_LDS_MAX_T = 480;                      // 480 x 80 x 4 B = 150 KiB
 template <bool HP, bool F16 = false>   // HP: fp16 hi | lo planes (precision 1); F16: one fp16 plane (precision 2); neither: bf16
 __global__ __launch_bounds__(256) void fbank_norm_lds_kernel(const float* __restrict__ L, int T, bf16_t* __restrict__ feats,
@@ -301,12 +304,13 @@ __global__ __launch_bounds__(256) void fbank_norm_lds_kernel(const float* __rest
   const float flo = red[0] - 80.0f;
   __syncthreads();
   const int m = tid % NMEL, g = tid / NMEL;
+  const float pv = fmaxf(tile[m], flo);                    // differences from the bin's first frame, as in the streaming form
   float s = 0.f;
   if (g < 3)
-    for (int t = g; t < T; t += 3) s += fmaxf(tile[t * NMEL + m], flo);
+    for (int t = g; t < T; t += 3) s += fmaxf(tile[t * NMEL + m], flo) - pv;
   red[tid] = s;
   __syncthreads();
-  if (tid < NMEL) mean[tid] = (red[tid] + red[tid + NMEL] + red[tid + 2 * NMEL]) / (float)T;
+  if (tid < NMEL) mean[tid] = pv + (red[tid] + red[tid + NMEL] + red[tid + 2 * NMEL]) / (float)T;
   __syncthreads();
   const int c8n = (HP ? ldf >> 1 : ldf) >> 3;
   bf16_t* out = feats + (int64_t)blockIdx.x * T * ldf;
