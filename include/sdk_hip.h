@@ -39,6 +39,7 @@
  *     sdk_diarize_assign_grouped  sdk_diarize_fold_grouped  sdk_diarize_reconstruct_grouped  sdk_diarize_first_seen  sdk_diarize_renumber
  *                                                                                                       speaker diarization (diarize.py)
  *     sdk_plda_transform  sdk_vbx_workspace_bytes  sdk_vbx  sdk_vbx_centroids                           VBx clustering (plda.py, cluster.vbx_cluster)
+ *     sdk_vbx_hmm_workspace_bytes  sdk_vbx_hmm                                                          VBx with its HMM, rows in time order (loop_prob > 0)
  *     sdk_cohort_stats_workspace_bytes  sdk_cohort_stats  sdk_affinity_topk_snorm                       adaptive score normalisation (snorm.py)
  * BUILDING BLOCKS AND KNOBS - exported for the parity tests and the A/B tools, free to change between rounds, not for binding:
  *     sdk_conv_gemm*  sdk_colstats_finish  sdk_res2net_chain*  sdk_se_*  sdk_asp_*  sdk_rows_fc  (pieces of sdk_ecapa_forward)
@@ -577,13 +578,33 @@ int sdk_diarize_renumber(sdk_ctx* ctx, const int32_t* first, const int32_t* cent
  *   sdk_vbx_centroids : gamma, pi, E, rows as above (d = E's width) -> K (one int32), keep [S] int32 (the speakers with pi > 1e-7 in
  *        their order, then -1), labels [n] int32 (or NULL: the arg-max of gamma over the kept speakers, ties to the lower), cent [S][d]
  *        fp32 and cent64 [S][d] float64 of which the first K rows are written: sum_t gamma[t][keep k] e_t in ascending row order, divided by
- *        sum_t gamma[t][keep k], divided by its norm (clamped at 1e-300) - the layout sdk_diarize_assign takes. */
+ *        sum_t gamma[t][keep k], divided by its norm (clamped at 1e-300) - the layout sdk_diarize_assign takes.
+ *   sdk_vbx_hmm : sdk_vbx with the HMM of VBx as published: the n rows are a sequence in TIME ORDER, and P = loop_prob in [0, 1) is the
+ *        probability that the speaker of row t is the speaker of row t - 1 (NaN, negative or >= 1: refused before any launch).  The
+ *        transition matrix tr[i][j] = P [i == j] + (1 - P) pi_j is never formed.  Arguments, outputs, status bits, the stop test, n_iter,
+ *        init_smoothing and the first iteration's pi = 1 / S are sdk_vbx's; per iteration, logp[t][s] = sdk_vbx's z[t][s] without ln pi_s, then
+ *        in the log domain (ln P = log(P), ln(1 - P) = log1p(-P); logaddexp(a, b) = max + log1p(exp(min - max)), which returns the other
+ *        argument exactly when one is -inf, and -inf when both are; every logsumexp with the maximum subtracted):
+ *          lf[0][s] = logp[0][s] + ln pi_s;  m[t] = logsumexp_s lf[t][s];
+ *          lf[t][s] = logp[t][s] + logaddexp(ln P + lf[t-1][s], (ln(1 - P) + ln pi_s) + m[t-1])                         (t >= 1)
+ *          lb[n-1][s] = 0;  q_s = logp[t+1][s] + lb[t+1][s];  r = logsumexp_s(ln pi_s + q_s);
+ *          lb[t][s] = logaddexp(ln P + q_s, ln(1 - P) + r)                                                              (t < n - 1)
+ *          tll = m[n-1];  gamma[t][s] = exp(lf[t][s] + lb[t][s] - tll);  elbo[ii] = tll + (Fb / 2) sum_{s,d} (ln invL - invL - alpha^2 + 1);
+ *          pi'_s = gamma[0][s] + ((1 - P) pi_s) sum_{t >= 1} exp(m[t-1] + logp[t][s] + lb[t][s] - tll);  pi = pi' / sum_s pi'_s
+ *        (pi_s == 0: ln pi_s = -inf and gamma[:, s] is exactly 0 from then on; P == 0: ln P = -inf, the mixture of sdk_vbx up to rounding).
+ *        The two passes run side by side in one launch of two single-wave workgroups, a step costing two cross-lane reductions; up to
+ *        S = 256 a lane keeps its speakers in registers, above it re-reads the rows it wrote.  Sums over rows: 64-row blocks combined in
+ *        block order, as sdk_vbx.  workspace: sdk_vbx_hmm_workspace_bytes (sdk_vbx's plus 3 n S + n doubles and the partials of pi'). */
 int sdk_plda_transform(sdk_ctx* ctx, const float* E, int d_in, const int32_t* rows, int n, const double* mean1, const double* lda,
                        const double* mean2, const double* mu, const double* Tt, int D0, int D, double* X, void* stream);
 size_t sdk_vbx_workspace_bytes(int n, int D, int S);
 int sdk_vbx(sdk_ctx* ctx, const double* X, const double* Phi, const int32_t* labels, int n, int D, int S, double Fa, double Fb, int max_iters,
             double epsilon, double init_smoothing, double* gamma, double* pi, double* elbo, int32_t* n_iter, int32_t* status, void* ws,
             size_t ws_bytes, void* stream);
+size_t sdk_vbx_hmm_workspace_bytes(int n, int D, int S);
+int sdk_vbx_hmm(sdk_ctx* ctx, const double* X, const double* Phi, const int32_t* labels, int n, int D, int S, double Fa, double Fb, int max_iters,
+                double epsilon, double init_smoothing, double loop_prob, double* gamma, double* pi, double* elbo, int32_t* n_iter,
+                int32_t* status, void* ws, size_t ws_bytes, void* stream);
 int sdk_vbx_centroids(sdk_ctx* ctx, const double* gamma, const double* pi, const float* E, const int32_t* rows, int n, int S, int d, int32_t* K,
                       int32_t* keep, int32_t* labels, float* cent, double* cent64, void* stream);
 

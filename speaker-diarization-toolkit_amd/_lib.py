@@ -159,6 +159,8 @@ SIGNATURES = {
     "sdk_plda_transform": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "sdk_vbx_workspace_bytes": (_sz, [_i, _i, _i]),
     "sdk_vbx": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f64, _f64, _i, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sdk_vbx_hmm_workspace_bytes": (_sz, [_i, _i, _i]),
+    "sdk_vbx_hmm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f64, _f64, _i, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sdk_vbx_centroids": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sdk_cohort_stats_workspace_bytes": (_sz, [_i, _i, _i]),
     "sdk_cohort_stats": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),

@@ -372,22 +372,43 @@ class Backend(EmbeddingBackend):
         sc = np.stack([parts[S][2][row] for _, S, row, _, _ in wins])
         return idx, sc, [(ri, a, b) for ri, _, _, a, b in wins]
 
+    def _ranges_plda(self, plda, d: int):
+        """The plda.Plda of cluster_ranges(clustering="vbx") for embeddings of width d: the one given, else Backend.diarizer()'s."""
+        if plda is None:
+            plda = self.diarizer().plda_model()
+        if plda.d_in != d:
+            raise ValueError(f"cluster_ranges: the PLDA model takes d_in={plda.d_in}, the embeddings have d={d}: pass plda= for this embedding family")
+        return plda
+
     def cluster_ranges(self, samples: np.ndarray, ranges: List[Tuple[float, float]], threshold: float = 0.7045654963945799,
-                       min_cluster_size: int = 12):
+                       min_cluster_size: int = 12, clustering: str = "ahc", loop_prob: float = 0.99, plda=None):      # cluster.VBX_LOOP_PROB
         """Speaker labels for a transcript's segments with no enrolled profiles: embed_ranges -> cluster.agglomerative_cluster (centroid
         linkage on the GPU, flat cut at `threshold`, clusters under min_cluster_size folded into the nearest large one).
         Returns (labels [W] int32 per window, windows [(range index, start s, end s)], range_labels [len(ranges)] int32): a range takes the
         majority label of its windows (ties -> the smaller label), -1 when it has no window.
         The default threshold and size are PyAnnote 3.1's, tuned for ITS trained ResNet34 embedding (SDK_MODEL=resnet34 with the trained
-        weights); with another family or the synthetic weights pass a threshold of your own."""
+        weights); with another family or the synthetic weights pass a threshold of your own.
+        clustering="vbx" (default "ahc", the path above): the windows, which embed_ranges returns in time order, are the sequence of a VBx
+        clustering with its HMM (cluster.vbx_cluster with loop_prob, default cluster.VBX_LOOP_PROB = 0.99: BUT's value for a 0.25-s step,
+        unpinned here).  `threshold` then cuts the linkage that only initialises it (pass cluster.VBX_AHC_THRESHOLD, 0.6); min_cluster_size is
+        not used; labels are the arg-max of gamma over the kept speakers.  plda: a plda.Plda for this family's embedding width; None takes
+        Backend.diarizer()'s ($SDK_PLDA_TRANSFORM and $SDK_PLDA, else the seeded synthetic model for the ResNet34's width).  One window:
+        label 0.  The same triple comes back."""
         if self.lite:
             raise ValueError("cluster_ranges needs the torch engine: not available with SDK_NO_TORCH=1")
-        from .cluster import agglomerative_cluster
+        if clustering not in ("ahc", "vbx"):
+            raise ValueError(f"cluster_ranges: clustering={clustering!r} (\"ahc\" or \"vbx\")")
+        from .cluster import agglomerative_cluster, vbx_cluster
         E, _, _, wins, _ = self.embed_ranges(samples, ranges)
         range_labels = np.full(len(ranges), -1, dtype=np.int32)
         if not wins:
             return np.zeros(0, np.int32), [], range_labels
-        labels = agglomerative_cluster(self.engine(), E, threshold, min_cluster_size).labels
+        if clustering == "ahc":
+            labels = agglomerative_cluster(self.engine(), E, threshold, min_cluster_size).labels
+        elif len(wins) == 1:
+            labels = np.zeros(1, np.int32)
+        else:
+            labels = vbx_cluster(self.engine(), E.contiguous(), self._ranges_plda(plda, int(E.shape[1])), threshold, loop_prob=loop_prob).labels
         per = {}
         for (ri, _, _), lab in zip(wins, labels):
             per.setdefault(ri, []).append(int(lab))

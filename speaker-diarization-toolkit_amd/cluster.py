@@ -335,6 +335,7 @@ def fold_small_clusters(E: np.ndarray, labels: np.ndarray, min_cluster_size: int
 VBX_AHC_THRESHOLD = 0.6          # the initial cut of the linkage (an over-split is what the mixture repairs)
 VBX_FA, VBX_FB, VBX_MAX_ITERS, VBX_EPSILON, VBX_INIT_SMOOTHING = 0.07, 0.8, 20, 1e-4, 7.0
 VBX_MIN_PI = 1e-7                # speakers whose weight falls to this or below have died out (the kernel's constant)
+VBX_LOOP_PROB = 0.99             # BUT's value for THEIR x-vectors at a 0.25-s step; unpinned here (no trained model on hand to tune it on)
 
 
 @dataclass
@@ -352,7 +353,7 @@ class VbxResult:
 
 
 def vbx_cluster(provider, E, plda, threshold: float = VBX_AHC_THRESHOLD, Fa: float = VBX_FA, Fb: float = VBX_FB, max_iters: int = VBX_MAX_ITERS,
-                epsilon: float = VBX_EPSILON, init_smoothing: float = VBX_INIT_SMOOTHING, rows=None) -> VbxResult:
+                epsilon: float = VBX_EPSILON, init_smoothing: float = VBX_INIT_SMOOTHING, rows=None, loop_prob: float = 0.0) -> VbxResult:
     """VBx clustering (Landini et al., BUT) of the unit rows E ([R, d] fp32 on the provider's device; rows: the ascending row numbers that
     take part, host integers, None = all), as the clustering half of PyAnnote's speaker-diarization-community-1 pipeline is stated HERE
     (written from the published description; no trained PLDA and no pyannote code is on hand: PARITY IS UNPINNED, the tests pin this rule):
@@ -360,7 +361,7 @@ def vbx_cluster(provider, E, plda, threshold: float = VBX_AHC_THRESHOLD, Fa: flo
       transform       x = the PLDA transform of every row (plda.py), float64, on the device (sdk_plda_transform)
       initialisation  Engine.centroid_linkage on the rows, cut with fcluster_distance(Z, threshold), no small-cluster fold: S canonical
                       clusters; gamma0[t, s] = softmax_s(init_smoothing [label_t == s]); pi = 1 / S
-      iteration       float64, no HMM (the loop probability is 0: the embeddings of overlapping chunks are not a chain).  With
+      iteration       float64; without the HMM at loop_prob = 0 (the embeddings of overlapping chunks are not a chain; HMM below).  With
                       rho = x sqrt(Phi), G_t = -(|x_t|^2 + D ln 2 pi) / 2, for ii = 0 .. max_iters - 1:
                         N_s = sum_t gamma[t, s];  invL[s, :] = 1 / (1 + (Fa / Fb) N_s Phi);  alpha[s, :] = (Fa / Fb) invL[s, :] sum_t gamma[t, s] rho[t, :]
                         logp[t, s] = Fa (rho_t . alpha_s - sum_d (invL[s, d] + alpha[s, d]^2) Phi_d / 2 + G_t)
@@ -369,12 +370,30 @@ def vbx_cluster(provider, E, plda, threshold: float = VBX_AHC_THRESHOLD, Fa: flo
                         ELBO = sum_t lse_t + (Fb / 2) sum_{s, d} (ln invL - invL - alpha^2 + 1);  pi = sum_t gamma / sum_{t, s} gamma
                         stop after this iteration when ii > 0 and ELBO - ELBO_prev < epsilon
                       All iterations are enqueued at once (sdk_vbx); the stop test runs on the device.
+      HMM             loop_prob = P in (0, 1) (default 0: the iteration above, unchanged): VBx as published, a Bayesian HMM over a sequence.
+                      THE ROWS MUST THEN BE IN TIME ORDER (the windows of Backend.cluster_ranges are; the (chunk, local speaker) rows of
+                      Diarizer.run are not a chain, and it passes no loop_prob).  The speaker of row t is the speaker of row t - 1 with
+                      probability P, else drawn from pi: tr[i][j] = P [i == j] + (1 - P) pi_j, never formed.  logp, invL, alpha, the
+                      ELBO's second term, the stop test and the first iteration's pi = 1 / S are as above; z, lse and gamma become, in the
+                      log domain (ln(1 - P) = log1p(-P); logaddexp(a, b) = max + log1p(exp(min - max)): an argument of -inf returns the
+                      other exactly; every logsumexp with the maximum subtracted):
+                        lf[0, s] = logp[0, s] + ln pi_s;  m_t = logsumexp_s lf[t, s]
+                        lf[t, s] = logp[t, s] + logaddexp(ln P + lf[t-1, s], (ln(1 - P) + ln pi_s) + m_{t-1})                    t >= 1
+                        lb[n-1, s] = 0;  q_s = logp[t+1, s] + lb[t+1, s];  r = logsumexp_s(ln pi_s + q_s)
+                        lb[t, s] = logaddexp(ln P + q_s, ln(1 - P) + r)                                                          t < n - 1
+                        tll = m_{n-1};  gamma[t, s] = exp(lf[t, s] + lb[t, s] - tll);  ELBO = tll + (Fb / 2) sum_{s, d} (...)
+                        pi'_s = gamma[0, s] + ((1 - P) pi_s) sum_{t >= 1} exp(m_{t-1} + logp[t, s] + lb[t, s] - tll);  pi = pi' / sum_s pi'_s
+                      (sdk_vbx_hmm: both passes in one launch, a step is two cross-lane reductions; csrc/vbx.hip).  VBX_LOOP_PROB (0.99) is
+                      BUT's value for their x-vectors at a 0.25-s step; like the rest of VBx it is unpinned here.
       result          speakers with pi > 1e-7 are kept, in their order; a kept speaker's centroid is sum_t gamma[t, k] e_t / sum_t gamma[t, k]
                       over the ORIGINAL unit rows, summed in float64 in ascending row order, re-normalised (sdk_vbx_centroids); a row's hard
                       label is the arg-max of gamma over the kept speakers, ties to the lower.
 
     Needs at least two rows.  The linkage Z is downloaded for the cut; after that one host read decides (n_iter, status, K, at the end; a
     non-finite row raises ValueError there), and the results (labels, pi, elbo, keep) are downloaded after it."""
+    loop_prob = float(loop_prob)
+    if not 0.0 <= loop_prob < 1.0:
+        raise ValueError(f"vbx_cluster: loop_prob={loop_prob} (at least 0, below 1)")                  # a NaN fails both
     R = int(E.shape[0])
     rows_h = np.arange(R, dtype=np.int64) if rows is None else np.asarray(rows, dtype=np.int64).reshape(-1)
     N = int(rows_h.size)
@@ -388,8 +407,12 @@ def vbx_cluster(provider, E, plda, threshold: float = VBX_AHC_THRESHOLD, Fa: flo
     init = fcluster_distance(Z, threshold).astype(np.int32)
     S = int(init.max()) + 1
     X = provider.plda_transform(E, rows_d, plda, check_rows=False)
-    gamma, pi, elbo, n_iter, status = provider.vbx(X, plda.device_arrays(E.device)["Phi"], torch.from_numpy(init).to(E.device), S, Fa, Fb, max_iters,
-                                                   epsilon, init_smoothing)
+    if loop_prob == 0.0:
+        gamma, pi, elbo, n_iter, status = provider.vbx(X, plda.device_arrays(E.device)["Phi"], torch.from_numpy(init).to(E.device), S, Fa, Fb, max_iters,
+                                                       epsilon, init_smoothing)
+    else:
+        gamma, pi, elbo, n_iter, status = provider.vbx_hmm(X, plda.device_arrays(E.device)["Phi"], torch.from_numpy(init).to(E.device), S, loop_prob,
+                                                           Fa, Fb, max_iters, epsilon, init_smoothing)
     K, keep, labels, cent, cent64 = provider.vbx_centroids(gamma, pi, E, rows_d, check_rows=False)
     n_it, st, Kn = (int(v) for v in torch.cat([n_iter, status, K]).cpu().numpy())       # the one read
     if st:

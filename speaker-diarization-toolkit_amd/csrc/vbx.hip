@@ -11,6 +11,8 @@
 //   vbx_mstep_kernel        block = speaker: F_s = partials in block order, invL, alpha, and the two per-speaker sums over d (fixed tree)
 //   vbx_estep_kernel        wave = 4 rows at a time, lane = speaker (lane-strided over any S): z, lse, gamma
 //   vbx_keep_kernel / vbx_labels_kernel / vbx_centroids_kernel   speakers with pi > 1e-7, the rows' hard labels, the kept speakers' centroids
+//   vbx_chain_kernel / vbx_chain_mem_kernel / vbx_hmm_post_kernel / vbx_hmm_finish_kernel   sdk_vbx_hmm: the HMM's forward and backward passes over
+//                           rows in time order, gamma and pi' (described where they stand)
 //
 // Every sum over rows runs over fixed 64-row blocks whose partials are combined in block order (the centroids: one pass in ascending row
 // order); no floating-point atomics; one owner per output element: results are bit-identical run to run.  The iterations are enqueued back to
@@ -242,6 +244,9 @@ __global__ __launch_bounds__(128) void vbx_mstep_kernel(const double* __restrict
 }
 
 // block = one 64-row block, wave = 16 of its rows, four at a time; lane = speaker, strided over any S.  z goes through the gamma buffer.
+// LOGP (sdk_vbx_hmm): `gamma` is the logp buffer; logp[t][s] = z without ln pi is stored and the softmax is left out.  LOGP = false is sdk_vbx's
+// kernel, instruction for instruction.
+template <bool LOGP>
 __global__ __launch_bounds__(VB_NT) void vbx_estep_kernel(const double* __restrict__ pi, int n, int D, int S, double Fa, double* __restrict__ gamma,
                                                           VbxWs w) {
   if (*w.done) return;
@@ -271,15 +276,16 @@ __global__ __launch_bounds__(VB_NT) void vbx_estep_kernel(const double* __restri
         for (int r = 0; r < 4; ++r) acc[r] = fma(rr[r][d], a, acc[r]);
       }
       if (act) {
-        const double c = w.cs[s], lp = log(pi[s]);                       // pi == 0: z = -inf, gamma exactly 0
+        const double c = w.cs[s], lp = LOGP ? 0.0 : log(pi[s]);          // pi == 0: z = -inf, gamma exactly 0
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const double z = Fa * (acc[r] + c + G[r]) + lp;
+          const double z = LOGP ? Fa * (acc[r] + c + G[r]) : Fa * (acc[r] + c + G[r]) + lp;
           if (r < nr) gamma[(int64_t)(ta + r) * S + s] = z;
           M[r] = fmax(M[r], z);
         }
       }
     }
+    if (LOGP) continue;
 #pragma unroll
     for (int r = 0; r < 4; ++r) M[r] = wave_max_d(M[r]);
     double sum[4] = {0.0, 0.0, 0.0, 0.0};
@@ -375,6 +381,255 @@ __global__ __launch_bounds__(VB_NT) void vbx_centroids_kernel(const double* __re
   }
 }
 
+// ---- the HMM of sdk_vbx_hmm: logp [n][S] (vbx_estep_kernel<true>), the forward and backward chains, gamma and the partials of pi'
+//
+//   vbx_chain_kernel<K>     ONE launch of two blocks of one wave: block 0 the forward pass, block 1 the backward pass, side by side.  Lane l holds
+//                           speakers l, l + 64, .. in K registers (S <= 64 K, K <= VH_MAXK: S <= 256); a step is two cross-lane reductions (the
+//                           maximum, the sum of exponentials: DPP inside a row of 16 lanes, then the four rows through v_readlane), no barrier,
+//                           no LDS and no load the recurrence waits for: the logp rows, which do not depend on it, are loaded VH_PF .. 2 VH_PF
+//                           steps ahead into two register buffers.  lf, lb [n][S] and m [n] leave by plain vector stores.
+//   vbx_chain_mem_kernel    the same passes for S > 256: a lane's speakers do not fit its registers, so it re-reads the previous row of lf / lb,
+//                           of which it wrote every element it reads (no other lane's stores are read: no fence), three sweeps per step.
+//   vbx_hmm_post_kernel     block = 64-row block, thread = speaker: gamma, and the block's partial of sum_{t >= 1} exp(m[t-1] + logp + lb - tll)
+//                           in ascending row order
+//   vbx_hmm_finish_kernel   one block: N_s and pi' from the partials in block order, the ELBO, the stop test, n_iter and pi
+// Reduction orders: per lane over its registers ascending, then lanes l ^ 1, l ^ 2, l ^ 4, l ^ 8 (the xor butterfly), then rows (0 + 1) + (2 + 3).
+struct VbxHmmWs {
+  double *logp, *lf, *lb, *m, *pipart, *pinew;
+};
+
+constexpr int VH_PF = 4;             // logp rows per register buffer of the chain (two buffers: a row is loaded 4 .. 8 steps before its use; the
+                                     // step is unrolled 2 VH_PF times per direction, and at K = 4 that is the instruction cache's 64 KB)
+constexpr int VH_MAXK = 4;           // speakers per lane that the chain holds in registers: S <= 256
+
+// the value of lane DPP(l) in every lane; CTRL permutes inside rows of 16 lanes, so every lane reads a live one
+template <int CTRL>
+__device__ __forceinline__ double dpp_d(double v) {
+  const int lo = __double2loint(v), hi = __double2hiint(v);
+  return __hiloint2double(__builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xF, 0xF, false), __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xF, 0xF, false));
+}
+
+__device__ __forceinline__ double lane_d(double v, int l) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+
+// quad_perm [1,0,3,2] and [2,3,0,1] are l ^ 1 and l ^ 2; after them a quad is uniform, so row_half_mirror (l -> 7 - l) reads what l ^ 4 holds, and
+// row_mirror (l -> 15 - l) what l ^ 8 holds.  Whole wave active, uniform control flow only.
+__device__ __forceinline__ double chain_max(double v) {
+  v = fmax(v, dpp_d<0xB1>(v));
+  v = fmax(v, dpp_d<0x4E>(v));
+  v = fmax(v, dpp_d<0x141>(v));
+  v = fmax(v, dpp_d<0x140>(v));
+  return fmax(fmax(lane_d(v, 0), lane_d(v, 16)), fmax(lane_d(v, 32), lane_d(v, 48)));
+}
+
+__device__ __forceinline__ double chain_sum(double v) {
+  v += dpp_d<0xB1>(v);
+  v += dpp_d<0x4E>(v);
+  v += dpp_d<0x141>(v);
+  v += dpp_d<0x140>(v);
+  return (lane_d(v, 0) + lane_d(v, 16)) + (lane_d(v, 32) + lane_d(v, 48));
+}
+
+// ln(e^a + e^b) = max + log1p(exp(min - max)); -inf with a finite other argument returns that argument exactly; both -inf: -inf
+__device__ __forceinline__ double logaddexp_d(double a, double b) {
+  const double hi = fmax(a, b), lo = fmin(a, b);
+  return hi == -HUGE_VAL ? hi : hi + log1p(exp(lo - hi));
+}
+
+// logsumexp over the wave's K registers per lane, the maximum subtracted
+template <int K>
+__device__ __forceinline__ double chain_lse(const double (&u)[K]) {
+  double mx = u[0];
+#pragma unroll
+  for (int k = 1; k < K; ++k) mx = fmax(mx, u[k]);
+  mx = chain_max(mx);
+  double sum = 0.0;
+#pragma unroll
+  for (int k = 0; k < K; ++k) sum += exp(u[k] - mx);
+  return mx + log(chain_sum(sum));
+}
+
+// row min(max(t, 0), n - 1) of logp: lane's K speakers; 0 for a speaker past S (whose ln pi is -inf)
+template <int K>
+__device__ __forceinline__ void chain_load(const double* __restrict__ logp, int t, int n, int S, int lane, double (&dst)[K]) {
+  const double* row = logp + (int64_t)min(max(t, 0), n - 1) * S;
+#pragma unroll
+  for (int k = 0; k < K; ++k) dst[k] = lane + 64 * k < S ? row[lane + 64 * k] : 0.0;
+}
+
+template <int K>
+__global__ __launch_bounds__(64) void vbx_chain_kernel(const double* __restrict__ pi, int n, int S, double lnP, double ln1mP, VbxWs w, VbxHmmWs h) {
+  if (*w.done) return;
+  const int lane = threadIdx.x;
+  const double* __restrict__ logp = h.logp;
+  double lnpi[K], x[K], u[K], A[VH_PF][K], B[VH_PF][K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) lnpi[k] = lane + 64 * k < S ? log(pi[lane + 64 * k]) : -HUGE_VAL;      // pi == 0: -inf
+  if (blockIdx.x == 0) {
+    // forward: x = lf[t - 1]
+    double* __restrict__ lf = h.lf;
+    double c[K];
+    chain_load<K>(logp, 0, n, S, lane, u);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      c[k] = ln1mP + lnpi[k];
+      x[k] = u[k] + lnpi[k];
+      if (lane + 64 * k < S) lf[lane + 64 * k] = x[k];
+    }
+    auto step = [&](const double (&lp)[K], int t) {
+      const double m = chain_lse<K>(x);
+      if (lane == 0) h.m[t - 1] = m;
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        x[k] = lp[k] + logaddexp_d(lnP + x[k], c[k] + m);
+        if (lane + 64 * k < S) lf[(int64_t)t * S + lane + 64 * k] = x[k];
+      }
+    };
+#pragma unroll
+    for (int j = 0; j < VH_PF; ++j) chain_load<K>(logp, 1 + j, n, S, lane, A[j]);
+    for (int t0 = 1; t0 < n; t0 += 2 * VH_PF) {                           // t0 and n are wave-uniform
+#pragma unroll
+      for (int j = 0; j < VH_PF; ++j) chain_load<K>(logp, t0 + VH_PF + j, n, S, lane, B[j]);
+#pragma unroll
+      for (int j = 0; j < VH_PF; ++j)
+        if (t0 + j < n) step(A[j], t0 + j);
+#pragma unroll
+      for (int j = 0; j < VH_PF; ++j) chain_load<K>(logp, t0 + 2 * VH_PF + j, n, S, lane, A[j]);
+#pragma unroll
+      for (int j = 0; j < VH_PF; ++j)
+        if (t0 + VH_PF + j < n) step(B[j], t0 + VH_PF + j);
+    }
+    const double m = chain_lse<K>(x);
+    if (lane == 0) h.m[n - 1] = m;                                        // tll
+  } else {
+    // backward: x = lb[t + 1], lp = logp[t + 1]
+    double* __restrict__ lb = h.lb;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      x[k] = 0.0;
+      if (lane + 64 * k < S) lb[(int64_t)(n - 1) * S + lane + 64 * k] = 0.0;
+    }
+    auto step = [&](const double (&lp)[K], int t) {
+      double q[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        q[k] = lp[k] + x[k];
+        u[k] = lnpi[k] + q[k];
+      }
+      const double r = ln1mP + chain_lse<K>(u);
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        x[k] = logaddexp_d(lnP + q[k], r);
+        if (lane + 64 * k < S) lb[(int64_t)t * S + lane + 64 * k] = x[k];
+      }
+    };
+#pragma unroll
+    for (int j = 0; j < VH_PF; ++j) chain_load<K>(logp, n - 1 - j, n, S, lane, A[j]);
+    for (int t0 = n - 2; t0 >= 0; t0 -= 2 * VH_PF) {                      // step j of a buffer: row t = t0 - j, reading logp[t + 1]
+#pragma unroll
+      for (int j = 0; j < VH_PF; ++j) chain_load<K>(logp, t0 - VH_PF - j + 1, n, S, lane, B[j]);
+#pragma unroll
+      for (int j = 0; j < VH_PF; ++j)
+        if (t0 - j >= 0) step(A[j], t0 - j);
+#pragma unroll
+      for (int j = 0; j < VH_PF; ++j) chain_load<K>(logp, t0 - 2 * VH_PF - j + 1, n, S, lane, A[j]);
+#pragma unroll
+      for (int j = 0; j < VH_PF; ++j)
+        if (t0 - VH_PF - j >= 0) step(B[j], t0 - VH_PF - j);
+    }
+  }
+}
+
+// S > 256.  lf and lb are read back by the lane that wrote them, through the pointer that wrote them.
+__global__ __launch_bounds__(64) void vbx_chain_mem_kernel(const double* __restrict__ pi, int n, int S, double lnP, double ln1mP, VbxWs w, VbxHmmWs h) {
+  if (*w.done) return;
+  const int lane = threadIdx.x;
+  const double* __restrict__ logp = h.logp;
+  const double ninf = -HUGE_VAL;
+  if (blockIdx.x == 0) {
+    double* lf = h.lf;
+    for (int s = lane; s < S; s += 64) lf[s] = logp[s] + log(pi[s]);
+    for (int t = 1; t <= n; ++t) {
+      const double* prev = lf + (int64_t)(t - 1) * S;
+      double mx = ninf, sum = 0.0;
+      for (int s = lane; s < S; s += 64) mx = fmax(mx, prev[s]);
+      mx = chain_max(mx);
+      for (int s = lane; s < S; s += 64) sum += exp(prev[s] - mx);
+      const double m = mx + log(chain_sum(sum));
+      if (lane == 0) h.m[t - 1] = m;
+      if (t == n) break;
+      for (int s = lane; s < S; s += 64)
+        lf[(int64_t)t * S + s] = logp[(int64_t)t * S + s] + logaddexp_d(lnP + prev[s], (ln1mP + log(pi[s])) + m);
+    }
+  } else {
+    double* lb = h.lb;
+    for (int s = lane; s < S; s += 64) lb[(int64_t)(n - 1) * S + s] = 0.0;
+    for (int t = n - 2; t >= 0; --t) {
+      const double* nx = lb + (int64_t)(t + 1) * S;
+      const double* lp = logp + (int64_t)(t + 1) * S;
+      double mx = ninf, sum = 0.0;
+      for (int s = lane; s < S; s += 64) mx = fmax(mx, log(pi[s]) + (lp[s] + nx[s]));
+      mx = chain_max(mx);
+      for (int s = lane; s < S; s += 64) sum += exp(log(pi[s]) + (lp[s] + nx[s]) - mx);
+      const double r = ln1mP + (mx + log(chain_sum(sum)));
+      for (int s = lane; s < S; s += 64) lb[(int64_t)t * S + s] = logaddexp_d(lnP + (lp[s] + nx[s]), r);
+    }
+  }
+}
+
+__global__ __launch_bounds__(VB_NT) void vbx_hmm_post_kernel(int n, int S, double* __restrict__ gamma, VbxWs w, VbxHmmWs h) {
+  if (*w.done) return;
+  const int b = blockIdx.x, t0 = b * VB_ROWS, m = min(VB_ROWS, n - t0);
+  const double tll = h.m[n - 1];
+  for (int s = threadIdx.x; s < S; s += VB_NT) {
+    double acc = 0.0;
+    for (int i = 0; i < m; ++i) {
+      const int t = t0 + i;
+      const int64_t o = (int64_t)t * S + s;
+      const double lb = h.lb[o];
+      gamma[o] = exp(h.lf[o] + lb - tll);
+      if (t > 0) acc += exp(h.m[t - 1] + h.logp[o] + lb - tll);
+    }
+    h.pipart[(int64_t)b * S + s] = acc;
+  }
+}
+
+// one block, as vbx_finish_kernel with ii >= 0: ELBO = tll + the M step's sum; pi' = gamma[0] + (1 - P) pi (the partials in block order)
+__global__ __launch_bounds__(VB_NT) void vbx_hmm_finish_kernel(int nblk, int n, int S, int ii, double epsilon, double loop_prob,
+                                                               const double* __restrict__ gamma, double* __restrict__ pi,
+                                                               double* __restrict__ elbo, int32_t* __restrict__ n_iter,
+                                                               int32_t* __restrict__ status, VbxWs w, VbxHmmWs h) {
+  __shared__ double s_tot;
+  if (*w.done) return;
+  const int tid = threadIdx.x;
+  for (int s = tid; s < S; s += VB_NT) {
+    double a = 0.0, p = 0.0;
+#pragma unroll 8
+    for (int b = 0; b < nblk; ++b) a += w.Npart[(int64_t)b * S + s];
+#pragma unroll 8
+    for (int b = 0; b < nblk; ++b) p += h.pipart[(int64_t)b * S + s];
+    w.N[s] = a;
+    h.pinew[s] = gamma[s] + ((1.0 - loop_prob) * pi[s]) * p;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double e2 = 0.0, tot = 0.0;
+    for (int s = 0; s < S; ++s) e2 += w.es[s];
+    for (int s = 0; s < S; ++s) tot += h.pinew[s];
+    const double v = h.m[n - 1] + e2;
+    elbo[ii] = v;
+    *n_iter = ii + 1;
+    s_tot = tot;
+    const bool fin = isfinite(v);
+    if (!fin) atomicOr(status, VB_ST_ELBO);
+    if (!fin || (ii > 0 && v - *w.prev < epsilon)) *w.done = 1;
+    *w.prev = v;
+  }
+  __syncthreads();
+  for (int s = tid; s < S; s += VB_NT) pi[s] = h.pinew[s] / s_tot;
+}
+
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 bool vbx_shape_ok(int n, int D, int S) { return n >= 1 && n <= VB_MAX_ROWS && (D == 64 || D == 128) && S >= 1 && S <= VB_MAX_ROWS; }
@@ -397,6 +652,21 @@ size_t vbx_carve(char* base, int n, int D, int S, VbxWs* w) {
   double* prev = take(1);
   int32_t* done = reinterpret_cast<int32_t*>(take(1));
   if (w) *w = VbxWs{rho, G, lse, Npart, Fpart, lsepart, N, alphaT, cs, es, prev, done};
+  return o;
+}
+
+// sdk_vbx_hmm's workspace: sdk_vbx's, then the chain's
+size_t vbx_hmm_carve(char* base, int n, int D, int S, VbxWs* w, VbxHmmWs* h) {
+  const size_t nblk = (size_t)(n + VB_ROWS - 1) / VB_ROWS;
+  size_t o = vbx_carve(base, n, D, S, w);
+  auto take = [&](size_t doubles) { char* p = base + o; o += align256(doubles * sizeof(double)); return reinterpret_cast<double*>(p); };
+  double* logp = take((size_t)n * S);
+  double* lf = take((size_t)n * S);
+  double* lb = take((size_t)n * S);
+  double* m = take(n);
+  double* pipart = take(nblk * S);
+  double* pinew = take(S);
+  if (h) *h = VbxHmmWs{logp, lf, lb, m, pipart, pinew};
   return o;
 }
 
@@ -457,9 +727,70 @@ extern "C" int sdk_vbx(sdk_ctx* ctx, const double* X, const double* Phi, const i
   hipLaunchKernelGGL(vbx_finish_kernel, dim3(1), dim3(VB_NT), 0, st, nblk, S, -1, epsilon, pi, elbo, n_iter, status, w);
   for (int ii = 0; ii < max_iters; ++ii) {
     hipLaunchKernelGGL(vbx_mstep_kernel, dim3(S), dim3(D), 0, st, Phi, nblk, D, S, Fa, Fb, w);
-    hipLaunchKernelGGL(vbx_estep_kernel, dim3(nblk), dim3(VB_NT), 0, st, pi, n, D, S, Fa, gamma, w);
+    hipLaunchKernelGGL(vbx_estep_kernel<false>, dim3(nblk), dim3(VB_NT), 0, st, pi, n, D, S, Fa, gamma, w);
     hipLaunchKernelGGL(vbx_stats_kernel, gstats, dim3(D), 0, st, gamma, n, D, S, 1, w);
     hipLaunchKernelGGL(vbx_finish_kernel, dim3(1), dim3(VB_NT), 0, st, nblk, S, ii, epsilon, pi, elbo, n_iter, status, w);
+  }
+  SDK_LAUNCH_CHECK();
+  return 0;
+}
+
+// the chain's launch: speakers in registers up to S = 64 VH_MAXK, the memory form above
+static void vbx_chain_launch(hipStream_t st, const double* pi, int n, int S, double lnP, double ln1mP, const VbxWs& w, const VbxHmmWs& h) {
+  const int K = (S + 63) / 64;
+  static_assert(VH_MAXK == 4, "one instantiation per K");
+  if (K == 1) hipLaunchKernelGGL(vbx_chain_kernel<1>, dim3(2), dim3(64), 0, st, pi, n, S, lnP, ln1mP, w, h);
+  else if (K == 2) hipLaunchKernelGGL(vbx_chain_kernel<2>, dim3(2), dim3(64), 0, st, pi, n, S, lnP, ln1mP, w, h);
+  else if (K == 3) hipLaunchKernelGGL(vbx_chain_kernel<3>, dim3(2), dim3(64), 0, st, pi, n, S, lnP, ln1mP, w, h);
+  else if (K == 4) hipLaunchKernelGGL(vbx_chain_kernel<4>, dim3(2), dim3(64), 0, st, pi, n, S, lnP, ln1mP, w, h);
+  else hipLaunchKernelGGL(vbx_chain_mem_kernel, dim3(2), dim3(64), 0, st, pi, n, S, lnP, ln1mP, w, h);
+}
+
+extern "C" size_t sdk_vbx_hmm_workspace_bytes(int n, int D, int S) {
+  if (!vbx_shape_ok(n, D, S)) {
+    sdk_set_error("sdk_vbx_hmm_workspace_bytes: n=%d D=%d S=%d (n and S 1 .. %d, D 64 or 128)", n, D, S, VB_MAX_ROWS);
+    return 0;
+  }
+  return vbx_hmm_carve(nullptr, n, D, S, nullptr, nullptr);
+}
+
+extern "C" int sdk_vbx_hmm(sdk_ctx* ctx, const double* X, const double* Phi, const int32_t* labels, int n, int D, int S, double Fa, double Fb,
+                           int max_iters, double epsilon, double init_smoothing, double loop_prob, double* gamma, double* pi, double* elbo,
+                           int32_t* n_iter, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  SDK_REQUIRE(loop_prob >= 0.0 && loop_prob < 1.0, "sdk_vbx_hmm: loop_prob=%g (at least 0, below 1)", loop_prob);      // a NaN fails both
+  SDK_REQUIRE(ctx, "sdk_vbx_hmm: null context");
+  SDK_REQUIRE(n >= 1 && n <= VB_MAX_ROWS, "sdk_vbx_hmm: n=%d (1 .. %d)", n, VB_MAX_ROWS);
+  SDK_REQUIRE(D == 64 || D == 128, "sdk_vbx_hmm: D=%d not supported (64 or 128)", D);
+  SDK_REQUIRE(S >= 1 && S <= VB_MAX_ROWS, "sdk_vbx_hmm: S=%d (1 .. %d)", S, VB_MAX_ROWS);
+  SDK_REQUIRE(max_iters >= 1 && max_iters <= 1000, "sdk_vbx_hmm: max_iters=%d (1 .. 1000)", max_iters);
+  SDK_REQUIRE(Fa > 0.0 && Fb > 0.0 && isfinite(Fa) && isfinite(Fb), "sdk_vbx_hmm: Fa=%g Fb=%g (positive and finite)", Fa, Fb);
+  SDK_REQUIRE(epsilon == epsilon, "sdk_vbx_hmm: epsilon is NaN");
+  SDK_REQUIRE(init_smoothing >= 0.0 && isfinite(init_smoothing), "sdk_vbx_hmm: init_smoothing=%g (finite, at least 0)", init_smoothing);
+  SDK_REQUIRE(X && Phi && labels && gamma && pi && elbo && n_iter && status && ws,
+              "sdk_vbx_hmm: null argument (X=%p Phi=%p labels=%p gamma=%p pi=%p elbo=%p n_iter=%p status=%p ws=%p)", (const void*)X, (const void*)Phi,
+              (const void*)labels, (void*)gamma, (void*)pi, (void*)elbo, (void*)n_iter, (void*)status, ws);
+  const size_t need = vbx_hmm_carve(nullptr, n, D, S, nullptr, nullptr);
+  SDK_REQUIRE(ws_bytes >= need, "sdk_vbx_hmm: workspace of %zu bytes, %zu needed", ws_bytes, need);
+  SDK_REQUIRE(((uintptr_t)ws & 255) == 0, "sdk_vbx_hmm: ws=%p must be 256-byte aligned", ws);
+  VbxWs w;
+  VbxHmmWs h;
+  vbx_hmm_carve(static_cast<char*>(ws), n, D, S, &w, &h);
+  const int nblk = (n + VB_ROWS - 1) / VB_ROWS;
+  const double lnP = log(loop_prob), ln1mP = log1p(-loop_prob);          // loop_prob == 0: -inf and 0
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 gstats(nblk, (S + VB_SC - 1) / VB_SC);
+  ProfScope ps(ctx, stream, SDK_K_COPY, 4.0 * max_iters * (double)n * S * D, 16.0 * max_iters * (double)n * (4.0 * S + D));
+  hipLaunchKernelGGL(vbx_reset_kernel, dim3(1), dim3(64), 0, st, S, max_iters, pi, elbo, n_iter, status, w);
+  hipLaunchKernelGGL(vbx_init_kernel, dim3((n + 3) / 4), dim3(VB_NT), 0, st, X, Phi, labels, n, D, S, init_smoothing, gamma, status, w);
+  hipLaunchKernelGGL(vbx_stats_kernel, gstats, dim3(D), 0, st, gamma, n, D, S, 0, w);
+  hipLaunchKernelGGL(vbx_finish_kernel, dim3(1), dim3(VB_NT), 0, st, nblk, S, -1, epsilon, pi, elbo, n_iter, status, w);
+  for (int ii = 0; ii < max_iters; ++ii) {
+    hipLaunchKernelGGL(vbx_mstep_kernel, dim3(S), dim3(D), 0, st, Phi, nblk, D, S, Fa, Fb, w);
+    hipLaunchKernelGGL(vbx_estep_kernel<true>, dim3(nblk), dim3(VB_NT), 0, st, pi, n, D, S, Fa, h.logp, w);
+    vbx_chain_launch(st, pi, n, S, lnP, ln1mP, w, h);
+    hipLaunchKernelGGL(vbx_hmm_post_kernel, dim3(nblk), dim3(VB_NT), 0, st, n, S, gamma, w, h);
+    hipLaunchKernelGGL(vbx_stats_kernel, gstats, dim3(D), 0, st, gamma, n, D, S, 0, w);
+    hipLaunchKernelGGL(vbx_hmm_finish_kernel, dim3(1), dim3(VB_NT), 0, st, nblk, n, S, ii, epsilon, loop_prob, gamma, pi, elbo, n_iter, status, w, h);
   }
   SDK_LAUNCH_CHECK();
   return 0;

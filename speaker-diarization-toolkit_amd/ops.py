@@ -836,28 +836,41 @@ class Engine:
             epsilon: float = 1e-4, init_smoothing: float = 7.0):
         """X [n, D] float64, Phi [D] float64, labels [n] int32 in [0, S) (all on the device) -> (gamma [n, S], pi [S], elbo [max_iters],
         n_iter [1] int32, status [1] int32), all on the device and not read back: sdk_vbx.  The caller reads n_iter and status once."""
+        return self._vbx("vbx", None, X, Phi, labels, S, Fa, Fb, max_iters, epsilon, init_smoothing)
+
+    def vbx_hmm(self, X: torch.Tensor, Phi: torch.Tensor, labels: torch.Tensor, S: int, loop_prob: float, Fa: float = 0.07, Fb: float = 0.8,
+                max_iters: int = 20, epsilon: float = 1e-4, init_smoothing: float = 7.0):
+        """vbx with the HMM: the rows of X are a sequence in time order and loop_prob in [0, 1) is the probability that a row keeps the speaker
+        of the row before it (sdk_vbx_hmm).  The same five device tensors."""
+        loop_prob = float(loop_prob)
+        if not 0.0 <= loop_prob < 1.0:                                    # a NaN fails both
+            raise ValueError(f"vbx_hmm: loop_prob={loop_prob} (at least 0, below 1)")
+        return self._vbx("vbx_hmm", loop_prob, X, Phi, labels, S, Fa, Fb, max_iters, epsilon, init_smoothing)
+
+    def _vbx(self, who, loop_prob, X, Phi, labels, S, Fa, Fb, max_iters, epsilon, init_smoothing):
         if X.dim() != 2 or X.dtype != torch.float64 or not X.is_contiguous() or not X.is_cuda:
-            raise ValueError(f"vbx: X must be a contiguous float64 [n, D] device tensor, got {tuple(X.shape)} {X.dtype}")
+            raise ValueError(f"{who}: X must be a contiguous float64 [n, D] device tensor, got {tuple(X.shape)} {X.dtype}")
         n, D = int(X.shape[0]), int(X.shape[1])
         if D not in (64, 128):
-            raise ValueError(f"vbx: D={D} not supported (64 or 128)")
+            raise ValueError(f"{who}: D={D} not supported (64 or 128)")
         if n < 1 or n > 65536:
-            raise ValueError(f"vbx: n={n} rows (1 .. 65536)")
+            raise ValueError(f"{who}: n={n} rows (1 .. 65536)")
         if Phi.dtype != torch.float64 or tuple(Phi.shape) != (D,) or not Phi.is_contiguous() or not Phi.is_cuda:
-            raise ValueError(f"vbx: Phi must be a contiguous float64 [{D}] device tensor, got {tuple(Phi.shape)} {Phi.dtype}")
+            raise ValueError(f"{who}: Phi must be a contiguous float64 [{D}] device tensor, got {tuple(Phi.shape)} {Phi.dtype}")
         if labels.dtype != torch.int32 or tuple(labels.shape) != (n,) or not labels.is_contiguous() or not labels.is_cuda:
-            raise ValueError(f"vbx: labels must be a contiguous int32 [{n}] device tensor, got {tuple(labels.shape)} {labels.dtype}")
+            raise ValueError(f"{who}: labels must be a contiguous int32 [{n}] device tensor, got {tuple(labels.shape)} {labels.dtype}")
         S, max_iters = int(S), int(max_iters)
         if S < 1 or S > 65536:
-            raise ValueError(f"vbx: S={S} (1 .. 65536)")
+            raise ValueError(f"{who}: S={S} (1 .. 65536)")
         if max_iters < 1 or max_iters > 1000:
-            raise ValueError(f"vbx: max_iters={max_iters} (1 .. 1000)")
+            raise ValueError(f"{who}: max_iters={max_iters} (1 .. 1000)")
         Fa, Fb, epsilon, init_smoothing = float(Fa), float(Fb), float(epsilon), float(init_smoothing)
         if not (0 < Fa < np.inf and 0 < Fb < np.inf) or epsilon != epsilon or not (0 <= init_smoothing < np.inf):
-            raise ValueError(f"vbx: Fa={Fa} Fb={Fb} (positive, finite), epsilon={epsilon} (not NaN), init_smoothing={init_smoothing} (finite, >= 0)")
-        nbytes = self.lib.sdk_vbx_workspace_bytes(n, D, S)
+            raise ValueError(f"{who}: Fa={Fa} Fb={Fb} (positive, finite), epsilon={epsilon} (not NaN), init_smoothing={init_smoothing} (finite, >= 0)")
+        sizer = "sdk_vbx_workspace_bytes" if loop_prob is None else "sdk_vbx_hmm_workspace_bytes"
+        nbytes = getattr(self.lib, sizer)(n, D, S)
         if nbytes == 0:
-            raise SdkError(f"sdk_vbx_workspace_bytes: {self.lib.sdk_last_error().decode()}")
+            raise SdkError(f"{sizer}: {self.lib.sdk_last_error().decode()}")
         dev = X.device
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         gamma = torch.empty((n, S), dtype=torch.float64, device=dev)
@@ -865,9 +878,12 @@ class Engine:
         elbo = torch.empty((max_iters,), dtype=torch.float64, device=dev)
         n_iter = torch.empty((1,), dtype=torch.int32, device=dev)
         status = torch.empty((1,), dtype=torch.int32, device=dev)
-        check(self.lib.sdk_vbx(self.ctx, X.data_ptr(), Phi.data_ptr(), labels.data_ptr(), n, D, S, Fa, Fb, max_iters, epsilon, init_smoothing,
-                               gamma.data_ptr(), pi.data_ptr(), elbo.data_ptr(), n_iter.data_ptr(), status.data_ptr(), ws.data_ptr(), nbytes,
-                               _stream()), "sdk_vbx")
+        head = (self.ctx, X.data_ptr(), Phi.data_ptr(), labels.data_ptr(), n, D, S, Fa, Fb, max_iters, epsilon, init_smoothing)
+        tail = (gamma.data_ptr(), pi.data_ptr(), elbo.data_ptr(), n_iter.data_ptr(), status.data_ptr(), ws.data_ptr(), nbytes, _stream())
+        if loop_prob is None:
+            check(self.lib.sdk_vbx(*head, *tail), "sdk_vbx")
+        else:
+            check(self.lib.sdk_vbx_hmm(*head, loop_prob, *tail), "sdk_vbx_hmm")
         return gamma, pi, elbo, n_iter, status
 
     def vbx_centroids(self, gamma: torch.Tensor, pi: torch.Tensor, E: torch.Tensor, rows: torch.Tensor, check_rows: bool = True):
