@@ -41,6 +41,7 @@
  *     sdk_plda_transform  sdk_vbx_workspace_bytes  sdk_vbx  sdk_vbx_centroids                           VBx clustering (plda.py, cluster.vbx_cluster)
  *     sdk_vbx_hmm_workspace_bytes  sdk_vbx_hmm                                                          VBx with its HMM, rows in time order (loop_prob > 0)
  *     sdk_cohort_stats_workspace_bytes  sdk_cohort_stats  sdk_affinity_topk_snorm                       adaptive score normalisation (snorm.py)
+ *     sdk_kmeans_rows_workspace_bytes  sdk_kmeans_rows                                                  spherical k-means on unit rows (cluster.kmeans_cluster)
  * BUILDING BLOCKS AND KNOBS - exported for the parity tests and the A/B tools, free to change between rounds, not for binding:
  *     sdk_conv_gemm*  sdk_colstats_finish  sdk_res2net_chain*  sdk_se_*  sdk_asp_*  sdk_rows_fc  (pieces of sdk_ecapa_forward)
  *     sdk_resnet_conv2d  (piece of sdk_resnet_forward)  sdk_resnet_masked_pool  (piece of sdk_resnet_forward_masked)
@@ -607,6 +608,29 @@ int sdk_vbx_hmm(sdk_ctx* ctx, const double* X, const double* Phi, const int32_t*
                 int32_t* status, void* ws, size_t ws_bytes, void* stream);
 int sdk_vbx_centroids(sdk_ctx* ctx, const double* gamma, const double* pi, const float* E, const int32_t* rows, int n, int S, int d, int32_t* K,
                       int32_t* keep, int32_t* labels, float* cent, double* cent64, void* stream);
+
+/* ---- spherical k-means on unit rows (cluster.kmeans_cluster; csrc/kmeans.hip): the forced speaker count of the diarization (`speakers=`) with
+ *      clustering="vbx".  float64 arithmetic, no floating-point atomics, one owner per output element, every sum in one fixed order:
+ *      bit-identical run to run.  n <= 65 536 rows, d a multiple of 64 up to 512, 1 <= k <= min(n, 64).
+ *   sdk_kmeans_rows : E [R][d] fp32 unit rows, rows [n] int32 ascending (rows of E; must lie inside E: the library does not read them back
+ *        to check) -> labels [n] int32 in [0, k) (NOT canonical; a centre may end without rows), n_iter and status (one int32 each), all on
+ *        the device.  Row t below is E[rows[t]].
+ *          seeding     centre 0 = row 0; centre j = the row whose largest cosine to the centres 0 .. j - 1 is least, ties to the lowest row.
+ *                      A seed is a row, so each cosine is a sum of exact products, added over the columns in ascending order.
+ *          assignment  label[t] = argmax_c <centre c, row t>: each cosine one float64 fma chain over the columns in ascending order; ties to
+ *                      the lower centre; a NaN never wins.
+ *          update      s_c = the float64 sum of the rows labelled c: per segment of 1024 rows (rows t = 1024 g .. 1024 g + 1023) in
+ *                      ascending order, then the segments' partials in segment order; centre c = s_c / |s_c|.  A centre without rows, or
+ *                      with |s_c| = 0, stays as it was.
+ *          stop        iteration it = 0, 1, ..: assignment, then update.  The loop ends after the first assignment with it >= 1 that
+ *                      changed no label, or after max_iters (1 .. 1000) assignments; n_iter counts the assignments made and labels are
+ *                      those of the last one.
+ *        Every iteration is enqueued; the stop test runs on the device and the launches after the stop leave every output untouched.
+ *        status: 0, or 1 (a non-finite value in a row: nothing ran, n_iter = 0, labels = -1).  The host reads n_iter and status once,
+ *        after the call.  workspace: sdk_kmeans_rows_workspace_bytes (0 for arguments sdk_kmeans_rows would refuse), 256-byte aligned. */
+size_t sdk_kmeans_rows_workspace_bytes(int n, int d, int k);
+int sdk_kmeans_rows(sdk_ctx* ctx, const float* E, const int32_t* rows, int n, int d, int k, int max_iters, int32_t* labels, int32_t* n_iter,
+                    int32_t* status, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- adaptive score normalisation against a cohort (AS-norm; snorm.py, csrc/snorm.hip).  E [N][d], P [Pn][d] and Cn [M][d] are unit fp32 rows,
  *      16-byte aligned; d a multiple of 64, at most 512.  Scores are fp32 dot products on the fp32-input MFMA: one fused-multiply-add chain over

@@ -192,6 +192,8 @@ SIGNATURES = {
     "sdk_chol_inverse": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "sdk_kmeans_mindist": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
     "sdk_kmeans_assign": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sdk_kmeans_rows_workspace_bytes": (_sz, [_i, _i, _i]),
+    "sdk_kmeans_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sdk_centroid_linkage_workspace_bytes": (_sz, [_vp, _i, _i]),
     "sdk_centroid_linkage": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "sdk_affinity_topk": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -381,7 +381,7 @@ class Backend(EmbeddingBackend):
         return plda
 
     def cluster_ranges(self, samples: np.ndarray, ranges: List[Tuple[float, float]], threshold: float = 0.7045654963945799,
-                       min_cluster_size: int = 12, clustering: str = "ahc", loop_prob: float = 0.99, plda=None):      # cluster.VBX_LOOP_PROB
+                       min_cluster_size: int = 12, speakers=None, clustering: str = "ahc", loop_prob: float = 0.99, plda=None):      # cluster.VBX_LOOP_PROB
         """Speaker labels for a transcript's segments with no enrolled profiles: embed_ranges -> cluster.agglomerative_cluster (centroid
         linkage on the GPU, flat cut at `threshold`, clusters under min_cluster_size folded into the nearest large one).
         Returns (labels [W] int32 per window, windows [(range index, start s, end s)], range_labels [len(ranges)] int32): a range takes the
@@ -393,22 +393,28 @@ class Backend(EmbeddingBackend):
         unpinned here).  `threshold` then cuts the linkage that only initialises it (pass cluster.VBX_AHC_THRESHOLD, 0.6); min_cluster_size is
         not used; labels are the arg-max of gamma over the kept speakers.  plda: a plda.Plda for this family's embedding width; None takes
         Backend.diarizer()'s ($SDK_PLDA_TRANSFORM and $SDK_PLDA, else the seeded synthetic model for the ResNet34's width).  One window:
-        label 0.  The same triple comes back."""
+        label 0.  The same triple comes back.
+        speakers: the number of speakers, None, an int k (exactly k) or a pair (lo, hi), either side None (cluster.parse_speakers and the
+        bounds stated above it; pyannote's max_speakers is speakers=(None, hi)).  When the count found lies outside, "ahc" takes the level
+        search of cluster.agglomerative_cluster rule 7 and "vbx" the k-means of cluster.kmeans_cluster on the window rows, whose labels come
+        back; fewer than two windows: nothing is forced."""
         if self.lite:
             raise ValueError("cluster_ranges needs the torch engine: not available with SDK_NO_TORCH=1")
         if clustering not in ("ahc", "vbx"):
             raise ValueError(f"cluster_ranges: clustering={clustering!r} (\"ahc\" or \"vbx\")")
-        from .cluster import agglomerative_cluster, vbx_cluster
+        from .cluster import agglomerative_cluster, parse_speakers, vbx_cluster
+        speakers = parse_speakers(speakers, "cluster_ranges")
         E, _, _, wins, _ = self.embed_ranges(samples, ranges)
         range_labels = np.full(len(ranges), -1, dtype=np.int32)
         if not wins:
             return np.zeros(0, np.int32), [], range_labels
         if clustering == "ahc":
-            labels = agglomerative_cluster(self.engine(), E, threshold, min_cluster_size).labels
+            labels = agglomerative_cluster(self.engine(), E, threshold, min_cluster_size, speakers=speakers).labels
         elif len(wins) == 1:
             labels = np.zeros(1, np.int32)
         else:
-            labels = vbx_cluster(self.engine(), E.contiguous(), self._ranges_plda(plda, int(E.shape[1])), threshold, loop_prob=loop_prob).labels
+            labels = vbx_cluster(self.engine(), E.contiguous(), self._ranges_plda(plda, int(E.shape[1])), threshold, loop_prob=loop_prob,
+                                 speakers=speakers).labels
         per = {}
         for (ri, _, _), lab in zip(wins, labels):
             per.setdefault(ri, []).append(int(lab))
@@ -493,13 +499,15 @@ class Backend(EmbeddingBackend):
         """Who spoke when, with no transcript and no enrolled profiles: a recording (16 kHz mono int16 samples, or the path of an audio file,
         decoded to the audio profile) -> diarize.DiarizationResult (turns [(start_s, end_s, speaker)], n_speakers, unit centroids in the
         embedding space of score_windows, labels, count, speakers); diarize.to_rttm(result.turns, uri) writes RTTM.  Keywords: step_s,
-        threshold, min_cluster_size, max_speakers, logp, constrained, clustering, vbx (diarize.Diarizer.run).  The default threshold is PyAnnote 3.1's, tuned
+        threshold, min_cluster_size, max_speakers, logp, constrained, clustering, vbx, speakers (diarize.Diarizer.run).  The default threshold is PyAnnote 3.1's, tuned
         for its trained ResNet34 ($SDK_RESNET_WEIGHTS); with the synthetic weights pass a threshold of your own.  constrained=True
         (PyAnnote's constrained_argmax; default False): the local speakers of a chunk get pairwise different clusters, the one-to-one
         matching of largest total cosine, computed on the device; the result then carries scores [C, 3].  clustering="vbx" (default "ahc"):
         the cut of the linkage at `threshold` (pass cluster.VBX_AHC_THRESHOLD, 0.6) only initialises a VBx clustering in PLDA space
         (cluster.vbx_cluster; the model of Backend.diarizer), whose speakers' centroids the assignment then reads; vbx: a dict of Fa, Fb,
-        max_iters, epsilon, init_smoothing.  The result then carries scores, pi and elbo.  Parity with PyAnnote is unpinned."""
+        max_iters, epsilon, init_smoothing.  The result then carries scores, pi and elbo.  speakers=k, or (lo, hi) with either side None:
+        the number of speakers of the recording ("bounds" in diarize.py; pyannote's max_speakers is speakers=(None, hi), max_speakers here
+        is the cap per frame); result.forced says whether the clustering was overruled.  Parity with PyAnnote is unpinned."""
         dz = self.diarizer()
         if isinstance(samples_or_path, (str, Path)):
             samples_or_path = decode_to_profile(Path(samples_or_path), self.engine(), self.get_audio_profile())

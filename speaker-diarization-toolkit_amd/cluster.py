@@ -236,6 +236,7 @@ class AgglomerativeResult:
     labels: np.ndarray            # [N] int32 canonical (order of first appearance)
     linkage: np.ndarray           # [N - 1, 4] float64, scipy's layout and numbering (Engine.centroid_linkage)
     n_large: int                  # clusters at least the effective minimum size after the cut (all clusters when n_clusters is given)
+    forced = None                 # speakers= overruled the cut: {found, target, method: "level", level, n_iter: None} (a class default, not a field)
 
 
 def _flat_partition(Z: np.ndarray, n: int, n_merges: int) -> np.ndarray:
@@ -259,6 +260,13 @@ def _flat_partition(Z: np.ndarray, n: int, n_merges: int) -> np.ndarray:
     return canonical_labels(roots).astype(np.int32)
 
 
+def cut_level(Z: np.ndarray, t: float) -> int:
+    """The number of merges that fcluster_distance(Z, t) keeps: the rows of Z before the first whose height exceeds t."""
+    Z = np.asarray(Z, dtype=np.float64)
+    above = np.flatnonzero(Z[:, 2] > t)
+    return int(above[0]) if above.size else int(Z.shape[0])
+
+
 def fcluster_distance(Z: np.ndarray, t: float) -> np.ndarray:
     """The flat cut of linkage Z at distance t: canonical labels of the partition formed by the merges BEFORE the first row whose height
     exceeds t (numpy only).
@@ -272,13 +280,72 @@ def fcluster_distance(Z: np.ndarray, t: float) -> np.ndarray:
     """
     Z = np.asarray(Z, dtype=np.float64)
     n = Z.shape[0] + 1
-    above = np.flatnonzero(Z[:, 2] > t)
-    k = int(above[0]) if above.size else n - 1
-    return _flat_partition(Z, n, k)
+    return _flat_partition(Z, n, cut_level(Z, t))
+
+
+# ------------------------------------------------------------------ bounds on the speaker count (`speakers=`)
+# bounds      (this build's statement of pyannote's num_speakers / min_speakers / max_speakers, written from the published description; no
+#             pyannote code is on hand: PARITY IS UNPINNED, the tests pin THIS rule).  speakers = None: no bound, today's path.  An int k >= 1:
+#             exactly k (lo = hi = k).  A pair (lo, hi), either side None, 1 <= lo <= hi: bounds.  pyannote's max_speakers is
+#             speakers=(None, hi) here; Diarizer.run's max_speakers is the cap PER FRAME and never touches the clustering.
+#               1. the unbounded clustering runs first and finds K0 speakers ("ahc": the clusters after cut and fold; "vbx": the kept ones);
+#               2. lo <= K0 <= hi: the result IS the unbounded one, bit for bit;
+#               3. otherwise target = lo when K0 < lo, else hi, clamped to 1 .. N (N training rows);
+#               4. fewer than two training rows: nothing is forced;
+#               5. "ahc": the level search of agglomerative_cluster; "vbx": kmeans_cluster with k = target on the original unit rows.
+def parse_speakers(speakers, who: str = "speakers"):
+    """speakers (None, an int k >= 1, or a pair (lo, hi) with either side None and 1 <= lo <= hi) -> None or (lo, hi) with hi = None for no
+    upper bound.  Anything else is a ValueError; nothing here touches the device."""
+    def one(v):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{who}: speakers={speakers!r} (None, an int k >= 1, or a pair (lo, hi) of ints or None with 1 <= lo <= hi)")
+        return int(v)
+    if speakers is None:
+        return None
+    if isinstance(speakers, (tuple, list)):
+        if len(speakers) != 2:
+            one(None)
+        lo, hi = (None if v is None else one(v) for v in speakers)
+    else:
+        lo = hi = one(speakers)
+    lo = 1 if lo is None else lo
+    if lo < 1 or (hi is not None and hi < lo):
+        one(None)
+    return lo, hi
+
+
+def speaker_target(found: int, bounds, n_rows: int) -> Optional[int]:
+    """Rules 2 - 4 of the bounds: None when the count found stands, else the count to force."""
+    if bounds is None or n_rows < 2:
+        return None
+    lo, hi = bounds
+    if found >= lo and (hi is None or found <= hi):
+        return None
+    return min(max(lo if found < lo else hi, 1), int(n_rows))
+
+
+def level_counts(Z: np.ndarray, eff: int) -> np.ndarray:
+    """L [N] int64: L[t] = the clusters of at least eff rows after the first t merges of the linkage Z [N - 1, 4], in ONE pass over Z's sizes:
+    merge t joins nodes a and b (a leaf has one row, node N + i has Z[i, 3]) into one of Z[t, 3] rows, so
+    L[t + 1] = L[t] + [Z[t, 3] >= eff] - [size a >= eff] - [size b >= eff]."""
+    Z = np.asarray(Z, dtype=np.float64)
+    N = Z.shape[0] + 1
+    size = np.concatenate([np.ones(N, np.int64), np.rint(Z[:, 3]).astype(np.int64)])
+    big = (size >= int(eff)).astype(np.int64)
+    step = big[N:] - big[Z[:, 0].astype(np.int64)] - big[Z[:, 1].astype(np.int64)]
+    return np.concatenate([[N * int(big[0])], N * int(big[0]) + np.cumsum(step)]).astype(np.int64)
+
+
+def level_search(Z: np.ndarray, eff: int, t0: int, target: int):
+    """The level of the forced count: the t in 0 .. N - 1 that minimises (|L[t] - target|, |t - t0|, t) -> (t, L[t])."""
+    L = level_counts(Z, eff)
+    t = np.arange(L.size)
+    best = np.lexsort((t, np.abs(t - int(t0)), np.abs(L - int(target))))[0]
+    return int(best), int(L[best])
 
 
 def agglomerative_cluster(provider, E, threshold: float = PYANNOTE_THRESHOLD, min_cluster_size: int = PYANNOTE_MIN_CLUSTER_SIZE,
-                          n_clusters: Optional[int] = None) -> AgglomerativeResult:
+                          n_clusters: Optional[int] = None, speakers=None) -> AgglomerativeResult:
     """Speaker clusters without knowing their number: centroid linkage on the unit rows E ([N, d] fp32 on the provider's device; the linkage
     runs in libsdk_hip.so, Engine.centroid_linkage), a flat cut at `threshold`, small clusters folded into the nearest large one.
 
@@ -290,9 +357,21 @@ def agglomerative_cluster(provider, E, threshold: float = PYANNOTE_THRESHOLD, mi
       4. otherwise every small cluster joins the large cluster whose centroid (mean of its unit rows) is nearest in 1 - cos, ties to the
          large cluster that comes first in label order;
       5. N == 1 gives [0];
-      6. n_clusters given: the partition after the first N - n_clusters merges, min_cluster_size not applied.  PyAnnote's search over
-         dendrogram levels for a forced count is not reproduced.
+      6. n_clusters given: the partition after the first N - n_clusters merges, min_cluster_size not applied.  For a count that respects
+         the minimum size, pass `speakers` (rule 7).
+      7. speakers given (parse_speakers; the bounds stated above it; PyAnnote's search over dendrogram levels, written from the published
+         description, parity unpinned, the tests pin THIS rule): rules 1 - 5 run first and find K0 clusters (n_large, or 1 when no
+         cluster is large).  Inside the bounds the result is that one.  Otherwise, with target from speaker_target, eff from rule 1 and
+         t0 = the merges the cut keeps (cut_level), let L(t) be the clusters of at least eff rows after the first t merges, t = 0 .. N - 1
+         (level_counts: host integers on Z's size column, O(N)).  The level t* minimises (|L(t) - target|, |t - t0|, t); the partition
+         after t* merges is folded by rules 2 - 4 as the cut is.  Every target <= K0 is reached: a merge changes L by +1, 0 or -1, so L
+         moves in unit steps from L(t0) = K0 (wherever a cluster is large) down to L(N - 1) = 1.  A target > K0 may be out of
+         reach when eff > 1 (fewer than target clusters of eff rows at any level): the closest count is taken.  The result's `forced`
+         then says what was found and what was taken.
     Labels are canonical (order of first appearance)."""
+    bounds = parse_speakers(speakers, "agglomerative_cluster")
+    if bounds is not None and n_clusters is not None:
+        raise ValueError("agglomerative_cluster: n_clusters and speakers are two ways to a count: pass one")
     N = int(E.shape[0])
     if N == 0:
         return AgglomerativeResult(np.zeros(0, np.int32), np.zeros((0, 4)), 0)
@@ -305,13 +384,24 @@ def agglomerative_cluster(provider, E, threshold: float = PYANNOTE_THRESHOLD, mi
         return AgglomerativeResult(lab, Z, int(lab.max()) + 1)
     Eh = E.detach().cpu().numpy().astype(np.float64) if isinstance(E, torch.Tensor) else np.asarray(E, dtype=np.float64)
     lab, n_large = fold_small_clusters(Eh, fcluster_distance(Z, threshold), min_cluster_size)
-    return AgglomerativeResult(lab, Z, n_large)
+    res = AgglomerativeResult(lab, Z, n_large)
+    target = speaker_target(max(n_large, 1), bounds, N)
+    if target is not None:
+        level, _ = level_search(Z, effective_min_size(min_cluster_size, N), cut_level(Z, threshold), target)
+        res.labels, res.n_large = fold_small_clusters(Eh, _flat_partition(Z, N, level), min_cluster_size)
+        res.forced = {"found": max(n_large, 1), "target": target, "method": "level", "level": level, "n_iter": None}
+    return res
+
+
+def effective_min_size(min_cluster_size: int, N: int) -> int:
+    """Rule 1 of agglomerative_cluster."""
+    return min(int(min_cluster_size), max(1, round(0.1 * N)))
 
 
 def fold_small_clusters(E: np.ndarray, labels: np.ndarray, min_cluster_size: int):
     """Rules 1-4 of agglomerative_cluster on a flat partition (canonical labels) of the rows E (float64): -> (canonical labels, large count)."""
     N = labels.shape[0]
-    eff = min(int(min_cluster_size), max(1, round(0.1 * N)))
+    eff = effective_min_size(min_cluster_size, N)
     K = int(labels.max()) + 1
     sizes = np.bincount(labels, minlength=K)
     large = np.flatnonzero(sizes >= eff)
@@ -350,10 +440,14 @@ class VbxResult:
     cent: object                  # [K, d] fp32 unit centroids (device tensor)
     cent64: object                # [K, d] float64, the same before the final rounding (device tensor; what sdk_diarize_assign reads)
     gamma: object                 # [N, S] float64 responsibilities (device tensor)
+    # speakers= overruled the mixture: {found, target, method: "kmeans", level: None, n_iter}; labels, n_speakers, cent and cent64 are then
+    # kmeans_cluster's, and pi, elbo, n_iter, keep, init_labels and gamma stay those of the VBx pass that was overruled (a class default, not a field)
+    forced = None
 
 
 def vbx_cluster(provider, E, plda, threshold: float = VBX_AHC_THRESHOLD, Fa: float = VBX_FA, Fb: float = VBX_FB, max_iters: int = VBX_MAX_ITERS,
-                epsilon: float = VBX_EPSILON, init_smoothing: float = VBX_INIT_SMOOTHING, rows=None, loop_prob: float = 0.0) -> VbxResult:
+                epsilon: float = VBX_EPSILON, init_smoothing: float = VBX_INIT_SMOOTHING, rows=None, speakers=None,
+                loop_prob: float = 0.0) -> VbxResult:
     """VBx clustering (Landini et al., BUT) of the unit rows E ([R, d] fp32 on the provider's device; rows: the ascending row numbers that
     take part, host integers, None = all), as the clustering half of PyAnnote's speaker-diarization-community-1 pipeline is stated HERE
     (written from the published description; no trained PLDA and no pyannote code is on hand: PARITY IS UNPINNED, the tests pin this rule):
@@ -388,12 +482,18 @@ def vbx_cluster(provider, E, plda, threshold: float = VBX_AHC_THRESHOLD, Fa: flo
       result          speakers with pi > 1e-7 are kept, in their order; a kept speaker's centroid is sum_t gamma[t, k] e_t / sum_t gamma[t, k]
                       over the ORIGINAL unit rows, summed in float64 in ascending row order, re-normalised (sdk_vbx_centroids); a row's hard
                       label is the arg-max of gamma over the kept speakers, ties to the lower.
+      bounds          speakers given (parse_speakers; the bounds stated above it; community-1's fallback as best known here, written from the
+                      published description, parity unpinned, the tests pin THIS rule): the pass above runs first and keeps K0 speakers.
+                      Inside the bounds the result is that one.  Otherwise kmeans_cluster with k = target (speaker_target; above
+                      KMEANS_MAX_K it is a ValueError) on the original unit rows gives labels, n_speakers, cent and cent64; pi, elbo and
+                      the rest stay those of the pass that was overruled, and `forced` says what was found and what was taken.
 
     Needs at least two rows.  The linkage Z is downloaded for the cut; after that one host read decides (n_iter, status, K, at the end; a
     non-finite row raises ValueError there), and the results (labels, pi, elbo, keep) are downloaded after it."""
     loop_prob = float(loop_prob)
     if not 0.0 <= loop_prob < 1.0:
         raise ValueError(f"vbx_cluster: loop_prob={loop_prob} (at least 0, below 1)")                  # a NaN fails both
+    bounds = parse_speakers(speakers, "vbx_cluster")
     R = int(E.shape[0])
     rows_h = np.arange(R, dtype=np.int64) if rows is None else np.asarray(rows, dtype=np.int64).reshape(-1)
     N = int(rows_h.size)
@@ -418,5 +518,79 @@ def vbx_cluster(provider, E, plda, threshold: float = VBX_AHC_THRESHOLD, Fa: flo
     if st:
         raise ValueError(f"vbx_cluster: non-finite input (status {st}: 1 = a non-finite embedding or PLDA value, 4 = a non-finite ELBO after "
                          f"{n_it} iterations)")
-    return VbxResult(labels.cpu().numpy(), Kn, pi.cpu().numpy(), elbo[:n_it].cpu().numpy(), n_it, keep[:Kn].cpu().numpy(), init, cent[:Kn], cent64[:Kn],
-                     gamma)
+    res = VbxResult(labels.cpu().numpy(), Kn, pi.cpu().numpy(), elbo[:n_it].cpu().numpy(), n_it, keep[:Kn].cpu().numpy(), init, cent[:Kn], cent64[:Kn],
+                    gamma)
+    target = speaker_target(Kn, bounds, N)
+    if target is not None:
+        if target > KMEANS_MAX_K:
+            raise ValueError(f"vbx_cluster: speakers={speakers!r} asks for {target} speakers ({Kn} found); the k-means serves at most {KMEANS_MAX_K}")
+        km = kmeans_cluster(provider, E, target, rows=rows_h)
+        res.labels, res.n_speakers, res.cent, res.cent64 = km.labels, km.n_clusters, km.cent, km.cent64
+        res.forced = {"found": Kn, "target": target, "method": "kmeans", "level": None, "n_iter": km.n_iter}
+    return res
+
+
+# ------------------------------------------------------------------ spherical k-means on unit rows: the forced count of "vbx"
+KMEANS_MAX_K = 64                # one lane per centre (csrc/kmeans.hip)
+KMEANS_MAX_ITERS = 20
+KMEANS_MAX_ROWS = 65536
+KMEANS_SEGMENT = 1024            # rows per segment of the centre sums (the kernel's constant)
+KMEANS_HOST_READS = 2            # kmeans_cluster waits for the device twice: the one read (n_iter, status), then the labels
+
+
+@dataclass
+class KmeansResult:
+    labels: np.ndarray            # [N] int32 canonical (order of first appearance), centres left without rows dropped
+    n_clusters: int               # K <= k
+    n_iter: int                   # assignments made
+    cent: object                  # [K, d] fp32 unit centroids of the labels (device tensor; sdk_diarize_centroids)
+    cent64: object                # [K, d] float64, the same before the final rounding (device tensor; what sdk_diarize_assign reads)
+    counts: np.ndarray            # [K] int64 rows per cluster
+
+
+def kmeans_cluster(provider, E, k: int, rows=None, max_iters: int = KMEANS_MAX_ITERS) -> KmeansResult:
+    """Spherical k-means with k centres on the unit rows E, on the device with the whole loop in one enqueue (Engine.kmeans_rows,
+    sdk_kmeans_rows; csrc/kmeans.hip).  The rule (this build's; the tests pin it; row t below is E[rows[t]]):
+
+      input       E [R, d] fp32 unit rows on the provider's device, d = 64, 128, .. 512 (the widths sdk_diarize_assign serves); rows: the
+                  ascending row numbers that take part, strictly inside [0, R), host integers (None = all), N = len(rows) <= 65 536;
+                  1 <= k <= min(N, KMEANS_MAX_K = 64); 1 <= max_iters <= 1000.  Anything else is a ValueError before the launch.
+      seeding     maximin, as the thin k-means of spectral_cluster: centre 0 is row 0; centre j is the row whose largest cosine to the
+                  centres 0 .. j - 1 is smallest, ties to the lowest row.  Seeds are rows, so their cosines are sums of exact products,
+                  added in float64 over the columns in ascending order.
+      assignment  label_t = argmax_c <centre c, row t>: each cosine one float64 sum over the columns in ascending order (an fma chain);
+                  ties to the lower c; a NaN never wins.
+      update      s_c = the float64 sum of the rows labelled c, in this order: per segment of KMEANS_SEGMENT = 1024 rows (t = 1024 g ..
+                  1024 g + 1023) in ascending row order from 0.0, then the segments' partials in segment order from 0.0; centre c =
+                  s_c / |s_c|.  A centre without rows, or with |s_c| = 0, keeps its value.  No atomics.
+      stop        iteration it = 0, 1, ..: assignment, then update.  The loop stops after the first assignment with it >= 1 in which
+                  no label changed, or after max_iters assignments; n_iter counts the assignments made.  All iterations are enqueued
+                  at once; the stop flag lives on the device and later launches return on it, as in sdk_vbx.  ONE host read at the end,
+                  (n_iter, status); status != 0 (a non-finite value in a row) raises ValueError after that read.
+      result      the labels of the last assignment, downloaded after the read; centres left without rows are dropped and the labels
+                  made canonical; cent / cent64 come from sdk_diarize_centroids over those labels (the float64 mean of the unit rows in
+                  ascending row order, re-normalised), in the layout sdk_diarize_assign takes."""
+    import torch as _torch
+    from .diarize import diarize_centroids, _check_rows
+    _check_rows("kmeans_cluster", E)
+    R = int(E.shape[0])
+    rows_h = np.arange(R, dtype=np.int64) if rows is None else np.asarray(rows, dtype=np.int64).reshape(-1)
+    N = int(rows_h.size)
+    if N < 1 or N > KMEANS_MAX_ROWS:
+        raise ValueError(f"kmeans_cluster: {N} rows (1 .. {KMEANS_MAX_ROWS})")
+    if rows_h.min() < 0 or rows_h.max() >= R or (np.diff(rows_h) <= 0).any():
+        raise ValueError(f"kmeans_cluster: rows must ascend strictly inside [0, {R}), got {int(rows_h.min())} .. {int(rows_h.max())}")
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or k < 1 or k > min(N, KMEANS_MAX_K):
+        raise ValueError(f"kmeans_cluster: k={k!r} (an int, 1 .. min(N, {KMEANS_MAX_K}), N={N})")
+    max_iters = int(max_iters)
+    if max_iters < 1 or max_iters > 1000:
+        raise ValueError(f"kmeans_cluster: max_iters={max_iters} (1 .. 1000)")
+    rows_d = _torch.from_numpy(rows_h.astype(np.int32)).to(E.device)
+    lab_d, n_iter, status = provider.kmeans_rows(E, rows_d, int(k), max_iters, check_rows=False)
+    n_it, st = (int(v) for v in _torch.cat([n_iter, status]).cpu().numpy())                # the one read
+    if st:
+        raise ValueError(f"kmeans_cluster: non-finite input (status {st}: a row holds a NaN or an infinity)")
+    labels = canonical_labels(lab_d.cpu().numpy()).astype(np.int32)
+    K = int(labels.max()) + 1
+    cent, cent64 = diarize_centroids(provider, E, rows_d, _torch.from_numpy(labels).to(E.device), K, check_rows=False)
+    return KmeansResult(labels, K, n_it, cent, cent64, np.bincount(labels, minlength=K).astype(np.int64))

@@ -31,6 +31,20 @@ tests pin these rules.
               kept speakers' centroids are the responsibility-weighted means of the original unit rows; every candidate row is then assigned
               by sdk_diarize_assign with the caller's `constrained` flag, so the stretch from embeddings to labels stays on the device and the
               result carries scores either way.  With fewer than two training rows: as "ahc" (one cluster or none).
+  bounds      (speakers=; pyannote's num_speakers / min_speakers / max_speakers, written from the published description; parity unpinned, the
+              tests pin THIS rule, stated in full in cluster.py above parse_speakers).  None: no bound, every result field is what it was.
+              An int k >= 1: exactly k speakers; a pair (lo, hi), either side None, 1 <= lo <= hi: bounds; pyannote's max_speakers is
+              speakers=(None, hi) here, while max_speakers below stays the cap PER FRAME and never touches the clustering.  The
+              unbounded clustering runs first and finds K0 speakers ("ahc": the clusters after cut and fold; "vbx": the kept speakers).
+              lo <= K0 <= hi: the result IS the unbounded one, bit for bit.  Otherwise target = lo when K0 < lo, else hi, clamped to
+              1 .. N training rows.  "ahc": the level search of cluster.agglomerative_cluster rule 7 (host integers on Z, O(N)): the level
+              whose count of clusters of the effective minimum size is nearest the target, then nearest the cut, then lowest, folded as
+              the cut is; a target above K0 may be out of reach, then the closest count is taken.  "vbx": cluster.kmeans_cluster with
+              k = target on the original unit rows of the training set (sdk_kmeans_rows: the whole loop in one enqueue), whose labels go
+              through sdk_diarize_centroids and sdk_diarize_assign as VBx's centroids do; pi and elbo of the VBx pass that was overruled
+              stay on the result.  With fewer than two training rows nothing is forced.  The result's `forced` is None, or
+              {found: K0, target, method: "level" | "kmeans", level: t* or None, n_iter: int or None}.  In run_many the level search
+              replaces the cut per recording inside _pack_ahc, on the host: the waits per pack do not grow.
   stitching   on the global frame grid of segmentation.aggregate_counts (frame g, centre 270 g + 495, takes frame g + q_c of chunk c,
               q_c = (135 - start_c) // 270): act[g, k] = chunks in which a local speaker labelled k is active; count[g] = the mean chunk count
               rounded half up, at most 2 and max_speakers; speakers[g] = the count[g] clusters of largest act > 0 (ties to the lower cluster)
@@ -99,6 +113,7 @@ class DiarizationResult:
     # field list, and with it the positional constructor, ends with scores as before.
     pi = None                                 # [S] float64 weights of the S initial speakers after the last iteration
     elbo = None                               # [n_iter] float64
+    forced = None                             # speakers= overruled the clustering: {found, target, method, level, n_iter} ("bounds" above); else None
 
 
 # ------------------------------------------------------------------------------------------------ host restatements (numpy, vectorised)
@@ -690,8 +705,8 @@ class Diarizer:
         return self.plda
 
     # ---------------------------------------------------------------------------------------------- what run and run_many share
-    def _check_options(self, who: str, clustering, vbx, max_speakers) -> dict:
-        """-> vbx as a dict of its own."""
+    def _check_options(self, who: str, clustering, vbx, max_speakers, speakers=None):
+        """-> (vbx as a dict of its own, the bounds of cluster.parse_speakers)."""
         if clustering not in ("ahc", "vbx"):
             raise ValueError(f"{who}: clustering={clustering!r} (\"ahc\" or \"vbx\")")
         vbx = dict(vbx or {})
@@ -699,7 +714,8 @@ class Diarizer:
             raise ValueError(f"{who}: vbx={vbx} (keys Fa, Fb, max_iters, epsilon, init_smoothing; only with clustering=\"vbx\")")
         if max_speakers is not None and int(max_speakers) < 0:
             raise ValueError(f"max_speakers={max_speakers}: must be None or >= 0")
-        return vbx
+        from .cluster import parse_speakers
+        return vbx, parse_speakers(speakers, who)
 
     def _check_recording(self, who: str, Cn: int, n_samples: int, step_s: float, logp=None):
         """The linkage's row bound and the shape of an injected logp, for a recording of n_samples > 0 samples in Cn chunks."""
@@ -747,7 +763,7 @@ class Diarizer:
     # ---------------------------------------------------------------------------------------------- one recording
     def run(self, samples, step_s: float = 1.0, threshold: float = PYANNOTE_THRESHOLD, min_cluster_size: int = PYANNOTE_MIN_CLUSTER_SIZE,
             max_speakers: Optional[int] = None, logp=None, constrained: bool = False, clustering: str = "ahc",
-            vbx: Optional[dict] = None) -> DiarizationResult:
+            vbx: Optional[dict] = None, speakers=None) -> DiarizationResult:
         """samples: 16 kHz mono int16 (host) -> DiarizationResult.  logp [C, 589, 7] (fp32, host or device) replaces the segmentation
         model's output (the chunks are chunk_starts(len(samples), step_s)).  The default threshold and size are PyAnnote 3.1's, tuned for
         ITS trained embedding; with other weights pass a threshold of your own.  constrained=True: the constrained assignment of the
@@ -755,8 +771,12 @@ class Diarizer:
         clustering="vbx": the VBx clustering of the module docstring instead of the cut-and-fold ("ahc", the default); `threshold` keeps its
         meaning, the cut of the linkage, which now only initialises: pass cluster.VBX_AHC_THRESHOLD (0.6) with it; min_cluster_size is not
         used.  vbx: a dict of Fa, Fb, max_iters, epsilon, init_smoothing (cluster.vbx_cluster's defaults otherwise).  The result carries
-        scores, pi and elbo."""
-        vbx = self._check_options("diarize", clustering, vbx, max_speakers)
+        scores, pi and elbo.
+        speakers: the number of speakers of the recording, "bounds" in the module docstring: None, an int k (exactly k) or a pair (lo, hi),
+        either side None.  pyannote's num_speakers=k is speakers=k, its min_speakers / max_speakers are speakers=(lo, hi), its
+        max_speakers alone is speakers=(None, hi); max_speakers HERE is the cap per frame and keeps that meaning.  The result's `forced`
+        says whether the clustering was overruled."""
+        vbx, bounds = self._check_options("diarize", clustering, vbx, max_speakers, speakers)
         torch = _native()[0]
         from .cluster import agglomerative_cluster, vbx_cluster
         eng = self.eng
@@ -775,11 +795,14 @@ class Diarizer:
         cls, info_dev, E_dev = self._embed_all(rec, x.size, starts_dev, logp)     # decode, masks, embedding
         info = info_dev.cpu().numpy()
         train = training_rows(info, F)                          # training rows and their clustering
-        vres, tl = None, np.zeros(len(train), np.int32)
+        vres, tl, forced = None, np.zeros(len(train), np.int32), None
         if len(train) > 1 and clustering == "vbx":
-            vres = vbx_cluster(eng, E_dev, self.plda_model(), threshold, rows=train, **vbx)
+            vres = vbx_cluster(eng, E_dev, self.plda_model(), threshold, rows=train, speakers=bounds, **vbx)
+            forced = vres.forced
         elif len(train) > 1:
-            tl = agglomerative_cluster(eng, E_dev.index_select(0, torch.from_numpy(train).to(eng.device)).contiguous(), threshold, min_cluster_size).labels
+            ares = agglomerative_cluster(eng, E_dev.index_select(0, torch.from_numpy(train).to(eng.device)).contiguous(), threshold, min_cluster_size,
+                                         speakers=bounds)
+            tl, forced = ares.labels, ares.forced
         if constrained or clustering == "vbx":                  # assignment on the device: the embeddings stay there, the result carries scores
             if vres is not None:
                 c32, c64 = vres.cent, vres.cent64.contiguous()
@@ -814,12 +837,14 @@ class Diarizer:
         res = DiarizationResult(turns_from_frames(speakers, K), K, cent, labels, count, speakers, st, info, cls, scores)
         if vres is not None:
             res.pi, res.elbo = vres.pi, vres.elbo
+        if forced is not None:
+            res.forced = forced
         return res
 
     # ---------------------------------------------------------------------------------------------- many recordings in one device pass
     def run_many(self, recordings, step_s: float = 1.0, threshold: float = PYANNOTE_THRESHOLD, min_cluster_size: int = PYANNOTE_MIN_CLUSTER_SIZE,
                  max_speakers: Optional[int] = None, logp=None, constrained: bool = False, clustering: str = "ahc",
-                 vbx: Optional[dict] = None) -> List[DiarizationResult]:
+                 vbx: Optional[dict] = None, speakers=None) -> List[DiarizationResult]:
         """recordings: a list of 16 kHz mono int16 arrays (host) -> one DiarizationResult per recording, in order; the keywords are run's,
         logp is None or a list with one [C_r, 589, 7] array per recording.  The recordings cross the pipeline in packs (pack_recordings) of
         at most $SDK_DIARIZE_PACK_SAMPLES samples (default 2^28, gaps included) whose grouped linkage stays within
@@ -830,9 +855,11 @@ class Diarizer:
         fold, final centroids, assignment, stitching, renumbering and second stitching on the device, and one download each of labels,
         scores, centroids, count and speakers.  self.last_sync holds the number of such waits of the last call, per pack.
         Where the results differ from run's on purpose: "shared" in the module docstring.  clustering="vbx" runs cluster.vbx_cluster
-        recording by recording (its own linkage, cut and host reads) between the packed embedding and the grouped assignment."""
+        recording by recording (its own linkage, cut and host reads) between the packed embedding and the grouped assignment.
+        speakers: run's, applied to every recording; for "ahc" the level search replaces the cut on the host and adds no wait, for "vbx" a
+        recording whose count is overruled adds cluster.KMEANS_HOST_READS waits."""
         from .cluster import vbx_cluster  # noqa: F401  (checked early: the package imports)
-        vbx = self._check_options("diarize_many", clustering, vbx, max_speakers)
+        vbx, bounds = self._check_options("diarize_many", clustering, vbx, max_speakers, speakers)
         xs = [np.ascontiguousarray(x, dtype=np.int16).reshape(-1) for x in recordings]
         if logp is not None and (not isinstance(logp, (list, tuple)) or len(logp) != len(xs)):
             raise ValueError(f"diarize_many: logp must be None or a list with one array per recording ({len(xs)}), got "
@@ -859,7 +886,7 @@ class Diarizer:
         self.last_sync = []
         for idx in packs:
             for i, res in zip(idx, self._run_pack([xs[i] for i in idx], None if logp is None else [logp[i] for i in idx], step_s, threshold,
-                                                  min_cluster_size, max_speakers, constrained, clustering, vbx)):
+                                                  min_cluster_size, max_speakers, constrained, clustering, vbx, bounds)):
                 out[i] = res
         return out
 
@@ -880,7 +907,7 @@ class Diarizer:
             stage_s[name] = stage_s.get(name, 0.0) + now - self._t_mark
             self._t_mark = now
 
-    def _run_pack(self, xs, logps, step_s, threshold, min_cluster_size, max_speakers, constrained, clustering, vbx):
+    def _run_pack(self, xs, logps, step_s, threshold, min_cluster_size, max_speakers, constrained, clustering, vbx, bounds=None):
         """One pack through its stages; every _mark ends a stage of last_stage_s."""
         sync = {"downloads": 0, "uploads": 0}
         self.last_sync.append(sync)
@@ -895,15 +922,15 @@ class Diarizer:
         self._mark("segmentation_embedding")
         rows, n_train = self._pack_rows(info, pack.chunk_off)
         if clustering == "vbx":
-            c32, c64, cent_off, vres = self._pack_vbx(E_dev, pack.chunk_off, rows, n_train, threshold, vbx)
+            c32, c64, cent_off, vres, forced = self._pack_vbx(E_dev, pack.chunk_off, rows, n_train, threshold, vbx, bounds)
         else:
-            c32, c64, cent_off, vres = self._pack_ahc(E_dev, rows, n_train, threshold, min_cluster_size)
+            c32, c64, cent_off, vres, forced = self._pack_ahc(E_dev, rows, n_train, threshold, min_cluster_size, bounds)
         tab.set_clusters(cent_off)
         sync["uploads"] += tab.uploads
         self._mark("cut_fold_centroids")
         host = self._pack_assign(tab, cls, info_dev, E_dev, c32, c64, constrained, max_speakers)
         self._mark("assign_stitch_download")
-        out = self._pack_results(xs, pack, cent_off, info, cls, vres, *host)
+        out = self._pack_results(xs, pack, cent_off, info, cls, vres, forced, *host)
         self._mark("turns")
         return out
 
@@ -932,16 +959,20 @@ class Diarizer:
             rows.append(tr if len(tr) else a + np.flatnonzero(cand_ok[a:b]))      # no training row: one cluster of the candidates
         return rows, n_train
 
-    def _pack_vbx(self, E_dev, co, rows, n_train, threshold, vbx):
-        """cluster.vbx_cluster recording by recording (its own linkage, cut and host reads) -> (c32, c64, cent_off, {recording: VbxResult})."""
+    def _pack_vbx(self, E_dev, co, rows, n_train, threshold, vbx, bounds=None):
+        """cluster.vbx_cluster recording by recording (its own linkage, cut and host reads) -> (c32, c64, cent_off, {recording: VbxResult},
+        {recording: forced})."""
         torch = _native()[0]
-        from .cluster import vbx_cluster
-        vres, cents, K_r = {}, [], []
+        from .cluster import KMEANS_HOST_READS, vbx_cluster
+        vres, cents, K_r, forced = {}, [], [], {}
         for r in range(len(rows)):
             a, K = N_LOCAL * int(co[r]), min(len(rows[r]), 1)
             if n_train[r] > 1:
-                v = vres[r] = vbx_cluster(self.eng, E_dev[a:N_LOCAL * int(co[r + 1])], self.plda_model(), threshold, rows=rows[r] - a, **vbx)
+                v = vres[r] = vbx_cluster(self.eng, E_dev[a:N_LOCAL * int(co[r + 1])], self.plda_model(), threshold, rows=rows[r] - a, speakers=bounds, **vbx)
                 self.last_sync[-1]["downloads"] += VBX_HOST_READS
+                if v.forced is not None:
+                    forced[r] = v.forced
+                    self.last_sync[-1]["downloads"] += KMEANS_HOST_READS
                 cents.append((v.cent, v.cent64))
                 K = int(v.n_speakers)
             elif K:                                             # one training row, or the candidates: one cluster
@@ -949,15 +980,16 @@ class Diarizer:
                                                torch.zeros(len(rows[r]), dtype=torch.int32, device=self.eng.device), 1, check_rows=False))
             K_r.append(K)
         c32, c64 = (torch.cat(c).contiguous() for c in zip(*cents)) if cents else (None, None)    # None: no recording has a cluster
-        return c32, c64, np.concatenate([[0], np.cumsum(K_r)]).astype(np.int64), vres
+        return c32, c64, np.concatenate([[0], np.cumsum(K_r)]).astype(np.int64), vres, forced
 
-    def _pack_ahc(self, E_dev, rows, n_train, threshold, min_cluster_size):
-        """ONE grouped linkage over the recordings with at least two training rows, the cut per recording on the host, the cut's centroids,
-        the grouped fold and the final centroids -> (c32, c64, cent_off, {}), as _pack_vbx."""
-        from .cluster import fcluster_distance
+    def _pack_ahc(self, E_dev, rows, n_train, threshold, min_cluster_size, bounds=None):
+        """ONE grouped linkage over the recordings with at least two training rows, the cut per recording on the host (with bounds: the
+        level search of cluster.agglomerative_cluster rule 7 in its place, host integers on the same Z), the cut's centroids, the grouped
+        fold and the final centroids -> (c32, c64, cent_off, {}, {recording: forced}), as _pack_vbx."""
+        from .cluster import _flat_partition, cut_level, effective_min_size, fcluster_distance, level_search, speaker_target
         eng, R = self.eng, len(rows)
         link = [r for r in range(R) if n_train[r] > 1]
-        cuts = {}
+        cuts, forced = {}, {}
         if link:
             off = np.concatenate([[0], np.cumsum([n_train[r] for r in link])]).astype(np.int64)
             E_link = E_dev.index_select(0, self._up(np.concatenate([rows[r] for r in link]))).contiguous()
@@ -965,7 +997,16 @@ class Diarizer:
             self.last_sync[-1]["downloads"] += LINKAGE_HOST_READS
             self._mark("linkage")
             for g, r in enumerate(link):
-                cuts[r] = fcluster_distance(Z[int(off[g]) - g:int(off[g + 1]) - g - 1], threshold)
+                Zr = Z[int(off[g]) - g:int(off[g + 1]) - g - 1]
+                cuts[r] = fcluster_distance(Zr, threshold)
+                if bounds is not None:                                             # K0 = the clusters the fold will keep: the large ones of the cut, or one
+                    eff_r = effective_min_size(min_cluster_size, n_train[r])
+                    found = max(1, int((np.bincount(cuts[r]) >= eff_r).sum()))
+                    target = speaker_target(found, bounds, n_train[r])
+                    if target is not None:
+                        level, _ = level_search(Zr, eff_r, cut_level(Zr, threshold), target)
+                        cuts[r] = _flat_partition(Zr, n_train[r], level)
+                        forced[r] = {"found": found, "target": target, "method": "level", "level": level, "n_iter": None}
         cut_all, sizes, cl_off, eff, cent_off = [], [], [0], [], [0]
         for r in range(R):
             n = len(rows[r])
@@ -979,12 +1020,12 @@ class Diarizer:
             cent_off.append(cent_off[-1] + (max(1, int((sz >= m).sum())) if len(sz) else 0))
         cent_off = np.asarray(cent_off, np.int64)
         if not cl_off[-1]:
-            return None, None, cent_off, {}
+            return None, None, cent_off, {}, forced
         rows_d = self._up(np.concatenate(rows).astype(np.int32))
         cut_d = self._up(np.concatenate(cut_all).astype(np.int32))
         _, cut64 = diarize_centroids(eng, E_dev, rows_d, cut_d, cl_off[-1], check_rows=False)
         _, final_d = diarize_fold_grouped(eng, cut64, np.concatenate(sizes), cl_off, eff, cent_off, cut_d, upload=self._up)
-        return diarize_centroids(eng, E_dev, rows_d, final_d, int(cent_off[-1]), check_rows=False) + (cent_off, {})
+        return diarize_centroids(eng, E_dev, rows_d, final_d, int(cent_off[-1]), check_rows=False) + (cent_off, {}, forced)
 
     def _pack_assign(self, tab, cls, info_dev, E_dev, c32, c64, constrained, max_speakers):
         """Grouped assignment, stitching, renumbering by appearance and second stitching -> (labels, scores, cent, count, speakers) on the host."""
@@ -999,7 +1040,7 @@ class Diarizer:
         cnt_dev, spk_dev, _ = diarize_reconstruct_grouped(eng, cls, lab_dev, tab, max_speakers)
         return tuple(self._down(t) for t in (lab_dev, score_dev, c32, cnt_dev, spk_dev))
 
-    def _pack_results(self, xs, pack: Pack, cent_off, info, cls, vres, labels, scores, cent, count, speakers):
+    def _pack_results(self, xs, pack: Pack, cent_off, info, cls, vres, forced, labels, scores, cent, count, speakers):
         """The pack's host arrays cut into one DiarizationResult per recording."""
         out = []
         for r, x in enumerate(xs):
@@ -1011,5 +1052,7 @@ class Diarizer:
                                     speakers[g0:g1].copy(), pack.starts_local[a:b].astype(np.int64), info[a:b].copy(), cls[a:b], scores[a:b].copy())
             if r in vres:
                 res.pi, res.elbo = vres[r].pi, vres[r].elbo
+            if r in forced:
+                res.forced = forced[r]
             out.append(res)
         return out

@@ -905,6 +905,29 @@ class Engine:
                                          labels.data_ptr(), cent.data_ptr(), cent64.data_ptr(), _stream()), "sdk_vbx_centroids")
         return K, keep, labels, cent, cent64
 
+    # ---- spherical k-means on unit rows (cluster.kmeans_cluster; csrc/kmeans.hip): the whole loop in one enqueue, nothing read back here
+    def kmeans_rows(self, E: torch.Tensor, rows: torch.Tensor, k: int, max_iters: int = 20, check_rows: bool = True):
+        """E [R, d] fp32 unit rows, rows [n] int32 ascending (device), 1 <= k <= min(n, 64) -> (labels [n] int32 in [0, k), not canonical,
+        n_iter [1] int32, status [1] int32), all on the device and not read back: sdk_kmeans_rows (the rule: cluster.kmeans_cluster).  The
+        caller reads n_iter and status once.  check_rows=False: the caller has checked that rows lie in [0, R)."""
+        n = self._vbx_rows("kmeans_rows", E, rows, check_rows)
+        k, max_iters, d = int(k), int(max_iters), int(E.shape[1])
+        if k < 1 or k > min(n, 64):
+            raise ValueError(f"kmeans_rows: k={k} (1 .. min(n, 64), n={n})")
+        if max_iters < 1 or max_iters > 1000:
+            raise ValueError(f"kmeans_rows: max_iters={max_iters} (1 .. 1000)")
+        nbytes = self.lib.sdk_kmeans_rows_workspace_bytes(n, d, k)
+        if nbytes == 0:
+            raise SdkError(f"sdk_kmeans_rows_workspace_bytes: {self.lib.sdk_last_error().decode()}")
+        dev = E.device
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        labels = torch.empty((n,), dtype=torch.int32, device=dev)
+        n_iter = torch.empty((1,), dtype=torch.int32, device=dev)
+        status = torch.empty((1,), dtype=torch.int32, device=dev)
+        check(self.lib.sdk_kmeans_rows(self.ctx, E.data_ptr(), rows.data_ptr(), n, d, k, max_iters, labels.data_ptr(), n_iter.data_ptr(),
+                                       status.data_ptr(), ws.data_ptr(), nbytes, _stream()), "sdk_kmeans_rows")
+        return labels, n_iter, status
+
     def asp_fused(self, ah, w2, b2, h, B, T, kblocked=False):
         """kblocked: h is [Cm / 64, B*T, 64] (to_kblocked) - the per-segment form only (sdk_asp_kblocked_ok).  The element format (bf16 or
         fp16) is h's dtype; ah and w2 must match it."""
