@@ -318,11 +318,18 @@ class Segmentation:
 
     @staticmethod
     def _source(samples, starts, ld, B, S):
+        """-> (samples, starts, ld, B, S, n): n samples are addressable from samples.data_ptr().  A [B, S] matrix may be a view with a row
+        stride of its own (its extent is (B - 1) stride + S samples, not numel()); its samples must be contiguous within a row."""
+        n = samples.numel()
         if starts is None:
             if samples.dim() == 2:
+                if samples.shape[1] > 1 and samples.stride(1) != 1:
+                    raise ValueError(f"segmentation: the samples of a row must be contiguous (stride(1)={samples.stride(1)})")
                 B, S, ld = samples.shape[0], samples.shape[1], samples.stride(0)
-            return samples, None, int(ld), int(B), int(S or CHUNK)
-        return samples, starts, 0, int(starts.numel()), int(S or CHUNK)
+                if B > 0:
+                    n = (B - 1) * ld + S
+            return samples, None, int(ld), int(B), int(S or CHUNK), int(n)
+        return samples, starts, 0, int(starts.numel()), int(S or CHUNK), int(n)
 
     def forward(self, samples, starts=None, S: int = 0, ld: int = 0, B: int = 0):
         """samples: a [B, S] int16 device matrix (rows are chunks), or a 1-D recording with starts [B] int32 (device; chunks of S samples,
@@ -330,12 +337,12 @@ class Segmentation:
         import torch
         from ._lib import check
         from .ops import _stream
-        samples, starts, ld, B, S = self._source(samples, starts, ld, B, S)
+        samples, starts, ld, B, S, n = self._source(samples, starts, ld, B, S)
         lib = self.eng.lib
         F = num_frames(S)
         logp = torch.empty((B, max(F, 0), 7), dtype=torch.float32, device=self.eng.device)
         ws = self._ws("segmentation", lib.sdk_segmentation_workspace_bytes(C.byref(self.desc), B, S))
-        check(lib.sdk_segmentation_forward(self.eng.ctx, self.blob.data_ptr(), C.byref(self.desc), samples.data_ptr(), samples.numel(),
+        check(lib.sdk_segmentation_forward(self.eng.ctx, self.blob.data_ptr(), C.byref(self.desc), samples.data_ptr(), n,
                                            starts.data_ptr() if starts is not None else None, ld, B, S, ws.data_ptr(), ws.numel(),
                                            logp.data_ptr(), _stream()), "sdk_segmentation_forward")
         return logp
@@ -345,11 +352,11 @@ class Segmentation:
         import torch
         from ._lib import check
         from .ops import _stream
-        samples, starts, ld, B, S = self._source(samples, starts, ld, B, S)
+        samples, starts, ld, B, S, n = self._source(samples, starts, ld, B, S)
         lib = self.eng.lib
         out = torch.empty((B * num_frames(S), 64), dtype=torch.float32, device=self.eng.device)
         ws = self._ws("segmentation", lib.sdk_segmentation_workspace_bytes(C.byref(self.desc), B, S))
-        check(lib.sdk_sincnet_frontend(self.eng.ctx, self.blob.data_ptr(), C.byref(self.desc), samples.data_ptr(), samples.numel(),
+        check(lib.sdk_sincnet_frontend(self.eng.ctx, self.blob.data_ptr(), C.byref(self.desc), samples.data_ptr(), n,
                                        starts.data_ptr() if starts is not None else None, ld, B, S, ws.data_ptr(), ws.numel(),
                                        out.data_ptr(), _stream()), "sdk_sincnet_frontend")
         return out

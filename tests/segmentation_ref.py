@@ -139,3 +139,19 @@ def mixed_audio(B, S, seed=0):
         s0 = int(rng.integers(0, S))
         x[b, s0:s0 + S // 8] = 0.0
     return np.clip(np.round(x * 32767), -32768, 32767).astype(np.int16)
+
+
+def stage_dims(S: int):
+    """(L1, L2, F): the lengths after the sinc, conv-2 and conv-3 blocks (conv, then MaxPool1d(3, 3)) of a chunk of S samples."""
+    L1 = ((S - 251) // 10 + 1) // 3
+    L2 = (L1 - 4) // 3
+    return L1, L2, (L2 - 4) // 3
+
+
+def cut_windows(rec: np.ndarray, starts, S: int) -> np.ndarray:
+    """The windows [s, s + S) of a 1-D int16 recording as rows [len(starts), S]; samples past the recording's end are zero."""
+    rows = np.zeros((len(starts), S), np.int16)
+    for i, s in enumerate(starts):
+        piece = rec[int(s):int(s) + S]
+        rows[i, :len(piece)] = piece
+    return rows

@@ -117,13 +117,17 @@ def test_reference_matches_torch_nn():
     w = seg.from_public_state_dict(m.state_dict())
     # the float64 reference rebuilds the filters from the fp32 host dict: give the torch model the same fp32 values
     m.load_state_dict({k: (torch.from_numpy(w[k]).double() if k in w else v) for k, v in m.state_dict().items()})
-    pcm = mixed_audio(3, 32000)
-    with torch.no_grad():
-        want = m(torch.from_numpy(pcm.astype(np.float64))[:, None, :])
-    got = SegRef(w, None, torch.float64).forward(pcm)
-    assert got.shape == want.shape == (3, seg.num_frames(32000), 7)
-    err = float((got - want).abs().max())
-    assert err <= 1e-9, err
+    # 32 000 samples, then the edge shapes of tests/test_segmentation_edges_gpu.py: F = 2, one sinc position into a second tile, a conv-2 tile
+    # plus one, a full conv-3 tile (S = 991, a single frame, stays out: torch's instance norm refuses it)
+    for S in (32000, 1261, 2191, 6211, 18001):
+        pcm = mixed_audio(3, S, seed=S % 1000 if S != 32000 else 0)
+        with torch.no_grad():
+            want = m(torch.from_numpy(pcm.astype(np.float64))[:, None, :])
+        got = SegRef(w, None, torch.float64).forward(pcm)
+        assert got.shape == want.shape == (3, seg.num_frames(S), 7)
+        err = float((got - want).abs().max())
+        print(f"reference vs torch nn, S={S}: max|d| {err:.3e}")
+        assert err <= 1e-9, (S, err)
     # the prefix is stripped; a bad shape or a stray key is refused
     w2 = seg.from_public_state_dict({"model." + k: v for k, v in m.state_dict().items()}, prefix="model.")
     assert all(np.array_equal(w2[k], w[k]) for k in w)
@@ -143,7 +147,7 @@ def test_npz_round_trip(tmp_path):
     assert set(w2) == set(w) and all(np.array_equal(w2[k], w[k]) for k in w)
 
 
-@pytest.mark.parametrize("S", [991, 1000, 32000, 160000, 160001])
+@pytest.mark.parametrize("S", [991, 1000, 32000, 160000, 160001, 1261, 1531, 2161, 2191, 4081, 6121, 6211, 17731, 18001, 18009, 18271, 36001])
 def test_num_frames_matches_torch(S):
     m = PyanNet().float().eval()
     with torch.no_grad():                 # the model's convs and pools (torch's instance norm refuses a single frame)
