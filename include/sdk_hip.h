@@ -47,6 +47,7 @@
  *     sdk_resnet_conv2d  (piece of sdk_resnet_forward)  sdk_resnet_masked_pool  (piece of sdk_resnet_forward_masked)
  *     sdk_sincnet_frontend  sdk_bilstm_layer  (pieces of sdk_segmentation_forward)
  *     sdk_set_option  sdk_set_gemm_variant  sdk_profile_begin / _end  sdk_debug_set_ptr  sdk_affinity_plan*  sdk_affinity_block_plan*  sdk_affinity_matvec_plan  sdk_conv_gemm_hp
+ *     sdk_seg_mean_hp  sdk_se_apply_hp  sdk_asp_stats_hp  sdk_asp_pool_hp  (the precise mode's sweeps, pieces of its forwards)
  *     sdk_allgather  sdk_laplacian_topk_workspace_bytes  sdk_laplacian_topk        k5 / k6 drivers for a non-Python host (the library holds no
  *                                                                                     communicator: the caller passes its ncclComm_t; the Python
  *                                                                                     host layer uses torch.distributed, dist.py / cluster.py)
@@ -323,6 +324,19 @@ typedef struct sdk_conv_gemm_hp_args {
   uint32_t flags;
 } sdk_conv_gemm_hp_args;
 int sdk_conv_gemm_hp(sdk_ctx* ctx, const sdk_conv_gemm_hp_args* a, void* stream);
+/* The precise mode's HBM-bound sweeps on plane pairs (pieces of its forwards, exported for the parity tests).  A plane operand [B*T, C] is
+ * (pointer, ld, lo): hi values at p[row * ld + c], lo values `lo` columns to the right; C % 8 == 0, ld % 8 == 0, lo % 8 == 0, lo >= C,
+ * ld >= lo + C, pointer 16-byte aligned - anything else is refused before a launch.  All arithmetic fp32.
+ *   sdk_seg_mean_hp:  out [B, C] fp32 = mean over the T frames of each segment (the SE squeeze)
+ *   sdk_se_apply_hp:  out planes = gate[b, c] * z + x  (gate [B, C] fp32; the pair store saturates at +-65504)
+ *   sdk_asp_stats_hp: out [B, 2C] fp32 = mean | sqrt(max(var, 1e-12)) over frames
+ *   sdk_asp_pool_hp:  pooled [B, 2C] fp32 = softmax-over-frames weighted mean | std of h, logits [B*T, ldl] fp32 (ldl >= C) */
+int sdk_seg_mean_hp(sdk_ctx* ctx, const uint16_t* z, int64_t ldz, int64_t z_lo, int B, int T, int C, float* out, void* stream);
+int sdk_se_apply_hp(sdk_ctx* ctx, const uint16_t* z, int64_t ldz, int64_t z_lo, const uint16_t* x, int64_t ldx, int64_t x_lo,
+                    const float* gate, uint16_t* out, int64_t ldo, int64_t o_lo, int B, int T, int C, void* stream);
+int sdk_asp_stats_hp(sdk_ctx* ctx, const uint16_t* h, int64_t ldh, int64_t h_lo, int B, int T, int C, float* out, void* stream);
+int sdk_asp_pool_hp(sdk_ctx* ctx, const float* logits, int64_t ldl, const uint16_t* h, int64_t ldh, int64_t h_lo, int B, int T, int C,
+                    float* pooled, void* stream);
 
 /* Whole forward: feats [B*T, ldf] bf16 -> raw embeddings emb [B, 192] fp32.
  * `wblob` is the packed device weight blob and `wdesc` (HOST) its offset table, both produced by

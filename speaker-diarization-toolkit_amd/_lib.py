@@ -111,6 +111,10 @@ SIGNATURES = {
     "sdk_ingest_copy_ms": (_i, [_vp, _i, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
     "sdk_conv_gemm": (_i, [_vp, C.POINTER(ConvGemmArgs), _vp]),
     "sdk_conv_gemm_hp": (_i, [_vp, C.POINTER(ConvGemmHpArgs), _vp]),
+    "sdk_seg_mean_hp": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _vp, _vp]),
+    "sdk_se_apply_hp": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i, _i, _i, _vp]),
+    "sdk_asp_stats_hp": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _vp, _vp]),
+    "sdk_asp_pool_hp": (_i, [_vp, _vp, _i64, _vp, _i64, _i64, _i, _i, _i, _vp, _vp]),
     "sdk_set_gemm_variant": (_i, [_i]),
     "sdk_conv_gemm_stats_bytes": (_sz, [_i, _i, _i]),
     "sdk_conv_gemm_stats_fusable": (_i, [_i, _i, _i]),

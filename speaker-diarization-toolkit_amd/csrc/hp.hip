@@ -846,7 +846,21 @@ extern "C" int sdk_conv_gemm_hp(sdk_ctx* ctx, const sdk_conv_gemm_hp_args* a, vo
   return 0;
 }
 
+// ---- the sweeps: launch helpers of the forward schedule (hp.hpp) and their exports.  The kernels read and write whole 16-byte pieces of 8
+// channels per plane (load8 / store8), so a malformed operand is refused here, by name, before anything is launched.
+#define HP_SWEEP_SHAPE(fn, B, T, C)                                                                                                \
+  SDK_REQUIRE((B) > 0 && (T) > 0 && (C) > 0 && (C) % 8 == 0, fn ": B=%d T=%d C=%d must be positive, C a multiple of 8", (B), (T), (C))
+#define HP_SWEEP_PLANES(fn, name, p, ld, lo, C)                                                                                    \
+  do {                                                                                                                             \
+    SDK_REQUIRE((ld) % 8 == 0 && (lo) % 8 == 0 && (lo) >= (C) && (ld) >= (lo) + (C),                                               \
+                fn ": bad " name " planes: ld=%lld lo=%lld must be multiples of 8 with lo >= C=%d and ld >= lo + C", (long long)(ld), (long long)(lo), (C)); \
+    SDK_REQUIRE(((uintptr_t)(p) % 16) == 0, fn ": " name "=%p must be 16-byte aligned", (const void*)(p));                          \
+  } while (0)
+
 int hp_seg_mean(sdk_ctx* ctx, const uint16_t* z, int64_t ldz, int64_t z_lo, int B, int T, int C, float* out, void* stream) {
+  SDK_REQUIRE(ctx && z && out, "sdk_seg_mean_hp: null argument");
+  HP_SWEEP_SHAPE("sdk_seg_mean_hp", B, T, C);
+  HP_SWEEP_PLANES("sdk_seg_mean_hp", "z", z, ldz, z_lo, C);
   ProfScope ps(ctx, stream, SDK_K_SE_GATE, 1.0 * B * T * C, 4.0 * B * T * C);
   hipLaunchKernelGGL(seg_mean_hp_kernel, dim3(B, ceil_div(C, 512)), dim3(256), 0, (hipStream_t)stream, z, ldz, z_lo, T, C, out);
   SDK_LAUNCH_CHECK();
@@ -855,6 +869,11 @@ int hp_seg_mean(sdk_ctx* ctx, const uint16_t* z, int64_t ldz, int64_t z_lo, int 
 
 int hp_se_apply(sdk_ctx* ctx, const uint16_t* z, int64_t ldz, int64_t z_lo, const uint16_t* x, int64_t ldx, int64_t x_lo, const float* gate,
                 uint16_t* out, int64_t ldo, int64_t o_lo, int B, int T, int C, void* stream) {
+  SDK_REQUIRE(ctx && z && x && gate && out, "sdk_se_apply_hp: null argument");
+  HP_SWEEP_SHAPE("sdk_se_apply_hp", B, T, C);
+  HP_SWEEP_PLANES("sdk_se_apply_hp", "z", z, ldz, z_lo, C);
+  HP_SWEEP_PLANES("sdk_se_apply_hp", "x", x, ldx, x_lo, C);
+  HP_SWEEP_PLANES("sdk_se_apply_hp", "out", out, ldo, o_lo, C);
   ProfScope ps(ctx, stream, SDK_K_SE_GATE, 2.0 * B * T * C, 12.0 * B * T * C);
   hipLaunchKernelGGL(se_apply_hp_kernel, dim3(B, ceil_div(T, 8)), dim3(256), 0, (hipStream_t)stream, z, ldz, z_lo, x, ldx, x_lo, gate, out, ldo, o_lo, T, C);
   SDK_LAUNCH_CHECK();
@@ -862,6 +881,9 @@ int hp_se_apply(sdk_ctx* ctx, const uint16_t* z, int64_t ldz, int64_t z_lo, cons
 }
 
 int hp_asp_stats(sdk_ctx* ctx, const uint16_t* h, int64_t ldh, int64_t h_lo, int B, int T, int C, float* out, void* stream) {
+  SDK_REQUIRE(ctx && h && out, "sdk_asp_stats_hp: null argument");
+  HP_SWEEP_SHAPE("sdk_asp_stats_hp", B, T, C);
+  HP_SWEEP_PLANES("sdk_asp_stats_hp", "h", h, ldh, h_lo, C);
   ProfScope ps(ctx, stream, SDK_K_ASP_STATS, 3.0 * B * T * C, 4.0 * B * T * C);
   hipLaunchKernelGGL(asp_stats_hp_kernel, dim3(B, ceil_div(C, 1024)), dim3(256), 0, (hipStream_t)stream, h, ldh, h_lo, T, C, out);
   SDK_LAUNCH_CHECK();
@@ -870,8 +892,28 @@ int hp_asp_stats(sdk_ctx* ctx, const uint16_t* h, int64_t ldh, int64_t h_lo, int
 
 int hp_asp_pool(sdk_ctx* ctx, const float* logits, int64_t ldl, const uint16_t* h, int64_t ldh, int64_t h_lo, int B, int T, int C, float* pooled,
                 void* stream) {
+  SDK_REQUIRE(ctx && logits && h && pooled, "sdk_asp_pool_hp: null argument");
+  HP_SWEEP_SHAPE("sdk_asp_pool_hp", B, T, C);
+  HP_SWEEP_PLANES("sdk_asp_pool_hp", "h", h, ldh, h_lo, C);
+  SDK_REQUIRE(ldl >= C, "sdk_asp_pool_hp: ldl=%lld is shorter than a row of C=%d logits", (long long)ldl, C);
   ProfScope ps(ctx, stream, SDK_K_ASP_POOL, 8.0 * B * T * C, 12.0 * B * T * C);
   hipLaunchKernelGGL(asp_pool_hp_kernel, dim3(B, ceil_div(C, 256)), dim3(256), 0, (hipStream_t)stream, logits, ldl, h, ldh, h_lo, T, C, pooled);
   SDK_LAUNCH_CHECK();
   return 0;
+}
+
+// the sweeps as entry points of their own (the parity tests call each kernel directly): the helpers above, checks included
+extern "C" int sdk_seg_mean_hp(sdk_ctx* ctx, const uint16_t* z, int64_t ldz, int64_t z_lo, int B, int T, int C, float* out, void* stream) {
+  return hp_seg_mean(ctx, z, ldz, z_lo, B, T, C, out, stream);
+}
+extern "C" int sdk_se_apply_hp(sdk_ctx* ctx, const uint16_t* z, int64_t ldz, int64_t z_lo, const uint16_t* x, int64_t ldx, int64_t x_lo,
+                               const float* gate, uint16_t* out, int64_t ldo, int64_t o_lo, int B, int T, int C, void* stream) {
+  return hp_se_apply(ctx, z, ldz, z_lo, x, ldx, x_lo, gate, out, ldo, o_lo, B, T, C, stream);
+}
+extern "C" int sdk_asp_stats_hp(sdk_ctx* ctx, const uint16_t* h, int64_t ldh, int64_t h_lo, int B, int T, int C, float* out, void* stream) {
+  return hp_asp_stats(ctx, h, ldh, h_lo, B, T, C, out, stream);
+}
+extern "C" int sdk_asp_pool_hp(sdk_ctx* ctx, const float* logits, int64_t ldl, const uint16_t* h, int64_t ldh, int64_t h_lo, int B, int T, int C,
+                               float* pooled, void* stream) {
+  return hp_asp_pool(ctx, logits, ldl, h, ldh, h_lo, B, T, C, pooled, stream);
 }

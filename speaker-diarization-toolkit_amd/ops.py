@@ -631,6 +631,37 @@ class Engine:
         check(self.lib.sdk_conv_gemm_hp(self.ctx, C.byref(g), _stream()), "sdk_conv_gemm_hp")
         return Cout, C32, S
 
+    # the precise mode's sweeps, one kernel each (sdk_*_hp in csrc/hp.hip).  A plane operand is an fp16 tensor or view [B*T, >= lo + C] taken
+    # as it is: row stride from the tensor, the lo plane `lo` columns to the right of the hi plane; the library checks the rest.
+    def seg_mean_hp(self, z, z_lo, B, T, C_, out=None):
+        """per-segment channel means of z planes -> [B, C] fp32 (out: a contiguous [B, C] fp32 tensor or view to write into)"""
+        _need(z, torch.float16, "z")
+        out = torch.empty((B, C_), dtype=torch.float32, device=self.device) if out is None else out
+        check(self.lib.sdk_seg_mean_hp(self.ctx, z.data_ptr(), z.stride(0), z_lo, B, T, C_, out.data_ptr(), _stream()), "sdk_seg_mean_hp")
+        return out
+
+    def se_apply_hp(self, z, z_lo, x, x_lo, gate, out, o_lo, B, T, C_):
+        """out planes = gate [B, C] fp32 * z + x, written into the caller's view `out` (hi plane at its column 0, lo plane o_lo to the right)"""
+        _need(z, torch.float16, "z"); _need(x, torch.float16, "x"); _need(out, torch.float16, "out"); _need(gate, torch.float32, "gate")
+        check(self.lib.sdk_se_apply_hp(self.ctx, z.data_ptr(), z.stride(0), z_lo, x.data_ptr(), x.stride(0), x_lo, gate.data_ptr(),
+                                       out.data_ptr(), out.stride(0), o_lo, B, T, C_, _stream()), "sdk_se_apply_hp")
+        return out
+
+    def asp_stats_hp(self, h, h_lo, B, T, C_, out=None):
+        """mean | std over frames of h planes -> [B, 2C] fp32"""
+        _need(h, torch.float16, "h")
+        out = torch.empty((B, 2 * C_), dtype=torch.float32, device=self.device) if out is None else out
+        check(self.lib.sdk_asp_stats_hp(self.ctx, h.data_ptr(), h.stride(0), h_lo, B, T, C_, out.data_ptr(), _stream()), "sdk_asp_stats_hp")
+        return out
+
+    def asp_pool_hp(self, logits, h, h_lo, B, T, C_, out=None):
+        """softmax over frames of fp32 logits [B*T, >= C] -> weighted mean | std of h planes -> [B, 2C] fp32"""
+        _need(h, torch.float16, "h"); _need(logits, torch.float32, "logits")
+        out = torch.empty((B, 2 * C_), dtype=torch.float32, device=self.device) if out is None else out
+        check(self.lib.sdk_asp_pool_hp(self.ctx, logits.data_ptr(), logits.stride(0), h.data_ptr(), h.stride(0), h_lo, B, T, C_,
+                                       out.data_ptr(), _stream()), "sdk_asp_pool_hp")
+        return out
+
     def se_gate_residual(self, z, x, w1t, b1, w2t, b2, B, T, split: bool = True):
         C_ = z.shape[1]
         out = torch.empty_like(z)

@@ -113,6 +113,65 @@ def test_conv_gemm_hp_256_tile_kernel(precise, M, T, N, Cin, taps, dil):
     assert float((out[0] - out[1]).abs().max()) <= 3e-6 * float(want.abs().max())
 
 
+# (M, T, N, Cin, taps, dil): segments shorter than a tile and the dispatch rule's edges (taps > 1 && T < 64, or M < 256 -> the 128^2 kernel)
+SHORT_SEGMENT_SHAPES = [
+    (1, 1, 128, 32, 1, 1),              # the smallest call
+    (9, 9, 128, 64, 3, 4),              # a short segment with a dilated halo
+    (18, 9, 128, 128, 3, 4),            # two short segments in one tile
+    (3, 3, 128, 32, 3, 2),              # halo = T - 1
+    (150, 50, 256, 96, 5, 1),           # five taps, a partial m-tile
+    (640, 40, 256, 128, 3, 3),          # M >= 256 but T < 64: the 128^2 kernel
+    (256, 64, 256, 64, 3, 4),           # the dispatch edge T = 64: four segments inside one 256-row tile
+    (260, 65, 256, 64, 3, 3),           # one full 256-row tile plus a partial tile of 4 live rows
+]
+
+
+@pytest.mark.parametrize("M,T,N,Cin,taps,dil", SHORT_SEGMENT_SHAPES)
+def test_conv_gemm_hp_short_segments(precise, M, T, N, Cin, taps, dil):
+    """sdk_conv_gemm_hp where the forward's shortest windows put it: segment-local reflection with several segment boundaries inside one
+    tile, tiles of mostly clamped rows, both sides of the 256^2 kernel's dispatch rule.  The fp32 output by the method and tolerances of
+    test_conv_gemm_hp_matches_float64, the planes with the full epilogue by those of test_conv_gemm_hp_256_tile_kernel in both
+    hp_gemm_variant 0 and 1; where the rule keeps the 256^2 kernel out, variant 0 must BE the 128^2 kernel: the same bits."""
+    eng = precise
+    g = torch.Generator().manual_seed(M + N + Cin + taps)
+    a = torch.randn(M, Cin, generator=g) * 2.0
+    w = torch.randn(N, taps * Cin, generator=g) * 0.04
+    bias, sc, sh = torch.randn(N, generator=g), torch.rand(N, generator=g) + 0.5, torch.randn(N, generator=g)
+    Ap = OPS.Engine.to_planes(a)
+    slot = WP.hp_weight_planes(w.numpy())
+    Wd = torch.from_numpy(slot.view(np.int16)).cuda()
+    pre, mag = _conv_ref64(OPS.Engine.from_planes(Ap), torch.from_numpy(WP.hp_planes_to_f64(slot, N, taps * Cin)), Cin, taps, dil, T)
+    shape = f"conv_gemm_hp M {M} T {T} N {N} Cin {Cin} taps {taps} dil {dil}"
+    # the bare product, fp32 out
+    Cp, C32, _ = eng.conv_gemm_hp(Ap.cuda(), Wd, N, Cin, taps=taps, dil=dil, T=T, out_f32=True)
+    torch.cuda.synchronize()
+    err = (C32.cpu().double() - pre).abs()
+    print(f"{shape} fp32 out: worst err / tol {float((err / mag).max()) / 1.5e-6:.3f}")
+    assert float((err / mag).max()) < 1.5e-6, float((err / mag).max())
+    assert float(err.max()) < 3e-6 * float(pre.abs().max()) + 1e-30
+    assert float((OPS.Engine.from_planes(Cp.cpu()) - C32.cpu()).abs().max()) <= 2.0 ** -21 * float(C32.abs().max())
+    # planes out with bias / ReLU / BN affine, both kernels where both are eligible
+    out, bits = {}, {}
+    for variant in (0, 1):
+        eng.set_option("hp_gemm_variant", variant)
+        try:
+            Cp, _, _ = eng.conv_gemm_hp(Ap.cuda(), Wd, N, Cin, taps=taps, dil=dil, T=T, bias=bias.cuda(), scale=sc.cuda(), shift=sh.cuda(), relu=True)
+            torch.cuda.synchronize()
+        finally:
+            eng.set_option("hp_gemm_variant", 0)
+        bits[variant] = Cp.cpu()
+        out[variant] = OPS.Engine.from_planes(bits[variant]).double()
+    want = torch.relu(pre + bias.double()) * sc.double() + sh.double()
+    tol = 1.5e-6 * mag * sc.double() + 2.0 ** -21 * want.abs() + 1e-7
+    for variant in (0, 1):
+        err = (out[variant] - want).abs()
+        print(f"{shape} planes out variant {variant}: worst err / tol {float((err / tol).max()):.3f}")
+        assert (err <= tol).all(), (variant, float((err / tol).max()), float(err.max()))
+    assert float((out[0] - out[1]).abs().max()) <= 3e-6 * float(want.abs().max())
+    if not (M >= 256 and N % 256 == 0 and (taps == 1 or T >= 64)):
+        assert torch.equal(bits[0].view(torch.int16), bits[1].view(torch.int16)), "the 256^2 kernel ran outside its dispatch rule"
+
+
 @pytest.mark.parametrize("M,T,N,Cin,taps,dil", [(40200, 201, 1024, 64, 1, 1), (20100, 201, 1024, 96, 3, 2), (66000, 200, 1024, 32, 1, 1), (40200, 201, 2048, 32, 1, 1)])
 def test_conv_gemm_hp_half_tile_tail_is_bit_identical(precise, M, T, N, Cin, taps, dil):
     """Round 5: the precise GEMM's 256^2 kernel computes a mostly idle last tile round as 128 x 256 half tiles (as conv_gemm256_kernel does): the
@@ -205,6 +264,67 @@ def test_ecapa_forward_precise_vs_unrounded_oracle(precise):
 
 
 PRECISE_SCORE_BOUND = 1e-5          # north_star: "cosine scores within 1e-5 fp32"
+
+
+def _unit_profiles():
+    import importlib, sys
+    sys.path.insert(0, str(ROOT))
+    return torch.from_numpy(importlib.import_module("bench").unit_rows(100, 192, seed=1)).double()
+
+
+def _judge_embeddings(emb, want, what):
+    """the forward test's element-wise criterion and the product's own: every cosine score against 100 seeded unit profiles within 1e-5"""
+    a, b = emb.double(), want.double()
+    assert not torch.isnan(a).any()
+    d_el = float((a - b).abs().max()) / float(b.abs().max())
+    P = _unit_profiles()
+    d_score = float(((a / a.norm(dim=1, keepdim=True)) @ P.T - (b / b.norm(dim=1, keepdim=True)) @ P.T).abs().max())
+    print(f"{what}: max |d emb| / max |emb| {d_el:.3g} (bound 3e-6), max |d score| {d_score:.3g} (bound {PRECISE_SCORE_BOUND:g}): "
+          f"worst err / bound {max(d_el / 3e-6, d_score / PRECISE_SCORE_BOUND):.3f}")
+    return d_el, d_score
+
+
+@pytest.mark.parametrize("B,T", [(3, 50), (2, 9), (1, 201), (2, 301)])
+@pytest.mark.parametrize("cfg_name", ["full", "small"])
+def test_ecapa_forward_precise_off_its_one_shape(precise, cfg_name, B, T):
+    """the whole precise forward at the window lengths the default mode's forward is tested at (short segments: the 128^2 GEMM and the
+    sweeps' T < 8 paths; 301: past one ASP block), C = 1024 and test_gpu_kernels' small configuration, against the un-rounded oracle"""
+    from test_gpu_kernels import SMALL
+    g = torch.Generator().manual_seed(40 + T)
+    feats = torch.randn(B, T, 80, generator=g) * 4.0
+    f96 = torch.zeros(B * T, 96)
+    f96[:, :80] = feats.reshape(-1, 80)
+    if cfg_name == "full":
+        eng, weights = precise, W.synthetic_weights(0)
+        orc = oecapa.EcapaOracle(weights, "fp32", torch.float64)
+    else:
+        weights = W.synthetic_weights(3, SMALL)
+        eng = OPS.Engine(0, weights=weights, cfg=SMALL, bias_correction=False)
+        eng.set_precision(1)
+        orc = oecapa.EcapaOracle(weights, "fp32", torch.float64, n_dilations=SMALL.dilations, scale=SMALL.res2net_scale)
+    emb = eng.ecapa_forward(OPS.Engine.to_planes(f96).cuda(), B, T).cpu()
+    want = orc.embed(feats)
+    d_el, d_score = _judge_embeddings(emb, want, f"precise ecapa forward {cfg_name} B {B} T {T}")
+    assert float((emb - want).abs().max()) < 3e-6 * float(want.abs().max())
+    assert d_score <= PRECISE_SCORE_BOUND
+
+
+@pytest.mark.parametrize("B,T", [(3, 50), (1, 20), (2, 301)])
+def test_xvector_forward_precise_off_its_one_shape(engine, B, T):
+    """the x-vector family's precise forward at feature level (planes in, sdk_conv_gemm_hp per frame layer, asp_stats_hp pooling)
+    against the fp32 model with float64 accumulation: the 1e-5 score criterion of test_xvector_precise_mode_meets_1e5"""
+    from oracle import xvector as oxv
+    XV = sub("xvector")
+    w = XV.synthetic_weights(0)
+    xv = XV.XVector(engine, w, precision=1)
+    g = torch.Generator().manual_seed(60 + T)
+    feats = torch.randn(B, T, 80, generator=g) * 3.0
+    f96 = torch.zeros(B * T, 96)
+    f96[:, :80] = feats.reshape(-1, 80)
+    emb = xv.forward(OPS.Engine.to_planes(f96).cuda(), B, T).cpu()
+    want = oxv.xvector_embed(w, feats, mode="fp32", acc=torch.float64)
+    _, d_score = _judge_embeddings(emb, want, f"precise x-vector forward B {B} T {T}")
+    assert d_score <= PRECISE_SCORE_BOUND
 
 
 def test_pcm_to_score_within_1e5_in_precise_mode(precise):
