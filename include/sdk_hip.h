@@ -33,6 +33,8 @@
  *     sdk_affinity_matvec_workspace_bytes  sdk_affinity_matvec  sdk_rows_gram_workspace_bytes  sdk_rows_gram
  *     sdk_rows_apply  sdk_chol_inverse  sdk_rows_unit  sdk_kmeans_mindist  sdk_kmeans_assign            k6 (driven by cluster.py)
  *     sdk_centroid_linkage_workspace_bytes  sdk_centroid_linkage                                    k6 threshold path (cluster.agglomerative_cluster)
+ *     sdk_linked_linkage_workspace_bytes  sdk_linked_linkage                                        speakers across recordings: constrained, early-stopping
+ *                                                                                                       centroid linkage (cluster.link_rows, diarize.link_speakers)
  *     sdk_segmentation_frames  sdk_segmentation_workspace_bytes  sdk_segmentation_forward               speaker segmentation (PyanNet, segmentation.py)
  *     sdk_powerset_decode  sdk_diarize_masks  sdk_resnet_last_map_frames  sdk_resnet_masked_workspace_bytes
  *     sdk_resnet_forward_masked  sdk_diarize_frames  sdk_diarize_reconstruct  sdk_diarize_centroids  sdk_diarize_assign
@@ -788,6 +790,24 @@ int sdk_kmeans_assign(sdk_ctx* ctx, const float* R, int n, int k, const float* c
 size_t sdk_centroid_linkage_workspace_bytes(const int32_t* offsets, int G, int dim);
 int sdk_centroid_linkage(sdk_ctx* ctx, const float* E, int ldE, int dim, const int32_t* offsets, int G, double* Z, int32_t* status,
                          void* workspace, size_t ws_bytes, void* stream);
+
+/* ---- linked centroid linkage: sdk_centroid_linkage with forbidden pairs and an early stop (the join of speakers across recordings:
+ *      cluster.link_rows, diarize.link_speakers).  E, offsets, Z's layout, distances, the update, ties and the limits are sdk_centroid_linkage's.
+ *   group    DEVICE int32 [N_total]: rows i != j of one problem with group[i] == group[j] >= 0 are forbidden to each other (a negative group
+ *            is a free row); two clusters are forbidden to each other when any row of one is forbidden to any row of the other.
+ *   stop     a distance >= 0, or +inf.  Each step merges the ALLOWED live pair of least centroid distance; the problem ends when no allowed
+ *            pair is left or that least distance exceeds stop.
+ *   merges   DEVICE int32 [G]: the merges made.  Rows merges[g] .. n_g - 2 of the problem's Z are zero.
+ *   status   as sdk_centroid_linkage's (1 is judged on the computed distances before any pair is masked; merges[g] is then 0 and the
+ *            problem's Z rows are not written).
+ *   No forbidden pair and stop = +inf: Z is sdk_centroid_linkage's bit for bit.  stop = t: merges[g] is the number of leading rows of the
+ *   stop = +inf run whose height is <= t (the first row above t ends the problem), and those rows are the same.
+ *   workspace: sdk_linked_linkage_workspace_bytes (the same size as sdk_centroid_linkage's).  Refusals (a null or misaligned pointer, group
+ *   included; ldE < dim; bad offsets; a short workspace; stop negative or NaN) return non-zero, name the value and launch nothing.
+ *   sdk_set_option "ahc_distances_only" applies here too (tools/link_bench.py). */
+size_t sdk_linked_linkage_workspace_bytes(const int32_t* offsets, int G, int dim);
+int sdk_linked_linkage(sdk_ctx* ctx, const float* E, int ldE, int dim, const int32_t* group, const int32_t* offsets, int G, double stop,
+                       double* Z, int32_t* merges, int32_t* status, void* workspace, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

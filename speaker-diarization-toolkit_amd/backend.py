@@ -533,6 +533,34 @@ class Backend(EmbeddingBackend):
             if dz.eng.precision != prec:
                 dz.eng.set_precision(prec)                       # the front end's format goes back to the selected family's contract
 
+    def link_speakers(self, results, threshold: float = 0.7045654963945799, min_speech_s: float = 0.0, candidates=None):
+        """One speaker inventory for the results of diarize_many (diarize.link_speakers, which states the rule): the local speakers of
+        different recordings joined into global ones by a constrained centroid linkage on the device - two speakers of one recording never
+        join - cut at `threshold` (PyAnnote's within-recording default: untuned for centroids across recordings, pass your own).
+        candidates: profile dicts as identify_speaker takes them, loaded through the same store path; each enrolled speaker gives ONE row, the
+        float64 mean of their enrolled unit embeddings, re-normalised, and no global speaker ever holds two of them.  The result
+        (diarize.SpeakerLinks) then carries names [n_global]: the speaker_id, or None.  The centroids of a diarization live in the ResNet34's
+        space, so candidates need SDK_MODEL=resnet34 (their embeddings are then the diarizer's own)."""
+        if self.lite:
+            raise ValueError("link_speakers needs the torch engine: not available with SDK_NO_TORCH=1")
+        if candidates is not None and self.model != "resnet34":
+            raise ValueError(f"link_speakers: candidates are enrolled in the {self.model!r} embedding space (SDK_MODEL), the centroids of a diarization "
+                             "in the diarizer's ResNet34 space: enrol and link with SDK_MODEL=resnet34")
+        from .diarize import link_speakers
+        profiles, names = None, None
+        if candidates is not None:
+            batch = self._load_candidates(candidates)
+            names = list(dict.fromkeys(batch.speaker_ids))                       # one row per speaker, in order of first appearance
+            M = np.asarray(batch.matrix, dtype=np.float64).reshape(len(batch), -1)
+            M = M / np.maximum(np.linalg.norm(M, axis=1, keepdims=True), 1e-12)
+            sid = np.asarray([names.index(s) for s in batch.speaker_ids], dtype=np.int64)
+            mean = np.stack([M[sid == i].mean(axis=0) for i in range(len(names))]) if names else np.zeros((0, int(self.embedding_dim)))
+            profiles = (mean / np.maximum(np.linalg.norm(mean, axis=1, keepdims=True), 1e-12)).astype(np.float32)
+        links = link_speakers(self.engine(), results, threshold, min_speech_s, profiles)
+        if names is not None:
+            links.names = [names[p] if p >= 0 else None for p in links.profile.tolist()]
+        return links
+
     # ---- a2: enroll (base.py:107-128) ---------------------------------------------------------
     def _enroll_vector(self, audio_path: Path, segments: Optional[List[Tuple[float, float]]] = None):
         """The unit mean embedding of a recording's windows (what enroll_speaker stores) and the windows' spans."""

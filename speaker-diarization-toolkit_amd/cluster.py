@@ -283,6 +283,35 @@ def fcluster_distance(Z: np.ndarray, t: float) -> np.ndarray:
     return _flat_partition(Z, n, cut_level(Z, t))
 
 
+# ------------------------------------------------------------------ linked centroid linkage: rows that must stay apart (speakers across recordings)
+@dataclass
+class LinkResult:
+    labels: np.ndarray            # [N] int32 canonical (order of first appearance)
+    linkage: np.ndarray           # [N - 1, 4] float64: the merges made, in scipy's layout and numbering; the rows from n_merges on are zero
+    n_merges: int
+
+
+def link_rows(provider, E, group, threshold: float) -> LinkResult:
+    """Clusters of the unit rows E ([N, d] fp32 on the provider's device) in which no two rows of one group meet: the linked centroid linkage
+    (Engine.linked_linkage, sdk_linked_linkage; the rule heads csrc/ahc.hip) run with stop = threshold, so the device makes only the merges at
+    or below it.  group [N] ints: rows with the same group >= 0 are forbidden to each other, and so are clusters that hold such rows; a negative
+    group is a free row.  labels = _flat_partition(Z, N, n_merges), canonical.  Parity with any outside tool is unpinned: the tests pin this rule.
+    N == 0 and N == 1 are answered on the host."""
+    N = int(E.shape[0])
+    if N <= 1:
+        return LinkResult(np.zeros(N, np.int32), np.zeros((0, 4)), 0)
+    g = np.ascontiguousarray(group.detach().cpu().numpy() if isinstance(group, torch.Tensor) else group).astype(np.int32)
+    if g.shape != (N,):
+        raise ValueError(f"link_rows: group must be [N] = [{N}], got {list(g.shape)}")
+    if not float(threshold) >= 0.0:
+        raise ValueError(f"link_rows: threshold={threshold} (a distance >= 0)")
+    gd = torch.from_numpy(g).to(E.device) if isinstance(E, torch.Tensor) else g
+    Z, merges = provider.linked_linkage(E, gd, None, float(threshold))
+    Z = Z.cpu().numpy()
+    m = int(merges.cpu().numpy()[0])
+    return LinkResult(_flat_partition(Z, N, m), Z, m)
+
+
 # ------------------------------------------------------------------ bounds on the speaker count (`speakers=`)
 # bounds      (this build's statement of pyannote's num_speakers / min_speakers / max_speakers, written from the published description; no
 #             pyannote code is on hand: PARITY IS UNPINNED, the tests pin THIS rule).  speakers = None: no bound, today's path.  An int k >= 1:

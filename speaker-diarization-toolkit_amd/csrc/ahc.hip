@@ -14,6 +14,23 @@
 //                      merge when many rows point at one growing cluster: tight clusters of 10^4 rows took minutes that way.)  Only
 //                      __syncthreads inside the workgroup: nothing waits on another workgroup.
 //
+// Linked centroid linkage (sdk_linked_linkage; the LINK instantiations of the dist and merge kernels) - the rule:
+//   input    unit rows E [N, d] fp32, group [N] int32, problems by offsets as above, stop: a float64 >= 0 or +inf
+//   forbidden rows i != j of a problem are forbidden to each other when group[i] == group[j] >= 0 (a negative group is a free row); two clusters
+//            are forbidden to each other when any row of one is forbidden to any row of the other
+//   merges   distances, the Lance-Williams update, slot handling, tie rules and Z's layout and numbering are those above; each step merges the
+//            ALLOWED live pair of least centroid distance (ties: lowest row slot, then lowest neighbour); the problem ends when no allowed pair
+//            is left or when that least distance exceeds stop
+//   output   merges[g] = the merges made; rows merges[g] .. of the problem's Z are zero.  No forbidden pair and stop = +inf: Z is
+//            sdk_centroid_linkage's bit for bit.  stop = t: merges = cluster.cut_level of the stop = +inf run and the rows before it are the
+//            same (every step is a global minimum over the allowed pairs, so fcluster_distance's argument carries over)
+//   method   ahc_dist_kernel<true> stores +inf for a forbidden pair AFTER it has judged the computed distance (status 1 is decided on the
+//            unmasked value; the diagonal is never masked, so a NaN / Inf row still shows itself).  centroid_lw then carries the constraint:
+//            n_x inf^2 + .. - finite = +inf, and d_xy of a merged pair is finite, so no inf - inf arises; no scan ever picks +inf (every
+//            comparison is a strict < against a running minimum that starts at +inf), so a row without an allowed neighbour holds
+//            (nnd = +inf, nn = -1) and the pair search returning no row is the normal end.  A stale finite bound towards a pair that became
+//            forbidden is caught by the lazy check D[x][y] == bound and rescanned like any other stale bound.
+//
 // Every index into D is int64 (a batch's distance storage passes 2^31 elements long before HBM runs out).  This file is compiled with
 // -ffp-contract=off (Makefile): the update must round exactly as scipy's _centroid does.
 #include <math.h>
@@ -83,8 +100,9 @@ __device__ inline int find_prob(int G, int64_t v, F key) {
   return lo;
 }
 
+template <bool LINK>
 __global__ void __launch_bounds__(256) ahc_dist_kernel(const float* __restrict__ E, int64_t ldE, int dim, const AhcProb* __restrict__ tab, int G,
-                                                       char* ws, int32_t* status) {
+                                                       char* ws, int32_t* status, const int32_t* __restrict__ group) {
   __shared__ double sm[2][TILE][KC + 1];       // the two row blocks of a k-chunk; afterwards the mirrored [64][65] output tile
   double (*sa)[KC + 1] = sm[0];
   double (*sb)[KC + 1] = sm[1];
@@ -143,17 +161,28 @@ __global__ void __launch_bounds__(256) ahc_dist_kernel(const float* __restrict__
   }
   Region R = region(ws, p);
   bool bad = false;
+  int gi[4], gj[4];                             // LINK: the groups of this thread's rows and columns (-1: free, also past the end)
+  if constexpr (LINK) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const int64_t i = i0 + ty + 16 * a, j = j0 + tx + 16 * a;
+      gi[a] = i < n ? group[p.row0 + i] : -1;
+      gj[a] = j < n ? group[p.row0 + j] : -1;
+    }
+  }
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
       const int64_t i = i0 + ty + 16 * a, j = j0 + tx + 16 * b;
-      const double v = sqrt(acc[a][b]);
-      acc[a][b] = v;
-      if (i < n && j < n) {
-        bad |= !isfinite(v);
-        R.D[i * n + j] = v;
+      double v = sqrt(acc[a][b]);
+      const bool in = i < n && j < n;
+      if (in) bad |= !isfinite(v);              // judged before any masking
+      if constexpr (LINK) {
+        if (i != j && gi[a] >= 0 && gi[a] == gj[b]) v = INFINITY;
       }
+      acc[a][b] = v;
+      if (in) R.D[i * n + j] = v;
     }
   if (bad) status[g] = 1;
   if (ti == tj) return;                         // a diagonal tile wrote both triangles
@@ -215,7 +244,9 @@ __device__ inline double centroid_lw(double dxz, double dyz, double dxy, int nx,
   return sqrt(fmax(0.0, t / (double)(nx + ny)));
 }
 
-__global__ void __launch_bounds__(MERGE_THREADS) ahc_merge_kernel(const AhcProb* __restrict__ tab, int lds_rows, char* ws, double* Z, int32_t* status) {
+template <bool LINK>
+__global__ void __launch_bounds__(MERGE_THREADS) ahc_merge_kernel(const AhcProb* __restrict__ tab, int lds_rows, char* ws, double* Z, int32_t* status,
+                                                                  double stop, int32_t* merges) {
   extern __shared__ __align__(16) char lds[];
   __shared__ double red_v[3][MERGE_WAVES];      // [0]: the pair search; [1], [2]: the rescans, alternating
   __shared__ int red_i[3][MERGE_WAVES];
@@ -239,6 +270,11 @@ __global__ void __launch_bounds__(MERGE_THREADS) ahc_merge_kernel(const AhcProb*
   double* D = R.D;
   double* Zg = Z + p.zrow * 4;
   __syncthreads();
+  // LINK: the problem ends after t merges (uniform): the rest of its Z is zero
+  auto finish = [&](int64_t t) {
+    for (int64_t e = t * 4 + tid; e < (n - 1) * 4; e += MERGE_THREADS) Zg[e] = 0.0;
+    if (tid == 0) merges[g] = (int32_t)t;
+  };
 
   // nearest live j > r of row r (ties -> lowest j), skipping slot `dead`, by the whole workgroup; thread 0 stores it after a barrier.  The
   // partial slots alternate (1, 2) between calls: the next call may write while a slow thread still reads this one's.
@@ -294,6 +330,12 @@ __global__ void __launch_bounds__(MERGE_THREADS) ahc_merge_kernel(const AhcProb*
       __syncthreads();
       bv = red_v[0][0]; bi = red_i[0][0];
       for (int w = 1; w < MERGE_WAVES; ++w) take_min(bv, bi, red_v[0][w], red_i[0][w]);
+      if constexpr (LINK) {
+        if (bi < 0) {                           // no allowed pair left: the normal end
+          finish(t);
+          return;
+        }
+      }
       if (bi < 0 || tries > n) {                // no finite pair left (non-finite distances); a bound is never rescanned twice per merge
         if (tid == 0) status[g] = 2;
         return;
@@ -302,6 +344,12 @@ __global__ void __launch_bounds__(MERGE_THREADS) ahc_merge_kernel(const AhcProb*
       if (D[x * n + y] == bv) break;            // uniform: every thread read the same values after the barrier
       rescan(x, -1);
       __syncthreads();
+    }
+    if constexpr (LINK) {
+      if (dxy > stop) {                         // the accepted minimum is exact: every allowed pair is above stop
+        finish(t);
+        return;
+      }
     }
     const int nx = sz[x], ny = sz[y];
     // B + C: emit, Lance-Williams update of row / column y, bound upkeep of the rows below y (scipy's order: a row that pointed at x now
@@ -355,6 +403,7 @@ __global__ void __launch_bounds__(MERGE_THREADS) ahc_merge_kernel(const AhcProb*
     rescan(y, x);
     __syncthreads();
   }
+  if constexpr (LINK) finish(n - 1);
 }
 
 }  // namespace
@@ -365,12 +414,15 @@ size_t ahc_workspace_bytes(const int32_t* offsets, int G) {
   return (size_t)b;
 }
 
-int ahc_launch(sdk_ctx* ctx, const float* E, int ldE, int dim, const int32_t* offsets, int G, double* Z, int32_t* status, void* ws, void* stream) {
+namespace {
+// group == nullptr: sdk_centroid_linkage (stop and merges unused); else sdk_linked_linkage
+int launch_all(const char* fn, sdk_ctx* ctx, const float* E, int ldE, int dim, const int32_t* group, const int32_t* offsets, int G, double stop, double* Z,
+               int32_t* merges, int32_t* status, void* ws, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   AhcProb* tab = (AhcProb*)ws;
   int64_t tiles = 0;
   for (int g = 0; g < G; ++g) tiles += tiles_of((int64_t)offsets[g + 1] - offsets[g]);
-  SDK_REQUIRE(tiles < (int64_t)INT32_MAX, "sdk_centroid_linkage: %lld distance tiles exceed one launch", (long long)tiles);
+  SDK_REQUIRE(tiles < (int64_t)INT32_MAX, "%s: %lld distance tiles exceed one launch", fn, (long long)tiles);
   int64_t off = table_bytes(G), max_n = 0;
   tiles = 0;
   AhcTableArgs a;
@@ -391,7 +443,12 @@ int ahc_launch(sdk_ctx* ctx, const float* E, int ldE, int dim, const int32_t* of
   }
   const int64_t n_total = (int64_t)offsets[G] - offsets[0];
   SDK_HIP_OK(hipMemsetAsync(status, 0, (size_t)G * 4, s));
-  hipLaunchKernelGGL(ahc_dist_kernel, dim3((unsigned)tiles), dim3(256), 0, s, E, (int64_t)ldE, dim, (const AhcProb*)tab, G, (char*)ws, status);
+  if (group) {
+    SDK_HIP_OK(hipMemsetAsync(merges, 0, (size_t)G * 4, s));
+    hipLaunchKernelGGL(ahc_dist_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, s, E, (int64_t)ldE, dim, (const AhcProb*)tab, G, (char*)ws, status, group);
+  } else {
+    hipLaunchKernelGGL(ahc_dist_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, s, E, (int64_t)ldE, dim, (const AhcProb*)tab, G, (char*)ws, status, group);
+  }
   SDK_LAUNCH_CHECK();
   hipLaunchKernelGGL(ahc_nn_kernel, dim3((unsigned)((n_total + 3) / 4)), dim3(256), 0, s, (const AhcProb*)tab, G, n_total, (char*)ws);
   SDK_LAUNCH_CHECK();
@@ -399,8 +456,23 @@ int ahc_launch(sdk_ctx* ctx, const float* E, int ldE, int dim, const int32_t* of
   // per-row state in LDS up to 8192 rows (16 B per row: nnd, nn, sz); larger problems keep it in the workspace
   const int lds_rows = (int)(max_n < 8192 ? max_n : 8192);
   const int lds = lds_rows * 16;
-  if (lds > 64 * 1024 && sdk_lds_optin(ctx, (const void*)ahc_merge_kernel, 8192 * 16)) return 1;
-  hipLaunchKernelGGL(ahc_merge_kernel, dim3(G), dim3(MERGE_THREADS), lds, s, (const AhcProb*)tab, lds_rows, (char*)ws, Z, status);
+  if (group) {
+    if (lds > 64 * 1024 && sdk_lds_optin(ctx, (const void*)ahc_merge_kernel<true>, 8192 * 16)) return 1;
+    hipLaunchKernelGGL(ahc_merge_kernel<true>, dim3(G), dim3(MERGE_THREADS), lds, s, (const AhcProb*)tab, lds_rows, (char*)ws, Z, status, stop, merges);
+  } else {
+    if (lds > 64 * 1024 && sdk_lds_optin(ctx, (const void*)ahc_merge_kernel<false>, 8192 * 16)) return 1;
+    hipLaunchKernelGGL(ahc_merge_kernel<false>, dim3(G), dim3(MERGE_THREADS), lds, s, (const AhcProb*)tab, lds_rows, (char*)ws, Z, status, stop, merges);
+  }
   SDK_LAUNCH_CHECK();
   return 0;
+}
+}  // namespace
+
+int ahc_launch(sdk_ctx* ctx, const float* E, int ldE, int dim, const int32_t* offsets, int G, double* Z, int32_t* status, void* ws, void* stream) {
+  return launch_all("sdk_centroid_linkage", ctx, E, ldE, dim, nullptr, offsets, G, 0.0, Z, nullptr, status, ws, stream);
+}
+
+int link_launch(sdk_ctx* ctx, const float* E, int ldE, int dim, const int32_t* group, const int32_t* offsets, int G, double stop, double* Z, int32_t* merges,
+                int32_t* status, void* ws, void* stream) {
+  return launch_all("sdk_linked_linkage", ctx, E, ldE, dim, group, offsets, G, stop, Z, merges, status, ws, stream);
 }

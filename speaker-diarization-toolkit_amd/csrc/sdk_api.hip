@@ -812,3 +812,26 @@ extern "C" int sdk_centroid_linkage(sdk_ctx* ctx, const float* E, int ldE, int d
   SDK_REQUIRE(ws_bytes >= need, "sdk_centroid_linkage: workspace of %zu bytes, %zu needed", ws_bytes, need);
   return ahc_launch(ctx, E, ldE, dim, offsets, G, Z, status, workspace, stream);
 }
+
+// ------------------------------------------------------------------------------ linked centroid linkage (ahc.hip, the LINK kernels)
+extern "C" size_t sdk_linked_linkage_workspace_bytes(const int32_t* offsets, int G, int dim) {
+  if (check_ahc_offsets("sdk_linked_linkage_workspace_bytes", offsets, G, dim)) return 0;
+  return ahc_workspace_bytes(offsets, G);
+}
+
+extern "C" int sdk_linked_linkage(sdk_ctx* ctx, const float* E, int ldE, int dim, const int32_t* group, const int32_t* offsets, int G, double stop,
+                                  double* Z, int32_t* merges, int32_t* status, void* workspace, size_t ws_bytes, void* stream) {
+  SDK_REQUIRE(ctx && E && group && Z && merges && status && workspace,
+              "sdk_linked_linkage: null argument (ctx=%p E=%p group=%p Z=%p merges=%p status=%p workspace=%p)", (void*)ctx, (const void*)E,
+              (const void*)group, (void*)Z, (void*)merges, (void*)status, workspace);
+  if (int rc = check_ahc_offsets("sdk_linked_linkage", offsets, G, dim)) return rc;
+  SDK_REQUIRE(ldE >= dim, "sdk_linked_linkage: ldE=%d < dim=%d", ldE, dim);
+  SDK_REQUIRE(stop >= 0.0, "sdk_linked_linkage: stop=%g (a distance >= 0, or +inf for every allowed merge)", stop);     // false for a NaN too
+  SDK_REQUIRE((uintptr_t)E % 4 == 0 && (uintptr_t)group % 4 == 0 && (uintptr_t)Z % 8 == 0 && (uintptr_t)merges % 4 == 0 && (uintptr_t)status % 4 == 0 &&
+                  (uintptr_t)workspace % 256 == 0,
+              "sdk_linked_linkage: misaligned pointer (E=%p needs 4, group=%p needs 4, Z=%p needs 8, merges=%p needs 4, status=%p needs 4, workspace=%p "
+              "needs 256 bytes)", (const void*)E, (const void*)group, (void*)Z, (void*)merges, (void*)status, workspace);
+  const size_t need = ahc_workspace_bytes(offsets, G);
+  SDK_REQUIRE(ws_bytes >= need, "sdk_linked_linkage: workspace of %zu bytes, %zu needed", ws_bytes, need);
+  return link_launch(ctx, E, ldE, dim, group, offsets, G, stop, Z, merges, status, workspace, stream);
+}

@@ -831,6 +831,50 @@ class Engine:
             raise err
         return Z
 
+    def linked_linkage(self, E: torch.Tensor, group: torch.Tensor, offsets=None, stop=None):
+        """E [N, d] fp32 unit rows, group [N] int32 (device) -> (Z float64 [N - G, 4], merges int32 [G]) on the device: the linked centroid
+        linkage of every problem (sdk_linked_linkage; the rule heads csrc/ahc.hip).  Rows of one problem that share a group >= 0 never
+        share a cluster (a negative group is a free row); each step merges the allowed pair of least centroid distance and the problem ends
+        when none is left or that distance exceeds stop (None: +inf).  Problem g's rows of Z start at offsets[g] - g as in centroid_linkage;
+        the rows from merges[g] on are zero.  Raises ValueError naming the problem when one holds a non-finite row, as centroid_linkage
+        does (.linkage, .merges and .status on the exception)."""
+        _need(E, torch.float32, "E")
+        _need(group, torch.int32, "group")
+        if E.dim() != 2 or E.stride(1) != 1:
+            E = E.contiguous()
+        N, d = E.shape
+        if group.dim() != 1 or group.numel() != N:
+            raise ValueError(f"linked_linkage: group must be [N] = [{N}], got {list(group.shape)}")
+        group = group.contiguous()
+        stop = float("inf") if stop is None else float(stop)
+        if not stop >= 0.0:
+            raise ValueError(f"linked_linkage: stop={stop} (a distance >= 0, or None / +inf for every allowed merge)")
+        off = np.asarray([0, N] if offsets is None else offsets, dtype=np.int64)
+        if off.ndim != 1 or off.size < 2 or off[0] != 0 or off[-1] != N:
+            raise ValueError(f"linked_linkage: offsets must run from 0 to N = {N}, got {off.tolist()[:8]}")
+        off32 = np.ascontiguousarray(off.astype(np.int32))
+        G = off32.size - 1
+        op = off32.ctypes.data_as(C.POINTER(C.c_int32))
+        nbytes = self.lib.sdk_linked_linkage_workspace_bytes(op, G, d)
+        if nbytes == 0:
+            raise SdkError(f"sdk_linked_linkage_workspace_bytes: {self.lib.sdk_last_error().decode()}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        Zbuf = torch.empty((max(N - G, 1), 4), dtype=torch.float64, device=self.device)   # never a null pointer
+        merges = torch.empty((G,), dtype=torch.int32, device=self.device)
+        status = torch.empty((G,), dtype=torch.int32, device=self.device)
+        check(self.lib.sdk_linked_linkage(self.ctx, E.data_ptr(), E.stride(0), d, group.data_ptr(), op, G, stop, Zbuf.data_ptr(), merges.data_ptr(),
+                                          status.data_ptr(), ws.data_ptr(), nbytes, _stream()), "sdk_linked_linkage")
+        Z = Zbuf[:N - G]
+        st = status.cpu().numpy()
+        bad = np.flatnonzero(st)
+        if bad.size:
+            g = int(bad[0])
+            err = ValueError(f"linked_linkage: problem {g} (rows {int(off[g])} .. {int(off[g + 1])}) has a non-finite row or distance "
+                             f"(status {int(st[g])}); problems with one: {bad.tolist()[:16]}")
+            err.linkage, err.merges, err.status = Z, merges, st     # the other problems' rows of Z are valid
+            raise err
+        return Z, merges
+
     # ---- VBx clustering (cluster.vbx_cluster, plda.py; csrc/vbx.hip): nothing here synchronises with the host except the range check of rows
     @staticmethod
     def _vbx_rows(name: str, E: torch.Tensor, rows: torch.Tensor, check_rows: bool) -> int:
