@@ -44,6 +44,7 @@
  *     sdk_vbx_hmm_workspace_bytes  sdk_vbx_hmm                                                          VBx with its HMM, rows in time order (loop_prob > 0)
  *     sdk_cohort_stats_workspace_bytes  sdk_cohort_stats  sdk_affinity_topk_snorm                       adaptive score normalisation (snorm.py)
  *     sdk_kmeans_rows_workspace_bytes  sdk_kmeans_rows                                                  spherical k-means on unit rows (cluster.kmeans_cluster)
+ *     sdk_stream_state_bytes  sdk_stream_reset  sdk_stream_step  sdk_stream_flush  sdk_stream_centroids streaming diarization: online speaker tracking (stream.py)
  * BUILDING BLOCKS AND KNOBS - exported for the parity tests and the A/B tools, free to change between rounds, not for binding:
  *     sdk_conv_gemm*  sdk_colstats_finish  sdk_res2net_chain*  sdk_se_*  sdk_asp_*  sdk_rows_fc  (pieces of sdk_ecapa_forward)
  *     sdk_resnet_conv2d  (piece of sdk_resnet_forward)  sdk_resnet_masked_pool  (piece of sdk_resnet_forward_masked)
@@ -808,6 +809,49 @@ int sdk_centroid_linkage(sdk_ctx* ctx, const float* E, int ldE, int dim, const i
 size_t sdk_linked_linkage_workspace_bytes(const int32_t* offsets, int G, int dim);
 int sdk_linked_linkage(sdk_ctx* ctx, const float* E, int ldE, int dim, const int32_t* group, const int32_t* offsets, int G, double stop,
                        double* Z, int32_t* merges, int32_t* status, void* workspace, size_t ws_bytes, void* stream);
+
+/* ---- streaming diarization (stream.py states the rule; csrc/stream.hip): a bank of R live streams steps together.  The embedding of the
+ *      streams' due chunks is one ordinary batch (sdk_segmentation_forward .. sdk_resnet_forward_masked, sdk_l2norm); everything after it -
+ *      the speaker inventory that grows online, the constrained mapping of a chunk's local speakers onto it, the rolling stitch that emits
+ *      frames once their latency has passed - is ONE launch per bank step, one workgroup per stream, on a state block that stays on the device.
+ *   state    DEVICE, 256-byte aligned, sdk_stream_state_bytes(R, capacity, d) bytes (0 for arguments the calls refuse), opaque.  Per stream:
+ *            the emission frontier and the ring's reach (int64), K and the counts n_k (int32 [64]); the float64 sums S [capacity][d] and
+ *            the unit centroids S_k / ||S_k|| [capacity][d], renewed whenever a sum changes; the ring of SDK_STREAM_RING frames: chunk
+ *            count and count sum (uint16 each) and act [frame][capacity rounded up to 8] uint16.
+ *   which / active   DEVICE uint8 [R]: streams with 0 are left alone - their state and their rows of every output stay bit for bit.
+ *            sdk_stream_reset alone takes NULL: every stream.
+ *   sdk_stream_reset      K = 0, frontier = reach = 0 (sums and ring need no clearing: a founder overwrites its sum, the ring is cleared
+ *                         as it comes into reach).  A fresh state block must be reset before its first step.
+ *   sdk_stream_step       stream r's chunk: unit rows E [3 r .. 3 r + 2][d] fp32, info [r][3][4] and cls [r][F] (sdk_diarize_masks,
+ *                         sdk_powerset_decode), starts [r] int64 = the chunk's first sample.  The chunks of a stream must come in the order
+ *                         of their starts and advance by hop (the last one by less); hop >= 270 and latency >= hop are in samples,
+ *                         hold = (latency - hop) / 270 frames, and hold + hop / 270 + 2 <= SDK_STREAM_RING: the ring holds every frame
+ *                         between the frontier and the newest chunk's reach (a latency of 10 s at any hop fits); delta_new in [0, 2]; max_speakers >= 0 as in sdk_diarize_reconstruct.
+ *                         n_end: NULL, or DEVICE int64 [R]: n_end [r] > 0 says that the chunk is the stream's last and the stream ends at that
+ *                         sample; no frame from sdk_diarize_frames(n_end [r]) on is then emitted (a zero-padded chunk reaches beyond it).
+ *                         -> labels [r][3] int32, score [r][3] fp32, K [r] int32 (speakers after the step), emit_lo [r] int64 and
+ *                         emit_n [r] int32: the frames emit_lo .. emit_lo + emit_n - 1 leave the ring as count [r][j] uint8 and
+ *                         speakers [r][j][2] int32, j < emit_n <= SDK_STREAM_RING (rows j >= emit_n are not written).
+ *   sdk_stream_flush      the end of stream r at n_samples [r] (int64): every frame not yet emitted, up to sdk_diarize_frames(n_samples [r]).
+ *   sdk_stream_centroids  of the streams first .. first + count - 1, indexed from first: -> cent [r][capacity][d] fp32 unit rows (rows >= K [r]
+ *                         zero), counts [r][capacity] int32 (0 there), K [r] int32, and, where sums is not NULL, the float64 sums
+ *                         [r][capacity][d] (rows >= K [r] zero).
+ *   d a multiple of 64, at most 512 (sdk_diarize_assign's limit); capacity 1 .. 64; 1 <= F <= SDK_STREAM_RING.  Every sum is float64 in a
+ *   fixed order, every output element has one owner, there are no atomics: two runs agree bit for bit.  Refusals (a null or misaligned
+ *   pointer, capacity, d, F, hop below 270, latency below hop or beyond the ring, delta_new, a short state block) return non-zero, name the value in
+ *   sdk_last_error() and launch nothing. */
+#define SDK_STREAM_RING 1024
+#define SDK_STREAM_MAX_SPEAKERS 64
+int64_t sdk_stream_state_bytes(int R, int capacity, int d);
+int sdk_stream_reset(sdk_ctx* ctx, void* state, int64_t state_bytes, int R, int capacity, int d, const uint8_t* which, void* stream);
+int sdk_stream_step(sdk_ctx* ctx, const float* E, const int32_t* info, const uint8_t* cls, const int64_t* starts, const uint8_t* active,
+                    const int64_t* n_end, int R, int F, int d, int capacity, int hop, int latency, double delta_new, int max_speakers, void* state, int64_t state_bytes,
+                    int32_t* labels, float* score, int32_t* K, int64_t* emit_lo, int32_t* emit_n, uint8_t* count, int32_t* speakers,
+                    void* stream);
+int sdk_stream_flush(sdk_ctx* ctx, const int64_t* n_samples, const uint8_t* active, int R, int capacity, int d, int max_speakers, void* state,
+                     int64_t state_bytes, int64_t* emit_lo, int32_t* emit_n, uint8_t* count, int32_t* speakers, void* stream);
+int sdk_stream_centroids(sdk_ctx* ctx, const void* state, int64_t state_bytes, int R, int capacity, int d, int first, int count, float* cent,
+                         int32_t* counts, int32_t* K, double* sums, void* stream);
 
 #ifdef __cplusplus
 }

@@ -533,6 +533,13 @@ class Backend(EmbeddingBackend):
             if dz.eng.precision != prec:
                 dz.eng.set_precision(prec)                       # the front end's format goes back to the selected family's contract
 
+    def open_streams(self, n_streams: int = 1, **options):
+        """Streaming diarization: a stream.StreamBank of n_streams live streams on the models diarize loads (options: step_s, latency_s,
+        capacity, delta_new, max_speakers).  bank.push([samples or None per stream]) feeds 16 kHz mono int16 audio as it arrives and returns
+        the newly emitted frames per stream, bank.finish(r) ends a stream with its diarize.DiarizationResult (stream.py states the rule).
+        The bank steps in the ResNet34's numerical contract; every push and finish gives the engine back in the precision it had."""
+        return self.diarizer().open_streams(n_streams, **options)
+
     def link_speakers(self, results, threshold: float = 0.7045654963945799, min_speech_s: float = 0.0, candidates=None):
         """One speaker inventory for the results of diarize_many (diarize.link_speakers, which states the rule): the local speakers of
         different recordings joined into global ones by a constrained centroid linkage on the device - two speakers of one recording never

@@ -12,15 +12,12 @@
 // Every kernel is a gather: one owner per output element, no atomics, every sum in a fixed order (the first three kernels are integer
 // arithmetic: the weights are 0 / 1), so the results are bit-identical run to run.
 #include "common.hpp"
+#include "diarize_assign.hpp"
 
 namespace {
 
 constexpr int DZ_NT = 256;
-constexpr int DZ_HOP = 270;          // samples between segmentation frames
 constexpr int DZ_MIN_CLEAN = 4;      // columns of the last map a speaker needs alone before the overlapped ones are dropped (diarize.MIN_CLEAN_COLUMNS)
-
-// the speakers of powerset class c = {}, {0}, {1}, {2}, {0,1}, {0,2}, {1,2} as a 3-bit mask (0 for anything else)
-__device__ __forceinline__ int cls_mask(int c) { return (unsigned)c < 7u ? (0x6534210 >> (4 * c)) & 7 : 0; }
 
 __device__ __forceinline__ int wave_sum_i(int v) {
 #pragma unroll
@@ -96,12 +93,6 @@ __global__ __launch_bounds__(64) void diarize_masks_kernel(const uint8_t* __rest
   }
 }
 
-// q_c = floor((135 - start_c) / 270): global frame g reads frame g + q_c of chunk c
-__device__ __forceinline__ int64_t chunk_q(int64_t start) {
-  const int64_t a = 135 - start;
-  return a >= 0 ? a / DZ_HOP : -((-a + DZ_HOP - 1) / DZ_HOP);
-}
-
 // thread = one global frame.  The starts ascend, so q_c never grows with c: the chunks with g + q_c >= 0 are a prefix, those with
 // g + q_c < F a suffix, and the chunks that see the frame are the range between two binary searches.
 // Frame g of a recording whose chunks are cb .. ce - 1 of cls / starts / labels; count, speakers and act point at the frame's own elements.
@@ -158,7 +149,6 @@ __global__ __launch_bounds__(DZ_NT) void diarize_reconstruct_kernel(const uint8_
 }
 
 // ---- assignment (diarize.py "assignment"): centroids of the training rows, then every candidate row to a centroid ------------------------
-constexpr int DZ_MAX_D = 512;        // embedding width served by the two assignment kernels (a multiple of 64)
 constexpr int DZ_TILE = 256;         // (row, label) pairs staged in LDS per step of the centroid sum
 
 // block = one cluster k, thread = the columns tid, tid + 256.  The n (row, label) pairs pass through LDS in tiles; every thread walks them in
@@ -212,141 +202,24 @@ __global__ __launch_bounds__(DZ_NT) void diarize_centroids_kernel(const float* _
   }
 }
 
-// (value, cluster) lists of a row's three largest cosines, best first; ties to the lower cluster; idx < 0: empty
-struct Top3 { double v[3]; int k[3]; };
-
-__device__ __forceinline__ bool better(double v, int k, double bv, int bk) { return bk < 0 || v > bv || (v == bv && k < bk); }
-
-__device__ __forceinline__ void top3_push(Top3& t, double v, int k) {
-  if (!(v == v)) return;                               // a NaN never wins
-  if (better(v, k, t.v[0], t.k[0])) {
-    t.v[2] = t.v[1]; t.k[2] = t.k[1]; t.v[1] = t.v[0]; t.k[1] = t.k[0]; t.v[0] = v; t.k[0] = k;
-  } else if (better(v, k, t.v[1], t.k[1])) {
-    t.v[2] = t.v[1]; t.k[2] = t.k[1]; t.v[1] = v; t.k[1] = k;
-  } else if (better(v, k, t.v[2], t.k[2])) {
-    t.v[2] = v; t.k[2] = k;
-  }
-}
-
-// one wave per chunk.  The chunk's candidate rows go to LDS as float64; lane l takes the clusters l, l + 64, ..: one float64 dot product per
-// (candidate, cluster), summed over the columns in ascending order, and keeps the three best per candidate.  Three rounds of a wave arg-max
-// merge the lanes' lists; lane 0 then walks the tuples.  Every candidate picks among its (at most) three best clusters, or -1 when there
-// are fewer clusters than candidates: at most 4^3 tuples, of which the valid ones (n = min(m, K) pairwise different clusters) are compared by
-// their total, summed in slot order, then by the label tuple with -1 last.
+// one wave per chunk: the chunk's candidate rows go to LDS, the wave solves the assignment (diarize_assign.hpp), lane 0 writes the chunk's
+// three labels and scores
 __device__ __forceinline__ void assign_chunk(const float* __restrict__ E, const int32_t* __restrict__ info, const double* __restrict__ cent, int K,
                                              int d, int constrained, int32_t* __restrict__ labels, float* __restrict__ score, int c) {
-  __shared__ double s_e[3][DZ_MAX_D];
-  __shared__ double s_v[3][3];
-  __shared__ int s_k[3][3];
+  __shared__ AssignLds L;
   const int lane = threadIdx.x;
   bool cand[3];
-#pragma unroll
-  for (int s = 0; s < 3; ++s) {
-    const int32_t* in = info + ((int64_t)c * 3 + s) * 4;
-    cand[s] = in[3] != 0 && in[0] > 0;
-  }
-#pragma unroll
-  for (int s = 0; s < 3; ++s) {
-    if (cand[s]) {
-      const float* e = E + ((int64_t)c * 3 + s) * d;
-      for (int j = lane; j < d; j += 64) s_e[s][j] = (double)e[j];
-    }
-  }
+  assign_candidates(info + (int64_t)c * 12, cand);
+  assign_stage(L, E + (int64_t)c * 3 * d, cand, d, lane, 64);
   __syncthreads();
-  Top3 t[3];
-#pragma unroll
-  for (int s = 0; s < 3; ++s)
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { t[s].v[i] = 0.0; t[s].k[i] = -1; }
-  for (int k = lane; k < K; k += 64) {
-    const double* ck = cent + (int64_t)k * d;
-    double a[3] = {0.0, 0.0, 0.0};
-    for (int j = 0; j < d; j += 2) {
-      const double2 w = *reinterpret_cast<const double2*>(ck + j);
-#pragma unroll
-      for (int s = 0; s < 3; ++s) {
-        if (cand[s]) {
-          a[s] = fma(s_e[s][j], w.x, a[s]);
-          a[s] = fma(s_e[s][j + 1], w.y, a[s]);
-        }
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < 3; ++s) if (cand[s]) top3_push(t[s], a[s], k);
-  }
-#pragma unroll
-  for (int s = 0; s < 3; ++s) {
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {                      // round r: the best head of the wave, popped from the lane that holds it
-      double v = t[s].v[0];
-      int k = t[s].k[0];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(v, o, 64);
-        const int ok = __shfl_xor(k, o, 64);
-        if (ok >= 0 && better(ov, ok, v, k)) { v = ov; k = ok; }
-      }
-      if (k >= 0 && k == t[s].k[0]) {
-        t[s].v[0] = t[s].v[1]; t[s].k[0] = t[s].k[1]; t[s].v[1] = t[s].v[2]; t[s].k[1] = t[s].k[2]; t[s].k[2] = -1;
-      }
-      if (lane == 0) { s_v[s][r] = v; s_k[s][r] = k; }
-    }
-  }
+  int32_t lab[3];
+  double cosv[3];
+  assign_solve(L, cand, cent, K, d, constrained, lane, lab, cosv);
   if (lane != 0) return;
-  int slot[3], m = 0;
-  int32_t lab[3] = {-1, -1, -1};
-  float sc[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < 3; ++s) if (cand[s]) slot[m++] = s;
-  if (!constrained) {
-    for (int i = 0; i < m; ++i) {
-      const int s = slot[i];
-      if (s_k[s][0] >= 0) { lab[s] = s_k[s][0]; sc[s] = (float)s_v[s][0]; }
-    }
-  } else if (m > 0) {
-    const int n = min(m, K), nopt = K < m ? 4 : 3;     // option 3 of a candidate: no cluster (only when some candidate must go without)
-    bool have = false;
-    double best = 0.0;
-    int bl[3] = {-1, -1, -1}, bo[3] = {0, 0, 0};
-    const int total_tuples = m == 1 ? nopt : m == 2 ? nopt * nopt : nopt * nopt * nopt;
-    for (int u = 0; u < total_tuples; ++u) {
-      int o[3], l[3], used = 0;
-      int rest = u;
-      for (int i = m - 1; i >= 0; --i) { o[i] = rest % nopt; rest /= nopt; }      // slot 0 is the most significant digit
-      bool ok = true;
-      double tot = 0.0;
-      for (int i = 0; i < m && ok; ++i) {
-        l[i] = o[i] < 3 ? s_k[slot[i]][o[i]] : -1;
-        if (o[i] < 3) {
-          ok = l[i] >= 0;
-          for (int p = 0; p < i; ++p) ok = ok && l[p] != l[i];
-          if (ok) { tot += s_v[slot[i]][o[i]]; ++used; }
-        }
-      }
-      if (!ok || used != n) continue;
-      bool take = !have || tot > best;
-      if (have && tot == best) {                       // the smaller label tuple in slot order, -1 after every cluster
-        for (int i = 0; i < m; ++i) {
-          const unsigned x = (unsigned)l[i], y = (unsigned)bl[i];               // -1 -> 0xffffffff
-          if (x != y) { take = x < y; break; }
-        }
-      }
-      if (take) {
-        have = true;
-        best = tot;
-        for (int i = 0; i < m; ++i) { bl[i] = l[i]; bo[i] = o[i]; }
-      }
-    }
-    if (have)
-      for (int i = 0; i < m; ++i) {
-        lab[slot[i]] = bl[i];
-        sc[slot[i]] = bl[i] >= 0 ? (float)s_v[slot[i]][bo[i]] : 0.f;
-      }
-  }
 #pragma unroll
   for (int s = 0; s < 3; ++s) {
     labels[(int64_t)c * 3 + s] = lab[s];
-    score[(int64_t)c * 3 + s] = sc[s];
+    score[(int64_t)c * 3 + s] = (float)cosv[s];
   }
 }
 
@@ -368,11 +241,6 @@ __device__ __forceinline__ int find_group(const int32_t* __restrict__ off, int R
     if (off[mid] <= x) lo = mid; else hi = mid;
   }
   return lo;
-}
-
-__host__ __device__ inline int64_t dz_frames(int64_t n_samples) {
-  const int64_t g = (n_samples - 495 + DZ_HOP - 1) / DZ_HOP;
-  return n_samples < 495 || g < 0 ? 0 : g;
 }
 
 // one wave per chunk, the rule of diarize_assign_kernel on the centroids of the chunk's own recording; labels are local to the recording

@@ -63,6 +63,10 @@ tests pin these rules.
               recording, go through the linked centroid linkage on the device (cluster.link_rows, sdk_linked_linkage: two speakers of one
               recording never join, merging stops at the threshold); enrolled profiles join as rows of one further group.  The rule is
               stated at link_speakers; run_many's results are not changed by it.
+  streaming   (Diarizer.open_streams, Backend.open_streams) audio fed as it arrives, "who is speaking now" a bounded delay later: the same chunks
+              and embed_chunks, then an inventory that grows online, the constrained assignment above against its centroids and a rolling
+              stitch on this frame grid that emits frames once their latency has passed.  The rule, its numpy restatement and the bank of
+              live streams that steps in one launch are stream.py's; run and run_many are not changed by it.
   shared      run and run_many are one pipeline: Diarizer._check_options, _check_recording, _embed_all (the batches of embed_chunks) and
               _empty serve both, as do candidate_mask, training_mask and _speaker_cap; after the embedding run clusters one recording and
               run_many takes the pack through _pack_rows, _pack_vbx or _pack_ahc, _pack_assign and _pack_results.  They differ on purpose in
@@ -852,6 +856,12 @@ class Diarizer:
             infos.append(i)
             embs.append(e)
         return cls, torch.cat(infos), torch.cat(embs)
+
+    def open_streams(self, n_streams: int = 1, **options):
+        """A stream.StreamBank of n_streams live streams on this pipeline (options: step_s, latency_s, capacity, delta_new, max_speakers;
+        stream.py states the rule)."""
+        from .stream import StreamBank
+        return StreamBank(self, n_streams, **options)
 
     # ---------------------------------------------------------------------------------------------- one recording
     def run(self, samples, step_s: float = 1.0, threshold: float = PYANNOTE_THRESHOLD, min_cluster_size: int = PYANNOTE_MIN_CLUSTER_SIZE,

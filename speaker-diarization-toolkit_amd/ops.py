@@ -83,6 +83,25 @@ def num_frames(n_samples: int) -> int:
     return 1 + n_samples // HOP
 
 
+STREAM_RING = 1024       # SDK_STREAM_RING: frames a stream's ring holds, and the most a step emits
+
+
+class StreamState:
+    """Engine.stream_state: the opaque device block of a bank of live streams (buf) and the rows its steps write."""
+
+    def __init__(self, eng, R: int, capacity: int, d: int, nbytes: int):
+        dev = eng.device
+        self.R, self.capacity, self.d, self.nbytes = R, capacity, d, nbytes
+        self.buf = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        self.labels = torch.full((R, 3), -1, dtype=torch.int32, device=dev)
+        self.score = torch.zeros((R, 3), dtype=torch.float32, device=dev)
+        self.K = torch.zeros((R,), dtype=torch.int32, device=dev)
+        self.emit_lo = torch.zeros((R,), dtype=torch.int64, device=dev)
+        self.emit_n = torch.zeros((R,), dtype=torch.int32, device=dev)
+        self.count = torch.zeros((R, STREAM_RING), dtype=torch.uint8, device=dev)
+        self.speakers = torch.full((R, STREAM_RING, 2), -1, dtype=torch.int32, device=dev)
+
+
 class Engine:
     def __init__(self, device: int = 0, weights: Optional[Dict[str, np.ndarray]] = None,
                  cfg: EcapaConfig = DEFAULT_CONFIG, seed: int = 0, cache_key: Optional[str] = None, weights_fn=None, digest_fn=None,
@@ -874,6 +893,72 @@ class Engine:
             err.linkage, err.merges, err.status = Z, merges, st     # the other problems' rows of Z are valid
             raise err
         return Z, merges
+
+    # ---- streaming diarization (stream.py; csrc/stream.hip): a bank's speaker tables and frame rings live in one device block
+    def stream_state(self, n_streams: int, capacity: int, d: int) -> "StreamState":
+        """The device state of a bank of n_streams live streams (capacity speakers each, embedding width d), reset, with the output rows
+        that stream_step and stream_flush write."""
+        nbytes = int(self.lib.sdk_stream_state_bytes(int(n_streams), int(capacity), int(d)))
+        if nbytes == 0:
+            raise ValueError(f"stream_state: n_streams={n_streams} (at least 1), capacity={capacity} (1 .. 64), d={d} (a multiple of 64, at most 512)")
+        st = StreamState(self, int(n_streams), int(capacity), int(d), nbytes)
+        self.stream_reset(st)
+        return st
+
+    def stream_reset(self, st: "StreamState", which: Optional[torch.Tensor] = None) -> None:
+        """Empty the speaker table and the ring of the streams with which[r] != 0 (uint8 [R], device); None: of every stream."""
+        if which is not None:
+            which = _thin(which, "which", "stream_reset", (st.R,), torch.uint8)
+        check(self.lib.sdk_stream_reset(self.ctx, st.buf.data_ptr(), st.nbytes, st.R, st.capacity, st.d, _ptr(which), _stream()), "sdk_stream_reset")
+
+    def stream_step(self, st: "StreamState", E: torch.Tensor, info: torch.Tensor, cls: torch.Tensor, starts: torch.Tensor, active: torch.Tensor,
+                    hop: int, latency: int, delta_new: float = 1.0, max_speakers: Optional[int] = None,
+                    n_end: Optional[torch.Tensor] = None) -> "StreamState":
+        """One bank step (sdk_stream_step): stream r's chunk is E [3 r .. 3 r + 2] (unit fp32 rows), info [r] (int32 [3, 4]), cls [r] (uint8 [F])
+        and starts [r] (int64, samples); streams with active [r] == 0 (uint8) are left alone.  hop and latency in samples.  n_end (int64 [R], or None): n_end [r] > 0 says
+        that the chunk is stream r's last and where the stream ends; no frame beyond that end is emitted.  The results stand
+        in st.labels, st.score, st.K, st.emit_lo, st.emit_n, st.count and st.speakers (device), rows of inactive streams untouched."""
+        R, d = st.R, st.d
+        _thin(E, "E", "stream_step", (3 * R, d))
+        _thin(info, "info", "stream_step", (R, 3, 4), torch.int32)
+        _thin(cls, "cls", "stream_step", None, torch.uint8)
+        if cls.dim() != 2 or cls.shape[0] != R:
+            raise ValueError(f"stream_step: cls must be [{R}, F], got {list(cls.shape)}")
+        _thin(starts, "starts", "stream_step", (R,), torch.int64)
+        _thin(active, "active", "stream_step", (R,), torch.uint8)
+        if n_end is not None:
+            _thin(n_end, "n_end", "stream_step", (R,), torch.int64)
+        cap = 2 if max_speakers is None else int(max_speakers)
+        check(self.lib.sdk_stream_step(self.ctx, E.data_ptr(), info.data_ptr(), cls.data_ptr(), starts.data_ptr(), active.data_ptr(), _ptr(n_end), R, int(cls.shape[1]),
+                                       d, st.capacity, int(hop), int(latency), float(delta_new), cap, st.buf.data_ptr(), st.nbytes,
+                                       st.labels.data_ptr(), st.score.data_ptr(), st.K.data_ptr(), st.emit_lo.data_ptr(), st.emit_n.data_ptr(),
+                                       st.count.data_ptr(), st.speakers.data_ptr(), _stream()), "sdk_stream_step")
+        return st
+
+    def stream_flush(self, st: "StreamState", n_samples: torch.Tensor, active: torch.Tensor, max_speakers: Optional[int] = None) -> "StreamState":
+        """The end of the streams with active [r] != 0 at n_samples [r] (int64, device): every frame not yet emitted stands in st.emit_lo,
+        st.emit_n, st.count and st.speakers (sdk_stream_flush)."""
+        _thin(n_samples, "n_samples", "stream_flush", (st.R,), torch.int64)
+        _thin(active, "active", "stream_flush", (st.R,), torch.uint8)
+        cap = 2 if max_speakers is None else int(max_speakers)
+        check(self.lib.sdk_stream_flush(self.ctx, n_samples.data_ptr(), active.data_ptr(), st.R, st.capacity, st.d, cap, st.buf.data_ptr(), st.nbytes,
+                                        st.emit_lo.data_ptr(), st.emit_n.data_ptr(), st.count.data_ptr(), st.speakers.data_ptr(), _stream()),
+              "sdk_stream_flush")
+        return st
+
+    def stream_centroids(self, st: "StreamState", first: int = 0, count: Optional[int] = None, sums: bool = False):
+        """Of the streams first .. first + count - 1 (count None: to the last) -> (cent [count, capacity, d] fp32 unit rows, zero from K [r]
+        on; counts [count, capacity] int32; K [count] int32) on the device; sums=True: and the float64 sums [count, capacity, d]."""
+        count = st.R - int(first) if count is None else int(count)
+        if not (0 <= int(first) and 1 <= count <= st.R - int(first)):
+            raise ValueError(f"stream_centroids: streams first={first}, count={count} of {st.R}")
+        cent = torch.empty((count, st.capacity, st.d), dtype=torch.float32, device=self.device)
+        counts = torch.empty((count, st.capacity), dtype=torch.int32, device=self.device)
+        K = torch.empty((count,), dtype=torch.int32, device=self.device)
+        S = torch.empty((count, st.capacity, st.d), dtype=torch.float64, device=self.device) if sums else None
+        check(self.lib.sdk_stream_centroids(self.ctx, st.buf.data_ptr(), st.nbytes, st.R, st.capacity, st.d, int(first), count, cent.data_ptr(),
+                                            counts.data_ptr(), K.data_ptr(), _ptr(S), _stream()), "sdk_stream_centroids")
+        return (cent, counts, K, S) if sums else (cent, counts, K)
 
     # ---- VBx clustering (cluster.vbx_cluster, plda.py; csrc/vbx.hip): nothing here synchronises with the host except the range check of rows
     @staticmethod

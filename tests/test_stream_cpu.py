@@ -1,0 +1,214 @@
+"""CPU checks of streaming diarization (stream.py): the chunk schedule against segmentation.chunk_starts, the numpy restatement of the step
+kernel against tests/stream_ref.py (written independently from the rule text), the emitted frames against diarize.reconstruct_host, the
+frontier against later chunks, and the rule's corner cases."""
+from __future__ import annotations
+
+import importlib
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import stream_ref as SR  # noqa: E402
+
+PKG = "speaker-diarization-toolkit_amd"
+st = importlib.import_module(f"{PKG}.stream")
+dz = importlib.import_module(f"{PKG}.diarize")
+seg = importlib.import_module(f"{PKG}.segmentation")
+CHUNK, F = 160000, 589
+
+
+def run_host(s, n, capacity, hop, latency, delta_new=1.0, max_speakers=None):
+    """stream.py's restatement over a whole stream of stream_ref.make_stream -> the dict of stream_ref.run_stream, and the HostStream."""
+    hs = st.HostStream(capacity, s["E"].shape[2])
+    hold = (latency - hop) // 270
+    labels, score, count, speakers, lows = [], [], [], [], []
+    for c in range(len(s["starts"])):
+        added = c == len(s["starts"]) - 1 and (n < CHUNK or (n - CHUNK) % hop != 0)                     # the chunk finish() adds
+        lab, sc, lo, cnt, spk = st.step_host(hs, s["E"][c], s["info"][c], s["cls"][c], int(s["starts"][c]), hold, delta_new, max_speakers,
+                                             n if added else None)
+        labels.append(lab), score.append(sc), count.append(cnt), speakers.append(spk), lows.append(lo)
+    lo, cnt, spk = st.flush_host(hs, n, max_speakers)
+    count.append(cnt), speakers.append(spk), lows.append(lo)
+    return {"labels": np.asarray(labels, np.int32).reshape(-1, 3), "score": np.asarray(score).reshape(-1, 3), "count": np.concatenate(count),
+            "speakers": np.concatenate(speakers), "K": hs.K, "lows": lows, "parts": count}, hs
+
+
+@pytest.mark.parametrize("hop", [8000, 4321, 270, 160000])
+def test_schedule_equals_chunk_starts_under_any_push_sizes(hop):
+    rng = np.random.default_rng(hop)
+    sizes = [0, 1, 494, CHUNK - 1, CHUNK, CHUNK + 1, CHUNK + hop - 1, CHUNK + hop, CHUNK + hop + 1, CHUNK + 7 * hop, CHUNK + 7 * hop + 2999]
+    for n in sizes:
+        for piece in (1 << 30, 4800, 48000, None):
+            sch, got, fed = st.ChunkSchedule(hop), [], 0
+            while fed < n:
+                k = min(n - fed, int(rng.integers(1, 70000)) if piece is None else piece)
+                assert sch.due(k) == len(sch.push(0)) + sch.due(k)            # due() does not move the schedule
+                before = sch.due(k)
+                new = sch.push(k)
+                assert len(new) == before
+                got += new
+                fed += k
+                assert all(s + CHUNK <= fed for s in new) and sch.due(0) == 0
+            last = sch.finish()
+            got += [] if last is None else [last]
+            want = seg.chunk_starts(n, hop / 16000.0).tolist() if n else []
+            assert got == want == SR.schedule(n, hop), (n, piece)
+            with pytest.raises(ValueError):
+                sch.push(1)
+    sch = st.ChunkSchedule(hop)                                                # one sample at a time across the first due point
+    sch.push(CHUNK - 2)
+    assert [sch.push(1) for _ in range(3)] == [[], [0], []]
+
+
+CASES = [(64, 4, 8000, 8000, 0.6, None), (128, 2, 8000, 32000, 0.6, 1), (64, 64, 4321, 160000, 0.6, None), (64, 1, 8000, 8000, 1.0, None),
+         (192, 3, 16000, 100000, 0.3, None)]
+
+
+@pytest.mark.parametrize("d,capacity,hop,latency,delta,maxsp", CASES)
+@pytest.mark.parametrize("off_grid", [False, True])
+def test_host_restatement_equals_the_independent_reference(d, capacity, hop, latency, delta, maxsp, off_grid):
+    n = CHUNK + 59 * hop + (1234 if off_grid else 0)
+    s = SR.make_stream(7 + d + capacity, d, n, hop, n_speakers=5)
+    ref = SR.run_stream(s["E"], s["info"], s["cls"], s["starts"], n, capacity, hop, latency, delta, maxsp)
+    assert ref["ref"].margin > 1e-8
+    got, hs = run_host(s, n, capacity, hop, latency, delta, maxsp)
+    for key in ("labels", "count", "speakers", "K"):
+        assert np.array_equal(got[key], ref[key]), key
+    assert np.abs(got["score"] - ref["score"]).max() < 1e-12
+    assert np.array_equal(hs.n[:hs.K], ref["ref"].n) and np.allclose(hs.S[:hs.K], np.stack(ref["ref"].sums), rtol=1e-13, atol=0)
+    assert len(got["count"]) == dz.global_frames(n) and ref["K"] >= min(capacity, 2)
+    lo = 0
+    for part, at in zip(got["parts"], got["lows"]):                            # the updates tile the frames in order
+        assert at == lo
+        lo += len(part)
+
+
+@pytest.mark.parametrize("hop,m", [(8000, 12), (4321, 30), (16000, 5)])
+def test_full_latency_on_the_grid_equals_reconstruct_host(hop, m):
+    """latency_s = 10, n = CHUNK + m hop: every frame leaves after its last chunk, so the stream's frames are the batch stitching of its own
+    labels (160000 = 592 x 270 + 160: hold frames cover what the next chunk still reaches)."""
+    n = CHUNK + m * hop
+    s = SR.make_stream(3, 64, n, hop, n_speakers=4)
+    got, hs = run_host(s, n, 8, hop, CHUNK, 0.6)
+    assert len(got["lows"]) == m + 2 and len(got["parts"][-1]) > 0
+    count, speakers, _, _ = dz.reconstruct_host(s["cls"], s["starts"], got["labels"], max(hs.K, 1), n)
+    assert np.array_equal(got["count"], count) and np.array_equal(got["speakers"], speakers)
+
+
+@pytest.mark.parametrize("hop,latency", [(8000, 8000), (8000, 32000), (4321, 160000), (4321, 4321), (270, 270), (270, 5000), (40000, 100000)])
+def test_frontier_never_passes_a_frame_a_later_grid_chunk_changes(hop, latency):
+    """What has left the stream is final, and it left with everything the chunks so far said about it.  The checks that carry weight:
+    (a) the frontier of the restatement and of the reference is the rule's formula after every step, and the ring always spans what lies
+    between it and the newest chunk's reach; (b) the ring agrees with the reference, which keeps every frame, on every live frame;
+    (c) the frames a step emits equal a ring-free recomputation: diarize.reconstruct_host over the chunks up to that step with the labels
+    so far - a chunk covering a frame that is still in the stream has contributed to it, whatever the latency; (d) with the full latency
+    the frontier stays at or below the first frame of the next grid chunk, so nothing a grid chunk says is dropped; only the final
+    off-grid chunk of finish() may find its first frames gone.  (The reference skips emitted frames by construction, so comparing its rows
+    of emitted frames before and after later chunks would prove nothing; (c) is what stands in for it.)"""
+    hold = (latency - hop) // 270
+    n = CHUNK + 24 * hop + 1234
+    s = SR.make_stream(11, 64, n, hop, n_speakers=3)
+    ref, hs = SR.RefStream(4, 64, hop, latency, 0.6), st.HostStream(4, 64)
+    labels, want_front, fronts = [], 0, []
+    last = len(s["starts"]) - 1
+    for c, start in enumerate(s["starts"]):
+        end = n if c == last else None                                         # the chunk finish() adds
+        _, _, rlo, rcnt, rspk = ref.step(s["E"][c], s["info"][c], s["cls"][c], int(start), end)
+        lab, _, lo, cnt, spk = st.step_host(hs, s["E"][c], s["info"][c], s["cls"][c], int(start), hold, 0.6, None, end)
+        labels.append(lab)
+        rule = F - st.chunk_q(start) - hold
+        want_front = max(want_front, rule if end is None else min(rule, dz.global_frames(n)))
+        assert hs.frontier == ref.emitted == want_front and hs.reach - hs.frontier <= st.RING          # (a)
+        assert lo == rlo and np.array_equal(cnt, rcnt) and np.array_equal(spk, rspk)
+        fronts.append(hs.frontier)
+        live = np.arange(hs.frontier, hs.reach)                                                          # (b)
+        assert np.array_equal(hs.nc[live % st.RING], ref.nc[live]) and np.array_equal(hs.act[live % st.RING], ref.act[live])
+        if len(cnt):                                                                                     # (c)
+            count, speakers, _, _ = dz.reconstruct_host(s["cls"][:c + 1], s["starts"][:c + 1], np.asarray(labels), max(hs.K, 1), 270 * (hs.reach + 2) + 495)
+            assert np.array_equal(cnt, count[lo:lo + len(cnt)]) and np.array_equal(spk, speakers[lo:lo + len(cnt)])
+    assert fronts == sorted(fronts) and fronts[-1] > 0
+    grid = np.arange(0, 70 * hop, hop)
+    first = np.array([-st.chunk_q(v) for v in grid])                           # the first frame chunk c reaches
+    frontier = np.array([F - st.chunk_q(v) - hold for v in grid])              # frames below it have left after chunk c
+    if latency >= CHUNK:                                                       # (d)
+        assert (frontier[:-1] <= first[1:]).all()
+
+
+def info_of(active, clean):
+    return np.array([[a, c, int(c >= 4), int(a > 0)] for a, c in zip(active, clean)], np.int32)
+
+
+def unit(rng, d, n):
+    x = rng.standard_normal((n, d))
+    return (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(np.float32)
+
+
+def test_founding_order_full_table_and_three_long_candidates_at_k0():
+    rng = np.random.default_rng(0)
+    E = unit(rng, 64, 9)
+    long3 = info_of([300, 300, 300], [200, 200, 200])
+    for impl in ("host", "ref"):
+        def fresh(capacity):
+            return st.HostStream(capacity, 64) if impl == "host" else SR.RefStream(capacity, 64, 8000, 8000, 0.5)
+
+        def step(h, E3, info3):
+            if impl == "host":
+                return st.map_chunk_host(h, E3, info3, F, 0.5)
+            return h.step(E3, info3, np.zeros(F, np.uint8), 0)[:2]
+        h = fresh(4)
+        lab, sc = step(h, E[:3], long3)                                         # K = 0: three long candidates found 0, 1, 2 in slot order
+        assert lab.tolist() == [0, 1, 2] and np.allclose(sc, 1.0) and h.K == 3
+        lab, sc = step(h, E[[1, 3, 0]], long3)                                  # two match, the stranger founds 3; the table is then full
+        assert lab.tolist() == [1, 3, 0] and h.K == 4 and sc[1] == 1.0 and abs(sc[0] - 1.0) < 1e-6
+        assert list(np.asarray(h.n)[:4]) == [2, 2, 1, 1]
+        lab, sc = step(h, E[[4, 5, 6]], long3)                                  # a full table: strangers keep their constrained labels
+        assert h.K == 4 and sorted(lab.tolist()) == sorted(set(lab.tolist())) and (lab >= 0).all() and (np.asarray(sc) < 0.9).all()
+        assert list(np.asarray(h.n)[:4]) == [2, 2, 1, 1]
+        h = fresh(1)                                                            # capacity 1 at K = 0: one founder, the others -1
+        lab, sc = step(h, E[:3], long3)
+        assert lab.tolist() == [0, -1, -1] and sc.tolist() == [1.0, 0.0, 0.0]
+        lab, sc = step(h, E[[7, 0, 8]], long3)                                  # K < m: one candidate takes the speaker, the others go without
+        assert lab.tolist() == [-1, 0, -1] and h.K == 1 and np.asarray(h.n)[0] == 2
+
+
+def test_short_candidates_never_found_or_update():
+    rng = np.random.default_rng(1)
+    E = unit(rng, 64, 6)
+    short = info_of([100, 100, 0], [50, 117, 0])                                # 5 * 117 < 589: not long; slot 2 is no candidate
+    E_nan = E[:3].copy()
+    E_nan[2] = np.nan
+    for h, step in ((st.HostStream(4, 64), lambda h, a, b: st.map_chunk_host(h, a, b, F, 0.5)),
+                    (SR.RefStream(4, 64, 8000, 8000, 0.5), lambda h, a, b: h.step(a, b, np.zeros(F, np.uint8), 0)[:2])):
+        lab, sc = step(h, E_nan, short)
+        assert lab.tolist() == [-1, -1, -1] and h.K == 0
+        step(h, E[:3], info_of([300, 0, 0], [118, 0, 0]))                       # 5 * 118 >= 589: long
+        assert h.K == 1
+        before = np.array(h.S[0] if hasattr(h, "S") else h.sums[0])
+        lab, sc = step(h, np.stack([E[0], E[4], E_nan[2]]), short)              # a short match does not move the sum, a short stranger founds nobody
+        assert lab.tolist() == [0, -1, -1] and h.K == 1 and abs(sc[0] - 1) < 1e-6
+        assert np.array_equal(before, h.S[0] if hasattr(h, "S") else h.sums[0]) and np.asarray(h.n)[0] == 1
+
+
+def test_constructor_refusals():
+    ok = dict(step_s=0.5, latency_s=2.0, capacity=20, delta_new=1.0, max_speakers=None)
+    assert st.check_stream_options(**ok) == (8000, 32000, 24000 // 270)
+    assert st.check_stream_options(0.5) == (8000, 8000, 0)
+    for bad in (dict(step_s=0.0168), dict(step_s=0), dict(step_s=float("nan")), dict(latency_s=0.4), dict(latency_s=10.5), dict(capacity=0),
+                dict(capacity=65), dict(capacity=2.5), dict(delta_new=-0.1), dict(delta_new=2.5), dict(delta_new=float("nan")),
+                dict(delta_new=float("inf")), dict(max_speakers=-1)):
+        with pytest.raises(ValueError):
+            st.check_stream_options(**{**ok, **bad})
+    assert st.check_stream_options(270 / 16000)[0] == 270
+
+
+def test_turns_of_frames_keeps_frames_to_ranges_boundaries():
+    sp = np.full((10, 2), -1, np.int32)
+    sp[2:5, 0] = 1
+    sp[4:9, 1] = 0
+    got = st.turns_of_frames(100, sp)
+    want = sorted([(a + 100 * 270 / 16000, b + 100 * 270 / 16000, k) for k in (0, 1) for a, b in seg.frames_to_ranges((sp == k).any(1))],
+                  key=lambda t: (t[0], t[2]))
+    assert len(got) == 2 and np.allclose(np.array(got), np.array(want), atol=1e-12)

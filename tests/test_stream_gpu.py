@@ -1,0 +1,319 @@
+"""GPU checks of streaming diarization: sdk_stream_step / sdk_stream_flush (csrc/stream.hip) alone on generated rows against tests/stream_ref.py
+- integers bit for bit, sums within 1e-12 relative, scores within 1e-6, on inputs whose every decision stands more than 1e-8 from its
+threshold - then the state's and the emission's invariants, the C entry points' refusals, and StreamBank end to end with injected logp."""
+from __future__ import annotations
+
+import ctypes as C
+import importlib
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import stream_ref as SR  # noqa: E402
+
+PKG = "speaker-diarization-toolkit_amd"
+st = importlib.import_module(f"{PKG}.stream")
+dz = importlib.import_module(f"{PKG}.diarize")
+seg = importlib.import_module(f"{PKG}.segmentation")
+rn = importlib.import_module(f"{PKG}.resnet")
+LIB = importlib.import_module(f"{PKG}._lib")
+pytestmark = pytest.mark.gpu
+CHUNK, F, DELTA = 160000, 589, 0.6
+N_DISTINCT = 3                                    # generated streams per shape; stream r of a bank runs number r % 3
+STEPS = {8000: 60, 4321: 100}                     # chunks per stream: more than 2 x 1024 frames, the ring wraps more than once
+
+_streams, _refs = {}, {}
+
+
+def stream_of(d, hop, i):
+    """Generated stream i at this width and hop (the odd ones end off the grid: finish() adds a chunk) -> (dict, n_samples)."""
+    key = (d, hop, i)
+    if key not in _streams:
+        n = CHUNK + (STEPS[hop] - 1 - i % 2) * hop + (1234 if i % 2 else 0)
+        _streams[key] = (SR.make_stream(100 * i + d + hop, d, n, hop, n_speakers=5), n)
+        assert len(_streams[key][0]["starts"]) == STEPS[hop] >= 45
+    return _streams[key]
+
+
+def ref_of(d, capacity, hop, latency, i):
+    """The reference's run of stream i, computed once per shape; its inputs must decide every step."""
+    key = (d, capacity, hop, latency, i)
+    if key not in _refs:
+        s, n = stream_of(d, hop, i)
+        _refs[key] = SR.run_stream(s["E"], s["info"], s["cls"], s["starts"], n, capacity, hop, latency, DELTA)
+        assert _refs[key]["ref"].margin > 1e-8, f"{key}: a decision within {_refs[key]['ref'].margin:.2e} of its threshold: choose another seed"
+    return _refs[key]
+
+
+def run_device(engine, streams, capacity, hop, latency, delta=DELTA, nan_fill=False, max_speakers=None):
+    """streams: [(dict, n)] of one length C -> per stream a dict as stream_ref.run_stream's, plus "sums", "n", "cent", "lows"."""
+    R, Cn, d = len(streams), len(streams[0][0]["starts"]), streams[0][0]["E"].shape[2]
+    state = engine.stream_state(R, capacity, d)
+    E = np.stack([s["E"] for s, _ in streams], 1).copy()                   # [C, R, 3, d]
+    info = np.stack([s["info"] for s, _ in streams], 1)
+    if nan_fill:
+        E[~dz.candidate_mask(info).reshape(Cn, R, 3)] = np.nan
+    E_d, info_d = torch.from_numpy(E).cuda(), torch.from_numpy(info).cuda()
+    cls_d = torch.from_numpy(np.stack([s["cls"] for s, _ in streams], 1)).cuda()
+    starts_d = torch.from_numpy(np.stack([s["starts"] for s, _ in streams], 1)).cuda()
+    on = torch.ones(R, dtype=torch.uint8, device="cuda")
+    ends = [n if (n < CHUNK or (n - CHUNK) % hop) else 0 for _, n in streams]           # streams whose last chunk is the one finish() adds
+    end_d = torch.tensor(ends, dtype=torch.int64, device="cuda")
+    steps = []
+    for c in range(Cn):
+        engine.stream_step(state, E_d[c].reshape(3 * R, d), info_d[c], cls_d[c], starts_d[c], on, hop, latency, delta, max_speakers,
+                           end_d if c == Cn - 1 and any(ends) else None)
+        steps.append([t.clone() for t in (state.labels, state.score, state.K, state.emit_lo, state.emit_n, state.count, state.speakers)])
+    engine.stream_flush(state, torch.tensor([n for _, n in streams], dtype=torch.int64, device="cuda"), on, max_speakers)
+    flush = [t.clone() for t in (state.emit_lo, state.emit_n, state.count, state.speakers)]
+    cent, counts, K, sums = (t.cpu().numpy() for t in engine.stream_centroids(state, sums=True))
+    steps = [[t.cpu().numpy() for t in s] for s in steps]
+    flush = [t.cpu().numpy() for t in flush]
+    out = []
+    for r in range(R):
+        count = [s[5][r, :s[4][r]] for s in steps] + [flush[2][r, :flush[1][r]]]
+        speakers = [s[6][r, :s[4][r]] for s in steps] + [flush[3][r, :flush[1][r]]]
+        out.append({"labels": np.stack([s[0][r] for s in steps]), "score": np.stack([s[1][r] for s in steps]), "K": int(K[r]),
+                    "Ks": [int(s[2][r]) for s in steps], "lows": [int(s[3][r]) for s in steps] + [int(flush[0][r])],
+                    "ns": [int(s[4][r]) for s in steps] + [int(flush[1][r])], "count": np.concatenate(count), "speakers": np.concatenate(speakers),
+                    "sums": sums[r], "n": counts[r], "cent": cent[r]})
+    return out, state
+
+
+def check_against_ref(got, ref):
+    for key in ("labels", "count", "speakers", "K"):
+        assert np.array_equal(got[key], ref[key]), key
+    K = ref["K"]
+    assert got["Ks"][-1] == K and np.array_equal(got["n"][:K], ref["ref"].n) and not got["n"][K:].any()
+    assert got["lows"] == ref["lows"] and got["ns"] == ref["ns"]            # emit_lo, emit_n of every step and of the flush: WHEN a frame leaves
+    assert got["Ks"] == (np.maximum.accumulate(ref["labels"].max(1)) + 1).tolist()   # K after every step: speakers are founded in order
+    lo = 0
+    for at, n in zip(got["lows"], got["ns"]):                              # and they tile the frames in order
+        assert at == lo
+        lo += n
+    S = np.stack(ref["ref"].sums) if K else np.zeros((0, got["sums"].shape[1]))
+    assert np.abs(got["sums"][:K] - S).max(initial=0.0) <= 1e-12 * max(1.0, np.abs(S).max(initial=0.0))
+    assert np.abs(got["score"] - ref["score"]).max() <= 1e-6
+    U = S / np.maximum(np.linalg.norm(S, axis=1, keepdims=True), 1e-300)
+    assert np.abs(got["cent"][:K] - U).max(initial=0.0) <= 1e-6 and not got["cent"][K:].any()
+
+
+@pytest.mark.parametrize("hop,latency_s", [(8000, 0.5), (8000, 2.0), (4321, 10.0)])
+@pytest.mark.parametrize("capacity", [1, 2, 4, 64])
+@pytest.mark.parametrize("d", [64, 256, 512])
+@pytest.mark.parametrize("R", [1, 3, 65])
+def test_step_kernel_equals_the_reference(engine, R, d, capacity, hop, latency_s):
+    latency = int(round(latency_s * 16000))
+    refs = [ref_of(d, capacity, hop, latency, i) for i in range(min(R, N_DISTINCT))]        # asserted decisive before the device is asked
+    got, _ = run_device(engine, [stream_of(d, hop, r % N_DISTINCT) for r in range(R)], capacity, hop, latency)
+    for r in range(R):
+        check_against_ref(got[r], refs[r % N_DISTINCT])
+
+
+def test_nan_rows_inactive_streams_reruns_and_banks(engine):
+    d, capacity, hop, latency = 256, 4, 8000, 32000
+    streams = [stream_of(d, hop, i) for i in range(3)]
+    base, state = run_device(engine, streams, capacity, hop, latency)
+    again, _ = run_device(engine, streams, capacity, hop, latency)
+    nan, _ = run_device(engine, streams, capacity, hop, latency, nan_fill=True)                # rows that are no candidates are never read
+    for r in range(3):
+        alone, _ = run_device(engine, [streams[r]], capacity, hop, latency)                    # a stream of a bank is the stream alone
+        for other in (again[r], nan[r], alone[0]):
+            for key in ("labels", "score", "count", "speakers", "sums", "n", "cent", "lows", "ns"):
+                assert np.array_equal(base[r][key], other[key]), (r, key)
+    # an inactive stream: its state and its rows of every output stay bit for bit
+    per = state.nbytes // 3
+    before = [t.clone() for t in (state.buf, state.labels, state.score, state.K, state.emit_lo, state.emit_n, state.count, state.speakers)]
+    s = streams[0][0]
+    on = torch.tensor([1, 0, 1], dtype=torch.uint8, device="cuda")
+    args = (torch.from_numpy(np.tile(s["E"][5], (3, 1))).cuda(), torch.from_numpy(np.tile(s["info"][5], (3, 1, 1))).cuda(),
+            torch.from_numpy(np.tile(s["cls"][5], (3, 1))).cuda(), torch.full((3,), 10 ** 6, dtype=torch.int64, device="cuda"))
+    engine.stream_step(state, *args, on, hop, latency, DELTA)
+    engine.stream_flush(state, torch.full((3,), 2 * 10 ** 6, dtype=torch.int64, device="cuda"), on)
+    after = (state.buf, state.labels, state.score, state.K, state.emit_lo, state.emit_n, state.count, state.speakers)
+    assert torch.equal(before[0][per:2 * per], after[0][per:2 * per]) and not torch.equal(before[0][:per], after[0][:per])
+    for b, a in zip(before[1:], after[1:]):
+        assert torch.equal(b[1], a[1])
+    assert not torch.equal(before[4][0], after[4][0])
+    which = torch.tensor([0, 0, 1], dtype=torch.uint8, device="cuda")                           # reset of one stream leaves the others
+    keep = state.buf.clone()
+    engine.stream_reset(state, which)
+    assert torch.equal(keep[:2 * per], state.buf[:2 * per]) and int(engine.stream_centroids(state)[2][2]) == 0
+
+
+@pytest.mark.parametrize("n", [300, 100000, CHUNK, CHUNK + 5 * 8000, CHUNK + 5 * 8000 + 4321, CHUNK + 1])
+@pytest.mark.parametrize("latency", [8000, 48000, 160000])
+def test_flush_tiles_the_frames_exactly_once(engine, n, latency):
+    hop = 8000
+    s = SR.make_stream(n % 97, 64, n, hop, n_speakers=3)
+    assert s["starts"].tolist() == seg.chunk_starts(n, 0.5).tolist()
+    got, _ = run_device(engine, [(s, n)], 4, hop, latency)
+    ref = SR.run_stream(s["E"], s["info"], s["cls"], s["starts"], n, 4, hop, latency, DELTA)
+    assert ref["ref"].margin > 1e-8
+    G = dz.global_frames(n)
+    assert got[0]["lows"] == ref["lows"] and got[0]["ns"] == ref["ns"]
+    assert sum(got[0]["ns"]) == G == len(got[0]["count"]) and got[0]["lows"] == np.concatenate([[0], np.cumsum(got[0]["ns"])[:-1]]).tolist()
+    assert np.array_equal(got[0]["count"], ref["count"]) and np.array_equal(got[0]["speakers"], ref["speakers"])
+
+
+def test_every_refusal_returns_nonzero_and_launches_nothing(engine):
+    lib, R, cap, d = engine.lib, 2, 4, 64
+    state = engine.stream_state(R, cap, d)
+    E = torch.zeros((3 * R, d), device="cuda")
+    info = torch.zeros((R, 3, 4), dtype=torch.int32, device="cuda")
+    cls = torch.zeros((R, F), dtype=torch.uint8, device="cuda")
+    starts = torch.zeros(R, dtype=torch.int64, device="cuda")
+    on = torch.ones(R, dtype=torch.uint8, device="cuda")
+    snap = [t.clone() for t in (state.buf, state.labels, state.K, state.emit_n, state.count)]
+    ok = dict(E=E.data_ptr(), info=info.data_ptr(), cls=cls.data_ptr(), starts=starts.data_ptr(), active=on.data_ptr(), R=R, F=F, d=d, capacity=cap,
+              hop=8000, latency=8000, delta=1.0, maxsp=2, state=state.buf.data_ptr(), nbytes=state.nbytes, labels=state.labels.data_ptr(),
+              score=state.score.data_ptr(), K=state.K.data_ptr(), lo=state.emit_lo.data_ptr(), n=state.emit_n.data_ptr(), count=state.count.data_ptr(),
+              speakers=state.speakers.data_ptr())
+
+    def step(**kw):
+        a = {**ok, **kw}
+        return lib.sdk_stream_step(engine.ctx, a["E"], a["info"], a["cls"], a["starts"], a["active"], a.get("n_end"), a["R"], a["F"], a["d"], a["capacity"], a["hop"],
+                                   a["latency"], a["delta"], a["maxsp"], a["state"], a["nbytes"], a["labels"], a["score"], a["K"], a["lo"], a["n"],
+                                   a["count"], a["speakers"], torch.cuda.current_stream().cuda_stream)
+    bad = [(dict(E=None), "null"), (dict(speakers=None), "null"), (dict(E=E.data_ptr() + 2), "misaligned"), (dict(starts=starts.data_ptr() + 4), "misaligned"), (dict(n_end=starts.data_ptr() + 4), "misaligned"),
+           (dict(state=state.buf.data_ptr() + 16), "256-byte"), (dict(state=None), "256-byte"), (dict(capacity=0), "capacity=0"),
+           (dict(capacity=65), "capacity=65"), (dict(d=96), "d=96"), (dict(d=576), "d=576"), (dict(latency=7999), "latency=7999"), (dict(latency=300000), "ring"), (dict(hop=280000, latency=280000), "ring"),
+           (dict(hop=269, latency=269), "hop=269"), (dict(nbytes=state.nbytes - 1), "state block"), (dict(delta=2.5), "delta_new"),
+           (dict(delta=float("nan")), "delta_new"), (dict(F=1025), "F=1025"), (dict(R=0), "R=0"), (dict(maxsp=-1), "max_speakers")]
+    for kw, word in bad:
+        assert step(**kw) != 0 and word in lib.sdk_last_error().decode(), (kw, lib.sdk_last_error())
+    s = torch.cuda.current_stream().cuda_stream
+    ns = torch.zeros(R, dtype=torch.int64, device="cuda")
+    assert lib.sdk_stream_flush(engine.ctx, None, on.data_ptr(), R, cap, d, 2, state.buf.data_ptr(), state.nbytes, state.emit_lo.data_ptr(),
+                                state.emit_n.data_ptr(), state.count.data_ptr(), state.speakers.data_ptr(), s) != 0
+    assert lib.sdk_stream_flush(engine.ctx, ns.data_ptr(), on.data_ptr(), R, cap, d, 2, state.buf.data_ptr(), state.nbytes - 1, state.emit_lo.data_ptr(),
+                                state.emit_n.data_ptr(), state.count.data_ptr(), state.speakers.data_ptr(), s) != 0
+    assert lib.sdk_stream_reset(engine.ctx, state.buf.data_ptr(), state.nbytes, R, cap + 1, d, None, s) != 0 and b"state block" in lib.sdk_last_error()
+    assert lib.sdk_stream_reset(engine.ctx, None, state.nbytes, R, cap, d, None, s) != 0
+    kp = state.K.data_ptr()
+    assert lib.sdk_stream_centroids(engine.ctx, state.buf.data_ptr(), state.nbytes, R, cap, d, 0, R, None, kp, kp, None, s) != 0
+    for first, count in ((0, R + 1), (R, 1), (-1, 1), (0, 0)):
+        assert lib.sdk_stream_centroids(engine.ctx, state.buf.data_ptr(), state.nbytes, R, cap, d, first, count, E.data_ptr(), kp, kp, None, s) != 0
+        assert b"first=" in lib.sdk_last_error()
+    with pytest.raises(ValueError):
+        engine.stream_centroids(state, 1, R)
+    assert lib.sdk_stream_state_bytes(0, cap, d) == 0 and lib.sdk_stream_state_bytes(R, 65, d) == 0 and lib.sdk_stream_state_bytes(R, cap, 100) == 0
+    torch.cuda.synchronize()
+    for a, b in zip(snap, (state.buf, state.labels, state.K, state.emit_n, state.count)):
+        assert torch.equal(a, b)
+    assert step() == 0                                                      # and the accepted call runs
+    torch.cuda.synchronize()
+    with pytest.raises(ValueError):
+        engine.stream_state(1, 65, 64)
+
+
+# ------------------------------------------------------------------------------------------------ end to end: StreamBank with injected logp
+RATE, N_E2E, STEP_S = 16000, 16 * 16000 + 777, 0.5
+
+
+def logp_of(cls):
+    lp = np.full(cls.shape + (7,), -20.0, np.float32)
+    np.put_along_axis(lp, cls[..., None].astype(np.int64), 0.0, axis=-1)
+    return lp
+
+
+@pytest.fixture(scope="module")
+def e2e(engine):
+    """~16 s of generated audio, a class table per chunk, and the run that pushes everything at once."""
+    rng = np.random.default_rng(5)
+    t = np.arange(N_E2E) / RATE
+    x = 0.1 * rng.standard_normal(N_E2E) + 0.2 * np.sin(2 * np.pi * (180 + 60 * np.floor(t / 2.5)) * t)
+    pcm = np.clip(np.round(x * 32768), -32768, 32767).astype(np.int16)
+    starts = seg.chunk_starts(N_E2E, STEP_S)
+    cls = SR.make_stream(9, 64, N_E2E, 8000)["cls"]
+    assert len(cls) == len(starts) == 14
+    diar = dz.Diarizer(engine, None, rn.ResNet34(engine, rn.synthetic_weights(0), precision=0))
+    return pcm, starts, cls, diar
+
+
+def run_bank(diar, pcm, cls, piece, **options):
+    bank = diar.open_streams(1, step_s=STEP_S, **options)
+    bank.keep_embeddings = True
+    lp, used, ups, syncs = logp_of(cls), 0, [], []
+    for a in range(0, len(pcm), piece):
+        x = pcm[a:a + piece]
+        k = bank.due(0, len(x))
+        ups += bank.push([x], [lp[used:used + k]])
+        used += k
+        syncs += bank.last_sync
+    res = bank.finish(0, lp[used:used + 1] if used < len(cls) else None)
+    syncs += bank.last_sync[:-1]
+    with pytest.raises(ValueError):
+        bank.push([pcm[:10]])
+    return res, ups, syncs, bank
+
+
+@pytest.mark.parametrize("latency_s", [0.5, 3.0])
+def test_bank_end_to_end_pieces_reference_and_waits(e2e, latency_s):
+    """Everything at once against pieces of 0.3 s, 3 s and 1 sample; the device's own embeddings through the reference; one wait per bank step.
+    The 1-sample run is RESTRICTED: one sample per push only for the three samples before and after each of the first two due points
+    (CHUNK and CHUNK + hop samples, where a push changes what is due), the audio between and behind them in bulk: 256 777 pushes of one
+    sample would take the test from seconds to minutes and pass through the same two code paths, a push with no chunk due and one with."""
+    pcm, starts, cls, diar = e2e
+    whole, ups, syncs, bank = run_bank(diar, pcm, cls, len(pcm), latency_s=latency_s, capacity=6, delta_new=DELTA)
+    assert len(syncs) == len(starts) and all(s["downloads"] == 1 and s["active"] == 1 for s in syncs)     # one wait per bank step
+    assert np.array_equal(whole.starts, starts) and whole.labels.shape == (len(starts), 3) and whole.cls is None
+    assert len(whole.count) == dz.global_frames(len(pcm)) and whole.centroids.shape == (whole.n_speakers, diar.resnet.cfg.embed_dim)
+    E, kept_cls = bank.embeddings(0)                                       # the device's own embeddings through the reference
+    assert np.array_equal(kept_cls, cls) and np.array_equal(whole.info, dz.masks_host(cls, 126)[1])
+    latency = int(round(latency_s * RATE))
+    ref = SR.run_stream(E, whole.info, cls, starts, len(pcm), 6, 8000, latency, DELTA)
+    print(f"stream e2e latency {latency_s}: K={ref['K']} margin {ref['ref'].margin:.3e} labels {whole.labels.tolist()}")
+    assert ref["ref"].margin > 1e-6 and ref["K"] >= 1                       # fp32 embeddings of different batch sizes differ by far less
+    assert np.array_equal(whole.labels, ref["labels"]) and whole.n_speakers == ref["K"]
+    assert np.array_equal(whole.count, ref["count"]) and np.array_equal(whole.speakers, ref["speakers"])
+    assert np.abs(whole.scores - ref["score"]).max() <= 1e-6
+    assert whole.turns == dz.turns_from_frames(ref["speakers"], ref["K"])
+    emitted = np.concatenate([u.speakers for u in ups])
+    assert np.array_equal(emitted, whole.speakers[:len(emitted)]) and ups[0].frame_lo == 0
+    for piece in (4800, 48000, 1):                                         # 0.3 s, 3 s, and one sample at a time (see the docstring)
+        if piece == 1:
+            bank1 = diar.open_streams(1, step_s=STEP_S, latency_s=latency_s, capacity=6, delta_new=DELTA)
+            lp, used = logp_of(cls), 0
+            cuts = [CHUNK - 3] + [1] * 6 + [7994] + [1] * 6 + [len(pcm) - CHUNK - 8003]
+            assert sum(cuts) == len(pcm)
+            a = 0
+            for k in cuts:
+                due = bank1.due(0, k)
+                bank1.push([pcm[a:a + k]], [lp[used:used + due]])
+                a, used = a + k, used + due
+            other = bank1.finish(0, lp[used:used + 1])
+        else:
+            other = run_bank(diar, pcm, cls, piece, latency_s=latency_s, capacity=6, delta_new=DELTA)[0]
+        assert np.array_equal(other.labels, whole.labels) and np.array_equal(other.count, whole.count)
+        assert np.array_equal(other.speakers, whole.speakers) and other.turns == whole.turns
+
+
+def test_bank_of_streams_steps_together_and_resets(e2e):
+    """Three streams of different lengths in one bank: every stream gets what it gets alone; one wait per bank step however many streams
+    are due; a finished slot reopens after reset."""
+    pcm, starts, cls, diar = e2e
+    lens = [len(pcm), CHUNK + 8000 * 3, 90000]
+    alone = []
+    for n in lens:
+        k = len(seg.chunk_starts(n, STEP_S))
+        alone.append(run_bank(diar, pcm[:n], cls[:k], n, capacity=6, delta_new=DELTA)[0])
+    bank = diar.open_streams(3, step_s=STEP_S, capacity=6, delta_new=DELTA)
+    lp = logp_of(cls)
+    due = [bank.due(r, n) for r, n in enumerate(lens)]
+    assert due == [13, 4, 0]
+    bank.push([pcm[:n] for n in lens], [lp[:k] for k in due])
+    assert len(bank.last_sync) == 13 and [s["active"] for s in bank.last_sync[:5]] == [2, 2, 2, 2, 1]
+    assert all(s["downloads"] == 1 for s in bank.last_sync)
+    for r, n in enumerate(lens):
+        res = bank.finish(r, lp[due[r]:due[r] + 1] if len(seg.chunk_starts(n, STEP_S)) > due[r] else None)
+        assert np.array_equal(res.labels, alone[r].labels) and np.array_equal(res.speakers, alone[r].speakers) and res.turns == alone[r].turns
+    bank.reset(1)
+    bank.push([None, pcm[:lens[1]], None], [None, lp[:4], None])
+    again = bank.finish(1)
+    assert np.array_equal(again.labels, alone[1].labels) and np.array_equal(again.count, alone[1].count)
+    assert bank.slots[2].sched.finished and diar.open_streams(1).finish(0).n_speakers == 0
