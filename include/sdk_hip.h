@@ -47,7 +47,7 @@
  *     sdk_stream_state_bytes  sdk_stream_reset  sdk_stream_step  sdk_stream_flush  sdk_stream_centroids streaming diarization: online speaker tracking (stream.py)
  * BUILDING BLOCKS AND KNOBS - exported for the parity tests and the A/B tools, free to change between rounds, not for binding:
  *     sdk_conv_gemm*  sdk_colstats_finish  sdk_res2net_chain*  sdk_se_*  sdk_asp_*  sdk_rows_fc  (pieces of sdk_ecapa_forward)
- *     sdk_resnet_conv2d  (piece of sdk_resnet_forward)  sdk_resnet_masked_pool  (piece of sdk_resnet_forward_masked)
+ *     sdk_resnet_conv2d  sdk_resnet_pool  (pieces of sdk_resnet_forward)  sdk_resnet_masked_pool  (piece of sdk_resnet_forward_masked)
  *     sdk_sincnet_frontend  sdk_bilstm_layer  (pieces of sdk_segmentation_forward)
  *     sdk_set_option  sdk_set_gemm_variant  sdk_profile_begin / _end  sdk_debug_set_ptr  sdk_affinity_plan*  sdk_affinity_block_plan*  sdk_affinity_matvec_plan  sdk_conv_gemm_hp
  *     sdk_seg_mean_hp  sdk_se_apply_hp  sdk_asp_stats_hp  sdk_asp_pool_hp  (the precise mode's sweeps, pieces of its forwards)
@@ -442,13 +442,16 @@ int sdk_resnet_conv2d(sdk_ctx* ctx, const sdk_resnet_conv_args* a, void* stream)
  *   order, feature order as in sdk_resnet_forward; with 0 / 1 weights the unbiased statistic over the selected columns.  A row depends on
  *   its own weights only.  Rows with valid == 0 are written as zeros (a valid row needs v1 - v2 / v1 > 0: two columns).
  *   Precision 0 and 2 (1 is refused).  Workspace: sdk_resnet_masked_workspace_bytes(d, B, T, S).
- *   sdk_resnet_masked_pool: building block: the pooling alone on a last map x [B][F][T][C] (fmt 0: bf16, 2: fp16) -> out [B S][2 C F]. */
+ *   sdk_resnet_masked_pool: building block: the pooling alone on a last map x [B][F][T][C] (fmt 0: bf16, 2: fp16) -> out [B S][2 C F].
+ *   sdk_resnet_pool: building block: the unweighted pooling of sdk_resnet_forward alone on the same layout -> out [B][2 C F]: mean = sum x
+ *   (1 / T), std = sqrt(sum (x - mean)^2 (1 / (T - 1)) + 1e-7), two passes, fp32, frames in order.  T < 2 and fmt 1 are refused. */
 int sdk_resnet_last_map_frames(const sdk_resnet_desc* d, int T);
 size_t sdk_resnet_masked_workspace_bytes(const sdk_resnet_desc* d, int B, int T, int S);
 int sdk_resnet_forward_masked(sdk_ctx* ctx, const void* wblob, const sdk_resnet_desc* d, const uint16_t* feats, int ldf, int B, int T,
                               int S, const float* w, const int32_t* valid, void* ws, size_t ws_bytes, float* emb, void* stream);
 int sdk_resnet_masked_pool(sdk_ctx* ctx, const uint16_t* x, int B, int F, int T, int C, int S, const float* w, const int32_t* valid,
                            float* out, int fmt, void* stream);
+int sdk_resnet_pool(sdk_ctx* ctx, const uint16_t* x, int B, int F, int T, int C, float* out, int fmt, void* stream);
 
 /* ---- speaker segmentation: PyanNet as in pyannote segmentation-3.0 (segmentation.py; csrc/segmentation.hip).  One chunk of S >= 991
  *      samples (16 kHz mono int16) -> F(S) = ((((S - 251) / 10 + 1) / 3 - 4) / 3 - 4) / 3 frames (589 at S = 160 000; frame i sees samples

@@ -149,6 +149,7 @@ SIGNATURES = {
     "sdk_resnet_masked_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
     "sdk_resnet_forward_masked": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
     "sdk_resnet_masked_pool": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "sdk_resnet_pool": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "sdk_powerset_decode": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "sdk_diarize_masks": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "sdk_diarize_frames": (_i64, [_i64]),

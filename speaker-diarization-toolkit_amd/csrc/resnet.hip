@@ -410,3 +410,9 @@ extern "C" int sdk_resnet_masked_pool(sdk_ctx* ctx, const uint16_t* x, int B, in
   SDK_REQUIRE(fmt == 0 || fmt == 2, "sdk_resnet_masked_pool: fmt=%d (0: bf16, 2: fp16; the precise mode is not built for the ResNet34 family)", fmt);
   return resnet_masked_tstp_impl(ctx, x, B, F, T, C, S, w, valid, out, stream, fmt == 2);
 }
+
+extern "C" int sdk_resnet_pool(sdk_ctx* ctx, const uint16_t* x, int B, int F, int T, int C, float* out, int fmt, void* stream) {
+  SDK_REQUIRE(fmt == 0 || fmt == 2, "sdk_resnet_pool: fmt=%d (0: bf16, 2: fp16; the precise mode is not built for the ResNet34 family)", fmt);
+  SDK_REQUIRE((int64_t)B * F < (1ll << 31), "sdk_resnet_pool: batch too large (B=%d F=%d)", B, F);
+  return resnet_tstp_impl(ctx, x, B, F, T, C, out, stream, fmt == 2);
+}

@@ -130,8 +130,14 @@ def global_frames(n_samples: int) -> int:
 
 
 def decode_host(logp: np.ndarray) -> np.ndarray:
-    """logp [..., 7] -> uint8 argmax class (numpy's first maximum: ties to the lower class)."""
-    return np.argmax(np.asarray(logp), axis=-1).astype(np.uint8)
+    """logp [..., 7] -> uint8 argmax class (numpy's first maximum: ties to the lower class).  NaN as in sdk_powerset_decode, whose scan keeps
+    the best so far unless a class is greater: a NaN in class 0 keeps class 0, a NaN elsewhere is never taken."""
+    logp = np.asarray(logp)
+    nan = np.isnan(logp)
+    if nan.any():
+        logp = np.where(nan, -np.inf, logp)
+        logp[..., 0] = np.where(nan[..., 0], np.inf, logp[..., 0])
+    return np.argmax(logp, axis=-1).astype(np.uint8)
 
 
 def masks_host(cls: np.ndarray, T4: int):

@@ -4,10 +4,13 @@ loop form, written from the rules and sharing no code with diarize.py.
   decode / masks / reconstruct   plain Python loops over frames, columns and chunks (reconstruct scans EVERY chunk per global frame)
   last_map / weighted_embed      resnet_ref.layer_boundary_embed's layer loop restated up to the pooling (that function does not return the
                                  last map), then the weighted statistics and seg_1 in float64
+  *_fp32_in_order / *_one_pass   fp32 restatements of the poolings: the yardstick of their bounds, and the one-pass form the bounds must reject
+  pool_case / pool_cases         the seeded inputs of the pooling edge tests (tests/test_diarize_edges_cpu.py, tests/test_diarize_edges_gpu.py)
   cluster / assign / order / turns / rttm   the host stages, with scipy's centroid linkage and ahc_ref's threshold rule
 """
 from __future__ import annotations
 
+import functools
 import os
 import sys
 from typing import Optional
@@ -57,6 +60,20 @@ def masks(cls, T4: int):
             w[b, s] = row
             info[b, s] = (active, clean_frames, used, sum(row) >= MIN_VALID)
     return w, info
+
+
+def column_counts(cls, T4: int) -> np.ndarray:
+    """-> [B, 3, 2] int: per (chunk, speaker) the columns of the last map in which the speaker is active, and those in which it is alone
+    (the sums that masks() compares with MIN_CLEAN and MIN_VALID)."""
+    B, F = cls.shape
+    out = np.zeros((B, 3, 2), np.int64)
+    for b in range(B):
+        for j in range(T4):
+            members = CLASSES[cls[b, min(F - 1, (j * F) // T4)]]
+            for s in members:
+                out[b, s, 0] += 1
+                out[b, s, 1] += len(members) < 2
+    return out
 
 
 def n_global(n_samples: int) -> int:
@@ -158,6 +175,112 @@ def weighted_stats_fp32_in_order(last: torch.Tensor, w: torch.Tensor) -> torch.T
         d = x[..., t] - mean
         q = fma(w[..., t] * d, d, q)
     return torch.cat([mean, torch.sqrt(q / (v1 - v2 / v1) + 1e-7)], dim=2)
+
+
+def weighted_stats_fp32_one_pass(last: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """What the pooling must NOT be: the same statistic in fp32 from ONE sweep (sum w x and sum w x^2 by fused multiply-adds in frame order,
+    var = (sum w x^2 - (sum w x)^2 / v1) / (v1 - v2 / v1)).  On data with a large mean the subtraction cancels; the edge tests measure how
+    far beyond the yardstick this lands, to show that their bound tells the two apart."""
+    x = last.float().reshape(last.shape[0], 1, -1, last.shape[-1])
+    w = w.float()[:, :, None, :]
+
+    def fma(a, b, c):
+        return (a.double() * b.double() + c.double()).float()
+    v1 = torch.zeros(w.shape[:-1])
+    v2 = torch.zeros(w.shape[:-1])
+    s = torch.zeros(w.shape[0], w.shape[1], x.shape[2])
+    q = torch.zeros_like(s)
+    for t in range(x.shape[-1]):
+        v1 = v1 + w[..., t]
+        v2 = fma(w[..., t], w[..., t], v2)
+        s = fma(w[..., t].expand_as(s), x[..., t].expand_as(s), s)
+        q = fma(w[..., t] * x[..., t], x[..., t].expand_as(s), q)
+    var = (q - s * s / v1) / (v1 - v2 / v1)
+    return torch.cat([s / v1, torch.sqrt(var.clamp_min(0.0) + 1e-7)], dim=2)
+
+
+def tstp_stats_fp32_in_order(x: torch.Tensor) -> torch.Tensor:
+    """The unweighted pooling (resnet_ref.tstp_stats) in fp32 with the kernel's order on the channel-last map x [B, F, T, C] -> [B, 2 C F]:
+    the sum in frame order, mean = s * (1 / T), the square sum by fused multiply-adds, q * (1 / (T - 1)), sqrt(. + 1e-7).  Its deviation
+    from float64 is the yardstick of the unmasked pooling's bound."""
+    B, F, T, C = x.shape
+    x = x.float().permute(0, 3, 1, 2).reshape(B, C * F, T)
+    s = torch.zeros(B, C * F)
+    one = torch.ones_like(s)                                             # every constant as an fp32 tensor: no scalar is applied in a wider type
+    inv_t, inv_t1, eps = one / torch.full_like(s, T), one / torch.full_like(s, T - 1), torch.full_like(s, 1e-7)
+    for t in range(T):
+        s = s + x[..., t]
+    mean = s * inv_t
+    q = torch.zeros_like(s)
+    for t in range(T):
+        d = x[..., t] - mean
+        q = (d.double() * d.double() + q.double()).float()
+    return torch.cat([mean, torch.sqrt(q * inv_t1 + eps)], dim=1)
+
+
+# the edge shapes of the masked pooling (B, F4, T4, C, S): idle lanes (C < 256), the strided channel loop (C = 300, 512), a full speaker group
+# (S = 4), a second group of one speaker (S = 5, 9), S T4 at the 12288-float LDS limit, and the production shape
+POOL_SHAPES = [(1, 1, 2, 64, 1), (2, 3, 3, 32, 4), (2, 2, 37, 300, 5), (1, 2, 126, 512, 9), (1, 1, 4096, 64, 3), (3, 10, 126, 256, 3)]
+# the unmasked pooling (B, F4, T4, C)
+TSTP_SHAPES = [(1, 1, 2, 64), (2, 3, 9, 32), (2, 2, 37, 300), (1, 10, 126, 256), (1, 1, 1001, 512)]
+POOL_DTYPE = {0: torch.bfloat16, 2: torch.float16}
+
+
+def pool_data(rng, shape, data: str, fmt: int) -> torch.Tensor:
+    """A channel-last last map in the 2-byte format fmt.  signed: randn; offset: 100 + 0.25 randn, rounded to the format (bf16 keeps steps
+    of 0.5 there, fp16 of 1 / 16: a mean 200 to 1600 times the spread, which a one-pass variance does not survive in fp32)."""
+    g = rng.standard_normal(shape).astype(np.float32)
+    return torch.from_numpy(g if data == "signed" else 100.0 + 0.25 * g).to(POOL_DTYPE[fmt])
+
+
+def pool_case(shape, data: str, weights: str, fmt: int):
+    """Seeded inputs of one masked-pooling edge case -> (x [B, F4, T4, C] 2-byte, w [B, S, T4] fp32, valid [B, S] int32).
+    binary weights: p = 0.4 with the first and the last column forced to 1 (every row has its two columns), and the middle column of
+    row 0 of segment 0; fractional: uniform in [0.05, 1].  S >= 4: valid is mixed - row 1 of every segment is invalid with all-zero weights, row 3 invalid with weights, and in a second
+    segment row 0 (zero weights) as well, so that valid is read at b S + s."""
+    B, F4, T4, Cc, S = shape
+    rng = np.random.default_rng([B, F4, T4, Cc, S, fmt, data == "offset", weights == "binary"])
+    x = pool_data(rng, (B, F4, T4, Cc), data, fmt)
+    if weights == "binary":
+        w = (rng.random((B, S, T4)) < 0.4).astype(np.float32)
+        w[:, :, 0] = w[:, :, -1] = 1.0
+        w[0, 0, T4 // 2] = 1.0                                            # a valid row of three columns even at T4 = 3 (two columns divide exactly)
+    else:
+        w = (0.05 + 0.95 * rng.random((B, S, T4))).astype(np.float32)
+    valid = np.ones((B, S), np.int32)
+    if S >= 4:
+        valid[:, 1] = valid[:, 3] = 0
+        w[:, 1] = 0.0
+        if B > 1:
+            valid[1, 0] = 0
+            w[1, 0] = 0.0
+    return x, torch.from_numpy(w), torch.from_numpy(valid)
+
+
+@functools.lru_cache(maxsize=None)
+def pool_reference(shape, data: str, weights: str, fmt: int):
+    """One edge case with its float64 statistics and its yardstick, computed once per process and left unchanged by its users ->
+    (x, w, valid, want [B, S, 2 C F4] float64, yardstick: the fp32-in-order restatement's largest deviation over the valid rows)."""
+    x, w, valid = pool_case(shape, data, weights, fmt)
+    last = x.float().permute(0, 3, 1, 2)
+    want = weighted_stats(last, w)
+    ok = valid.bool()
+    yard = float((weighted_stats_fp32_in_order(last, w).double() - want)[ok].abs().max())
+    return x, w, valid, want, yard
+
+
+@functools.lru_cache(maxsize=None)
+def tstp_reference(shape, data: str, fmt: int):
+    """One edge case of the unmasked pooling -> (x [B, F4, T4, C] 2-byte, want [B, 2 C F4] float64, yardstick)."""
+    rng = np.random.default_rng(list(shape) + [fmt, data == "offset"])
+    x = pool_data(rng, shape, data, fmt)
+    want = RR.tstp_stats(x.float())
+    return x, want, float((tstp_stats_fp32_in_order(x).double() - want).abs().max())
+
+
+def pool_cases():
+    """Every (shape, data, weights) of the edge tests; fractional weights from T4 = 37 on."""
+    return [(sh, data, wk) for sh in POOL_SHAPES for data in ("signed", "offset") for wk in ("binary", "fractional") if wk == "binary" or sh[2] >= 37]
 
 
 def weighted_embed(weights, last: torch.Tensor, w: torch.Tensor) -> torch.Tensor:

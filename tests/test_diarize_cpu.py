@@ -191,7 +191,7 @@ def test_last_map_restatement_reproduces_layer_boundary_embed():
 def test_new_symbols_exist_in_the_built_library():
     lib = sub("_lib").load_library()
     for name in ("sdk_powerset_decode", "sdk_diarize_masks", "sdk_diarize_reconstruct", "sdk_diarize_frames", "sdk_resnet_forward_masked",
-                 "sdk_resnet_masked_workspace_bytes", "sdk_resnet_last_map_frames", "sdk_resnet_masked_pool"):
+                 "sdk_resnet_masked_workspace_bytes", "sdk_resnet_last_map_frames", "sdk_resnet_masked_pool", "sdk_resnet_pool"):
         assert hasattr(lib, name)
     rn = sub("resnet")
     _, d = rn.pack_weights(rn.synthetic_weights(0))
