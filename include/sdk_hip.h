@@ -697,6 +697,12 @@ int sdk_l2norm(sdk_ctx* ctx, const float* X, int N, int d, float* E, uint16_t* E
  *                 (k = 1 is the fast path: ~1 % of rows rescanned; larger k rescans more).
  * d must be 192 (= 12 MFMA k-steps), k <= 4.  idx [N,k] int32, score [N,k] fp32.
  * n_rescanned (device int32, may be NULL) receives the number of rows that took the exact path.
+ *   non-finite rows : a NaN score compares with nothing and is never taken.  A slot for which no profile has a comparable score holds
+ *                 idx -1, score -inf: every slot of a segment row that holds a NaN, and the slots past the comparable profiles when
+ *                 profile rows hold NaNs.  idx is always in [-1, P); a caller skips idx < 0 (backend.aggregate_matches does, and
+ *                 -inf clears no threshold).  All other rows keep the guarantee above.  A NaN residual (resid_e[n], or resid_p[0]
+ *                 as the max over profile residuals with a NaN among them) certifies nothing: the rows it touches take the exact
+ *                 rescan and are counted in n_rescanned.  The same on every path (k = 1 fast path, all its plans; general path).
  * ws: sdk_affinity_workspace_bytes(N, P). */
 size_t sdk_affinity_workspace_bytes(int N, int P);
 /* Host-only (no device): the k = 1 path's work decomposition, for tests.  out5 = {segment groups, profile stages per group,

@@ -121,6 +121,12 @@ __device__ __forceinline__ void insert_sorted(float x, float* m) {
 
 __device__ __forceinline__ float max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 
+// NaN test on the BITS: this file is built -fno-honor-nans, under which a floating-point comparison with a NaN operand means whatever the
+// compiler likes (`!(a > b)` may become `a <= b`).  The exact pass and the rescan keep the NaN contract of sdk_affinity_topk (include/sdk_hip.h)
+// with it: a NaN score is never taken, a row whose certificate is not a number takes the rescan, a row left without a score reports (-1, -inf).
+__device__ __forceinline__ bool nan_bits(float v) { return (__float_as_uint(v) & 0x7fffffffu) > 0x7f800000u; }
+constexpr int NO_IDX = 0x7fffffff;     // "no profile yet" inside the kernels (loses every tie); reported as -1
+
 // WAVES waves x SEGB blocks of 32 segments; TPS tiles per LDS stage; NSTAGE stages.  (Rounds 3-4 also built, measured level or behind and removed: the
 // reduction of tile t-1 dealt out by hand under tile t's MFMAs - 4-6 % slower, the two waves of a SIMD overlap those phases already -, static wave
 // priorities, hand-pipelined fragment reads in this kernel, 4 tiles per stage, a late ring refill; docs/rounds/r01-r04_design_history.md 5.11.)
@@ -651,6 +657,7 @@ __global__ __launch_bounds__(256) void aff_rowcol_rescore_kernel(const float* __
     bs = dot192_group8(e24, Pm + (int64_t)bi * D, j);
   }
   const int c_first = bi;
+  if (nan_bits(bs)) { bs = -INFINITY; bi = NO_IDX; }                 // a NaN row (segment or profile): not a score, and no cut either
   const float cut = fmaxf(best - 3.0f * eps, bs - eps);
   float u = -INFINITY;
   int mine[MAXP][3];
@@ -712,7 +719,7 @@ __global__ __launch_bounds__(256) void aff_rowcol_rescore_kernel(const float* __
       for (int q = 1; q < MAXC; ++q)
         if (q == m) c0 = list[q];
       const float s0 = dot192_group8(e24, Pm + (int64_t)c0 * D, j);
-      if (better(s0, c0, bs, bi)) { bs = s0; bi = c0; }
+      if (!nan_bits(s0) && better(s0, c0, bs, bi)) { bs = s0; bi = c0; }
     }
   }
   u = fmaxf(u, __shfl_xor(u, 4, 64));
@@ -721,11 +728,12 @@ __global__ __launch_bounds__(256) void aff_rowcol_rescore_kernel(const float* __
     // (b) intersections pruned by best - 3 eps: exact < best - 2 eps; (c) intersections pruned by s1 - eps: exact < s1
     // (the slack inside eps exceeds the tag truncation), and s1 <= the winner's score by construction.
     const float outside = fmaxf(u + eps, best - 2.0f * eps);
-    const bool uncertain = M > MAXC || !(bs > outside) || np_raw > MAXP;   // (np_raw > MAXP: a part's record was dropped - cannot happen)
+    // (np_raw > MAXP: a part's record was dropped - cannot happen; a NaN eps - a NaN residual, of this row or of a profile - certifies nothing)
+    const bool uncertain = M > MAXC || !(bs > outside) || np_raw > MAXP || nan_bits(eps) || bi == NO_IDX;
     row_best[row] = 0ull;                                            // the rescan's per-flagged-row keys (index < count <= N) ...
     if ((row & (RS_ROWS - 1)) == 0) quad_done[row / RS_ROWS] = 0;   // arrival counters of the rescan's row quads (index < count / RS_ROWS <= N / RS_ROWS)
     if (uncertain) flag_rows[atomicAdd(flag_count, 1)] = row;
-    idx[row] = bi;
+    idx[row] = bi == NO_IDX ? -1 : bi;
     score[row] = bs;
   }
 }
@@ -798,8 +806,8 @@ __global__ __launch_bounds__(256) void aff_rescan4_kernel(const float* __restric
       for (int x = 0; x < RS_ROWS; ++x) {
         const float sa = dot192_regs(e24[x], pv[0]);              // every lane of the group runs the shuffles
         const float sb = dot192_regs(e24[x], pv[1]);
-        if (p0 + g < s1 && better(sa, pa, bs[x], bi[x])) { bs[x] = sa; bi[x] = pa; }
-        if (p0 + g + 32 < s1 && better(sb, pb, bs[x], bi[x])) { bs[x] = sb; bi[x] = pb; }
+        if (p0 + g < s1 && !nan_bits(sa) && better(sa, pa, bs[x], bi[x])) { bs[x] = sa; bi[x] = pa; }
+        if (p0 + g + 32 < s1 && !nan_bits(sb) && better(sb, pb, bs[x], bi[x])) { bs[x] = sb; bi[x] = pb; }
       }
     }
     if (j == 0) {
@@ -814,7 +822,7 @@ __global__ __launch_bounds__(256) void aff_rescan4_kernel(const float* __restric
       group_best32(s, i);
       const int f = q * RS_ROWS + x;
       if (l == 0 && f < count) {
-        if (nsl == 1) { const int row = flag_rows[f]; idx[row] = i; score[row] = s; }
+        if (nsl == 1) { const int row = flag_rows[f]; idx[row] = i == NO_IDX ? -1 : i; score[row] = s; }
         else __hip_atomic_fetch_max(row_best + f, best_key(s, i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
@@ -840,7 +848,8 @@ __global__ __launch_bounds__(256) void aff_rescan4_kernel(const float* __restric
         const int f = q * RS_ROWS + tid;
         const unsigned long long key = __hip_atomic_load(row_best + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const int row = flag_rows[f];
-        idx[row] = (int)(0xffffffffu - (uint32_t)key);
+        const int wi = (int)(0xffffffffu - (uint32_t)key);
+        idx[row] = wi == NO_IDX ? -1 : wi;                           // (no comparable score in any slice: the key of (-inf, NO_IDX))
         const uint32_t o = (uint32_t)(key >> 32);
         score[row] = __uint_as_float((o & 0x80000000u) ? o & 0x7fffffffu : ~o);
       }

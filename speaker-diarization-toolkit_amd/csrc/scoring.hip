@@ -200,6 +200,10 @@ __global__ __launch_bounds__(WAVES * 64, 2) void affinity_coarse_kernel(const bf
   }
 }
 
+// A list slot that no score entered (a NaN compares with nothing: better() is false) still holds (-inf, 0x7fffffff); it is reported as
+// (-1, -inf), the NaN contract of sdk_affinity_topk (include/sdk_hip.h).  Only the three places that write idx / score do this.
+__device__ __forceinline__ int report_idx(int i) { return i == 0x7fffffff ? -1 : i; }
+
 __global__ __launch_bounds__(256) void affinity_rescore_kernel(const float* __restrict__ E, const float* __restrict__ Pm,
                                                               const float* __restrict__ resid_e,
                                                               const float* __restrict__ resid_p, int N, int P, int k,
@@ -270,7 +274,7 @@ __global__ __launch_bounds__(256) void affinity_rescore_kernel(const float* __re
       flag_rows[slot] = row;
     }
     for (int q = 0; q < k; ++q) {
-      idx[(int64_t)row * k + q] = bi[q];
+      idx[(int64_t)row * k + q] = report_idx(bi[q]);
       score[(int64_t)row * k + q] = bs[q];
     }
   }
@@ -323,7 +327,7 @@ __global__ __launch_bounds__(256) void affinity_rescan_kernel(const float* __res
       wave_select4(ls[tid], li[tid], ls[tid + 64], li[tid + 64], os, oi);
       if (tid == 0) {
         if (nsl == 1) {
-          for (int q = 0; q < k; ++q) { idx[(int64_t)row * k + q] = oi[q]; score[(int64_t)row * k + q] = os[q]; }
+          for (int q = 0; q < k; ++q) { idx[(int64_t)row * k + q] = report_idx(oi[q]); score[(int64_t)row * k + q] = os[q]; }
         } else {
 #pragma unroll
           for (int q = 0; q < 4; ++q) { part_s[(int64_t)item * 4 + q] = os[q]; part_i[(int64_t)item * 4 + q] = oi[q]; }
@@ -358,7 +362,7 @@ __global__ __launch_bounds__(64) void affinity_rescan_merge_kernel(int P, int k,
     }
     if (lane == 0) {
       const int row = flag_rows[f];
-      for (int q = 0; q < k; ++q) { idx[(int64_t)row * k + q] = fi[q]; score[(int64_t)row * k + q] = fs[q]; }
+      for (int q = 0; q < k; ++q) { idx[(int64_t)row * k + q] = report_idx(fi[q]); score[(int64_t)row * k + q] = fs[q]; }
     }
   }
 }

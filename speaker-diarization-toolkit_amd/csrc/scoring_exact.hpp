@@ -1,6 +1,7 @@
 // Exact fp32 scoring helpers shared by the general top-k path (scoring.hip) and the k = 1 row/column-maxima
 // fast path (affinity_rowcol.hip).  ONE dot-product routine everywhere: a profile's reported score is
-// bit-identical whichever kernel computed it (tests: k = 3 top-1 == k = 1 result).
+// bit-identical whichever kernel computed it (tests/test_affinity_edges_gpu.py: every path against the host restatement of
+// this routine, tests/affinity_ref.py, bit for bit; test_first_column_equals_every_k1_path: the first column of k = 2, 3, 4 == every k = 1 path).
 #pragma once
 #include "common.hpp"
 
