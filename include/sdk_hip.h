@@ -26,6 +26,7 @@
  *     sdk_fbank_tables_bytes  sdk_fbank_tables_fill  sdk_fbank_workspace_bytes  sdk_fbank  sdk_fbank_windows          k1
  *     sdk_ingest_create / _destroy / _acquire / _commit / _submit / _release / _copy_ms          host audio -> HBM, pinned + double-buffered
  *     sdk_ecapa_workspace_bytes  sdk_ecapa_forward  sdk_ecapa_calib_floats  sdk_ecapa_forward_calib            k2
+ *     sdk_ecapa_masked_workspace_bytes  sdk_ecapa_forward_masked  (diarization in the ECAPA space: S masked poolings per chunk)
  *     sdk_xvector_workspace_bytes  sdk_xvector_forward                                                  k2 (second model family)
  *     sdk_resnet_workspace_bytes  sdk_resnet_forward                                                    k2 (third model family: ResNet34)
  *     sdk_l2norm                                                                                        k3
@@ -65,7 +66,7 @@
 extern "C" {
 #endif
 
-#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5); still 4 with sdk_cohort_stats* and sdk_affinity_topk_snorm: new exports only, no caller of version 4 breaks */
+#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5); still 4 with sdk_cohort_stats* and sdk_affinity_topk_snorm, and with sdk_ecapa_forward_masked, sdk_ecapa_masked_workspace_bytes, sdk_asp_stats_masked_fmt and sdk_asp_pool_masked_fmt: new exports only, no struct or existing signature changes, no caller of version 4 breaks */
 
 typedef struct sdk_ctx sdk_ctx;
 
@@ -367,6 +368,42 @@ int sdk_ecapa_forward(sdk_ctx* ctx, const void* wblob, const sdk_ecapa_desc* wde
 size_t sdk_ecapa_calib_floats(const sdk_ecapa_desc* d, int B);
 int sdk_ecapa_forward_calib(sdk_ctx* ctx, const void* wblob, const sdk_ecapa_desc* wdesc, const uint16_t* feats, int ldf, int B, int T,
                             void* ws, size_t ws_bytes, float* emb, float* calib, void* stream);
+
+/* ---- The ECAPA-TDNN forward with S MASKED attentive statistics poolings per chunk (diarize.py with ecapa_diar.EcapaEmbedder: one per local
+ *      speaker of a 10-s chunk, so that diarization's centroids live in the space of sdk_ecapa_forward, the enrolled profiles and the AS-norm
+ *      cohort).  Parity with SpeechBrain / PyAnnote is unpinned, as everywhere here: THIS RULE is what the tests pin.
+ *   For a chunk b the trunk of sdk_ecapa_forward - blk0, the SE-Res2Net blocks and MFA, up to h [T, Cm] - runs ONCE, bit for bit the values
+ *   sdk_ecapa_forward computes at the same (B, T) (one function serves both); the SE squeeze stays over all T frames.  The mask enters at the
+ *   pooling only.  For each slot s < S, w = w[b][s][0..T) >= 0 (ANY non-negative weights, not only 0 / 1), v1 = sum_t w_t:
+ *     context    mu_c = sum_t w_t h_tc / v1,  sd_c = sqrt(max(sum_t w_t (h_tc - mu_c)^2 / v1, 1e-12))   (the biased form and floor of sdk_asp_stats)
+ *     ubias      = Wms [mu | sd] + b in fp32 (sdk_rows_fc), one row per (b, s)
+ *     hidden     a_t = tanh(BN(relu(h_t Wh + ubias))), stored in the 2-byte format
+ *     logits     l_tc = a_t . W2_c + b2_c, fp32
+ *     attention  m_c = max over {t : w_t > 0} of l_tc,  e_tc = w_t exp(l_tc - m_c),  alpha_tc = e_tc / sum_t e_tc; a frame with w_t = 0 enters
+ *                neither the maximum nor any sum
+ *     pooled     wmu_c = sum_t alpha_tc h_tc,  wsd_c = sqrt(max(sum_t alpha_tc (h_tc - wmu_c)^2, 1e-12))
+ *     embedding  pooled [b S + s] = wmu | wsd, then asp_bn and fc over the B S rows -> emb [B S, embed_dim]
+ *   A row depends on its own weights only.  Rows with valid[b][s] == 0 are written as zeros and their weights are never used for a division.  A
+ *   row with valid != 0 and v1 <= 0 is ZEROED (not refused: the weights are device memory), in the embeddings and in both building blocks.
+ *   With w == 1 this is the pooling of sdk_ecapa_forward; with 0 / 1 weights SpeechBrain's masked AttentiveStatisticsPooling with that mask.
+ *   fp32 arithmetic in two (statistics) and three (pooling) sweeps, every thread's frames in order, partial sums joined in a fixed order: results are
+ *   bit-identical run to run, no float atomics.
+ *   Schedule: trunk (h row-major), ONE sdk_asp_stats_masked launch for the B S rows, sdk_rows_fc, then per slot sdk_conv_gemm (hidden, the slot's
+ *   ubias rows: ldub = S A) + sdk_conv_gemm (logits into one reused fp32 buffer) + sdk_asp_pool_masked, sdk_rows_fc over B S rows.
+ *   Refused with a message: a precision-1 blob, S < 1 or S > 8, a null pointer, too small a workspace, T not above the receptive halo.
+ *   Building blocks (fmt 0: bf16 elements, 2: fp16; 1 refused), any T >= 1:
+ *   sdk_asp_stats_masked_fmt: h [B*T, ldh] (C % 8 == 0, ldh % 8 == 0, ldh >= C, 16-byte aligned) read once for all S slots -> out_ctx [B S][2 C] mean | std.
+ *   sdk_asp_pool_masked_fmt:  the logits [B*T, ldl] fp32 of slot s (C % 64 == 0, ldl % 4 == 0, ldh % 8 == 0, 16-byte aligned pointers) -> rows b S + s of
+ *                             pooled [B S][2 C]; the other rows are not touched. */
+size_t sdk_ecapa_masked_workspace_bytes(const sdk_ecapa_desc* d, int B, int T, int S);
+int sdk_ecapa_forward_masked(sdk_ctx* ctx, const void* wblob, const sdk_ecapa_desc* d, const uint16_t* feats, int ldf, int B, int T,
+                             int S, const float* w /*[B][S][T]*/, const int32_t* valid /*[B][S]*/, void* ws, size_t ws_bytes,
+                             float* emb /*[B S][embed_dim]*/, void* stream);
+int sdk_asp_stats_masked_fmt(sdk_ctx* ctx, const uint16_t* h, int64_t ldh, int B, int T, int C, int S, const float* w, const int32_t* valid,
+                             float* out_ctx /*[B S][2 C]*/, int precision, void* stream);
+int sdk_asp_pool_masked_fmt(sdk_ctx* ctx, const float* logits, int64_t ldl, const uint16_t* h, int64_t ldh, int B, int T, int C,
+                            int S, int s /*slot of these logits*/, const float* w, const int32_t* valid, float* pooled /*[B S][2 C]*/,
+                            int precision, void* stream);
 
 /* ---- x-vector (plain TDNN) forward - north_star names "ECAPA-TDNN/x-vector".  Frame layers l = 0..n_frame_layers-1:
  *      dilated conv (kernel[l], dilation[l], "same" length by segment-local reflection) -> ReLU -> BatchNorm(eval), bf16 layer-boundary

@@ -140,6 +140,10 @@ SIGNATURES = {
     "sdk_ecapa_forward": (_i, [_vp, _vp, C.POINTER(EcapaDesc), _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "sdk_ecapa_calib_floats": (_sz, [C.POINTER(EcapaDesc), _i]),
     "sdk_ecapa_forward_calib": (_i, [_vp, _vp, C.POINTER(EcapaDesc), _vp, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
+    "sdk_ecapa_masked_workspace_bytes": (_sz, [C.POINTER(EcapaDesc), _i, _i, _i]),
+    "sdk_ecapa_forward_masked": (_i, [_vp, _vp, C.POINTER(EcapaDesc), _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "sdk_asp_stats_masked_fmt": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "sdk_asp_pool_masked_fmt": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "sdk_xvector_workspace_bytes": (_sz, [_vp, _i, _i]),
     "sdk_xvector_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "sdk_resnet_workspace_bytes": (_sz, [_vp, _i, _i]),

@@ -15,6 +15,10 @@ Environment:
                       / "resnet34" (the WeSpeaker ResNet34 that PyAnnote 3.1 embeds with, resnet.py; 192-d).  SDK_RESNET_WEIGHTS: .npz in the public
                       state-dict naming of resnet.py (default: seeded synthetic).  Serves SDK_PRECISION 0 and 2, no bias correction, torch engine
                       only (SDK_NO_TORCH=1 is refused)
+  SDK_DIARIZE_MODEL   the embedding network of diarize / diarize_many / open_streams: "resnet34" (default: the ResNet34 of $SDK_RESNET_WEIGHTS, whatever
+                      SDK_MODEL is) / "ecapa" (the backend's own ECAPA-TDNN with masked attentive statistics pooling, ecapa_diar.py: needs
+                      SDK_MODEL=ecapa and SDK_PRECISION 0 or 2; a diarization's centroids then live in the enrolled profiles' space, so
+                      link_speakers(candidates=...) can name its speakers)
   SDK_ECAPA_WEIGHTS   .npz checkpoint in the weights.py naming (default: seeded synthetic weights -
                       there is no network here to fetch a pretrained model; a warning is printed)
   SDK_ECAPA_LAYOUT    "public": SDK_ECAPA_WEIGHTS is a checkpoint in the public ECAPA-TDNN state-dict naming (.ckpt / .pt via
@@ -62,6 +66,15 @@ class Backend(EmbeddingBackend):
         self.model = os.environ.get("SDK_MODEL", "ecapa").strip().lower()
         if self.model not in ("ecapa", "xvector", "resnet34"):
             raise ValueError(f"SDK_MODEL={self.model!r}: expected 'ecapa', 'xvector' or 'resnet34'")
+        self.diarize_model = os.environ.get("SDK_DIARIZE_MODEL", "resnet34").strip().lower()
+        if self.diarize_model not in ("resnet34", "ecapa"):
+            raise ValueError(f"SDK_DIARIZE_MODEL={self.diarize_model!r}: expected 'resnet34' (default) or 'ecapa'")
+        if self.diarize_model == "ecapa":
+            if self.model != "ecapa":
+                raise ValueError(f"SDK_DIARIZE_MODEL=ecapa diarizes in the space of the backend's own ECAPA-TDNN: it requires SDK_MODEL=ecapa, got SDK_MODEL={self.model!r}")
+            if os.environ.get("SDK_PRECISION", "0").strip() not in ("0", "2"):
+                raise ValueError(f"SDK_DIARIZE_MODEL=ecapa requires SDK_PRECISION 0 (bf16) or 2 (fp16): the masked pooling is not built for the precise mode, got "
+                                 f"SDK_PRECISION={os.environ.get('SDK_PRECISION')!r}")
         wenv = {"xvector": "SDK_XVECTOR_WEIGHTS", "resnet34": "SDK_RESNET_WEIGHTS"}.get(self.model, "SDK_ECAPA_WEIGHTS")
         if not os.environ.get(wenv):
             print(f"mi355x backend: {wenv} not set - using seeded synthetic {dict(xvector='x-vector', resnet34='ResNet34').get(self.model, 'ECAPA-TDNN')} weights "
@@ -461,8 +474,11 @@ class Backend(EmbeddingBackend):
         return aggregate_counts(np.concatenate(counts), st, x.size)
 
     def diarizer(self):
-        """The resident diarization pipeline (diarize.py): Backend.segmentation() and the ResNet34 built from $SDK_RESNET_WEIGHTS (.npz in the
-        public naming, else seeded synthetic) whatever SDK_MODEL is; precision from SDK_PRECISION (0 or 2).  The PLDA model of
+        """The resident diarization pipeline (diarize.py): Backend.segmentation() and the embedding network SDK_DIARIZE_MODEL names.
+        "resnet34" (default): the ResNet34 built from $SDK_RESNET_WEIGHTS (.npz in the public naming, else seeded synthetic) whatever
+        SDK_MODEL is; precision from SDK_PRECISION (0 or 2).  "ecapa" (needs SDK_MODEL=ecapa, SDK_PRECISION 0 or 2): ecapa_diar.EcapaEmbedder
+        on the engine's own ECAPA-TDNN - its weights ($SDK_ECAPA_WEIGHTS), bias correction and embedding space, the one profiles are
+        enrolled in - with S masked attentive statistics poolings per chunk (sdk_ecapa_forward_masked).  The PLDA model of
         clustering="vbx" comes from $SDK_PLDA_TRANSFORM (xvec_transform.npz: mean1, mean2, lda) and $SDK_PLDA (plda.npz: mu, tr, psi), both or
         neither, with $SDK_PLDA_DIM (64 or 128, default 128) dimensions kept; else a seeded synthetic model, made on first use."""
         if self.lite:
@@ -471,7 +487,10 @@ class Backend(EmbeddingBackend):
             from . import resnet
             from .diarize import Diarizer
             model = self.segmentation()
-            if self.model == "resnet34":
+            if self.diarize_model == "ecapa":
+                from .ecapa_diar import EcapaEmbedder
+                net = EcapaEmbedder(self.engine())                # the engine's own blob: the enrolled space, bias correction included
+            elif self.model == "resnet34":
                 net = self._extractor                            # built by engine() from the same weights
             else:
                 prec = int(os.environ.get("SDK_PRECISION", "0"))
@@ -498,7 +517,8 @@ class Backend(EmbeddingBackend):
     def diarize(self, samples_or_path, **kw):
         """Who spoke when, with no transcript and no enrolled profiles: a recording (16 kHz mono int16 samples, or the path of an audio file,
         decoded to the audio profile) -> diarize.DiarizationResult (turns [(start_s, end_s, speaker)], n_speakers, unit centroids in the
-        embedding space of score_windows, labels, count, speakers); diarize.to_rttm(result.turns, uri) writes RTTM.  Keywords: step_s,
+        diarizer's embedding space - that of score_windows and the enrolled profiles under SDK_MODEL=resnet34, or SDK_MODEL=ecapa with
+        SDK_DIARIZE_MODEL=ecapa - labels, count, speakers); diarize.to_rttm(result.turns, uri) writes RTTM.  Keywords: step_s,
         threshold, min_cluster_size, max_speakers, logp, constrained, clustering, vbx, speakers (diarize.Diarizer.run).  The default threshold is PyAnnote 3.1's, tuned
         for its trained ResNet34 ($SDK_RESNET_WEIGHTS); with the synthetic weights pass a threshold of your own.  constrained=True
         (PyAnnote's constrained_argmax; default False): the local speakers of a chunk get pairwise different clusters, the one-to-one
@@ -546,13 +566,14 @@ class Backend(EmbeddingBackend):
         join - cut at `threshold` (PyAnnote's within-recording default: untuned for centroids across recordings, pass your own).
         candidates: profile dicts as identify_speaker takes them, loaded through the same store path; each enrolled speaker gives ONE row, the
         float64 mean of their enrolled unit embeddings, re-normalised, and no global speaker ever holds two of them.  The result
-        (diarize.SpeakerLinks) then carries names [n_global]: the speaker_id, or None.  The centroids of a diarization live in the ResNet34's
-        space, so candidates need SDK_MODEL=resnet34 (their embeddings are then the diarizer's own)."""
+        (diarize.SpeakerLinks) then carries names [n_global]: the speaker_id, or None.  The centroids of a diarization live in the
+        diarizer's space, so candidates need it to be the enrolled one: SDK_MODEL=resnet34, or SDK_MODEL=ecapa with SDK_DIARIZE_MODEL=ecapa."""
         if self.lite:
             raise ValueError("link_speakers needs the torch engine: not available with SDK_NO_TORCH=1")
-        if candidates is not None and self.model != "resnet34":
+        if candidates is not None and not (self.model == "resnet34" or (self.model == "ecapa" and self.diarize_model == "ecapa")):
             raise ValueError(f"link_speakers: candidates are enrolled in the {self.model!r} embedding space (SDK_MODEL), the centroids of a diarization "
-                             "in the diarizer's ResNet34 space: enrol and link with SDK_MODEL=resnet34")
+                             f"in the diarizer's {self.diarize_model!r} space (SDK_DIARIZE_MODEL): enrol and link with SDK_MODEL=resnet34, or with "
+                             "SDK_MODEL=ecapa and SDK_DIARIZE_MODEL=ecapa")
         from .diarize import link_speakers
         profiles, names = None, None
         if candidates is not None:

@@ -66,6 +66,13 @@ int se_gate_residual_impl(sdk_ctx* ctx, const uint16_t* z, int64_t ldz, const ui
 int asp_stats_impl(sdk_ctx* ctx, const uint16_t* h, int64_t ldh, int B, int T, int C, float* out_ctx, void* stream, bool f16);
 int asp_pool_impl(sdk_ctx* ctx, const float* logits, int64_t ldl, const uint16_t* h, int64_t ldh, int B, int T, int C, float* pooled, void* stream, bool f16);
 
+// asp_masked.hip: the masked attentive statistics pooling sweeps (internal; sdk_ecapa_forward_masked).  ok_out (optional, [B S] int32): 1 where
+// valid != 0 and the row has weight (v1 > 0) - the rows that are not written as zeros
+int asp_stats_masked_impl(sdk_ctx* ctx, const uint16_t* h, int64_t ldh, int B, int T, int C, int S, const float* w, const int32_t* valid, float* out_ctx,
+                          void* stream, bool f16, int32_t* ok_out);
+int asp_pool_masked_impl(sdk_ctx* ctx, const float* logits, int64_t ldl, const uint16_t* h, int64_t ldh, int B, int T, int C, int S, int s, const float* w,
+                         const int32_t* valid, float* pooled, void* stream, bool f16);
+
 // res2net.hip: sdk_res2net_chain with the optional fragment-ordered weight copies (internal; sdk_ecapa_forward)
 int res2net_chain_launch(sdk_ctx* ctx, const uint16_t* U, int64_t ldu, uint16_t* R, int64_t ldr, const uint16_t* const* W,
                          const uint16_t* const* Wpk, const float* const* bias, const float* const* scale, const float* const* shift,

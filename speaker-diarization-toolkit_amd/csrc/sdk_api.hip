@@ -182,7 +182,8 @@ struct FwdWs {
   float *ctx, *ubias, *logits, *pooled, *se, *stats, *mean;
 };
 
-size_t fwd_layout(const sdk_ecapa_desc* d, int B, int T, char* base, FwdWs* w) {
+// full_logits: the masked forward's pooling reads the fp32 logits from HBM at every T
+size_t fwd_layout(const sdk_ecapa_desc* d, int B, int T, char* base, FwdWs* w, bool full_logits = false) {
   const size_t M = (size_t)B * T, C = d->channels, Cm = d->mfa_channels, S = d->sub_channels, A = d->attn_channels;
   size_t off = 0;
   auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += a256(bytes); return p; };
@@ -198,7 +199,7 @@ size_t fwd_layout(const sdk_ecapa_desc* d, int B, int T, char* base, FwdWs* w) {
   char* cx = take((size_t)B * 2 * Cm * 4);
   char* ub = take((size_t)B * A * 4);
   // the [M, Cm] fp32 attention logits exist in HBM only on the unfused pooling path (37 % of the workspace otherwise)
-  const bool fused_asp = A == 128 && T <= sdk_asp_fused_max_frames();
+  const bool fused_asp = !full_logits && A == 128 && T <= sdk_asp_fused_max_frames();
   char* lg = take(fused_asp ? 256 : M * Cm * 4);
   char* po = take((size_t)B * 2 * Cm * 4);
   char* se = take(sdk_se_workspace_bytes(B, (int)C, d->se_channels));
@@ -378,32 +379,15 @@ extern "C" int sdk_ecapa_forward_calib(sdk_ctx* ctx, const void* wblob, const sd
   return ecapa_forward_impl(ctx, wblob, d, feats, ldf, B, T, ws, ws_bytes, emb, calib, stream);
 }
 
-static int ecapa_forward_impl(sdk_ctx* ctx, const void* wblob, const sdk_ecapa_desc* d, const uint16_t* feats, int ldf,
-                              int B, int T, void* ws, size_t ws_bytes, float* emb, float* calib, void* stream) {
-  SDK_REQUIRE(ctx && wblob && feats && ws && emb, "sdk_ecapa_forward: null argument");
-  if (int rc = check_desc(d)) return rc;
-  SDK_REQUIRE(B > 0 && T > 0, "sdk_ecapa_forward: empty batch (B=%d T=%d)", B, T);
-  SDK_REQUIRE((int64_t)B * T < (1ll << 31), "sdk_ecapa_forward: B*T overflows int32; split the batch");
-  SDK_REQUIRE(ldf >= d->n_mels_padded && ldf % 8 == 0, "sdk_ecapa_forward: ldf=%d < padded mel width %d", ldf, d->n_mels_padded);
-  // The numerical contract is the DESCRIPTOR's (per call): features must be in that format (sdk_fbank_fmt with the same precision).  The context's
-  // "precision" option plays no part here since round 5 - two engines with different contracts on one device share no mutable state.
-  int maxhalo = d->kernel0 / 2;
-  for (int i = 0; i < d->n_blocks; ++i) maxhalo = d->dilation[i] > maxhalo ? d->dilation[i] : maxhalo;
-  SDK_REQUIRE(T > maxhalo, "sdk_ecapa_forward: segments of %d frames are shorter than the receptive halo %d", T, maxhalo);
-  SDK_REQUIRE(ws_bytes >= sdk_ecapa_workspace_bytes(d, B, T), "sdk_ecapa_forward: workspace too small (%zu < %zu)", ws_bytes,
-              sdk_ecapa_workspace_bytes(d, B, T));
-  SDK_REQUIRE(((uintptr_t)ws % 256) == 0 && ((uintptr_t)wblob % 256) == 0, "sdk_ecapa_forward: ws/wblob must be 256-byte aligned");
-
-  {  // every slot the schedule dereferences must be present in the blob
-    const int tbs = EL_TAIL_BASE(d->n_blocks);
-    for (int i = 1; i <= d->n_blocks; ++i)
-      for (int s = EL_SE_W1T; s <= EL_SE_B2; ++s)
-        SDK_REQUIRE(d->off[EL_BLOCK_BASE(i) + s] >= 0, "sdk_ecapa_forward: SE weight slot %d of block %d missing", s, i);
-    for (int s = EL_ASP_WH; s <= EL_FC_B; ++s) SDK_REQUIRE(d->off[tbs + s] >= 0, "sdk_ecapa_forward: tail weight slot %d missing", s);
-  }
-  if (d->precision == 1) return ecapa_forward_hp(ctx, wblob, d, feats, ldf, B, T, ws, emb, stream);
-  FwdWs w;
-  fwd_layout(d, B, T, (char*)ws, &w);
+// The trunk shared by sdk_ecapa_forward and sdk_ecapa_forward_masked: blk0, the SE-Res2Net blocks and MFA, feats -> h [M, Cm] in w.H (K-blocked
+// where *h_kb), with the fused column statistics of h in w.stats where *fuse_ctx.  One function, so that the masked forward's h is the
+// unmasked forward's bit for bit at the same (B, T): the same launches with the same arguments.  allow_kblocked = false only changes where
+// the MFA epilogue stores a value, not the value - on the default GEMM dispatch.  ONE EXCEPTION, reachable through the A/B knob alone: with
+// "gemm_variant" 1 (SDK_GEMM_VARIANT=1: every GEMM on the 128^2 kernel) a K-blocked output still forces the 256^2 kernel (sdk_conv_gemm), so
+// where the unmasked forward writes h K-blocked (96 < T <= 208 by default) its MFA runs another kernel than the masked forward's and h agrees
+// to fp32 summation order only.  At diarization's T = 1001 neither forward writes h K-blocked, whatever the knob.
+static int ecapa_trunk(sdk_ctx* ctx, const void* wblob, const sdk_ecapa_desc* d, const uint16_t* feats, int ldf, int B, int T, const FwdWs& w,
+                       float* calib, void* stream, bool allow_kblocked, bool* fuse_ctx_out, bool* h_kb_out) {
   const char* wb = (const char*)wblob;
   auto P16 = [&](int slot) -> const uint16_t* { return d->off[slot] < 0 ? nullptr : (const uint16_t*)(wb + d->off[slot]); };
   auto P32 = [&](int slot) -> const float* { return d->off[slot] < 0 ? nullptr : (const float*)(wb + d->off[slot]); };
@@ -501,10 +485,56 @@ static int ecapa_forward_impl(sdk_ctx* ctx, const void* wblob, const sdk_ecapa_d
     if (int rc = asp_stats_impl(ctx, w.CAT, Cm, B, T, Cm, calib + calib_offset(d, B, d->n_blocks, 0), stream, f16)) return rc;
   // h [M, Cm] is the widest activation and is read twice, both times in 64- / 32-channel pieces of its 6-KB rows (the skinny attention-hidden GEMM,
   // the per-segment ASP slabs): where those two are its only readers it is written K-BLOCKED, [Cm / 64][M][64] (sdk_hip.h SDK_GEMM_C_KBLOCKED)
-  const bool h_kb = !ctx->no_h_kblocked && !calib && fuse_ctx && A == 128 && sdk_asp_kblocked_ok(ctx, T, Cm) != 0;
+  const bool h_kb = allow_kblocked && !ctx->no_h_kblocked && !calib && fuse_ctx && A == 128 && sdk_asp_kblocked_ok(ctx, T, Cm) != 0;
   if (int rc = tdnn(w.CAT, Cm, Cm, 1, 1, tb + EL_MFA, Cm, w.H, Cm, nullptr, 0, nullptr, 0, fuse_ctx ? 2 : 0, h_kb ? SDK_GEMM_C_KBLOCKED : 0)) return rc;
   if (calib)
     if (int rc = asp_stats_impl(ctx, w.H, Cm, B, T, Cm, calib + calib_offset(d, B, d->n_blocks, 1), stream, f16)) return rc;
+  *fuse_ctx_out = fuse_ctx;
+  *h_kb_out = h_kb;
+  return 0;
+}
+
+// The checks both forwards make after their null-pointer and descriptor checks, in sdk_ecapa_forward's order and words (fn: the entry point's name;
+// need: its workspace size): batch, feature width, receptive halo, workspace, alignment, weight slots.
+static int check_forward_args(const char* fn, const void* wblob, const sdk_ecapa_desc* d, int ldf, int B, int T, const void* ws, size_t ws_bytes, size_t need) {
+  SDK_REQUIRE(B > 0 && T > 0, "%s: empty batch (B=%d T=%d)", fn, B, T);
+  SDK_REQUIRE((int64_t)B * T < (1ll << 31), "%s: B*T overflows int32; split the batch", fn);
+  SDK_REQUIRE(ldf >= d->n_mels_padded && ldf % 8 == 0, "%s: ldf=%d < padded mel width %d", fn, ldf, d->n_mels_padded);
+  // The numerical contract is the DESCRIPTOR's (per call): features must be in that format (sdk_fbank_fmt with the same precision).  The context's
+  // "precision" option plays no part here since round 5 - two engines with different contracts on one device share no mutable state.
+  int maxhalo = d->kernel0 / 2;
+  for (int i = 0; i < d->n_blocks; ++i) maxhalo = d->dilation[i] > maxhalo ? d->dilation[i] : maxhalo;
+  SDK_REQUIRE(T > maxhalo, "%s: segments of %d frames are shorter than the receptive halo %d", fn, T, maxhalo);
+  SDK_REQUIRE(ws_bytes >= need, "%s: workspace too small (%zu < %zu)", fn, ws_bytes, need);
+  SDK_REQUIRE(((uintptr_t)ws % 256) == 0 && ((uintptr_t)wblob % 256) == 0, "%s: ws/wblob must be 256-byte aligned", fn);
+
+  {  // every slot the schedule dereferences must be present in the blob
+    const int tbs = EL_TAIL_BASE(d->n_blocks);
+    for (int i = 1; i <= d->n_blocks; ++i)
+      for (int s = EL_SE_W1T; s <= EL_SE_B2; ++s)
+        SDK_REQUIRE(d->off[EL_BLOCK_BASE(i) + s] >= 0, "%s: SE weight slot %d of block %d missing", fn, s, i);
+    for (int s = EL_ASP_WH; s <= EL_FC_B; ++s) SDK_REQUIRE(d->off[tbs + s] >= 0, "%s: tail weight slot %d missing", fn, s);
+  }
+  return 0;
+}
+
+static int ecapa_forward_impl(sdk_ctx* ctx, const void* wblob, const sdk_ecapa_desc* d, const uint16_t* feats, int ldf,
+                              int B, int T, void* ws, size_t ws_bytes, float* emb, float* calib, void* stream) {
+  SDK_REQUIRE(ctx && wblob && feats && ws && emb, "sdk_ecapa_forward: null argument");
+  if (int rc = check_desc(d)) return rc;
+  if (int rc = check_forward_args("sdk_ecapa_forward", wblob, d, ldf, B, T, ws, ws_bytes, sdk_ecapa_workspace_bytes(d, B, T))) return rc;
+  if (d->precision == 1) return ecapa_forward_hp(ctx, wblob, d, feats, ldf, B, T, ws, emb, stream);
+  FwdWs w;
+  fwd_layout(d, B, T, (char*)ws, &w);
+  bool fuse_ctx = false, h_kb = false;
+  if (int rc = ecapa_trunk(ctx, wblob, d, feats, ldf, B, T, w, calib, stream, true, &fuse_ctx, &h_kb)) return rc;
+  const char* wb = (const char*)wblob;
+  auto P16 = [&](int slot) -> const uint16_t* { return d->off[slot] < 0 ? nullptr : (const uint16_t*)(wb + d->off[slot]); };
+  auto P32 = [&](int slot) -> const float* { return d->off[slot] < 0 ? nullptr : (const float*)(wb + d->off[slot]); };
+  const int M = B * T, Cm = d->mfa_channels, A = d->attn_channels;
+  const bool f16 = d->precision == 2;
+  const uint32_t fmt = f16 ? SDK_GEMM_F16 : 0u;
+  const int tb = EL_TAIL_BASE(d->n_blocks);
   if (fuse_ctx) {
     if (int rc = sdk_colstats_finish(ctx, w.stats, M, Cm, T, 2, w.ctx, stream)) return rc;
   } else {
@@ -531,6 +561,77 @@ static int ecapa_forward_impl(sdk_ctx* ctx, const void* wblob, const sdk_ecapa_d
   }
   return sdk_rows_fc(ctx, w.pooled, 2 * Cm, P32(tb + EL_ASPBN_SCALE), P32(tb + EL_ASPBN_SHIFT), P32(tb + EL_FC_WT),
                      P32(tb + EL_FC_B), emb, d->embed_dim, B, 2 * Cm, d->embed_dim, 0, stream);
+}
+
+// ------------------------------------------------------------------------------ ECAPA forward with S masked poolings per chunk
+// (diarize.py: one per local speaker of a 10-s chunk; the rule is in sdk_hip.h and csrc/asp_masked.hip).  The trunk runs once per chunk
+// with h row-major; the mask enters at the pooling only: one masked statistics sweep for all B S rows, the context bias per row, then per
+// slot the attention-hidden GEMM with that slot's bias rows (ubias row b S + s: ldub = S A), the logits GEMM into ONE reused fp32 buffer and
+// the masked softmax pooling; asp_bn + fc over the B S rows; invalid rows zeroed.
+namespace {
+struct MaskedWs {
+  FwdWs f;
+  float *ctx, *ubias, *pooled;
+  int32_t* ok;                       // [B S]: valid != 0 and v1 > 0, written by the statistics sweep: the rows that are not zeros
+};
+size_t masked_layout(const sdk_ecapa_desc* d, int B, int T, int S, char* base, MaskedWs* w) {
+  size_t off = a256(fwd_layout(d, B, T, base, w ? &w->f : nullptr, true));
+  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += a256(bytes); return p; };
+  const size_t R = (size_t)B * S, Cm = d->mfa_channels, A = d->attn_channels;
+  char* cx = take(R * 2 * Cm * 4);
+  char* ub = take(R * A * 4);
+  char* po = take(R * 2 * Cm * 4);
+  char* ok = take(R * 4);
+  if (w) { w->ctx = (float*)cx; w->ubias = (float*)ub; w->pooled = (float*)po; w->ok = (int32_t*)ok; }
+  return off;
+}
+}  // namespace
+
+extern "C" size_t sdk_ecapa_masked_workspace_bytes(const sdk_ecapa_desc* d, int B, int T, int S) {
+  if (!d || B <= 0 || T <= 0 || S <= 0 || d->precision == 1) return 0;
+  return masked_layout(d, B, T, S, nullptr, nullptr);
+}
+
+extern "C" int sdk_ecapa_forward_masked(sdk_ctx* ctx, const void* wblob, const sdk_ecapa_desc* d, const uint16_t* feats, int ldf, int B, int T, int S,
+                                        const float* wgt, const int32_t* valid, void* ws, size_t ws_bytes, float* emb, void* stream) {
+  SDK_REQUIRE(ctx && wblob && feats && ws && emb, "sdk_ecapa_forward_masked: null pointer (ctx=%p wblob=%p feats=%p ws=%p emb=%p)", (void*)ctx, wblob,
+              (const void*)feats, ws, (void*)emb);
+  SDK_REQUIRE(wgt && valid, "sdk_ecapa_forward_masked: null pointer (w=%p valid=%p)", (const void*)wgt, (const void*)valid);
+  if (int rc = check_desc(d)) return rc;
+  SDK_REQUIRE(d->precision != 1, "sdk_ecapa_forward_masked: precision 1 (the precise mode's fp16 hi+lo planes) is not built for the masked pooling; use a blob of precision 0 (bf16) or 2 (fp16)");
+  SDK_REQUIRE(S >= 1 && S <= 8, "sdk_ecapa_forward_masked: S=%d weight rows per chunk (served: 1 .. 8)", S);
+  SDK_REQUIRE((int64_t)B * S < (1ll << 31), "sdk_ecapa_forward_masked: B*S overflows int32; split the batch");
+  if (int rc = check_forward_args("sdk_ecapa_forward_masked", wblob, d, ldf, B, T, ws, ws_bytes, sdk_ecapa_masked_workspace_bytes(d, B, T, S))) return rc;
+  const int tb = EL_TAIL_BASE(d->n_blocks);
+
+  MaskedWs w;
+  masked_layout(d, B, T, S, (char*)ws, &w);
+  bool fuse_ctx = false, h_kb = false;
+  if (int rc = ecapa_trunk(ctx, wblob, d, feats, ldf, B, T, w.f, nullptr, stream, false, &fuse_ctx, &h_kb)) return rc;
+  const char* wb = (const char*)wblob;
+  auto P16 = [&](int slot) -> const uint16_t* { return (const uint16_t*)(wb + d->off[slot]); };
+  auto P32 = [&](int slot) -> const float* { return (const float*)(wb + d->off[slot]); };
+  const int M = B * T, Cm = d->mfa_channels, A = d->attn_channels, R = B * S;
+  const bool f16 = d->precision == 2;
+  const uint32_t fmt = f16 ? SDK_GEMM_F16 : 0u;
+  if (int rc = asp_stats_masked_impl(ctx, w.f.H, Cm, B, T, Cm, S, wgt, valid, w.ctx, stream, f16, w.ok)) return rc;
+  if (int rc = sdk_rows_fc(ctx, w.ctx, 2 * Cm, nullptr, nullptr, P32(tb + EL_ASP_WMS_T), P32(tb + EL_ASP_B), w.ubias, A, R, 2 * Cm, A, 0, stream)) return rc;
+  for (int s = 0; s < S; ++s) {
+    sdk_conv_gemm_args g;
+    memset(&g, 0, sizeof(g));
+    g.A = w.f.H; g.lda = Cm; g.W = P16(tb + EL_ASP_WH); g.C = w.f.AH; g.ldc = A;
+    g.ubias = w.ubias + (int64_t)s * A; g.ldub = (int64_t)S * A; g.scale = P32(tb + EL_ASP_SCALE); g.shift = P32(tb + EL_ASP_SHIFT);
+    g.M = M; g.N = A; g.Cin = Cm; g.taps = 1; g.dil = 1; g.T = T; g.flags = SDK_GEMM_RELU | SDK_GEMM_TANH | fmt;
+    if (int rc = sdk_conv_gemm(ctx, &g, stream)) return rc;
+    memset(&g, 0, sizeof(g));
+    g.A = w.f.AH; g.lda = A; g.W = P16(tb + EL_ASP_W2); g.C32 = w.f.logits; g.ldc32 = Cm; g.bias = P32(tb + EL_ASP_B2);
+    g.M = M; g.N = Cm; g.Cin = A; g.taps = 1; g.dil = 1; g.T = T; g.flags = fmt;
+    if (int rc = sdk_conv_gemm(ctx, &g, stream)) return rc;
+    if (int rc = asp_pool_masked_impl(ctx, w.f.logits, Cm, w.f.H, Cm, B, T, Cm, S, s, wgt, w.ok, w.pooled, stream, f16)) return rc;
+  }
+  if (int rc = sdk_rows_fc(ctx, w.pooled, 2 * Cm, P32(tb + EL_ASPBN_SCALE), P32(tb + EL_ASPBN_SHIFT), P32(tb + EL_FC_WT), P32(tb + EL_FC_B), emb,
+                           d->embed_dim, R, 2 * Cm, d->embed_dim, 0, stream)) return rc;
+  return resnet_zero_invalid_impl(ctx, emb, R, d->embed_dim, w.ok, stream);      // (the row-zeroing kernel of the ResNet34 family's masked forward)
 }
 
 // ------------------------------------------------------------------------------ x-vector forward

@@ -109,7 +109,7 @@ _COUNT = _MASK.sum(1).astype(np.int64)
 class DiarizationResult:
     turns: List[Tuple[float, float, int]]     # (start_s, end_s, speaker), by start then speaker
     n_speakers: int
-    centroids: np.ndarray                     # [K, embed_dim] unit fp32, in the embedding space of score_windows and enrolled profiles
+    centroids: np.ndarray                     # [K, embed_dim] unit fp32, in the space of the Diarizer's embedder: that of score_windows and enrolled profiles under SDK_MODEL=resnet34, or SDK_MODEL=ecapa with SDK_DIARIZE_MODEL=ecapa (backend.py)
     labels: np.ndarray                        # [C, 3] int32: cluster of every (chunk, local speaker), -1: none
     count: np.ndarray                         # [G] uint8 speakers per global frame
     speakers: np.ndarray                      # [G, 2] int32, padded with -1
@@ -791,7 +791,10 @@ def diarize_renumber(eng, first, labels, cent, cent64, tab: GroupTables):
 
 
 class Diarizer:
-    """The pipeline on one ops.Engine: a resident segmentation.Segmentation and a resident resnet.ResNet34.  run and run_many share the option
+    """The pipeline on one ops.Engine: a resident segmentation.Segmentation and a resident embedding network - resnet.ResNet34, or
+    ecapa_diar.EcapaEmbedder for a diarization in the ECAPA space; any object with .cfg.embed_dim, .precision, .last_map_frames(T) and
+    .forward_masked(feats, B, T, w, valid) serves (the parameter and the attribute keep the name `resnet`; `embedder` is its read-only
+    alias).  run and run_many share the option
     and recording checks, the embedding of all chunks (_embed_all) and the empty result; they part after that (the module docstring)."""
 
     def __init__(self, engine, segmentation, resnet, plda=None):
@@ -799,6 +802,12 @@ class Diarizer:
         self.trace = False               # True: run_many appends one {stage: seconds} per pack to last_stage_s, every stage ended by a device synchronisation
         self.last_stage_s: List[dict] = []
         self.last_sync: List[dict] = []  # run_many: the downloads and uploads of the last call, one dict per pack
+
+    @property
+    def embedder(self):
+        """The embedding network (read-only; the attribute `resnet` under its family-neutral name).  Any object with .cfg.embed_dim,
+        .precision, .last_map_frames(T) and .forward_masked(feats, B, T, w, valid) serves: resnet.ResNet34, or ecapa_diar.EcapaEmbedder."""
+        return self.resnet
 
     def plda_model(self):
         """The plda.Plda of clustering="vbx": the one given, else a seeded synthetic model for the embedding width."""

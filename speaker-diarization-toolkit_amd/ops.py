@@ -408,6 +408,33 @@ class Engine:
                                          B, T, ws.data_ptr(), ws.numel(), emb.data_ptr(), _stream()), "sdk_ecapa_forward")
         return emb
 
+    def ecapa_forward_masked(self, feats: torch.Tensor, B: int, T: int, w: torch.Tensor, valid: torch.Tensor) -> torch.Tensor:
+        """The ECAPA-TDNN forward with S masked attentive statistics poolings per chunk (sdk_ecapa_forward_masked; the rule is in
+        include/sdk_hip.h): the trunk runs once per chunk, bit for bit ecapa_forward's; w [B, S, T] fp32 >= 0 (any weights) and valid [B, S]
+        int32, both on the device -> raw embeddings [B * S, embed_dim] fp32, row b * S + s; rows with valid == 0, or without weight, are
+        zeros.  Precision 0 and 2 (the precise mode is refused)."""
+        if self.precision == 1:
+            raise SdkError("ecapa_forward_masked: precision 1 (the precise mode) is not built for the masked pooling: use precision 0 or 2")
+        _need(feats, torch.bfloat16 if self.precision == 0 else torch.float16, "feats")
+        if feats.shape[0] != B * T or feats.stride(1) != 1:
+            raise SdkError(f"feats must be [B*T={B * T}, ldf] row-major, got {tuple(feats.shape)}")
+        if not isinstance(w, torch.Tensor) or w.dim() != 3 or w.shape[0] != B or w.shape[2] != T or w.dtype != torch.float32 or not w.is_contiguous() or not w.is_cuda:
+            raise ValueError(f"ecapa_forward_masked: w must be a contiguous fp32 device tensor [B = {B}, S, T = {T}], got "
+                             f"{tuple(w.shape) if isinstance(w, torch.Tensor) else type(w).__name__} {getattr(w, 'dtype', None)}")
+        S = int(w.shape[1])
+        if not 1 <= S <= 8:
+            raise ValueError(f"ecapa_forward_masked: S = {S} weight rows per chunk (served: 1 .. 8)")
+        if not isinstance(valid, torch.Tensor) or tuple(valid.shape) != (B, S) or valid.dtype != torch.int32 or not valid.is_contiguous() or not valid.is_cuda:
+            raise ValueError(f"ecapa_forward_masked: valid must be a contiguous int32 device tensor [{B}, {S}], got "
+                             f"{tuple(valid.shape) if isinstance(valid, torch.Tensor) else type(valid).__name__} {getattr(valid, 'dtype', None)}")
+        d = self.desc
+        ws = self._scratch_bytes("ecapa_masked", self.lib.sdk_ecapa_masked_workspace_bytes(C.byref(d), B, T, S))
+        emb = torch.empty((B * S, self.cfg.embed_dim), dtype=torch.float32, device=self.device)
+        check(self.lib.sdk_ecapa_forward_masked(self.ctx, self._wblob.data_ptr(), C.byref(d), feats.data_ptr(), feats.stride(0), B, T, S,
+                                                w.data_ptr(), valid.data_ptr(), ws.data_ptr(), ws.numel(), emb.data_ptr(), _stream()),
+              "sdk_ecapa_forward_masked")
+        return emb
+
     # ------------------------------------------------------------------ k3
     def l2norm(self, X: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """X [N, d] fp32 -> (E fp32 unit rows, Eb bf16 copy, resid [N] = ||E - Eb||)."""
