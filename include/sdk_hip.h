@@ -41,6 +41,7 @@
  *     sdk_resnet_forward_masked  sdk_diarize_frames  sdk_diarize_reconstruct  sdk_diarize_centroids  sdk_diarize_assign
  *     sdk_diarize_assign_grouped  sdk_diarize_fold_grouped  sdk_diarize_reconstruct_grouped  sdk_diarize_first_seen  sdk_diarize_renumber
  *                                                                                                       speaker diarization (diarize.py)
+ *     sdk_score_reference  sdk_score_cooccur  sdk_score_map                                             diarization error rate against a reference (score.py)
  *     sdk_plda_transform  sdk_vbx_workspace_bytes  sdk_vbx  sdk_vbx_centroids                           VBx clustering (plda.py, cluster.vbx_cluster)
  *     sdk_vbx_hmm_workspace_bytes  sdk_vbx_hmm                                                          VBx with its HMM, rows in time order (loop_prob > 0)
  *     sdk_cohort_stats_workspace_bytes  sdk_cohort_stats  sdk_affinity_topk_snorm                       adaptive score normalisation (snorm.py)
@@ -66,7 +67,7 @@
 extern "C" {
 #endif
 
-#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5); still 4 with sdk_cohort_stats* and sdk_affinity_topk_snorm, and with sdk_ecapa_forward_masked, sdk_ecapa_masked_workspace_bytes, sdk_asp_stats_masked_fmt and sdk_asp_pool_masked_fmt: new exports only, no struct or existing signature changes, no caller of version 4 breaks */
+#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5); still 4 with sdk_cohort_stats* and sdk_affinity_topk_snorm, and with sdk_ecapa_forward_masked, sdk_ecapa_masked_workspace_bytes, sdk_asp_stats_masked_fmt and sdk_asp_pool_masked_fmt, and with sdk_score_reference, sdk_score_cooccur and sdk_score_map: new exports only, no struct or existing signature changes, no caller of version 4 breaks */
 
 typedef struct sdk_ctx sdk_ctx;
 
@@ -613,6 +614,30 @@ int sdk_diarize_first_seen(sdk_ctx* ctx, const int32_t* speakers, const int32_t*
 int sdk_diarize_renumber(sdk_ctx* ctx, const int32_t* first, const int32_t* cent_off, const int32_t* chunk_off, int R, int K, int C, int d,
                          int32_t* renum, int32_t* labels, const float* cent, const double* cent64, float* cent_out, double* cent64_out,
                          void* stream);
+
+/* ---- scoring a diarization against a reference (score.py; csrc/score.hip): the diarization error rate on the packed frame grid above
+ *      (frame g of recording r, at frame_off[r] + g, has centre sample 270 g + 495).  frame_off, cent_off as above; turn_off, ref_off [R + 1]
+ *      int32 are the prefix sums of the recordings' merged reference turns and reference speakers, co_off [R + 1] int64 those of S_r K_r.
+ *      max_ref / max_hyp: the largest S_r / K_r, stated by the caller; more than 64 is refused.  Integer arithmetic only (atomic OR, atomic
+ *      integer add, stores of one value): bit-identical run to run.  Three calls, in stream order; no call reads the device on the host.
+ *   sdk_score_reference : turns [M][3] (s0, s1, speaker; samples; merged per speaker by the caller: score.prepare_reference) ->
+ *        ref_mask [G] uint64, bit i set iff a turn of speaker i has s0 <= 270 g + 495 < s1; scored [G] uint8 = 1, but 0 on the frames with
+ *        |270 g + 495 - b| < collar for a boundary b (an s0 or s1 of a turn with s1 > s0; collar in samples, 0: none), and with
+ *        skip_overlap != 0 on the frames with two or more bits.  Turns with s1 <= s0 or a speaker outside 0 .. S_r - 1 are skipped.
+ *   sdk_score_cooccur : over the frames with scored != 0, nref = bits of ref_mask, nhyp = entries >= 0 of speakers [G][2]: tally [R][5] int64 =
+ *        (frames, sum nref, sum max(0, nref - nhyp), sum max(0, nhyp - nref), sum min(nref, nhyp)) and co (int32; recording r's
+ *        [S_r][K_r] table at co_off[r], co_total cells in all) = the frames in which reference i and hypothesis j are both active (an
+ *        entry >= K_r names nobody; a speaker named twice in a frame counts once).  Both are cleared first.
+ *   sdk_score_map : one wave per recording, the exact maximum-weight assignment on its co table (zero-padded to square, shortest augmenting
+ *        paths, int64 potentials) -> correct [R] int64, the optimum, and map [ref_off[R]] int32: the hypothesis speaker of every
+ *        reference speaker in one optimal assignment, -1 where it has none or the pair never co-occurs. */
+int sdk_score_reference(sdk_ctx* ctx, const int32_t* turns, const int32_t* turn_off, const int32_t* frame_off, const int32_t* ref_off, int R,
+                        int M, int64_t G, int max_ref, int collar, int skip_overlap, uint64_t* ref_mask, uint8_t* scored, void* stream);
+int sdk_score_cooccur(sdk_ctx* ctx, const uint64_t* ref_mask, const uint8_t* scored, const int32_t* speakers, const int32_t* frame_off,
+                      const int32_t* ref_off, const int32_t* cent_off, const int64_t* co_off, int R, int64_t G, int max_ref, int max_hyp,
+                      int64_t co_total, int32_t* co, int64_t* tally, void* stream);
+int sdk_score_map(sdk_ctx* ctx, const int32_t* co, const int32_t* ref_off, const int32_t* cent_off, const int64_t* co_off, int R, int max_ref,
+                  int max_hyp, int32_t* map, int64_t* correct, void* stream);
 
 /* ---- VBx clustering of the diarization (cluster.vbx_cluster, plda.py; csrc/vbx.hip): float64 arithmetic, every sum over rows over fixed 64-row
  *      blocks whose partials are combined in block order, no floating-point atomics, one owner per output element: bit-identical run to

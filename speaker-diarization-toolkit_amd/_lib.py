@@ -165,6 +165,9 @@ SIGNATURES = {
     "sdk_diarize_reconstruct_grouped": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
     "sdk_diarize_first_seen": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _vp, _vp]),
     "sdk_diarize_renumber": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sdk_score_reference": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _i, _vp, _vp, _vp]),
+    "sdk_score_cooccur": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i64, _vp, _vp, _vp]),
+    "sdk_score_map": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "sdk_plda_transform": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "sdk_vbx_workspace_bytes": (_sz, [_i, _i, _i]),
     "sdk_vbx": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f64, _f64, _i, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -553,6 +553,45 @@ class Backend(EmbeddingBackend):
             if dz.eng.precision != prec:
                 dz.eng.set_precision(prec)                       # the front end's format goes back to the selected family's contract
 
+    def _references(self, who: str, references, uris, n: int):
+        """One turn list per recording from `references`: a list of turn lists [(start_s, end_s, name)], or an RTTM path / text / {uri: turns}
+        with the recordings' uris."""
+        from .score import references_for
+        if isinstance(references, (str, Path, dict)):
+            if uris is None or len(uris) != n:
+                raise ValueError(f"{who}: an RTTM reference needs uris, one per recording ({n}), got {None if uris is None else len(uris)}")
+            return references_for(references, list(uris))
+        references = list(references)
+        if len(references) != n:
+            raise ValueError(f"{who}: {len(references)} references for {n} recordings")
+        return references
+
+    def score_diarization(self, results, references, uris=None, collar_s: float = 0.0, skip_overlap: bool = False):
+        """How good diarize / diarize_many / a finished stream did: the diarization error rate of every result against its reference -> a list
+        of score.DerResult (scored, total, missed, false_alarm, confusion, correct, der, mapping, co); score.pool(list) is the corpus
+        figure.  references: one list of (start_s, end_s, name) per result, or the path or text of an RTTM file (or {uri: turns}) with
+        `uris` naming the results' recordings in it.  collar_s: md-eval's collar, on each side of every reference boundary; skip_overlap:
+        frames with two or more reference speakers are not scored.  Scored on the device in one pack (score.py states the rule; parity
+        with md-eval and pyannote.metrics is unpinned)."""
+        results = list(results)
+        return self.diarizer().score(results, self._references("score_diarization", references, uris, len(results)), collar_s, skip_overlap)
+
+    def tune_diarization(self, samples_or_paths, references, thresholds, uris=None, **kw):
+        """The DER of diarize_many at every threshold of `thresholds` against `references` (as score_diarization takes them) ->
+        score.SweepResult (thresholds, per_recording [T][R], pooled [T], best): the tool for choosing the clustering threshold on a
+        development set with weights of your own.  The recordings are embedded and linked once per pack; every threshold costs only the cut,
+        the grouped assignment, the stitching and the scoring kernels (diarize.Diarizer.sweep).  Keywords: step_s, min_cluster_size,
+        max_speakers, logp, constrained, collar_s, skip_overlap; clustering="ahc" without speakers= only."""
+        dz = self.diarizer()
+        recs = [decode_to_profile(Path(x), self.engine(), self.get_audio_profile()) if isinstance(x, (str, Path)) else x for x in samples_or_paths]
+        refs = self._references("tune_diarization", references, uris, len(recs))
+        prec = dz.eng.precision
+        try:
+            return dz.sweep(recs, refs, thresholds, **kw)
+        finally:
+            if dz.eng.precision != prec:
+                dz.eng.set_precision(prec)                       # the front end's format goes back to the selected family's contract
+
     def open_streams(self, n_streams: int = 1, **options):
         """Streaming diarization: a stream.StreamBank of n_streams live streams on the models diarize loads (options: step_s, latency_s,
         capacity, delta_new, max_speakers).  bank.push([samples or None per stream]) feeds 16 kHz mono int16 audio as it arrives and returns

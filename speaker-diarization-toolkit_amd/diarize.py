@@ -67,6 +67,14 @@ tests pin these rules.
               and embed_chunks, then an inventory that grows online, the constrained assignment above against its centroids and a rolling
               stitch on this frame grid that emits frames once their latency has passed.  The rule, its numpy restatement and the bank of
               live streams that steps in one launch are stream.py's; run and run_many are not changed by it.
+  score       (Diarizer.score, Backend.score_diarization) how good a result is: the diarization error rate of results against reference
+              annotations (turn lists, or RTTM), on this frame grid.  The results' speakers tables are scored on the device as one pack -
+              reference masks, co-occurrence tallies and the exact reference-to-hypothesis assignment in three integer kernels
+              (csrc/score.hip).  The rule, its numpy restatement (score_host) and the RTTM reader are score.py's.
+  sweep       (Diarizer.sweep, Backend.tune_diarization) the DER of run_many at many thresholds, for tuning the cut on a development set:
+              per pack one embedding and one linkage (_pack_link), then per threshold the cut-to-centroids stage (_pack_cut), the grouped
+              assignment and stitching, and the scoring kernels on the hypothesis where it lies; every threshold's tallies come down in one
+              download per pack.  clustering="ahc" without speaker bounds only; run_many is not changed by it.
   shared      run and run_many are one pipeline: Diarizer._check_options, _check_recording, _embed_all (the batches of embed_chunks) and
               _empty serve both, as do candidate_mask, training_mask and _speaker_cap; after the embedding run clusters one recording and
               run_many takes the pack through _pack_rows, _pack_vbx or _pack_ahc, _pack_assign and _pack_results.  They differ on purpose in
@@ -978,6 +986,17 @@ class Diarizer:
         recording whose count is overruled adds cluster.KMEANS_HOST_READS waits."""
         from .cluster import vbx_cluster  # noqa: F401  (checked early: the package imports)
         vbx, bounds = self._check_options("diarize_many", clustering, vbx, max_speakers, speakers)
+        xs, packs = self._plan_packs(recordings, logp, step_s)
+        out: List[Optional[DiarizationResult]] = [None] * len(xs)
+        self.last_sync = []
+        for idx in packs:
+            for i, res in zip(idx, self._run_pack([xs[i] for i in idx], None if logp is None else [logp[i] for i in idx], step_s, threshold,
+                                                  min_cluster_size, max_speakers, constrained, clustering, vbx, bounds)):
+                out[i] = res
+        return out
+
+    def _plan_packs(self, recordings, logp, step_s):
+        """run_many's and sweep's checks of the recordings and their split into packs -> (xs as int16 rows, [[recording index]] per pack)."""
         xs = [np.ascontiguousarray(x, dtype=np.int16).reshape(-1) for x in recordings]
         if logp is not None and (not isinstance(logp, (list, tuple)) or len(logp) != len(xs)):
             raise ValueError(f"diarize_many: logp must be None or a list with one array per recording ({len(xs)}), got "
@@ -1000,15 +1019,101 @@ class Diarizer:
             ns, nb = ns + s_i, nb + b_i
         if cur:
             packs.append(cur)
-        out: List[Optional[DiarizationResult]] = [None] * len(xs)
+        return xs, packs
+
+    # ---------------------------------------------------------------------------------------------- scoring against a reference, threshold sweep
+    def score(self, results, references, collar_s: float = 0.0, skip_overlap: bool = False):
+        """DiarizationResults (run's, run_many's or a finished stream's) and one reference turn list [(start_s, end_s, name)] per result ->
+        one score.DerResult per result: their `speakers` are uploaded and scored on the device as one pack (score.py states the rule)."""
+        from .score import MAX_SCORE_SPEAKERS, score_grouped
+        results, references = list(results), list(references)
+        if len(references) != len(results):
+            raise ValueError(f"score: {len(references)} references for {len(results)} recordings")
+        if not results:
+            return []
+        spk = [np.ascontiguousarray(res.speakers, dtype=np.int32).reshape(-1, 2) for res in results]
+        for r, (res, sp) in enumerate(zip(results, spk)):
+            if sp.size and int(sp.max()) >= int(res.n_speakers):
+                raise ValueError(f"score: recording {r}: speakers names {int(sp.max())}, the result has {res.n_speakers} speakers")
+            if int(res.n_speakers) > MAX_SCORE_SPEAKERS:
+                raise ValueError(f"score: recording {r}: {res.n_speakers} hypothesis speakers; at most {MAX_SCORE_SPEAKERS} per recording")
+        torch = _native()[0]
+        G_r = [len(sp) for sp in spk]
+        n_samples = [FRAME_HOP * g + 226 if g else 0 for g in G_r]                      # a length with global_frames(n) == g: only the grid is read
+        tab = GroupTables(self.eng, np.zeros(len(results) + 1, np.int64), np.concatenate([[0], np.cumsum(G_r)]), n_samples)
+        tab.set_clusters(np.concatenate([[0], np.cumsum([int(res.n_speakers) for res in results])]))
+        spk_dev = torch.from_numpy(np.concatenate(spk)).to(self.eng.device)
+        return score_grouped(self.eng, spk_dev, tab, references, collar_s, skip_overlap)
+
+    def sweep(self, recordings, references, thresholds, step_s: float = 1.0, min_cluster_size: int = PYANNOTE_MIN_CLUSTER_SIZE,
+              max_speakers: Optional[int] = None, logp=None, constrained: bool = False, collar_s: float = 0.0, skip_overlap: bool = False,
+              clustering: str = "ahc", speakers=None):
+        """The DER of run_many(recordings, threshold=t, ...) against `references` for every t of `thresholds` -> score.SweepResult
+        (thresholds, per_recording [T][R], pooled [T], best).  Per pack the recordings are embedded ONCE and linked ONCE (_pack_embed,
+        _pack_link); per threshold only the cheap tail runs - cut on host integers, fold, centroids, assignment, stitching, renumbering and
+        second stitching exactly as run_many's (_pack_cut, _pack_assign_dev), then the three scoring kernels on the hypothesis where it
+        lies.  The tallies of all thresholds stay on the device and come down in one download per pack: the waits per pack (last_sync) do
+        not grow with the number of thresholds.  Only clustering="ahc" without speaker bounds: the sweep is over the cut of the linkage.
+        A recording that the cut splits into more than score.MAX_SCORE_SPEAKERS speakers at some threshold is a ValueError."""
+        from .score import SweepResult, best_threshold, pool, rasterise_references, results_from_tables, score_host, score_tables, split_tables
+        if clustering != "ahc" or speakers is not None:
+            raise ValueError(f"sweep: clustering={clustering!r}, speakers={speakers!r}: the sweep is over the cut of clustering=\"ahc\" with speakers=None")
+        self._check_options("sweep", clustering, None, max_speakers, None)
+        ths = [float(t) for t in thresholds]
+        if not ths or any(t != t for t in ths):
+            raise ValueError(f"sweep: thresholds={list(thresholds)!r} (at least one number)")
+        references = list(references)
+        if len(references) != len(recordings):
+            raise ValueError(f"sweep: {len(references)} references for {len(recordings)} recordings")
+        xs, packs = self._plan_packs(recordings, logp, step_s)
+        per = [[None] * len(xs) for _ in ths]
         self.last_sync = []
         for idx in packs:
-            for i, res in zip(idx, self._run_pack([xs[i] for i in idx], None if logp is None else [logp[i] for i in idx], step_s, threshold,
-                                                  min_cluster_size, max_speakers, constrained, clustering, vbx, bounds)):
-                out[i] = res
-        return out
+            sync = {"downloads": 0, "uploads": 0}
+            self.last_sync.append(sync)
+            if self.trace:
+                self.last_stage_s.append({})
+            self._t_mark = time.perf_counter()
+            pxs, refs = [xs[i] for i in idx], [references[i] for i in idx]
+            pack = pack_recordings(pxs, step_s)
+            if int(pack.chunk_off[-1]) == 0:                      # nothing but empty recordings: no frame to score
+                for t in range(len(ths)):
+                    for i, ref in zip(idx, refs):
+                        per[t][i] = score_host(np.zeros((0, 2), np.int32), 0, ref, collar_s, skip_overlap)
+                continue
+            torch = _native()[0]
+            tab, cls, info_dev, E_dev = self._pack_embed(pack, pxs, None if logp is None else [logp[i] for i in idx])
+            info = self._down(info_dev)
+            self._mark("segmentation_embedding")
+            rows, n_train = self._pack_rows(info, pack.chunk_off)
+            linkage = self._pack_link(E_dev, rows, n_train)
+            ref = rasterise_references(self.eng, tab, refs, collar_s, skip_overlap, upload=self._up)
+            self._mark("reference")
+            held, shapes = [], []
+            for t in ths:
+                c32, c64, cent_off, _, _ = self._pack_cut(E_dev, rows, n_train, linkage, t, min_cluster_size, None)
+                tab.set_clusters(cent_off)
+                self._mark("cut_fold_centroids")
+                spk_dev = self._pack_assign_dev(tab, cls, info_dev, E_dev, c32, c64, constrained, max_speakers)[4]
+                self._mark("assign_stitch")
+                tally, correct, mapping, co, co_off = score_tables(self.eng, spk_dev, tab, ref, upload=self._up)
+                held += [tally.reshape(-1), correct, mapping.to(torch.int64), co.to(torch.int64)]
+                shapes.append((cent_off, co_off))
+                self._mark("score")
+            sync["uploads"] += tab.uploads
+            flat = self._down(torch.cat(held))                    # every threshold's tallies, tables and maps: ONE download
+            pos = 0
+            for t, (cent_off, co_off) in enumerate(shapes):
+                n = 6 * tab.R + int(ref.ref_off[-1]) + int(co_off[-1])
+                res = results_from_tables(ref, cent_off, co_off, *split_tables(flat[pos:pos + n], tab.R, int(ref.ref_off[-1]), int(co_off[-1])))
+                pos += n
+                for i, one in zip(idx, res):
+                    per[t][i] = one
+            self._mark("download")
+        pooled = [pool(row) for row in per]
+        return SweepResult(ths, per, pooled, best_threshold(ths, pooled))
 
-    def _up(self, a, dtype=None):                               # host -> device, counted for the current pack (dtype: torch.as_tensor converts on the way)
+    def _up(self, a, dtype=None):                              # host -> device, counted for the current pack (dtype: torch.as_tensor converts on the way)
         torch = _native()[0]
         self.last_sync[-1]["uploads"] += 1
         return (torch.from_numpy(np.ascontiguousarray(a)) if dtype is None else torch.as_tensor(a, dtype=dtype)).to(self.eng.device)
@@ -1101,19 +1206,33 @@ class Diarizer:
         return c32, c64, np.concatenate([[0], np.cumsum(K_r)]).astype(np.int64), vres, forced
 
     def _pack_ahc(self, E_dev, rows, n_train, threshold, min_cluster_size, bounds=None):
-        """ONE grouped linkage over the recordings with at least two training rows, the cut per recording on the host (with bounds: the
-        level search of cluster.agglomerative_cluster rule 7 in its place, host integers on the same Z), the cut's centroids, the grouped
-        fold and the final centroids -> (c32, c64, cent_off, {}, {recording: forced}), as _pack_vbx."""
+        """The linkage stage (_pack_link), then the cut-to-centroids stage (_pack_cut) -> (c32, c64, cent_off, {}, {recording: forced}), as
+        _pack_vbx."""
+        return self._pack_cut(E_dev, rows, n_train, self._pack_link(E_dev, rows, n_train), threshold, min_cluster_size, bounds)
+
+    def _pack_link(self, E_dev, rows, n_train):
+        """ONE grouped linkage over the recordings with at least two training rows -> (those recordings, the prefix sums of their training
+        rows, Z on the host); (no recording, None, None) when there is nothing to link.  It does not depend on the threshold: sweep runs it
+        once per pack."""
+        link = [r for r in range(len(rows)) if n_train[r] > 1]
+        if not link:
+            return link, None, None
+        off = np.concatenate([[0], np.cumsum([n_train[r] for r in link])]).astype(np.int64)
+        E_link = E_dev.index_select(0, self._up(np.concatenate([rows[r] for r in link]))).contiguous()
+        Z = self._down(self.eng.centroid_linkage(E_link, off))                     # ONE launch for all recordings; reads status, then Z
+        self.last_sync[-1]["downloads"] += LINKAGE_HOST_READS
+        self._mark("linkage")
+        return link, off, Z
+
+    def _pack_cut(self, E_dev, rows, n_train, linkage, threshold, min_cluster_size, bounds=None):
+        """The cut per recording on the host (with bounds: the level search of cluster.agglomerative_cluster rule 7 in its place, host
+        integers on the same Z), the cut's centroids, the grouped fold and the final centroids -> (c32, c64, cent_off, {},
+        {recording: forced}).  linkage: _pack_link's result."""
         from .cluster import _flat_partition, cut_level, effective_min_size, fcluster_distance, level_search, speaker_target
         eng, R = self.eng, len(rows)
-        link = [r for r in range(R) if n_train[r] > 1]
+        link, off, Z = linkage
         cuts, forced = {}, {}
         if link:
-            off = np.concatenate([[0], np.cumsum([n_train[r] for r in link])]).astype(np.int64)
-            E_link = E_dev.index_select(0, self._up(np.concatenate([rows[r] for r in link]))).contiguous()
-            Z = self._down(eng.centroid_linkage(E_link, off))                      # ONE launch for all recordings; reads status, then Z
-            self.last_sync[-1]["downloads"] += LINKAGE_HOST_READS
-            self._mark("linkage")
             for g, r in enumerate(link):
                 Zr = Z[int(off[g]) - g:int(off[g + 1]) - g - 1]
                 cuts[r] = fcluster_distance(Zr, threshold)
@@ -1147,6 +1266,10 @@ class Diarizer:
 
     def _pack_assign(self, tab, cls, info_dev, E_dev, c32, c64, constrained, max_speakers):
         """Grouped assignment, stitching, renumbering by appearance and second stitching -> (labels, scores, cent, count, speakers) on the host."""
+        return tuple(self._down(t) for t in self._pack_assign_dev(tab, cls, info_dev, E_dev, c32, c64, constrained, max_speakers))
+
+    def _pack_assign_dev(self, tab, cls, info_dev, E_dev, c32, c64, constrained, max_speakers):
+        """_pack_assign without its downloads: (labels, scores, cent, count, speakers) on the device."""
         torch, eng = _native()[0], self.eng
         if c64 is None:                                          # no cluster anywhere: the kernels still get a row to point at
             d = self.resnet.cfg.embed_dim
@@ -1156,7 +1279,7 @@ class Diarizer:
         first = diarize_first_seen(eng, spk_dev, tab)
         _, c32, c64 = diarize_renumber(eng, first, lab_dev, c32, c64, tab)         # ties in the top-2 go to the lower number: stitch again
         cnt_dev, spk_dev, _ = diarize_reconstruct_grouped(eng, cls, lab_dev, tab, max_speakers)
-        return tuple(self._down(t) for t in (lab_dev, score_dev, c32, cnt_dev, spk_dev))
+        return lab_dev, score_dev, c32, cnt_dev, spk_dev
 
     def _pack_results(self, xs, pack: Pack, cent_off, info, cls, vres, forced, labels, scores, cent, count, speakers):
         """The pack's host arrays cut into one DiarizationResult per recording."""

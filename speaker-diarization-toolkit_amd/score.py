@@ -1,0 +1,370 @@
+"""Scoring a diarization against a reference annotation: the diarization error rate (DER), computed on the device for a pack of recordings,
+and the threshold sweep built on it (diarize.Diarizer.score / sweep, Backend.score_diarization / tune_diarization).  The rule below is THIS
+build's statement, following NIST md-eval and pyannote.metrics as published; none of their code is on hand, so PARITY IS UNPINNED and the
+tests pin this rule.
+
+  grid        the global frame grid of diarize.py: frame g of a recording has centre sample 270 g + 495, g < global_frames(n_samples).  The
+              hypothesis on it is a result's speakers [G, 2] (int32, padded with -1): hypothesis speaker j is active in frame g iff j stands
+              in speakers[g]; nhyp(g) = the number of entries >= 0
+  reference   per recording a list of (start_s, end_s, name), prepared on the host (prepare_reference): seconds to samples by
+              floor(t * 16000 + 0.5) (times must be finite, >= 0 and below 2^31 samples); names numbered 0 .. S - 1 in order of their first
+              start (in samples), then by name; per speaker the union of the turns that overlap or abut (sorted by (s0, s1), a turn joins
+              the running one when s0 <= its s1), then turns with s1 <= s0 are dropped (a speaker whose turns are all dropped keeps its
+              number and is never active).  Reference speaker i is active in frame g iff one of its turns has s0 <= 270 g + 495 < s1;
+              nref(g) = the number of active reference speakers
+  scored      every frame of the recording, with two exceptions.  collar_s > 0: with c = floor(collar_s * 16000 + 0.5), a frame is not scored
+              if some boundary b (an s0 or s1 of a merged reference turn) has |270 g + 495 - b| < c - md-eval's convention, the collar
+              applies on each side of the boundary.  skip_overlap=True: a frame with nref >= 2 is not scored.  No UEM files.
+  tallies     over the scored frames, all integers: scored (frames), total = sum nref, missed = sum max(0, nref - nhyp), false_alarm =
+              sum max(0, nhyp - nref), both = sum min(nref, nhyp), co[i, j] = the frames in which reference i and hypothesis j are both
+              active
+  mapping     correct = the maximum of sum co[i, m(i)] over maps m that give some reference speakers pairwise different hypothesis speakers
+              (an exact maximum-weight assignment); the mapping reported is any map that attains it, pairs with co == 0 reported as
+              unmapped (-1); confusion = both - correct.  correct is unique even where the map is not, so every tally is unique
+  DER         der = (missed + false_alarm + confusion) / total; with total == 0 it is 0.0 when there is no error, else inf.  Pooled over
+              recordings (pool): the ratio of the sums.  Durations are frames * 270 / 16000 s
+  limits      at most MAX_SCORE_SPEAKERS = 64 reference and 64 hypothesis speakers per recording: more is a ValueError here and refused by
+              the library
+
+The device path is three calls in stream order on the prefix-sum tables of diarize.GroupTables (csrc/score.hip): sdk_score_reference
+(reference turns -> a 64-bit speaker mask and a scored flag per frame), sdk_score_cooccur (masks and speakers -> co and the tallies, summed per
+workgroup in LDS, then integer atomics) and sdk_score_map (one wave per recording: shortest augmenting paths with int64 potentials).  Only
+integers, OR and integer adds: the results do not depend on any order and are bit-identical run to run.  The *_host functions restate the three
+kernels in numpy; score_host joins them for one recording.
+"""
+from __future__ import annotations
+
+import math
+import os
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from .diarize import global_frames
+from .segmentation import FRAME_HOP, SAMPLE_RATE
+
+MAX_SCORE_SPEAKERS = 64
+FRAME_FIRST = 495                # centre sample of frame 0
+_INF = 1 << 62
+
+
+@dataclass
+class DerResult:
+    scored: int                               # frames scored
+    total: int                                # reference speaker-frames
+    missed: int
+    false_alarm: int
+    confusion: int
+    correct: int
+    der: float
+    mapping: Dict[object, int]                # reference name -> hypothesis speaker, -1: unmapped ({} for a pooled result)
+    co: Optional[np.ndarray]                  # [S, K] int32 co-occurrence (None for a pooled result)
+
+    @property
+    def scored_s(self) -> float:
+        return self.scored * FRAME_HOP / SAMPLE_RATE
+
+    @property
+    def total_s(self) -> float:
+        return self.total * FRAME_HOP / SAMPLE_RATE
+
+
+@dataclass
+class SweepResult:
+    thresholds: List[float]
+    per_recording: List[List[DerResult]]      # [T][R]
+    pooled: List[DerResult]                   # [T]
+    best: int                                 # index of the least pooled DER; ties to the threshold nearest PYANNOTE_THRESHOLD, then the lower
+
+
+def der_value(total: int, missed: int, false_alarm: int, confusion: int) -> float:
+    err = int(missed) + int(false_alarm) + int(confusion)
+    if total == 0:
+        return 0.0 if err == 0 else math.inf
+    return err / int(total)
+
+
+def pool(results: Sequence[DerResult]) -> DerResult:
+    """The summed tallies of many recordings and the ratio of the sums; mapping {} and co None (not comparable across recordings)."""
+    s = [sum(int(getattr(r, f)) for r in results) for f in ("scored", "total", "missed", "false_alarm", "confusion", "correct")]
+    return DerResult(*s, der_value(s[1], s[2], s[3], s[4]), {}, None)
+
+
+def best_threshold(thresholds: Sequence[float], pooled: Sequence[DerResult]) -> int:
+    from .cluster import PYANNOTE_THRESHOLD
+    return min(range(len(thresholds)), key=lambda t: (pooled[t].der, abs(float(thresholds[t]) - PYANNOTE_THRESHOLD), float(thresholds[t])))
+
+
+# ------------------------------------------------------------------------------------------------ RTTM and the reference on the host
+def parse_rttm(text: str) -> Dict[str, List[Tuple[float, float, str]]]:
+    """RTTM text -> {uri: [(start_s, end_s, name)]} in file order.  Reads the SPEAKER lines (`SPEAKER <uri> <chan> <start> <dur> <NA> <NA>
+    <name> ...`, what diarize.to_rttm writes) and ignores every other line."""
+    out: Dict[str, List[Tuple[float, float, str]]] = {}
+    for n, line in enumerate(text.splitlines(), 1):
+        f = line.split()
+        if not f or f[0] != "SPEAKER":
+            continue
+        if len(f) < 8:
+            raise ValueError(f"parse_rttm: line {n}: a SPEAKER line has at least 8 fields, got {len(f)}")
+        try:
+            start, dur = float(f[3]), float(f[4])
+        except ValueError:
+            raise ValueError(f"parse_rttm: line {n}: start {f[3]!r} and duration {f[4]!r} must be numbers") from None
+        out.setdefault(f[1], []).append((start, start + dur, f[7]))
+    return out
+
+
+def references_for(rttm, uris: Sequence[str]) -> List[List[Tuple[float, float, str]]]:
+    """An RTTM path or text (or a {uri: turns} dict) and the recordings' uris, in order -> one turn list per recording.  A uri the
+    annotation does not hold is a ValueError (an annotation without speech is an empty list in a dict)."""
+    if isinstance(rttm, dict):
+        table = rttm
+    else:
+        text = os.fspath(rttm)
+        if "\n" not in text and os.path.exists(text):
+            with open(text, "r", encoding="utf-8") as fh:
+                text = fh.read()
+        table = parse_rttm(text)
+    missing = [u for u in uris if u not in table]
+    if missing:
+        raise ValueError(f"score: the reference holds no uri {missing[:4]} (it has {sorted(table)[:8]})")
+    return [list(table[u]) for u in uris]
+
+
+def to_samples(t: float) -> int:
+    if not (t == t and 0.0 <= t and t * SAMPLE_RATE + 0.5 < float(1 << 31)):
+        raise ValueError(f"score: time {t} s (finite, >= 0 and below 2^31 samples)")
+    return int(math.floor(float(t) * SAMPLE_RATE + 0.5))
+
+
+def collar_samples(collar_s: float) -> int:
+    if not (collar_s == collar_s and 0.0 <= collar_s and collar_s * SAMPLE_RATE + 0.5 < float(1 << 30)):
+        raise ValueError(f"score: collar_s={collar_s} (seconds, >= 0)")
+    return int(math.floor(float(collar_s) * SAMPLE_RATE + 0.5))
+
+
+def prepare_reference(turns) -> Tuple[np.ndarray, list]:
+    """[(start_s, end_s, name)] -> (merged [M, 3] int32 rows (s0, s1, speaker) by speaker then s0, names [S]): "reference" in the module
+    docstring."""
+    conv = [(to_samples(a), to_samples(b), name) for a, b, name in turns]
+    first: dict = {}
+    for s0, _, name in conv:
+        first[name] = min(first.get(name, s0), s0)
+    names = sorted(first, key=lambda nm: (first[nm], nm))
+    rows = []
+    for i, name in enumerate(names):
+        cur = None
+        for s0, s1 in sorted((s0, s1) for s0, s1, nm in conv if nm == name):
+            if cur is not None and s0 <= cur[1]:
+                cur[1] = max(cur[1], s1)
+            else:
+                cur = [s0, s1, i]
+                rows.append(cur)
+    merged = np.asarray([row for row in rows if row[1] > row[0]], dtype=np.int32).reshape(-1, 3)
+    return merged, names
+
+
+def _first_frame(s):
+    """The least g >= 0 with 270 g + 495 >= s."""
+    a = np.asarray(s, dtype=np.int64) - FRAME_FIRST
+    return np.where(a <= 0, 0, (a + FRAME_HOP - 1) // FRAME_HOP)
+
+
+def reference_masks_host(merged: np.ndarray, G: int, collar: int = 0, skip_overlap: bool = False):
+    """sdk_score_reference for one recording in numpy: merged [M, 3], G frames, collar in samples -> (ref_mask [G] uint64, scored [G] uint8)."""
+    mask, scored = np.zeros(G, np.uint64), np.ones(G, np.uint8)
+    m = np.asarray(merged, dtype=np.int64).reshape(-1, 3)
+    for s0, s1, i in m:
+        if s1 <= s0 or not 0 <= i < MAX_SCORE_SPEAKERS:
+            continue
+        mask[int(_first_frame(s0)):min(int(_first_frame(s1)), G)] |= np.uint64(1) << np.uint64(i)
+    if skip_overlap:
+        scored[_popcount(mask) >= 2] = 0
+    if collar > 0:
+        for s0, s1, _ in m:
+            if s1 > s0:
+                for b in (s0, s1):
+                    scored[int(_first_frame(b - collar + 1)):min(int(_first_frame(b + collar)), G)] = 0
+    return mask, scored
+
+
+def _popcount(mask: np.ndarray) -> np.ndarray:
+    return np.unpackbits(np.ascontiguousarray(mask, dtype="<u8").view(np.uint8).reshape(-1, 8), axis=1).sum(1).astype(np.int64)
+
+
+def cooccur_host(ref_mask: np.ndarray, scored: np.ndarray, speakers: np.ndarray, S: int, K: int):
+    """sdk_score_cooccur for one recording in numpy -> (co [S, K] int32, tally [5] int64: scored, total, missed, false_alarm, both)."""
+    on = np.asarray(scored).astype(bool)
+    mask, sp = np.asarray(ref_mask, dtype=np.uint64)[on], np.asarray(speakers, dtype=np.int64).reshape(-1, 2)[on]
+    nref, nhyp = _popcount(mask), (sp >= 0).sum(1)
+    tally = np.array([on.sum(), nref.sum(), np.maximum(nref - nhyp, 0).sum(), np.maximum(nhyp - nref, 0).sum(), np.minimum(nref, nhyp).sum()], np.int64)
+    ref = ((mask[:, None] >> np.arange(S, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.float64)        # [frames, S]
+    hyp = (sp[:, :, None] == np.arange(K)[None, None, :]).any(1).astype(np.float64)                            # [frames, K]: named twice counts once
+    return np.rint(ref.T @ hyp).astype(np.int32).reshape(S, K), tally                                           # counts below 2^30: exact in float64
+
+
+def assignment_host(co: np.ndarray):
+    """sdk_score_map for one recording in numpy: co [S, K] -> (map [S] int32, correct): the exact maximum-weight assignment on the table
+    padded with zeros to square, by shortest augmenting paths on cost = -co with integer potentials (ties to the lower column, as the kernel's
+    cross-lane minimum); a pair with co == 0 is reported unmapped."""
+    co = np.asarray(co, dtype=np.int64)
+    S, K = co.shape
+    n = max(S, K)
+    w = np.zeros((n, n), np.int64)
+    w[:S, :K] = co
+    u, v, p = np.zeros(n, np.int64), np.zeros(n, np.int64), np.full(n, -1, np.int64)
+    for i in range(n):
+        minv, way, used = np.full(n, _INF, np.int64), np.full(n, -1, np.int64), np.zeros(n, bool)
+        j0, i0 = -1, i
+        while True:
+            cur = -w[i0] - u[i0] - v
+            upd = ~used & (cur < minv)
+            minv[upd], way[upd] = cur[upd], j0
+            cand = np.where(used, _INF, minv)
+            j1 = int(np.argmin(cand))
+            delta = cand[j1]
+            u[p[used]] += delta
+            v[used] -= delta
+            minv[~used] -= delta
+            u[i] += delta
+            j0 = j1
+            used[j0] = True
+            i0 = int(p[j0])
+            if i0 < 0:
+                break
+        while j0 >= 0:
+            j1 = int(way[j0])
+            p[j0] = p[j1] if j1 >= 0 else i
+            j0 = j1
+    out, correct = np.full(S, -1, np.int32), 0
+    for j in range(K):
+        if 0 <= p[j] < S and co[p[j], j] > 0:
+            out[p[j]] = j
+            correct += int(co[p[j], j])
+    return out, correct
+
+
+def _result(names, co, tally, mapping, correct) -> DerResult:
+    scored, total, missed, fa, both = (int(x) for x in tally)
+    conf = both - int(correct)
+    return DerResult(scored, total, missed, fa, conf, int(correct), der_value(total, missed, fa, conf),
+                     {name: int(mapping[i]) for i, name in enumerate(names)}, np.asarray(co, dtype=np.int32))
+
+
+def _check_counts(who: str, S: int, K: int):
+    if S > MAX_SCORE_SPEAKERS or K > MAX_SCORE_SPEAKERS:
+        raise ValueError(f"{who}: {S} reference and {K} hypothesis speakers; at most {MAX_SCORE_SPEAKERS} of each per recording")
+
+
+def score_host(speakers, n_samples: int, reference, collar_s: float = 0.0, skip_overlap: bool = False) -> DerResult:
+    """One recording on the host: speakers [G, 2] int32 (a DiarizationResult's), its n_samples and the reference turns -> DerResult.  The
+    numpy restatement of the three kernels; K is the largest speaker named, plus one."""
+    sp = np.asarray(speakers, dtype=np.int32).reshape(-1, 2)
+    G = global_frames(n_samples)
+    if sp.shape[0] != G:
+        raise ValueError(f"score_host: speakers holds {sp.shape[0]} frames, {n_samples} samples give {G}")
+    merged, names = prepare_reference(reference)
+    S, K = len(names), (int(sp.max()) + 1 if sp.size else 0)
+    _check_counts("score_host", S, max(K, 0))
+    mask, scored = reference_masks_host(merged, G, collar_samples(collar_s), bool(skip_overlap))
+    co, tally = cooccur_host(mask, scored, sp, S, max(K, 0))
+    mapping, correct = assignment_host(co)
+    return _result(names, co, tally, mapping, correct)
+
+
+# ------------------------------------------------------------------------------------------------ the device path
+class PackReference:
+    """The references of a pack, prepared (host) and rasterised on the packed frame grid (device): rasterise_references."""
+    names: list                  # per recording, the reference names in speaker order
+    ref_off: np.ndarray          # [R + 1] int64 prefix sums of the S_r
+    max_ref: int
+    ref_off_d = None             # [R + 1] int32
+    ref_mask = None              # [G] int64 holding the uint64 masks
+    scored = None                # [G] uint8
+
+
+def rasterise_references(eng, tab, references, collar_s: float = 0.0, skip_overlap: bool = False, upload=None) -> PackReference:
+    """One turn list per recording of the pack (tab: diarize.GroupTables) -> PackReference: sdk_score_reference.  upload: what carries the
+    one table of host integers to the device (a caller that counts its transfers passes its own)."""
+    from .diarize import _native
+    torch, check, _stream = _native()
+    if len(references) != tab.R:
+        raise ValueError(f"score: {len(references)} references for {tab.R} recordings")
+    collar = collar_samples(collar_s)
+    prepared = [prepare_reference(t) for t in references]
+    ref = PackReference()
+    ref.names = [names for _, names in prepared]
+    for r, names in enumerate(ref.names):
+        _check_counts(f"score: recording {r}", len(names), 0)
+    ref.ref_off = np.concatenate([[0], np.cumsum([len(n) for n in ref.names])]).astype(np.int64)
+    ref.max_ref = max([len(n) for n in ref.names] + [0])
+    turn_off = np.concatenate([[0], np.cumsum([len(m) for m, _ in prepared])]).astype(np.int64)
+    M, R = int(turn_off[-1]), tab.R
+    if M >= (1 << 28):
+        raise ValueError(f"score: {M} reference turns in one pack (fewer than 2^28)")
+    table = np.concatenate([turn_off, ref.ref_off] + [m.reshape(-1) for m, _ in prepared]).astype(np.int32)
+    up = (upload or (lambda a: torch.from_numpy(a).to(eng.device)))(table)                                   # one upload
+    turn_off_d, ref.ref_off_d, turns_d = up[:R + 1], up[R + 1:2 * R + 2], up[2 * R + 2:]
+    ref.ref_mask = torch.empty((max(tab.G, 1),), dtype=torch.int64, device=eng.device)
+    ref.scored = torch.empty((max(tab.G, 1),), dtype=torch.uint8, device=eng.device)
+    check(eng.lib.sdk_score_reference(eng.ctx, turns_d.data_ptr() if M else None, turn_off_d.data_ptr(), tab.frame_off_d.data_ptr(), ref.ref_off_d.data_ptr(),
+                                      R, M, tab.G, ref.max_ref, collar, int(bool(skip_overlap)), ref.ref_mask.data_ptr(), ref.scored.data_ptr(), _stream()),
+          "sdk_score_reference")
+    ref.ref_mask, ref.scored = ref.ref_mask[:tab.G], ref.scored[:tab.G]
+    return ref
+
+
+def score_tables(eng, speakers_dev, tab, ref: PackReference, upload=None):
+    """speakers [G, 2] int32 on the packed grid (device), tab with clusters set (K_r = the hypothesis speakers of recording r) ->
+    (tally [R, 5] int64, correct [R] int64, map [sum S_r] int32, co int32 [co_off[-1]], co_off [R + 1] int64 on the host), the first four
+    on the device: sdk_score_cooccur, then sdk_score_map.  Nothing is read back."""
+    from .diarize import _native
+    torch, check, _stream = _native()
+    if tab.cent_off is None:
+        raise ValueError("score: the tables hold no clusters (set_clusters)")
+    if str(speakers_dev.dtype) != "torch.int32" or tuple(speakers_dev.shape) != (tab.G, 2) or not speakers_dev.is_contiguous():
+        raise ValueError(f"score: speakers must be a contiguous int32 [{tab.G}, 2] tensor, got {tuple(speakers_dev.shape)} {speakers_dev.dtype}")
+    S_r, K_r = np.diff(ref.ref_off), np.diff(tab.cent_off)
+    for r in range(tab.R):
+        _check_counts(f"score: recording {r}", int(S_r[r]), int(K_r[r]))
+    co_off = np.concatenate([[0], np.cumsum(S_r * K_r)]).astype(np.int64)
+    R, total, max_hyp = tab.R, int(co_off[-1]), int(K_r.max()) if K_r.size else 0
+    co_off_d = (upload or (lambda a: torch.from_numpy(a).to(eng.device)))(co_off)
+    co = torch.empty((max(total, 1),), dtype=torch.int32, device=eng.device)
+    tally = torch.empty((R, 5), dtype=torch.int64, device=eng.device)
+    mapping = torch.empty((max(int(ref.ref_off[-1]), 1),), dtype=torch.int32, device=eng.device)
+    correct = torch.empty((R,), dtype=torch.int64, device=eng.device)
+    check(eng.lib.sdk_score_cooccur(eng.ctx, ref.ref_mask.data_ptr() if tab.G else None, ref.scored.data_ptr() if tab.G else None,
+                                    speakers_dev.data_ptr() if tab.G else None, tab.frame_off_d.data_ptr(), ref.ref_off_d.data_ptr(), tab.cent_off_d.data_ptr(),
+                                    co_off_d.data_ptr(), R, tab.G, ref.max_ref, max_hyp, total, co.data_ptr(), tally.data_ptr(), _stream()), "sdk_score_cooccur")
+    check(eng.lib.sdk_score_map(eng.ctx, co.data_ptr(), ref.ref_off_d.data_ptr(), tab.cent_off_d.data_ptr(), co_off_d.data_ptr(), R, ref.max_ref, max_hyp,
+                                mapping.data_ptr(), correct.data_ptr(), _stream()), "sdk_score_map")
+    return tally, correct, mapping[:int(ref.ref_off[-1])], co[:total], co_off
+
+
+def results_from_tables(ref: PackReference, cent_off, co_off, tally, correct, mapping, co) -> List[DerResult]:
+    """The downloaded tables of score_tables (numpy) cut into one DerResult per recording."""
+    out = []
+    for r, names in enumerate(ref.names):
+        S, K = len(names), int(cent_off[r + 1] - cent_off[r])
+        a = int(co_off[r])
+        out.append(_result(names, np.asarray(co[a:a + S * K]).reshape(S, K), tally[r], mapping[int(ref.ref_off[r]):int(ref.ref_off[r + 1])], correct[r]))
+    return out
+
+
+def score_grouped(eng, speakers_dev, tab, references, collar_s: float = 0.0, skip_overlap: bool = False) -> List[DerResult]:
+    """The device path for one pack: speakers [G, 2] int32 on the packed frame grid of tab (diarize.GroupTables with clusters set), one
+    reference turn list per recording -> one DerResult per recording.  Three kernels calls, then one download of the integer tables."""
+    from .diarize import _native
+    torch = _native()[0]
+    ref = rasterise_references(eng, tab, references, collar_s, skip_overlap)
+    tally, correct, mapping, co, co_off = score_tables(eng, speakers_dev, tab, ref)
+    flat = torch.cat([tally.reshape(-1), correct, mapping.to(torch.int64), co.to(torch.int64)]).cpu().numpy()
+    return results_from_tables(ref, tab.cent_off, co_off, *split_tables(flat, tab.R, int(ref.ref_off[-1]), int(co_off[-1])))
+
+
+def split_tables(flat: np.ndarray, R: int, n_ref: int, n_co: int):
+    """One int64 download [5 R + R + n_ref + n_co] -> (tally [R, 5], correct [R], map [n_ref], co [n_co])."""
+    a, b, c = 5 * R, 6 * R, 6 * R + n_ref
+    return flat[:a].reshape(R, 5), flat[a:b], flat[b:c], flat[c:c + n_co]
