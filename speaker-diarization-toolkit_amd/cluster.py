@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import dist as sdist
+from .diarize_ops import _check_rows, diarize_centroids
 
 
 @dataclass
@@ -600,7 +601,6 @@ def kmeans_cluster(provider, E, k: int, rows=None, max_iters: int = KMEANS_MAX_I
                   made canonical; cent / cent64 come from sdk_diarize_centroids over those labels (the float64 mean of the unit rows in
                   ascending row order, re-normalised), in the layout sdk_diarize_assign takes."""
     import torch as _torch
-    from .diarize import diarize_centroids, _check_rows
     _check_rows("kmeans_cluster", E)
     R = int(E.shape[0])
     rows_h = np.arange(R, dtype=np.int64) if rows is None else np.asarray(rows, dtype=np.int64).reshape(-1)

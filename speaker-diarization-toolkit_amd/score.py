@@ -26,7 +26,7 @@ tests pin this rule.
   limits      at most MAX_SCORE_SPEAKERS = 64 reference and 64 hypothesis speakers per recording: more is a ValueError here and refused by
               the library
 
-The device path is three calls in stream order on the prefix-sum tables of diarize.GroupTables (csrc/score.hip): sdk_score_reference
+The device path is three calls in stream order on the prefix-sum tables of diarize_ops.GroupTables (csrc/score.hip): sdk_score_reference
 (reference turns -> a 64-bit speaker mask and a scored flag per frame), sdk_score_cooccur (masks and speakers -> co and the tallies, summed per
 workgroup in LDS, then integer atomics) and sdk_score_map (one wave per recording: shortest augmenting paths with int64 potentials).  Only
 integers, OR and integer adds: the results do not depend on any order and are bit-identical run to run.  The *_host functions restate the three
@@ -41,7 +41,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .diarize import global_frames
+from .diarize_host import global_frames
+from .diarize_ops import GroupTables, _native
 from .segmentation import FRAME_HOP, SAMPLE_RATE
 
 MAX_SCORE_SPEAKERS = 64
@@ -99,7 +100,7 @@ def best_threshold(thresholds: Sequence[float], pooled: Sequence[DerResult]) -> 
 # ------------------------------------------------------------------------------------------------ RTTM and the reference on the host
 def parse_rttm(text: str) -> Dict[str, List[Tuple[float, float, str]]]:
     """RTTM text -> {uri: [(start_s, end_s, name)]} in file order.  Reads the SPEAKER lines (`SPEAKER <uri> <chan> <start> <dur> <NA> <NA>
-    <name> ...`, what diarize.to_rttm writes) and ignores every other line."""
+    <name> ...`, what diarize_host.to_rttm writes) and ignores every other line."""
     out: Dict[str, List[Tuple[float, float, str]]] = {}
     for n, line in enumerate(text.splitlines(), 1):
         f = line.split()
@@ -285,9 +286,8 @@ class PackReference:
 
 
 def rasterise_references(eng, tab, references, collar_s: float = 0.0, skip_overlap: bool = False, upload=None) -> PackReference:
-    """One turn list per recording of the pack (tab: diarize.GroupTables) -> PackReference: sdk_score_reference.  upload: what carries the
+    """One turn list per recording of the pack (tab: diarize_ops.GroupTables) -> PackReference: sdk_score_reference.  upload: what carries the
     one table of host integers to the device (a caller that counts its transfers passes its own)."""
-    from .diarize import _native
     torch, check, _stream = _native()
     if len(references) != tab.R:
         raise ValueError(f"score: {len(references)} references for {tab.R} recordings")
@@ -319,7 +319,6 @@ def score_tables(eng, speakers_dev, tab, ref: PackReference, upload=None):
     """speakers [G, 2] int32 on the packed grid (device), tab with clusters set (K_r = the hypothesis speakers of recording r) ->
     (tally [R, 5] int64, correct [R] int64, map [sum S_r] int32, co int32 [co_off[-1]], co_off [R + 1] int64 on the host), the first four
     on the device: sdk_score_cooccur, then sdk_score_map.  Nothing is read back."""
-    from .diarize import _native
     torch, check, _stream = _native()
     if tab.cent_off is None:
         raise ValueError("score: the tables hold no clusters (set_clusters)")
@@ -354,14 +353,35 @@ def results_from_tables(ref: PackReference, cent_off, co_off, tally, correct, ma
 
 
 def score_grouped(eng, speakers_dev, tab, references, collar_s: float = 0.0, skip_overlap: bool = False) -> List[DerResult]:
-    """The device path for one pack: speakers [G, 2] int32 on the packed frame grid of tab (diarize.GroupTables with clusters set), one
+    """The device path for one pack: speakers [G, 2] int32 on the packed frame grid of tab (diarize_ops.GroupTables with clusters set), one
     reference turn list per recording -> one DerResult per recording.  Three kernels calls, then one download of the integer tables."""
-    from .diarize import _native
     torch = _native()[0]
     ref = rasterise_references(eng, tab, references, collar_s, skip_overlap)
     tally, correct, mapping, co, co_off = score_tables(eng, speakers_dev, tab, ref)
     flat = torch.cat([tally.reshape(-1), correct, mapping.to(torch.int64), co.to(torch.int64)]).cpu().numpy()
     return results_from_tables(ref, tab.cent_off, co_off, *split_tables(flat, tab.R, int(ref.ref_off[-1]), int(co_off[-1])))
+
+
+def score_results(eng, results, references, collar_s: float = 0.0, skip_overlap: bool = False) -> List[DerResult]:
+    """Diarizer.score: DiarizationResults and one reference turn list per result -> one DerResult per result; their `speakers` are uploaded
+    and scored on the device as one pack (score_grouped)."""
+    results, references = list(results), list(references)
+    if len(references) != len(results):
+        raise ValueError(f"score: {len(references)} references for {len(results)} recordings")
+    if not results:
+        return []
+    spk = [np.ascontiguousarray(res.speakers, dtype=np.int32).reshape(-1, 2) for res in results]
+    for r, (res, sp) in enumerate(zip(results, spk)):
+        if sp.size and int(sp.max()) >= int(res.n_speakers):
+            raise ValueError(f"score: recording {r}: speakers names {int(sp.max())}, the result has {res.n_speakers} speakers")
+        if int(res.n_speakers) > MAX_SCORE_SPEAKERS:
+            raise ValueError(f"score: recording {r}: {res.n_speakers} hypothesis speakers; at most {MAX_SCORE_SPEAKERS} per recording")
+    torch = _native()[0]
+    G_r = [len(sp) for sp in spk]
+    n_samples = [FRAME_HOP * g + 226 if g else 0 for g in G_r]                      # a length with global_frames(n) == g: only the grid is read
+    tab = GroupTables(eng, np.zeros(len(results) + 1, np.int64), np.concatenate([[0], np.cumsum(G_r)]), n_samples)
+    tab.set_clusters(np.concatenate([[0], np.cumsum([int(res.n_speakers) for res in results])]))
+    return score_grouped(eng, torch.from_numpy(np.concatenate(spk)).to(eng.device), tab, references, collar_s, skip_overlap)
 
 
 def split_tables(flat: np.ndarray, R: int, n_ref: int, n_co: int):

@@ -9,7 +9,7 @@ design) as best known here; no code of it is on hand, so PARITY IS UNPINNED, as 
               j * hop + CHUNK samples have arrived; finish() adds the chunk that ends at the stream's end when (n - CHUNK) % hop != 0, and the
               single zero-padded chunk at 0 when n <= CHUNK.  A stream with no samples is empty.
   embedding   Diarizer.embed_chunks, unchanged: cls [F], info [3, 4] and three unit rows per chunk.  The candidates of a chunk are its
-              diarize.candidate_mask rows; a candidate is LONG when it is in diarize.training_mask (TRAIN_CLEAN_DEN * clean_frames >= F).
+              diarize_host.candidate_mask rows; a candidate is LONG when it is in diarize_host.training_mask (TRAIN_CLEAN_DEN * clean_frames >= F).
               Rows that are no candidates are never read.
   inventory   K <= capacity speakers; per speaker the float64 sum S_k of the unit fp32 rows added to it and their number n_k; its unit
               centroid is S_k / ||S_k||.  Speakers are numbered in the order in which they are founded and never renumbered.  A cosine is the
@@ -27,7 +27,7 @@ design) as best known here; no code of it is on hand, so PARITY IS UNPINNED, as 
               hold = (round(latency_s * 16000) - hop) // 270 frames.  After chunk c the stream emits every frame not yet emitted with
               g < F - q_c - hold (a chunk that finish() adds: and g < global_frames(n) - the zero-padded chunk reaches beyond the
               stream's end); finish() then emits the rest, up to global_frames(n).  An emitted frame's count and speakers follow
-              diarize.reconstruct_host's rule on the chunks that have contributed SO FAR (the mean count rounded half up and capped; the
+              diarize_host.reconstruct_host's rule on the chunks that have contributed SO FAR (the mean count rounded half up and capped; the
               clusters of largest act > 0, ties to the lower id).  Emitted frames never change: a later chunk's verdict on them is dropped.
               With latency_s = 10 and (n - CHUNK) % hop == 0 every frame is emitted after its last chunk, so the stream's frames are
               reconstruct_host's on its own labels; a shorter latency trades chunks per frame for delay, and the final off-grid chunk of
@@ -39,7 +39,7 @@ design) as best known here; no code of it is on hand, so PARITY IS UNPINNED, as 
 
 The *_host functions restate sdk_stream_step and sdk_stream_flush in numpy (HostStream holds what the device block holds, ring included);
 tests/stream_ref.py restates the rule a second time without the ring.  Re-clustering or merging of online speakers is out of scope: a
-speaker founded twice stays two (diarize.link_speakers joins inventories after the fact).
+speaker founded twice stays two (diarize_link.link_speakers joins inventories after the fact).
 """
 from __future__ import annotations
 
@@ -48,8 +48,8 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
-from .diarize import (N_LOCAL, DiarizationResult, _COUNT, _MASK, _speaker_cap, candidate_mask, constrained_chunk,
-                      global_frames, training_mask, turns_from_frames)
+from .diarize_host import (N_LOCAL, DiarizationResult, _COUNT, _MASK, _speaker_cap, candidate_mask, constrained_chunk,
+                           global_frames, training_mask, turns_from_frames)
 from .segmentation import CHUNK, FRAME_HOP, SAMPLE_RATE
 from .segmentation import num_frames as seg_frames
 
@@ -161,7 +161,7 @@ def map_chunk_host(hs: HostStream, E3: np.ndarray, info3: np.ndarray, F: int, de
 
 
 def emit_host(nc, cnt, act, K: int, max_speakers: Optional[int] = None):
-    """nc [n], cnt [n], act [n, >= K] of n frames -> (count [n] uint8, speakers [n, 2] int32): diarize.reconstruct_host's last lines."""
+    """nc [n], cnt [n], act [n, >= K] of n frames -> (count [n] uint8, speakers [n, 2] int32): diarize_host.reconstruct_host's last lines."""
     n = len(nc)
     count = np.where(nc > 0, np.minimum((2 * cnt + nc) // np.maximum(2 * nc, 1), _speaker_cap(max_speakers)), 0)
     a = np.asarray(act)[:, :K]

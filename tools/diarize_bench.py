@@ -4,10 +4,10 @@ device; clustering / assignment / reconstruction / host by wall clock), chunks/s
 process on the same inputs:
   trunk sharing   three ResNet34.forward calls per chunk at T = 1001 (what embedding each (chunk, speaker) pair separately costs) against
                   the one masked forward; the ratio is reported, not gated
-  reconstruction  the numpy statement of the stitching rule (diarize.reconstruct_host) on the same class table
+  reconstruction  the numpy statement of the stitching rule (diarize_host.reconstruct_host) on the same class table
   assignment      the constrained stage on the device (training rows and labels up, sdk_diarize_centroids + sdk_diarize_assign, labels, scores
                   and centroids down; wall clock, best of three after a warm-up) beside the host stage it stands in for (the download of
-                  the embeddings + diarize.assign_rows) on the same embeddings, and how many chunks the constraint changed
+                  the embeddings + diarize_host.assign_rows) on the same embeddings, and how many chunks the constraint changed
   vbx             the VBx clustering's device stretch (sdk_plda_transform + sdk_vbx, all iterations enqueued + sdk_vbx_centroids; wall clock
                   around ONE final synchronisation, best of three after a warm-up) on two inputs - the hour's training rows with the initial
                   labels of the linkage's cut at 0.6, and a generated table of N = 10 000 rows, D = 128, with 5 true speakers split into 50
