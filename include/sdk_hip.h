@@ -44,6 +44,7 @@
  *     sdk_score_reference  sdk_score_cooccur  sdk_score_map                                             diarization error rate against a reference (score.py)
  *     sdk_plda_transform  sdk_vbx_workspace_bytes  sdk_vbx  sdk_vbx_centroids                           VBx clustering (plda.py, cluster.vbx_cluster)
  *     sdk_vbx_hmm_workspace_bytes  sdk_vbx_hmm                                                          VBx with its HMM, rows in time order (loop_prob > 0)
+ *     sdk_plda_fit_stats_workspace_bytes  sdk_plda_fit_stats  sdk_plda_project                          training the VBx PLDA from labelled rows (plda.fit)
  *     sdk_cohort_stats_workspace_bytes  sdk_cohort_stats  sdk_affinity_topk_snorm                       adaptive score normalisation (snorm.py)
  *     sdk_kmeans_rows_workspace_bytes  sdk_kmeans_rows                                                  spherical k-means on unit rows (cluster.kmeans_cluster)
  *     sdk_stream_state_bytes  sdk_stream_reset  sdk_stream_step  sdk_stream_flush  sdk_stream_centroids streaming diarization: online speaker tracking (stream.py)
@@ -690,6 +691,26 @@ int sdk_vbx_hmm(sdk_ctx* ctx, const double* X, const double* Phi, const int32_t*
                 int32_t* status, void* ws, size_t ws_bytes, void* stream);
 int sdk_vbx_centroids(sdk_ctx* ctx, const double* gamma, const double* pi, const float* E, const int32_t* rows, int n, int S, int d, int32_t* K,
                       int32_t* keep, int32_t* labels, float* cent, double* cent64, void* stream);
+
+/* ---- training the VBx PLDA from labelled embeddings (plda.fit; csrc/plda_fit.hip): the sums over n <= 2^24 labelled rows that the host's d x d
+ *      solves start from.  Float64 results; no floating-point atomics, one owner per output element; rows are cut into
+ *      ceil(n / RB) fixed blocks of RB = max(512, 64 ceil(n / 16384)) rows, summed inside a block in ascending order (the scatter: four rows per
+ *      f64 MFMA) and across blocks in block order; a class sum runs over the class's rows in the order of `order`: bit-identical run to run.
+ *   sdk_plda_fit_stats : exactly one source - E [n][d] fp32 rows (d a multiple of 64, at most 512; with mean1 [d] every row enters as
+ *        sqrt(d) unit(e - mean1), with mean1 NULL as it is) or X [n][d] float64 rows as they lie (d 1 .. 512, mean1 NULL) - and, with K > 0,
+ *        labels [n] int32 and order [n] int32 (the row indices sorted by label, stably: ascending inside a class) -> counts [K] int64,
+ *        sums [K][d] (zeros for a class without rows), total [d], scatter [d][d] = sum x x^T (the upper triangle is computed and mirrored:
+ *        exactly symmetric; NULL skips it) and status (one int32: bit 1 = a label outside [0, K) - it is never used as an index; such rows are
+ *        in total and scatter and in no class).  K = 0: labels, order, counts and sums may be NULL.  workspace:
+ *        sdk_plda_fit_stats_workspace_bytes(n, d, K, scatter != NULL) (0 for arguments the call would refuse), 256-byte aligned.
+ *   sdk_plda_project : E [n][d_in] fp32 rows, mean1 [d_in], lda [d_in][D0] (D0 <= 512), mean2 [D0] -> X2 [n][D0] float64:
+ *        x2 = sqrt(D0) unit(lda^T sqrt(d_in) unit(e - mean1) - mean2), sdk_plda_transform's first two steps for every row. */
+size_t sdk_plda_fit_stats_workspace_bytes(int n, int d, int K, int with_scatter);
+int sdk_plda_fit_stats(sdk_ctx* ctx, const float* E, const double* X, const double* mean1, int n, int d, const int32_t* labels,
+                       const int32_t* order, int K, int64_t* counts, double* sums, double* total, double* scatter, int32_t* status, void* ws,
+                       size_t ws_bytes, void* stream);
+int sdk_plda_project(sdk_ctx* ctx, const float* E, int d_in, int n, const double* mean1, const double* lda, const double* mean2, int D0,
+                     double* X2, void* stream);
 
 /* ---- spherical k-means on unit rows (cluster.kmeans_cluster; csrc/kmeans.hip): the forced speaker count of the diarization (`speakers=`) with
  *      clustering="vbx".  float64 arithmetic, no floating-point atomics, one owner per output element, every sum in one fixed order:

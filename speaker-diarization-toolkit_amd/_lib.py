@@ -174,6 +174,9 @@ SIGNATURES = {
     "sdk_vbx_hmm_workspace_bytes": (_sz, [_i, _i, _i]),
     "sdk_vbx_hmm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f64, _f64, _i, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sdk_vbx_centroids": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sdk_plda_fit_stats_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "sdk_plda_fit_stats": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sdk_plda_project": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "sdk_cohort_stats_workspace_bytes": (_sz, [_i, _i, _i]),
     "sdk_cohort_stats": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "sdk_affinity_topk_snorm": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

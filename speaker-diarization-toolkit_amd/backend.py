@@ -61,6 +61,19 @@ from .wav import cut_ranges, cut_windows, decode_to_profile, range_starts, windo
 from .weights import DEFAULT_CONFIG, load_weights, synthetic_weights, weights_digest
 
 
+def plda_classes(recording, speaker, names, uris, speaker_key):
+    """The class of every labelled row of Diarizer.plda_rows: (uri, reference name), numbered by first appearance, unless
+    speaker_key(uri, name) maps several to one key; uri is the recording's entry of `uris`, else its index -> (labels int32, keys)."""
+    keys: dict = {}
+    labels = np.zeros(len(speaker), np.int32)
+    for j, (r, s) in enumerate(zip(recording, speaker)):
+        uri = uris[int(r)] if uris is not None else int(r)
+        name = names[int(r)][int(s)]
+        key = speaker_key(uri, name) if speaker_key is not None else (uri, name)
+        labels[j] = keys.setdefault(key, len(keys))
+    return labels, list(keys)
+
+
 class Backend(EmbeddingBackend):
     def __init__(self) -> None:
         self.model = os.environ.get("SDK_MODEL", "ecapa").strip().lower()
@@ -591,6 +604,39 @@ class Backend(EmbeddingBackend):
         finally:
             if dz.eng.precision != prec:
                 dz.eng.set_precision(prec)                       # the front end's format goes back to the selected family's contract
+
+    def train_plda(self, samples_or_paths, references, uris=None, out_dir=None, D0: int = 128, lda_dim: int = 128, n_iters: int = 10,
+                   step_s: float = 1.0, speaker_key=None, logp=None):
+        """A PLDA model for clustering="vbx" fitted to THIS embedding space from recordings with reference annotations (the inputs of
+        tune_diarization; references as score_diarization takes them) -> (plda.Plda, report).  The recordings are embedded in packs and every
+        training row is labelled with the reference speaker that covers it (diarize.Diarizer.plda_rows); a class is (recording, reference
+        name) - one person in two recordings is two classes - unless speaker_key(uri, name) maps several to one key (uri: the recording's
+        entry of `uris`, else its index).  plda.fit then runs on the device (plda.py states the rule and what it refuses: at least D0 + 1
+        classes and N - K' >= the embedding width).  report: rows_used, rows_dropped, classes, counts, objf, and with out_dir the two paths
+        written, xvec_transform.npz and plda.npz, which $SDK_PLDA_TRANSFORM / $SDK_PLDA accept."""
+        from . import plda as plda_mod
+        dz = self.diarizer()
+        recs = [decode_to_profile(Path(x), self.engine(), self.get_audio_profile()) if isinstance(x, (str, Path)) else x for x in samples_or_paths]
+        refs = self._references("train_plda", references, uris, len(recs))
+        prec = dz.eng.precision
+        try:
+            got = dz.plda_rows(recs, refs, step_s=step_s, logp=logp)
+        finally:
+            if dz.eng.precision != prec:
+                dz.eng.set_precision(prec)                       # the front end's format goes back to the selected family's contract
+        labels, keys = plda_classes(got["recording"], got["speaker"], got["names"], uris, speaker_key)
+        if not len(labels):
+            raise ValueError("train_plda: no training row is covered by a reference speaker")
+        import torch
+        model, fit = plda_mod.fit(dz.eng, got["E"], torch.from_numpy(labels).to(got["E"].device), D0, lda_dim, n_iters, K=len(keys))
+        report = {"rows_used": int(len(labels)), "rows_dropped": int(got["n_dropped"]), "classes": int(fit.n_classes), "class_keys": keys,
+                  "counts": fit.counts, "objf": fit.objf}
+        if out_dir is not None:
+            out = Path(out_dir)
+            out.mkdir(parents=True, exist_ok=True)
+            report["transform_npz"], report["plda_npz"] = out / "xvec_transform.npz", out / "plda.npz"
+            plda_mod.save_plda(model, report["transform_npz"], report["plda_npz"])
+        return model, report
 
     def open_streams(self, n_streams: int = 1, **options):
         """Streaming diarization: a stream.StreamBank of n_streams live streams on the models diarize loads (options: step_s, latency_s,

@@ -105,7 +105,7 @@ from .diarize_host import (DEFAULT_BATCH, DEFAULT_PACK_LINKAGE_BYTES, DEFAULT_PA
                            MIN_CLEAN_COLUMNS, MIN_VALID_COLUMNS, N_LOCAL, TRAIN_CLEAN_DEN, _COUNT, _MASK, DiarizationResult, Pack, _centroids64,
                            _dot_in_order, _speaker_cap, appearance_order, assign_constrained_host, assign_grouped_host, assign_rows, candidate_mask,
                            constrained_chunk, decode_host, first_seen_host, fold_grouped_host, global_frames, masks_host, pack_recordings, pack_rows,
-                           reconstruct_grouped_host, reconstruct_host, renumber_host, split_packs, to_rttm, training_mask, training_rows, turns_from_frames)
+                           reconstruct_grouped_host, reconstruct_host, reference_labels, renumber_host, split_packs, to_rttm, training_mask, training_rows, turns_from_frames)
 from .diarize_link import SpeakerLinks, link_speakers, relabel_turns  # noqa: F401
 from .diarize_ops import (LINKAGE_HOST_READS, VBX_HOST_READS, GroupTables, _check_dim, _check_rows, _check_tensor, _native, diarize_assign,  # noqa: F401
                           diarize_assign_grouped, diarize_centroids, diarize_first_seen, diarize_fold_grouped, diarize_masks, diarize_reconstruct,
@@ -419,6 +419,55 @@ class Diarizer:
             self._mark("download")
         pooled = [pool(row) for row in per]
         return SweepResult(ths, per, pooled, best_threshold(ths, pooled))
+
+    # ---------------------------------------------------------------------------------------------- labelled rows for training a PLDA
+    def plda_rows(self, samples_list, references, step_s: float = 1.0, logp=None) -> dict:
+        """The training rows of the recordings with the reference speaker each belongs to, for plda.fit (Backend.train_plda).  references:
+        one turn list [(start_s, end_s, name)] per recording; logp as run_many's.  The recordings go through _embed_all in packs, as
+        run_many's do, and the embeddings stay on the device; per pack the class tables come down once and every training row
+        (training_mask) is labelled on the host in integers (diarize_host.reference_labels states the rule; the reference is
+        score.prepare_reference rasterised by score.reference_masks_host, no collar).  -> dict(E [n, d] fp32 unit rows on the device, the
+        labelled rows in recording then row order; recording [n], row [n] (c * 3 + s inside the recording) and speaker [n] int32 (the index
+        into names[recording]); names: one list per recording; n_training, n_dropped: the training rows seen and those left out)."""
+        from .score import MAX_SCORE_SPEAKERS, prepare_reference, reference_masks_host
+        torch = _native()[0]
+        references = list(references)
+        if len(references) != len(samples_list):
+            raise ValueError(f"plda_rows: {len(references)} references for {len(samples_list)} recordings")
+        opts = _Options(step_s, None, PYANNOTE_MIN_CLUSTER_SIZE, None, False, "ahc", {}, None)
+        xs, packs = self._plan_packs(samples_list, logp, step_s)
+        names: List[list] = [[] for _ in xs]
+        E, rec_of, row_of, spk_of = [], [], [], []
+        n_training = 0
+        self.last_sync = []
+        for idx in packs:
+            p = self._pack_begin([xs[i] for i in idx], None if logp is None else [logp[i] for i in idx], opts)
+            if p is None:
+                continue
+            cls = self._down(p.cls)
+            co, fo = p.pack.chunk_off, p.pack.frame_off
+            take = []
+            for r, i in enumerate(idx):
+                merged, names[i] = prepare_reference(references[i])
+                if len(names[i]) > MAX_SCORE_SPEAKERS:
+                    raise ValueError(f"plda_rows: recording {i} has {len(names[i])} reference speakers; at most {MAX_SCORE_SPEAKERS}")
+                a, b = int(co[r]), int(co[r + 1])
+                mask, _ = reference_masks_host(merged, int(fo[r + 1] - fo[r]))
+                lab = reference_labels(cls[a:b], p.info[a:b], p.pack.starts_local[a:b], mask, len(names[i]))
+                n_training += int(training_mask(p.info[a:b], cls.shape[1]).sum())
+                rows = np.flatnonzero(lab >= 0)
+                take.append(N_LOCAL * a + rows)
+                rec_of.append(np.full(len(rows), i, np.int32))
+                row_of.append(rows.astype(np.int32))
+                spk_of.append(lab[rows])
+            take = np.concatenate(take)
+            if len(take):
+                E.append(p.E_dev.index_select(0, self._up(take.astype(np.int64))))
+        cat = (lambda v: np.concatenate(v) if v else np.zeros(0, np.int32))
+        d = self.resnet.cfg.embed_dim
+        E_all = torch.cat(E).contiguous() if E else torch.empty((0, d), dtype=torch.float32, device=self.eng.device)
+        return dict(E=E_all, recording=cat(rec_of), row=cat(row_of), speaker=cat(spk_of), names=names, n_training=n_training,
+                    n_dropped=n_training - int(E_all.shape[0]))
 
     def _up(self, a, dtype=None):                              # host -> device, counted for the current pack (dtype: torch.as_tensor converts on the way)
         torch = _native()[0]

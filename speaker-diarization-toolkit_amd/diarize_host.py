@@ -123,6 +123,38 @@ def training_rows(info: np.ndarray, F: int) -> np.ndarray:
     return np.flatnonzero(training_mask(info, F))
 
 
+def reference_labels(cls: np.ndarray, info: np.ndarray, starts: np.ndarray, ref_mask: np.ndarray, n_ref: int) -> np.ndarray:
+    """The reference speaker of every row (c * 3 + s) of one recording, for training a PLDA (Diarizer.plda_rows), in integers on the host.
+    cls [C, F] uint8, info [C, 3, 4], starts [C] the chunks' first samples, ref_mask [G] uint64 (score.reference_masks_host, no collar: bit r
+    = reference speaker r is active in global frame g), n_ref speakers.  A row outside training_mask gets -1.  A training row: over the chunk
+    frames i where its local speaker is active and the frame's count is < 2, mapped to g = i - q_c (the stitching's map,
+    q_c = (135 - start_c) // 270) and kept where 0 <= g < G, tally per reference speaker the frames in which that speaker is active; the row
+    takes the speaker of the largest tally (ties to the lower index) if 2 * tally >= the number of those frames, else -1."""
+    cls, starts = np.asarray(cls), np.asarray(starts, dtype=np.int64)
+    Cn, F = cls.shape
+    G = int(len(ref_mask))
+    train = training_mask(info, F)
+    out = np.full(Cn * N_LOCAL, -1, np.int32)
+    bit = np.uint64(1) << np.arange(max(int(n_ref), 1), dtype=np.uint64)
+    for c in range(Cn):
+        if not train[N_LOCAL * c:N_LOCAL * (c + 1)].any() or not n_ref:
+            continue
+        g = np.arange(F, dtype=np.int64) - (135 - int(starts[c])) // FRAME_HOP
+        ok = (g >= 0) & (g < G) & (_COUNT[cls[c]] < 2)
+        for s in range(N_LOCAL):
+            if not train[N_LOCAL * c + s]:
+                continue
+            sel = ok & _MASK[cls[c]][:, s]
+            n = int(sel.sum())
+            if n == 0:
+                continue
+            tally = ((np.asarray(ref_mask, dtype=np.uint64)[g[sel]][:, None] & bit[None, :]) != 0).sum(0)
+            best = int(np.argmax(tally))                                 # the first maximum: ties to the lower index
+            if 2 * int(tally[best]) >= n:
+                out[N_LOCAL * c + s] = best
+    return out
+
+
 def pack_rows(info: np.ndarray, chunk_off: np.ndarray):
     """Per recording of a pack: the rows that make its centroids (global rows of E, ascending) and how many of them are training rows."""
     cand_ok, train_ok = candidate_mask(info), training_mask(info, seg_frames(CHUNK))

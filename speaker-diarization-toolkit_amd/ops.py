@@ -1092,6 +1092,71 @@ class Engine:
                                          labels.data_ptr(), cent.data_ptr(), cent64.data_ptr(), _stream()), "sdk_vbx_centroids")
         return K, keep, labels, cent, cent64
 
+    # ---- training the PLDA from labelled rows (plda.fit; csrc/plda_fit.hip)
+    def plda_fit_stats(self, rows: torch.Tensor, labels: Optional[torch.Tensor] = None, K: int = 0, mean1: Optional[torch.Tensor] = None,
+                       scatter: bool = True, check_labels: bool = True) -> dict:
+        """rows [N, d] on the device: fp32 (d a multiple of 64, at most 512; with mean1 [d] float64 every row enters as
+        sqrt(d) unit(e - mean1)) or float64 as they lie (d 1 .. 512); labels [N] int32 in [0, K) or None (K = 0: the total and the scatter
+        only) -> dict(counts [K] int64, sums [K, d], total [d], scatter [d, d] or None, status [1] int32), float64 on the device:
+        sdk_plda_fit_stats.  The labels' range is checked here, before any launch (one read-back; check_labels=False: the caller has), and the
+        row indices are sorted by label with torch's stable sort."""
+        if rows.dim() != 2 or rows.dtype not in (torch.float32, torch.float64) or not rows.is_contiguous() or not rows.is_cuda:
+            raise ValueError(f"plda_fit_stats: rows must be a contiguous fp32 or float64 [N, d] device tensor, got {tuple(rows.shape)} {rows.dtype}")
+        N, d, K = int(rows.shape[0]), int(rows.shape[1]), int(K)
+        f32 = rows.dtype == torch.float32
+        if N < 1 or N > 1 << 24:
+            raise ValueError(f"plda_fit_stats: N={N} rows (1 .. 2^24)")
+        if (d < 64 or d % 64 or d > 512) if f32 else (d < 1 or d > 512):
+            raise ValueError(f"plda_fit_stats: d={d} not supported (fp32 rows: a multiple of 64 in 64 .. 512; float64 rows: 1 .. 512)")
+        if mean1 is not None and (not f32 or mean1.dtype != torch.float64 or tuple(mean1.shape) != (d,) or not mean1.is_contiguous() or not mean1.is_cuda):
+            raise ValueError(f"plda_fit_stats: mean1 goes with fp32 rows and must be a contiguous float64 [{d}] device tensor")
+        if K < 0 or K > 1 << 24 or (labels is None) != (K == 0):
+            raise ValueError(f"plda_fit_stats: K={K} (1 .. 2^24 with labels, 0 without)")
+        dev = rows.device
+        order = counts = sums = None
+        if labels is not None:
+            if labels.dtype != torch.int32 or tuple(labels.shape) != (N,) or not labels.is_contiguous() or not labels.is_cuda:
+                raise ValueError(f"plda_fit_stats: labels must be a contiguous int32 [{N}] device tensor, got {tuple(labels.shape)} {labels.dtype}")
+            if check_labels:
+                lo, hi = int(labels.min()), int(labels.max())
+                if lo < 0 or hi >= K:
+                    raise ValueError(f"plda_fit_stats: labels must lie in [0, {K}), got {lo} .. {hi}")
+            order = torch.sort(labels, stable=True).indices.to(torch.int32)
+            counts = torch.empty((K,), dtype=torch.int64, device=dev)
+            sums = torch.empty((K, d), dtype=torch.float64, device=dev)
+        nbytes = int(self.lib.sdk_plda_fit_stats_workspace_bytes(N, d, K, int(bool(scatter))))
+        if nbytes == 0:
+            raise SdkError(f"sdk_plda_fit_stats_workspace_bytes: {self.lib.sdk_last_error().decode()}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        total = torch.empty((d,), dtype=torch.float64, device=dev)
+        S = torch.empty((d, d), dtype=torch.float64, device=dev) if scatter else None
+        status = torch.empty((1,), dtype=torch.int32, device=dev)
+        check(self.lib.sdk_plda_fit_stats(self.ctx, rows.data_ptr() if f32 else None, None if f32 else rows.data_ptr(), _ptr(mean1), N, d, _ptr(labels),
+                                          _ptr(order), K, _ptr(counts), _ptr(sums), total.data_ptr(), _ptr(S), status.data_ptr(), ws.data_ptr(), nbytes,
+                                          _stream()), "sdk_plda_fit_stats")
+        return dict(counts=counts, sums=sums, total=total, scatter=S, status=status)
+
+    def plda_project(self, E: torch.Tensor, mean1: torch.Tensor, lda: torch.Tensor, mean2: torch.Tensor) -> torch.Tensor:
+        """E [N, d_in] fp32 rows, mean1 [d_in], lda [d_in, D0], mean2 [D0] (float64, device) -> x2 [N, D0] float64:
+        sqrt(D0) unit(lda^T sqrt(d_in) unit(e - mean1) - mean2), sdk_plda_transform's first two steps for every row (sdk_plda_project)."""
+        if E.dim() != 2 or E.dtype != torch.float32 or not E.is_contiguous() or not E.is_cuda:
+            raise ValueError(f"plda_project: E must be a contiguous fp32 [N, d] device tensor, got {tuple(E.shape)} {E.dtype}")
+        N, d_in = int(E.shape[0]), int(E.shape[1])
+        if N < 1 or N > 1 << 24:
+            raise ValueError(f"plda_project: N={N} rows (1 .. 2^24)")
+        if d_in < 64 or d_in % 64 or d_in > 512:
+            raise ValueError(f"plda_project: d_in={d_in} not supported (a multiple of 64, at most 512)")
+        if lda.dim() != 2 or lda.shape[0] != d_in or not 1 <= lda.shape[1] <= 512:
+            raise ValueError(f"plda_project: lda must be [{d_in}, D0 <= 512], got {tuple(lda.shape)}")
+        D0 = int(lda.shape[1])
+        for name, t, shape in (("mean1", mean1, (d_in,)), ("lda", lda, (d_in, D0)), ("mean2", mean2, (D0,))):
+            if t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"plda_project: {name} must be a contiguous float64 {list(shape)} device tensor, got {tuple(t.shape)} {t.dtype}")
+        X2 = torch.empty((N, D0), dtype=torch.float64, device=E.device)
+        check(self.lib.sdk_plda_project(self.ctx, E.data_ptr(), d_in, N, mean1.data_ptr(), lda.data_ptr(), mean2.data_ptr(), D0, X2.data_ptr(),
+                                        _stream()), "sdk_plda_project")
+        return X2
+
     # ---- spherical k-means on unit rows (cluster.kmeans_cluster; csrc/kmeans.hip): the whole loop in one enqueue, nothing read back here
     def kmeans_rows(self, E: torch.Tensor, rows: torch.Tensor, k: int, max_iters: int = 20, check_rows: bool = True):
         """E [R, d] fp32 unit rows, rows [n] int32 ascending (device), 1 <= k <= min(n, 64) -> (labels [n] int32 in [0, k), not canonical,
