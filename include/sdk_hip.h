@@ -46,6 +46,8 @@
  *     sdk_vbx_hmm_workspace_bytes  sdk_vbx_hmm                                                          VBx with its HMM, rows in time order (loop_prob > 0)
  *     sdk_plda_fit_stats_workspace_bytes  sdk_plda_fit_stats  sdk_plda_project                          training the VBx PLDA from labelled rows (plda.fit)
  *     sdk_cohort_stats_workspace_bytes  sdk_cohort_stats  sdk_affinity_topk_snorm                       adaptive score normalisation (snorm.py)
+ *     sdk_plda_enroll_workspace_bytes  sdk_plda_enroll  sdk_plda_score_workspace_bytes  sdk_plda_score_topk    PLDA log-likelihood-ratio scoring of
+ *                                                                                                       windows against enrolled speakers (plda_score.py)
  *     sdk_kmeans_rows_workspace_bytes  sdk_kmeans_rows                                                  spherical k-means on unit rows (cluster.kmeans_cluster)
  *     sdk_stream_state_bytes  sdk_stream_reset  sdk_stream_step  sdk_stream_flush  sdk_stream_centroids streaming diarization: online speaker tracking (stream.py)
  * BUILDING BLOCKS AND KNOBS - exported for the parity tests and the A/B tools, free to change between rounds, not for binding:
@@ -68,7 +70,7 @@
 extern "C" {
 #endif
 
-#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5); still 4 with sdk_cohort_stats* and sdk_affinity_topk_snorm, and with sdk_ecapa_forward_masked, sdk_ecapa_masked_workspace_bytes, sdk_asp_stats_masked_fmt and sdk_asp_pool_masked_fmt, and with sdk_score_reference, sdk_score_cooccur and sdk_score_map: new exports only, no struct or existing signature changes, no caller of version 4 breaks */
+#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5); still 4 with sdk_cohort_stats* and sdk_affinity_topk_snorm, and with sdk_ecapa_forward_masked, sdk_ecapa_masked_workspace_bytes, sdk_asp_stats_masked_fmt and sdk_asp_pool_masked_fmt, and with sdk_score_reference, sdk_score_cooccur and sdk_score_map, and with sdk_plda_enroll* and sdk_plda_score*: new exports only, no struct or existing signature changes, no caller of version 4 breaks */
 
 typedef struct sdk_ctx sdk_ctx;
 
@@ -755,6 +757,35 @@ int sdk_cohort_stats(sdk_ctx* ctx, const float* E, int N, const float* Cn, int M
                      size_t ws_bytes, void* stream);
 int sdk_affinity_topk_snorm(sdk_ctx* ctx, const float* E, const float* mean_e, const float* std_e, int N, const float* P, const float* mean_p,
                             const float* std_p, int Pn, int d, int k, int32_t* idx, float* score, float* raw, void* stream);
+
+/* ---- PLDA log-likelihood-ratio scoring of windows against enrolled SPEAKERS (plda_score.py states the rule; csrc/plda_score.hip).  Float64, in
+ *      the space of sdk_plda_transform: D = 64 or 128 columns, within-speaker covariance I, between-speaker covariance diag(Phi).  For a speaker
+ *      with pooled enrolment mean u and effective count n > 0, per column:  a = n Phi / (n Phi + 1),  v = 1 + Phi / (n Phi + 1),  g = a / v,
+ *      q = -(1 / v - 1 / (1 + Phi)) / 2,  h = -a^2 / (2 v),  c = -(ln v - ln(1 + Phi)) / 2, and
+ *          llr(x, s) = r_s + sum_d x_d G[s][d] + sum_d x_d^2 G[s][D + d],   G[s] = [g o u, q],   r_s = sum_d (c_d + u_d^2 h_d)
+ *      = ln N(x | a u, v) - ln N(x | 0, 1 + Phi).  No floating-point atomics, one owner per output element, every sum in a fixed order:
+ *      bit-identical run to run.
+ *   sdk_plda_enroll : Xp [P][D] transformed profile rows (P <= 2^22), group [P] int32 (the speaker of every row, in any order), n_eff [S],
+ *        Phi [D] -> G [S][2 D], r [S] (1 <= S <= 2^20) and status (one int32).  u_s = (the sum of the speaker's rows, added in ascending row
+ *        order) / (their number).  A label outside [0, S) is never used as an index: the row belongs to no speaker and status bit 1 is set.
+ *        A speaker without a row, or whose n_eff is not a finite number above 0: G row of zeros and r = NaN - it never wins.  A speaker's
+ *        rows are found by a walk that costs (its rows)^2 / 64 index reads: meant for up to a few hundred enrolments per speaker.
+ *        workspace: sdk_plda_enroll_workspace_bytes(P, S), 256-byte aligned.
+ *   sdk_plda_score_topk : X [N][D] transformed windows (N <= 65 536; N = 0 is a no-op), G, r -> per window the k <= 4 largest llr, ties to the
+ *        lower speaker, a NaN never taken: idx [N][k] int32, score [N][k].  Slots left without a candidate hold idx -1, score 0; when k > S
+ *        the columns S .. k - 1 are NOT written.  scores (NULL to skip): the whole matrix [N][S]; score[n][j] is scores[n][idx[n][j]] bit for
+ *        bit.  The kernel forms x^2 itself ([x, x^2] is never in memory) and runs the depth-2D product on the f64 MFMA; every llr is one
+ *        chain in one order, so it depends on its window and its speaker only.  The speakers are cut into tiles of 64 and splits of at
+ *        least 4 tiles, a function of (N, S) alone; the splits' lists are merged in split order under a strict total order, so the answer
+ *        does not depend on the cut.  X and G 16-byte aligned.  workspace: sdk_plda_score_workspace_bytes(N, S, k), 256-byte aligned.
+ *   Both sizers are host-only and return 0 with sdk_last_error set for arguments the calls refuse.  Shape refusals (D, S, P, N, k) come before
+ *   anything else, the null context included. */
+size_t sdk_plda_enroll_workspace_bytes(int P, int S);
+int sdk_plda_enroll(sdk_ctx* ctx, const double* Xp, const int32_t* group, int P, int D, const double* n_eff, const double* Phi, int S, double* G,
+                    double* r, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+size_t sdk_plda_score_workspace_bytes(int N, int S, int k);
+int sdk_plda_score_topk(sdk_ctx* ctx, const double* X, int N, int D, const double* G, const double* r, int S, int k, int32_t* idx, double* score,
+                        double* scores, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- audio conversion to the AudioProfile: replaces the ffmpeg subprocess the reference's backends
  *      run before upload (audio_profiles.py:70-100 `format_ffmpeg_args`; speechmatics_backend.py:231-281).

@@ -44,6 +44,16 @@ Environment:
   SDK_COHORT_TOPK     cohort scores per side that the statistics are taken over (default 300; min(K, M) is used)
   SDK_COHORT_THRESHOLD  the vote threshold on the z scale (a float).  No default: it depends on the model family and the cohort, and no trained
                       weights are on hand to tune one - a cohort without a threshold is refused
+  SDK_SCORE_PLDA_TRANSFORM / SDK_SCORE_PLDA   the two .npz files of a PLDA model of THIS family's embedding space (plda.save_plda writes them;
+                      Backend.train_plda under the matching SDK_DIARIZE_MODEL makes one): both or neither.  identify_speaker, identify_many
+                      and verify_speaker then decide on the PLDA log-likelihood ratio of a window against an enrolled SPEAKER - the speaker's
+                      enrolled embeddings pooled, their number in the score (plda_score.py) - instead of the best single cosine.  They are
+                      distinct from SDK_PLDA_TRANSFORM / SDK_PLDA, the model of the diarizer's embedding space, which may be another family.
+                      Needs the torch engine (SDK_NO_TORCH=1 is refused); refused together with SDK_COHORT.  score_ranges stays on the cosine
+  SDK_SCORE_PLDA_DIM  the PLDA dimensions kept, 64 or 128 (default 128)
+  SDK_SCORE_PLDA_THRESHOLD  the vote threshold on the log-likelihood-ratio scale (a float, default 0: the point of equal likelihood under the
+                      model).  The scale is UNCALIBRATED: no trained weights are on hand to tune an operating point
+  SDK_SCORE_PLDA_COUNT  1 (default): a speaker's effective count n_s is the number of their enrolled embeddings ("by the book") / 0: n_s = 1
 """
 from __future__ import annotations
 
@@ -120,6 +130,36 @@ class Backend(EmbeddingBackend):
                 raise ValueError(f"SDK_COHORT_TOPK={self.cohort_topk}: at least 1")
             if os.environ.get("SDK_NO_TORCH") == "1":
                 raise ValueError("SDK_COHORT with SDK_NO_TORCH=1: the normalised path needs the torch engine; unset SDK_NO_TORCH (or SDK_COHORT)")
+        # PLDA log-likelihood-ratio scoring (plda_score.py): off unless a scoring model is configured
+        tpath, ppath = os.environ.get("SDK_SCORE_PLDA_TRANSFORM") or None, os.environ.get("SDK_SCORE_PLDA") or None
+        self.score_plda_paths: Optional[Tuple[str, str]] = None
+        self.score_plda_dim = 128
+        self.score_plda_threshold = 0.0
+        self.score_plda_count = True
+        self._score_plda = None
+        if bool(tpath) != bool(ppath):
+            raise ValueError("SDK_SCORE_PLDA_TRANSFORM and SDK_SCORE_PLDA name the two files of one PLDA model: set both or neither "
+                             f"({'SDK_SCORE_PLDA' if tpath else 'SDK_SCORE_PLDA_TRANSFORM'} is not set)")
+        if tpath:
+            if self.cohort_path:
+                raise ValueError("SDK_SCORE_PLDA* together with SDK_COHORT: the identify decision is made on ONE scale, the PLDA log-likelihood "
+                                 "ratio or the cohort-normalised cosine; unset one of them")
+            if os.environ.get("SDK_NO_TORCH") == "1":
+                raise ValueError("SDK_SCORE_PLDA* with SDK_NO_TORCH=1: PLDA scoring needs the torch engine; unset SDK_NO_TORCH (or SDK_SCORE_PLDA*)")
+            dim = os.environ.get("SDK_SCORE_PLDA_DIM", "128").strip()
+            if dim not in ("64", "128"):
+                raise ValueError(f"SDK_SCORE_PLDA_DIM={dim!r}: the PLDA dimensions kept, 64 or 128")
+            thr = os.environ.get("SDK_SCORE_PLDA_THRESHOLD", "0")
+            try:
+                self.score_plda_threshold = float(thr)
+            except ValueError:
+                raise ValueError(f"SDK_SCORE_PLDA_THRESHOLD={thr!r}: a float on the log-likelihood-ratio scale expected") from None
+            if self.score_plda_threshold != self.score_plda_threshold:
+                raise ValueError("SDK_SCORE_PLDA_THRESHOLD is NaN: a float on the log-likelihood-ratio scale expected")
+            cnt = os.environ.get("SDK_SCORE_PLDA_COUNT", "1").strip()
+            if cnt not in ("0", "1"):
+                raise ValueError(f"SDK_SCORE_PLDA_COUNT={cnt!r}: 1 (a speaker's count is the number of their enrolled embeddings) or 0 (it is 1)")
+            self.score_plda_paths, self.score_plda_dim, self.score_plda_count = (tpath, ppath), int(dim), cnt == "1"
 
     # ---- metadata (base.py:25-105) -------------------------------------------------------
     @property
@@ -780,6 +820,86 @@ class Backend(EmbeddingBackend):
             raise ValueError("score_windows_snorm: no cohort configured (SDK_COHORT)")
         return tuple(t.cpu().numpy() for t in self._snorm_enqueue(E, batch, k))
 
+    # ---- PLDA log-likelihood-ratio scoring (plda_score.py) ------------------------------------------------
+    @property
+    def plda_scoring(self) -> bool:
+        """Whether identify / verify decide on the PLDA log-likelihood ratio (SDK_SCORE_PLDA_TRANSFORM and SDK_SCORE_PLDA are set)."""
+        return self.score_plda_paths is not None
+
+    def score_plda(self):
+        """The configured scoring model (plda.Plda; None without SDK_SCORE_PLDA*), loaded on first use.  A model whose d_in is not this
+        family's embedding_dim is refused."""
+        if self.score_plda_paths and self._score_plda is None:
+            import hashlib
+            from .plda import load_plda
+            model = load_plda(self.score_plda_paths[0], self.score_plda_paths[1], self.score_plda_dim)
+            if model.d_in != int(self.embedding_dim):
+                raise ValueError(f"SDK_SCORE_PLDA_TRANSFORM={self.score_plda_paths[0]}: the PLDA model takes d_in={model.d_in}, the {self.model!r} family "
+                                 f"(SDK_MODEL) embeds into embedding_dim={int(self.embedding_dim)}: train one in this space (Backend.train_plda)")
+            h = hashlib.sha256(np.asarray([model.lda_dim], dtype=np.int64).tobytes())
+            for a in (model.mean1, model.lda, model.mean2, model.mu, model.tr, model.psi):
+                h.update(np.asarray(a.shape, dtype=np.int64).tobytes())
+                h.update(a.tobytes())
+            self._score_plda = (model, h.hexdigest()[:16])
+        return self._score_plda[0] if self._score_plda else None
+
+    def _plda_rows(self, E):
+        """fp32 unit rows [n, d] (device) -> their float64 rows [n, D] in the scoring model's space (plda_transform, 65 536 rows per call)."""
+        import torch
+        eng, model = self.engine(), self.score_plda()
+        E = E.contiguous()
+        n, step = int(E.shape[0]), 65536
+        if n == 0:
+            return torch.empty((0, model.lda_dim), dtype=torch.float64, device=E.device)
+        parts = [eng.plda_transform(E, torch.arange(a, min(n, a + step), dtype=torch.int32, device=E.device), model, check_rows=False)
+                 for a in range(0, n, step)]
+        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+
+    def speaker_table(self, batch):
+        """The speaker table of a ProfileBatch under the scoring model -> (G, r device tensors, speakers, first rows, counts): its rows
+        grouped by speaker_id (plda_score.group_speakers), transformed and pooled on the device (Engine.plda_enroll), computed once per batch
+        object and cached on it, keyed by the model's content digest and the count mode."""
+        import torch
+        from .plda_score import group_speakers
+        eng, model = self.engine(), self.score_plda()
+        key = (self._score_plda[1], self.score_plda_count)
+        got = getattr(batch, "_plda", None)
+        if got is not None and got[0] is eng and got[1] == key:
+            return got[2]
+        group, speakers, first, counts = group_speakers(batch.speaker_ids)
+        n_eff = counts.astype(np.float64) if self.score_plda_count else np.ones(len(speakers), np.float64)
+        Xp = self._plda_rows(self.profile_tensors(batch)[0])
+        G, r, _ = eng.plda_enroll(Xp, torch.from_numpy(group).to(eng.device), torch.from_numpy(n_eff).to(eng.device),
+                                  model.device_arrays(eng.device)["Phi"])          # group_speakers' labels lie in [0, S): status is not read
+        out = (G, r, speakers, first, counts)
+        batch._plda = (eng, key, out)
+        return out
+
+    def _plda_enqueue(self, E, batch, k: int = 1):
+        """PLDA top-k of embedded windows against a ProfileBatch's speakers -> (idx, llr) device tensors; nothing waits."""
+        import torch
+        eng = self.engine()
+        G, r = self.speaker_table(batch)[:2]
+        X = self._plda_rows(E)
+        k = max(1, min(int(k), int(G.shape[0]), 4))
+        n, step = int(X.shape[0]), 65536
+        if n <= step:
+            return eng.plda_score_topk(X, G, r, k=k)
+        parts = [eng.plda_score_topk(X[a:a + step], G, r, k=k) for a in range(0, n, step)]
+        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+
+    def score_windows_plda(self, E, batch, k: int = 1):
+        """score_windows on the PLDA scale: E [N, d] fp32 unit rows (device) -> (idx [N, k] int32: SPEAKER indices in the order of
+        plda_score.group_speakers(batch.speaker_ids), llr [N, k] float64) on the host; needs a configured scoring model."""
+        if self.score_plda() is None:
+            raise ValueError("score_windows_plda: no scoring model configured (SDK_SCORE_PLDA_TRANSFORM and SDK_SCORE_PLDA)")
+        return tuple(t.cpu().numpy() for t in self._plda_enqueue(E, batch, k))
+
+    def _aggregate_plda(self, idx, llr, spans, batch):
+        from .plda_score import aggregate_matches_plda
+        _, _, speakers, first, counts = self.speaker_table(batch)
+        return aggregate_matches_plda(idx, llr, spans, speakers, [batch.embedding_ids[int(p)] for p in first], counts, self.score_plda_threshold)
+
     def score_windows(self, E, Eb, re, batch, k: int = 1):
         """Device scoring of embedded windows against a ProfileBatch -> (idx, score) on host."""
         eng = self.engine()
@@ -805,11 +925,19 @@ class Backend(EmbeddingBackend):
 
     def identify_speaker(self, audio_path: Path, candidates: List[Dict[str, Any]], threshold: float = 0.354) -> List[Dict[str, Any]]:
         """With a cohort configured (SDK_COHORT) a window's winner is its normalised top-1 and it votes when z >= SDK_COHORT_THRESHOLD: the raw
-        `threshold` is NOT applied.  The rows then carry norm_score and are sorted by it (aggregate_matches_snorm)."""
+        `threshold` is NOT applied.  The rows then carry norm_score and are sorted by it (aggregate_matches_snorm).
+        With a scoring PLDA configured (SDK_SCORE_PLDA*) a window's winner is the SPEAKER of its largest log-likelihood ratio and it votes
+        when llr >= SDK_SCORE_PLDA_THRESHOLD: the raw `threshold` is NOT applied.  The rows then carry llr (uncalibrated) and n_embeddings,
+        similarity = confidence = 1 / (1 + exp(-llr)), embedding_id is the speaker's first embedding, and they are sorted by llr
+        (plda_score.aggregate_matches_plda)."""
         batch = self._load_candidates(candidates)
         if len(batch) == 0:
             return []
         samples, starts, W, spans = self._windows(audio_path, None)
+        if self.plda_scoring:
+            E, _, _ = self.embed_tables(samples, {W: starts})[W]
+            idx, llr = self.score_windows_plda(E, batch)
+            return self._aggregate_plda(idx[:, 0], llr[:, 0], spans, batch)
         if self.cohort_path:
             E, _, _ = self.embed_tables(samples, {W: starts})[W]
             idx, z, raw = self.score_windows_snorm(E, batch)
@@ -827,10 +955,18 @@ class Backend(EmbeddingBackend):
         loaded and uploaded once; every recording is decoded, handed to the staging slots and its kernels enqueued WITHOUT waiting for the previous
         one - the upload of recording i + 1 runs under the forward pass of recording i (csrc/ingest.hip) - and the host synchronises once, at the end.
         Row lists equal identify_speaker's, recording by recording (tests/test_gpu_ingest.py).  With a cohort configured (SDK_COHORT) the
-        decision is identify_speaker's normalised one and the raw `threshold` is NOT applied."""
+        decision is identify_speaker's normalised one and the raw `threshold` is NOT applied; with a scoring PLDA (SDK_SCORE_PLDA*) it is
+        identify_speaker's log-likelihood-ratio one, and the raw `threshold` is NOT applied either."""
         batch = self._load_candidates(candidates)
         if len(batch) == 0:
             return [[] for _ in audio_paths]
+        if self.plda_scoring:
+            pending = []
+            for path in audio_paths:
+                samples, starts, W, spans = self._windows(path, None)
+                E, _, _ = self.embed_tables(samples, {W: starts})[W]
+                pending.append((self._plda_enqueue(E, batch), spans))                # enqueued; nothing waits here
+            return [self._aggregate_plda(i.cpu().numpy()[:, 0], l.cpu().numpy()[:, 0], spans, batch) for (i, l), spans in pending]
         if self.cohort_path:
             pending = []
             for path in audio_paths:
@@ -859,7 +995,9 @@ class Backend(EmbeddingBackend):
     # ---- a3: verify - the CLI reads result['confidence'] (speaker_detection:1173-1174) ---------
     def verify_speaker(self, audio_path: Path, speaker_profile: Dict[str, Any], threshold: float = 0.354) -> Dict[str, Any]:
         """With a cohort configured (SDK_COHORT) the match is identify_speaker's normalised decision (the raw `threshold` is NOT applied) and
-        the result carries norm_score; similarity and confidence stay the mean raw cosine."""
+        the result carries norm_score; similarity and confidence stay the mean raw cosine.  With a scoring PLDA configured (SDK_SCORE_PLDA*)
+        the match is identify_speaker's log-likelihood-ratio decision (the raw `threshold` is NOT applied), the result carries llr, and
+        similarity and confidence are 1 / (1 + exp(-llr))."""
         hits = self.identify_speaker(audio_path, [speaker_profile], threshold)
         if not hits:
             return {"match": False, "similarity": 0.0, "confidence": 0.0, "embedding_id": None}
@@ -867,6 +1005,8 @@ class Backend(EmbeddingBackend):
         out = {"match": True, "similarity": h["similarity"], "confidence": h["similarity"], "embedding_id": h.get("embedding_id")}
         if "norm_score" in h:
             out["norm_score"] = h["norm_score"]
+        if "llr" in h:
+            out["llr"] = h["llr"]
         return out
 
 

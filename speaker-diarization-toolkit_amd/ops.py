@@ -1157,6 +1157,83 @@ class Engine:
                                         _stream()), "sdk_plda_project")
         return X2
 
+    # ---- PLDA log-likelihood-ratio scoring (plda_score.py; csrc/plda_score.hip): nothing here synchronises with the host
+    @staticmethod
+    def _plda_f64(who: str, name: str, t, shape) -> None:
+        """A float64 argument of the PLDA scoring calls: a contiguous device tensor of exactly `shape` (None: any extent)."""
+        want = "[" + ", ".join("*" if s is None else str(s) for s in shape) + "]"
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.dim() != len(shape) or not t.is_contiguous() or not t.is_cuda \
+                or any(s is not None and int(t.shape[i]) != s for i, s in enumerate(shape)):
+            raise ValueError(f"{who}: {name} must be a contiguous float64 {want} device tensor, got "
+                             f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__} {getattr(t, 'dtype', '')}")
+
+    def plda_enroll(self, Xp: torch.Tensor, group: torch.Tensor, n_eff: torch.Tensor, Phi: torch.Tensor):
+        """Xp [P, D] float64 transformed profile rows (plda_transform; D 64 or 128, P <= 2^22), group [P] int32 (the speaker index of every
+        row, in any order), n_eff [S] float64 (1 <= S <= 2^20), Phi [D] float64, all on the device -> (G [S, 2 D], r [S], status [1] int32)
+        on the device: the speaker table of plda_score.py (sdk_plda_enroll).  A label outside [0, S) belongs to no speaker and sets status
+        bit 1; a speaker without a row or with an n_eff that is not a finite number above 0 gets r = NaN.  The caller reads status."""
+        self._plda_f64("plda_enroll", "Xp", Xp, (None, None))
+        P, D = int(Xp.shape[0]), int(Xp.shape[1])
+        if D not in (64, 128):
+            raise ValueError(f"plda_enroll: D={D} not supported (64 or 128)")
+        if P > 1 << 22:
+            raise ValueError(f"plda_enroll: P={P} rows (0 .. 2^22)")
+        if not isinstance(group, torch.Tensor) or group.dtype != torch.int32 or tuple(group.shape) != (P,) or not group.is_contiguous() or not group.is_cuda:
+            raise ValueError(f"plda_enroll: group must be a contiguous int32 [{P}] device tensor, got "
+                             f"{tuple(group.shape) if isinstance(group, torch.Tensor) else type(group).__name__} {getattr(group, 'dtype', '')}")
+        self._plda_f64("plda_enroll", "n_eff", n_eff, (None,))
+        S = int(n_eff.shape[0])
+        if S < 1 or S > 1 << 20:
+            raise ValueError(f"plda_enroll: S={S} speakers (1 .. 2^20)")
+        self._plda_f64("plda_enroll", "Phi", Phi, (D,))
+        nbytes = int(self.lib.sdk_plda_enroll_workspace_bytes(P, S))
+        if nbytes == 0:
+            raise SdkError(f"sdk_plda_enroll_workspace_bytes: {self.lib.sdk_last_error().decode()}")
+        dev = Xp.device
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        G = torch.empty((S, 2 * D), dtype=torch.float64, device=dev)
+        r = torch.empty((S,), dtype=torch.float64, device=dev)
+        status = torch.empty((1,), dtype=torch.int32, device=dev)
+        check(self.lib.sdk_plda_enroll(self.ctx, Xp.data_ptr() if P else None, group.data_ptr() if P else None, P, D, n_eff.data_ptr(),
+                                       Phi.data_ptr(), S, G.data_ptr(), r.data_ptr(), status.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+              "sdk_plda_enroll")
+        return G, r, status
+
+    def plda_score_topk(self, X: torch.Tensor, G: torch.Tensor, r: torch.Tensor, k: int = 1, scores: bool = False,
+                        ws: Optional[torch.Tensor] = None):
+        """X [N, D] float64 transformed windows (N <= 65 536), (G [S, 2 D], r [S]) a speaker table of plda_enroll -> (idx [N, k] int32,
+        score [N, k] float64) and, with scores=True, the whole matrix [N, S]: per window the k <= 4 largest log-likelihood ratios
+        r_s + sum_d x_d G[s, d] + x_d^2 G[s, D + d]; ties to the lower speaker, a NaN never taken, a slot without a candidate holds
+        (-1, 0); with k > S the columns S .. k - 1 are not written (sdk_plda_score_topk).  ws: a uint8 device tensor to use as the workspace
+        (default: one of sdk_plda_score_workspace_bytes(N, S, k) bytes is allocated)."""
+        self._plda_f64("plda_score_topk", "X", X, (None, None))
+        N, D = int(X.shape[0]), int(X.shape[1])
+        if D not in (64, 128):
+            raise ValueError(f"plda_score_topk: D={D} not supported (64 or 128)")
+        if N > 65536:
+            raise ValueError(f"plda_score_topk: N={N} windows (0 .. 65536)")
+        self._plda_f64("plda_score_topk", "G", G, (None, 2 * D))
+        S, k = int(G.shape[0]), int(k)
+        if S < 1 or S > 1 << 20:
+            raise ValueError(f"plda_score_topk: S={S} speakers (1 .. 2^20)")
+        self._plda_f64("plda_score_topk", "r", r, (S,))
+        if k < 1 or k > 4:
+            raise ValueError(f"plda_score_topk: k={k} (1 .. 4)")
+        nbytes = int(self.lib.sdk_plda_score_workspace_bytes(N, S, k))
+        if nbytes == 0:
+            raise SdkError(f"sdk_plda_score_workspace_bytes: {self.lib.sdk_last_error().decode()}")
+        dev = X.device
+        if ws is None:
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        elif ws.dtype != torch.uint8 or ws.dim() != 1 or not ws.is_cuda or not ws.is_contiguous():
+            raise ValueError(f"plda_score_topk: ws must be a contiguous uint8 device tensor, got {tuple(ws.shape)} {ws.dtype}")
+        idx = torch.empty((N, k), dtype=torch.int32, device=dev)
+        sc = torch.empty((N, k), dtype=torch.float64, device=dev)
+        full = torch.empty((N, S), dtype=torch.float64, device=dev) if scores else None
+        check(self.lib.sdk_plda_score_topk(self.ctx, X.data_ptr(), N, D, G.data_ptr(), r.data_ptr(), S, k, idx.data_ptr(), sc.data_ptr(), _ptr(full),
+                                           ws.data_ptr(), ws.numel(), _stream()), "sdk_plda_score_topk")
+        return (idx, sc, full) if scores else (idx, sc)
+
     # ---- spherical k-means on unit rows (cluster.kmeans_cluster; csrc/kmeans.hip): the whole loop in one enqueue, nothing read back here
     def kmeans_rows(self, E: torch.Tensor, rows: torch.Tensor, k: int, max_iters: int = 20, check_rows: bool = True):
         """E [R, d] fp32 unit rows, rows [n] int32 ascending (device), 1 <= k <= min(n, 64) -> (labels [n] int32 in [0, k), not canonical,
