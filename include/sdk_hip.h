@@ -32,7 +32,8 @@
  *     sdk_l2norm                                                                                        k3
  *     sdk_affinity_workspace_bytes  sdk_affinity_topk                                                   k4
  *     sdk_affinity_matvec_workspace_bytes  sdk_affinity_matvec  sdk_rows_gram_workspace_bytes  sdk_rows_gram
- *     sdk_rows_apply  sdk_chol_inverse  sdk_rows_unit  sdk_kmeans_mindist  sdk_kmeans_assign            k6 (driven by cluster.py)
+ *     sdk_rows_apply  sdk_chol_inverse  sdk_sym_eigh  sdk_rows_unit  sdk_kmeans_mindist  sdk_kmeans_assign      k6 (driven by cluster.py;
+ *                                                                                                       sdk_sym_eigh by sdk_laplacian_topk)
  *     sdk_centroid_linkage_workspace_bytes  sdk_centroid_linkage                                    k6 threshold path (cluster.agglomerative_cluster)
  *     sdk_linked_linkage_workspace_bytes  sdk_linked_linkage                                        speakers across recordings: constrained, early-stopping
  *                                                                                                       centroid linkage (cluster.link_rows, diarize.link_speakers)
@@ -857,8 +858,13 @@ int sdk_affinity_topk(sdk_ctx* ctx, const float* E, const uint16_t* Eb, const fl
  *                         "chol_shift_ppb" > 0: shifted CholeskyQR (G + s I, s = that fraction, in 1e-9, of the mean diagonal entry) for
  *                         nearly rank-deficient blocks; follow it with unshifted passes (cluster.spectral_cluster retries once that way
  *                         when the flag was raised - over-clustered or near-duplicate inputs - before it reports a lost rank)
+ *   sdk_sym_eigh        : the Ritz step of sdk_laplacian_topk alone: all eigenpairs of H = (G + G^T)/2, G [k,k] fp32 row-major, 1 <= k <= 32
+ *                         (anything else, or a null pointer, is refused with a message and launches nothing).  Cyclic Jacobi in float64 by one
+ *                         lane, rounded to fp32 once at the end; never synchronises with the host.  lam DEVICE [k] descending, equal eigenvalues
+ *                         in ascending order of the diagonal position they converged at (a diagonal G: its own index); Q DEVICE [k,k] row-major,
+ *                         column c = the eigenvector of lam[c], unit length, its largest-magnitude component (the first of equals) positive.
  *   sdk_rows_unit       : rows scaled to unit length
- *   sdk_kmeans_mindist  : d2[i] = (first ? : min(d2[i],)) |R[i] - centre|^2      (maximin initialisation)
+ *   sdk_kmeans_mindist : d2[i] = (first ? : min(d2[i],)) |R[i] - centre|^2      (maximin initialisation)
  *   sdk_kmeans_assign   : label[i] = nearest of kc centres (ties -> lowest), dist2, optional per-256-row-block
  *                         partial sums [nblk, kc, k] and counts [nblk, kc]
  */
@@ -893,6 +899,7 @@ size_t sdk_rows_gram_workspace_bytes(int n, int k);
 int sdk_rows_gram(sdk_ctx* ctx, const float* X, const float* Y, int n, int k, float* G, void* ws, size_t ws_bytes, void* stream);
 int sdk_rows_apply(sdk_ctx* ctx, const float* X, const float* R, const float* scale, int n, int k, float* Y, void* stream);
 int sdk_chol_inverse(sdk_ctx* ctx, const float* G, int k, float* Rinv, int32_t* not_spd, void* stream);
+int sdk_sym_eigh(sdk_ctx* ctx, const float* G, int k, float* Q, float* lam, void* stream);
 int sdk_rows_unit(sdk_ctx* ctx, const float* X, int n, int k, float* Y, void* stream);
 int sdk_kmeans_mindist(sdk_ctx* ctx, const float* R, int n, int k, const float* centre, float* d2, int first, void* stream);
 int sdk_kmeans_assign(sdk_ctx* ctx, const float* R, int n, int k, const float* centres, int kc, int32_t* label,

@@ -135,9 +135,11 @@ __global__ __launch_bounds__(64) void jacobi_eigh_kernel(const float* __restrict
   }
   int order[KV];
   for (int i = 0; i < k; ++i) order[i] = i;
-  for (int i = 0; i < k; ++i)                                  // selection sort, descending, ties -> lower index first
-    for (int j = i + 1; j < k; ++j)
-      if (A[order[j]][order[j]] > A[order[i]][order[i]]) { const int t = order[i]; order[i] = order[j]; order[j] = t; }
+  for (int i = 0; i < k; ++i)                                  // selection sort, descending, ties -> lower index first (the swaps move
+    for (int j = i + 1; j < k; ++j) {                          // equal entries past each other, so the index is part of the comparison)
+      const double aj = A[order[j]][order[j]], ai = A[order[i]][order[i]];
+      if (aj > ai || (aj == ai && order[j] < order[i])) { const int t = order[i]; order[i] = order[j]; order[j] = t; }
+    }
   for (int c = 0; c < k; ++c) {
     const int src = order[c];
     lam[c] = (float)A[src][src];
@@ -224,6 +226,15 @@ extern "C" int sdk_allgather_direct(sdk_ctx* ctx, const void* shard, void* out, 
     sdk_set_error("sdk_allgather_direct: RCCL error %d (%s)", rc ? rc : rc_end, g_rccl.errstr ? g_rccl.errstr(rc ? rc : rc_end) : "?");
     return 1;
   }
+  return 0;
+}
+
+// The Ritz step of sdk_laplacian_topk on its own (the same kernel, the same launch), so that it can be held to a float64 reference alone.
+extern "C" int sdk_sym_eigh(sdk_ctx* ctx, const float* G, int k, float* Q, float* lam, void* stream) {
+  SDK_REQUIRE(ctx && G && Q && lam, "sdk_sym_eigh: null argument");
+  SDK_REQUIRE(k >= 1 && k <= KV, "sdk_sym_eigh: k=%d must be in [1, %d]", k, KV);
+  hipLaunchKernelGGL(jacobi_eigh_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, G, k, Q, lam);
+  SDK_LAUNCH_CHECK();
   return 0;
 }
 

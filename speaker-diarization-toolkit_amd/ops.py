@@ -762,10 +762,33 @@ class Engine:
         """The C-ABI spectral driver for non-Python hosts (sdk_laplacian_topk): top-k Ritz pairs of D^-1/2 A D^-1/2 by subspace iteration,
         never leaving the stream.  V0 [rows, k] fp32 start block (not modified) -> (U [rows, k], eigenvalues [k] device, descending).
         comm: an ncclComm_t as an integer (or None on one GPU)."""
-        _need(Eb_all, torch.bfloat16, "Eb_all"); _need(V0, torch.float32, "V0")
-        N = Eb_all.shape[0]
+        what = "laplacian_topk"
+        # the C entry reads Eb_all as [N, 192] and V as [rows, k] through bare pointers: everything it cannot see is refused here, before
+        # the scratch allocation and any launch
+        _thin(Eb_all, "Eb_all", what, dtype=torch.bfloat16, contiguous=False)
+        if Eb_all.dim() != 2 or Eb_all.shape[0] < 1 or Eb_all.shape[1] != 192:
+            raise ValueError(f"{what}: Eb_all must be [N, 192] with N >= 1 (the width the mat-vec kernel is built for), got {list(Eb_all.shape)}")
+        _thin(Eb_all, "Eb_all", what, dtype=torch.bfloat16)
+        N = int(Eb_all.shape[0])
+        if not (isinstance(row0, (int, np.integer)) and row0 >= 0):
+            raise ValueError(f"{what}: row0 = {row0!r} must be an integer >= 0")
         rows = N - row0 if rows is None else rows
-        k = V0.shape[1]
+        if not (isinstance(rows, (int, np.integer)) and rows >= 1):
+            raise ValueError(f"{what}: rows = {rows!r} must be an integer >= 1 (row0 = {row0}, N = {N})")
+        if row0 + rows > N:
+            raise ValueError(f"{what}: row0 + rows = {row0 + rows} exceeds the N = {N} rows of Eb_all")
+        _thin(V0, "V0", what, contiguous=False)
+        if V0.dim() != 2 or not 1 <= V0.shape[1] <= THIN_MAX:
+            raise ValueError(f"{what}: V0 must be [rows, k] with k in 1..{THIN_MAX}, got {list(V0.shape)}")
+        if V0.shape[0] != rows:
+            raise ValueError(f"{what}: V0 must have rows = {rows} rows (one per owned row of Eb_all), got {list(V0.shape)}")
+        if not (isinstance(n_iter, (int, np.integer)) and n_iter >= 0):
+            raise ValueError(f"{what}: n_iter = {n_iter!r} must be an integer >= 0")
+        if flag is not None:
+            _thin(flag, "flag", what, dtype=torch.int32)
+            if flag.numel() != 1:
+                raise ValueError(f"{what}: flag must hold one int32, got shape {list(flag.shape)}")
+        k = int(V0.shape[1])
         V = V0.contiguous().clone()
         lam = torch.empty((k,), dtype=torch.float32, device=self.device)
         ws = self._scratch_bytes("laplacian", self.lib.sdk_laplacian_topk_workspace_bytes(N, k))
@@ -802,6 +825,22 @@ class Engine:
         Rinv = torch.empty((k, k), dtype=torch.float32, device=self.device)
         check(self.lib.sdk_chol_inverse(self.ctx, G.contiguous().data_ptr(), k, Rinv.data_ptr(), _ptr(flag), _stream()), "sdk_chol_inverse")
         return Rinv
+
+    def sym_eigh(self, G):
+        """(Q [k, k], lam [k]) fp32 on the device: every eigenpair of (G + G^T) / 2 for a contiguous fp32 G [k, k], 1 <= k <= 32 - the Ritz
+        step of laplacian_topk alone (sdk_sym_eigh: cyclic Jacobi in float64, stays on the stream).  lam descending, equal eigenvalues in
+        ascending order of their diagonal position; column c of Q belongs to lam[c], with its largest-magnitude component positive."""
+        _thin(G, "G", "sym_eigh", contiguous=False)
+        if G.dim() != 2 or G.shape[0] != G.shape[1]:
+            raise ValueError(f"sym_eigh: G must be square [k, k], got {list(G.shape)}")
+        k = int(G.shape[0])
+        if not 1 <= k <= THIN_MAX:
+            raise ValueError(f"sym_eigh: k = {k} (the order of G) must be in 1..{THIN_MAX}")
+        _thin(G, "G", "sym_eigh")
+        Q = torch.empty((k, k), dtype=torch.float32, device=self.device)
+        lam = torch.empty((k,), dtype=torch.float32, device=self.device)
+        check(self.lib.sdk_sym_eigh(self.ctx, G.data_ptr(), k, Q.data_ptr(), lam.data_ptr(), _stream()), "sdk_sym_eigh")
+        return Q, lam
 
     def rows_unit(self, X):
         """The rows of a contiguous fp32 [n, k] block scaled to unit length (a row shorter than 1e-12 is divided by 1e-12: a zero row stays zero)."""
