@@ -49,6 +49,8 @@
  *     sdk_cohort_stats_workspace_bytes  sdk_cohort_stats  sdk_affinity_topk_snorm                       adaptive score normalisation (snorm.py)
  *     sdk_plda_enroll_workspace_bytes  sdk_plda_enroll  sdk_plda_score_workspace_bytes  sdk_plda_score_topk    PLDA log-likelihood-ratio scoring of
  *                                                                                                       windows against enrolled speakers (plda_score.py)
+ *     sdk_trial_hist                                                                                    verification trials: two-class score histograms for EER, minDCF
+ *                                                                                                       and the DET curve (trials.py)
  *     sdk_kmeans_rows_workspace_bytes  sdk_kmeans_rows                                                  spherical k-means on unit rows (cluster.kmeans_cluster)
  *     sdk_stream_state_bytes  sdk_stream_reset  sdk_stream_step  sdk_stream_flush  sdk_stream_centroids streaming diarization: online speaker tracking (stream.py)
  * BUILDING BLOCKS AND KNOBS - exported for the parity tests and the A/B tools, free to change between rounds, not for binding:
@@ -71,7 +73,7 @@
 extern "C" {
 #endif
 
-#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5); still 4 with sdk_cohort_stats* and sdk_affinity_topk_snorm, and with sdk_ecapa_forward_masked, sdk_ecapa_masked_workspace_bytes, sdk_asp_stats_masked_fmt and sdk_asp_pool_masked_fmt, and with sdk_score_reference, sdk_score_cooccur and sdk_score_map, and with sdk_plda_enroll* and sdk_plda_score*: new exports only, no struct or existing signature changes, no caller of version 4 breaks */
+#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5); still 4 with sdk_cohort_stats* and sdk_affinity_topk_snorm, and with sdk_ecapa_forward_masked, sdk_ecapa_masked_workspace_bytes, sdk_asp_stats_masked_fmt and sdk_asp_pool_masked_fmt, and with sdk_score_reference, sdk_score_cooccur and sdk_score_map, and with sdk_plda_enroll* and sdk_plda_score*, and with sdk_trial_hist: new exports only, no struct or existing signature changes, no caller of version 4 breaks */
 
 typedef struct sdk_ctx sdk_ctx;
 
@@ -787,6 +789,24 @@ int sdk_plda_enroll(sdk_ctx* ctx, const double* Xp, const int32_t* group, int P,
 size_t sdk_plda_score_workspace_bytes(int N, int S, int k);
 int sdk_plda_score_topk(sdk_ctx* ctx, const double* X, int N, int D, const double* G, const double* r, int S, int k, int32_t* idx, double* score,
                         double* scores, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- verification trials: every (test row i < N, model row j < M) pair scored, classed and binned; the score matrix is never written (trials.py
+ *      states the rule; csrc/trials.hip).  A [N][K], B [M][K], r [M] float64, K a multiple of 16 in 16 .. 512, 1 <= N, M <= 2^20; la, sa [N] and
+ *      lb, sb [M] int32 labels and sessions.
+ *          s(i, j) = r[j] + sum_k A[i][k] B[j][k]   on the f64 MFMA, one chain in one order per element
+ *          t = (s - lo) * scale   one float64 subtraction, then one float64 multiplication (no FMA); scale = 2^24 / (hi - lo), formed by the caller
+ *          NaN -> nan;  t < 0 -> below;  t >= 2^24 (+inf included) -> above;  else q = floor(t)
+ *      Trial (i, j) is EXCLUDED when la[i] < 0 or lb[j] < 0 or (sa[i] >= 0 and sa[i] == sb[j]); else its class is 1 (target) when la[i] == lb[j],
+ *      else 0.  With bin = (q >> shift) - base a trial that is neither excluded nor nan is counted exactly once: in hist[class][bin] when
+ *      0 <= bin < 4096, in under[class] when (q >> shift) < base or below, in over[class] otherwise (above included).
+ *      out: 8199 uint64 on the device - hist[2][4096], under[2], over[2], nan[2], excluded[1] - zeroed by the call in stream order.
+ *      max_blocks: 0 = the default grid, else a cap on the number of (persistent) workgroups; the counters do not depend on it.  Integer
+ *      counting only after the product: bit-identical run to run.  Refused (status 2, nothing launched): K, N, M, shift (0 .. 24), base
+ *      (0 .. 2^24) or max_blocks (>= 0) outside their limits, a lo that is not finite, a scale that is not finite and above 0 (lo >= hi), a null
+ *      pointer, A or B not 16-byte aligned.  sdk_set_option "trials_no_hist" 1 (bench knob, tools/trials_bench.py): the kernel without its LDS
+ *      atomics; the in-range trials of a class then land in its bin 0. */
+int sdk_trial_hist(sdk_ctx* ctx, const double* A, int N, const double* B, const double* r, int M, int K, const int32_t* la, const int32_t* sa,
+                   const int32_t* lb, const int32_t* sb, double lo, double scale, int shift, int base, int max_blocks, uint64_t* out, void* stream);
 
 /* ---- audio conversion to the AudioProfile: replaces the ffmpeg subprocess the reference's backends
  *      run before upload (audio_profiles.py:70-100 `format_ffmpeg_args`; speechmatics_backend.py:231-281).

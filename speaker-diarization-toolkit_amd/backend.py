@@ -52,7 +52,8 @@ Environment:
                       Needs the torch engine (SDK_NO_TORCH=1 is refused); refused together with SDK_COHORT.  score_ranges stays on the cosine
   SDK_SCORE_PLDA_DIM  the PLDA dimensions kept, 64 or 128 (default 128)
   SDK_SCORE_PLDA_THRESHOLD  the vote threshold on the log-likelihood-ratio scale (a float, default 0: the point of equal likelihood under the
-                      model).  The scale is UNCALIBRATED: no trained weights are on hand to tune an operating point
+                      model).  The scale is UNCALIBRATED: 0 is not a tuned operating point.  Backend.tune_verification returns the thresholds
+                      at the equal error rate and at the minimum detection cost of a labelled development set (trials.py)
   SDK_SCORE_PLDA_COUNT  1 (default): a speaker's effective count n_s is the number of their enrolled embeddings ("by the book") / 0: n_s = 1
 """
 from __future__ import annotations
@@ -644,6 +645,76 @@ class Backend(EmbeddingBackend):
         finally:
             if dz.eng.precision != prec:
                 dz.eng.set_precision(prec)                       # the front end's format goes back to the selected family's contract
+
+    def score_verification(self, audio_paths, speaker_ids, candidates, score_range=None, p_target: float = 0.01, c_miss: float = 1.0,
+                           c_fa: float = 1.0, max_refine: int = 8):
+        """How well the decision rule of identify_speaker / verify_speaker separates the enrolled speakers on labelled recordings ->
+        trials.VerificationResult (eer, eer_threshold, min_dcf, min_dcf_lower, min_dcf_exact, min_dcf_threshold, the DET arrays, the counts).
+        audio_paths: recordings of ONE speaker each; speaker_ids: that speaker's id per recording as the candidates' profiles name it (an id
+        no candidate has: the recording's windows are nontarget trials against everybody; None: they take part in no trial).
+        Every window of every recording, embedded on identify's path, is one test row (its session: the index of its recording); the model
+        rows are the candidates' enrolled embeddings (profile_tensors) under the cosine rule, their speakers (speaker_table) under the PLDA
+        rule (SDK_SCORE_PLDA*) - the rule identify_speaker would use.  Scored on the device in trials.py's integer form (the rule is stated
+        there; parity with outside toolkits is unpinned); score_range defaults to trials.COSINE_RANGE / trials.PLDA_RANGE.  With a cohort
+        configured (SDK_COHORT): ValueError - AS-norm trials are not built."""
+        import torch
+        from . import trials
+        if self.cohort_path:
+            raise ValueError("score_verification: AS-norm trials are not built: with SDK_COHORT set the decision is made on the normalised scale, "
+                             "which has no matrix form here; unset SDK_COHORT to evaluate the cosine or the PLDA rule")
+        if self.lite:
+            raise ValueError("score_verification: needs the torch engine; unset SDK_NO_TORCH")
+        audio_paths, speaker_ids = list(audio_paths), list(speaker_ids)
+        if len(audio_paths) != len(speaker_ids) or not audio_paths:
+            raise ValueError(f"score_verification: {len(audio_paths)} recordings with {len(speaker_ids)} speaker ids (one per recording, at least one)")
+        batch = self._load_candidates(candidates)
+        if len(batch) == 0:
+            raise ValueError("score_verification: no candidate embedding to score against")
+        eng = self.engine()
+        rows, la, sa = [], [], []
+        if self.plda_scoring:
+            G, r, speakers = self.speaker_table(batch)[:3]
+            index = {sid: s for s, sid in enumerate(speakers)}
+        else:
+            index: Dict[Any, int] = {}
+            for sid in batch.speaker_ids:
+                index.setdefault(sid, len(index))
+        known = len(index)
+        for f, (path, sid) in enumerate(zip(audio_paths, speaker_ids)):
+            samples, starts, W, _ = self._windows(Path(path), None)
+            E = self.embed_tables(samples, {W: starts})[W][0]
+            rows.append(E)
+            label = -1 if sid is None else index.setdefault(sid, len(index))
+            la += [label] * int(E.shape[0])
+            sa += [f] * int(E.shape[0])
+        E = torch.cat(rows, dim=0).contiguous()
+        dev = E.device
+        i32 = lambda a: torch.from_numpy(np.asarray(a, dtype=np.int32)).to(dev)        # noqa: E731
+        if self.plda_scoring:
+            X = self._plda_rows(E)
+            A, B, kind = torch.cat([X, X * X], dim=1).contiguous(), G, "plda"
+            lb = np.arange(known)
+        else:
+            A, B, kind = E.double(), self.profile_tensors(batch)[0].double().contiguous(), "cosine"
+            r = torch.zeros((int(B.shape[0]),), dtype=torch.float64, device=dev)
+            lb = [index[sid] for sid in batch.speaker_ids]
+        sb = np.full(len(lb), -1)
+        return trials.evaluate_scores(eng, A, B, r, i32(la), i32(sa), i32(lb), i32(sb), kind, score_range, p_target, c_miss, c_fa, max_refine)
+
+    def tune_verification(self, audio_paths, speaker_ids, candidates, score_range=None, p_target: float = 0.01, c_miss: float = 1.0,
+                          c_fa: float = 1.0, max_refine: int = 8) -> Dict[str, Any]:
+        """The thresholds of the identify / verify decision on a labelled development set (the arguments of score_verification) ->
+        {"kind", "eer", "eer_threshold", "min_dcf", "min_dcf_threshold", "min_dcf_lower", "min_dcf_exact", "n_target", "n_nontarget", "n_nan",
+        "n_excluded", "n_test_rows", "n_model_rows", "score_range", "result": the VerificationResult}.  kind "cosine": the thresholds are
+        directly usable as threshold= of identify_speaker and verify_speaker.  The evaluation scores the float64 product of the fp32 unit
+        rows; identify's fp32 cosines of the same rows agree with it only to fp32 rounding (a few 1e-7), so a window within that of the
+        threshold may vote differently.  kind "plda": they are usable as SDK_SCORE_PLDA_THRESHOLD - the tuned operating point that the
+        uncalibrated default 0 is not."""
+        res = self.score_verification(audio_paths, speaker_ids, candidates, score_range, p_target, c_miss, c_fa, max_refine)
+        return {"kind": res.kind, "eer": res.eer, "eer_threshold": res.eer_threshold, "min_dcf": res.min_dcf, "min_dcf_threshold": res.min_dcf_threshold,
+                "min_dcf_lower": res.min_dcf_lower, "min_dcf_exact": res.min_dcf_exact, "n_target": res.n_target, "n_nontarget": res.n_nontarget,
+                "n_nan": res.n_nan, "n_excluded": res.n_excluded, "n_test_rows": res.test_rows, "n_model_rows": res.model_rows, "score_range": res.score_range,
+                "result": res}
 
     def train_plda(self, samples_or_paths, references, uris=None, out_dir=None, D0: int = 128, lda_dim: int = 128, n_iters: int = 10,
                    step_s: float = 1.0, speaker_key=None, logp=None):

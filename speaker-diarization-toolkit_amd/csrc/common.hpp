@@ -46,6 +46,7 @@ struct sdk_ctx {
   int chol_shift_ppb = 0;         // sdk_chol_inverse: shifted CholeskyQR, G + s I with s = this fraction (in 1e-9) of the mean diagonal entry (0 = off)
   bool ahc_distances_only = false;  // bench knob (tools/ahc_bench.py): sdk_centroid_linkage stops after the distance and nearest-neighbour kernels
   bool snorm_scores_only = false;   // bench knob (tools/snorm_bench.py): sdk_cohort_stats runs its scoring kernel only (mean and std are not written)
+  bool trials_no_hist = false;      // bench knob (tools/trials_bench.py): sdk_trial_hist without the epilogue's LDS atomics (in-range trials land in bin 0)
   int aff_variant = 0;            // A/B knob: coarse-pass plan of the row/column kernel (0 = cost model, 7 = range plan, 8 / 12 / 13 = block plan; affinity_rowcol.hip)
   std::vector<const void*> lds_optin;   // kernels of THIS context's device already opted in to > 64 KiB dynamic LDS
   std::vector<sdk_prof_rec> prof;

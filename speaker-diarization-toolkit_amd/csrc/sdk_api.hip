@@ -130,6 +130,7 @@ extern "C" int sdk_set_option(sdk_ctx* ctx, const char* name, int value) {
   if (strcmp(name, "chol_shift_ppb") == 0) { ctx->chol_shift_ppb = value < 0 ? 0 : value; return 0; }
   if (strcmp(name, "ahc_distances_only") == 0) { ctx->ahc_distances_only = value != 0; return 0; }
   if (strcmp(name, "snorm_scores_only") == 0) { ctx->snorm_scores_only = value != 0; return 0; }
+  if (strcmp(name, "trials_no_hist") == 0) { ctx->trials_no_hist = value != 0; return 0; }
   sdk_set_error("sdk_set_option: unknown option '%s'", name);
   return 2;
 }

@@ -1273,6 +1273,45 @@ class Engine:
                                            ws.data_ptr(), ws.numel(), _stream()), "sdk_plda_score_topk")
         return (idx, sc, full) if scores else (idx, sc)
 
+    # ---- verification trials (trials.py; csrc/trials.hip): nothing here synchronises with the host
+    def trial_hist(self, A: torch.Tensor, B: torch.Tensor, r: torch.Tensor, la: torch.Tensor, sa: torch.Tensor, lb: torch.Tensor,
+                   sb: torch.Tensor, lo: float, hi: float, shift: int = 12, base: int = 0, max_blocks: int = 0):
+        """One pass of the trial histogram: A [N, K] test rows, B [M, K] model rows, r [M] float64 (K a multiple of 16 in 16 .. 512,
+        1 <= N, M <= 2^20), la, sa [N] and lb, sb [M] int32 labels and sessions, all on the device -> (hist [2, 4096], under [2], over [2],
+        nan [2], excluded [1]) int64 device tensors, views of one array (sdk_trial_hist; trials.py states the rule).  The score
+        r[j] + A[i] . B[j] is cut into q = floor((s - lo) * scale), scale = 2^24 / (hi - lo) formed here in float64, and lands in bin
+        (q >> shift) - base.  max_blocks: 0 = the default grid, else a cap on the workgroups (the counts do not depend on it)."""
+        self._plda_f64("trial_hist", "A", A, (None, None))
+        N, K = int(A.shape[0]), int(A.shape[1])
+        if K < 16 or K > 512 or K % 16:
+            raise ValueError(f"trial_hist: K={K} not supported (a multiple of 16 in 16 .. 512)")
+        self._plda_f64("trial_hist", "B", B, (None, K))
+        M = int(B.shape[0])
+        if not (1 <= N <= 1 << 20 and 1 <= M <= 1 << 20):
+            raise ValueError(f"trial_hist: N={N} test rows, M={M} model rows (1 .. 2^20 each)")
+        self._plda_f64("trial_hist", "r", r, (M,))
+        for name, t, n in (("la", la, N), ("sa", sa, N), ("lb", lb, M), ("sb", sb, M)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f"trial_hist: {name} must be a contiguous int32 [{n}] device tensor, got "
+                                 f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__} {getattr(t, 'dtype', '')}")
+        lo, hi, shift, base, max_blocks = float(lo), float(hi), int(shift), int(base), int(max_blocks)
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+            raise ValueError(f"trial_hist: score range ({lo}, {hi}): finite lo < hi expected")
+        with np.errstate(over="ignore"):
+            scale = float(np.float64(16777216.0) / (np.float64(hi) - np.float64(lo)))
+        if not (np.isfinite(scale) and scale > 0.0):
+            raise ValueError(f"trial_hist: scale = 2^24 / (hi - lo) = {scale} is not a finite number above 0 (range ({lo}, {hi}))")
+        if shift < 0 or shift > 24:
+            raise ValueError(f"trial_hist: shift={shift} (0 .. 24)")
+        if base < 0 or base > 1 << 24:
+            raise ValueError(f"trial_hist: base={base} (0 .. 2^24)")
+        if max_blocks < 0:
+            raise ValueError(f"trial_hist: max_blocks={max_blocks} (0: the default grid, else a cap on the workgroups)")
+        out = torch.empty((2 * 4096 + 7,), dtype=torch.int64, device=A.device)           # uint64 counters, all below 2^40
+        check(self.lib.sdk_trial_hist(self.ctx, A.data_ptr(), N, B.data_ptr(), r.data_ptr(), M, K, la.data_ptr(), sa.data_ptr(), lb.data_ptr(),
+                                      sb.data_ptr(), lo, scale, shift, base, max_blocks, out.data_ptr(), _stream()), "sdk_trial_hist")
+        return out[:8192].view(2, 4096), out[8192:8194], out[8194:8196], out[8196:8198], out[8198:8199]
+
     # ---- spherical k-means on unit rows (cluster.kmeans_cluster; csrc/kmeans.hip): the whole loop in one enqueue, nothing read back here
     def kmeans_rows(self, E: torch.Tensor, rows: torch.Tensor, k: int, max_iters: int = 20, check_rows: bool = True):
         """E [R, d] fp32 unit rows, rows [n] int32 ascending (device), 1 <= k <= min(n, 64) -> (labels [n] int32 in [0, k), not canonical,

@@ -20,7 +20,8 @@ So the score matrix is one product of depth 2 D plus a constant per speaker: wit
   top-k    per window the k <= 4 largest llr, ties to the lowest speaker index; a NaN never wins; a slot without a candidate holds
            idx -1, score 0.
   decision a window votes for its top-1 speaker when llr >= threshold (a NaN does not).  The llr scale is UNCALIBRATED: 0 is the point of
-           equal likelihood under the model, not a tuned operating point.
+           equal likelihood under the model, not a tuned operating point.  Backend.tune_verification (trials.py) finds one on a labelled
+           development set: the thresholds at the equal error rate and at the minimum detection cost.
 
 On the device: ops.Engine.plda_enroll and ops.Engine.plda_score_topk (csrc/plda_score.hip: the product on the f64 MFMA, x^2 formed in the
 kernel, the speakers split across workgroups and merged in a fixed order).  This module holds the numpy float64 restatements for hosts that
