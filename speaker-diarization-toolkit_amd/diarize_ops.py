@@ -8,6 +8,7 @@ from typing import Optional
 
 import numpy as np
 
+from . import _args
 from .diarize_host import MAX_ASSIGN_DIM, N_LOCAL, _speaker_cap, global_frames
 
 VBX_HOST_READS = 7              # cluster.vbx_cluster waits for the device 7 times: the linkage's status and Z, the one read (n_iter, status, K), labels, pi, elbo, keep
@@ -23,28 +24,27 @@ def _native():
 
 
 def _check_dim(name: str, d: int):
-    if d < 64 or d % 64 or d > MAX_ASSIGN_DIM:
-        raise ValueError(f"{name}: d={d} not supported (a multiple of 64, at most {MAX_ASSIGN_DIM})")
+    _args.row_width(name, d, MAX_ASSIGN_DIM)
 
 
 def _check_rows(name: str, E, rows: Optional[int] = None):
-    if E.dim() != 2 or str(E.dtype) != "torch.float32" or not E.is_contiguous() or not E.is_cuda or (rows is not None and E.shape[0] != rows):
-        raise ValueError(f"{name}: E must be a contiguous fp32 [{'rows' if rows is None else rows}, d] device tensor, got {tuple(E.shape)} {E.dtype}")
-    _check_dim(name, int(E.shape[1]))
+    """E: contiguous fp32 [rows, d] on the device (rows None: any count), d a width the assignment kernels serve -> (rows, d)."""
+    return _args.rows(name, "E", E, n=rows, limit=MAX_ASSIGN_DIM)
 
 
-def _check_tensor(name: str, what: str, t, dtype: str, shape: tuple, min_rows: int = 0):
+def _check_tensor(name: str, what: str, t, dtype: str, shape: tuple, min_rows: int = 0, contiguous: bool = True):
     """The wrappers' check of cls (uint8 [C, F]), labels (int32 [C, 3]), info (int32 [C, 3, 4]), the centroids (float64 [K, d]) and the like:
-    contiguous, torch's dtype `dtype`, of `shape` (None: any size), at least min_rows rows."""
-    if str(t.dtype) != "torch." + dtype or t.dim() != len(shape) or any(n not in (None, m) for n, m in zip(shape, t.shape)) or not t.is_contiguous() or t.shape[0] < min_rows:
-        raise ValueError(f"{name}: {what} must be a contiguous {dtype} tensor of shape {shape} (None: any size; {min_rows} rows or more), got {tuple(t.shape)} {t.dtype}")
+    on the device, contiguous (contiguous=False: the wrapper passes t.contiguous() on), torch's dtype `dtype`, of `shape` (None: any size),
+    at least min_rows rows."""
+    if _args.tensor(name, what, t, dtype, shape, contiguous=contiguous).shape[0] < min_rows:
+        raise ValueError(f"{name}: {what} must hold {min_rows} rows or more, got {list(t.shape)}")
 
 
 def powerset_decode(eng, logp):
     """logp [C, F, 7] fp32 (device) -> cls [C, F] uint8 (device): sdk_powerset_decode."""
     torch, check, _stream = _native()
+    _check_tensor("powerset_decode", "logp", logp, "float32", (None, None, 7), contiguous=False)
     logp = logp.contiguous()
-    _check_tensor("powerset_decode", "logp", logp, "float32", (None, None, 7))
     cls = torch.empty(logp.shape[:2], dtype=torch.uint8, device=logp.device)
     check(eng.lib.sdk_powerset_decode(eng.ctx, logp.data_ptr(), logp.shape[0], logp.shape[1], cls.data_ptr(), _stream()), "sdk_powerset_decode")
     return cls
@@ -67,9 +67,9 @@ def diarize_reconstruct(eng, cls, starts, labels, K: int, n_samples: int, max_sp
     torch, check, _stream = _native()
     _check_tensor("diarize_reconstruct", "cls", cls, "uint8", (None, None))
     Cn, F = cls.shape
+    _check_tensor("diarize_reconstruct", "starts", starts, "int32", (Cn,), contiguous=False)
+    _check_tensor("diarize_reconstruct", "labels", labels, "int32", (Cn, N_LOCAL), contiguous=False)
     starts, labels = starts.contiguous(), labels.contiguous()
-    _check_tensor("diarize_reconstruct", "starts", starts, "int32", (Cn,))
-    _check_tensor("diarize_reconstruct", "labels", labels, "int32", (Cn, N_LOCAL))
     G = int(eng.lib.sdk_diarize_frames(int(n_samples)))
     count = torch.zeros((G,), dtype=torch.uint8, device=cls.device)
     speakers = torch.full((G, 2), -1, dtype=torch.int32, device=cls.device)
@@ -88,9 +88,9 @@ def diarize_centroids(eng, E, rows, labels, K: int, check_rows: bool = True):
     _check_rows("diarize_centroids", E)
     if int(K) < 1:
         raise ValueError(f"diarize_centroids: K={K} (at least 1)")
+    _check_tensor("diarize_centroids", "rows", rows, "int32", (None,), contiguous=False)
+    _check_tensor("diarize_centroids", "labels", labels, "int32", tuple(rows.shape), contiguous=False)
     rows, labels = rows.contiguous(), labels.contiguous()
-    _check_tensor("diarize_centroids", "rows", rows, "int32", (None,))
-    _check_tensor("diarize_centroids", "labels", labels, "int32", tuple(rows.shape))
     n, d = int(rows.numel()), int(E.shape[1])
     if check_rows and n and not (0 <= int(rows.min()) and int(rows.max()) < E.shape[0]):   # the kernel reads E at these rows
         raise ValueError(f"diarize_centroids: rows must lie in [0, {E.shape[0]}), got {int(rows.min())} .. {int(rows.max())}")
@@ -105,9 +105,10 @@ def diarize_assign(eng, E, info, cent, constrained: bool = False):
     """E [3 C, d] fp32 unit rows, info [C, 3, 4] int32, cent [K, d] float64 (diarize_centroids' second result), all on the device ->
     (labels [C, 3] int32, score [C, 3] fp32) on the device: sdk_diarize_assign."""
     torch, check, _stream = _native()
-    Cn = E.shape[0] // N_LOCAL
-    _check_rows("diarize_assign", E, N_LOCAL * Cn)
-    d = int(E.shape[1])
+    n, d = _check_rows("diarize_assign", E)
+    Cn = n // N_LOCAL
+    if n != N_LOCAL * Cn:
+        raise ValueError(f"diarize_assign: E must hold {N_LOCAL} rows per chunk, got {n} rows")
     _check_tensor("diarize_assign", "info", info, "int32", (Cn, N_LOCAL, 4))
     _check_tensor("diarize_assign", "the centroids", cent, "float64", (None, d))
     if cent.shape[0] < 1:
@@ -195,9 +196,9 @@ def diarize_fold_grouped(eng, cent, sizes, cl_off, eff, cent_off, cut=None, uplo
     _check_tensor("diarize_fold_grouped", "the centroids", cent, "float64", (None, None), Kc)
     d = int(cent.shape[1])
     _check_dim("diarize_fold_grouped", d)
-    n = 0 if cut is None else int(cut.numel())
     if cut is not None:
         _check_tensor("diarize_fold_grouped", "cut", cut, "int32", (None,))
+    n = 0 if cut is None else int(cut.numel())
     up = (upload or (lambda a: torch.from_numpy(a).to(cent.device)))(np.concatenate([sizes, cl_off, eff, cent_off]).astype(np.int32))
     sizes_d, cl_d, eff_d, co_d = up[:Kc], up[Kc:Kc + R + 1], up[Kc + R + 1:Kc + 2 * R + 1], up[Kc + 2 * R + 1:]
     target = torch.empty((max(Kc, 1),), dtype=torch.int32, device=cent.device)
@@ -233,8 +234,9 @@ def diarize_reconstruct_grouped(eng, cls, labels, tab: GroupTables, max_speakers
 def diarize_first_seen(eng, speakers, tab: GroupTables):
     """speakers [G, 2] int32 (device) -> first [K] int32 (device): sdk_diarize_first_seen (integer atomicMin)."""
     torch, check, _stream = _native()
-    if speakers.dtype != torch.int32 or tuple(speakers.shape) != (tab.G, 2) or not speakers.is_contiguous() or tab.cent_off is None:
-        raise ValueError(f"diarize_first_seen: speakers must be a contiguous int32 [{tab.G}, 2] tensor and the tables hold clusters, got {tuple(speakers.shape)} {speakers.dtype}")
+    if tab.cent_off is None:
+        raise ValueError("diarize_first_seen: the tables hold no clusters (set_clusters)")
+    _check_tensor("diarize_first_seen", "speakers", speakers, "int32", (tab.G, 2))
     first = torch.empty((max(tab.K, 1),), dtype=torch.int32, device=speakers.device)
     check(eng.lib.sdk_diarize_first_seen(eng.ctx, speakers.data_ptr(), tab.frame_off_d.data_ptr(), tab.cent_off_d.data_ptr(), tab.R, tab.G, tab.K,
                                          first.data_ptr(), _stream()), "sdk_diarize_first_seen")

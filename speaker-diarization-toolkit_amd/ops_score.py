@@ -1,0 +1,223 @@
+"""Engine's scoring calls beyond the cosine affinity: adaptive score normalisation against a cohort (snorm.py), the PLDA's training
+statistics and projection (plda.fit), PLDA log-likelihood-ratio scoring (plda_score.py) and the verification-trial histogram (trials.py).
+Nothing here synchronises with the host except plda_fit_stats' range check of its labels.
+
+ScoreMixin is a mixin of ops.Engine: no state and no __init__ of its own.  It uses self.lib, self.ctx, self.device, self._scratch_bytes
+and self._workspace_bytes only, and this module imports ops.py for nothing (ops.py imports it).
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _args
+from ._lib import check
+from .ops_util import _ptr, _stream
+
+
+class ScoreMixin:
+    # ------------------------------------------------------------------ adaptive score normalisation (snorm.py; csrc/snorm.hip)
+    def cohort_stats(self, E: torch.Tensor, cohort: torch.Tensor, K: int, ws: Optional[torch.Tensor] = None):
+        """Unit fp32 rows E [N, d] and cohort [M, d] (device) -> (mean [N], std [N]) fp32 of every row's K largest cohort cosines: the mean and
+        the population standard deviation, floored at snorm.STD_FLOOR (sdk_cohort_stats).  ws: a uint8 device tensor to use as the workspace
+        (default: one of sdk_cohort_stats_workspace_bytes(N, M, K) bytes is allocated)."""
+        N, d = _args.rows("cohort_stats", "E", E)
+        M, _ = _args.rows("cohort_stats", "the cohort", cohort, d=d)
+        K = int(K)
+        if M < 1 or M > (1 << 20):
+            raise ValueError(f"cohort_stats: M={M} cohort rows (1 .. 2^20)")
+        if K < 1 or K > M:
+            raise ValueError(f"cohort_stats: K={K} (1 .. M={M})")
+        nbytes = self._workspace_bytes("sdk_cohort_stats_workspace_bytes", N, M, K)
+        if ws is None:
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=E.device)
+        else:
+            _args.tensor("cohort_stats", "ws", ws, "uint8", (None,))
+        mean = torch.empty((N,), dtype=torch.float32, device=E.device)
+        std = torch.empty((N,), dtype=torch.float32, device=E.device)
+        check(self.lib.sdk_cohort_stats(self.ctx, E.data_ptr(), N, cohort.data_ptr(), M, d, K, mean.data_ptr(), std.data_ptr(), ws.data_ptr(),
+                                        ws.numel(), _stream()), "sdk_cohort_stats")
+        return mean, std
+
+    def affinity_topk_snorm(self, E: torch.Tensor, mean_e: torch.Tensor, std_e: torch.Tensor, P: torch.Tensor, mean_p: torch.Tensor,
+                            std_p: torch.Tensor, k: int = 1):
+        """Unit fp32 rows E [N, d] and P [Pn, d] with their cohort statistics (cohort_stats) -> (idx [N, k] int32, score [N, k] fp32,
+        raw [N, k] fp32): per window the k <= min(4, Pn) largest z = ((s - mean_e) / std_e + (s - mean_p) / std_p) / 2, s the cosine; ties to
+        the lower profile; raw is s.  A slot without a finite z holds (-1, 0, 0) (sdk_affinity_topk_snorm)."""
+        who = "affinity_topk_snorm"
+        N, d = _args.rows(who, "E", E)
+        Pn, _ = _args.rows(who, "P", P, d=d)
+        for name, t, n in (("mean_e", mean_e, N), ("std_e", std_e, N), ("mean_p", mean_p, Pn), ("std_p", std_p, Pn)):
+            _args.tensor(who, name, t, "float32", (n,))
+        k = int(k)
+        if k < 1 or k > 4:
+            raise ValueError(f"affinity_topk_snorm: k={k} (1 .. 4)")
+        if Pn < 1 or k > Pn:
+            raise ValueError(f"affinity_topk_snorm: k={k} with Pn={Pn} profiles (the caller clamps k to the number of profiles, at least 1)")
+        idx = torch.empty((N, k), dtype=torch.int32, device=E.device)
+        sc = torch.empty((N, k), dtype=torch.float32, device=E.device)
+        raw = torch.empty((N, k), dtype=torch.float32, device=E.device)
+        check(self.lib.sdk_affinity_topk_snorm(self.ctx, E.data_ptr(), mean_e.data_ptr(), std_e.data_ptr(), N, P.data_ptr(), mean_p.data_ptr(),
+                                               std_p.data_ptr(), Pn, d, k, idx.data_ptr(), sc.data_ptr(), raw.data_ptr(), _stream()),
+              "sdk_affinity_topk_snorm")
+        return idx, sc, raw
+
+    # ---- training the PLDA from labelled rows (plda.fit; csrc/plda_fit.hip)
+    def plda_fit_stats(self, rows: torch.Tensor, labels: Optional[torch.Tensor] = None, K: int = 0, mean1: Optional[torch.Tensor] = None,
+                       scatter: bool = True, check_labels: bool = True) -> dict:
+        """rows [N, d] on the device: fp32 (d a multiple of 64, at most 512; with mean1 [d] float64 every row enters as
+        sqrt(d) unit(e - mean1)) or float64 as they lie (d 1 .. 512); labels [N] int32 in [0, K) or None (K = 0: the total and the scatter
+        only) -> dict(counts [K] int64, sums [K, d], total [d], scatter [d, d] or None, status [1] int32), float64 on the device:
+        sdk_plda_fit_stats.  The labels' range is checked here, before any launch (one read-back; check_labels=False: the caller has), and the
+        row indices are sorted by label with torch's stable sort."""
+        who = "plda_fit_stats"
+        _args.tensor(who, "rows", rows, ("float32", "float64"), (None, None))
+        N, d, K = int(rows.shape[0]), int(rows.shape[1]), int(K)
+        f32 = rows.dtype == torch.float32
+        if N < 1 or N > 1 << 24:
+            raise ValueError(f"plda_fit_stats: N={N} rows (1 .. 2^24)")
+        if f32:
+            _args.row_width(who, d)
+        elif d < 1 or d > _args.MAX_ROW_DIM:
+            raise ValueError(f"plda_fit_stats: d={d} not supported (float64 rows: 1 .. {_args.MAX_ROW_DIM})")
+        if mean1 is not None:
+            if not f32:
+                raise ValueError("plda_fit_stats: mean1 goes with fp32 rows")
+            _args.tensor(who, "mean1", mean1, "float64", (d,))
+        if K < 0 or K > 1 << 24 or (labels is None) != (K == 0):
+            raise ValueError(f"plda_fit_stats: K={K} (1 .. 2^24 with labels, 0 without)")
+        dev = rows.device
+        order = counts = sums = None
+        if labels is not None:
+            _args.tensor(who, "labels", labels, "int32", (N,))
+            if check_labels:
+                lo, hi = int(labels.min()), int(labels.max())
+                if lo < 0 or hi >= K:
+                    raise ValueError(f"plda_fit_stats: labels must lie in [0, {K}), got {lo} .. {hi}")
+            order = torch.sort(labels, stable=True).indices.to(torch.int32)
+            counts = torch.empty((K,), dtype=torch.int64, device=dev)
+            sums = torch.empty((K, d), dtype=torch.float64, device=dev)
+        nbytes = self._workspace_bytes("sdk_plda_fit_stats_workspace_bytes", N, d, K, int(bool(scatter)))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        total = torch.empty((d,), dtype=torch.float64, device=dev)
+        S = torch.empty((d, d), dtype=torch.float64, device=dev) if scatter else None
+        status = torch.empty((1,), dtype=torch.int32, device=dev)
+        check(self.lib.sdk_plda_fit_stats(self.ctx, rows.data_ptr() if f32 else None, None if f32 else rows.data_ptr(), _ptr(mean1), N, d, _ptr(labels),
+                                          _ptr(order), K, _ptr(counts), _ptr(sums), total.data_ptr(), _ptr(S), status.data_ptr(), ws.data_ptr(), nbytes,
+                                          _stream()), "sdk_plda_fit_stats")
+        return dict(counts=counts, sums=sums, total=total, scatter=S, status=status)
+
+    def plda_project(self, E: torch.Tensor, mean1: torch.Tensor, lda: torch.Tensor, mean2: torch.Tensor) -> torch.Tensor:
+        """E [N, d_in] fp32 rows, mean1 [d_in], lda [d_in, D0], mean2 [D0] (float64, device) -> x2 [N, D0] float64:
+        sqrt(D0) unit(lda^T sqrt(d_in) unit(e - mean1) - mean2), sdk_plda_transform's first two steps for every row (sdk_plda_project)."""
+        who = "plda_project"
+        N, d_in = _args.rows(who, "E", E)
+        if N < 1 or N > 1 << 24:
+            raise ValueError(f"plda_project: N={N} rows (1 .. 2^24)")
+        D0 = int(_args.tensor(who, "lda", lda, "float64", (d_in, None)).shape[1])
+        if not 1 <= D0 <= _args.MAX_ROW_DIM:
+            raise ValueError(f"plda_project: lda must be [{d_in}, D0 <= {_args.MAX_ROW_DIM}], got {list(lda.shape)}")
+        _args.tensor(who, "mean1", mean1, "float64", (d_in,))
+        _args.tensor(who, "mean2", mean2, "float64", (D0,))
+        X2 = torch.empty((N, D0), dtype=torch.float64, device=E.device)
+        check(self.lib.sdk_plda_project(self.ctx, E.data_ptr(), d_in, N, mean1.data_ptr(), lda.data_ptr(), mean2.data_ptr(), D0, X2.data_ptr(),
+                                        _stream()), "sdk_plda_project")
+        return X2
+
+    # ---- PLDA log-likelihood-ratio scoring (plda_score.py; csrc/plda_score.hip)
+    def plda_enroll(self, Xp: torch.Tensor, group: torch.Tensor, n_eff: torch.Tensor, Phi: torch.Tensor):
+        """Xp [P, D] float64 transformed profile rows (plda_transform; D 64 or 128, P <= 2^22), group [P] int32 (the speaker index of every
+        row, in any order), n_eff [S] float64 (1 <= S <= 2^20), Phi [D] float64, all on the device -> (G [S, 2 D], r [S], status [1] int32)
+        on the device: the speaker table of plda_score.py (sdk_plda_enroll).  A label outside [0, S) belongs to no speaker and sets status
+        bit 1; a speaker without a row or with an n_eff that is not a finite number above 0 gets r = NaN.  The caller reads status."""
+        who = "plda_enroll"
+        P, D = (int(v) for v in _args.tensor(who, "Xp", Xp, "float64", (None, None)).shape)
+        if D not in (64, 128):
+            raise ValueError(f"plda_enroll: D={D} not supported (64 or 128)")
+        if P > 1 << 22:
+            raise ValueError(f"plda_enroll: P={P} rows (0 .. 2^22)")
+        _args.tensor(who, "group", group, "int32", (P,))
+        S = int(_args.tensor(who, "n_eff", n_eff, "float64", (None,)).shape[0])
+        if S < 1 or S > 1 << 20:
+            raise ValueError(f"plda_enroll: S={S} speakers (1 .. 2^20)")
+        _args.tensor(who, "Phi", Phi, "float64", (D,))
+        nbytes = self._workspace_bytes("sdk_plda_enroll_workspace_bytes", P, S)
+        dev = Xp.device
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        G = torch.empty((S, 2 * D), dtype=torch.float64, device=dev)
+        r = torch.empty((S,), dtype=torch.float64, device=dev)
+        status = torch.empty((1,), dtype=torch.int32, device=dev)
+        check(self.lib.sdk_plda_enroll(self.ctx, Xp.data_ptr() if P else None, group.data_ptr() if P else None, P, D, n_eff.data_ptr(),
+                                       Phi.data_ptr(), S, G.data_ptr(), r.data_ptr(), status.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+              "sdk_plda_enroll")
+        return G, r, status
+
+    def plda_score_topk(self, X: torch.Tensor, G: torch.Tensor, r: torch.Tensor, k: int = 1, scores: bool = False,
+                        ws: Optional[torch.Tensor] = None):
+        """X [N, D] float64 transformed windows (N <= 65 536), (G [S, 2 D], r [S]) a speaker table of plda_enroll -> (idx [N, k] int32,
+        score [N, k] float64) and, with scores=True, the whole matrix [N, S]: per window the k <= 4 largest log-likelihood ratios
+        r_s + sum_d x_d G[s, d] + x_d^2 G[s, D + d]; ties to the lower speaker, a NaN never taken, a slot without a candidate holds
+        (-1, 0); with k > S the columns S .. k - 1 are not written (sdk_plda_score_topk).  ws: a uint8 device tensor to use as the workspace
+        (default: one of sdk_plda_score_workspace_bytes(N, S, k) bytes is allocated)."""
+        who = "plda_score_topk"
+        N, D = (int(v) for v in _args.tensor(who, "X", X, "float64", (None, None)).shape)
+        if D not in (64, 128):
+            raise ValueError(f"plda_score_topk: D={D} not supported (64 or 128)")
+        if N > 65536:
+            raise ValueError(f"plda_score_topk: N={N} windows (0 .. 65536)")
+        S, k = int(_args.tensor(who, "G", G, "float64", (None, 2 * D)).shape[0]), int(k)
+        if S < 1 or S > 1 << 20:
+            raise ValueError(f"plda_score_topk: S={S} speakers (1 .. 2^20)")
+        _args.tensor(who, "r", r, "float64", (S,))
+        if k < 1 or k > 4:
+            raise ValueError(f"plda_score_topk: k={k} (1 .. 4)")
+        nbytes = self._workspace_bytes("sdk_plda_score_workspace_bytes", N, S, k)
+        dev = X.device
+        if ws is None:
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        else:
+            _args.tensor(who, "ws", ws, "uint8", (None,))
+        idx = torch.empty((N, k), dtype=torch.int32, device=dev)
+        sc = torch.empty((N, k), dtype=torch.float64, device=dev)
+        full = torch.empty((N, S), dtype=torch.float64, device=dev) if scores else None
+        check(self.lib.sdk_plda_score_topk(self.ctx, X.data_ptr(), N, D, G.data_ptr(), r.data_ptr(), S, k, idx.data_ptr(), sc.data_ptr(), _ptr(full),
+                                           ws.data_ptr(), ws.numel(), _stream()), "sdk_plda_score_topk")
+        return (idx, sc, full) if scores else (idx, sc)
+
+    # ---- verification trials (trials.py; csrc/trials.hip)
+    def trial_hist(self, A: torch.Tensor, B: torch.Tensor, r: torch.Tensor, la: torch.Tensor, sa: torch.Tensor, lb: torch.Tensor,
+                   sb: torch.Tensor, lo: float, hi: float, shift: int = 12, base: int = 0, max_blocks: int = 0):
+        """One pass of the trial histogram: A [N, K] test rows, B [M, K] model rows, r [M] float64 (K a multiple of 16 in 16 .. 512,
+        1 <= N, M <= 2^20), la, sa [N] and lb, sb [M] int32 labels and sessions, all on the device -> (hist [2, 4096], under [2], over [2],
+        nan [2], excluded [1]) int64 device tensors, views of one array (sdk_trial_hist; trials.py states the rule).  The score
+        r[j] + A[i] . B[j] is cut into q = floor((s - lo) * scale), scale = 2^24 / (hi - lo) formed here in float64, and lands in bin
+        (q >> shift) - base.  max_blocks: 0 = the default grid, else a cap on the workgroups (the counts do not depend on it)."""
+        who = "trial_hist"
+        N, K = (int(v) for v in _args.tensor(who, "A", A, "float64", (None, None)).shape)
+        if K < 16 or K > 512 or K % 16:
+            raise ValueError(f"trial_hist: K={K} not supported (a multiple of 16 in 16 .. 512)")
+        M = int(_args.tensor(who, "B", B, "float64", (None, K)).shape[0])
+        if not (1 <= N <= 1 << 20 and 1 <= M <= 1 << 20):
+            raise ValueError(f"trial_hist: N={N} test rows, M={M} model rows (1 .. 2^20 each)")
+        _args.tensor(who, "r", r, "float64", (M,))
+        for name, t, n in (("la", la, N), ("sa", sa, N), ("lb", lb, M), ("sb", sb, M)):
+            _args.tensor(who, name, t, "int32", (n,))
+        lo, hi, shift, base, max_blocks = float(lo), float(hi), int(shift), int(base), int(max_blocks)
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+            raise ValueError(f"trial_hist: score range ({lo}, {hi}): finite lo < hi expected")
+        with np.errstate(over="ignore"):
+            scale = float(np.float64(16777216.0) / (np.float64(hi) - np.float64(lo)))
+        if not (np.isfinite(scale) and scale > 0.0):
+            raise ValueError(f"trial_hist: scale = 2^24 / (hi - lo) = {scale} is not a finite number above 0 (range ({lo}, {hi}))")
+        if shift < 0 or shift > 24:
+            raise ValueError(f"trial_hist: shift={shift} (0 .. 24)")
+        if base < 0 or base > 1 << 24:
+            raise ValueError(f"trial_hist: base={base} (0 .. 2^24)")
+        if max_blocks < 0:
+            raise ValueError(f"trial_hist: max_blocks={max_blocks} (0: the default grid, else a cap on the workgroups)")
+        out = torch.empty((2 * 4096 + 7,), dtype=torch.int64, device=A.device)           # uint64 counters, all below 2^40
+        check(self.lib.sdk_trial_hist(self.ctx, A.data_ptr(), N, B.data_ptr(), r.data_ptr(), M, K, la.data_ptr(), sa.data_ptr(), lb.data_ptr(),
+                                      sb.data_ptr(), lo, scale, shift, base, max_blocks, out.data_ptr(), _stream()), "sdk_trial_hist")
+        return out[:8192].view(2, 4096), out[8192:8194], out[8194:8196], out[8196:8198], out[8198:8199]

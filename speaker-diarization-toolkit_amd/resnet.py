@@ -32,6 +32,7 @@ from typing import Dict, List, Tuple
 
 import numpy as np
 
+from . import _args
 from .weights_pack import ALIGN, to_bits16
 
 BN_EPS = 1e-5
@@ -252,11 +253,8 @@ class ResNet34:
         from .ops import _stream
         lib = self.eng.lib
         T4 = self.last_map_frames(T)
-        if w.dim() != 3 or w.shape[0] != B or w.shape[2] != T4 or w.dtype != torch.float32 or not w.is_contiguous():
-            raise ValueError(f"forward_masked: w must be a contiguous fp32 [B = {B}, S, T4 = {T4}] tensor, got {tuple(w.shape)} {w.dtype}")
-        S = int(w.shape[1])
-        if tuple(valid.shape) != (B, S) or valid.dtype != torch.int32 or not valid.is_contiguous():
-            raise ValueError(f"forward_masked: valid must be a contiguous int32 [{B}, {S}] tensor, got {tuple(valid.shape)} {valid.dtype}")
+        S = int(_args.tensor("forward_masked", "w", w, "float32", (B, None, T4)).shape[1])      # T4: the width of the last map
+        _args.tensor("forward_masked", "valid", valid, "int32", (B, S))
         ws = self.eng._scratch_bytes("resnet", lib.sdk_resnet_masked_workspace_bytes(C.byref(self.desc), B, T, S))
         emb = torch.empty((B * S, self.cfg.embed_dim), dtype=torch.float32, device=self.eng.device)
         check(lib.sdk_resnet_forward_masked(self.eng.ctx, self.blob.data_ptr(), C.byref(self.desc), feats.data_ptr(), feats.stride(0), B, T, S,

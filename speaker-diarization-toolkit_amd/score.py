@@ -42,7 +42,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .diarize_host import global_frames
-from .diarize_ops import GroupTables, _native
+from .diarize_ops import GroupTables, _check_tensor, _native
 from .segmentation import FRAME_HOP, SAMPLE_RATE
 
 MAX_SCORE_SPEAKERS = 64
@@ -322,8 +322,7 @@ def score_tables(eng, speakers_dev, tab, ref: PackReference, upload=None):
     torch, check, _stream = _native()
     if tab.cent_off is None:
         raise ValueError("score: the tables hold no clusters (set_clusters)")
-    if str(speakers_dev.dtype) != "torch.int32" or tuple(speakers_dev.shape) != (tab.G, 2) or not speakers_dev.is_contiguous():
-        raise ValueError(f"score: speakers must be a contiguous int32 [{tab.G}, 2] tensor, got {tuple(speakers_dev.shape)} {speakers_dev.dtype}")
+    _check_tensor("score", "speakers", speakers_dev, "int32", (tab.G, 2))
     S_r, K_r = np.diff(ref.ref_off), np.diff(tab.cent_off)
     for r in range(tab.R):
         _check_counts(f"score: recording {r}", int(S_r[r]), int(K_r[r]))
