@@ -67,6 +67,7 @@ import numpy as np
 
 from . import BACKEND_NAME
 from .plugin_api import EmbeddingBackend
+from .rules import Cosine, aggregate_matches, aggregate_matches_snorm, cached, rule_from_env  # noqa: F401  (the aggregations: imported from here)
 from .store import load_profile_batch, publish_pack, save_vector, vector_path
 from .wav import cut_ranges, cut_windows, decode_to_profile, range_starts, window_starts
 from .weights import DEFAULT_CONFIG, load_weights, synthetic_weights, weights_digest
@@ -85,7 +86,17 @@ def plda_classes(recording, speaker, names, uris, speaker_key):
     return labels, list(keys)
 
 
+def _of_rule(name: str) -> property:
+    """A Backend attribute that is a setting of its decision rule (rules.py): read and written there."""
+    return property(lambda self: getattr(self.rule, name), lambda self, value: setattr(self.rule, name, value))
+
+
 class Backend(EmbeddingBackend):
+    cohort_path, cohort_threshold, cohort_topk = _of_rule("cohort_path"), _of_rule("cohort_threshold"), _of_rule("cohort_topk")
+    score_plda_paths, score_plda_dim = _of_rule("score_plda_paths"), _of_rule("score_plda_dim")
+    score_plda_threshold, score_plda_count = _of_rule("score_plda_threshold"), _of_rule("score_plda_count")
+    _score_plda = _of_rule("loaded")                    # (plda.Plda, content digest) once score_plda() has read the files
+
     def __init__(self) -> None:
         self.model = os.environ.get("SDK_MODEL", "ecapa").strip().lower()
         if self.model not in ("ecapa", "xvector", "resnet34"):
@@ -110,57 +121,7 @@ class Backend(EmbeddingBackend):
         self._digest: Optional[str] = None
         self.window_s = float(os.environ.get("SDK_WINDOW_S", "2.0"))
         self.hop_s = float(os.environ.get("SDK_HOP_S", "1.0"))
-        # adaptive score normalisation (snorm.py): off unless a cohort is configured
-        self.cohort_path = os.environ.get("SDK_COHORT") or None
-        self.cohort_topk = int(os.environ.get("SDK_COHORT_TOPK", "300"))
-        thr = os.environ.get("SDK_COHORT_THRESHOLD")
-        self.cohort_threshold: Optional[float] = None
-        self._cohort = None
-        if bool(self.cohort_path) != bool(thr):
-            raise ValueError("SDK_COHORT (the cohort file) and SDK_COHORT_THRESHOLD (the vote threshold on the normalised scale) go together: "
-                             f"{'SDK_COHORT_THRESHOLD' if self.cohort_path else 'SDK_COHORT'} is not set.  There is no default threshold: it depends on "
-                             "the model family and the cohort")
-        if self.cohort_path:
-            try:
-                self.cohort_threshold = float(thr)
-            except ValueError:
-                raise ValueError(f"SDK_COHORT_THRESHOLD={thr!r}: a float on the normalised (z) scale expected") from None
-            if self.cohort_threshold != self.cohort_threshold:
-                raise ValueError("SDK_COHORT_THRESHOLD is NaN: a float on the normalised (z) scale expected")
-            if self.cohort_topk < 1:
-                raise ValueError(f"SDK_COHORT_TOPK={self.cohort_topk}: at least 1")
-            if os.environ.get("SDK_NO_TORCH") == "1":
-                raise ValueError("SDK_COHORT with SDK_NO_TORCH=1: the normalised path needs the torch engine; unset SDK_NO_TORCH (or SDK_COHORT)")
-        # PLDA log-likelihood-ratio scoring (plda_score.py): off unless a scoring model is configured
-        tpath, ppath = os.environ.get("SDK_SCORE_PLDA_TRANSFORM") or None, os.environ.get("SDK_SCORE_PLDA") or None
-        self.score_plda_paths: Optional[Tuple[str, str]] = None
-        self.score_plda_dim = 128
-        self.score_plda_threshold = 0.0
-        self.score_plda_count = True
-        self._score_plda = None
-        if bool(tpath) != bool(ppath):
-            raise ValueError("SDK_SCORE_PLDA_TRANSFORM and SDK_SCORE_PLDA name the two files of one PLDA model: set both or neither "
-                             f"({'SDK_SCORE_PLDA' if tpath else 'SDK_SCORE_PLDA_TRANSFORM'} is not set)")
-        if tpath:
-            if self.cohort_path:
-                raise ValueError("SDK_SCORE_PLDA* together with SDK_COHORT: the identify decision is made on ONE scale, the PLDA log-likelihood "
-                                 "ratio or the cohort-normalised cosine; unset one of them")
-            if os.environ.get("SDK_NO_TORCH") == "1":
-                raise ValueError("SDK_SCORE_PLDA* with SDK_NO_TORCH=1: PLDA scoring needs the torch engine; unset SDK_NO_TORCH (or SDK_SCORE_PLDA*)")
-            dim = os.environ.get("SDK_SCORE_PLDA_DIM", "128").strip()
-            if dim not in ("64", "128"):
-                raise ValueError(f"SDK_SCORE_PLDA_DIM={dim!r}: the PLDA dimensions kept, 64 or 128")
-            thr = os.environ.get("SDK_SCORE_PLDA_THRESHOLD", "0")
-            try:
-                self.score_plda_threshold = float(thr)
-            except ValueError:
-                raise ValueError(f"SDK_SCORE_PLDA_THRESHOLD={thr!r}: a float on the log-likelihood-ratio scale expected") from None
-            if self.score_plda_threshold != self.score_plda_threshold:
-                raise ValueError("SDK_SCORE_PLDA_THRESHOLD is NaN: a float on the log-likelihood-ratio scale expected")
-            cnt = os.environ.get("SDK_SCORE_PLDA_COUNT", "1").strip()
-            if cnt not in ("0", "1"):
-                raise ValueError(f"SDK_SCORE_PLDA_COUNT={cnt!r}: 1 (a speaker's count is the number of their enrolled embeddings) or 0 (it is 1)")
-            self.score_plda_paths, self.score_plda_dim, self.score_plda_count = (tpath, ppath), int(dim), cnt == "1"
+        self.rule = rule_from_env(os.environ)           # cosine, AS-norm or PLDA (rules.py); refuses a setting that does not hold together
 
     # ---- metadata (base.py:25-105) -------------------------------------------------------
     @property
@@ -421,7 +382,10 @@ class Backend(EmbeddingBackend):
     def score_ranges(self, samples: np.ndarray, ranges: List[Tuple[float, float]], batch, k: int = 1):
         """Single-speaker ranges -> per window (best profile rows [W, k], scores [W, k]) on the host + windows [(range index, start s, end s)]:
         embed_ranges + score_windows in one call, on either host path (torch engine or SDK_NO_TORCH=1).  With a cohort configured (SDK_COHORT)
-        the rows are the normalised top-k and the scores are z values (score_windows_snorm), not cosines."""
+        the rows are the normalised top-k and the scores are z values (score_windows_snorm), not cosines.  With a scoring PLDA configured
+        (SDK_SCORE_PLDA*) they are COSINES against the enrolled embeddings, not log-likelihood ratios; with SDK_NO_TORCH=1 the host path
+        below answers, with cosines.  So this is the one call that does not follow the Backend's rule ("known gaps": the PLDA
+        rule is not applied here, and identify.make_rows_fn(per_label=True) votes on what comes back at the raw cosine threshold, z or not)."""
         if not self.lite:
             E, Eb, re, wins, _ = self.embed_ranges(samples, ranges)
             if not wins:
@@ -659,9 +623,7 @@ class Backend(EmbeddingBackend):
         configured (SDK_COHORT): ValueError - AS-norm trials are not built."""
         import torch
         from . import trials
-        if self.cohort_path:
-            raise ValueError("score_verification: AS-norm trials are not built: with SDK_COHORT set the decision is made on the normalised scale, "
-                             "which has no matrix form here; unset SDK_COHORT to evaluate the cosine or the PLDA rule")
+        self.rule.refuse_trials()
         if self.lite:
             raise ValueError("score_verification: needs the torch engine; unset SDK_NO_TORCH")
         audio_paths, speaker_ids = list(audio_paths), list(speaker_ids)
@@ -671,33 +633,17 @@ class Backend(EmbeddingBackend):
         if len(batch) == 0:
             raise ValueError("score_verification: no candidate embedding to score against")
         eng = self.engine()
-        rows, la, sa = [], [], []
-        if self.plda_scoring:
-            G, r, speakers = self.speaker_table(batch)[:3]
-            index = {sid: s for s, sid in enumerate(speakers)}
-        else:
-            index: Dict[Any, int] = {}
-            for sid in batch.speaker_ids:
-                index.setdefault(sid, len(index))
-        known = len(index)
-        for f, (path, sid) in enumerate(zip(audio_paths, speaker_ids)):
+        rows = []
+        for path in audio_paths:
             samples, starts, W, _ = self._windows(Path(path), None)
-            E = self.embed_tables(samples, {W: starts})[W][0]
-            rows.append(E)
-            label = -1 if sid is None else index.setdefault(sid, len(index))
-            la += [label] * int(E.shape[0])
-            sa += [f] * int(E.shape[0])
+            rows.append(self.embed_tables(samples, {W: starts})[W][0])
         E = torch.cat(rows, dim=0).contiguous()
-        dev = E.device
-        i32 = lambda a: torch.from_numpy(np.asarray(a, dtype=np.int32)).to(dev)        # noqa: E731
-        if self.plda_scoring:
-            X = self._plda_rows(E)
-            A, B, kind = torch.cat([X, X * X], dim=1).contiguous(), G, "plda"
-            lb = np.arange(known)
-        else:
-            A, B, kind = E.double(), self.profile_tensors(batch)[0].double().contiguous(), "cosine"
-            r = torch.zeros((int(B.shape[0]),), dtype=torch.float64, device=dev)
-            lb = [index[sid] for sid in batch.speaker_ids]
+        A, B, r, lb, kind, index = self.rule.trial_matrices(self, E, batch)
+        la, sa = [], []
+        for f, sid in enumerate(speaker_ids):                    # an id no candidate has: a label of its own, past the model rows'
+            la += [-1 if sid is None else index.setdefault(sid, len(index))] * int(rows[f].shape[0])
+            sa += [f] * int(rows[f].shape[0])
+        i32 = lambda a: torch.from_numpy(np.asarray(a, dtype=np.int32)).to(E.device)        # noqa: E731
         sb = np.full(len(lb), -1)
         return trials.evaluate_scores(eng, A, B, r, i32(la), i32(sa), i32(lb), i32(sb), kind, score_range, p_target, c_miss, c_fa, max_refine)
 
@@ -830,21 +776,19 @@ class Backend(EmbeddingBackend):
         miss: one sdk_l2norm pass, whose outputs are then published as the set's pack (store.publish_pack) - so hit and miss score bit-identically."""
         import torch
         eng = self.engine()
-        dev = getattr(batch, "_dev", None)
-        if dev is not None and dev[0] is eng:
-            return dev[1]
-        if batch.norm is not None:
-            E, Eb, r = batch.norm
-            Pn = torch.from_numpy(np.array(E, dtype=np.float32)).to(eng.device)
-            Pb = torch.from_numpy(np.array(Eb, dtype=np.uint16).view(np.int16)).to(eng.device).view(torch.bfloat16)
-            rp = torch.from_numpy(np.array(r, dtype=np.float32)).to(eng.device)
-        else:
-            Pn, Pb, rp = eng.l2norm(torch.from_numpy(np.ascontiguousarray(batch.matrix, dtype=np.float32)).to(eng.device))
-            if batch.pack_ref:
-                publish_pack(batch, Pn.cpu().numpy(), Pb.view(torch.int16).cpu().numpy().view(np.uint16), rp.cpu().numpy())
-        out = (Pn, Pb, rp.max().reshape(1))
-        batch._dev = (eng, out)
-        return out
+
+        def make():
+            if batch.norm is not None:
+                E, Eb, r = batch.norm
+                Pn = torch.from_numpy(np.array(E, dtype=np.float32)).to(eng.device)
+                Pb = torch.from_numpy(np.array(Eb, dtype=np.uint16).view(np.int16)).to(eng.device).view(torch.bfloat16)
+                rp = torch.from_numpy(np.array(r, dtype=np.float32)).to(eng.device)
+            else:
+                Pn, Pb, rp = eng.l2norm(torch.from_numpy(np.ascontiguousarray(batch.matrix, dtype=np.float32)).to(eng.device))
+                if batch.pack_ref:
+                    publish_pack(batch, Pn.cpu().numpy(), Pb.view(torch.int16).cpu().numpy().view(np.uint16), rp.cpu().numpy())
+            return Pn, Pb, rp.max().reshape(1)
+        return cached(batch, "_dev", eng, None, make)
 
     # ---- adaptive score normalisation (snorm.py) ---------------------------------------------------
     def make_cohort(self, audio_paths: List[Path], out_path: Path) -> Dict[str, Any]:
@@ -861,35 +805,20 @@ class Backend(EmbeddingBackend):
 
     def cohort(self):
         """The configured snorm.Cohort (None without SDK_COHORT), loaded on first use."""
-        if self.cohort_path and self._cohort is None:
-            from .snorm import Cohort
-            self._cohort = Cohort.load(self.cohort_path, self.embedding_dim)
-        return self._cohort
+        return self.rule.cohort(self)
 
     def profile_stats(self, batch):
         """(mean_p, std_p) device tensors: the cohort statistics of a ProfileBatch's rows, computed once per batch object and cached on it
         beside its device copies, keyed by the cohort's digest and K."""
         eng, co = self.engine(), self.cohort()
         K = min(self.cohort_topk, len(co))
-        got = getattr(batch, "_snorm", None)
-        if got is not None and got[0] is eng and got[1] == (co.digest, K):
-            return got[2]
-        out = eng.cohort_stats(self.profile_tensors(batch)[0], co.device_rows(eng), K)
-        batch._snorm = (eng, (co.digest, K), out)
-        return out
-
-    def _snorm_enqueue(self, E, batch, k: int = 1):
-        """Normalised top-k of embedded windows against a ProfileBatch -> (idx, z, raw) device tensors; nothing waits."""
-        eng, co = self.engine(), self.cohort()
-        mean_p, std_p = self.profile_stats(batch)
-        mean_e, std_e = eng.cohort_stats(E, co.device_rows(eng), min(self.cohort_topk, len(co)))
-        return eng.affinity_topk_snorm(E, mean_e, std_e, self.profile_tensors(batch)[0], mean_p, std_p, k=max(1, min(k, len(batch), 4)))
+        return cached(batch, "_snorm", eng, (co.digest, K), lambda: eng.cohort_stats(self.profile_tensors(batch)[0], co.device_rows(eng), K))
 
     def score_windows_snorm(self, E, batch, k: int = 1):
         """score_windows on the normalised scale -> (idx, z, raw) on the host; needs a configured cohort."""
         if self.cohort() is None:
             raise ValueError("score_windows_snorm: no cohort configured (SDK_COHORT)")
-        return tuple(t.cpu().numpy() for t in self._snorm_enqueue(E, batch, k))
+        return tuple(t.cpu().numpy() for t in self.rule.enqueue(self, (E, None, None), batch, k))
 
     # ---- PLDA log-likelihood-ratio scoring (plda_score.py) ------------------------------------------------
     @property
@@ -900,19 +829,7 @@ class Backend(EmbeddingBackend):
     def score_plda(self):
         """The configured scoring model (plda.Plda; None without SDK_SCORE_PLDA*), loaded on first use.  A model whose d_in is not this
         family's embedding_dim is refused."""
-        if self.score_plda_paths and self._score_plda is None:
-            import hashlib
-            from .plda import load_plda
-            model = load_plda(self.score_plda_paths[0], self.score_plda_paths[1], self.score_plda_dim)
-            if model.d_in != int(self.embedding_dim):
-                raise ValueError(f"SDK_SCORE_PLDA_TRANSFORM={self.score_plda_paths[0]}: the PLDA model takes d_in={model.d_in}, the {self.model!r} family "
-                                 f"(SDK_MODEL) embeds into embedding_dim={int(self.embedding_dim)}: train one in this space (Backend.train_plda)")
-            h = hashlib.sha256(np.asarray([model.lda_dim], dtype=np.int64).tobytes())
-            for a in (model.mean1, model.lda, model.mean2, model.mu, model.tr, model.psi):
-                h.update(np.asarray(a.shape, dtype=np.int64).tobytes())
-                h.update(a.tobytes())
-            self._score_plda = (model, h.hexdigest()[:16])
-        return self._score_plda[0] if self._score_plda else None
+        return self.rule.model(self)
 
     def _plda_rows(self, E):
         """fp32 unit rows [n, d] (device) -> their float64 rows [n, D] in the scoring model's space (plda_transform, 65 536 rows per call)."""
@@ -933,49 +850,26 @@ class Backend(EmbeddingBackend):
         import torch
         from .plda_score import group_speakers
         eng, model = self.engine(), self.score_plda()
-        key = (self._score_plda[1], self.score_plda_count)
-        got = getattr(batch, "_plda", None)
-        if got is not None and got[0] is eng and got[1] == key:
-            return got[2]
-        group, speakers, first, counts = group_speakers(batch.speaker_ids)
-        n_eff = counts.astype(np.float64) if self.score_plda_count else np.ones(len(speakers), np.float64)
-        Xp = self._plda_rows(self.profile_tensors(batch)[0])
-        G, r, _ = eng.plda_enroll(Xp, torch.from_numpy(group).to(eng.device), torch.from_numpy(n_eff).to(eng.device),
-                                  model.device_arrays(eng.device)["Phi"])          # group_speakers' labels lie in [0, S): status is not read
-        out = (G, r, speakers, first, counts)
-        batch._plda = (eng, key, out)
-        return out
 
-    def _plda_enqueue(self, E, batch, k: int = 1):
-        """PLDA top-k of embedded windows against a ProfileBatch's speakers -> (idx, llr) device tensors; nothing waits."""
-        import torch
-        eng = self.engine()
-        G, r = self.speaker_table(batch)[:2]
-        X = self._plda_rows(E)
-        k = max(1, min(int(k), int(G.shape[0]), 4))
-        n, step = int(X.shape[0]), 65536
-        if n <= step:
-            return eng.plda_score_topk(X, G, r, k=k)
-        parts = [eng.plda_score_topk(X[a:a + step], G, r, k=k) for a in range(0, n, step)]
-        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+        def make():
+            group, speakers, first, counts = group_speakers(batch.speaker_ids)
+            n_eff = counts.astype(np.float64) if self.score_plda_count else np.ones(len(speakers), np.float64)
+            Xp = self._plda_rows(self.profile_tensors(batch)[0])
+            G, r, _ = eng.plda_enroll(Xp, torch.from_numpy(group).to(eng.device), torch.from_numpy(n_eff).to(eng.device),
+                                      model.device_arrays(eng.device)["Phi"])          # group_speakers' labels lie in [0, S): status is not read
+            return G, r, speakers, first, counts
+        return cached(batch, "_plda", eng, (self._score_plda[1], self.score_plda_count), make)
 
     def score_windows_plda(self, E, batch, k: int = 1):
         """score_windows on the PLDA scale: E [N, d] fp32 unit rows (device) -> (idx [N, k] int32: SPEAKER indices in the order of
         plda_score.group_speakers(batch.speaker_ids), llr [N, k] float64) on the host; needs a configured scoring model."""
         if self.score_plda() is None:
             raise ValueError("score_windows_plda: no scoring model configured (SDK_SCORE_PLDA_TRANSFORM and SDK_SCORE_PLDA)")
-        return tuple(t.cpu().numpy() for t in self._plda_enqueue(E, batch, k))
-
-    def _aggregate_plda(self, idx, llr, spans, batch):
-        from .plda_score import aggregate_matches_plda
-        _, _, speakers, first, counts = self.speaker_table(batch)
-        return aggregate_matches_plda(idx, llr, spans, speakers, [batch.embedding_ids[int(p)] for p in first], counts, self.score_plda_threshold)
+        return tuple(t.cpu().numpy() for t in self.rule.enqueue(self, (E, None, None), batch, k))
 
     def score_windows(self, E, Eb, re, batch, k: int = 1):
-        """Device scoring of embedded windows against a ProfileBatch -> (idx, score) on host."""
-        eng = self.engine()
-        Pn, Pb, rpm = self.profile_tensors(batch)
-        idx, sc = eng.affinity_topk(E, Eb, re, Pn, Pb, rpm, k=min(k, len(batch)))
+        """Device scoring of embedded windows against a ProfileBatch -> (idx, score) on host: cosines, whatever the Backend's rule is."""
+        idx, sc = Cosine().enqueue(self, (E, Eb, re), batch, k)
         return idx.cpu().numpy(), sc.cpu().numpy()
 
     def _load_candidates(self, candidates: List[Dict[str, Any]]):
@@ -994,6 +888,23 @@ class Backend(EmbeddingBackend):
             raise ValueError(batch.all_skipped_message())
         return batch
 
+    def _enqueue_identify(self, audio_path: Path, batch):
+        """One recording on the torch engine: its windows embedded and the rule's top-1 against the batch enqueued -> (device columns, spans).
+        Nothing waits on the host here."""
+        samples, starts, W, spans = self._windows(audio_path, None)
+        return self.rule.enqueue(self, self.embed_tables(samples, {W: starts})[W], batch), spans
+
+    def _collect_identify(self, pending, batch, threshold: float) -> List[Dict[str, Any]]:
+        """The result rows of one _enqueue_identify: its columns downloaded (the host waits here) and aggregated by the rule."""
+        cols, spans = pending
+        return self.rule.rows(self, [t.cpu().numpy()[:, 0] for t in cols], spans, batch, threshold)
+
+    def _identify_lite(self, audio_path: Path, batch, threshold: float) -> List[Dict[str, Any]]:
+        """One recording on the torch-free path (SDK_NO_TORCH=1; the cosine rule only): embedded, scored and downloaded on the null stream."""
+        samples, starts, W, spans = self._windows(audio_path, None)
+        _, idx, sc = self.embed_tables_host(samples, {W: starts}, batch)[W]
+        return aggregate_matches(idx[:, 0], sc[:, 0], spans, batch, threshold)
+
     def identify_speaker(self, audio_path: Path, candidates: List[Dict[str, Any]], threshold: float = 0.354) -> List[Dict[str, Any]]:
         """With a cohort configured (SDK_COHORT) a window's winner is its normalised top-1 and it votes when z >= SDK_COHORT_THRESHOLD: the raw
         `threshold` is NOT applied.  The rows then carry norm_score and are sorted by it (aggregate_matches_snorm).
@@ -1004,21 +915,9 @@ class Backend(EmbeddingBackend):
         batch = self._load_candidates(candidates)
         if len(batch) == 0:
             return []
-        samples, starts, W, spans = self._windows(audio_path, None)
-        if self.plda_scoring:
-            E, _, _ = self.embed_tables(samples, {W: starts})[W]
-            idx, llr = self.score_windows_plda(E, batch)
-            return self._aggregate_plda(idx[:, 0], llr[:, 0], spans, batch)
-        if self.cohort_path:
-            E, _, _ = self.embed_tables(samples, {W: starts})[W]
-            idx, z, raw = self.score_windows_snorm(E, batch)
-            return aggregate_matches_snorm(idx[:, 0], z[:, 0], raw[:, 0], spans, batch, self.cohort_threshold)
         if self.lite:
-            _, idx, sc = self.embed_tables_host(samples, {W: starts}, batch)[W]
-        else:
-            E, Eb, re = self.embed_tables(samples, {W: starts})[W]
-            idx, sc = self.score_windows(E, Eb, re, batch)
-        return aggregate_matches(idx[:, 0], sc[:, 0], spans, batch, threshold)
+            return self._identify_lite(audio_path, batch, threshold)
+        return self._collect_identify(self._enqueue_identify(audio_path, batch), batch, threshold)
 
     def identify_many(self, audio_paths: List[Path], candidates: List[Dict[str, Any]], threshold: float = 0.354) -> List[List[Dict[str, Any]]]:
         """identify_speaker over SEVERAL recordings against one candidate set, as one pipelined pass (an extension: the reference's contract is one
@@ -1031,37 +930,10 @@ class Backend(EmbeddingBackend):
         batch = self._load_candidates(candidates)
         if len(batch) == 0:
             return [[] for _ in audio_paths]
-        if self.plda_scoring:
-            pending = []
-            for path in audio_paths:
-                samples, starts, W, spans = self._windows(path, None)
-                E, _, _ = self.embed_tables(samples, {W: starts})[W]
-                pending.append((self._plda_enqueue(E, batch), spans))                # enqueued; nothing waits here
-            return [self._aggregate_plda(i.cpu().numpy()[:, 0], l.cpu().numpy()[:, 0], spans, batch) for (i, l), spans in pending]
-        if self.cohort_path:
-            pending = []
-            for path in audio_paths:
-                samples, starts, W, spans = self._windows(path, None)
-                E, _, _ = self.embed_tables(samples, {W: starts})[W]
-                pending.append((self._snorm_enqueue(E, batch), spans))               # enqueued; nothing waits here
-            return [aggregate_matches_snorm(i.cpu().numpy()[:, 0], z.cpu().numpy()[:, 0], r.cpu().numpy()[:, 0], spans, batch, self.cohort_threshold)
-                    for (i, z, r), spans in pending]
         if self.lite:                       # the torch-free path downloads per recording (everything on the null stream): sequential
-            out = []
-            for path in audio_paths:
-                samples, starts, W, spans = self._windows(path, None)
-                _, idx, sc = self.embed_tables_host(samples, {W: starts}, batch)[W]
-                out.append(aggregate_matches(idx[:, 0], sc[:, 0], spans, batch, threshold))
-            return out
-        eng = self.engine()
-        Pn, Pb, rpm = self.profile_tensors(batch)
-        pending = []
-        for path in audio_paths:
-            samples, starts, W, spans = self._windows(path, None)
-            E, Eb, re = self.embed_tables(samples, {W: starts})[W]
-            idx, sc = eng.affinity_topk(E, Eb, re, Pn, Pb, rpm, k=1)      # enqueued; nothing waits here
-            pending.append((idx, sc, spans))
-        return [aggregate_matches(idx.cpu().numpy()[:, 0], sc.cpu().numpy()[:, 0], spans, batch, threshold) for idx, sc, spans in pending]
+            return [self._identify_lite(path, batch, threshold) for path in audio_paths]
+        pending = [self._enqueue_identify(path, batch) for path in audio_paths]             # enqueued; nothing waits here
+        return [self._collect_identify(p, batch, threshold) for p in pending]
 
     # ---- a3: verify - the CLI reads result['confidence'] (speaker_detection:1173-1174) ---------
     def verify_speaker(self, audio_path: Path, speaker_profile: Dict[str, Any], threshold: float = 0.354) -> Dict[str, Any]:
@@ -1074,56 +946,6 @@ class Backend(EmbeddingBackend):
             return {"match": False, "similarity": 0.0, "confidence": 0.0, "embedding_id": None}
         h = hits[0]
         out = {"match": True, "similarity": h["similarity"], "confidence": h["similarity"], "embedding_id": h.get("embedding_id")}
-        if "norm_score" in h:
-            out["norm_score"] = h["norm_score"]
-        if "llr" in h:
-            out["llr"] = h["llr"]
+        out.update((key, h[key]) for key in self.rule.verify_keys)          # norm_score under a cohort, llr under a scoring PLDA
         return out
 
-
-def aggregate_matches(best_idx: np.ndarray, best_score: np.ndarray, spans, batch, threshold: float) -> List[Dict[str, Any]]:
-    """Per-window argmax (integer profile row, fp32 cosine) -> one result row per matched speaker.
-    A window votes for the speaker owning its best profile row if the cosine clears `threshold`;
-    similarity = float64 mean of the speaker's window scores; rows sorted by similarity desc, ties
-    by speaker id.  embedding_id = the speaker's embedding that won most windows (ties: first)."""
-    per: Dict[str, Dict[str, Any]] = {}
-    for w, (row, s) in enumerate(zip(best_idx.tolist(), best_score.tolist())):
-        if row < 0 or s < threshold:
-            continue
-        sid = batch.speaker_ids[row]
-        acc = per.setdefault(sid, {"scores": [], "rows": {}, "first": spans[w][0], "last": spans[w][1]})
-        acc["scores"].append(float(s))
-        acc["rows"][row] = acc["rows"].get(row, 0) + 1
-        acc["last"] = spans[w][1]
-    out = []
-    for sid, acc in per.items():
-        win_row = max(acc["rows"].items(), key=lambda kv: (kv[1], -kv[0]))[0]
-        sim = float(np.mean(np.asarray(acc["scores"], dtype=np.float64)))
-        out.append({"speaker_id": sid, "similarity": sim, "confidence": sim, "embedding_id": batch.embedding_ids[win_row],
-                    "segment": (acc["first"], acc["last"]), "n_segments": len(acc["scores"])})
-    out.sort(key=lambda r: (-r["similarity"], r["speaker_id"]))
-    return out
-
-
-def aggregate_matches_snorm(best_idx: np.ndarray, best_z: np.ndarray, best_raw: np.ndarray, spans, batch, z_threshold: float) -> List[Dict[str, Any]]:
-    """aggregate_matches for the normalised path (snorm.py): a window votes for the speaker owning its normalised top-1 row when its z clears
-    `z_threshold` (no raw threshold applies).  similarity = confidence = float64 mean of the RAW cosines of the speaker's voting windows (so
-    combine_signals keeps its [-1, 1] input); norm_score = float64 mean of their z.  Rows sorted by norm_score descending, then speaker id."""
-    per: Dict[str, Dict[str, Any]] = {}
-    for w, (row, z, s) in enumerate(zip(best_idx.tolist(), best_z.tolist(), best_raw.tolist())):
-        if row < 0 or not z >= z_threshold:
-            continue
-        sid = batch.speaker_ids[row]
-        acc = per.setdefault(sid, {"z": [], "raw": [], "rows": {}, "first": spans[w][0], "last": spans[w][1]})
-        acc["z"].append(float(z))
-        acc["raw"].append(float(s))
-        acc["rows"][row] = acc["rows"].get(row, 0) + 1
-        acc["last"] = spans[w][1]
-    out = []
-    for sid, acc in per.items():
-        win_row = max(acc["rows"].items(), key=lambda kv: (kv[1], -kv[0]))[0]
-        sim = float(np.mean(np.asarray(acc["raw"], dtype=np.float64)))
-        out.append({"speaker_id": sid, "similarity": sim, "confidence": sim, "norm_score": float(np.mean(np.asarray(acc["z"], dtype=np.float64))),
-                    "embedding_id": batch.embedding_ids[win_row], "segment": (acc["first"], acc["last"]), "n_segments": len(acc["z"])})
-    out.sort(key=lambda r: (-r["norm_score"], r["speaker_id"]))
-    return out

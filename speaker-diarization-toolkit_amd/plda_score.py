@@ -26,7 +26,7 @@ So the score matrix is one product of depth 2 D plus a constant per speaker: wit
 On the device: ops.Engine.plda_enroll and ops.Engine.plda_score_topk (csrc/plda_score.hip: the product on the f64 MFMA, x^2 formed in the
 kernel, the speakers split across workgroups and merged in a fixed order).  This module holds the numpy float64 restatements for hosts that
 post-process stored embeddings, the grouping of a profile batch's rows by speaker and the aggregation of per-window winners into result
-rows; it imports neither torch nor the library.
+rows (the voting loop is rules.py's, shared with the other two rules); it imports neither torch nor the library.
 """
 from __future__ import annotations
 
@@ -34,6 +34,8 @@ import math
 from typing import Any, Dict, List, Sequence, Tuple
 
 import numpy as np
+
+from .rules import _mean, _tally
 
 MAX_TOPK = 4                      # k of the top-k
 MAX_SPEAKERS = 1 << 20            # speakers sdk_plda_enroll / sdk_plda_score_topk serve
@@ -136,18 +138,13 @@ def aggregate_matches_plda(best_idx, best_llr, spans, speakers, embedding_ids, c
     (idx -1 and a NaN do not vote).  speakers [S]: the ids; embedding_ids [S]: every speaker's first embedding in batch order; counts [S]:
     their enrolled embeddings.  llr = the float64 mean of the speaker's voting windows' llr; similarity = confidence = 1 / (1 + exp(-llr));
     rows sorted by llr descending, then speaker id."""
-    per: Dict[int, Dict[str, Any]] = {}
-    for w, (s, l) in enumerate(zip(np.asarray(best_idx).tolist(), np.asarray(best_llr, dtype=np.float64).tolist())):
-        if s < 0 or not l >= threshold:
-            continue
-        acc = per.setdefault(s, {"llr": [], "first": spans[w][0], "last": spans[w][1]})
-        acc["llr"].append(l)
-        acc["last"] = spans[w][1]
+    per = _tally((None if s < 0 or not l >= threshold else (s, l)
+                  for s, l in zip(np.asarray(best_idx).tolist(), np.asarray(best_llr, dtype=np.float64).tolist())), spans)
     out = []
     for s, acc in per.items():
-        llr = float(np.mean(np.asarray(acc["llr"], dtype=np.float64)))
+        llr = _mean(acc["votes"])
         conf = confidence(llr)
         out.append({"speaker_id": speakers[s], "llr": llr, "similarity": conf, "confidence": conf, "embedding_id": embedding_ids[s],
-                    "n_embeddings": int(counts[s]), "segment": (acc["first"], acc["last"]), "n_segments": len(acc["llr"])})
+                    "n_embeddings": int(counts[s]), "segment": (acc["first"], acc["last"]), "n_segments": len(acc["votes"])})
     out.sort(key=lambda r: (-r["llr"], r["speaker_id"]))
     return out

@@ -8,6 +8,7 @@ are plain data (tests/golden/*.json), and this script is the committed recipe
 that made them.  The GPU box never runs this file.
 
     python3 tests/golden/make_golden.py          # rewrites tests/golden/*.json
+    python3 tests/golden/make_golden.py aggregate   # rewrites aggregate_rows.json alone: taken from this package, needs no reference
 
 Reference entry points exercised (file:line):
   speaker-assign:418-492      combine_signals
@@ -228,7 +229,74 @@ def make_registry_golden(here: Path) -> None:
     print("wrote", here / "registry_golden.json")
 
 
+def aggregate_case():
+    """The fixed input of aggregate_rows.json: 40 windows over 4 speakers who own 7 profile rows.  Dyadic scores, so every mean is exact.
+    ann's rows 0 and 2 win equally many windows (the embedding is the first row's), bob and cy vote with the same scores (equal means: the
+    tie goes by id), window 3 has index -1, window 7 a NaN score, window 11 a score exactly at the threshold.  The z of the normalised rule
+    is 4 x the cosine and the llr of the PLDA rule 8 x the cosine - 4, both exact, so the three rules see the same votes."""
+    import numpy as np
+    speaker_ids = ["ann", "bob", "ann", "cy", "bob", "dee", "cy"]
+    rng = np.random.default_rng(20260)
+    idx = rng.choice([0, 2, 5], size=40).astype(np.int32)
+    cos = (rng.integers(26, 60, size=40) / 64.0).astype(np.float32)             # 0.40625 .. 0.921875: some below the threshold 0.5
+    cos[rng.choice(40, size=4, replace=False)] = np.float32(0.515625)           # repeated scores
+    for w, row, s in ((13, 1, 0.75), (21, 4, 0.625), (17, 3, 0.625), (29, 6, 0.75), (3, -1, 0.875), (7, 5, np.nan), (11, 5, 0.5)):
+        idx[w], cos[w] = row, s
+    ann = [w for w in range(40) if idx[w] in (0, 2) and cos[w] >= 0.5]
+    if len(ann) % 2:
+        idx[ann.pop()] = 5
+    for j, w in enumerate(ann):
+        idx[w] = (2, 0)[j % 2]                                                  # row 2 votes first, row 0 as often
+    spans = [[0.5 * w, 0.5 * w + 2.0] for w in range(40)]
+    return {"speaker_ids": speaker_ids, "embedding_ids": [f"e{p}" for p in range(7)], "idx": idx.tolist(), "cos": cos.tolist(), "spans": spans,
+            "thresholds": {"cosine": [0.5, 2.0], "snorm": [2.0, 100.0], "plda": [0.0, 1e9]}}
+
+
+def nan_as_text(x):
+    """x with every NaN replaced by the string "nan" (float("nan") reads it back): a NaN is not equal to itself, and JSON has no word for it."""
+    if isinstance(x, dict):
+        return {k: nan_as_text(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [nan_as_text(v) for v in x]
+    return "nan" if isinstance(x, float) and x != x else x
+
+
+def make_aggregate_golden(here: Path) -> None:
+    """What backend.aggregate_matches, backend.aggregate_matches_snorm and plda_score.aggregate_matches_plda answer for aggregate_case(), at
+    its two thresholds each (the second is one that nobody clears): recorded from the three functions as they stood before they shared
+    one voting loop, so the record pins them to that.  Needs no reference and no torch.  tests/test_rules_cpu.py compares with ==
+    after the same nan_as_text."""
+    import importlib
+    import numpy as np
+    sys.path.insert(0, str(here.parent.parent))
+    pkg = "speaker-diarization-toolkit_amd"
+    bk, ps = importlib.import_module(f"{pkg}.backend"), importlib.import_module(f"{pkg}.plda_score")
+    case = aggregate_case()
+
+    class batch:
+        speaker_ids, embedding_ids = case["speaker_ids"], case["embedding_ids"]
+    idx, cos = np.asarray(case["idx"], np.int32), np.asarray(case["cos"], np.float32)
+    spans = [tuple(s) for s in case["spans"]]
+    group, speakers, first, counts = ps.group_speakers(batch.speaker_ids)
+    sidx = np.where(idx >= 0, group[np.maximum(idx, 0)], -1).astype(np.int32)
+    rows = {"cosine": [bk.aggregate_matches(idx, cos, spans, batch, t) for t in case["thresholds"]["cosine"]],
+            "snorm": [bk.aggregate_matches_snorm(idx, cos * np.float32(4), cos, spans, batch, t) for t in case["thresholds"]["snorm"]],
+            "plda": [ps.aggregate_matches_plda(sidx, cos.astype(np.float64) * 8 - 4, spans, speakers, [batch.embedding_ids[int(p)] for p in first],
+                                               counts, t) for t in case["thresholds"]["plda"]]}
+    main_rows = rows["cosine"][0]
+    by = {r["speaker_id"]: r for r in main_rows}
+    assert [r["speaker_id"] for r in main_rows].index("bob") + 1 == [r["speaker_id"] for r in main_rows].index("cy")
+    assert by["bob"]["similarity"] == by["cy"]["similarity"] and by["ann"]["embedding_id"] == "e0" and by["bob"]["embedding_id"] == "e1"
+    assert set(by) == {"ann", "bob", "cy", "dee"} and rows["snorm"][1] == rows["plda"][1] == []
+    assert [r["speaker_id"] for r in rows["cosine"][1]] == ["dee"]         # `s < threshold` is false for a NaN: under the cosine rule it votes
+    (here / "aggregate_rows.json").write_text(json.dumps(nan_as_text({"case": case, "rows": rows}), indent=1, allow_nan=False) + "\n")
+    print("wrote", here / "aggregate_rows.json", (here / "aggregate_rows.json").stat().st_size, "bytes")
+
+
 def main() -> int:
+    if sys.argv[1:] == ["aggregate"]:                 # the one record that is taken from this package, not from the reference
+        make_aggregate_golden(HERE)
+        return 0
     if not REF.exists():
         print("reference not mounted; golden vectors can only be regenerated in the build container",
               file=sys.stderr)
