@@ -57,7 +57,7 @@
  *     sdk_conv_gemm*  sdk_colstats_finish  sdk_res2net_chain*  sdk_se_*  sdk_asp_*  sdk_rows_fc  (pieces of sdk_ecapa_forward)
  *     sdk_resnet_conv2d  sdk_resnet_pool  (pieces of sdk_resnet_forward)  sdk_resnet_masked_pool  (piece of sdk_resnet_forward_masked)
  *     sdk_sincnet_frontend  sdk_bilstm_layer  (pieces of sdk_segmentation_forward)
- *     sdk_set_option  sdk_set_gemm_variant  sdk_profile_begin / _end  sdk_debug_set_ptr  sdk_affinity_plan*  sdk_affinity_block_plan*  sdk_affinity_matvec_plan  sdk_conv_gemm_hp
+ *     sdk_set_option  sdk_set_gemm_variant  sdk_profile_begin / _end  sdk_debug_set_ptr  sdk_affinity_plan*  sdk_affinity_block_plan*  sdk_affinity_matvec_plan  sdk_conv_gemm_hp  sdk_resample_plan
  *     sdk_seg_mean_hp  sdk_se_apply_hp  sdk_asp_stats_hp  sdk_asp_pool_hp  (the precise mode's sweeps, pieces of its forwards)
  *     sdk_allgather  sdk_laplacian_topk_workspace_bytes  sdk_laplacian_topk        k5 / k6 drivers for a non-Python host (the library holds no
  *                                                                                     communicator: the caller passes its ncclComm_t; the Python
@@ -817,6 +817,10 @@ int sdk_trial_hist(sdk_ctx* ctx, const double* A, int N, const double* B, const 
 int64_t sdk_resample_out_len(int64_t n_in, int L, int M);
 int sdk_resample_s16(sdk_ctx* ctx, const int16_t* x, int64_t n_in, int channels, const int32_t* taps, int L, int M, int K,
                      int16_t* y, int64_t n_out, void* stream);
+/* Host only: where sdk_resample_s16 stages its operands for a filter shape, the decision its launch is taken from.  Bit 0: the tap
+ * table sits in LDS; bit 1: the workgroup's down-mixed input window sits in LDS (each when it fits in 64 KiB; otherwise the kernel
+ * reads it from global memory).  -1: a shape sdk_resample_s16 refuses (L, M >= 1, K even and >= 2, L * K <= 2^22). */
+int sdk_resample_plan(int L, int M, int K);
 
 /* ---- k3: L2-normalise rows.  X [N, d] fp32 -> E fp32 unit rows, Eb bf16 copy,
  *      resid[n] = || E[n] - float(Eb[n]) ||_2 (rigorous per-row bf16 rounding residual). -- */

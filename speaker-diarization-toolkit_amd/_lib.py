@@ -191,6 +191,7 @@ SIGNATURES = {
     "sdk_sincnet_frontend": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "sdk_bilstm_layer": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "sdk_resample_out_len": (_i64, [_i64, _i, _i]),
+    "sdk_resample_plan": (_i, [_i, _i, _i]),
     "sdk_resample_s16": (_i, [_vp, _vp, _i64, _i, _vp, _i, _i, _i, _vp, _i64, _vp]),
     "sdk_l2norm": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "sdk_affinity_workspace_bytes": (_sz, [_i, _i]),

@@ -73,31 +73,46 @@ __global__ __launch_bounds__(RS_NT) void resample_kernel(const int16_t* __restri
   }
 }
 
+constexpr size_t RS_LDS_LIMIT = 64 * 1024;   // each of the two operands is staged in LDS when it fits in this
+
+// The launch decision for a filter shape, and the one place its limits live: bit 0 taps in LDS, bit 1 window in LDS;
+// -1 for a shape that is refused.  The byte sizes go to the launch.
+int resample_plan(int L, int M, int K, size_t* tab_bytes, size_t* win_bytes) {
+  if (!(L >= 1 && M >= 1 && K >= 2 && (K & 1) == 0 && (int64_t)L * K <= (1 << 22))) return -1;
+  const size_t tab = (size_t)L * K * sizeof(int32_t);
+  // input samples one workgroup touches: (RS_PER_WG - 1) * M / L + K, rounded up
+  const size_t win = ((size_t)(((int64_t)(RS_PER_WG - 1) * M) / L + K + 2) * sizeof(int16_t) + 3) & ~(size_t)3;
+  if (tab_bytes) *tab_bytes = tab;
+  if (win_bytes) *win_bytes = win;
+  return (tab <= RS_LDS_LIMIT ? 1 : 0) | (win <= RS_LDS_LIMIT ? 2 : 0);
+}
+
 }  // namespace
 
 extern "C" int64_t sdk_resample_out_len(int64_t n_in, int L, int M) {
   return (L > 0 && M > 0 && n_in >= 0) ? (n_in * L + M - 1) / M : -1;
 }
 
+extern "C" int sdk_resample_plan(int L, int M, int K) { return resample_plan(L, M, K, nullptr, nullptr); }
+
 extern "C" int sdk_resample_s16(sdk_ctx* ctx, const int16_t* x, int64_t n_in, int channels, const int32_t* taps, int L,
                                 int M, int K, int16_t* y, int64_t n_out, void* stream) {
   SDK_REQUIRE(ctx && x && taps && y, "sdk_resample_s16: null argument");
   SDK_REQUIRE(n_in > 0 && channels >= 1 && channels <= 64, "sdk_resample_s16: n_in=%lld channels=%d", (long long)n_in, channels);
-  SDK_REQUIRE(L >= 1 && M >= 1 && K >= 2 && (K & 1) == 0 && (int64_t)L * K <= (1 << 22), "sdk_resample_s16: bad filter shape L=%d M=%d K=%d", L, M, K);
+  size_t tab_bytes = 0, win_bytes = 0;
+  const int plan = resample_plan(L, M, K, &tab_bytes, &win_bytes);
+  SDK_REQUIRE(plan >= 0, "sdk_resample_s16: bad filter shape L=%d M=%d K=%d", L, M, K);
   SDK_REQUIRE(n_out == sdk_resample_out_len(n_in, L, M), "sdk_resample_s16: n_out=%lld, expected ceil(n_in*L/M)=%lld", (long long)n_out,
               (long long)sdk_resample_out_len(n_in, L, M));
   SDK_REQUIRE(n_in < (1ll << 40), "sdk_resample_s16: input too long");
   ProfScope ps(ctx, stream, SDK_K_RESAMPLE, 2.0 * (double)n_out * K, 2.0 * (double)n_in * channels + 2.0 * (double)n_out);
-  const size_t tab_bytes = (size_t)L * K * sizeof(int32_t);
   const int64_t nwg = (n_out + RS_PER_WG - 1) / RS_PER_WG;
   SDK_REQUIRE(nwg < (1ll << 31), "sdk_resample_s16: output too long");
-  // input samples one workgroup touches: (RS_PER_WG - 1) * M / L + K, rounded up
-  const size_t win_bytes = ((size_t)(((int64_t)(RS_PER_WG - 1) * M) / L + K + 2) * sizeof(int16_t) + 3) & ~(size_t)3;
-  const bool lds_taps = tab_bytes <= 64 * 1024;
-  const bool lds_win = win_bytes <= 64 * 1024;
-  if (sdk_lds_optin(ctx, (const void*)resample_kernel<true, true>, 128 * 1024)) return 1;
-  if (sdk_lds_optin(ctx, (const void*)resample_kernel<true, false>, 64 * 1024)) return 1;
-  if (sdk_lds_optin(ctx, (const void*)resample_kernel<false, true>, 64 * 1024)) return 1;
+  const bool lds_taps = plan & 1;
+  const bool lds_win = plan & 2;
+  if (sdk_lds_optin(ctx, (const void*)resample_kernel<true, true>, 2 * (int)RS_LDS_LIMIT)) return 1;
+  if (sdk_lds_optin(ctx, (const void*)resample_kernel<true, false>, (int)RS_LDS_LIMIT)) return 1;
+  if (sdk_lds_optin(ctx, (const void*)resample_kernel<false, true>, (int)RS_LDS_LIMIT)) return 1;
   const dim3 grid((unsigned)nwg), block(RS_NT);
   hipStream_t st = (hipStream_t)stream;
   if (lds_taps && lds_win)

@@ -305,6 +305,8 @@ class LiteEngine:
         """x int16 [n] or [n, C] interleaved at rate_in -> mono int16 at rate_out (GPU integer polyphase FIR, bit-exact vs oracle/resample.py)."""
         from . import resample
         x = np.ascontiguousarray(x, dtype=np.int16)
+        if x.ndim not in (1, 2) or x.shape[0] < 1:
+            raise ValueError(f"resample_s16_host: x must be int16 [n] or [n, C] with n >= 1, got {list(x.shape)}")
         n_in = x.shape[0]
         ch = 1 if x.ndim == 1 else x.shape[1]
         taps, L, M, K = resample.design_taps(int(rate_in), int(rate_out))

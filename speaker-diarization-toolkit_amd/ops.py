@@ -236,6 +236,8 @@ class Engine(BlocksMixin, ClusterMixin, ScoreMixin):
     def resample_s16(self, x: torch.Tensor, rate_in: int, rate_out: int = 16000) -> torch.Tensor:
         """x int16 [n] or [n, C] interleaved (device) at rate_in -> mono int16 [ceil(n*L/M)] at rate_out."""
         _need(x, torch.int16, "x")
+        if x.dim() not in (1, 2) or x.shape[0] < 1:
+            raise ValueError(f"resample_s16: x must be int16 [n] or [n, C] with n >= 1, got {list(x.shape)}")
         x = x.contiguous()
         n_in = x.shape[0]
         ch = 1 if x.dim() == 1 else x.shape[1]
