@@ -51,6 +51,8 @@
  *                                                                                                       windows against enrolled speakers (plda_score.py)
  *     sdk_trial_hist                                                                                    verification trials: two-class score histograms for EER, minDCF
  *                                                                                                       and the DET curve (trials.py)
+ *     sdk_trial_calib_workspace_bytes  sdk_trial_calib                                                  verification trials: the sums of the logistic calibration
+ *                                                                                                       objective, its gradient and Hessian (trials.py)
  *     sdk_kmeans_rows_workspace_bytes  sdk_kmeans_rows                                                  spherical k-means on unit rows (cluster.kmeans_cluster)
  *     sdk_stream_state_bytes  sdk_stream_reset  sdk_stream_step  sdk_stream_flush  sdk_stream_centroids streaming diarization: online speaker tracking (stream.py)
  * BUILDING BLOCKS AND KNOBS - exported for the parity tests and the A/B tools, free to change between rounds, not for binding:
@@ -807,6 +809,25 @@ int sdk_plda_score_topk(sdk_ctx* ctx, const double* X, int N, int D, const doubl
  *      atomics; the in-range trials of a class then land in its bin 0. */
 int sdk_trial_hist(sdk_ctx* ctx, const double* A, int N, const double* B, const double* r, int M, int K, const int32_t* la, const int32_t* sa,
                    const int32_t* lb, const int32_t* sb, double lo, double scale, int shift, int base, int max_blocks, uint64_t* out, void* stream);
+
+/* ---- calibration of verification scores: one pass of the prior-weighted logistic objective over the trials of sdk_trial_hist (the same A, B, r,
+ *      labels, sessions, classes, exclusions and score; trials.py states the rule; csrc/trials.hip).  With y = +1 for a target, -1 otherwise:
+ *          z = a * s + c   one float64 multiplication, then one float64 addition (no FMA);   m = y z;   e = exp(-|m|)
+ *          loss = max(-m, 0) + log1p(e);   p = e / (1 + e);   q = 1 / (1 + e);   w = p when m >= 0, else q;   v = p * q
+ *      A trial whose score is NaN, +inf or -inf is counted in nonfinite[class] and left out of every sum.
+ *      sums: [2][7] float64 on the device, per class (0 nontarget, 1 target) the sums of loss, w, w s, v, v s, (v s) s and s.
+ *      counts: 5 uint64 on the device - n[2] (the trials summed, per class), nonfinite[2], excluded - zeroed by the call in stream order.
+ *      No floating-point atomics: a lane adds its trials in tile order, the lanes of a wave in a fixed tree, the four waves in wave order, one
+ *      row per workgroup in the workspace; a second kernel adds the rows in ascending order.  The sums are a function of the inputs and the grid
+ *      alone: bit-identical run to run; another max_blocks (0 = the default grid, else a cap on the persistent workgroups) reorders additions
+ *      and changes them by rounding only.  The counts do not depend on it.  workspace: sdk_trial_calib_workspace_bytes(N, M, max_blocks),
+ *      256-byte aligned; the sizer is host-only and returns 0 with sdk_last_error set for arguments the call refuses.  Refused (status 2,
+ *      nothing launched): K, N, M or max_blocks outside their limits, an a or c that is not finite, a null pointer, A or B not 16-byte aligned,
+ *      a workspace that is null, too small or misaligned. */
+size_t sdk_trial_calib_workspace_bytes(int N, int M, int max_blocks);
+int sdk_trial_calib(sdk_ctx* ctx, const double* A, int N, const double* B, const double* r, int M, int K, const int32_t* la, const int32_t* sa,
+                    const int32_t* lb, const int32_t* sb, double a, double c, int max_blocks, double* sums, uint64_t* counts, void* ws,
+                    size_t ws_bytes, void* stream);
 
 /* ---- audio conversion to the AudioProfile: replaces the ffmpeg subprocess the reference's backends
  *      run before upload (audio_profiles.py:70-100 `format_ffmpeg_args`; speechmatics_backend.py:231-281).

@@ -53,8 +53,14 @@ Environment:
   SDK_SCORE_PLDA_DIM  the PLDA dimensions kept, 64 or 128 (default 128)
   SDK_SCORE_PLDA_THRESHOLD  the vote threshold on the log-likelihood-ratio scale (a float, default 0: the point of equal likelihood under the
                       model).  The scale is UNCALIBRATED: 0 is not a tuned operating point.  Backend.tune_verification returns the thresholds
-                      at the equal error rate and at the minimum detection cost of a labelled development set (trials.py)
+                      at the equal error rate and at the minimum detection cost of a labelled development set (trials.py);
+                      calibrate_verification fits the map from this scale to a log-likelihood ratio (SDK_SCORE_CALIBRATION)
   SDK_SCORE_PLDA_COUNT  1 (default): a speaker's effective count n_s is the number of their enrolled embeddings ("by the book") / 0: n_s = 1
+  SDK_SCORE_CALIBRATION  a calibration file (calibrate_verification(backend, ..., out_path=) below writes one; trials.py states the fit): rows of
+                      identify_speaker / identify_many, and verify_speaker's answer, gain calibrated_llr = a * score + b (the score: the row's mean
+                      cosine, or its mean llr under SDK_SCORE_PLDA*) and posterior = sigmoid(calibrated_llr + logit(SDK_SCORE_PRIOR)).  No decision,
+                      threshold, order or existing key changes.  Refused when the file was fitted to the other rule, and together with SDK_COHORT
+  SDK_SCORE_PRIOR     the prior of a target behind `posterior`, inside (0, 1) (default 0.5)
 """
 from __future__ import annotations
 
@@ -621,17 +627,22 @@ class Backend(EmbeddingBackend):
         rule (SDK_SCORE_PLDA*) - the rule identify_speaker would use.  Scored on the device in trials.py's integer form (the rule is stated
         there; parity with outside toolkits is unpinned); score_range defaults to trials.COSINE_RANGE / trials.PLDA_RANGE.  With a cohort
         configured (SDK_COHORT): ValueError - AS-norm trials are not built."""
-        import torch
         from . import trials
+        eng, tensors, kind = self._verification_trials("score_verification", audio_paths, speaker_ids, candidates)
+        return trials.evaluate_scores(eng, *tensors, kind, score_range, p_target, c_miss, c_fa, max_refine)
+
+    def _verification_trials(self, who: str, audio_paths, speaker_ids, candidates):
+        """The trials of score_verification and calibrate_verification in matrix form -> (engine, (A, B, r, la, sa, lb, sb), kind)."""
+        import torch
         self.rule.refuse_trials()
         if self.lite:
-            raise ValueError("score_verification: needs the torch engine; unset SDK_NO_TORCH")
+            raise ValueError(f"{who}: needs the torch engine; unset SDK_NO_TORCH")
         audio_paths, speaker_ids = list(audio_paths), list(speaker_ids)
         if len(audio_paths) != len(speaker_ids) or not audio_paths:
-            raise ValueError(f"score_verification: {len(audio_paths)} recordings with {len(speaker_ids)} speaker ids (one per recording, at least one)")
+            raise ValueError(f"{who}: {len(audio_paths)} recordings with {len(speaker_ids)} speaker ids (one per recording, at least one)")
         batch = self._load_candidates(candidates)
         if len(batch) == 0:
-            raise ValueError("score_verification: no candidate embedding to score against")
+            raise ValueError(f"{who}: no candidate embedding to score against")
         eng = self.engine()
         rows = []
         for path in audio_paths:
@@ -645,7 +656,7 @@ class Backend(EmbeddingBackend):
             sa += [f] * int(rows[f].shape[0])
         i32 = lambda a: torch.from_numpy(np.asarray(a, dtype=np.int32)).to(E.device)        # noqa: E731
         sb = np.full(len(lb), -1)
-        return trials.evaluate_scores(eng, A, B, r, i32(la), i32(sa), i32(lb), i32(sb), kind, score_range, p_target, c_miss, c_fa, max_refine)
+        return eng, (A, B, r, i32(la), i32(sa), i32(lb), i32(sb)), kind
 
     def tune_verification(self, audio_paths, speaker_ids, candidates, score_range=None, p_target: float = 0.01, c_miss: float = 1.0,
                           c_fa: float = 1.0, max_refine: int = 8) -> Dict[str, Any]:
@@ -903,7 +914,7 @@ class Backend(EmbeddingBackend):
         """One recording on the torch-free path (SDK_NO_TORCH=1; the cosine rule only): embedded, scored and downloaded on the null stream."""
         samples, starts, W, spans = self._windows(audio_path, None)
         _, idx, sc = self.embed_tables_host(samples, {W: starts}, batch)[W]
-        return aggregate_matches(idx[:, 0], sc[:, 0], spans, batch, threshold)
+        return self.rule.rows(self, (idx[:, 0], sc[:, 0]), spans, batch, threshold)      # the cosine rule's rows, calibration included
 
     def identify_speaker(self, audio_path: Path, candidates: List[Dict[str, Any]], threshold: float = 0.354) -> List[Dict[str, Any]]:
         """With a cohort configured (SDK_COHORT) a window's winner is its normalised top-1 and it votes when z >= SDK_COHORT_THRESHOLD: the raw
@@ -949,3 +960,23 @@ class Backend(EmbeddingBackend):
         out.update((key, h[key]) for key in self.rule.verify_keys)          # norm_score under a cohort, llr under a scoring PLDA
         return out
 
+
+def calibrate_verification(be: Backend, audio_paths, speaker_ids, candidates, out_path=None, score_range=None, p_target: float = 0.01,
+                           c_miss: float = 1.0, c_fa: float = 1.0, grad_tol: float = 1e-10, max_passes: int = 24, max_refine: int = 8):
+    """What a score of Backend `be`'s decision rule means, on a labelled development set (the arguments and the trials of
+    Backend.score_verification) -> trials.Calibration: the affine map llr = a * score + b fitted by prior-weighted logistic regression on the
+    device, Cllr before and after, the actual DCF at the Bayes threshold beside minDCF (trials.py states the rule; parity with outside
+    toolkits is unpinned).  out_path: the calibration is also written there (trials.save_calibration), the file SDK_SCORE_CALIBRATION names.
+    With a cohort configured (SDK_COHORT): ValueError - AS-norm trials are not built.  A fit that did not converge (separable classes have no
+    finite minimiser): ValueError.
+
+    A function of the Backend, not a method of it: the Backend's public surface is pinned name for name (tests/test_rules_cpu.py)."""
+    from . import trials
+    eng, tensors, kind = be._verification_trials("calibrate_verification", audio_paths, speaker_ids, candidates)
+    cal = trials.calibrate_scores(eng, *tensors, kind, score_range, p_target, c_miss, c_fa, grad_tol, max_passes, max_refine)
+    if not cal.converged:
+        raise ValueError(f"calibrate_verification: the fit did not converge in {cal.n_passes} passes (a={cal.a:g}, b={cal.b:g}, gradient {cal.grad}): "
+                         "classes that a threshold separates without error have no finite minimiser - use more, or harder, development trials")
+    if out_path is not None:
+        trials.save_calibration(cal, out_path)
+    return cal

@@ -221,3 +221,37 @@ class ScoreMixin:
         check(self.lib.sdk_trial_hist(self.ctx, A.data_ptr(), N, B.data_ptr(), r.data_ptr(), M, K, la.data_ptr(), sa.data_ptr(), lb.data_ptr(),
                                       sb.data_ptr(), lo, scale, shift, base, max_blocks, out.data_ptr(), _stream()), "sdk_trial_hist")
         return out[:8192].view(2, 4096), out[8192:8194], out[8194:8196], out[8196:8198], out[8198:8199]
+
+
+# ---- calibration of verification scores (trials.py; csrc/trials.hip)
+def trial_calib(engine, A: torch.Tensor, B: torch.Tensor, r: torch.Tensor, la: torch.Tensor, sa: torch.Tensor, lb: torch.Tensor, sb: torch.Tensor,
+                a: float, c: float, max_blocks: int = 0):
+    """One pass of the calibration objective over the trials of Engine.trial_hist (the same tensors) at the map z = a * s + c ->
+    (n [2] int64, sums [2, 7] float64, nonfinite [2] int64, excluded [1] int64) device tensors; row 0 nontarget, row 1 target; the sums are
+    L, W0, W1, H0, H1, H2, S1 of trials.py (sdk_trial_calib).  Nothing waits.  max_blocks: 0 = the default grid, else a cap on the
+    workgroups (the counts do not depend on it; the sums change by rounding).
+
+    A function of the engine, not a method of it: Engine's public surface is pinned name for name (tests/test_ops_layout_cpu.py)."""
+    who = "trial_calib"
+    N, K = (int(v) for v in _args.tensor(who, "A", A, "float64", (None, None)).shape)
+    if K < 16 or K > 512 or K % 16:
+        raise ValueError(f"trial_calib: K={K} not supported (a multiple of 16 in 16 .. 512)")
+    M = int(_args.tensor(who, "B", B, "float64", (None, K)).shape[0])
+    if not (1 <= N <= 1 << 20 and 1 <= M <= 1 << 20):
+        raise ValueError(f"trial_calib: N={N} test rows, M={M} model rows (1 .. 2^20 each)")
+    _args.tensor(who, "r", r, "float64", (M,))
+    for name, t, n in (("la", la, N), ("sa", sa, N), ("lb", lb, M), ("sb", sb, M)):
+        _args.tensor(who, name, t, "int32", (n,))
+    a, c, max_blocks = float(a), float(c), int(max_blocks)
+    if not (np.isfinite(a) and np.isfinite(c)):
+        raise ValueError(f"trial_calib: a={a}, c={c} (the map z = a s + c: both finite)")
+    if max_blocks < 0:
+        raise ValueError(f"trial_calib: max_blocks={max_blocks} (0: the default grid, else a cap on the workgroups)")
+    nbytes = engine._workspace_bytes("sdk_trial_calib_workspace_bytes", N, M, max_blocks)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=A.device)
+    sums = torch.empty((2, 7), dtype=torch.float64, device=A.device)
+    counts = torch.empty((5,), dtype=torch.int64, device=A.device)                     # uint64 counters, all below 2^40
+    check(engine.lib.sdk_trial_calib(engine.ctx, A.data_ptr(), N, B.data_ptr(), r.data_ptr(), M, K, la.data_ptr(), sa.data_ptr(), lb.data_ptr(),
+                                     sb.data_ptr(), a, c, max_blocks, sums.data_ptr(), counts.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+          "sdk_trial_calib")
+    return counts[0:2], sums, counts[2:4], counts[4:5]

@@ -11,6 +11,7 @@ A rule holds its settings and its lazily loaded model (cohort(be) / model(be)) a
   rows(be, columns, spans, batch, threshold)   the result rows from the downloaded top-1 columns (in enqueue's order)
   refuse_trials() / trial_matrices(be, E, batch)   what score_verification scores
   verify_keys   the keys of a result row that verify_speaker copies beside the ABC's own
+  calibrated(rows, key)   with SDK_SCORE_CALIBRATION: the rows with calibrated_llr and posterior added (below); else the rows as they are
 
 The Backend keeps what is per candidate set and cached on it (profile_tensors, profile_stats, speaker_table; `cached` below is their one
 cache) and the public score_windows* calls.  This module imports neither torch nor the engine until a rule computes.
@@ -98,6 +99,8 @@ class Rule:
     score_plda_paths = None
     score_plda_dim, score_plda_threshold, score_plda_count = 128, 0.0, True
     loaded = None                                   # Plda: (plda.Plda, content digest) once model(be) has read the files
+    calibration = None                              # trials.Calibration of SDK_SCORE_CALIBRATION
+    score_prior = 0.5                               # SDK_SCORE_PRIOR
 
     def cohort(self, be):
         return None
@@ -107,6 +110,23 @@ class Rule:
 
     def refuse_trials(self) -> None:
         """Raise where score_verification has no matrix form of this rule; before it does any work."""
+
+    def calibrated(self, rows, key: str):
+        """With a calibration configured every row gains calibrated_llr = a * row[key] + b in float64 and
+        posterior = sigmoid(calibrated_llr + logit(score_prior)); nothing else changes - no decision, threshold, order or existing key.
+        row[key] is the mean score of the speaker's voting windows (the cosine, or the llr under PLDA); an affine map commutes with the
+        mean, so calibrated_llr is the mean of the windows' calibrated log-likelihood ratios.  Without one the rows are returned as they
+        are."""
+        cal = self.calibration
+        if cal is None:
+            return rows
+        shift = float(np.log(self.score_prior / (1.0 - self.score_prior)))
+        for row in rows:
+            llr = float(cal.llr(row[key]))
+            x = llr + shift
+            row["calibrated_llr"] = llr
+            row["posterior"] = float(1.0 / (1.0 + np.exp(-x))) if x >= 0 else float(np.exp(x) / (1.0 + np.exp(x)))
+        return rows
 
 
 class Cosine(Rule):
@@ -118,7 +138,7 @@ class Cosine(Rule):
         return be.engine().affinity_topk(*emb, Pn, Pb, rpm, k=min(k, len(batch)))
 
     def rows(self, be, cols, spans, batch, threshold: float):
-        return aggregate_matches(cols[0], cols[1], spans, batch, threshold)
+        return self.calibrated(aggregate_matches(cols[0], cols[1], spans, batch, threshold), "similarity")
 
     def trial_matrices(self, be, E, batch):
         """Test rows E against the candidates' enrolled embeddings -> (A, B, r, the label of every model row, kind, {speaker id: label})."""
@@ -199,7 +219,8 @@ class Plda(Rule):
     def rows(self, be, cols, spans, batch, threshold: float):
         from .plda_score import aggregate_matches_plda
         _, _, speakers, first, counts = be.speaker_table(batch)
-        return aggregate_matches_plda(cols[0], cols[1], spans, speakers, [batch.embedding_ids[int(p)] for p in first], counts, self.score_plda_threshold)
+        return self.calibrated(aggregate_matches_plda(cols[0], cols[1], spans, speakers, [batch.embedding_ids[int(p)] for p in first], counts,
+                                                      self.score_plda_threshold), "llr")
 
     def trial_matrices(self, be, E, batch):
         """Test rows E against the candidates' SPEAKERS (speaker_table) -> (A, B, r, the label of every model row, kind, {speaker id: label})."""
@@ -210,7 +231,8 @@ class Plda(Rule):
 
 
 def rule_from_env(environ) -> Rule:
-    """The configured rule, or the refusal of a setting that does not hold together.  Reads no file."""
+    """The configured rule, or the refusal of a setting that does not hold together.  Reads no file but the calibration's
+    (SDK_SCORE_CALIBRATION: a few hundred bytes of JSON, whose kind must be the rule's)."""
     lite = environ.get("SDK_NO_TORCH") == "1"
     # adaptive score normalisation (snorm.py): off unless a cohort is configured
     cohort, topk, thr = environ.get("SDK_COHORT") or None, int(environ.get("SDK_COHORT_TOPK", "300")), environ.get("SDK_COHORT_THRESHOLD")
@@ -256,4 +278,24 @@ def rule_from_env(environ) -> Rule:
             raise ValueError(f"SDK_SCORE_PLDA_COUNT={cnt!r}: 1 (a speaker's count is the number of their enrolled embeddings) or 0 (it is 1)")
         rule = Plda((tpath, ppath), int(dim), llr, cnt == "1")
     rule.cohort_topk = topk
+    # the calibration of the rule's score (trials.py): off unless a file is configured
+    cpath = environ.get("SDK_SCORE_CALIBRATION") or None
+    if cpath:
+        if cohort:
+            raise ValueError("SDK_SCORE_CALIBRATION together with SDK_COHORT: calibrations are fitted to the cosine or the PLDA rule "
+                             "(backend.calibrate_verification(backend, ...) refuses a cohort); unset one of them")
+        prior = environ.get("SDK_SCORE_PRIOR", "0.5")
+        try:
+            rule.score_prior = float(prior)
+        except ValueError:
+            raise ValueError(f"SDK_SCORE_PRIOR={prior!r}: the prior of a target, a float inside (0, 1)") from None
+        if not 0.0 < rule.score_prior < 1.0:
+            raise ValueError(f"SDK_SCORE_PRIOR={prior!r}: the prior of a target, a float inside (0, 1)")
+        from .trials import load_calibration
+        cal = load_calibration(cpath)
+        if cal.kind != rule.kind:
+            raise ValueError(f"SDK_SCORE_CALIBRATION={cpath}: fitted to the {cal.kind!r} rule, the configured rule is {rule.kind!r}: "
+                             "calibrate under the settings you score with (backend.calibrate_verification(backend, ...))")
+        rule.calibration = cal
+        rule.verify_keys = tuple(rule.verify_keys) + ("calibrated_llr", "posterior")
     return rule

@@ -36,6 +36,44 @@ On the device: ops.Engine.trial_hist (csrc/trials.hip: the product tile by tile 
 histogram in LDS; the score matrix is never written).  Everything after the product is integer arithmetic: the counts are bit-identical run
 to run.  This module holds the numpy restatement of a pass, the metric functions on counts and the driver of pass 1 and the zooms; it imports
 neither torch nor the library at module level.
+
+Calibration: an affine map llr = a s + b from the score s of a decision rule to a log-likelihood ratio, fitted by prior-weighted
+logistic regression on labelled trials, and the cost of the log-likelihood ratio (Cllr) before and after (this build's statement; parity
+with BOSARIS, Kaldi or any outside toolkit is unpinned, as for the metrics above).
+
+  trials     Trials, classes, exclusions and the score s(i, j) are exactly those of the rule above.  A trial whose score is not finite
+             (NaN, +inf or -inf) is counted in nonfinite[class] and left out of every sum; excluded trials are counted in `excluded`.
+  a pass     takes (a, c).  With y = +1 for a target and -1 for a nontarget:
+               z = a * s + c      ONE float64 multiplication, then ONE float64 addition (never an FMA)
+               m = y z,  e = exp(-|m|)
+               loss = max(-m, 0) + log1p(e)                           the stable form of softplus(-m)
+               p = e / (1 + e),  q = 1 / (1 + e),  w = p when m >= 0, else q      w = sigmoid(-m)
+               v = p * q                                              w (1 - w); 1 - w is the OTHER quotient, never a subtraction (for m far
+                                                                      below 0 the subtraction would cancel: w rounds to 1)
+             Per class the pass returns the count n of the trials summed and seven float64 sums over them:
+               L = sum loss, W0 = sum w, W1 = sum w s, H0 = sum v, H1 = sum v s, H2 = sum (v s) s, S1 = sum s
+             and nonfinite[2], excluded.
+  objective  The effective prior P = p c_miss / (p c_miss + (1 - p) c_fa) (defaults as minDCF: 0.01, 1, 1), theta = ln(P / (1 - P)).
+               J(a, b) = P L_1 / n_1 + (1 - P) L_0 / n_0    at c = b + theta
+             d loss / dm = -w and d2 loss / dm2 = v, with dm/da = y s and dm/db = y, so with u_1 = P / n_1 and u_0 = (1 - P) / n_0:
+               dJ/da = u_0 W1_0 - u_1 W1_1        dJ/db = u_0 W0_0 - u_1 W0_1
+               Haa = u_0 H2_0 + u_1 H2_1          Hab = u_0 H1_0 + u_1 H1_1          Hbb = u_0 H0_0 + u_1 H0_1
+               Cllr(a, b) = (L_1 / n_1 + L_0 / n_0) / (2 ln 2)    at c = b
+  fit        Start: the minimiser of J on pass 1's coarse counts - the 4096 bin centres in score units with the counts as weights, the
+             trials in under / over at lo / hi (host only).  Then damped Newton on the device sums: the step -H^-1 grad (the gradient
+             itself when H is not positive definite) is halved until the point it leads to has a J that is not above the current one
+             (8 x 2^-53 of it are allowed for the rounding of J at the minimum); every point tried costs one pass.  Stop when both gradient components are at most
+             grad_tol (1e-10) times J in magnitude, or after max_passes (24) passes of the iteration.  Separable classes have no finite
+             minimiser: the result then says converged = False.  ValueError when either class is empty.
+  reported   cllr_raw: one pass at (1, 0).  cllr: one pass at (a, b).  min_cllr_coarse: the minimum Cllr of the COARSELY QUANTISED score -
+             pool-adjacent-violators on pass 1's bins (under, the 4096 bins, over: 4098 cells in score order), each pooled block's
+             log-likelihood ratio ln(T_g Nn / (N_g T)); a bound that any monotone map of the 4096-bin score can reach, not the minimum over
+             the unquantised score.  bayes_threshold = (-theta - b) / a in score units.  act_dcf: the normalised DCF of the metrics above at
+             the integer threshold q(bayes_threshold) (0 when it lies below lo, 2^24 at or above hi), exact from pass 1 and one zoom;
+             min_dcf beside it.  n_passes counts every pass: the two reported ones and the iteration's.
+
+On the device: ops_score.trial_calib (csrc/trials.hip, tr_calib_kernel: trial_hist's tiling and product, the sums formed in the product's
+epilogue in a fixed order without a float atomic - bit-identical run to run, a function of the inputs and the grid alone).
 """
 from __future__ import annotations
 
@@ -351,15 +389,8 @@ def plda_test_rows(engine, E_test, plda):
     return torch.cat([X, X * X], dim=1).contiguous()
 
 
-def evaluate(engine, E_test, labels, sessions, E_model, model_labels, model_sessions, kind: str = "cosine", plda=None, count_by_book: bool = True,
-             score_range: Optional[Tuple[float, float]] = None, p_target: float = 0.01, c_miss: float = 1.0, c_fa: float = 1.0,
-             max_refine: int = 8, max_blocks: int = 0) -> VerificationResult:
-    """Every test row against every model row under one decision rule -> VerificationResult.  E_test [N, d], E_model [P, d]: fp32 unit rows
-    on the device; labels, sessions [N] and model_labels, model_sessions [P]: integers (a negative label: the row takes part in no trial;
-    session -1: no session).  kind="cosine": the model rows are scored one by one (d a multiple of 16).  kind="plda": `plda` is a plda.Plda
-    of this embedding space; the model rows are grouped by label into speakers and pooled (Engine.plda_enroll, count_by_book as
-    SDK_SCORE_PLDA_COUNT), the trials are test rows against SPEAKERS.  score_range defaults to (-1 - 2^-16, 1 + 2^-16) for cosine and
-    (-1024, 1024) for PLDA."""
+def trial_tensors(engine, E_test, labels, sessions, E_model, model_labels, model_sessions, kind: str = "cosine", plda=None, count_by_book: bool = True):
+    """The trials of evaluate / calibrate in matrix form -> (A, B, r, la, sa, lb, sb) device tensors (evaluate states the arguments)."""
     import torch
     if not (isinstance(E_test, torch.Tensor) and isinstance(E_model, torch.Tensor) and E_test.is_cuda and E_model.is_cuda and E_test.dim() == 2
             and E_model.dim() == 2 and E_test.shape[1] == E_model.shape[1] and E_test.dtype == torch.float32 and E_model.dtype == torch.float32):
@@ -380,4 +411,363 @@ def evaluate(engine, E_test, labels, sessions, E_model, model_labels, model_sess
         lb, sb = torch.from_numpy(spk).to(dev), torch.from_numpy(sess).to(dev)
     else:
         raise ValueError(f"evaluate: kind={kind!r} ('cosine' or 'plda')")
-    return evaluate_scores(engine, A, B, r, la, sa, lb, sb, kind, score_range, p_target, c_miss, c_fa, max_refine, max_blocks)
+    return A, B, r, la, sa, lb, sb
+
+
+def evaluate(engine, E_test, labels, sessions, E_model, model_labels, model_sessions, kind: str = "cosine", plda=None, count_by_book: bool = True,
+             score_range: Optional[Tuple[float, float]] = None, p_target: float = 0.01, c_miss: float = 1.0, c_fa: float = 1.0,
+             max_refine: int = 8, max_blocks: int = 0) -> VerificationResult:
+    """Every test row against every model row under one decision rule -> VerificationResult.  E_test [N, d], E_model [P, d]: fp32 unit rows
+    on the device; labels, sessions [N] and model_labels, model_sessions [P]: integers (a negative label: the row takes part in no trial;
+    session -1: no session).  kind="cosine": the model rows are scored one by one (d a multiple of 16).  kind="plda": `plda` is a plda.Plda
+    of this embedding space; the model rows are grouped by label into speakers and pooled (Engine.plda_enroll, count_by_book as
+    SDK_SCORE_PLDA_COUNT), the trials are test rows against SPEAKERS.  score_range defaults to (-1 - 2^-16, 1 + 2^-16) for cosine and
+    (-1024, 1024) for PLDA."""
+    tensors = trial_tensors(engine, E_test, labels, sessions, E_model, model_labels, model_sessions, kind, plda, count_by_book)
+    return evaluate_scores(engine, *tensors, kind, score_range, p_target, c_miss, c_fa, max_refine, max_blocks)
+
+
+# ---- calibration: what a score means ---------------------------------------------------------------------------------------------------------
+
+
+class CalibSums(NamedTuple):
+    """One calibration pass on the host; row 0 nontarget, row 1 target; the sums in the order L, W0, W1, H0, H1, H2, S1."""
+    n: np.ndarray                  # [2] int64
+    sums: np.ndarray               # [2, 7] float64
+    nonfinite: np.ndarray          # [2] int64
+    excluded: int
+
+
+def effective_prior(p_target: float = 0.01, c_miss: float = 1.0, c_fa: float = 1.0) -> float:
+    p, cm, cf = float(p_target), float(c_miss), float(c_fa)
+    if not (0.0 < p < 1.0 and cm > 0.0 and cf > 0.0 and math.isfinite(cm) and math.isfinite(cf)):
+        raise ValueError(f"calibrate: p_target={p} (inside (0, 1)), c_miss={cm}, c_fa={cf} (finite, above 0)")
+    return p * cm / (p * cm + (1.0 - p) * cf)
+
+
+def _terms(s: np.ndarray, y: np.ndarray, a: float, c: float) -> np.ndarray:
+    """The seven terms [7, n] of finite float64 scores s with y = +1 / -1, operation for operation as the kernel forms them."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        z = np.float64(a) * s + np.float64(c)              # numpy rounds the product, then the sum
+        m = y * z
+        e = np.exp(-np.abs(m))
+        d = 1.0 + e
+        p, q = e / d, 1.0 / d
+        w = np.where(m >= 0.0, p, q)
+        v = p * q
+        vs = v * s
+        return np.stack([np.maximum(-m, 0.0) + np.log1p(e), w, w * s, v, vs, vs * s, s])
+
+
+def calib_sums_host(S, cls, a: float, c: float, weights=None) -> CalibSums:
+    """The numpy restatement of a calibration pass over a score array S (any shape) with classes cls (1 target, 0 nontarget, negative =
+    excluded).  weights (same shape, non-negative integers; default 1): a score stands for that many trials (fit_from_counts)."""
+    S = np.asarray(S, dtype=np.float64).ravel()
+    cls = np.asarray(cls).ravel()
+    wt = np.ones(S.shape, np.int64) if weights is None else np.asarray(weights).ravel().astype(np.int64)
+    keep = cls >= 0
+    excluded = int(wt[~keep].sum())
+    S, cls, wt = S[keep], cls[keep].astype(np.int64), wt[keep]
+    fin = np.isfinite(S)
+    n, sums, nonfinite = np.zeros(2, np.int64), np.zeros((2, 7), np.float64), np.zeros(2, np.int64)
+    for k in (0, 1):
+        sel = cls == k
+        nonfinite[k] = int(wt[sel & ~fin].sum())
+        s, g = S[sel & fin], wt[sel & fin]
+        n[k] = int(g.sum())
+        if len(s):
+            t = _terms(s, np.full(s.shape, 1.0 if k else -1.0), a, c)
+            sums[k] = (t * g[None, :]).sum(axis=1) if weights is not None else t.sum(axis=1)
+    return CalibSums(n, sums, nonfinite, excluded)
+
+
+def objective(cs: CalibSums, prior: float):
+    """J, its gradient [2] and Hessian [2, 2] in (a, b) from the sums of a pass at c = b + theta (the docstring's formulas)."""
+    n0, n1 = int(cs.n[0]), int(cs.n[1])
+    if n0 == 0 or n1 == 0:
+        raise ValueError(f"calibration needs both classes: {n1} target and {n0} nontarget trials with a finite score "
+                         f"({int(np.sum(cs.nonfinite))} not finite, {int(cs.excluded)} excluded)")
+    u0, u1 = (1.0 - prior) / n0, prior / n1
+    x0, x1 = cs.sums[0], cs.sums[1]
+    J = u1 * x1[0] + u0 * x0[0]
+    g = np.asarray([u0 * x0[2] - u1 * x1[2], u0 * x0[1] - u1 * x1[1]])
+    H = np.asarray([[u0 * x0[5] + u1 * x1[5], u0 * x0[4] + u1 * x1[4]], [u0 * x0[4] + u1 * x1[4], u0 * x0[3] + u1 * x1[3]]])
+    return float(J), g, H
+
+
+def cllr_of(cs: CalibSums) -> float:
+    """Cllr from the sums of a pass at c = b."""
+    n0, n1 = int(cs.n[0]), int(cs.n[1])
+    if n0 == 0 or n1 == 0:
+        raise ValueError(f"Cllr needs both classes: {n1} target and {n0} nontarget trials with a finite score")
+    return float((cs.sums[1][0] / n1 + cs.sums[0][0] / n0) / (2.0 * math.log(2.0)))
+
+
+class FitResult(NamedTuple):
+    a: float
+    b: float
+    J: float
+    grad: Tuple[float, float]
+    n_passes: int
+    converged: bool
+
+
+def newton_fit(sums: Callable[[float, float], CalibSums], a0: float, b0: float, prior: float, grad_tol: float = 1e-10,
+               max_passes: int = 24) -> FitResult:
+    """The damped Newton iteration of the rule from (a0, b0); sums(a, c) is one pass."""
+    theta = math.log(prior / (1.0 - prior))
+    a, b = float(a0), float(b0)
+    J, g, H = objective(sums(a, b + theta), prior)
+    passes = 1
+    met = lambda J, g: math.isfinite(J) and J > 0.0 and bool(np.all(np.abs(g) <= grad_tol * J))        # noqa: E731
+    while not met(J, g) and passes < max_passes:
+        det = H[0, 0] * H[1, 1] - H[0, 1] * H[1, 0]
+        if math.isfinite(det) and det > 0.0 and H[0, 0] > 0.0:
+            step = -np.asarray([H[1, 1] * g[0] - H[0, 1] * g[1], H[0, 0] * g[1] - H[1, 0] * g[0]]) / det
+        else:
+            step = -g
+        if not np.all(np.isfinite(step)):
+            break
+        t, moved = 1.0, False
+        while passes < max_passes:
+            na, nb = a + t * step[0], b + t * step[1]
+            nJ, ng, nH = objective(sums(na, nb + theta), prior)
+            passes += 1
+            if nJ <= J * (1.0 + 8.0 * 2.0 ** -53):
+                a, b, J, g, H, moved = na, nb, nJ, ng, nH, True
+                break
+            t *= 0.5
+        if not moved:
+            break
+    return FitResult(a, b, J, (float(g[0]), float(g[1])), passes, met(J, g) and math.isfinite(a) and math.isfinite(b))
+
+
+def _coarse_points(coarse: PassCounts, lo: float, hi: float):
+    """Pass 1 as weighted scores: under at lo, the 4096 bin centres, over at hi -> (x [4098], targets [4098], nontargets [4098])."""
+    scale = scale_of(lo, hi)
+    centres = lo + (BINS * np.arange(BINS) + BINS // 2) / scale
+    x = np.concatenate([[float(lo)], centres, [float(hi)]])
+    cnt = lambda k: np.concatenate([[int(coarse.under[k])], coarse.hist[k].astype(np.int64), [int(coarse.over[k])]])        # noqa: E731
+    return x, cnt(1), cnt(0)
+
+
+def fit_from_counts(coarse: PassCounts, lo: float, hi: float, prior: float, grad_tol: float = 1e-10, max_passes: int = 64) -> FitResult:
+    """The starting point: the fit on pass 1's coarse counts, on the host (a separable or degenerate set of counts ends with
+    converged = False and the caller starts from where it stopped)."""
+    totals(coarse)
+    x, t, n = _coarse_points(coarse, lo, hi)
+    S, cls, wt = np.concatenate([x, x]), np.concatenate([np.ones(len(x), np.int64), np.zeros(len(x), np.int64)]), np.concatenate([t, n])
+    live = wt > 0
+    S, cls, wt = S[live], cls[live], wt[live]
+    # Newton starts where the scores are not saturated: the map of two Gaussians of the classes' means and the pooled variance
+    mean = lambda k: float((S[cls == k] * wt[cls == k]).sum() / wt[cls == k].sum())        # noqa: E731
+    m0, m1 = mean(0), mean(1)
+    var = float(sum((wt[cls == k] * (S[cls == k] - m) ** 2).sum() for k, m in ((0, m0), (1, m1))) / wt.sum())
+    a0 = (m1 - m0) / var if var > 0.0 and m1 > m0 else (1.0 / math.sqrt(var) if var > 0.0 else 1.0)
+    return newton_fit(lambda a, c: calib_sums_host(S, cls, a, c, wt), a0, -a0 * (m0 + m1) / 2.0, prior, grad_tol, max_passes)
+
+
+def pav_min_cllr(coarse: PassCounts) -> float:
+    """The minimum Cllr of the coarsely quantised score: pool-adjacent-violators over the 4098 cells of pass 1 in score order (under, the
+    bins, over; empty cells skipped), exact integer comparisons; a pooled block with T_g targets and N_g nontargets has the
+    log-likelihood ratio ln(T_g Nn / (N_g T)).  ValueError when either class is empty."""
+    T, Nn = totals(coarse)
+    t = [int(coarse.under[1])] + _ints(coarse.hist[1]) + [int(coarse.over[1])]
+    n = [int(coarse.under[0])] + _ints(coarse.hist[0]) + [int(coarse.over[0])]
+    blocks = []                                              # (targets, trials), the target fraction non-decreasing along the stack
+    for tg, ng in zip(t, n):
+        if tg + ng == 0:
+            continue
+        ct, cn = tg, tg + ng
+        while blocks and blocks[-1][0] * cn > ct * blocks[-1][1]:
+            pt, pn = blocks.pop()
+            ct, cn = ct + pt, cn + pn
+        blocks.append((ct, cn))
+    ct_sum = cn_sum = 0.0
+    for tg, tot in blocks:
+        ng = tot - tg
+        if tg:
+            ct_sum += tg * math.log1p((ng * T) / (tg * Nn))          # log(1 + exp(-llr_g))
+        if ng:
+            cn_sum += ng * math.log1p((tg * Nn) / (ng * T))          # log(1 + exp(+llr_g))
+    return (ct_sum / T + cn_sum / Nn) / (2.0 * math.log(2.0))
+
+
+def threshold_q(threshold: float, lo: float, hi: float) -> int:
+    """The integer threshold of a score threshold: q(threshold) as a pass forms it, 0 below the range, 2^24 at or above hi (and for NaN)."""
+    t = (np.float64(threshold) - np.float64(lo)) * np.float64(scale_of(lo, hi))
+    if t != t or t >= float(Q_MAX):
+        return Q_MAX
+    return 0 if t < 0.0 else int(math.floor(t))
+
+
+def dcf_at(coarse: PassCounts, zoom: Callable[[int], PassCounts], tq: int, p_target: float, c_miss: float, c_fa: float) -> float:
+    """The normalised DCF of accepting q >= tq, exact: from pass 1 when tq is a coarse threshold, else with one zoom."""
+    T, Nn = totals(coarse)
+    b, j = divmod(int(tq), BINS)
+    if j == 0:
+        miss, fa = _cumulative(coarse)
+        return _dcf(miss[b], fa[b], T, Nn, float(p_target), float(c_miss), float(c_fa))
+    fine = zoom(b)
+    _check_zoom(coarse, fine, b)
+    fmiss, ffa = _cumulative(fine)
+    return _dcf(fmiss[j], ffa[j], T, Nn, float(p_target), float(c_miss), float(c_fa))
+
+
+@dataclass
+class Calibration:
+    kind: str
+    a: float
+    b: float
+    prior: float                                         # the effective prior P of the fit
+    score_range: Tuple[float, float]
+    cllr_raw: float = math.nan
+    cllr: float = math.nan
+    min_cllr_coarse: float = math.nan
+    bayes_threshold: float = math.nan
+    act_dcf: float = math.nan
+    min_dcf: float = math.nan
+    n_target: int = 0
+    n_nontarget: int = 0
+    n_nonfinite: int = 0
+    n_excluded: int = 0
+    n_passes: int = 0
+    converged: bool = False
+    grad: Tuple[float, float] = (math.nan, math.nan)
+    p_target: float = 0.01
+    c_miss: float = 1.0
+    c_fa: float = 1.0
+
+    def llr(self, score):
+        """a * score + b in float64."""
+        return np.float64(self.a) * np.float64(score) + np.float64(self.b)
+
+
+def calibration_from_passes(coarse: PassCounts, zoom: Callable[[int], PassCounts], sums: Callable[[float, float], CalibSums], kind: str, lo: float,
+                            hi: float, p_target: float = 0.01, c_miss: float = 1.0, c_fa: float = 1.0, grad_tol: float = 1e-10,
+                            max_passes: int = 24, max_refine: int = 8) -> Calibration:
+    """The fit and every reported value of the rule from pass 1, a zoom callback and a calibration-pass callback sums(a, c)."""
+    done: Dict[int, PassCounts] = {}
+
+    def cached(b: int) -> PassCounts:
+        if b not in done:
+            done[b] = zoom(b)
+        return done[b]
+
+    calls = [0]
+
+    def counted(a: float, c: float) -> CalibSums:
+        calls[0] += 1
+        return sums(a, c)
+
+    totals(coarse)
+    prior = effective_prior(p_target, c_miss, c_fa)
+    theta = math.log(prior / (1.0 - prior))
+    raw = counted(1.0, 0.0)
+    cllr_raw = cllr_of(raw)
+    start = fit_from_counts(coarse, lo, hi, prior)
+    a0, b0 = (start.a, start.b) if math.isfinite(start.a) and math.isfinite(start.b) and start.a > 0.0 else (1.0, 0.0)
+    fit = newton_fit(counted, a0, b0, prior, grad_tol, max_passes)
+    final = counted(fit.a, fit.b)
+    thr = (-theta - fit.b) / fit.a if fit.a != 0.0 else math.nan
+    act = dcf_at(coarse, cached, threshold_q(thr, lo, hi), p_target, c_miss, c_fa)
+    d = min_dcf_from_counts(coarse, cached, lo, hi, p_target, c_miss, c_fa, max_refine)
+    return Calibration(kind=kind, a=fit.a, b=fit.b, prior=prior, score_range=(float(lo), float(hi)), cllr_raw=cllr_raw, cllr=cllr_of(final),
+                       min_cllr_coarse=pav_min_cllr(coarse), bayes_threshold=thr, act_dcf=act, min_dcf=d["min_dcf"], n_target=int(final.n[1]),
+                       n_nontarget=int(final.n[0]), n_nonfinite=int(final.nonfinite.sum()), n_excluded=int(final.excluded), n_passes=calls[0],
+                       converged=fit.converged, grad=fit.grad, p_target=float(p_target), c_miss=float(c_miss), c_fa=float(c_fa))
+
+
+def sums_to_host(dev) -> CalibSums:
+    """ops_score.trial_calib's device tensors -> CalibSums (this is where the host waits for the pass)."""
+    n, sums, nonfinite, excluded = (t.cpu().numpy() for t in dev)
+    return CalibSums(n.astype(np.int64), sums.astype(np.float64), nonfinite.astype(np.int64), int(excluded[0]))
+
+
+def calibrate_scores(engine, A, B, r, la, sa, lb, sb, kind: str, score_range: Optional[Tuple[float, float]] = None, p_target: float = 0.01,
+                     c_miss: float = 1.0, c_fa: float = 1.0, grad_tol: float = 1e-10, max_passes: int = 24, max_refine: int = 8,
+                     max_blocks: int = 0) -> Calibration:
+    """The calibration of trials already in matrix form (device tensors as Engine.trial_hist takes them), beside evaluate_scores: pass 1 and
+    the zooms through Engine.trial_hist, the calibration passes through ops_score.trial_calib."""
+    if kind not in ("cosine", "plda"):
+        raise ValueError(f"calibrate: kind={kind!r} ('cosine' or 'plda')")
+    from .ops_score import trial_calib
+    lo, hi = score_range if score_range is not None else (COSINE_RANGE if kind == "cosine" else PLDA_RANGE)
+    scale_of(lo, hi)
+
+    def run(shift: int, base: int) -> PassCounts:
+        return counts_to_host(engine.trial_hist(A, B, r, la, sa, lb, sb, lo, hi, shift=shift, base=base, max_blocks=max_blocks))
+
+    return calibration_from_passes(run(COARSE_SHIFT, 0), lambda b: run(0, BINS * b),
+                                   lambda a, c: sums_to_host(trial_calib(engine, A, B, r, la, sa, lb, sb, a, c, max_blocks=max_blocks)), kind, lo, hi,
+                                   p_target, c_miss, c_fa, grad_tol, max_passes, max_refine)
+
+
+CALIBRATION_KEYS = ("kind", "a", "b", "prior", "score_range", "cllr_raw", "cllr", "min_cllr_coarse", "bayes_threshold", "act_dcf", "min_dcf",
+                    "n_target", "n_nontarget", "n_nonfinite", "n_excluded", "n_passes", "converged", "grad", "p_target", "c_miss", "c_fa")
+
+
+def save_calibration(cal: Calibration, path) -> None:
+    """A small JSON file of settings: every field of the Calibration, in standard JSON - a figure that is not finite (one never computed,
+    or of a fit that did not converge) is written as null and read back as NaN.  Refused (ValueError): what load_calibration refuses."""
+    import json
+    _check_map(path, cal.kind, float(cal.a), float(cal.b), float(cal.prior), tuple(float(v) for v in cal.score_range))
+    num = lambda v: float(v) if math.isfinite(float(v)) else None        # noqa: E731
+    doc: Dict[str, Any] = {}
+    for k in CALIBRATION_KEYS:
+        v = getattr(cal, k)
+        if k in ("score_range", "grad"):
+            doc[k] = [num(x) for x in v]
+        elif isinstance(v, (bool, np.bool_)):
+            doc[k] = bool(v)
+        elif isinstance(v, (int, np.integer)):
+            doc[k] = int(v)
+        elif isinstance(v, (float, np.floating)):
+            doc[k] = num(v)
+        else:
+            doc[k] = v
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1, allow_nan=False)
+        f.write("\n")
+
+
+def _check_map(path, kind, a: float, b: float, prior: float, score_range) -> None:
+    """What save_calibration and load_calibration refuse in the settings that are applied."""
+    if kind not in ("cosine", "plda"):
+        raise ValueError(f"{path}: kind={kind!r} ('cosine' or 'plda')")
+    if not (math.isfinite(a) and math.isfinite(b)):
+        raise ValueError(f"{path}: a={a}, b={b}: the map llr = a s + b needs finite numbers")
+    if a <= 0.0:
+        raise ValueError(f"{path}: a={a}: a calibration keeps the order of the scores, a > 0")
+    if not 0.0 < prior < 1.0:
+        raise ValueError(f"{path}: prior={prior}: the effective prior of the fit lies inside (0, 1)")
+    scale_of(*score_range)                                   # finite lo < hi
+
+
+def load_calibration(path) -> Calibration:
+    """save_calibration's file -> Calibration.  Refused (ValueError): a file that is not a JSON object with kind, a, b, prior and score_range,
+    an unknown kind, an a or b that is not finite, a <= 0, a prior outside (0, 1), a score_range that is not finite lo < hi.  A null
+    among the reported figures reads as NaN."""
+    import json
+    with open(path) as f:
+        doc = json.load(f)
+    if not isinstance(doc, dict) or any(k not in doc for k in ("kind", "a", "b", "prior", "score_range")):
+        raise ValueError(f"{path}: not a calibration file (a JSON object with kind, a, b, prior, score_range: trials.save_calibration writes one)")
+    try:
+        a, b, prior = float(doc["a"]), float(doc["b"]), float(doc["prior"])
+        lo, hi = (float(v) for v in doc["score_range"])
+    except (TypeError, ValueError):
+        raise ValueError(f"{path}: a, b, prior and the two ends of score_range must be numbers") from None
+    _check_map(path, doc["kind"], a, b, prior, (lo, hi))
+    nan = lambda v: math.nan if v is None else v                          # noqa: E731
+    rest = {k: nan(doc[k]) for k in CALIBRATION_KEYS if k in doc and k not in ("kind", "a", "b", "prior", "score_range", "grad")}
+    grad = tuple(float(nan(v)) for v in doc["grad"]) if "grad" in doc else (math.nan, math.nan)
+    return Calibration(kind=doc["kind"], a=a, b=b, prior=prior, score_range=(lo, hi), grad=grad, **rest)
+
+
+def calibrate(engine, E_test, labels, sessions, E_model, model_labels, model_sessions, kind: str = "cosine", plda=None, count_by_book: bool = True,
+              score_range: Optional[Tuple[float, float]] = None, p_target: float = 0.01, c_miss: float = 1.0, c_fa: float = 1.0,
+              grad_tol: float = 1e-10, max_passes: int = 24, max_refine: int = 8, max_blocks: int = 0) -> Calibration:
+    """evaluate's trials (the same arguments, the same matrices: trial_tensors) -> their Calibration."""
+    tensors = trial_tensors(engine, E_test, labels, sessions, E_model, model_labels, model_sessions, kind, plda, count_by_book)
+    return calibrate_scores(engine, *tensors, kind, score_range, p_target, c_miss, c_fa, grad_tol, max_passes, max_refine, max_blocks)
