@@ -56,7 +56,7 @@
  *     sdk_kmeans_rows_workspace_bytes  sdk_kmeans_rows                                                  spherical k-means on unit rows (cluster.kmeans_cluster)
  *     sdk_stream_state_bytes  sdk_stream_reset  sdk_stream_step  sdk_stream_flush  sdk_stream_centroids streaming diarization: online speaker tracking (stream.py)
  * BUILDING BLOCKS AND KNOBS - exported for the parity tests and the A/B tools, free to change between rounds, not for binding:
- *     sdk_conv_gemm*  sdk_colstats_finish  sdk_res2net_chain*  sdk_se_*  sdk_asp_*  sdk_rows_fc  (pieces of sdk_ecapa_forward)
+ *     sdk_conv_gemm*  sdk_colstats_finish  sdk_res2net_chain*  sdk_se_*  sdk_asp_*  sdk_rows_fc  sdk_rows_fc_path  (pieces of sdk_ecapa_forward)
  *     sdk_resnet_conv2d  sdk_resnet_pool  (pieces of sdk_resnet_forward)  sdk_resnet_masked_pool  (piece of sdk_resnet_forward_masked)
  *     sdk_sincnet_frontend  sdk_bilstm_layer  (pieces of sdk_segmentation_forward)
  *     sdk_set_option  sdk_set_gemm_variant  sdk_profile_begin / _end  sdk_debug_set_ptr  sdk_affinity_plan*  sdk_affinity_block_plan*  sdk_affinity_matvec_plan  sdk_conv_gemm_hp  sdk_resample_plan
@@ -297,6 +297,11 @@ int sdk_asp_stats_fmt(sdk_ctx* ctx, const uint16_t* h, int64_t ldh, int B, int T
 int sdk_rows_fc(sdk_ctx* ctx, const float* in, int64_t ldin, const float* in_scale, const float* in_shift,
                 const float* wt, const float* bias, float* out, int64_t ldout,
                 int B, int Cin, int Nout, int act, void* stream);
+/* which kernel sdk_rows_fc launches for these arguments (host only: no context, nothing is launched; the pointers are looked at for their
+ * alignment, never read): 0 the plain kernel (any shape), 1 the matrix-pipe kernel with 4 K-slices (Cin % 32 == 0), 2 and 3 the one with
+ * 16 K-slices (Cin % 128 == 0, Cin >= 2048), 3 when it also fetches the weights as 16-byte rows (Nout % 32 == 0, wt 16-byte aligned).
+ * 1..3 need ldin % 4 == 0, `in` 16-byte aligned and, with an input affine (has_affine != 0), Cin <= 8192; everything else is path 0. */
+int sdk_rows_fc_path(const float* in, int64_t ldin, int has_affine, const float* wt, int Cin, int Nout);
 int sdk_asp_pool(sdk_ctx* ctx, const float* logits, int64_t ldl, const uint16_t* h, int64_t ldh,
                  int B, int T, int C, float* pooled, void* stream);
 int sdk_asp_pool_fmt(sdk_ctx* ctx, const float* logits, int64_t ldl, const uint16_t* h, int64_t ldh,
@@ -844,7 +849,10 @@ int sdk_resample_s16(sdk_ctx* ctx, const int16_t* x, int64_t n_in, int channels,
 int sdk_resample_plan(int L, int M, int K);
 
 /* ---- k3: L2-normalise rows.  X [N, d] fp32 -> E fp32 unit rows, Eb bf16 copy,
- *      resid[n] = || E[n] - float(Eb[n]) ||_2 (rigorous per-row bf16 rounding residual). -- */
+ *      resid[n] = || E[n] - float(Eb[n]) ||_2 (rigorous per-row bf16 rounding residual).
+ *      E = X[n] / max(||X[n]||, 1e-12) with the squared norm summed in fp32: a row of finite entries whose squared norm overflows fp32
+ *      (entries past about 1e19 / sqrt(d)) comes back as a ZERO row (E, Eb and resid all 0), not as a unit row, and a row whose squared norm
+ *      underflows is divided by the 1e-12 floor; a row with a NaN entry comes back all NaN (resid too).  E, Eb and resid may each be null: that output is skipped, the others are unchanged. -- */
 int sdk_l2norm(sdk_ctx* ctx, const float* X, int N, int d, float* E, uint16_t* Eb, float* resid, void* stream);
 
 /* ---- k4: segments x profiles cosine affinity with fused top-k (replaces the scoring a local

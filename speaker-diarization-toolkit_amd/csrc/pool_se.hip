@@ -840,7 +840,10 @@ __global__ __launch_bounds__(NT) void l2norm_kernel(const float* __restrict__ X,
   float ss = 0.f;
   for (int i = lane; i < d; i += 64) ss += x[i] * x[i];
   ss = wave_sum(ss);
-  const float inv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+  // not fmaxf: it returns the floor for a NaN norm, and a row with a NaN entry came back as its finite entries times 1e12 - a NaN norm stays
+  // NaN (the whole row is NaN, as numpy's maximum gives it in oracle/ecapa.py); every other row rounds exactly as before
+  const float nrm = sqrtf(ss);
+  const float inv = 1.0f / (nrm < 1e-12f ? 1e-12f : nrm);
   float rr = 0.f;
   for (int i = lane; i < d; i += 64) {
     const float e = x[i] * inv;
@@ -939,6 +942,18 @@ extern "C" int sdk_asp_stats_fmt(sdk_ctx* ctx, const uint16_t* h, int64_t ldh, i
   return asp_stats_impl(ctx, h, ldh, B, T, C, out_ctx, stream, precision == 2);
 }
 
+constexpr int kRowsFcAffMax = 64 * 1024;                     // dynamic LDS of the MFMA kernels (beside up to 84 KB static): an input affine of Cin <= 8192
+
+// Which kernel sdk_rows_fc launches (host only, no context, launches nothing): 0 rows_fc_kernel, 1 rows_fc_mfma_kernel<4>,
+// 2 rows_fc_mfma_kernel<16, false>, 3 rows_fc_mfma_kernel<16, true>.  The rule lives here alone; sdk_rows_fc switches on the result.
+extern "C" int sdk_rows_fc_path(const float* in, int64_t ldin, int has_affine, const float* wt, int Cin, int Nout) {
+  const bool mfma_ok = ldin % 4 == 0 && ((uintptr_t)in % 16) == 0 && (!has_affine || (size_t)Cin * 8 <= (size_t)kRowsFcAffMax);
+  const bool wlds_ok = Nout % 32 == 0 && ((uintptr_t)wt % 16) == 0;
+  if (!mfma_ok) return 0;
+  if (Cin % 128 == 0 && Cin >= 2048) return wlds_ok ? 3 : 2;   // long K (context bias, final FC): 16 K-slices; 3: weights as 16-byte rows via LDS
+  return Cin % 32 == 0 ? 1 : 0;
+}
+
 extern "C" int sdk_rows_fc(sdk_ctx* ctx, const float* in, int64_t ldin, const float* in_scale, const float* in_shift,
                            const float* wt, const float* bias, float* out, int64_t ldout, int B, int Cin, int Nout,
                            int act, void* stream) {
@@ -947,27 +962,30 @@ extern "C" int sdk_rows_fc(sdk_ctx* ctx, const float* in, int64_t ldin, const fl
   SDK_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "sdk_rows_fc: in_scale and in_shift go together");
   SDK_REQUIRE(act >= 0 && act <= 2, "sdk_rows_fc: act=%d", act);
   ProfScope ps(ctx, stream, SDK_K_ROWS_FC, 2.0 * B * Cin * Nout, 4.0 * ((double)B * Cin + (double)Cin * Nout + (double)B * Nout));
-  constexpr int kAffMax = 64 * 1024;                         // dynamic LDS of the MFMA kernels (beside up to 84 KB static): an input affine of Cin <= 8192
-  const bool mfma_ok = ldin % 4 == 0 && ((uintptr_t)in % 16) == 0 && (!in_scale || (size_t)Cin * 8 <= (size_t)kAffMax);
-  if (in_scale && mfma_ok) {
-    if (sdk_lds_optin(ctx, (const void*)rows_fc_mfma_kernel<16, true>, kAffMax)) return 1;
-    if (sdk_lds_optin(ctx, (const void*)rows_fc_mfma_kernel<16, false>, kAffMax)) return 1;
-    if (sdk_lds_optin(ctx, (const void*)rows_fc_mfma_kernel<4, false>, kAffMax)) return 1;
+  const int path = sdk_rows_fc_path(in, ldin, in_scale != nullptr, wt, Cin, Nout);
+  if (in_scale && path != 0) {
+    if (sdk_lds_optin(ctx, (const void*)rows_fc_mfma_kernel<16, true>, kRowsFcAffMax)) return 1;
+    if (sdk_lds_optin(ctx, (const void*)rows_fc_mfma_kernel<16, false>, kRowsFcAffMax)) return 1;
+    if (sdk_lds_optin(ctx, (const void*)rows_fc_mfma_kernel<4, false>, kRowsFcAffMax)) return 1;
   }
-  const bool wlds_ok = Nout % 32 == 0 && ((uintptr_t)wt % 16) == 0;
   const size_t aff_bytes = in_scale ? (size_t)Cin * 8 : 0;      // the MFMA kernels stage the input affine in dynamic LDS ([2][Cin] fp32)
-  if (mfma_ok && Cin % 128 == 0 && Cin >= 2048 && wlds_ok)   // long K (context bias, final FC): 16 K-slices, weights as 16-byte rows via LDS
-    hipLaunchKernelGGL((rows_fc_mfma_kernel<16, true>), dim3(ceil_div(B, 32), ceil_div(Nout, 32)), dim3(1024), aff_bytes, (hipStream_t)stream,
-                       in, ldin, in_scale, in_shift, wt, bias, out, ldout, B, Cin, Nout, act);
-  else if (mfma_ok && Cin % 128 == 0 && Cin >= 2048)
-    hipLaunchKernelGGL(rows_fc_mfma_kernel<16>, dim3(ceil_div(B, 32), ceil_div(Nout, 32)), dim3(1024), aff_bytes, (hipStream_t)stream,
-                       in, ldin, in_scale, in_shift, wt, bias, out, ldout, B, Cin, Nout, act);
-  else if (mfma_ok && Cin % 32 == 0)
-    hipLaunchKernelGGL(rows_fc_mfma_kernel<4>, dim3(ceil_div(B, 32), ceil_div(Nout, 32)), dim3(NT), aff_bytes, (hipStream_t)stream,
-                       in, ldin, in_scale, in_shift, wt, bias, out, ldout, B, Cin, Nout, act);
-  else
-    hipLaunchKernelGGL(rows_fc_kernel, dim3(ceil_div(B, FC_ROWS), ceil_div(Nout, FC_OUT)), dim3(NT), 0, (hipStream_t)stream,
-                       in, ldin, in_scale, in_shift, wt, bias, out, ldout, B, Cin, Nout, act);
+  switch (path) {
+    case 3:
+      hipLaunchKernelGGL((rows_fc_mfma_kernel<16, true>), dim3(ceil_div(B, 32), ceil_div(Nout, 32)), dim3(1024), aff_bytes, (hipStream_t)stream,
+                         in, ldin, in_scale, in_shift, wt, bias, out, ldout, B, Cin, Nout, act);
+      break;
+    case 2:
+      hipLaunchKernelGGL(rows_fc_mfma_kernel<16>, dim3(ceil_div(B, 32), ceil_div(Nout, 32)), dim3(1024), aff_bytes, (hipStream_t)stream,
+                         in, ldin, in_scale, in_shift, wt, bias, out, ldout, B, Cin, Nout, act);
+      break;
+    case 1:
+      hipLaunchKernelGGL(rows_fc_mfma_kernel<4>, dim3(ceil_div(B, 32), ceil_div(Nout, 32)), dim3(NT), aff_bytes, (hipStream_t)stream,
+                         in, ldin, in_scale, in_shift, wt, bias, out, ldout, B, Cin, Nout, act);
+      break;
+    default:
+      hipLaunchKernelGGL(rows_fc_kernel, dim3(ceil_div(B, FC_ROWS), ceil_div(Nout, FC_OUT)), dim3(NT), 0, (hipStream_t)stream,
+                         in, ldin, in_scale, in_shift, wt, bias, out, ldout, B, Cin, Nout, act);
+  }
   SDK_LAUNCH_CHECK();
   return 0;
 }
