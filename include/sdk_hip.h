@@ -53,6 +53,8 @@
  *                                                                                                       and the DET curve (trials.py)
  *     sdk_trial_calib_workspace_bytes  sdk_trial_calib                                                  verification trials: the sums of the logistic calibration
  *                                                                                                       objective, its gradient and Hessian (trials.py)
+ *     sdk_trial_hist_snorm                                                                              verification trials on the cohort-normalised (AS-norm) scale: the
+ *                                                                                                       histograms that tune SDK_COHORT_THRESHOLD (trials_snorm.py)
  *     sdk_kmeans_rows_workspace_bytes  sdk_kmeans_rows                                                  spherical k-means on unit rows (cluster.kmeans_cluster)
  *     sdk_stream_state_bytes  sdk_stream_reset  sdk_stream_step  sdk_stream_flush  sdk_stream_centroids streaming diarization: online speaker tracking (stream.py)
  * BUILDING BLOCKS AND KNOBS - exported for the parity tests and the A/B tools, free to change between rounds, not for binding:
@@ -75,7 +77,7 @@
 extern "C" {
 #endif
 
-#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5); still 4 with sdk_cohort_stats* and sdk_affinity_topk_snorm, and with sdk_ecapa_forward_masked, sdk_ecapa_masked_workspace_bytes, sdk_asp_stats_masked_fmt and sdk_asp_pool_masked_fmt, and with sdk_score_reference, sdk_score_cooccur and sdk_score_map, and with sdk_plda_enroll* and sdk_plda_score*, and with sdk_trial_hist: new exports only, no struct or existing signature changes, no caller of version 4 breaks */
+#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5); still 4 with sdk_cohort_stats* and sdk_affinity_topk_snorm, and with sdk_ecapa_forward_masked, sdk_ecapa_masked_workspace_bytes, sdk_asp_stats_masked_fmt and sdk_asp_pool_masked_fmt, and with sdk_score_reference, sdk_score_cooccur and sdk_score_map, and with sdk_plda_enroll* and sdk_plda_score*, and with sdk_trial_hist, sdk_trial_calib* and sdk_trial_hist_snorm: new exports only, no struct or existing signature changes, no caller of version 4 breaks */
 
 typedef struct sdk_ctx sdk_ctx;
 
@@ -833,6 +835,21 @@ size_t sdk_trial_calib_workspace_bytes(int N, int M, int max_blocks);
 int sdk_trial_calib(sdk_ctx* ctx, const double* A, int N, const double* B, const double* r, int M, int K, const int32_t* la, const int32_t* sa,
                     const int32_t* lb, const int32_t* sb, double a, double c, int max_blocks, double* sums, uint64_t* counts, void* ws,
                     size_t ws_bytes, void* stream);
+
+/* ---- verification trials on the cohort-normalised (AS-norm) scale: sdk_trial_hist with the score replaced (trials_snorm.py states the rule;
+ *      csrc/trials_snorm.hip).  A [N][K], B [M][K] float64 as for sdk_trial_hist (no r); mean_a, inv_a [N] and mean_b, inv_b [M] float64: per row the
+ *      mean of its cohort scores and the RECIPROCAL of their standard deviation (the caller divides once per row: a trial costs no division).
+ *          s(i, j) = sum_k A[i][k] B[j][k]   on the f64 MFMA, sdk_trial_hist's chain
+ *          z = ((s - mean_a[i]) * inv_a[i] + (s - mean_b[j]) * inv_b[j]) * 0.5   six rounded float64 operations in this order (subtract, multiply,
+ *              subtract, multiply, add, multiply; no FMA)
+ *          t = (z - lo) * scale, then nan / below / above / q, the exclusions, the classes, bin = (q >> shift) - base and the 8199 counters of `out`
+ *              exactly as sdk_trial_hist forms them; a NaN z (a NaN statistic, inf * 0) is counted in nan[class].
+ *      A statistic of a row i >= N or j >= M is never read.  out is zeroed by the call in stream order; max_blocks as for sdk_trial_hist; integer
+ *      counting only after z: bit-identical run to run.  Refused (status 2, nothing launched): what sdk_trial_hist refuses (K, N, M, shift, base,
+ *      max_blocks, lo, scale, a null pointer - the four statistics included -, A or B not 16-byte aligned). */
+int sdk_trial_hist_snorm(sdk_ctx* ctx, const double* A, int N, const double* B, int M, int K, const double* mean_a, const double* inv_a,
+                         const double* mean_b, const double* inv_b, const int32_t* la, const int32_t* sa, const int32_t* lb, const int32_t* sb,
+                         double lo, double scale, int shift, int base, int max_blocks, uint64_t* out, void* stream);
 
 /* ---- audio conversion to the AudioProfile: replaces the ffmpeg subprocess the reference's backends
  *      run before upload (audio_profiles.py:70-100 `format_ffmpeg_args`; speechmatics_backend.py:231-281).

@@ -185,6 +185,7 @@ SIGNATURES = {
     "sdk_trial_hist": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _f64, _f64, _i, _i, _i, _vp, _vp]),
     "sdk_trial_calib_workspace_bytes": (_sz, [_i, _i, _i]),
     "sdk_trial_calib": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _f64, _f64, _i, _vp, _vp, _vp, _sz, _vp]),
+    "sdk_trial_hist_snorm": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _i, _i, _i, _vp, _vp]),
     "sdk_cohort_stats_workspace_bytes": (_sz, [_i, _i, _i]),
     "sdk_cohort_stats": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "sdk_affinity_topk_snorm": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

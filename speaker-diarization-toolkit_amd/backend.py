@@ -43,7 +43,8 @@ Environment:
                       torch engine (SDK_NO_TORCH=1 is refused) and SDK_COHORT_THRESHOLD
   SDK_COHORT_TOPK     cohort scores per side that the statistics are taken over (default 300; min(K, M) is used)
   SDK_COHORT_THRESHOLD  the vote threshold on the z scale (a float).  No default: it depends on the model family and the cohort, and no trained
-                      weights are on hand to tune one - a cohort without a threshold is refused
+                      weights are on hand to tune one - a cohort without a threshold is refused.  tune_cohort_threshold(backend, ...) of
+                      this module finds it on a labelled development set (trials_snorm.py); it needs no SDK_COHORT (cohort=)
   SDK_SCORE_PLDA_TRANSFORM / SDK_SCORE_PLDA   the two .npz files of a PLDA model of THIS family's embedding space (plda.save_plda writes them;
                       Backend.train_plda under the matching SDK_DIARIZE_MODEL makes one): both or neither.  identify_speaker, identify_many
                       and verify_speaker then decide on the PLDA log-likelihood ratio of a window against an enrolled SPEAKER - the speaker's
@@ -633,8 +634,15 @@ class Backend(EmbeddingBackend):
 
     def _verification_trials(self, who: str, audio_paths, speaker_ids, candidates):
         """The trials of score_verification and calibrate_verification in matrix form -> (engine, (A, B, r, la, sa, lb, sb), kind)."""
-        import torch
         self.rule.refuse_trials()
+        eng, E, speaker_ids, counts, batch = self._trial_windows(who, audio_paths, speaker_ids, candidates)
+        A, B, r, lb, kind, index = self.rule.trial_matrices(self, E, batch)
+        return eng, (A, B, r) + self._trial_labels(E.device, speaker_ids, counts, lb, index), kind
+
+    def _trial_windows(self, who: str, audio_paths, speaker_ids, candidates):
+        """The test side of verification trials, whatever the rule: every window of every recording embedded on identify's path ->
+        (engine, E [windows, d], the speaker ids as a list, the windows per recording, the candidates' ProfileBatch)."""
+        import torch
         if self.lite:
             raise ValueError(f"{who}: needs the torch engine; unset SDK_NO_TORCH")
         audio_paths, speaker_ids = list(audio_paths), list(speaker_ids)
@@ -648,15 +656,20 @@ class Backend(EmbeddingBackend):
         for path in audio_paths:
             samples, starts, W, _ = self._windows(Path(path), None)
             rows.append(self.embed_tables(samples, {W: starts})[W][0])
-        E = torch.cat(rows, dim=0).contiguous()
-        A, B, r, lb, kind, index = self.rule.trial_matrices(self, E, batch)
+        return eng, torch.cat(rows, dim=0).contiguous(), speaker_ids, [int(r.shape[0]) for r in rows], batch
+
+    @staticmethod
+    def _trial_labels(device, speaker_ids, counts, lb, index):
+        """(la, sa, lb, sb) int32 device tensors: a window's label is its recording's speaker in `index` ({speaker id: label}, as the rule's
+        trial_matrices numbered the model rows `lb`), its session the index of its recording; the model rows have no session."""
+        import torch
         la, sa = [], []
         for f, sid in enumerate(speaker_ids):                    # an id no candidate has: a label of its own, past the model rows'
-            la += [-1 if sid is None else index.setdefault(sid, len(index))] * int(rows[f].shape[0])
-            sa += [f] * int(rows[f].shape[0])
-        i32 = lambda a: torch.from_numpy(np.asarray(a, dtype=np.int32)).to(E.device)        # noqa: E731
+            la += [-1 if sid is None else index.setdefault(sid, len(index))] * counts[f]
+            sa += [f] * counts[f]
+        i32 = lambda a: torch.from_numpy(np.asarray(a, dtype=np.int32)).to(device)        # noqa: E731
         sb = np.full(len(lb), -1)
-        return eng, (A, B, r, i32(la), i32(sa), i32(lb), i32(sb)), kind
+        return i32(la), i32(sa), i32(lb), i32(sb)
 
     def tune_verification(self, audio_paths, speaker_ids, candidates, score_range=None, p_target: float = 0.01, c_miss: float = 1.0,
                           c_fa: float = 1.0, max_refine: int = 8) -> Dict[str, Any]:
@@ -980,3 +993,61 @@ def calibrate_verification(be: Backend, audio_paths, speaker_ids, candidates, ou
     if out_path is not None:
         trials.save_calibration(cal, out_path)
     return cal
+
+
+def _snorm_trials(be: Backend, who: str, audio_paths, speaker_ids, candidates, cohort, topk, score_range, p_target, c_miss, c_fa, max_refine):
+    """-> (trials.VerificationResult, the snorm.Cohort, the K its statistics were taken over)."""
+    from . import trials_snorm
+    from .rules import Cosine
+    from .snorm import Cohort
+    if be.lite:
+        raise ValueError(f"{who}: needs the torch engine; unset SDK_NO_TORCH")
+    co = be.cohort() if cohort is None else cohort if isinstance(cohort, Cohort) else Cohort.load(cohort, be.embedding_dim)
+    if co is None:
+        raise ValueError(f"{who}: no cohort: pass cohort= (a .npy path as SDK_COHORT names one, Backend.make_cohort writes it; or a snorm.Cohort) "
+                         "or configure SDK_COHORT")
+    if co.dim != int(be.embedding_dim):
+        raise ValueError(f"{who}: cohort {co.source}: rows of d={co.dim}, the model's embedding_dim is {int(be.embedding_dim)}")
+    K = min(int(be.cohort_topk if topk is None else topk), len(co))
+    if K < 1:
+        raise ValueError(f"{who}: topk={topk}: at least 1")
+    eng, E, speaker_ids, counts, batch = be._trial_windows(who, audio_paths, speaker_ids, candidates)
+    A, B, _, lb, _, index = Cosine().trial_matrices(be, E, batch)              # the cosine rule's matrices: windows against enrolled embeddings
+    la, sa, lb, sb = be._trial_labels(E.device, speaker_ids, counts, lb, index)
+    rows = co.device_rows(eng)
+    mean_a, inv_a = trials_snorm.cohort_statistics(eng, E, rows, K)
+    mean_b, inv_b = trials_snorm.cohort_statistics(eng, be.profile_tensors(batch)[0].contiguous(), rows, K)
+    res = trials_snorm.evaluate_snorm_scores(eng, A, B, mean_a, inv_a, mean_b, inv_b, la, sa, lb, sb, score_range, p_target, c_miss, c_fa, max_refine)
+    return res, co, K
+
+
+def score_verification_snorm(be: Backend, audio_paths, speaker_ids, candidates, cohort=None, topk=None, score_range=None, p_target: float = 0.01,
+                             c_miss: float = 1.0, c_fa: float = 1.0, max_refine: int = 8):
+    """Backend.score_verification on the AS-norm scale -> trials.VerificationResult with kind "snorm": how well the cohort-normalised decision
+    of identify_speaker / verify_speaker (SDK_COHORT) separates the enrolled speakers on labelled recordings.  The inputs and the trials are
+    those of Backend.score_verification under the cosine rule: every window of every recording is a test row, the model rows are the
+    candidates' enrolled embeddings (profile_tensors).  cohort: a .npy path (Backend.make_cohort writes one) or a snorm.Cohort; None: the
+    configured SDK_COHORT (ValueError when neither is given).  topk: the cohort scores per side that the statistics are taken over; None:
+    the backend's cohort_topk (SDK_COHORT_TOPK); min(topk, the cohort's rows) is used.  score_range defaults to trials_snorm.SNORM_RANGE.
+    Works on a Backend under the cosine rule and on one configured with SDK_COHORT; SDK_NO_TORCH=1 is refused.  trials_snorm.py states
+    the rule (parity with outside toolkits is unpinned).
+
+    A function of the Backend, not a method of it: the Backend's public surface is pinned name for name (tests/test_rules_cpu.py)."""
+    return _snorm_trials(be, "score_verification_snorm", audio_paths, speaker_ids, candidates, cohort, topk, score_range, p_target, c_miss, c_fa,
+                         max_refine)[0]
+
+
+def tune_cohort_threshold(be: Backend, audio_paths, speaker_ids, candidates, cohort=None, topk=None, score_range=None, p_target: float = 0.01,
+                          c_miss: float = 1.0, c_fa: float = 1.0, max_refine: int = 8) -> Dict[str, Any]:
+    """The thresholds of the AS-norm decision on a labelled development set (the arguments of score_verification_snorm) ->
+    Backend.tune_verification's dict with kind "snorm", plus "cohort_digest" (the content hash of the cohort the statistics came from) and
+    "topk" (the K used).  eer_threshold and min_dcf_threshold are on the z scale: they are what SDK_COHORT_THRESHOLD takes, for THIS cohort
+    and K.  The evaluation scores the float64 product of the fp32 unit rows and normalises it in float64; identify computes z from its
+    fp32 cosines and fp32 statistics.  The two agree to fp32 rounding times inv = 1 / std (a few 1e-7 of cosine, scaled by 1 / std), so
+    a window that close to the threshold may vote differently."""
+    res, co, K = _snorm_trials(be, "tune_cohort_threshold", audio_paths, speaker_ids, candidates, cohort, topk, score_range, p_target, c_miss, c_fa,
+                               max_refine)
+    return {"kind": res.kind, "eer": res.eer, "eer_threshold": res.eer_threshold, "min_dcf": res.min_dcf, "min_dcf_threshold": res.min_dcf_threshold,
+            "min_dcf_lower": res.min_dcf_lower, "min_dcf_exact": res.min_dcf_exact, "n_target": res.n_target, "n_nontarget": res.n_nontarget,
+            "n_nan": res.n_nan, "n_excluded": res.n_excluded, "n_test_rows": res.test_rows, "n_model_rows": res.model_rows, "score_range": res.score_range,
+            "result": res, "cohort_digest": co.digest, "topk": K}

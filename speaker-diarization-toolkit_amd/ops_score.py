@@ -1,6 +1,7 @@
 """Engine's scoring calls beyond the cosine affinity: adaptive score normalisation against a cohort (snorm.py), the PLDA's training
-statistics and projection (plda.fit), PLDA log-likelihood-ratio scoring (plda_score.py) and the verification-trial histogram (trials.py).
-Nothing here synchronises with the host except plda_fit_stats' range check of its labels.
+statistics and projection (plda.fit), PLDA log-likelihood-ratio scoring (plda_score.py), the verification-trial histogram and calibration
+pass (trials.py) and the histogram on the cohort-normalised scale (trials_snorm.py).  Nothing here synchronises with the host except
+plda_fit_stats' range check of its labels.
 
 ScoreMixin is a mixin of ops.Engine: no state and no __init__ of its own.  It uses self.lib, self.ctx, self.device, self._scratch_bytes
 and self._workspace_bytes only, and this module imports ops.py for nothing (ops.py imports it).
@@ -255,3 +256,45 @@ def trial_calib(engine, A: torch.Tensor, B: torch.Tensor, r: torch.Tensor, la: t
                                      sb.data_ptr(), a, c, max_blocks, sums.data_ptr(), counts.data_ptr(), ws.data_ptr(), nbytes, _stream()),
           "sdk_trial_calib")
     return counts[0:2], sums, counts[2:4], counts[4:5]
+
+
+# ---- verification trials on the cohort-normalised scale (trials_snorm.py; csrc/trials_snorm.hip)
+def trial_hist_snorm(engine, A: torch.Tensor, B: torch.Tensor, mean_a: torch.Tensor, inv_a: torch.Tensor, mean_b: torch.Tensor, inv_b: torch.Tensor,
+                     la: torch.Tensor, sa: torch.Tensor, lb: torch.Tensor, sb: torch.Tensor, lo: float, hi: float, shift: int = 12, base: int = 0,
+                     max_blocks: int = 0):
+    """One pass of the trial histogram on the AS-norm scale: Engine.trial_hist's A [N, K], B [M, K], labels and sessions (no r), and per row the
+    float64 mean of its cohort scores and the RECIPROCAL of their standard deviation - mean_a, inv_a [N], mean_b, inv_b [M] - all on the
+    device -> Engine.trial_hist's five int64 views (hist [2, 4096], under [2], over [2], nan [2], excluded [1]) of
+    z = ((s - mean_a[i]) * inv_a[i] + (s - mean_b[j]) * inv_b[j]) * 0.5, s = A[i] . B[j], cut into q = floor((z - lo) * scale) as there
+    (sdk_trial_hist_snorm; trials_snorm.py states the rule).  Nothing waits.
+
+    A function of the engine, not a method of it: Engine's public surface is pinned name for name (tests/test_ops_layout_cpu.py)."""
+    who = "trial_hist_snorm"
+    lo, hi, shift, base, max_blocks = float(lo), float(hi), int(shift), int(base), int(max_blocks)
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise ValueError(f"trial_hist_snorm: score range ({lo}, {hi}): finite lo < hi expected")
+    with np.errstate(over="ignore"):
+        scale = float(np.float64(16777216.0) / (np.float64(hi) - np.float64(lo)))
+    if not (np.isfinite(scale) and scale > 0.0):
+        raise ValueError(f"trial_hist_snorm: scale = 2^24 / (hi - lo) = {scale} is not a finite number above 0 (range ({lo}, {hi}))")
+    if shift < 0 or shift > 24:
+        raise ValueError(f"trial_hist_snorm: shift={shift} (0 .. 24)")
+    if base < 0 or base > 1 << 24:
+        raise ValueError(f"trial_hist_snorm: base={base} (0 .. 2^24)")
+    if max_blocks < 0:
+        raise ValueError(f"trial_hist_snorm: max_blocks={max_blocks} (0: the default grid, else a cap on the workgroups)")
+    N, K = (int(v) for v in _args.tensor(who, "A", A, "float64", (None, None)).shape)
+    if K < 16 or K > 512 or K % 16:
+        raise ValueError(f"trial_hist_snorm: K={K} not supported (a multiple of 16 in 16 .. 512)")
+    M = int(_args.tensor(who, "B", B, "float64", (None, K)).shape[0])
+    if not (1 <= N <= 1 << 20 and 1 <= M <= 1 << 20):
+        raise ValueError(f"trial_hist_snorm: N={N} test rows, M={M} model rows (1 .. 2^20 each)")
+    for name, t, n in (("mean_a", mean_a, N), ("inv_a", inv_a, N), ("mean_b", mean_b, M), ("inv_b", inv_b, M)):
+        _args.tensor(who, name, t, "float64", (n,))
+    for name, t, n in (("la", la, N), ("sa", sa, N), ("lb", lb, M), ("sb", sb, M)):
+        _args.tensor(who, name, t, "int32", (n,))
+    out = torch.empty((2 * 4096 + 7,), dtype=torch.int64, device=A.device)           # uint64 counters, all below 2^40
+    check(engine.lib.sdk_trial_hist_snorm(engine.ctx, A.data_ptr(), N, B.data_ptr(), M, K, mean_a.data_ptr(), inv_a.data_ptr(), mean_b.data_ptr(),
+                                          inv_b.data_ptr(), la.data_ptr(), sa.data_ptr(), lb.data_ptr(), sb.data_ptr(), lo, scale, shift, base,
+                                          max_blocks, out.data_ptr(), _stream()), "sdk_trial_hist_snorm")
+    return out[:8192].view(2, 4096), out[8192:8194], out[8194:8196], out[8196:8198], out[8198:8199]

@@ -177,7 +177,9 @@ class Snorm(Rule):
 
     def refuse_trials(self) -> None:
         raise ValueError("score_verification: AS-norm trials are not built: with SDK_COHORT set the decision is made on the normalised scale, "
-                         "which has no matrix form here; unset SDK_COHORT to evaluate the cosine or the PLDA rule")
+                         "which has no matrix form here; unset SDK_COHORT to evaluate the cosine or the PLDA rule.  The normalised scale "
+                         "has entry points of its own: backend.score_verification_snorm(backend, ...) and "
+                         "backend.tune_cohort_threshold(backend, ...) (trials_snorm.py)")
 
 
 class Plda(Rule):
