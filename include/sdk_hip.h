@@ -43,6 +43,8 @@
  *     sdk_diarize_assign_grouped  sdk_diarize_fold_grouped  sdk_diarize_reconstruct_grouped  sdk_diarize_first_seen  sdk_diarize_renumber
  *                                                                                                       speaker diarization (diarize.py)
  *     sdk_score_reference  sdk_score_cooccur  sdk_score_map                                             diarization error rate against a reference (score.py)
+ *     sdk_words_attribute  sdk_words_cooccur                                                            speaker-attributed transcripts: words onto the diarization
+ *                                                                                                       frames, and the word-level error rate's tables (words.py)
  *     sdk_plda_transform  sdk_vbx_workspace_bytes  sdk_vbx  sdk_vbx_centroids                           VBx clustering (plda.py, cluster.vbx_cluster)
  *     sdk_vbx_hmm_workspace_bytes  sdk_vbx_hmm                                                          VBx with its HMM, rows in time order (loop_prob > 0)
  *     sdk_plda_fit_stats_workspace_bytes  sdk_plda_fit_stats  sdk_plda_project                          training the VBx PLDA from labelled rows (plda.fit)
@@ -77,7 +79,7 @@
 extern "C" {
 #endif
 
-#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5); still 4 with sdk_cohort_stats* and sdk_affinity_topk_snorm, and with sdk_ecapa_forward_masked, sdk_ecapa_masked_workspace_bytes, sdk_asp_stats_masked_fmt and sdk_asp_pool_masked_fmt, and with sdk_score_reference, sdk_score_cooccur and sdk_score_map, and with sdk_plda_enroll* and sdk_plda_score*, and with sdk_trial_hist, sdk_trial_calib* and sdk_trial_hist_snorm: new exports only, no struct or existing signature changes, no caller of version 4 breaks */
+#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5); still 4 with sdk_cohort_stats* and sdk_affinity_topk_snorm, and with sdk_ecapa_forward_masked, sdk_ecapa_masked_workspace_bytes, sdk_asp_stats_masked_fmt and sdk_asp_pool_masked_fmt, and with sdk_score_reference, sdk_score_cooccur and sdk_score_map, and with sdk_plda_enroll* and sdk_plda_score*, and with sdk_trial_hist, sdk_trial_calib* and sdk_trial_hist_snorm, and with sdk_words_attribute and sdk_words_cooccur: new exports only, no struct or existing signature changes, no caller of version 4 breaks */
 
 typedef struct sdk_ctx sdk_ctx;
 
@@ -653,6 +655,31 @@ int sdk_score_cooccur(sdk_ctx* ctx, const uint64_t* ref_mask, const uint8_t* sco
                       int64_t co_total, int32_t* co, int64_t* tally, void* stream);
 int sdk_score_map(sdk_ctx* ctx, const int32_t* co, const int32_t* ref_off, const int32_t* cent_off, const int64_t* co_off, int R, int max_ref,
                   int max_hyp, int32_t* map, int64_t* correct, void* stream);
+
+/* ---- speaker-attributed transcripts (words.py; csrc/words.hip): the words of a transcript onto the per-frame speakers of a diarization, on
+ *      the packed frame grid above.  word_off [R + 1] int32: the prefix sums of the recordings' words; frame_off, cent_off, ref_off, co_off as
+ *      above.  Integer arithmetic only (integer LDS atomics, integer atomic adds): bit-identical run to run.  No call reads the device on
+ *      the host.
+ *   sdk_words_attribute : words [W][2] int32 (s0, s1: samples inside the word's recording), speakers [G][2] -> out [W][8] int32 = (speaker,
+ *        votes, solo, span, second, second_votes, distance, g0).  One wave per word.  With n the recording's frames, g0 = min(ceil((s0 - 495)
+ *        / 270), n) and g1 likewise from s1, both at least 0 (the frames whose centre lies in [s0, s1)); if g1 <= g0 the one frame nearest
+ *        the midpoint m = (s0 + s1) >> 1: g0 = clamp(floor((m - 360) / 270), 0, n - 1), g1 = g0 + 1.  span = g1 - g0; g0 is local to the
+ *        recording.  v[k] = the frames of the word that name speaker k (an entry < 0 or >= K_r names nobody, a speaker named twice in a
+ *        frame counts once), u[k] = those that name k alone.  speaker = the k with v[k] > 0 first in the order (v descending, u descending,
+ *        k ascending), votes = v, solo = u; second, second_votes = the next in that order with v > 0, else (-1, 0); distance = 0.  Every v
+ *        0: the least delta in 1 .. gap_frames for which frame g0 - delta or g1 - 1 + delta, inside the word's own recording, names somebody
+ *        (the earlier side first, then the first entry of the frame) gives speaker, votes = solo = 0, second = -1, distance = delta; none:
+ *        speaker = distance = -1.  A recording without frames: (-1, 0, 0, 0, -1, 0, -1, 0).  max_hyp: the largest K_r, stated by the
+ *        caller (the counters in LDS are sized by it; more than 1024 is refused; a K_r above it is read as max_hyp rounded up to 64).
+ *   sdk_words_cooccur : rows = sdk_words_attribute's out, ref [W] int32 = the reference speaker of every word (outside 0 .. S_r - 1: not
+ *        scored) -> tally [R][3] int64 = (scored words, scored words whose speaker is outside 0 .. K_r - 1, words) and co (int32; recording
+ *        r's [S_r][K_r] table at co_off[r], co_total cells in all) = the scored words with reference i and speaker j.  Both are cleared
+ *        first.  More than 64 speakers a side is refused; sdk_score_map then runs on co as it stands. */
+int sdk_words_attribute(sdk_ctx* ctx, const int32_t* words, const int32_t* word_off, const int32_t* speakers, const int32_t* frame_off,
+                        const int32_t* cent_off, int R, int W, int64_t G, int max_hyp, int gap_frames, int32_t* out, void* stream);
+int sdk_words_cooccur(sdk_ctx* ctx, const int32_t* rows, const int32_t* ref, const int32_t* word_off, const int32_t* ref_off,
+                      const int32_t* cent_off, const int64_t* co_off, int R, int W, int max_ref, int max_hyp, int64_t co_total, int32_t* co,
+                      int64_t* tally, void* stream);
 
 /* ---- VBx clustering of the diarization (cluster.vbx_cluster, plda.py; csrc/vbx.hip): float64 arithmetic, every sum over rows over fixed 64-row
  *      blocks whose partials are combined in block order, no floating-point atomics, one owner per output element: bit-identical run to

@@ -1,6 +1,7 @@
 """Engine's scoring calls beyond the cosine affinity: adaptive score normalisation against a cohort (snorm.py), the PLDA's training
 statistics and projection (plda.fit), PLDA log-likelihood-ratio scoring (plda_score.py), the verification-trial histogram and calibration
-pass (trials.py) and the histogram on the cohort-normalised scale (trials_snorm.py).  Nothing here synchronises with the host except
+pass (trials.py), the histogram on the cohort-normalised scale (trials_snorm.py) and the attribution of a transcript's words to the
+diarization's frames (words.py).  Nothing here synchronises with the host except
 plda_fit_stats' range check of its labels.
 
 ScoreMixin is a mixin of ops.Engine: no state and no __init__ of its own.  It uses self.lib, self.ctx, self.device, self._scratch_bytes
@@ -298,3 +299,64 @@ def trial_hist_snorm(engine, A: torch.Tensor, B: torch.Tensor, mean_a: torch.Ten
                                           inv_b.data_ptr(), la.data_ptr(), sa.data_ptr(), lb.data_ptr(), sb.data_ptr(), lo, scale, shift, base,
                                           max_blocks, out.data_ptr(), _stream()), "sdk_trial_hist_snorm")
     return out[:8192].view(2, 4096), out[8192:8194], out[8194:8196], out[8196:8198], out[8198:8199]
+
+
+# ---- speaker-attributed transcripts (words.py; csrc/words.hip)
+def _prefix(who: str, name: str, t, R: int):
+    return _args.tensor(who, name, t, "int32", (R + 1,))
+
+
+def words_attribute(engine, words: torch.Tensor, word_off: torch.Tensor, speakers: torch.Tensor, frame_off: torch.Tensor, cent_off: torch.Tensor,
+                    max_hyp: int, gap_frames: int) -> torch.Tensor:
+    """words [W, 2] int32 (s0, s1 in samples inside the word's recording), speakers [G, 2] int32 on the packed frame grid, word_off, frame_off,
+    cent_off [R + 1] int32 prefix sums (diarize_ops.GroupTables), all on the device -> rows [W, 8] int32 (speaker, votes, solo, span, second,
+    second_votes, distance, g0) on the device: one launch, one wave per word (sdk_words_attribute; words.py states the rule).  max_hyp: the
+    largest K_r of the pack (at most words.MAX_WORD_SPEAKERS); gap_frames: how far a word in non-speech looks for a voiced frame.  Nothing waits.
+
+    A function of the engine, not a method of it: Engine's public surface is pinned name for name (tests/test_ops_layout_cpu.py)."""
+    who = "words_attribute"
+    W = int(_args.tensor(who, "words", words, "int32", (None, 2)).shape[0])
+    G = int(_args.tensor(who, "speakers", speakers, "int32", (None, 2)).shape[0])
+    R = int(_args.tensor(who, "word_off", word_off, "int32", (None,)).shape[0]) - 1
+    if R < 1:
+        raise ValueError(f"words_attribute: word_off must hold R + 1 >= 2 prefix sums, got {list(word_off.shape)}")
+    _prefix(who, "frame_off", frame_off, R)
+    _prefix(who, "cent_off", cent_off, R)
+    max_hyp, gap_frames = int(max_hyp), int(gap_frames)
+    if max_hyp < 0 or max_hyp > 1024:
+        raise ValueError(f"words_attribute: {max_hyp} hypothesis speakers in a recording (at most 1024)")
+    if gap_frames < 0 or gap_frames >= 1 << 30:
+        raise ValueError(f"words_attribute: gap_frames={gap_frames} (0 .. 2^30 - 1)")
+    out = torch.empty((W, 8), dtype=torch.int32, device=words.device)
+    check(engine.lib.sdk_words_attribute(engine.ctx, words.data_ptr() if W else None, word_off.data_ptr(), speakers.data_ptr() if G else None,
+                                         frame_off.data_ptr(), cent_off.data_ptr(), R, W, G, max_hyp, gap_frames, out.data_ptr() if W else None,
+                                         _stream()), "sdk_words_attribute")
+    return out
+
+
+def words_cooccur(engine, rows: torch.Tensor, ref: torch.Tensor, word_off: torch.Tensor, ref_off: torch.Tensor, cent_off: torch.Tensor,
+                  co_off: torch.Tensor, max_ref: int, max_hyp: int, co_total: int):
+    """rows [W, 8] int32 (words_attribute), ref [W] int32 (the reference speaker of every word, -1: not scored), word_off, ref_off, cent_off
+    [R + 1] int32 and co_off [R + 1] int64 prefix sums, all on the device -> (co [max(co_total, 1)] int32: recording r's [S_r, K_r] table at co_off[r];
+    tally [R, 3] int64: scored, unassigned, words) on the device (sdk_words_cooccur); Engine.score_map's kernel then runs on co.  At most 64
+    speakers a side.  Nothing waits.
+
+    A function of the engine, not a method of it: Engine's public surface is pinned name for name (tests/test_ops_layout_cpu.py)."""
+    who = "words_cooccur"
+    W = int(_args.tensor(who, "rows", rows, "int32", (None, 8)).shape[0])
+    _args.tensor(who, "ref", ref, "int32", (W,))
+    R = int(_args.tensor(who, "word_off", word_off, "int32", (None,)).shape[0]) - 1
+    if R < 1:
+        raise ValueError(f"words_cooccur: word_off must hold R + 1 >= 2 prefix sums, got {list(word_off.shape)}")
+    _prefix(who, "ref_off", ref_off, R)
+    _prefix(who, "cent_off", cent_off, R)
+    _args.tensor(who, "co_off", co_off, "int64", (R + 1,))
+    max_ref, max_hyp, co_total = int(max_ref), int(max_hyp), int(co_total)
+    if co_total < 0:
+        raise ValueError(f"words_cooccur: co_total={co_total} (the cells of every recording's table, >= 0)")
+    co = torch.empty((max(co_total, 1),), dtype=torch.int32, device=rows.device)
+    tally = torch.empty((R, 3), dtype=torch.int64, device=rows.device)
+    check(engine.lib.sdk_words_cooccur(engine.ctx, rows.data_ptr() if W else None, ref.data_ptr() if W else None, word_off.data_ptr(), ref_off.data_ptr(),
+                                       cent_off.data_ptr(), co_off.data_ptr(), R, W, max_ref, max_hyp, co_total, co.data_ptr(), tally.data_ptr(),
+                                       _stream()), "sdk_words_cooccur")
+    return co, tally
