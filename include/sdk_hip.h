@@ -45,6 +45,9 @@
  *     sdk_score_reference  sdk_score_cooccur  sdk_score_map                                             diarization error rate against a reference (score.py)
  *     sdk_words_attribute  sdk_words_cooccur                                                            speaker-attributed transcripts: words onto the diarization
  *                                                                                                       frames, and the word-level error rate's tables (words.py)
+ *     sdk_samples_runs_workspace_bytes  sdk_samples_runs  sdk_samples_score_workspace_bytes  sdk_samples_score
+ *                                                                                                       speaker samples: each speaker's solo runs on the diarization
+ *                                                                                                       frames, and the scores of the clips cut from them (samples.py)
  *     sdk_plda_transform  sdk_vbx_workspace_bytes  sdk_vbx  sdk_vbx_centroids                           VBx clustering (plda.py, cluster.vbx_cluster)
  *     sdk_vbx_hmm_workspace_bytes  sdk_vbx_hmm                                                          VBx with its HMM, rows in time order (loop_prob > 0)
  *     sdk_plda_fit_stats_workspace_bytes  sdk_plda_fit_stats  sdk_plda_project                          training the VBx PLDA from labelled rows (plda.fit)
@@ -79,7 +82,7 @@
 extern "C" {
 #endif
 
-#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5); still 4 with sdk_cohort_stats* and sdk_affinity_topk_snorm, and with sdk_ecapa_forward_masked, sdk_ecapa_masked_workspace_bytes, sdk_asp_stats_masked_fmt and sdk_asp_pool_masked_fmt, and with sdk_score_reference, sdk_score_cooccur and sdk_score_map, and with sdk_plda_enroll* and sdk_plda_score*, and with sdk_trial_hist, sdk_trial_calib* and sdk_trial_hist_snorm, and with sdk_words_attribute and sdk_words_cooccur: new exports only, no struct or existing signature changes, no caller of version 4 breaks */
+#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5); still 4 with sdk_cohort_stats* and sdk_affinity_topk_snorm, and with sdk_ecapa_forward_masked, sdk_ecapa_masked_workspace_bytes, sdk_asp_stats_masked_fmt and sdk_asp_pool_masked_fmt, and with sdk_score_reference, sdk_score_cooccur and sdk_score_map, and with sdk_plda_enroll* and sdk_plda_score*, and with sdk_trial_hist, sdk_trial_calib* and sdk_trial_hist_snorm, and with sdk_words_attribute and sdk_words_cooccur, and with sdk_samples_runs* and sdk_samples_score*: new exports only, no struct or existing signature changes, no caller of version 4 breaks */
 
 typedef struct sdk_ctx sdk_ctx;
 
@@ -680,6 +683,37 @@ int sdk_words_attribute(sdk_ctx* ctx, const int32_t* words, const int32_t* word_
 int sdk_words_cooccur(sdk_ctx* ctx, const int32_t* rows, const int32_t* ref, const int32_t* word_off, const int32_t* ref_off,
                       const int32_t* cent_off, const int64_t* co_off, int R, int W, int max_ref, int max_hyp, int64_t co_total, int32_t* co,
                       int64_t* tally, void* stream);
+
+/* ---- speaker samples (samples.py; csrc/samples.hip): each diarized speaker's clean stretches of audio on the packed frame grid above, and
+ *      the scores of the clips cut from them.  frame_off, cent_off as above.  Every output is bit-identical run to run: the runs are
+ *      integers and every element has one owner, the scores are float64 sums in a fixed order without floating-point atomics.  No call
+ *      reads the device on the host.
+ *   sdk_samples_runs : speakers [G][2] -> run_off [R + 1] int32, rows [run_off[R]][4] int32 = (speaker, g0, g1, solo).  An entry < 0 or
+ *        >= K_r names nobody (max_hyp: the largest K_r, stated by the caller; more than 1024 is refused and a K_r above 1024 is read as 1024) and a speaker named twice counts once; a frame that names nobody is silent, one that
+ *        names exactly {k} is solo for k, any other is overlapped.  A run of k is a maximal [g0, g1) inside one recording whose first and
+ *        last frames are solo for k, whose frames are all solo for k or silent and in which no more than gap_frames silent frames follow
+ *        one another; solo counts its solo frames, and it is written iff solo >= min_frames (at least 1).  g0 and g1 are local to the
+ *        recording; recording r's rows are run_off[r] .. run_off[r + 1] - 1, by ascending g0.  rows_cap: the rows that `rows` can hold, at
+ *        least G / min_frames (the most runs G frames hold; rows is 16-byte aligned).  A segmented scan and a compaction in nine short
+ *        launches (csrc/samples.hip lists them): the cost does not depend on how long the runs are.  ws: a 16-byte aligned device buffer of
+ *        sdk_samples_runs_workspace_bytes(G) bytes (0 with sdk_last_error: G outside 0 .. 2^30 - 1); not read with G = 0.
+ *   sdk_samples_score : E [W][d] fp32 rows on the device (read as they are: not renormalised; d a multiple of 64, at most 512), clip_off
+ *        [M + 1] int32 (clip i holds the rows clip_off[i] .. clip_off[i + 1] - 1), clip_spk [M] int32 (the clip's speaker, numbered over
+ *        the pack: spk_off[r] + its number inside recording r; outside 0 .. S - 1: nobody's, scored (0, 0, -1, windows, 1)), spk_off
+ *        [R + 1] int32 prefix sums of the recordings' speakers, S = spk_off[R].  With c_i the float64 sum of clip i's rows, m_s the sum of
+ *        the c_i of speaker s in ascending i and cos(a, b) = a . b / (sqrt(a . a) sqrt(b . b)):  mean [S][d] float64 = m_s / (the rows of
+ *        speaker s), zeros without rows;  out_f [M][2] float64 = (own, rival), own = cos(c_i, m_s - c_i), 0 with alone = 1 when either
+ *        has norm 0; rival = the largest cos(c_i, m_t) over the other speakers t of the clip's recording with |m_t| > 0, the lowest t at
+ *        equal values, (0, -1) when there is none or |c_i| = 0;  out_i [M][3] int32 = (rival's number inside the recording or -1, the
+ *        clip's rows, alone).  ws: an 8-byte aligned device buffer of sdk_samples_score_workspace_bytes(M, S, d) bytes. */
+size_t sdk_samples_runs_workspace_bytes(int64_t G);
+int sdk_samples_runs(sdk_ctx* ctx, const int32_t* speakers, const int32_t* frame_off, const int32_t* cent_off, int R, int64_t G,
+                     int max_hyp, int gap_frames, int min_frames, int32_t* run_off, int32_t* rows, int64_t rows_cap, void* ws, size_t ws_bytes,
+                     void* stream);
+size_t sdk_samples_score_workspace_bytes(int M, int S, int d);
+int sdk_samples_score(sdk_ctx* ctx, const float* E, int W, int d, const int32_t* clip_off, const int32_t* clip_spk, int M,
+                      const int32_t* spk_off, int R, int S, double* mean, double* out_f, int32_t* out_i, void* ws, size_t ws_bytes,
+                      void* stream);
 
 /* ---- VBx clustering of the diarization (cluster.vbx_cluster, plda.py; csrc/vbx.hip): float64 arithmetic, every sum over rows over fixed 64-row
  *      blocks whose partials are combined in block order, no floating-point atomics, one owner per output element: bit-identical run to

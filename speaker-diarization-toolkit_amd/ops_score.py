@@ -1,7 +1,7 @@
 """Engine's scoring calls beyond the cosine affinity: adaptive score normalisation against a cohort (snorm.py), the PLDA's training
 statistics and projection (plda.fit), PLDA log-likelihood-ratio scoring (plda_score.py), the verification-trial histogram and calibration
 pass (trials.py), the histogram on the cohort-normalised scale (trials_snorm.py) and the attribution of a transcript's words to the
-diarization's frames (words.py).  Nothing here synchronises with the host except
+diarization's frames (words.py) and each speaker's solo runs and clip scores (samples.py).  Nothing here synchronises with the host except
 plda_fit_stats' range check of its labels.
 
 ScoreMixin is a mixin of ops.Engine: no state and no __init__ of its own.  It uses self.lib, self.ctx, self.device, self._scratch_bytes
@@ -360,3 +360,73 @@ def words_cooccur(engine, rows: torch.Tensor, ref: torch.Tensor, word_off: torch
                                        cent_off.data_ptr(), co_off.data_ptr(), R, W, max_ref, max_hyp, co_total, co.data_ptr(), tally.data_ptr(),
                                        _stream()), "sdk_words_cooccur")
     return co, tally
+
+
+# ---- speaker samples (samples.py; csrc/samples.hip)
+SAMPLES_SCAN_SPAN = 2048      # the packed frames one workgroup of sdk_samples_runs scans (SM_SPAN: 256 threads x 8 frames)
+
+
+def samples_runs(engine, speakers: torch.Tensor, frame_off: torch.Tensor, cent_off: torch.Tensor, max_hyp: int, gap_frames: int, min_frames: int):
+    """speakers [G, 2] int32 on the packed frame grid, frame_off, cent_off [R + 1] int32 prefix sums (diarize_ops.GroupTables), all on the
+    device -> (run_off [R + 1] int32, rows [max(G // min_frames, 1), 4] int32) on the device: recording r's kept runs (speaker, g0, g1, solo) are
+    rows[run_off[r]:run_off[r + 1]], the rows from run_off[R] on are not written (sdk_samples_runs; samples.py states the rule).  max_hyp:
+    the largest K_r of the pack (at most words.MAX_WORD_SPEAKERS); gap_frames: the silent frames a run may bridge; min_frames: the solo
+    frames a run must hold (at least 1).  Nothing waits.
+
+    A function of the engine, not a method of it: Engine's public surface is pinned name for name (tests/test_ops_layout_cpu.py)."""
+    who = "samples_runs"
+    G = int(_args.tensor(who, "speakers", speakers, "int32", (None, 2)).shape[0])
+    R = int(_args.tensor(who, "frame_off", frame_off, "int32", (None,)).shape[0]) - 1
+    if R < 1:
+        raise ValueError(f"samples_runs: frame_off must hold R + 1 >= 2 prefix sums, got {list(frame_off.shape)}")
+    _prefix(who, "cent_off", cent_off, R)
+    max_hyp, gap_frames, min_frames = int(max_hyp), int(gap_frames), int(min_frames)
+    if max_hyp < 0 or max_hyp > 1024:
+        raise ValueError(f"samples_runs: {max_hyp} hypothesis speakers in a recording (at most 1024)")
+    if gap_frames < 0 or gap_frames >= 1 << 30:
+        raise ValueError(f"samples_runs: gap_frames={gap_frames} (0 .. 2^30 - 1)")
+    if min_frames < 1 or min_frames >= 1 << 30:
+        raise ValueError(f"samples_runs: min_frames={min_frames} (1 .. 2^30 - 1)")
+    if G >= 1 << 30:
+        raise ValueError(f"samples_runs: G={G} frames in one pack (fewer than 2^30)")
+    cap = G // min_frames
+    run_off = torch.empty((R + 1,), dtype=torch.int32, device=speakers.device)
+    rows = torch.empty((max(cap, 1), 4), dtype=torch.int32, device=speakers.device)
+    nbytes = engine._workspace_bytes("sdk_samples_runs_workspace_bytes", G)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=speakers.device)
+    check(engine.lib.sdk_samples_runs(engine.ctx, speakers.data_ptr() if G else None, frame_off.data_ptr(), cent_off.data_ptr(), R, G, max_hyp, gap_frames,
+                                      min_frames, run_off.data_ptr(), rows.data_ptr(), cap, ws.data_ptr(), nbytes, _stream()), "sdk_samples_runs")
+    return run_off, rows
+
+
+def samples_score(engine, E: torch.Tensor, clip_off: torch.Tensor, clip_spk: torch.Tensor, spk_off: torch.Tensor, n_speakers: int):
+    """E [W, d] fp32 rows (read as they are; d a multiple of 64, at most diarize_host.MAX_ASSIGN_DIM), clip_off [M + 1] int32 (clip i holds the
+    rows clip_off[i]:clip_off[i + 1]), clip_spk [M] int32 (the clip's speaker numbered over the pack: spk_off[r] + k), spk_off [R + 1] int32
+    prefix sums of the recordings' speakers with spk_off[R] == n_speakers, all on the device -> (mean [S, d] float64, out_f [M, 2] float64 =
+    (own, rival), out_i [M, 3] int32 = (rival_speaker local, windows, alone)) on the device (sdk_samples_score; samples.py states the rule).
+    Nothing waits and E never goes to the host.
+
+    A function of the engine, not a method of it: Engine's public surface is pinned name for name (tests/test_ops_layout_cpu.py)."""
+    who = "samples_score"
+    _args.tensor(who, "E", E, "float32", (None, None))
+    W, d = int(E.shape[0]), _args.row_width(who, int(E.shape[1]))
+    M = int(_args.tensor(who, "clip_off", clip_off, "int32", (None,)).shape[0]) - 1
+    if M < 0:
+        raise ValueError(f"samples_score: clip_off must hold M + 1 >= 1 prefix sums, got {list(clip_off.shape)}")
+    _args.tensor(who, "clip_spk", clip_spk, "int32", (M,))
+    R = int(_args.tensor(who, "spk_off", spk_off, "int32", (None,)).shape[0]) - 1
+    if R < 1:
+        raise ValueError(f"samples_score: spk_off must hold R + 1 >= 2 prefix sums, got {list(spk_off.shape)}")
+    S = int(n_speakers)
+    if S < 0 or S >= 1 << 24 or M >= 1 << 24 or W >= 1 << 24:
+        raise ValueError(f"samples_score: W={W} windows, M={M} clips, S={S} speakers (fewer than 2^24 each)")
+    dev = E.device
+    mean = torch.empty((S, d), dtype=torch.float64, device=dev)
+    out_f = torch.empty((M, 2), dtype=torch.float64, device=dev)
+    out_i = torch.empty((M, 3), dtype=torch.int32, device=dev)
+    nbytes = engine._workspace_bytes("sdk_samples_score_workspace_bytes", M, S, d)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(engine.lib.sdk_samples_score(engine.ctx, E.data_ptr() if W else None, W, d, clip_off.data_ptr(), clip_spk.data_ptr() if M else None, M,
+                                       spk_off.data_ptr(), R, S, mean.data_ptr() if S else None, out_f.data_ptr() if M else None,
+                                       out_i.data_ptr() if M else None, ws.data_ptr(), nbytes, _stream()), "sdk_samples_score")
+    return mean, out_f, out_i
