@@ -19,12 +19,6 @@ namespace {
 constexpr int DZ_NT = 256;
 constexpr int DZ_MIN_CLEAN = 4;      // columns of the last map a speaker needs alone before the overlapped ones are dropped (diarize.MIN_CLEAN_COLUMNS)
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(DZ_NT) void powerset_decode_kernel(const float* __restrict__ logp, int64_t n, uint8_t* __restrict__ cls) {
   const int64_t i = (int64_t)blockIdx.x * DZ_NT + threadIdx.x;
   if (i >= n) return;
@@ -68,10 +62,10 @@ __global__ __launch_bounds__(64) void diarize_masks_kernel(const uint8_t* __rest
   bool use_clean[3];
 #pragma unroll
   for (int s = 0; s < 3; ++s) {
-    act[s] = wave_sum_i(act[s]);
-    cln[s] = wave_sum_i(cln[s]);
-    colf[s] = wave_sum_i(colf[s]);
-    colc[s] = wave_sum_i(colc[s]);
+    act[s] = wave_sum(act[s]);
+    cln[s] = wave_sum(cln[s]);
+    colf[s] = wave_sum(colf[s]);
+    colc[s] = wave_sum(colc[s]);
     use_clean[s] = colc[s] >= DZ_MIN_CLEAN;
     if (lane == 0) {
       int32_t* o = info + ((int64_t)b * 3 + s) * 4;
@@ -152,8 +146,8 @@ __global__ __launch_bounds__(DZ_NT) void diarize_reconstruct_kernel(const uint8_
 constexpr int DZ_TILE = 256;         // (row, label) pairs staged in LDS per step of the centroid sum
 
 // block = one cluster k, thread = the columns tid, tid + 256.  The n (row, label) pairs pass through LDS in tiles; every thread walks them in
-// ascending order and adds the rows labelled k in float64, so a column's sum has one owner and one order.  Then mean, norm (block sum of
-// squares in a fixed tree), unit row.  A cluster without rows gives a zero row.
+// ascending order and adds the rows labelled k in float64, so a column's sum has one owner and one order.  Then mean, norm (block_sum of
+// the squares, reduce.hpp), unit row.  A cluster without rows gives a zero row.
 __global__ __launch_bounds__(DZ_NT) void diarize_centroids_kernel(const float* __restrict__ E, const int32_t* __restrict__ rows,
                                                                   const int32_t* __restrict__ labels, int n, int d, float* __restrict__ cent,
                                                                   double* __restrict__ cent64) {
@@ -181,15 +175,7 @@ __global__ __launch_bounds__(DZ_NT) void diarize_centroids_kernel(const float* _
     }
   }
   if (cnt) { a0 /= (double)cnt; a1 /= (double)cnt; }
-  double q = (j0 < d ? a0 * a0 : 0.0) + (j1 < d ? a1 * a1 : 0.0);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-  if ((tid & 63) == 0) s_red[tid >> 6] = q;
-  __syncthreads();
-  double nrm = 0.0;
-#pragma unroll
-  for (int w = 0; w < DZ_NT / 64; ++w) nrm += s_red[w];
-  nrm = fmax(sqrt(nrm), 1e-300);
+  const double nrm = fmax(sqrt(block_sum((j0 < d ? a0 * a0 : 0.0) + (j1 < d ? a1 * a1 : 0.0), s_red)), 1e-300);
   a0 /= nrm;
   a1 /= nrm;
   if (j0 < d) {

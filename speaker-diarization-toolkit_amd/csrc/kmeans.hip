@@ -14,7 +14,7 @@
 //   km_step_kernel        n_iter = it + 1; from it = 1 on, an assignment that changed no label sets done
 //   km_sums_kernel        workgroup = (1024-row segment, centre): the segment's rows with that label, listed in ascending order by one wave
 //                         (ballot + popcount), summed in that order in float64, thread = columns tid, tid + 256
-//   km_finish_kernel      workgroup = centre: the segments' partials in segment order, the norm (fixed tree), c = s / |s|; a centre without
+//   km_finish_kernel      workgroup = centre: the segments' partials in segment order, the norm (block_sum, reduce.hpp), c = s / |s|; a centre without
 //                         rows, or with |s| = 0, is left as it was
 //
 // Every launch after `done` leaves at its first instruction, as in vbx.hip.  No floating-point atomics, one owner per output element, every
@@ -261,15 +261,7 @@ __global__ __launch_bounds__(KM_NT) void km_finish_kernel(int nseg, int d, int k
     if (j1 < d) a1 += p[j1];
     cnt += w.pcnt[s * k + kk];
   }
-  double q = (j0 < d ? a0 * a0 : 0.0) + (j1 < d ? a1 * a1 : 0.0);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-  if ((tid & 63) == 0) s_red[tid >> 6] = q;
-  __syncthreads();
-  double nrm = 0.0;
-#pragma unroll
-  for (int v = 0; v < KM_NT / 64; ++v) nrm += s_red[v];
-  nrm = sqrt(nrm);
+  const double nrm = sqrt(block_sum((j0 < d ? a0 * a0 : 0.0) + (j1 < d ? a1 * a1 : 0.0), s_red));
   if (cnt == 0 || !(nrm > 0.0)) return;                // uniform over the workgroup: the centre stays
   if (j0 < d) w.Ct[(int64_t)j0 * KM_MAX_K + kk] = a0 / nrm;
   if (j1 < d) w.Ct[(int64_t)j1 * KM_MAX_K + kk] = a1 / nrm;

@@ -3,7 +3,7 @@
 //
 //   pf_rowscale_kernel   wave = one fp32 row: s_i = sqrt(d) / max(|e_i - mean1|, 1e-300).  The stage-1 transform x1 = (e - mean1) s_i is then
 //                        applied wherever the statistics kernels load a row, by the same two operations, so they all see the same bits
-//                        (pf_project_kernel forms its own norm, in plda_transform_kernel's order, and may differ from them in the last bit).
+//                        (pf_project_kernel forms its own norm, in plda_front.hpp's order, and may differ from them in the last bit).
 //   pf_count_kernel      counts [K] int64 by integer atomics (exact in any order); a label outside [0, K) is counted nowhere and sets status
 //   pf_offsets_kernel    one block: the exclusive scan of the counts (the classes' segments of `order`)
 //   pf_class_kernel      block = class, thread = the columns tid, tid + 256: the class's rows in the order of `order` (the stable sort of the
@@ -15,7 +15,8 @@
 //                        waves, each a 32 x 32 quadrant = 2 x 2 MFMA tiles; rows enter 16 at a time through LDS (transformed once), the next
 //                        16 are in flight in registers meanwhile.  A quadrant below the diagonal of a diagonal macro tile is not computed.
 //   pf_scatter_finish_kernel   thread = an element (i <= j): the row blocks' partials in block order, written to [i][j] and [j][i]
-//   pf_project_kernel    the first two steps of plda_transform_kernel (vbx.hip) for all rows, no row table: x2 = sqrt(D0) unit(lda^T x1 - mean2)
+//   pf_project_kernel    the front transform of plda_front.hpp, which plda_transform_kernel (vbx.hip) starts with too, for all rows, no row
+//                        table: x2 = sqrt(D0) unit(lda^T x1 - mean2)
 //
 // Order of every sum (it depends on N, d, K and the labels only).  Rows are cut into nblk = ceil(N / RB) fixed blocks of
 // RB = max(512, 64 ceil(N / 16384)) rows (at most 256 blocks).  An element of the scatter: inside a row block, four rows per MFMA in ascending
@@ -23,18 +24,17 @@
 // ascending, then block order.  An element of a class sum: the class's rows in ascending row order.  No floating-point atomics, one owner per
 // output element: two calls on the same input return the same bits.  Row offsets are 64-bit; N <= 2^24.
 #include "common.hpp"
+#include "plda_front.hpp"
 
 #include <math.h>
 
 namespace {
 
 constexpr int PF_NT = 256;
-constexpr int PF_MAX_DIM = 512;
 constexpr int PF_MAX_ROWS = 1 << 24;
 constexpr int PF_MT = 64;            // macro tile of the scatter
 constexpr int PF_KC = 16;            // rows per LDS chunk
 constexpr int PF_LD = 80;            // LDS row pitch in doubles: rows k and k + 1 of a fragment read fall into different halves of the banks
-constexpr int PF_RPB = 4;            // rows per block of the projection
 constexpr int PF_ST_LABEL = 1;
 
 typedef double pf_d4 __attribute__((ext_vector_type(4)));
@@ -53,17 +53,6 @@ __device__ __forceinline__ double pf_at(const PfSrc& s, int64_t i, int j) {
   return s.mean1 ? (e - s.mean1[j]) * s.scale[i] : e;
 }
 
-__device__ __forceinline__ double pf_block_sum(double v, double* s_red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double r = 0.0;
-  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) r += s_red[w];
-  return r;
-}
-
 __global__ __launch_bounds__(PF_NT) void pf_rowscale_kernel(const float* __restrict__ E, const double* __restrict__ mean1, int n, int d,
                                                             double* __restrict__ scale) {
   const int lane = threadIdx.x & 63;
@@ -75,8 +64,7 @@ __global__ __launch_bounds__(PF_NT) void pf_rowscale_kernel(const float* __restr
     const double v = (double)e[j] - mean1[j];
     q = fma(v, v, q);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+  q = wave_sum(q);
   if (lane == 0) scale[i] = sqrt((double)d) / fmax(sqrt(q), 1e-300);
 }
 
@@ -234,50 +222,14 @@ __global__ __launch_bounds__(PF_NT) void pf_scatter_finish_kernel(const double* 
   S[(int64_t)j * d + i] = a;
 }
 
-__global__ __launch_bounds__(PF_NT) void pf_project_kernel(const float* __restrict__ E, int d_in, int n, const double* __restrict__ mean1,
-                                                           const double* __restrict__ lda, const double* __restrict__ mean2, int D0,
-                                                           double* __restrict__ X2) {
-  __shared__ double s_a[PF_RPB][PF_MAX_DIM];
-  __shared__ double s_red[PF_NT / 64];
-  const int tid = threadIdx.x;
-  const int64_t i0 = (int64_t)blockIdx.x * PF_RPB;
-  const int j0 = tid, j1 = tid + PF_NT;
-  // 1: x1 = sqrt(d_in) unit(e - mean1)
-  for (int r = 0; r < PF_RPB; ++r) {
-    const bool ok = i0 + r < n;                                          // uniform over the block
-    const float* e = E + (ok ? i0 + r : 0) * d_in;
-    const double v0 = ok && j0 < d_in ? (double)e[j0] - mean1[j0] : 0.0;
-    const double v1 = ok && j1 < d_in ? (double)e[j1] - mean1[j1] : 0.0;
-    const double nrm = pf_block_sum(fma(v0, v0, v1 * v1), s_red);
-    const double sc = sqrt((double)d_in) / fmax(sqrt(nrm), 1e-300);
-    if (j0 < d_in) s_a[r][j0] = v0 * sc;
-    if (j1 < d_in) s_a[r][j1] = v1 * sc;
-  }
-  __syncthreads();
-  // 2: x2 = sqrt(D0) unit(lda^T x1 - mean2)
-  double a0[PF_RPB], a1[PF_RPB];
-#pragma unroll
-  for (int r = 0; r < PF_RPB; ++r) a0[r] = a1[r] = 0.0;
-  for (int i = 0; i < d_in; ++i) {
-    const double l0 = j0 < D0 ? lda[(int64_t)i * D0 + j0] : 0.0;
-    const double l1 = j1 < D0 ? lda[(int64_t)i * D0 + j1] : 0.0;
-#pragma unroll
-    for (int r = 0; r < PF_RPB; ++r) {
-      const double x = s_a[r][i];
-      a0[r] = fma(x, l0, a0[r]);
-      a1[r] = fma(x, l1, a1[r]);
-    }
-  }
-  for (int r = 0; r < PF_RPB; ++r) {
-    const double v0 = j0 < D0 ? a0[r] - mean2[j0] : 0.0;
-    const double v1 = j1 < D0 ? a1[r] - mean2[j1] : 0.0;
-    const double nrm = pf_block_sum(fma(v0, v0, v1 * v1), s_red);
-    const double sc = sqrt((double)D0) / fmax(sqrt(nrm), 1e-300);
-    if (i0 + r < n) {
-      if (j0 < D0) X2[(i0 + r) * D0 + j0] = v0 * sc;
-      if (j1 < D0) X2[(i0 + r) * D0 + j1] = v1 * sc;
-    }
-  }
+__global__ __launch_bounds__(PLDA_NT) void pf_project_kernel(const float* __restrict__ E, int d_in, int n, const double* __restrict__ mean1,
+                                                             const double* __restrict__ lda, const double* __restrict__ mean2, int D0,
+                                                             double* __restrict__ X2) {
+  __shared__ double s_a[PLDA_RPB][PLDA_MAX_DIM];
+  __shared__ double s_red[PLDA_NT / 64];
+  const int64_t i0 = (int64_t)blockIdx.x * PLDA_RPB;
+  plda_front([&](int r) { return i0 + r < n ? E + (i0 + r) * d_in : nullptr; }, d_in, mean1, lda, mean2, D0, s_a, s_red,
+             [&](int r, int j, double x2) { if (i0 + r < n) X2[(i0 + r) * D0 + j] = x2; });
 }
 
 inline size_t pf_align(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -307,13 +259,13 @@ PfLayout pf_layout(int n, int d, int K, int with_scatter) {
   return l;
 }
 
-bool pf_shape_ok(int n, int d, int K) { return n >= 1 && n <= PF_MAX_ROWS && d >= 1 && d <= PF_MAX_DIM && K >= 0 && K <= PF_MAX_ROWS; }
+bool pf_shape_ok(int n, int d, int K) { return n >= 1 && n <= PF_MAX_ROWS && d >= 1 && d <= PLDA_MAX_DIM && K >= 0 && K <= PF_MAX_ROWS; }
 
 }  // namespace
 
 extern "C" size_t sdk_plda_fit_stats_workspace_bytes(int n, int d, int K, int with_scatter) {
   if (!pf_shape_ok(n, d, K)) {
-    sdk_set_error("sdk_plda_fit_stats_workspace_bytes: n=%d d=%d K=%d (n 1 .. %d, d 1 .. %d, K 0 .. %d)", n, d, K, PF_MAX_ROWS, PF_MAX_DIM, PF_MAX_ROWS);
+    sdk_set_error("sdk_plda_fit_stats_workspace_bytes: n=%d d=%d K=%d (n 1 .. %d, d 1 .. %d, K 0 .. %d)", n, d, K, PF_MAX_ROWS, PLDA_MAX_DIM, PF_MAX_ROWS);
     return 0;
   }
   return pf_layout(n, d, K, with_scatter).bytes;
@@ -326,8 +278,8 @@ extern "C" int sdk_plda_fit_stats(sdk_ctx* ctx, const float* E, const double* X,
   SDK_REQUIRE(n >= 1 && n <= PF_MAX_ROWS, "sdk_plda_fit_stats: n=%d rows (1 .. %d)", n, PF_MAX_ROWS);
   SDK_REQUIRE((E != nullptr) != (X != nullptr), "sdk_plda_fit_stats: exactly one source (E=%p fp32 rows, X=%p float64 rows)", (const void*)E,
               (const void*)X);
-  if (E) SDK_REQUIRE(d >= 64 && d <= PF_MAX_DIM && d % 64 == 0, "sdk_plda_fit_stats: d=%d not supported for fp32 rows (a multiple of 64, at most %d)", d, PF_MAX_DIM);
-  else SDK_REQUIRE(d >= 1 && d <= PF_MAX_DIM && !mean1, "sdk_plda_fit_stats: float64 rows take d=%d in 1 .. %d and no mean1", d, PF_MAX_DIM);
+  if (E) SDK_REQUIRE(d >= 64 && d <= PLDA_MAX_DIM && d % 64 == 0, "sdk_plda_fit_stats: d=%d not supported for fp32 rows (a multiple of 64, at most %d)", d, PLDA_MAX_DIM);
+  else SDK_REQUIRE(d >= 1 && d <= PLDA_MAX_DIM && !mean1, "sdk_plda_fit_stats: float64 rows take d=%d in 1 .. %d and no mean1", d, PLDA_MAX_DIM);
   SDK_REQUIRE(K >= 0 && K <= PF_MAX_ROWS, "sdk_plda_fit_stats: K=%d classes (0 .. %d)", K, PF_MAX_ROWS);
   if (K > 0) SDK_REQUIRE(labels && order && counts && sums, "sdk_plda_fit_stats: K=%d needs labels=%p order=%p counts=%p sums=%p", K,
                          (const void*)labels, (const void*)order, (void*)counts, (void*)sums);
@@ -365,13 +317,13 @@ extern "C" int sdk_plda_project(sdk_ctx* ctx, const float* E, int d_in, int n, c
                                 double* X2, void* stream) {
   SDK_REQUIRE(ctx, "sdk_plda_project: null context");
   SDK_REQUIRE(n >= 1 && n <= PF_MAX_ROWS, "sdk_plda_project: n=%d rows (1 .. %d)", n, PF_MAX_ROWS);
-  SDK_REQUIRE(d_in >= 64 && d_in <= PF_MAX_DIM && d_in % 64 == 0, "sdk_plda_project: d_in=%d not supported (a multiple of 64, at most %d)", d_in,
-              PF_MAX_DIM);
-  SDK_REQUIRE(D0 >= 1 && D0 <= PF_MAX_DIM, "sdk_plda_project: D0=%d (1 .. %d)", D0, PF_MAX_DIM);
+  SDK_REQUIRE(d_in >= 64 && d_in <= PLDA_MAX_DIM && d_in % 64 == 0, "sdk_plda_project: d_in=%d not supported (a multiple of 64, at most %d)", d_in,
+              PLDA_MAX_DIM);
+  SDK_REQUIRE(D0 >= 1 && D0 <= PLDA_MAX_DIM, "sdk_plda_project: D0=%d (1 .. %d)", D0, PLDA_MAX_DIM);
   SDK_REQUIRE(E && mean1 && lda && mean2 && X2, "sdk_plda_project: null argument (E=%p mean1=%p lda=%p mean2=%p X2=%p)", (const void*)E,
               (const void*)mean1, (const void*)lda, (const void*)mean2, (void*)X2);
   ProfScope ps(ctx, stream, SDK_K_COPY, 0.0, (double)n * (4.0 * d_in + 8.0 * D0) + 8.0 * D0 * d_in);
-  hipLaunchKernelGGL(pf_project_kernel, dim3((n + PF_RPB - 1) / PF_RPB), dim3(PF_NT), 0, (hipStream_t)stream, E, d_in, n, mean1, lda, mean2, D0, X2);
+  hipLaunchKernelGGL(pf_project_kernel, dim3((n + PLDA_RPB - 1) / PLDA_RPB), dim3(PLDA_NT), 0, (hipStream_t)stream, E, d_in, n, mean1, lda, mean2, D0, X2);
   SDK_LAUNCH_CHECK();
   return 0;
 }

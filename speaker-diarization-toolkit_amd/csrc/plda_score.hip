@@ -116,8 +116,7 @@ __global__ __launch_bounds__(PS_NT) void pe_pool_kernel(const double* __restrict
       const int v = rows[p0 + j];
       if (v > last && v < best) best = v;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) best = min(best, __shfl_xor(best, o, 64));
+    best = wave_min(best);
     if ((unsigned)best >= (unsigned)P) break;            // cannot happen (m distinct rows in [0, P)); never an index outside Xp
     last = best;
 #pragma unroll
@@ -142,8 +141,7 @@ __global__ __launch_bounds__(PS_NT) void pe_pool_kernel(const double* __restrict
     G[(int64_t)s * (2 * D) + d] = g;
     G[(int64_t)s * (2 * D) + D + d] = q;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) term += __shfl_xor(term, o, 64);
+  term = wave_sum(term);
   if (lane == 0) r[s] = ok ? term : (double)NAN;
 }
 

@@ -293,12 +293,6 @@ SmWs sm_layout(int64_t G) {
 // ---------------------------------------------------------------------------------------------------------------- scores
 constexpr int SS_NT = 256;
 
-__device__ __forceinline__ double ss_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ void ss_clip_sum_kernel(const float* __restrict__ E, const int32_t* __restrict__ clip_off, int W, int d, double* __restrict__ c,
                                    int32_t* __restrict__ out_i) {
   const int i = blockIdx.x;
@@ -368,7 +362,7 @@ __global__ __launch_bounds__(SS_NT) void ss_score_kernel(const double* __restric
     const double a = ci[col], m = ms[col] - a;
     p0 += a * m; p1 += a * a; p2 += m * m;
   }
-  p0 = ss_wave_sum(p0); p1 = ss_wave_sum(p1); p2 = ss_wave_sum(p2);
+  p0 = wave_sum(p0); p1 = wave_sum(p1); p2 = wave_sum(p2);
   if (lane == 0) { red[w][0] = p0; red[w][1] = p1; red[w][2] = p2; }
   __syncthreads();
   p0 = p1 = p2 = 0.0;
@@ -396,7 +390,7 @@ __global__ __launch_bounds__(SS_NT) void ss_score_kernel(const double* __restric
           q0 += av[q] * m; q1 += m * m;
         }
       }
-      q0 = ss_wave_sum(q0); q1 = ss_wave_sum(q1);
+      q0 = wave_sum(q0); q1 = wave_sum(q1);
       if (!(q1 > 0.0)) continue;
       const double cs = q0 / (sqrt(p1) * sqrt(q1));
       if (cs == cs && (bt < 0 || cs > bc)) { bc = cs; bt = t; }   // t ascends: at equal values the lower t stays

@@ -74,12 +74,6 @@ __global__ __launch_bounds__(SC_NT) void score_collar_kernel(const int32_t* __re
   for (int64_t g = lo + lane; g < hi; g += 64) scored[g0 + g] = 0;
 }
 
-__device__ __forceinline__ int sc_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(SC_NT) void score_cooccur_kernel(const unsigned long long* __restrict__ ref_mask, const uint8_t* __restrict__ scored,
                                                               const int32_t* __restrict__ speakers, const int32_t* __restrict__ frame_off,
                                                               const int32_t* __restrict__ ref_off, const int32_t* __restrict__ cent_off,
@@ -119,7 +113,7 @@ __global__ __launch_bounds__(SC_NT) void score_cooccur_kernel(const unsigned lon
         if (on1) atomicAdd(&tab[i * K + h1], 1);
       }
     }
-    n_sc = sc_wave_sum(n_sc); n_ref = sc_wave_sum(n_ref); n_miss = sc_wave_sum(n_miss); n_fa = sc_wave_sum(n_fa); n_both = sc_wave_sum(n_both);
+    n_sc = wave_sum(n_sc); n_ref = wave_sum(n_ref); n_miss = wave_sum(n_miss); n_fa = wave_sum(n_fa); n_both = wave_sum(n_both);
     if ((tid & 63) == 0) {
       atomicAdd(&tal[0], n_sc); atomicAdd(&tal[1], n_ref); atomicAdd(&tal[2], n_miss); atomicAdd(&tal[3], n_fa); atomicAdd(&tal[4], n_both);
     }
@@ -208,8 +202,7 @@ __global__ __launch_bounds__(64) void score_map_kernel(const int32_t* __restrict
     const int c = w[p * SC_MAX + lane];
     if (c > 0) { row_col[p] = lane; sum = c; }                  // a pair that never co-occurs is no pair
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  sum = wave_sum(sum);
   __syncthreads();
   if (lane < S) map[ref_off[r] + lane] = row_col[lane];
   if (lane == 0) correct[r] = sum;

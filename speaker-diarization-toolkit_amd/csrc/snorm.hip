@@ -9,7 +9,7 @@
 //   snorm_select_kernel   one workgroup per row of S: radix select (4 x 8 bits, LDS histograms with INTEGER atomics) on the order-preserving
 //                         uint32 key of the fp32 score finds the K-th largest value t and the count c of scores strictly above it; then
 //                         mean = (sum_{s > t} s + (K - c) t) / K and var = (sum_{s > t} (s - mean)^2 + (K - c) (t - mean)^2) / K in float64:
-//                         a thread adds its columns (tid, tid + 256, ..) in ascending order, the 256 partial sums meet in a fixed tree.
+//                         a thread adds its columns (tid, tid + 256, ..) in ascending order, the 256 partial sums meet in a fixed tree (block_sum, reduce.hpp).
 //   snorm_topk_kernel     epilogue 2: z = ((s - mean_e) / std_e + (s - mean_p) / std_p) / 2 in float64, a running top-4 per (row, 32-column
 //                         part) across the profile tiles, merged at the end; ties to the lower profile, a NaN z never wins.
 //
@@ -120,16 +120,6 @@ __device__ __forceinline__ uint32_t score_key(float s) {
 }
 __device__ __forceinline__ float key_score(uint32_t key) { return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key); }
 
-// the block's 256 values in a fixed tree: xor shuffles inside a wave, then the four waves in order (every thread returns the sum)
-__device__ __forceinline__ double sn_block_sum(double v, double* s_red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();                                     // s_red is free again
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
-}
-
 __global__ __launch_bounds__(SN_NT) void snorm_select_kernel(const float* __restrict__ S, int M, int K, float* __restrict__ mean,
                                                              float* __restrict__ sd) {
   __shared__ int s_hist[256];
@@ -177,7 +167,7 @@ __global__ __launch_bounds__(SN_NT) void snorm_select_kernel(const float* __rest
     const float s = row[j];
     if (score_key(s) > tkey) a += (double)s;
   }
-  const double mu = (sn_block_sum(a, s_red) + nk * t) / dK;
+  const double mu = (block_sum(a, s_red) + nk * t) / dK;
   a = 0.0;
   for (int j = tid; j < M; j += SN_NT) {
     const float s = row[j];
@@ -186,7 +176,7 @@ __global__ __launch_bounds__(SN_NT) void snorm_select_kernel(const float* __rest
       a += dv * dv;
     }
   }
-  const double var = (sn_block_sum(a, s_red) + nk * ((t - mu) * (t - mu))) / dK;
+  const double var = (block_sum(a, s_red) + nk * ((t - mu) * (t - mu))) / dK;
   if (tid == 0) {
     const float sdev = (float)sqrt(var);
     mean[blockIdx.x] = (float)mu;

@@ -148,16 +148,7 @@ __global__ __launch_bounds__(ST_NT) void stream_step_kernel(const float* __restr
     double v0 = 0.0, v1 = 0.0;
     if (j0 < d) v0 = (how == 1 ? Sk[j0] : 0.0) + L.e[s][j0];
     if (j1 < d) v1 = (how == 1 ? Sk[j1] : 0.0) + L.e[s][j1];
-    double q = v0 * v0 + v1 * v1;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
-    __syncthreads();                                     // s_red of the slot before has been read
-    if ((tid & 63) == 0) s_red[tid >> 6] = q;
-    __syncthreads();
-    double nrm = 0.0;
-#pragma unroll
-    for (int w = 0; w < ST_NT / 64; ++w) nrm += s_red[w];
-    nrm = fmax(sqrt(nrm), 1e-300);
+    const double nrm = fmax(sqrt(block_sum(v0 * v0 + v1 * v1, s_red)), 1e-300);
     if (j0 < d) { Sk[j0] = v0; Uk[j0] = v0 / nrm; }
     if (j1 < d) { Sk[j1] = v1; Uk[j1] = v1 / nrm; }
     if (tid == 0) st.hdr->n[k] = how == 1 ? st.hdr->n[k] + 1 : 1;

@@ -47,12 +47,6 @@ struct TrCount {
   uint32_t under[2], over[2], nan[2], excluded;
 };
 
-__device__ __forceinline__ uint32_t tr_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
-  return v;
-}
-
 // HIST = false: the bench-only variant without the LDS atomics (in-range trials are counted per class in a register and land in bin 0)
 template <bool HIST>
 __global__ __launch_bounds__(TR_NT) void tr_hist_kernel(const double* __restrict__ A, int N, const double* __restrict__ B,
@@ -87,7 +81,7 @@ __global__ __launch_bounds__(TR_NT) void tr_hist_kernel(const double* __restrict
     }
     uint32_t v[9] = {c.under[0], c.under[1], c.over[0], c.over[1], c.nan[0], c.nan[1], c.excluded, inr[0], inr[1]};
 #pragma unroll
-    for (int k = 0; k < 9; ++k) v[k] = tr_wave_sum(v[k]);             // at most 64 lanes x 2^19 tiles x 16 elements = 2^29
+    for (int k = 0; k < 9; ++k) v[k] = wave_sum(v[k]);             // at most 64 lanes x 2^19 tiles x 16 elements = 2^29
     if (lane == 0) {
 #pragma unroll
       for (int k = 0; k < 7; ++k)
@@ -229,18 +223,6 @@ constexpr int TC_COUNTS = 5;                // n[2], nonfinite[2], excluded
 constexpr int TC_DEFAULT_BLOCKS = 512;      // 256 CUs x 2 workgroups: the compiler gives 191 VGPRs + 32 AGPRs, no scratch, 2 waves / SIMD - the registers bind, not
                                             // the 22 KB of LDS (forced to 3 waves / SIMD it fits 168 VGPRs with 12 bytes of scratch per lane: not taken, unmeasured)
 
-__device__ __forceinline__ double tc_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = __dadd_rn(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-__device__ __forceinline__ unsigned long long tc_wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (unsigned long long)__shfl_xor((long long)v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(TR_NT) void tr_calib_kernel(const double* __restrict__ A, int N, const double* __restrict__ B,
                                                          const double* __restrict__ r, int M, int K, const int32_t* __restrict__ la,
                                                          const int32_t* __restrict__ sa, const int32_t* __restrict__ lb,
@@ -364,16 +346,16 @@ __global__ __launch_bounds__(TR_NT) void tr_calib_kernel(const double* __restric
   for (int c = 0; c < 2; ++c) {
 #pragma unroll
     for (int k = 0; k < TC_TERMS; ++k) {
-      const double t = tc_wave_sum(sum[c][k]);
+      const double t = wave_sum(sum[c][k]);
       if (lane == 0) s_red[wave][c * TC_TERMS + k] = t;
     }
-    const unsigned long long tn = tc_wave_sum(n[c]), tf = tc_wave_sum(nonfinite[c]);
+    const unsigned long long tn = wave_sum(n[c]), tf = wave_sum(nonfinite[c]);
     if (lane == 0) {
       s_cnt[wave][c] = tn;
       if (tf) atomicAdd(counts + 2 + c, tf);
     }
   }
-  const unsigned long long tx = tc_wave_sum(excluded);
+  const unsigned long long tx = wave_sum(excluded);
   if (lane == 0 && tx) atomicAdd(counts + 4, tx);
   __syncthreads();
   double* row = partials + (size_t)blockIdx.x * TC_ROW;

@@ -61,12 +61,6 @@ struct TsCount {
   uint32_t under[2], over[2], nan[2], excluded;
 };
 
-__device__ __forceinline__ uint32_t ts_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(TS_NT) void tr_hist_snorm_kernel(const double* __restrict__ A, int N, const double* __restrict__ B, int M, int K,
                                                               const double* __restrict__ mean_a, const double* __restrict__ inv_a,
                                                               const double* __restrict__ mean_b, const double* __restrict__ inv_b,
@@ -100,7 +94,7 @@ __global__ __launch_bounds__(TS_NT) void tr_hist_snorm_kernel(const double* __re
     }
     uint32_t v[7] = {c.under[0], c.under[1], c.over[0], c.over[1], c.nan[0], c.nan[1], c.excluded};
 #pragma unroll
-    for (int k = 0; k < 7; ++k) v[k] = ts_wave_sum(v[k]);             // at most 64 lanes x 2^19 tiles x 16 elements = 2^29
+    for (int k = 0; k < 7; ++k) v[k] = wave_sum(v[k]);             // at most 64 lanes x 2^19 tiles x 16 elements = 2^29
     if (lane == 0) {
 #pragma unroll
       for (int k = 0; k < 7; ++k)

@@ -1,14 +1,14 @@
 // VBx clustering (plda.py, cluster.vbx_cluster): the PLDA transform of the training embeddings, the variational-Bayes mixture that re-estimates
 // the speakers the centroid linkage initialised, and the responsibility-weighted centroids the assignment stage reads.  Float64 throughout.
 //
-//   plda_transform_kernel   E rows -> X [n][D]: centre, length-normalise, LDA, centre, length-normalise, PLDA basis.  Block = 4 rows, thread = a
-//                           column; every dot product runs over its index in ascending order.
+//   plda_transform_kernel   E rows -> X [n][D]: the front transform of plda_front.hpp (centre, length-normalise, LDA, centre, length-normalise),
+//                           then the PLDA basis.  Block = 4 rows, thread = a column; every dot product runs over its index in ascending order.
 //   vbx_reset_kernel        pi = 1 / S, elbo = 0, n_iter = status = done = 0
 //   vbx_init_kernel         wave = one row: rho = x sqrt(Phi), G_t, gamma0 from the initial labels; a non-finite rho sets status and done
 //   vbx_stats_kernel        block = (64-row block b, 16 speakers): partial N[b][s] and F[b][s][:] = sum over the block's rows, ascending; and the
 //                           block's partial of sum_t lse_t
 //   vbx_finish_kernel       one block: N_s = partials in block order; ELBO, the stop test, n_iter and pi
-//   vbx_mstep_kernel        block = speaker: F_s = partials in block order, invL, alpha, and the two per-speaker sums over d (fixed tree)
+//   vbx_mstep_kernel        block = speaker: F_s = partials in block order, invL, alpha, and the two per-speaker sums over d (block_sum, reduce.hpp)
 //   vbx_estep_kernel        wave = 4 rows at a time, lane = speaker (lane-strided over any S): z, lse, gamma
 //   vbx_keep_kernel / vbx_labels_kernel / vbx_centroids_kernel   speakers with pi > 1e-7, the rows' hard labels, the kept speakers' centroids
 //   vbx_chain_kernel / vbx_chain_mem_kernel / vbx_hmm_post_kernel / vbx_hmm_finish_kernel   sdk_vbx_hmm: the HMM's forward and backward passes over
@@ -18,6 +18,7 @@
 // order); no floating-point atomics; one owner per output element: results are bit-identical run to run.  The iterations are enqueued back to
 // back; the stop test runs on the device (vbx_finish_kernel sets `done`), and every later launch leaves at its first instruction.
 #include "common.hpp"
+#include "plda_front.hpp"
 
 #include <math.h>
 
@@ -26,91 +27,33 @@ namespace {
 constexpr int VB_NT = 256;
 constexpr int VB_ROWS = 64;          // rows per block of every sum over rows
 constexpr int VB_SC = 16;            // speakers per block of the statistics kernel
-constexpr int VB_RPB = 4;            // rows per block of the transform
-constexpr int VB_MAX_DIM = 512;      // d_in and D0
 constexpr int VB_MAX_ROWS = 65536;   // diarize.MAX_LINKAGE_ROWS
 constexpr int VB_ST_NONFINITE = 1, VB_ST_LABEL = 2, VB_ST_ELBO = 4;
 
-// sum over the block (blockDim a multiple of 64, at most 256) in a fixed tree; every thread gets it.  Uniform control flow only.
-__device__ __forceinline__ double block_sum(double v, double* s_red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double r = 0.0;
-  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) r += s_red[w];
-  return r;
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-__global__ __launch_bounds__(VB_NT) void plda_transform_kernel(const float* __restrict__ E, int d_in, const int32_t* __restrict__ rows, int n,
-                                                               const double* __restrict__ mean1, const double* __restrict__ lda,
-                                                               const double* __restrict__ mean2, const double* __restrict__ mu,
-                                                               const double* __restrict__ Tt, int D0, int D, double* __restrict__ X) {
-  __shared__ double s_a[VB_RPB][VB_MAX_DIM];
-  __shared__ double s_b[VB_RPB][VB_MAX_DIM];
-  __shared__ double s_red[VB_NT / 64];
-  const int tid = threadIdx.x, i0 = blockIdx.x * VB_RPB;
-  const int j0 = tid, j1 = tid + VB_NT;
-  // 1: x1 = sqrt(d_in) unit(e - mean1)
-  for (int r = 0; r < VB_RPB; ++r) {
-    const bool ok = i0 + r < n;                                          // uniform over the block
-    const float* e = E + (int64_t)(ok ? rows[i0 + r] : 0) * d_in;
-    const double v0 = ok && j0 < d_in ? (double)e[j0] - mean1[j0] : 0.0;
-    const double v1 = ok && j1 < d_in ? (double)e[j1] - mean1[j1] : 0.0;
-    const double nrm = block_sum(fma(v0, v0, v1 * v1), s_red);
-    const double sc = sqrt((double)d_in) / fmax(sqrt(nrm), 1e-300);
-    if (j0 < d_in) s_a[r][j0] = v0 * sc;
-    if (j1 < d_in) s_a[r][j1] = v1 * sc;
-  }
-  __syncthreads();
-  // 2: x2 = sqrt(D0) unit(lda^T x1 - mean2), stored minus mu
-  double a0[VB_RPB], a1[VB_RPB];
-#pragma unroll
-  for (int r = 0; r < VB_RPB; ++r) a0[r] = a1[r] = 0.0;
-  for (int i = 0; i < d_in; ++i) {
-    const double l0 = j0 < D0 ? lda[(int64_t)i * D0 + j0] : 0.0;
-    const double l1 = j1 < D0 ? lda[(int64_t)i * D0 + j1] : 0.0;
-#pragma unroll
-    for (int r = 0; r < VB_RPB; ++r) {
-      const double x = s_a[r][i];
-      a0[r] = fma(x, l0, a0[r]);
-      a1[r] = fma(x, l1, a1[r]);
-    }
-  }
-  for (int r = 0; r < VB_RPB; ++r) {
-    const double v0 = j0 < D0 ? a0[r] - mean2[j0] : 0.0;
-    const double v1 = j1 < D0 ? a1[r] - mean2[j1] : 0.0;
-    const double nrm = block_sum(fma(v0, v0, v1 * v1), s_red);
-    const double sc = sqrt((double)D0) / fmax(sqrt(nrm), 1e-300);
-    if (j0 < D0) s_b[r][j0] = v0 * sc - mu[j0];
-    if (j1 < D0) s_b[r][j1] = v1 * sc - mu[j1];
-  }
+__global__ __launch_bounds__(PLDA_NT) void plda_transform_kernel(const float* __restrict__ E, int d_in, const int32_t* __restrict__ rows, int n,
+                                                                 const double* __restrict__ mean1, const double* __restrict__ lda,
+                                                                 const double* __restrict__ mean2, const double* __restrict__ mu,
+                                                                 const double* __restrict__ Tt, int D0, int D, double* __restrict__ X) {
+  __shared__ double s_a[PLDA_RPB][PLDA_MAX_DIM];
+  __shared__ double s_b[PLDA_RPB][PLDA_MAX_DIM];
+  __shared__ double s_red[PLDA_NT / 64];
+  const int tid = threadIdx.x, i0 = blockIdx.x * PLDA_RPB;
+  // 1, 2: x2 (plda_front.hpp), stored minus mu
+  plda_front([&](int r) { return i0 + r < n ? E + (int64_t)rows[i0 + r] * d_in : nullptr; }, d_in, mean1, lda, mean2, D0, s_a, s_red,
+             [&](int r, int j, double x2) { s_b[r][j] = x2 - mu[j]; });
   __syncthreads();
   // 3: x = ((x2 - mu) T^T)[:D]; Tt [D0][D] holds the first D rows of T, transposed
-  for (int j = tid; j < D; j += VB_NT) {
-    double acc[VB_RPB];
+  for (int j = tid; j < D; j += PLDA_NT) {
+    double acc[PLDA_RPB];
 #pragma unroll
-    for (int r = 0; r < VB_RPB; ++r) acc[r] = 0.0;
+    for (int r = 0; r < PLDA_RPB; ++r) acc[r] = 0.0;
     for (int k = 0; k < D0; ++k) {
       const double t = Tt[(int64_t)k * D + j];
 #pragma unroll
-      for (int r = 0; r < VB_RPB; ++r) acc[r] = fma(s_b[r][k], t, acc[r]);
+      for (int r = 0; r < PLDA_RPB; ++r) acc[r] = fma(s_b[r][k], t, acc[r]);
     }
 #pragma unroll
-    for (int r = 0; r < VB_RPB; ++r)
+    for (int r = 0; r < PLDA_RPB; ++r)
       if (i0 + r < n) X[(int64_t)(i0 + r) * D + j] = acc[r];
   }
 }
@@ -150,7 +93,7 @@ __global__ __launch_bounds__(VB_NT) void vbx_init_kernel(const double* __restric
     q = fma(x, x, q);
     bad = bad || !isfinite(r);
   }
-  q = wave_sum_d(q);
+  q = wave_sum(q);
   const int lab = labels[t];
   if (lane == 0) w.G[t] = -0.5 * (q + (double)D * 1.8378770664093454835606594728112);      // ln 2 pi
   if (bad) { atomicOr(status, VB_ST_NONFINITE); *w.done = 1; }
@@ -184,7 +127,7 @@ __global__ __launch_bounds__(128) void vbx_stats_kernel(const double* __restrict
     w.Npart[(int64_t)b * S + s0 + d] = a;
   }
   if (with_lse && blockIdx.y == 0 && d < 64) {                           // the first wave (D is 64 or 128)
-    const double v = wave_sum_d(d < m ? w.lse[t0 + d] : 0.0);
+    const double v = wave_sum(d < m ? w.lse[t0 + d] : 0.0);
     if (d == 0) w.lsepart[b] = v;
   }
 }
@@ -287,7 +230,7 @@ __global__ __launch_bounds__(VB_NT) void vbx_estep_kernel(const double* __restri
     }
     if (LOGP) continue;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) M[r] = wave_max_d(M[r]);
+    for (int r = 0; r < 4; ++r) M[r] = wave_max(M[r]);
     double sum[4] = {0.0, 0.0, 0.0, 0.0};
     for (int s = lane; s < S; s += 64) {
 #pragma unroll
@@ -296,7 +239,7 @@ __global__ __launch_bounds__(VB_NT) void vbx_estep_kernel(const double* __restri
     }
     double lse[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) lse[r] = M[r] + log(wave_sum_d(sum[r]));
+    for (int r = 0; r < 4; ++r) lse[r] = M[r] + log(wave_sum(sum[r]));
     for (int s = lane; s < S; s += 64) {
 #pragma unroll
       for (int r = 0; r < 4; ++r)
@@ -676,15 +619,15 @@ extern "C" int sdk_plda_transform(sdk_ctx* ctx, const float* E, int d_in, const 
                                   const double* mean2, const double* mu, const double* Tt, int D0, int D, double* X, void* stream) {
   SDK_REQUIRE(ctx, "sdk_plda_transform: null context");
   SDK_REQUIRE(n >= 0 && n <= VB_MAX_ROWS, "sdk_plda_transform: n=%d (0 .. %d)", n, VB_MAX_ROWS);
-  SDK_REQUIRE(d_in >= 64 && d_in <= VB_MAX_DIM && d_in % 64 == 0, "sdk_plda_transform: d_in=%d not supported (a multiple of 64, at most %d)", d_in,
-              VB_MAX_DIM);
-  SDK_REQUIRE(D0 >= 1 && D0 <= VB_MAX_DIM, "sdk_plda_transform: D0=%d (1 .. %d)", D0, VB_MAX_DIM);
+  SDK_REQUIRE(d_in >= 64 && d_in <= PLDA_MAX_DIM && d_in % 64 == 0, "sdk_plda_transform: d_in=%d not supported (a multiple of 64, at most %d)", d_in,
+              PLDA_MAX_DIM);
+  SDK_REQUIRE(D0 >= 1 && D0 <= PLDA_MAX_DIM, "sdk_plda_transform: D0=%d (1 .. %d)", D0, PLDA_MAX_DIM);
   SDK_REQUIRE((D == 64 || D == 128) && D <= D0, "sdk_plda_transform: D=%d not supported (64 or 128, at most D0=%d)", D, D0);
   if (n == 0) return 0;
   SDK_REQUIRE(E && rows && mean1 && lda && mean2 && mu && Tt && X, "sdk_plda_transform: null argument (E=%p rows=%p mean1=%p lda=%p mean2=%p mu=%p Tt=%p X=%p)",
               (const void*)E, (const void*)rows, (const void*)mean1, (const void*)lda, (const void*)mean2, (const void*)mu, (const void*)Tt, (void*)X);
   ProfScope ps(ctx, stream, SDK_K_COPY, 2.0 * n * ((double)d_in * D0 + (double)D0 * D), (double)n * (4.0 * d_in + 8.0 * D) + 8.0 * D0 * (d_in + D));
-  hipLaunchKernelGGL(plda_transform_kernel, dim3((n + VB_RPB - 1) / VB_RPB), dim3(VB_NT), 0, (hipStream_t)stream, E, d_in, rows, n, mean1, lda, mean2, mu,
+  hipLaunchKernelGGL(plda_transform_kernel, dim3((n + PLDA_RPB - 1) / PLDA_RPB), dim3(PLDA_NT), 0, (hipStream_t)stream, E, d_in, rows, n, mean1, lda, mean2, mu,
                      Tt, D0, D, X);
   SDK_LAUNCH_CHECK();
   return 0;
@@ -800,7 +743,7 @@ extern "C" int sdk_vbx_centroids(sdk_ctx* ctx, const double* gamma, const double
                                  int32_t* K, int32_t* keep, int32_t* labels, float* cent, double* cent64, void* stream) {
   SDK_REQUIRE(ctx, "sdk_vbx_centroids: null context");
   SDK_REQUIRE(n >= 1 && n <= VB_MAX_ROWS && S >= 1 && S <= VB_MAX_ROWS, "sdk_vbx_centroids: n=%d S=%d (each 1 .. %d)", n, S, VB_MAX_ROWS);
-  SDK_REQUIRE(d >= 64 && d <= VB_MAX_DIM && d % 64 == 0, "sdk_vbx_centroids: d=%d not supported (a multiple of 64, at most %d)", d, VB_MAX_DIM);
+  SDK_REQUIRE(d >= 64 && d <= PLDA_MAX_DIM && d % 64 == 0, "sdk_vbx_centroids: d=%d not supported (a multiple of 64, at most %d)", d, PLDA_MAX_DIM);
   SDK_REQUIRE(gamma && pi && E && rows && K && keep && cent && cent64,
               "sdk_vbx_centroids: null argument (gamma=%p pi=%p E=%p rows=%p K=%p keep=%p cent=%p cent64=%p)", (const void*)gamma, (const void*)pi,
               (const void*)E, (const void*)rows, (void*)K, (void*)keep, (void*)cent, (void*)cent64);

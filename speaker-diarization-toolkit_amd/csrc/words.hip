@@ -148,12 +148,6 @@ __global__ __launch_bounds__(64) void words_attribute_kernel(const int32_t* __re
   }
 }
 
-__device__ __forceinline__ int wd_wave_sum(int x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
-}
-
 __global__ __launch_bounds__(WD_NT) void words_cooccur_kernel(const int32_t* __restrict__ rows, const int32_t* __restrict__ ref,
                                                               const int32_t* __restrict__ word_off, const int32_t* __restrict__ ref_off,
                                                               const int32_t* __restrict__ cent_off, const int64_t* __restrict__ co_off, int R,
@@ -180,7 +174,7 @@ __global__ __launch_bounds__(WD_NT) void words_cooccur_kernel(const int32_t* __r
       n_sc += 1;
       if (j >= 0 && j < K) atomicAdd(&tab[i * K + j], 1); else n_un += 1;
     }
-    n_sc = wd_wave_sum(n_sc); n_un = wd_wave_sum(n_un); n_w = wd_wave_sum(n_w);
+    n_sc = wave_sum(n_sc); n_un = wave_sum(n_un); n_w = wave_sum(n_w);
     if ((tid & 63) == 0) { atomicAdd(&tal[0], n_sc); atomicAdd(&tal[1], n_un); atomicAdd(&tal[2], n_w); }
     __syncthreads();
     int32_t* dst = co + co_off[r];

@@ -150,7 +150,7 @@ def test_a_label_outside_the_range_raises_and_the_next_call_is_fine(engine):
 
 
 # ------------------------------------------------------------------------------------------------ projection
-@pytest.mark.parametrize("case", [(1, 64, 64), (63, 192, 100), (2049, 256, 128)], ids=lambda c: "N%d-%dto%d" % c)
+@pytest.mark.parametrize("case", [(1, 64, 64), (63, 192, 100), (2049, 256, 128), (5, 512, 300)], ids=lambda c: "N%d-%dto%d" % c)
 def test_projection(engine, case):
     N, d_in, D0 = case
     E, _, _ = FR.labelled_rows(N + D0, N, d_in, 1)
