@@ -9,8 +9,13 @@
 //   ahc_merge_kernel : one workgroup per problem, exactly n - 1 merges of Muellner's generic algorithm (scipy's fast_linkage), nnd kept as
 //                      lower bounds checked lazily: argmin of the live rows' nnd (ties -> lowest row) = (x, y = nn[x]), accepted when
 //                      D[x][y] equals it, else row x is rescanned and the search repeats; emit Z; Lance-Williams update of row and column y;
-//                      rows that pointed at x point at y, a smaller new distance lowers a bound; rescan row y.  Slot x dies, the merged
-//                      cluster takes slot y and id n + t.  (Rescanning every row whose neighbour was x or y at once costs O(n) rescans per
+//                      a smaller new distance (or an equal one to a lower slot) lowers a bound; a row that pointed at x keeps its bound
+//                      and holds NO neighbour (nn = -1) until it is the least and is rescanned; rescan row y.  Slot x dies, the merged
+//                      cluster takes slot y and id n + t.  The pair of every step is therefore the live pair of least distance with ties
+//                      to the lowest row slot, then the lowest neighbour, whatever the history.  (scipy guesses y for a row that pointed
+//                      at x; a guess that happens to sit at the kept bound is accepted although a lower slot may sit there too, which
+//                      made the tree of tied inputs depend on the order of earlier merges.)
+//                      (Rescanning every row whose neighbour was x or y at once costs O(n) rescans per
 //                      merge when many rows point at one growing cluster: tight clusters of 10^4 rows took minutes that way.)  Only
 //                      __syncthreads inside the workgroup: nothing waits on another workgroup.
 //
@@ -341,7 +346,7 @@ __global__ void __launch_bounds__(MERGE_THREADS) ahc_merge_kernel(const AhcProb*
         return;
       }
       x = bi; y = nn[x]; dxy = bv;
-      if (D[x * n + y] == bv) break;            // uniform: every thread read the same values after the barrier
+      if (y >= 0 && D[x * n + y] == bv) break;  // uniform: every thread read the same values after the barrier (y < 0: neighbour unknown)
       rescan(x, -1);
       __syncthreads();
     }
@@ -352,8 +357,9 @@ __global__ void __launch_bounds__(MERGE_THREADS) ahc_merge_kernel(const AhcProb*
       }
     }
     const int nx = sz[x], ny = sz[y];
-    // B + C: emit, Lance-Williams update of row / column y, bound upkeep of the rows below y (scipy's order: a row that pointed at x now
-    // points at y with its bound kept; a smaller new distance lowers the bound).  sz / nnd / nn of slots x and y are read by every thread
+    // B + C: emit, Lance-Williams update of row / column y, bound upkeep of the rows below y (a smaller new distance, or an equal one when
+    // y is below the stored neighbour, lowers the bound; else a row that pointed at x keeps its bound without a neighbour: any live slot
+    // may sit at that bound, so only a rescan names the lowest).  sz / nnd / nn of slots x and y are read by every thread
     // above, so they change only after the next barrier (the loop below skips x and y itself)
     if (tid == 0) {
       const int ia = R.id[x], ib = R.id[y];
@@ -392,7 +398,7 @@ __global__ void __launch_bounds__(MERGE_THREADS) ahc_merge_kernel(const AhcProb*
         D[z * n + y] = v;
         if (z < y) {
           if (v < cur[u] || (v == cur[u] && (int)y < c[u])) { nnd[z] = v; nn[z] = (int32_t)y; }
-          else if (c[u] == (int)x) nn[z] = (int32_t)y;
+          else if (c[u] == (int)x) nn[z] = -1;
         }
       }
     }
