@@ -90,7 +90,7 @@ def reconstruct_host(cls: np.ndarray, starts: np.ndarray, labels: np.ndarray, K:
         cnt[g[m]] += _COUNT[cls[c][m]]
         nc[g[m]] += 1
         on = _MASK[cls[c][m]]                                             # [frames, 3]
-        for k in {int(v) for v in labels[c] if v >= 0}:
+        for k in {int(v) for v in labels[c] if 0 <= v < K}:              # a label at or above K names no cluster: it counts, but for no act
             act[g[m], k] += on[:, labels[c] == k].any(1)
     count = np.where(nc > 0, np.minimum((2 * cnt + nc) // np.maximum(2 * nc, 1), cap), 0)
     order = np.argsort(-act, axis=1, kind="stable")[:, :2] if K else np.zeros((G, 0), np.int64)      # stable: ties to the lower cluster
@@ -385,7 +385,9 @@ def fold_grouped_host(cent64, sizes, cl_off, eff, cent_off) -> np.ndarray:
         else:
             small = b + np.flatnonzero(sizes[b:e] < eff[r])
             if small.size:
-                target[small - b] = large[np.argmax(_dot_in_order(cent64[small], cent64[large]), axis=1)]   # first maximum: the lower cluster
+                cos = _dot_in_order(cent64[small], cent64[large])
+                cos = np.where(cos == cos, cos, -np.inf)                  # a NaN never wins; all NaN: the first large cluster
+                target[small - b] = large[np.argmax(cos, axis=1)]         # first maximum: the lower cluster
         _, first = np.unique(target, return_index=True)                   # kept clusters by the lowest cluster sent to them
         new = {int(t): int(cent_off[r]) + n for n, t in enumerate(target[np.sort(first)])}
         remap[b:e] = [new[int(t)] for t in target]
@@ -435,7 +437,8 @@ def renumber_host(first, cent_off, chunk_off, labels, cent):
         renum[b + order] = np.arange(e - b)
         out[b + renum[b:e]] = cent[b:e]
         lab = labels[int(chunk_off[r]):int(chunk_off[r + 1])]
-        lab[lab >= 0] = renum[b + lab[lab >= 0]]
+        ok = (lab >= 0) & (lab < e - b)                                   # a label at or above the recording's cluster count stays as it is
+        lab[ok] = renum[b + lab[ok]]
     return renum, labels, out
 
 

@@ -95,7 +95,7 @@ def reconstruct(cls, starts, labels, K: int, n_samples: int, max_speakers: Optio
                 continue
             nc += 1
             cnt += len(CLASSES[cls[c, i]])
-            for k in {int(labels[c, s]) for s in CLASSES[cls[c, i]] if labels[c, s] >= 0}:
+            for k in {int(labels[c, s]) for s in CLASSES[cls[c, i]] if 0 <= labels[c, s] < K}:    # a label at or above K names no cluster
                 act[g, k] += 1
         ncs[g] = nc
         if nc == 0:
