@@ -196,33 +196,59 @@ class ScoreMixin:
         nan [2], excluded [1]) int64 device tensors, views of one array (sdk_trial_hist; trials.py states the rule).  The score
         r[j] + A[i] . B[j] is cut into q = floor((s - lo) * scale), scale = 2^24 / (hi - lo) formed here in float64, and lands in bin
         (q >> shift) - base.  max_blocks: 0 = the default grid, else a cap on the workgroups (the counts do not depend on it)."""
-        who = "trial_hist"
-        N, K = (int(v) for v in _args.tensor(who, "A", A, "float64", (None, None)).shape)
-        if K < 16 or K > 512 or K % 16:
-            raise ValueError(f"trial_hist: K={K} not supported (a multiple of 16 in 16 .. 512)")
-        M = int(_args.tensor(who, "B", B, "float64", (None, K)).shape[0])
-        if not (1 <= N <= 1 << 20 and 1 <= M <= 1 << 20):
-            raise ValueError(f"trial_hist: N={N} test rows, M={M} model rows (1 .. 2^20 each)")
-        _args.tensor(who, "r", r, "float64", (M,))
-        for name, t, n in (("la", la, N), ("sa", sa, N), ("lb", lb, M), ("sb", sb, M)):
-            _args.tensor(who, name, t, "int32", (n,))
-        lo, hi, shift, base, max_blocks = float(lo), float(hi), int(shift), int(base), int(max_blocks)
-        if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
-            raise ValueError(f"trial_hist: score range ({lo}, {hi}): finite lo < hi expected")
-        with np.errstate(over="ignore"):
-            scale = float(np.float64(16777216.0) / (np.float64(hi) - np.float64(lo)))
-        if not (np.isfinite(scale) and scale > 0.0):
-            raise ValueError(f"trial_hist: scale = 2^24 / (hi - lo) = {scale} is not a finite number above 0 (range ({lo}, {hi}))")
-        if shift < 0 or shift > 24:
-            raise ValueError(f"trial_hist: shift={shift} (0 .. 24)")
-        if base < 0 or base > 1 << 24:
-            raise ValueError(f"trial_hist: base={base} (0 .. 2^24)")
-        if max_blocks < 0:
-            raise ValueError(f"trial_hist: max_blocks={max_blocks} (0: the default grid, else a cap on the workgroups)")
-        out = torch.empty((2 * 4096 + 7,), dtype=torch.int64, device=A.device)           # uint64 counters, all below 2^40
+        N, M, K = _trial_tensors("trial_hist", A, B, (("r", r, "M"),), la, sa, lb, sb)
+        lo, scale, shift, base, max_blocks = _trial_range("trial_hist", lo, hi, shift, base, max_blocks)
+        out = torch.empty((_TRIAL_OUT,), dtype=torch.int64, device=A.device)             # uint64 counters, all below 2^40
         check(self.lib.sdk_trial_hist(self.ctx, A.data_ptr(), N, B.data_ptr(), r.data_ptr(), M, K, la.data_ptr(), sa.data_ptr(), lb.data_ptr(),
                                       sb.data_ptr(), lo, scale, shift, base, max_blocks, out.data_ptr(), _stream()), "sdk_trial_hist")
-        return out[:8192].view(2, 4096), out[8192:8194], out[8194:8196], out[8196:8198], out[8198:8199]
+        return _trial_views(out)
+
+
+_TRIAL_OUT = 2 * 4096 + 7      # hist[2][4096], under[2], over[2], nan[2], excluded[1] (csrc/trial_tile.hpp)
+
+
+def _trial_tensors(who: str, A, B, payload, la, sa, lb, sb):
+    """The tensors every trial pass takes: A [N, K], B [M, K] float64, the pass's own float64 rows `payload` ((name, tensor, "N" or "M"), ..)
+    and the int32 labels and sessions -> (N, M, K)."""
+    N, K = (int(v) for v in _args.tensor(who, "A", A, "float64", (None, None)).shape)
+    if K < 16 or K > 512 or K % 16:
+        raise ValueError(f"{who}: K={K} not supported (a multiple of 16 in 16 .. 512)")
+    M = int(_args.tensor(who, "B", B, "float64", (None, K)).shape[0])
+    if not (1 <= N <= 1 << 20 and 1 <= M <= 1 << 20):
+        raise ValueError(f"{who}: N={N} test rows, M={M} model rows (1 .. 2^20 each)")
+    for name, t, side in payload:
+        _args.tensor(who, name, t, "float64", (N if side == "N" else M,))
+    for name, t, n in (("la", la, N), ("sa", sa, N), ("lb", lb, M), ("sb", sb, M)):
+        _args.tensor(who, name, t, "int32", (n,))
+    return N, M, K
+
+
+def _trial_max_blocks(who: str, max_blocks) -> int:
+    max_blocks = int(max_blocks)
+    if max_blocks < 0:
+        raise ValueError(f"{who}: max_blocks={max_blocks} (0: the default grid, else a cap on the workgroups)")
+    return max_blocks
+
+
+def _trial_range(who: str, lo, hi, shift, base, max_blocks):
+    """The score range of a histogram pass -> (lo, scale = 2^24 / (hi - lo) in float64, shift, base, max_blocks)."""
+    lo, hi, shift, base = float(lo), float(hi), int(shift), int(base)
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise ValueError(f"{who}: score range ({lo}, {hi}): finite lo < hi expected")
+    with np.errstate(over="ignore"):
+        scale = float(np.float64(16777216.0) / (np.float64(hi) - np.float64(lo)))
+    if not (np.isfinite(scale) and scale > 0.0):
+        raise ValueError(f"{who}: scale = 2^24 / (hi - lo) = {scale} is not a finite number above 0 (range ({lo}, {hi}))")
+    if shift < 0 or shift > 24:
+        raise ValueError(f"{who}: shift={shift} (0 .. 24)")
+    if base < 0 or base > 1 << 24:
+        raise ValueError(f"{who}: base={base} (0 .. 2^24)")
+    return lo, scale, shift, base, _trial_max_blocks(who, max_blocks)
+
+
+def _trial_views(out: torch.Tensor):
+    """(hist [2, 4096], under [2], over [2], nan [2], excluded [1]): views of a histogram pass's one array."""
+    return out[:8192].view(2, 4096), out[8192:8194], out[8194:8196], out[8196:8198], out[8198:8199]
 
 
 # ---- calibration of verification scores (trials.py; csrc/trials.hip)
@@ -234,21 +260,11 @@ def trial_calib(engine, A: torch.Tensor, B: torch.Tensor, r: torch.Tensor, la: t
     workgroups (the counts do not depend on it; the sums change by rounding).
 
     A function of the engine, not a method of it: Engine's public surface is pinned name for name (tests/test_ops_layout_cpu.py)."""
-    who = "trial_calib"
-    N, K = (int(v) for v in _args.tensor(who, "A", A, "float64", (None, None)).shape)
-    if K < 16 or K > 512 or K % 16:
-        raise ValueError(f"trial_calib: K={K} not supported (a multiple of 16 in 16 .. 512)")
-    M = int(_args.tensor(who, "B", B, "float64", (None, K)).shape[0])
-    if not (1 <= N <= 1 << 20 and 1 <= M <= 1 << 20):
-        raise ValueError(f"trial_calib: N={N} test rows, M={M} model rows (1 .. 2^20 each)")
-    _args.tensor(who, "r", r, "float64", (M,))
-    for name, t, n in (("la", la, N), ("sa", sa, N), ("lb", lb, M), ("sb", sb, M)):
-        _args.tensor(who, name, t, "int32", (n,))
-    a, c, max_blocks = float(a), float(c), int(max_blocks)
+    N, M, K = _trial_tensors("trial_calib", A, B, (("r", r, "M"),), la, sa, lb, sb)
+    a, c = float(a), float(c)
     if not (np.isfinite(a) and np.isfinite(c)):
         raise ValueError(f"trial_calib: a={a}, c={c} (the map z = a s + c: both finite)")
-    if max_blocks < 0:
-        raise ValueError(f"trial_calib: max_blocks={max_blocks} (0: the default grid, else a cap on the workgroups)")
+    max_blocks = _trial_max_blocks("trial_calib", max_blocks)
     nbytes = engine._workspace_bytes("sdk_trial_calib_workspace_bytes", N, M, max_blocks)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=A.device)
     sums = torch.empty((2, 7), dtype=torch.float64, device=A.device)
@@ -270,35 +286,14 @@ def trial_hist_snorm(engine, A: torch.Tensor, B: torch.Tensor, mean_a: torch.Ten
     (sdk_trial_hist_snorm; trials_snorm.py states the rule).  Nothing waits.
 
     A function of the engine, not a method of it: Engine's public surface is pinned name for name (tests/test_ops_layout_cpu.py)."""
-    who = "trial_hist_snorm"
-    lo, hi, shift, base, max_blocks = float(lo), float(hi), int(shift), int(base), int(max_blocks)
-    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
-        raise ValueError(f"trial_hist_snorm: score range ({lo}, {hi}): finite lo < hi expected")
-    with np.errstate(over="ignore"):
-        scale = float(np.float64(16777216.0) / (np.float64(hi) - np.float64(lo)))
-    if not (np.isfinite(scale) and scale > 0.0):
-        raise ValueError(f"trial_hist_snorm: scale = 2^24 / (hi - lo) = {scale} is not a finite number above 0 (range ({lo}, {hi}))")
-    if shift < 0 or shift > 24:
-        raise ValueError(f"trial_hist_snorm: shift={shift} (0 .. 24)")
-    if base < 0 or base > 1 << 24:
-        raise ValueError(f"trial_hist_snorm: base={base} (0 .. 2^24)")
-    if max_blocks < 0:
-        raise ValueError(f"trial_hist_snorm: max_blocks={max_blocks} (0: the default grid, else a cap on the workgroups)")
-    N, K = (int(v) for v in _args.tensor(who, "A", A, "float64", (None, None)).shape)
-    if K < 16 or K > 512 or K % 16:
-        raise ValueError(f"trial_hist_snorm: K={K} not supported (a multiple of 16 in 16 .. 512)")
-    M = int(_args.tensor(who, "B", B, "float64", (None, K)).shape[0])
-    if not (1 <= N <= 1 << 20 and 1 <= M <= 1 << 20):
-        raise ValueError(f"trial_hist_snorm: N={N} test rows, M={M} model rows (1 .. 2^20 each)")
-    for name, t, n in (("mean_a", mean_a, N), ("inv_a", inv_a, N), ("mean_b", mean_b, M), ("inv_b", inv_b, M)):
-        _args.tensor(who, name, t, "float64", (n,))
-    for name, t, n in (("la", la, N), ("sa", sa, N), ("lb", lb, M), ("sb", sb, M)):
-        _args.tensor(who, name, t, "int32", (n,))
-    out = torch.empty((2 * 4096 + 7,), dtype=torch.int64, device=A.device)           # uint64 counters, all below 2^40
+    lo, scale, shift, base, max_blocks = _trial_range("trial_hist_snorm", lo, hi, shift, base, max_blocks)
+    N, M, K = _trial_tensors("trial_hist_snorm", A, B, (("mean_a", mean_a, "N"), ("inv_a", inv_a, "N"), ("mean_b", mean_b, "M"), ("inv_b", inv_b, "M")),
+                             la, sa, lb, sb)
+    out = torch.empty((_TRIAL_OUT,), dtype=torch.int64, device=A.device)                 # uint64 counters, all below 2^40
     check(engine.lib.sdk_trial_hist_snorm(engine.ctx, A.data_ptr(), N, B.data_ptr(), M, K, mean_a.data_ptr(), inv_a.data_ptr(), mean_b.data_ptr(),
                                           inv_b.data_ptr(), la.data_ptr(), sa.data_ptr(), lb.data_ptr(), sb.data_ptr(), lo, scale, shift, base,
                                           max_blocks, out.data_ptr(), _stream()), "sdk_trial_hist_snorm")
-    return out[:8192].view(2, 4096), out[8192:8194], out[8194:8196], out[8196:8198], out[8198:8199]
+    return _trial_views(out)
 
 
 # ---- speaker-attributed transcripts (words.py; csrc/words.hip)

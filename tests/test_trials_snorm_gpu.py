@@ -89,6 +89,42 @@ def test_histograms_are_bit_exact_on_exact_products(engine, N, M, K, max_blocks)
     assert same(gotz, wantz)
 
 
+# ---- the three trial kernels share one tile walk: with neutral statistics they must count the same trials ------------------------------------
+@pytest.mark.parametrize("max_blocks", [0, 1])
+@pytest.mark.parametrize("N,M,K", [(63, 65, 16), (130, 200, 256)])
+def test_neutral_statistics_equal_the_plain_histogram_and_the_calibration_counts(engine, N, M, K, max_blocks):
+    """mean = 0 and inv = 1 on both sides: z = (s + s) * 0.5 = s exactly, so trial_hist_snorm returns Engine.trial_hist's 8199 counters at
+    r = 0 on the same rows, labels and sessions, at the coarse pass and at a zoom pass; trial_calib's n + nonfinite and excluded are the
+    class totals and excluded of that pass.  Integer equality throughout."""
+    A, B, _, _, _, _, la, sa, lb, sb = grid_inputs(N, M, K, 300 + N + K)
+    assert (la < 0).any() and (lb < 0).any() and ((sa[:, None] >= 0) & (sa[:, None] == sb[None, :])).any()
+    la32, sa32, lb32, sb32 = (dev(v.astype(np.int32)) for v in (la, sa, lb, sb))
+    dA, dB, zeros_m = dev(A), dev(B), dev(np.zeros(M))
+    lo, hi = -512.0, 512.0
+
+    def plain(shift, base):
+        out = engine.trial_hist(dA, dB, zeros_m, la32, sa32, lb32, sb32, lo, hi, shift=shift, base=base, max_blocks=max_blocks)
+        torch.cuda.synchronize()
+        return T.counts_to_host(out)
+
+    def snorm(shift, base):
+        return gpu_hist(engine, A, B, np.zeros(N), np.ones(N), np.zeros(M), np.ones(M), la, sa, lb, sb, lo, hi, shift, base, max_blocks)
+
+    coarse = plain(12, 0)
+    assert coarse.excluded > 0 and int(coarse.hist[0].sum()) > 0 and int(coarse.hist[1].sum()) > 0
+    assert coarse.total() + int(coarse.nan.sum()) + coarse.excluded == N * M
+    assert same(snorm(12, 0), coarse)
+    b = int(np.argmax(coarse.hist.sum(axis=0)))
+    zoom = plain(0, 4096 * b)
+    assert int(zoom.hist.sum()) == int(coarse.hist[:, b].sum()) > 0
+    assert same(snorm(0, 4096 * b), zoom)
+    n, _, nonfinite, excluded = OPS.trial_calib(engine, dA, dB, zeros_m, la32, sa32, lb32, sb32, 1.0, 0.0, max_blocks=max_blocks)
+    torch.cuda.synchronize()
+    per_class = coarse.hist.sum(axis=1) + coarse.under + coarse.over + coarse.nan
+    assert np.array_equal(n.cpu().numpy() + nonfinite.cpu().numpy(), per_class)
+    assert int(excluded.item()) == coarse.excluded
+
+
 # ---- special values --------------------------------------------------------------------------------------------------------------------------
 def test_special_statistics_exclusions_and_empty_ranges(engine):
     K = 16
