@@ -1114,6 +1114,39 @@ int sdk_stream_flush(sdk_ctx* ctx, const int64_t* n_samples, const uint8_t* acti
 int sdk_stream_centroids(sdk_ctx* ctx, const void* state, int64_t state_bytes, int R, int capacity, int d, int first, int count, float* cent,
                          int32_t* counts, int32_t* K, double* sums, void* stream);
 
+/* ---- the nearest-neighbour graph of eigengap spectral clustering (cluster.nmesc_cluster states the rule; csrc/nmesc.hip).  One problem per
+ *      call: n rows, 2 <= n <= 65536, P = min(64, n - 1); every pointer is DEVICE memory; every call is enqueued on `stream` and reads nothing back.
+ *   sdk_knn_rows     E fp32 [n][d] unit rows, d a multiple of 64, at most 512 -> idx int32 [n][P], cosv float64 [n][P]: row i's P rows j != i of
+ *                    largest c(i, j), ties to the lower j, in that order.  c(i, j) is the float64 sum over the columns in ascending order of
+ *                    the products E[i][t] E[j][t] (exact in float64), rounded once per addition; it is symmetric bit for bit.  A NaN
+ *                    cosine ranks, and is stored, as -inf.  status int32 [2]: the number of rows that hold a non-finite value and the
+ *                    lowest of them (INT_MAX: none); the lists are written either way, and those of a problem without such a row are
+ *                    not affected by an earlier call that had one.
+ *   sdk_knn_reverse  idx -> the incoming edges as CSR: rev_off int32 [n + 1], and for row j the entries rev_off[j] .. rev_off[j + 1] - 1 of
+ *                    rev_src / rev_rank int32 [n P]: the rows i that list j, in ascending order of i, and the position of j in i's list.
+ *                    Integer counting per block of 256 source rows, a scan, a fill: no order depends on scheduling.  status int32 [2]: the
+ *                    entries of idx outside [0, n) (they are skipped) and the lowest row that holds one (INT_MAX: none).
+ *                    workspace: sdk_knn_reverse_workspace_bytes(n, P) (4 n ceil(n / 256) bytes of counts + O(n)), 256-byte aligned; 0 for
+ *                    arguments the call refuses.
+ *   sdk_knn_degree   for 1 <= p <= P: deg int32 [n], deg[i] = p + the entries of row i's reverse list with rank < p (the row sum of
+ *                    A_p = B_p + B_p^T, B_p(i, j) = 1 iff j is among the first p entries of list i), and dinv float64 [n] =
+ *                    1 / sqrt((double)deg[i]): a correctly rounded square root, then a correctly rounded division.
+ *   sdk_knn_matvec   Y = T_p X, T_p = (I + D^-1/2 A_p D^-1/2) / 2, for X fp32 [n][kv], 1 <= kv <= 32, Y fp32 [n][kv], Y != X.  For every
+ *                    row i and column c, in float64, each operation rounded once and none fused:
+ *                      s = 0;  for r = 0 .. p - 1, j = idx[i][r]:                                  s = s + dinv[j] * X[j][c]
+ *                              for e = rev_off[i] .. rev_off[i + 1] - 1 with rev_rank[e] < p, j = rev_src[e]:  s = s + dinv[j] * X[j][c]
+ *                      Y[i][c] = (float)(0.5 * (X[i][c] + dinv[i] * s))
+ *                    No atomics: one thread owns an element of Y.
+ *   Refusals (a null pointer, n, d, P other than min(64, n - 1), p outside 1 .. P, kv, a short or misaligned workspace) return non-zero,
+ *   name the value in sdk_last_error() and launch nothing. */
+int sdk_knn_rows(sdk_ctx* ctx, const float* E, int n, int d, int P, int32_t* idx, double* cosv, int32_t* status, void* stream);
+size_t sdk_knn_reverse_workspace_bytes(int n, int P);
+int sdk_knn_reverse(sdk_ctx* ctx, const int32_t* idx, int n, int P, int32_t* rev_off, int32_t* rev_src, int32_t* rev_rank, int32_t* status,
+                    void* workspace, size_t ws_bytes, void* stream);
+int sdk_knn_degree(sdk_ctx* ctx, const int32_t* rev_off, const int32_t* rev_rank, int n, int P, int p, int32_t* deg, double* dinv, void* stream);
+int sdk_knn_matvec(sdk_ctx* ctx, const int32_t* idx, const int32_t* rev_off, const int32_t* rev_src, const int32_t* rev_rank, const double* dinv,
+                   int n, int P, int p, const float* X, int kv, float* Y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

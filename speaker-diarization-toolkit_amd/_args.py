@@ -11,6 +11,7 @@ A leaf: it imports neither torch nor _lib with the module (diarize_ops.py import
 """
 from __future__ import annotations
 
+import numbers
 import sys
 
 THIN_MAX = 32      # KV of csrc/spectral.hip: the widest [n, k] block (and the most centres) the thin helpers take
@@ -94,3 +95,27 @@ def thin(who: str, name: str, t):
         raise ValueError(f"{who}: k = {k} (the width of {name}) must be in 1..{THIN_MAX}")
     _on_device(who, name, t, "float32", (None, None), True)
     return n, k
+
+
+KNN_P_MAX = 64     # KNN_P_MAX of csrc/nmesc.hip: the longest neighbour list, one lane per entry (cluster.NMESC_P_MAX)
+
+
+def knn_shape(who: str, n: int) -> int:
+    """The rows of a neighbour graph (knn_rows .. knn_matvec) -> P = min(KNN_P_MAX, n - 1)."""
+    if n < 2 or n > 65536:
+        raise ValueError(f"{who}: n={n} rows (2 .. 65536)")
+    return min(KNN_P_MAX, n - 1)
+
+
+def knn_lists(who: str, idx):
+    """The neighbour lists idx int32 [n, P] with P = min(KNN_P_MAX, n - 1) -> (n, P)."""
+    n, P = (int(v) for v in tensor(who, "idx", idx, "int32", (None, None)).shape)
+    if knn_shape(who, n) != P:
+        raise ValueError(f"{who}: idx must be [n, min({KNN_P_MAX}, n - 1)], got {list(idx.shape)}")
+    return n, P
+
+
+def knn_p(who: str, p, P: int) -> None:
+    """The neighbours kept of a list of P: an integer (no bool), 1 <= p <= P."""
+    if isinstance(p, bool) or not isinstance(p, numbers.Integral) or not 1 <= p <= P:      # numpy's integers are Integral, its bool_ is not
+        raise ValueError(f"{who}: p={p!r} (an int, 1 .. P={P})")

@@ -235,6 +235,11 @@ SIGNATURES = {
     "sdk_stream_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f64, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sdk_stream_flush": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "sdk_stream_centroids": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sdk_knn_rows": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "sdk_knn_reverse_workspace_bytes": (_sz, [_i, _i]),
+    "sdk_knn_reverse": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "sdk_knn_degree": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "sdk_knn_matvec": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     "sdk_affinity_topk": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sdk_device_malloc": (_i, [_vp, _sz, C.POINTER(C.c_void_p)]),
     "sdk_device_free": (_i, [_vp, _vp]),

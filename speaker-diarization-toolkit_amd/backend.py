@@ -435,12 +435,14 @@ class Backend(EmbeddingBackend):
         speakers: the number of speakers, None, an int k (exactly k) or a pair (lo, hi), either side None (cluster.parse_speakers and the
         bounds stated above it; pyannote's max_speakers is speakers=(None, hi)).  When the count found lies outside, "ahc" takes the level
         search of cluster.agglomerative_cluster rule 7 and "vbx" the k-means of cluster.kmeans_cluster on the window rows, whose labels come
-        back; fewer than two windows: nothing is forced."""
+        back; fewer than two windows: nothing is forced.
+        clustering="nmesc": the eigengap spectral clustering of cluster.nmesc_cluster on the window rows, with no threshold: `threshold`,
+        min_cluster_size, loop_prob and plda are not used, and `speakers` bounds the eigengap search itself."""
         if self.lite:
             raise ValueError("cluster_ranges needs the torch engine: not available with SDK_NO_TORCH=1")
-        if clustering not in ("ahc", "vbx"):
-            raise ValueError(f"cluster_ranges: clustering={clustering!r} (\"ahc\" or \"vbx\")")
-        from .cluster import agglomerative_cluster, parse_speakers, vbx_cluster
+        if clustering not in ("ahc", "vbx", "nmesc"):
+            raise ValueError(f"cluster_ranges: clustering={clustering!r} (\"ahc\", \"vbx\" or \"nmesc\")")
+        from .cluster import agglomerative_cluster, nmesc_cluster, parse_speakers, vbx_cluster
         speakers = parse_speakers(speakers, "cluster_ranges")
         E, _, _, wins, _ = self.embed_ranges(samples, ranges)
         range_labels = np.full(len(ranges), -1, dtype=np.int32)
@@ -450,6 +452,8 @@ class Backend(EmbeddingBackend):
             labels = agglomerative_cluster(self.engine(), E, threshold, min_cluster_size, speakers=speakers).labels
         elif len(wins) == 1:
             labels = np.zeros(1, np.int32)
+        elif clustering == "nmesc":
+            labels = nmesc_cluster(self.engine(), E.contiguous(), speakers=speakers).labels
         else:
             labels = vbx_cluster(self.engine(), E.contiguous(), self._ranges_plda(plda, int(E.shape[1])), threshold, loop_prob=loop_prob,
                                  speakers=speakers).labels
@@ -544,7 +548,7 @@ class Backend(EmbeddingBackend):
         decoded to the audio profile) -> diarize.DiarizationResult (turns [(start_s, end_s, speaker)], n_speakers, unit centroids in the
         diarizer's embedding space - that of score_windows and the enrolled profiles under SDK_MODEL=resnet34, or SDK_MODEL=ecapa with
         SDK_DIARIZE_MODEL=ecapa - labels, count, speakers); diarize.to_rttm(result.turns, uri) writes RTTM.  Keywords: step_s,
-        threshold, min_cluster_size, max_speakers, logp, constrained, clustering, vbx, speakers (diarize.Diarizer.run).  The default threshold is PyAnnote 3.1's, tuned
+        threshold, min_cluster_size, max_speakers, logp, constrained, clustering, vbx, speakers, nmesc (diarize.Diarizer.run; clustering="nmesc" is the eigengap spectral clustering, which needs no threshold).  The default threshold is PyAnnote 3.1's, tuned
         for its trained ResNet34 ($SDK_RESNET_WEIGHTS); with the synthetic weights pass a threshold of your own.  constrained=True
         (PyAnnote's constrained_argmax; default False): the local speakers of a chunk get pairwise different clusters, the one-to-one
         matching of largest total cosine, computed on the device; the result then carries scores [C, 3].  clustering="vbx" (default "ahc"):

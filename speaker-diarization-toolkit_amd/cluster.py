@@ -28,7 +28,9 @@ import numpy as np
 import torch
 
 from . import dist as sdist
+from ._args import THIN_MAX
 from .diarize_ops import _check_rows, diarize_centroids
+from .ops_cluster import knn_degree, knn_matvec, knn_reverse, knn_rows
 
 
 @dataclass
@@ -42,9 +44,11 @@ class SpectralResult:
 
 
 class _Comm:
-    def __init__(self, group=None):
+    def __init__(self, group=None, single: bool = False):
+        """single: a whole, unsharded problem on this process alone (nmesc_cluster): off whatever torch.distributed holds, so that nothing
+        is all-reduced across ranks that each hold all the rows."""
         import torch.distributed as d
-        self.on = d.is_available() and d.is_initialized() and d.get_world_size(group) > 1
+        self.on = not single and d.is_available() and d.is_initialized() and d.get_world_size(group) > 1
         self.group = group
         self.rank = d.get_rank(group) if self.on else 0
         self.world = d.get_world_size(group) if self.on else 1
@@ -623,3 +627,297 @@ def kmeans_cluster(provider, E, k: int, rows=None, max_iters: int = KMEANS_MAX_I
     K = int(labels.max()) + 1
     cent, cent64 = diarize_centroids(provider, E, rows_d, _torch.from_numpy(labels).to(E.device), K, check_rows=False)
     return KmeansResult(labels, K, n_it, cent, cent64, np.bincount(labels, minlength=K).astype(np.int64))
+
+
+# ------------------------------------------------------------------ NME-SC: spectral clustering on a pruned nearest-neighbour graph, no threshold
+# nmesc       (clustering="nmesc"; the eigengap spectral clustering with normalised-maximum-eigengap pruning that NeMo's diarizer defaults to,
+#             written from the published description; no NeMo code is on hand: PARITY IS UNPINNED, the tests pin THIS rule).  The input is
+#             the n training rows X of one recording: unit rows, fp32 [n, d], d a width the row kernels serve, 2 <= n <= 65 536.
+#   cosine      c(i, j) = the float64 sum, in ascending column order, of the exact products x_i[t] x_j[t] (diarize_host._dot_in_order's
+#               arithmetic): symmetric bit for bit.  A row with a non-finite value is a ValueError that names it.
+#   lists       P = min(NMESC_P_MAX = 64, n - 1).  Row i's list: the P rows j != i of largest c(i, j), ties to the lower j, in that order:
+#               idx int32 [n, P], cos float64 [n, P] (sdk_knn_rows).
+#   graph       at p <= P: B_p(i, j) = 1 iff j is among the first p entries of list i; A_p = B_p + B_p^T (entries 0, 1, 2);
+#               deg_p(i) = p + in_p(i), integers; T_p = (I + D^-1/2 A_p D^-1/2) / 2.  The lazy form is the point: a nearest-neighbour
+#               graph has eigenvalues near -1 (p = 1 gives matched pairs), to which plain subspace iteration on D^-1/2 A D^-1/2 would
+#               converge; T_p's spectrum lies in [0, 1] in the same order.
+#   candidates  the members of NMESC_NEIGHBOURS = (2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64) that are <= P; none: the one candidate (P,).
+#               `neighbours` replaces NMESC_NEIGHBOURS.
+#   spectrum    per candidate p the m = min(n, max_count + 1) largest eigenvalues tau_1 >= .. >= tau_m of T_p, block width
+#               b = min(n, THIN_MAX, m + 8).  n <= NMESC_DENSE_ROWS = 64: on the host, the dense T_p built from the downloaded lists,
+#               numpy.linalg.eigh in float64.  Above: on the device, from the seeded gaussian [n, b] (numpy default_rng(seed)), n_iter
+#               steps of V <- orth(T_p V) (CholeskyQR2, _orth; sdk_knn_matvec), the Ritz step H = V^T T_p V with sdk_sym_eigh, the first m
+#               values.  All candidates' eigenvalues come down in ONE download.
+#   selection   nmesc_select, host float64 on that table: g_i(p) = tau_i - tau_{i+1} for i in [lo, hi], the bounds of `speakers`
+#               (parse_speakers) clipped to 1 .. m - 1, default 1 .. m - 1; k(p) = the lowest i of largest g_i(p), g(p) that gap;
+#               r(p) = p / g(p), +inf when g(p) <= NMESC_FLAT_GAP = 1e-6; p* = the candidate of least r, ties to the lower p; k* = k(p*).
+#               Every r infinite: k* = lo, p* = the largest candidate.  The bounds are part of the rule: nothing is `forced`.
+#   labels      k* = 1: every label 0.  Otherwise the first k* Ritz vectors of T_p* (same seed and block; the host's eigenvectors for
+#               n <= NMESC_DENSE_ROWS) go through rows_unit and the maximin + Lloyd k-means of spectral_cluster (_kmeans) with
+#               NMESC_KMEANS_PASSES = 20 passes, then canonical_labels.
+NMESC_P_MAX = 64
+NMESC_NEIGHBOURS = (2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64)
+NMESC_DENSE_ROWS = 64
+NMESC_MAX_COUNT = 15
+NMESC_N_ITER = 30
+NMESC_KMEANS_PASSES = 20
+NMESC_FLAT_GAP = 1e-6
+NMESC_MAX_ROWS = 65536
+
+
+@dataclass
+class NmescResult:
+    labels: np.ndarray            # [n] int32 canonical
+    n_speakers: int               # k*
+    p: int                        # p*, the neighbours kept
+    ps: tuple                     # the candidates
+    eigenvalues: np.ndarray       # [n_p, m] float64, descending per candidate
+    ratios: np.ndarray            # [n_p] float64 r(p), +inf for a flat spectrum
+    n_iter: int                   # steps of the subspace iteration (0: the host's dense eigensolve)
+    retried: bool = False         # the sweep was repeated with shifted CholeskyQR (spectral_cluster's rule)
+    host_reads: int = 0           # the waits for the device this call made
+
+
+def nmesc_candidates(n: int, neighbours=None) -> tuple:
+    """The candidates of the rule for n >= 2 rows."""
+    P = min(NMESC_P_MAX, int(n) - 1)
+    src = NMESC_NEIGHBOURS if neighbours is None else tuple(neighbours)
+    if not src or any(isinstance(p, (bool, np.bool_)) or not isinstance(p, (int, np.integer)) or p < 1 for p in src):
+        raise ValueError(f"nmesc: neighbours={neighbours!r} (a sequence of ints >= 1)")
+    ps = tuple(sorted({int(p) for p in src if p <= P}))
+    return ps if ps else (P,)
+
+
+def _nmesc_shape(n: int, max_count):
+    """-> (m, b) of the rule."""
+    if isinstance(max_count, (bool, np.bool_)) or not isinstance(max_count, (int, np.integer)) or not 1 <= max_count <= THIN_MAX - 1:
+        raise ValueError(f"nmesc: max_count={max_count!r} (an int, 1 .. {THIN_MAX - 1})")
+    m = min(int(n), int(max_count) + 1)
+    return m, min(int(n), THIN_MAX, m + 8)
+
+
+def nmesc_select(ps, taus, bounds, n: int):
+    """The selection of the rule, a pure function: ps the candidates (ascending), taus [n_p, m] float64 their eigenvalues in descending order,
+    bounds None or parse_speakers' (lo, hi), n the rows -> (p*, k*, ratios [n_p] float64, ks [n_p] int)."""
+    taus = np.asarray(taus, dtype=np.float64)
+    ps = [int(p) for p in ps]
+    if taus.ndim != 2 or taus.shape[0] != len(ps) or not ps or taus.shape[1] < 2 or taus.shape[1] > int(n):
+        raise ValueError(f"nmesc_select: taus must be [{len(ps)}, m] with 2 <= m <= n = {n}, got {list(taus.shape)}")
+    if not np.isfinite(taus).all():
+        raise ValueError("nmesc_select: a non-finite eigenvalue")
+    m = taus.shape[1]
+    lo, hi = (1, None) if bounds is None else bounds
+    hi = m - 1 if hi is None else min(int(hi), m - 1)
+    lo = min(max(int(lo), 1), m - 1)
+    hi = max(hi, lo)
+    gaps = taus[:, lo - 1:hi] - taus[:, lo:hi + 1]                   # column c is g_{lo + c}
+    at = np.argmax(gaps, axis=1)                                    # first maximum: the lowest i
+    ks = (lo + at).astype(np.int64)
+    g = gaps[np.arange(len(ps)), at]
+    ratios = np.where(g > NMESC_FLAT_GAP, np.asarray(ps, np.float64) / np.where(g > NMESC_FLAT_GAP, g, 1.0), np.inf)
+    if not np.isfinite(ratios).any():
+        return ps[-1], lo, ratios, ks
+    best = int(np.argmin(ratios))                                   # first minimum: ps ascend, so the lower p
+    return ps[best], int(ks[best]), ratios, ks
+
+
+# ---- the graph in numpy (what the kernels of csrc/nmesc.hip compute, bit for bit)
+def knn_rows_host(E: np.ndarray):
+    """E [n, d] fp32 unit rows -> (idx int32 [n, P], cos float64 [n, P]): the lists of the rule (sdk_knn_rows)."""
+    X = np.asarray(E, dtype=np.float32).astype(np.float64)
+    n = X.shape[0]
+    P = min(NMESC_P_MAX, n - 1)
+    C = np.zeros((n, n))
+    for t in range(X.shape[1]):
+        C += X[:, t, None] * X[None, :, t]
+    C = np.where(C == C, C, -np.inf)                                # a NaN ranks as -inf
+    order = np.argsort(-C, axis=1, kind="stable")                   # ties to the lower j
+    order = order[order != np.arange(n)[:, None]].reshape(n, n - 1)[:, :P]
+    return order.astype(np.int32), np.take_along_axis(C, order, axis=1)
+
+
+def knn_reverse_host(idx: np.ndarray):
+    """idx [n, P] -> (rev_off int32 [n + 1], rev_src int32 [n P], rev_rank int32 [n P]): sdk_knn_reverse."""
+    n, P = idx.shape
+    tgt = idx.reshape(-1).astype(np.int64)
+    src, rank = np.repeat(np.arange(n), P), np.tile(np.arange(P), n)
+    order = np.lexsort((src, tgt))
+    off = np.concatenate([[0], np.cumsum(np.bincount(tgt, minlength=n))])
+    return off.astype(np.int32), src[order].astype(np.int32), rank[order].astype(np.int32)
+
+
+def knn_degree_host(rev_off: np.ndarray, rev_rank: np.ndarray, p: int):
+    """-> (deg int32 [n], dinv float64 [n]): sdk_knn_degree."""
+    n = rev_off.size - 1
+    row = np.repeat(np.arange(n), np.diff(rev_off))
+    deg = int(p) + np.bincount(row[rev_rank < p], minlength=n)
+    return deg.astype(np.int32), 1.0 / np.sqrt(deg.astype(np.float64))
+
+
+def knn_matvec_host(idx: np.ndarray, rev, dinv: np.ndarray, p: int, X: np.ndarray) -> np.ndarray:
+    """Y = T_p X in the arithmetic sdk_knn_matvec states (include/sdk_hip.h): float64, row i's sum over its out-neighbours by rank, then over its
+    reverse entries in stored order, every operation rounded once, the result rounded once to fp32."""
+    rev_off, rev_src, rev_rank = rev
+    n = idx.shape[0]
+    X64 = np.asarray(X, dtype=np.float32).astype(np.float64)
+    Z = dinv[:, None] * X64
+    s = np.zeros_like(X64)
+    for r in range(int(p)):
+        s = s + Z[idx[:, r]]
+    keep = rev_rank < p
+    row = np.repeat(np.arange(n), np.diff(rev_off))[keep]
+    src = rev_src[keep]
+    first = np.concatenate([[0], np.cumsum(np.bincount(row, minlength=n))])[:-1]
+    pos = np.arange(row.size) - first[row]                          # the entry's place among its row's kept entries
+    order = np.argsort(pos, kind="stable")
+    cut = np.concatenate([[0], np.cumsum(np.bincount(pos, minlength=1))])
+    for t in range(cut.size - 1):                                   # step t: every row's t-th entry (one entry per row at most)
+        sl = order[cut[t]:cut[t + 1]]
+        s[row[sl]] = s[row[sl]] + Z[src[sl]]
+    return (0.5 * (X64 + dinv[:, None] * s)).astype(np.float32)
+
+
+def knn_dense_host(idx: np.ndarray, p: int) -> np.ndarray:
+    """The dense T_p [n, n] float64 of the lists' first p entries."""
+    n = idx.shape[0]
+    B = np.zeros((n, n))
+    B[np.arange(n)[:, None], idx[:, :int(p)]] = 1.0
+    A = B + B.T
+    dinv = 1.0 / np.sqrt(A.sum(1))
+    return 0.5 * (np.eye(n) + dinv[:, None] * A * dinv[None, :])
+
+
+def _dense_top(idx: np.ndarray, p: int, m: int):
+    """The m largest eigenvalues of T_p, descending, and their eigenvectors [n, m] (numpy.linalg.eigh, float64)."""
+    lam, Q = np.linalg.eigh(knn_dense_host(idx, p))
+    return lam[::-1][:m].copy(), Q[:, ::-1][:, :m].copy()
+
+
+def _kmeans_host(R: np.ndarray, k: int, passes: int) -> np.ndarray:
+    """_kmeans in numpy float64: maximin seeds from row 0 (ties to the lowest row), `passes` Lloyd passes (a centre without rows keeps its
+    value), the labels of one more assignment (ties to the lowest centre)."""
+    R = np.asarray(R, dtype=np.float64)
+    centres = [R[0]]
+    d2 = ((R - R[0]) ** 2).sum(1)
+    for _ in range(1, k):
+        j = int(np.argmax(d2))
+        centres.append(R[j])
+        d2 = np.minimum(d2, ((R - R[j]) ** 2).sum(1))
+    C = np.stack(centres)
+
+    def assign():
+        return np.argmin(((R[:, None, :] - C[None, :, :]) ** 2).sum(2), axis=1)
+    for _ in range(passes):
+        lab = assign()
+        for c in range(k):
+            if (lab == c).any():
+                C[c] = R[lab == c].mean(0)
+    return assign()
+
+
+def _pick_rows(who: str, R: int, rows):
+    rows_h = np.arange(R, dtype=np.int64) if rows is None else np.asarray(rows, dtype=np.int64).reshape(-1)
+    if rows_h.size and (rows_h.min() < 0 or rows_h.max() >= R or (np.diff(rows_h) <= 0).any()):
+        raise ValueError(f"{who}: rows must ascend strictly inside [0, {R}), got {int(rows_h.min())} .. {int(rows_h.max())}")
+    if rows_h.size > NMESC_MAX_ROWS:
+        raise ValueError(f"{who}: {rows_h.size} rows (at most {NMESC_MAX_ROWS})")
+    return rows_h
+
+
+def nmesc_host(E, rows=None, speakers=None, neighbours=None, max_count: int = NMESC_MAX_COUNT) -> NmescResult:
+    """The whole rule in numpy float64, with the dense eigensolve at every n (so its eigenvalues are exact where nmesc_cluster's device path
+    iterates): E [R, d] fp32 unit rows on the host, the other arguments nmesc_cluster's."""
+    bounds = parse_speakers(speakers, "nmesc_host")
+    E = np.asarray(E, dtype=np.float32)
+    rows_h = _pick_rows("nmesc_host", E.shape[0], rows)
+    X = E[rows_h]
+    n = X.shape[0]
+    m, _ = _nmesc_shape(max(n, 1), max_count)
+    if n < 2:
+        return NmescResult(np.zeros(n, np.int32), n, 0, (), np.zeros((0, m)), np.zeros(0), 0)
+    bad = np.flatnonzero(~np.isfinite(X).all(1))
+    if bad.size:
+        raise ValueError(f"nmesc_host: row {int(bad[0])} has a non-finite value ({bad.size} such rows in all)")
+    ps = nmesc_candidates(n, neighbours)
+    idx, _ = knn_rows_host(X)
+    tops = [_dense_top(idx, p, m) for p in ps]
+    taus = np.stack([t[0] for t in tops])
+    p_star, k_star, ratios, _ = nmesc_select(ps, taus, bounds, n)
+    labels = np.zeros(n, np.int32)
+    if k_star > 1:
+        U = tops[ps.index(p_star)][1][:, :k_star]
+        Rn = U / np.maximum(np.sqrt((U * U).sum(1, keepdims=True)), 1e-12)
+        labels = canonical_labels(_kmeans_host(Rn, k_star, NMESC_KMEANS_PASSES)).astype(np.int32)
+    return NmescResult(labels, k_star, p_star, ps, taus, ratios, 0)
+
+
+def nmesc_cluster(provider, E, rows=None, speakers=None, neighbours=None, max_count: int = NMESC_MAX_COUNT, n_iter: int = NMESC_N_ITER,
+                  seed: int = 0) -> NmescResult:
+    """Speaker clusters with neither a threshold nor a count: the rule stated above (E [R, d] fp32 unit rows on the provider's device; rows: the
+    ascending row numbers that take part, host integers, None = all).  speakers: parse_speakers' bounds, part of the selection.  neighbours:
+    the candidates in place of NMESC_NEIGHBOURS.  max_count: the most speakers looked for (1 .. THIN_MAX - 1).  The lists, their reverse, the
+    degrees and every T_p V run in libsdk_hip.so (ops_cluster.knn_rows .. knn_matvec, csrc/nmesc.hip) beside the thin helpers of spectral_cluster.
+    The host waits for the device result.host_reads times: the status of the lists, the eigenvalue table with the CholeskyQR flag (n <=
+    NMESC_DENSE_ROWS: the lists instead), and the labels when k* > 1.  Fewer than two rows: one cluster or none, nothing launched.
+    A single-process call: the rows are whole on this device and nothing is reduced across torch.distributed ranks.
+    Ritz value i is converged to fp32 where (tau_{b+1} / tau_i)^(2 n_iter) is below 2^-24.  At the default n_iter = 30 that holds for the
+    leading values of a clustered input, not for the bulk behind them (tau_{b+1} / tau_m of 0.8 .. 0.99 asks for 35 .. 900 steps): the
+    table can then differ from nmesc_host's by a few 1e-3, and where two candidates' r(p) lie within that, p* can differ from
+    nmesc_host's (k* and the labels rest on the leading gap).  n_iter, up to 1000, buys the agreement."""
+    bounds = parse_speakers(speakers, "nmesc_cluster")
+    if isinstance(n_iter, (bool, np.bool_)) or not isinstance(n_iter, (int, np.integer)) or not 0 <= n_iter <= 1000:
+        raise ValueError(f"nmesc_cluster: n_iter={n_iter!r} (an int, 0 .. 1000)")
+    rows_h = _pick_rows("nmesc_cluster", int(E.shape[0]), rows)
+    n = int(rows_h.size)
+    m, b = _nmesc_shape(max(n, 1), max_count)
+    if n < 2:
+        return NmescResult(np.zeros(n, np.int32), n, 0, (), np.zeros((0, m)), np.zeros(0), 0)
+    ps = nmesc_candidates(n, neighbours)
+    dev = E.device
+    Et = E if rows is None else E.index_select(0, torch.from_numpy(rows_h).to(dev)).contiguous()
+    idx, _ = knn_rows(provider, Et)                                                  # read 1: the status
+    reads, comm, P = 1, _Comm(single=True), min(NMESC_P_MAX, n - 1)     # every rank that calls holds the whole problem: nothing is reduced
+    retried = False
+    if n <= NMESC_DENSE_ROWS:
+        idx_h = idx.cpu().numpy()                                                   # read 2: the lists
+        reads += 1
+        tops = [_dense_top(idx_h, p, m) for p in ps]
+        taus, n_iter = np.stack([t[0] for t in tops]), 0
+    else:
+        rev = knn_reverse(provider, idx, check_idx=False)                                # the lists are the kernel's own: no status read
+        V0 = torch.from_numpy(np.random.default_rng(seed).standard_normal((n, b)).astype(np.float32)).to(dev)
+        spd_flag = torch.zeros((1,), dtype=torch.int32, device=dev)
+
+        def ritz(p: int, shifted: bool):
+            """-> (V [n, b] orthonormal after n_iter steps, Q [b, b], lam [b] descending) of T_p, on the device."""
+            _, dinv = knn_degree(provider, rev[0], rev[2], P, p)
+            V = _orth(provider, comm, V0, b, spd_flag, shifted)
+            for _ in range(n_iter):
+                V = _orth(provider, comm, knn_matvec(provider, idx, rev, dinv, p, V), b, spd_flag, shifted)
+            Q, lam = provider.sym_eigh(provider.rows_gram(V, knn_matvec(provider, idx, rev, dinv, p, V)))
+            return V, Q, lam
+
+        def sweep(shifted: bool):
+            table = torch.cat([ritz(p, shifted)[2][:m].double() for p in ps] + [spd_flag.double()]).cpu().numpy()      # ONE download
+            return table[:-1].reshape(len(ps), m), bool(table[-1])
+        taus, flagged = sweep(False)
+        reads += 1
+        if flagged and np.isfinite(taus).all() and hasattr(provider, "set_option"):
+            spd_flag.zero_()                                                        # spectral_cluster's retry: shifted CholeskyQR
+            retried = True
+            taus, flagged = sweep(True)
+            reads += 1
+        if flagged or not np.isfinite(taus).all():
+            raise np.linalg.LinAlgError(f"nmesc_cluster: the b = {b} block lost rank (Gram matrix not positive definite) on {n} rows")
+    p_star, k_star, ratios, _ = nmesc_select(ps, taus, bounds, n)
+    labels = np.zeros(n, np.int32)
+    if k_star > 1:
+        if n <= NMESC_DENSE_ROWS:
+            U = torch.from_numpy(tops[ps.index(p_star)][1][:, :k_star].astype(np.float32)).to(dev).contiguous()
+        else:
+            V, Q, _ = ritz(p_star, retried)                                         # the same seed and block: the sweep's bits again
+            U = provider.rows_apply(V, Q)[:, :k_star].contiguous()
+        lab = _kmeans(provider, comm, provider.rows_unit(U), 0, n, k_star, NMESC_KMEANS_PASSES)
+        labels = canonical_labels(lab.cpu().numpy()).astype(np.int32)               # the last read
+        reads += 1
+    return NmescResult(labels, k_star, p_star, ps, taus, ratios, int(n_iter), retried, reads)

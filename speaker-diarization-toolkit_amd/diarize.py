@@ -31,6 +31,16 @@ tests pin these rules.
               kept speakers' centroids are the responsibility-weighted means of the original unit rows; every candidate row is then assigned
               by sdk_diarize_assign with the caller's `constrained` flag, so the stretch from embeddings to labels stays on the device and the
               result carries scores either way.  With fewer than two training rows: as "ahc" (one cluster or none).
+  nmesc       (clustering="nmesc"; eigengap spectral clustering with normalised-maximum-eigengap pruning, NeMo's default, stated in cluster.py
+              above NMESC_P_MAX; parity unpinned, the tests pin THIS rule): no threshold.  Each training row lists its 64 nearest rows by
+              cosine (sdk_knn_rows); for every candidate p the graph pruned to p neighbours gives the lazy operator
+              T_p = (I + D^-1/2 A_p D^-1/2) / 2, whose leading eigenvalues come from a subspace iteration on the device (from a dense host
+              eigensolve at 64 rows or fewer); the largest eigengap of the candidate with the least p / gap is the speaker count, and the
+              k-means of that candidate's Ritz vectors gives the labels.  `speakers` bounds the eigengap search itself, so `forced` stays
+              None; `threshold` and `min_cluster_size` are not used and no small cluster is folded.  The labels go through
+              sdk_diarize_centroids and sdk_diarize_assign with the caller's `constrained` flag, as VBx's centroids do, and the result
+              carries scores and `nmesc` = {p, k, ps, eigenvalues, ratios}.  With fewer than two training rows: as "ahc" (one cluster or
+              none).  nmesc: a dict of neighbours, max_count, n_iter, seed (cluster.nmesc_cluster's defaults otherwise).
   bounds      (speakers=; pyannote's num_speakers / min_speakers / max_speakers, written from the published description; parity unpinned, the
               tests pin THIS rule, stated in full in cluster.py above parse_speakers).  None: no bound, every result field is what it was.
               An int k >= 1: exactly k speakers; a pair (lo, hi), either side None, 1 <= lo <= hi: bounds; pyannote's max_speakers is
@@ -100,7 +110,7 @@ from typing import List, NamedTuple, Optional
 import numpy as np
 
 from .cluster import (KMEANS_HOST_READS, PYANNOTE_MIN_CLUSTER_SIZE, PYANNOTE_THRESHOLD, _flat_partition, agglomerative_cluster, cut_level,
-                      effective_min_size, fcluster_distance, level_search, parse_speakers, speaker_target, vbx_cluster)
+                      effective_min_size, fcluster_distance, level_search, nmesc_cluster, parse_speakers, speaker_target, vbx_cluster)
 from .diarize_host import (DEFAULT_BATCH, DEFAULT_PACK_LINKAGE_BYTES, DEFAULT_PACK_SAMPLES, MAX_ASSIGN_DIM, MAX_LINKAGE_ROWS, MAX_PACK_SAMPLES,  # noqa: F401
                            MIN_CLEAN_COLUMNS, MIN_VALID_COLUMNS, N_LOCAL, TRAIN_CLEAN_DEN, _COUNT, _MASK, DiarizationResult, Pack, _centroids64,
                            _dot_in_order, _speaker_cap, appearance_order, assign_constrained_host, assign_grouped_host, assign_rows, candidate_mask,
@@ -114,6 +124,11 @@ from .segmentation import CHUNK, chunk_starts
 from .segmentation import num_frames as seg_frames
 
 
+def _nmesc_fields(nres) -> dict:
+    """DiarizationResult.nmesc of a cluster.NmescResult."""
+    return {"p": nres.p, "k": nres.n_speakers, "ps": nres.ps, "eigenvalues": nres.eigenvalues, "ratios": nres.ratios}
+
+
 @dataclass(frozen=True)
 class _Options:
     """The checked keywords of run, run_many and sweep, built once per call and handed down the stages."""
@@ -125,6 +140,7 @@ class _Options:
     clustering: str
     vbx: dict                    # _check_options' copy
     bounds: Optional[tuple]      # cluster.parse_speakers' result
+    nmesc: Optional[dict] = None # _check_nmesc's copy
 
 
 @dataclass
@@ -149,6 +165,7 @@ class _Clusters(NamedTuple):
     cent_off: np.ndarray         # [R + 1] int64 prefix sums of the recordings' cluster counts
     vres: dict                   # {recording: cluster.VbxResult}
     forced: dict                 # {recording: forced}
+    nres: Optional[dict] = None  # {recording: cluster.NmescResult}
 
 
 class Diarizer:
@@ -179,14 +196,21 @@ class Diarizer:
     # ---------------------------------------------------------------------------------------------- what run and run_many share
     def _check_options(self, who: str, clustering, vbx, max_speakers, speakers=None):
         """-> (vbx as a dict of its own, the bounds of cluster.parse_speakers)."""
-        if clustering not in ("ahc", "vbx"):
-            raise ValueError(f"{who}: clustering={clustering!r} (\"ahc\" or \"vbx\")")
+        if clustering not in ("ahc", "vbx", "nmesc"):
+            raise ValueError(f"{who}: clustering={clustering!r} (\"ahc\", \"vbx\" or \"nmesc\")")
         vbx = dict(vbx or {})
         if set(vbx) - {"Fa", "Fb", "max_iters", "epsilon", "init_smoothing"} or (vbx and clustering != "vbx"):
             raise ValueError(f"{who}: vbx={vbx} (keys Fa, Fb, max_iters, epsilon, init_smoothing; only with clustering=\"vbx\")")
         if max_speakers is not None and int(max_speakers) < 0:
             raise ValueError(f"max_speakers={max_speakers}: must be None or >= 0")
         return vbx, parse_speakers(speakers, who)
+
+    def _check_nmesc(self, who: str, clustering, nmesc) -> dict:
+        """-> nmesc as a dict of its own."""
+        nmesc = dict(nmesc or {})
+        if set(nmesc) - {"neighbours", "max_count", "n_iter", "seed"} or (nmesc and clustering != "nmesc"):
+            raise ValueError(f"{who}: nmesc={nmesc} (keys neighbours, max_count, n_iter, seed; only with clustering=\"nmesc\")")
+        return nmesc
 
     def _check_recording(self, who: str, n_samples: int, step_s: float, logp=None) -> int:
         """The linkage's row bound and the shape of an injected logp, for a recording of n_samples > 0 samples -> its number of chunks."""
@@ -241,7 +265,7 @@ class Diarizer:
     # ---------------------------------------------------------------------------------------------- one recording
     def run(self, samples, step_s: float = 1.0, threshold: float = PYANNOTE_THRESHOLD, min_cluster_size: int = PYANNOTE_MIN_CLUSTER_SIZE,
             max_speakers: Optional[int] = None, logp=None, constrained: bool = False, clustering: str = "ahc",
-            vbx: Optional[dict] = None, speakers=None) -> DiarizationResult:
+            vbx: Optional[dict] = None, speakers=None, nmesc: Optional[dict] = None) -> DiarizationResult:
         """samples: 16 kHz mono int16 (host) -> DiarizationResult.  logp [C, 589, 7] (fp32, host or device) replaces the segmentation
         model's output (the chunks are chunk_starts(len(samples), step_s)).  The default threshold and size are PyAnnote 3.1's, tuned for
         ITS trained embedding; with other weights pass a threshold of your own.  constrained=True: the constrained assignment of the
@@ -250,11 +274,15 @@ class Diarizer:
         meaning, the cut of the linkage, which now only initialises: pass cluster.VBX_AHC_THRESHOLD (0.6) with it; min_cluster_size is not
         used.  vbx: a dict of Fa, Fb, max_iters, epsilon, init_smoothing (cluster.vbx_cluster's defaults otherwise).  The result carries
         scores, pi and elbo.
+        clustering="nmesc": the eigengap spectral clustering of the module docstring (cluster.nmesc_cluster): threshold and min_cluster_size
+        are not used; nmesc: a dict of neighbours, max_count, n_iter, seed.  The result carries scores and `nmesc`; `speakers` bounds the
+        eigengap search and `forced` stays None.
         speakers: the number of speakers of the recording, "bounds" in the module docstring: None, an int k (exactly k) or a pair (lo, hi),
         either side None.  pyannote's num_speakers=k is speakers=k, its min_speakers / max_speakers are speakers=(lo, hi), its
         max_speakers alone is speakers=(None, hi); max_speakers HERE is the cap per frame and keeps that meaning.  The result's `forced`
         says whether the clustering was overruled."""
         vbx, bounds = self._check_options("diarize", clustering, vbx, max_speakers, speakers)
+        nmesc = self._check_nmesc("diarize", clustering, nmesc)
         torch, eng = _native()[0], self.eng
         x = np.ascontiguousarray(samples, dtype=np.int16).reshape(-1)
         if x.size == 0:
@@ -270,15 +298,18 @@ class Diarizer:
         cls, info_dev, E_dev = self._embed_all(rec, x.size, starts_dev, logp)     # decode, masks, embedding
         info = info_dev.cpu().numpy()
         train = training_rows(info, F)                          # training rows and their clustering
-        vres, tl, forced = None, np.zeros(len(train), np.int32), None
-        if len(train) > 1 and clustering == "vbx":
+        vres, nres, tl, forced = None, None, np.zeros(len(train), np.int32), None
+        if len(train) > 1 and clustering == "nmesc":
+            nres = nmesc_cluster(eng, E_dev, rows=train, speakers=bounds, **nmesc)
+            tl = nres.labels
+        elif len(train) > 1 and clustering == "vbx":
             vres = vbx_cluster(eng, E_dev, self.plda_model(), threshold, rows=train, speakers=bounds, **vbx)
             forced = vres.forced
         elif len(train) > 1:
             ares = agglomerative_cluster(eng, E_dev.index_select(0, torch.from_numpy(train).to(eng.device)).contiguous(), threshold, min_cluster_size,
                                          speakers=bounds)
             tl, forced = ares.labels, ares.forced
-        if constrained or clustering == "vbx":                  # assignment on the device: the embeddings stay there, the result carries scores
+        if constrained or clustering != "ahc":                  # assignment on the device: the embeddings stay there, the result carries scores
             if vres is not None:
                 c32, c64 = vres.cent, vres.cent64.contiguous()
             else:
@@ -312,6 +343,8 @@ class Diarizer:
         res = DiarizationResult(turns_from_frames(speakers, K), K, cent, labels, count, speakers, st, info, cls, scores)
         if vres is not None:
             res.pi, res.elbo = vres.pi, vres.elbo
+        if nres is not None:
+            res.nmesc = _nmesc_fields(nres)
         if forced is not None:
             res.forced = forced
         return res
@@ -319,7 +352,7 @@ class Diarizer:
     # ---------------------------------------------------------------------------------------------- many recordings in one device pass
     def run_many(self, recordings, step_s: float = 1.0, threshold: float = PYANNOTE_THRESHOLD, min_cluster_size: int = PYANNOTE_MIN_CLUSTER_SIZE,
                  max_speakers: Optional[int] = None, logp=None, constrained: bool = False, clustering: str = "ahc",
-                 vbx: Optional[dict] = None, speakers=None) -> List[DiarizationResult]:
+                 vbx: Optional[dict] = None, speakers=None, nmesc: Optional[dict] = None) -> List[DiarizationResult]:
         """recordings: a list of 16 kHz mono int16 arrays (host) -> one DiarizationResult per recording, in order; the keywords are run's,
         logp is None or a list with one [C_r, 589, 7] array per recording.  The recordings cross the pipeline in packs (pack_recordings) of
         at most $SDK_DIARIZE_PACK_SAMPLES samples (default 2^28, gaps included) whose grouped linkage stays within
@@ -332,9 +365,12 @@ class Diarizer:
         Where the results differ from run's on purpose: "shared" in the module docstring.  clustering="vbx" runs cluster.vbx_cluster
         recording by recording (its own linkage, cut and host reads) between the packed embedding and the grouped assignment.
         speakers: run's, applied to every recording; for "ahc" the level search replaces the cut on the host and adds no wait, for "vbx" a
-        recording whose count is overruled adds cluster.KMEANS_HOST_READS waits."""
+        recording whose count is overruled adds cluster.KMEANS_HOST_READS waits.  clustering="nmesc" runs cluster.nmesc_cluster recording
+        by recording in the same place (_pack_nmesc), as "vbx" does; its waits per recording (NmescResult.host_reads: the status of the
+        lists, the eigenvalue table or the lists, the labels) are counted in last_sync."""
         vbx, bounds = self._check_options("diarize_many", clustering, vbx, max_speakers, speakers)
-        opts = _Options(step_s, threshold, min_cluster_size, max_speakers, bool(constrained), clustering, vbx, bounds)
+        opts = _Options(step_s, threshold, min_cluster_size, max_speakers, bool(constrained), clustering, vbx, bounds,
+                        self._check_nmesc("diarize_many", clustering, nmesc))
         xs, packs = self._plan_packs(recordings, logp, step_s)
         out: List[Optional[DiarizationResult]] = [None] * len(xs)
         self.last_sync = []
@@ -491,7 +527,7 @@ class Diarizer:
         p = self._pack_begin(xs, logps, opts)
         if p is None:
             return [self._empty() for _ in xs]
-        cl = self._pack_vbx(p, opts) if opts.clustering == "vbx" else self._pack_ahc(p, opts)
+        cl = {"vbx": self._pack_vbx, "nmesc": self._pack_nmesc}.get(opts.clustering, self._pack_ahc)(p, opts)
         p.tab.set_clusters(cl.cent_off)
         p.sync["uploads"] += p.tab.uploads
         self._mark("cut_fold_centroids")
@@ -554,6 +590,25 @@ class Diarizer:
             K_r.append(K)
         c32, c64 = (torch.cat(c).contiguous() for c in zip(*cents)) if cents else (None, None)    # None: no recording has a cluster
         return _Clusters(c32, c64, np.concatenate([[0], np.cumsum(K_r)]).astype(np.int64), vres, forced)
+
+    def _pack_nmesc(self, p: _PackState, opts: _Options) -> _Clusters:
+        """cluster.nmesc_cluster recording by recording, as _pack_vbx runs VBx: between the packed embedding and the grouped assignment.  A
+        recording's labels go through sdk_diarize_centroids; its host reads (NmescResult.host_reads) are counted in last_sync."""
+        torch = _native()[0]
+        E_dev, co, rows = p.E_dev, p.pack.chunk_off, p.rows
+        nres, cents, K_r = {}, [], []
+        for r in range(len(rows)):
+            a, K = N_LOCAL * int(co[r]), min(len(rows[r]), 1)
+            lab = np.zeros(len(rows[r]), np.int32)                # one training row, or the candidates: one cluster
+            if p.n_train[r] > 1:
+                v = nres[r] = nmesc_cluster(self.eng, E_dev[a:N_LOCAL * int(co[r + 1])], rows=rows[r] - a, speakers=opts.bounds, **opts.nmesc)
+                p.sync["downloads"] += v.host_reads
+                lab, K = v.labels, int(v.n_speakers)
+            if K:
+                cents.append(diarize_centroids(self.eng, E_dev, self._up(rows[r].astype(np.int32)), self._up(lab.astype(np.int32)), K, check_rows=False))
+            K_r.append(K)
+        c32, c64 = (torch.cat(c).contiguous() for c in zip(*cents)) if cents else (None, None)    # None: no recording has a cluster
+        return _Clusters(c32, c64, np.concatenate([[0], np.cumsum(K_r)]).astype(np.int64), {}, {}, nres)
 
     def _pack_ahc(self, p: _PackState, opts: _Options) -> _Clusters:
         """The linkage stage (_pack_link), then the cut-to-centroids stage (_pack_cut)."""
@@ -643,5 +698,7 @@ class Diarizer:
                 res.pi, res.elbo = vres[r].pi, vres[r].elbo
             if r in forced:
                 res.forced = forced[r]
+            if cl.nres and r in cl.nres:
+                res.nmesc = _nmesc_fields(cl.nres[r])
             out.append(res)
         return out

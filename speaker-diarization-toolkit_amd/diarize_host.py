@@ -41,6 +41,7 @@ class DiarizationResult:
     # field list, and with it the positional constructor, ends with scores as before.
     pi = None                                 # [S] float64 weights of the S initial speakers after the last iteration
     elbo = None                               # [n_iter] float64
+    nmesc = None                              # clustering="nmesc": {p, k, ps, eigenvalues [n_p, m], ratios [n_p]} of cluster.nmesc_cluster ("nmesc" in diarize.py); else None
     forced = None                             # speakers= overruled the clustering: {found, target, method, level, n_iter} ("bounds" in diarize.py); else None
 
 

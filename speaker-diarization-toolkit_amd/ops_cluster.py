@@ -415,3 +415,79 @@ class ClusterMixin:
         check(self.lib.sdk_stream_centroids(self.ctx, st.buf.data_ptr(), st.nbytes, st.R, st.capacity, st.d, int(first), count, cent.data_ptr(),
                                             counts.data_ptr(), K.data_ptr(), _ptr(S), _stream()), "sdk_stream_centroids")
         return (cent, counts, K, S) if sums else (cent, counts, K)
+
+
+# ---- the nearest-neighbour graph of cluster.nmesc_cluster (csrc/nmesc.hip): functions of an engine, as diarize_ops.py's wrappers are, so that
+# ops.Engine's public names stay the ones tests/test_ops_layout_cpu.py lists.  Only knn_rows and knn_reverse read a status back.
+
+def knn_rows(eng, E: torch.Tensor):
+    """E [n, d] fp32 unit rows (device), 2 <= n <= 65536 -> (idx int32 [n, P], cos float64 [n, P]) on the device, P = min(KNN_P_MAX, n - 1):
+    row i's P rows j != i of largest cosine, ties to the lower j, in that order (sdk_knn_rows; the cosine is the float64 sum of the exact
+    products in column order).  One host read, the status: a row that holds a non-finite value raises ValueError naming the first one
+    (.idx, .cos and .status on the exception; a NaN cosine ranks as -inf)."""
+    n, d = _args.rows("knn_rows", "E", E)
+    P = _args.knn_shape("knn_rows", n)
+    idx = torch.empty((n, P), dtype=torch.int32, device=eng.device)
+    cos = torch.empty((n, P), dtype=torch.float64, device=eng.device)
+    status = torch.empty((2,), dtype=torch.int32, device=eng.device)
+    check(eng.lib.sdk_knn_rows(eng.ctx, E.data_ptr(), n, d, P, idx.data_ptr(), cos.data_ptr(), status.data_ptr(), _stream()), "sdk_knn_rows")
+    bad, first = (int(v) for v in status.cpu().numpy())
+    if bad:
+        err = ValueError(f"knn_rows: row {first} has a non-finite value ({bad} such rows in all)")
+        err.idx, err.cos, err.status = idx, cos, (bad, first)
+        raise err
+    return idx, cos
+
+
+def knn_reverse(eng, idx: torch.Tensor, check_idx: bool = True):
+    """idx int32 [n, P] (knn_rows') -> (rev_off int32 [n + 1], rev_src int32 [n P], rev_rank int32 [n P]) on the device: the incoming
+    edges as CSR, row j's entries the rows that list j in ascending order with j's position in their lists (sdk_knn_reverse).  One host
+    read, the status: an entry of idx outside [0, n) raises ValueError naming its row (the kernels skip such an entry).  check_idx=False:
+    idx is knn_rows' own, nothing is read back."""
+    n, P = _args.knn_lists("knn_reverse", idx)
+    rev_off = torch.empty((n + 1,), dtype=torch.int32, device=eng.device)
+    rev_src = torch.empty((n * P,), dtype=torch.int32, device=eng.device)
+    rev_rank = torch.empty((n * P,), dtype=torch.int32, device=eng.device)
+    status = torch.empty((2,), dtype=torch.int32, device=eng.device)
+    nbytes = eng._workspace_bytes("sdk_knn_reverse_workspace_bytes", n, P)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=eng.device)
+    check(eng.lib.sdk_knn_reverse(eng.ctx, idx.data_ptr(), n, P, rev_off.data_ptr(), rev_src.data_ptr(), rev_rank.data_ptr(), status.data_ptr(),
+                                   ws.data_ptr(), nbytes, _stream()), "sdk_knn_reverse")
+    bad, first = (int(v) for v in status.cpu().numpy()) if check_idx else (0, 0)
+    if bad:
+        raise ValueError(f"knn_reverse: row {first} of idx lists a row outside [0, {n}) ({bad} such entries in all)")
+    return rev_off, rev_src, rev_rank
+
+
+def knn_degree(eng, rev_off: torch.Tensor, rev_rank: torch.Tensor, P: int, p: int):
+    """The graph pruned to the first p <= P neighbours -> (deg int32 [n], dinv float64 [n]) on the device: deg = p + the reverse entries
+    of rank < p, dinv = 1 / sqrt(deg) (sdk_knn_degree).  Nothing is read back."""
+    n = int(_args.tensor("knn_degree", "rev_off", rev_off, "int32", (None,)).numel()) - 1
+    if _args.knn_shape("knn_degree", n) != int(P):
+        raise ValueError(f"knn_degree: P={P} must be min({_args.KNN_P_MAX}, n - 1) = {_args.knn_shape('knn_degree', n)} (n={n})")
+    _args.tensor("knn_degree", "rev_rank", rev_rank, "int32", (n * int(P),))
+    _args.knn_p("knn_degree", p, P)
+    deg = torch.empty((n,), dtype=torch.int32, device=eng.device)
+    dinv = torch.empty((n,), dtype=torch.float64, device=eng.device)
+    check(eng.lib.sdk_knn_degree(eng.ctx, rev_off.data_ptr(), rev_rank.data_ptr(), n, int(P), int(p), deg.data_ptr(), dinv.data_ptr(), _stream()),
+          "sdk_knn_degree")
+    return deg, dinv
+
+
+def knn_matvec(eng, idx: torch.Tensor, rev, dinv: torch.Tensor, p: int, X: torch.Tensor):
+    """Y = T_p X for X fp32 [n, kv], kv <= 32, T_p = (I + D^-1/2 A_p D^-1/2) / 2 over the lists idx, their reverse rev = (rev_off, rev_src,
+    rev_rank) and dinv of knn_degree at the same p (sdk_knn_matvec; include/sdk_hip.h states the arithmetic operation by operation).
+    Nothing is read back."""
+    n, P = _args.knn_lists("knn_matvec", idx)
+    rev_off, rev_src, rev_rank = rev
+    _args.tensor("knn_matvec", "rev_off", rev_off, "int32", (n + 1,))
+    _args.tensor("knn_matvec", "rev_src", rev_src, "int32", (n * P,))
+    _args.tensor("knn_matvec", "rev_rank", rev_rank, "int32", (n * P,))
+    _args.tensor("knn_matvec", "dinv", dinv, "float64", (n,))
+    _args.knn_p("knn_matvec", p, P)
+    _, kv = _args.thin("knn_matvec", "X", X)
+    _args.tensor("knn_matvec", "X", X, "float32", (n, kv))
+    Y = torch.empty_like(X)
+    check(eng.lib.sdk_knn_matvec(eng.ctx, idx.data_ptr(), rev_off.data_ptr(), rev_src.data_ptr(), rev_rank.data_ptr(), dinv.data_ptr(), n, P,
+                                  int(p), X.data_ptr(), kv, Y.data_ptr(), _stream()), "sdk_knn_matvec")
+    return Y

@@ -1,0 +1,206 @@
+"""CPU checks of clustering="nmesc" (cluster.py): the selection rule on hand-made eigenvalue tables, the whole rule in numpy (nmesc_host) on
+planted mixtures, the numpy restatements of the graph kernels against a brute-force dense construction, and the option checks."""
+from __future__ import annotations
+
+import importlib
+
+import numpy as np
+import pytest
+
+from oracle.spectral import adjusted_rand_index, vmf_mixture
+
+PKG = "speaker-diarization-toolkit_amd"
+cluster = importlib.import_module(f"{PKG}.cluster")
+diarize = importlib.import_module(f"{PKG}.diarize")
+
+# The planted inputs shared with tests/test_nmesc_gpu.py: (planted speakers, rows, width, seed), noise 0.35, candidates SPARSE.  With the
+# default candidates (2, 3, 4, 6, ..) neighbouring r(p) = p / g(p) differ by a few per cent on every input tried (n = 40 .. 2000, noise
+# 0.2 .. 0.5), so no input meets the margin below; the candidates (4, 32) do, and the `neighbours` option is part of the rule.
+SPARSE = (4, 32)
+PLANTED = [(1, 40, 64, 0), (2, 64, 64, 1), (2, 65, 64, 0), (2, 120, 128, 1), (4, 200, 64, 0), (7, 400, 64, 0)]
+NOISE = 0.35
+# Per planted input above NMESC_DENSE_ROWS: (max_count, n_iter) at which the host spectrum says the WHOLE table of both SPARSE candidates has
+# converged, (tau_{b+1} / tau_m)^(2 n_iter) < 2^-24.  tau_{b+1} / tau_m is 0.84 .. 0.98 on these inputs, so the default 30 steps do not
+# do; the steps needed, log(2^24) / (2 log(tau_m / tau_{b+1})), are 233 / 209 / 263 / 247 for the four rows.
+CONVERGED = {(2, 65, 64, 0): (3, 240), (2, 120, 128, 1): (7, 220), (4, 200, 64, 0): (15, 270), (7, 400, 64, 0): (7, 260)}
+FP32_RESOLUTION = 2.0 ** -24
+
+
+def convergence(idx, p, m, b, n_iter):
+    """-> ((tau_{b+1} / tau_m)^(2 n_iter), tau [m]) of T_p from the dense float64 eigensolve: the slowest Ritz value's error factor."""
+    tau = cluster._dense_top(idx, p, b + 1)[0]
+    return float((tau[b] / tau[m - 1]) ** (2 * n_iter)), tau[:m]
+
+
+def margins(res):
+    """(runner-up r / best r, winning gap / next gap at p*)."""
+    r = np.sort(res.ratios)
+    g = np.sort(-np.diff(res.eigenvalues[res.ps.index(res.p)]))[::-1]
+    return r[1] / r[0], g[0] / max(g[1], 1e-300)
+
+
+def table(*rows):
+    return np.array(rows, dtype=np.float64)
+
+
+# ---------------------------------------------------------------------------------------------- nmesc_select
+@pytest.mark.parametrize("k", [1, 2, 15])
+def test_select_planted_gap(k):
+    m = 16                                                            # Kmax = 15
+    tau = np.concatenate([np.full(k, 1.0), np.linspace(0.5, 0.4, m - k)])
+    flat = np.linspace(1.0, 0.9, m)                                   # gaps of 1 / 150 each: r = 8 * 150
+    p, kk, ratios, ks = cluster.nmesc_select((4, 8), table(tau, flat), None, 100)
+    assert (p, kk) == (4, k) and ks[0] == k
+    assert ratios[0] == 4 / (1.0 - 0.5) and np.isclose(ratios[1], 8 * 150)
+
+
+def test_select_ties():
+    # two candidates with the same r: the lower p; two equal gaps: the lower i
+    a = [1.0, 0.5, 0.0, 0.0]                                          # p = 2: gaps 0.5, 0.5, 0 -> k = 1, r = 4
+    b = [1.0, 1.0, 0.0, 0.0]                                          # p = 4: gap 1 at i = 2 -> r = 4
+    assert cluster.nmesc_select((2, 4), table(a, b), None, 10)[:2] == (2, 1)
+    assert cluster.nmesc_select((4, 8), table(b, [1.0, 1.0, -1.0, -1.0]), None, 10)[:2] == (4, 2)
+
+
+def test_select_bounds_move_the_choice():
+    tau = table([1.0, 0.9, 0.5, 0.45, 0.2, 0.1])                      # gaps .1 .4 .05 .25 .1
+    sel = lambda sp: cluster.nmesc_select((4,), tau, cluster.parse_speakers(sp), 50)[:2]
+    assert sel(None) == (4, 2)
+    assert sel(1) == (4, 1) and sel(3) == (4, 3) and sel(5) == (4, 5)
+    assert sel((3, None)) == (4, 4) and sel((None, 1)) == (4, 1) and sel((3, 3)) == (4, 3)
+    # the bounds move p* too: inside [3, 5] the second candidate has the larger gap per neighbour
+    two = table([1.0, 0.2, 0.19, 0.18, 0.17], [1.0, 0.99, 0.98, 0.1, 0.0])
+    assert cluster.nmesc_select((2, 4), two, None, 50)[:2] == (2, 1)
+    assert cluster.nmesc_select((2, 4), two, (3, None), 50)[:2] == (4, 3)
+
+
+def test_select_flat_spectra_and_short_tables():
+    flat = np.ones((3, 5))
+    p, k, ratios, _ = cluster.nmesc_select((2, 4, 8), flat, None, 9)
+    assert (p, k) == (8, 1) and np.isinf(ratios).all()
+    assert cluster.nmesc_select((2, 4, 8), flat, (3, 4), 9)[:2] == (8, 3)
+    flat[1, 2] = 1.0 - 0.5e-6                                         # a gap at the flat threshold or under it is still flat
+    assert np.isinf(cluster.nmesc_select((2, 4, 8), flat, None, 9)[2]).all()
+    # m - 1 < lo: the bounds are clipped to m - 1
+    assert cluster.nmesc_select((1,), table([1.0, 0.5, 0.1]), (7, 9), 3)[:2] == (1, 2)
+    with pytest.raises(ValueError, match="nmesc_select"):
+        cluster.nmesc_select((1, 2), table([1.0, 0.5]), None, 3)
+
+
+def test_candidates():
+    assert cluster.nmesc_candidates(2) == (1,) and cluster.nmesc_candidates(3) == (2,)
+    assert cluster.nmesc_candidates(10) == (2, 3, 4, 6, 8) and cluster.nmesc_candidates(65) == cluster.NMESC_NEIGHBOURS
+    assert cluster.nmesc_candidates(20, (40, 5, 5)) == (5,) and cluster.nmesc_candidates(4, (40,)) == (3,)
+    with pytest.raises(ValueError, match="neighbours"):
+        cluster.nmesc_candidates(20, (0, 3))
+
+
+# ---------------------------------------------------------------------------------------------- the whole rule on planted mixtures
+@pytest.mark.parametrize("k,n,d,seed", PLANTED)
+def test_host_finds_the_planted_speakers(k, n, d, seed):
+    E, lab = vmf_mixture(n, d, k, seed, NOISE)
+    res = cluster.nmesc_host(E, neighbours=SPARSE)
+    ratio_margin, gap_margin = margins(res)
+    print(f"k={k} n={n}: p*={res.p} k*={res.n_speakers} r margin {ratio_margin:.2f} gap margin {gap_margin:.2f}")
+    assert ratio_margin >= 2.0 and gap_margin >= 2.0                  # the preconditions that make the device comparison meaningful
+    assert res.n_speakers == k and adjusted_rand_index(res.labels, lab) == 1.0
+    assert np.array_equal(res.labels, lab)                            # both canonical
+    # the default candidates find the same count (their neighbouring r are too close for a margin: see SPARSE)
+    dflt = cluster.nmesc_host(E)
+    assert dflt.n_speakers == k and np.array_equal(dflt.labels, lab)
+
+
+def test_converged_settings_cover_every_device_input():
+    """The precondition of the device eigenvalue comparison (tests/test_nmesc_gpu.py), from the host spectrum alone."""
+    assert set(CONVERGED) == {c for c in PLANTED if c[1] > cluster.NMESC_DENSE_ROWS}
+    for (k, n, d, seed), (max_count, n_iter) in CONVERGED.items():
+        idx, _ = cluster.knn_rows_host(vmf_mixture(n, d, k, seed, NOISE)[0])
+        m, b = cluster._nmesc_shape(n, max_count)
+        assert max_count >= k and n_iter <= 1000
+        for p in SPARSE:
+            factor, _ = convergence(idx, p, m, b, n_iter)
+            print(f"n={n} p={p} max_count={max_count} n_iter={n_iter}: (tau_b+1 / tau_m)^(2 n_iter) = {factor:.2e}")
+            assert factor < FP32_RESOLUTION
+
+
+def test_host_edges():
+    E, _ = vmf_mixture(5, 64, 1, 0, NOISE)
+    assert cluster.nmesc_host(E[:0]).labels.size == 0 and cluster.nmesc_host(E[:1]).labels.tolist() == [0]
+    two = cluster.nmesc_host(E[:2])
+    assert two.ps == (1,) and two.labels.tolist() == [0, 0]
+    E[3, 7] = np.nan
+    with pytest.raises(ValueError, match="row 3 "):
+        cluster.nmesc_host(E)
+    picked = cluster.nmesc_host(vmf_mixture(90, 64, 2, 3, NOISE)[0], rows=np.arange(0, 90, 2), speakers=3)
+    assert picked.n_speakers == 3 and picked.labels.size == 45
+
+
+# ---------------------------------------------------------------------------------------------- the graph restatements against a dense construction
+def tie_rows(n, d, seed, distinct=4):
+    rng = np.random.default_rng(seed)
+    V = rng.standard_normal((distinct, d))
+    V /= np.linalg.norm(V, axis=1, keepdims=True)
+    return V[rng.integers(0, distinct, n)].astype(np.float32)
+
+
+@pytest.mark.parametrize("n", [2, 3, 30, 66, 90])
+def test_graph_restatements_against_brute_force(n):
+    E = tie_rows(n, 64, n)
+    P = min(64, n - 1)
+    idx, cos = cluster.knn_rows_host(E)
+    X = E.astype(np.float64)
+    full = np.zeros((n, n))
+    for t in range(64):
+        full += np.outer(X[:, t], X[:, t])
+    assert np.array_equal(full, full.T)
+    for i in range(n):                                                # the list: a plain sort of (cosine descending, row ascending)
+        want = sorted((j for j in range(n) if j != i), key=lambda j: (-full[i, j], j))[:P]
+        assert idx[i].tolist() == want and np.array_equal(cos[i], full[i, want])
+    off, src, rank = cluster.knn_reverse_host(idx)
+    for j in range(n):                                                # the reverse list: ascending sources, each with j's position
+        want = [(i, idx[i].tolist().index(j)) for i in range(n) if j in idx[i]]
+        assert list(zip(src[off[j]:off[j + 1]].tolist(), rank[off[j]:off[j + 1]].tolist())) == want
+    rng = np.random.default_rng(n)
+    for p in sorted({1, max(1, P // 2), P}):
+        B = np.zeros((n, n))
+        for i in range(n):
+            B[i, idx[i, :p]] = 1.0
+        A = B + B.T
+        deg, dinv = cluster.knn_degree_host(off, rank, p)
+        assert np.array_equal(deg, A.sum(1)) and np.array_equal(dinv, 1.0 / np.sqrt(A.sum(1)))
+        T = 0.5 * (np.eye(n) + A / np.sqrt(np.outer(A.sum(1), A.sum(1))))
+        assert np.allclose(cluster.knn_dense_host(idx, p), T, rtol=0, atol=1e-15)
+        Xv = rng.standard_normal((n, 5)).astype(np.float32)
+        Y = cluster.knn_matvec_host(idx, (off, src, rank), dinv, p, Xv)
+        assert Y.dtype == np.float32 and np.abs(Y - T @ Xv.astype(np.float64)).max() <= 2.0 ** -22 * max(1.0, np.abs(T @ Xv).max())
+        # and operation by operation, one row at a time
+        for i in (0, n - 1):
+            s = np.zeros(5)
+            for r in range(p):
+                s = s + dinv[idx[i, r]] * Xv[idx[i, r]].astype(np.float64)
+            for e in range(off[i], off[i + 1]):
+                if rank[e] < p:
+                    s = s + dinv[src[e]] * Xv[src[e]].astype(np.float64)
+            assert np.array_equal(Y[i], (0.5 * (Xv[i].astype(np.float64) + dinv[i] * s)).astype(np.float32))
+
+
+# ---------------------------------------------------------------------------------------------- options
+def test_option_checks():
+    d = diarize.Diarizer(None, None, None)
+    x = np.zeros(16000, np.int16)
+    with pytest.raises(ValueError, match="only with clustering=\"nmesc\""):
+        d.run(x, clustering="ahc", nmesc={"n_iter": 10})
+    with pytest.raises(ValueError, match="only with clustering=\"nmesc\""):
+        d.run_many([x], clustering="vbx", nmesc={"seed": 1})
+    with pytest.raises(ValueError, match="keys neighbours, max_count, n_iter, seed"):
+        d.run(x, clustering="nmesc", nmesc={"threshold": 0.5})
+    with pytest.raises(ValueError, match="only with clustering=\"vbx\""):
+        d.run(x, clustering="nmesc", vbx={"Fa": 0.1})
+    with pytest.raises(ValueError, match="clustering='spectral'"):
+        d.run(x, clustering="spectral")
+    with pytest.raises(ValueError, match="sweep: clustering='nmesc'"):
+        d.sweep([x], [[]], [0.5], clustering="nmesc")
+    assert d._check_options("x", "nmesc", None, None, (2, 3)) == ({}, (2, 3))
+    assert d._check_nmesc("x", "nmesc", {"max_count": 7}) == {"max_count": 7}
+    with pytest.raises(ValueError, match="max_count"):
+        cluster.nmesc_host(np.zeros((4, 64), np.float32), max_count=32)

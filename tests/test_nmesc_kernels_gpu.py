@@ -1,0 +1,183 @@
+"""GPU checks, exact, of the nearest-neighbour graph kernels of clustering="nmesc" (sdk_knn_rows, sdk_knn_reverse, sdk_knn_degree,
+sdk_knn_matvec; csrc/nmesc.hip) against their numpy restatements in cluster.py (knn_rows_host .. knn_matvec_host): every output bit for bit.
+
+Nothing here has a tolerance.  The cosine is a float64 sum of exact products in column order on both sides; the reverse lists and the degrees
+are integers; the mat-vec's arithmetic is stated operation by operation in include/sdk_hip.h and the restatement performs the same operations
+in the same order."""
+from __future__ import annotations
+
+import importlib
+
+import numpy as np
+import pytest
+import torch
+
+PKG = "speaker-diarization-toolkit_amd"
+cluster = importlib.import_module(f"{PKG}.cluster")
+OC = importlib.import_module(f"{PKG}.ops_cluster")
+pytestmark = pytest.mark.gpu
+
+# the kernels' edges (constants of csrc/nmesc.hip)
+KNN_RB = 32        # query rows per workgroup of knn_rows_kernel
+KNN_RW = 8         # query rows per wave
+KNN_TC = 64        # candidate rows per tile, one lane each; also KNN_P_MAX
+KNN_TJ = 64        # columns per LDS tile
+KNN_CH = 256       # source rows per chunk of the reverse fill; also the threads of the row scan
+KNN_NT = 256       # threads of the mat-vec workgroup: n * kv crosses it
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def unit(v):
+    v = np.asarray(v, np.float64)
+    return (v / np.linalg.norm(v, axis=-1, keepdims=True)).astype(np.float32)
+
+
+def random_rows(n, d, seed):
+    return unit(np.random.default_rng(seed).standard_normal((n, d)))
+
+
+def tie_rows(n, d, seed, distinct=5):
+    """Rows drawn from a few distinct unit vectors, with duplicates: many cosines are exactly equal."""
+    distinct = min(distinct, n - 1)                                  # at least one duplicate
+    rng = np.random.default_rng(seed)
+    return unit(rng.standard_normal((distinct, d)))[rng.integers(0, distinct, n)]
+
+
+def graph_host(E):
+    idx, cos = cluster.knn_rows_host(E)
+    return idx, cos, cluster.knn_reverse_host(idx)
+
+
+def graph_dev(engine, E):
+    idx, cos = OC.knn_rows(engine, dev(E))
+    return idx, cos, OC.knn_reverse(engine, idx)
+
+
+def assert_graph_equal(engine, E, ps, kvs, seed=0):
+    idx_h, cos_h, rev_h = graph_host(E)
+    idx, cos, rev = graph_dev(engine, E)
+    n, P = idx_h.shape
+    assert np.array_equal(idx.cpu().numpy(), idx_h)
+    assert np.array_equal(cos.cpu().numpy().view(np.int64), cos_h.view(np.int64))
+    for got, want in zip(rev, rev_h):
+        assert np.array_equal(got.cpu().numpy(), want)
+    rng = np.random.default_rng(seed)
+    for p in ps:
+        deg_h, dinv_h = cluster.knn_degree_host(rev_h[0], rev_h[2], p)
+        deg, dinv = OC.knn_degree(engine, rev[0], rev[2], P, p)
+        assert np.array_equal(deg.cpu().numpy(), deg_h)
+        assert np.array_equal(dinv.cpu().numpy().view(np.int64), dinv_h.view(np.int64))
+        for kv in kvs:
+            X = rng.standard_normal((n, kv)).astype(np.float32)
+            Y = OC.knn_matvec(engine, idx, rev, dinv, p, dev(X)).cpu().numpy()
+            Yh = cluster.knn_matvec_host(idx_h, rev_h, dinv_h, p, X)
+            assert np.array_equal(Y.view(np.int32), Yh.view(np.int32)), (n, p, kv, np.abs(Y - Yh).max())
+    return idx_h, rev_h
+
+
+# n = 2, 3: P = 1, 2.  65: P = 64 = n - 1, every row lists every other; 66: the first n at which a row is left out.  One size on each side of
+# the workgroup of query rows (KNN_RB), of the wave's rows (KNN_RW), of the candidate tile (KNN_TC: 64 / 65 above, 128 / 129 for the second
+# tile) and of the fill's chunk and the row scan (KNN_CH).
+@pytest.mark.parametrize("n", [2, 3, KNN_RW, KNN_RW + 1, KNN_RB, KNN_RB + 1, KNN_TC, 65, 66, 2 * KNN_TC, 2 * KNN_TC + 1, KNN_CH, KNN_CH + 1])
+def test_every_size_edge(engine, n):
+    P = min(64, n - 1)
+    assert_graph_equal(engine, random_rows(n, 64, n), sorted({1, P}), (1, 32))
+
+
+@pytest.mark.parametrize("d", [64, 192, 512])                       # one, three and eight column tiles (KNN_TJ)
+def test_widths(engine, d):
+    assert_graph_equal(engine, random_rows(97, d, d), (1, 64), (1, 32))
+
+
+@pytest.mark.parametrize("n,d", [(3, 64), (65, 64), (66, 64), (131, 192), (300, 64)])
+def test_tie_rich_rows(engine, n, d):
+    """Duplicated rows: the cosines tie exactly and the lower row must come first, on the device as in the restatement."""
+    E = tie_rows(n, d, n)
+    idx_h, _ = assert_graph_equal(engine, E, sorted({1, min(64, n - 1)}), (1, 32))
+    C = cluster.knn_rows_host(E)[1]
+    assert (np.diff(C, axis=1) == 0).any()                          # the input does tie
+
+
+def test_matvec_crosses_its_workgroup(engine):
+    """n * kv on each side of KNN_NT, at a kv that does not divide it."""
+    for n, kv in ((KNN_NT // 8, 8), (KNN_NT // 8 + 1, 8), (37, 7)):
+        assert_graph_equal(engine, random_rows(n, 64, n + kv), (1, 5, min(64, n - 1)), (kv,))
+
+
+def hub_rows(n, d, seed, outliers=3):
+    """Row 0 is e_0; the last `outliers` rows are 0.5 e_0 + e_{d-1-t}; every other row is e_0 + 0.5 u with u a random unit vector in the
+    columns between.  Cosines: row to hub 0.894, row to row 0.8 + 0.2 u.u' (u.u' stays far under 0.47), outlier to hub 0.447, outlier to
+    row 0.4, outlier to outlier 0.2: every row lists the hub first, and nobody lists an outlier once n - 1 > 64."""
+    rng = np.random.default_rng(seed)
+    U = np.zeros((n, d))
+    U[:, 1:d - outliers] = rng.standard_normal((n, d - outliers - 1))
+    E = 0.5 * U / np.linalg.norm(U, axis=1, keepdims=True)
+    E[:, 0] = 1.0
+    E[0, 1:] = 0.0
+    for t in range(outliers):
+        E[n - 1 - t] = 0.0
+        E[n - 1 - t, 0] = 0.5
+        E[n - 1 - t, d - 1 - t] = 1.0
+    return unit(E)
+
+
+def test_hub_and_rows_nobody_lists(engine):
+    """A row that every other row lists first: in-degree n - 1 = 1099, a reverse list longer than a workgroup can be (1024) and than four
+    chunks of KNN_CH sources; and three rows of in-degree 0."""
+    n = 1100
+    idx_h, rev_h = assert_graph_equal(engine, hub_rows(n, 128, 5), (1, 8, 64), (1, 32))
+    indeg = np.diff(rev_h[0])
+    assert (idx_h[1:, 0] == 0).all() and indeg[0] == n - 1
+    assert np.flatnonzero(indeg == 0).tolist() == [n - 3, n - 2, n - 1]
+
+
+def test_nan_row_is_named_and_later_calls_are_clean(engine):
+    n, d = 70, 64
+    E = random_rows(n, d, 11)
+    bad = E.copy()
+    bad[37] = np.nan
+    with pytest.raises(ValueError, match="row 37 ") as info:
+        OC.knn_rows(engine, dev(bad))
+    assert info.value.status == (1, 37)
+    # the lists are written all the same: a NaN cosine ranks as -inf, so every other row lists the NaN row last of all, and their first
+    # entries are those of the restatement on the same input
+    idx_h, cos_h = cluster.knn_rows_host(bad)
+    assert np.array_equal(info.value.idx.cpu().numpy(), idx_h)
+    assert np.array_equal(info.value.cos.cpu().numpy().view(np.int64), cos_h.view(np.int64))
+    assert not (idx_h[np.arange(n) != 37] == 37).any()              # n - 1 > P: the NaN row drops off every list
+    assert_graph_equal(engine, E, (1, 64), (4,))                    # the next problem is not affected
+
+
+def test_two_runs_give_identical_bytes(engine):
+    E = dev(tie_rows(700, 128, 3, distinct=40))
+    X = dev(np.random.default_rng(1).standard_normal((700, 32)).astype(np.float32))
+
+    def run():
+        idx, cos = OC.knn_rows(engine, E)
+        rev = OC.knn_reverse(engine, idx)
+        deg, dinv = OC.knn_degree(engine, rev[0], rev[2], 64, 12)
+        Y = OC.knn_matvec(engine, idx, rev, dinv, 12, X)
+        return [t.cpu().numpy().tobytes() for t in (idx, cos, *rev, deg, dinv, Y)]
+    assert run() == run()
+
+
+def test_refusals(engine):
+    E = dev(random_rows(10, 64, 0))
+    idx, _ = OC.knn_rows(engine, E)
+    rev = OC.knn_reverse(engine, idx)
+    _, dinv = OC.knn_degree(engine, rev[0], rev[2], 9, 3)
+    with pytest.raises(ValueError, match="knn_rows"):
+        OC.knn_rows(engine, E[:1])
+    with pytest.raises(ValueError, match="knn_degree: p="):
+        OC.knn_degree(engine, rev[0], rev[2], 9, 10)
+    with pytest.raises(ValueError, match="knn_matvec: k = 33"):
+        OC.knn_matvec(engine, idx, rev, dinv, 3, torch.zeros((10, 33), device="cuda"))
+    with pytest.raises(ValueError, match="knn_matvec: X must be"):
+        OC.knn_matvec(engine, idx, rev, dinv, 3, torch.zeros((11, 4), device="cuda"))
+    wrong = idx.clone()
+    wrong[4, 2] = 10
+    with pytest.raises(ValueError, match="knn_reverse: row 4 "):
+        OC.knn_reverse(engine, wrong)
