@@ -43,6 +43,7 @@
  *     sdk_diarize_assign_grouped  sdk_diarize_fold_grouped  sdk_diarize_reconstruct_grouped  sdk_diarize_first_seen  sdk_diarize_renumber
  *                                                                                                       speaker diarization (diarize.py)
  *     sdk_score_reference  sdk_score_cooccur  sdk_score_map                                             diarization error rate against a reference (score.py)
+ *     sdk_score_uem  sdk_score_durations  sdk_score_jaccard                                             evaluation maps (UEM) and the Jaccard error rate (score.py)
  *     sdk_words_attribute  sdk_words_cooccur                                                            speaker-attributed transcripts: words onto the diarization
  *                                                                                                       frames, and the word-level error rate's tables (words.py)
  *     sdk_samples_runs_workspace_bytes  sdk_samples_runs  sdk_samples_score_workspace_bytes  sdk_samples_score
@@ -82,7 +83,7 @@
 extern "C" {
 #endif
 
-#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5); still 4 with sdk_cohort_stats* and sdk_affinity_topk_snorm, and with sdk_ecapa_forward_masked, sdk_ecapa_masked_workspace_bytes, sdk_asp_stats_masked_fmt and sdk_asp_pool_masked_fmt, and with sdk_score_reference, sdk_score_cooccur and sdk_score_map, and with sdk_plda_enroll* and sdk_plda_score*, and with sdk_trial_hist, sdk_trial_calib* and sdk_trial_hist_snorm, and with sdk_words_attribute and sdk_words_cooccur, and with sdk_samples_runs* and sdk_samples_score*: new exports only, no struct or existing signature changes, no caller of version 4 breaks */
+#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5); still 4 with sdk_cohort_stats* and sdk_affinity_topk_snorm, and with sdk_ecapa_forward_masked, sdk_ecapa_masked_workspace_bytes, sdk_asp_stats_masked_fmt and sdk_asp_pool_masked_fmt, and with sdk_score_reference, sdk_score_cooccur and sdk_score_map, and with sdk_plda_enroll* and sdk_plda_score*, and with sdk_trial_hist, sdk_trial_calib* and sdk_trial_hist_snorm, and with sdk_words_attribute and sdk_words_cooccur, and with sdk_samples_runs* and sdk_samples_score*, and with sdk_score_uem, sdk_score_durations and sdk_score_jaccard: new exports only, no struct or existing signature changes, no caller of version 4 breaks */
 
 typedef struct sdk_ctx sdk_ctx;
 
@@ -658,6 +659,29 @@ int sdk_score_cooccur(sdk_ctx* ctx, const uint64_t* ref_mask, const uint8_t* sco
                       int64_t co_total, int32_t* co, int64_t* tally, void* stream);
 int sdk_score_map(sdk_ctx* ctx, const int32_t* co, const int32_t* ref_off, const int32_t* cent_off, const int64_t* co_off, int R, int max_ref,
                   int max_hyp, int32_t* map, int64_t* correct, void* stream);
+
+/* ---- scoring the DIHARD way (score.py; csrc/score_jer.hip): the evaluation map (UEM) and the tables of the Jaccard error rate, on the tables of
+ *      the three calls above.  Integer arithmetic only (stores of one value, integer atomic adds, an unsigned 64-bit quotient): bit-identical
+ *      run to run.  In stream order after the calls they follow; no call reads the device on the host.
+ *   sdk_score_uem : after sdk_score_reference.  uem [U][2] int32 (s0, s1; samples), recording r's intervals at uem_off[r] .. uem_off[r + 1]
+ *        (uem_off [R + 1] int32), sorted and disjoint (merged by the caller: score.prepare_uem) -> scored [G] = 0 on every frame whose centre
+ *        270 g + 495 lies in none of its recording's intervals (s0 <= centre < s1); other frames keep what they hold.  A recording that is
+ *        scored everywhere is handed the one interval [0, 2^31 - 1).  U == 0: nothing is scored.
+ *   sdk_score_durations : after sdk_score_uem.  Over the frames with scored != 0: ref_frames [ref_off[R]] int32 = the frames in which
+ *        reference speaker i is active (bit i of ref_mask, i < S_r), hyp_frames [cent_off[R]] int32 = the frames that name hypothesis speaker
+ *        j (an entry of speakers [G][2] >= K_r names nobody; a speaker named twice in a frame counts once).  Both are cleared first.  More
+ *        than 64 speakers a side is refused.
+ *   sdk_score_jaccard : after sdk_score_cooccur and sdk_score_durations.  q (int32, laid out as co: recording r's [S_r][K_r] table at
+ *        co_off[r]) = floor(co[i][j] * 2^30 / (ref_frames[i] + hyp_frames[j] - co[i][j])) in unsigned 64-bit arithmetic where co > 0, else
+ *        0: the Jaccard index of the pair in units of 2^-30, at most 2^30 (co never exceeds ref_frames or hyp_frames).  sdk_score_map then
+ *        runs on q as it stands: its `correct` is the Jaccard sum of the best assignment. */
+int sdk_score_uem(sdk_ctx* ctx, const int32_t* uem, const int32_t* uem_off, const int32_t* frame_off, int R, int U, int64_t G, uint8_t* scored,
+                  void* stream);
+int sdk_score_durations(sdk_ctx* ctx, const uint64_t* ref_mask, const uint8_t* scored, const int32_t* speakers, const int32_t* frame_off,
+                        const int32_t* ref_off, const int32_t* cent_off, int R, int64_t G, int max_ref, int max_hyp, int32_t* ref_frames,
+                        int32_t* hyp_frames, void* stream);
+int sdk_score_jaccard(sdk_ctx* ctx, const int32_t* co, const int32_t* ref_frames, const int32_t* hyp_frames, const int32_t* ref_off,
+                      const int32_t* cent_off, const int64_t* co_off, int R, int64_t co_total, int32_t* q, void* stream);
 
 /* ---- speaker-attributed transcripts (words.py; csrc/words.hip): the words of a transcript onto the per-frame speakers of a diarization, on
  *      the packed frame grid above.  word_off [R + 1] int32: the prefix sums of the recordings' words; frame_off, cent_off, ref_off, co_off as

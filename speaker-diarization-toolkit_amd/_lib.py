@@ -169,6 +169,9 @@ SIGNATURES = {
     "sdk_score_reference": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _i, _vp, _vp, _vp]),
     "sdk_score_cooccur": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i64, _vp, _vp, _vp]),
     "sdk_score_map": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "sdk_score_uem": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _vp]),
+    "sdk_score_durations": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _i, _vp, _vp, _vp]),
+    "sdk_score_jaccard": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp]),
     "sdk_words_attribute": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp, _vp]),
     "sdk_words_cooccur": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp, _vp]),
     "sdk_samples_runs_workspace_bytes": (_sz, [_i64]),

@@ -601,7 +601,8 @@ class Backend(EmbeddingBackend):
         figure.  references: one list of (start_s, end_s, name) per result, or the path or text of an RTTM file (or {uri: turns}) with
         `uris` naming the results' recordings in it.  collar_s: md-eval's collar, on each side of every reference boundary; skip_overlap:
         frames with two or more reference speakers are not scored.  Scored on the device in one pack (score.py states the rule; parity
-        with md-eval and pyannote.metrics is unpinned)."""
+        with md-eval and pyannote.metrics is unpinned).  With an evaluation map (UEM) or the Jaccard error rate: score_diarization_uem
+        below."""
         results = list(results)
         return self.diarizer().score(results, self._references("score_diarization", references, uris, len(results)), collar_s, skip_overlap)
 
@@ -610,13 +611,14 @@ class Backend(EmbeddingBackend):
         score.SweepResult (thresholds, per_recording [T][R], pooled [T], best): the tool for choosing the clustering threshold on a
         development set with weights of your own.  The recordings are embedded and linked once per pack; every threshold costs only the cut,
         the grouped assignment, the stitching and the scoring kernels (diarize.Diarizer.sweep).  Keywords: step_s, min_cluster_size,
-        max_speakers, logp, constrained, collar_s, skip_overlap; clustering="ahc" without speakers= only."""
+        max_speakers, logp, constrained, collar_s, skip_overlap; clustering="ahc" without speakers= only.  uem, jer: as score_diarization's (a
+        UEM file is read with `uris`); metric="der" or "jer": what `best` minimises, the pooled DER or the pooled Jaccard error rate."""
         dz = self.diarizer()
         recs = [decode_to_profile(Path(x), self.engine(), self.get_audio_profile()) if isinstance(x, (str, Path)) else x for x in samples_or_paths]
         refs = self._references("tune_diarization", references, uris, len(recs))
         prec = dz.eng.precision
         try:
-            return dz.sweep(recs, refs, thresholds, **kw)
+            return dz.sweep(recs, refs, thresholds, uris=uris, **kw)
         finally:
             if dz.eng.precision != prec:
                 dz.eng.set_precision(prec)                       # the front end's format goes back to the selected family's contract
@@ -1028,6 +1030,18 @@ def score_words(be: Backend, results, transcripts, max_gap_s: float = 0.5):
     words = [wd.transcript_words(t) for t in transcripts]
     per = wd.wder(be.engine(), results, words, [[w[3] for w in ws] for ws in words], max_gap_s)
     return per, wd.pool(per)
+
+
+# ---- scoring the DIHARD way (score.py).  A function of the backend for the same reason: Backend.score_diarization keeps its signature.
+def score_diarization_uem(be: Backend, results, references, uris=None, collar_s: float = 0.0, skip_overlap: bool = False, uem=None, jer: bool = False):
+    """Backend.score_diarization with an evaluation map and the Jaccard error rate.  uem: the map outside which nothing is scored - one
+    entry per result (None, or a list of (start_s, end_s)), or the path or text of a UEM file (or {uri: intervals}) read with `uris`; a
+    uri it does not hold is scored everywhere.  jer=True: every score.DerResult carries the Jaccard error rate (jer, jsum, ref_speakers,
+    ref_frames, hyp_frames, jer_mapping), purity and coverage beside the DER; score.pool(list) pools them too.  With uem=None and
+    jer=False it is score_diarization.  Backend.tune_diarization takes the same two keywords, and metric="jer"."""
+    results = list(results)
+    return be.diarizer().score(results, be._references("score_diarization_uem", references, uris, len(results)), collar_s, skip_overlap,
+                               uem=uem, jer=jer, uris=uris)
 
 
 # ---- speaker samples (samples.py).  Functions of the backend for the same reason.

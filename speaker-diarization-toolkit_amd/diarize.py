@@ -80,11 +80,15 @@ tests pin these rules.
   score       (Diarizer.score, Backend.score_diarization) how good a result is: the diarization error rate of results against reference
               annotations (turn lists, or RTTM), on this frame grid.  The results' speakers tables are scored on the device as one pack -
               reference masks, co-occurrence tallies and the exact reference-to-hypothesis assignment in three integer kernels
-              (csrc/score.hip).  The rule, its numpy restatement (score_host) and the RTTM reader are score.py's.
+              (csrc/score.hip).  The rule, its numpy restatement (score_host) and the RTTM reader are score.py's.  Opt-in, the DIHARD way
+              (csrc/score_jer.hip): uem= scores only inside each recording's evaluation map (a UEM file, or interval lists), jer=True adds
+              the Jaccard error rate - every reference speaker weighing the same - with purity and coverage; integers on the device, the
+              same one download.
   sweep       (Diarizer.sweep, Backend.tune_diarization) the DER of run_many at many thresholds, for tuning the cut on a development set:
               per pack one embedding and one linkage (_pack_link), then per threshold the cut-to-centroids stage (_pack_cut), the grouped
               assignment and stitching, and the scoring kernels on the hypothesis where it lies; every threshold's tallies come down in one
-              download per pack.  clustering="ahc" without speaker bounds only; run_many is not changed by it.
+              download per pack.  clustering="ahc" without speaker bounds only; run_many is not changed by it.  uem= and jer= as score's,
+              without a further wait per pack; metric="jer" picks `best` by the pooled JER instead of the pooled DER.
   shared      run and run_many are one pipeline: Diarizer._check_options, _check_recording, _embed_all (the batches of embed_chunks) and
               _empty serve both, as do candidate_mask, training_mask and _speaker_cap; after the embedding run clusters one recording and
               run_many takes the pack through _pack_begin, _pack_vbx or _pack_ahc, _pack_assign and _pack_results.  They differ on purpose in
@@ -390,23 +394,30 @@ class Diarizer:
         return xs, split_packs([x.size for x in xs], n_chunks)
 
     # ---------------------------------------------------------------------------------------------- scoring against a reference, threshold sweep
-    def score(self, results, references, collar_s: float = 0.0, skip_overlap: bool = False):
+    def score(self, results, references, collar_s: float = 0.0, skip_overlap: bool = False, uem=None, jer: bool = False, uris=None):
         """DiarizationResults (run's, run_many's or a finished stream's) and one reference turn list [(start_s, end_s, name)] per result ->
-        one score.DerResult per result: their `speakers` are uploaded and scored on the device as one pack (score.py states the rule)."""
-        from .score import score_results
-        return score_results(self.eng, results, references, collar_s, skip_overlap)
+        one score.DerResult per result: their `speakers` are uploaded and scored on the device as one pack (score.py states the rule).
+        uem: one entry per result (None, or the [(start_s, end_s)] outside which nothing is scored), or a UEM path or text with `uris` naming
+        the results' recordings in it.  jer=True: the Jaccard error rate, purity and coverage too (the result's fields from jer on)."""
+        from .score import resolve_uems, score_results
+        results = list(results)
+        return score_results(self.eng, results, references, collar_s, skip_overlap, resolve_uems("score", uem, uris, len(results)), jer)
 
     def sweep(self, recordings, references, thresholds, step_s: float = 1.0, min_cluster_size: int = PYANNOTE_MIN_CLUSTER_SIZE,
               max_speakers: Optional[int] = None, logp=None, constrained: bool = False, collar_s: float = 0.0, skip_overlap: bool = False,
-              clustering: str = "ahc", speakers=None):
+              clustering: str = "ahc", speakers=None, uem=None, jer: bool = False, metric: str = "der", uris=None):
         """The DER of run_many(recordings, threshold=t, ...) against `references` for every t of `thresholds` -> score.SweepResult
         (thresholds, per_recording [T][R], pooled [T], best).  Per pack the recordings are embedded ONCE and linked ONCE (_pack_embed,
         _pack_link); per threshold only the cheap tail runs - cut on host integers, fold, centroids, assignment, stitching, renumbering and
         second stitching exactly as run_many's (_pack_cut, _pack_assign_dev), then the three scoring kernels on the hypothesis where it
         lies.  The tallies of all thresholds stay on the device and come down in one download per pack: the waits per pack (last_sync) do
         not grow with the number of thresholds.  Only clustering="ahc" without speaker bounds: the sweep is over the cut of the linkage.
-        A recording that the cut splits into more than score.MAX_SCORE_SPEAKERS speakers at some threshold is a ValueError."""
-        from .score import SweepResult, best_threshold, pool, rasterise_references, results_from_tables, score_host, score_tables, split_tables
+        A recording that the cut splits into more than score.MAX_SCORE_SPEAKERS speakers at some threshold is a ValueError.
+        uem, jer, uris: as score's; the UEM intervals ride in the reference's upload and the Jaccard tables in the one download, so the waits
+        per pack stay what they are.  metric: "der" or "jer" (which computes the JER whatever jer says) - what `best` minimises."""
+        from .score import (SweepResult, best_threshold, check_metric, jer_download_size, join_tables, pool, rasterise_references, resolve_uems,
+                            results_from_tables, results_from_tables_jer, score_host, score_tables, split_tables, split_tables_jer)
+        jer = bool(jer) or check_metric("sweep", metric) == "jer"
         if clustering != "ahc" or speakers is not None:
             raise ValueError(f"sweep: clustering={clustering!r}, speakers={speakers!r}: the sweep is over the cut of clustering=\"ahc\" with speakers=None")
         vbx, bounds = self._check_options("sweep", clustering, None, max_speakers, None)
@@ -417,20 +428,21 @@ class Diarizer:
         references = list(references)
         if len(references) != len(recordings):
             raise ValueError(f"sweep: {len(references)} references for {len(recordings)} recordings")
+        uems = resolve_uems("sweep", uem, uris, len(recordings))
         xs, packs = self._plan_packs(recordings, logp, step_s)
         per = [[None] * len(xs) for _ in ths]
         self.last_sync = []
         for idx in packs:
-            refs = [references[i] for i in idx]
+            refs, pack_uems = [references[i] for i in idx], None if uems is None else [uems[i] for i in idx]
             p = self._pack_begin([xs[i] for i in idx], None if logp is None else [logp[i] for i in idx], opts)
             if p is None:                                         # nothing but empty recordings: no frame to score
                 for t in range(len(ths)):
-                    for i, ref in zip(idx, refs):
-                        per[t][i] = score_host(np.zeros((0, 2), np.int32), 0, ref, collar_s, skip_overlap)
+                    for k, (i, ref) in enumerate(zip(idx, refs)):
+                        per[t][i] = score_host(np.zeros((0, 2), np.int32), 0, ref, collar_s, skip_overlap, None if uems is None else pack_uems[k], jer)
                 continue
             torch, tab = _native()[0], p.tab
             linkage = self._pack_link(p)
-            ref = rasterise_references(self.eng, tab, refs, collar_s, skip_overlap, upload=self._up)
+            ref = rasterise_references(self.eng, tab, refs, collar_s, skip_overlap, upload=self._up, uems=pack_uems)
             self._mark("reference")
             held, shapes = [], []
             for t in ths:
@@ -439,22 +451,26 @@ class Diarizer:
                 self._mark("cut_fold_centroids")
                 spk_dev = self._pack_assign_dev(p, cl, opts)[4]
                 self._mark("assign_stitch")
-                tally, correct, mapping, co, co_off = score_tables(self.eng, spk_dev, tab, ref, upload=self._up)
-                held += [tally.reshape(-1), correct, mapping.to(torch.int64), co.to(torch.int64)]
-                shapes.append((cl.cent_off, co_off))
+                tables = score_tables(self.eng, spk_dev, tab, ref, upload=self._up, jer=jer)
+                held += join_tables(tables[:4] + tables[5:])
+                shapes.append((cl.cent_off, tables[4]))
                 self._mark("score")
             p.sync["uploads"] += tab.uploads
             flat = self._down(torch.cat(held))                    # every threshold's tallies, tables and maps: ONE download
-            pos = 0
+            pos, n_ref = 0, int(ref.ref_off[-1])
             for t, (cent_off, co_off) in enumerate(shapes):
-                n = 6 * tab.R + int(ref.ref_off[-1]) + int(co_off[-1])
-                res = results_from_tables(ref, cent_off, co_off, *split_tables(flat[pos:pos + n], tab.R, int(ref.ref_off[-1]), int(co_off[-1])))
+                if jer:
+                    n = jer_download_size(tab.R, n_ref, int(cent_off[-1]), int(co_off[-1]))
+                    res = results_from_tables_jer(ref, cent_off, co_off, *split_tables_jer(flat[pos:pos + n], tab.R, n_ref, int(cent_off[-1]), int(co_off[-1])))
+                else:
+                    n = 6 * tab.R + n_ref + int(co_off[-1])
+                    res = results_from_tables(ref, cent_off, co_off, *split_tables(flat[pos:pos + n], tab.R, n_ref, int(co_off[-1])))
                 pos += n
                 for i, one in zip(idx, res):
                     per[t][i] = one
             self._mark("download")
         pooled = [pool(row) for row in per]
-        return SweepResult(ths, per, pooled, best_threshold(ths, pooled))
+        return SweepResult(ths, per, pooled, best_threshold(ths, pooled, metric))
 
     # ---------------------------------------------------------------------------------------------- labelled rows for training a PLDA
     def plda_rows(self, samples_list, references, step_s: float = 1.0, logp=None) -> dict:

@@ -14,8 +14,14 @@ tests pin this rule.
               nref(g) = the number of active reference speakers
   scored      every frame of the recording, with two exceptions.  collar_s > 0: with c = floor(collar_s * 16000 + 0.5), a frame is not scored
               if some boundary b (an s0 or s1 of a merged reference turn) has |270 g + 495 - b| < c - md-eval's convention, the collar
-              applies on each side of the boundary.  skip_overlap=True: a frame with nref >= 2 is not scored.  No UEM files.
-  tallies     over the scored frames, all integers: scored (frames), total = sum nref, missed = sum max(0, nref - nhyp), false_alarm =
+              applies on each side of the boundary.  skip_overlap=True: a frame with nref >= 2 is not scored.  A UEM (below) removes more.
+  UEM         (opt-in: uem=) the un-partitioned evaluation map that DIHARD, AMI and VoxConverse distribute: per recording None (every frame
+              is eligible) or a list of (start_s, end_s) (prepare_uem): seconds to samples as above, intervals sorted and merged where they
+              overlap or abut (a join when s0 <= the running s1), then intervals with s1 <= s0 dropped.  Frame g is eligible iff one merged
+              interval has s0 <= 270 g + 495 < s1; scored becomes the above AND eligible.  The collar still measures from the reference
+              boundaries, whatever the UEM.  An empty list scores nothing; an interval may run past the recording's end.  parse_uem reads
+              `<uri> <channel> <start> <end>` lines; a uri the file does not hold gets None (uems_for)
+  tallies    over the scored frames, all integers: scored (frames), total = sum nref, missed = sum max(0, nref - nhyp), false_alarm =
               sum max(0, nhyp - nref), both = sum min(nref, nhyp), co[i, j] = the frames in which reference i and hypothesis j are both
               active
   mapping     correct = the maximum of sum co[i, m(i)] over maps m that give some reference speakers pairwise different hypothesis speakers
@@ -23,14 +29,30 @@ tests pin this rule.
               unmapped (-1); confusion = both - correct.  correct is unique even where the map is not, so every tally is unique
   DER         der = (missed + false_alarm + confusion) / total; with total == 0 it is 0.0 when there is no error, else inf.  Pooled over
               recordings (pool): the ratio of the sums.  Durations are frames * 270 / 16000 s
-  limits      at most MAX_SCORE_SPEAKERS = 64 reference and 64 hypothesis speakers per recording: more is a ValueError here and refused by
+  JER         (opt-in: jer=True) DIHARD's Jaccard error rate, every reference speaker weighing the same; it follows dscore as published.
+              Over the scored frames ref_frames[i] = the frames with reference i active, hyp_frames[j] = the frames that name hypothesis j
+              (a name >= K counts for nobody, a name twice in a frame counts once, as in co).  The Jaccard table, int32:
+              q[i, j] = floor(co[i, j] * 2^30 / (ref_frames[i] + hyp_frames[j] - co[i, j])) where co[i, j] > 0, else 0, in unsigned 64-bit
+              arithmetic (the numerator reaches 2^61, the denominator passes 2^31); its largest value is exactly 2^30.  jsum = the
+              maximum-weight assignment on q (the mapping rule above, run on q as it stands), jer_mapping a map that attains it; S' = the
+              reference speakers with ref_frames > 0; jer = 1 - jsum / (2^30 S'), and with S' == 0 it is 0.0 when no hyp_frames is positive,
+              else 1.0.  Pooled: 1 - sum jsum / (2^30 sum S'), the mean over all reference speakers of all recordings (recordings with
+              S' == 0 add nothing to either sum; if sum S' == 0 the pooled value is 0.0 unless one of them had 1.0).  jsum is unique where
+              the map is not.  Each q / 2^30 lies within 2^-30 BELOW the true Jaccard index, so jer lies within 2^-30 of the exact rational
+              optimum (above it: at most S' pairs, each short by less than 2^-30, divided by S')
+  purity      (with jer=True, on the host from the downloaded integers) coverage = sum_i max_j co[i, j] / sum_i ref_frames[i], purity =
+              sum_j max_i co[i, j] / sum_j hyp_frames[j]; each is 1.0 when its denominator is 0; pooled: the ratios of the sums
+  limits     at most MAX_SCORE_SPEAKERS = 64 reference and 64 hypothesis speakers per recording: more is a ValueError here and refused by
               the library
 
 The device path is three calls in stream order on the prefix-sum tables of diarize_ops.GroupTables (csrc/score.hip): sdk_score_reference
 (reference turns -> a 64-bit speaker mask and a scored flag per frame), sdk_score_cooccur (masks and speakers -> co and the tallies, summed per
 workgroup in LDS, then integer atomics) and sdk_score_map (one wave per recording: shortest augmenting paths with int64 potentials).  Only
 integers, OR and integer adds: the results do not depend on any order and are bit-identical run to run.  The *_host functions restate the three
-kernels in numpy; score_host joins them for one recording.
+kernels in numpy; score_host joins them for one recording.  The opt-in parts add calls of csrc/score_jer.hip in the same stream: sdk_score_uem
+(a frame's recording and its interval by two binary searches) behind sdk_score_reference, and for jer=True sdk_score_durations (the walk of
+sdk_score_cooccur with 64 + 64 counters), sdk_score_jaccard (one thread per cell, an unsigned 64-bit quotient) and sdk_score_map again, on
+the Jaccard table.  Integers too, and the same one download.  With uem=None and jer=False no call is added and every result is what it was.
 """
 from __future__ import annotations
 
@@ -48,6 +70,8 @@ from .segmentation import FRAME_HOP, SAMPLE_RATE
 MAX_SCORE_SPEAKERS = 64
 FRAME_FIRST = 495                # centre sample of frame 0
 _INF = 1 << 62
+JACCARD_ONE = 1 << 30            # the Jaccard table's unit: q / 2^30 is the index
+UEM_EVERYTHING = (0, (1 << 31) - 1)   # the interval a recording without a UEM is handed on the device
 
 
 @dataclass
@@ -61,6 +85,16 @@ class DerResult:
     der: float
     mapping: Dict[object, int]                # reference name -> hypothesis speaker, -1: unmapped ({} for a pooled result)
     co: Optional[np.ndarray]                  # [S, K] int32 co-occurrence (None for a pooled result)
+    # With jer=True (None otherwise; the positional constructor above keeps working):
+    jer: Optional[float] = None
+    jsum: Optional[int] = None                # the Jaccard sum of the best assignment, in units of 2^-30
+    ref_speakers: Optional[int] = None        # S': the reference speakers with ref_frames > 0
+    ref_frames: Optional[np.ndarray] = None   # [S] int32 (None for a pooled result)
+    hyp_frames: Optional[np.ndarray] = None   # [K] int32 (None for a pooled result)
+    jer_mapping: Optional[Dict[object, int]] = None   # reference name -> hypothesis speaker under the Jaccard assignment ({} for a pooled result)
+    purity: Optional[float] = None
+    coverage: Optional[float] = None
+    pc_sums: Optional[Tuple[int, int, int, int]] = None   # purity's numerator and denominator, then coverage's: what pool adds up
 
     @property
     def scored_s(self) -> float:
@@ -76,7 +110,7 @@ class SweepResult:
     thresholds: List[float]
     per_recording: List[List[DerResult]]      # [T][R]
     pooled: List[DerResult]                   # [T]
-    best: int                                 # index of the least pooled DER; ties to the threshold nearest PYANNOTE_THRESHOLD, then the lower
+    best: int                                 # index of the least pooled DER (metric="jer": JER); ties to the threshold nearest PYANNOTE_THRESHOLD, then the lower
 
 
 def der_value(total: int, missed: int, false_alarm: int, confusion: int) -> float:
@@ -86,15 +120,37 @@ def der_value(total: int, missed: int, false_alarm: int, confusion: int) -> floa
     return err / int(total)
 
 
+def jer_value(jsum: int, ref_speakers: int, any_hyp: bool = False) -> float:
+    """jsum in units of 2^-30 and S' -> 1 - jsum / (2^30 S'); with S' == 0: 1.0 if a hypothesis speaker holds a scored frame, else 0.0."""
+    if ref_speakers == 0:
+        return 1.0 if any_hyp else 0.0
+    return 1.0 - int(jsum) / (JACCARD_ONE * int(ref_speakers))
+
+
 def pool(results: Sequence[DerResult]) -> DerResult:
-    """The summed tallies of many recordings and the ratio of the sums; mapping {} and co None (not comparable across recordings)."""
+    """The summed tallies of many recordings and the ratio of the sums; mapping {} and co None (not comparable across recordings).  Where
+    every result carries them, jsum and ref_speakers are summed too (jer: "JER" in the module docstring), and so are purity's and coverage's
+    numerators and denominators."""
     s = [sum(int(getattr(r, f)) for r in results) for f in ("scored", "total", "missed", "false_alarm", "confusion", "correct")]
-    return DerResult(*s, der_value(s[1], s[2], s[3], s[4]), {}, None)
+    out = DerResult(*s, der_value(s[1], s[2], s[3], s[4]), {}, None)
+    if results and all(r.jsum is not None and r.ref_speakers is not None for r in results):
+        out.jsum, out.ref_speakers = sum(int(r.jsum) for r in results), sum(int(r.ref_speakers) for r in results)
+        out.jer, out.jer_mapping = jer_value(out.jsum, out.ref_speakers, any(r.ref_speakers == 0 and r.jer == 1.0 for r in results)), {}
+    if results and all(r.pc_sums is not None for r in results):
+        out.pc_sums = tuple(sum(int(r.pc_sums[k]) for r in results) for k in range(4))
+        out.purity, out.coverage = _ratio(*out.pc_sums[:2]), _ratio(*out.pc_sums[2:])
+    return out
 
 
-def best_threshold(thresholds: Sequence[float], pooled: Sequence[DerResult]) -> int:
+def best_threshold(thresholds: Sequence[float], pooled: Sequence[DerResult], metric: str = "der") -> int:
     from .cluster import PYANNOTE_THRESHOLD
-    return min(range(len(thresholds)), key=lambda t: (pooled[t].der, abs(float(thresholds[t]) - PYANNOTE_THRESHOLD), float(thresholds[t])))
+    return min(range(len(thresholds)), key=lambda t: (getattr(pooled[t], metric), abs(float(thresholds[t]) - PYANNOTE_THRESHOLD), float(thresholds[t])))
+
+
+def check_metric(who: str, metric: str) -> str:
+    if metric not in ("der", "jer"):
+        raise ValueError(f"{who}: metric={metric!r} (\"der\" or \"jer\")")
+    return metric
 
 
 # ------------------------------------------------------------------------------------------------ RTTM and the reference on the host
@@ -122,11 +178,7 @@ def references_for(rttm, uris: Sequence[str]) -> List[List[Tuple[float, float, s
     if isinstance(rttm, dict):
         table = rttm
     else:
-        text = os.fspath(rttm)
-        if "\n" not in text and os.path.exists(text):
-            with open(text, "r", encoding="utf-8") as fh:
-                text = fh.read()
-        table = parse_rttm(text)
+        table = parse_rttm(_text_of(rttm))
     missing = [u for u in uris if u not in table]
     if missing:
         raise ValueError(f"score: the reference holds no uri {missing[:4]} (it has {sorted(table)[:8]})")
@@ -137,6 +189,78 @@ def to_samples(t: float) -> int:
     if not (t == t and 0.0 <= t and t * SAMPLE_RATE + 0.5 < float(1 << 31)):
         raise ValueError(f"score: time {t} s (finite, >= 0 and below 2^31 samples)")
     return int(math.floor(float(t) * SAMPLE_RATE + 0.5))
+
+
+def _text_of(source) -> str:
+    """A path, or the text itself (anything with a line break, or that names no file)."""
+    text = os.fspath(source)
+    if "\n" not in text and os.path.exists(text):
+        with open(text, "r", encoding="utf-8") as fh:
+            text = fh.read()
+    return text
+
+
+def parse_uem(text: str) -> Dict[str, List[Tuple[float, float]]]:
+    """UEM text -> {uri: [(start_s, end_s)]} in file order: lines of `<uri> <channel> <start> <end>`; blank lines and lines that start with
+    `;` are ignored."""
+    out: Dict[str, List[Tuple[float, float]]] = {}
+    for n, line in enumerate(text.splitlines(), 1):
+        f = line.split()
+        if not f or f[0].startswith(";"):
+            continue
+        if len(f) < 4:
+            raise ValueError(f"parse_uem: line {n}: a UEM line has 4 fields (uri, channel, start, end), got {len(f)}")
+        try:
+            start, end = float(f[2]), float(f[3])
+        except ValueError:
+            raise ValueError(f"parse_uem: line {n}: start {f[2]!r} and end {f[3]!r} must be numbers") from None
+        out.setdefault(f[0], []).append((start, end))
+    return out
+
+
+def uems_for(uem, uris: Sequence[str]) -> List[Optional[List[Tuple[float, float]]]]:
+    """A UEM path or text (or a {uri: intervals} dict) and the recordings' uris, in order -> one interval list per recording; a uri the map
+    does not hold gets None (scored everywhere), unlike references_for."""
+    table = uem if isinstance(uem, dict) else parse_uem(_text_of(uem))
+    return [list(table[u]) if u in table else None for u in uris]
+
+
+def resolve_uems(who: str, uem, uris, n: int):
+    """The uem= keyword of the public calls -> None, or one entry (None or an interval list) per recording: a list of n entries, or a UEM
+    path / text / {uri: intervals} with the recordings' uris."""
+    if uem is None:
+        return None
+    if isinstance(uem, (str, os.PathLike, dict)):
+        if uris is None or len(uris) != n:
+            raise ValueError(f"{who}: a UEM file needs uris, one per recording ({n}), got {None if uris is None else len(uris)}")
+        return uems_for(uem, list(uris))
+    uem = list(uem)
+    if len(uem) != n:
+        raise ValueError(f"{who}: {len(uem)} UEM entries for {n} recordings")
+    return uem
+
+
+def prepare_uem(uem) -> np.ndarray:
+    """None or [(start_s, end_s)] -> the merged intervals [U, 2] int32 (s0, s1) in samples, sorted and disjoint: "UEM" in the module
+    docstring.  None gives the one interval UEM_EVERYTHING, an empty list no interval."""
+    if uem is None:
+        return np.asarray([UEM_EVERYTHING], dtype=np.int32)
+    rows = []
+    for s0, s1 in sorted((to_samples(a), to_samples(b)) for a, b in uem):
+        if rows and s0 <= rows[-1][1]:
+            rows[-1][1] = max(rows[-1][1], s1)
+        else:
+            rows.append([s0, s1])
+    return np.asarray([row for row in rows if row[1] > row[0]], dtype=np.int32).reshape(-1, 2)
+
+
+def uem_mask_host(intervals: np.ndarray, G: int) -> np.ndarray:
+    """sdk_score_uem for one recording in numpy: prepare_uem's intervals [U, 2], G frames -> eligible [G] uint8."""
+    eligible = np.zeros(G, np.uint8)
+    for s0, s1 in np.asarray(intervals, dtype=np.int64).reshape(-1, 2):
+        if s1 > s0:
+            eligible[int(_first_frame(s0)):min(int(_first_frame(s1)), G)] = 1
+    return eligible
 
 
 def collar_samples(collar_s: float) -> int:
@@ -246,11 +370,56 @@ def assignment_host(co: np.ndarray):
     return out, correct
 
 
-def _result(names, co, tally, mapping, correct) -> DerResult:
+def durations_host(ref_mask: np.ndarray, scored: np.ndarray, speakers: np.ndarray, S: int, K: int):
+    """sdk_score_durations for one recording in numpy -> (ref_frames [S] int32, hyp_frames [K] int32) over the scored frames."""
+    on = np.asarray(scored).astype(bool)
+    mask, sp = np.asarray(ref_mask, dtype=np.uint64)[on], np.asarray(speakers, dtype=np.int64).reshape(-1, 2)[on]
+    ref = (mask[:, None] >> np.arange(S, dtype=np.uint64)[None, :]) & np.uint64(1)                              # [frames, S]
+    hyp = (sp[:, :, None] == np.arange(K)[None, None, :]).any(1)                                               # [frames, K]: named twice counts once
+    return ref.sum(0).astype(np.int32).reshape(S), hyp.sum(0).astype(np.int32).reshape(K)
+
+
+def jaccard_table_host(co: np.ndarray, ref_frames: np.ndarray, hyp_frames: np.ndarray) -> np.ndarray:
+    """sdk_score_jaccard for one recording: co [S, K], ref_frames [S], hyp_frames [K] -> q [S, K] int32 in units of 2^-30.  Python integers:
+    the numerator passes 2^53.  A denominator of 0 (tables that are no co-occurrence of these durations) gives 0, as on the device."""
+    co = np.asarray(co, dtype=np.int64)
+    q = np.zeros(co.shape, np.int32)
+    for i, j in zip(*np.nonzero(co > 0)):
+        den = int(ref_frames[i]) + int(hyp_frames[j]) - int(co[i, j])
+        q[i, j] = (int(co[i, j]) << 30) // den if den else 0
+    return q
+
+
+def _ratio(num: int, den: int) -> float:
+    return int(num) / int(den) if den else 1.0
+
+
+def _pc_sums(co, ref_frames, hyp_frames) -> Tuple[int, int, int, int]:
+    co = np.asarray(co, dtype=np.int64)
+    return (int(co.max(0).sum()) if co.size else 0, int(np.asarray(hyp_frames, dtype=np.int64).sum()),
+            int(co.max(1).sum()) if co.size else 0, int(np.asarray(ref_frames, dtype=np.int64).sum()))
+
+
+def purity_coverage(co: np.ndarray, ref_frames: np.ndarray, hyp_frames: np.ndarray) -> Tuple[float, float]:
+    """"purity" in the module docstring -> (purity, coverage)."""
+    s = _pc_sums(co, ref_frames, hyp_frames)
+    return _ratio(*s[:2]), _ratio(*s[2:])
+
+
+def _result(names, co, tally, mapping, correct, jer=None) -> DerResult:
+    """jer: None, or (ref_frames [S], hyp_frames [K], jsum, jer_mapping [S]) as sdk_score_durations and sdk_score_map on q leave them."""
     scored, total, missed, fa, both = (int(x) for x in tally)
     conf = both - int(correct)
-    return DerResult(scored, total, missed, fa, conf, int(correct), der_value(total, missed, fa, conf),
-                     {name: int(mapping[i]) for i, name in enumerate(names)}, np.asarray(co, dtype=np.int32))
+    out = DerResult(scored, total, missed, fa, conf, int(correct), der_value(total, missed, fa, conf),
+                    {name: int(mapping[i]) for i, name in enumerate(names)}, np.asarray(co, dtype=np.int32))
+    if jer is not None:
+        out.ref_frames, out.hyp_frames = np.asarray(jer[0], dtype=np.int32), np.asarray(jer[1], dtype=np.int32)
+        out.jsum, out.ref_speakers = int(jer[2]), int((out.ref_frames > 0).sum())
+        out.jer = jer_value(out.jsum, out.ref_speakers, bool((out.hyp_frames > 0).any()))
+        out.jer_mapping = {name: int(jer[3][i]) for i, name in enumerate(names)}
+        out.pc_sums = _pc_sums(out.co, out.ref_frames, out.hyp_frames)
+        out.purity, out.coverage = _ratio(*out.pc_sums[:2]), _ratio(*out.pc_sums[2:])
+    return out
 
 
 def _check_counts(who: str, S: int, K: int):
@@ -258,9 +427,10 @@ def _check_counts(who: str, S: int, K: int):
         raise ValueError(f"{who}: {S} reference and {K} hypothesis speakers; at most {MAX_SCORE_SPEAKERS} of each per recording")
 
 
-def score_host(speakers, n_samples: int, reference, collar_s: float = 0.0, skip_overlap: bool = False) -> DerResult:
+def score_host(speakers, n_samples: int, reference, collar_s: float = 0.0, skip_overlap: bool = False, uem=None, jer: bool = False) -> DerResult:
     """One recording on the host: speakers [G, 2] int32 (a DiarizationResult's), its n_samples and the reference turns -> DerResult.  The
-    numpy restatement of the three kernels; K is the largest speaker named, plus one."""
+    numpy restatement of the kernels; K is the largest speaker named, plus one.  uem: None or the recording's [(start_s, end_s)]; jer=True
+    fills the result's fields from jer on."""
     sp = np.asarray(speakers, dtype=np.int32).reshape(-1, 2)
     G = global_frames(n_samples)
     if sp.shape[0] != G:
@@ -269,9 +439,15 @@ def score_host(speakers, n_samples: int, reference, collar_s: float = 0.0, skip_
     S, K = len(names), (int(sp.max()) + 1 if sp.size else 0)
     _check_counts("score_host", S, max(K, 0))
     mask, scored = reference_masks_host(merged, G, collar_samples(collar_s), bool(skip_overlap))
+    if uem is not None:
+        scored &= uem_mask_host(prepare_uem(uem), G)
     co, tally = cooccur_host(mask, scored, sp, S, max(K, 0))
     mapping, correct = assignment_host(co)
-    return _result(names, co, tally, mapping, correct)
+    if not jer:
+        return _result(names, co, tally, mapping, correct)
+    ref_frames, hyp_frames = durations_host(mask, scored, sp, S, max(K, 0))
+    jer_mapping, jsum = assignment_host(jaccard_table_host(co, ref_frames, hyp_frames))
+    return _result(names, co, tally, mapping, correct, (ref_frames, hyp_frames, jsum, jer_mapping))
 
 
 # ------------------------------------------------------------------------------------------------ the device path
@@ -285,12 +461,15 @@ class PackReference:
     scored = None                # [G] uint8
 
 
-def rasterise_references(eng, tab, references, collar_s: float = 0.0, skip_overlap: bool = False, upload=None) -> PackReference:
+def rasterise_references(eng, tab, references, collar_s: float = 0.0, skip_overlap: bool = False, upload=None, uems=None) -> PackReference:
     """One turn list per recording of the pack (tab: diarize_ops.GroupTables) -> PackReference: sdk_score_reference.  upload: what carries the
-    one table of host integers to the device (a caller that counts its transfers passes its own)."""
+    one table of host integers to the device (a caller that counts its transfers passes its own).  uems: None, or per recording None or its
+    [(start_s, end_s)]: the merged intervals ride in the same upload and sdk_score_uem runs behind sdk_score_reference."""
     torch, check, _stream = _native()
     if len(references) != tab.R:
         raise ValueError(f"score: {len(references)} references for {tab.R} recordings")
+    if uems is not None and len(uems) != tab.R:
+        raise ValueError(f"score: {len(uems)} UEM entries for {tab.R} recordings")
     collar = collar_samples(collar_s)
     prepared = [prepare_reference(t) for t in references]
     ref = PackReference()
@@ -303,22 +482,37 @@ def rasterise_references(eng, tab, references, collar_s: float = 0.0, skip_overl
     M, R = int(turn_off[-1]), tab.R
     if M >= (1 << 28):
         raise ValueError(f"score: {M} reference turns in one pack (fewer than 2^28)")
-    table = np.concatenate([turn_off, ref.ref_off] + [m.reshape(-1) for m, _ in prepared]).astype(np.int32)
+    parts = [turn_off, ref.ref_off] + [m.reshape(-1) for m, _ in prepared]
+    if uems is not None:
+        merged_uem = [prepare_uem(u) for u in uems]
+        uem_off = np.concatenate([[0], np.cumsum([len(m) for m in merged_uem])]).astype(np.int64)
+        U = int(uem_off[-1])
+        if U >= (1 << 28):
+            raise ValueError(f"score: {U} UEM intervals in one pack (fewer than 2^28)")
+        parts += [uem_off] + [m.reshape(-1) for m in merged_uem]
+    table = np.concatenate(parts).astype(np.int32)
     up = (upload or (lambda a: torch.from_numpy(a).to(eng.device)))(table)                                   # one upload
-    turn_off_d, ref.ref_off_d, turns_d = up[:R + 1], up[R + 1:2 * R + 2], up[2 * R + 2:]
+    turn_off_d, ref.ref_off_d, turns_d = up[:R + 1], up[R + 1:2 * R + 2], up[2 * R + 2:2 * R + 2 + 3 * M]
     ref.ref_mask = torch.empty((max(tab.G, 1),), dtype=torch.int64, device=eng.device)
     ref.scored = torch.empty((max(tab.G, 1),), dtype=torch.uint8, device=eng.device)
     check(eng.lib.sdk_score_reference(eng.ctx, turns_d.data_ptr() if M else None, turn_off_d.data_ptr(), tab.frame_off_d.data_ptr(), ref.ref_off_d.data_ptr(),
                                       R, M, tab.G, ref.max_ref, collar, int(bool(skip_overlap)), ref.ref_mask.data_ptr(), ref.scored.data_ptr(), _stream()),
           "sdk_score_reference")
+    if uems is not None:
+        a = 2 * R + 2 + 3 * M
+        uem_off_d, uem_d = up[a:a + R + 1], up[a + R + 1:]
+        check(eng.lib.sdk_score_uem(eng.ctx, uem_d.data_ptr() if U else None, uem_off_d.data_ptr(), tab.frame_off_d.data_ptr(), R, U, tab.G,
+                                    ref.scored.data_ptr(), _stream()), "sdk_score_uem")
     ref.ref_mask, ref.scored = ref.ref_mask[:tab.G], ref.scored[:tab.G]
     return ref
 
 
-def score_tables(eng, speakers_dev, tab, ref: PackReference, upload=None):
+def score_tables(eng, speakers_dev, tab, ref: PackReference, upload=None, jer: bool = False):
     """speakers [G, 2] int32 on the packed grid (device), tab with clusters set (K_r = the hypothesis speakers of recording r) ->
     (tally [R, 5] int64, correct [R] int64, map [sum S_r] int32, co int32 [co_off[-1]], co_off [R + 1] int64 on the host), the first four
-    on the device: sdk_score_cooccur, then sdk_score_map.  Nothing is read back."""
+    on the device: sdk_score_cooccur, then sdk_score_map.  Nothing is read back.  jer=True appends (ref_frames [sum S_r] int32, hyp_frames
+    [sum K_r] int32, jsum [R] int64, jer_mapping [sum S_r] int32), all on the device: sdk_score_durations, sdk_score_jaccard, then
+    sdk_score_map on the Jaccard table."""
     torch, check, _stream = _native()
     if tab.cent_off is None:
         raise ValueError("score: the tables hold no clusters (set_clusters)")
@@ -338,7 +532,23 @@ def score_tables(eng, speakers_dev, tab, ref: PackReference, upload=None):
                                     co_off_d.data_ptr(), R, tab.G, ref.max_ref, max_hyp, total, co.data_ptr(), tally.data_ptr(), _stream()), "sdk_score_cooccur")
     check(eng.lib.sdk_score_map(eng.ctx, co.data_ptr(), ref.ref_off_d.data_ptr(), tab.cent_off_d.data_ptr(), co_off_d.data_ptr(), R, ref.max_ref, max_hyp,
                                 mapping.data_ptr(), correct.data_ptr(), _stream()), "sdk_score_map")
-    return tally, correct, mapping[:int(ref.ref_off[-1])], co[:total], co_off
+    out = (tally, correct, mapping[:int(ref.ref_off[-1])], co[:total], co_off)
+    if not jer:
+        return out
+    n_ref, n_hyp = int(ref.ref_off[-1]), int(tab.cent_off[-1])
+    ref_frames = torch.empty((max(n_ref, 1),), dtype=torch.int32, device=eng.device)
+    hyp_frames = torch.empty((max(n_hyp, 1),), dtype=torch.int32, device=eng.device)
+    q = torch.empty((max(total, 1),), dtype=torch.int32, device=eng.device)
+    jer_mapping = torch.empty((max(n_ref, 1),), dtype=torch.int32, device=eng.device)
+    jsum = torch.empty((R,), dtype=torch.int64, device=eng.device)
+    check(eng.lib.sdk_score_durations(eng.ctx, ref.ref_mask.data_ptr() if tab.G else None, ref.scored.data_ptr() if tab.G else None,
+                                      speakers_dev.data_ptr() if tab.G else None, tab.frame_off_d.data_ptr(), ref.ref_off_d.data_ptr(), tab.cent_off_d.data_ptr(),
+                                      R, tab.G, ref.max_ref, max_hyp, ref_frames.data_ptr(), hyp_frames.data_ptr(), _stream()), "sdk_score_durations")
+    check(eng.lib.sdk_score_jaccard(eng.ctx, co.data_ptr(), ref_frames.data_ptr(), hyp_frames.data_ptr(), ref.ref_off_d.data_ptr(), tab.cent_off_d.data_ptr(),
+                                    co_off_d.data_ptr(), R, total, q.data_ptr(), _stream()), "sdk_score_jaccard")
+    check(eng.lib.sdk_score_map(eng.ctx, q.data_ptr(), ref.ref_off_d.data_ptr(), tab.cent_off_d.data_ptr(), co_off_d.data_ptr(), R, ref.max_ref, max_hyp,
+                                jer_mapping.data_ptr(), jsum.data_ptr(), _stream()), "sdk_score_map")
+    return out + (ref_frames[:n_ref], hyp_frames[:n_hyp], jsum, jer_mapping[:n_ref])
 
 
 def results_from_tables(ref: PackReference, cent_off, co_off, tally, correct, mapping, co) -> List[DerResult]:
@@ -351,22 +561,46 @@ def results_from_tables(ref: PackReference, cent_off, co_off, tally, correct, ma
     return out
 
 
-def score_grouped(eng, speakers_dev, tab, references, collar_s: float = 0.0, skip_overlap: bool = False) -> List[DerResult]:
-    """The device path for one pack: speakers [G, 2] int32 on the packed frame grid of tab (diarize_ops.GroupTables with clusters set), one
-    reference turn list per recording -> one DerResult per recording.  Three kernels calls, then one download of the integer tables."""
+def results_from_tables_jer(ref: PackReference, cent_off, co_off, tally, correct, mapping, co, ref_frames, hyp_frames, jsum, jer_mapping) -> List[DerResult]:
+    """results_from_tables for the downloaded tables of score_tables(jer=True)."""
+    out = []
+    for r, names in enumerate(ref.names):
+        S, K = len(names), int(cent_off[r + 1] - cent_off[r])
+        a, i0, i1, j0, j1 = int(co_off[r]), int(ref.ref_off[r]), int(ref.ref_off[r + 1]), int(cent_off[r]), int(cent_off[r + 1])
+        out.append(_result(names, np.asarray(co[a:a + S * K]).reshape(S, K), tally[r], mapping[i0:i1], correct[r],
+                           (ref_frames[i0:i1], hyp_frames[j0:j1], jsum[r], jer_mapping[i0:i1])))
+    return out
+
+
+def join_tables(tables):
+    """What score_tables left on the device (without co_off) -> the pieces of one int64 download, in the order split_tables / split_tables_jer cut."""
     torch = _native()[0]
-    ref = rasterise_references(eng, tab, references, collar_s, skip_overlap)
-    tally, correct, mapping, co, co_off = score_tables(eng, speakers_dev, tab, ref)
-    flat = torch.cat([tally.reshape(-1), correct, mapping.to(torch.int64), co.to(torch.int64)]).cpu().numpy()
-    return results_from_tables(ref, tab.cent_off, co_off, *split_tables(flat, tab.R, int(ref.ref_off[-1]), int(co_off[-1])))
+    return [t.reshape(-1).to(torch.int64) for t in tables]
 
 
-def score_results(eng, results, references, collar_s: float = 0.0, skip_overlap: bool = False) -> List[DerResult]:
+def score_grouped(eng, speakers_dev, tab, references, collar_s: float = 0.0, skip_overlap: bool = False, uems=None, jer: bool = False) -> List[DerResult]:
+    """The device path for one pack: speakers [G, 2] int32 on the packed frame grid of tab (diarize_ops.GroupTables with clusters set), one
+    reference turn list per recording -> one DerResult per recording.  Three kernels calls, then one download of the integer tables.  uems:
+    None, or one entry per recording (None or its UEM intervals): one more call; jer=True: three more, the same one download."""
+    torch = _native()[0]
+    ref = rasterise_references(eng, tab, references, collar_s, skip_overlap, uems=uems)
+    if not jer:
+        tally, correct, mapping, co, co_off = score_tables(eng, speakers_dev, tab, ref)
+        flat = torch.cat([tally.reshape(-1), correct, mapping.to(torch.int64), co.to(torch.int64)]).cpu().numpy()
+        return results_from_tables(ref, tab.cent_off, co_off, *split_tables(flat, tab.R, int(ref.ref_off[-1]), int(co_off[-1])))
+    t = score_tables(eng, speakers_dev, tab, ref, jer=True)
+    flat = torch.cat(join_tables(t[:4] + t[5:])).cpu().numpy()
+    return results_from_tables_jer(ref, tab.cent_off, t[4], *split_tables_jer(flat, tab.R, int(ref.ref_off[-1]), int(tab.cent_off[-1]), int(t[4][-1])))
+
+
+def score_results(eng, results, references, collar_s: float = 0.0, skip_overlap: bool = False, uems=None, jer: bool = False) -> List[DerResult]:
     """Diarizer.score: DiarizationResults and one reference turn list per result -> one DerResult per result; their `speakers` are uploaded
     and scored on the device as one pack (score_grouped)."""
     results, references = list(results), list(references)
     if len(references) != len(results):
         raise ValueError(f"score: {len(references)} references for {len(results)} recordings")
+    if uems is not None and len(uems) != len(results):
+        raise ValueError(f"score: {len(uems)} UEM entries for {len(results)} recordings")
     if not results:
         return []
     spk = [np.ascontiguousarray(res.speakers, dtype=np.int32).reshape(-1, 2) for res in results]
@@ -380,10 +614,22 @@ def score_results(eng, results, references, collar_s: float = 0.0, skip_overlap:
     n_samples = [FRAME_HOP * g + 226 if g else 0 for g in G_r]                      # a length with global_frames(n) == g: only the grid is read
     tab = GroupTables(eng, np.zeros(len(results) + 1, np.int64), np.concatenate([[0], np.cumsum(G_r)]), n_samples)
     tab.set_clusters(np.concatenate([[0], np.cumsum([int(res.n_speakers) for res in results])]))
-    return score_grouped(eng, torch.from_numpy(np.concatenate(spk)).to(eng.device), tab, references, collar_s, skip_overlap)
+    return score_grouped(eng, torch.from_numpy(np.concatenate(spk)).to(eng.device), tab, references, collar_s, skip_overlap, uems, jer)
 
 
 def split_tables(flat: np.ndarray, R: int, n_ref: int, n_co: int):
     """One int64 download [5 R + R + n_ref + n_co] -> (tally [R, 5], correct [R], map [n_ref], co [n_co])."""
     a, b, c = 5 * R, 6 * R, 6 * R + n_ref
     return flat[:a].reshape(R, 5), flat[a:b], flat[b:c], flat[c:c + n_co]
+
+
+def jer_download_size(R: int, n_ref: int, n_hyp: int, n_co: int) -> int:
+    return 7 * R + 3 * n_ref + n_hyp + n_co
+
+
+def split_tables_jer(flat: np.ndarray, R: int, n_ref: int, n_hyp: int, n_co: int):
+    """One int64 download of score_tables(jer=True) [jer_download_size] -> split_tables' four, then (ref_frames [n_ref], hyp_frames [n_hyp],
+    jsum [R], jer_mapping [n_ref])."""
+    d = 6 * R + n_ref + n_co
+    e, f, g = d + n_ref, d + n_ref + n_hyp, d + n_ref + n_hyp + R
+    return split_tables(flat, R, n_ref, n_co) + (flat[d:e], flat[e:f], flat[f:g], flat[g:g + n_ref])
