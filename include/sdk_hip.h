@@ -49,6 +49,8 @@
  *     sdk_samples_runs_workspace_bytes  sdk_samples_runs  sdk_samples_score_workspace_bytes  sdk_samples_score
  *                                                                                                       speaker samples: each speaker's solo runs on the diarization
  *                                                                                                       frames, and the scores of the clips cut from them (samples.py)
+ *     sdk_smooth_turns_workspace_bytes  sdk_smooth_turns                                                smoothing of the diarized turns: short pauses filled, short
+ *                                                                                                       runs dropped, on the diarization frames (smooth.py)
  *     sdk_plda_transform  sdk_vbx_workspace_bytes  sdk_vbx  sdk_vbx_centroids                           VBx clustering (plda.py, cluster.vbx_cluster)
  *     sdk_vbx_hmm_workspace_bytes  sdk_vbx_hmm                                                          VBx with its HMM, rows in time order (loop_prob > 0)
  *     sdk_plda_fit_stats_workspace_bytes  sdk_plda_fit_stats  sdk_plda_project                          training the VBx PLDA from labelled rows (plda.fit)
@@ -83,7 +85,7 @@
 extern "C" {
 #endif
 
-#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5); still 4 with sdk_cohort_stats* and sdk_affinity_topk_snorm, and with sdk_ecapa_forward_masked, sdk_ecapa_masked_workspace_bytes, sdk_asp_stats_masked_fmt and sdk_asp_pool_masked_fmt, and with sdk_score_reference, sdk_score_cooccur and sdk_score_map, and with sdk_plda_enroll* and sdk_plda_score*, and with sdk_trial_hist, sdk_trial_calib* and sdk_trial_hist_snorm, and with sdk_words_attribute and sdk_words_cooccur, and with sdk_samples_runs* and sdk_samples_score*, and with sdk_score_uem, sdk_score_durations and sdk_score_jaccard: new exports only, no struct or existing signature changes, no caller of version 4 breaks */
+#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5); still 4 with sdk_cohort_stats* and sdk_affinity_topk_snorm, and with sdk_ecapa_forward_masked, sdk_ecapa_masked_workspace_bytes, sdk_asp_stats_masked_fmt and sdk_asp_pool_masked_fmt, and with sdk_score_reference, sdk_score_cooccur and sdk_score_map, and with sdk_plda_enroll* and sdk_plda_score*, and with sdk_trial_hist, sdk_trial_calib* and sdk_trial_hist_snorm, and with sdk_words_attribute and sdk_words_cooccur, and with sdk_samples_runs* and sdk_samples_score*, and with sdk_score_uem, sdk_score_durations and sdk_score_jaccard, and with sdk_smooth_turns*: new exports only, no struct or existing signature changes, no caller of version 4 breaks */
 
 typedef struct sdk_ctx sdk_ctx;
 
@@ -738,6 +740,24 @@ size_t sdk_samples_score_workspace_bytes(int M, int S, int d);
 int sdk_samples_score(sdk_ctx* ctx, const float* E, int W, int d, const int32_t* clip_off, const int32_t* clip_spk, int M,
                       const int32_t* spk_off, int R, int S, double* mean, double* out_f, int32_t* out_i, void* ws, size_t ws_bytes,
                       void* stream);
+
+/* ---- smoothing of the diarized turns (smooth.py; csrc/smooth.hip): a speaker's short pauses filled, then the short runs dropped, on the
+ *      packed frame grid above.  frame_off, cent_off as above.  Integers only, one owner per frame in every launch, integer atomic sums for
+ *      the tallies: bit-identical run to run.  Everything is enqueued on `stream`; nothing waits and nothing is read on the host.
+ *   sdk_smooth_turns : speakers [G][2] int32, REWRITTEN in place.  An entry < 0 or >= K_r names nobody and a speaker named twice in a frame
+ *        counts once (any K_r >= 0: the kernels hold no per-speaker memory).  (1) fill: a gap of k is a maximal stretch of frames that do
+ *        not name k whose neighbours on both sides lie in the same recording and name k; k is a filler of every frame of a gap of at most
+ *        fill_frames frames, decided on the input alone.  (2) cap: the intermediate frame names the input frame's speakers in slot order,
+ *        each once, compacted to the low slot, then its fillers in ascending k until `cap` (1 or 2) speakers stand; a filler never
+ *        displaces a speaker of the input.  (3) drop: with keep_frames > 0, every maximal run of consecutive frames of one recording that
+ *        name k in the intermediate table and is shorter than keep_frames loses k; what remains of a frame is compacted in the same order.
+ *        Empty slots hold -1.  fill_frames = keep_frames = 0 returns the canonical form of the input.  Both are at most 1024 frames; more
+ *        is refused.  tallies [R][2] int32 (zeroed by the call) = per recording (filled: the (frame, speaker) pairs the intermediate
+ *        table names and the input does not; dropped: those the intermediate table names and the output does not).  ws: a 16-byte aligned
+ *        device buffer of sdk_smooth_turns_workspace_bytes(G) bytes (0 with sdk_last_error: G outside 0 .. 2^30 - 1); not read with G = 0. */
+size_t sdk_smooth_turns_workspace_bytes(int64_t G);
+int sdk_smooth_turns(sdk_ctx* ctx, int32_t* speakers, const int32_t* frame_off, const int32_t* cent_off, int R, int64_t G, int fill_frames,
+                     int keep_frames, int cap, int32_t* tallies, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- VBx clustering of the diarization (cluster.vbx_cluster, plda.py; csrc/vbx.hip): float64 arithmetic, every sum over rows over fixed 64-row
  *      blocks whose partials are combined in block order, no floating-point atomics, one owner per output element: bit-identical run to

@@ -556,7 +556,10 @@ class Backend(EmbeddingBackend):
         (cluster.vbx_cluster; the model of Backend.diarizer), whose speakers' centroids the assignment then reads; vbx: a dict of Fa, Fb,
         max_iters, epsilon, init_smoothing.  The result then carries scores, pi and elbo.  speakers=k, or (lo, hi) with either side None:
         the number of speakers of the recording ("bounds" in diarize.py; pyannote's max_speakers is speakers=(None, hi), max_speakers here
-        is the cap per frame); result.forced says whether the clustering was overruled.  Parity with PyAnnote is unpinned."""
+        is the cap per frame); result.forced says whether the clustering was overruled.  min_duration_off, min_duration_on (seconds,
+        default 0: nothing is done): a speaker's pauses no longer than the first are filled, then the turns shorter than the second are
+        dropped, on the device before the speakers table comes down (smooth.py states the rule); result.smoothing says what was done, and
+        smooth_diarization below does the same to finished results.  Parity with PyAnnote is unpinned."""
         dz = self.diarizer()
         if isinstance(samples_or_path, (str, Path)):
             samples_or_path = decode_to_profile(Path(samples_or_path), self.engine(), self.get_audio_profile())
@@ -572,7 +575,8 @@ class Backend(EmbeddingBackend):
         files, decoded to the audio profile) -> a list of diarize.DiarizationResult, in order.  Chunks of different recordings share the
         segmentation and embedding batches, one grouped linkage launch clusters all recordings, and assignment, fold and stitching run in
         grouped kernels; the host waits for the device a fixed number of times per pack, not per recording (diarize.Diarizer.run_many,
-        which also states how the results relate to diarize's).  Keywords as diarize; logp is a list with one array per recording."""
+        which also states how the results relate to diarize's).  Keywords as diarize, min_duration_off and min_duration_on among them (the
+        pack's table is smoothed in one launch sequence and no wait is added); logp is a list with one array per recording."""
         dz = self.diarizer()
         recs = [decode_to_profile(Path(x), self.engine(), self.get_audio_profile()) if isinstance(x, (str, Path)) else x for x in samples_or_paths]
         prec = dz.eng.precision
@@ -612,7 +616,11 @@ class Backend(EmbeddingBackend):
         development set with weights of your own.  The recordings are embedded and linked once per pack; every threshold costs only the cut,
         the grouped assignment, the stitching and the scoring kernels (diarize.Diarizer.sweep).  Keywords: step_s, min_cluster_size,
         max_speakers, logp, constrained, collar_s, skip_overlap; clustering="ahc" without speakers= only.  uem, jer: as score_diarization's (a
-        UEM file is read with `uris`); metric="der" or "jer": what `best` minimises, the pooled DER or the pooled Jaccard error rate."""
+        UEM file is read with `uris`); metric="der" or "jer": what `best` minimises, the pooled DER or the pooled Jaccard error rate.
+        smoothing: None, or a list of (min_duration_off, min_duration_on) pairs: every threshold is then scored under every pair (the
+        table smoothed on the device where it lies, no further wait) -> score.SmoothSweepResult (thresholds, smoothing, per_recording
+        [T][S][R], pooled [T][S], best = (threshold, min_duration_off, min_duration_on)): whether half a second of gap filling helps more
+        than another cut."""
         dz = self.diarizer()
         recs = [decode_to_profile(Path(x), self.engine(), self.get_audio_profile()) if isinstance(x, (str, Path)) else x for x in samples_or_paths]
         refs = self._references("tune_diarization", references, uris, len(recs))
@@ -1042,6 +1050,21 @@ def score_diarization_uem(be: Backend, results, references, uris=None, collar_s:
     results = list(results)
     return be.diarizer().score(results, be._references("score_diarization_uem", references, uris, len(results)), collar_s, skip_overlap,
                                uem=uem, jer=jer, uris=uris)
+
+
+# ---- smoothing finished results (smooth.py).  A function of the backend for the same reason.
+def smooth_diarization(be: Backend, results, min_duration_off: float = 0.0, min_duration_on: float = 0.0, max_speakers=None):
+    """The results of diarize / diarize_many / a closed stream with their turns smoothed: a speaker's pauses no longer than
+    min_duration_off seconds are filled (where the frame has a free slot: at most 2 speakers per frame, fewer with max_speakers, and a
+    speaker the diarization put there is never displaced), then the turns shorter than min_duration_on seconds are dropped - PyAnnote's
+    Binarize hyper-parameters, in its order.  -> copies of the results with speakers, turns and smoothing ({min_duration_off,
+    min_duration_on, fill, keep, filled, dropped}) replaced; everything else, count included, is what it was.  One upload, one launch
+    sequence (sdk_smooth_turns) and one download for the whole list; a single result gives a single result.  diarize(min_duration_off=,
+    min_duration_on=) does the same before the table comes down (smooth.py states the rule; parity with PyAnnote is unpinned)."""
+    from .smooth import smooth_results
+    single = not isinstance(results, (list, tuple))
+    out = smooth_results(be.engine(), [results] if single else list(results), min_duration_off, min_duration_on, max_speakers)
+    return out[0] if single else out
 
 
 # ---- speaker samples (samples.py).  Functions of the backend for the same reason.

@@ -60,7 +60,16 @@ tests pin these rules.
               rounded half up, at most 2 and max_speakers; speakers[g] = the count[g] clusters of largest act > 0 (ties to the lower cluster)
   numbering   clusters are renumbered by first appearance in time: frame order, then slot order, of a provisional stitching pass (clusters
               that never surface keep their relative order behind the others); the stitching is then run with the final numbers
-  turns       per speaker, runs of frames with segmentation.frames_to_ranges's boundaries; no gap filling; overlap gives simultaneous turns
+  turns       per speaker, runs of frames with segmentation.frames_to_ranges's boundaries; no gap filling unless asked for (smoothing,
+              below); overlap gives simultaneous turns
+  smoothing   (min_duration_off=, min_duration_on=; PyAnnote's Binarize hyper-parameters, in its order: fill, then drop) with either above 0
+              the final speakers table is smoothed on the device before it comes down (smooth.py states the rule; csrc/smooth.hip): a
+              speaker's pauses of at most min_duration_off are filled where the frame has a free slot under the cap per frame, then the
+              runs shorter than min_duration_on are dropped; turns are cut from the smoothed table and the result's `smoothing` holds
+              {min_duration_off, min_duration_on, fill, keep, filled, dropped}.  count, labels, centroids, scores, n_speakers and the
+              numbering stay as they are.  In run_many the tallies ride in the download of the speakers table: the waits per pack do not
+              grow.  Both at 0 (the default): the path is not entered and every result is what it was.  sweep(smoothing=[pairs]) scores
+              every threshold under every pair; backend.smooth_diarization smooths finished results
 
   many        (Diarizer.run_many, Backend.diarize_many) a folder of recordings crosses the pipeline as packs: the recordings laid end to end in
               one buffer with CHUNK zero samples behind each (pack_recordings), so chunks of different recordings share the segmentation /
@@ -145,6 +154,7 @@ class _Options:
     vbx: dict                    # _check_options' copy
     bounds: Optional[tuple]      # cluster.parse_speakers' result
     nmesc: Optional[dict] = None # _check_nmesc's copy
+    smooth: Optional[tuple] = None   # (min_duration_off, min_duration_on, fill, keep) when either time is above 0 (_check_smoothing)
 
 
 @dataclass
@@ -216,6 +226,18 @@ class Diarizer:
             raise ValueError(f"{who}: nmesc={nmesc} (keys neighbours, max_count, n_iter, seed; only with clustering=\"nmesc\")")
         return nmesc
 
+    def _check_smoothing(self, min_duration_off, min_duration_on) -> Optional[tuple]:
+        """-> None when both times are 0 (the path is not entered), else (min_duration_off, min_duration_on, fill, keep)."""
+        from .smooth import fill_frames_of, keep_frames_of
+        fill, keep = fill_frames_of(min_duration_off), keep_frames_of(min_duration_on)
+        return (float(min_duration_off), float(min_duration_on), fill, keep) if float(min_duration_off) > 0.0 or float(min_duration_on) > 0.0 else None
+
+    def _smoothed(self, res: DiarizationResult, smooth: Optional[tuple], tally=(0, 0)) -> DiarizationResult:
+        if smooth is not None:
+            from .smooth import smoothing_fields
+            res.smoothing = smoothing_fields(*smooth, tally)
+        return res
+
     def _check_recording(self, who: str, n_samples: int, step_s: float, logp=None) -> int:
         """The linkage's row bound and the shape of an injected logp, for a recording of n_samples > 0 samples -> its number of chunks."""
         Cn, F = len(chunk_starts(n_samples, step_s)), seg_frames(CHUNK)
@@ -269,7 +291,8 @@ class Diarizer:
     # ---------------------------------------------------------------------------------------------- one recording
     def run(self, samples, step_s: float = 1.0, threshold: float = PYANNOTE_THRESHOLD, min_cluster_size: int = PYANNOTE_MIN_CLUSTER_SIZE,
             max_speakers: Optional[int] = None, logp=None, constrained: bool = False, clustering: str = "ahc",
-            vbx: Optional[dict] = None, speakers=None, nmesc: Optional[dict] = None) -> DiarizationResult:
+            vbx: Optional[dict] = None, speakers=None, nmesc: Optional[dict] = None, min_duration_off: float = 0.0,
+            min_duration_on: float = 0.0) -> DiarizationResult:
         """samples: 16 kHz mono int16 (host) -> DiarizationResult.  logp [C, 589, 7] (fp32, host or device) replaces the segmentation
         model's output (the chunks are chunk_starts(len(samples), step_s)).  The default threshold and size are PyAnnote 3.1's, tuned for
         ITS trained embedding; with other weights pass a threshold of your own.  constrained=True: the constrained assignment of the
@@ -284,13 +307,16 @@ class Diarizer:
         speakers: the number of speakers of the recording, "bounds" in the module docstring: None, an int k (exactly k) or a pair (lo, hi),
         either side None.  pyannote's num_speakers=k is speakers=k, its min_speakers / max_speakers are speakers=(lo, hi), its
         max_speakers alone is speakers=(None, hi); max_speakers HERE is the cap per frame and keeps that meaning.  The result's `forced`
-        says whether the clustering was overruled."""
+        says whether the clustering was overruled.
+        min_duration_off, min_duration_on: seconds, "smoothing" in the module docstring - a speaker's pauses no longer than the first are
+        filled, then the turns shorter than the second are dropped, on the device; the result's `smoothing` says what was done."""
         vbx, bounds = self._check_options("diarize", clustering, vbx, max_speakers, speakers)
         nmesc = self._check_nmesc("diarize", clustering, nmesc)
+        smooth = self._check_smoothing(min_duration_off, min_duration_on)
         torch, eng = _native()[0], self.eng
         x = np.ascontiguousarray(samples, dtype=np.int16).reshape(-1)
         if x.size == 0:
-            return self._empty()
+            return self._smoothed(self._empty(), smooth)
         st = chunk_starts(x.size, step_s)                       # chunks
         Cn, F = self._check_recording("diarize", x.size, step_s, logp), seg_frames(CHUNK)
         if logp is not None:
@@ -331,11 +357,12 @@ class Diarizer:
             E[info.reshape(-1, 4)[:, 3] == 0] = 0.0            # rows that are not valid are never read as embeddings
             labels, cent = assign_rows(E, info, train, tl)
             scores = None
-        K = cent.shape[0]
+        K, last = cent.shape[0], {}
 
         def stitch(lab):                                        # stitching; numbering by appearance below, then turns
             cnt, spk, _ = diarize_reconstruct(eng, cls, starts_dev, torch.from_numpy(np.ascontiguousarray(lab, dtype=np.int32)).to(eng.device),
                                               max(K, 1), x.size, max_speakers)
+            last["spk_dev"] = spk                               # the table where it lies, for the smoothing below
             return cnt.cpu().numpy(), spk.cpu().numpy()
         count, speakers = stitch(labels)
         if K > 1:
@@ -344,7 +371,14 @@ class Diarizer:
                 labels = np.where(labels >= 0, new[np.maximum(labels, 0)], -1).astype(np.int32)
                 cent = cent[np.argsort(new)]
                 count, speakers = stitch(labels)
-        res = DiarizationResult(turns_from_frames(speakers, K), K, cent, labels, count, speakers, st, info, cls, scores)
+        tally = (0, 0)
+        if smooth is not None:                                  # fill, then drop, on the table where it lies; one download with the tallies
+            from .smooth import smooth_turns
+            off = torch.tensor([0, len(speakers), 0, K], dtype=torch.int32).to(eng.device)
+            spk_dev, tal_dev = smooth_turns(eng, last["spk_dev"], (off[:2], off[2:]), smooth[2], smooth[3], max(_speaker_cap(max_speakers), 1))
+            flat = torch.cat([spk_dev.reshape(-1), tal_dev.reshape(-1)]).cpu().numpy()
+            speakers, tally = flat[:-2].reshape(-1, 2).copy(), flat[-2:]
+        res = self._smoothed(DiarizationResult(turns_from_frames(speakers, K), K, cent, labels, count, speakers, st, info, cls, scores), smooth, tally)
         if vres is not None:
             res.pi, res.elbo = vres.pi, vres.elbo
         if nres is not None:
@@ -356,7 +390,8 @@ class Diarizer:
     # ---------------------------------------------------------------------------------------------- many recordings in one device pass
     def run_many(self, recordings, step_s: float = 1.0, threshold: float = PYANNOTE_THRESHOLD, min_cluster_size: int = PYANNOTE_MIN_CLUSTER_SIZE,
                  max_speakers: Optional[int] = None, logp=None, constrained: bool = False, clustering: str = "ahc",
-                 vbx: Optional[dict] = None, speakers=None, nmesc: Optional[dict] = None) -> List[DiarizationResult]:
+                 vbx: Optional[dict] = None, speakers=None, nmesc: Optional[dict] = None, min_duration_off: float = 0.0,
+                 min_duration_on: float = 0.0) -> List[DiarizationResult]:
         """recordings: a list of 16 kHz mono int16 arrays (host) -> one DiarizationResult per recording, in order; the keywords are run's,
         logp is None or a list with one [C_r, 589, 7] array per recording.  The recordings cross the pipeline in packs (pack_recordings) of
         at most $SDK_DIARIZE_PACK_SAMPLES samples (default 2^28, gaps included) whose grouped linkage stays within
@@ -371,10 +406,12 @@ class Diarizer:
         speakers: run's, applied to every recording; for "ahc" the level search replaces the cut on the host and adds no wait, for "vbx" a
         recording whose count is overruled adds cluster.KMEANS_HOST_READS waits.  clustering="nmesc" runs cluster.nmesc_cluster recording
         by recording in the same place (_pack_nmesc), as "vbx" does; its waits per recording (NmescResult.host_reads: the status of the
-        lists, the eigenvalue table or the lists, the labels) are counted in last_sync."""
+        lists, the eigenvalue table or the lists, the labels) are counted in last_sync.
+        min_duration_off, min_duration_on: run's; the pack's speakers table is smoothed on the device after the second stitching
+        (sdk_smooth_turns) and its tallies ride in the table's download, so last_sync is what it is without them."""
         vbx, bounds = self._check_options("diarize_many", clustering, vbx, max_speakers, speakers)
         opts = _Options(step_s, threshold, min_cluster_size, max_speakers, bool(constrained), clustering, vbx, bounds,
-                        self._check_nmesc("diarize_many", clustering, nmesc))
+                        self._check_nmesc("diarize_many", clustering, nmesc), self._check_smoothing(min_duration_off, min_duration_on))
         xs, packs = self._plan_packs(recordings, logp, step_s)
         out: List[Optional[DiarizationResult]] = [None] * len(xs)
         self.last_sync = []
@@ -405,7 +442,7 @@ class Diarizer:
 
     def sweep(self, recordings, references, thresholds, step_s: float = 1.0, min_cluster_size: int = PYANNOTE_MIN_CLUSTER_SIZE,
               max_speakers: Optional[int] = None, logp=None, constrained: bool = False, collar_s: float = 0.0, skip_overlap: bool = False,
-              clustering: str = "ahc", speakers=None, uem=None, jer: bool = False, metric: str = "der", uris=None):
+              clustering: str = "ahc", speakers=None, uem=None, jer: bool = False, metric: str = "der", uris=None, smoothing=None):
         """The DER of run_many(recordings, threshold=t, ...) against `references` for every t of `thresholds` -> score.SweepResult
         (thresholds, per_recording [T][R], pooled [T], best).  Per pack the recordings are embedded ONCE and linked ONCE (_pack_embed,
         _pack_link); per threshold only the cheap tail runs - cut on host integers, fold, centroids, assignment, stitching, renumbering and
@@ -414,8 +451,15 @@ class Diarizer:
         not grow with the number of thresholds.  Only clustering="ahc" without speaker bounds: the sweep is over the cut of the linkage.
         A recording that the cut splits into more than score.MAX_SCORE_SPEAKERS speakers at some threshold is a ValueError.
         uem, jer, uris: as score's; the UEM intervals ride in the reference's upload and the Jaccard tables in the one download, so the waits
-        per pack stay what they are.  metric: "der" or "jer" (which computes the JER whatever jer says) - what `best` minimises."""
-        from .score import (SweepResult, best_threshold, check_metric, jer_download_size, join_tables, pool, rasterise_references, resolve_uems,
+        per pack stay what they are.  metric: "der" or "jer" (which computes the JER whatever jer says) - what `best` minimises.
+        smoothing: None (this call as it always was), or a list of (min_duration_off, min_duration_on) pairs ("smoothing" in the module
+        docstring): per threshold the tail still runs once, and per pair sdk_smooth_turns and the scoring kernels run on the smoothed table
+        where it lies (the pair (0, 0) scores the table as it is); everything comes down in the same one download per pack, and last_sync
+        is what it is without the keyword.  -> score.SmoothSweepResult (thresholds, smoothing, per_recording [T][S][R], pooled [T][S],
+        best = (threshold, min_duration_off, min_duration_on): the least pooled metric, ties across thresholds as SweepResult.best breaks
+        them, then to the earlier pair)."""
+        from .smooth import check_pairs, smooth_turns
+        from .score import (SmoothSweepResult, SweepResult, best_threshold, check_metric, jer_download_size, join_tables, pool, rasterise_references, resolve_uems,
                             results_from_tables, results_from_tables_jer, score_host, score_tables, split_tables, split_tables_jer)
         jer = bool(jer) or check_metric("sweep", metric) == "jer"
         if clustering != "ahc" or speakers is not None:
@@ -429,16 +473,20 @@ class Diarizer:
         if len(references) != len(recordings):
             raise ValueError(f"sweep: {len(references)} references for {len(recordings)} recordings")
         uems = resolve_uems("sweep", uem, uris, len(recordings))
+        pairs = check_pairs("sweep", smoothing)
+        cols = [None] if pairs is None else pairs               # what every threshold's table is scored under; None: as it is
+        cap = max(_speaker_cap(max_speakers), 1)
         xs, packs = self._plan_packs(recordings, logp, step_s)
-        per = [[None] * len(xs) for _ in ths]
+        per = [[[None] * len(xs) for _ in cols] for _ in ths]   # [T][S][R]
         self.last_sync = []
         for idx in packs:
             refs, pack_uems = [references[i] for i in idx], None if uems is None else [uems[i] for i in idx]
             p = self._pack_begin([xs[i] for i in idx], None if logp is None else [logp[i] for i in idx], opts)
             if p is None:                                         # nothing but empty recordings: no frame to score
                 for t in range(len(ths)):
-                    for k, (i, ref) in enumerate(zip(idx, refs)):
-                        per[t][i] = score_host(np.zeros((0, 2), np.int32), 0, ref, collar_s, skip_overlap, None if uems is None else pack_uems[k], jer)
+                    for s in range(len(cols)):
+                        for k, (i, ref) in enumerate(zip(idx, refs)):
+                            per[t][s][i] = score_host(np.zeros((0, 2), np.int32), 0, ref, collar_s, skip_overlap, None if uems is None else pack_uems[k], jer)
                 continue
             torch, tab = _native()[0], p.tab
             linkage = self._pack_link(p)
@@ -451,14 +499,23 @@ class Diarizer:
                 self._mark("cut_fold_centroids")
                 spk_dev = self._pack_assign_dev(p, cl, opts)[4]
                 self._mark("assign_stitch")
-                tables = score_tables(self.eng, spk_dev, tab, ref, upload=self._up, jer=jer)
-                held += join_tables(tables[:4] + tables[5:])
-                shapes.append((cl.cent_off, tables[4]))
+                co_off_d = []                                     # the threshold's co_off goes up once, whatever the number of pairs
+
+                def up_once(a):
+                    if not co_off_d:
+                        co_off_d.append(self._up(a))
+                    return co_off_d[0]
+                for pair in cols:
+                    hyp = spk_dev if pair is None or (pair[2] == 0 and pair[3] == 0) else smooth_turns(self.eng, spk_dev, tab, pair[2], pair[3], cap)[0]
+                    tables = score_tables(self.eng, hyp, tab, ref, upload=up_once, jer=jer)
+                    held += join_tables(tables[:4] + tables[5:])
+                    shapes.append((cl.cent_off, tables[4]))
                 self._mark("score")
             p.sync["uploads"] += tab.uploads
             flat = self._down(torch.cat(held))                    # every threshold's tallies, tables and maps: ONE download
             pos, n_ref = 0, int(ref.ref_off[-1])
-            for t, (cent_off, co_off) in enumerate(shapes):
+            for n_col, (cent_off, co_off) in enumerate(shapes):
+                t, s = divmod(n_col, len(cols))
                 if jer:
                     n = jer_download_size(tab.R, n_ref, int(cent_off[-1]), int(co_off[-1]))
                     res = results_from_tables_jer(ref, cent_off, co_off, *split_tables_jer(flat[pos:pos + n], tab.R, n_ref, int(cent_off[-1]), int(co_off[-1])))
@@ -467,10 +524,16 @@ class Diarizer:
                     res = results_from_tables(ref, cent_off, co_off, *split_tables(flat[pos:pos + n], tab.R, n_ref, int(co_off[-1])))
                 pos += n
                 for i, one in zip(idx, res):
-                    per[t][i] = one
+                    per[t][s][i] = one
             self._mark("download")
-        pooled = [pool(row) for row in per]
-        return SweepResult(ths, per, pooled, best_threshold(ths, pooled, metric))
+        if pairs is None:
+            per = [row[0] for row in per]
+            pooled = [pool(row) for row in per]
+            return SweepResult(ths, per, pooled, best_threshold(ths, pooled, metric))
+        pooled = [[pool(row) for row in per_t] for per_t in per]
+        t, s = min(((t, s) for t in range(len(ths)) for s in range(len(cols))),
+                   key=lambda ts: (getattr(pooled[ts[0]][ts[1]], metric), abs(ths[ts[0]] - PYANNOTE_THRESHOLD), ths[ts[0]], ts[1]))
+        return SmoothSweepResult(ths, [(a, b) for a, b, _, _ in pairs], per, pooled, (ths[t], pairs[s][0], pairs[s][1]))
 
     # ---------------------------------------------------------------------------------------------- labelled rows for training a PLDA
     def plda_rows(self, samples_list, references, step_s: float = 1.0, logp=None) -> dict:
@@ -542,14 +605,14 @@ class Diarizer:
         """One pack through its stages; every _mark ends a stage of last_stage_s."""
         p = self._pack_begin(xs, logps, opts)
         if p is None:
-            return [self._empty() for _ in xs]
+            return [self._smoothed(self._empty(), opts.smooth) for _ in xs]
         cl = {"vbx": self._pack_vbx, "nmesc": self._pack_nmesc}.get(opts.clustering, self._pack_ahc)(p, opts)
         p.tab.set_clusters(cl.cent_off)
         p.sync["uploads"] += p.tab.uploads
         self._mark("cut_fold_centroids")
         host = self._pack_assign(p, cl, opts)
         self._mark("assign_stitch_download")
-        out = self._pack_results(p, cl, host)
+        out = self._pack_results(p, cl, host, opts.smooth)
         self._mark("turns")
         return out
 
@@ -683,7 +746,14 @@ class Diarizer:
 
     def _pack_assign(self, p: _PackState, cl: _Clusters, opts: _Options):
         """Grouped assignment, stitching, renumbering by appearance and second stitching -> (labels, scores, cent, count, speakers) on the host."""
-        return tuple(self._down(t) for t in self._pack_assign_dev(p, cl, opts))
+        dev = self._pack_assign_dev(p, cl, opts)
+        if opts.smooth is None:
+            return tuple(self._down(t) for t in dev)
+        from .smooth import smooth_turns
+        spk_dev, tal_dev = smooth_turns(self.eng, dev[4], p.tab, opts.smooth[2], opts.smooth[3], max(_speaker_cap(opts.max_speakers), 1))
+        host = tuple(self._down(t) for t in dev[:4])
+        flat = self._down(_native()[0].cat([spk_dev.reshape(-1), tal_dev.reshape(-1)]))    # the tallies ride with the speakers table: no further wait
+        return host + (flat[:2 * p.tab.G].reshape(-1, 2), flat[2 * p.tab.G:].reshape(-1, 2))
 
     def _pack_assign_dev(self, p: _PackState, cl: _Clusters, opts: _Options):
         """_pack_assign without its downloads: (labels, scores, cent, count, speakers) on the device."""
@@ -698,14 +768,15 @@ class Diarizer:
         cnt_dev, spk_dev, _ = diarize_reconstruct_grouped(eng, p.cls, lab_dev, tab, opts.max_speakers)
         return lab_dev, score_dev, c32, cnt_dev, spk_dev
 
-    def _pack_results(self, p: _PackState, cl: _Clusters, host):
-        """The pack's host arrays (host: _pack_assign's result) cut into one DiarizationResult per recording."""
+    def _pack_results(self, p: _PackState, cl: _Clusters, host, smooth: Optional[tuple] = None):
+        """The pack's host arrays (host: _pack_assign's result; with smoothing the tallies [R, 2] stand behind them) cut into one
+        DiarizationResult per recording."""
         pack, cent_off, info, cls, vres, forced = p.pack, cl.cent_off, p.info, p.cls, cl.vres, cl.forced
-        labels, scores, cent, count, speakers = host
+        labels, scores, cent, count, speakers = host[:5]
         out = []
         for r, x in enumerate(p.xs):
             if x.size == 0:
-                out.append(self._empty())
+                out.append(self._smoothed(self._empty(), smooth))
                 continue
             a, b, g0, g1, k0, k1 = (int(v) for v in (pack.chunk_off[r], pack.chunk_off[r + 1], pack.frame_off[r], pack.frame_off[r + 1], cent_off[r], cent_off[r + 1]))
             res = DiarizationResult(turns_from_frames(speakers[g0:g1], k1 - k0), k1 - k0, cent[k0:k1].copy(), labels[a:b].copy(), count[g0:g1].copy(),
@@ -716,5 +787,5 @@ class Diarizer:
                 res.forced = forced[r]
             if cl.nres and r in cl.nres:
                 res.nmesc = _nmesc_fields(cl.nres[r])
-            out.append(res)
+            out.append(self._smoothed(res, smooth, host[5][r] if smooth is not None else (0, 0)))
         return out

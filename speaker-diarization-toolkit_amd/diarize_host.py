@@ -42,6 +42,7 @@ class DiarizationResult:
     pi = None                                 # [S] float64 weights of the S initial speakers after the last iteration
     elbo = None                               # [n_iter] float64
     nmesc = None                              # clustering="nmesc": {p, k, ps, eigenvalues [n_p, m], ratios [n_p]} of cluster.nmesc_cluster ("nmesc" in diarize.py); else None
+    smoothing = None                          # min_duration_off / min_duration_on above 0: {min_duration_off, min_duration_on, fill, keep, filled, dropped} ("smoothing" in diarize.py, smooth.py); else None
     forced = None                             # speakers= overruled the clustering: {found, target, method, level, n_iter} ("bounds" in diarize.py); else None
 
 

@@ -113,6 +113,16 @@ class SweepResult:
     best: int                                 # index of the least pooled DER (metric="jer": JER); ties to the threshold nearest PYANNOTE_THRESHOLD, then the lower
 
 
+@dataclass
+class SmoothSweepResult:
+    """Diarizer.sweep(smoothing=[pairs]): every threshold under every (min_duration_off, min_duration_on) pair (smooth.py)."""
+    thresholds: List[float]
+    smoothing: List[Tuple[float, float]]      # [S] the pairs, as given
+    per_recording: List[List[List[DerResult]]]    # [T][S][R]
+    pooled: List[List[DerResult]]             # [T][S]
+    best: Tuple[float, float, float]          # (threshold, min_duration_off, min_duration_on) of the least pooled metric; ties across thresholds as SweepResult.best, then to the earlier pair
+
+
 def der_value(total: int, missed: int, false_alarm: int, confusion: int) -> float:
     err = int(missed) + int(false_alarm) + int(confusion)
     if total == 0:
