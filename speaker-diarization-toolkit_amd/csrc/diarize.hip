@@ -217,17 +217,8 @@ __global__ __launch_bounds__(64) void diarize_assign_kernel(const float* __restr
 
 // ---- many recordings in one pass (diarize.Diarizer.run_many): R recordings laid end to end.  chunk_off, frame_off and cent_off [R + 1] are
 // the prefix sums of their chunks, global frames and clusters; a kernel finds the recording of its element by a binary search on the table
-// that counts such elements (no per-element table is built).  Every output element has one owner and every sum a fixed order, as above.
-
-// the r with off[r] <= x < off[r + 1], for 0 <= x < off[R] (recordings without elements are stepped over)
-__device__ __forceinline__ int find_group(const int32_t* __restrict__ off, int R, int x) {
-  int lo = 0, hi = R;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= x) lo = mid; else hi = mid;
-  }
-  return lo;
-}
+// that counts such elements (packed_grid.hpp's pg_find_group; no per-element table is built).  Every output element has one owner and every
+// sum a fixed order, as above.
 
 // one wave per chunk, the rule of diarize_assign_kernel on the centroids of the chunk's own recording; labels are local to the recording
 __global__ __launch_bounds__(64) void diarize_assign_grouped_kernel(const float* __restrict__ E, const int32_t* __restrict__ info,
@@ -235,7 +226,7 @@ __global__ __launch_bounds__(64) void diarize_assign_grouped_kernel(const float*
                                                                     const int32_t* __restrict__ cent_off, int R, int d, int constrained,
                                                                     int32_t* __restrict__ labels, float* __restrict__ score) {
   const int c = blockIdx.x;
-  const int r = find_group(chunk_off, R, c);
+  const int r = pg_find_group(chunk_off, R, c);
   const int k0 = cent_off[r], K = cent_off[r + 1] - k0;
   if (K <= 0) {                                        // uniform over the wave: a recording without clusters
     if (threadIdx.x < 3) {
@@ -254,7 +245,7 @@ __global__ __launch_bounds__(64) void diarize_fold_target_kernel(const double* _
                                                                  const int32_t* __restrict__ cl_off, const int32_t* __restrict__ eff, int R, int d,
                                                                  int32_t* __restrict__ target) {
   const int k = blockIdx.x, lane = threadIdx.x;
-  const int r = find_group(cl_off, R, k);
+  const int r = pg_find_group(cl_off, R, k);
   const int b = cl_off[r], e = cl_off[r + 1], m = eff[r];
   if (sizes[k] >= m) {
     if (lane == 0) target[k] = k;
@@ -318,7 +309,7 @@ __global__ __launch_bounds__(DZ_NT) void diarize_reconstruct_grouped_kernel(cons
                                                                             int32_t* __restrict__ act, const int64_t* __restrict__ act_off) {
   const int gp = blockIdx.x * DZ_NT + threadIdx.x;
   if (gp >= G) return;
-  const int r = find_group(frame_off, R, gp);
+  const int r = pg_find_group(frame_off, R, gp);
   const int g = gp - frame_off[r];
   const int K = max(cent_off[r + 1] - cent_off[r], 1);  // no cluster: one cluster that no label names
   if (g >= dz_frames(n_samples[r])) {                   // a frame table longer than the recording: no chunk sees the frame
@@ -343,7 +334,7 @@ __global__ __launch_bounds__(DZ_NT) void diarize_first_seen_kernel(const int32_t
   const int k = speakers[i];
   if (k < 0) return;
   const int gp = (int)(i >> 1);
-  const int r = find_group(frame_off, R, gp);
+  const int r = pg_find_group(frame_off, R, gp);
   if (k >= cent_off[r + 1] - cent_off[r]) return;
   atomicMin(first + cent_off[r] + k, 2 * (gp - frame_off[r]) + (int)(i & 1));
 }
@@ -353,7 +344,7 @@ __global__ __launch_bounds__(DZ_NT) void diarize_rank_kernel(const int32_t* __re
                                                              int32_t* __restrict__ renum) {
   const int k = blockIdx.x * DZ_NT + threadIdx.x;
   if (k >= K) return;
-  const int r = find_group(cent_off, R, k);
+  const int r = pg_find_group(cent_off, R, k);
   const int f = first[k];
   int n = 0;
   for (int j = cent_off[r]; j < cent_off[r + 1]; ++j) {
@@ -369,7 +360,7 @@ __global__ __launch_bounds__(DZ_NT) void diarize_relabel_kernel(const int32_t* _
   if (i >= 3 * C) return;
   const int l = labels[i];
   if (l < 0) return;
-  const int r = find_group(chunk_off, R, i / 3);
+  const int r = pg_find_group(chunk_off, R, i / 3);
   if (l < cent_off[r + 1] - cent_off[r]) labels[i] = renum[cent_off[r] + l];
 }
 
@@ -378,7 +369,7 @@ __global__ __launch_bounds__(DZ_NT) void diarize_permute_kernel(const int32_t* _
                                                                 const float* __restrict__ c32, const double* __restrict__ c64,
                                                                 float* __restrict__ o32, double* __restrict__ o64) {
   const int k = blockIdx.x;
-  const int r = find_group(cent_off, R, k);
+  const int r = pg_find_group(cent_off, R, k);
   const int64_t dst = (int64_t)(cent_off[r] + renum[k]) * d, src = (int64_t)k * d;
   for (int j = threadIdx.x; j < d; j += DZ_NT) {
     o32[dst + j] = c32[src + j];
@@ -461,7 +452,7 @@ extern "C" int sdk_diarize_assign(sdk_ctx* ctx, const float* E, const int32_t* i
 }
 
 // ---- many recordings in one pass: the offset tables are DEVICE arrays (the kernels search them); the totals come as arguments
-#define DZ_GRID(n) dim3((unsigned)(((int64_t)(n) + DZ_NT - 1) / DZ_NT))
+#define DZ_GRID(n) pg_grid(n, DZ_NT)
 
 extern "C" int sdk_diarize_assign_grouped(sdk_ctx* ctx, const float* E, const int32_t* info, const double* cent64, const int32_t* chunk_off,
                                           const int32_t* cent_off, int R, int C, int d, int constrained, int32_t* labels, float* score, void* stream) {

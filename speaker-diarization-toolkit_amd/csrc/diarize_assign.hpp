@@ -2,26 +2,24 @@
 // assignment of one chunk's candidates to unit centroids (diarize.py "assignment" and "constrained assignment").
 #pragma once
 #include "common.hpp"
+#include "packed_grid.hpp"
 
 namespace {
 
-constexpr int DZ_HOP = 270;          // samples between segmentation frames
+constexpr int DZ_HOP = PG_HOP;       // samples between segmentation frames: the chunk grid's name for the hop of the global frame grid
 constexpr int DZ_MAX_D = 512;        // embedding width served by the assignment (a multiple of 64)
 
 // the speakers of powerset class c = {}, {0}, {1}, {2}, {0,1}, {0,2}, {1,2} as a 3-bit mask (0 for anything else)
 __device__ __forceinline__ int cls_mask(int c) { return (unsigned)c < 7u ? (0x6534210 >> (4 * c)) & 7 : 0; }
 
-// q_c = floor((135 - start_c) / 270): global frame g reads frame g + q_c of chunk c
+// q_c = floor((DZ_HOP / 2 - start_c) / DZ_HOP): global frame g reads frame g + q_c of chunk c
 __device__ __forceinline__ int64_t chunk_q(int64_t start) {
-  const int64_t a = 135 - start;
+  const int64_t a = DZ_HOP / 2 - start;
   return a >= 0 ? a / DZ_HOP : -((-a + DZ_HOP - 1) / DZ_HOP);
 }
 
-// global frames of a recording of n_samples samples (diarize.global_frames)
-__host__ __device__ inline int64_t dz_frames(int64_t n_samples) {
-  const int64_t g = (n_samples - 495 + DZ_HOP - 1) / DZ_HOP;
-  return n_samples < 495 || g < 0 ? 0 : g;
-}
+// global frames of a recording of n_samples samples (diarize.global_frames): the frames whose centre lies before its end
+__host__ __device__ inline int64_t dz_frames(int64_t n_samples) { return pg_first_frame(n_samples); }
 
 // (value, cluster) lists of a row's three largest cosines, best first; ties to the lower cluster; idx < 0: empty
 struct Top3 { double v[3]; int k[3]; };

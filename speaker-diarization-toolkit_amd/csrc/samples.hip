@@ -1,4 +1,4 @@
-// Speaker samples (samples.py): each diarized speaker's clean stretches of audio, on the packed frame grid of diarize.hip's grouped kernels,
+// Speaker samples (samples.py): each diarized speaker's clean stretches of audio, on the packed frame grid (packed_grid.hpp),
 // and the scores of the clips cut from them.
 //
 //   sdk_samples_runs    speakers [G][2] -> run_off [R + 1], rows [N][4] int32 = (speaker, g0, g1, solo), g0 and g1 local to the recording.  A
@@ -27,6 +27,7 @@
 //                       time by ballot), scores (a workgroup per clip; the rivals are dealt to its 4 waves, lanes over columns).  Every sum
 //                       has one owner and a fixed order and there is no floating-point atomic: two runs give the same bytes.
 #include "common.hpp"
+#include "packed_grid.hpp"
 
 namespace {
 
@@ -36,16 +37,6 @@ constexpr int SM_IPT = 8;                    // frames (groups) per thread
 constexpr int SM_SPAN = SM_NT * SM_IPT;      // frames (groups) per workgroup: 2048 (ops_score.SAMPLES_SCAN_SPAN)
 constexpr int SM_SILENT = -1, SM_OVER = -2;
 constexpr int SM_MAX_DIM = 512;              // diarize_host.MAX_ASSIGN_DIM
-
-// the r with off[r] <= x < off[r + 1], for 0 <= x < off[R] (groups without elements are stepped over): diarize.hip's find_group
-__device__ __forceinline__ int sm_find_group(const int32_t* __restrict__ off, int R, int x) {
-  int lo = 0, hi = R;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= x) lo = mid; else hi = mid;
-  }
-  return lo;
-}
 
 // exclusive prefix sum of v over the workgroup's 256 threads, and the total; sh holds 4 ints
 __device__ __forceinline__ int sm_block_excl_sum(int v, int* sh, int& total) {
@@ -101,13 +92,13 @@ __global__ __launch_bounds__(SM_NT) void sm_classify_kernel(const int32_t* __res
   const int64_t f0 = (int64_t)blockIdx.x * SM_SPAN + (int64_t)threadIdx.x * SM_IPT;
   int last = -1;
   if (f0 < G) {
-    int r = sm_find_group(frame_off, R, (int)f0);
+    int r = pg_find_group(frame_off, R, (int)f0);
     const int2* sp = reinterpret_cast<const int2*>(speakers);
 #pragma unroll
     for (int i = 0; i < SM_IPT; ++i) {
       const int f = (int)f0 + i;
       if (f >= G) break;
-      while (r + 1 < R && frame_off[r + 1] <= f) ++r;
+      r = pg_next_group(frame_off, R, r, f);
       const int K = min(max(cent_off[r + 1] - cent_off[r], 0), SM_MAX_SPK);
       const int2 h = sp[f];
       const bool on0 = h.x >= 0 && h.x < K, on1 = h.y >= 0 && h.y < K;
@@ -172,14 +163,14 @@ __global__ __launch_bounds__(SM_NT) void sm_groups_kernel(const int32_t* __restr
   int unused;
   const int before = max(sm_block_excl_max(last, sh, unused), blk_last[blockIdx.x]);   // the last frame before f0 that is not silent, else -1
   int p = before, pk = before >= 0 ? kind[before] : SM_SILENT;
-  int r = f0 < G ? sm_find_group(frame_off, R, f0) : 0;
+  int r = f0 < G ? pg_find_group(frame_off, R, f0) : 0;
   int n_brk = 0, n_solo = 0;
   unsigned brk = 0;
 #pragma unroll
   for (int i = 0; i < SM_IPT; ++i) {
     if (k[i] == SM_SILENT) continue;
     const int f = f0 + i;
-    while (r + 1 < R && frame_off[r + 1] <= f) ++r;
+    r = pg_next_group(frame_off, R, r, f);
     const bool b = p < frame_off[r] || pk != k[i] || k[i] == SM_OVER || f - p - 1 > gap;       // p == -1 is before every recording
     if (b) { brk |= 1u << i; ++n_brk; }
     if (k[i] >= 0) ++n_solo;
@@ -245,7 +236,7 @@ __global__ __launch_bounds__(SM_NT) void sm_keep_kernel(const int32_t* __restric
       const int j = (int)j0 + i;
       if (idx < rows_cap) {
         const int g0 = grp_start[j], g1 = grp_end[j] + 1;
-        const int base = frame_off[sm_find_group(frame_off, R, g0)];
+        const int base = frame_off[pg_find_group(frame_off, R, g0)];
         reinterpret_cast<int4*>(rows)[idx] = make_int4(kind[g0], g0 - base, g1 - base, grp_solo[j + 1] - grp_solo[j]);
         kept_start[idx] = g0;
       }
@@ -371,7 +362,7 @@ __global__ __launch_bounds__(SS_NT) void ss_score_kernel(const double* __restric
   const bool alone = !(p1 > 0.0) || !(p2 > 0.0);
   const double own = alone ? 0.0 : p0 / (sqrt(p1) * sqrt(p2));
   // the rivals: the other speakers of the recording, dealt to the waves; the lanes hold the clip's columns lane, lane + 64, ..
-  const int r = sm_find_group(spk_off, R, s);
+  const int r = pg_find_group(spk_off, R, s);
   const int t0 = min(max(spk_off[r], 0), S), t1 = min(max(spk_off[r + 1], t0), S);
   double av[SM_MAX_DIM / 64];
 #pragma unroll

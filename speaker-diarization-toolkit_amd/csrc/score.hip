@@ -1,12 +1,12 @@
-// Scoring a diarization against a reference (score.py): the diarization error rate on the packed frame grid of diarize.hip's grouped kernels.
+// Scoring a diarization against a reference (score.py): the diarization error rate on the packed frame grid (packed_grid.hpp).
 //
 //   score_turns_kernel     merged reference turns [M][3] (s0, s1, speaker) -> ref_mask [G] uint64, bit i = reference speaker i active in the
-//                          frame (centre 270 g + 495 in [s0, s1)).  One wave per turn, a 64-bit integer atomicOr per frame of the turn.
+//                          frame (its centre lies in [s0, s1)).  One wave per turn, a 64-bit integer atomicOr per frame of the turn.
 //   score_overlap_kernel   (skip_overlap) thread = frame: scored = 0 where two or more bits are set.
-//   score_collar_kernel    (collar > 0) one wave per boundary (a turn's s0 and s1): scored = 0 on the frames with |270 g + 495 - b| < collar.
+//   score_collar_kernel    (collar > 0) one wave per boundary (a turn's s0 and s1): scored = 0 on the frames with |centre - b| < collar.
 //   score_cooccur_kernel   ref_mask, scored, speakers [G][2] -> per recording co [S_r][K_r] int32 and tally [5] int64.  A workgroup takes
-//                          SC_FRAMES consecutive packed frames and serves the recordings inside them one at a time: the recording's table
-//                          is summed in LDS (at most 64 x 64 int32, 16 KB), then one integer atomic add per non-zero cell.
+//                          SC_FRAMES consecutive packed frames and serves the recordings inside them one at a time (pg_walk): the
+//                          recording's table is summed in LDS (at most 64 x 64 int32, 16 KB), then one integer atomic add per non-zero cell.
 //   score_map_kernel       one wave per recording: the exact maximum-weight assignment on its co table padded with zeros to n x n,
 //                          n = max(S_r, K_r) <= 64, by shortest augmenting paths with int64 potentials; column j lives on lane j and the
 //                          row minimum is a cross-lane reduction.
@@ -15,42 +15,25 @@
 // bit-identical run to run; `correct` is the optimum's value, unique where the map is not.  No kernel needs an ordering between
 // workgroups of one launch: the launches follow each other in stream order.
 #include "common.hpp"
+#include "packed_grid.hpp"
 
 namespace {
 
 constexpr int SC_NT = 256;
-constexpr int SC_MAX = 64;                   // reference and hypothesis speakers per recording (score.MAX_SCORE_SPEAKERS)
 constexpr int SC_FPT = 16;                   // frames per thread of score_cooccur_kernel
 constexpr int SC_FRAMES = SC_NT * SC_FPT;    // frames per workgroup
-constexpr int SC_HOP = 270, SC_FIRST = 495;  // frame g has centre sample 270 g + 495 (diarize.global_frames)
-
-// the r with off[r] <= x < off[r + 1], for 0 <= x < off[R] (groups without elements are stepped over): diarize.hip's find_group
-__device__ __forceinline__ int sc_find_group(const int32_t* __restrict__ off, int R, int x) {
-  int lo = 0, hi = R;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= x) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-// the least g >= 0 with 270 g + 495 >= s (int64: s + 269 may pass 2^31)
-__device__ __forceinline__ int64_t sc_first_frame(int64_t s) {
-  const int64_t a = s - SC_FIRST;
-  return a <= 0 ? 0 : (a + SC_HOP - 1) / SC_HOP;
-}
 
 __global__ __launch_bounds__(SC_NT) void score_turns_kernel(const int32_t* __restrict__ turns, const int32_t* __restrict__ turn_off,
                                                             const int32_t* __restrict__ frame_off, const int32_t* __restrict__ ref_off, int R,
                                                             int M, unsigned long long* __restrict__ ref_mask) {
   const int t = blockIdx.x * (SC_NT / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (t >= M) return;
-  const int r = sc_find_group(turn_off, R, t);
+  const int r = pg_find_group(turn_off, R, t);
   const int64_t s0 = turns[3 * (int64_t)t], s1 = turns[3 * (int64_t)t + 1];
   const int i = turns[3 * (int64_t)t + 2];
-  if (i < 0 || i >= ref_off[r + 1] - ref_off[r] || i >= SC_MAX || s1 <= s0) return;
+  if (i < 0 || i >= ref_off[r + 1] - ref_off[r] || i >= PG_MAX_SPK || s1 <= s0) return;
   const int64_t g0 = frame_off[r], n_g = frame_off[r + 1] - g0;
-  const int64_t lo = sc_first_frame(s0), hi = min(sc_first_frame(s1), n_g);      // the frames lo <= g < hi have s0 <= centre < s1
+  const int64_t lo = pg_first_frame(s0), hi = min(pg_first_frame(s1), n_g);      // the frames lo <= g < hi have s0 <= centre < s1
   const unsigned long long bit = 1ull << i;
   for (int64_t g = lo + lane; g < hi; g += 64) atomicOr(ref_mask + g0 + g, bit);
 }
@@ -66,11 +49,11 @@ __global__ __launch_bounds__(SC_NT) void score_collar_kernel(const int32_t* __re
   const int w = blockIdx.x * (SC_NT / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (w >= 2 * M) return;
   const int t = w >> 1;
-  const int r = sc_find_group(turn_off, R, t);
+  const int r = pg_find_group(turn_off, R, t);
   if (turns[3 * (int64_t)t + 1] <= turns[3 * (int64_t)t]) return;                  // no turn, no boundary
   const int64_t b = turns[3 * (int64_t)t + (w & 1)];
   const int64_t g0 = frame_off[r], n_g = frame_off[r + 1] - g0;
-  const int64_t lo = sc_first_frame(b - collar + 1), hi = min(sc_first_frame(b + collar), n_g);   // b - collar < centre < b + collar
+  const int64_t lo = pg_first_frame(b - collar + 1), hi = min(pg_first_frame(b + collar), n_g);   // b - collar < centre < b + collar
   for (int64_t g = lo + lane; g < hi; g += 64) scored[g0 + g] = 0;
 }
 
@@ -79,20 +62,13 @@ __global__ __launch_bounds__(SC_NT) void score_cooccur_kernel(const unsigned lon
                                                               const int32_t* __restrict__ ref_off, const int32_t* __restrict__ cent_off,
                                                               const int64_t* __restrict__ co_off, int R, int G, int32_t* __restrict__ co,
                                                               unsigned long long* __restrict__ tally) {
-  __shared__ int32_t tab[SC_MAX * SC_MAX];
+  __shared__ int32_t tab[PG_MAX_SPK * PG_MAX_SPK];
   __shared__ int32_t tal[5];
   const int tid = threadIdx.x;
-  const int f0 = blockIdx.x * SC_FRAMES, f1 = min(f0 + SC_FRAMES, G);
-  if (f0 >= f1) return;
-  int r = sc_find_group(frame_off, R, f0);
-  for (int a = f0; a < f1;) {                                   // every quantity of the loop is uniform over the workgroup
-    while (frame_off[r + 1] <= a) ++r;                          // a < f1 <= G = frame_off[R]: ends with r < R
-    const int b = min(f1, frame_off[r + 1]);
-    const int S = min(ref_off[r + 1] - ref_off[r], SC_MAX), K = min(cent_off[r + 1] - cent_off[r], SC_MAX);
-    const int cells = max(S, 0) * max(K, 0);
-    for (int c = tid; c < cells; c += SC_NT) tab[c] = 0;
-    if (tid < 5) tal[tid] = 0;
-    __syncthreads();
+  const int f0 = blockIdx.x * SC_FRAMES;
+  pg_walk(frame_off, R, f0, min(f0 + SC_FRAMES, G), [&](int r, int a, int b) {
+    const int S = pg_speakers(ref_off, r), K = pg_speakers(cent_off, r);
+    pg_co_clear<5, SC_NT>(tab, tal, S * K);
     int n_sc = 0, n_ref = 0, n_miss = 0, n_fa = 0, n_both = 0;
     for (int g = a + tid; g < b; g += SC_NT) {
       if (!scored[g]) continue;
@@ -113,20 +89,8 @@ __global__ __launch_bounds__(SC_NT) void score_cooccur_kernel(const unsigned lon
         if (on1) atomicAdd(&tab[i * K + h1], 1);
       }
     }
-    n_sc = wave_sum(n_sc); n_ref = wave_sum(n_ref); n_miss = wave_sum(n_miss); n_fa = wave_sum(n_fa); n_both = wave_sum(n_both);
-    if ((tid & 63) == 0) {
-      atomicAdd(&tal[0], n_sc); atomicAdd(&tal[1], n_ref); atomicAdd(&tal[2], n_miss); atomicAdd(&tal[3], n_fa); atomicAdd(&tal[4], n_both);
-    }
-    __syncthreads();
-    int32_t* dst = co + co_off[r];
-    for (int c = tid; c < cells; c += SC_NT) {
-      const int v = tab[c];
-      if (v) atomicAdd(dst + c, v);
-    }
-    if (tid < 5 && tal[tid]) atomicAdd(tally + 5 * (int64_t)r + tid, (unsigned long long)tal[tid]);
-    __syncthreads();                                            // the table is cleared again for the next recording
-    a = b;
-  }
+    pg_co_flush<5, SC_NT>(tab, tal, {n_sc, n_ref, n_miss, n_fa, n_both}, S * K, co + co_off[r], tally + 5 * (int64_t)r);
+  });
 }
 
 struct ScKey { long long v; int j; };
@@ -146,18 +110,18 @@ __device__ __forceinline__ ScKey sc_wave_argmin(long long v, int j) {           
 __global__ __launch_bounds__(64) void score_map_kernel(const int32_t* __restrict__ co, const int32_t* __restrict__ ref_off,
                                                        const int32_t* __restrict__ cent_off, const int64_t* __restrict__ co_off,
                                                        int32_t* __restrict__ map, long long* __restrict__ correct) {
-  __shared__ int32_t w[SC_MAX * SC_MAX];
-  __shared__ long long u[SC_MAX];
-  __shared__ int32_t row_col[SC_MAX];
+  __shared__ int32_t w[PG_MAX_SPK * PG_MAX_SPK];
+  __shared__ long long u[PG_MAX_SPK];
+  __shared__ int32_t row_col[PG_MAX_SPK];
   const int r = blockIdx.x, lane = threadIdx.x;
-  const int S = min(ref_off[r + 1] - ref_off[r], SC_MAX), K = min(cent_off[r + 1] - cent_off[r], SC_MAX);
+  const int S = pg_speakers(ref_off, r), K = pg_speakers(cent_off, r);
   const int n = max(S, K);
   if (n <= 0) {
     if (lane == 0) correct[r] = 0;
     return;
   }
   const int32_t* src = co + co_off[r];
-  for (int c = lane; c < n * SC_MAX; c += 64) {
+  for (int c = lane; c < n * PG_MAX_SPK; c += 64) {
     const int i = c >> 6, j = c & 63;
     w[c] = (i < S && j < K) ? src[i * K + j] : 0;
   }
@@ -175,7 +139,7 @@ __global__ __launch_bounds__(64) void score_map_kernel(const int32_t* __restrict
     for (;;) {
       const long long ui0 = u[i0];
       if (!used) {
-        const long long cur = -(long long)w[i0 * SC_MAX + lane] - ui0 - v;
+        const long long cur = -(long long)w[i0 * PG_MAX_SPK + lane] - ui0 - v;
         if (cur < minv) { minv = cur; way = j0; }
       }
       const ScKey best = sc_wave_argmin(used ? INF : minv, lane);
@@ -199,7 +163,7 @@ __global__ __launch_bounds__(64) void score_map_kernel(const int32_t* __restrict
   }
   long long sum = 0;
   if (lane < K && p >= 0 && p < S) {
-    const int c = w[p * SC_MAX + lane];
+    const int c = w[p * PG_MAX_SPK + lane];
     if (c > 0) { row_col[p] = lane; sum = c; }                  // a pair that never co-occurs is no pair
   }
   sum = wave_sum(sum);
@@ -208,8 +172,6 @@ __global__ __launch_bounds__(64) void score_map_kernel(const int32_t* __restrict
   if (lane == 0) correct[r] = sum;
 }
 
-#define SC_GRID(n, per) dim3((unsigned)(((int64_t)(n) + (per) - 1) / (per)))
-
 }  // namespace
 
 extern "C" int sdk_score_reference(sdk_ctx* ctx, const int32_t* turns, const int32_t* turn_off, const int32_t* frame_off, const int32_t* ref_off, int R,
@@ -217,7 +179,7 @@ extern "C" int sdk_score_reference(sdk_ctx* ctx, const int32_t* turns, const int
   SDK_REQUIRE(ctx, "sdk_score_reference: null context");
   SDK_REQUIRE(R >= 1 && M >= 0 && G >= 0 && G < (1ll << 30) && M < (1 << 28), "sdk_score_reference: R=%d M=%d G=%lld (R at least 1, fewer than 2^28 turns and 2^30 frames)",
               R, M, (long long)G);
-  SDK_REQUIRE(max_ref >= 0 && max_ref <= SC_MAX, "sdk_score_reference: %d reference speakers in a recording (at most %d)", max_ref, SC_MAX);
+  SDK_REQUIRE(max_ref >= 0 && max_ref <= PG_MAX_SPK, "sdk_score_reference: %d reference speakers in a recording (at most %d)", max_ref, PG_MAX_SPK);
   SDK_REQUIRE(collar >= 0 && collar < (1 << 30) && (skip_overlap == 0 || skip_overlap == 1), "sdk_score_reference: collar=%d samples (0 .. 2^30 - 1), skip_overlap=%d (0 or 1)",
               collar, skip_overlap);
   if (G == 0) return 0;
@@ -227,15 +189,15 @@ extern "C" int sdk_score_reference(sdk_ctx* ctx, const int32_t* turns, const int
   SDK_HIP_OK(hipMemsetAsync(ref_mask, 0, (size_t)G * 8, s));
   SDK_HIP_OK(hipMemsetAsync(scored, 1, (size_t)G, s));
   if (M) {
-    hipLaunchKernelGGL(score_turns_kernel, SC_GRID(M, SC_NT / 64), dim3(SC_NT), 0, s, turns, turn_off, frame_off, ref_off, R, M, (unsigned long long*)ref_mask);
+    hipLaunchKernelGGL(score_turns_kernel, pg_grid(M, SC_NT / 64), dim3(SC_NT), 0, s, turns, turn_off, frame_off, ref_off, R, M, (unsigned long long*)ref_mask);
     SDK_LAUNCH_CHECK();
   }
   if (skip_overlap && M) {
-    hipLaunchKernelGGL(score_overlap_kernel, SC_GRID(G, SC_NT), dim3(SC_NT), 0, s, (const unsigned long long*)ref_mask, (int)G, scored);
+    hipLaunchKernelGGL(score_overlap_kernel, pg_grid(G, SC_NT), dim3(SC_NT), 0, s, (const unsigned long long*)ref_mask, (int)G, scored);
     SDK_LAUNCH_CHECK();
   }
   if (collar > 0 && M) {
-    hipLaunchKernelGGL(score_collar_kernel, SC_GRID(2 * (int64_t)M, SC_NT / 64), dim3(SC_NT), 0, s, turns, turn_off, frame_off, R, M, collar, scored);
+    hipLaunchKernelGGL(score_collar_kernel, pg_grid(2 * (int64_t)M, SC_NT / 64), dim3(SC_NT), 0, s, turns, turn_off, frame_off, R, M, collar, scored);
     SDK_LAUNCH_CHECK();
   }
   return 0;
@@ -247,8 +209,8 @@ extern "C" int sdk_score_cooccur(sdk_ctx* ctx, const uint64_t* ref_mask, const u
   SDK_REQUIRE(ctx, "sdk_score_cooccur: null context");
   SDK_REQUIRE(R >= 1 && G >= 0 && G < (1ll << 30) && co_total >= 0, "sdk_score_cooccur: R=%d G=%lld co_total=%lld (R at least 1, fewer than 2^30 frames)", R,
               (long long)G, (long long)co_total);
-  SDK_REQUIRE(max_ref >= 0 && max_ref <= SC_MAX && max_hyp >= 0 && max_hyp <= SC_MAX,
-              "sdk_score_cooccur: %d reference and %d hypothesis speakers in a recording (at most %d each)", max_ref, max_hyp, SC_MAX);
+  SDK_REQUIRE(max_ref >= 0 && max_ref <= PG_MAX_SPK && max_hyp >= 0 && max_hyp <= PG_MAX_SPK,
+              "sdk_score_cooccur: %d reference and %d hypothesis speakers in a recording (at most %d each)", max_ref, max_hyp, PG_MAX_SPK);
   SDK_REQUIRE(tally && (co_total == 0 || co), "sdk_score_cooccur: null argument (co=%p tally=%p)", (void*)co, (void*)tally);
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(ctx, stream, SDK_K_COPY, 0.0, 17.0 * G + 4.0 * co_total);
@@ -256,7 +218,7 @@ extern "C" int sdk_score_cooccur(sdk_ctx* ctx, const uint64_t* ref_mask, const u
   if (co_total) SDK_HIP_OK(hipMemsetAsync(co, 0, (size_t)co_total * 4, s));
   if (G == 0) return 0;
   SDK_REQUIRE(ref_mask && scored && speakers && frame_off && ref_off && cent_off && co_off, "sdk_score_cooccur: null argument");
-  hipLaunchKernelGGL(score_cooccur_kernel, SC_GRID(G, SC_FRAMES), dim3(SC_NT), 0, s, (const unsigned long long*)ref_mask, scored, speakers, frame_off, ref_off,
+  hipLaunchKernelGGL(score_cooccur_kernel, pg_grid(G, SC_FRAMES), dim3(SC_NT), 0, s, (const unsigned long long*)ref_mask, scored, speakers, frame_off, ref_off,
                      cent_off, co_off, R, (int)G, co, (unsigned long long*)tally);
   SDK_LAUNCH_CHECK();
   return 0;
@@ -266,8 +228,8 @@ extern "C" int sdk_score_map(sdk_ctx* ctx, const int32_t* co, const int32_t* ref
                              int max_hyp, int32_t* map, int64_t* correct, void* stream) {
   SDK_REQUIRE(ctx, "sdk_score_map: null context");
   SDK_REQUIRE(R >= 1, "sdk_score_map: R=%d (at least 1)", R);
-  SDK_REQUIRE(max_ref >= 0 && max_ref <= SC_MAX && max_hyp >= 0 && max_hyp <= SC_MAX,
-              "sdk_score_map: %d reference and %d hypothesis speakers in a recording (at most %d each)", max_ref, max_hyp, SC_MAX);
+  SDK_REQUIRE(max_ref >= 0 && max_ref <= PG_MAX_SPK && max_hyp >= 0 && max_hyp <= PG_MAX_SPK,
+              "sdk_score_map: %d reference and %d hypothesis speakers in a recording (at most %d each)", max_ref, max_hyp, PG_MAX_SPK);
   SDK_REQUIRE(ref_off && cent_off && co_off && correct && (max_ref == 0 || map) && (max_ref == 0 || max_hyp == 0 || co), "sdk_score_map: null argument");
   ProfScope ps(ctx, stream, SDK_K_COPY, 0.0, (double)R * (4.0 * max_ref * max_hyp + 4.0 * max_ref + 8.0));
   hipLaunchKernelGGL(score_map_kernel, dim3(R), dim3(64), 0, (hipStream_t)stream, co, ref_off, cent_off, co_off, map, (long long*)correct);

@@ -1,5 +1,5 @@
-// Smoothing of diarized turns (smooth.py): fill a speaker's short pauses, then drop the short runs, on the packed frame grid of diarize.hip's
-// grouped kernels.  Integers only: every frame has one owner in every launch and the tallies are integer atomic sums, so two runs give the
+// Smoothing of diarized turns (smooth.py): fill a speaker's short pauses, then drop the short runs, on the packed frame grid
+// (packed_grid.hpp).  Integers only: every frame has one owner in every launch and the tallies are integer atomic sums, so two runs give the
 // same bytes.  The kernels hold no per-speaker memory, so the cost does not depend on K_r.
 //
 //   sdk_smooth_turns    speakers [G][2] in and out, tallies [R][2] = (filled, dropped).  Three launches of one thread per frame, SMT_NT = 256
@@ -18,21 +18,12 @@
 //                       No launch writes what it reads of other frames: 1 reads speakers and writes ent, 2 reads ent and writes mid, 3 reads
 //                       mid and writes speakers.  The walks of 2 and 3 read consecutive frames from consecutive lanes (coalesced, from the L2).
 #include "common.hpp"
+#include "packed_grid.hpp"
 
 namespace {
 
 constexpr int SMT_NT = 256;                  // frames per workgroup (smooth.SMOOTH_BLOCK_FRAMES)
 constexpr int SMT_MAX_FRAMES = 1024;         // the longest fill and keep, in frames (smooth.MAX_SMOOTH_FRAMES)
-
-// the r with off[r] <= x < off[r + 1], for 0 <= x < off[R] (groups without elements are stepped over): diarize.hip's find_group
-__device__ __forceinline__ int smt_find_group(const int32_t* __restrict__ off, int R, int x) {
-  int lo = 0, hi = R;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= x) lo = mid; else hi = mid;
-  }
-  return lo;
-}
 
 // v added to tally [2 r + which]: one atomic per wave where the wave lies inside one recording (almost always), else one per lane
 __device__ __forceinline__ void smt_tally(int32_t* __restrict__ tallies, int r, int which, int v, bool live) {
@@ -50,7 +41,7 @@ __global__ __launch_bounds__(SMT_NT) void smt_next_kernel(const int32_t* __restr
   const int64_t gw = (int64_t)blockIdx.x * SMT_NT + threadIdx.x;
   if (gw >= G) return;
   const int g = (int)gw;
-  const int r = smt_find_group(frame_off, R, g);
+  const int r = pg_find_group(frame_off, R, g);
   const int end = min(frame_off[r + 1], G);
   const int K = max(cent_off[r + 1] - cent_off[r], 0);
   const int2* sp = reinterpret_cast<const int2*>(speakers);
@@ -81,7 +72,7 @@ __global__ __launch_bounds__(SMT_NT) void smt_fill_kernel(const int4* __restrict
   int r = 0, added = 0;
   if (live) {
     const int g = (int)gw;
-    r = smt_find_group(frame_off, R, g);
+    r = pg_find_group(frame_off, R, g);
     const int start = max(frame_off[r], 0);
     const int4 e = ent[g];
     int o0 = e.x, o1 = e.y;
@@ -130,7 +121,7 @@ __global__ __launch_bounds__(SMT_NT) void smt_drop_kernel(const int2* __restrict
   int r = 0, dropped = 0;
   if (live) {
     const int g = (int)gw;
-    r = smt_find_group(frame_off, R, g);
+    r = pg_find_group(frame_off, R, g);
     const int start = max(frame_off[r], 0), end = min(frame_off[r + 1], G);
     const int2 m = mid[g];
     int o0 = m.x, o1 = m.y;
@@ -172,7 +163,7 @@ extern "C" int sdk_smooth_turns(sdk_ctx* ctx, int32_t* speakers, const int32_t* 
               (void*)speakers);
   int4* ent = static_cast<int4*>(ws);
   int2* mid = reinterpret_cast<int2*>(ent + G);
-  const dim3 grid((unsigned)((G + SMT_NT - 1) / SMT_NT)), nt(SMT_NT);
+  const dim3 grid = pg_grid(G, SMT_NT), nt(SMT_NT);
   const int g = (int)G;
   ProfScope ps(ctx, stream, SDK_K_COPY, 0.0, (8.0 + 16.0) * G + (16.0 + 8.0) * G + (8.0 + 8.0) * G);
   hipLaunchKernelGGL(smt_next_kernel, grid, nt, 0, st, speakers, frame_off, cent_off, R, g, fill_frames, ent);

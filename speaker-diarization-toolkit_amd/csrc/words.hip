@@ -1,5 +1,5 @@
 // Speaker-attributed transcripts (words.py): the words of a transcript onto the per-frame speakers of a diarization, and the word-level
-// diarization error rate (WDER) tables, on the packed frame grid of diarize.hip's grouped kernels.
+// diarization error rate (WDER) tables, on the packed frame grid (packed_grid.hpp).
 //
 //   words_attribute_kernel   words [W][2] (s0, s1 in samples of the word's recording), speakers [G][2] -> rows [W][8] int32 (speaker, votes,
 //                            solo, span, second, second_votes, distance, g0).  One wave per word (a workgroup is one wave): the word's
@@ -9,39 +9,22 @@
 //                            u descending, k ascending), taken twice (the second time without the winner); a word in non-speech searches its
 //                            nearest voiced frame on both sides, 64 distances at a time.
 //   words_cooccur_kernel     rows, ref [W] -> per recording co [S_r][K_r] int32 and tally [3] int64 (scored, unassigned, words).  A workgroup
-//                            takes WD_WORDS consecutive words and serves the recordings inside them one at a time: the recording's table is
-//                            summed in LDS (at most 64 x 64 int32), then one integer atomic add per non-zero cell (score_cooccur_kernel on
-//                            words).  sdk_score_map then runs on co unchanged.
+//                            takes WD_WORDS consecutive words and serves the recordings inside them one at a time (pg_walk): the recording's
+//                            table is summed in LDS (at most 64 x 64 int32), then one integer atomic add per non-zero cell
+//                            (score_cooccur_kernel on words).  sdk_score_map then runs on co unchanged.
 //
 // Integer arithmetic only.  Integer adds do not depend on the order they land in and every row is written by one wave, so every output is
 // bit-identical run to run.
 #include "common.hpp"
+#include "packed_grid.hpp"
 
 namespace {
 
-constexpr int WD_MAX_SPK = 1024;             // hypothesis speakers per recording (words.MAX_WORD_SPEAKERS)
-constexpr int WD_SC_MAX = 64;                // reference and hypothesis speakers per recording in the WDER tables (score.MAX_SCORE_SPEAKERS)
+constexpr int WD_MAX_SPK = 1024;             // hypothesis speakers per recording (words.MAX_WORD_SPEAKERS); the WDER tables: PG_MAX_SPK a side
 constexpr int WD_NT = 256;
 constexpr int WD_WPT = 4;                    // words per thread of words_cooccur_kernel
 constexpr int WD_WORDS = WD_NT * WD_WPT;     // words per workgroup
-constexpr int WD_HOP = 270, WD_FIRST = 495;  // frame g has centre sample 270 g + 495 (diarize.global_frames)
-constexpr int WD_HALF = 360;                 // floor((m - 360) / 270): the frame whose centre is nearest m (centres 270 g + 495; half way: the later)
-
-// the r with off[r] <= x < off[r + 1], for 0 <= x < off[R] (groups without elements are stepped over): diarize.hip's find_group
-__device__ __forceinline__ int wd_find_group(const int32_t* __restrict__ off, int R, int x) {
-  int lo = 0, hi = R;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= x) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-// the least g >= 0 with 270 g + 495 >= s
-__device__ __forceinline__ int64_t wd_first_frame(int64_t s) {
-  const int64_t a = s - WD_FIRST;
-  return a <= 0 ? 0 : (a + WD_HOP - 1) / WD_HOP;
-}
+constexpr int WD_HALF = PG_FIRST - PG_HOP / 2;   // floor((m - WD_HALF) / PG_HOP): the frame whose centre is nearest m (half way: the later)
 
 struct WdBest { int v, u, k; };              // k == -1: nobody
 
@@ -89,7 +72,7 @@ __global__ __launch_bounds__(64) void words_attribute_kernel(const int32_t* __re
   const int w = blockIdx.x, lane = threadIdx.x;
   if (w >= W) return;
   int32_t* row = out + 8 * (int64_t)w;
-  const int r = wd_find_group(word_off, R, w);
+  const int r = pg_find_group(word_off, R, w);
   const int64_t fbase = frame_off[r];
   const int64_t n_g = frame_off[r + 1] - fbase;
   const int K = min(max(cent_off[r + 1] - cent_off[r], 0), cap);  // never past the counters, whatever the tables say
@@ -98,11 +81,11 @@ __global__ __launch_bounds__(64) void words_attribute_kernel(const int32_t* __re
     return;
   }
   const int64_t s0 = words[2 * (int64_t)w], s1 = words[2 * (int64_t)w + 1];
-  int64_t g0 = min(wd_first_frame(s0), n_g), g1 = min(wd_first_frame(s1), n_g);
+  int64_t g0 = min(pg_first_frame(s0), n_g), g1 = min(pg_first_frame(s1), n_g);
   if (g1 <= g0) {                                               // no centre inside [s0, s1): the frame nearest the midpoint
     const int64_t m = (s0 + s1) >> 1;
     const int64_t a = m - WD_HALF;
-    g0 = min(a <= 0 ? (int64_t)0 : a / WD_HOP, n_g - 1);
+    g0 = min(a <= 0 ? (int64_t)0 : a / PG_HOP, n_g - 1);
     g1 = g0 + 1;
   }
   for (int k = lane; k < K; k += 64) { v[k] = 0; u[k] = 0; }
@@ -152,20 +135,13 @@ __global__ __launch_bounds__(WD_NT) void words_cooccur_kernel(const int32_t* __r
                                                               const int32_t* __restrict__ word_off, const int32_t* __restrict__ ref_off,
                                                               const int32_t* __restrict__ cent_off, const int64_t* __restrict__ co_off, int R,
                                                               int W, int32_t* __restrict__ co, unsigned long long* __restrict__ tally) {
-  __shared__ int32_t tab[WD_SC_MAX * WD_SC_MAX];
+  __shared__ int32_t tab[PG_MAX_SPK * PG_MAX_SPK];
   __shared__ int32_t tal[3];
   const int tid = threadIdx.x;
-  const int w0 = blockIdx.x * WD_WORDS, w1 = min(w0 + WD_WORDS, W);
-  if (w0 >= w1) return;
-  int r = wd_find_group(word_off, R, w0);
-  for (int a = w0; a < w1;) {                                   // every quantity of the loop is uniform over the workgroup
-    while (word_off[r + 1] <= a) ++r;                           // a < w1 <= W = word_off[R]: ends with r < R
-    const int b = min(w1, word_off[r + 1]);
-    const int S = min(max(ref_off[r + 1] - ref_off[r], 0), WD_SC_MAX), K = min(max(cent_off[r + 1] - cent_off[r], 0), WD_SC_MAX);
-    const int cells = S * K;
-    for (int c = tid; c < cells; c += WD_NT) tab[c] = 0;
-    if (tid < 3) tal[tid] = 0;
-    __syncthreads();
+  const int w0 = blockIdx.x * WD_WORDS;
+  pg_walk(word_off, R, w0, min(w0 + WD_WORDS, W), [&](int r, int a, int b) {
+    const int S = pg_speakers(ref_off, r), K = pg_speakers(cent_off, r);
+    pg_co_clear<3, WD_NT>(tab, tal, S * K);
     int n_sc = 0, n_un = 0, n_w = 0;
     for (int x = a + tid; x < b; x += WD_NT) {
       const int i = ref[x], j = rows[8 * (int64_t)x];
@@ -174,18 +150,8 @@ __global__ __launch_bounds__(WD_NT) void words_cooccur_kernel(const int32_t* __r
       n_sc += 1;
       if (j >= 0 && j < K) atomicAdd(&tab[i * K + j], 1); else n_un += 1;
     }
-    n_sc = wave_sum(n_sc); n_un = wave_sum(n_un); n_w = wave_sum(n_w);
-    if ((tid & 63) == 0) { atomicAdd(&tal[0], n_sc); atomicAdd(&tal[1], n_un); atomicAdd(&tal[2], n_w); }
-    __syncthreads();
-    int32_t* dst = co + co_off[r];
-    for (int c = tid; c < cells; c += WD_NT) {
-      const int x = tab[c];
-      if (x) atomicAdd(dst + c, x);
-    }
-    if (tid < 3 && tal[tid]) atomicAdd(tally + 3 * (int64_t)r + tid, (unsigned long long)tal[tid]);
-    __syncthreads();                                            // the table is cleared again for the next recording
-    a = b;
-  }
+    pg_co_flush<3, WD_NT>(tab, tal, {n_sc, n_un, n_w}, S * K, co + co_off[r], tally + 3 * (int64_t)r);
+  });
 }
 
 }  // namespace
@@ -213,8 +179,8 @@ extern "C" int sdk_words_cooccur(sdk_ctx* ctx, const int32_t* rows, const int32_
   SDK_REQUIRE(ctx, "sdk_words_cooccur: null context");
   SDK_REQUIRE(R >= 1 && W >= 0 && W < (1 << 28) && co_total >= 0, "sdk_words_cooccur: R=%d W=%d co_total=%lld (R at least 1, fewer than 2^28 words)", R, W,
               (long long)co_total);
-  SDK_REQUIRE(max_ref >= 0 && max_ref <= WD_SC_MAX && max_hyp >= 0 && max_hyp <= WD_SC_MAX,
-              "sdk_words_cooccur: %d reference and %d hypothesis speakers in a recording (at most %d each)", max_ref, max_hyp, WD_SC_MAX);
+  SDK_REQUIRE(max_ref >= 0 && max_ref <= PG_MAX_SPK && max_hyp >= 0 && max_hyp <= PG_MAX_SPK,
+              "sdk_words_cooccur: %d reference and %d hypothesis speakers in a recording (at most %d each)", max_ref, max_hyp, PG_MAX_SPK);
   SDK_REQUIRE(tally && (co_total == 0 || co), "sdk_words_cooccur: null argument (co=%p tally=%p)", (void*)co, (void*)tally);
   hipStream_t s = (hipStream_t)stream;
   ProfScope ps(ctx, stream, SDK_K_COPY, 0.0, 8.0 * W + 4.0 * co_total);
@@ -222,7 +188,7 @@ extern "C" int sdk_words_cooccur(sdk_ctx* ctx, const int32_t* rows, const int32_
   if (co_total) SDK_HIP_OK(hipMemsetAsync(co, 0, (size_t)co_total * 4, s));
   if (W == 0) return 0;
   SDK_REQUIRE(rows && ref && word_off && ref_off && cent_off && co_off, "sdk_words_cooccur: null argument");
-  hipLaunchKernelGGL(words_cooccur_kernel, dim3((unsigned)((W + WD_WORDS - 1) / WD_WORDS)), dim3(WD_NT), 0, s, rows, ref, word_off, ref_off, cent_off, co_off,
+  hipLaunchKernelGGL(words_cooccur_kernel, pg_grid(W, WD_WORDS), dim3(WD_NT), 0, s, rows, ref, word_off, ref_off, cent_off, co_off,
                      R, W, co, (unsigned long long*)tally);
   SDK_LAUNCH_CHECK();
   return 0;

@@ -459,8 +459,7 @@ class Diarizer:
         best = (threshold, min_duration_off, min_duration_on): the least pooled metric, ties across thresholds as SweepResult.best breaks
         them, then to the earlier pair)."""
         from .smooth import check_pairs, smooth_turns
-        from .score import (SmoothSweepResult, SweepResult, best_threshold, check_metric, jer_download_size, join_tables, pool, rasterise_references, resolve_uems,
-                            results_from_tables, results_from_tables_jer, score_host, score_tables, split_tables, split_tables_jer)
+        from .score import SmoothSweepResult, SweepResult, best_threshold, check_metric, pool, rasterise_references, resolve_uems, score_host, score_tables
         jer = bool(jer) or check_metric("sweep", metric) == "jer"
         if clustering != "ahc" or speakers is not None:
             raise ValueError(f"sweep: clustering={clustering!r}, speakers={speakers!r}: the sweep is over the cut of clustering=\"ahc\" with speakers=None")
@@ -492,7 +491,7 @@ class Diarizer:
             linkage = self._pack_link(p)
             ref = rasterise_references(self.eng, tab, refs, collar_s, skip_overlap, upload=self._up, uems=pack_uems)
             self._mark("reference")
-            held, shapes = [], []
+            held, pieces = [], []                                 # one score.ScoreTables per (threshold, pair) and the int64 pieces of them all
             for t in ths:
                 cl = self._pack_cut(p, linkage, t, opts)
                 tab.set_clusters(cl.cent_off)
@@ -507,24 +506,17 @@ class Diarizer:
                     return co_off_d[0]
                 for pair in cols:
                     hyp = spk_dev if pair is None or (pair[2] == 0 and pair[3] == 0) else smooth_turns(self.eng, spk_dev, tab, pair[2], pair[3], cap)[0]
-                    tables = score_tables(self.eng, hyp, tab, ref, upload=up_once, jer=jer)
-                    held += join_tables(tables[:4] + tables[5:])
-                    shapes.append((cl.cent_off, tables[4]))
+                    held.append(score_tables(self.eng, hyp, tab, ref, upload=up_once, jer=jer))
+                    pieces += held[-1].pieces()
                 self._mark("score")
             p.sync["uploads"] += tab.uploads
-            flat = self._down(torch.cat(held))                    # every threshold's tallies, tables and maps: ONE download
-            pos, n_ref = 0, int(ref.ref_off[-1])
-            for n_col, (cent_off, co_off) in enumerate(shapes):
+            flat = self._down(torch.cat(pieces))                  # every threshold's tallies, tables and maps: ONE download
+            pos = 0
+            for n_col, tables in enumerate(held):
                 t, s = divmod(n_col, len(cols))
-                if jer:
-                    n = jer_download_size(tab.R, n_ref, int(cent_off[-1]), int(co_off[-1]))
-                    res = results_from_tables_jer(ref, cent_off, co_off, *split_tables_jer(flat[pos:pos + n], tab.R, n_ref, int(cent_off[-1]), int(co_off[-1])))
-                else:
-                    n = 6 * tab.R + n_ref + int(co_off[-1])
-                    res = results_from_tables(ref, cent_off, co_off, *split_tables(flat[pos:pos + n], tab.R, n_ref, int(co_off[-1])))
-                pos += n
-                for i, one in zip(idx, res):
+                for i, one in zip(idx, tables.results(ref, flat[pos:pos + tables.size])):
                     per[t][s][i] = one
+                pos += tables.size
             self._mark("download")
         if pairs is None:
             per = [row[0] for row in per]

@@ -10,7 +10,7 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
-from .segmentation import CHUNK, FRAME_HOP, POWERSET, chunk_starts, frames_to_ranges
+from .segmentation import CHUNK, FRAME_FIRST, FRAME_HOP, POWERSET, chunk_starts, frames_to_ranges
 from .segmentation import num_frames as seg_frames
 
 MIN_CLEAN_COLUMNS = 4            # ours (~0.32 s of the last map): below it the overlapped columns are kept
@@ -48,7 +48,7 @@ class DiarizationResult:
 
 # ------------------------------------------------------------------------------------------------ host restatements (numpy, vectorised)
 def global_frames(n_samples: int) -> int:
-    return max(0, (int(n_samples) - 495 + FRAME_HOP - 1) // FRAME_HOP)
+    return max(0, (int(n_samples) - FRAME_FIRST + FRAME_HOP - 1) // FRAME_HOP)
 
 
 def decode_host(logp: np.ndarray) -> np.ndarray:

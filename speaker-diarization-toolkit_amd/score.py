@@ -65,10 +65,9 @@ import numpy as np
 
 from .diarize_host import global_frames
 from .diarize_ops import GroupTables, _check_tensor, _native
-from .segmentation import FRAME_HOP, SAMPLE_RATE
+from .segmentation import FRAME_FIRST, FRAME_HOP, SAMPLE_RATE   # FRAME_FIRST is re-exported: words.py reads it here
 
 MAX_SCORE_SPEAKERS = 64
-FRAME_FIRST = 495                # centre sample of frame 0
 _INF = 1 << 62
 JACCARD_ONE = 1 << 30            # the Jaccard table's unit: q / 2^30 is the index
 UEM_EVERYTHING = (0, (1 << 31) - 1)   # the interval a recording without a UEM is handed on the device
@@ -328,15 +327,21 @@ def _popcount(mask: np.ndarray) -> np.ndarray:
     return np.unpackbits(np.ascontiguousarray(mask, dtype="<u8").view(np.uint8).reshape(-1, 8), axis=1).sum(1).astype(np.int64)
 
 
-def cooccur_host(ref_mask: np.ndarray, scored: np.ndarray, speakers: np.ndarray, S: int, K: int):
-    """sdk_score_cooccur for one recording in numpy -> (co [S, K] int32, tally [5] int64: scored, total, missed, false_alarm, both)."""
+def _active_host(ref_mask: np.ndarray, scored: np.ndarray, speakers: np.ndarray, S: int, K: int):
+    """The n scored frames of one recording -> (mask [n] uint64, speakers [n, 2], ref [n, S] bool: reference i is active, hyp [n, K] bool:
+    the frame names hypothesis j - named twice counts once)."""
     on = np.asarray(scored).astype(bool)
     mask, sp = np.asarray(ref_mask, dtype=np.uint64)[on], np.asarray(speakers, dtype=np.int64).reshape(-1, 2)[on]
+    ref = ((mask[:, None] >> np.arange(S, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
+    return mask, sp, ref, (sp[:, :, None] == np.arange(K)[None, None, :]).any(1)
+
+
+def cooccur_host(ref_mask: np.ndarray, scored: np.ndarray, speakers: np.ndarray, S: int, K: int):
+    """sdk_score_cooccur for one recording in numpy -> (co [S, K] int32, tally [5] int64: scored, total, missed, false_alarm, both)."""
+    mask, sp, ref, hyp = _active_host(ref_mask, scored, speakers, S, K)
     nref, nhyp = _popcount(mask), (sp >= 0).sum(1)
-    tally = np.array([on.sum(), nref.sum(), np.maximum(nref - nhyp, 0).sum(), np.maximum(nhyp - nref, 0).sum(), np.minimum(nref, nhyp).sum()], np.int64)
-    ref = ((mask[:, None] >> np.arange(S, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.float64)        # [frames, S]
-    hyp = (sp[:, :, None] == np.arange(K)[None, None, :]).any(1).astype(np.float64)                            # [frames, K]: named twice counts once
-    return np.rint(ref.T @ hyp).astype(np.int32).reshape(S, K), tally                                           # counts below 2^30: exact in float64
+    tally = np.array([len(mask), nref.sum(), np.maximum(nref - nhyp, 0).sum(), np.maximum(nhyp - nref, 0).sum(), np.minimum(nref, nhyp).sum()], np.int64)
+    return np.rint(ref.T.astype(np.float64) @ hyp.astype(np.float64)).astype(np.int32).reshape(S, K), tally   # counts below 2^30: exact in float64
 
 
 def assignment_host(co: np.ndarray):
@@ -382,10 +387,7 @@ def assignment_host(co: np.ndarray):
 
 def durations_host(ref_mask: np.ndarray, scored: np.ndarray, speakers: np.ndarray, S: int, K: int):
     """sdk_score_durations for one recording in numpy -> (ref_frames [S] int32, hyp_frames [K] int32) over the scored frames."""
-    on = np.asarray(scored).astype(bool)
-    mask, sp = np.asarray(ref_mask, dtype=np.uint64)[on], np.asarray(speakers, dtype=np.int64).reshape(-1, 2)[on]
-    ref = (mask[:, None] >> np.arange(S, dtype=np.uint64)[None, :]) & np.uint64(1)                              # [frames, S]
-    hyp = (sp[:, :, None] == np.arange(K)[None, None, :]).any(1)                                               # [frames, K]: named twice counts once
+    _, _, ref, hyp = _active_host(ref_mask, scored, speakers, S, K)
     return ref.sum(0).astype(np.int32).reshape(S), hyp.sum(0).astype(np.int32).reshape(K)
 
 
@@ -517,12 +519,51 @@ def rasterise_references(eng, tab, references, collar_s: float = 0.0, skip_overl
     return ref
 
 
-def score_tables(eng, speakers_dev, tab, ref: PackReference, upload=None, jer: bool = False):
+@dataclass
+class ScoreTables:
+    """What score_tables leaves on the device for one pack, by name, and the layout of its one int64 download: pieces() in a fixed order,
+    `size` of them, results() to cut a downloaded slice.  The four fields from ref_frames on are None without jer=True."""
+    tally: object                             # [R, 5] int64: scored, total, missed, false_alarm, both
+    correct: object                           # [R] int64
+    mapping: object                           # [sum S_r] int32
+    co: object                                # [co_off[-1]] int32: recording r's [S_r, K_r] table at co_off[r]
+    co_off: np.ndarray                        # [R + 1] int64, on the host
+    cent_off: np.ndarray                      # [R + 1]: the tables' cent_off as it stood at the call
+    ref_off: np.ndarray                       # [R + 1]: the reference's
+    ref_frames: object = None                 # [sum S_r] int32
+    hyp_frames: object = None                 # [sum K_r] int32
+    jsum: object = None                       # [R] int64
+    jer_mapping: object = None                # [sum S_r] int32
+
+    def _tensors(self) -> list:
+        plain = [self.tally, self.correct, self.mapping, self.co]
+        return plain if self.jsum is None else plain + [self.ref_frames, self.hyp_frames, self.jsum, self.jer_mapping]
+
+    def pieces(self) -> list:
+        """The int64 pieces of the download: tally, correct, map, co, then with jer=True ref_frames, hyp_frames, jsum, jer_mapping."""
+        torch = _native()[0]
+        return [t.reshape(-1).to(torch.int64) for t in self._tensors()]
+
+    @property
+    def size(self) -> int:
+        return sum(int(t.numel()) for t in self._tensors())
+
+    def results(self, ref: PackReference, flat: np.ndarray) -> List[DerResult]:
+        """The downloaded pieces (numpy, `size` integers) cut into one DerResult per recording."""
+        cut = np.cumsum([0] + [int(t.numel()) for t in self._tensors()])
+        p = [flat[a:b] for a, b in zip(cut[:-1], cut[1:])]
+        tally, out = p[0].reshape(-1, 5), []
+        for r, names in enumerate(ref.names):
+            a, i0, i1, j0, j1 = (int(v) for v in (self.co_off[r], self.ref_off[r], self.ref_off[r + 1], self.cent_off[r], self.cent_off[r + 1]))
+            jer = None if self.jsum is None else (p[4][i0:i1], p[5][j0:j1], p[6][r], p[7][i0:i1])
+            out.append(_result(names, np.asarray(p[3][a:a + (i1 - i0) * (j1 - j0)]).reshape(i1 - i0, j1 - j0), tally[r], p[2][i0:i1], p[1][r], jer))
+        return out
+
+
+def score_tables(eng, speakers_dev, tab, ref: PackReference, upload=None, jer: bool = False) -> ScoreTables:
     """speakers [G, 2] int32 on the packed grid (device), tab with clusters set (K_r = the hypothesis speakers of recording r) ->
-    (tally [R, 5] int64, correct [R] int64, map [sum S_r] int32, co int32 [co_off[-1]], co_off [R + 1] int64 on the host), the first four
-    on the device: sdk_score_cooccur, then sdk_score_map.  Nothing is read back.  jer=True appends (ref_frames [sum S_r] int32, hyp_frames
-    [sum K_r] int32, jsum [R] int64, jer_mapping [sum S_r] int32), all on the device: sdk_score_durations, sdk_score_jaccard, then
-    sdk_score_map on the Jaccard table."""
+    ScoreTables, every tensor on the device: sdk_score_cooccur, then sdk_score_map.  Nothing is read back.  jer=True fills ref_frames,
+    hyp_frames, jsum and jer_mapping too: sdk_score_durations, sdk_score_jaccard, then sdk_score_map on the Jaccard table."""
     torch, check, _stream = _native()
     if tab.cent_off is None:
         raise ValueError("score: the tables hold no clusters (set_clusters)")
@@ -542,10 +583,11 @@ def score_tables(eng, speakers_dev, tab, ref: PackReference, upload=None, jer: b
                                     co_off_d.data_ptr(), R, tab.G, ref.max_ref, max_hyp, total, co.data_ptr(), tally.data_ptr(), _stream()), "sdk_score_cooccur")
     check(eng.lib.sdk_score_map(eng.ctx, co.data_ptr(), ref.ref_off_d.data_ptr(), tab.cent_off_d.data_ptr(), co_off_d.data_ptr(), R, ref.max_ref, max_hyp,
                                 mapping.data_ptr(), correct.data_ptr(), _stream()), "sdk_score_map")
-    out = (tally, correct, mapping[:int(ref.ref_off[-1])], co[:total], co_off)
+    n_ref = int(ref.ref_off[-1])
+    out = ScoreTables(tally, correct, mapping[:n_ref], co[:total], co_off, tab.cent_off, ref.ref_off)   # set_clusters binds a new cent_off, it never writes into this one
     if not jer:
         return out
-    n_ref, n_hyp = int(ref.ref_off[-1]), int(tab.cent_off[-1])
+    n_hyp = int(tab.cent_off[-1])
     ref_frames = torch.empty((max(n_ref, 1),), dtype=torch.int32, device=eng.device)
     hyp_frames = torch.empty((max(n_hyp, 1),), dtype=torch.int32, device=eng.device)
     q = torch.empty((max(total, 1),), dtype=torch.int32, device=eng.device)
@@ -558,49 +600,17 @@ def score_tables(eng, speakers_dev, tab, ref: PackReference, upload=None, jer: b
                                     co_off_d.data_ptr(), R, total, q.data_ptr(), _stream()), "sdk_score_jaccard")
     check(eng.lib.sdk_score_map(eng.ctx, q.data_ptr(), ref.ref_off_d.data_ptr(), tab.cent_off_d.data_ptr(), co_off_d.data_ptr(), R, ref.max_ref, max_hyp,
                                 jer_mapping.data_ptr(), jsum.data_ptr(), _stream()), "sdk_score_map")
-    return out + (ref_frames[:n_ref], hyp_frames[:n_hyp], jsum, jer_mapping[:n_ref])
-
-
-def results_from_tables(ref: PackReference, cent_off, co_off, tally, correct, mapping, co) -> List[DerResult]:
-    """The downloaded tables of score_tables (numpy) cut into one DerResult per recording."""
-    out = []
-    for r, names in enumerate(ref.names):
-        S, K = len(names), int(cent_off[r + 1] - cent_off[r])
-        a = int(co_off[r])
-        out.append(_result(names, np.asarray(co[a:a + S * K]).reshape(S, K), tally[r], mapping[int(ref.ref_off[r]):int(ref.ref_off[r + 1])], correct[r]))
+    out.ref_frames, out.hyp_frames, out.jsum, out.jer_mapping = ref_frames[:n_ref], hyp_frames[:n_hyp], jsum, jer_mapping[:n_ref]
     return out
-
-
-def results_from_tables_jer(ref: PackReference, cent_off, co_off, tally, correct, mapping, co, ref_frames, hyp_frames, jsum, jer_mapping) -> List[DerResult]:
-    """results_from_tables for the downloaded tables of score_tables(jer=True)."""
-    out = []
-    for r, names in enumerate(ref.names):
-        S, K = len(names), int(cent_off[r + 1] - cent_off[r])
-        a, i0, i1, j0, j1 = int(co_off[r]), int(ref.ref_off[r]), int(ref.ref_off[r + 1]), int(cent_off[r]), int(cent_off[r + 1])
-        out.append(_result(names, np.asarray(co[a:a + S * K]).reshape(S, K), tally[r], mapping[i0:i1], correct[r],
-                           (ref_frames[i0:i1], hyp_frames[j0:j1], jsum[r], jer_mapping[i0:i1])))
-    return out
-
-
-def join_tables(tables):
-    """What score_tables left on the device (without co_off) -> the pieces of one int64 download, in the order split_tables / split_tables_jer cut."""
-    torch = _native()[0]
-    return [t.reshape(-1).to(torch.int64) for t in tables]
 
 
 def score_grouped(eng, speakers_dev, tab, references, collar_s: float = 0.0, skip_overlap: bool = False, uems=None, jer: bool = False) -> List[DerResult]:
     """The device path for one pack: speakers [G, 2] int32 on the packed frame grid of tab (diarize_ops.GroupTables with clusters set), one
     reference turn list per recording -> one DerResult per recording.  Three kernels calls, then one download of the integer tables.  uems:
     None, or one entry per recording (None or its UEM intervals): one more call; jer=True: three more, the same one download."""
-    torch = _native()[0]
     ref = rasterise_references(eng, tab, references, collar_s, skip_overlap, uems=uems)
-    if not jer:
-        tally, correct, mapping, co, co_off = score_tables(eng, speakers_dev, tab, ref)
-        flat = torch.cat([tally.reshape(-1), correct, mapping.to(torch.int64), co.to(torch.int64)]).cpu().numpy()
-        return results_from_tables(ref, tab.cent_off, co_off, *split_tables(flat, tab.R, int(ref.ref_off[-1]), int(co_off[-1])))
-    t = score_tables(eng, speakers_dev, tab, ref, jer=True)
-    flat = torch.cat(join_tables(t[:4] + t[5:])).cpu().numpy()
-    return results_from_tables_jer(ref, tab.cent_off, t[4], *split_tables_jer(flat, tab.R, int(ref.ref_off[-1]), int(tab.cent_off[-1]), int(t[4][-1])))
+    tables = score_tables(eng, speakers_dev, tab, ref, jer=jer)
+    return tables.results(ref, _native()[0].cat(tables.pieces()).cpu().numpy())
 
 
 def score_results(eng, results, references, collar_s: float = 0.0, skip_overlap: bool = False, uems=None, jer: bool = False) -> List[DerResult]:
@@ -625,21 +635,3 @@ def score_results(eng, results, references, collar_s: float = 0.0, skip_overlap:
     tab = GroupTables(eng, np.zeros(len(results) + 1, np.int64), np.concatenate([[0], np.cumsum(G_r)]), n_samples)
     tab.set_clusters(np.concatenate([[0], np.cumsum([int(res.n_speakers) for res in results])]))
     return score_grouped(eng, torch.from_numpy(np.concatenate(spk)).to(eng.device), tab, references, collar_s, skip_overlap, uems, jer)
-
-
-def split_tables(flat: np.ndarray, R: int, n_ref: int, n_co: int):
-    """One int64 download [5 R + R + n_ref + n_co] -> (tally [R, 5], correct [R], map [n_ref], co [n_co])."""
-    a, b, c = 5 * R, 6 * R, 6 * R + n_ref
-    return flat[:a].reshape(R, 5), flat[a:b], flat[b:c], flat[c:c + n_co]
-
-
-def jer_download_size(R: int, n_ref: int, n_hyp: int, n_co: int) -> int:
-    return 7 * R + 3 * n_ref + n_hyp + n_co
-
-
-def split_tables_jer(flat: np.ndarray, R: int, n_ref: int, n_hyp: int, n_co: int):
-    """One int64 download of score_tables(jer=True) [jer_download_size] -> split_tables' four, then (ref_frames [n_ref], hyp_frames [n_hyp],
-    jsum [R], jer_mapping [n_ref])."""
-    d = 6 * R + n_ref + n_co
-    e, f, g = d + n_ref, d + n_ref + n_hyp, d + n_ref + n_hyp + R
-    return split_tables(flat, R, n_ref, n_co) + (flat[d:e], flat[e:f], flat[f:g], flat[g:g + n_ref])

@@ -38,6 +38,7 @@ from .weights_pack import ALIGN, round16, to_bits16
 SAMPLE_RATE = 16000
 CHUNK = 160000
 FRAME_HOP = 270                  # samples between frames
+FRAME_FIRST = 495                # centre sample of frame 0
 FRAME_SPAN = 991                 # samples a frame sees
 POWERSET = ((), (0,), (1,), (2,), (0, 1), (0, 2), (1, 2))
 NORM_EPS = 1e-5
@@ -396,7 +397,7 @@ def aggregate_counts(counts: np.ndarray, starts: np.ndarray, n_samples: int):
     [(270 g0 + 360) / 16000, (270 g1 + 630) / 16000)."""
     counts = np.asarray(counts)
     Cn, F = counts.shape
-    G = max(0, (n_samples - 495 + FRAME_HOP - 1) // FRAME_HOP)
+    G = max(0, (n_samples - FRAME_FIRST + FRAME_HOP - 1) // FRAME_HOP)
     sp, ov, nc = np.zeros(G), np.zeros(G), np.zeros(G)
     for c in range(Cn):
         q = (135 - int(starts[c])) // FRAME_HOP                        # i = g + q

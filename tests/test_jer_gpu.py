@@ -111,9 +111,10 @@ def test_uem_durations_jaccard_and_map_bit_for_bit(engine, collar_s, skip):
     ref = sc.rasterise_references(engine, tab, refs, collar_s, skip, uems=UEMS)
     scored = ref.scored.cpu().numpy()
     assert scored.shape == (tab.G,)
-    tally, correct, mapping, co, co_off, ref_frames, hyp_frames, jsum, jer_mapping = sc.score_tables(engine, spk, tab, ref, jer=True)
-    q, q_map, q_sum = jaccard_dev(engine, co, ref_frames, hyp_frames, ref.ref_off, tab.cent_off, co_off)
-    tally, correct, co, rf, hf, jsum, jmap = (t.cpu().numpy() for t in (tally, correct, co, ref_frames, hyp_frames, jsum, jer_mapping))
+    st = sc.score_tables(engine, spk, tab, ref, jer=True)
+    co_off = st.co_off
+    q, q_map, q_sum = jaccard_dev(engine, st.co, st.ref_frames, st.hyp_frames, ref.ref_off, tab.cent_off, co_off)
+    tally, correct, co, rf, hf, jsum, jmap = (t.cpu().numpy() for t in (st.tally, st.correct, st.co, st.ref_frames, st.hyp_frames, st.jsum, st.jer_mapping))
     assert rf.shape == (sum(S_R),) and hf.shape == (sum(K_R),) and rf.dtype == hf.dtype == q.dtype == np.int32
     assert np.array_equal(q_sum, jsum) and np.array_equal(q_map, jmap)                      # the test's own launches: the same bytes
     for r, w in enumerate(want):
@@ -230,9 +231,10 @@ def test_defaults_run_the_untouched_path(engine):
     tab = tables(engine)
     spk = torch.from_numpy(np.concatenate(hyps)).to(engine.device)
     ref = sc.rasterise_references(engine, tab, refs, 0.25, False)
-    tally, correct, mapping, co, co_off = sc.score_tables(engine, spk, tab, ref)
-    flat = torch.cat([tally.reshape(-1), correct, mapping.to(torch.int64), co.to(torch.int64)]).cpu().numpy()
-    want = sc.results_from_tables(ref, tab.cent_off, co_off, *sc.split_tables(flat, tab.R, int(ref.ref_off[-1]), int(co_off[-1])))
+    st = sc.score_tables(engine, spk, tab, ref)
+    flat = torch.cat([st.tally.reshape(-1), st.correct, st.mapping.to(torch.int64), st.co.to(torch.int64)]).cpu().numpy()
+    assert flat.shape == (st.size,) and all(getattr(st, f) is None for f in ("ref_frames", "hyp_frames", "jsum", "jer_mapping"))
+    want = st.results(ref, flat)
     host = [sc.score_host(h, n, t, 0.25, False) for h, n, t in zip(hyps, N_SAMPLES, refs)]
     d = dz.Diarizer(engine, None, None)
     for got in (sc.score_grouped(engine, spk, tab, refs, 0.25, False), sc.score_grouped(engine, spk, tab, refs, 0.25, False, uems=None, jer=False),

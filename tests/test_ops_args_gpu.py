@@ -227,4 +227,8 @@ def test_score_tables(engine, monkeypatch):
     refs, hyps = TD.pack_case(0)
     tab = TD.tables(engine, TD.N_SAMPLES, TD.K_SETS[0])
     ref = sc.rasterise_references(engine, tab, refs, 0.0, False)
-    exercise(engine, monkeypatch, lambda _, speakers: sc.score_tables(engine, speakers, tab, ref)[:4], dict(speakers=dev(np.concatenate(hyps))))
+
+    def call(_, speakers):
+        t = sc.score_tables(engine, speakers, tab, ref)
+        return t.tally, t.correct, t.mapping, t.co
+    exercise(engine, monkeypatch, call, dict(speakers=dev(np.concatenate(hyps))))

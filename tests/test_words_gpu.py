@@ -61,7 +61,21 @@ def test_rows_bit_for_bit_on_random_packs_and_twice_the_same_bytes(engine, seed)
         assert np.array_equal(lab.speaker, want[:, 0]) and np.array_equal(lab.distance, want[:, 6])
 
 
-WDER_CASES = {"small": (31, (0, 1, 3, 5, 6), (4, 0, 6, 1, 3)), "small2": (32, (6, 5, 0, 3, 1), (0, 6, 2, 5, 4)), "wide": (33, (64, 3, 64, 1, 0), (3, 64, 64, 0, 1))}
+# (seed, K_r, S_r) and, where the word counts are fixed, W_r.  "straddle": sdk_words_cooccur's workgroups take 1024 words, so the first serves
+# recording 1 and the head of recording 2, the second the tail of recording 2, then recordings 3 and 4; recording 0 has no word.
+WDER_CASES = {"small": (31, (0, 1, 3, 5, 6), (4, 0, 6, 1, 3)), "small2": (32, (6, 5, 0, 3, 1), (0, 6, 2, 5, 4)), "wide": (33, (64, 3, 64, 1, 0), (3, 64, 64, 0, 1)),
+              "straddle": (34, (3, 2, 5, 4, 3), (2, 3, 4, 5, 2), (0, 3, 1024 + 17, 301, 5))}
+
+
+def wder_case(case):
+    """The recordings (speakers, K, words) and reference labels of WDER_CASES[case]."""
+    seed, K_r, S_r, *fixed = WDER_CASES[case]
+    rng = np.random.default_rng(seed)
+    recs = []
+    for r, K in enumerate(K_r):
+        G = int(rng.integers(200, 1500))
+        recs.append((WR.random_speakers(rng, G, K), K, WR.random_words(rng, G, fixed[0][r] if fixed else 0 if r == 2 and case == "small" else int(rng.integers(50, 300)))))
+    return recs, [WR.random_reference(rng, len(words), S) for (_, _, words), S in zip(recs, S_r)]
 
 
 @pytest.mark.parametrize("case", sorted(WDER_CASES))
@@ -69,13 +83,9 @@ def test_wder_tables_bit_for_bit(engine, case):
     """co, the tallies, correct and the map of a pack against the loops; correct against the brute force where the table can be enumerated,
     against scipy's assignment where it cannot (64 a side)."""
     from scipy.optimize import linear_sum_assignment
-    seed, K_r, S_r = WDER_CASES[case]
-    rng = np.random.default_rng(seed)
-    recs = []
-    for r, K in enumerate(K_r):
-        G = int(rng.integers(200, 1500))
-        recs.append((WR.random_speakers(rng, G, K), K, WR.random_words(rng, G, 0 if r == 2 and case == "small" else int(rng.integers(50, 300)))))
-    refs = [WR.random_reference(rng, len(words), S) for (_, _, words), S in zip(recs, S_r)]
+    recs, refs = wder_case(case)
+    if case == "straddle":
+        assert [len(words) for _, _, words in recs] == [0, 3, 1041, 301, 5] and all(max(K, len(set(ref))) <= 8 for (_, K, _), ref in zip(recs, refs))
     gap = 10
     pack = wd.attribute_pack(engine, as_results(recs), as_seconds(recs), gap * WR.HOP / WR.RATE)
     got, again = wd.wder_pack(engine, pack, refs), wd.wder_pack(engine, pack, refs)

@@ -72,17 +72,17 @@ def main() -> None:
         uem_off = torch.from_numpy(np.concatenate([[0], np.cumsum([len(m) for m in merged])]).astype(np.int32)).to(eng.device)
         uem_d = torch.from_numpy(np.concatenate(merged).astype(np.int32)).to(eng.device)
         U = int(uem_d.shape[0])
-        tally, correct, mapping, co, co_off, ref_frames, hyp_frames, jsum, jer_mapping = sc.score_tables(eng, spk, tab, ref, jer=True)
-        co_off_d = torch.from_numpy(co_off).to(eng.device)
-        q = torch.empty((max(int(co_off[-1]), 1),), dtype=torch.int32, device=eng.device)
+        t = sc.score_tables(eng, spk, tab, ref, jer=True)
+        co_off_d = torch.from_numpy(t.co_off).to(eng.device)
+        q = torch.empty((max(int(t.co_off[-1]), 1),), dtype=torch.int32, device=eng.device)
         t_uem = device_ms(lambda: lib.check(eng.lib.sdk_score_uem(eng.ctx, uem_d.data_ptr(), uem_off.data_ptr(), tab.frame_off_d.data_ptr(), R, U, tab.G,
                                                                   ref.scored.data_ptr(), None), "sdk_score_uem"), a.iters)
         t_dur = device_ms(lambda: lib.check(eng.lib.sdk_score_durations(
             eng.ctx, ref.ref_mask.data_ptr(), ref.scored.data_ptr(), spk.data_ptr(), tab.frame_off_d.data_ptr(), ref.ref_off_d.data_ptr(), tab.cent_off_d.data_ptr(), R,
-            tab.G, ref.max_ref, 4, ref_frames.data_ptr(), hyp_frames.data_ptr(), None), "sdk_score_durations"), a.iters)
+            tab.G, ref.max_ref, 4, t.ref_frames.data_ptr(), t.hyp_frames.data_ptr(), None), "sdk_score_durations"), a.iters)
         t_jac = device_ms(lambda: lib.check(eng.lib.sdk_score_jaccard(
-            eng.ctx, co.data_ptr(), ref_frames.data_ptr(), hyp_frames.data_ptr(), ref.ref_off_d.data_ptr(), tab.cent_off_d.data_ptr(), co_off_d.data_ptr(), R,
-            int(co_off[-1]), q.data_ptr(), None), "sdk_score_jaccard"), a.iters)
+            eng.ctx, t.co.data_ptr(), t.ref_frames.data_ptr(), t.hyp_frames.data_ptr(), ref.ref_off_d.data_ptr(), tab.cent_off_d.data_ptr(), co_off_d.data_ptr(), R,
+            int(t.co_off[-1]), q.data_ptr(), None), "sdk_score_jaccard"), a.iters)
         t_tables = device_ms(lambda: sc.score_tables(eng, spk, tab, ref), a.iters)
         t_tables_jer = device_ms(lambda: sc.score_tables(eng, spk, tab, ref, jer=True), a.iters)
         out["scoring"].append({
