@@ -1043,6 +1043,7 @@ int sdk_affinity_topk(sdk_ctx* ctx, const float* E, const uint16_t* Eb, const fl
  *   sdk_kmeans_assign   : label[i] = nearest of kc centres (ties -> lowest), dist2, optional per-256-row-block
  *                         partial sums [nblk, kc, k] and counts [nblk, kc]
  */
+/* N at most 2^24 rows (sdk_affinity_matvec, sdk_laplacian_topk, sdk_rows_gram: more is refused, and the sizers then return 0 with sdk_last_error). */
 size_t sdk_affinity_matvec_workspace_bytes(int N);
 /* Host-only (no device): the mat-vec kernel's work decomposition, for tests.  out4 = {row groups of 512, j stages per group, workgroups,
  * partial-tile slots per group}; *units = groups * stages; workgroup i sweeps the units [i * units / workgroups, (i + 1) * units / workgroups)

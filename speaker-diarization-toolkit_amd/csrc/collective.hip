@@ -239,15 +239,19 @@ extern "C" int sdk_sym_eigh(sdk_ctx* ctx, const float* G, int k, float* Q, float
 }
 
 extern "C" size_t sdk_laplacian_topk_workspace_bytes(int N, int k) {
-  if (N <= 0 || k < 1 || k > KV) return 0;
+  if (N <= 0 || N > (1 << 24) || k < 1 || k > KV) {
+    sdk_set_error("sdk_laplacian_topk_workspace_bytes: N=%d k=%d (N 1 .. 2^24, k 1 .. %d)", N, k, KV);
+    return 0;
+  }
   return lt_layout(N, k, nullptr, nullptr);
 }
 
 extern "C" int sdk_laplacian_topk(sdk_ctx* ctx, const uint16_t* Eb_all, int N, int row0, int rows, int k, int n_iter, float* V,
                                   float* eigvals, int32_t* not_spd, void* ws, size_t ws_bytes, void* comm, int world, void* stream) {
   SDK_REQUIRE(ctx && Eb_all && V && eigvals && ws, "sdk_laplacian_topk: null argument");
-  SDK_REQUIRE(N > 0 && rows > 0 && row0 >= 0 && row0 + rows <= N && k >= 1 && k <= KV && n_iter >= 0, "sdk_laplacian_topk: bad shape (N=%d rows=%d k=%d)", N, rows, k);
-  SDK_REQUIRE(ws_bytes >= sdk_laplacian_topk_workspace_bytes(N, k) && ((uintptr_t)ws % 256) == 0, "sdk_laplacian_topk: workspace too small or misaligned");
+  SDK_REQUIRE(N > 0 && N <= (1 << 24) && rows > 0 && row0 >= 0 && row0 <= N - rows && k >= 1 && k <= KV && n_iter >= 0, "sdk_laplacian_topk: bad shape (N=%d rows=%d k=%d)", N, rows, k);
+  SDK_REQUIRE(ws_bytes >= sdk_laplacian_topk_workspace_bytes(N, k) && ((uintptr_t)ws % 256) == 0, "sdk_laplacian_topk: workspace too small or misaligned (%zu bytes at %p, %zu needed, 256-byte aligned)",
+              ws_bytes, ws, sdk_laplacian_topk_workspace_bytes(N, k));
   if (comm) {
     SDK_REQUIRE(world >= 1 && (int64_t)rows * world == N && row0 % rows == 0, "sdk_laplacian_topk: with a communicator every rank owns N / world = %d rows (got rows=%d row0=%d)", N / (world > 0 ? world : 1), rows, row0);
     if (rccl_resolve()) return 1;

@@ -860,7 +860,11 @@ __global__ __launch_bounds__(NT) void l2norm_kernel(const float* __restrict__ X,
 }  // namespace
 
 extern "C" size_t sdk_se_workspace_bytes(int B, int C, int Cse) {
-  return B > 0 ? ((size_t)B * C * 2 + (size_t)B * Cse) * sizeof(float) : 0;
+  if (!(B > 0 && C > 0 && Cse > 0)) {
+    sdk_set_error("sdk_se_workspace_bytes: B=%d C=%d Cse=%d (at least 1 each)", B, C, Cse);
+    return 0;
+  }
+  return ((size_t)B * C * 2 + (size_t)B * Cse) * sizeof(float);
 }
 
 // (sdk_ecapa_forward passes the blob's format; the exported wrapper below takes the context's "precision" option)
@@ -873,7 +877,9 @@ int se_gate_residual_impl(sdk_ctx* ctx, const uint16_t* z, int64_t ldz, const ui
   SDK_REQUIRE(C % 8 == 0 && C / 8 <= NT && NT % (C / 8) == 0, "sdk_se_gate_residual: C=%d unsupported (need C/8 | 256)", C);
   SDK_REQUIRE(Cse > 0 && Cse <= NT && NT % Cse == 0 && Cse <= C, "sdk_se_gate_residual: Cse=%d unsupported (need Cse | 256)", Cse);
   SDK_REQUIRE(ldz % 8 == 0 && ldx % 8 == 0 && ldo % 8 == 0, "sdk_se_gate_residual: row strides must be multiples of 8");
-  if (ws && ws_bytes >= sdk_se_workspace_bytes(B, C, Cse)) {
+  SDK_REQUIRE(!ws || ws_bytes >= sdk_se_workspace_bytes(B, C, Cse), "sdk_se_gate_residual: workspace of %zu bytes, %zu needed (sdk_se_workspace_bytes; ws = NULL: the one-kernel form)",
+              ws_bytes, sdk_se_workspace_bytes(B, C, Cse));
+  if (ws) {
     // split schedule: channel means (one sweep of z) -> the two gate FCs batched over all segments on the
     // matrix pipe (weights read once per 32 segments instead of once per segment) -> gate*z + x sweep
     float* mean = (float*)ws;

@@ -378,7 +378,10 @@ int aff_rowcol_top1(sdk_ctx* ctx, const float* E, const uint16_t* Eb, const floa
                     const float* resid_p, int N, int Pn, int32_t* idx, float* score, int32_t* n_rescanned, void* ws, void* stream);
 
 extern "C" size_t sdk_affinity_workspace_bytes(int N, int P) {
-  if (N <= 0 || P <= 0) return 0;
+  if (N <= 0 || P <= 0) {
+    sdk_set_error("sdk_affinity_workspace_bytes: N=%d P=%d (at least 1 each)", N, P);
+    return 0;
+  }
   const size_t a = ws_layout(N, P, nullptr, nullptr), b = aff_rowcol_workspace_bytes(N, P);
   return a > b ? a : b;
 }
@@ -391,7 +394,8 @@ extern "C" int sdk_affinity_topk(sdk_ctx* ctx, const float* E, const uint16_t* E
   SDK_REQUIRE(d == D, "sdk_affinity_topk: d=%d, this build is specialised for d=%d", d, D);
   SDK_REQUIRE(N > 0 && Pn > 0, "sdk_affinity_topk: empty problem (N=%d P=%d)", N, Pn);
   SDK_REQUIRE(k >= 1 && k <= 4 && k <= Pn, "sdk_affinity_topk: k=%d must be in [1, min(4, P)]", k);
-  SDK_REQUIRE(ws_bytes >= sdk_affinity_workspace_bytes(N, Pn), "sdk_affinity_topk: workspace too small");
+  SDK_REQUIRE(ws_bytes >= sdk_affinity_workspace_bytes(N, Pn), "sdk_affinity_topk: workspace too small (%zu bytes, %zu needed)", ws_bytes,
+              sdk_affinity_workspace_bytes(N, Pn));
   SDK_REQUIRE(((uintptr_t)E % 16) == 0 && ((uintptr_t)Eb % 16) == 0 && ((uintptr_t)P % 16) == 0 && ((uintptr_t)Pb % 16) == 0,
               "sdk_affinity_topk: matrices must be 16-byte aligned");
   if (k == 1 && ctx->aff_fast && aff_rowcol_supported(Pn))

@@ -341,7 +341,10 @@ int ecapa_forward_hp(sdk_ctx* ctx, const void* wblob, const sdk_ecapa_desc* d, c
 }  // namespace
 
 extern "C" size_t sdk_ecapa_workspace_bytes(const sdk_ecapa_desc* d, int B, int T) {
-  if (!d || B <= 0 || T <= 0) return 0;
+  if (!d || B <= 0 || T <= 0 || (int64_t)B * T >= (1ll << 31)) {
+    sdk_set_error("sdk_ecapa_workspace_bytes: d=%p B=%d T=%d (a descriptor, B and T at least 1, B*T below 2^31)", (const void*)d, B, T);
+    return 0;
+  }
   if (d->precision == 1) return fwd_layout_hp(d, B, T, nullptr, nullptr);
   return fwd_layout(d, B, T, nullptr, nullptr);
 }
@@ -589,7 +592,11 @@ size_t masked_layout(const sdk_ecapa_desc* d, int B, int T, int S, char* base, M
 }  // namespace
 
 extern "C" size_t sdk_ecapa_masked_workspace_bytes(const sdk_ecapa_desc* d, int B, int T, int S) {
-  if (!d || B <= 0 || T <= 0 || S <= 0 || d->precision == 1) return 0;
+  if (!d || B <= 0 || T <= 0 || S < 1 || S > 8 || (int64_t)B * T >= (1ll << 31) || d->precision == 1) {
+    sdk_set_error("sdk_ecapa_masked_workspace_bytes: d=%p B=%d T=%d S=%d precision=%d (a descriptor of precision 0 or 2, B and T at least 1, B*T below 2^31, S 1 .. 8)",
+                  (const void*)d, B, T, S, d ? d->precision : -1);
+    return 0;
+  }
   return masked_layout(d, B, T, S, nullptr, nullptr);
 }
 
@@ -674,7 +681,11 @@ size_t xv_layout(const sdk_xvector_desc* d, int B, int T, char* base, uint16_t**
 }  // namespace
 
 extern "C" size_t sdk_xvector_workspace_bytes(const sdk_xvector_desc* d, int B, int T) {
-  if (!d || B <= 0 || T <= 0 || d->n_frame_layers < 1 || d->n_frame_layers > 8) return 0;
+  if (!d || B <= 0 || T <= 0 || (int64_t)B * T >= (1ll << 31) || d->n_frame_layers < 1 || d->n_frame_layers > 8) {
+    sdk_set_error("sdk_xvector_workspace_bytes: d=%p B=%d T=%d n_frame_layers=%d (a descriptor of 1 .. 8 frame layers, B and T at least 1, B*T below 2^31)",
+                  (const void*)d, B, T, d ? d->n_frame_layers : -1);
+    return 0;
+  }
   return xv_layout(d, B, T, nullptr, nullptr, nullptr, nullptr);
 }
 
@@ -690,7 +701,8 @@ extern "C" int sdk_xvector_forward(sdk_ctx* ctx, const void* wblob, const sdk_xv
   else SDK_REQUIRE(ldf >= d->n_feats && ldf % 8 == 0, "sdk_xvector_forward: ldf=%d < feature width %d", ldf, d->n_feats);
   for (int l = 0; l < d->n_frame_layers; ++l)
     SDK_REQUIRE(T > (d->kernel[l] / 2) * d->dilation[l], "sdk_xvector_forward: segments of %d frames are shorter than layer %d's halo", T, l);
-  SDK_REQUIRE(ws_bytes >= sdk_xvector_workspace_bytes(d, B, T) && ((uintptr_t)ws % 256) == 0 && ((uintptr_t)wblob % 256) == 0, "sdk_xvector_forward: workspace too small or misaligned");
+  SDK_REQUIRE(ws_bytes >= sdk_xvector_workspace_bytes(d, B, T) && ((uintptr_t)ws % 256) == 0 && ((uintptr_t)wblob % 256) == 0, "sdk_xvector_forward: workspace too small or misaligned (%zu bytes at %p, %zu needed, 256-byte aligned)",
+              ws_bytes, ws, sdk_xvector_workspace_bytes(d, B, T));
   uint16_t *b0, *b1;
   float* stats;
   xv_layout(d, B, T, (char*)ws, &b0, &b1, &stats);
@@ -818,12 +830,20 @@ int rn_trunk(sdk_ctx* ctx, const char* wb, const sdk_resnet_desc* d, const uint1
 }  // namespace
 
 extern "C" size_t sdk_resnet_workspace_bytes(const sdk_resnet_desc* d, int B, int T) {
-  if (!d || B <= 0 || T <= 0 || d->n_feats <= 0) return 0;
+  if (!d || B <= 0 || T <= 0 || (int64_t)B * T >= (1ll << 31) || d->n_feats <= 0) {
+    sdk_set_error("sdk_resnet_workspace_bytes: d=%p B=%d T=%d n_feats=%d (a descriptor, B, T and n_feats at least 1, B*T below 2^31)", (const void*)d, B, T,
+                  d ? d->n_feats : -1);
+    return 0;
+  }
   return rn_layout(d, B, T, 1, nullptr, nullptr, nullptr);
 }
 
 extern "C" size_t sdk_resnet_masked_workspace_bytes(const sdk_resnet_desc* d, int B, int T, int S) {
-  if (!d || B <= 0 || T <= 0 || S <= 0 || d->n_feats <= 0) return 0;
+  if (!d || B <= 0 || T <= 0 || S <= 0 || (int64_t)B * T >= (1ll << 31) || (int64_t)B * S >= (1ll << 31) || d->n_feats <= 0) {
+    sdk_set_error("sdk_resnet_masked_workspace_bytes: d=%p B=%d T=%d S=%d n_feats=%d (a descriptor, B, T, S and n_feats at least 1, B*T and B*S below 2^31)",
+                  (const void*)d, B, T, S, d ? d->n_feats : -1);
+    return 0;
+  }
   return rn_layout(d, B, T, S, nullptr, nullptr, nullptr);
 }
 
@@ -840,7 +860,8 @@ extern "C" int sdk_resnet_forward(sdk_ctx* ctx, const void* wblob, const sdk_res
   SDK_REQUIRE(B > 0 && T >= 9 && (int64_t)B * T < (1ll << 31), "sdk_resnet_forward: bad batch (B=%d T=%d; segments need >= 9 frames)", B, T);
   SDK_REQUIRE(ldf >= d->n_feats, "sdk_resnet_forward: ldf=%d < feature width %d", ldf, d->n_feats);
   SDK_REQUIRE(ws_bytes >= sdk_resnet_workspace_bytes(d, B, T) && ((uintptr_t)ws % 256) == 0 && ((uintptr_t)wblob % 256) == 0,
-              "sdk_resnet_forward: workspace too small or misaligned");
+              "sdk_resnet_forward: workspace too small or misaligned (%zu bytes at %p, %zu needed, 256-byte aligned)", ws_bytes, ws,
+              sdk_resnet_workspace_bytes(d, B, T));
   uint16_t* buf[3];
   float* stats;
   rn_layout(d, B, T, 1, (char*)ws, buf, &stats);

@@ -154,13 +154,15 @@ extern "C" int sdk_smooth_turns(sdk_ctx* ctx, int32_t* speakers, const int32_t* 
   SDK_REQUIRE(cap == 1 || cap == 2, "sdk_smooth_turns: cap=%d (1 or 2 speakers per frame)", cap);
   SDK_REQUIRE(frame_off && cent_off && tallies && (G == 0 || speakers), "sdk_smooth_turns: null argument");
   hipStream_t st = (hipStream_t)stream;
+  if (G > 0) {                                         // every refusal comes before the first write: a refused call leaves tallies as they were
+    const size_t need = sdk_smooth_turns_workspace_bytes(G);
+    SDK_REQUIRE(ws, "sdk_smooth_turns: null workspace (%zu bytes needed, sdk_smooth_turns_workspace_bytes)", need);
+    SDK_REQUIRE(ws_bytes >= need, "sdk_smooth_turns: workspace of %zu bytes, %zu needed (sdk_smooth_turns_workspace_bytes)", ws_bytes, need);
+    SDK_REQUIRE(((uintptr_t)ws & 15) == 0 && ((uintptr_t)speakers & 7) == 0, "sdk_smooth_turns: ws=%p must be 16-byte and speakers=%p 8-byte aligned", ws,
+                (void*)speakers);
+  }
   SDK_HIP_OK(hipMemsetAsync(tallies, 0, (size_t)R * 2 * sizeof(int32_t), st));
   if (G == 0) return 0;
-  const size_t need = sdk_smooth_turns_workspace_bytes(G);
-  SDK_REQUIRE(ws, "sdk_smooth_turns: null workspace (%zu bytes needed, sdk_smooth_turns_workspace_bytes)", need);
-  SDK_REQUIRE(ws_bytes >= need, "sdk_smooth_turns: workspace of %zu bytes, %zu needed (sdk_smooth_turns_workspace_bytes)", ws_bytes, need);
-  SDK_REQUIRE(((uintptr_t)ws & 15) == 0 && ((uintptr_t)speakers & 7) == 0, "sdk_smooth_turns: ws=%p must be 16-byte and speakers=%p 8-byte aligned", ws,
-              (void*)speakers);
   int4* ent = static_cast<int4*>(ws);
   int2* mid = reinterpret_cast<int2*>(ent + G);
   const dim3 grid = pg_grid(G, SMT_NT), nt(SMT_NT);

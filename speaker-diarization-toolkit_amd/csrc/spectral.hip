@@ -493,12 +493,16 @@ __global__ __launch_bounds__(64) void chol_inverse_kernel(const float* __restric
 
 }  // namespace
 
+constexpr int MV_MAX_N = 1 << 24;       // rows: the tile and fragment counts of the kernels are 32-bit (N / 32 tiles x 128 threads)
 static size_t mv_xp_bytes(int N) { return (((size_t)((N + PT - 1) / PT) * 4 * 64 * 8 * sizeof(uint16_t)) + 255) & ~(size_t)255; }
 // partial Y tiles: groups x maxp tiles of 64 KiB; maxp <= G / ngroups + 3, so groups x maxp <= G + 3 groups for any row block of <= N rows
 static size_t mv_ypart_bytes(int N) { return ((size_t)MV_MAX_WG + 3 * (size_t)ceil_div(N, MV_SEGS)) * MV_SEGS * KV * sizeof(float); }
 
 extern "C" size_t sdk_affinity_matvec_workspace_bytes(int N) {
-  if (N <= 0) return 0;
+  if (N <= 0 || N > MV_MAX_N) {
+    sdk_set_error("sdk_affinity_matvec_workspace_bytes: N=%d (1 .. %d)", N, MV_MAX_N);
+    return 0;
+  }
   // packed X fragments | partial Y tiles of the parts of every row group | part counts
   return mv_xp_bytes(N) + mv_ypart_bytes(N) + (size_t)ceil_div(N, MV_SEGS) * sizeof(int32_t) + 256;
 }
@@ -515,9 +519,11 @@ extern "C" int sdk_affinity_matvec(sdk_ctx* ctx, const uint16_t* Eb, int N, int 
                                    const float* xscale, int kv, float* Y, void* ws, size_t ws_bytes, void* stream) {
   SDK_REQUIRE(ctx && Eb && X && Y && ws, "sdk_affinity_matvec: null argument");
   SDK_REQUIRE(d == D, "sdk_affinity_matvec: d=%d, this build is specialised for d=%d", d, D);
-  SDK_REQUIRE(N > 0 && rows > 0 && row0 >= 0 && row0 + rows <= N, "sdk_affinity_matvec: bad row block [%d, %d) of %d", row0, row0 + rows, N);
+  SDK_REQUIRE(N > 0 && N <= MV_MAX_N, "sdk_affinity_matvec: N=%d (1 .. %d)", N, MV_MAX_N);
+  SDK_REQUIRE(rows > 0 && row0 >= 0 && row0 <= N - rows, "sdk_affinity_matvec: bad row block [%d, %d + %d) of %d", row0, row0, rows, N);
   SDK_REQUIRE(kv >= 1 && kv <= KV, "sdk_affinity_matvec: kv=%d must be in [1, %d]", kv, KV);
-  SDK_REQUIRE(ws_bytes >= sdk_affinity_matvec_workspace_bytes(N), "sdk_affinity_matvec: workspace too small");
+  SDK_REQUIRE(ws_bytes >= sdk_affinity_matvec_workspace_bytes(N), "sdk_affinity_matvec: workspace too small (%zu bytes, %zu needed)", ws_bytes,
+              sdk_affinity_matvec_workspace_bytes(N));
   SDK_REQUIRE(((uintptr_t)Eb % 16) == 0 && ((uintptr_t)ws % 16) == 0, "sdk_affinity_matvec: Eb/ws must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   const int ntiles = ceil_div(N, PT);
@@ -547,13 +553,20 @@ extern "C" int sdk_affinity_matvec(sdk_ctx* ctx, const uint16_t* Eb, int N, int 
   return 0;
 }
 
-extern "C" size_t sdk_rows_gram_workspace_bytes(int n, int k) { return n > 0 ? (size_t)ceil_div(n, GR_ROWS) * k * k * sizeof(float) : 0; }
+extern "C" size_t sdk_rows_gram_workspace_bytes(int n, int k) {
+  if (!(n > 0 && n <= MV_MAX_N && k >= 1 && k <= KV)) {
+    sdk_set_error("sdk_rows_gram_workspace_bytes: n=%d k=%d (n 1 .. %d, k 1 .. %d)", n, k, MV_MAX_N, KV);
+    return 0;
+  }
+  return (size_t)ceil_div(n, GR_ROWS) * k * k * sizeof(float);
+}
 
 extern "C" int sdk_rows_gram(sdk_ctx* ctx, const float* X, const float* Yv, int n, int k, float* G, void* ws, size_t ws_bytes,
                              void* stream) {
   SDK_REQUIRE(ctx && X && Yv && G && ws, "sdk_rows_gram: null argument");
-  SDK_REQUIRE(n > 0 && k >= 1 && k <= KV, "sdk_rows_gram: bad shape n=%d k=%d", n, k);
-  SDK_REQUIRE(ws_bytes >= sdk_rows_gram_workspace_bytes(n, k), "sdk_rows_gram: workspace too small");
+  SDK_REQUIRE(n > 0 && n <= MV_MAX_N && k >= 1 && k <= KV, "sdk_rows_gram: bad shape n=%d k=%d (n 1 .. %d, k 1 .. %d)", n, k, MV_MAX_N, KV);
+  SDK_REQUIRE(ws_bytes >= sdk_rows_gram_workspace_bytes(n, k), "sdk_rows_gram: workspace too small (%zu bytes, %zu needed)", ws_bytes,
+              sdk_rows_gram_workspace_bytes(n, k));
   const int nb = ceil_div(n, GR_ROWS);
   hipLaunchKernelGGL(gram_partial_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, X, Yv, n, k, (float*)ws);
   SDK_LAUNCH_CHECK();

@@ -272,7 +272,12 @@ inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)
               (long long)state_bytes, (long long)sdk_stream_state_bytes(R, capacity, d))
 
 extern "C" int64_t sdk_stream_state_bytes(int R, int capacity, int d) {
-  return st_shape_ok(R, capacity, d) ? (int64_t)R * st_layout(capacity, d).per : 0;
+  if (!st_shape_ok(R, capacity, d)) {
+    sdk_set_error("sdk_stream_state_bytes: R=%d capacity=%d d=%d (R 1 .. 2^20, capacity 1 .. %d, d a multiple of 64 up to %d)", R, capacity, d, ST_MAXK,
+                  DZ_MAX_D);
+    return 0;
+  }
+  return (int64_t)R * st_layout(capacity, d).per;
 }
 
 extern "C" int sdk_stream_reset(sdk_ctx* ctx, void* state, int64_t state_bytes, int R, int capacity, int d, const uint8_t* which, void* stream) {
