@@ -18,6 +18,15 @@
  *   - bf16 tensors are passed as uint16_t* (raw bfloat16 bits).
  *   - "rows" of an activation tensor are frames: row m = segment (m / T), frame (m % T),
  *     channel-last, row stride given explicitly (ld*, in elements).
+ *   - the workspace protocol, the same for every entry point that takes (ws, ws_bytes): the caller asks the entry point's
+ *     sdk_*_workspace_bytes for a byte count (0 with sdk_last_error: arguments the call would refuse too), passes a device buffer of at
+ *     least that many bytes, and the library assumes nothing about its contents and writes nothing past the count.  The call checks the
+ *     workspace in three steps, each with its own message, each returning non-zero before anything is written or enqueued:
+ *         "<fn>: null workspace (<need> bytes needed, <sizer>)"
+ *         "<fn>: workspace of <ws_bytes> bytes, <need> needed (<sizer>)"
+ *         "<fn>: ws=<address> must be <align>-byte aligned"
+ *     The alignment is the one stated at the entry point (DESIGN.md lists them in one table); the arrays inside are carved in a fixed
+ *     order, each rounded up to 256 bytes (csrc/workspace.hpp), by the one layout function the sizer and the call share.
  *
  * STABLE SURFACE - what a backend binds (INTEGRATION.md shows the stub); SDK_ABI_VERSION changes when any of these does:
  *     sdk_abi_version  sdk_init  sdk_shutdown  sdk_last_error  sdk_get_device_info

@@ -863,21 +863,16 @@ __global__ void copy_count_kernel(const int32_t* src, int32_t* dst) { *dst = *sr
 struct Ws {
   float* stats; int32_t* part_base; int32_t* part_cnt; int32_t* flag_count; int32_t* flag_rows; unsigned long long* row_best; int32_t* quad_done;
 };
-inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-size_t ws_layout(int N, int P, char* base, Ws* w) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += al256(bytes); return p; };
+size_t aff_rowcol_carve(WsCarver c, int N, int P, Ws* w) {
   const size_t ngroups_max = (size_t)(N + 31) / 32;            // the smallest group any variant uses (the block plan: 32 segments)
-  char* a = take((size_t)N * MAXP * 2 * 8 * 4);
-  char* b = take(ngroups_max * MAXP * 4);
-  char* c = take(ngroups_max * 4);
-  char* d = take(256);                                          // flag_count
-  char* e = take((size_t)N * 4);
-  char* f1 = take((size_t)N * 8);                                // per flagged row: 64-bit (score, index) key the rescan's slices fold into
-  char* g = take(((size_t)N / RS_ROWS + 1) * 4);
-  if (w) { w->stats = (float*)a; w->part_base = (int32_t*)b; w->part_cnt = (int32_t*)c; w->flag_count = (int32_t*)d;
-           w->flag_rows = (int32_t*)e; w->row_best = (unsigned long long*)f1; w->quad_done = (int32_t*)g; }
-  return off;
+  w->stats = c.take<float>((size_t)N * MAXP * 2 * 8);
+  w->part_base = c.take<int32_t>(ngroups_max * MAXP);
+  w->part_cnt = c.take<int32_t>(ngroups_max);
+  w->flag_count = c.take<int32_t>(64);                          // (256 bytes of its own)
+  w->flag_rows = c.take<int32_t>((size_t)N);
+  w->row_best = c.take<unsigned long long>((size_t)N);          // per flagged row: 64-bit (score, index) key the rescan's slices fold into
+  w->quad_done = c.take<int32_t>((size_t)N / RS_ROWS + 1);
+  return c.bytes();
 }
 
 // Work decomposition of the coarse kernel (host side; the kernel derives each workgroup's range from it).
@@ -914,7 +909,10 @@ int launch_coarse(sdk_ctx* ctx, const bf16_t* Eb, const bf16_t* Pb, int N, int P
 
 }  // namespace
 
-size_t aff_rowcol_workspace_bytes(int N, int P) { return ws_layout(N, P, nullptr, nullptr); }
+size_t aff_rowcol_workspace_bytes(int N, int P) {
+  Ws w;
+  return aff_rowcol_carve({}, N, P, &w);
+}
 
 // Host-only view of the decomposition for tests (no device needed): out = {groups, stages per group, workgroups, segments per
 // group, record slots per segment}, units = groups * stages.  Workgroup i sweeps units [i*units/wg, (i+1)*units/wg).
@@ -963,7 +961,7 @@ int aff_rowcol_top1(sdk_ctx* ctx, const float* E, const uint16_t* Eb, const floa
                     void* stream) {
   hipStream_t s = (hipStream_t)stream;
   Ws w;
-  ws_layout(N, Pn, (char*)ws, &w);
+  aff_rowcol_carve({(char*)ws, 0}, N, Pn, &w);
   // no memset: the coarse kernel zeroes the uncertain-row counter, the exact pass zeroes the rescan's arrival counters
   int segs;
   {

@@ -68,7 +68,6 @@ struct AhcTableArgs {
 
 // per-problem region: D [n][n] f64 | nnd [n] f64 | nn [n] i32 | sz [n] i32 | id [n] i32
 __host__ __device__ inline int64_t r256(int64_t b) { return (b + 255) & ~(int64_t)255; }
-__host__ __device__ inline int64_t region_bytes(int64_t n) { return r256(n * n * 8) + r256(n * 8) + 3 * r256(n * 4); }
 __host__ __device__ inline int64_t tiles_of(int64_t n) { const int64_t t = (n + TILE - 1) / TILE; return t * (t + 1) / 2; }
 
 struct Region {
@@ -86,8 +85,14 @@ __device__ inline Region region(char* ws, const AhcProb& p) {
   return r;
 }
 
-// the table lives at the start of the workspace
-__host__ __device__ inline int64_t table_bytes(int G) { return r256((int64_t)G * (int64_t)sizeof(AhcProb)); }
+// the host's side of region(): the same five arrays in the same order -> the region's byte offset in the workspace
+inline int64_t region_carve(WsCarver& c, int64_t n) {
+  const int64_t off = (int64_t)c.bytes();
+  c.take<double>((size_t)(n * n));
+  c.take<double>((size_t)n);
+  for (int i = 0; i < 3; ++i) c.take<int32_t>((size_t)n);
+  return off;
+}
 
 __global__ void ahc_table_kernel(AhcProb* tab, AhcTableArgs a) {
   const int i = threadIdx.x;
@@ -415,9 +420,10 @@ __global__ void __launch_bounds__(MERGE_THREADS) ahc_merge_kernel(const AhcProb*
 }  // namespace
 
 size_t ahc_workspace_bytes(const int32_t* offsets, int G) {
-  int64_t b = table_bytes(G);
-  for (int g = 0; g < G; ++g) b += region_bytes((int64_t)offsets[g + 1] - offsets[g]);
-  return (size_t)b;
+  WsCarver c{};
+  c.take<AhcProb>((size_t)G);                          // the table lives at the start of the workspace
+  for (int g = 0; g < G; ++g) region_carve(c, (int64_t)offsets[g + 1] - offsets[g]);
+  return c.bytes();
 }
 
 namespace {
@@ -425,11 +431,12 @@ namespace {
 int launch_all(const char* fn, sdk_ctx* ctx, const float* E, int ldE, int dim, const int32_t* group, const int32_t* offsets, int G, double stop, double* Z,
                int32_t* merges, int32_t* status, void* ws, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  AhcProb* tab = (AhcProb*)ws;
+  WsCarver carve{(char*)ws, 0};
+  AhcProb* tab = carve.take<AhcProb>((size_t)G);
   int64_t tiles = 0;
   for (int g = 0; g < G; ++g) tiles += tiles_of((int64_t)offsets[g + 1] - offsets[g]);
   SDK_REQUIRE(tiles < (int64_t)INT32_MAX, "%s: %lld distance tiles exceed one launch", fn, (long long)tiles);
-  int64_t off = table_bytes(G), max_n = 0;
+  int64_t max_n = 0;
   tiles = 0;
   AhcTableArgs a;
   memset(&a, 0, sizeof(a));
@@ -439,8 +446,7 @@ int launch_all(const char* fn, sdk_ctx* ctx, const float* E, int ldE, int dim, c
     for (int i = 0; i < a.count; ++i) {
       const int g = g0 + i;
       const int64_t n = (int64_t)offsets[g + 1] - offsets[g];
-      a.p[i] = AhcProb{offsets[g], n, off, tiles, (int64_t)offsets[g] - g, 0};
-      off += region_bytes(n);
+      a.p[i] = AhcProb{offsets[g], n, region_carve(carve, n), tiles, (int64_t)offsets[g] - g, 0};
       tiles += tiles_of(n);
       max_n = n > max_n ? n : max_n;
     }

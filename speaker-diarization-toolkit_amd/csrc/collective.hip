@@ -151,37 +151,30 @@ __global__ __launch_bounds__(64) void jacobi_eigh_kernel(const float* __restrict
   }
 }
 
-inline size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct LtWs {
   float *Xall, *Y, *dinv_all, *dinv_loc, *V2, *SV, *G, *Rinv, *eye, *Q;
   int32_t* flag;
   char *mv, *gram;
   size_t mv_bytes, gram_bytes;
 };
-size_t lt_layout(int N, int k, char* base, LtWs* w) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += a256(bytes); return p; };
-  char* xall = take((size_t)N * k * 4);
-  char* y = take((size_t)N * k * 4);
-  char* da = take((size_t)N * 4);
-  char* dl = take((size_t)N * 4);
-  char* v2 = take((size_t)N * k * 4);
-  char* sv = take((size_t)N * k * 4);
-  char* g = take(KV * KV * 4);
-  char* ri = take(KV * KV * 4);
-  char* ey = take(KV * KV * 4);
-  char* q = take(KV * KV * 4);
-  char* fl = take(256);
-  const size_t mvb = sdk_affinity_matvec_workspace_bytes(N), grb = sdk_rows_gram_workspace_bytes(N, k);
-  char* mv = take(mvb);
-  char* gr = take(grb);
-  if (w) {
-    w->Xall = (float*)xall; w->Y = (float*)y; w->dinv_all = (float*)da; w->dinv_loc = (float*)dl; w->V2 = (float*)v2; w->SV = (float*)sv;
-    w->G = (float*)g; w->Rinv = (float*)ri; w->eye = (float*)ey; w->Q = (float*)q; w->flag = (int32_t*)fl; w->mv = mv; w->gram = gr;
-    w->mv_bytes = mvb; w->gram_bytes = grb;
-  }
-  return off;
+size_t lt_carve(WsCarver c, int N, int k, LtWs* w) {
+  const size_t Nk = (size_t)N * k;
+  w->Xall = c.take<float>(Nk);
+  w->Y = c.take<float>(Nk);
+  w->dinv_all = c.take<float>((size_t)N);
+  w->dinv_loc = c.take<float>((size_t)N);
+  w->V2 = c.take<float>(Nk);
+  w->SV = c.take<float>(Nk);
+  w->G = c.take<float>(KV * KV);
+  w->Rinv = c.take<float>(KV * KV);
+  w->eye = c.take<float>(KV * KV);
+  w->Q = c.take<float>(KV * KV);
+  w->flag = c.take<int32_t>(64);                               // (256 bytes of its own)
+  w->mv_bytes = sdk_affinity_matvec_workspace_bytes(N);
+  w->gram_bytes = sdk_rows_gram_workspace_bytes(N, k);
+  w->mv = c.take<char>(w->mv_bytes);
+  w->gram = c.take<char>(w->gram_bytes);
+  return c.bytes();
 }
 
 }  // namespace
@@ -243,15 +236,15 @@ extern "C" size_t sdk_laplacian_topk_workspace_bytes(int N, int k) {
     sdk_set_error("sdk_laplacian_topk_workspace_bytes: N=%d k=%d (N 1 .. 2^24, k 1 .. %d)", N, k, KV);
     return 0;
   }
-  return lt_layout(N, k, nullptr, nullptr);
+  LtWs w;
+  return lt_carve({}, N, k, &w);
 }
 
 extern "C" int sdk_laplacian_topk(sdk_ctx* ctx, const uint16_t* Eb_all, int N, int row0, int rows, int k, int n_iter, float* V,
                                   float* eigvals, int32_t* not_spd, void* ws, size_t ws_bytes, void* comm, int world, void* stream) {
   SDK_REQUIRE(ctx && Eb_all && V && eigvals && ws, "sdk_laplacian_topk: null argument");
   SDK_REQUIRE(N > 0 && N <= (1 << 24) && rows > 0 && row0 >= 0 && row0 <= N - rows && k >= 1 && k <= KV && n_iter >= 0, "sdk_laplacian_topk: bad shape (N=%d rows=%d k=%d)", N, rows, k);
-  SDK_REQUIRE(ws_bytes >= sdk_laplacian_topk_workspace_bytes(N, k) && ((uintptr_t)ws % 256) == 0, "sdk_laplacian_topk: workspace too small or misaligned (%zu bytes at %p, %zu needed, 256-byte aligned)",
-              ws_bytes, ws, sdk_laplacian_topk_workspace_bytes(N, k));
+  SDK_REQUIRE_WS("sdk_laplacian_topk", "sdk_laplacian_topk_workspace_bytes", ws, ws_bytes, sdk_laplacian_topk_workspace_bytes(N, k), 256);
   if (comm) {
     SDK_REQUIRE(world >= 1 && (int64_t)rows * world == N && row0 % rows == 0, "sdk_laplacian_topk: with a communicator every rank owns N / world = %d rows (got rows=%d row0=%d)", N / (world > 0 ? world : 1), rows, row0);
     if (rccl_resolve()) return 1;
@@ -260,7 +253,7 @@ extern "C" int sdk_laplacian_topk(sdk_ctx* ctx, const uint16_t* Eb_all, int N, i
   }
   hipStream_t s = (hipStream_t)stream;
   LtWs w;
-  lt_layout(N, k, (char*)ws, &w);
+  lt_carve({(char*)ws, 0}, N, k, &w);
   auto grid = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
   auto gather = [&](const float* loc, float* all, int width) -> int {     // rows x width floats per rank -> N x width
     if (!comm) {

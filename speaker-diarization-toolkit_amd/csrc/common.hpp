@@ -135,6 +135,8 @@ void sdk_set_error(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
     }                                                                              \
   } while (0)
 
+#include "workspace.hpp"   // ws_round, WsCarver, SDK_REQUIRE_WS
+
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 // ---------------------------------------------------------------- device helpers

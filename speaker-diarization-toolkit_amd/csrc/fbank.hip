@@ -428,7 +428,7 @@ extern "C" int sdk_fbank_tables_fill(void* host_dst, size_t bytes) {
 
 extern "C" size_t sdk_fbank_workspace_bytes(int B, int S) {
   if (B <= 0 || S <= 0) {
-    sdk_set_error("sdk_fbank_workspace_bytes: B=%d S=%d (at least 1 each)", B, S);
+    sdk_set_error("sdk_fbank_workspace_bytes: empty batch (B=%d S=%d: at least 1 each)", B, S);       // the words of the calls' own refusal
     return 0;
   }
   return (size_t)B * (size_t)(1 + S / HOP) * NMEL * sizeof(float);
@@ -442,7 +442,7 @@ static int fbank_launch(sdk_ctx* ctx, const int16_t* pcm, const int32_t* starts,
   const bool hp = precision == 1;
   if (hp) SDK_REQUIRE((ldf >> 1) >= NMEL && ldf % 16 == 0, "%s: precise mode writes planes: ldf=%d must be >= 160 and a multiple of 16", who, ldf);
   SDK_REQUIRE(ldf >= NMEL && ldf % 8 == 0, "%s: ldf=%d must be >= 80 and a multiple of 8", who, ldf);
-  SDK_REQUIRE(ws_bytes >= sdk_fbank_workspace_bytes(B, S), "%s: workspace too small (%zu bytes, %zu needed)", who, ws_bytes, sdk_fbank_workspace_bytes(B, S));
+  SDK_REQUIRE_WS(who, "sdk_fbank_workspace_bytes", ws, ws_bytes, sdk_fbank_workspace_bytes(B, S), 1);
   SDK_REQUIRE(((uintptr_t)feats % 16) == 0 && ((uintptr_t)tabs % 16) == 0, "%s: feats/tabs must be 16-byte aligned", who);
   const int T = 1 + S / HOP;
   const int tps = ceil_div(T, FT);

@@ -35,8 +35,6 @@ constexpr int KM_TJ = 64;            // columns per LDS tile
 constexpr int KM_SEG = 1024;         // rows per segment of the centre sums (cluster.KMEANS_SEGMENT)
 constexpr int KM_ST_NONFINITE = 1;
 
-inline size_t km_align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct KmWs {
   double* Ct;        // [d][64] centres, transposed
   double* maxcos;    // [n]
@@ -48,20 +46,17 @@ struct KmWs {
   int32_t* changed;
 };
 
-size_t km_carve(char* base, int n, int d, int k, KmWs* w) {
+size_t km_carve(WsCarver c, int n, int d, int k, KmWs* w) {
   const size_t nblk = (size_t)(n + KM_NT - 1) / KM_NT, nseg = (size_t)(n + KM_SEG - 1) / KM_SEG;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { char* p = base + o; o += km_align256(bytes); return p; };
-  double* Ct = reinterpret_cast<double*>(take((size_t)d * KM_MAX_K * sizeof(double)));
-  double* maxcos = reinterpret_cast<double*>(take((size_t)n * sizeof(double)));
-  double* sval = reinterpret_cast<double*>(take(nblk * sizeof(double)));
-  int32_t* srow = reinterpret_cast<int32_t*>(take(nblk * sizeof(int32_t)));
-  double* psum = reinterpret_cast<double*>(take(nseg * k * d * sizeof(double)));
-  int32_t* pcnt = reinterpret_cast<int32_t*>(take(nseg * k * sizeof(int32_t)));
-  int32_t* done = reinterpret_cast<int32_t*>(take(sizeof(int32_t)));
-  int32_t* changed = reinterpret_cast<int32_t*>(take(sizeof(int32_t)));
-  if (w) *w = KmWs{Ct, maxcos, sval, srow, psum, pcnt, done, changed};
-  return o;
+  w->Ct = c.take<double>((size_t)d * KM_MAX_K);
+  w->maxcos = c.take<double>(n);
+  w->sval = c.take<double>(nblk);
+  w->srow = c.take<int32_t>(nblk);
+  w->psum = c.take<double>(nseg * k * d);
+  w->pcnt = c.take<int32_t>(nseg * k);
+  w->done = c.take<int32_t>(1);
+  w->changed = c.take<int32_t>(1);
+  return c.bytes();
 }
 
 bool km_shape_ok(int n, int d, int k) {
@@ -275,7 +270,8 @@ extern "C" size_t sdk_kmeans_rows_workspace_bytes(int n, int d, int k) {
                   KM_MAX_D, KM_MAX_K);
     return 0;
   }
-  return km_carve(nullptr, n, d, k, nullptr);
+  KmWs w;
+  return km_carve({}, n, d, k, &w);
 }
 
 extern "C" int sdk_kmeans_rows(sdk_ctx* ctx, const float* E, const int32_t* rows, int n, int d, int k, int max_iters, int32_t* labels,
@@ -287,11 +283,9 @@ extern "C" int sdk_kmeans_rows(sdk_ctx* ctx, const float* E, const int32_t* rows
   SDK_REQUIRE(max_iters >= 1 && max_iters <= 1000, "sdk_kmeans_rows: max_iters=%d (1 .. 1000)", max_iters);
   SDK_REQUIRE(E && rows && labels && n_iter && status && ws, "sdk_kmeans_rows: null argument (E=%p rows=%p labels=%p n_iter=%p status=%p ws=%p)",
               (const void*)E, (const void*)rows, (void*)labels, (void*)n_iter, (void*)status, ws);
-  const size_t need = km_carve(nullptr, n, d, k, nullptr);
-  SDK_REQUIRE(ws_bytes >= need, "sdk_kmeans_rows: workspace of %zu bytes, %zu needed", ws_bytes, need);
-  SDK_REQUIRE(((uintptr_t)ws & 255) == 0, "sdk_kmeans_rows: ws=%p must be 256-byte aligned", ws);
+  SDK_REQUIRE_WS("sdk_kmeans_rows", "sdk_kmeans_rows_workspace_bytes", ws, ws_bytes, sdk_kmeans_rows_workspace_bytes(n, d, k), 256);
   KmWs w;
-  km_carve(static_cast<char*>(ws), n, d, k, &w);
+  km_carve({static_cast<char*>(ws), 0}, n, d, k, &w);
   const int nblk = (n + KM_NT - 1) / KM_NT, nseg = (n + KM_SEG - 1) / KM_SEG;
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(ctx, stream, SDK_K_COPY, 2.0 * max_iters * (double)n * k * d, (double)max_iters * n * (8.0 * d + 8.0));

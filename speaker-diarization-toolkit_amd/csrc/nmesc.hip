@@ -42,7 +42,16 @@ constexpr int KNN_TJ = 64;           // columns per LDS tile
 constexpr int KNN_CH = 256;          // source rows per chunk of the reverse fill
 constexpr int KNN_MAX_KV = 32;       // the widest block of the mat-vec (THIN_MAX)
 
-inline size_t knn_align256(size_t v) { return (v + 255) & ~(size_t)255; }
+struct KnnWs {
+  int32_t* cnt;      // [ceil(n / KNN_CH)][n] reverse-edge counts per chunk of source rows
+  int32_t* tot;      // [n]
+};
+size_t knn_carve(WsCarver c, int n, KnnWs* w) {
+  const size_t nch = (size_t)(n + KNN_CH - 1) / KNN_CH;
+  w->cnt = c.take<int32_t>(nch * n);
+  w->tot = c.take<int32_t>(n);
+  return c.bytes();
+}
 
 bool knn_shape_ok(int n, int P) { return n >= 2 && n <= KNN_MAX_ROWS && P == (n - 1 < KNN_P_MAX ? n - 1 : KNN_P_MAX); }
 
@@ -244,8 +253,8 @@ extern "C" size_t sdk_knn_reverse_workspace_bytes(int n, int P) {
     sdk_set_error("sdk_knn_reverse_workspace_bytes: n=%d P=%d (n 2 .. %d, P = min(%d, n - 1))", n, P, KNN_MAX_ROWS, KNN_P_MAX);
     return 0;
   }
-  const size_t nch = (size_t)(n + KNN_CH - 1) / KNN_CH;
-  return knn_align256(nch * n * sizeof(int32_t)) + knn_align256((size_t)n * sizeof(int32_t));
+  KnnWs w;
+  return knn_carve({}, n, &w);
 }
 
 extern "C" int sdk_knn_reverse(sdk_ctx* ctx, const int32_t* idx, int n, int P, int32_t* rev_off, int32_t* rev_src, int32_t* rev_rank,
@@ -254,13 +263,12 @@ extern "C" int sdk_knn_reverse(sdk_ctx* ctx, const int32_t* idx, int n, int P, i
   SDK_REQUIRE(knn_shape_ok(n, P), "sdk_knn_reverse: n=%d P=%d (n 2 .. %d, P = min(%d, n - 1))", n, P, KNN_MAX_ROWS, KNN_P_MAX);
   SDK_REQUIRE(idx && rev_off && rev_src && rev_rank && status && ws, "sdk_knn_reverse: null argument (idx=%p rev_off=%p rev_src=%p rev_rank=%p status=%p ws=%p)",
               (const void*)idx, (void*)rev_off, (void*)rev_src, (void*)rev_rank, (void*)status, ws);
-  const size_t need = sdk_knn_reverse_workspace_bytes(n, P);
-  SDK_REQUIRE(ws_bytes >= need, "sdk_knn_reverse: workspace of %zu bytes, %zu needed", ws_bytes, need);
-  SDK_REQUIRE(((uintptr_t)ws & 255) == 0, "sdk_knn_reverse: ws=%p must be 256-byte aligned", ws);
+  SDK_REQUIRE_WS("sdk_knn_reverse", "sdk_knn_reverse_workspace_bytes", ws, ws_bytes, sdk_knn_reverse_workspace_bytes(n, P), 256);
   const int nch = (n + KNN_CH - 1) / KNN_CH;
-  const size_t cnt_bytes = knn_align256((size_t)nch * n * sizeof(int32_t));
-  int32_t* cnt = static_cast<int32_t*>(ws);
-  int32_t* tot = reinterpret_cast<int32_t*>(static_cast<char*>(ws) + cnt_bytes);
+  KnnWs w;
+  knn_carve({static_cast<char*>(ws), 0}, n, &w);
+  int32_t *const cnt = w.cnt, *const tot = w.tot;
+  const size_t cnt_bytes = ws_round((size_t)nch * n * sizeof(int32_t));
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(ctx, stream, SDK_K_COPY, 0.0, 16.0 * (double)n * P + 8.0 * (double)nch * n);
   SDK_HIP_OK(hipMemsetAsync(cnt, 0, cnt_bytes, st));

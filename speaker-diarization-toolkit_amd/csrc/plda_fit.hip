@@ -232,8 +232,6 @@ __global__ __launch_bounds__(PLDA_NT) void pf_project_kernel(const float* __rest
              [&](int r, int j, double x2) { if (i0 + r < n) X2[(i0 + r) * D0 + j] = x2; });
 }
 
-inline size_t pf_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 inline int pf_row_block(int n) { return max(512, 64 * ((n + 16383) / 16384)); }
 
 struct PfWs {
@@ -241,22 +239,13 @@ struct PfWs {
   int64_t* off;
 };
 
-// the workspace: offsets of its four parts and its size, without forming a pointer
-struct PfLayout {
-  size_t scale, colpart, scatpart, off, bytes;
-};
-
-PfLayout pf_layout(int n, int d, int K, int with_scatter) {
+size_t pf_carve(WsCarver c, int n, int d, int K, int with_scatter, PfWs* w) {
   const size_t nblk = (size_t)(n + pf_row_block(n) - 1) / pf_row_block(n);
-  PfLayout l;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += pf_align(bytes); return at; };
-  l.scale = take((size_t)n * 8);
-  l.colpart = take(nblk * d * 8);
-  l.scatpart = take(with_scatter ? nblk * d * d * 8 : 0);
-  l.off = take(((size_t)K + 1) * 8);
-  l.bytes = o;
-  return l;
+  w->scale = c.take<double>((size_t)n);
+  w->colpart = c.take<double>(nblk * d);
+  w->scatpart = c.take<double>(with_scatter ? nblk * d * d : 0);
+  w->off = c.take<int64_t>((size_t)K + 1);
+  return c.bytes();
 }
 
 bool pf_shape_ok(int n, int d, int K) { return n >= 1 && n <= PF_MAX_ROWS && d >= 1 && d <= PLDA_MAX_DIM && K >= 0 && K <= PF_MAX_ROWS; }
@@ -268,7 +257,8 @@ extern "C" size_t sdk_plda_fit_stats_workspace_bytes(int n, int d, int K, int wi
     sdk_set_error("sdk_plda_fit_stats_workspace_bytes: n=%d d=%d K=%d (n 1 .. %d, d 1 .. %d, K 0 .. %d)", n, d, K, PF_MAX_ROWS, PLDA_MAX_DIM, PF_MAX_ROWS);
     return 0;
   }
-  return pf_layout(n, d, K, with_scatter).bytes;
+  PfWs w;
+  return pf_carve({}, n, d, K, with_scatter, &w);
 }
 
 extern "C" int sdk_plda_fit_stats(sdk_ctx* ctx, const float* E, const double* X, const double* mean1, int n, int d, const int32_t* labels,
@@ -284,12 +274,10 @@ extern "C" int sdk_plda_fit_stats(sdk_ctx* ctx, const float* E, const double* X,
   if (K > 0) SDK_REQUIRE(labels && order && counts && sums, "sdk_plda_fit_stats: K=%d needs labels=%p order=%p counts=%p sums=%p", K,
                          (const void*)labels, (const void*)order, (void*)counts, (void*)sums);
   SDK_REQUIRE(total && status && ws, "sdk_plda_fit_stats: null argument (total=%p status=%p ws=%p)", (void*)total, (void*)status, ws);
-  const PfLayout lay = pf_layout(n, d, K, scatter != nullptr);
-  SDK_REQUIRE(ws_bytes >= lay.bytes, "sdk_plda_fit_stats: workspace of %zu bytes, %zu needed", ws_bytes, lay.bytes);
-  SDK_REQUIRE(((uintptr_t)ws & 255) == 0, "sdk_plda_fit_stats: ws=%p must be 256-byte aligned", ws);
-  char* base = static_cast<char*>(ws);
-  const PfWs w{reinterpret_cast<double*>(base + lay.scale), reinterpret_cast<double*>(base + lay.colpart),
-               reinterpret_cast<double*>(base + lay.scatpart), reinterpret_cast<int64_t*>(base + lay.off)};
+  SDK_REQUIRE_WS("sdk_plda_fit_stats", "sdk_plda_fit_stats_workspace_bytes", ws, ws_bytes,
+                 sdk_plda_fit_stats_workspace_bytes(n, d, K, scatter != nullptr), 256);
+  PfWs w;
+  pf_carve({static_cast<char*>(ws), 0}, n, d, K, scatter != nullptr, &w);
   hipStream_t st = (hipStream_t)stream;
   const int RB = pf_row_block(n), nblk = (n + RB - 1) / RB;
   const PfSrc src{E, X, mean1, w.scale, d};

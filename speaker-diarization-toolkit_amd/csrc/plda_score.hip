@@ -335,34 +335,28 @@ __global__ __launch_bounds__(PS_NT) void ps_merge_kernel(const int32_t* __restri
   ps_write(top, n, k, S, idx, score);
 }
 
-inline size_t ps_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // the score workspace: the splits' lists, scores [nsplit][N][4] float64 then indices [nsplit][N][4] int32 (nothing with one split)
-struct PsLayout {
-  size_t pscore, pidx, bytes;
+struct PsWs {
+  double* pscore;
+  int32_t* pidx;
 };
-inline PsLayout ps_layout(int N, int S) {
+inline size_t ps_carve(WsCarver c, int N, int S, PsWs* w) {
   const PsPlan p = ps_plan(N, S);
-  PsLayout l{0, 0, 0};
-  if (p.nsplit > 1 && N > 0) {
-    const size_t e = (size_t)p.nsplit * (size_t)N * PS_MAX_TOPK;
-    l.pidx = ps_align(e * 8);
-    l.bytes = l.pidx + ps_align(e * 4);
-  }
-  return l;
+  const size_t e = p.nsplit > 1 && N > 0 ? (size_t)p.nsplit * (size_t)N * PS_MAX_TOPK : 0;
+  w->pscore = c.take<double>(e);
+  w->pidx = c.take<int32_t>(e);
+  return c.bytes();
 }
 
 // the enrolment workspace: off [S + 1], cursor [S], rows [P], int32
-struct PeLayout {
-  size_t off, cursor, rows, bytes;
+struct PeWs {
+  int32_t *off, *cursor, *rows;
 };
-inline PeLayout pe_layout(int P, int S) {
-  PeLayout l;
-  l.off = 0;
-  l.cursor = ps_align(((size_t)S + 1) * 4);
-  l.rows = l.cursor + ps_align((size_t)S * 4);
-  l.bytes = l.rows + ps_align((size_t)(P < 1 ? 1 : P) * 4);
-  return l;
+inline size_t pe_carve(WsCarver c, int P, int S, PeWs* w) {
+  w->off = c.take<int32_t>((size_t)S + 1);
+  w->cursor = c.take<int32_t>((size_t)S);
+  w->rows = c.take<int32_t>((size_t)(P < 1 ? 1 : P));
+  return c.bytes();
 }
 
 #define PS_REQUIRE_D(fn, D) SDK_REQUIRE((D) == 64 || (D) == 128, fn ": D=%d not supported (64 or 128)", (D))
@@ -375,7 +369,8 @@ extern "C" size_t sdk_plda_enroll_workspace_bytes(int P, int S) {
     sdk_set_error("sdk_plda_enroll_workspace_bytes: P=%d S=%d (0 <= P <= %d, 1 <= S <= %d)", P, S, PS_MAX_P, PS_MAX_S);
     return 0;
   }
-  return pe_layout(P, S).bytes;
+  PeWs w;
+  return pe_carve({}, P, S, &w);
 }
 
 extern "C" int sdk_plda_enroll(sdk_ctx* ctx, const double* Xp, const int32_t* group, int P, int D, const double* n_eff, const double* Phi, int S,
@@ -387,13 +382,10 @@ extern "C" int sdk_plda_enroll(sdk_ctx* ctx, const double* Xp, const int32_t* gr
   SDK_REQUIRE((P == 0 || (Xp && group)) && n_eff && Phi && G && r && status && ws,
               "sdk_plda_enroll: null argument (Xp=%p group=%p n_eff=%p Phi=%p G=%p r=%p status=%p ws=%p)", (const void*)Xp, (const void*)group,
               (const void*)n_eff, (const void*)Phi, (void*)G, (void*)r, (void*)status, ws);
-  const PeLayout lay = pe_layout(P, S);
-  SDK_REQUIRE(ws_bytes >= lay.bytes, "sdk_plda_enroll: workspace of %zu bytes, %zu needed (sdk_plda_enroll_workspace_bytes)", ws_bytes, lay.bytes);
-  SDK_REQUIRE(((uintptr_t)ws & 255) == 0, "sdk_plda_enroll: ws=%p must be 256-byte aligned", ws);
-  char* base = static_cast<char*>(ws);
-  int32_t* off = reinterpret_cast<int32_t*>(base + lay.off);
-  int32_t* cursor = reinterpret_cast<int32_t*>(base + lay.cursor);
-  int32_t* rows = reinterpret_cast<int32_t*>(base + lay.rows);
+  SDK_REQUIRE_WS("sdk_plda_enroll", "sdk_plda_enroll_workspace_bytes", ws, ws_bytes, sdk_plda_enroll_workspace_bytes(P, S), 256);
+  PeWs w;
+  pe_carve({static_cast<char*>(ws), 0}, P, S, &w);
+  int32_t *const off = w.off, *const cursor = w.cursor, *const rows = w.rows;
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(ctx, stream, SDK_K_COPY, 0.0, 8.0 * ((double)P * D + 2.0 * (double)S * D) + 4.0 * (3.0 * P + 3.0 * S));
   SDK_HIP_OK(hipMemsetAsync(status, 0, sizeof(int32_t), st));
@@ -414,7 +406,8 @@ extern "C" size_t sdk_plda_score_workspace_bytes(int N, int S, int k) {
                   PS_MAX_TOPK);
     return 0;
   }
-  const size_t b = ps_layout(N, S).bytes;
+  PsWs w;
+  const size_t b = ps_carve({}, N, S, &w);
   return b ? b : 256;                                    // never 0 for arguments the call takes: 0 is the refusal
 }
 
@@ -430,16 +423,13 @@ extern "C" int sdk_plda_score_topk(sdk_ctx* ctx, const double* X, int N, int D, 
               (const void*)r, (void*)idx, (void*)score);
   SDK_REQUIRE((((uintptr_t)X | (uintptr_t)G) & 15) == 0, "sdk_plda_score_topk: X=%p and G=%p must be 16-byte aligned", (const void*)X, (const void*)G);
   const PsPlan plan = ps_plan(N, S);
-  const PsLayout lay = ps_layout(N, S);
-  int32_t* pidx = nullptr;
-  double* pscore = nullptr;
+  PsWs w{nullptr, nullptr};
   if (plan.nsplit > 1) {
-    SDK_REQUIRE(ws, "sdk_plda_score_topk: null workspace (%zu bytes needed, sdk_plda_score_workspace_bytes)", lay.bytes);
-    SDK_REQUIRE(ws_bytes >= lay.bytes, "sdk_plda_score_topk: workspace of %zu bytes, %zu needed (sdk_plda_score_workspace_bytes)", ws_bytes, lay.bytes);
-    SDK_REQUIRE(((uintptr_t)ws & 255) == 0, "sdk_plda_score_topk: ws=%p must be 256-byte aligned", ws);
-    pscore = reinterpret_cast<double*>(static_cast<char*>(ws) + lay.pscore);
-    pidx = reinterpret_cast<int32_t*>(static_cast<char*>(ws) + lay.pidx);
+    SDK_REQUIRE_WS("sdk_plda_score_topk", "sdk_plda_score_workspace_bytes", ws, ws_bytes, sdk_plda_score_workspace_bytes(N, S, k), 256);
+    ps_carve({static_cast<char*>(ws), 0}, N, S, &w);
   }
+  int32_t* const pidx = w.pidx;
+  double* const pscore = w.pscore;
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(ctx, stream, SDK_K_COPY, 4.0 * N * (double)S * D,
                8.0 * ((double)N * D + (double)plan.ntn * S * (2.0 * D + 1.0) + (scores ? (double)N * S : 0.0)) + 12.0 * N * k);

@@ -877,9 +877,8 @@ int se_gate_residual_impl(sdk_ctx* ctx, const uint16_t* z, int64_t ldz, const ui
   SDK_REQUIRE(C % 8 == 0 && C / 8 <= NT && NT % (C / 8) == 0, "sdk_se_gate_residual: C=%d unsupported (need C/8 | 256)", C);
   SDK_REQUIRE(Cse > 0 && Cse <= NT && NT % Cse == 0 && Cse <= C, "sdk_se_gate_residual: Cse=%d unsupported (need Cse | 256)", Cse);
   SDK_REQUIRE(ldz % 8 == 0 && ldx % 8 == 0 && ldo % 8 == 0, "sdk_se_gate_residual: row strides must be multiples of 8");
-  SDK_REQUIRE(!ws || ws_bytes >= sdk_se_workspace_bytes(B, C, Cse), "sdk_se_gate_residual: workspace of %zu bytes, %zu needed (sdk_se_workspace_bytes; ws = NULL: the one-kernel form)",
-              ws_bytes, sdk_se_workspace_bytes(B, C, Cse));
-  if (ws) {
+  if (ws) {                                                  // (ws = NULL: the one-kernel form below)
+    SDK_REQUIRE_WS("sdk_se_gate_residual", "sdk_se_workspace_bytes", ws, ws_bytes, sdk_se_workspace_bytes(B, C, Cse), 1);
     // split schedule: channel means (one sweep of z) -> the two gate FCs batched over all segments on the
     // matrix pipe (weights read once per 32 segments instead of once per segment) -> gate*z + x sweep
     float* mean = (float*)ws;

@@ -403,6 +403,12 @@ __global__ __launch_bounds__(SS_NT) void ss_score_kernel(const double* __restric
   }
 }
 
+// one block: c [M][d] clip sums, then msum [S][d] speaker sums, then 256 bytes
+size_t ss_carve(WsCarver c, int M, int S, int d, double** sums) {
+  *sums = c.take<double>(((size_t)M + (size_t)S) * d + 256 / sizeof(double));
+  return c.bytes();
+}
+
 }  // namespace
 
 extern "C" size_t sdk_samples_runs_workspace_bytes(int64_t G) {
@@ -410,7 +416,9 @@ extern "C" size_t sdk_samples_runs_workspace_bytes(int64_t G) {
     sdk_set_error("sdk_samples_runs_workspace_bytes: G=%lld (fewer than 2^30 frames)", (long long)G);
     return 0;
   }
-  return (sm_layout(G).total * sizeof(int32_t) + 255) & ~(size_t)255;
+  WsCarver c{};
+  c.take<int32_t>(sm_layout(G).total);
+  return c.bytes();
 }
 
 extern "C" int sdk_samples_runs(sdk_ctx* ctx, const int32_t* speakers, const int32_t* frame_off, const int32_t* cent_off, int R, int64_t G,
@@ -429,12 +437,11 @@ extern "C" int sdk_samples_runs(sdk_ctx* ctx, const int32_t* speakers, const int
     SDK_HIP_OK(hipMemsetAsync(run_off, 0, (size_t)(R + 1) * sizeof(int32_t), st));
     return 0;
   }
-  const size_t need = sdk_samples_runs_workspace_bytes(G);
-  SDK_REQUIRE(ws, "sdk_samples_runs: null workspace (%zu bytes needed, sdk_samples_runs_workspace_bytes)", need);
-  SDK_REQUIRE(ws_bytes >= need, "sdk_samples_runs: workspace of %zu bytes, %zu needed (sdk_samples_runs_workspace_bytes)", ws_bytes, need);
-  SDK_REQUIRE(((uintptr_t)ws & 15) == 0 && ((uintptr_t)rows & 15) == 0, "sdk_samples_runs: ws=%p and rows=%p must be 16-byte aligned", ws, (void*)rows);
+  SDK_REQUIRE_WS("sdk_samples_runs", "sdk_samples_runs_workspace_bytes", ws, ws_bytes, sdk_samples_runs_workspace_bytes(G), 16);
+  SDK_REQUIRE(((uintptr_t)rows & 15) == 0, "sdk_samples_runs: rows=%p must be 16-byte aligned", (void*)rows);
   const SmWs L = sm_layout(G);
-  int32_t* base = static_cast<int32_t*>(ws);
+  WsCarver carve{static_cast<char*>(ws), 0};
+  int32_t* base = carve.take<int32_t>(L.total);                    // one block: sm_layout's offsets are inside it
   int32_t *kind = base + L.kind, *grp_start = base + L.grp_start, *grp_end = base + L.grp_end, *grp_solo = base + L.grp_solo;
   int32_t *kept_start = base + L.kept_start, *blk_last = base + L.blk_last, *blk_brk = base + L.blk_brk, *blk_solo = base + L.blk_solo;
   int32_t *blk_keep = base + L.blk_keep, *counts = base + L.counts;
@@ -459,7 +466,8 @@ extern "C" size_t sdk_samples_score_workspace_bytes(int M, int S, int d) {
     sdk_set_error("sdk_samples_score_workspace_bytes: M=%d S=%d d=%d (fewer than 2^24 clips and speakers, d a multiple of 64, at most %d)", M, S, d, SM_MAX_DIM);
     return 0;
   }
-  return (((size_t)M + (size_t)S) * d * sizeof(double) + 256 + 255) & ~(size_t)255;
+  double* sums;
+  return ss_carve({}, M, S, d, &sums);
 }
 
 extern "C" int sdk_samples_score(sdk_ctx* ctx, const float* E, int W, int d, const int32_t* clip_off, const int32_t* clip_spk, int M,
@@ -471,12 +479,10 @@ extern "C" int sdk_samples_score(sdk_ctx* ctx, const float* E, int W, int d, con
               "sdk_samples_score: W=%d M=%d R=%d S=%d (fewer than 2^24 windows, clips and speakers, R at least 1)", W, M, R, S);
   SDK_REQUIRE(clip_off && spk_off && (W == 0 || E) && (M == 0 || (clip_spk && out_f && out_i)) && (S == 0 || mean), "sdk_samples_score: null argument");
   if (M == 0 && S == 0) return 0;
-  const size_t need = sdk_samples_score_workspace_bytes(M, S, d);
-  SDK_REQUIRE(ws, "sdk_samples_score: null workspace (%zu bytes needed, sdk_samples_score_workspace_bytes)", need);
-  SDK_REQUIRE(ws_bytes >= need, "sdk_samples_score: workspace of %zu bytes, %zu needed (sdk_samples_score_workspace_bytes)", ws_bytes, need);
-  SDK_REQUIRE(((uintptr_t)ws & 7) == 0, "sdk_samples_score: ws=%p must be 8-byte aligned", ws);
+  SDK_REQUIRE_WS("sdk_samples_score", "sdk_samples_score_workspace_bytes", ws, ws_bytes, sdk_samples_score_workspace_bytes(M, S, d), 8);
   hipStream_t st = (hipStream_t)stream;
-  double* c = static_cast<double*>(ws);
+  double* c;
+  ss_carve({static_cast<char*>(ws), 0}, M, S, d, &c);
   double* msum = c + (size_t)M * d;
   ProfScope ps(ctx, stream, SDK_K_COPY, 2.0 * W * (double)d, 4.0 * W * (double)d + 24.0 * ((double)M + S) * d);
   if (M) hipLaunchKernelGGL(ss_clip_sum_kernel, dim3((unsigned)M), dim3((unsigned)min(d, SS_NT)), 0, st, E, clip_off, W, d, c, out_i);

@@ -49,22 +49,16 @@ struct Workspace {        // layout inside the caller's scratch buffer
   int32_t* part_i;
 };
 
-__host__ __device__ inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-inline size_t ws_layout(int N, int P, char* base, Workspace* w) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
-  char* a = take((size_t)N * NCAND * 4);
-  char* b = take((size_t)N * NCAND * 4);
-  char* c = take((size_t)N * 4);
-  char* d = take(256);
-  char* e = take((size_t)N * 4);
+inline size_t aff_carve(WsCarver c, int N, int P, Workspace* w) {
+  w->cand_val = c.take<float>((size_t)N * NCAND);
+  w->cand_idx = c.take<int32_t>((size_t)N * NCAND);
+  w->ubound = c.take<float>((size_t)N);
+  w->flag_count = c.take<int32_t>(64);                          // (256 bytes of its own)
+  w->flag_rows = c.take<int32_t>((size_t)N);
   const size_t nsl = (size_t)((P + 1023) / 1024);
-  char* f1 = take(nsl > 1 ? (size_t)N * nsl * 16 : 16);
-  char* f2 = take(nsl > 1 ? (size_t)N * nsl * 16 : 16);
-  if (w) { w->part_s = (float*)f1; w->part_i = (int32_t*)f2; }
-  if (w) { w->cand_val = (float*)a; w->cand_idx = (int32_t*)b; w->ubound = (float*)c; w->flag_count = (int32_t*)d; w->flag_rows = (int32_t*)e; }
-  return off;
+  w->part_s = c.take<float>(nsl > 1 ? (size_t)N * nsl * 4 : 4);
+  w->part_i = c.take<int32_t>(nsl > 1 ? (size_t)N * nsl * 4 : 4);
+  return c.bytes();
 }
 
 // sorted insert of x into m[0] >= m[1] >= ... : 1 v_max + (DEPTH-1) v_med3; values are packed floats
@@ -382,7 +376,8 @@ extern "C" size_t sdk_affinity_workspace_bytes(int N, int P) {
     sdk_set_error("sdk_affinity_workspace_bytes: N=%d P=%d (at least 1 each)", N, P);
     return 0;
   }
-  const size_t a = ws_layout(N, P, nullptr, nullptr), b = aff_rowcol_workspace_bytes(N, P);
+  Workspace w;
+  const size_t a = aff_carve({}, N, P, &w), b = aff_rowcol_workspace_bytes(N, P);
   return a > b ? a : b;
 }
 
@@ -394,15 +389,14 @@ extern "C" int sdk_affinity_topk(sdk_ctx* ctx, const float* E, const uint16_t* E
   SDK_REQUIRE(d == D, "sdk_affinity_topk: d=%d, this build is specialised for d=%d", d, D);
   SDK_REQUIRE(N > 0 && Pn > 0, "sdk_affinity_topk: empty problem (N=%d P=%d)", N, Pn);
   SDK_REQUIRE(k >= 1 && k <= 4 && k <= Pn, "sdk_affinity_topk: k=%d must be in [1, min(4, P)]", k);
-  SDK_REQUIRE(ws_bytes >= sdk_affinity_workspace_bytes(N, Pn), "sdk_affinity_topk: workspace too small (%zu bytes, %zu needed)", ws_bytes,
-              sdk_affinity_workspace_bytes(N, Pn));
+  SDK_REQUIRE_WS("sdk_affinity_topk", "sdk_affinity_workspace_bytes", ws, ws_bytes, sdk_affinity_workspace_bytes(N, Pn), 1);
   SDK_REQUIRE(((uintptr_t)E % 16) == 0 && ((uintptr_t)Eb % 16) == 0 && ((uintptr_t)P % 16) == 0 && ((uintptr_t)Pb % 16) == 0,
               "sdk_affinity_topk: matrices must be 16-byte aligned");
   if (k == 1 && ctx->aff_fast && aff_rowcol_supported(Pn))
     return aff_rowcol_top1(ctx, E, Eb, resid_e, P, Pb, resid_p, N, Pn, idx, score, n_rescanned, ws, stream);
   hipStream_t s = (hipStream_t)stream;
   Workspace w;
-  ws_layout(N, Pn, (char*)ws, &w);
+  aff_carve({(char*)ws, 0}, N, Pn, &w);
   SDK_HIP_OK(hipMemsetAsync(w.flag_count, 0, sizeof(int32_t), s));
   {
   ProfScope ps(ctx, stream, SDK_K_AFF_COARSE, 2.0 * N * (double)Pn * D, 2.0 * ((double)N + Pn) * D + 68.0 * N);

@@ -176,43 +176,33 @@ extern "C" int sdk_profile_end(sdk_ctx* ctx, sdk_profile_report* out) {
 // ------------------------------------------------------------------------------ ECAPA forward
 namespace {
 
-inline size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct FwdWs {
   uint16_t *X0, *U, *R, *Z, *Sa, *Sb, *CAT, *H, *AH;
   float *ctx, *ubias, *logits, *pooled, *se, *stats, *mean;
 };
 
 // full_logits: the masked forward's pooling reads the fp32 logits from HBM at every T
-size_t fwd_layout(const sdk_ecapa_desc* d, int B, int T, char* base, FwdWs* w, bool full_logits = false) {
+size_t fwd_carve(WsCarver c, const sdk_ecapa_desc* d, int B, int T, FwdWs* w, bool full_logits = false) {
   const size_t M = (size_t)B * T, C = d->channels, Cm = d->mfa_channels, S = d->sub_channels, A = d->attn_channels;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += a256(bytes); return p; };
-  char* x0 = take(M * C * 2);
-  char* u = take(M * C * 2);
-  char* r = take(M * C * 2);
-  char* z = take(M * C * 2);
-  char* sa = take(M * S * 2);
-  char* sb = take(M * S * 2);
-  char* cat = take(M * Cm * 2);
-  char* h = take(M * Cm * 2);
-  char* ah = take(M * A * 2);
-  char* cx = take((size_t)B * 2 * Cm * 4);
-  char* ub = take((size_t)B * A * 4);
+  w->X0 = c.take<uint16_t>(M * C);
+  w->U = c.take<uint16_t>(M * C);
+  w->R = c.take<uint16_t>(M * C);
+  w->Z = c.take<uint16_t>(M * C);
+  w->Sa = c.take<uint16_t>(M * S);
+  w->Sb = c.take<uint16_t>(M * S);
+  w->CAT = c.take<uint16_t>(M * Cm);
+  w->H = c.take<uint16_t>(M * Cm);
+  w->AH = c.take<uint16_t>(M * A);
+  w->ctx = c.take<float>((size_t)B * 2 * Cm);
+  w->ubias = c.take<float>((size_t)B * A);
   // the [M, Cm] fp32 attention logits exist in HBM only on the unfused pooling path (37 % of the workspace otherwise)
   const bool fused_asp = !full_logits && A == 128 && T <= sdk_asp_fused_max_frames();
-  char* lg = take(fused_asp ? 256 : M * Cm * 4);
-  char* po = take((size_t)B * 2 * Cm * 4);
-  char* se = take(sdk_se_workspace_bytes(B, (int)C, d->se_channels));
-  char* stp = take(sdk_conv_gemm_stats_bytes((int)M, (int)Cm, 2));
-  char* mn = take((size_t)B * C * 4);
-  if (w) { w->se = (float*)se; w->stats = (float*)stp; w->mean = (float*)mn; }
-  if (w) {
-    w->X0 = (uint16_t*)x0; w->U = (uint16_t*)u; w->R = (uint16_t*)r; w->Z = (uint16_t*)z;
-    w->Sa = (uint16_t*)sa; w->Sb = (uint16_t*)sb; w->CAT = (uint16_t*)cat; w->H = (uint16_t*)h; w->AH = (uint16_t*)ah;
-    w->ctx = (float*)cx; w->ubias = (float*)ub; w->logits = (float*)lg; w->pooled = (float*)po;
-  }
-  return off;
+  w->logits = c.take<float>(fused_asp ? 64 : M * Cm);
+  w->pooled = c.take<float>((size_t)B * 2 * Cm);
+  w->se = (float*)c.take<char>(sdk_se_workspace_bytes(B, (int)C, d->se_channels));
+  w->stats = (float*)c.take<char>(sdk_conv_gemm_stats_bytes((int)M, (int)Cm, 2));
+  w->mean = c.take<float>((size_t)B * C);
+  return c.bytes();
 }
 
 // ---- precise mode: every activation a pair of fp16 planes [M, 2 C] (hi | lo), logits fp32
@@ -221,32 +211,25 @@ struct FwdWsHp {
   float *ctx, *ubias, *logits, *pooled, *mean, *hid, *gate;
 };
 
-size_t fwd_layout_hp(const sdk_ecapa_desc* d, int B, int T, char* base, FwdWsHp* w) {
+size_t fwd_carve_hp(WsCarver c, const sdk_ecapa_desc* d, int B, int T, FwdWsHp* w) {
   const size_t M = (size_t)B * T, C = d->channels, Cm = d->mfa_channels, S = d->sub_channels, A = d->attn_channels;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += a256(bytes); return p; };
-  char* x0 = take(M * C * 4);
-  char* u = take(M * C * 4);
-  char* r = take(M * C * 4);
-  char* z = take(M * C * 4);
-  char* sa = take(M * S * 4);
-  char* sb = take(M * S * 4);
-  char* cat = take(M * Cm * 4);
-  char* h = take(M * Cm * 4);
-  char* ah = take(M * A * 4);
-  char* cx = take((size_t)B * 2 * Cm * 4);
-  char* ub = take((size_t)B * A * 4);
-  char* lg = take(M * Cm * 4);
-  char* po = take((size_t)B * 2 * Cm * 4);
-  char* mn = take((size_t)B * C * 4);
-  char* hd = take((size_t)B * d->se_channels * 4);
-  char* gt = take((size_t)B * C * 4);
-  if (w) {
-    w->X0 = (uint16_t*)x0; w->U = (uint16_t*)u; w->R = (uint16_t*)r; w->Z = (uint16_t*)z; w->Sa = (uint16_t*)sa; w->Sb = (uint16_t*)sb;
-    w->CAT = (uint16_t*)cat; w->H = (uint16_t*)h; w->AH = (uint16_t*)ah; w->ctx = (float*)cx; w->ubias = (float*)ub; w->logits = (float*)lg;
-    w->pooled = (float*)po; w->mean = (float*)mn; w->hid = (float*)hd; w->gate = (float*)gt;
-  }
-  return off;
+  w->X0 = c.take<uint16_t>(M * C * 2);
+  w->U = c.take<uint16_t>(M * C * 2);
+  w->R = c.take<uint16_t>(M * C * 2);
+  w->Z = c.take<uint16_t>(M * C * 2);
+  w->Sa = c.take<uint16_t>(M * S * 2);
+  w->Sb = c.take<uint16_t>(M * S * 2);
+  w->CAT = c.take<uint16_t>(M * Cm * 2);
+  w->H = c.take<uint16_t>(M * Cm * 2);
+  w->AH = c.take<uint16_t>(M * A * 2);
+  w->ctx = c.take<float>((size_t)B * 2 * Cm);
+  w->ubias = c.take<float>((size_t)B * A);
+  w->logits = c.take<float>(M * Cm);
+  w->pooled = c.take<float>((size_t)B * 2 * Cm);
+  w->mean = c.take<float>((size_t)B * C);
+  w->hid = c.take<float>((size_t)B * d->se_channels);
+  w->gate = c.take<float>((size_t)B * C);
+  return c.bytes();
 }
 
 int check_desc(const sdk_ecapa_desc* d) {
@@ -266,7 +249,7 @@ int check_desc(const sdk_ecapa_desc* d) {
 int ecapa_forward_hp(sdk_ctx* ctx, const void* wblob, const sdk_ecapa_desc* d, const uint16_t* feats, int ldf, int B, int T, void* ws,
                      float* emb, void* stream) {
   FwdWsHp w;
-  fwd_layout_hp(d, B, T, (char*)ws, &w);
+  fwd_carve_hp({(char*)ws, 0}, d, B, T, &w);
   const char* wb = (const char*)wblob;
   auto P16 = [&](int slot) -> const uint16_t* { return d->off[slot] < 0 ? nullptr : (const uint16_t*)(wb + d->off[slot]); };
   auto P32 = [&](int slot) -> const float* { return d->off[slot] < 0 ? nullptr : (const float*)(wb + d->off[slot]); };
@@ -345,8 +328,9 @@ extern "C" size_t sdk_ecapa_workspace_bytes(const sdk_ecapa_desc* d, int B, int 
     sdk_set_error("sdk_ecapa_workspace_bytes: d=%p B=%d T=%d (a descriptor, B and T at least 1, B*T below 2^31)", (const void*)d, B, T);
     return 0;
   }
-  if (d->precision == 1) return fwd_layout_hp(d, B, T, nullptr, nullptr);
-  return fwd_layout(d, B, T, nullptr, nullptr);
+  FwdWs w;
+  FwdWsHp whp;
+  return d->precision == 1 ? fwd_carve_hp({}, d, B, T, &whp) : fwd_carve({}, d, B, T, &w);
 }
 
 // Calibration slots (sdk_ecapa_forward_calib): per-segment mean | std (sdk_asp_stats layout [B, 2 C_l]) of the INPUT of every bf16 GEMM layer whose
@@ -500,7 +484,7 @@ static int ecapa_trunk(sdk_ctx* ctx, const void* wblob, const sdk_ecapa_desc* d,
 
 // The checks both forwards make after their null-pointer and descriptor checks, in sdk_ecapa_forward's order and words (fn: the entry point's name;
 // need: its workspace size): batch, feature width, receptive halo, workspace, alignment, weight slots.
-static int check_forward_args(const char* fn, const void* wblob, const sdk_ecapa_desc* d, int ldf, int B, int T, const void* ws, size_t ws_bytes, size_t need) {
+static int check_forward_args(const char* fn, const void* wblob, const sdk_ecapa_desc* d, int ldf, int B, int T, const void* ws, size_t ws_bytes, const char* sizer, size_t need) {
   SDK_REQUIRE(B > 0 && T > 0, "%s: empty batch (B=%d T=%d)", fn, B, T);
   SDK_REQUIRE((int64_t)B * T < (1ll << 31), "%s: B*T overflows int32; split the batch", fn);
   SDK_REQUIRE(ldf >= d->n_mels_padded && ldf % 8 == 0, "%s: ldf=%d < padded mel width %d", fn, ldf, d->n_mels_padded);
@@ -509,8 +493,8 @@ static int check_forward_args(const char* fn, const void* wblob, const sdk_ecapa
   int maxhalo = d->kernel0 / 2;
   for (int i = 0; i < d->n_blocks; ++i) maxhalo = d->dilation[i] > maxhalo ? d->dilation[i] : maxhalo;
   SDK_REQUIRE(T > maxhalo, "%s: segments of %d frames are shorter than the receptive halo %d", fn, T, maxhalo);
-  SDK_REQUIRE(ws_bytes >= need, "%s: workspace too small (%zu < %zu)", fn, ws_bytes, need);
-  SDK_REQUIRE(((uintptr_t)ws % 256) == 0 && ((uintptr_t)wblob % 256) == 0, "%s: ws/wblob must be 256-byte aligned", fn);
+  SDK_REQUIRE_WS(fn, sizer, ws, ws_bytes, need, 256);
+  SDK_REQUIRE(((uintptr_t)wblob % 256) == 0, "%s: wblob must be 256-byte aligned", fn);
 
   {  // every slot the schedule dereferences must be present in the blob
     const int tbs = EL_TAIL_BASE(d->n_blocks);
@@ -526,10 +510,10 @@ static int ecapa_forward_impl(sdk_ctx* ctx, const void* wblob, const sdk_ecapa_d
                               int B, int T, void* ws, size_t ws_bytes, float* emb, float* calib, void* stream) {
   SDK_REQUIRE(ctx && wblob && feats && ws && emb, "sdk_ecapa_forward: null argument");
   if (int rc = check_desc(d)) return rc;
-  if (int rc = check_forward_args("sdk_ecapa_forward", wblob, d, ldf, B, T, ws, ws_bytes, sdk_ecapa_workspace_bytes(d, B, T))) return rc;
+  if (int rc = check_forward_args("sdk_ecapa_forward", wblob, d, ldf, B, T, ws, ws_bytes, "sdk_ecapa_workspace_bytes", sdk_ecapa_workspace_bytes(d, B, T))) return rc;
   if (d->precision == 1) return ecapa_forward_hp(ctx, wblob, d, feats, ldf, B, T, ws, emb, stream);
   FwdWs w;
-  fwd_layout(d, B, T, (char*)ws, &w);
+  fwd_carve({(char*)ws, 0}, d, B, T, &w);
   bool fuse_ctx = false, h_kb = false;
   if (int rc = ecapa_trunk(ctx, wblob, d, feats, ldf, B, T, w, calib, stream, true, &fuse_ctx, &h_kb)) return rc;
   const char* wb = (const char*)wblob;
@@ -578,16 +562,14 @@ struct MaskedWs {
   float *ctx, *ubias, *pooled;
   int32_t* ok;                       // [B S]: valid != 0 and v1 > 0, written by the statistics sweep: the rows that are not zeros
 };
-size_t masked_layout(const sdk_ecapa_desc* d, int B, int T, int S, char* base, MaskedWs* w) {
-  size_t off = a256(fwd_layout(d, B, T, base, w ? &w->f : nullptr, true));
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += a256(bytes); return p; };
+size_t masked_carve(WsCarver c, const sdk_ecapa_desc* d, int B, int T, int S, MaskedWs* w) {
+  c.off = fwd_carve(c, d, B, T, &w->f, true);
   const size_t R = (size_t)B * S, Cm = d->mfa_channels, A = d->attn_channels;
-  char* cx = take(R * 2 * Cm * 4);
-  char* ub = take(R * A * 4);
-  char* po = take(R * 2 * Cm * 4);
-  char* ok = take(R * 4);
-  if (w) { w->ctx = (float*)cx; w->ubias = (float*)ub; w->pooled = (float*)po; w->ok = (int32_t*)ok; }
-  return off;
+  w->ctx = c.take<float>(R * 2 * Cm);
+  w->ubias = c.take<float>(R * A);
+  w->pooled = c.take<float>(R * 2 * Cm);
+  w->ok = c.take<int32_t>(R);
+  return c.bytes();
 }
 }  // namespace
 
@@ -597,7 +579,8 @@ extern "C" size_t sdk_ecapa_masked_workspace_bytes(const sdk_ecapa_desc* d, int 
                   (const void*)d, B, T, S, d ? d->precision : -1);
     return 0;
   }
-  return masked_layout(d, B, T, S, nullptr, nullptr);
+  MaskedWs w;
+  return masked_carve({}, d, B, T, S, &w);
 }
 
 extern "C" int sdk_ecapa_forward_masked(sdk_ctx* ctx, const void* wblob, const sdk_ecapa_desc* d, const uint16_t* feats, int ldf, int B, int T, int S,
@@ -609,11 +592,11 @@ extern "C" int sdk_ecapa_forward_masked(sdk_ctx* ctx, const void* wblob, const s
   SDK_REQUIRE(d->precision != 1, "sdk_ecapa_forward_masked: precision 1 (the precise mode's fp16 hi+lo planes) is not built for the masked pooling; use a blob of precision 0 (bf16) or 2 (fp16)");
   SDK_REQUIRE(S >= 1 && S <= 8, "sdk_ecapa_forward_masked: S=%d weight rows per chunk (served: 1 .. 8)", S);
   SDK_REQUIRE((int64_t)B * S < (1ll << 31), "sdk_ecapa_forward_masked: B*S overflows int32; split the batch");
-  if (int rc = check_forward_args("sdk_ecapa_forward_masked", wblob, d, ldf, B, T, ws, ws_bytes, sdk_ecapa_masked_workspace_bytes(d, B, T, S))) return rc;
+  if (int rc = check_forward_args("sdk_ecapa_forward_masked", wblob, d, ldf, B, T, ws, ws_bytes, "sdk_ecapa_masked_workspace_bytes", sdk_ecapa_masked_workspace_bytes(d, B, T, S))) return rc;
   const int tb = EL_TAIL_BASE(d->n_blocks);
 
   MaskedWs w;
-  masked_layout(d, B, T, S, (char*)ws, &w);
+  masked_carve({(char*)ws, 0}, d, B, T, S, &w);
   bool fuse_ctx = false, h_kb = false;
   if (int rc = ecapa_trunk(ctx, wblob, d, feats, ldf, B, T, w.f, nullptr, stream, false, &fuse_ctx, &h_kb)) return rc;
   const char* wb = (const char*)wblob;
@@ -665,18 +648,19 @@ int check_xdesc(const sdk_xvector_desc* d) {
   SDK_REQUIRE(d->off[60] >= 0 && d->off[61] >= 0, "xvector desc: embedding layer slots missing");
   return 0;
 }
-size_t xv_layout(const sdk_xvector_desc* d, int B, int T, char* base, uint16_t** buf0, uint16_t** buf1, float** stats) {
+struct XvWs {
+  uint16_t *b0, *b1;
+  float* stats;
+};
+size_t xv_carve(WsCarver c, const sdk_xvector_desc* d, int B, int T, XvWs* w) {
   size_t cmax = 0;
   for (int l = 0; l < d->n_frame_layers; ++l) cmax = (size_t)d->cout[l] > cmax ? (size_t)d->cout[l] : cmax;
   const size_t M = (size_t)B * T;
-  const size_t esz = d->off[62] == 1 ? 4 : 2;                  // precise blob: activations travel as fp16 hi + lo planes (4 bytes per element)
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += a256(bytes); return p; };
-  char* a = take(M * cmax * esz);
-  char* b = take(M * cmax * esz);
-  char* c = take((size_t)B * 2 * d->cout[d->n_frame_layers - 1] * 4);
-  if (buf0) { *buf0 = (uint16_t*)a; *buf1 = (uint16_t*)b; *stats = (float*)c; }
-  return off;
+  const size_t planes = d->off[62] == 1 ? 2 : 1;               // precise blob: activations travel as fp16 hi + lo planes (4 bytes per element)
+  w->b0 = c.take<uint16_t>(M * cmax * planes);
+  w->b1 = c.take<uint16_t>(M * cmax * planes);
+  w->stats = c.take<float>((size_t)B * 2 * d->cout[d->n_frame_layers - 1]);
+  return c.bytes();
 }
 }  // namespace
 
@@ -686,7 +670,8 @@ extern "C" size_t sdk_xvector_workspace_bytes(const sdk_xvector_desc* d, int B, 
                   (const void*)d, B, T, d ? d->n_frame_layers : -1);
     return 0;
   }
-  return xv_layout(d, B, T, nullptr, nullptr, nullptr, nullptr);
+  XvWs w;
+  return xv_carve({}, d, B, T, &w);
 }
 
 extern "C" int sdk_xvector_forward(sdk_ctx* ctx, const void* wblob, const sdk_xvector_desc* d, const uint16_t* feats, int ldf, int B, int T,
@@ -701,11 +686,12 @@ extern "C" int sdk_xvector_forward(sdk_ctx* ctx, const void* wblob, const sdk_xv
   else SDK_REQUIRE(ldf >= d->n_feats && ldf % 8 == 0, "sdk_xvector_forward: ldf=%d < feature width %d", ldf, d->n_feats);
   for (int l = 0; l < d->n_frame_layers; ++l)
     SDK_REQUIRE(T > (d->kernel[l] / 2) * d->dilation[l], "sdk_xvector_forward: segments of %d frames are shorter than layer %d's halo", T, l);
-  SDK_REQUIRE(ws_bytes >= sdk_xvector_workspace_bytes(d, B, T) && ((uintptr_t)ws % 256) == 0 && ((uintptr_t)wblob % 256) == 0, "sdk_xvector_forward: workspace too small or misaligned (%zu bytes at %p, %zu needed, 256-byte aligned)",
-              ws_bytes, ws, sdk_xvector_workspace_bytes(d, B, T));
-  uint16_t *b0, *b1;
-  float* stats;
-  xv_layout(d, B, T, (char*)ws, &b0, &b1, &stats);
+  SDK_REQUIRE_WS("sdk_xvector_forward", "sdk_xvector_workspace_bytes", ws, ws_bytes, sdk_xvector_workspace_bytes(d, B, T), 256);
+  SDK_REQUIRE(((uintptr_t)wblob % 256) == 0, "sdk_xvector_forward: wblob=%p must be 256-byte aligned", wblob);
+  XvWs w;
+  xv_carve({(char*)ws, 0}, d, B, T, &w);
+  uint16_t *const b0 = w.b0, *const b1 = w.b1;
+  float* const stats = w.stats;
   const char* wb = (const char*)wblob;
   const uint16_t* in = feats;
   int64_t ldin = ldf;
@@ -772,7 +758,11 @@ int check_rdesc(const sdk_resnet_desc* d) {
 int rn_out(int n, int s) { return (n - 1) / s + 1; }
 // the three activation buffers hold the largest map of the network; then the pooled statistics [rows B][2 C4 F4] (rows = 1: one per segment;
 // the masked forward has S per segment)
-size_t rn_layout(const sdk_resnet_desc* d, int B, int T, int rows, char* base, uint16_t** bufs, float** stats) {
+struct RnWs {
+  uint16_t* buf[3];
+  float* stats;
+};
+size_t rn_carve(WsCarver c, const sdk_resnet_desc* d, int B, int T, int rows, RnWs* w) {
   int F = d->n_feats, Tl = T;
   size_t big = (size_t)F * T * d->width[0];
   for (int l = 0; l < 4; ++l) {
@@ -780,15 +770,9 @@ size_t rn_layout(const sdk_resnet_desc* d, int B, int T, int rows, char* base, u
     const size_t e = (size_t)F * Tl * d->width[l];
     big = e > big ? e : big;
   }
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += a256(bytes); return p; };
-  for (int i = 0; i < 3; ++i) {
-    char* p = take((size_t)B * big * 2);
-    if (bufs) bufs[i] = (uint16_t*)p;
-  }
-  char* s = take((size_t)B * rows * 2 * d->width[3] * F * 4);
-  if (stats) *stats = (float*)s;
-  return off;
+  for (int i = 0; i < 3; ++i) w->buf[i] = c.take<uint16_t>((size_t)B * big);
+  w->stats = c.take<float>((size_t)B * rows * 2 * d->width[3] * F);
+  return c.bytes();
 }
 
 // the conv trunk shared by both forwards: feats -> the last map [B][F][Tl][C] in one of the three buffers (*last)
@@ -835,7 +819,8 @@ extern "C" size_t sdk_resnet_workspace_bytes(const sdk_resnet_desc* d, int B, in
                   d ? d->n_feats : -1);
     return 0;
   }
-  return rn_layout(d, B, T, 1, nullptr, nullptr, nullptr);
+  RnWs w;
+  return rn_carve({}, d, B, T, 1, &w);
 }
 
 extern "C" size_t sdk_resnet_masked_workspace_bytes(const sdk_resnet_desc* d, int B, int T, int S) {
@@ -844,7 +829,8 @@ extern "C" size_t sdk_resnet_masked_workspace_bytes(const sdk_resnet_desc* d, in
                   (const void*)d, B, T, S, d ? d->n_feats : -1);
     return 0;
   }
-  return rn_layout(d, B, T, S, nullptr, nullptr, nullptr);
+  RnWs w;
+  return rn_carve({}, d, B, T, S, &w);
 }
 
 extern "C" int sdk_resnet_last_map_frames(const sdk_resnet_desc* d, int T) {
@@ -859,12 +845,12 @@ extern "C" int sdk_resnet_forward(sdk_ctx* ctx, const void* wblob, const sdk_res
   if (int rc = check_rdesc(d)) return rc;
   SDK_REQUIRE(B > 0 && T >= 9 && (int64_t)B * T < (1ll << 31), "sdk_resnet_forward: bad batch (B=%d T=%d; segments need >= 9 frames)", B, T);
   SDK_REQUIRE(ldf >= d->n_feats, "sdk_resnet_forward: ldf=%d < feature width %d", ldf, d->n_feats);
-  SDK_REQUIRE(ws_bytes >= sdk_resnet_workspace_bytes(d, B, T) && ((uintptr_t)ws % 256) == 0 && ((uintptr_t)wblob % 256) == 0,
-              "sdk_resnet_forward: workspace too small or misaligned (%zu bytes at %p, %zu needed, 256-byte aligned)", ws_bytes, ws,
-              sdk_resnet_workspace_bytes(d, B, T));
-  uint16_t* buf[3];
-  float* stats;
-  rn_layout(d, B, T, 1, (char*)ws, buf, &stats);
+  SDK_REQUIRE_WS("sdk_resnet_forward", "sdk_resnet_workspace_bytes", ws, ws_bytes, sdk_resnet_workspace_bytes(d, B, T), 256);
+  SDK_REQUIRE(((uintptr_t)wblob % 256) == 0, "sdk_resnet_forward: wblob=%p must be 256-byte aligned", wblob);
+  RnWs rw;
+  rn_carve({(char*)ws, 0}, d, B, T, 1, &rw);
+  uint16_t* const* buf = rw.buf;
+  float* const stats = rw.stats;
   const char* wb = (const char*)wblob;
   const uint16_t* X;
   int F, Tl, C;
@@ -881,12 +867,12 @@ extern "C" int sdk_resnet_forward_masked(sdk_ctx* ctx, const void* wblob, const 
   SDK_REQUIRE(B > 0 && T >= 9 && (int64_t)B * T < (1ll << 31), "sdk_resnet_forward_masked: bad batch (B=%d T=%d; segments need >= 9 frames)", B, T);
   SDK_REQUIRE(S >= 1 && (int64_t)B * S < (1ll << 31), "sdk_resnet_forward_masked: S=%d weight rows per segment (B=%d)", S, B);
   SDK_REQUIRE(ldf >= d->n_feats, "sdk_resnet_forward_masked: ldf=%d < feature width %d", ldf, d->n_feats);
-  const size_t need = sdk_resnet_masked_workspace_bytes(d, B, T, S);
-  SDK_REQUIRE(ws_bytes >= need, "sdk_resnet_forward_masked: workspace of %zu bytes, %zu needed (sdk_resnet_masked_workspace_bytes)", ws_bytes, need);
-  SDK_REQUIRE(((uintptr_t)ws % 256) == 0 && ((uintptr_t)wblob % 256) == 0, "sdk_resnet_forward_masked: ws / wblob must be 256-byte aligned");
-  uint16_t* buf[3];
-  float* stats;
-  rn_layout(d, B, T, S, (char*)ws, buf, &stats);
+  SDK_REQUIRE_WS("sdk_resnet_forward_masked", "sdk_resnet_masked_workspace_bytes", ws, ws_bytes, sdk_resnet_masked_workspace_bytes(d, B, T, S), 256);
+  SDK_REQUIRE(((uintptr_t)wblob % 256) == 0, "sdk_resnet_forward_masked: wblob=%p must be 256-byte aligned", wblob);
+  RnWs rw;
+  rn_carve({(char*)ws, 0}, d, B, T, S, &rw);
+  uint16_t* const* buf = rw.buf;
+  float* const stats = rw.stats;
   const char* wb = (const char*)wblob;
   const uint16_t* X;
   int F, Tl, C;
@@ -931,8 +917,7 @@ extern "C" int sdk_centroid_linkage(sdk_ctx* ctx, const float* E, int ldE, int d
   SDK_REQUIRE((uintptr_t)E % 4 == 0 && (uintptr_t)Z % 8 == 0 && (uintptr_t)status % 4 == 0 && (uintptr_t)workspace % 256 == 0,
               "sdk_centroid_linkage: misaligned pointer (E=%p needs 4, Z=%p needs 8, status=%p needs 4, workspace=%p needs 256 bytes)",
               (const void*)E, (void*)Z, (void*)status, workspace);
-  const size_t need = ahc_workspace_bytes(offsets, G);
-  SDK_REQUIRE(ws_bytes >= need, "sdk_centroid_linkage: workspace of %zu bytes, %zu needed", ws_bytes, need);
+  SDK_REQUIRE_WS("sdk_centroid_linkage", "sdk_centroid_linkage_workspace_bytes", workspace, ws_bytes, ahc_workspace_bytes(offsets, G), 1);
   return ahc_launch(ctx, E, ldE, dim, offsets, G, Z, status, workspace, stream);
 }
 
@@ -954,7 +939,6 @@ extern "C" int sdk_linked_linkage(sdk_ctx* ctx, const float* E, int ldE, int dim
                   (uintptr_t)workspace % 256 == 0,
               "sdk_linked_linkage: misaligned pointer (E=%p needs 4, group=%p needs 4, Z=%p needs 8, merges=%p needs 4, status=%p needs 4, workspace=%p "
               "needs 256 bytes)", (const void*)E, (const void*)group, (void*)Z, (void*)merges, (void*)status, workspace);
-  const size_t need = ahc_workspace_bytes(offsets, G);
-  SDK_REQUIRE(ws_bytes >= need, "sdk_linked_linkage: workspace of %zu bytes, %zu needed", ws_bytes, need);
+  SDK_REQUIRE_WS("sdk_linked_linkage", "sdk_linked_linkage_workspace_bytes", workspace, ws_bytes, ahc_workspace_bytes(offsets, G), 1);
   return link_launch(ctx, E, ldE, dim, group, offsets, G, stop, Z, merges, status, workspace, stream);
 }

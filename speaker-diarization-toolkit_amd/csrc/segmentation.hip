@@ -32,7 +32,6 @@ constexpr int SG_GATES = 4 * SG_HID;
 constexpr int SG_LSTM_TILE = 16;      // chunks per recurrence workgroup
 constexpr int SG_HPAD = SG_HID + 8;   // LDS row of h (+16 bytes: spreads the b128 operand reads over the banks)
 
-inline size_t seg_a256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 __device__ __forceinline__ float leaky(float v) { return v > 0.f ? v : 0.01f * v; }
 __device__ __forceinline__ float sigm(float v) { return 1.f / (1.f + expf(-v)); }
@@ -517,22 +516,19 @@ int check_sdesc(const sdk_segmentation_desc* d) {
 }
 
 // the three work regions of the forward: R1 fp32 pooled maps and the gate pre-activations, R2 normalised 2-byte maps, R3 the LSTM output
-struct SegLayout { size_t ab, r1, r2, r3, total; };
-SegLayout seg_layout(int B, int S) {
+struct SegWs { float *ab, *R1, *R2, *R3; };
+size_t seg_carve(WsCarver c, int B, int S, SegWs* w) {
   const SegDims g = seg_dims(S);
-  SegLayout L;
   const size_t b = (size_t)B;
-  size_t r1 = b * g.L1 * 80 * 4;
-  r1 = r1 > b * g.L2 * 64 * 4 ? r1 : b * g.L2 * 64 * 4;
-  r1 = r1 > b * g.F * 1024 * 4 ? r1 : b * g.F * 1024 * 4;
-  size_t r2 = b * g.L1 * 80 * 4;
-  r2 = r2 > b * g.L2 * 64 * 4 ? r2 : b * g.L2 * 64 * 4;
-  L.ab = 0;
-  L.r1 = seg_a256(b * 8);
-  L.r2 = L.r1 + seg_a256(r1);
-  L.r3 = L.r2 + seg_a256(r2 + 64);
-  L.total = L.r3 + seg_a256(b * g.F * 256 * 4);
-  return L;
+  size_t r1 = b * g.L1 * 80;
+  r1 = r1 > b * g.L2 * 64 ? r1 : b * g.L2 * 64;
+  const size_t r2 = r1;
+  r1 = r1 > b * g.F * 1024 ? r1 : b * g.F * 1024;
+  w->ab = c.take<float>(b * 2);
+  w->R1 = c.take<float>(r1);
+  w->R2 = c.take<float>(r2 + 16);
+  w->R3 = c.take<float>(b * g.F * 256);
+  return c.bytes();
 }
 
 template <bool F16, bool SINC, int NB>
@@ -557,10 +553,9 @@ template <bool F16>
 int frontend(sdk_ctx* ctx, const char* wb, const sdk_segmentation_desc* d, const int16_t* samples, int64_t n_samples, const int32_t* starts, int ld,
              int B, int S, char* ws, float* out, hipStream_t st) {
   const SegDims g = seg_dims(S);
-  const SegLayout L = seg_layout(B, S);
-  float* ab = (float*)(ws + L.ab);
-  float* R1 = (float*)(ws + L.r1);
-  float* R2 = (float*)(ws + L.r2);
+  SegWs w;
+  seg_carve({ws, 0}, B, S, &w);
+  float *const ab = w.ab, *const R1 = w.R1, *const R2 = w.R2;
   auto F32 = [&](int s) { return (const float*)(wb + d->off[s]); };
   auto U16 = [&](int s) { return (const bf16_t*)(wb + d->off[s]); };
   hipLaunchKernelGGL(seg_wavstats_kernel, dim3(B), dim3(SG_NT), 0, st, samples, n_samples, starts, ld, S, F32(SDK_SEG_WAVNORM), ab);
@@ -620,8 +615,12 @@ int check_source(const char* fn, const int16_t* samples, int64_t n_samples, int 
 extern "C" int sdk_segmentation_frames(int S) { return seg_frames(S); }
 
 extern "C" size_t sdk_segmentation_workspace_bytes(const sdk_segmentation_desc* d, int B, int S) {
-  if (!d || B <= 0 || S < 991) return 0;
-  return seg_layout(B, S).total;
+  if (!d || B <= 0 || S < 991) {
+    sdk_set_error("sdk_segmentation_workspace_bytes: d=%p B=%d S=%d (a descriptor, B at least 1, a chunk of at least 991 samples: one frame)", (const void*)d, B, S);
+    return 0;
+  }
+  SegWs w;
+  return seg_carve({}, B, S, &w);
 }
 
 extern "C" int sdk_sincnet_frontend(sdk_ctx* ctx, const void* wblob, const sdk_segmentation_desc* d, const int16_t* samples, int64_t n_samples,
@@ -632,9 +631,8 @@ extern "C" int sdk_sincnet_frontend(sdk_ctx* ctx, const void* wblob, const sdk_s
   if (B == 0) return 0;
   SDK_REQUIRE(starts || (ld >= S && (int64_t)(B - 1) * ld + S <= n_samples),
               "sdk_sincnet_frontend: rows of ld=%d samples: B=%d rows of S=%d need ld >= S and (B - 1) ld + S <= n_samples=%lld", ld, B, S, (long long)n_samples);
-  const size_t need = sdk_segmentation_workspace_bytes(d, B, S);
-  SDK_REQUIRE(ws && ws_bytes >= need && (uintptr_t)ws % 256 == 0 && (uintptr_t)wblob % 256 == 0 && (uintptr_t)out % 16 == 0,
-              "sdk_sincnet_frontend: workspace of %zu bytes, %zu needed (256-byte aligned; out 16-byte aligned)", ws_bytes, need);
+  SDK_REQUIRE_WS("sdk_sincnet_frontend", "sdk_segmentation_workspace_bytes", ws, ws_bytes, sdk_segmentation_workspace_bytes(d, B, S), 256);
+  SDK_REQUIRE((uintptr_t)wblob % 256 == 0 && (uintptr_t)out % 16 == 0, "sdk_sincnet_frontend: wblob=%p must be 256-byte aligned, out=%p 16-byte aligned", wblob, (void*)out);
   const hipStream_t st = (hipStream_t)stream;
   return d->precision == 2 ? frontend<true>(ctx, (const char*)wblob, d, samples, n_samples, starts, ld, B, S, (char*)ws, out, st)
                            : frontend<false>(ctx, (const char*)wblob, d, samples, n_samples, starts, ld, B, S, (char*)ws, out, st);
@@ -650,9 +648,9 @@ extern "C" int sdk_bilstm_layer(sdk_ctx* ctx, const void* wblob, const sdk_segme
   const int kin = layer ? 256 : 64;
   SDK_REQUIRE(ldx >= kin && ldx % 8 == 0, "sdk_bilstm_layer: ldx=%d (a multiple of 8, at least %d for layer %d)", ldx, kin, layer);
   SDK_REQUIRE((int64_t)B * F < (1ll << 31) / 64, "sdk_bilstm_layer: B*F=%lld frames too many", (long long)B * F);
-  const size_t need = (size_t)B * F * 1024 * 4;
-  SDK_REQUIRE(ws && ws_bytes >= need && (uintptr_t)ws % 256 == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0 && (uintptr_t)wblob % 256 == 0,
-              "sdk_bilstm_layer: workspace of %zu bytes, %zu needed (256-byte aligned; x and y 16-byte aligned)", ws_bytes, need);
+  SDK_REQUIRE_WS("sdk_bilstm_layer", "4096 B F: the gate pre-activations", ws, ws_bytes, (size_t)B * F * 1024 * 4, 256);
+  SDK_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0 && (uintptr_t)wblob % 256 == 0,
+              "sdk_bilstm_layer: x=%p and y=%p must be 16-byte aligned, wblob=%p 256-byte aligned", (const void*)x, (void*)y, wblob);
   const hipStream_t st = (hipStream_t)stream;
   return d->precision == 2 ? bilstm<true>((const char*)wblob, d, layer, x, ldx, B, F, (float*)ws, y, st)
                            : bilstm<false>((const char*)wblob, d, layer, x, ldx, B, F, (float*)ws, y, st);
@@ -669,16 +667,15 @@ extern "C" int sdk_segmentation_forward(sdk_ctx* ctx, const void* wblob, const s
               (long long)n_samples);
   const int F = seg_frames(S);
   SDK_REQUIRE((int64_t)B * F < (1ll << 31) / 64, "sdk_segmentation_forward: B*F=%lld frames too many", (long long)B * F);
-  const size_t need = sdk_segmentation_workspace_bytes(d, B, S);
-  SDK_REQUIRE(ws && ws_bytes >= need && (uintptr_t)ws % 256 == 0 && (uintptr_t)wblob % 256 == 0,
-              "sdk_segmentation_forward: workspace of %zu bytes, %zu needed (256-byte aligned)", ws_bytes, need);
+  SDK_REQUIRE_WS("sdk_segmentation_forward", "sdk_segmentation_workspace_bytes", ws, ws_bytes, sdk_segmentation_workspace_bytes(d, B, S), 256);
+  SDK_REQUIRE((uintptr_t)wblob % 256 == 0, "sdk_segmentation_forward: wblob=%p must be 256-byte aligned", wblob);
   const hipStream_t st = (hipStream_t)stream;
   const char* wb = (const char*)wblob;
-  const SegLayout L = seg_layout(B, S);
   char* w = (char*)ws;
-  float* X0 = (float*)(w + L.r2);      // the 60-d frames [B F][64] (R2 is free once conv 3 has read its input)
-  float* G = (float*)(w + L.r1);
-  float* H = (float*)(w + L.r3);
+  SegWs sw;
+  seg_carve({w, 0}, B, S, &sw);
+  float* const X0 = sw.R2;             // the 60-d frames [B F][64] (R2 is free once conv 3 has read its input)
+  float *const G = sw.R1, *const H = sw.R3;
   const bool f16 = d->precision == 2;
   // the last norm reads R1 and writes X0 in R2, whose conv-3 input is dead by then
   if (int rc = f16 ? frontend<true>(ctx, wb, d, samples, n_samples, starts, ld, B, S, w, X0, st)

@@ -135,6 +135,12 @@ __global__ __launch_bounds__(SMT_NT) void smt_drop_kernel(const int2* __restrict
   smt_tally(tallies, r, 1, dropped, live);
 }
 
+// one block: ent [G] int4, then mid [G] int2, then 256 bytes (never 0 bytes: that is the refusal)
+size_t smt_carve(WsCarver c, int64_t G, int4** ent) {
+  *ent = (int4*)c.take<char>((size_t)G * (sizeof(int4) + sizeof(int2)) + 256);
+  return c.bytes();
+}
+
 }  // namespace
 
 extern "C" size_t sdk_smooth_turns_workspace_bytes(int64_t G) {
@@ -142,7 +148,8 @@ extern "C" size_t sdk_smooth_turns_workspace_bytes(int64_t G) {
     sdk_set_error("sdk_smooth_turns_workspace_bytes: G=%lld (fewer than 2^30 frames)", (long long)G);
     return 0;
   }
-  return ((size_t)G * (sizeof(int4) + sizeof(int2)) + 256 + 255) & ~(size_t)255;        // never 0: that is the refusal
+  int4* ent;
+  return smt_carve({}, G, &ent);
 }
 
 extern "C" int sdk_smooth_turns(sdk_ctx* ctx, int32_t* speakers, const int32_t* frame_off, const int32_t* cent_off, int R, int64_t G, int fill_frames,
@@ -155,15 +162,13 @@ extern "C" int sdk_smooth_turns(sdk_ctx* ctx, int32_t* speakers, const int32_t* 
   SDK_REQUIRE(frame_off && cent_off && tallies && (G == 0 || speakers), "sdk_smooth_turns: null argument");
   hipStream_t st = (hipStream_t)stream;
   if (G > 0) {                                         // every refusal comes before the first write: a refused call leaves tallies as they were
-    const size_t need = sdk_smooth_turns_workspace_bytes(G);
-    SDK_REQUIRE(ws, "sdk_smooth_turns: null workspace (%zu bytes needed, sdk_smooth_turns_workspace_bytes)", need);
-    SDK_REQUIRE(ws_bytes >= need, "sdk_smooth_turns: workspace of %zu bytes, %zu needed (sdk_smooth_turns_workspace_bytes)", ws_bytes, need);
-    SDK_REQUIRE(((uintptr_t)ws & 15) == 0 && ((uintptr_t)speakers & 7) == 0, "sdk_smooth_turns: ws=%p must be 16-byte and speakers=%p 8-byte aligned", ws,
-                (void*)speakers);
+    SDK_REQUIRE_WS("sdk_smooth_turns", "sdk_smooth_turns_workspace_bytes", ws, ws_bytes, sdk_smooth_turns_workspace_bytes(G), 16);
+    SDK_REQUIRE(((uintptr_t)speakers & 7) == 0, "sdk_smooth_turns: speakers=%p must be 8-byte aligned", (void*)speakers);
   }
   SDK_HIP_OK(hipMemsetAsync(tallies, 0, (size_t)R * 2 * sizeof(int32_t), st));
   if (G == 0) return 0;
-  int4* ent = static_cast<int4*>(ws);
+  int4* ent;
+  smt_carve({static_cast<char*>(ws), 0}, G, &ent);
   int2* mid = reinterpret_cast<int2*>(ent + G);
   const dim3 grid = pg_grid(G, SMT_NT), nt(SMT_NT);
   const int g = (int)G;

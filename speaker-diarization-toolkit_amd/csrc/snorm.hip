@@ -282,8 +282,7 @@ extern "C" size_t sdk_cohort_stats_workspace_bytes(int N, int M, int K) {
     sdk_set_error("sdk_cohort_stats_workspace_bytes: N=%d M=%d K=%d (N at least 0, 1 <= M <= %d, 1 <= K <= M)", N, M, K, SN_MAX_M);
     return 0;
   }
-  const size_t b = (size_t)sn_alloc_rows(N, M) * (size_t)M * sizeof(float);
-  return (b + 255) & ~(size_t)255;
+  return ws_round((size_t)sn_alloc_rows(N, M) * (size_t)M * sizeof(float));
 }
 
 extern "C" int sdk_cohort_stats(sdk_ctx* ctx, const float* E, int N, const float* Cn, int M, int d, int K, float* mean, float* stdev, void* ws,
@@ -296,8 +295,7 @@ extern "C" int sdk_cohort_stats(sdk_ctx* ctx, const float* E, int N, const float
               (void*)mean, (void*)stdev, ws);
   SDK_REQUIRE((((uintptr_t)E | (uintptr_t)Cn | (uintptr_t)ws) & 15) == 0, "sdk_cohort_stats: E=%p, Cn=%p and ws=%p must be 16-byte aligned", (const void*)E,
               (const void*)Cn, ws);
-  const size_t need = sdk_cohort_stats_workspace_bytes(N, M, K);
-  SDK_REQUIRE(ws_bytes >= need, "sdk_cohort_stats: workspace of %zu bytes, %zu needed (sdk_cohort_stats_workspace_bytes)", ws_bytes, need);
+  SDK_REQUIRE_WS("sdk_cohort_stats", "sdk_cohort_stats_workspace_bytes", ws, ws_bytes, sdk_cohort_stats_workspace_bytes(N, M, K), 1);
   const int rb = sn_alloc_rows(N, M);
   float* S = static_cast<float*>(ws);
   hipStream_t s = (hipStream_t)stream;

@@ -494,17 +494,28 @@ __global__ __launch_bounds__(64) void chol_inverse_kernel(const float* __restric
 }  // namespace
 
 constexpr int MV_MAX_N = 1 << 24;       // rows: the tile and fragment counts of the kernels are 32-bit (N / 32 tiles x 128 threads)
-static size_t mv_xp_bytes(int N) { return (((size_t)((N + PT - 1) / PT) * 4 * 64 * 8 * sizeof(uint16_t)) + 255) & ~(size_t)255; }
 // partial Y tiles: groups x maxp tiles of 64 KiB; maxp <= G / ngroups + 3, so groups x maxp <= G + 3 groups for any row block of <= N rows
 static size_t mv_ypart_bytes(int N) { return ((size_t)MV_MAX_WG + 3 * (size_t)ceil_div(N, MV_SEGS)) * MV_SEGS * KV * sizeof(float); }
+// packed X fragments | partial Y tiles of the parts of every row group | part counts and 256 bytes: the tail is not rounded up
+struct MvWs {
+  bf16_t* xp;
+  float* ypart;
+  int32_t* pcnt;
+};
+static size_t mv_carve(WsCarver c, int N, MvWs* w) {
+  w->xp = c.take<bf16_t>((size_t)ceil_div(N, PT) * 4 * 64 * 8);
+  w->ypart = c.take<float>(mv_ypart_bytes(N) / sizeof(float));
+  w->pcnt = c.take<int32_t>(0);
+  return c.bytes() + (size_t)ceil_div(N, MV_SEGS) * sizeof(int32_t) + 256;
+}
 
 extern "C" size_t sdk_affinity_matvec_workspace_bytes(int N) {
   if (N <= 0 || N > MV_MAX_N) {
     sdk_set_error("sdk_affinity_matvec_workspace_bytes: N=%d (1 .. %d)", N, MV_MAX_N);
     return 0;
   }
-  // packed X fragments | partial Y tiles of the parts of every row group | part counts
-  return mv_xp_bytes(N) + mv_ypart_bytes(N) + (size_t)ceil_div(N, MV_SEGS) * sizeof(int32_t) + 256;
+  MvWs w;
+  return mv_carve({}, N, &w);
 }
 
 extern "C" int sdk_affinity_matvec_plan(int rows, int N, int num_cu, int32_t* out4, int64_t* units) {
@@ -522,28 +533,29 @@ extern "C" int sdk_affinity_matvec(sdk_ctx* ctx, const uint16_t* Eb, int N, int 
   SDK_REQUIRE(N > 0 && N <= MV_MAX_N, "sdk_affinity_matvec: N=%d (1 .. %d)", N, MV_MAX_N);
   SDK_REQUIRE(rows > 0 && row0 >= 0 && row0 <= N - rows, "sdk_affinity_matvec: bad row block [%d, %d + %d) of %d", row0, row0, rows, N);
   SDK_REQUIRE(kv >= 1 && kv <= KV, "sdk_affinity_matvec: kv=%d must be in [1, %d]", kv, KV);
-  SDK_REQUIRE(ws_bytes >= sdk_affinity_matvec_workspace_bytes(N), "sdk_affinity_matvec: workspace too small (%zu bytes, %zu needed)", ws_bytes,
-              sdk_affinity_matvec_workspace_bytes(N));
-  SDK_REQUIRE(((uintptr_t)Eb % 16) == 0 && ((uintptr_t)ws % 16) == 0, "sdk_affinity_matvec: Eb/ws must be 16-byte aligned");
+  SDK_REQUIRE_WS("sdk_affinity_matvec", "sdk_affinity_matvec_workspace_bytes", ws, ws_bytes, sdk_affinity_matvec_workspace_bytes(N), 16);
+  SDK_REQUIRE(((uintptr_t)Eb % 16) == 0, "sdk_affinity_matvec: Eb=%p must be 16-byte aligned", (const void*)Eb);
+  MvWs w;
+  mv_carve({(char*)ws, 0}, N, &w);
   hipStream_t s = (hipStream_t)stream;
   const int ntiles = ceil_div(N, PT);
-  hipLaunchKernelGGL(pack_x_kernel, dim3(ceil_div(ntiles * 2 * 64, 256)), dim3(256), 0, s, X, N, kv, (bf16_t*)ws, xscale);
+  hipLaunchKernelGGL(pack_x_kernel, dim3(ceil_div(ntiles * 2 * 64, 256)), dim3(256), 0, s, X, N, kv, w.xp, xscale);
   SDK_LAUNCH_CHECK();
   if (ctx->matvec_variant == 1) {                    // A/B + test knob ("matvec_variant" 1): round 1's kernel, one 32-row block per wave
     ProfScope ps(ctx, stream, SDK_K_AFF_MATVEC, 2.0 * rows * (double)N * (D + KV), 2.0 * (double)N * D + 4.0 * N * kv);
     hipLaunchKernelGGL(affinity_matvec_kernel, dim3(ceil_div(rows, 128)), dim3(256), 0, s, (const bf16_t*)Eb, N, row0, rows,
-                       (const bf16_t*)ws, kv, Y);
+                       (const bf16_t*)w.xp, kv, Y);
     SDK_LAUNCH_CHECK();
     return 0;
   }
-  float* ypart = reinterpret_cast<float*>((char*)ws + mv_xp_bytes(N));
-  int32_t* pcnt = reinterpret_cast<int32_t*>((char*)ws + mv_xp_bytes(N) + mv_ypart_bytes(N));
+  float* const ypart = w.ypart;
+  int32_t* const pcnt = w.pcnt;
   const MvGeom gm = mv_geometry(rows, N, ctx->num_cu);
   SDK_REQUIRE((size_t)gm.ngroups * gm.maxp * MV_SEGS * KV * sizeof(float) <= mv_ypart_bytes(N), "sdk_affinity_matvec: internal: %d groups x %d parts exceed the workspace", gm.ngroups, gm.maxp);
   if (sdk_lds_optin(ctx, (const void*)affinity_matvec2_kernel, MV_LDS)) return 1;
   {
     ProfScope ps(ctx, stream, SDK_K_AFF_MATVEC, 2.0 * rows * (double)N * (D + KV), 2.0 * (double)N * D + 4.0 * N * kv);
-    hipLaunchKernelGGL(affinity_matvec2_kernel, dim3(gm.G), dim3(MV_WAVES * 64), MV_LDS, s, (const bf16_t*)Eb, N, row0, rows, (const bf16_t*)ws, gm,
+    hipLaunchKernelGGL(affinity_matvec2_kernel, dim3(gm.G), dim3(MV_WAVES * 64), MV_LDS, s, (const bf16_t*)Eb, N, row0, rows, (const bf16_t*)w.xp, gm,
                        ypart, pcnt);
   }
   SDK_LAUNCH_CHECK();
@@ -565,8 +577,7 @@ extern "C" int sdk_rows_gram(sdk_ctx* ctx, const float* X, const float* Yv, int 
                              void* stream) {
   SDK_REQUIRE(ctx && X && Yv && G && ws, "sdk_rows_gram: null argument");
   SDK_REQUIRE(n > 0 && n <= MV_MAX_N && k >= 1 && k <= KV, "sdk_rows_gram: bad shape n=%d k=%d (n 1 .. %d, k 1 .. %d)", n, k, MV_MAX_N, KV);
-  SDK_REQUIRE(ws_bytes >= sdk_rows_gram_workspace_bytes(n, k), "sdk_rows_gram: workspace too small (%zu bytes, %zu needed)", ws_bytes,
-              sdk_rows_gram_workspace_bytes(n, k));
+  SDK_REQUIRE_WS("sdk_rows_gram", "sdk_rows_gram_workspace_bytes", ws, ws_bytes, sdk_rows_gram_workspace_bytes(n, k), 1);
   const int nb = ceil_div(n, GR_ROWS);
   hipLaunchKernelGGL(gram_partial_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, X, Yv, n, k, (float*)ws);
   SDK_LAUNCH_CHECK();

@@ -189,8 +189,7 @@ extern "C" size_t sdk_trial_calib_workspace_bytes(int N, int M, int max_blocks) 
     sdk_set_error("sdk_trial_calib_workspace_bytes: N=%d M=%d max_blocks=%d (1 <= N, M <= %d, max_blocks at least 0)", N, M, max_blocks, TT_MAX_ROWS);
     return 0;
   }
-  const size_t b = (size_t)tt_grid(N, M, max_blocks, nullptr) * TC_ROW * sizeof(double);
-  return (b + 255) & ~(size_t)255;
+  return ws_round((size_t)tt_grid(N, M, max_blocks, nullptr) * TC_ROW * sizeof(double));
 }
 
 extern "C" int sdk_trial_calib(sdk_ctx* ctx, const double* A, int N, const double* B, const double* r, int M, int K, const int32_t* la,
@@ -204,10 +203,7 @@ extern "C" int sdk_trial_calib(sdk_ctx* ctx, const double* A, int N, const doubl
               (void*)counts);
   int64_t tiles = 0;
   const int grid = tt_grid(N, M, max_blocks, &tiles);
-  const size_t need = (size_t)grid * TC_ROW * sizeof(double);
-  SDK_REQUIRE(ws, "sdk_trial_calib: null workspace (%zu bytes needed, sdk_trial_calib_workspace_bytes)", need);
-  SDK_REQUIRE(ws_bytes >= need, "sdk_trial_calib: workspace of %zu bytes, %zu needed (sdk_trial_calib_workspace_bytes)", ws_bytes, need);
-  SDK_REQUIRE(((uintptr_t)ws & 255) == 0, "sdk_trial_calib: ws=%p must be 256-byte aligned", ws);
+  SDK_REQUIRE_WS("sdk_trial_calib", "sdk_trial_calib_workspace_bytes", ws, ws_bytes, (size_t)grid * TC_ROW * sizeof(double), 256);
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(ctx, stream, SDK_K_COPY, 2.0 * N * (double)M * K, 8.0 * (double)tiles * (TT_BM + TT_BN) * K);
   SDK_HIP_OK(hipMemsetAsync(counts, 0, (size_t)TC_COUNTS * sizeof(uint64_t), st));

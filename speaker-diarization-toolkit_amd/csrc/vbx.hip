@@ -573,44 +573,23 @@ __global__ __launch_bounds__(VB_NT) void vbx_hmm_finish_kernel(int nblk, int n, 
   for (int s = tid; s < S; s += VB_NT) pi[s] = h.pinew[s] / s_tot;
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 bool vbx_shape_ok(int n, int D, int S) { return n >= 1 && n <= VB_MAX_ROWS && (D == 64 || D == 128) && S >= 1 && S <= VB_MAX_ROWS; }
 
-// carves the workspace; returns its size
-size_t vbx_carve(char* base, int n, int D, int S, VbxWs* w) {
-  const size_t nblk = (size_t)(n + VB_ROWS - 1) / VB_ROWS;
-  size_t o = 0;
-  auto take = [&](size_t doubles) { char* p = base + o; o += align256(doubles * sizeof(double)); return reinterpret_cast<double*>(p); };
-  double* rho = take((size_t)n * D);
-  double* G = take(n);
-  double* lse = take(n);
-  double* Npart = take(nblk * S);
-  double* Fpart = take(nblk * S * D);
-  double* lsepart = take(nblk);
-  double* N = take(S);
-  double* alphaT = take((size_t)D * S);
-  double* cs = take(S);
-  double* es = take(S);
-  double* prev = take(1);
-  int32_t* done = reinterpret_cast<int32_t*>(take(1));
-  if (w) *w = VbxWs{rho, G, lse, Npart, Fpart, lsepart, N, alphaT, cs, es, prev, done};
-  return o;
+// carves the workspace (the members of VbxWs in their order); returns its size
+size_t vbx_carve(WsCarver c, int n, int D, int S, VbxWs* w) {
+  const size_t nblk = (size_t)(n + VB_ROWS - 1) / VB_ROWS, Ss = S, Ds = D;
+  *w = VbxWs{c.take<double>(n * Ds),      c.take<double>(n),    c.take<double>(n),       c.take<double>(nblk * Ss), c.take<double>(nblk * Ss * Ds),
+             c.take<double>(nblk),        c.take<double>(Ss),   c.take<double>(Ds * Ss), c.take<double>(Ss),        c.take<double>(Ss),
+             c.take<double>(1),           c.take<int32_t>(1)};
+  return c.bytes();
 }
 
 // sdk_vbx_hmm's workspace: sdk_vbx's, then the chain's
-size_t vbx_hmm_carve(char* base, int n, int D, int S, VbxWs* w, VbxHmmWs* h) {
-  const size_t nblk = (size_t)(n + VB_ROWS - 1) / VB_ROWS;
-  size_t o = vbx_carve(base, n, D, S, w);
-  auto take = [&](size_t doubles) { char* p = base + o; o += align256(doubles * sizeof(double)); return reinterpret_cast<double*>(p); };
-  double* logp = take((size_t)n * S);
-  double* lf = take((size_t)n * S);
-  double* lb = take((size_t)n * S);
-  double* m = take(n);
-  double* pipart = take(nblk * S);
-  double* pinew = take(S);
-  if (h) *h = VbxHmmWs{logp, lf, lb, m, pipart, pinew};
-  return o;
+size_t vbx_hmm_carve(WsCarver c, int n, int D, int S, VbxWs* w, VbxHmmWs* h) {
+  const size_t nblk = (size_t)(n + VB_ROWS - 1) / VB_ROWS, Ss = S;
+  c.off = vbx_carve(c, n, D, S, w);
+  *h = VbxHmmWs{c.take<double>(n * Ss), c.take<double>(n * Ss), c.take<double>(n * Ss), c.take<double>(n), c.take<double>(nblk * Ss), c.take<double>(Ss)};
+  return c.bytes();
 }
 
 }  // namespace
@@ -638,7 +617,8 @@ extern "C" size_t sdk_vbx_workspace_bytes(int n, int D, int S) {
     sdk_set_error("sdk_vbx_workspace_bytes: n=%d D=%d S=%d (n and S 1 .. %d, D 64 or 128)", n, D, S, VB_MAX_ROWS);
     return 0;
   }
-  return vbx_carve(nullptr, n, D, S, nullptr);
+  VbxWs w;
+  return vbx_carve({}, n, D, S, &w);
 }
 
 extern "C" int sdk_vbx(sdk_ctx* ctx, const double* X, const double* Phi, const int32_t* labels, int n, int D, int S, double Fa, double Fb,
@@ -655,11 +635,9 @@ extern "C" int sdk_vbx(sdk_ctx* ctx, const double* X, const double* Phi, const i
   SDK_REQUIRE(X && Phi && labels && gamma && pi && elbo && n_iter && status && ws,
               "sdk_vbx: null argument (X=%p Phi=%p labels=%p gamma=%p pi=%p elbo=%p n_iter=%p status=%p ws=%p)", (const void*)X, (const void*)Phi,
               (const void*)labels, (void*)gamma, (void*)pi, (void*)elbo, (void*)n_iter, (void*)status, ws);
-  const size_t need = vbx_carve(nullptr, n, D, S, nullptr);
-  SDK_REQUIRE(ws_bytes >= need, "sdk_vbx: workspace of %zu bytes, %zu needed", ws_bytes, need);
-  SDK_REQUIRE(((uintptr_t)ws & 255) == 0, "sdk_vbx: ws=%p must be 256-byte aligned", ws);
+  SDK_REQUIRE_WS("sdk_vbx", "sdk_vbx_workspace_bytes", ws, ws_bytes, sdk_vbx_workspace_bytes(n, D, S), 256);
   VbxWs w;
-  vbx_carve(static_cast<char*>(ws), n, D, S, &w);
+  vbx_carve({static_cast<char*>(ws), 0}, n, D, S, &w);
   const int nblk = (n + VB_ROWS - 1) / VB_ROWS;
   hipStream_t st = (hipStream_t)stream;
   const dim3 gstats(nblk, (S + VB_SC - 1) / VB_SC);
@@ -694,7 +672,9 @@ extern "C" size_t sdk_vbx_hmm_workspace_bytes(int n, int D, int S) {
     sdk_set_error("sdk_vbx_hmm_workspace_bytes: n=%d D=%d S=%d (n and S 1 .. %d, D 64 or 128)", n, D, S, VB_MAX_ROWS);
     return 0;
   }
-  return vbx_hmm_carve(nullptr, n, D, S, nullptr, nullptr);
+  VbxWs w;
+  VbxHmmWs h;
+  return vbx_hmm_carve({}, n, D, S, &w, &h);
 }
 
 extern "C" int sdk_vbx_hmm(sdk_ctx* ctx, const double* X, const double* Phi, const int32_t* labels, int n, int D, int S, double Fa, double Fb,
@@ -712,12 +692,10 @@ extern "C" int sdk_vbx_hmm(sdk_ctx* ctx, const double* X, const double* Phi, con
   SDK_REQUIRE(X && Phi && labels && gamma && pi && elbo && n_iter && status && ws,
               "sdk_vbx_hmm: null argument (X=%p Phi=%p labels=%p gamma=%p pi=%p elbo=%p n_iter=%p status=%p ws=%p)", (const void*)X, (const void*)Phi,
               (const void*)labels, (void*)gamma, (void*)pi, (void*)elbo, (void*)n_iter, (void*)status, ws);
-  const size_t need = vbx_hmm_carve(nullptr, n, D, S, nullptr, nullptr);
-  SDK_REQUIRE(ws_bytes >= need, "sdk_vbx_hmm: workspace of %zu bytes, %zu needed", ws_bytes, need);
-  SDK_REQUIRE(((uintptr_t)ws & 255) == 0, "sdk_vbx_hmm: ws=%p must be 256-byte aligned", ws);
+  SDK_REQUIRE_WS("sdk_vbx_hmm", "sdk_vbx_hmm_workspace_bytes", ws, ws_bytes, sdk_vbx_hmm_workspace_bytes(n, D, S), 256);
   VbxWs w;
   VbxHmmWs h;
-  vbx_hmm_carve(static_cast<char*>(ws), n, D, S, &w, &h);
+  vbx_hmm_carve({static_cast<char*>(ws), 0}, n, D, S, &w, &h);
   const int nblk = (n + VB_ROWS - 1) / VB_ROWS;
   const double lnP = log(loop_prob), ln1mP = log1p(-loop_prob);          // loop_prob == 0: -inf and 0
   hipStream_t st = (hipStream_t)stream;

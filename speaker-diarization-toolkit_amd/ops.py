@@ -81,13 +81,14 @@ class Engine(BlocksMixin, ClusterMixin, ScoreMixin):
             self._scratch[key] = buf = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
         return buf
 
-    def _workspace_bytes(self, sizer: str, *args) -> int:
-        """The byte count of the library's sizer `sizer` (an sdk_*_workspace_bytes, by name) for `args`; 0 is its refusal of them: SdkError
-        with the library's message."""
+    def _workspace(self, sizer: str, *args, cache: Optional[str] = None) -> torch.Tensor:
+        """A uint8 device tensor of at least the bytes the library's sizer `sizer` (an sdk_*_workspace_bytes, by name) asks for `args`; 0 is
+        its refusal of them: SdkError with the library's message.  cache: the key of the per-stream scratch to take it from (grown when too
+        small, never shrunk: numel() may exceed the sizer's count); None: a fresh tensor of exactly that many bytes."""
         nbytes = int(getattr(self.lib, sizer)(*args))
         if nbytes == 0:
-            raise SdkError(f"{sizer}: {self.lib.sdk_last_error().decode()}")
-        return nbytes
+            raise SdkError(f"{sizer}: {(self.lib.sdk_last_error() or b'?').decode()}")
+        return torch.empty(nbytes, dtype=torch.uint8, device=self.device) if cache is None else self._scratch_bytes(cache, nbytes)
 
     def fbank_tables(self) -> torch.Tensor:
         if self._fbank_tabs is None:
@@ -157,7 +158,7 @@ class Engine(BlocksMixin, ClusterMixin, ScoreMixin):
             feats = self.fbank(pcm)
             nfl = self.lib.sdk_ecapa_calib_floats(C.byref(d), B)
             calib = torch.zeros((nfl,), dtype=torch.float32, device=self.device)
-            ws = self._scratch_bytes("ecapa", self.lib.sdk_ecapa_workspace_bytes(C.byref(d), B, T))
+            ws = self._workspace("sdk_ecapa_workspace_bytes", C.byref(d), B, T, cache="ecapa")
             emb = torch.empty((B, self.cfg.embed_dim), dtype=torch.float32, device=self.device)
             check(self.lib.sdk_ecapa_forward_calib(self.ctx, wdev.data_ptr(), C.byref(d), feats.data_ptr(), feats.stride(0), B, T, ws.data_ptr(),
                                                    ws.numel(), emb.data_ptr(), calib.data_ptr(), _stream()), "sdk_ecapa_forward_calib")
@@ -270,7 +271,7 @@ class Engine(BlocksMixin, ClusterMixin, ScoreMixin):
         pcm = pcm.contiguous()
         B, S = pcm.shape
         ldf, feats = self._fbank_out(B, S, ldf)
-        ws = self._scratch_bytes("fbank", self.lib.sdk_fbank_workspace_bytes(B, S))
+        ws = self._workspace("sdk_fbank_workspace_bytes", B, S, cache="fbank")
         check(self.lib.sdk_fbank_fmt(self.ctx, pcm.data_ptr(), B, S, self.fbank_tables().data_ptr(), feats.data_ptr(), ldf,
                                      ws.data_ptr(), ws.numel(), self.precision, _stream()), "sdk_fbank")
         return feats
@@ -279,7 +280,7 @@ class Engine(BlocksMixin, ClusterMixin, ScoreMixin):
         """fbank with the windows cut on the device (sdk_fbank_windows): samples_ptr -> int16 [n_samples] resident recording, starts_ptr -> int32 [B]
         first samples; same features as fbank() on the materialised [B, S] windows, bit for bit."""
         ldf, feats = self._fbank_out(B, S, ldf)
-        ws = self._scratch_bytes("fbank", self.lib.sdk_fbank_workspace_bytes(B, S))
+        ws = self._workspace("sdk_fbank_workspace_bytes", B, S, cache="fbank")
         check(self.lib.sdk_fbank_windows_fmt(self.ctx, samples_ptr, n_samples, starts_ptr, B, S, self.fbank_tables().data_ptr(), feats.data_ptr(), ldf,
                                              ws.data_ptr(), ws.numel(), self.precision, _stream()), "sdk_fbank_windows")
         return feats
@@ -350,8 +351,7 @@ class Engine(BlocksMixin, ClusterMixin, ScoreMixin):
         """feats [B*T, ldf] bf16 (precise mode: fp16 planes) -> raw embeddings [B, 192] fp32."""
         self._need_feats(feats, B, T)
         d = self.desc
-        wsb = self.lib.sdk_ecapa_workspace_bytes(C.byref(d), B, T)
-        ws = self._scratch_bytes("ecapa", wsb)
+        ws = self._workspace("sdk_ecapa_workspace_bytes", C.byref(d), B, T, cache="ecapa")
         emb = torch.empty((B, self.cfg.embed_dim), dtype=torch.float32, device=self.device)
         check(self.lib.sdk_ecapa_forward(self.ctx, self._wblob.data_ptr(), C.byref(d), feats.data_ptr(), feats.stride(0),
                                          B, T, ws.data_ptr(), ws.numel(), emb.data_ptr(), _stream()), "sdk_ecapa_forward")
@@ -370,7 +370,7 @@ class Engine(BlocksMixin, ClusterMixin, ScoreMixin):
             raise ValueError(f"ecapa_forward_masked: S = {S} weight rows per chunk (served: 1 .. 8)")
         _args.tensor("ecapa_forward_masked", "valid", valid, "int32", (B, S))
         d = self.desc
-        ws = self._scratch_bytes("ecapa_masked", self.lib.sdk_ecapa_masked_workspace_bytes(C.byref(d), B, T, S))
+        ws = self._workspace("sdk_ecapa_masked_workspace_bytes", C.byref(d), B, T, S, cache="ecapa_masked")
         emb = torch.empty((B * S, self.cfg.embed_dim), dtype=torch.float32, device=self.device)
         check(self.lib.sdk_ecapa_forward_masked(self.ctx, self._wblob.data_ptr(), C.byref(d), feats.data_ptr(), feats.stride(0), B, T, S,
                                                 w.data_ptr(), valid.data_ptr(), ws.data_ptr(), ws.numel(), emb.data_ptr(), _stream()),
@@ -401,7 +401,7 @@ class Engine(BlocksMixin, ClusterMixin, ScoreMixin):
         idx = torch.empty((N, k), dtype=torch.int32, device=self.device)
         sc = torch.empty((N, k), dtype=torch.float32, device=self.device)
         cnt = torch.zeros((1,), dtype=torch.int32, device=self.device) if want_count else None
-        ws = self._scratch_bytes("affinity", self.lib.sdk_affinity_workspace_bytes(N, Pn))
+        ws = self._workspace("sdk_affinity_workspace_bytes", N, Pn, cache="affinity")
         check(self.lib.sdk_affinity_topk(self.ctx, E.data_ptr(), Eb.data_ptr(), re.data_ptr(), P.data_ptr(), Pb.data_ptr(),
                                          rp_max.data_ptr(), N, Pn, d, k, idx.data_ptr(), sc.data_ptr(), _ptr(cnt),
                                          ws.data_ptr(), ws.numel(), _stream()), "sdk_affinity_topk")

@@ -1,8 +1,8 @@
 """Engine's building blocks, kept for tests and tuning: the conv GEMM of both modes, the layout conversions, and the sweeps of the forward
 one kernel at a time (SE, attentive statistics pooling, the per-utterance FC).  The product's forward never calls them: it is one C call.
 
-BlocksMixin is a mixin of ops.Engine: no state and no __init__ of its own.  It uses self.lib, self.ctx, self.device, self._scratch_bytes
-and self._workspace_bytes only, and this module imports ops.py for nothing (ops.py imports it).
+BlocksMixin is a mixin of ops.Engine: no state and no __init__ of its own.  It uses self.lib, self.ctx, self.device, self._workspace
+only, and this module imports ops.py for nothing (ops.py imports it).
 """
 from __future__ import annotations
 
@@ -139,7 +139,7 @@ class BlocksMixin:
     def se_gate_residual(self, z, x, w1t, b1, w2t, b2, B, T, split: bool = True):
         C_ = z.shape[1]
         out = torch.empty_like(z)
-        ws = self._scratch_bytes("se", self.lib.sdk_se_workspace_bytes(B, C_, w1t.shape[1])) if split else None
+        ws = self._workspace("sdk_se_workspace_bytes", B, C_, w1t.shape[1], cache="se") if split else None
         fmt = _elem_fmt(z, "se_gate_residual")
         if x.dtype != z.dtype:
             raise ValueError(f"se_gate_residual: z is {z.dtype} but x is {x.dtype}")

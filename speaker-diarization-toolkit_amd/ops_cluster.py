@@ -1,8 +1,8 @@
 """Engine's clustering calls: the spectral pieces (the rectified-affinity mat-vec, the C spectral driver and the thin [n, k] helpers), both
 centroid linkages, the device k-means, the PLDA transform with VBx and its centroids, and the streaming diarization's speaker tracking.
 
-ClusterMixin is a mixin of ops.Engine: no state and no __init__ of its own.  It uses self.lib, self.ctx, self.device, self._scratch_bytes
-and self._workspace_bytes only, and this module imports ops.py for nothing (ops.py imports it).
+ClusterMixin is a mixin of ops.Engine: no state and no __init__ of its own.  It uses self.lib, self.ctx, self.device, self._workspace
+only, and this module imports ops.py for nothing (ops.py imports it).
 """
 from __future__ import annotations
 
@@ -81,7 +81,7 @@ class ClusterMixin:
         kv = X.shape[1]
         rows = N - row0 if rows is None else rows
         Y = out if out is not None else torch.zeros((N, kv), dtype=torch.float32, device=self.device)
-        ws = self._scratch_bytes("matvec", self.lib.sdk_affinity_matvec_workspace_bytes(N))
+        ws = self._workspace("sdk_affinity_matvec_workspace_bytes", N, cache="matvec")
         check(self.lib.sdk_affinity_matvec(self.ctx, Eb.data_ptr(), N, d, row0, rows, X.contiguous().data_ptr(), _ptr(xscale), kv,
                                            Y.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "sdk_affinity_matvec")
         return Y
@@ -113,7 +113,7 @@ class ClusterMixin:
             raise ValueError(f"{what}: flag must hold one int32, got shape {list(flag.shape)}")
         V = V0.contiguous().clone()
         lam = torch.empty((k,), dtype=torch.float32, device=self.device)
-        ws = self._scratch_bytes("laplacian", self.lib.sdk_laplacian_topk_workspace_bytes(N, k))
+        ws = self._workspace("sdk_laplacian_topk_workspace_bytes", N, k, cache="laplacian")
         check(self.lib.sdk_laplacian_topk(self.ctx, Eb_all.data_ptr(), N, row0, rows, k, n_iter, V.data_ptr(), lam.data_ptr(), _ptr(flag), ws.data_ptr(),
                                           ws.numel(), comm, world, _stream()), "sdk_laplacian_topk")
         return V, lam
@@ -123,7 +123,7 @@ class ClusterMixin:
         n, k = _args.thin("rows_gram", "X", X)
         _args.tensor("rows_gram", "Y", Y, "float32", (n, k))
         G = torch.empty((k, k), dtype=torch.float32, device=self.device)
-        ws = self._scratch_bytes("gram", self.lib.sdk_rows_gram_workspace_bytes(n, k))
+        ws = self._workspace("sdk_rows_gram_workspace_bytes", n, k, cache="gram")
         check(self.lib.sdk_rows_gram(self.ctx, X.data_ptr(), Y.data_ptr(), n, k, G.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "sdk_rows_gram")
         return G
 
@@ -209,12 +209,11 @@ class ClusterMixin:
             E = E.contiguous()
         N, d = E.shape
         off, off32, G, op = _linkage_offsets("centroid_linkage", offsets, N)
-        nbytes = self._workspace_bytes("sdk_centroid_linkage_workspace_bytes", op, G, d)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        ws = self._workspace("sdk_centroid_linkage_workspace_bytes", op, G, d)
         Zbuf = torch.empty((max(N - G, 1), 4), dtype=torch.float64, device=self.device)   # never a null pointer (G single-row problems: no rows)
         status = torch.empty((G,), dtype=torch.int32, device=self.device)
         check(self.lib.sdk_centroid_linkage(self.ctx, E.data_ptr(), E.stride(0), d, op, G, Zbuf.data_ptr(), status.data_ptr(), ws.data_ptr(),
-                                            nbytes, _stream()), "sdk_centroid_linkage")
+                                            ws.numel(), _stream()), "sdk_centroid_linkage")
         Z = Zbuf[:N - G]
         _linkage_status("centroid_linkage", off, status, Z)
         return Z
@@ -238,13 +237,12 @@ class ClusterMixin:
         if not stop >= 0.0:
             raise ValueError(f"linked_linkage: stop={stop} (a distance >= 0, or None / +inf for every allowed merge)")
         off, off32, G, op = _linkage_offsets("linked_linkage", offsets, N)
-        nbytes = self._workspace_bytes("sdk_linked_linkage_workspace_bytes", op, G, d)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        ws = self._workspace("sdk_linked_linkage_workspace_bytes", op, G, d)
         Zbuf = torch.empty((max(N - G, 1), 4), dtype=torch.float64, device=self.device)   # never a null pointer
         merges = torch.empty((G,), dtype=torch.int32, device=self.device)
         status = torch.empty((G,), dtype=torch.int32, device=self.device)
         check(self.lib.sdk_linked_linkage(self.ctx, E.data_ptr(), E.stride(0), d, group.data_ptr(), op, G, stop, Zbuf.data_ptr(), merges.data_ptr(),
-                                          status.data_ptr(), ws.data_ptr(), nbytes, _stream()), "sdk_linked_linkage")
+                                          status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "sdk_linked_linkage")
         Z = Zbuf[:N - G]
         _linkage_status("linked_linkage", off, status, Z, merges)
         return Z, merges
@@ -260,14 +258,13 @@ class ClusterMixin:
             raise ValueError(f"kmeans_rows: k={k} (1 .. min(n, 64), n={n})")
         if max_iters < 1 or max_iters > 1000:
             raise ValueError(f"kmeans_rows: max_iters={max_iters} (1 .. 1000)")
-        nbytes = self._workspace_bytes("sdk_kmeans_rows_workspace_bytes", n, d, k)
+        ws = self._workspace("sdk_kmeans_rows_workspace_bytes", n, d, k)
         dev = E.device
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         labels = torch.empty((n,), dtype=torch.int32, device=dev)
         n_iter = torch.empty((1,), dtype=torch.int32, device=dev)
         status = torch.empty((1,), dtype=torch.int32, device=dev)
         check(self.lib.sdk_kmeans_rows(self.ctx, E.data_ptr(), rows.data_ptr(), n, d, k, max_iters, labels.data_ptr(), n_iter.data_ptr(),
-                                       status.data_ptr(), ws.data_ptr(), nbytes, _stream()), "sdk_kmeans_rows")
+                                       status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "sdk_kmeans_rows")
         return labels, n_iter, status
 
     # ---- VBx clustering (cluster.vbx_cluster, plda.py; csrc/vbx.hip): nothing here synchronises with the host except the range check of rows
@@ -318,16 +315,15 @@ class ClusterMixin:
         Fa, Fb, epsilon, init_smoothing = float(Fa), float(Fb), float(epsilon), float(init_smoothing)
         if not (0 < Fa < np.inf and 0 < Fb < np.inf) or epsilon != epsilon or not (0 <= init_smoothing < np.inf):
             raise ValueError(f"{who}: Fa={Fa} Fb={Fb} (positive, finite), epsilon={epsilon} (not NaN), init_smoothing={init_smoothing} (finite, >= 0)")
-        nbytes = self._workspace_bytes("sdk_vbx_workspace_bytes" if loop_prob is None else "sdk_vbx_hmm_workspace_bytes", n, D, S)
+        ws = self._workspace("sdk_vbx_workspace_bytes" if loop_prob is None else "sdk_vbx_hmm_workspace_bytes", n, D, S)
         dev = X.device
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         gamma = torch.empty((n, S), dtype=torch.float64, device=dev)
         pi = torch.empty((S,), dtype=torch.float64, device=dev)
         elbo = torch.empty((max_iters,), dtype=torch.float64, device=dev)
         n_iter = torch.empty((1,), dtype=torch.int32, device=dev)
         status = torch.empty((1,), dtype=torch.int32, device=dev)
         head = (self.ctx, X.data_ptr(), Phi.data_ptr(), labels.data_ptr(), n, D, S, Fa, Fb, max_iters, epsilon, init_smoothing)
-        tail = (gamma.data_ptr(), pi.data_ptr(), elbo.data_ptr(), n_iter.data_ptr(), status.data_ptr(), ws.data_ptr(), nbytes, _stream())
+        tail = (gamma.data_ptr(), pi.data_ptr(), elbo.data_ptr(), n_iter.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
         if loop_prob is None:
             check(self.lib.sdk_vbx(*head, *tail), "sdk_vbx")
         else:
@@ -449,10 +445,9 @@ def knn_reverse(eng, idx: torch.Tensor, check_idx: bool = True):
     rev_src = torch.empty((n * P,), dtype=torch.int32, device=eng.device)
     rev_rank = torch.empty((n * P,), dtype=torch.int32, device=eng.device)
     status = torch.empty((2,), dtype=torch.int32, device=eng.device)
-    nbytes = eng._workspace_bytes("sdk_knn_reverse_workspace_bytes", n, P)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=eng.device)
+    ws = eng._workspace("sdk_knn_reverse_workspace_bytes", n, P)
     check(eng.lib.sdk_knn_reverse(eng.ctx, idx.data_ptr(), n, P, rev_off.data_ptr(), rev_src.data_ptr(), rev_rank.data_ptr(), status.data_ptr(),
-                                   ws.data_ptr(), nbytes, _stream()), "sdk_knn_reverse")
+                                   ws.data_ptr(), ws.numel(), _stream()), "sdk_knn_reverse")
     bad, first = (int(v) for v in status.cpu().numpy()) if check_idx else (0, 0)
     if bad:
         raise ValueError(f"knn_reverse: row {first} of idx lists a row outside [0, {n}) ({bad} such entries in all)")

@@ -4,8 +4,8 @@ pass (trials.py), the histogram on the cohort-normalised scale (trials_snorm.py)
 diarization's frames (words.py) and each speaker's solo runs and clip scores (samples.py).  Nothing here synchronises with the host except
 plda_fit_stats' range check of its labels.
 
-ScoreMixin is a mixin of ops.Engine: no state and no __init__ of its own.  It uses self.lib, self.ctx, self.device, self._scratch_bytes
-and self._workspace_bytes only, and this module imports ops.py for nothing (ops.py imports it).
+ScoreMixin is a mixin of ops.Engine: no state and no __init__ of its own.  It uses self.lib, self.ctx, self.device, self._workspace
+only, and this module imports ops.py for nothing (ops.py imports it).
 """
 from __future__ import annotations
 
@@ -32,11 +32,7 @@ class ScoreMixin:
             raise ValueError(f"cohort_stats: M={M} cohort rows (1 .. 2^20)")
         if K < 1 or K > M:
             raise ValueError(f"cohort_stats: K={K} (1 .. M={M})")
-        nbytes = self._workspace_bytes("sdk_cohort_stats_workspace_bytes", N, M, K)
-        if ws is None:
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=E.device)
-        else:
-            _args.tensor("cohort_stats", "ws", ws, "uint8", (None,))
+        ws = self._workspace("sdk_cohort_stats_workspace_bytes", N, M, K) if ws is None else _args.tensor("cohort_stats", "ws", ws, "uint8", (None,))
         mean = torch.empty((N,), dtype=torch.float32, device=E.device)
         std = torch.empty((N,), dtype=torch.float32, device=E.device)
         check(self.lib.sdk_cohort_stats(self.ctx, E.data_ptr(), N, cohort.data_ptr(), M, d, K, mean.data_ptr(), std.data_ptr(), ws.data_ptr(),
@@ -101,13 +97,12 @@ class ScoreMixin:
             order = torch.sort(labels, stable=True).indices.to(torch.int32)
             counts = torch.empty((K,), dtype=torch.int64, device=dev)
             sums = torch.empty((K, d), dtype=torch.float64, device=dev)
-        nbytes = self._workspace_bytes("sdk_plda_fit_stats_workspace_bytes", N, d, K, int(bool(scatter)))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = self._workspace("sdk_plda_fit_stats_workspace_bytes", N, d, K, int(bool(scatter)))
         total = torch.empty((d,), dtype=torch.float64, device=dev)
         S = torch.empty((d, d), dtype=torch.float64, device=dev) if scatter else None
         status = torch.empty((1,), dtype=torch.int32, device=dev)
         check(self.lib.sdk_plda_fit_stats(self.ctx, rows.data_ptr() if f32 else None, None if f32 else rows.data_ptr(), _ptr(mean1), N, d, _ptr(labels),
-                                          _ptr(order), K, _ptr(counts), _ptr(sums), total.data_ptr(), _ptr(S), status.data_ptr(), ws.data_ptr(), nbytes,
+                                          _ptr(order), K, _ptr(counts), _ptr(sums), total.data_ptr(), _ptr(S), status.data_ptr(), ws.data_ptr(), ws.numel(),
                                           _stream()), "sdk_plda_fit_stats")
         return dict(counts=counts, sums=sums, total=total, scatter=S, status=status)
 
@@ -145,14 +140,13 @@ class ScoreMixin:
         if S < 1 or S > 1 << 20:
             raise ValueError(f"plda_enroll: S={S} speakers (1 .. 2^20)")
         _args.tensor(who, "Phi", Phi, "float64", (D,))
-        nbytes = self._workspace_bytes("sdk_plda_enroll_workspace_bytes", P, S)
+        ws = self._workspace("sdk_plda_enroll_workspace_bytes", P, S)
         dev = Xp.device
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         G = torch.empty((S, 2 * D), dtype=torch.float64, device=dev)
         r = torch.empty((S,), dtype=torch.float64, device=dev)
         status = torch.empty((1,), dtype=torch.int32, device=dev)
         check(self.lib.sdk_plda_enroll(self.ctx, Xp.data_ptr() if P else None, group.data_ptr() if P else None, P, D, n_eff.data_ptr(),
-                                       Phi.data_ptr(), S, G.data_ptr(), r.data_ptr(), status.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+                                       Phi.data_ptr(), S, G.data_ptr(), r.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
               "sdk_plda_enroll")
         return G, r, status
 
@@ -175,12 +169,8 @@ class ScoreMixin:
         _args.tensor(who, "r", r, "float64", (S,))
         if k < 1 or k > 4:
             raise ValueError(f"plda_score_topk: k={k} (1 .. 4)")
-        nbytes = self._workspace_bytes("sdk_plda_score_workspace_bytes", N, S, k)
+        ws = self._workspace("sdk_plda_score_workspace_bytes", N, S, k) if ws is None else _args.tensor(who, "ws", ws, "uint8", (None,))
         dev = X.device
-        if ws is None:
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        else:
-            _args.tensor(who, "ws", ws, "uint8", (None,))
         idx = torch.empty((N, k), dtype=torch.int32, device=dev)
         sc = torch.empty((N, k), dtype=torch.float64, device=dev)
         full = torch.empty((N, S), dtype=torch.float64, device=dev) if scores else None
@@ -265,12 +255,11 @@ def trial_calib(engine, A: torch.Tensor, B: torch.Tensor, r: torch.Tensor, la: t
     if not (np.isfinite(a) and np.isfinite(c)):
         raise ValueError(f"trial_calib: a={a}, c={c} (the map z = a s + c: both finite)")
     max_blocks = _trial_max_blocks("trial_calib", max_blocks)
-    nbytes = engine._workspace_bytes("sdk_trial_calib_workspace_bytes", N, M, max_blocks)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=A.device)
+    ws = engine._workspace("sdk_trial_calib_workspace_bytes", N, M, max_blocks)
     sums = torch.empty((2, 7), dtype=torch.float64, device=A.device)
     counts = torch.empty((5,), dtype=torch.int64, device=A.device)                     # uint64 counters, all below 2^40
     check(engine.lib.sdk_trial_calib(engine.ctx, A.data_ptr(), N, B.data_ptr(), r.data_ptr(), M, K, la.data_ptr(), sa.data_ptr(), lb.data_ptr(),
-                                     sb.data_ptr(), a, c, max_blocks, sums.data_ptr(), counts.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+                                     sb.data_ptr(), a, c, max_blocks, sums.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
           "sdk_trial_calib")
     return counts[0:2], sums, counts[2:4], counts[4:5]
 
@@ -387,10 +376,9 @@ def samples_runs(engine, speakers: torch.Tensor, frame_off: torch.Tensor, cent_o
     cap = G // min_frames
     run_off = torch.empty((R + 1,), dtype=torch.int32, device=speakers.device)
     rows = torch.empty((max(cap, 1), 4), dtype=torch.int32, device=speakers.device)
-    nbytes = engine._workspace_bytes("sdk_samples_runs_workspace_bytes", G)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=speakers.device)
+    ws = engine._workspace("sdk_samples_runs_workspace_bytes", G)
     check(engine.lib.sdk_samples_runs(engine.ctx, speakers.data_ptr() if G else None, frame_off.data_ptr(), cent_off.data_ptr(), R, G, max_hyp, gap_frames,
-                                      min_frames, run_off.data_ptr(), rows.data_ptr(), cap, ws.data_ptr(), nbytes, _stream()), "sdk_samples_runs")
+                                      min_frames, run_off.data_ptr(), rows.data_ptr(), cap, ws.data_ptr(), ws.numel(), _stream()), "sdk_samples_runs")
     return run_off, rows
 
 
@@ -419,9 +407,8 @@ def samples_score(engine, E: torch.Tensor, clip_off: torch.Tensor, clip_spk: tor
     mean = torch.empty((S, d), dtype=torch.float64, device=dev)
     out_f = torch.empty((M, 2), dtype=torch.float64, device=dev)
     out_i = torch.empty((M, 3), dtype=torch.int32, device=dev)
-    nbytes = engine._workspace_bytes("sdk_samples_score_workspace_bytes", M, S, d)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = engine._workspace("sdk_samples_score_workspace_bytes", M, S, d)
     check(engine.lib.sdk_samples_score(engine.ctx, E.data_ptr() if W else None, W, d, clip_off.data_ptr(), clip_spk.data_ptr() if M else None, M,
                                        spk_off.data_ptr(), R, S, mean.data_ptr() if S else None, out_f.data_ptr() if M else None,
-                                       out_i.data_ptr() if M else None, ws.data_ptr(), nbytes, _stream()), "sdk_samples_score")
+                                       out_i.data_ptr() if M else None, ws.data_ptr(), ws.numel(), _stream()), "sdk_samples_score")
     return mean, out_f, out_i

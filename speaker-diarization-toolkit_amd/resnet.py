@@ -234,7 +234,7 @@ class ResNet34:
         from ._lib import check
         from .ops import _stream
         lib = self.eng.lib
-        ws = self.eng._scratch_bytes("resnet", lib.sdk_resnet_workspace_bytes(C.byref(self.desc), B, T))
+        ws = self.eng._workspace("sdk_resnet_workspace_bytes", C.byref(self.desc), B, T, cache="resnet")
         emb = torch.empty((B, self.cfg.embed_dim), dtype=torch.float32, device=self.eng.device)
         check(lib.sdk_resnet_forward(self.eng.ctx, self.blob.data_ptr(), C.byref(self.desc), feats.data_ptr(), feats.stride(0), B, T,
                                      ws.data_ptr(), ws.numel(), emb.data_ptr(), _stream()), "sdk_resnet_forward")
@@ -255,7 +255,7 @@ class ResNet34:
         T4 = self.last_map_frames(T)
         S = int(_args.tensor("forward_masked", "w", w, "float32", (B, None, T4)).shape[1])      # T4: the width of the last map
         _args.tensor("forward_masked", "valid", valid, "int32", (B, S))
-        ws = self.eng._scratch_bytes("resnet", lib.sdk_resnet_masked_workspace_bytes(C.byref(self.desc), B, T, S))
+        ws = self.eng._workspace("sdk_resnet_masked_workspace_bytes", C.byref(self.desc), B, T, S, cache="resnet")
         emb = torch.empty((B * S, self.cfg.embed_dim), dtype=torch.float32, device=self.eng.device)
         check(lib.sdk_resnet_forward_masked(self.eng.ctx, self.blob.data_ptr(), C.byref(self.desc), feats.data_ptr(), feats.stride(0), B, T, S,
                                             w.data_ptr(), valid.data_ptr(), ws.data_ptr(), ws.numel(), emb.data_ptr(), _stream()),

@@ -314,9 +314,6 @@ class Segmentation:
         blob, self.desc = pack_weights(self.weights, self.precision)
         self.blob = torch.from_numpy(blob).to(engine.device)
 
-    def _ws(self, key: str, nbytes: int):
-        return self.eng._scratch_bytes(key, max(int(nbytes), 256))
-
     @staticmethod
     def _source(samples, starts, ld, B, S):
         """-> (samples, starts, ld, B, S, n): n samples are addressable from samples.data_ptr().  A [B, S] matrix may be a view with a row
@@ -342,7 +339,9 @@ class Segmentation:
         lib = self.eng.lib
         F = num_frames(S)
         logp = torch.empty((B, max(F, 0), 7), dtype=torch.float32, device=self.eng.device)
-        ws = self._ws("segmentation", lib.sdk_segmentation_workspace_bytes(C.byref(self.desc), B, S))
+        if B == 0:
+            return logp
+        ws = self.eng._workspace("sdk_segmentation_workspace_bytes", C.byref(self.desc), B, S, cache="segmentation")
         check(lib.sdk_segmentation_forward(self.eng.ctx, self.blob.data_ptr(), C.byref(self.desc), samples.data_ptr(), n,
                                            starts.data_ptr() if starts is not None else None, ld, B, S, ws.data_ptr(), ws.numel(),
                                            logp.data_ptr(), _stream()), "sdk_segmentation_forward")
@@ -356,7 +355,9 @@ class Segmentation:
         samples, starts, ld, B, S, n = self._source(samples, starts, ld, B, S)
         lib = self.eng.lib
         out = torch.empty((B * num_frames(S), 64), dtype=torch.float32, device=self.eng.device)
-        ws = self._ws("segmentation", lib.sdk_segmentation_workspace_bytes(C.byref(self.desc), B, S))
+        if B == 0:
+            return out
+        ws = self.eng._workspace("sdk_segmentation_workspace_bytes", C.byref(self.desc), B, S, cache="segmentation")
         check(lib.sdk_sincnet_frontend(self.eng.ctx, self.blob.data_ptr(), C.byref(self.desc), samples.data_ptr(), n,
                                        starts.data_ptr() if starts is not None else None, ld, B, S, ws.data_ptr(), ws.numel(),
                                        out.data_ptr(), _stream()), "sdk_sincnet_frontend")
@@ -368,7 +369,7 @@ class Segmentation:
         from ._lib import check
         from .ops import _stream
         y = torch.empty((B * F, 256), dtype=torch.float32, device=self.eng.device)
-        ws = self._ws("segmentation_lstm", B * F * 4096)
+        ws = self.eng._scratch_bytes("segmentation_lstm", B * F * 4096)             # (no sizer: the gate pre-activations, [B F][1024] fp32)
         check(self.eng.lib.sdk_bilstm_layer(self.eng.ctx, self.blob.data_ptr(), C.byref(self.desc), int(layer), x.data_ptr(), x.stride(0), B, F,
                                             ws.data_ptr(), ws.numel(), y.data_ptr(), _stream()), "sdk_bilstm_layer")
         return y

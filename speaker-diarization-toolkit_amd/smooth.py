@@ -188,10 +188,9 @@ def smooth_turns(eng, speakers_dev, tab_or_offsets, fill: int, keep: int, cap: i
         raise ValueError(f"smooth_turns: G={G} frames in one pack (fewer than 2^30)")
     out = speakers_dev.clone()
     tallies = torch.empty((R, 2), dtype=torch.int32, device=speakers_dev.device)
-    nbytes = eng._workspace_bytes("sdk_smooth_turns_workspace_bytes", G)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=speakers_dev.device)
+    ws = eng._workspace("sdk_smooth_turns_workspace_bytes", G)
     check(eng.lib.sdk_smooth_turns(eng.ctx, out.data_ptr() if G else None, frame_off.data_ptr(), cent_off.data_ptr(), R, G, fill, keep, cap,
-                                   tallies.data_ptr(), ws.data_ptr(), nbytes, _stream()), "sdk_smooth_turns")
+                                   tallies.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "sdk_smooth_turns")
     return out, tallies
 
 

@@ -243,7 +243,7 @@ class XVector:
         from ._lib import check
         from .ops import _stream
         lib = self.eng.lib
-        ws = self.eng._scratch_bytes("xvector", lib.sdk_xvector_workspace_bytes(C.byref(self.desc), B, T))
+        ws = self.eng._workspace("sdk_xvector_workspace_bytes", C.byref(self.desc), B, T, cache="xvector")
         emb = torch.empty((B, self.cfg.embed_dim), dtype=torch.float32, device=self.eng.device)
         check(lib.sdk_xvector_forward(self.eng.ctx, self.blob.data_ptr(), C.byref(self.desc), feats.data_ptr(), feats.stride(0), B, T,
                                       ws.data_ptr(), ws.numel(), emb.data_ptr(), _stream()), "sdk_xvector_forward")

@@ -340,7 +340,7 @@ def test_refusals(engine):
         call(S_=0)
     with pytest.raises(SdkError, match=r"S=9 weight rows per chunk \(served: 1 .. 8\)"):
         call(S_=9)
-    with pytest.raises(SdkError, match=rf"workspace too small \({need - 256} < {need}"):
+    with pytest.raises(SdkError, match=rf"workspace of {need - 256} bytes, {need} needed \(sdk_ecapa_masked_workspace_bytes\)"):
         call(nbytes=need - 256)
     with pytest.raises(SdkError, match=r"null pointer \(w=\(nil\)"):
         call(wp=None)

@@ -339,8 +339,8 @@ def test_driver_c_entry_refusals(engine):
     assert np.array_equal(bits(host(V)), bits(want[0])) and np.array_equal(bits(host(lam)[:k]), bits(want[1]))
     V33 = torch.zeros((N, 33), dtype=torch.float32, device="cuda")
     cases = [
-        ("workspace too small or misaligned", lambda: call(V.data_ptr(), ws_bytes=need - 1)),
-        ("workspace too small or misaligned", lambda: call(V.data_ptr(), ws_ptr=ws.data_ptr() + 16, ws_bytes=need + 256)),
+        (f"workspace of {need - 1} bytes, {need} needed (sdk_laplacian_topk_workspace_bytes)", lambda: call(V.data_ptr(), ws_bytes=need - 1)),
+        ("must be 256-byte aligned", lambda: call(V.data_ptr(), ws_ptr=ws.data_ptr() + 16, ws_bytes=need + 256)),
         ("bad shape", lambda: call(V33.data_ptr(), kk=33, ws_bytes=need + 512)),
         ("bad shape", lambda: call(V.data_ptr(), kk=0)),
         ("bad shape", lambda: call(V.data_ptr(), it=-1)),

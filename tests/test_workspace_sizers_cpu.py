@@ -173,6 +173,31 @@ LOWER = [
 ]
 
 
+# The sizers above that are only lower-bounded, at the smallest, a middle and the largest argument set this file gives them: the values the
+# library returned on the commit before every layout moved onto csrc/workspace.hpp's carver (read from that build, not derived), which a
+# layout must go on returning byte for byte.
+PINNED = {
+    "sdk_vbx_workspace_bytes": {(1, 64, 1): 3840, (130, 64, 17): 105984, (65536, 128, 65536): 69393195520},
+    "sdk_vbx_hmm_workspace_bytes": {(1, 64, 1): 5376, (130, 64, 17): 161792, (65536, 128, 65536): 173010330112},
+    "sdk_affinity_workspace_bytes": {(1, 1): 1792, (600, 1025): 124160, (1 << 20, 1 << 20): 34435236096},
+    "sdk_fbank_workspace_bytes": {(1, 400): 960, (7, 16000): 226240, (4096, 160000): 1312030720},
+    "sdk_se_workspace_bytes": {(1, 256, 64): 2304, (3, 1024, 128): 26112, (65536, 1024, 128): 570425344},
+}
+PINNED_PRECISE_ECAPA = {(1, 9): 551424, (3, 230): 37976064, (1 << 20, 2047): 117651502268416}      # ecapa_desc(precision=1) below
+
+
+@pytest.mark.parametrize("sizer", sorted(PINNED))
+def test_lower_bounded_sizers_return_the_pinned_values(lib, sizer):
+    for args, want in PINNED[sizer].items():
+        assert int(getattr(lib, sizer)(*args)) == want, (sizer, args)
+
+
+def test_precise_ecapa_sizer_returns_the_pinned_values(lib):
+    hp = ecapa_desc(precision=1)
+    for (B, T), want in PINNED_PRECISE_ECAPA.items():
+        assert int(lib.sdk_ecapa_workspace_bytes(C.byref(hp), B, T)) == want, (B, T)
+
+
 @pytest.mark.parametrize("sizer,args,least,why", LOWER, ids=[row[0] for row in LOWER])
 def test_sizer_covers_its_arrays_at_the_largest_arguments(lib, sizer, args, least, why):
     got = int(getattr(lib, sizer)(*args))
