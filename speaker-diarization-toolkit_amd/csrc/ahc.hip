@@ -417,8 +417,6 @@ __global__ void __launch_bounds__(MERGE_THREADS) ahc_merge_kernel(const AhcProb*
   if constexpr (LINK) finish(n - 1);
 }
 
-}  // namespace
-
 size_t ahc_workspace_bytes(const int32_t* offsets, int G) {
   WsCarver c{};
   c.take<AhcProb>((size_t)G);                          // the table lives at the start of the workspace
@@ -426,7 +424,6 @@ size_t ahc_workspace_bytes(const int32_t* offsets, int G) {
   return c.bytes();
 }
 
-namespace {
 // group == nullptr: sdk_centroid_linkage (stop and merges unused); else sdk_linked_linkage
 int launch_all(const char* fn, sdk_ctx* ctx, const float* E, int ldE, int dim, const int32_t* group, const int32_t* offsets, int G, double stop, double* Z,
                int32_t* merges, int32_t* status, void* ws, void* stream) {
@@ -478,13 +475,61 @@ int launch_all(const char* fn, sdk_ctx* ctx, const float* E, int ldE, int dim, c
   SDK_LAUNCH_CHECK();
   return 0;
 }
+
+constexpr int AHC_MAX_N = 65536;    // the condensed distance count of one problem stays under 2^31
+constexpr int AHC_MAX_DIM = 2048;
+// the host-side refusals shared by both entry points: 0 = the offsets describe G problems the kernels serve
+int check_ahc_offsets(const char* fn, const int32_t* offsets, int G, int dim) {
+  SDK_REQUIRE(offsets, "%s: offsets is null", fn);
+  SDK_REQUIRE(G >= 1, "%s: G=%d (at least one problem)", fn, G);
+  SDK_REQUIRE(dim >= 1 && dim <= AHC_MAX_DIM, "%s: dim=%d (served: 1 .. %d)", fn, dim, AHC_MAX_DIM);
+  SDK_REQUIRE(offsets[0] == 0, "%s: offsets[0]=%d (the first problem starts at row 0)", fn, offsets[0]);
+  for (int g = 0; g < G; ++g) {
+    const int64_t n = (int64_t)offsets[g + 1] - offsets[g];
+    SDK_REQUIRE(n >= 1, "%s: offsets not increasing at problem %d (offsets[%d]=%d, offsets[%d]=%d: every problem needs a row)", fn, g, g, offsets[g],
+                g + 1, offsets[g + 1]);
+    SDK_REQUIRE(n <= AHC_MAX_N, "%s: problem %d has n=%lld rows (at most %d)", fn, g, (long long)n, AHC_MAX_N);
+  }
+  return 0;
+}
 }  // namespace
 
-int ahc_launch(sdk_ctx* ctx, const float* E, int ldE, int dim, const int32_t* offsets, int G, double* Z, int32_t* status, void* ws, void* stream) {
-  return launch_all("sdk_centroid_linkage", ctx, E, ldE, dim, nullptr, offsets, G, 0.0, Z, nullptr, status, ws, stream);
+// ---- the entry points: host-side comparisons only (no floating-point arithmetic for -ffp-contract to bear on), then launch_all
+extern "C" size_t sdk_centroid_linkage_workspace_bytes(const int32_t* offsets, int G, int dim) {
+  if (check_ahc_offsets("sdk_centroid_linkage_workspace_bytes", offsets, G, dim)) return 0;
+  return ahc_workspace_bytes(offsets, G);
 }
 
-int link_launch(sdk_ctx* ctx, const float* E, int ldE, int dim, const int32_t* group, const int32_t* offsets, int G, double stop, double* Z, int32_t* merges,
-                int32_t* status, void* ws, void* stream) {
-  return launch_all("sdk_linked_linkage", ctx, E, ldE, dim, group, offsets, G, stop, Z, merges, status, ws, stream);
+extern "C" int sdk_centroid_linkage(sdk_ctx* ctx, const float* E, int ldE, int dim, const int32_t* offsets, int G, double* Z, int32_t* status,
+                                    void* workspace, size_t ws_bytes, void* stream) {
+  SDK_REQUIRE(ctx && E && Z && status && workspace, "sdk_centroid_linkage: null argument (ctx=%p E=%p Z=%p status=%p workspace=%p)", (void*)ctx,
+              (const void*)E, (void*)Z, (void*)status, workspace);
+  if (int rc = check_ahc_offsets("sdk_centroid_linkage", offsets, G, dim)) return rc;
+  SDK_REQUIRE(ldE >= dim, "sdk_centroid_linkage: ldE=%d < dim=%d", ldE, dim);
+  SDK_REQUIRE((uintptr_t)E % 4 == 0 && (uintptr_t)Z % 8 == 0 && (uintptr_t)status % 4 == 0 && (uintptr_t)workspace % 256 == 0,
+              "sdk_centroid_linkage: misaligned pointer (E=%p needs 4, Z=%p needs 8, status=%p needs 4, workspace=%p needs 256 bytes)",
+              (const void*)E, (void*)Z, (void*)status, workspace);
+  SDK_REQUIRE_WS("sdk_centroid_linkage", "sdk_centroid_linkage_workspace_bytes", workspace, ws_bytes, ahc_workspace_bytes(offsets, G), 1);
+  return launch_all("sdk_centroid_linkage", ctx, E, ldE, dim, nullptr, offsets, G, 0.0, Z, nullptr, status, workspace, stream);
+}
+
+extern "C" size_t sdk_linked_linkage_workspace_bytes(const int32_t* offsets, int G, int dim) {
+  if (check_ahc_offsets("sdk_linked_linkage_workspace_bytes", offsets, G, dim)) return 0;
+  return ahc_workspace_bytes(offsets, G);
+}
+
+extern "C" int sdk_linked_linkage(sdk_ctx* ctx, const float* E, int ldE, int dim, const int32_t* group, const int32_t* offsets, int G, double stop,
+                                  double* Z, int32_t* merges, int32_t* status, void* workspace, size_t ws_bytes, void* stream) {
+  SDK_REQUIRE(ctx && E && group && Z && merges && status && workspace,
+              "sdk_linked_linkage: null argument (ctx=%p E=%p group=%p Z=%p merges=%p status=%p workspace=%p)", (void*)ctx, (const void*)E,
+              (const void*)group, (void*)Z, (void*)merges, (void*)status, workspace);
+  if (int rc = check_ahc_offsets("sdk_linked_linkage", offsets, G, dim)) return rc;
+  SDK_REQUIRE(ldE >= dim, "sdk_linked_linkage: ldE=%d < dim=%d", ldE, dim);
+  SDK_REQUIRE(stop >= 0.0, "sdk_linked_linkage: stop=%g (a distance >= 0, or +inf for every allowed merge)", stop);     // false for a NaN too
+  SDK_REQUIRE((uintptr_t)E % 4 == 0 && (uintptr_t)group % 4 == 0 && (uintptr_t)Z % 8 == 0 && (uintptr_t)merges % 4 == 0 && (uintptr_t)status % 4 == 0 &&
+                  (uintptr_t)workspace % 256 == 0,
+              "sdk_linked_linkage: misaligned pointer (E=%p needs 4, group=%p needs 4, Z=%p needs 8, merges=%p needs 4, status=%p needs 4, workspace=%p "
+              "needs 256 bytes)", (const void*)E, (const void*)group, (void*)Z, (void*)merges, (void*)status, workspace);
+  SDK_REQUIRE_WS("sdk_linked_linkage", "sdk_linked_linkage_workspace_bytes", workspace, ws_bytes, ahc_workspace_bytes(offsets, G), 1);
+  return launch_all("sdk_linked_linkage", ctx, E, ldE, dim, group, offsets, G, stop, Z, merges, status, workspace, stream);
 }

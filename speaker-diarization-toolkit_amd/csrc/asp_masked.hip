@@ -1,4 +1,4 @@
-// Masked attentive statistics pooling: the two HBM sweeps of sdk_ecapa_forward_masked (sdk_api.hip), S weighted poolings per chunk on ONE
+// Masked attentive statistics pooling: the two HBM sweeps of sdk_ecapa_forward_masked (forward_ecapa.hip), S weighted poolings per chunk on ONE
 // trunk output h [B*T, C].  THE RULE (include/sdk_hip.h states it in full): for chunk b and slot s < S, w = w[b][s][0..T) >= 0 (any
 // non-negative weights, not only 0 / 1), v1 = sum_t w_t:
 //   context    mu_c = sum_t w_t h_tc / v1,  sd_c = sqrt(max(sum_t w_t (h_tc - mu_c)^2 / v1, 1e-12))          (asp_stats_masked)

@@ -87,13 +87,6 @@ int resnet_masked_tstp_impl(sdk_ctx* ctx, const uint16_t* x, int B, int F, int T
                             void* stream, bool f16);
 int resnet_zero_invalid_impl(sdk_ctx* ctx, float* emb, int n, int dim, const int32_t* valid, void* stream);
 
-// ahc.hip: centroid-linkage agglomerative clustering (sdk_centroid_linkage checks the arguments, then calls these)
-size_t ahc_workspace_bytes(const int32_t* offsets, int G);
-int ahc_launch(sdk_ctx* ctx, const float* E, int ldE, int dim, const int32_t* offsets, int G, double* Z, int32_t* status, void* ws, void* stream);
-// the linked (constrained, early-stopping) linkage on the same kernels and workspace (sdk_linked_linkage); group is a device pointer
-int link_launch(sdk_ctx* ctx, const float* E, int ldE, int dim, const int32_t* group, const int32_t* offsets, int G, double stop, double* Z, int32_t* merges,
-                int32_t* status, void* ws, void* stream);
-
 struct ProfScope {   // brackets one kernel launch with two events when profiling is enabled
   sdk_ctx* c; hipStream_t s; size_t slot; bool on;
   ProfScope(sdk_ctx* ctx, void* stream, int family, double flops, double bytes) : c(ctx), s((hipStream_t)stream), slot(0), on(ctx && ctx->prof_on) {

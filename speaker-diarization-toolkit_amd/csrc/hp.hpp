@@ -51,7 +51,7 @@ __device__ __forceinline__ float load1(const uint16_t* p, int64_t lo_off) {
 
 }  // namespace sdk_hp
 
-// hp.hip launch helpers used by the forward schedule (sdk_api.hip)
+// hp.hip launch helpers used by the forward schedules (forward_ecapa.hip, forward_xvector.hip)
 int hp_seg_mean(sdk_ctx* ctx, const uint16_t* z, int64_t ldz, int64_t z_lo, int B, int T, int C, float* out, void* stream);
 int hp_se_apply(sdk_ctx* ctx, const uint16_t* z, int64_t ldz, int64_t z_lo, const uint16_t* x, int64_t ldx, int64_t x_lo, const float* gate,
                 uint16_t* out, int64_t ldo, int64_t o_lo, int B, int T, int C, void* stream);
