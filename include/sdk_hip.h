@@ -60,6 +60,8 @@
  *                                                                                                       frames, and the scores of the clips cut from them (samples.py)
  *     sdk_smooth_turns_workspace_bytes  sdk_smooth_turns                                                smoothing of the diarized turns: short pauses filled, short
  *                                                                                                       runs dropped, on the diarization frames (smooth.py)
+ *     sdk_fuse_masks  sdk_fuse_cooccur  sdk_fuse_labels  sdk_fuse_vote                                  fusing several diarizations of a recording: DOVER-Lap label
+ *                                                                                                       mapping and weighted voting (fuse.py)
  *     sdk_plda_transform  sdk_vbx_workspace_bytes  sdk_vbx  sdk_vbx_centroids                           VBx clustering (plda.py, cluster.vbx_cluster)
  *     sdk_vbx_hmm_workspace_bytes  sdk_vbx_hmm                                                          VBx with its HMM, rows in time order (loop_prob > 0)
  *     sdk_plda_fit_stats_workspace_bytes  sdk_plda_fit_stats  sdk_plda_project                          training the VBx PLDA from labelled rows (plda.fit)
@@ -94,7 +96,7 @@
 extern "C" {
 #endif
 
-#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5); still 4 with sdk_cohort_stats* and sdk_affinity_topk_snorm, and with sdk_ecapa_forward_masked, sdk_ecapa_masked_workspace_bytes, sdk_asp_stats_masked_fmt and sdk_asp_pool_masked_fmt, and with sdk_score_reference, sdk_score_cooccur and sdk_score_map, and with sdk_plda_enroll* and sdk_plda_score*, and with sdk_trial_hist, sdk_trial_calib* and sdk_trial_hist_snorm, and with sdk_words_attribute and sdk_words_cooccur, and with sdk_samples_runs* and sdk_samples_score*, and with sdk_score_uem, sdk_score_durations and sdk_score_jaccard, and with sdk_smooth_turns*: new exports only, no struct or existing signature changes, no caller of version 4 breaks */
+#define SDK_ABI_VERSION 4   /* 2: sdk_ecapa_desc.precision (round 3); 3: sdk_fbank_windows + sdk_ingest_* (round 4); 4: precision 2, sdk_fbank_fmt, SDK_GEMM_F16, lazy ingest slots (round 5); still 4 with sdk_cohort_stats* and sdk_affinity_topk_snorm, and with sdk_ecapa_forward_masked, sdk_ecapa_masked_workspace_bytes, sdk_asp_stats_masked_fmt and sdk_asp_pool_masked_fmt, and with sdk_score_reference, sdk_score_cooccur and sdk_score_map, and with sdk_plda_enroll* and sdk_plda_score*, and with sdk_trial_hist, sdk_trial_calib* and sdk_trial_hist_snorm, and with sdk_words_attribute and sdk_words_cooccur, and with sdk_samples_runs* and sdk_samples_score*, and with sdk_score_uem, sdk_score_durations and sdk_score_jaccard, and with sdk_smooth_turns*, and with sdk_fuse_masks, sdk_fuse_cooccur, sdk_fuse_labels and sdk_fuse_vote: new exports only, no struct or existing signature changes, no caller of version 4 breaks */
 
 typedef struct sdk_ctx sdk_ctx;
 
@@ -767,6 +769,46 @@ int sdk_samples_score(sdk_ctx* ctx, const float* E, int W, int d, const int32_t*
 size_t sdk_smooth_turns_workspace_bytes(int64_t G);
 int sdk_smooth_turns(sdk_ctx* ctx, int32_t* speakers, const int32_t* frame_off, const int32_t* cent_off, int R, int64_t G, int fill_frames,
                      int keep_frames, int cap, int32_t* tallies, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- fusing several diarizations of a recording (fuse.py; csrc/fuse.hip): DOVER-Lap label mapping and weighted voting on the packed frame
+ *      grid above.  R recordings, each with the same H hypotheses (2 .. 8); hypothesis h of recording r is group h R + r, spk_off [H R + 1]
+ *      int32 holds the prefix sums of the groups' speaker counts K (at most 64 each; max_spk: the largest, stated by the caller) and the masks
+ *      are [H][G] uint64, bit k of mask[h][g] set iff speaker k of the group is active in the frame; bits at or above K name nobody.  Pairs
+ *      (a, b), a < b, are numbered p = a (2 H - a - 1) / 2 + (b - a - 1), P = H (H - 1) / 2 of them; pair group q = p R + r, and co_off
+ *      [P R + 1] int64 holds the prefix sums of K_a K_b.  Integers only (stores of one value, integer atomic adds): bit-identical run to
+ *      run.  No call takes a workspace; each clears what it accumulates into; everything is enqueued on `stream`, nothing waits and
+ *      nothing is read on the host.  Refused, with sdk_last_error: H outside 2 .. 8, max_spk above 64, G outside 0 .. 2^30 - 1, cap
+ *      outside {1, 2}.
+ *   sdk_fuse_masks : one hypothesis.  speakers [G][2] int32 (8-byte aligned), spk_off [R + 1] int32 (the hypothesis' slice of the table
+ *        above: only differences are read) -> mask [G]: bit k set iff an entry of speakers[g] is k with 0 <= k < K_r (a name twice counts
+ *        once).  One thread per frame.
+ *   sdk_fuse_cooccur : all P pairs in one launch.  co (int32; pair group q's [K_a][K_b] table at co_off[q], co_total cells in all) = the
+ *        frames in which bit i of mask[a] and bit j of mask[b] are both set; tally [P R][2] int64 = (sum max(n_a, n_b), sum min(n_a, n_b))
+ *        with n the valid bits of a frame.  Both are cleared first.  sdk_score_map then runs on co as it stands, with P R "recordings" and
+ *        the prefix sums of K_a and K_b as ref_off and cent_off: correct [P R].
+ *   sdk_fuse_labels : one wave per recording.  dis [R][H][H] int64: dis[a][b] = dis[b][a] = tally[q][0] - correct[q], 0 on the diagonal;
+ *        order [R][H] int32: the hypotheses by ascending D_h = sum_b dis[h][b], ties to the lower h; weight [R][H] int32: weights[h]
+ *        (weights [H] int32, 1 .. 65536) when weights is not null, else rank_weight[rank of h] (rank_weight [8] int32).  label_of
+ *        [spk_off[H R]] int32, the fused label of every speaker of every group: the anchor order[0] keeps its numbers and L = K_anchor; then
+ *        for h = order[1], order[2], ..: A[u][j] = the sum of co(h', h)[i][j] over the earlier h' and their speakers i with label u; greedily
+ *        the largest A[u][j] > 0 over unused u and unmapped j (ties to the lowest u, then the lowest j) gives label_of[h][j] = u until none
+ *        is positive; the unmapped j in ascending order get L, L + 1, .. while L < 64, then -1, each -1 counted in overflow [R] int32.
+ *        n_labels [R] int32 = L at the end.
+ *   sdk_fuse_vote : one thread per frame.  With c_h the valid bits of mask[h][g], seen_h the labels >= 0 of those bits, v[u] = the sum of
+ *        weight[r][h] over the h with u in seen_h and W the sum of the weights: n = min(cap, (2 sum_h w_h c_h + W) / (2 W)); speakers
+ *        [G][2] int32 (8-byte aligned) names the labels with v > 0 first in the order (v descending, u ascending), at most n, from slot
+ *        0; empty slots hold -1.  tallies [R][4] int64 = (frames that name somebody, frames that name two, frames whose H sets seen_h are
+ *        all equal, overflow[r]). */
+int sdk_fuse_masks(sdk_ctx* ctx, const int32_t* speakers, const int32_t* frame_off, const int32_t* spk_off, int R, int64_t G, int max_spk,
+                   uint64_t* mask, void* stream);
+int sdk_fuse_cooccur(sdk_ctx* ctx, const uint64_t* mask, const int32_t* frame_off, const int32_t* spk_off, const int64_t* co_off, int H, int R,
+                     int64_t G, int max_spk, int64_t co_total, int32_t* co, int64_t* tally, void* stream);
+int sdk_fuse_labels(sdk_ctx* ctx, const int32_t* co, const int64_t* tally, const int64_t* correct, const int32_t* spk_off, const int64_t* co_off,
+                    const int32_t* rank_weight, const int32_t* weights, int H, int R, int max_spk, int64_t* dis, int32_t* order, int32_t* weight,
+                    int32_t* label_of, int32_t* n_labels, int32_t* overflow, void* stream);
+int sdk_fuse_vote(sdk_ctx* ctx, const uint64_t* mask, const int32_t* frame_off, const int32_t* spk_off, const int32_t* label_of,
+                  const int32_t* weight, const int32_t* overflow, int H, int R, int64_t G, int max_spk, int cap, int32_t* speakers,
+                  int64_t* tallies, void* stream);
 
 /* ---- VBx clustering of the diarization (cluster.vbx_cluster, plda.py; csrc/vbx.hip): float64 arithmetic, every sum over rows over fixed 64-row
  *      blocks whose partials are combined in block order, no floating-point atomics, one owner per output element: bit-identical run to

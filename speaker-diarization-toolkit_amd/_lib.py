@@ -180,6 +180,10 @@ SIGNATURES = {
     "sdk_samples_score": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sdk_smooth_turns_workspace_bytes": (_sz, [_i64]),
     "sdk_smooth_turns": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "sdk_fuse_masks": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _vp, _vp]),
+    "sdk_fuse_cooccur": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i64, _vp, _vp, _vp]),
+    "sdk_fuse_labels": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sdk_fuse_vote": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _vp]),
     "sdk_plda_transform": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "sdk_vbx_workspace_bytes": (_sz, [_i, _i, _i]),
     "sdk_vbx": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f64, _f64, _i, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -1067,6 +1067,55 @@ def smooth_diarization(be: Backend, results, min_duration_off: float = 0.0, min_
     return out[0] if single else out
 
 
+# ---- fusing several diarizations of a recording (fuse.py).  Functions of the backend for the same reason: the class keeps its public names.
+def _per_recording(x) -> bool:
+    """True where x is a list over recordings, False where it is one hypothesis (a result, or a non-empty turn list)."""
+    from .fuse import is_hypothesis
+    return not (is_hypothesis(x) and not (isinstance(x, (list, tuple)) and len(x) == 0))
+
+
+def fuse_diarizations(be: Backend, hypotheses, n_samples=None, weights=None, max_speakers=None):
+    """Several diarizations of the same recordings combined into one each, DOVER-Lap's way: hypotheses[r] = the H (2 .. 8) answers for
+    recording r, each a diarize.DiarizationResult (of diarize / diarize_many under different models, clusterings or thresholds) or a turn
+    list [(start_s, end_s, name)] (an outside diarizer's; then n_samples, the recordings' lengths, fixes the frame grid where no result
+    does).  The speakers of the hypotheses are mapped onto common labels through their pairwise co-occurrence, starting from the hypothesis
+    that agrees most with the others; the hypotheses are weighted by their rank in mean disagreement (or by weights=, H integers in
+    1 .. 65536) and every frame is voted, the number of speakers from the weighted mean count (at most 2, fewer with max_speakers).  -> one
+    result per recording: the anchor's result copied (else a fuse.FusedDiarization) with speakers, turns and n_speakers replaced and
+    `fusion` = {order, weights, dis, label_of, speech, overlap, unanimous, overflow}.  One upload, the device calls and one download for
+    the whole list (fuse.py states the rule; parity with DOVER-Lap is unpinned)."""
+    from .fuse import fuse_results
+    return fuse_results(be.engine(), list(hypotheses), n_samples, weights, max_speakers)
+
+
+def compare_diarizations(be: Backend, a, b, n_samples=None):
+    """Two diarizations of the same recording laid side by side: a and b are one hypothesis each (as fuse_diarizations takes them), or
+    lists of them, one per recording -> per recording a dict of co [K_a, K_b] (the frames speaker i of a shares with speaker j of b), mapping
+    (b's speaker for each of a's under an optimal assignment), names_a, names_b, sum_max, sum_min, correct, disagreement = (sum_max -
+    correct) / sum_max - the symmetric diarization error of one against the other, 0.0 for two silent answers - and unanimous, the frames
+    on which they agree.  A single pair gives a single dict."""
+    from .fuse import compare
+    single = not _per_recording(a)
+    if single:
+        a, b = [a], [b]
+        n_samples = None if n_samples is None else [n_samples]
+    out = compare(be.engine(), a, b, n_samples)
+    return out[0] if single else out
+
+
+def diarize_fused(be: Backend, samples_or_path, variants, **fuse_kw):
+    """diarize once per keyword set of `variants` (for example [{"clustering": "ahc"}, {"clustering": "vbx", "threshold": 0.6},
+    {"clustering": "nmesc"}]) and the results fused (fuse_diarizations; fuse_kw: weights, max_speakers) -> the fused result.  Every
+    variant runs the whole pipeline: the embedding pass is not shared between them."""
+    variants = [dict(v) for v in variants]
+    from .fuse import MAX_FUSE_HYPS
+    if not 2 <= len(variants) <= MAX_FUSE_HYPS:
+        raise ValueError(f"diarize_fused: {len(variants)} variants (2 .. {MAX_FUSE_HYPS})")
+    if isinstance(samples_or_path, (str, Path)):
+        samples_or_path = decode_to_profile(Path(samples_or_path), be.engine(), be.get_audio_profile())
+    return fuse_diarizations(be, [[be.diarize(samples_or_path, **v) for v in variants]], **fuse_kw)[0]
+
+
 # ---- speaker samples (samples.py).  Functions of the backend for the same reason.
 def speaker_samples(be: Backend, results, samples_or_paths, min_s: float = 0.5, max_gap_s: float = 1.0, max_clip_s=None, max_candidates=None,
                     max_clips=None, max_total_s=None, min_margin: float = 0.0):
