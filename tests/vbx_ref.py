@@ -109,7 +109,8 @@ def vbx(X, Phi, init_labels, S, Fa=0.07, Fb=0.8, max_iters=20, epsilon=1e-4, ini
 
 def result(gamma, pi, E, dtype=np.float64, reverse=False):
     """-> dict(keep [K], labels [n] over the kept speakers (ties to the lower), cent [K, d] unit): the speakers with pi > 1e-7 and their
-    centroids sum_t gamma[t, k] e_t / sum_t gamma[t, k] over the original rows, re-normalised."""
+    centroids sum_t gamma[t, k] e_t / sum_t gamma[t, k] over the original rows, re-normalised.  A kept speaker without any weight has the zero
+    centroid; with no speaker kept every label is -1."""
     gamma, E = np.asarray(gamma).astype(dtype), np.asarray(E).astype(dtype)
     n, d = E.shape
     keep = [s for s in range(len(pi)) if pi[s] > dtype(MIN_PI)]
@@ -120,7 +121,8 @@ def result(gamma, pi, E, dtype=np.float64, reverse=False):
         for t in _row_order(n, reverse):
             acc = acc + gamma[t, s] * E[t]
             w = w + gamma[t, s]
-        acc = acc / w
+        if w > 0:
+            acc = acc / w
         q = dtype(0)
         for j in range(d):
             q = q + acc[j] * acc[j]
@@ -131,7 +133,7 @@ def result(gamma, pi, E, dtype=np.float64, reverse=False):
         for k in range(1, len(keep)):
             if gamma[t, keep[k]] > gamma[t, keep[best]]:
                 best = k
-        labels[t] = best
+        labels[t] = best if keep else -1
     return dict(keep=np.array(keep, np.int32), labels=labels, cent=cent)
 
 
