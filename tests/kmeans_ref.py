@@ -10,6 +10,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ahc_ref as AHC  # noqa: E402
+import partial_width as PW  # noqa: E402
 
 SEGMENT = 1024                    # rows per segment of the centre sums (cluster.KMEANS_SEGMENT)
 
@@ -83,6 +84,14 @@ def kmeans(E32: np.ndarray, k: int, max_iters: int = 20, rows=None) -> dict:
     cent /= np.linalg.norm(cent, axis=1, keepdims=True)
     return dict(labels=can, raw=labels, n_clusters=K, n_iter=n_iter, counts=np.bincount(can, minlength=K), cent64=cent, margins=margins,
                 least=float(min(m.min() for m in margins)))
+
+
+def second_column_weight(name: str, E32: np.ndarray, k: int, cent_bound: float, ref: dict = None, **kw) -> float:
+    """partial_width.weight for kmeans on rows wider than 256: the labels and counts without the columns 256.. against those of `ref` (the run on
+    the full rows), the unit centres against cent_bound."""
+    ref = kmeans(E32, k, **kw) if ref is None else ref
+    cut = kmeans(PW.first_columns(E32), k, **kw)
+    return PW.weight(name, ints=[(ref["labels"], cut["labels"]), (ref["counts"], cut["counts"])], floats=[(ref["cent64"], cut["cent64"])], bound=cent_bound)
 
 
 # ------------------------------------------------------------------------------------------------ bounds and the level search

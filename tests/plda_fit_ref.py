@@ -59,6 +59,13 @@ def stats(X, labels, K, dtype=np.float64, reverse=False, scatter=True):
     return dict(counts=counts, sums=sums, total=total, scatter=S)
 
 
+def second_column_weight(name, ref, cut, tolerance) -> float:
+    """partial_width.weight of a case wider than 256 columns, quantity by quantity: ref and cut are {quantity: array} of this module's functions on
+    the full input and on its first 256 columns alone (partial_width.first_columns), tolerance {quantity: the case's bound}.  -> the least ratio."""
+    import partial_width as PW
+    return min(PW.weight(f"{name} {q}", floats=[(np.asarray(ref[q], np.float64), np.asarray(cut[q], np.float64))], bound=tolerance[q]) for q in tolerance)
+
+
 # ------------------------------------------------------------------------------------------------ planted two-covariance model
 class Planted:
     """Speaker means y ~ N(0, diag(between)), rows y + N(0, diag(within)), rotated by a seeded orthogonal matrix, shifted, and put on the unit

@@ -123,6 +123,17 @@ def score_case(seed: int, d: int, layout, max_windows: int = 12):
 # a speaker with one clip (alone), a clip without windows, a recording with one speaker, interleaved clips, a speaker without any clip
 SCORE_LAYOUT = [[[None], [None, None, 0, None], [None, None, None]], [[None, None, None]], [[None, None], [], [None, None, None, None], [None, None], [5, 7]]]
 SCORE_CASES = {64: (41, 64, SCORE_LAYOUT, 190), 192: (42, 192, SCORE_LAYOUT, 12), 256: (43, 256, SCORE_LAYOUT, 12), 512: (44, 512, SCORE_LAYOUT, 8)}
+# the widths at which a second column is live for a part of the workgroup only (ss_clip_sum's blockDim = 256 with columns tid + 256 q, ss_score's
+# lane + 64 q with 5 and 7 of 8 registers live), at the fewest windows the layout allows: one per drawn clip, beside its clips of 5, 7 and 0
+SCORE_CASES.update({320: (45, 320, SCORE_LAYOUT, 1), 448: (46, 448, SCORE_LAYOUT, 1)})
+
+
+def second_column_weight(name: str, E, clip_off, clip_spk, spk_off, ref: dict, bound: float = 1e-12) -> float:
+    """partial_width.weight of a score case wider than 256 columns: score_ref without the columns 256.. of the rows against `ref`."""
+    import partial_width as PW
+    cut = score_ref(PW.first_columns(E), clip_off, clip_spk, spk_off)
+    return PW.weight(name, ints=[(ref[q], cut[q]) for q in ("rival_speaker", "windows", "alone")], floats=[(ref[q], cut[q]) for q in ("mean", "own", "rival")],
+                     bound=bound)
 
 
 # ------------------------------------------------------------------------------------------------ the packs both test files run

@@ -27,6 +27,20 @@ def cohort_stats(E, cohort, K):
     return mean, std
 
 
+def second_column_weight_stats(name, E, cohort, K, ref, bound):
+    """partial_width.weight of a statistics case wider than 256 columns: cohort_stats without the columns 256.. of the rows against ref = (mean, std)."""
+    import partial_width as PW
+    cut = cohort_stats(PW.first_columns(E), cohort, K)
+    return PW.weight(name, floats=list(zip(ref, cut)), bound=bound)
+
+
+def second_column_weight_topk(name, E, mean_e, std_e, P, mean_p, std_p, k, ref, bound):
+    """The same for topk: ref = topk's tuple on the full rows; the indices as integers, z against `bound` (the largest element bound in use)."""
+    import partial_width as PW
+    cut = topk(PW.first_columns(E), mean_e, std_e, P, mean_p, std_p, k)
+    return PW.weight(name, ints=[(ref[0], cut[0])], floats=[(ref[1], cut[1]), (ref[2], cut[2])], bound=bound)
+
+
 def zscores(E, mean_e, std_e, P, mean_p, std_p):
     S = cosines(E, P)
     Z = np.empty_like(S)

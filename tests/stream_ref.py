@@ -151,6 +151,16 @@ def run_stream(E, info, cls, starts, n_samples, capacity, hop, latency, delta_ne
             "speakers": np.concatenate(speakers), "K": ref.K, "ref": ref, "lows": lows, "ns": [len(v) for v in count]}
 
 
+def second_column_weight(name: str, s: dict, n_samples: int, ref: dict, capacity, hop, latency, delta_new=1.0, score_bound: float = 1e-6) -> float:
+    """partial_width.weight for a stream wider than 256 columns: the run without the columns 256.. of its rows against `ref` (the run on the full
+    rows) - labels, frames and the speaker count as integers, the scores and the speakers' sums against score_bound."""
+    import partial_width as PW
+    cut = run_stream(PW.first_columns(s["E"]), s["info"], s["cls"], s["starts"], n_samples, capacity, hop, latency, delta_new)
+    sums = [(np.stack(r["ref"].sums) if r["K"] else np.zeros((0, s["E"].shape[2]))) for r in (ref, cut)]
+    return PW.weight(name, ints=[(ref[q], cut[q]) for q in ("labels", "count", "speakers", "K")], floats=[(ref["score"], cut["score"]), tuple(sums)],
+                     bound=score_bound)
+
+
 def make_stream(seed: int, d: int, n: int, hop: int, n_speakers: int = 5, noise: float = 0.35):
     """A generated stream of n samples: per chunk of schedule(n, hop) a random class table (runs of silence, single speakers and overlap),
     its info (diarize.masks_host) and three unit rows drawn around n_speakers seeded unit centres (oracle.spectral.vmf_mixture); the local

@@ -77,14 +77,50 @@ def test_one_step_equals_the_restatement(engine, N):
             assert int(got.labels.max()) + 1 == got.n_clusters <= k and got.counts.sum() == N and got.counts.min() >= 1
 
 
+# widths at which the second column of a thread (j1 = tid + 256 of km_seed_pick, km_sums, km_finish) is live for one wave only (320) and for
+# all waves but the last (448), at the one N that crosses the 256-row seed block and the 32-row assignment block; k = 64 fills the centre table
+PARTIAL_ONE_STEP = [(257, d, k) for d in KR.PW.WIDTHS for k in (3, 64)]
+PARTIAL_LOOP = (300, 320, 3, 13, 5.0)
+
+
+def one_step_rows(N: int, d: int) -> np.ndarray:
+    return unit(np.random.default_rng(1000 * N + d).standard_normal((N, d)))
+
+
+@pytest.mark.parametrize("N,d,k", PARTIAL_ONE_STEP)
+def test_one_step_where_the_second_column_is_partly_live(engine, N, d, k):
+    """The one-step check at d = 320 and 448, with NO row left out.  Checked on the CPU (tests/test_speaker_bounds_cpu.py prints them): the
+    restatement's least margins are 9.5e-5 (d = 320, k = 3), 3.6e-4 (320, 64), 1.2e-4 (448, 3) and 2.0e-4 (448, 64), seven orders over
+    10 x the bound; without the columns 256.. the restatement gives other labels in all four cases."""
+    E = one_step_rows(N, d)
+    ref = KR.kmeans(E, k, max_iters=1)
+    bound = kmeans_bound(d)
+    print(f"one step N={N} d={d} k={k}: bound {bound:.3e}; restatement's least margin {ref['least']:.3e} (must exceed {10 * bound:.3e}, no row left out)")
+    assert ref["least"] > 10 * bound and ref["n_iter"] == 1
+    KR.second_column_weight(f"one step N={N} d={d} k={k}", E, k, (d + 4) * 2.0 ** -53, ref, max_iters=1)
+    got = cluster.kmeans_cluster(engine, dev(E), k, max_iters=1)
+    raw = engine.kmeans_rows(dev(E), dev(np.arange(N, dtype=np.int32)), k, 1)[0].cpu().numpy()
+    e64 = float(np.abs(got.cent64.cpu().numpy() - ref["cent64"]).max()) if got.n_clusters == ref["n_clusters"] else np.inf
+    print(f"  labels differing {int((got.labels != ref['labels']).sum())} of {N}; clusters {got.n_clusters} (restatement {ref['n_clusters']}); cent64 max|d| {e64:.3e} "
+          f"(bound {(d + 4) * 2.0 ** -53:.3e}, ratio {e64 / ((d + 4) * 2.0 ** -53):.3f})")
+    assert got.n_iter == 1 and np.array_equal(raw, ref["raw"])
+    assert np.array_equal(got.labels, ref["labels"]) and got.n_clusters == ref["n_clusters"] and np.array_equal(got.counts, ref["counts"])
+    assert int(got.labels.max()) + 1 == got.n_clusters <= k and got.counts.sum() == N and got.counts.min() >= 1
+    assert e64 <= (d + 4) * 2.0 ** -53 and np.array_equal(got.cent.cpu().numpy(), got.cent64.cpu().numpy().astype(np.float32))
+
+
 # ------------------------------------------------------------------------------------------------ the whole loop
-@pytest.mark.parametrize("N,d,k,seed,noise", [(300, 192, 3, 11, 3.0), (1000, 256, 8, 12, 3.0)])
+@pytest.mark.parametrize("N,d,k,seed,noise", [(300, 192, 3, 11, 3.0), (1000, 256, 8, 12, 3.0), PARTIAL_LOOP])
 def test_whole_loop_equals_the_restatement(engine, N, d, k, seed, noise):
     """Planted clusters: k seeded directions plus noise.  Checked on the CPU: with these seeds the restatement's least margin over ALL
-    iterations is 2.6e-5 and 1.2e-5, seven orders over 10 x the bound, and the loop stops by itself after 6 and 5 of the 20 assignments."""
+    iterations is 2.6e-5 and 1.2e-5, seven orders over 10 x the bound, and the loop stops by itself after 6 and 5 of the 20 assignments.
+    At d = 320 (the second column live for wave 0 only; tests/test_speaker_bounds_cpu.py prints its figures): least margin 1.2e-4 over
+    8 assignments, and without the columns 256.. the restatement gives other labels."""
     E = planted(seed, N, d, k, noise)
     ref = KR.kmeans(E, k)
     bound = kmeans_bound(d)
+    if d > KR.PW.FIRST:
+        KR.second_column_weight(f"whole loop N={N} d={d} k={k}", E, k, (d + 4) * 2.0 ** -53, ref)
     got = cluster.kmeans_cluster(engine, dev(E), k)
     c64 = got.cent64.cpu().numpy()
     e64 = float(np.abs(c64 - ref["cent64"]).max())

@@ -185,6 +185,12 @@ def test_graph_restatements_against_brute_force(n):
 
 
 # ---------------------------------------------------------------------------------------------- options
+def test_the_gpu_width_case_at_320_weighs_the_columns_past_256():
+    """What tests/test_nmesc_kernels_gpu.py::test_widths asserts on the restatement alone at d = 320 before it asks the device."""
+    import test_nmesc_kernels_gpu as NK                                        # its rows; importing it needs no GPU
+    assert NK.second_column_weight(NK.random_rows(NK.WIDTH_ROWS, 320, 320)) > 100
+
+
 def test_option_checks():
     d = diarize.Diarizer(None, None, None)
     x = np.zeros(16000, np.int16)

@@ -7,10 +7,15 @@ in the same order."""
 from __future__ import annotations
 
 import importlib
+import os
+import sys
 
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import partial_width as PW  # noqa: E402
 
 PKG = "speaker-diarization-toolkit_amd"
 cluster = importlib.import_module(f"{PKG}.cluster")
@@ -87,9 +92,26 @@ def test_every_size_edge(engine, n):
     assert_graph_equal(engine, random_rows(n, 64, n), sorted({1, P}), (1, 32))
 
 
-@pytest.mark.parametrize("d", [64, 192, 512])                       # one, three and eight column tiles (KNN_TJ)
+WIDTH_ROWS = 97
+
+
+def second_column_weight(E) -> float:
+    """partial_width.weight of rows wider than 256 columns: the restatement's neighbour lists without the columns 256.. (the cosines against
+    their spacing, one ulp of 1.0: the comparison is exact, so any bound is this small)."""
+    (idx, cos), (idx_c, cos_c) = cluster.knn_rows_host(E), cluster.knn_rows_host(PW.first_columns(E))
+    rows = int((idx != idx_c).any(axis=1).sum())
+    print(f"knn rows n={len(E)} d={E.shape[1]}: without the columns {PW.FIRST}.. {rows} of {len(E)} neighbour lists differ")
+    return PW.weight(f"knn rows n={len(E)} d={E.shape[1]}", ints=[(idx, idx_c)], floats=[(cos, cos_c)], bound=2.0 ** -52)
+
+
+@pytest.mark.parametrize("d", [64, 192, 320, 512])                  # one, three, five and eight column tiles (KNN_TJ)
 def test_widths(engine, d):
-    assert_graph_equal(engine, random_rows(97, d, d), (1, 64), (1, 32))
+    """d = 320: five column tiles, the first odd count above one wave of tiles, and a width between 256 and 512.  Checked on the CPU
+    (tests/test_nmesc_cpu.py prints it): without the columns 256.. all 97 neighbour lists of the restatement differ."""
+    E = random_rows(WIDTH_ROWS, d, d)
+    if d in PW.WIDTHS:
+        second_column_weight(E)
+    assert_graph_equal(engine, E, (1, 64), (1, 32))
 
 
 @pytest.mark.parametrize("n,d", [(3, 64), (65, 64), (66, 64), (131, 192), (300, 64)])

@@ -202,3 +202,18 @@ def test_speaker_key_merges_a_speaker_across_recordings():
     assert lab.tolist() == [0, 1, 0, 2, 0] and keys == ["ann", "bob", "cy"]
     lab, keys = be.plda_classes(rec, spk, names, None, None)
     assert keys == [(0, "ann"), (0, "bob"), (1, "ann"), (1, "cy")]
+
+
+# ------------------------------------------------------------------------------------------------ the GPU cases at partly live second columns
+def test_the_gpu_cases_at_320_and_448_weigh_the_second_column():
+    """What tests/test_plda_fit_gpu.py asserts on the reference alone before it asks the device, at the widths where a thread's second column is
+    live for a part of the workgroup only: without the columns 256.. of the rows every compared quantity moves by more than 100 x its tolerance."""
+    import partial_width as PW
+    import test_plda_fit_gpu as FG                                             # its cases and references; importing it needs no GPU
+    stats = [c for c in FG.STATS_CASES if c[1] in PW.WIDTHS]
+    proj = [c for c in FG.PROJECTION_CASES if c[1] in PW.WIDTHS]
+    assert {c[1] for c in stats} == {c[1] for c in proj} == set(PW.WIDTHS) and any(PW.FIRST < c[2] < c[1] for c in proj)
+    for case in stats:
+        assert FG.stats_weight(case) > PW.FAR
+    for case in proj:
+        assert FG.projection_weight(case, *FG.projection_reference(case)) > PW.FAR

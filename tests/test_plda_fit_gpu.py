@@ -17,6 +17,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import partial_width as PW  # noqa: E402
 import plda_fit_ref as FR  # noqa: E402
 
 PKG = "speaker-diarization-toolkit_amd"
@@ -26,8 +27,11 @@ pytestmark = pytest.mark.gpu
 MARGIN, ULPS = 8.0, 4.0
 QUANT = ("sums", "total", "scatter")
 
-# (N, d, K): one row block and several (RB = 512), d below, at and above the 64-wide macro tile, classes of one row, unused ids
-STATS_CASES = [(2, 64, 1), (63, 64, 7), (65, 192, 65), (300, 100, 12), (2049, 256, 40), (2049, 512, 2)]
+# (N, d, K): one row block and several (RB = 512), d below, at and above the 64-wide macro tile, classes of one row, unused ids; the last two: the
+# widths at which a thread's second column (tid + 256) is live for wave 0 only (320) and for every wave but the last (448).  Checked on the CPU
+# (tests/test_plda_fit_cpu.py prints it): without the columns 256.. of the rows the reference's sums, total and scatter move by more than
+# 1e13 x their tolerances
+STATS_CASES = [(2, 64, 1), (63, 64, 7), (65, 192, 65), (300, 100, 12), (2049, 256, 40), (2049, 512, 2), (65, 320, 9), (300, 448, 12)]
 _cache = {}
 
 
@@ -68,10 +72,22 @@ def yardstick(runs, q):
     return max(float(np.abs(a - np.asarray(runs[o][q]).astype(np.longdouble)).max()) for o in ("ld", "rev"))
 
 
+def tolerance(runs, q):
+    return MARGIN * yardstick(runs, q) + ULPS * float(np.spacing(np.abs(np.asarray(runs["f64"][q], dtype=np.float64)).max()))
+
+
+def stats_weight(case) -> float:
+    """partial_width.weight of a statistics case wider than 256 columns, on the reference alone: the float64 rows without their columns 256..."""
+    N, d, K = case
+    _, lab, _, X64, _, runs64 = reference(case)
+    return FR.second_column_weight("plda fit statistics N=%d d=%d K=%d" % case, runs64["f64"], FR.stats(PW.first_columns(X64), lab, K),
+                                   {q: tolerance(runs64, q) for q in QUANT})
+
+
 def within(name, have, runs, q):
     want = np.asarray(runs["f64"][q], dtype=np.float64)
     y = yardstick(runs, q)
-    tol = MARGIN * y + ULPS * float(np.spacing(np.abs(want).max()))
+    tol = tolerance(runs, q)
     err = float(np.abs(have - want).max())
     print(f"  {name:10s} max|d| {err:.3e}  yardstick {y:.3e}  ratio {err / y if y > 0 else 0.0 if err == 0 else np.inf:.2f}  tolerance {tol:.3e}")
     assert have.shape == want.shape and np.isfinite(have).all() and err <= tol, name
@@ -101,6 +117,8 @@ def test_statistics_against_the_float64_reference(engine, case):
         assert (runs64["f64"]["counts"] == 1).all()
     if case == (2049, 256, 40):
         assert runs64["f64"]["counts"][3] == 0 and runs64["f64"]["counts"][39] == 0 and (np.diff(lab) < 0).any()
+    if d in PW.WIDTHS:
+        stats_weight(case)
     sources = [("float64 rows", dev(X64), None, runs64)]
     if runs32 is not None:
         sources.append(("fp32 rows, transform fused", dev(E), dev(mean1), runs32))
@@ -150,13 +168,31 @@ def test_a_label_outside_the_range_raises_and_the_next_call_is_fine(engine):
 
 
 # ------------------------------------------------------------------------------------------------ projection
-@pytest.mark.parametrize("case", [(1, 64, 64), (63, 192, 100), (2049, 256, 128), (5, 512, 300)], ids=lambda c: "N%d-%dto%d" % c)
-def test_projection(engine, case):
+# the last two: d_in = 320 into D0 = 300 (a thread's second column partial over the input AND the output) and 448 into 448.  Checked on the CPU
+# (tests/test_plda_fit_cpu.py prints it): without the input columns 256.. the reference's x2 moves by more than 1e13 x its tolerance
+PROJECTION_CASES = [(1, 64, 64), (63, 192, 100), (2049, 256, 128), (5, 512, 300), (63, 320, 300), (5, 448, 448)]
+
+
+def projection_reference(case):
+    """-> (E, the synthetic model, x2 in float64, x2 in long double) of one projection case."""
     N, d_in, D0 = case
     E, _, _ = FR.labelled_rows(N + D0, N, d_in, 1)
     m = P.synthetic_plda(d_in, D0, seed=N, lda_dim=64)
-    ref = FR.project(E, m.mean1, m.lda, m.mean2)
-    ld = FR.project(E, m.mean1, m.lda, m.mean2, np.longdouble)
+    return E, m, FR.project(E, m.mean1, m.lda, m.mean2), FR.project(E, m.mean1, m.lda, m.mean2, np.longdouble)
+
+
+def projection_weight(case, E, m, ref, ld) -> float:
+    runs = {"f64": {"x2": ref}, "ld": {"x2": ld}, "rev": {"x2": ref}}
+    return FR.second_column_weight("plda projection N=%d %d -> %d" % case, {"x2": ref}, {"x2": FR.project(PW.first_columns(E), m.mean1, m.lda, m.mean2)},
+                                   {"x2": tolerance(runs, "x2")})
+
+
+@pytest.mark.parametrize("case", PROJECTION_CASES, ids=lambda c: "N%d-%dto%d" % c)
+def test_projection(engine, case):
+    N, d_in, D0 = case
+    E, m, ref, ld = projection_reference(case)
+    if d_in in PW.WIDTHS:
+        projection_weight(case, E, m, ref, ld)
     got = engine.plda_project(dev(E), dev(m.mean1), dev(m.lda), dev(m.mean2))
     torch.cuda.synchronize()
     print(f"plda projection N={N} {d_in} -> {D0}:")

@@ -59,7 +59,11 @@ def test_score_host_against_the_loops(d):
     assert np.abs(mean - want["mean"]).max() <= 1e-12 and np.abs(out_f[:, 0] - want["own"]).max() <= 1e-12 and np.abs(out_f[:, 1] - want["rival"]).max() <= 1e-12
     assert np.array_equal(out_i[:, 0], want["rival_speaker"]) and np.array_equal(out_i[:, 1], want["windows"]) and np.array_equal(out_i[:, 2], want["alone"])
     assert want["alone"].sum() >= 2 and (want["windows"] == 0).sum() == 1 and (want["rival_speaker"] == -1).sum() >= 4
+    print(f"samples_score d={d}: least rest_ratio {want['rest_ratio'][want['alone'] == 0].min():.3e} (0.1 asked), least rival_gap {want['rival_gap'].min():.3e} "
+          f"(1e-9 asked); alone {int(want['alone'].sum())}, empty {int((want['windows'] == 0).sum())}, rival-less {int((want['rival_speaker'] == -1).sum())}")
     assert (want["rest_ratio"][want["alone"] == 0] >= 0.1).all() and (want["rival_gap"] > 1e-9).all()
+    if d > 256:                                                                # the GPU test's condition at a partly (and a fully) live second column
+        assert SR.second_column_weight(f"samples_score d={d}", E, clip_off, clip_spk, spk_off, want) > 100
 
 
 def test_min_frames_and_gap():

@@ -79,6 +79,25 @@ def test_snorm_topk_host_nan_never_wins():
         SN.snorm_topk_host(E, me, se, P, mp, sp, 5)
 
 
+# ---- the GPU cases at a partly live second column --------------------------------------------------------------------------------------
+def test_the_gpu_cases_at_320_and_448_weigh_the_second_column_and_excuse_no_more_rows():
+    """What tests/test_snorm_gpu.py asserts on the reference alone before it asks the device at d = 320 and 448: without the columns 256.. the
+    statistics move by more than 100 x their bound and the top-k names other profiles; the reference excuses at most 1 % of the top-k rows."""
+    import partial_width as PW
+    import test_snorm_gpu as SG                                       # its cases and generators; importing it needs no GPU
+    stats = [c for c in SG.STAT_CASES if c[3] in PW.WIDTHS]
+    assert {c[3] for c in stats} == set(PW.WIDTHS)
+    for N, M, K, d in stats:
+        E, Cn = SG.stats_rows(N, M, d, N * 7 + M)
+        assert SR.second_column_weight_stats(f"cohort_stats N={N} M={M} K={K} d={d}", E, Cn, K, SR.cohort_stats(E, Cn, K), SG.score_bound(d)) > PW.FAR
+    assert SG.TOPK_WIDE[:4] == (70, 100, 4, 320)
+    for N, Pn, k, d, seed in [SG.TOPK_WIDE]:
+        (E, P, me, se, mp, sp), ref, B, ok = SG.topk_reference(N, Pn, k, d, seed)
+        print(f"snorm topk N={N} Pn={Pn} k={k} d={d}: the reference alone excuses {int((~ok).sum())} of {N} rows (at most {0.01 * N:g})")
+        assert (~ok).sum() <= 0.01 * N
+        assert SR.second_column_weight_topk(f"snorm topk N={N} Pn={Pn} k={k} d={d}", E, me, se, P, mp, sp, k, ref[:3], float(B.max())) > PW.FAR
+
+
 # ---- the cohort file -----------------------------------------------------------------------------------------------------------------
 def test_cohort_loads_a_good_file_and_carries_a_content_digest(tmp_path):
     rng = np.random.default_rng(0)

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import partial_width as PW  # noqa: E402
 import snorm_ref as SR  # noqa: E402
 from conftest import ROOT, sub  # noqa: E402
 
@@ -61,16 +62,25 @@ def gpu_stats(engine, E, Cn, K):
 
 
 # ---- 1. statistics against float64 ---------------------------------------------------------------------------------------------------
-STAT_CASES = [(1, 64, 1, 64), (33, 257, 100, 192), (70, 1000, 300, 192), (5, 4099, 4099, 192), (5, 4099, 4098, 192), (3, 300, 7, 512)]
+# the last two: the widths at which the second column of a thread (tid + 256) is live for wave 0 only (320) and for every wave but the last (448).
+# Checked on the CPU (tests/test_snorm_cpu.py prints it): without the columns 256.. the reference's statistics move by 253 and 537 x the bound
+STAT_CASES = [(1, 64, 1, 64), (33, 257, 100, 192), (70, 1000, 300, 192), (5, 4099, 4099, 192), (5, 4099, 4098, 192), (3, 300, 7, 512),
+              (33, 257, 100, 320), (3, 300, 7, 448)]
 _worst = {}
 
 
-def check_stats(engine, N, M, K, d, seed):
+def stats_rows(N, M, d, seed):
     rng = np.random.default_rng(seed)
-    E, Cn = unit(rng.standard_normal((N, d))), unit(rng.standard_normal((M, d)))
-    mean, std = gpu_stats(engine, E, Cn, K)
+    return unit(rng.standard_normal((N, d))), unit(rng.standard_normal((M, d)))
+
+
+def check_stats(engine, N, M, K, d, seed):
+    E, Cn = stats_rows(N, M, d, seed)
     rmean, rstd = SR.cohort_stats(E, Cn, K)
     b = score_bound(d)
+    if d in PW.WIDTHS:                                                 # on the reference alone, before the device is asked
+        SR.second_column_weight_stats(f"cohort_stats N={N} M={M} K={K} d={d}", E, Cn, K, (rmean, rstd), b)
+    mean, std = gpu_stats(engine, E, Cn, K)
     em, es = float(np.abs(mean - rmean).max()), float(np.abs(std - rstd).max())
     _worst[(N, M, K, d)] = max(em, es) / b
     print(f"cohort_stats N={N} M={M} K={K} d={d}: max |mean - ref| = {em:.3e}, max |std - ref| = {es:.3e}, bound {b:.3e}, "
@@ -198,14 +208,36 @@ def clear_rows(Z, B, k):
     return ok
 
 
-@pytest.mark.parametrize("N,Pn,k", [(33, 1, 1), (70, 100, 1), (70, 100, 4), (70, 3, 3)])
+TOPK_CASES = [(33, 1, 1), (70, 100, 1), (70, 100, 4), (70, 3, 3)]      # at d = 192, seed N + Pn + k
+# d = 320: the second column of a thread live for wave 0 only; seed 320, for which the reference alone excuses no row (174 excuses one of the 70)
+TOPK_WIDE = (70, 100, 4, 320, 320)
+
+
+def topk_reference(N, Pn, k, d, seed):
+    """-> (the planted inputs, SR.topk's tuple, the element bounds B [N, Pn], the rows whose reference ranking is decided)."""
+    inputs = planted(N, Pn, k, d, seed=seed)
+    E, P, me, se, mp, sp = inputs
+    ref = SR.topk(E, me, se, P, mp, sp, k)
+    B = 4.0 * score_bound(d) * (1.0 + np.abs(ref[3])) / np.minimum(se.astype(np.float64)[:, None], sp.astype(np.float64)[None, :])
+    return inputs, ref, B, clear_rows(ref[3], B, k)
+
+
+@pytest.mark.parametrize("N,Pn,k", TOPK_CASES)
 def test_normalised_topk_against_the_reference(engine, N, Pn, k):
-    d = 192
-    E, P, me, se, mp, sp = planted(N, Pn, k, d, seed=N + Pn + k)
-    ridx, rz, rraw, Z, S = SR.topk(E, me, se, P, mp, sp, k)
-    B = 4.0 * score_bound(d) * (1.0 + np.abs(Z)) / np.minimum(se.astype(np.float64)[:, None], sp.astype(np.float64)[None, :])
-    ok = clear_rows(Z, B, k)
+    check_topk(engine, N, Pn, k, 192, N + Pn + k)
+
+
+def test_normalised_topk_where_the_second_column_is_partly_live(engine):
+    """Checked on the CPU (tests/test_snorm_cpu.py prints it): the reference alone excuses 0 of the 70 rows (at most 1 % may be), and without
+    the columns 256.. it names other profiles."""
+    check_topk(engine, *TOPK_WIDE)
+
+
+def check_topk(engine, N, Pn, k, d, seed):
+    (E, P, me, se, mp, sp), (ridx, rz, rraw, Z, S), B, ok = topk_reference(N, Pn, k, d, seed)
     assert (~ok).sum() <= 0.01 * N, f"the reference alone excuses {(~ok).sum()} of {N} rows"
+    if d in PW.WIDTHS:
+        SR.second_column_weight_topk(f"snorm topk N={N} Pn={Pn} k={k} d={d}", E, me, se, P, mp, sp, k, (ridx, rz, rraw), float(B.max()))
     idx, z, raw = gpu_topk(engine, E, me, se, P, mp, sp, k)
     assert idx.shape == (N, k) and idx.dtype == np.int32 and z.dtype == np.float32 and raw.dtype == np.float32
     assert np.array_equal(idx[ok], ridx[ok])

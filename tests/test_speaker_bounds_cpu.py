@@ -180,3 +180,30 @@ def test_kmeans_restatement_finds_planted_clusters_and_states_its_order():
     assert two["labels"].tolist() == [0, 0] and two["n_clusters"] == 1
     with pytest.raises(ValueError):
         KR.kmeans(np.full((3, 64), np.nan, np.float32), 2)
+
+
+# ------------------------------------------------------------------------------------------------ the GPU cases at partly live second columns
+def _kmeans_gpu_cases():
+    import test_kmeans_gpu as KG                                              # its cases and generators; importing it needs no GPU
+    return KG
+
+
+@pytest.mark.parametrize("case", ["one-step-%d-%d-%d" % c for c in _kmeans_gpu_cases().PARTIAL_ONE_STEP] + ["whole-loop"])
+def test_the_kmeans_cases_at_320_and_448_decide_every_row_and_weigh_the_second_column(case):
+    """What tests/test_kmeans_gpu.py asserts on the restatement alone before it asks the device, at d = 320 and 448: the least margin over
+    10 x the bound with no row left out, and other labels (or centres 100 x their bound away) without the columns 256..."""
+    KG = _kmeans_gpu_cases()
+    if case == "whole-loop":
+        N, d, k, seed, noise = KG.PARTIAL_LOOP
+        E, kw = KG.planted(seed, N, d, k, noise), {}
+    else:
+        N, d, k = (int(v) for v in case.split("-")[2:])
+        E, kw = KG.one_step_rows(N, d), dict(max_iters=1)
+    ref = KR.kmeans(E, k, **kw)
+    bound = KG.kmeans_bound(d)
+    left_out = int(sum((m <= 10 * bound).sum() for m in ref["margins"]))
+    print(f"kmeans {case} N={N} d={d} k={k}: least margin {ref['least']:.3e} over {ref['n_iter']} assignments (10 x bound {10 * bound:.3e}); rows left out {left_out}; "
+          f"clusters {ref['n_clusters']}")
+    assert d in KR.PW.WIDTHS and ref["least"] > 10 * bound and left_out == 0
+    assert ref["n_iter"] == 1 if kw else 2 <= ref["n_iter"] < cluster.KMEANS_MAX_ITERS
+    assert KR.second_column_weight(f"kmeans {case}", E, k, (d + 4) * 2.0 ** -53, ref, **kw) > KR.PW.FAR

@@ -212,3 +212,18 @@ def test_turns_of_frames_keeps_frames_to_ranges_boundaries():
     want = sorted([(a + 100 * 270 / 16000, b + 100 * 270 / 16000, k) for k in (0, 1) for a, b in seg.frames_to_ranges((sp == k).any(1))],
                   key=lambda t: (t[0], t[2]))
     assert len(got) == 2 and np.allclose(np.array(got), np.array(want), atol=1e-12)
+
+
+@pytest.mark.parametrize("d", [320, 448])
+def test_the_gpu_streams_at_320_and_448_decide_every_step_and_weigh_the_second_column(d):
+    """What tests/test_stream_gpu.py asserts on the reference alone before it asks the device, at the widths where a thread's second column is
+    live for a part of the workgroup only: every decision more than 1e-8 from its threshold, and other integers (or scores 100 x their 1e-6
+    bound away) without the columns 256..."""
+    import test_stream_gpu as SG                                               # its streams and shape; importing it needs no GPU
+    capacity, hop, latency = 4, 8000, 8000
+    for i in range(3):
+        s, n = SG.stream_of(d, hop, i)
+        ref = SG.ref_of(d, capacity, hop, latency, i)
+        print(f"stream d={d} stream {i}: K={ref['K']}, least decision margin {ref['ref'].margin:.3e} (must exceed 1e-8)")
+        assert ref["ref"].margin > 1e-8 and ref["K"] >= 2
+        assert SR.second_column_weight(f"stream d={d} stream {i}", s, n, ref, capacity, hop, latency, SG.DELTA) > 100

@@ -26,6 +26,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import partial_width as PW  # noqa: E402
 import test_vbx_hmm_gpu as HG  # noqa: E402  (its mixture and yardstick; importing it needs no GPU)
 import vbx_hmm_ref as HR  # noqa: E402
 import vbx_ref as VR  # noqa: E402
@@ -188,7 +189,8 @@ def test_the_reference_runs_of_a_size_are_sound(S, D):
 
 
 # ------------------------------------------------------------------------------------------------ B: the inputs of sdk_vbx_centroids
-CENTROID_SHAPES = [(1, 1, 64), (255, 5, 320), (256, 5, 512), (257, 70, 512), (513, 3, 384), (300, 7, 256)]
+# the last two: a thread's second column (j1 = tid + 256) live for wave 0 only (d = 320) and for every wave but the last (448), one row past the tile
+CENTROID_SHAPES = [(1, 1, 64), (255, 5, 320), (256, 5, 512), (257, 70, 512), (513, 3, 384), (300, 7, 256), (257, 3, 320), (257, 5, 448)]
 NONE_KEPT = (257, 5, 320)
 MIN_PI = 1e-7
 MARGIN_OF_MAXIMA = 0.05
@@ -255,6 +257,23 @@ def centroid_runs(shape):
     return c["runs"]
 
 
+def centroid_tolerance(shape):
+    """-> (yardstick, tolerance) of cent64: MARGIN x the larger distance of the float64 run to its long-double and its descending run + ULPS ulp."""
+    runs = centroid_runs(shape)
+    want = runs["f64"]["cent"]
+    y = max(float(np.abs(want.astype(np.longdouble) - runs[k]["cent"].astype(np.longdouble)).max()) for k in ("ld", "rev"))
+    return y, HG.MARGIN * y + HG.ULPS * float(np.spacing(np.abs(want).max()))
+
+
+def centroid_weight(shape) -> float:
+    """partial_width.weight of a centroid case wider than 256: vbx_ref.result without the columns 256.. of the rows (the labels come from gamma
+    alone, so only the centroids can move)."""
+    c = centroid_case(shape)
+    ref = centroid_runs(shape)["f64"]
+    cut = VR.result(c["gamma"], c["pi"], PW.first_columns(c["E"][c["rows"]]))
+    return PW.weight("vbx centroids n=%d S=%d d=%d" % shape, ints=[(ref["keep"], cut["keep"])], floats=[(ref["cent"], cut["cent"])], bound=centroid_tolerance(shape)[1])
+
+
 def none_kept_case():
     """NONE_KEPT's inputs with every speaker weight at 0 or 1e-12: K = 0."""
     c = dict(centroid_case(NONE_KEPT))
@@ -306,10 +325,13 @@ def test_the_centroid_inputs_are_what_they_claim(shape):
     else:
         assert "zero" not in role
     assert all((gamma[:, s] > 0).any() for s in kept if role[s] == "kept")
+    if d > PW.FIRST:
+        assert centroid_weight(shape) > PW.FAR
 
 
 def test_the_shapes_cover_the_centroid_kernels_edges():
     assert {d > 256 for _, _, d in CENTROID_SHAPES} == {True, False} and max(d for _, _, d in CENTROID_SHAPES) == 512      # the second column per thread
+    assert {d for n, _, d in CENTROID_SHAPES if n == 257} >= set(PW.WIDTHS)               # .. live for one wave, and for all but one, past the row tile
     assert {n for n, _, _ in CENTROID_SHAPES} >= {1, 255, 256, 257, 513}                  # the 256-row LDS tile: below, exact, one over, two tiles and one
     assert any(S > 64 for _, S, _ in CENTROID_SHAPES)
     assert sum("zero" in roles(S) for _, S, _ in CENTROID_SHAPES) >= 3 and sum("nan" in roles(S) for _, S, _ in CENTROID_SHAPES) >= 3
@@ -317,3 +339,41 @@ def test_the_shapes_cover_the_centroid_kernels_edges():
     assert not (c["pi"] > MIN_PI).any() and (c["pi"] <= 1e-12).all() and set(c["pi"].tolist()) == {0.0, 1e-12}
     r = VR.result(c["gamma"], c["pi"], c["E"][c["rows"]])
     assert len(r["keep"]) == 0 and r["cent"].shape == (0, NONE_KEPT[2]) and (r["labels"] == -1).all()
+
+
+# ------------------------------------------------------------------------------------------------ C: sdk_plda_transform with two partial second columns
+TRANSFORM_CASE = (9, 320, 300, 128)               # n rows of a 12-row table, d_in, D0, D: the second column partial over d_in AND over D0
+_transform = {}
+
+
+def transform_case():
+    """-> dict(m the synthetic model, E [12, d_in] unit fp32 rows, rows [n] ascending strict subset, f64 / ld: vbx_ref.transform of the rows)."""
+    if not _transform:
+        n, d_in, D0, D = TRANSFORM_CASE
+        m = HG.P.synthetic_plda(d_in, D0, seed=d_in + D0, lda_dim=D)
+        rng = np.random.default_rng(d_in + D0 + n)
+        E = rng.standard_normal((n + 3, d_in))
+        E = (E / np.linalg.norm(E, axis=1, keepdims=True)).astype(np.float32)
+        rows = np.sort(rng.choice(n + 3, n, replace=False)).astype(np.int32)
+        _transform.update(m=m, E=E, rows=rows, **{k: VR.transform(E[rows], m.mean1, m.lda, m.mean2, m.mu, m.T, dt) for k, dt in (("f64", np.float64), ("ld", np.longdouble))})
+    return _transform
+
+
+def transform_tolerance():
+    c = transform_case()
+    y = float(np.abs(c["f64"].astype(np.longdouble) - c["ld"]).max())
+    return y, HG.MARGIN * y + HG.ULPS * float(np.spacing(np.abs(c["f64"]).max()))
+
+
+def test_the_transform_case_has_two_partial_second_columns_and_weighs_them():
+    n, d_in, D0, D = TRANSFORM_CASE
+    c = transform_case()
+    m = c["m"]
+    assert PW.FIRST < D0 < d_in < 512 and d_in in PW.WIDTHS and D0 % 64 and m.lda.shape == (d_in, D0) and m.T.shape == (D, D0)
+    assert c["f64"].shape == (n, D) and np.isfinite(c["f64"]).all() and len(c["rows"]) == n < len(c["E"])
+    y, tol = transform_tolerance()
+    # without the input columns 256.., and without the intermediate columns 256.. of x2 (the rows of T^T the second output column of a thread reads)
+    cut = VR.transform(PW.first_columns(c["E"][c["rows"]]), m.mean1, m.lda, m.mean2, m.mu, m.T)
+    assert PW.weight(f"plda transform {d_in} -> {D0} -> {D}, input columns", floats=[(c["f64"], cut)], bound=tol) > PW.FAR
+    cut = VR.transform(c["E"][c["rows"]], m.mean1, PW.first_columns(m.lda), PW.first_columns(m.mean2), PW.first_columns(m.mu), m.T)
+    assert PW.weight(f"plda transform {d_in} -> {D0} -> {D}, D0 columns", floats=[(c["f64"], cut)], bound=tol) > PW.FAR

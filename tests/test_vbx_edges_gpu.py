@@ -12,6 +12,11 @@ B. sdk_vbx_centroids alone (Engine.vbx_centroids) on constructed responsibilitie
    keep, the labels (one planted tie goes to the lower speaker; a dropped speaker's column holds the maximum of many rows), a kept speaker whose
    column is all zero (the zero centroid), NaN weights, widths above 256 (the second column per thread) and row counts at the 256-row tile's edge;
    cent64 within 8 x the yardstick of vbx_ref.result + 4 ulp, cent its fp32 rounding exactly, rows K.. zero; and no speaker kept at all.
+   At d = 320 and 448 the second column is live for one wave and for all waves but one: checked on the CPU (tests/test_vbx_edges_cpu.py prints
+   it), without the columns 256.. the reference's centroids move by 0.16, more than 1e13 x the tolerance.
+C. sdk_plda_transform alone at d_in = 320 and D0 = 300, where a thread's second column is partial over the input AND over the intermediate
+   width, against vbx_ref.transform in float64 within 8 x its distance to the long-double run + 4 ulp.  Checked on the CPU: without the input
+   columns 256.. the reference moves by 2.0, without the intermediate ones by 1.8, both more than 1e13 x the tolerance.
 
 Every test prints its figures before it asserts; profiles/vbx_edges_parity.txt records them as measured on an MI355X."""
 from __future__ import annotations
@@ -112,6 +117,8 @@ def test_centroids_on_constructed_inputs(engine, shape):
     runs = EC.centroid_runs(shape)
     ref = runs["f64"]
     K = len(ref["keep"])
+    if d in EC.PW.WIDTHS:                                                 # asserted on the reference alone, before the device is asked
+        EC.centroid_weight(shape)
     got = run_centroids(engine, c)
     again = run_centroids(engine, c)
     want = ref["cent"]
@@ -144,3 +151,18 @@ def test_centroids_with_no_speaker_kept(engine):
     assert got["K"] == 0 and (got["keep"] == -1).all() and got["keep"].shape == (S,)
     assert got["labels"].shape == (n,) and (got["labels"] == -1).all()
     assert got["cent"].shape == got["cent64"].shape == (S, d) and not got["cent"].any() and not got["cent64"].any()
+
+
+# ------------------------------------------------------------------------------------------------ C: the front transform
+def test_transform_with_two_partial_second_columns(engine):
+    n, d_in, D0, D = EC.TRANSFORM_CASE
+    c = EC.transform_case()
+    y, tol = EC.transform_tolerance()
+    X = engine.plda_transform(dev(c["E"]), dev(c["rows"]), c["m"])
+    again = engine.plda_transform(dev(c["E"]), dev(c["rows"]), c["m"])
+    torch.cuda.synchronize()
+    have = X.cpu().numpy()
+    err = float(np.abs(have - c["f64"]).max()) if have.shape == c["f64"].shape else np.inf
+    print(f"vbx edges transform n={n} {d_in} -> {D0} -> {D}: max|d| {err:.3e} yardstick {y:.3e} tolerance {tol:.3e} ratio {err / y if y > 0 else np.inf:.2f}")
+    assert have.dtype == np.float64 and have.shape == (n, D) and np.isfinite(have).all() and err <= tol
+    assert torch.equal(X, again)
