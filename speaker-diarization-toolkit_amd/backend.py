@@ -57,7 +57,7 @@ Environment:
                       at the equal error rate and at the minimum detection cost of a labelled development set (trials.py);
                       calibrate_verification fits the map from this scale to a log-likelihood ratio (SDK_SCORE_CALIBRATION)
   SDK_SCORE_PLDA_COUNT  1 (default): a speaker's effective count n_s is the number of their enrolled embeddings ("by the book") / 0: n_s = 1
-  SDK_SCORE_CALIBRATION  a calibration file (calibrate_verification(backend, ..., out_path=) below writes one; trials.py states the fit): rows of
+  SDK_SCORE_CALIBRATION  a calibration file (calibrate_verification(backend, ..., out_path=) of this module writes one; trials.py states the fit): rows of
                       identify_speaker / identify_many, and verify_speaker's answer, gain calibrated_llr = a * score + b (the score: the row's mean
                       cosine, or its mean llr under SDK_SCORE_PLDA*) and posterior = sigmoid(calibrated_llr + logit(SDK_SCORE_PRIOR)).  No decision,
                       threshold, order or existing key changes.  Refused when the file was fitted to the other rule, and together with SDK_COHORT
@@ -67,30 +67,30 @@ from __future__ import annotations
 
 import os
 import sys
+from contextlib import contextmanager
 from pathlib import Path
 from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 
-from . import BACKEND_NAME
+from . import BACKEND_NAME, settings
+from .families import FAMILIES
 from .plugin_api import EmbeddingBackend
 from .rules import Cosine, aggregate_matches, aggregate_matches_snorm, cached, rule_from_env  # noqa: F401  (the aggregations: imported from here)
 from .store import load_profile_batch, publish_pack, save_vector, vector_path
 from .wav import cut_ranges, cut_windows, decode_to_profile, range_starts, window_starts
-from .weights import DEFAULT_CONFIG, load_weights, synthetic_weights, weights_digest
+from .weights import weights_digest
 
-
-def plda_classes(recording, speaker, names, uris, speaker_key):
-    """The class of every labelled row of Diarizer.plda_rows: (uri, reference name), numbered by first appearance, unless
-    speaker_key(uri, name) maps several to one key; uri is the recording's entry of `uris`, else its index -> (labels int32, keys)."""
-    keys: dict = {}
-    labels = np.zeros(len(speaker), np.int32)
-    for j, (r, s) in enumerate(zip(recording, speaker)):
-        uri = uris[int(r)] if uris is not None else int(r)
-        name = names[int(r)][int(s)]
-        key = speaker_key(uri, name) if speaker_key is not None else (uri, name)
-        labels[j] = keys.setdefault(key, len(keys))
-    return labels, list(keys)
+# Functions that take a Backend and are not methods of it (its public surface is pinned name for name, tests/test_rules_cpu.py): each lives
+# with its subject and is importable from here, where callers and messages name it.
+from .fuse import _per_recording, compare_diarizations, diarize_fused, fuse_diarizations  # noqa: F401
+from .plda import plda_classes
+from .samples import speaker_samples, write_samples  # noqa: F401
+from .score import score_diarization_uem  # noqa: F401
+from .smooth import smooth_diarization  # noqa: F401
+from .trials import calibrate_verification  # noqa: F401
+from .trials_snorm import _snorm_trials, score_verification_snorm, tune_cohort_threshold  # noqa: F401
+from .words import attribute_transcript, attribute_transcripts, diarize_transcript, score_words  # noqa: F401
 
 
 def _of_rule(name: str) -> property:
@@ -106,20 +106,21 @@ class Backend(EmbeddingBackend):
 
     def __init__(self) -> None:
         self.model = os.environ.get("SDK_MODEL", "ecapa").strip().lower()
-        if self.model not in ("ecapa", "xvector", "resnet34"):
+        if self.model not in FAMILIES:
             raise ValueError(f"SDK_MODEL={self.model!r}: expected 'ecapa', 'xvector' or 'resnet34'")
+        self._family = FAMILIES[self.model]             # the selected family's row (families.py)
         self.diarize_model = os.environ.get("SDK_DIARIZE_MODEL", "resnet34").strip().lower()
         if self.diarize_model not in ("resnet34", "ecapa"):
             raise ValueError(f"SDK_DIARIZE_MODEL={self.diarize_model!r}: expected 'resnet34' (default) or 'ecapa'")
         if self.diarize_model == "ecapa":
             if self.model != "ecapa":
                 raise ValueError(f"SDK_DIARIZE_MODEL=ecapa diarizes in the space of the backend's own ECAPA-TDNN: it requires SDK_MODEL=ecapa, got SDK_MODEL={self.model!r}")
-            if os.environ.get("SDK_PRECISION", "0").strip() not in ("0", "2"):
+            text = settings.precision_text()
+            if ("0" if text is None else text).strip() not in ("0", "2"):
                 raise ValueError(f"SDK_DIARIZE_MODEL=ecapa requires SDK_PRECISION 0 (bf16) or 2 (fp16): the masked pooling is not built for the precise mode, got "
-                                 f"SDK_PRECISION={os.environ.get('SDK_PRECISION')!r}")
-        wenv = {"xvector": "SDK_XVECTOR_WEIGHTS", "resnet34": "SDK_RESNET_WEIGHTS"}.get(self.model, "SDK_ECAPA_WEIGHTS")
-        if not os.environ.get(wenv):
-            print(f"mi355x backend: {wenv} not set - using seeded synthetic {dict(xvector='x-vector', resnet34='ResNet34').get(self.model, 'ECAPA-TDNN')} weights "
+                                 f"SDK_PRECISION={text!r}")
+        if not settings.weights_path(self._family.weights_env):
+            print(f"mi355x backend: {self._family.weights_env} not set - using seeded synthetic {self._family.label} weights "
                   "(scores are self-consistent but not trained)", file=sys.stderr)
         self._cache_hit = False
         self._engine = None
@@ -141,22 +142,11 @@ class Backend(EmbeddingBackend):
 
     @property
     def embedding_dim(self) -> Optional[int]:
-        if self.model == "xvector":
-            from .xvector import DEFAULT_XVECTOR
-            return DEFAULT_XVECTOR.embed_dim
-        if self.model == "resnet34":
-            from .resnet import DEFAULT_RESNET
-            return DEFAULT_RESNET.embed_dim
-        return DEFAULT_CONFIG.embed_dim
+        return self._family.embed_dim
 
     @property
     def model_version(self) -> str:
-        if self.model == "xvector":
-            from .xvector import DEFAULT_XVECTOR
-            return f"{self.name}-xvector{DEFAULT_XVECTOR.channels[0]}-{self._weights_digest()}"
-        if self.model == "resnet34":
-            return f"{self.name}-resnet34-{self._weights_digest()}"
-        return f"{self.name}-ecapa1024-{self._weights_digest()}"
+        return f"{self.name}-{self._family.version_tag}-{self._weights_digest()}"
 
     @property
     def audio_profile(self):
@@ -164,45 +154,17 @@ class Backend(EmbeddingBackend):
 
     # ---- lazily built state --------------------------------------------------------------
     def _host_weights(self):
-        if self._weights is None and self.model == "xvector":
-            from . import xvector
-            path = os.environ.get("SDK_XVECTOR_WEIGHTS")
-            if path:
-                with np.load(path, allow_pickle=False) as z:             # numpy's non-executing loader
-                    self._weights = {k: np.ascontiguousarray(z[k], dtype=np.float32) for k in z.files}
-                xvector.pack_weights(self._weights)                      # shape check (raises ValueError naming the tensor)
-            else:
-                self._weights = xvector.synthetic_weights(0)
-        if self._weights is None and self.model == "resnet34":
-            from . import resnet
-            path = os.environ.get("SDK_RESNET_WEIGHTS")
-            if path:
-                with np.load(path, allow_pickle=False) as z:             # numpy's non-executing loader
-                    self._weights = {k: np.ascontiguousarray(z[k], dtype=np.float32) for k in z.files}
-                resnet.pack_weights(self._weights)                       # shape check (raises ValueError naming the tensor)
-            else:
-                self._weights = resnet.synthetic_weights(0)
         if self._weights is None:
-            path = os.environ.get("SDK_ECAPA_WEIGHTS")
-            if path:
-                # SDK_ECAPA_LAYOUT=public: a checkpoint in the public ECAPA-TDNN state-dict naming (weights.from_public_state_dict);
-                # default: the .npz naming of weights.py.  Both through non-executing loaders only.
-                if os.environ.get("SDK_ECAPA_LAYOUT", "native") == "public":
-                    from .weights import load_public_checkpoint
-                    self._weights = load_public_checkpoint(path, prefix=os.environ.get("SDK_ECAPA_PREFIX", ""))
-                else:
-                    self._weights = load_weights(path)
-            else:
-                self._weights = synthetic_weights(0)
+            self._weights = self._family.host_weights()              # the checkpoint its variable names, shape-checked, else seeded synthetic
         return self._weights
 
     def _cache_key(self) -> str:
-        """Identity of the weights for the packed-blob cache, without reading them (weights_cache.py)."""
+        """Identity of the weights for the packed-blob cache, without reading them (weights_cache.py); None: the family's blob is not cached."""
         from . import weights_cache
-        if self.model in ("xvector", "resnet34"):
-            return None                                  # 4.4 M / 6.3 M parameters: packed in well under a second, not cached
-        path = os.environ.get("SDK_ECAPA_WEIGHTS")
-        return weights_cache.key_for_file(path) if path else weights_cache.key_for_seed(0, DEFAULT_CONFIG)
+        if not self._family.cached:
+            return None
+        path = settings.weights_path(self._family.weights_env)
+        return weights_cache.key_for_file(path) if path else weights_cache.key_for_seed(0, self._family.config)
 
     def _weights_digest(self) -> str:
         """Content hash of the weights (part of model_version).  A process that finds the packed blob in the cache takes the digest
@@ -221,26 +183,26 @@ class Backend(EmbeddingBackend):
     def numerics(self) -> Dict[str, Any]:
         """The numerical setting embeddings are made under (stored beside every enrolled vector; identify warns when a candidate was made
         under another one): model_version names the WEIGHTS - both settings embed into the same space, ~4e-3 apart."""
-        prec = int(os.environ.get("SDK_PRECISION", "0"))
-        return {"precision": prec, "bias_correction": bool(os.environ.get("SDK_BIAS_CORRECTION", "1") != "0") and prec in (0, 2) and self.model != "resnet34"}
+        prec = settings.precision()
+        return {"precision": prec, "bias_correction": settings.bias_correction() and prec in (0, 2) and self._family.bias_correction}
 
     @property
     def lite(self) -> bool:
-        return os.environ.get("SDK_NO_TORCH") == "1"
+        return settings.lite()
 
     def _lite_engine(self):
         """lite.LiteEngine on the cached packed weights; a cache miss is filled ONCE by a child process that runs the torch engine (pack, bias-correction
         calibration pass, store) - this process must not import torch itself (one HIP runtime per process)."""
-        if self.model == "resnet34":
-            raise ValueError("SDK_NO_TORCH=1 with SDK_MODEL=resnet34: the torch-free host path does not serve the ResNet34 family; unset SDK_NO_TORCH")
+        fam = self._family
+        if not fam.lite:
+            raise ValueError(f"SDK_NO_TORCH=1 with SDK_MODEL={fam.name}: the torch-free host path does not serve the {fam.label} family; unset SDK_NO_TORCH")
         from .lite import LiteEngine
-        dev = int(os.environ.get("SDK_DEVICE", os.environ.get("LOCAL_RANK", "0")))
-        prec = int(os.environ.get("SDK_PRECISION", "0"))
+        dev, prec = settings.device(), settings.precision()
         if prec not in (0, 2):
             raise ValueError(f"SDK_NO_TORCH=1 serves the single-plane contracts (SDK_PRECISION=0 or 2); SDK_PRECISION={prec} needs the torch engine")
-        if self.model == "xvector":
+        if fam.lite_load is not None:                 # a family whose blob is packed here, not cached
             eng = LiteEngine(dev, precision=prec)
-            eng.load_xvector(self._host_weights())
+            fam.lite_load(eng, self._host_weights())
             return eng
         eng = LiteEngine(dev, cache_key=self._cache_key(), precision=prec)
         if not eng.has_cached_weights():
@@ -251,7 +213,7 @@ class Backend(EmbeddingBackend):
             code = f"import importlib; b = importlib.import_module('{__package__}.backend').Backend(); b.engine().desc"
             try:                                  # bounded: a stuck child must not hang the CLI; the build takes ~2 s
                 r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True,
-                                   timeout=float(os.environ.get("SDK_CACHE_BUILD_TIMEOUT_S", "300")))
+                                   timeout=settings.cache_build_timeout_s())
                 err = r.stderr.strip()[-400:] if r.returncode != 0 else ""
             except subprocess.TimeoutExpired:
                 r, err = None, "the child process did not finish in time (SDK_CACHE_BUILD_TIMEOUT_S)"
@@ -267,29 +229,17 @@ class Backend(EmbeddingBackend):
             self._engine = self._lite_engine()
         if self._engine is None:
             from .ops import Engine   # imports torch + dlopens libsdk_hip.so; raises SdkError if absent
-            dev = int(os.environ.get("SDK_DEVICE", os.environ.get("LOCAL_RANK", "0")))
-            if self.model == "xvector":
-                from .xvector import XVector
-                prec = int(os.environ.get("SDK_PRECISION", "0"))
+            fam, dev, prec = self._family, settings.device(), settings.precision()
+            if prec == 1 and 1 not in fam.precisions:
+                raise ValueError(f"SDK_PRECISION=1 (the precise mode) is not built for SDK_MODEL={fam.name}: use SDK_PRECISION=0 or 2")
+            if fam.extractor_name is None:               # the engine's own ECAPA-TDNN: packed on first use, from the cache where it can
+                self._engine = Engine(dev, cache_key=self._cache_key(), weights_fn=self._host_weights, digest_fn=self._weights_digest)
+            else:
                 self._engine = Engine(dev)               # front end, k3, k4; its ECAPA weights are never packed (lazy)
-                if prec:
-                    self._engine.set_precision(prec)
-                self._extractor = XVector(self._engine, self._host_weights(), precision=prec)    # bias correction: $SDK_BIAS_CORRECTION (default on)
-                return self._engine
-            if self.model == "resnet34":
-                from .resnet import ResNet34
-                prec = int(os.environ.get("SDK_PRECISION", "0"))
-                if prec == 1:
-                    raise ValueError("SDK_PRECISION=1 (the precise mode) is not built for SDK_MODEL=resnet34: use SDK_PRECISION=0 or 2")
-                self._engine = Engine(dev)               # front end, k3, k4; its ECAPA weights are never packed (lazy)
-                if prec:
-                    self._engine.set_precision(prec)
-                self._extractor = ResNet34(self._engine, self._host_weights(), precision=prec)
-                return self._engine
-            self._engine = Engine(dev, cache_key=self._cache_key(), weights_fn=self._host_weights, digest_fn=self._weights_digest)
-            prec = int(os.environ.get("SDK_PRECISION", "0"))
             if prec:
                 self._engine.set_precision(prec)
+            if fam.extractor_name is not None:
+                self._extractor = fam.extractor(self._engine, self._host_weights(), prec)    # bias correction: $SDK_BIAS_CORRECTION (default on)
         return self._engine
 
     def _embed_pcm(self, pcm_dev):
@@ -303,7 +253,7 @@ class Backend(EmbeddingBackend):
         Recordings of any length: the forward's scratch is ~6.7 MB per 2-s window, so the windows go through in batches
         of SDK_MAX_BATCH (default 2048 = 13.7 GB of scratch; a 1-h file at a 1-s hop is two batches)."""
         eng = self.engine()
-        step = max(1, int(os.environ.get("SDK_MAX_BATCH", "2048")))
+        step = settings.max_batch()
         if self.lite:
             raise RuntimeError("embed_windows returns device tensors: not available with SDK_NO_TORCH=1 (use embed_windows_host)")
         import torch
@@ -319,7 +269,7 @@ class Backend(EmbeddingBackend):
         (SDK_NO_TORCH=1), same bounded batches.  A ProfileBatch served from its pack is uploaded as packed (no normalisation pass); one loaded
         file by file is normalised on the device once and its pack is published."""
         eng = self.engine()
-        step = max(1, int(os.environ.get("SDK_MAX_BATCH", "2048")))
+        step = settings.max_batch()
         Es, idxs, scs = [], [], []
         batch = profiles if hasattr(profiles, "matrix") else None
         for a in range(0, pcm.shape[0], step):
@@ -349,13 +299,13 @@ class Backend(EmbeddingBackend):
         eng = self.engine()
         if self.lite:
             raise RuntimeError("embed_tables returns device tensors: not available with SDK_NO_TORCH=1 (use embed_tables_host)")
-        step = max(1, int(os.environ.get("SDK_MAX_BATCH", "2048")))
+        step = settings.max_batch()
         return eng.embed_from_host(samples, tables, step, forward=self._extractor.forward if self._extractor is not None else None)
 
     def embed_tables_host(self, samples: np.ndarray, tables: Dict[int, np.ndarray], batch=None, k: int = 1):
         """The same for the torch-free host path: {S: (E host, idx, score)}; with a ProfileBatch every batch of windows is scored while resident."""
         eng = self.engine()
-        step = max(1, int(os.environ.get("SDK_MAX_BATCH", "2048")))
+        step = settings.max_batch()
         kw = None
         if batch is not None:
             kw = {"norm": batch.norm, "tag": batch.uid, "on_norm": (lambda E, Eb, r: publish_pack(batch, E, Eb, r)) if batch.pack_ref else None}
@@ -471,10 +421,10 @@ class Backend(EmbeddingBackend):
             raise ValueError("speech_ranges needs the torch engine: not available with SDK_NO_TORCH=1")
         if getattr(self, "_segmentation", None) is None:
             from .segmentation import Segmentation, load_weights, synthetic_weights as seg_synthetic
-            prec = int(os.environ.get("SDK_PRECISION", "0"))
+            prec = settings.precision()
             if prec == 1:
                 raise ValueError("SDK_PRECISION=1 (the precise mode) is not built for the segmentation model: use SDK_PRECISION=0 or 2")
-            path = os.environ.get("SDK_SEGMENTATION_WEIGHTS")
+            path = settings.weights_path("SDK_SEGMENTATION_WEIGHTS")
             w = load_weights(path) if path else seg_synthetic(0)
             self._segmentation = Segmentation(self.engine(), w, precision=prec)
         return self._segmentation
@@ -495,7 +445,7 @@ class Backend(EmbeddingBackend):
             return [], []
         st = chunk_starts(x.size, step_s)
         rec = torch.from_numpy(x).to(model.eng.device)
-        step = max(1, int(os.environ.get("SDK_SEGMENTATION_BATCH", "256")))
+        step = settings.segmentation_batch()
         counts = []
         for a in range(0, len(st), step):
             s = torch.from_numpy(st[a:a + step].astype(np.int32)).to(model.eng.device)
@@ -513,35 +463,39 @@ class Backend(EmbeddingBackend):
         if self.lite:
             raise ValueError("diarize needs the torch engine: not available with SDK_NO_TORCH=1")
         if getattr(self, "_diarizer", None) is None:
-            from . import resnet
             from .diarize import Diarizer
             model = self.segmentation()
+            resnet34 = FAMILIES["resnet34"]
             if self.diarize_model == "ecapa":
                 from .ecapa_diar import EcapaEmbedder
                 net = EcapaEmbedder(self.engine())                # the engine's own blob: the enrolled space, bias correction included
-            elif self.model == "resnet34":
+            elif self._family is resnet34:
                 net = self._extractor                            # built by engine() from the same weights
             else:
-                prec = int(os.environ.get("SDK_PRECISION", "0"))
-                path = os.environ.get("SDK_RESNET_WEIGHTS")
-                if path:
-                    with np.load(path, allow_pickle=False) as z:             # numpy's non-executing loader
-                        w = {k: np.ascontiguousarray(z[k], dtype=np.float32) for k in z.files}
-                else:
-                    w = resnet.synthetic_weights(0)
-                net = resnet.ResNet34(self.engine(), w, precision=prec)
-            tpath, ppath = os.environ.get("SDK_PLDA_TRANSFORM"), os.environ.get("SDK_PLDA")
-            if bool(tpath) != bool(ppath):
-                raise ValueError("SDK_PLDA_TRANSFORM and SDK_PLDA name the two files of one PLDA model: set both or neither")
+                prec = settings.precision()
+                net = resnet34.extractor(self.engine(), resnet34.host_weights(), prec)
+            files = settings.diarizer_plda()                     # refuses one file without the other
             model_plda = None
-            if tpath:
+            if files is not None:
                 from .plda import load_plda
-                dim = os.environ.get("SDK_PLDA_DIM", "128")
-                if dim not in ("64", "128"):
-                    raise ValueError(f"SDK_PLDA_DIM={dim!r}: the PLDA dimensions kept, 64 or 128")
-                model_plda = load_plda(tpath, ppath, int(dim))
+                model_plda = load_plda(*files)
             self._diarizer = Diarizer(self.engine(), model, net, model_plda)
         return self._diarizer
+
+    def _recordings(self, samples_or_paths) -> list:
+        """A list of recordings, each 16 kHz mono int16 samples or the path of an audio file: the paths decoded to the audio profile."""
+        return [decode_to_profile(Path(x), self.engine(), self.get_audio_profile()) if isinstance(x, (str, Path)) else x for x in samples_or_paths]
+
+    @staticmethod
+    @contextmanager
+    def _restored_precision(dz):
+        """The diarizer steps in its network's numerical contract: on the way out its engine goes back to the precision it had."""
+        prec = dz.eng.precision
+        try:
+            yield
+        finally:
+            if dz.eng.precision != prec:
+                dz.eng.set_precision(prec)                       # the front end's format goes back to the selected family's contract
 
     def diarize(self, samples_or_path, **kw):
         """Who spoke when, with no transcript and no enrolled profiles: a recording (16 kHz mono int16 samples, or the path of an audio file,
@@ -559,16 +513,11 @@ class Backend(EmbeddingBackend):
         is the cap per frame); result.forced says whether the clustering was overruled.  min_duration_off, min_duration_on (seconds,
         default 0: nothing is done): a speaker's pauses no longer than the first are filled, then the turns shorter than the second are
         dropped, on the device before the speakers table comes down (smooth.py states the rule); result.smoothing says what was done, and
-        smooth_diarization below does the same to finished results.  Parity with PyAnnote is unpinned."""
+        smooth_diarization of this module does the same to finished results.  Parity with PyAnnote is unpinned."""
         dz = self.diarizer()
-        if isinstance(samples_or_path, (str, Path)):
-            samples_or_path = decode_to_profile(Path(samples_or_path), self.engine(), self.get_audio_profile())
-        prec = dz.eng.precision
-        try:
-            return dz.run(samples_or_path, **kw)
-        finally:
-            if dz.eng.precision != prec:
-                dz.eng.set_precision(prec)                       # the front end's format goes back to the selected family's contract
+        rec, = self._recordings([samples_or_path])
+        with self._restored_precision(dz):
+            return dz.run(rec, **kw)
 
     def diarize_many(self, samples_or_paths, **kw):
         """diarize for a folder of recordings in one device pass per pack: a list of recordings (16 kHz mono int16 samples or paths of audio
@@ -578,13 +527,9 @@ class Backend(EmbeddingBackend):
         which also states how the results relate to diarize's).  Keywords as diarize, min_duration_off and min_duration_on among them (the
         pack's table is smoothed in one launch sequence and no wait is added); logp is a list with one array per recording."""
         dz = self.diarizer()
-        recs = [decode_to_profile(Path(x), self.engine(), self.get_audio_profile()) if isinstance(x, (str, Path)) else x for x in samples_or_paths]
-        prec = dz.eng.precision
-        try:
+        recs = self._recordings(samples_or_paths)
+        with self._restored_precision(dz):
             return dz.run_many(recs, **kw)
-        finally:
-            if dz.eng.precision != prec:
-                dz.eng.set_precision(prec)                       # the front end's format goes back to the selected family's contract
 
     def _references(self, who: str, references, uris, n: int):
         """One turn list per recording from `references`: a list of turn lists [(start_s, end_s, name)], or an RTTM path / text / {uri: turns}
@@ -606,7 +551,7 @@ class Backend(EmbeddingBackend):
         `uris` naming the results' recordings in it.  collar_s: md-eval's collar, on each side of every reference boundary; skip_overlap:
         frames with two or more reference speakers are not scored.  Scored on the device in one pack (score.py states the rule; parity
         with md-eval and pyannote.metrics is unpinned).  With an evaluation map (UEM) or the Jaccard error rate: score_diarization_uem
-        below."""
+        of this module."""
         results = list(results)
         return self.diarizer().score(results, self._references("score_diarization", references, uris, len(results)), collar_s, skip_overlap)
 
@@ -622,14 +567,10 @@ class Backend(EmbeddingBackend):
         [T][S][R], pooled [T][S], best = (threshold, min_duration_off, min_duration_on)): whether half a second of gap filling helps more
         than another cut."""
         dz = self.diarizer()
-        recs = [decode_to_profile(Path(x), self.engine(), self.get_audio_profile()) if isinstance(x, (str, Path)) else x for x in samples_or_paths]
+        recs = self._recordings(samples_or_paths)
         refs = self._references("tune_diarization", references, uris, len(recs))
-        prec = dz.eng.precision
-        try:
+        with self._restored_precision(dz):
             return dz.sweep(recs, refs, thresholds, uris=uris, **kw)
-        finally:
-            if dz.eng.precision != prec:
-                dz.eng.set_precision(prec)                       # the front end's format goes back to the selected family's contract
 
     def score_verification(self, audio_paths, speaker_ids, candidates, score_range=None, p_target: float = 0.01, c_miss: float = 1.0,
                            c_fa: float = 1.0, max_refine: int = 8):
@@ -694,11 +635,8 @@ class Backend(EmbeddingBackend):
         rows; identify's fp32 cosines of the same rows agree with it only to fp32 rounding (a few 1e-7), so a window within that of the
         threshold may vote differently.  kind "plda": they are usable as SDK_SCORE_PLDA_THRESHOLD - the tuned operating point that the
         uncalibrated default 0 is not."""
-        res = self.score_verification(audio_paths, speaker_ids, candidates, score_range, p_target, c_miss, c_fa, max_refine)
-        return {"kind": res.kind, "eer": res.eer, "eer_threshold": res.eer_threshold, "min_dcf": res.min_dcf, "min_dcf_threshold": res.min_dcf_threshold,
-                "min_dcf_lower": res.min_dcf_lower, "min_dcf_exact": res.min_dcf_exact, "n_target": res.n_target, "n_nontarget": res.n_nontarget,
-                "n_nan": res.n_nan, "n_excluded": res.n_excluded, "n_test_rows": res.test_rows, "n_model_rows": res.model_rows, "score_range": res.score_range,
-                "result": res}
+        from .trials import summary
+        return summary(self.score_verification(audio_paths, speaker_ids, candidates, score_range, p_target, c_miss, c_fa, max_refine))
 
     def train_plda(self, samples_or_paths, references, uris=None, out_dir=None, D0: int = 128, lda_dim: int = 128, n_iters: int = 10,
                    step_s: float = 1.0, speaker_key=None, logp=None):
@@ -711,14 +649,10 @@ class Backend(EmbeddingBackend):
         written, xvec_transform.npz and plda.npz, which $SDK_PLDA_TRANSFORM / $SDK_PLDA accept."""
         from . import plda as plda_mod
         dz = self.diarizer()
-        recs = [decode_to_profile(Path(x), self.engine(), self.get_audio_profile()) if isinstance(x, (str, Path)) else x for x in samples_or_paths]
+        recs = self._recordings(samples_or_paths)
         refs = self._references("train_plda", references, uris, len(recs))
-        prec = dz.eng.precision
-        try:
+        with self._restored_precision(dz):
             got = dz.plda_rows(recs, refs, step_s=step_s, logp=logp)
-        finally:
-            if dz.eng.precision != prec:
-                dz.eng.set_precision(prec)                       # the front end's format goes back to the selected family's contract
         labels, keys = plda_classes(got["recording"], got["speaker"], got["names"], uris, speaker_key)
         if not len(labels):
             raise ValueError("train_plda: no training row is covered by a reference speaker")
@@ -986,296 +920,3 @@ class Backend(EmbeddingBackend):
         out = {"match": True, "similarity": h["similarity"], "confidence": h["similarity"], "embedding_id": h.get("embedding_id")}
         out.update((key, h[key]) for key in self.rule.verify_keys)          # norm_score under a cohort, llr under a scoring PLDA
         return out
-
-
-# ---- speaker-attributed transcripts (words.py).  Functions of the backend, not methods of it: Backend's public surface is pinned name for
-#      name (tests/test_rules_cpu.py), as calibrate_verification below.
-def attribute_transcripts(be: Backend, results, transcripts, max_gap_s: float = 0.5, names=None):
-    """Who said which word: the results of diarize / diarize_many / a finished stream and one word-timed transcript per result (dicts in
-    the Speechmatics, AssemblyAI or OpenAI verbose_json layout; the speakers they carry are not read) -> a list of (relabelled, rows):
-    the transcript relabelled in its own layout (OpenAI: in the Speechmatics layout) with speaker k as "S<k+1>", or names[k], or "UU"
-    for a word nobody is near, and rows [W, 8] int32 per word (speaker, votes, solo, span, second, second_votes, distance, g0).  A word
-    goes to the speaker active in most of its frames; a word in non-speech to the nearest voiced frame within max_gap_s.  All words of
-    all recordings are attributed in one launch on the device (words.py states the rule; parity with other toolkits is unpinned).
-    relabelled feeds segments.sentence_segments, extract_segments_as_tuples and assign.py; words.attributed_sentences(transcript,
-    rows) gives the sentences with their text."""
-    from . import words as wd
-    results, transcripts = list(results), list(transcripts)
-    if len(transcripts) != len(results):
-        raise ValueError(f"attribute_transcripts: {len(transcripts)} transcripts for {len(results)} recordings")
-    if not results:
-        return []
-    labels = wd.attribute(be.engine(), results, [wd.transcript_words(t) for t in transcripts], max_gap_s)
-    return [(wd.relabel_transcript(t, lab.rows, names), lab.rows) for t, lab in zip(transcripts, labels)]
-
-
-def attribute_transcript(be: Backend, result, transcript, max_gap_s: float = 0.5, names=None):
-    """attribute_transcripts for one recording -> (relabelled, rows)."""
-    return attribute_transcripts(be, [result], [transcript], max_gap_s, names)[0]
-
-
-def diarize_transcript(be: Backend, samples_or_path, transcript, max_gap_s: float = 0.5, names=None, **diarize_keywords):
-    """diarize, then attribute_transcript: a recording and its word-timed transcript (say OpenAI/Whisper verbose_json, which has no
-    speakers) -> (relabelled, rows, result): the transcript with a speaker on every word, the words' rows and the
-    diarize.DiarizationResult they were read from.  diarize_keywords: those of diarize."""
-    result = be.diarize(samples_or_path, **diarize_keywords)
-    relabelled, rows = attribute_transcript(be, result, transcript, max_gap_s, names)
-    return relabelled, rows, result
-
-
-def score_words(be: Backend, results, transcripts, max_gap_s: float = 0.5):
-    """How good the attribution is: the word-level diarization error rate (WDER) of attribute_transcripts against the speakers the
-    transcripts already carry -> (a list of words.WderResult (scored, unassigned, words, correct, wder, mapping, co), the pooled
-    WderResult).  A word is scored when the transcript gives it a speaker other than "UU"; the hypothesis speakers are mapped onto the
-    reference's by the exact maximum-weight assignment, and a scored word without a speaker is an error.  Attributed and scored on
-    the device in one pack (words.py states the rule; parity with other toolkits is unpinned)."""
-    from . import words as wd
-    results, transcripts = list(results), list(transcripts)
-    if len(transcripts) != len(results):
-        raise ValueError(f"score_words: {len(transcripts)} transcripts for {len(results)} recordings")
-    if not results:
-        return [], wd.pool([])
-    words = [wd.transcript_words(t) for t in transcripts]
-    per = wd.wder(be.engine(), results, words, [[w[3] for w in ws] for ws in words], max_gap_s)
-    return per, wd.pool(per)
-
-
-# ---- scoring the DIHARD way (score.py).  A function of the backend for the same reason: Backend.score_diarization keeps its signature.
-def score_diarization_uem(be: Backend, results, references, uris=None, collar_s: float = 0.0, skip_overlap: bool = False, uem=None, jer: bool = False):
-    """Backend.score_diarization with an evaluation map and the Jaccard error rate.  uem: the map outside which nothing is scored - one
-    entry per result (None, or a list of (start_s, end_s)), or the path or text of a UEM file (or {uri: intervals}) read with `uris`; a
-    uri it does not hold is scored everywhere.  jer=True: every score.DerResult carries the Jaccard error rate (jer, jsum, ref_speakers,
-    ref_frames, hyp_frames, jer_mapping), purity and coverage beside the DER; score.pool(list) pools them too.  With uem=None and
-    jer=False it is score_diarization.  Backend.tune_diarization takes the same two keywords, and metric="jer"."""
-    results = list(results)
-    return be.diarizer().score(results, be._references("score_diarization_uem", references, uris, len(results)), collar_s, skip_overlap,
-                               uem=uem, jer=jer, uris=uris)
-
-
-# ---- smoothing finished results (smooth.py).  A function of the backend for the same reason.
-def smooth_diarization(be: Backend, results, min_duration_off: float = 0.0, min_duration_on: float = 0.0, max_speakers=None):
-    """The results of diarize / diarize_many / a closed stream with their turns smoothed: a speaker's pauses no longer than
-    min_duration_off seconds are filled (where the frame has a free slot: at most 2 speakers per frame, fewer with max_speakers, and a
-    speaker the diarization put there is never displaced), then the turns shorter than min_duration_on seconds are dropped - PyAnnote's
-    Binarize hyper-parameters, in its order.  -> copies of the results with speakers, turns and smoothing ({min_duration_off,
-    min_duration_on, fill, keep, filled, dropped}) replaced; everything else, count included, is what it was.  One upload, one launch
-    sequence (sdk_smooth_turns) and one download for the whole list; a single result gives a single result.  diarize(min_duration_off=,
-    min_duration_on=) does the same before the table comes down (smooth.py states the rule; parity with PyAnnote is unpinned)."""
-    from .smooth import smooth_results
-    single = not isinstance(results, (list, tuple))
-    out = smooth_results(be.engine(), [results] if single else list(results), min_duration_off, min_duration_on, max_speakers)
-    return out[0] if single else out
-
-
-# ---- fusing several diarizations of a recording (fuse.py).  Functions of the backend for the same reason: the class keeps its public names.
-def _per_recording(x) -> bool:
-    """True where x is a list over recordings, False where it is one hypothesis (a result, or a non-empty turn list)."""
-    from .fuse import is_hypothesis
-    return not (is_hypothesis(x) and not (isinstance(x, (list, tuple)) and len(x) == 0))
-
-
-def fuse_diarizations(be: Backend, hypotheses, n_samples=None, weights=None, max_speakers=None):
-    """Several diarizations of the same recordings combined into one each, DOVER-Lap's way: hypotheses[r] = the H (2 .. 8) answers for
-    recording r, each a diarize.DiarizationResult (of diarize / diarize_many under different models, clusterings or thresholds) or a turn
-    list [(start_s, end_s, name)] (an outside diarizer's; then n_samples, the recordings' lengths, fixes the frame grid where no result
-    does).  The speakers of the hypotheses are mapped onto common labels through their pairwise co-occurrence, starting from the hypothesis
-    that agrees most with the others; the hypotheses are weighted by their rank in mean disagreement (or by weights=, H integers in
-    1 .. 65536) and every frame is voted, the number of speakers from the weighted mean count (at most 2, fewer with max_speakers).  -> one
-    result per recording: the anchor's result copied (else a fuse.FusedDiarization) with speakers, turns and n_speakers replaced and
-    `fusion` = {order, weights, dis, label_of, speech, overlap, unanimous, overflow}.  One upload, the device calls and one download for
-    the whole list (fuse.py states the rule; parity with DOVER-Lap is unpinned)."""
-    from .fuse import fuse_results
-    return fuse_results(be.engine(), list(hypotheses), n_samples, weights, max_speakers)
-
-
-def compare_diarizations(be: Backend, a, b, n_samples=None):
-    """Two diarizations of the same recording laid side by side: a and b are one hypothesis each (as fuse_diarizations takes them), or
-    lists of them, one per recording -> per recording a dict of co [K_a, K_b] (the frames speaker i of a shares with speaker j of b), mapping
-    (b's speaker for each of a's under an optimal assignment), names_a, names_b, sum_max, sum_min, correct, disagreement = (sum_max -
-    correct) / sum_max - the symmetric diarization error of one against the other, 0.0 for two silent answers - and unanimous, the frames
-    on which they agree.  A single pair gives a single dict."""
-    from .fuse import compare
-    single = not _per_recording(a)
-    if single:
-        a, b = [a], [b]
-        n_samples = None if n_samples is None else [n_samples]
-    out = compare(be.engine(), a, b, n_samples)
-    return out[0] if single else out
-
-
-def diarize_fused(be: Backend, samples_or_path, variants, **fuse_kw):
-    """diarize once per keyword set of `variants` (for example [{"clustering": "ahc"}, {"clustering": "vbx", "threshold": 0.6},
-    {"clustering": "nmesc"}]) and the results fused (fuse_diarizations; fuse_kw: weights, max_speakers) -> the fused result.  Every
-    variant runs the whole pipeline: the embedding pass is not shared between them."""
-    variants = [dict(v) for v in variants]
-    from .fuse import MAX_FUSE_HYPS
-    if not 2 <= len(variants) <= MAX_FUSE_HYPS:
-        raise ValueError(f"diarize_fused: {len(variants)} variants (2 .. {MAX_FUSE_HYPS})")
-    if isinstance(samples_or_path, (str, Path)):
-        samples_or_path = decode_to_profile(Path(samples_or_path), be.engine(), be.get_audio_profile())
-    return fuse_diarizations(be, [[be.diarize(samples_or_path, **v) for v in variants]], **fuse_kw)[0]
-
-
-# ---- speaker samples (samples.py).  Functions of the backend for the same reason.
-def speaker_samples(be: Backend, results, samples_or_paths, min_s: float = 0.5, max_gap_s: float = 1.0, max_clip_s=None, max_candidates=None,
-                    max_clips=None, max_total_s=None, min_margin: float = 0.0):
-    """Which stretches of audio of each diarized speaker are clean enough to listen to and to enrol from: the results of diarize /
-    diarize_many and their recordings (16 kHz mono int16 samples, or paths of audio files) -> one {speaker: [samples.SpeakerSample]} per
-    recording, a single dict for a single result.  A speaker's runs of solo frames (no overlap, pauses up to max_gap_s bridged, at least
-    min_s of solo frames) are found on the device for the whole pack, cut into clips of at most max_clip_s, embedded with the identify
-    model (embed_ranges) and scored on the device: own, the cosine of the clip to the rest of its speaker, and rival, its best cosine to
-    another speaker of the recording.  A clip is a sample when own - rival >= min_margin (or when it is its speaker's only clip:
-    alone); per speaker the best max_clips of them, at most max_total_s in all, best first.  The (start_s, end_s) pairs can be passed
-    unchanged as segments= of enroll_speaker; embedding is the unit mean of the clip's windows (samples.py states the rule; parity with
-    other toolkits is unpinned)."""
-    import torch
-    from . import samples as sm
-    single = not isinstance(results, (list, tuple))
-    results = [results] if single else list(results)
-    recs = [samples_or_paths] if single else list(samples_or_paths)
-    if len(recs) != len(results):
-        raise ValueError(f"speaker_samples: {len(recs)} recordings for {len(results)} results")
-    if not results:
-        return []
-    eng = be.engine()
-    recs = [decode_to_profile(Path(x), eng, be.get_audio_profile()) if isinstance(x, (str, Path)) else np.asarray(x) for x in recs]
-    for r, (res, pcm) in enumerate(zip(results, recs)):
-        if len(res.speakers) != sm.global_frames(len(pcm)):
-            raise ValueError(f"speaker_samples: recording {r} has {len(pcm)} samples, its result {len(res.speakers)} frames")
-    rows = sm.runs(eng, results, min_s, max_gap_s)
-    clips, parts, counts = [], [], []
-    for r, pcm in enumerate(recs):
-        cl = sm.cut_clips(rows[r], len(pcm), max_clip_s, max_candidates)
-        n_win = np.zeros(len(cl), np.int64)
-        if len(cl):
-            E, _, _, wins, _ = be.embed_ranges(pcm, [(int(a) / sm.SAMPLE_RATE, int(b) / sm.SAMPLE_RATE) for a, b in cl[:, 1:3]])
-            if wins:                                                        # in range order: a clip's windows are adjacent rows
-                n_win = np.bincount([ri for ri, _, _ in wins], minlength=len(cl)).astype(np.int64)
-                parts.append(E)
-        clips.append(cl[n_win > 0])                                         # a clip embed_ranges dropped is not a sample
-        counts.append(n_win[n_win > 0])
-    out = [dict() for _ in results]
-    if parts:
-        E = torch.cat(parts) if len(parts) > 1 else parts[0]
-        clip_off = np.concatenate([[0], np.cumsum(np.concatenate(counts))])
-        spk_off = np.concatenate([[0], np.cumsum([max(int(res.n_speakers), 0) for res in results])])
-        clip_spk = np.concatenate([spk_off[r] + cl[:, 0] for r, cl in enumerate(clips)])
-        _, out_f, out_i = sm.score(eng, E, clip_off, clip_spk, spk_off)
-        off = sm.split_by_recording(clips)
-        for r, cl in enumerate(clips):
-            a, b = int(off[r]), int(off[r + 1])
-            picked = sm.select(cl, out_f[a:b, 0], out_f[a:b, 1], out_i[a:b, 2], max_clips, max_total_s, min_margin)
-            emb = np.zeros((len(cl), int(E.shape[1])), np.float32)
-            chosen = sorted(i for idx in picked.values() for i in idx)
-            if chosen:
-                emb[chosen] = sm.clip_embeddings(E, np.stack([clip_off[a:b][chosen], clip_off[a + 1:b + 1][chosen]], 1))
-            out[r] = sm.as_samples(r, cl, picked, out_f[a:b], out_i[a:b], emb)
-    return out[0] if single else out
-
-
-def write_samples(out_dir, samples, audio) -> List[Path]:
-    """One recording's samples ({speaker: [SpeakerSample]}, speaker_samples) and its audio (16 kHz mono int16) ->
-    <out_dir>/S<speaker + 1>/sample-NNN.wav (s16le mono 16 kHz) beside sample-NNN.json (the SpeakerSample fields without the embedding),
-    NNN from 001 in the order of the list; -> the WAV paths.  The toolkit's .meta.yaml provenance layout is not written."""
-    import json
-    import wave
-    from dataclasses import asdict
-    from .samples import SAMPLE_RATE
-    audio = np.ascontiguousarray(audio, dtype=np.int16).reshape(-1)
-    paths = []
-    for k in sorted(samples):
-        folder = Path(out_dir) / f"S{int(k) + 1}"
-        folder.mkdir(parents=True, exist_ok=True)
-        for n, s in enumerate(samples[k], 1):
-            a, b = int(round(s.start_s * SAMPLE_RATE)), int(round(s.end_s * SAMPLE_RATE))
-            if not 0 <= a < b <= audio.size:
-                raise ValueError(f"write_samples: speaker {k} sample {n} ({s.start_s} .. {s.end_s} s) lies outside the recording's {audio.size} samples")
-            path = folder / f"sample-{n:03d}.wav"
-            with wave.open(str(path), "wb") as w:
-                w.setnchannels(1)
-                w.setsampwidth(2)
-                w.setframerate(SAMPLE_RATE)
-                w.writeframes(audio[a:b].astype("<i2").tobytes())
-            meta = {key: val for key, val in asdict(s).items() if key != "embedding"}
-            path.with_suffix(".json").write_text(json.dumps(meta, indent=2) + "\n")
-            paths.append(path)
-    return paths
-
-
-def calibrate_verification(be: Backend, audio_paths, speaker_ids, candidates, out_path=None, score_range=None, p_target: float = 0.01,
-                           c_miss: float = 1.0, c_fa: float = 1.0, grad_tol: float = 1e-10, max_passes: int = 24, max_refine: int = 8):
-    """What a score of Backend `be`'s decision rule means, on a labelled development set (the arguments and the trials of
-    Backend.score_verification) -> trials.Calibration: the affine map llr = a * score + b fitted by prior-weighted logistic regression on the
-    device, Cllr before and after, the actual DCF at the Bayes threshold beside minDCF (trials.py states the rule; parity with outside
-    toolkits is unpinned).  out_path: the calibration is also written there (trials.save_calibration), the file SDK_SCORE_CALIBRATION names.
-    With a cohort configured (SDK_COHORT): ValueError - AS-norm trials are not built.  A fit that did not converge (separable classes have no
-    finite minimiser): ValueError.
-
-    A function of the Backend, not a method of it: the Backend's public surface is pinned name for name (tests/test_rules_cpu.py)."""
-    from . import trials
-    eng, tensors, kind = be._verification_trials("calibrate_verification", audio_paths, speaker_ids, candidates)
-    cal = trials.calibrate_scores(eng, *tensors, kind, score_range, p_target, c_miss, c_fa, grad_tol, max_passes, max_refine)
-    if not cal.converged:
-        raise ValueError(f"calibrate_verification: the fit did not converge in {cal.n_passes} passes (a={cal.a:g}, b={cal.b:g}, gradient {cal.grad}): "
-                         "classes that a threshold separates without error have no finite minimiser - use more, or harder, development trials")
-    if out_path is not None:
-        trials.save_calibration(cal, out_path)
-    return cal
-
-
-def _snorm_trials(be: Backend, who: str, audio_paths, speaker_ids, candidates, cohort, topk, score_range, p_target, c_miss, c_fa, max_refine):
-    """-> (trials.VerificationResult, the snorm.Cohort, the K its statistics were taken over)."""
-    from . import trials_snorm
-    from .rules import Cosine
-    from .snorm import Cohort
-    if be.lite:
-        raise ValueError(f"{who}: needs the torch engine; unset SDK_NO_TORCH")
-    co = be.cohort() if cohort is None else cohort if isinstance(cohort, Cohort) else Cohort.load(cohort, be.embedding_dim)
-    if co is None:
-        raise ValueError(f"{who}: no cohort: pass cohort= (a .npy path as SDK_COHORT names one, Backend.make_cohort writes it; or a snorm.Cohort) "
-                         "or configure SDK_COHORT")
-    if co.dim != int(be.embedding_dim):
-        raise ValueError(f"{who}: cohort {co.source}: rows of d={co.dim}, the model's embedding_dim is {int(be.embedding_dim)}")
-    K = min(int(be.cohort_topk if topk is None else topk), len(co))
-    if K < 1:
-        raise ValueError(f"{who}: topk={topk}: at least 1")
-    eng, E, speaker_ids, counts, batch = be._trial_windows(who, audio_paths, speaker_ids, candidates)
-    A, B, _, lb, _, index = Cosine().trial_matrices(be, E, batch)              # the cosine rule's matrices: windows against enrolled embeddings
-    la, sa, lb, sb = be._trial_labels(E.device, speaker_ids, counts, lb, index)
-    rows = co.device_rows(eng)
-    mean_a, inv_a = trials_snorm.cohort_statistics(eng, E, rows, K)
-    mean_b, inv_b = trials_snorm.cohort_statistics(eng, be.profile_tensors(batch)[0].contiguous(), rows, K)
-    res = trials_snorm.evaluate_snorm_scores(eng, A, B, mean_a, inv_a, mean_b, inv_b, la, sa, lb, sb, score_range, p_target, c_miss, c_fa, max_refine)
-    return res, co, K
-
-
-def score_verification_snorm(be: Backend, audio_paths, speaker_ids, candidates, cohort=None, topk=None, score_range=None, p_target: float = 0.01,
-                             c_miss: float = 1.0, c_fa: float = 1.0, max_refine: int = 8):
-    """Backend.score_verification on the AS-norm scale -> trials.VerificationResult with kind "snorm": how well the cohort-normalised decision
-    of identify_speaker / verify_speaker (SDK_COHORT) separates the enrolled speakers on labelled recordings.  The inputs and the trials are
-    those of Backend.score_verification under the cosine rule: every window of every recording is a test row, the model rows are the
-    candidates' enrolled embeddings (profile_tensors).  cohort: a .npy path (Backend.make_cohort writes one) or a snorm.Cohort; None: the
-    configured SDK_COHORT (ValueError when neither is given).  topk: the cohort scores per side that the statistics are taken over; None:
-    the backend's cohort_topk (SDK_COHORT_TOPK); min(topk, the cohort's rows) is used.  score_range defaults to trials_snorm.SNORM_RANGE.
-    Works on a Backend under the cosine rule and on one configured with SDK_COHORT; SDK_NO_TORCH=1 is refused.  trials_snorm.py states
-    the rule (parity with outside toolkits is unpinned).
-
-    A function of the Backend, not a method of it: the Backend's public surface is pinned name for name (tests/test_rules_cpu.py)."""
-    return _snorm_trials(be, "score_verification_snorm", audio_paths, speaker_ids, candidates, cohort, topk, score_range, p_target, c_miss, c_fa,
-                         max_refine)[0]
-
-
-def tune_cohort_threshold(be: Backend, audio_paths, speaker_ids, candidates, cohort=None, topk=None, score_range=None, p_target: float = 0.01,
-                          c_miss: float = 1.0, c_fa: float = 1.0, max_refine: int = 8) -> Dict[str, Any]:
-    """The thresholds of the AS-norm decision on a labelled development set (the arguments of score_verification_snorm) ->
-    Backend.tune_verification's dict with kind "snorm", plus "cohort_digest" (the content hash of the cohort the statistics came from) and
-    "topk" (the K used).  eer_threshold and min_dcf_threshold are on the z scale: they are what SDK_COHORT_THRESHOLD takes, for THIS cohort
-    and K.  The evaluation scores the float64 product of the fp32 unit rows and normalises it in float64; identify computes z from its
-    fp32 cosines and fp32 statistics.  The two agree to fp32 rounding times inv = 1 / std (a few 1e-7 of cosine, scaled by 1 / std), so
-    a window that close to the threshold may vote differently."""
-    res, co, K = _snorm_trials(be, "tune_cohort_threshold", audio_paths, speaker_ids, candidates, cohort, topk, score_range, p_target, c_miss, c_fa,
-                               max_refine)
-    return {"kind": res.kind, "eer": res.eer, "eer_threshold": res.eer_threshold, "min_dcf": res.min_dcf, "min_dcf_threshold": res.min_dcf_threshold,
-            "min_dcf_lower": res.min_dcf_lower, "min_dcf_exact": res.min_dcf_exact, "n_target": res.n_target, "n_nontarget": res.n_nontarget,
-            "n_nan": res.n_nan, "n_excluded": res.n_excluded, "n_test_rows": res.test_rows, "n_model_rows": res.model_rows, "score_range": res.score_range,
-            "result": res, "cohort_digest": co.digest, "topk": K}

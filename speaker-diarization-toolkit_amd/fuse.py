@@ -55,12 +55,15 @@ from __future__ import annotations
 import copy
 import numbers
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import TYPE_CHECKING, List, Optional, Sequence
 
 import numpy as np
 
 from .diarize_host import _speaker_cap, global_frames, turns_from_frames
 from .score import MAX_SCORE_SPEAKERS, assignment_host, prepare_reference
+
+if TYPE_CHECKING:
+    from .backend import Backend
 
 MAX_FUSE_HYPS = 8                # FUSE_MAX_HYPS of csrc/fuse.hip
 MAX_FUSE_SPEAKERS = MAX_SCORE_SPEAKERS   # speakers of a hypothesis, and fused labels of a recording (PG_MAX_SPK)
@@ -618,3 +621,52 @@ def compare(eng, a, b, n_samples=None) -> List[dict]:
                     "sum_max": smax, "sum_min": smin, "correct": correct, "disagreement": (smax - correct) / smax if smax else 0.0,
                     "unanimous": int(out["tallies"][r][2])})
     return res
+
+
+# ---- fusing several diarizations of a recording.  Functions of a Backend (backend.py), not methods of it: the class keeps its public names;
+#      backend.py imports them, so callers reach them as backend.fuse_diarizations and so on.
+def _per_recording(x) -> bool:
+    """True where x is a list over recordings, False where it is one hypothesis (a result, or a non-empty turn list)."""
+    from .fuse import is_hypothesis
+    return not (is_hypothesis(x) and not (isinstance(x, (list, tuple)) and len(x) == 0))
+
+
+def fuse_diarizations(be: Backend, hypotheses, n_samples=None, weights=None, max_speakers=None):
+    """Several diarizations of the same recordings combined into one each, DOVER-Lap's way: hypotheses[r] = the H (2 .. 8) answers for
+    recording r, each a diarize.DiarizationResult (of diarize / diarize_many under different models, clusterings or thresholds) or a turn
+    list [(start_s, end_s, name)] (an outside diarizer's; then n_samples, the recordings' lengths, fixes the frame grid where no result
+    does).  The speakers of the hypotheses are mapped onto common labels through their pairwise co-occurrence, starting from the hypothesis
+    that agrees most with the others; the hypotheses are weighted by their rank in mean disagreement (or by weights=, H integers in
+    1 .. 65536) and every frame is voted, the number of speakers from the weighted mean count (at most 2, fewer with max_speakers).  -> one
+    result per recording: the anchor's result copied (else a fuse.FusedDiarization) with speakers, turns and n_speakers replaced and
+    `fusion` = {order, weights, dis, label_of, speech, overlap, unanimous, overflow}.  One upload, the device calls and one download for
+    the whole list (fuse.py states the rule; parity with DOVER-Lap is unpinned)."""
+    from .fuse import fuse_results
+    return fuse_results(be.engine(), list(hypotheses), n_samples, weights, max_speakers)
+
+
+def compare_diarizations(be: Backend, a, b, n_samples=None):
+    """Two diarizations of the same recording laid side by side: a and b are one hypothesis each (as fuse_diarizations takes them), or
+    lists of them, one per recording -> per recording a dict of co [K_a, K_b] (the frames speaker i of a shares with speaker j of b), mapping
+    (b's speaker for each of a's under an optimal assignment), names_a, names_b, sum_max, sum_min, correct, disagreement = (sum_max -
+    correct) / sum_max - the symmetric diarization error of one against the other, 0.0 for two silent answers - and unanimous, the frames
+    on which they agree.  A single pair gives a single dict."""
+    from .fuse import compare
+    single = not _per_recording(a)
+    if single:
+        a, b = [a], [b]
+        n_samples = None if n_samples is None else [n_samples]
+    out = compare(be.engine(), a, b, n_samples)
+    return out[0] if single else out
+
+
+def diarize_fused(be: Backend, samples_or_path, variants, **fuse_kw):
+    """diarize once per keyword set of `variants` (for example [{"clustering": "ahc"}, {"clustering": "vbx", "threshold": 0.6},
+    {"clustering": "nmesc"}]) and the results fused (fuse_diarizations; fuse_kw: weights, max_speakers) -> the fused result.  Every
+    variant runs the whole pipeline: the embedding pass is not shared between them."""
+    variants = [dict(v) for v in variants]
+    from .fuse import MAX_FUSE_HYPS
+    if not 2 <= len(variants) <= MAX_FUSE_HYPS:
+        raise ValueError(f"diarize_fused: {len(variants)} variants (2 .. {MAX_FUSE_HYPS})")
+    samples, = be._recordings([samples_or_path])                 # a path is decoded once, not per variant
+    return fuse_diarizations(be, [[be.diarize(samples, **v) for v in variants]], **fuse_kw)[0]

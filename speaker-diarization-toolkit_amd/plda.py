@@ -369,3 +369,16 @@ def fit(provider, E, labels, D0: int = 128, lda_dim: int = 128, n_iters: int = 1
 
     total0 = provider.plda_fit_stats(E, scatter=False)["total"].cpu().numpy()
     return fit_from_stats(total0, stats1, stats2, N, D0, lda_dim, n_iters)
+
+
+def plda_classes(recording, speaker, names, uris, speaker_key):
+    """The class of every labelled row of Diarizer.plda_rows: (uri, reference name), numbered by first appearance, unless
+    speaker_key(uri, name) maps several to one key; uri is the recording's entry of `uris`, else its index -> (labels int32, keys)."""
+    keys: dict = {}
+    labels = np.zeros(len(speaker), np.int32)
+    for j, (r, s) in enumerate(zip(recording, speaker)):
+        uri = uris[int(r)] if uris is not None else int(r)
+        name = names[int(r)][int(s)]
+        key = speaker_key(uri, name) if speaker_key is not None else (uri, name)
+        labels[j] = keys.setdefault(key, len(keys))
+    return labels, list(keys)

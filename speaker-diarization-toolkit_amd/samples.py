@@ -42,13 +42,17 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence
+from pathlib import Path
+from typing import TYPE_CHECKING, Dict, List, Optional, Sequence
 
 import numpy as np
 
 from .diarize_host import global_frames
 from .segmentation import FRAME_HOP, SAMPLE_RATE
 from .words import MAX_WORD_SPEAKERS, gap_frames
+
+if TYPE_CHECKING:
+    from .backend import Backend
 
 DEFAULT_MIN_S = 0.5
 DEFAULT_MAX_GAP_S = 1.0
@@ -304,3 +308,90 @@ def as_samples(recording: int, clips, picked: Dict[int, List[int]], out_f, out_i
 def split_by_recording(tables: Sequence[np.ndarray]) -> np.ndarray:
     """[R] arrays -> the [R + 1] prefix sums of their lengths."""
     return np.concatenate([[0], np.cumsum([len(t) for t in tables])]).astype(np.int64)
+
+
+# ---- the pipeline on a Backend (backend.py).  Functions of it, not methods: its public surface is pinned name for name; backend.py imports
+#      them, so callers reach them as backend.speaker_samples and backend.write_samples.
+def speaker_samples(be: Backend, results, samples_or_paths, min_s: float = 0.5, max_gap_s: float = 1.0, max_clip_s=None, max_candidates=None,
+                    max_clips=None, max_total_s=None, min_margin: float = 0.0):
+    """Which stretches of audio of each diarized speaker are clean enough to listen to and to enrol from: the results of diarize /
+    diarize_many and their recordings (16 kHz mono int16 samples, or paths of audio files) -> one {speaker: [samples.SpeakerSample]} per
+    recording, a single dict for a single result.  A speaker's runs of solo frames (no overlap, pauses up to max_gap_s bridged, at least
+    min_s of solo frames) are found on the device for the whole pack, cut into clips of at most max_clip_s, embedded with the identify
+    model (embed_ranges) and scored on the device: own, the cosine of the clip to the rest of its speaker, and rival, its best cosine to
+    another speaker of the recording.  A clip is a sample when own - rival >= min_margin (or when it is its speaker's only clip:
+    alone); per speaker the best max_clips of them, at most max_total_s in all, best first.  The (start_s, end_s) pairs can be passed
+    unchanged as segments= of enroll_speaker; embedding is the unit mean of the clip's windows (samples.py states the rule; parity with
+    other toolkits is unpinned)."""
+    import torch
+    from . import samples as sm
+    single = not isinstance(results, (list, tuple))
+    results = [results] if single else list(results)
+    recs = [samples_or_paths] if single else list(samples_or_paths)
+    if len(recs) != len(results):
+        raise ValueError(f"speaker_samples: {len(recs)} recordings for {len(results)} results")
+    if not results:
+        return []
+    eng = be.engine()
+    recs = [np.asarray(x) for x in be._recordings(recs)]
+    for r, (res, pcm) in enumerate(zip(results, recs)):
+        if len(res.speakers) != sm.global_frames(len(pcm)):
+            raise ValueError(f"speaker_samples: recording {r} has {len(pcm)} samples, its result {len(res.speakers)} frames")
+    rows = sm.runs(eng, results, min_s, max_gap_s)
+    clips, parts, counts = [], [], []
+    for r, pcm in enumerate(recs):
+        cl = sm.cut_clips(rows[r], len(pcm), max_clip_s, max_candidates)
+        n_win = np.zeros(len(cl), np.int64)
+        if len(cl):
+            E, _, _, wins, _ = be.embed_ranges(pcm, [(int(a) / sm.SAMPLE_RATE, int(b) / sm.SAMPLE_RATE) for a, b in cl[:, 1:3]])
+            if wins:                                                        # in range order: a clip's windows are adjacent rows
+                n_win = np.bincount([ri for ri, _, _ in wins], minlength=len(cl)).astype(np.int64)
+                parts.append(E)
+        clips.append(cl[n_win > 0])                                         # a clip embed_ranges dropped is not a sample
+        counts.append(n_win[n_win > 0])
+    out = [dict() for _ in results]
+    if parts:
+        E = torch.cat(parts) if len(parts) > 1 else parts[0]
+        clip_off = np.concatenate([[0], np.cumsum(np.concatenate(counts))])
+        spk_off = np.concatenate([[0], np.cumsum([max(int(res.n_speakers), 0) for res in results])])
+        clip_spk = np.concatenate([spk_off[r] + cl[:, 0] for r, cl in enumerate(clips)])
+        _, out_f, out_i = sm.score(eng, E, clip_off, clip_spk, spk_off)
+        off = sm.split_by_recording(clips)
+        for r, cl in enumerate(clips):
+            a, b = int(off[r]), int(off[r + 1])
+            picked = sm.select(cl, out_f[a:b, 0], out_f[a:b, 1], out_i[a:b, 2], max_clips, max_total_s, min_margin)
+            emb = np.zeros((len(cl), int(E.shape[1])), np.float32)
+            chosen = sorted(i for idx in picked.values() for i in idx)
+            if chosen:
+                emb[chosen] = sm.clip_embeddings(E, np.stack([clip_off[a:b][chosen], clip_off[a + 1:b + 1][chosen]], 1))
+            out[r] = sm.as_samples(r, cl, picked, out_f[a:b], out_i[a:b], emb)
+    return out[0] if single else out
+
+
+def write_samples(out_dir, samples, audio) -> List[Path]:
+    """One recording's samples ({speaker: [SpeakerSample]}, speaker_samples) and its audio (16 kHz mono int16) ->
+    <out_dir>/S<speaker + 1>/sample-NNN.wav (s16le mono 16 kHz) beside sample-NNN.json (the SpeakerSample fields without the embedding),
+    NNN from 001 in the order of the list; -> the WAV paths.  The toolkit's .meta.yaml provenance layout is not written."""
+    import json
+    import wave
+    from dataclasses import asdict
+    from .samples import SAMPLE_RATE
+    audio = np.ascontiguousarray(audio, dtype=np.int16).reshape(-1)
+    paths = []
+    for k in sorted(samples):
+        folder = Path(out_dir) / f"S{int(k) + 1}"
+        folder.mkdir(parents=True, exist_ok=True)
+        for n, s in enumerate(samples[k], 1):
+            a, b = int(round(s.start_s * SAMPLE_RATE)), int(round(s.end_s * SAMPLE_RATE))
+            if not 0 <= a < b <= audio.size:
+                raise ValueError(f"write_samples: speaker {k} sample {n} ({s.start_s} .. {s.end_s} s) lies outside the recording's {audio.size} samples")
+            path = folder / f"sample-{n:03d}.wav"
+            with wave.open(str(path), "wb") as w:
+                w.setnchannels(1)
+                w.setsampwidth(2)
+                w.setframerate(SAMPLE_RATE)
+                w.writeframes(audio[a:b].astype("<i2").tobytes())
+            meta = {key: val for key, val in asdict(s).items() if key != "embedding"}
+            path.with_suffix(".json").write_text(json.dumps(meta, indent=2) + "\n")
+            paths.append(path)
+    return paths

@@ -59,13 +59,16 @@ from __future__ import annotations
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import TYPE_CHECKING, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from .diarize_host import global_frames
 from .diarize_ops import GroupTables, _check_tensor, _native
 from .segmentation import FRAME_FIRST, FRAME_HOP, SAMPLE_RATE   # FRAME_FIRST is re-exported: words.py reads it here
+
+if TYPE_CHECKING:
+    from .backend import Backend
 
 MAX_SCORE_SPEAKERS = 64
 _INF = 1 << 62
@@ -635,3 +638,16 @@ def score_results(eng, results, references, collar_s: float = 0.0, skip_overlap:
     tab = GroupTables(eng, np.zeros(len(results) + 1, np.int64), np.concatenate([[0], np.cumsum(G_r)]), n_samples)
     tab.set_clusters(np.concatenate([[0], np.cumsum([int(res.n_speakers) for res in results])]))
     return score_grouped(eng, torch.from_numpy(np.concatenate(spk)).to(eng.device), tab, references, collar_s, skip_overlap, uems, jer)
+
+
+# ---- scoring the DIHARD way.  A function of a Backend (backend.py), not a method of it: Backend.score_diarization keeps its signature;
+#      backend.py imports it, so callers reach it as backend.score_diarization_uem.
+def score_diarization_uem(be: Backend, results, references, uris=None, collar_s: float = 0.0, skip_overlap: bool = False, uem=None, jer: bool = False):
+    """Backend.score_diarization with an evaluation map and the Jaccard error rate.  uem: the map outside which nothing is scored - one
+    entry per result (None, or a list of (start_s, end_s)), or the path or text of a UEM file (or {uri: intervals}) read with `uris`; a
+    uri it does not hold is scored everywhere.  jer=True: every score.DerResult carries the Jaccard error rate (jer, jsum, ref_speakers,
+    ref_frames, hyp_frames, jer_mapping), purity and coverage beside the DER; score.pool(list) pools them too.  With uem=None and
+    jer=False it is score_diarization.  Backend.tune_diarization takes the same two keywords, and metric="jer"."""
+    results = list(results)
+    return be.diarizer().score(results, be._references("score_diarization_uem", references, uris, len(results)), collar_s, skip_overlap,
+                               uem=uem, jer=jer, uris=uris)

@@ -37,13 +37,16 @@ waits for the device.  smooth_host restates it in numpy, speaker by speaker.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple
+from typing import TYPE_CHECKING, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from .samples import _seconds_to_samples
 from .segmentation import FRAME_HOP
 from .words import gap_frames
+
+if TYPE_CHECKING:
+    from .backend import Backend
 
 MAX_SMOOTH_FRAMES = 1024         # the longest fill and keep, in frames (SMT_MAX_FRAMES of csrc/smooth.hip): 1024 * 270 / 16000 = 17.28 s
 SMOOTH_BLOCK_FRAMES = 256        # the packed frames one workgroup of sdk_smooth_turns serves (SMT_NT); the walks read across its edges from memory
@@ -225,3 +228,19 @@ def smooth_results(eng, results: Sequence, min_duration_off: float = 0.0, min_du
         new.smoothing = smoothing_fields(min_duration_off, min_duration_on, fill, keep, tl[r])
         out.append(new)
     return out
+
+
+# ---- smoothing finished results.  A function of a Backend (backend.py), not a method of it (its public surface is pinned name for name);
+#      backend.py imports it, so callers reach it as backend.smooth_diarization.
+def smooth_diarization(be: Backend, results, min_duration_off: float = 0.0, min_duration_on: float = 0.0, max_speakers=None):
+    """The results of diarize / diarize_many / a closed stream with their turns smoothed: a speaker's pauses no longer than
+    min_duration_off seconds are filled (where the frame has a free slot: at most 2 speakers per frame, fewer with max_speakers, and a
+    speaker the diarization put there is never displaced), then the turns shorter than min_duration_on seconds are dropped - PyAnnote's
+    Binarize hyper-parameters, in its order.  -> copies of the results with speakers, turns and smoothing ({min_duration_off,
+    min_duration_on, fill, keep, filled, dropped}) replaced; everything else, count included, is what it was.  One upload, one launch
+    sequence (sdk_smooth_turns) and one download for the whole list; a single result gives a single result.  diarize(min_duration_off=,
+    min_duration_on=) does the same before the table comes down (smooth.py states the rule; parity with PyAnnote is unpinned)."""
+    from .smooth import smooth_results
+    single = not isinstance(results, (list, tuple))
+    out = smooth_results(be.engine(), [results] if single else list(results), min_duration_off, min_duration_on, max_speakers)
+    return out[0] if single else out

@@ -79,9 +79,12 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
-from typing import Any, Callable, Dict, NamedTuple, Optional, Tuple
+from typing import TYPE_CHECKING, Any, Callable, Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
+
+if TYPE_CHECKING:
+    from .backend import Backend
 
 BINS = 4096
 Q_BITS = 24
@@ -771,3 +774,33 @@ def calibrate(engine, E_test, labels, sessions, E_model, model_labels, model_ses
     """evaluate's trials (the same arguments, the same matrices: trial_tensors) -> their Calibration."""
     tensors = trial_tensors(engine, E_test, labels, sessions, E_model, model_labels, model_sessions, kind, plda, count_by_book)
     return calibrate_scores(engine, *tensors, kind, score_range, p_target, c_miss, c_fa, grad_tol, max_passes, max_refine, max_blocks)
+
+
+def summary(res: VerificationResult) -> Dict[str, Any]:
+    """The dict Backend.tune_verification and tune_cohort_threshold answer with: a VerificationResult's figures by name, and itself."""
+    return {"kind": res.kind, "eer": res.eer, "eer_threshold": res.eer_threshold, "min_dcf": res.min_dcf, "min_dcf_threshold": res.min_dcf_threshold,
+            "min_dcf_lower": res.min_dcf_lower, "min_dcf_exact": res.min_dcf_exact, "n_target": res.n_target, "n_nontarget": res.n_nontarget,
+            "n_nan": res.n_nan, "n_excluded": res.n_excluded, "n_test_rows": res.test_rows, "n_model_rows": res.model_rows, "score_range": res.score_range,
+            "result": res}
+
+
+def calibrate_verification(be: Backend, audio_paths, speaker_ids, candidates, out_path=None, score_range=None, p_target: float = 0.01,
+                           c_miss: float = 1.0, c_fa: float = 1.0, grad_tol: float = 1e-10, max_passes: int = 24, max_refine: int = 8):
+    """What a score of Backend `be`'s decision rule means, on a labelled development set (the arguments and the trials of
+    Backend.score_verification) -> trials.Calibration: the affine map llr = a * score + b fitted by prior-weighted logistic regression on the
+    device, Cllr before and after, the actual DCF at the Bayes threshold beside minDCF (trials.py states the rule; parity with outside
+    toolkits is unpinned).  out_path: the calibration is also written there (trials.save_calibration), the file SDK_SCORE_CALIBRATION names.
+    With a cohort configured (SDK_COHORT): ValueError - AS-norm trials are not built.  A fit that did not converge (separable classes have no
+    finite minimiser): ValueError.
+
+    A function of the Backend (backend.py, which imports it: backend.calibrate_verification), not a method of it: the Backend's public
+    surface is pinned name for name (tests/test_rules_cpu.py)."""
+    from . import trials
+    eng, tensors, kind = be._verification_trials("calibrate_verification", audio_paths, speaker_ids, candidates)
+    cal = trials.calibrate_scores(eng, *tensors, kind, score_range, p_target, c_miss, c_fa, grad_tol, max_passes, max_refine)
+    if not cal.converged:
+        raise ValueError(f"calibrate_verification: the fit did not converge in {cal.n_passes} passes (a={cal.a:g}, b={cal.b:g}, gradient {cal.grad}): "
+                         "classes that a threshold separates without error have no finite minimiser - use more, or harder, development trials")
+    if out_path is not None:
+        trials.save_calibration(cal, out_path)
+    return cal

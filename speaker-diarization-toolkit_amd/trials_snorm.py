@@ -26,12 +26,15 @@ neither torch nor the library at module level.
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import TYPE_CHECKING, Any, Dict, Optional, Tuple
 
 import numpy as np
 
 from . import trials
 from .trials import BINS, COARSE_SHIFT, PassCounts, VerificationResult
+
+if TYPE_CHECKING:
+    from .backend import Backend
 
 SNORM_RANGE = (-64.0, 64.0)
 STATS_BLOCK = 65536                # rows per Engine.cohort_stats call
@@ -114,3 +117,61 @@ def evaluate_snorm(engine, E_test, labels, sessions, E_model, model_labels, mode
     mean_b, inv_b = cohort_statistics(engine, E_model.contiguous(), cohort_rows, int(topk))
     return evaluate_snorm_scores(engine, A, B, mean_a, inv_a, mean_b, inv_b, la, sa, lb, sb, score_range, p_target, c_miss, c_fa, max_refine,
                                  max_blocks)
+
+
+# ---- the trials of a Backend (backend.py).  Functions of it, not methods: its public surface is pinned name for name
+#      (tests/test_rules_cpu.py); backend.py imports them, so callers reach them as backend.tune_cohort_threshold and so on.
+def _snorm_trials(be: Backend, who: str, audio_paths, speaker_ids, candidates, cohort, topk, score_range, p_target, c_miss, c_fa, max_refine):
+    """-> (trials.VerificationResult, the snorm.Cohort, the K its statistics were taken over)."""
+    from . import trials_snorm
+    from .rules import Cosine
+    from .snorm import Cohort
+    if be.lite:
+        raise ValueError(f"{who}: needs the torch engine; unset SDK_NO_TORCH")
+    co = be.cohort() if cohort is None else cohort if isinstance(cohort, Cohort) else Cohort.load(cohort, be.embedding_dim)
+    if co is None:
+        raise ValueError(f"{who}: no cohort: pass cohort= (a .npy path as SDK_COHORT names one, Backend.make_cohort writes it; or a snorm.Cohort) "
+                         "or configure SDK_COHORT")
+    if co.dim != int(be.embedding_dim):
+        raise ValueError(f"{who}: cohort {co.source}: rows of d={co.dim}, the model's embedding_dim is {int(be.embedding_dim)}")
+    K = min(int(be.cohort_topk if topk is None else topk), len(co))
+    if K < 1:
+        raise ValueError(f"{who}: topk={topk}: at least 1")
+    eng, E, speaker_ids, counts, batch = be._trial_windows(who, audio_paths, speaker_ids, candidates)
+    A, B, _, lb, _, index = Cosine().trial_matrices(be, E, batch)              # the cosine rule's matrices: windows against enrolled embeddings
+    la, sa, lb, sb = be._trial_labels(E.device, speaker_ids, counts, lb, index)
+    rows = co.device_rows(eng)
+    mean_a, inv_a = trials_snorm.cohort_statistics(eng, E, rows, K)
+    mean_b, inv_b = trials_snorm.cohort_statistics(eng, be.profile_tensors(batch)[0].contiguous(), rows, K)
+    res = trials_snorm.evaluate_snorm_scores(eng, A, B, mean_a, inv_a, mean_b, inv_b, la, sa, lb, sb, score_range, p_target, c_miss, c_fa, max_refine)
+    return res, co, K
+
+
+def score_verification_snorm(be: Backend, audio_paths, speaker_ids, candidates, cohort=None, topk=None, score_range=None, p_target: float = 0.01,
+                             c_miss: float = 1.0, c_fa: float = 1.0, max_refine: int = 8):
+    """Backend.score_verification on the AS-norm scale -> trials.VerificationResult with kind "snorm": how well the cohort-normalised decision
+    of identify_speaker / verify_speaker (SDK_COHORT) separates the enrolled speakers on labelled recordings.  The inputs and the trials are
+    those of Backend.score_verification under the cosine rule: every window of every recording is a test row, the model rows are the
+    candidates' enrolled embeddings (profile_tensors).  cohort: a .npy path (Backend.make_cohort writes one) or a snorm.Cohort; None: the
+    configured SDK_COHORT (ValueError when neither is given).  topk: the cohort scores per side that the statistics are taken over; None:
+    the backend's cohort_topk (SDK_COHORT_TOPK); min(topk, the cohort's rows) is used.  score_range defaults to trials_snorm.SNORM_RANGE.
+    Works on a Backend under the cosine rule and on one configured with SDK_COHORT; SDK_NO_TORCH=1 is refused.  trials_snorm.py states
+    the rule (parity with outside toolkits is unpinned).
+
+    A function of the Backend (backend.py, which imports it: backend.score_verification_snorm), not a method of it: the Backend's public
+    surface is pinned name for name (tests/test_rules_cpu.py)."""
+    return _snorm_trials(be, "score_verification_snorm", audio_paths, speaker_ids, candidates, cohort, topk, score_range, p_target, c_miss, c_fa,
+                         max_refine)[0]
+
+
+def tune_cohort_threshold(be: Backend, audio_paths, speaker_ids, candidates, cohort=None, topk=None, score_range=None, p_target: float = 0.01,
+                          c_miss: float = 1.0, c_fa: float = 1.0, max_refine: int = 8) -> Dict[str, Any]:
+    """The thresholds of the AS-norm decision on a labelled development set (the arguments of score_verification_snorm) ->
+    Backend.tune_verification's dict with kind "snorm", plus "cohort_digest" (the content hash of the cohort the statistics came from) and
+    "topk" (the K used).  eer_threshold and min_dcf_threshold are on the z scale: they are what SDK_COHORT_THRESHOLD takes, for THIS cohort
+    and K.  The evaluation scores the float64 product of the fp32 unit rows and normalises it in float64; identify computes z from its
+    fp32 cosines and fp32 statistics.  The two agree to fp32 rounding times inv = 1 / std (a few 1e-7 of cosine, scaled by 1 / std), so
+    a window that close to the threshold may vote differently."""
+    res, co, K = _snorm_trials(be, "tune_cohort_threshold", audio_paths, speaker_ids, candidates, cohort, topk, score_range, p_target, c_miss, c_fa,
+                               max_refine)
+    return dict(trials.summary(res), cohort_digest=co.digest, topk=K)

@@ -43,13 +43,16 @@ from __future__ import annotations
 import copy
 import math
 from dataclasses import dataclass
-from typing import Any, Dict, List, Optional, Sequence, Tuple
+from typing import TYPE_CHECKING, Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from .score import FRAME_FIRST, MAX_SCORE_SPEAKERS, _check_counts, _first_frame, assignment_host
 from .segmentation import FRAME_HOP, SAMPLE_RATE
 from .segments import UNKNOWN_SPEAKER, detect_transcript_format
+
+if TYPE_CHECKING:
+    from .backend import Backend
 
 MAX_WORD_SPEAKERS = 1024
 DEFAULT_MAX_GAP_S = 0.5
@@ -459,3 +462,55 @@ def attributed_sentences(data: Dict[str, Any], rows) -> List[Dict[str, Any]]:
     if cur is not None:
         out.append(cur)
     return out
+
+
+# ---- the functions of a Backend (backend.py) on words: not methods of it, whose public surface is pinned name for name
+#      (tests/test_rules_cpu.py); backend.py imports them, so callers reach them as backend.attribute_transcripts and so on.
+def attribute_transcripts(be: Backend, results, transcripts, max_gap_s: float = 0.5, names=None):
+    """Who said which word: the results of diarize / diarize_many / a finished stream and one word-timed transcript per result (dicts in
+    the Speechmatics, AssemblyAI or OpenAI verbose_json layout; the speakers they carry are not read) -> a list of (relabelled, rows):
+    the transcript relabelled in its own layout (OpenAI: in the Speechmatics layout) with speaker k as "S<k+1>", or names[k], or "UU"
+    for a word nobody is near, and rows [W, 8] int32 per word (speaker, votes, solo, span, second, second_votes, distance, g0).  A word
+    goes to the speaker active in most of its frames; a word in non-speech to the nearest voiced frame within max_gap_s.  All words of
+    all recordings are attributed in one launch on the device (words.py states the rule; parity with other toolkits is unpinned).
+    relabelled feeds segments.sentence_segments, extract_segments_as_tuples and assign.py; words.attributed_sentences(transcript,
+    rows) gives the sentences with their text."""
+    from . import words as wd
+    results, transcripts = list(results), list(transcripts)
+    if len(transcripts) != len(results):
+        raise ValueError(f"attribute_transcripts: {len(transcripts)} transcripts for {len(results)} recordings")
+    if not results:
+        return []
+    labels = wd.attribute(be.engine(), results, [wd.transcript_words(t) for t in transcripts], max_gap_s)
+    return [(wd.relabel_transcript(t, lab.rows, names), lab.rows) for t, lab in zip(transcripts, labels)]
+
+
+def attribute_transcript(be: Backend, result, transcript, max_gap_s: float = 0.5, names=None):
+    """attribute_transcripts for one recording -> (relabelled, rows)."""
+    return attribute_transcripts(be, [result], [transcript], max_gap_s, names)[0]
+
+
+def diarize_transcript(be: Backend, samples_or_path, transcript, max_gap_s: float = 0.5, names=None, **diarize_keywords):
+    """diarize, then attribute_transcript: a recording and its word-timed transcript (say OpenAI/Whisper verbose_json, which has no
+    speakers) -> (relabelled, rows, result): the transcript with a speaker on every word, the words' rows and the
+    diarize.DiarizationResult they were read from.  diarize_keywords: those of diarize."""
+    result = be.diarize(samples_or_path, **diarize_keywords)
+    relabelled, rows = attribute_transcript(be, result, transcript, max_gap_s, names)
+    return relabelled, rows, result
+
+
+def score_words(be: Backend, results, transcripts, max_gap_s: float = 0.5):
+    """How good the attribution is: the word-level diarization error rate (WDER) of attribute_transcripts against the speakers the
+    transcripts already carry -> (a list of words.WderResult (scored, unassigned, words, correct, wder, mapping, co), the pooled
+    WderResult).  A word is scored when the transcript gives it a speaker other than "UU"; the hypothesis speakers are mapped onto the
+    reference's by the exact maximum-weight assignment, and a scored word without a speaker is an error.  Attributed and scored on
+    the device in one pack (words.py states the rule; parity with other toolkits is unpinned)."""
+    from . import words as wd
+    results, transcripts = list(results), list(transcripts)
+    if len(transcripts) != len(results):
+        raise ValueError(f"score_words: {len(transcripts)} transcripts for {len(results)} recordings")
+    if not results:
+        return [], wd.pool([])
+    words = [wd.transcript_words(t) for t in transcripts]
+    per = wd.wder(be.engine(), results, words, [[w[3] for w in ws] for ws in words], max_gap_s)
+    return per, wd.pool(per)
