@@ -1233,9 +1233,23 @@ int sdk_stream_centroids(sdk_ctx* ctx, const void* state, int64_t state_bytes, i
  *                              for e = rev_off[i] .. rev_off[i + 1] - 1 with rev_rank[e] < p, j = rev_src[e]:  s = s + dinv[j] * X[j][c]
  *                      Y[i][c] = (float)(0.5 * (X[i][c] + dinv[i] * s))
  *                    No atomics: one thread owns an element of Y.
- *   Refusals (a null pointer, n, d, P other than min(64, n - 1), p outside 1 .. P, kv, a short or misaligned workspace) return non-zero,
- *   name the value in sdk_last_error() and launch nothing. */
+ *   sdk_knn_rows_fused  the lists of a MULTI-SCALE affinity (cluster.nmesc_multiscale): E_all fp32 [n_all][d] holds the unit rows of every scale
+ *                    stacked, 1 <= n_all <= 8 * 65536; maps int32 [S][n] (device), 1 <= S <= 8, names for base row i and scale s its row
+ *                    maps[s][i] of E_all; weights float64 [S] is HOST memory (read before the call returns).  For base rows i != j,
+ *                    c_s(i, j) is sdk_knn_rows' cosine of the rows maps[s][i] and maps[s][j] (the same chain, so equal row pairs give
+ *                    equal bits), and
+ *                      f = 0;  for s = 0 .. S - 1:  f = f + weights[s] * c_s(i, j)      (float64, the product and the sum each rounded once)
+ *                    idx / cosv [n][P] are row i's P rows j != i of largest f, ties to the lower j, and their f; a NaN f ranks, and is
+ *                    stored, as -inf.  With S = 1, weight 1.0 and the identity map the outputs are sdk_knn_rows' bit for bit.
+ *                    status int32 [4]: the rows of E_all that hold a non-finite value AND that a map entry names, and the lowest of
+ *                    them (INT_MAX: none); the map entries outside [0, n_all), and the lowest base row i that has one (INT_MAX: none).
+ *                    Nothing is read through such an entry (its row counts as zeros) and the lists of that call are not to be trusted.
+ *                    No floating-point atomics, one owner per output element.
+ *   Refusals (a null pointer, n, d, P other than min(64, n - 1), p outside 1 .. P, kv, S, n_all, a short or misaligned workspace) return
+ *   non-zero, name the value in sdk_last_error() and launch nothing. */
 int sdk_knn_rows(sdk_ctx* ctx, const float* E, int n, int d, int P, int32_t* idx, double* cosv, int32_t* status, void* stream);
+int sdk_knn_rows_fused(sdk_ctx* ctx, const float* E_all, int n_all, int d, const int32_t* maps, const double* weights, int S, int n, int P,
+                       int32_t* idx, double* cosv, int32_t* status, void* stream);
 size_t sdk_knn_reverse_workspace_bytes(int n, int P);
 int sdk_knn_reverse(sdk_ctx* ctx, const int32_t* idx, int n, int P, int32_t* rev_off, int32_t* rev_src, int32_t* rev_rank, int32_t* status,
                     void* workspace, size_t ws_bytes, void* stream);

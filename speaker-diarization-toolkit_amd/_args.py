@@ -115,6 +115,31 @@ def knn_lists(who: str, idx):
     return n, P
 
 
+KNN_MAX_SCALES = 8     # KNN_MAX_SCALES of csrc/nmesc.hip: the scales of one fused affinity
+
+
+def knn_maps(who: str, maps):
+    """The maps of a fused affinity: int32 [S, n], 1 <= S <= KNN_MAX_SCALES, n a neighbour graph's rows -> (S, n, P)."""
+    S, n = (int(v) for v in tensor(who, "maps", maps, "int32", (None, None)).shape)
+    if not 1 <= S <= KNN_MAX_SCALES:
+        raise ValueError(f"{who}: maps must be [S, n] with S in 1..{KNN_MAX_SCALES}, got {list(maps.shape)}")
+    return S, n, knn_shape(who, n)
+
+
+def knn_weights(who: str, weights, S: int):
+    """The scale weights of a fused affinity: S host numbers, finite, >= 0, not all zero -> a list of S floats, as given (the caller
+    normalises: cluster.nmesc_multiscale)."""
+    try:
+        w = [float(v) for v in weights]
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: weights must be {S} host numbers, got {weights!r}") from None
+    if len(w) != S or any(isinstance(v, bool) for v in weights):
+        raise ValueError(f"{who}: weights must be {S} host numbers (one per scale), got {weights!r}")
+    if not all(0.0 <= v < float("inf") for v in w) or not any(v > 0.0 for v in w):       # a NaN fails the comparison
+        raise ValueError(f"{who}: weights={w} (finite, >= 0, not all zero)")
+    return w
+
+
 def knn_p(who: str, p, P: int) -> None:
     """The neighbours kept of a list of P: an integer (no bool), 1 <= p <= P."""
     if isinstance(p, bool) or not isinstance(p, numbers.Integral) or not 1 <= p <= P:      # numpy's integers are Integral, its bool_ is not

@@ -245,6 +245,7 @@ SIGNATURES = {
     "sdk_stream_flush": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "sdk_stream_centroids": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "sdk_knn_rows": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "sdk_knn_rows_fused": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "sdk_knn_reverse_workspace_bytes": (_sz, [_i, _i]),
     "sdk_knn_reverse": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "sdk_knn_degree": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

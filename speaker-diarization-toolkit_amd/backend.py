@@ -84,6 +84,7 @@ from .weights import weights_digest
 # Functions that take a Backend and are not methods of it (its public surface is pinned name for name, tests/test_rules_cpu.py): each lives
 # with its subject and is importable from here, where callers and messages name it.
 from .fuse import _per_recording, compare_diarizations, diarize_fused, fuse_diarizations  # noqa: F401
+from .multiscale import cluster_ranges_multiscale  # noqa: F401
 from .plda import plda_classes
 from .samples import speaker_samples, write_samples  # noqa: F401
 from .score import score_diarization_uem  # noqa: F401
@@ -387,7 +388,8 @@ class Backend(EmbeddingBackend):
         search of cluster.agglomerative_cluster rule 7 and "vbx" the k-means of cluster.kmeans_cluster on the window rows, whose labels come
         back; fewer than two windows: nothing is forced.
         clustering="nmesc": the eigengap spectral clustering of cluster.nmesc_cluster on the window rows, with no threshold: `threshold`,
-        min_cluster_size, loop_prob and plda are not used, and `speakers` bounds the eigengap search itself."""
+        min_cluster_size, loop_prob and plda are not used, and `speakers` bounds the eigengap search itself.  Its multi-scale form - every
+        range at several window lengths, the affinities fused on the shortest one's windows - is backend.cluster_ranges_multiscale(be, ...)."""
         if self.lite:
             raise ValueError("cluster_ranges needs the torch engine: not available with SDK_NO_TORCH=1")
         if clustering not in ("ahc", "vbx", "nmesc"):

@@ -30,7 +30,8 @@ import torch
 from . import dist as sdist
 from ._args import THIN_MAX
 from .diarize_ops import _check_rows, diarize_centroids
-from .ops_cluster import knn_degree, knn_matvec, knn_reverse, knn_rows
+from . import _args
+from .ops_cluster import knn_degree, knn_matvec, knn_reverse, knn_rows, knn_rows_fused
 
 
 @dataclass
@@ -655,6 +656,20 @@ def kmeans_cluster(provider, E, k: int, rows=None, max_iters: int = KMEANS_MAX_I
 #   labels      k* = 1: every label 0.  Otherwise the first k* Ritz vectors of T_p* (same seed and block; the host's eigenvectors for
 #               n <= NMESC_DENSE_ROWS) go through rows_unit and the maximin + Lloyd k-means of spectral_cluster (_kmeans) with
 #               NMESC_KMEANS_PASSES = 20 passes, then canonical_labels.
+# multi-scale (nmesc_multiscale; the method was published with it: Park et al., "Multi-scale speaker diarization with neural affinity score
+#             fusion", ICASSP 2021, as NeMo's clustering diarizer runs it, with FIXED weights here: nothing is learned or tuned).  Every
+#             stretch of speech is embedded at S window lengths, longest first, the shortest being the BASE scale (wav.scale_starts states
+#             the windows and the map).  E_all fp32 [n_all, d] stacks the unit rows of every scale, maps int32 [S, n] names for base window i
+#             its row maps[s][i] of E_all at scale s (the window of that scale whose centre is nearest).
+#   weights     None: 1 / S each.  Given: S numbers, finite, >= 0, not all zero, divided by their sum in float64 on the host; that array
+#               is what the kernel and the restatement both receive.
+#   fused       for base windows i != j: c_s(i, j) = `cosine` above of the rows maps[s][i] and maps[s][j];
+#               f(i, j) = (..((0 + w_0 c_0) + w_1 c_1) .. + w_{S-1} c_{S-1}), float64, every product and every sum rounded once.  A NaN f
+#               ranks as -inf.  Symmetric bit for bit, as c_s is.
+#   lists       as above with f in place of c (sdk_knn_rows_fused, knn_rows_fused_host).  A map entry that is not a row of E_all, or a
+#               non-finite row that a map names, is a ValueError; a non-finite row no map names is not looked at.
+#   the rest    graph, candidates, spectrum, selection and labels are the rule above on those lists, unchanged: nothing behind the lists
+#               reads the rows.  With S = 1 and the identity map the whole result is nmesc_cluster's.
 NMESC_P_MAX = 64
 NMESC_NEIGHBOURS = (2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64)
 NMESC_DENSE_ROWS = 64
@@ -676,6 +691,7 @@ class NmescResult:
     n_iter: int                   # steps of the subspace iteration (0: the host's dense eigensolve)
     retried: bool = False         # the sweep was repeated with shifted CholeskyQR (spectral_cluster's rule)
     host_reads: int = 0           # the waits for the device this call made
+    scales: int = 1               # the scales whose affinities were fused (nmesc_multiscale; 1: the one table of nmesc_cluster)
 
 
 def nmesc_candidates(n: int, neighbours=None) -> tuple:
@@ -734,6 +750,33 @@ def knn_rows_host(E: np.ndarray):
     order = np.argsort(-C, axis=1, kind="stable")                   # ties to the lower j
     order = order[order != np.arange(n)[:, None]].reshape(n, n - 1)[:, :P]
     return order.astype(np.int32), np.take_along_axis(C, order, axis=1)
+
+
+def knn_rows_fused_host(E_all: np.ndarray, maps: np.ndarray, weights):
+    """E_all [n_all, d] fp32 unit rows, maps int [S, n], weights [S] float64 as the kernel receives them -> (idx int32 [n, P], f float64
+    [n, P]): the lists of the fused affinity (sdk_knn_rows_fused), the same operations in the same order."""
+    X = np.asarray(E_all, dtype=np.float32).astype(np.float64)
+    maps = np.asarray(maps, dtype=np.int64)
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    if maps.ndim != 2 or maps.shape[0] != w.size or not 1 <= w.size <= _args.KNN_MAX_SCALES:
+        raise ValueError(f"knn_rows_fused_host: maps must be [S, n] beside S weights, S in 1..{_args.KNN_MAX_SCALES}, got {list(maps.shape)} and {w.size}")
+    out = np.argwhere((maps < 0) | (maps >= X.shape[0]))
+    if out.size:
+        raise ValueError(f"knn_rows_fused_host: base row {int(out[:, 1].min())} has a map entry outside [0, {X.shape[0]}) ({len(out)} such entries in all)")
+    n = maps.shape[1]
+    P = min(NMESC_P_MAX, n - 1)
+    F = np.zeros((n, n))
+    with np.errstate(invalid="ignore"):
+        for s in range(w.size):
+            A = X[maps[s]]
+            C = np.zeros((n, n))
+            for t in range(A.shape[1]):                             # knn_rows_host's chain, on the gathered rows
+                C += A[:, t, None] * A[None, :, t]
+            F = F + w[s] * C                                        # one rounded product, one rounded sum
+    F = np.where(F == F, F, -np.inf)                                # a NaN ranks as -inf
+    order = np.argsort(-F, axis=1, kind="stable")                   # ties to the lower j
+    order = order[order != np.arange(n)[:, None]].reshape(n, n - 1)[:, :P]
+    return order.astype(np.int32), np.take_along_axis(F, order, axis=1)
 
 
 def knn_reverse_host(idx: np.ndarray):
@@ -824,22 +867,39 @@ def _pick_rows(who: str, R: int, rows):
     return rows_h
 
 
-def nmesc_host(E, rows=None, speakers=None, neighbours=None, max_count: int = NMESC_MAX_COUNT) -> NmescResult:
+def _given_lists(who: str, rows, made):
+    """The lists a `lists=` step made, (idx [n, P], values) -> (idx, n); such a step sees all of E, so `rows` has no meaning beside it."""
+    if rows is not None:
+        raise ValueError(f"{who}: rows and lists exclude each other (the lists step picks its own rows)")
+    idx = made[0]
+    n = int(idx.shape[0])
+    if idx.ndim != 2 or n < 2 or n > NMESC_MAX_ROWS or int(idx.shape[1]) != min(NMESC_P_MAX, n - 1):
+        raise ValueError(f"{who}: lists must return idx [n, min({NMESC_P_MAX}, n - 1)] with 2 <= n <= {NMESC_MAX_ROWS}, got {list(idx.shape)}")
+    return idx, n
+
+
+def nmesc_host(E, rows=None, speakers=None, neighbours=None, max_count: int = NMESC_MAX_COUNT, lists=None) -> NmescResult:
     """The whole rule in numpy float64, with the dense eigensolve at every n (so its eigenvalues are exact where nmesc_cluster's device path
-    iterates): E [R, d] fp32 unit rows on the host, the other arguments nmesc_cluster's."""
+    iterates): E [R, d] fp32 unit rows on the host, the other arguments nmesc_cluster's.  lists: as there, called as lists(E) ->
+    (idx [n, P], values) on the host."""
     bounds = parse_speakers(speakers, "nmesc_host")
     E = np.asarray(E, dtype=np.float32)
-    rows_h = _pick_rows("nmesc_host", E.shape[0], rows)
-    X = E[rows_h]
-    n = X.shape[0]
+    if lists is None:
+        rows_h = _pick_rows("nmesc_host", E.shape[0], rows)
+        X = E[rows_h]
+        n = X.shape[0]
+    else:
+        idx, n = _given_lists("nmesc_host", rows, lists(E))
     m, _ = _nmesc_shape(max(n, 1), max_count)
     if n < 2:
         return NmescResult(np.zeros(n, np.int32), n, 0, (), np.zeros((0, m)), np.zeros(0), 0)
-    bad = np.flatnonzero(~np.isfinite(X).all(1))
-    if bad.size:
-        raise ValueError(f"nmesc_host: row {int(bad[0])} has a non-finite value ({bad.size} such rows in all)")
+    if lists is None:
+        bad = np.flatnonzero(~np.isfinite(X).all(1))
+        if bad.size:
+            raise ValueError(f"nmesc_host: row {int(bad[0])} has a non-finite value ({bad.size} such rows in all)")
     ps = nmesc_candidates(n, neighbours)
-    idx, _ = knn_rows_host(X)
+    if lists is None:
+        idx, _ = knn_rows_host(X)
     tops = [_dense_top(idx, p, m) for p in ps]
     taus = np.stack([t[0] for t in tops])
     p_star, k_star, ratios, _ = nmesc_select(ps, taus, bounds, n)
@@ -852,7 +912,7 @@ def nmesc_host(E, rows=None, speakers=None, neighbours=None, max_count: int = NM
 
 
 def nmesc_cluster(provider, E, rows=None, speakers=None, neighbours=None, max_count: int = NMESC_MAX_COUNT, n_iter: int = NMESC_N_ITER,
-                  seed: int = 0) -> NmescResult:
+                  seed: int = 0, lists=None) -> NmescResult:
     """Speaker clusters with neither a threshold nor a count: the rule stated above (E [R, d] fp32 unit rows on the provider's device; rows: the
     ascending row numbers that take part, host integers, None = all).  speakers: parse_speakers' bounds, part of the selection.  neighbours:
     the candidates in place of NMESC_NEIGHBOURS.  max_count: the most speakers looked for (1 .. THIN_MAX - 1).  The lists, their reverse, the
@@ -863,19 +923,26 @@ def nmesc_cluster(provider, E, rows=None, speakers=None, neighbours=None, max_co
     Ritz value i is converged to fp32 where (tau_{b+1} / tau_i)^(2 n_iter) is below 2^-24.  At the default n_iter = 30 that holds for the
     leading values of a clustered input, not for the bulk behind them (tau_{b+1} / tau_m of 0.8 .. 0.99 asks for 35 .. 900 steps): the
     table can then differ from nmesc_host's by a few 1e-3, and where two candidates' r(p) lie within that, p* can differ from
-    nmesc_host's (k* and the labels rest on the leading gap).  n_iter, up to 1000, buys the agreement."""
+    nmesc_host's (k* and the labels rest on the leading gap).  n_iter, up to 1000, buys the agreement.
+    lists: the step that makes the neighbour lists, None for the rule's own (knn_rows on the picked rows).  Given, it is called as
+    lists(provider, E) and returns (idx int32 [n, P] on E's device, values), having made its one status read; n is then the number of
+    lists, `rows` must be None, and everything behind the lists runs unchanged (nmesc_multiscale passes the fused affinity's)."""
     bounds = parse_speakers(speakers, "nmesc_cluster")
     if isinstance(n_iter, (bool, np.bool_)) or not isinstance(n_iter, (int, np.integer)) or not 0 <= n_iter <= 1000:
         raise ValueError(f"nmesc_cluster: n_iter={n_iter!r} (an int, 0 .. 1000)")
-    rows_h = _pick_rows("nmesc_cluster", int(E.shape[0]), rows)
-    n = int(rows_h.size)
+    if lists is None:
+        rows_h = _pick_rows("nmesc_cluster", int(E.shape[0]), rows)
+        n = int(rows_h.size)
+    else:
+        idx, n = _given_lists("nmesc_cluster", rows, lists(provider, E))             # read 1: the status
     m, b = _nmesc_shape(max(n, 1), max_count)
     if n < 2:
         return NmescResult(np.zeros(n, np.int32), n, 0, (), np.zeros((0, m)), np.zeros(0), 0)
     ps = nmesc_candidates(n, neighbours)
     dev = E.device
-    Et = E if rows is None else E.index_select(0, torch.from_numpy(rows_h).to(dev)).contiguous()
-    idx, _ = knn_rows(provider, Et)                                                  # read 1: the status
+    if lists is None:
+        Et = E if rows is None else E.index_select(0, torch.from_numpy(rows_h).to(dev)).contiguous()
+        idx, _ = knn_rows(provider, Et)                                              # read 1: the status
     reads, comm, P = 1, _Comm(single=True), min(NMESC_P_MAX, n - 1)     # every rank that calls holds the whole problem: nothing is reduced
     retried = False
     if n <= NMESC_DENSE_ROWS:
@@ -921,3 +988,55 @@ def nmesc_cluster(provider, E, rows=None, speakers=None, neighbours=None, max_co
         labels = canonical_labels(lab.cpu().numpy()).astype(np.int32)               # the last read
         reads += 1
     return NmescResult(labels, k_star, p_star, ps, taus, ratios, int(n_iter), retried, reads)
+
+
+def _multiscale_args(who: str, n_all: int, maps, weights):
+    """maps on the host -> (maps int32 [S, n], the normalised weights float64 [S]) of the multi-scale rule."""
+    maps_h = np.ascontiguousarray(maps)
+    if maps_h.ndim != 2 or not np.issubdtype(maps_h.dtype, np.integer) or not 1 <= maps_h.shape[0] <= _args.KNN_MAX_SCALES:
+        raise ValueError(f"{who}: maps must be integers [S, n] with S in 1..{_args.KNN_MAX_SCALES}, got {list(maps_h.shape)} {maps_h.dtype}")
+    S, n = maps_h.shape
+    if n > NMESC_MAX_ROWS:
+        raise ValueError(f"{who}: {n} base rows (at most {NMESC_MAX_ROWS})")
+    if n and (maps_h.min() < 0 or maps_h.max() >= n_all):
+        raise ValueError(f"{who}: maps must lie in [0, {n_all}), got {int(maps_h.min())} .. {int(maps_h.max())}")
+    w = np.asarray(_args.knn_weights(who, [1.0] * S if weights is None else weights, S), dtype=np.float64)
+    return maps_h.astype(np.int32), w / w.sum()
+
+
+def nmesc_multiscale_host(E_all, maps, weights=None, speakers=None, neighbours=None, max_count: int = NMESC_MAX_COUNT) -> NmescResult:
+    """nmesc_multiscale in numpy float64 (nmesc_host on the fused affinity's lists): E_all [n_all, d] fp32 on the host."""
+    E_all = np.asarray(E_all, dtype=np.float32)
+    maps_h, w = _multiscale_args("nmesc_multiscale_host", E_all.shape[0], maps, weights)
+    S, n = maps_h.shape
+    if n < 2:
+        res = nmesc_host(E_all[:0], None, speakers, neighbours, max_count)
+        res.labels, res.n_speakers = np.zeros(n, np.int32), n
+    else:
+        bad = np.intersect1d(np.flatnonzero(~np.isfinite(E_all).all(1)), maps_h.reshape(-1))
+        if bad.size:
+            raise ValueError(f"nmesc_multiscale_host: row {int(bad[0])} of E_all, which a map names, has a non-finite value ({bad.size} such rows in all)")
+        res = nmesc_host(E_all, None, speakers, neighbours, max_count, lists=lambda E: knn_rows_fused_host(E, maps_h, w))
+    res.scales = S
+    return res
+
+
+def nmesc_multiscale(provider, E_all, maps, weights=None, speakers=None, neighbours=None, max_count: int = NMESC_MAX_COUNT,
+                     n_iter: int = NMESC_N_ITER, seed: int = 0) -> NmescResult:
+    """The eigengap clustering on the fused affinity of several window lengths: the multi-scale rule stated above NMESC_P_MAX.  E_all
+    [n_all, d] fp32 unit rows of every scale stacked, on the provider's device; maps integers [S, n] (a host array, or an int32 device
+    tensor, which is not read back): base window i's row of E_all at scale s; weights None (equal) or S numbers, normalised here.  The other arguments, the result and its
+    host_reads are nmesc_cluster's (read 1 is the status of sdk_knn_rows_fused); result.scales = S.  Fewer than two base windows: one
+    cluster or none, nothing launched."""
+    on_device = isinstance(maps, torch.Tensor) and maps.is_cuda      # then it is not read back: the kernel's status answers for its range
+    maps_h, w = _multiscale_args("nmesc_multiscale", int(E_all.shape[0]), np.zeros(tuple(maps.shape), np.int32) if on_device else maps, weights)
+    S, n = maps_h.shape
+    if n < 2:
+        res = nmesc_cluster(provider, E_all[:0], None, speakers, neighbours, max_count, n_iter, seed)
+        res.labels, res.n_speakers = np.zeros(n, np.int32), n
+    else:
+        maps_d = maps if on_device else torch.from_numpy(maps_h).to(E_all.device)
+        res = nmesc_cluster(provider, E_all, None, speakers, neighbours, max_count, n_iter, seed,
+                            lists=lambda eng, E: knn_rows_fused(eng, E, maps_d, w))
+    res.scales = S
+    return res

@@ -414,7 +414,7 @@ class ClusterMixin:
 
 
 # ---- the nearest-neighbour graph of cluster.nmesc_cluster (csrc/nmesc.hip): functions of an engine, as diarize_ops.py's wrappers are, so that
-# ops.Engine's public names stay the ones tests/test_ops_layout_cpu.py lists.  Only knn_rows and knn_reverse read a status back.
+# ops.Engine's public names stay the ones tests/test_ops_layout_cpu.py lists.  Only knn_rows, knn_rows_fused and knn_reverse read a status back.
 
 def knn_rows(eng, E: torch.Tensor):
     """E [n, d] fp32 unit rows (device), 2 <= n <= 65536 -> (idx int32 [n, P], cos float64 [n, P]) on the device, P = min(KNN_P_MAX, n - 1):
@@ -430,6 +430,34 @@ def knn_rows(eng, E: torch.Tensor):
     bad, first = (int(v) for v in status.cpu().numpy())
     if bad:
         err = ValueError(f"knn_rows: row {first} has a non-finite value ({bad} such rows in all)")
+        err.idx, err.cos, err.status = idx, cos, (bad, first)
+        raise err
+    return idx, cos
+
+
+def knn_rows_fused(eng, E_all: torch.Tensor, maps: torch.Tensor, weights):
+    """The lists of a multi-scale affinity (cluster.nmesc_multiscale; sdk_knn_rows_fused): E_all [n_all, d] fp32 unit rows of every scale
+    stacked (device), maps int32 [S, n] (device; base row i's row of E_all at scale s), weights S host numbers (finite, >= 0, not all
+    zero; used as given) -> (idx int32 [n, P], cos float64 [n, P]) on the device: row i's P rows j != i of largest
+    f(i, j) = sum over s in order of weights[s] * cosine(E_all[maps[s][i]], E_all[maps[s][j]]), ties to the lower j, and their f.  One host
+    read, the status: a map entry outside [0, n_all) raises ValueError naming its base row (nothing is read through it; the lists are
+    not to be trusted), and so does a row with a non-finite value that a map names (.idx, .cos and .status on the exception; a NaN f
+    ranks as -inf).  A non-finite row no map names is not looked at."""
+    n_all, d = _args.rows("knn_rows_fused", "E_all", E_all)
+    S, n, P = _args.knn_maps("knn_rows_fused", maps)
+    w = np.asarray(_args.knn_weights("knn_rows_fused", weights, S), dtype=np.float64)
+    if n_all < 1 or n_all > _args.KNN_MAX_SCALES * 65536:
+        raise ValueError(f"knn_rows_fused: E_all has {n_all} rows (1 .. {_args.KNN_MAX_SCALES * 65536})")
+    idx = torch.empty((n, P), dtype=torch.int32, device=eng.device)
+    cos = torch.empty((n, P), dtype=torch.float64, device=eng.device)
+    status = torch.empty((4,), dtype=torch.int32, device=eng.device)
+    check(eng.lib.sdk_knn_rows_fused(eng.ctx, E_all.data_ptr(), n_all, d, maps.data_ptr(), w.ctypes.data, S, n, P, idx.data_ptr(), cos.data_ptr(),
+                                     status.data_ptr(), _stream()), "sdk_knn_rows_fused")
+    bad, first, out, at = (int(v) for v in status.cpu().numpy())
+    if out:
+        raise ValueError(f"knn_rows_fused: base row {at} has a map entry outside [0, {n_all}) ({out} such entries in all)")
+    if bad:
+        err = ValueError(f"knn_rows_fused: row {first} of E_all, which a map names, has a non-finite value ({bad} such rows in all)")
         err.idx, err.cos, err.status = idx, cos, (bad, first)
         raise err
     return idx, cos

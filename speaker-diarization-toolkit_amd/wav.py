@@ -200,6 +200,77 @@ def range_starts(n: int, ranges: List[Tuple[float, float]], rate: int = 16000, b
     return {S: np.asarray(st, dtype=np.int32) for S, st in starts_by.items() if st}, windows, dropped
 
 
+# ------------------------------------------------------------------ multi-scale windows (cluster.nmesc_multiscale; backend.cluster_ranges_multiscale)
+# scales      scales_s: 1 .. 8 distinct members of BUCKETS_S, in any order; they are USED in descending order and the shortest is the BASE
+#             scale.  L_s = round(scale * rate) samples, hop H_s = L_s // 2.  Anything else is a ValueError.
+# a range     (start s, end s) -> samples [a, b) exactly as range_starts: a = max(0, round(start * rate)), b = min(n, round(end * rate)).
+# windows     of scale s in a range: starts a + k H_s for as long as start + L_s <= b; if the last of them ends before b, one more window
+#             flush with the end (start = b - L_s).  Nothing is padded and no window leaves its range.  A range shorter than the base
+#             length is `dropped`; a range shorter than L_s has no window at scale s.  Windows are ordered by range, then by start.
+# map         a window's key is the integer 2 start + L_s (twice its centre).  maps[s][i] = the window of scale s whose key is nearest to the
+#             key of base window i, searched over ALL windows of that scale in the call (a short range's base windows map into a neighbouring
+#             range's coarse windows), ties to the lower window index.  The base scale's map is the identity.
+# empty       a scale with no window at all, while the base scale has some, is a ValueError that names the scale (there is nothing to map
+#             onto).  No base window (every range dropped): empty tables and maps [n_scales, 0], no error.
+MAX_SCALES = 8
+
+
+def _scales_desc(scales_s) -> List[float]:
+    try:
+        given = [float(s) for s in scales_s]
+    except (TypeError, ValueError):
+        raise ValueError(f"scale_starts: scales_s={scales_s!r} (1 .. {MAX_SCALES} distinct members of {BUCKETS_S})") from None
+    if not 1 <= len(given) <= MAX_SCALES or len(set(given)) != len(given) or any(s not in BUCKETS_S for s in given):
+        raise ValueError(f"scale_starts: scales_s={scales_s!r} (1 .. {MAX_SCALES} distinct members of {BUCKETS_S})")
+    return sorted(given, reverse=True)
+
+
+def _nearest_keys(keys: np.ndarray, base: np.ndarray) -> np.ndarray:
+    """For every key of `base` the index into `keys` of the nearest key, ties to the lower index (keys in any order, not empty)."""
+    order = np.argsort(keys, kind="stable")                        # equal keys stay in index order: a group's first is its lowest index
+    sk = keys[order]
+    hi = np.searchsorted(sk, base, side="left")                    # the first key >= base: the head of its group of equal keys
+    lo = np.searchsorted(sk, sk[np.maximum(hi - 1, 0)], side="left")       # the head of the group just below
+    has_hi, has_lo = hi < sk.size, hi > 0
+    d_hi = np.where(has_hi, sk[np.minimum(hi, sk.size - 1)] - base, np.iinfo(np.int64).max)
+    d_lo = np.where(has_lo, base - sk[lo], np.iinfo(np.int64).max)
+    i_hi, i_lo = order[np.minimum(hi, sk.size - 1)], order[lo]
+    take_lo = (d_lo < d_hi) | ((d_lo == d_hi) & (i_lo < i_hi))
+    return np.where(take_lo, i_lo, i_hi).astype(np.int32)
+
+
+def scale_starts(n_samples: int, ranges: List[Tuple[float, float]], scales_s, rate: int = 16000):
+    """The multi-scale windows of single-speaker ranges, by the rule stated above -> (starts_by_len {L_s samples: int32 [B_s]}, what
+    Backend.embed_tables takes; windows_by_scale, per scale in descending order of length a list of (range index, start sample, length);
+    maps int32 [n_scales, n_base], row s indexing windows_by_scale[s]; dropped [range index])."""
+    scales = _scales_desc(scales_s)
+    lens = [int(round(s * rate)) for s in scales]
+    wins: List[List[Tuple[int, int, int]]] = [[] for _ in lens]
+    dropped: List[int] = []
+    for ri, (s, e) in enumerate(ranges):
+        a, b = max(0, int(round(s * rate))), min(int(n_samples), int(round(e * rate)))
+        if b - a < lens[-1]:
+            dropped.append(ri)
+            continue
+        for k, L in enumerate(lens):
+            if b - a < L:
+                continue
+            st = list(range(a, b - L + 1, L // 2))
+            if st[-1] + L < b:
+                st.append(b - L)
+            wins[k].extend((ri, x, L) for x in st)
+    n_base = len(wins[-1])
+    if n_base == 0:
+        return {}, wins, np.zeros((len(lens), 0), np.int32), dropped
+    keys = []
+    for k, w in enumerate(wins):
+        if not w:
+            raise ValueError(f"scale_starts: no range holds a window of scale {scales[k]} s ({lens[k]} samples): leave that scale out")
+        keys.append(np.asarray([2 * x + L for _, x, L in w], dtype=np.int64))
+    maps = np.stack([_nearest_keys(kk, keys[-1]) for kk in keys[:-1]] + [np.arange(n_base, dtype=np.int32)])
+    return {L: np.asarray([x for _, x, _ in w], dtype=np.int32) for L, w in zip(lens, wins)}, wins, maps, dropped
+
+
 def cut_ranges(samples: np.ndarray, ranges: List[Tuple[float, float]], rate: int = 16000, buckets_s: Tuple[float, ...] = BUCKETS_S,
                hop_s: float = 1.0):
     """True-length windows for (start, end) ranges that belong to ONE speaker each (sentences, enrollment segments).
